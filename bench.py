@@ -6,16 +6,21 @@ over one batch of synthetic tensors already resident in HBM.  Default workload =
 (C2: batch 4, 16 heads, head dim 128, seq 8192, bf16, non-causal) per GPU; with N GPUs every rank runs
 its own batch shard (no collective on the data path: attention shards over batch) => weak scaling.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c3|c4|c5] [--scaling weak|strong]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c3|c4|c5] [--scaling weak|strong] [--full]
+                  [--dump-outputs DIR]
   N>1: either under torchrun (python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ...
   bench.py --gpus N: RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* come from the env), or plain `python bench.py --gpus N`:
   the parent then starts the N ranks itself (fresh child processes, before it has touched the GPU) and relays rank 0's line.
   --scaling strong (c5 only: BASELINE config 5 / SURVEY.md 8(d)): the global batch of 32 is split 32/N per GPU.
   --dry-run: CPU rehearsal of the launch / rendezvous / timing / reporting logic (gloo, no kernel; "dry_run": true).
+  --full: also measure and check what the headline figure does not need: `cpu_baseline` and `checked` (below).
+  --dump-outputs DIR: after the timed steps, write what the last timed step returned as DIR/<name>.npy (float32; see
+  dump_outputs).  Inputs are seeded, so the same arguments give the same inputs and two builds compare file for file.
 
-Prints ONE JSON line on rank 0 with metric/value/unit (whole-job TFLOP/s), `roofline` (MFMA bound: the
-kernel's algorithmic FLOPs / its HIP-event duration vs the 2.5 PFLOP/s dense bf16 peak) and `cpu_baseline`
-(PyTorch-eager SDPA on the host cores, bounded sample; reported baseline, not a target).
+Prints ONE JSON line on rank 0 with metric/value/unit (whole-job TFLOP/s), ms_per_step (wall time of one timed step) and
+`roofline` (MFMA bound: the kernel's algorithmic FLOPs / its HIP-event duration, taken in the same timed steps, vs the
+2.5 PFLOP/s dense bf16 peak).  With --full it also carries `cpu_baseline` (PyTorch-eager SDPA on the host cores, bounded
+sample; reported baseline, not a target) and `checked` (64 sampled output rows against the oracle); without it both are null.
 FLOP convention = the reference's: 4*b*h*sq*sk*d, halved when causal
 (benchmarks/benchmark_flash_attention.py:27-30, hopper/benchmark_attn.py:62-74); softmax not counted.
 """
@@ -32,6 +37,7 @@ PEAK_BF16_TFLOPS = 2500.0  # dense bf16 MFMA peak, MI355X_MICROARCH.md (256 CU x
 C5_GLOBAL_BATCH = 32       # BASELINE config 5: global batch 32, strong-scaled over 1/2/4/8 GPUs
 C5_DTYPE = "fp8_e4m3 (both products on v_mfma_scale_f32_32x32x64_f8f6f4, unit scales; fp32 accumulate, bf16 out)"
 PEAK_FP8_TFLOPS = 5000.0   # dense fp8 peak of the block-scaled MFMA (2x bf16 per clock), MI355X_MICROARCH.md
+DUMP_CAP_BYTES = 64 * 10**6  # --dump-outputs: at most this much in all
 
 WORKLOADS = {
     # name: (description, batch, heads_q, heads_kv, seqlen, head_dim, causal, varlen lens or None)
@@ -194,6 +200,28 @@ def check_rows(w, q, k, v, extra, result, n_rows=64):
     return True, worst, worst_bound
 
 
+def dump_outputs(outdir, named):
+    """--dump-outputs: each (name, tensor) the last timed step returned, as <outdir>/<name>.npy in float32 (bf16 / fp16
+    outputs convert exactly).  A row is the trailing (heads, head_dim) slab (the trailing dim of a 2-D tensor); an array
+    over its share of DUMP_CAP_BYTES is written as a fixed sample of its rows (torch.randperm seeded with 0, sorted), whose
+    flat row indices go to <name>_rows.npy (float64).  After the timed region, never inside it."""
+    import numpy as np
+    import torch
+    os.makedirs(outdir, exist_ok=True)
+    share = (DUMP_CAP_BYTES - (1 << 20)) // len(named)  # 1 MB kept for the row-index files
+    for name, t in named:
+        t = t.detach()
+        rows = t.flatten(0, t.dim() - 3) if t.dim() >= 3 else t.reshape(-1, t.shape[-1])
+        keep = min(rows.shape[0], max(1, share // (4 * rows[0].numel())))
+        if keep < rows.shape[0]:
+            idx = torch.randperm(rows.shape[0], generator=torch.Generator().manual_seed(0))[:keep].sort().values
+            rows = rows.index_select(0, idx.to(rows.device))
+            np.save(os.path.join(outdir, f"{name}_rows.npy"), idx.numpy().astype(np.float64))
+        else:
+            rows = t
+        np.save(os.path.join(outdir, f"{name}.npy"), rows.float().cpu().numpy())
+
+
 def dry_run(args, w, rank, world, dist, timing_group):
     """CPU rehearsal (tests/test_bench_harness.py): same rendezvous, barriers, max-over-ranks timing and JSON line as the
     real run; the step is a fixed host-side wait instead of the kernel (there is no CPU fallback of the product path)."""
@@ -285,10 +313,17 @@ def main():
     ap.add_argument("--scaling", default="weak", choices=("weak", "strong"),
                     help="strong: c5 only, global batch 32 split over the GPUs (BASELINE config 5)")
     ap.add_argument("--variant", type=int, default=0, help="kernel variant override (0 = library default)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-check", action="store_true", help="skip the post-run comparison of 64 sampled output rows with the oracle")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the CPU baseline and compare 64 sampled output rows with the oracle (off: both null)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-check", action="store_true",
+                    help="with --full: skip the post-run comparison of 64 sampled output rows with the oracle")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step returned to DIR/<name>.npy (rank 0; at most 64 MB, float32)")
     ap.add_argument("--dry-run", action="store_true", help="CPU rehearsal of launch/rendezvous/reporting (gloo, no kernel)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.scaling == "strong" and args.workload != "c5":
         ap.error("--scaling strong is defined for --workload c5 (global batch 32, BASELINE config 5)")
     if args.scaling == "strong" and C5_GLOBAL_BATCH % args.gpus:
@@ -418,6 +453,10 @@ def main():
         elapsed = float(t.item())
     kernel_ms = sorted(a.elapsed_time(b_) for a, b_ in ev)
     avg_kernel_ms = sum(kernel_ms) / len(kernel_ms)
+    if rank == 0 and args.dump_outputs:
+        named = (list(zip(("dq", "dk", "dv", "softmax_d"), result)) if bwd_state is not None else
+                 [("out", result[0] if isinstance(result, (tuple, list)) else result)])
+        dump_outputs(args.dump_outputs, named)
 
     flops = flops_of(w)
     total_flops = flops * world * args.steps
@@ -473,12 +512,12 @@ def main():
                 "algorithmic_bytes_per_launch": algorithmic_bytes(w),
             },
         }
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(w)
         else:
             out["cpu_baseline"] = None
         # outside the timed region: 64 sampled rows of what the last step wrote, against the oracle
-        if args.workload in ("c2", "c3", "c4", "c5") and not args.no_check:
+        if args.full and args.workload in ("c2", "c3", "c4", "c5") and not args.no_check:
             ok, err, bound = check_rows(w, q, k, v, extra, result)
             out["checked"] = bool(ok)
             out["check"] = {"rows": 64, "max_err": round(err, 6), "bound": round(bound, 6),

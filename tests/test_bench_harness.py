@@ -52,6 +52,18 @@ def test_c5_strong_split(n, per_gpu):
     assert d["scaling"] == "strong" and d["n_gpus"] == n and d["config"]["batch_per_gpu"] == per_gpu
 
 
+@pytest.mark.parametrize("extra", [[], ["--full"]])
+def test_steps_sets_the_timed_steps(extra):
+    d = _one_line([sys.executable, "bench.py", "--dry-run", "--steps", "7", "--warmup", "2"] + extra)
+    assert d["steps"] == 7 and d["warmup"] == 2 and d["ms_per_step"] >= 1.0
+
+
+def test_steps_must_be_positive():
+    r = subprocess.run([sys.executable, "bench.py", "--dry-run", "--steps", "0"], cwd=ROOT, env=_clean_env(),
+                       capture_output=True, text=True, timeout=120)
+    assert r.returncode != 0 and "--steps" in r.stderr
+
+
 def test_strong_is_c5_only():
     r = subprocess.run([sys.executable, "bench.py", "--dry-run", "--scaling", "strong"], cwd=ROOT, env=_clean_env(),
                        capture_output=True, text=True, timeout=120)

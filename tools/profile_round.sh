@@ -6,8 +6,8 @@ R=gpurun_out/${1:-r3}_evidence
 mkdir -p $R && cd $GRAFT_REPO_ROOT
 export TMPDIR=/tmp
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | grep -v amdgpu.ids
-timeout -k 10 300 python bench.py > $R/bench_c2.json 2> $R/bench_c2.err
-for w in c3 c4 c5 c2_bwd c3_bwd decode; do timeout -k 10 300 python bench.py --workload $w --no-cpu-baseline > $R/bench_$w.json 2> $R/bench_$w.err; done
+timeout -k 10 300 python bench.py --full > $R/bench_c2.json 2> $R/bench_c2.err
+for w in c3 c4 c5 c2_bwd c3_bwd decode; do timeout -k 10 300 python bench.py --workload $w --full --no-cpu-baseline > $R/bench_$w.json 2> $R/bench_$w.err; done
 echo "bench lines done"
 for w in c2 c3 c4 c5; do
   timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $R/kt_$w -o $w -- python3 bench.py --workload $w --steps 100 --warmup 20 --no-cpu-baseline --no-check > $R/kt_bench_$w.json 2> $R/kt_$w.err
