@@ -1,5 +1,6 @@
-"""Shared host glue: torch tensors -> fa_fwd_params -> fa_fwd on torch's current stream.  Used by the FA2-shaped
-module (flash_attn_2_cuda.py) and the FA3-shaped one (flash_attn_3_cuda.py).  No compute happens here."""
+"""Host glue of the FA3 surface (flash_attn_3_cuda.py, flash_attn_3_ops.py): torch tensors -> fa_fwd_params /
+fa_bwd_params / fa_combine_params -> the C-ABI on torch's current stream.  No compute happens here.  (The FA2 surface's
+host logic is the compiled binding, csrc/torch_binding.cpp.)"""
 import ctypes
 
 import torch
@@ -26,24 +27,18 @@ def aligned(t):
 
 def launch(q, k, v, out, lse, *, varlen, batch, max_seqlen_q, max_seqlen_k, softmax_scale, causal, window_left,
            window_right, softcap, cu_seqlens_q=None, cu_seqlens_k=None, seqused_q=None, seqused_k=None,
-           q_descale=None, k_descale=None, v_descale=None, alibi_slopes=None, kv_batch_idx=None, block_table=None, num_splits=1, leftpad_k=None,
-           p_dropout=0.0, rng_state=None, s_dmask=None, fa3_window=False, s_dmask_block_n=0, attention_chunk=0):
+           q_descale=None, k_descale=None, v_descale=None, fa3_window=False, attention_chunk=0):
     """q/k/v/out: dense (b, s, h, d) or packed (total, h, d) tensors on one GPU, last stride 1, aligned()."""
     lib = _lib.load()
     prm = _lib.new_params()
     prm.q, prm.k, prm.v, prm.o = ptr(q), ptr(k), ptr(v), ptr(out)
     prm.softmax_lse = ptr(lse)
     if varlen:
-        for name, t in (("q", q), ("o", out)) + ((() if block_table is not None else (("k", k), ("v", v)))):
+        for name, t in (("q", q), ("k", k), ("v", v), ("o", out)):
             setattr(prm, f"{name}_batch_stride", 0)
             setattr(prm, f"{name}_row_stride", t.stride(0))
             setattr(prm, f"{name}_head_stride", t.stride(1))
-        if block_table is not None:  # k, v: (num_blocks, page_block_size, h_k, d)
-            for name, t in (("k", k), ("v", v)):
-                setattr(prm, f"{name}_batch_stride", t.stride(0))
-                setattr(prm, f"{name}_row_stride", t.stride(1))
-                setattr(prm, f"{name}_head_stride", t.stride(2))
-        prm.total_q, prm.total_k = q.shape[0], (0 if block_table is not None else k.shape[0])
+        prm.total_q, prm.total_k = q.shape[0], k.shape[0]
         prm.h, prm.h_k, prm.d = q.shape[1], k.shape[-2], q.shape[2]
     else:
         for name, t in (("q", q), ("k", k), ("v", v), ("o", out)):
@@ -65,24 +60,10 @@ def launch(q, k, v, out, lse, *, varlen, batch, max_seqlen_q, max_seqlen_k, soft
         if t is not None:
             setattr(prm, f"{name}_descale_batch_stride", t.stride(0))
             setattr(prm, f"{name}_descale_head_stride", t.stride(1))
-    if alibi_slopes is not None:  # (h) or (b, h) fp32, last stride 1 (checked by the callers)
-        prm.alibi_slopes = ptr(alibi_slopes)
-        prm.alibi_slopes_batch_stride = alibi_slopes.stride(0) if alibi_slopes.dim() == 2 else 0
-    prm.kv_batch_idx = ptr(kv_batch_idx)
-    prm.leftpad_k = ptr(leftpad_k)
-    prm.p_dropout = float(p_dropout)
-    prm.rng_state, prm.s_dmask = ptr(rng_state), ptr(s_dmask)
     prm.flags = _lib.FA_FLAG_FA3_WINDOW if fa3_window else 0
-    if s_dmask is not None and s_dmask_block_n > 0:  # the reference's sign-encoded layout (b, h, rows, cols), input dtype
-        prm.flags |= _lib.FA_FLAG_SDMASK_SIGNED
-        prm.s_dmask_rows, prm.s_dmask_cols, prm.s_dmask_block_n = s_dmask.shape[-2], s_dmask.shape[-1], int(s_dmask_block_n)
     prm.attention_chunk = int(attention_chunk)
     prm.d_v = int(v.shape[-1]) if v.shape[-1] != q.shape[-1] else 0  # FA3 headdim_v (include/fa_fwd.h, ABI v12)
-    prm.num_splits = int(num_splits)  # 1 = off (prefill entry points), 0 = library heuristic (decode), N = forced
-    if block_table is not None:
-        prm.block_table = ptr(block_table)
-        prm.block_table_batch_stride = block_table.stride(0)
-        prm.page_block_size = k.shape[1]
+    prm.num_splits = 1  # no split-KV: the decode calls of the FA3 surface go through the compiled _fwd_kvcache_impl
     workspace = None
     need = lib.fa_fwd_workspace_size(ctypes.byref(prm))
     if need < 0:
@@ -103,7 +84,7 @@ def launch(q, k, v, out, lse, *, varlen, batch, max_seqlen_q, max_seqlen_k, soft
 
 def launch_bwd(dout, q, k, v, out, lse, dq, dk, dv, softmax_d, *, varlen, batch, max_seqlen_q, max_seqlen_k,
                softmax_scale, causal, window_left, window_right, softcap, cu_seqlens_q=None, cu_seqlens_k=None,
-               alibi_slopes=None, deterministic=False, p_dropout=0.0, rng_state=None, fa3_window=False):
+               deterministic=False, fa3_window=False):
     """All tensors dense (b, s, h, d) or packed (total, h, d), last stride 1, aligned(); softmax_d fp32
     (b, h, row_len) / (h, row_len).  Enqueues fa_bwd (include/fa_bwd.h) on torch's current stream."""
     lib = _lib.load()
@@ -135,73 +116,12 @@ def launch_bwd(dout, q, k, v, out, lse, dq, dk, dv, softmax_d, *, varlen, batch,
     prm.softcap = float(softcap)
     prm.is_causal = int(bool(causal))
     prm.window_size_left, prm.window_size_right = int(window_left), int(window_right)
-    if alibi_slopes is not None:
-        prm.alibi_slopes = ptr(alibi_slopes)
-        prm.alibi_slopes_batch_stride = alibi_slopes.stride(0) if alibi_slopes.dim() == 2 else 0
     prm.flags = _lib.FA_FLAG_FA3_WINDOW if fa3_window else 0
     prm.deterministic = int(bool(deterministic))
-    prm.p_dropout = float(p_dropout)
-    prm.rng_state = ptr(rng_state)
     stream = torch.cuda.current_stream(q.device).cuda_stream
     st = lib.fa_bwd(ctypes.byref(prm), ctypes.c_void_p(stream))
     if st != 0:
         raise RuntimeError(f"fa_bwd failed ({st}): {_lib.strerror(st)}")
-
-
-def rotary_apply(src, dst, cos, sin, seqlen_offsets, interleaved, per_row_positions):
-    """dst[b, i] = rotary(src[b, i]) at position seqlen_offsets[b] + (i if per_row_positions else 0); (b, s, h, d)."""
-    lib = _lib.load()
-    prm = _lib.FaRotaryParams()
-    prm.abi_version = _lib.FA_ABI_VERSION
-    prm.struct_size = ctypes.sizeof(_lib.FaRotaryParams)
-    prm.src, prm.dst = ptr(src), ptr(dst)
-    for name, t in (("src", src), ("dst", dst)):
-        setattr(prm, f"{name}_batch_stride", t.stride(0))
-        setattr(prm, f"{name}_row_stride", t.stride(1))
-        setattr(prm, f"{name}_head_stride", t.stride(2))
-    prm.b, prm.s, prm.h, prm.d = src.shape
-    prm.dtype = _DT[src.dtype]
-    prm.rotary_dim = cos.shape[1] * 2
-    prm.rotary_interleaved = int(bool(interleaved))
-    prm.per_row_positions = int(bool(per_row_positions))
-    prm.rotary_cos, prm.rotary_sin, prm.seqlen_offsets = ptr(cos), ptr(sin), ptr(seqlen_offsets)
-    stream = torch.cuda.current_stream(src.device).cuda_stream
-    st = lib.fa_rotary_apply(ctypes.byref(prm), ctypes.c_void_p(stream))
-    if st != 0:
-        raise RuntimeError(f"fa_rotary_apply failed ({st}): {_lib.strerror(st)}")
-
-
-def kvcache_append(k_new, v_new, k_cache, v_cache, cache_seqlens, cache_batch_idx=None, block_table=None,
-                   rotary_cos=None, rotary_sin=None, rotary_interleaved=False, rotary_seqlens=None):
-    """(b, s_new, h_k, d) rows appended in place to (b_cache, s_cache, h_k, d) caches at cache_seqlens (int32, (b,))."""
-    lib = _lib.load()
-    prm = _lib.FaKvcacheAppendParams()
-    prm.abi_version = _lib.FA_ABI_VERSION
-    prm.struct_size = ctypes.sizeof(_lib.FaKvcacheAppendParams)
-    prm.k_new, prm.v_new, prm.k_cache, prm.v_cache = ptr(k_new), ptr(v_new), ptr(k_cache), ptr(v_cache)
-    for name, t in (("knew", k_new), ("vnew", v_new), ("kcache", k_cache), ("vcache", v_cache)):
-        setattr(prm, f"{name}_batch_stride", t.stride(0))
-        setattr(prm, f"{name}_row_stride", t.stride(1))
-        setattr(prm, f"{name}_head_stride", t.stride(2))
-    prm.b, prm.seqlen_new, prm.h_k, prm.d = k_new.shape
-    prm.seqlen_cache = k_cache.shape[1]
-    if block_table is not None:
-        prm.block_table = ptr(block_table)
-        prm.block_table_batch_stride = block_table.stride(0)
-        prm.page_block_size = k_cache.shape[1]
-        prm.seqlen_cache = block_table.shape[1] * k_cache.shape[1]
-    prm.cache_seqlens = ptr(cache_seqlens)
-    prm.cache_batch_idx = ptr(cache_batch_idx)
-    prm.dtype = _DT[k_new.dtype]
-    if rotary_cos is not None:
-        prm.rotary_cos, prm.rotary_sin = ptr(rotary_cos), ptr(rotary_sin)
-        prm.rotary_dim = rotary_cos.shape[1] * 2
-        prm.rotary_interleaved = int(bool(rotary_interleaved))
-        prm.rotary_seqlens = ptr(rotary_seqlens)   # FA3 seqlens_rotary (None: the cache fill levels)
-    stream = torch.cuda.current_stream(k_new.device).cuda_stream
-    st = lib.fa_kvcache_append(ctypes.byref(prm), ctypes.c_void_p(stream))
-    if st != 0:
-        raise RuntimeError(f"fa_kvcache_append failed ({st}): {_lib.strerror(st)}")
 
 
 _COMBINE_DT = {torch.float16: 0, torch.bfloat16: 1, torch.float32: 3}

@@ -5,7 +5,7 @@
 // (:767-971), mha_varlen_bwd (:973-1200) and mha_fwd_kvcache (:1202-1476) -- TORCH_CHECKs with the reference's texts, output /
 // LSE / softmax_d allocation, the params struct -- and enqueueing the gfx950 kernels on torch's current stream.  Host code
 // only: built by plain g++ against the torch headers (no hipify, no device code here), linked to libfa_fwd_gfx950.so.
-// The Python module flash_attn_2_cuda.py states the same logic and stays as the fallback binding (ctypes).
+// This is the only host path of the FA2 entry points: flash_attn_2_cuda.py re-exports these functions as they are.
 #include <torch/extension.h>
 #include <ATen/hip/impl/HIPGuardImplMasqueradingAsCUDA.h>
 #include <ATen/hip/impl/HIPStreamMasqueradingAsCUDA.h>

@@ -5,8 +5,7 @@ callable `hopper/flash_attn_interface.py:66` invokes — 34 positional arguments
 Built: fp16 / bf16 / fp8 e4m3 inputs (fp8 -> bf16 output, :859), per-(batch, kv head) q/k/v descales (:1115-1146),
 dense and varlen (`cu_seqlens_*`, `seqused_*`), causal / sliding window / softcap, GQA.
 KV-cache arguments (dense q, 16-bit): k_new/v_new (in-place append at seqused_k), page_table (any page size),
-kv_batch_idx, leftpad_k, rotary_cos/sin (+ interleaved), num_splits -- served by the same routines as the FA2
-`fwd_kvcache` surface (flash_attn_2_cuda.fwd_kvcache).
+kv_batch_idx, leftpad_k, rotary_cos/sin (+ interleaved), num_splits -- served by `_fwd_kvcache_impl`.
 Accepted and rejected by message, like the reference does for compiled-out features (:1148-1165): qv,
 attention_chunk, cu_seqlens_k_new, seqlens_rotary, KV-cache arguments together with cu_seqlens_q or fp8.
 `scheduler_metadata`, `pack_gqa`, `sm_margin` are performance hints and do not change results: ignored.

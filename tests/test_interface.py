@@ -1,6 +1,7 @@
 """CPU tests of the Python host layer: it mirrors the reference's operator interface (names, argument order,
 defaults) and it never computes attention on a fallback path."""
 import inspect
+import os
 
 import pytest
 import torch
@@ -30,9 +31,10 @@ def test_flash_attn_varlen_func_signature():
         ("alibi_slopes", None), ("deterministic", False), ("return_attn_probs", False), ("block_table", None)]
 
 
-def test_extension_module_surface():
+def test_extension_module_is_the_compiled_binding():
     """The five entry points flash_attn_interface.py looks up on flash_attn_2_cuda (:91,:168,:269,:369,:1594),
-    with the positional arity of the pybind signatures (csrc/flash_attn/flash_api.cpp:350-363, 514-535)."""
+    with the positional arity of the pybind signatures (csrc/flash_attn/flash_api.cpp:350-363, 514-535), are the
+    compiled binding's functions themselves."""
     import re
 
     def arity(fn):  # pybind functions carry their signature in the first docstring line
@@ -41,15 +43,15 @@ def test_extension_module_surface():
         except ValueError:
             return len(re.findall(r"\barg\d+:", fn.__doc__.splitlines()[0]))
     want = {"fwd": 13, "varlen_fwd": 21, "bwd": 19, "varlen_bwd": 24, "fwd_kvcache": 20}  # :350-363, 514-535, 767-786, 973-997, 1202-1222
+    from flash_attention_annotated_amd import flash_attn_2_cuda_C as compiled
+    import flash_attn_2_cuda as top_level_alias  # the name the reference imports
     for name, n in want.items():
         assert callable(getattr(flash_attn_2_cuda, name))
         assert arity(getattr(flash_attn_2_cuda, name)) == n, name
-        assert arity(flash_attn_2_cuda._py_entry_points[name]) == n, name   # the ctypes fallback states the same lists
-    import flash_attn_2_cuda as top_level_alias  # the name the reference imports
-    assert top_level_alias.fwd is flash_attn_2_cuda.fwd
-    if flash_attn_2_cuda.compiled is not None:  # the reference's flash_attn_gpu is then the compiled module's functions
-        assert top_level_alias.fwd is flash_attn_2_cuda.compiled.fwd
-        assert type(top_level_alias.fwd).__name__ == "builtin_function_or_method"
+        # the reference's flash_attn_gpu is the compiled module's functions, with nothing in between
+        assert getattr(top_level_alias, name) is getattr(flash_attn_2_cuda, name) is getattr(compiled, name), name
+        assert type(getattr(top_level_alias, name)).__name__ == "builtin_function_or_method", name
+    assert flash_attn_2_cuda._fwd_kvcache_impl is compiled._fwd_kvcache_impl
     assert [n for n, _ in _params(fa.flash_attn_with_kvcache)] == [
         "q", "k_cache", "v_cache", "k", "v", "rotary_cos", "rotary_sin", "cache_seqlens", "cache_batch_idx",
         "cache_leftpad", "block_table", "softmax_scale", "causal", "window_size", "softcap", "rotary_interleaved",
@@ -63,6 +65,35 @@ def test_no_cpu_fallback():
         fa.flash_attn_func(q, q, q)
     with pytest.raises(RuntimeError, match="only support fp16 and bf16"):
         fa.flash_attn_func(q.float(), q.float(), q.float())
+    # each entry point of the extension module, called directly as the reference's flash_attn_gpu does
+    lse = torch.zeros(1, 2, 16)
+    qv, lse_v, cu = q[0], torch.zeros(2, 16), torch.tensor([0, 16], dtype=torch.int32)
+    cache_seqlens = torch.zeros(1, dtype=torch.int32)
+    calls = (
+        lambda: flash_attn_2_cuda.fwd(q, q, q, None, None, 0.0, 0.125, False, -1, -1, 0.0, False, None),
+        lambda: flash_attn_2_cuda.varlen_fwd(qv, qv, qv, None, cu, cu, None, None, None, None, 16, 16, 0.0, 0.125, False,
+                                             False, -1, -1, 0.0, False, None),
+        lambda: flash_attn_2_cuda.bwd(q, q, q, q, q, lse, None, None, None, None, 0.0, 0.125, False, -1, -1, 0.0, False, None,
+                                      None),
+        lambda: flash_attn_2_cuda.varlen_bwd(qv, qv, qv, qv, qv, lse_v, None, None, None, cu, cu, None, 16, 16, 0.0, 0.125,
+                                             False, False, -1, -1, 0.0, False, None, None),
+        lambda: flash_attn_2_cuda.fwd_kvcache(q, q, q, None, None, cache_seqlens, None, None, None, None, None, None, None,
+                                              0.125, False, -1, -1, 0.0, False, 0),
+    )
+    for call in calls:
+        with pytest.raises(RuntimeError, match="must be on CUDA"):
+            call()
+
+
+def test_package_import_does_not_load_the_binding():
+    """The compiled binding is resolved on first use, so the package imports before build() has run (test collection
+    imports it before conftest.py builds)."""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    code = (f"import sys; sys.path.insert(0, {root!r}); import flash_attention_annotated_amd; "
+            "assert 'flash_attention_annotated_amd.flash_attn_2_cuda_C' not in sys.modules")
+    subprocess.run([sys.executable, "-c", code], check=True)
 
 
 def test_unpad_pad_roundtrip():
