@@ -27,7 +27,7 @@ def aligned(t):
 
 def launch(q, k, v, out, lse, *, varlen, batch, max_seqlen_q, max_seqlen_k, softmax_scale, causal, window_left,
            window_right, softcap, cu_seqlens_q=None, cu_seqlens_k=None, seqused_q=None, seqused_k=None,
-           q_descale=None, k_descale=None, v_descale=None, fa3_window=False, attention_chunk=0):
+           q_descale=None, k_descale=None, v_descale=None, fa3_window=False, attention_chunk=0, qv=None):
     """q/k/v/out: dense (b, s, h, d) or packed (total, h, d) tensors on one GPU, last stride 1, aligned()."""
     lib = _lib.load()
     prm = _lib.new_params()
@@ -63,6 +63,10 @@ def launch(q, k, v, out, lse, *, varlen, batch, max_seqlen_q, max_seqlen_k, soft
     prm.flags = _lib.FA_FLAG_FA3_WINDOW if fa3_window else 0
     prm.attention_chunk = int(attention_chunk)
     prm.d_v = int(v.shape[-1]) if v.shape[-1] != q.shape[-1] else 0  # FA3 headdim_v (include/fa_fwd.h, ABI v12)
+    if qv is not None:  # FA3 qv (include/fa_fwd.h, ABI v13): laid out like q, V's head dim
+        prm.qv = ptr(qv)
+        prm.qv_batch_stride = 0 if varlen else qv.stride(0)
+        prm.qv_row_stride, prm.qv_head_stride = qv.stride(-3), qv.stride(-2)
     prm.num_splits = 1  # no split-KV: the decode calls of the FA3 surface go through the compiled _fwd_kvcache_impl
     workspace = None
     need = lib.fa_fwd_workspace_size(ctypes.byref(prm))

@@ -14,7 +14,7 @@ LIB_PATH = os.path.join(_HERE, LIB_NAME)
 CSRC = os.path.join(_HERE, "csrc")
 INCLUDE = os.path.join(os.path.dirname(_HERE), "include")
 
-FA_ABI_VERSION = 12
+FA_ABI_VERSION = 13
 FA_FLAG_FA3_WINDOW = 1
 FA_FLAG_SDMASK_SIGNED = 2
 FA_DTYPE_FP16, FA_DTYPE_BF16, FA_DTYPE_FP8_E4M3 = 0, 1, 2
@@ -114,6 +114,10 @@ class FaFwdParams(ctypes.Structure):
         ("attention_chunk", ctypes.c_int32),
         ("d_v", ctypes.c_int32),
         ("reserved_v12", ctypes.c_int32),
+        ("qv", ctypes.c_void_p),
+        ("qv_batch_stride", ctypes.c_int64),
+        ("qv_row_stride", ctypes.c_int64),
+        ("qv_head_stride", ctypes.c_int64),
     ]
 
 
@@ -145,6 +149,7 @@ class FaKvcacheAppendParams(ctypes.Structure):
            ("page_block_size", ctypes.c_int32), ("dtype", ctypes.c_int32)]
         + [("rotary_cos", ctypes.c_void_p), ("rotary_sin", ctypes.c_void_p),
            ("rotary_dim", ctypes.c_int32), ("rotary_interleaved", ctypes.c_int32), ("rotary_seqlens", ctypes.c_void_p)]
+        + [("d_v", ctypes.c_int32), ("reserved_v13", ctypes.c_int32)]
     )
 
 

@@ -8,6 +8,7 @@
 #include "fa_fwd_kernel_w64.h"
 #include "fa_fwd_kernel_fp8.h"
 #include "fa_fwd_kernel_d256.h"
+#include "fa_fwd_kernel_qv.h"
 
 #include <algorithm>
 #include <atomic>
@@ -153,7 +154,8 @@ __global__ void rotary_kernel(const fa_rotary_params p) {
 // One thread = one slot of two 16-byte chunks of K and the same chunks of V.  HBM-bound elementwise pass.
 template <typename T>
 __global__ void kvcache_append_kernel(const fa_kvcache_append_params p) {
-    const int slots = (p.d / 8 + 1) / 2, chunks = p.d >> 3;
+    const int dv = p.d_v > 0 ? p.d_v : p.d;  // (ABI v13: V rows of their own width; slots past K's chunks copy V only)
+    const int slots = max((p.d / 8 + 1) / 2, (dv / 8 + 1) / 2), chunks = dv >> 3;
     const int64_t total = (int64_t)p.b * p.seqlen_new * p.h_k * slots;
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
         const int slot = (int)(i % slots);
@@ -295,6 +297,14 @@ int block_m_of(int variant, int d);
 inline bool own_dv(const fa_fwd_params *p) { return p->d_v > 0 && p->d_v != p->d; }
 inline bool generic_only(const fa_fwd_params *p) { return p->attention_chunk > 0 || own_dv(p); }
 inline int wide_dim(const fa_fwd_params *p) { return own_dv(p) ? std::max(p->d, std::min(p->d_v, 256)) : p->d; }  // what the LDS tile has to hold
+// ABI v13: the qv kernel (fa_fwd_kernel_qv.h) serves q/k head dims <= 64 beside a V head dim in [256, 512] -- every call with
+// qv, and without qv the paged / split-KV calls of that shape (the 256-column launches below cannot split or page).  The dense
+// and varlen calls without qv keep the 256-column launches.
+inline int dv_of(const fa_fwd_params *p) { return p->d_v > 0 ? p->d_v : p->d; }
+inline bool qv_shape(const fa_fwd_params *p) {
+    return p->dtype != FA_DTYPE_FP8_E4M3 && p->d <= 64 && dv_of(p) >= 256 && dv_of(p) <= 512;
+}
+inline bool qv_route(const fa_fwd_params *p) { return p->qv || (qv_shape(p) && (p->block_table || p->num_splits > 1)); }
 
 bool fp8_native(const fa_fwd_params *p) {
     if (p->dtype != FA_DTYPE_FP8_E4M3 || p->d != 128 || generic_only(p)) return false;
@@ -393,6 +403,31 @@ SplitPlan split_plan(const fa_fwd_params *p, int variant) {
     sp.total = sp.o_bytes + sp.lse_bytes;
     return sp;
 }
+
+// Split plan of the qv kernel: dense problems only, like split_plan.  Heuristic (num_splits == 0): one workgroup fills a CU
+// (its LDS), so the (batch, kv head, row block) groups are multiplied up to ~2 workgroups per CU of 256, with at least 4 key
+// blocks per split.  Partials: O (splits, b, seqlen_q, h, d_v), LSE (splits, b, h, seqlen_q), fp32.
+SplitPlan split_plan_qv(const fa_fwd_params *p) {
+    SplitPlan sp{1, 0, 0, 0};
+    if (p->cu_seqlens_q || p->seqlen_q <= 0 || p->seqlen_k <= 0) return sp;
+    int n = p->num_splits;
+    const int n_blocks = (p->seqlen_k + 63) / 64;
+    if (n == 0) {
+        const int64_t groups = (int64_t)p->b * p->h_k * (((int64_t)p->seqlen_q * (p->h / p->h_k) + 31) / 32);
+        n = 1;
+        if (groups < 512 && n_blocks >= 8) n = (int)std::max<int64_t>(1, std::min<int64_t>((512 + groups - 1) / groups, n_blocks / 4));
+        n = std::min(n, 64);
+    }
+    n = std::max(1, std::min(n, std::min(n_blocks, 128)));
+    if (n <= 1) return sp;
+    sp.splits = n;
+    const int64_t rows = (int64_t)p->b * p->seqlen_q;
+    sp.o_bytes = (n * rows * p->h * dv_of(p) * 4 + 255) & ~int64_t(255);
+    sp.lse_bytes = (n * rows * p->h * 4 + 255) & ~int64_t(255);
+    sp.total = sp.o_bytes + sp.lse_bytes;
+    return sp;
+}
+inline SplitPlan plan_of(const fa_fwd_params *p, int variant) { return qv_route(p) ? split_plan_qv(p) : split_plan(p, variant); }
 
 // ---- split-KV merge: out = sum_s w_s O_s / sum_s w_s, w_s = exp(lse_s - max lse); lse = max + log sum w.  One thread =
 // one 16-byte chunk of one (batch, row, head); splits with LSE = +inf (no key in their range) carry no weight.
@@ -677,6 +712,42 @@ int dispatch_hdim(const fa::KParams &kp, bool softcap, int variant, hipStream_t 
 
 int block_m_of(int variant, int d) { return (variant == 2 || head_dim_tile(d) == 256) ? 128 : 256; }
 
+template <typename T, int DVT, bool SOFTCAP>
+int launch_qv_form(const fa::QvParams &qa, int64_t grid, hipStream_t stream) {
+    constexpr int smem = fa::smem_bytes_qv<DVT>();
+    auto kernel = fa::fwd_kernel_qv<T, DVT, SOFTCAP>;
+    static std::atomic<uint64_t> attr_set{0};
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    const uint64_t bit = uint64_t(1) << (dev & 63);
+    if (smem > 65536 && !(attr_set.load(std::memory_order_acquire) & bit)) {
+        if (hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, smem) != hipSuccess) {
+            (void)hipGetLastError();
+            return FA_ERR_LAUNCH;
+        }
+        attr_set.fetch_or(bit, std::memory_order_release);
+    }
+    hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(fa::QV_NWAVES * 64), smem, stream, qa);
+    return hipGetLastError() == hipSuccess ? FA_OK : FA_ERR_LAUNCH;
+}
+// the qv kernel (fa_fwd_kernel_qv.h): V tile 256 (d_v = 256) or 512 columns (d_v in (256, 512])
+template <typename T>
+int launch_qv(const fa_fwd_params *p, const fa::KParams &kp, bool softcap, hipStream_t stream) {
+    fa::QvParams qa{};
+    qa.p = kp;
+    qa.qv = p->qv;
+    qa.qv_batch_stride = p->qv_batch_stride; qa.qv_row_stride = p->qv_row_stride; qa.qv_head_stride = p->qv_head_stride;
+    const int64_t pblocks = ((int64_t)p->seqlen_q * (p->h / p->h_k) + 31) / 32;
+    const int64_t groups = (int64_t)p->b * p->h_k * (kp.num_splits > 1 ? kp.num_splits : 1);
+    const int64_t grid = (groups + 7) / 8 * 8 * pblocks;
+    if (pblocks == 0 || groups == 0) return FA_OK;
+    if (grid > 0x7fffffff) return FA_ERR_BAD_SHAPE;
+    qa.num_pblocks = (int32_t)pblocks;
+    qa.num_groups = (int32_t)groups;
+    if (kp.dv <= 256) return softcap ? launch_qv_form<T, 256, true>(qa, grid, stream) : launch_qv_form<T, 256, false>(qa, grid, stream);
+    return softcap ? launch_qv_form<T, 512, true>(qa, grid, stream) : launch_qv_form<T, 512, false>(qa, grid, stream);
+}
+
 }  // namespace
 
 extern "C" {
@@ -745,6 +816,7 @@ int fa_kvcache_append(const fa_kvcache_append_params *p, void *stream_) {
     if (p->abi_version != FA_ABI_VERSION || p->struct_size != sizeof(fa_kvcache_append_params)) return FA_ERR_BAD_ABI;
     if (p->b <= 0 || p->h_k <= 0 || p->seqlen_new < 0 || p->seqlen_cache < 0) return FA_ERR_BAD_SHAPE;
     if (p->d <= 0 || p->d > 256 || p->d % 8 != 0) return FA_ERR_BAD_HEAD_DIM;
+    if (p->d_v < 0 || p->d_v > 512 || p->d_v % 8 != 0) return FA_ERR_BAD_HEAD_DIM;  // 0 = d
     if (p->seqlen_new == 0) return FA_OK;
     if (!p->k_new || !p->v_new || !p->k_cache || !p->v_cache || !p->cache_seqlens) return FA_ERR_NULL_POINTER;
     if (p->block_table && (p->page_block_size <= 0 || p->cache_batch_idx)) return FA_ERR_BAD_SHAPE;
@@ -763,7 +835,8 @@ int fa_kvcache_append(const fa_kvcache_append_params *p, void *stream_) {
     const void *ptrs[] = {p->k_new, p->v_new, p->k_cache, p->v_cache};
     for (const void *ptr : ptrs)
         if (reinterpret_cast<uintptr_t>(ptr) % 16 != 0) return FA_ERR_BAD_STRIDE;
-    const int64_t total = (int64_t)p->b * p->seqlen_new * p->h_k * ((p->d / 8 + 1) / 2);
+    const int dv = p->d_v > 0 ? p->d_v : p->d;
+    const int64_t total = (int64_t)p->b * p->seqlen_new * p->h_k * std::max((p->d / 8 + 1) / 2, (dv / 8 + 1) / 2);
     const int blocks = (int)std::min<int64_t>((total + 255) / 256, 256 * 8);
     if (p->rotary_cos && p->dtype == FA_DTYPE_FP16)
         hipLaunchKernelGGL(kvcache_append_kernel<_Float16>, dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(stream_), *p);
@@ -827,7 +900,7 @@ int64_t fa_fwd_workspace_size(const fa_fwd_params *p) {
     if (p->b <= 0 || p->h <= 0 || p->h_k <= 0 || p->d <= 0 || p->seqlen_q < 0 || p->seqlen_k < 0) return FA_ERR_BAD_SHAPE;
     if (p->cu_seqlens_q && (p->total_q < 0 || p->total_k < 0)) return FA_ERR_BAD_SHAPE;
     if (p->dtype == FA_DTYPE_FP8_E4M3) return fp8_native(p) ? 0 : fp8_plan(p).total;
-    return split_plan(p, effective_variant(p)).total;
+    return plan_of(p, effective_variant(p)).total;
 }
 
 int fa_fwd_validate(const fa_fwd_params *p) {
@@ -840,7 +913,14 @@ int fa_fwd_validate(const fa_fwd_params *p) {
     if (fp8 && p->d % 16 != 0) return FA_ERR_BAD_HEAD_DIM;  // hopper/flash_api.cpp:854-856
     if (p->attention_chunk < 0) return FA_ERR_BAD_SHAPE;
     if (p->d_v < 0 || p->d_v > 512 || p->d_v % 8 != 0) return FA_ERR_BAD_HEAD_DIM;  // 0 = d
-    if (own_dv(p) && (fp8 || p->block_table || p->num_splits > 1)) return FA_ERR_UNSUPPORTED;
+    if (p->qv) {  // ABI v13 (hopper/flash_api.cpp:1028-1048): d <= 64, 256 <= d_v <= 512, 16-bit; no ALiBi / dropout in FA3
+        if (fp8 || !qv_shape(p) || p->alibi_slopes || p->p_dropout > 0.f) return FA_ERR_UNSUPPORTED;
+        if (p->qv_row_stride % 8 != 0 || p->qv_head_stride % 8 != 0 || (!p->cu_seqlens_q && p->qv_batch_stride % 8 != 0) ||
+            reinterpret_cast<uintptr_t>(p->qv) % 16 != 0)
+            return FA_ERR_BAD_STRIDE;
+    }
+    if (own_dv(p) && (fp8 || p->block_table || p->num_splits > 1) && !qv_route(p)) return FA_ERR_UNSUPPORTED;
+    if (qv_route(p) && p->alibi_slopes) return FA_ERR_UNSUPPORTED;
     if (generic_only(p) && p->p_dropout > 0.f) return FA_ERR_UNSUPPORTED;  // (no dropout on the FA3 surface)
     if (p->attention_chunk > 0 && p->s_dmask) return FA_ERR_UNSUPPORTED;  // (the S_dmask pass knows windows only)
     if (p->h % p->h_k != 0) return FA_ERR_BAD_HEADS;
@@ -875,7 +955,7 @@ int fa_fwd_validate(const fa_fwd_params *p) {
     }
     if (p->num_splits < 0) return FA_ERR_BAD_SHAPE;
     if (!fp8 && !empty && p->seqlen_k > 0) {
-        const SplitPlan sp = split_plan(p, effective_variant(p));
+        const SplitPlan sp = plan_of(p, effective_variant(p));
         if (sp.splits > 1 && (!p->workspace || reinterpret_cast<uintptr_t>(p->workspace) % 256 != 0 ||
                               (int64_t)p->workspace_bytes < sp.total))
             return FA_ERR_WORKSPACE;
@@ -911,7 +991,8 @@ int fa_fwd(const fa_fwd_params *p, void *stream_) {
     if (st != FA_OK) return st;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
 
-    if (p->d_v > 256) {
+    const bool qv_kernel = qv_route(p);
+    if (p->d_v > 256 && !qv_kernel) {
         // V head dims above the widest tile (hopper/flash_api.cpp:783-792 allows up to 512 beside q/k <= 64): one launch per 256
         // columns of V and O -- the scores are formed again for each (d <= 64: a small part of the work), the LSE is written
         // by every launch with the same value.  Strides are untouched: the launches differ in the V / O column offset only.
@@ -1018,14 +1099,14 @@ int fa_fwd(const fa_fwd_params *p, void *stream_) {
         kp.num_cus = n;
     }
     // split-KV: `splits` copies of the grid; partial results go to the workspace and are merged below
-    const SplitPlan sp = nothing ? SplitPlan{1, 0, 0, 0} : split_plan(p, variant == 4 ? 0 : variant);
+    const SplitPlan sp = nothing ? SplitPlan{1, 0, 0, 0} : plan_of(p, variant == 4 ? 0 : variant);
     kp.num_splits = sp.splits;
     if (sp.splits > 1) {
         if (grid * sp.splits > 0x7fffffff) return FA_ERR_BAD_SHAPE;
         char *ws = static_cast<char *>(p->workspace);
         kp.o = ws;
         kp.lse = reinterpret_cast<float *>(ws + sp.o_bytes);
-        kp.o_row_stride = (int64_t)p->h * p->d; kp.o_head_stride = p->d; kp.o_batch_stride = kp.o_row_stride * p->seqlen_q;
+        kp.o_row_stride = (int64_t)p->h * dv_of(p); kp.o_head_stride = dv_of(p); kp.o_batch_stride = kp.o_row_stride * p->seqlen_q;
         kp.o_split_stride = kp.o_batch_stride * p->b;
         kp.lse_split_stride = (int64_t)p->b * p->h * p->seqlen_q;
     }
@@ -1094,8 +1175,9 @@ int fa_fwd(const fa_fwd_params *p, void *stream_) {
         return hipGetLastError() == hipSuccess ? FA_OK : FA_ERR_LAUNCH;
     }
     const bool bf16 = p->dtype == FA_DTYPE_BF16 || fp8;  // fp8: out is bf16
-    const int st_main = bf16 ? dispatch_hdim<__bf16>(kp, softcap, variant, stream)
-                             : dispatch_hdim<_Float16>(kp, softcap, variant, stream);
+    const int st_main = qv_kernel ? (bf16 ? launch_qv<__bf16>(p, kp, softcap, stream) : launch_qv<_Float16>(p, kp, softcap, stream))
+                        : bf16    ? dispatch_hdim<__bf16>(kp, softcap, variant, stream)
+                                  : dispatch_hdim<_Float16>(kp, softcap, variant, stream);
     if (st_main == FA_OK && sdmask_signed && !nothing) {
         const int nrb = (p->seqlen_q + 7) / 8;
         const int64_t blocks = (int64_t)nrb * p->h * p->b;
@@ -1119,16 +1201,17 @@ int fa_fwd(const fa_fwd_params *p, void *stream_) {
     }
     if (st_main != FA_OK || sp.splits <= 1) return st_main;
     // merge the partial results into the caller's out / softmax_lse
-    const int64_t total = (int64_t)p->b * p->seqlen_q * p->h * (p->d / 8);
+    const int dw = dv_of(p);  // (= d on every path but the qv kernel's: the others never split with a V head dim of its own)
+    const int64_t total = (int64_t)p->b * p->seqlen_q * p->h * (dw / 8);
     const int blocks = (int)std::min<int64_t>((total + 255) / 256, 256 * 8);
     if (bf16)
         hipLaunchKernelGGL(combine_splits_kernel<__bf16>, dim3(blocks), dim3(256), 0, stream, static_cast<const float *>(kp.o),
-                           kp.lse, static_cast<__bf16 *>(p->o), p->softmax_lse, sp.splits, p->b, p->seqlen_q, p->h, p->d,
+                           kp.lse, static_cast<__bf16 *>(p->o), p->softmax_lse, sp.splits, p->b, p->seqlen_q, p->h, dw,
                            p->o_batch_stride, p->o_row_stride, p->o_head_stride);
     else
         hipLaunchKernelGGL(combine_splits_kernel<_Float16>, dim3(blocks), dim3(256), 0, stream,
                            static_cast<const float *>(kp.o), kp.lse, static_cast<_Float16 *>(p->o), p->softmax_lse,
-                           sp.splits, p->b, p->seqlen_q, p->h, p->d, p->o_batch_stride, p->o_row_stride, p->o_head_stride);
+                           sp.splits, p->b, p->seqlen_q, p->h, dw, p->o_batch_stride, p->o_row_stride, p->o_head_stride);
     if (hipGetLastError() != hipSuccess) return FA_ERR_LAUNCH;
     return FA_OK;
 }

@@ -113,7 +113,7 @@ struct FwdArgs {
     double softmax_scale = 1.0, softcap = 0.0, p_dropout = 0.0;
     bool causal = false;
     int64_t window_left = -1, window_right = -1;
-    OptTensor cu_seqlens_q, cu_seqlens_k, seqused_k, alibi, kv_batch_idx, block_table, leftpad_k, rng_state, s_dmask;
+    OptTensor cu_seqlens_q, cu_seqlens_k, seqused_k, alibi, kv_batch_idx, block_table, leftpad_k, rng_state, s_dmask, qv;
     int num_splits = 1, s_dmask_block_n = 0;
 };
 
@@ -171,6 +171,11 @@ void launch_fwd(const Tensor &q, const Tensor &k, const Tensor &v, const Tensor 
         p.s_dmask_block_n = a.s_dmask_block_n;
     }
     p.num_splits = a.num_splits;
+    if (v.size(-1) != q.size(-1)) p.d_v = (int32_t)v.size(-1);  // FA3 headdim_v (q/k <= 64 beside v in [256, 512] here)
+    if (a.qv.has_value()) {  // FA3 qv, dense (b, s, h, d_v) like q (ABI v13)
+        p.qv = a.qv->data_ptr();
+        p.qv_batch_stride = a.qv->stride(0); p.qv_row_stride = a.qv->stride(1); p.qv_head_stride = a.qv->stride(2);
+    }
     if (paged) {
         p.block_table = static_cast<const int32_t *>(a.block_table->data_ptr());
         p.block_table_batch_stride = a.block_table->stride(0);
@@ -576,6 +581,7 @@ void kvcache_append(const Tensor &k_new, const Tensor &v_new, const Tensor &k_ca
     p.vcache_batch_stride = v_cache.stride(0); p.vcache_row_stride = v_cache.stride(1); p.vcache_head_stride = v_cache.stride(2);
     p.b = (int32_t)k_new.size(0); p.seqlen_new = (int32_t)k_new.size(1); p.h_k = (int32_t)k_new.size(2); p.d = (int32_t)k_new.size(3);
     p.seqlen_cache = (int32_t)k_cache.size(1);
+    if (v_cache.size(3) != k_cache.size(3)) p.d_v = (int32_t)v_cache.size(3);  // V rows of their own width (ABI v13)
     if (block_table.has_value()) {
         p.block_table = static_cast<const int32_t *>(block_table->data_ptr());
         p.block_table_batch_stride = block_table->stride(0);
@@ -602,7 +608,7 @@ std::vector<Tensor> fwd_kvcache_impl(Tensor q, const Tensor &kcache, const Tenso
                                      OptTensor alibi_slopes_, OptTensor out_, const double softmax_scale, bool is_causal,
                                      int64_t window_size_left, int64_t window_size_right, const double softcap,
                                      bool is_rotary_interleaved, int64_t num_splits, int64_t page_multiple,
-                                     OptTensor seqlens_rotary_) {
+                                     OptTensor seqlens_rotary_, OptTensor qv_) {
     const auto q_dtype = q.scalar_type();
     TORCH_CHECK(q_dtype == at::kHalf || q_dtype == at::kBFloat16, "FlashAttention only support fp16 and bf16 data type");
     TORCH_CHECK(kcache.scalar_type() == q_dtype, "query and key must have the same dtype");
@@ -618,6 +624,20 @@ std::vector<Tensor> fwd_kvcache_impl(Tensor q, const Tensor &kcache, const Tenso
     int64_t seqlen_q = q.size(1), num_heads = q.size(2);
     int64_t batch_size_c = kcache.size(0), seqlen_k = kcache.size(1);
     const int64_t num_heads_k = kcache.size(2);
+    // FA3: V head dim of its own for q/k <= 64 beside v in [256, 512] (MLA: the qv kernel), hopper/flash_api.cpp:783-792
+    const int64_t head_size_v = vcache.dim() == 4 ? vcache.size(3) : head_size_og;
+    const bool wide_v = head_size_og <= 64 && head_size_v >= 256 && head_size_v <= 512 && head_size_v % 8 == 0;
+    TORCH_CHECK(head_size_v == head_size_og || wide_v,
+                "If V headdim is different from Q/K dim, this KV-cache path only supports Q/K <= 64 and V in [256, 512]");
+    if (qv_.has_value()) {  // hopper/flash_api.cpp:1028-1048
+        TORCH_CHECK(wide_v, "This flash attention build does not support qv here: q_v is only supported for head_size <= 64 and "
+                            "hdim_v >= 256 (<= 512)");
+        TORCH_CHECK(qv_->scalar_type() == q_dtype, "q_v must have the same dtype as query");
+        CHECK_DEVICE(*qv_, "q_v");
+        TORCH_CHECK(qv_->get_device() == q.get_device(), "q_v must be on the same device as query");
+        CHECK_LAST_CONTIGUOUS(*qv_, "q_v tensor must have contiguous last dimension");
+        CHECK_SHAPE(*qv_, "q_v", q.size(0), q.size(1), q.size(2), head_size_v);
+    }
     int64_t page_block_size = 0;
     if (paged) {
         auto pr = check_block_table(*block_table_, kcache, batch_size, page_multiple);
@@ -632,7 +652,9 @@ std::vector<Tensor> fwd_kvcache_impl(Tensor q, const Tensor &kcache, const Tenso
     if (seqlen_q == 1 && !alibi.has_value()) is_causal = false;  // (:1270)
     if (is_causal) window_size_right = 0;
     // (b, 1, (h_k ngroups), d) -> (b, ngroups, h_k, d): one pass over the cache serves the whole GQA group (:1272-1285)
-    const bool swapped = seqlen_q == 1 && num_heads > num_heads_k && window_size_left < 0 && window_size_right < 0 && !alibi.has_value();
+    // (not with qv: the qv kernel packs the GQA group into its rows itself, for any seqlen_q)
+    const bool swapped = seqlen_q == 1 && num_heads > num_heads_k && window_size_left < 0 && window_size_right < 0 && !alibi.has_value() &&
+                         !qv_.has_value();
     if (swapped) {
         const int64_t ngroups = num_heads / num_heads_k;
         q = q.reshape({batch_size, num_heads_k, ngroups, head_size_og}).transpose(1, 2);
@@ -641,10 +663,10 @@ std::vector<Tensor> fwd_kvcache_impl(Tensor q, const Tensor &kcache, const Tenso
     CHECK_SHAPE(q, "q", batch_size, seqlen_q, num_heads, head_size_og);
     if (paged) {
         CHECK_SHAPE(kcache, "kcache", kcache.size(0), page_block_size, num_heads_k, head_size_og);
-        CHECK_SHAPE(vcache, "vcache", kcache.size(0), page_block_size, num_heads_k, head_size_og);
+        CHECK_SHAPE(vcache, "vcache", kcache.size(0), page_block_size, num_heads_k, head_size_v);
     } else {
         CHECK_SHAPE(kcache, "kcache", batch_size_c, seqlen_k, num_heads_k, head_size_og);
-        CHECK_SHAPE(vcache, "vcache", batch_size_c, seqlen_k, num_heads_k, head_size_og);
+        CHECK_SHAPE(vcache, "vcache", batch_size_c, seqlen_k, num_heads_k, head_size_v);
     }
     Tensor out;
     if (out_.has_value() && !swapped) {
@@ -652,9 +674,9 @@ std::vector<Tensor> fwd_kvcache_impl(Tensor q, const Tensor &kcache, const Tenso
         TORCH_CHECK(out.scalar_type() == q_dtype, "Output must have the same dtype as inputs");
         CHECK_DEVICE(out, "out");
         TORCH_CHECK(out.stride(-1) == 1, "Output tensor must have contiguous last dimension");
-        CHECK_SHAPE(out, "out", batch_size, seqlen_q, num_heads, head_size_og);
+        CHECK_SHAPE(out, "out", batch_size, seqlen_q, num_heads, head_size_v);
     } else {
-        out = at::empty({batch_size, seqlen_q, num_heads, head_size_og}, q.options());
+        out = at::empty({batch_size, seqlen_q, num_heads, head_size_v}, q.options());
     }
     int64_t seqlen_knew = 0;
     if (k_.has_value()) {
@@ -668,7 +690,7 @@ std::vector<Tensor> fwd_kvcache_impl(Tensor q, const Tensor &kcache, const Tenso
         TORCH_CHECK(v_->stride(-1) == 1, "Value tensor must have contiguous last dimension");
         seqlen_knew = k_->size(1);
         CHECK_SHAPE(*k_, "k", batch_size, seqlen_knew, num_heads_k, head_size_og);
-        CHECK_SHAPE(*v_, "v", batch_size, seqlen_knew, num_heads_k, head_size_og);
+        CHECK_SHAPE(*v_, "v", batch_size, seqlen_knew, num_heads_k, head_size_v);
     }
     if (seqlens_k_.has_value()) {
         TORCH_CHECK(seqlens_k_->scalar_type() == at::kInt, "seqlens_k must have dtype int32");
@@ -730,6 +752,7 @@ std::vector<Tensor> fwd_kvcache_impl(Tensor q, const Tensor &kcache, const Tenso
         a.causal = is_causal; a.window_left = window_size_left; a.window_right = window_size_right; a.softcap = softcap;
         a.seqused_k = seqused; a.alibi = alibi; a.kv_batch_idx = cache_batch_idx_; a.block_table = block_table_;
         a.num_splits = (int)num_splits; a.leftpad_k = leftpad_k_;
+        if (qv_.has_value()) a.qv = aligned_or_copy(*qv_);
         launch_fwd(qc, kcache, vcache, oc, softmax_lse, a);
         if (!oc.is_same(out)) out.copy_(oc);
     } else {
@@ -737,7 +760,7 @@ std::vector<Tensor> fwd_kvcache_impl(Tensor q, const Tensor &kcache, const Tenso
         softmax_lse.fill_(std::numeric_limits<float>::infinity());
     }
     if (swapped) {
-        out = out.transpose(1, 2).reshape({batch_size, 1, num_heads_k * seqlen_q, head_size_og});
+        out = out.transpose(1, 2).reshape({batch_size, 1, num_heads_k * seqlen_q, head_size_v});
         softmax_lse = softmax_lse.reshape({batch_size, num_heads_k * seqlen_q, 1});
         if (out_.has_value()) {
             out_->copy_(out);
@@ -753,9 +776,13 @@ std::vector<Tensor> mha_fwd_kvcache(Tensor &q, const Tensor &kcache, const Tenso
                                     OptTensor &alibi_slopes_, OptTensor &out_, const double softmax_scale, bool is_causal,
                                     int64_t window_size_left, int64_t window_size_right, const double softcap,
                                     bool is_rotary_interleaved, int64_t num_splits) {
+    // (the FA2 surface keeps one head dim for q, k and v: a V of its own width is an FA3 argument)
+    if (vcache.dim() == 4 && kcache.dim() == 4 && vcache.size(3) != kcache.size(3))
+        TORCH_CHECK(false, block_table_.has_value() ? "vcache must have shape (kcache.size(0), page_block_size, num_heads_k, head_size_og)"
+                                                    : "vcache must have shape (batch_size_c, seqlen_k, num_heads_k, head_size_og)");
     return fwd_kvcache_impl(q, kcache, vcache, k_, v_, seqlens_k_, rotary_cos_, rotary_sin_, cache_batch_idx_, leftpad_k_,
                             block_table_, alibi_slopes_, out_, softmax_scale, is_causal, window_size_left, window_size_right,
-                            softcap, is_rotary_interleaved, num_splits, 256, c10::nullopt);  // the reference's page rule (:1265)
+                            softcap, is_rotary_interleaved, num_splits, 256, c10::nullopt, c10::nullopt);  // the reference's page rule (:1265)
 }
 
 bool set_fa3_window_rule(bool on) {
@@ -778,6 +805,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("rotary_sin"), py::arg("cache_batch_idx"), py::arg("leftpad_k"), py::arg("block_table"), py::arg("alibi_slopes"),
           py::arg("out"), py::arg("softmax_scale"), py::arg("is_causal"), py::arg("window_size_left"), py::arg("window_size_right"),
           py::arg("softcap"), py::arg("is_rotary_interleaved"), py::arg("num_splits"), py::arg("page_multiple"),
-          py::arg("seqlens_rotary") = py::none());
+          py::arg("seqlens_rotary") = py::none(), py::arg("qv") = py::none());
     m.def("_set_fa3_window_rule", &set_fa3_window_rule, "FA3 window rule for the backward entry points (returns the previous value)");
 }

@@ -6,8 +6,10 @@ Built: fp16 / bf16 / fp8 e4m3 inputs (fp8 -> bf16 output, :859), per-(batch, kv 
 dense and varlen (`cu_seqlens_*`, `seqused_*`), causal / sliding window / softcap, GQA.
 KV-cache arguments (dense q, 16-bit): k_new/v_new (in-place append at seqused_k), page_table (any page size),
 kv_batch_idx, leftpad_k, rotary_cos/sin (+ interleaved), num_splits -- served by `_fwd_kvcache_impl`.
-Accepted and rejected by message, like the reference does for compiled-out features (:1148-1165): qv,
-attention_chunk, cu_seqlens_k_new, seqlens_rotary, KV-cache arguments together with cu_seqlens_q or fp8.
+qv (MLA absorbed attention, :1028-1048: scores = (q.k + qv.v) * scale, d <= 64 beside d_v in [256, 512], 16-bit) on the
+dense, varlen, decode and KV-cache routes; the KV-cache routes also take d <= 64 beside a V head dim in [256, 512] without qv.
+Accepted and rejected by message, like the reference does for compiled-out features (:1148-1165): cu_seqlens_k_new,
+qv of any other shape or with fp8, KV-cache arguments together with cu_seqlens_q or fp8.
 `scheduler_metadata`, `pack_gqa`, `sm_margin` are performance hints and do not change results: ignored.
 """
 import math
@@ -37,12 +39,21 @@ def fwd(q, k, v, k_new, v_new, qv, out, cu_seqlens_q, cu_seqlens_k, cu_seqlens_k
     for t, n in ((q, "q"), (k, "k"), (v, "v")):
         _check(t.is_cuda, f"{n} must be on CUDA")
         _check(t.stride(-1) == 1, "Input tensor must have contiguous last dimension")
-    for x, n in ((qv, "qv"), (cu_seqlens_k_new, "cu_seqlens_k_new")):
-        _check(x is None, f"This flash attention build does not support {n}.")
+    _check(cu_seqlens_k_new is None, "This flash attention build does not support cu_seqlens_k_new.")
     attention_chunk = int(attention_chunk or 0)
     _check(attention_chunk >= 0, "attention_chunk must be non-negative")
     is_fp8 = _FP8 is not None and q.dtype == _FP8
     head_size_v = v.shape[-1]  # hopper/flash_api.cpp:764
+    # MLA shape (:783-792, 1028-1048): q/k <= 64 beside a V head dim in [256, 512] -- the qv kernel's
+    wide_v = q.shape[-1] <= 64 and 256 <= head_size_v <= 512 and head_size_v % 8 == 0 and not is_fp8
+    if qv is not None:
+        _check(wide_v, "This flash attention build does not support qv here: q_v is only supported for head_size <= 64 "
+                       "and hdim_v >= 256 (<= 512), with fp16 / bf16 inputs")
+        _check(qv.dtype == q.dtype, "q_v must have the same dtype as query")
+        _check(qv.is_cuda and qv.device == q.device, "q_v must be on the same CUDA device as query")
+        _check(qv.stride(-1) == 1, "q_v tensor must have contiguous last dimension")
+        _check(tuple(qv.shape) == tuple(q.shape[:-1]) + (head_size_v,),
+               f"q_v must have shape {tuple(q.shape[:-1]) + (head_size_v,)}")
     if head_size_v != q.shape[-1]:  # :782-792 (the "Only Hopper" line is the one check that does not carry over)
         _check((128 < q.shape[-1] <= 192 and 96 < head_size_v <= 128) or (q.shape[-1] <= 64 and head_size_v <= 512),
                "If V headdim is different from Q/K dim, we only support Q/K headdim in (128, 192] and V headdim in (96, 128], "
@@ -60,32 +71,33 @@ def fwd(q, k, v, k_new, v_new, qv, out, cu_seqlens_q, cu_seqlens_k, cu_seqlens_k
         _check(cu_seqlens_q is None and cu_seqlens_k is None and seqused_q is None,
                "This flash attention build does not support KV-cache arguments together with cu_seqlens / seqused_q.")
         _check(not is_fp8, "This flash attention build does not support KV-cache arguments with fp8 inputs.")
-        _check(not attention_chunk and head_size_v == q.shape[-1],
-               "This flash attention build does not support attention_chunk or a V headdim of its own with KV-cache arguments.")
+        _check(not attention_chunk and (head_size_v == q.shape[-1] or wide_v),
+               "This flash attention build does not support attention_chunk or a V headdim of its own with KV-cache arguments "
+               "(except Q/K <= 64 beside V in [256, 512]).")
         _check((k_new is None) == (v_new is None), "k_new and v_new must be passed together")
         _check((rotary_cos is None) == (rotary_sin is None), "rotary_cos and rotary_sin must be passed together")
         if k_new is not None or leftpad_k is not None:
             _check(seqused_k is not None, "seqused_k must be provided with k_new / leftpad_k")
         if softmax_scale is None:
-            softmax_scale = q.shape[-1] ** (-0.5)
+            softmax_scale = (q.shape[-1] + (head_size_v if qv is not None else 0)) ** (-0.5)
         from . import flash_attn_2_cuda
         o, lse = flash_attn_2_cuda._fwd_kvcache_impl(q, k, v, k_new, v_new, seqused_k, rotary_cos, rotary_sin, kv_batch_idx,
                                                leftpad_k, page_table, None, out, softmax_scale, bool(is_causal),
                                                int(window_size_left), int(window_size_right), float(softcap),
-                                               bool(is_rotary_interleaved), int(num_splits), 1, seqlens_rotary)
+                                               bool(is_rotary_interleaved), int(num_splits), 1, seqlens_rotary, qv)
         return o, lse, None, None
     if (cu_seqlens_q is None and cu_seqlens_k is None and seqused_q is None and seqused_k is not None and not is_fp8
             and q.dim() == 4 and q.shape[1] <= 128 and window_size_left < 0 and (window_size_right < 0 or is_causal)
-            and out is None and not attention_chunk and head_size_v == q.shape[-1]):
+            and out is None and not attention_chunk and (head_size_v == q.shape[-1] or wide_v)):
         # plain decode over a cache (flash_attn_with_kvcache(q, k_cache, v_cache, cache_seqlens=...)): the same routine as
         # the append / paged calls, which brings the split-KV heuristic (num_splits = 0) and the (b, 1, h) -> (b, ngroups, h_k)
         # GQA swap (hopper/flash_api.cpp:935-1060 runs them for every call with seqused_k)
         if softmax_scale is None:
-            softmax_scale = q.shape[-1] ** (-0.5)
+            softmax_scale = (q.shape[-1] + (head_size_v if qv is not None else 0)) ** (-0.5)
         from . import flash_attn_2_cuda
         o, lse = flash_attn_2_cuda._fwd_kvcache_impl(q, k, v, None, None, seqused_k, None, None, None, None, None, None, None,
                                                softmax_scale, bool(is_causal), -1, -1, float(softcap), False,
-                                               int(num_splits), 1)
+                                               int(num_splits), 1, None, qv)
         return o, lse, None, None
     varlen_q = cu_seqlens_q is not None
     varlen_k = cu_seqlens_k is not None
@@ -118,7 +130,7 @@ def fwd(q, k, v, k_new, v_new, qv, out, cu_seqlens_q, cu_seqlens_k, cu_seqlens_k
             _check(is_fp8, f"{n} is only supported with fp8 inputs")
             _check(t.dtype == torch.float32 and tuple(t.shape) == (batch_size, num_heads_k), f"{n} must be fp32 (batch_size, num_heads_k)")
     if softmax_scale is None:
-        softmax_scale = head_size ** (-0.5)
+        softmax_scale = (head_size + (head_size_v if qv is not None else 0)) ** (-0.5)
     # causal/local normalisation, hopper/flash_api.cpp:796-805
     if window_size_left >= seqlen_k - 1:
         window_size_left = -1
@@ -140,13 +152,14 @@ def fwd(q, k, v, k_new, v_new, qv, out, cu_seqlens_q, cu_seqlens_k, cu_seqlens_k
         softmax_lse = torch.empty(lse_shape, dtype=torch.float32, device=q.device)
         if seqlen_k > 0 and total_q > 0 and seqlen_q > 0:
             qc, kc, vc = (x if _dispatch.aligned(x) else x.contiguous() for x in (q, k, v))
+            qvc = None if qv is None else qv if _dispatch.aligned(qv) else qv.contiguous()
             oc = out if _dispatch.aligned(out) else torch.empty_like(out)
             _dispatch.launch(qc, kc, vc, oc, softmax_lse, varlen=varlen_q, batch=batch_size, max_seqlen_q=seqlen_q,
                              max_seqlen_k=seqlen_k, softmax_scale=softmax_scale, causal=is_causal,
                              window_left=window_size_left, window_right=window_size_right, softcap=softcap,
                              cu_seqlens_q=cu_seqlens_q, cu_seqlens_k=cu_seqlens_k, seqused_q=seqused_q,
                              seqused_k=seqused_k, q_descale=q_descale, k_descale=k_descale, v_descale=v_descale,
-                             attention_chunk=attention_chunk,
+                             attention_chunk=attention_chunk, qv=qvc,
                              fa3_window=True)  # a missing window side is unbounded (hopper/flash_api.cpp:152-153)
             if oc is not out:
                 out.copy_(oc)

@@ -56,6 +56,7 @@ class FlashAttnFunc(torch.autograd.Function):
         ctx.save_for_backward(q, k, v, out, softmax_lse)
         ctx.softmax_scale, ctx.causal, ctx.window_size = softmax_scale, causal, window_size
         ctx.attention_chunk, ctx.softcap, ctx.deterministic, ctx.sm_margin = attention_chunk, softcap, deterministic, sm_margin
+        ctx.has_qv = qv is not None
         if return_softmax:
             ctx.mark_non_differentiable(softmax_lse)
         return (out, softmax_lse) if return_softmax else out
@@ -64,6 +65,7 @@ class FlashAttnFunc(torch.autograd.Function):
     def backward(ctx, dout, *args):
         q, k, v, out, softmax_lse = ctx.saved_tensors
         assert ctx.attention_chunk == 0, "FA3 backward does not support attention_chunk"
+        assert not ctx.has_qv, "FA3 backward does not support qv"  # (the reference has no qv backward)
         dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
         _flash_attn_backward(dout, q, k, v, out, softmax_lse, None, None, None, None, None, None, dq, dk, dv,
                              ctx.softmax_scale, ctx.causal, ctx.window_size, ctx.softcap, ctx.deterministic, ctx.sm_margin)
@@ -88,6 +90,7 @@ class FlashAttnVarlenFunc(torch.autograd.Function):
         ctx.max_seqlen_q, ctx.max_seqlen_k = max_seqlen_q, max_seqlen_k
         ctx.softmax_scale, ctx.causal, ctx.window_size = softmax_scale, causal, window_size
         ctx.attention_chunk, ctx.softcap, ctx.deterministic, ctx.sm_margin = attention_chunk, softcap, deterministic, sm_margin
+        ctx.has_qv = qv is not None
         if return_softmax:
             ctx.mark_non_differentiable(softmax_lse)
         return (out, softmax_lse) if return_softmax else out
@@ -96,6 +99,7 @@ class FlashAttnVarlenFunc(torch.autograd.Function):
     def backward(ctx, dout, *args):
         q, k, v, out, softmax_lse, cu_seqlens_q, cu_seqlens_k, seqused_q, seqused_k = ctx.saved_tensors
         assert ctx.attention_chunk == 0, "FA3 backward does not support attention_chunk"
+        assert not ctx.has_qv, "FA3 backward does not support qv"  # (the reference has no qv backward)
         dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
         _flash_attn_backward(dout, q, k, v, out, softmax_lse, cu_seqlens_q, cu_seqlens_k, seqused_q, seqused_k,
                              ctx.max_seqlen_q, ctx.max_seqlen_k, dq, dk, dv, ctx.softmax_scale, ctx.causal, ctx.window_size,

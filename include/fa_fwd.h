@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define FA_ABI_VERSION 12
+#define FA_ABI_VERSION 13
 
 #define FA_FLAG_FA3_WINDOW 1
 #define FA_FLAG_SDMASK_SIGNED 2   /* s_dmask is the reference's sign-encoded probability tensor (below), not random bytes */
@@ -197,9 +197,18 @@ typedef struct fa_fwd_params {
     int32_t attention_chunk;
     /* ABI v12 -- head dim of V and O when it differs from d (FA3 "headdim_v", hopper/flash_api.cpp:764,782-792: q/k in
      * (128, 192] with v in (96, 128], or q/k <= 64 with v <= 512): v is (.., h_k, d_v), o (.., h, d_v).  0 = d.  Multiple of 8,
-     * <= 512; above 256 the library runs one launch per 256 columns of V.  16-bit types; not with split-KV, paged or fp8. */
+     * <= 512; above 256 the library runs one launch per 256 columns of V.  16-bit types; not with split-KV, paged or fp8 --
+     * except d <= 64 beside d_v in [256, 512], which runs the qv kernel below on paged caches and with split-KV too. */
     int32_t d_v;
     int32_t reserved_v12;
+    /* ABI v13 -- FA3 `qv` (hopper/flash_api.cpp:1028-1048; oracle hopper/test_util.py:287-292): the score gets a second
+     * product, scores = (q.k + qv.v) * softmax_scale, with qv of V's head dim: dense (b, seqlen_q, h, d_v), varlen
+     * (total_q, h, d_v) (qv_batch_stride ignored).  NULL = off.  16-bit types, d <= 64, 256 <= d_v <= 512, 16-byte aligned
+     * rows; every mask, softcap, seqused_*, varlen, leftpad_k, kv_batch_idx, paged K/V and split-KV (its partials are
+     * (splits, b, seqlen_q, h, d_v) + (splits, b, h, seqlen_q) fp32 in the workspace).  Not with fp8, ALiBi or dropout
+     * (FA3 has neither).  The query heads of one kv head are packed into the kernel's rows: one pass over K/V serves them. */
+    const void *qv;
+    int64_t qv_batch_stride, qv_row_stride, qv_head_stride;
 } fa_fwd_params;
 
 /* Validate and enqueue the forward on `stream` (a hipStream_t; NULL = default
@@ -262,6 +271,10 @@ typedef struct fa_kvcache_append_params {
     /* ABI v12 -- FA3 `seqlens_rotary` (hopper/flash_api.cpp:1074-1079, hopper/seqlen.h:89): (b) int32 rotary position of the
      * first appended row of each batch entry when it is not the cache fill level; NULL = cache_seqlens. */
     const int32_t *rotary_seqlens;
+    /* ABI v13 -- head dim of v_new / v_cache when it differs from d (MLA: 512-wide V rows beside 64-wide K rows); 0 = d.
+     * Multiple of 8, <= 512.  Rotary still touches the keys only. */
+    int32_t d_v;
+    int32_t reserved_v13;
 } fa_kvcache_append_params;
 
 int fa_kvcache_append(const fa_kvcache_append_params *params, void *stream);
