@@ -5,9 +5,9 @@
 // kernels on the caller's stream.  No allocation, no synchronisation.
 #include "fa_bwd.h"
 #include "fa_bwd_kernel.h"
+#include "fa_launch.h"
 
 #include <algorithm>
-#include <atomic>
 #include <cmath>
 
 namespace {
@@ -16,25 +16,6 @@ int head_dim_tile_b(int d) {
     if (d <= 64) return 64;
     if (d <= 128) return 128;
     return 256;
-}
-
-template <typename K>
-int launch_kernel(K kernel, int smem, std::atomic<uint64_t> &attr_set, int grid, int threads, const fa::BParams &bp,
-                  hipStream_t stream) {
-    // the > 64 KiB dynamic-LDS opt-in is a per-device attribute of the kernel: one bit per device ordinal
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    const uint64_t bit = uint64_t(1) << (dev & 63);
-    if (smem > 65536 && !(attr_set.load(std::memory_order_acquire) & bit)) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, smem) != hipSuccess) {
-            (void)hipGetLastError();
-            return FA_ERR_LAUNCH;
-        }
-        attr_set.fetch_or(bit, std::memory_order_release);
-    }
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(threads), smem, stream, bp);
-    if (hipGetLastError() != hipSuccess) return FA_ERR_LAUNCH;
-    return FA_OK;
 }
 
 // grid of decode_block(): whole units of `blocks` workgroups for as many (batch, head) units as deal evenly over the 8 XCDs,
@@ -71,7 +52,6 @@ int run_bwd(fa::BParams bp, int rows_q_max, int rows_k_max, hipStream_t stream) 
     }
     // 2. dK, dV
     {
-        static std::atomic<uint64_t> attr{0}, attr1{0};
         const int NBK = one_block ? 1 : NBK2;
         bp.num_blocks = (rows_k_max + 128 * NBK - 1) / (128 * NBK);
         const int64_t tiles = (int64_t)bp.num_blocks * bp.h_k * bp.b;
@@ -84,18 +64,16 @@ int run_bwd(fa::BParams bp, int rows_q_max, int rows_k_max, hipStream_t stream) 
             int st;
             if constexpr (D == 128 && !SOFTCAP && !DROPOUT) {
                 // head dims <= 96 on the 128-wide tiles: the instantiation whose generated loop skips the zero padding
-                static std::atomic<uint64_t> attr96{0};
-                st = bp.d <= 96 ? launch_kernel(fa::bwd_dkdv_kernel<T, D, 1, false, false, 96>, fa::smem_bytes_dkdv<D>(), attr96, bp.grid, 256, bp, stream)
-                                : launch_kernel(fa::bwd_dkdv_kernel<T, D, 1, false, false>, fa::smem_bytes_dkdv<D>(), attr, bp.grid, 256, bp, stream);
+                st = bp.d <= 96 ? fa::launch_kernel<fa::bwd_dkdv_kernel<T, D, 1, false, false, 96>>(fa::smem_bytes_dkdv<D>(), bp.grid, 256, stream, bp)
+                                : fa::launch_kernel<fa::bwd_dkdv_kernel<T, D, 1, false, false>>(fa::smem_bytes_dkdv<D>(), bp.grid, 256, stream, bp);
             } else if constexpr (D == 256) {
                 // head-dim tile 256: dV and dK by a launch each (PART 1 / 2, fa_bwd_kernel.h) -- one accumulator set per sweep;
                 // head dims <= 160 / <= 192 on the instantiations that skip the zero padding (DEFF)
                 auto two = [&](auto deff_c) {
                     constexpr int DEFF = decltype(deff_c)::value;
-                    static std::atomic<uint64_t> attr_dv{0}, attr_dk{0};
-                    int s2 = launch_kernel(fa::bwd_dkdv_kernel<T, D, 1, SOFTCAP, DROPOUT, DEFF, 1>, fa::smem_bytes_dkdv<D>(), attr_dv, bp.grid, 256, bp, stream);
+                    int s2 = fa::launch_kernel<fa::bwd_dkdv_kernel<T, D, 1, SOFTCAP, DROPOUT, DEFF, 1>>(fa::smem_bytes_dkdv<D>(), bp.grid, 256, stream, bp);
                     if (s2 == FA_OK)
-                        s2 = launch_kernel(fa::bwd_dkdv_kernel<T, D, 1, SOFTCAP, DROPOUT, DEFF, 2>, fa::smem_bytes_dkdv<D>(), attr_dk, bp.grid, 256, bp, stream);
+                        s2 = fa::launch_kernel<fa::bwd_dkdv_kernel<T, D, 1, SOFTCAP, DROPOUT, DEFF, 2>>(fa::smem_bytes_dkdv<D>(), bp.grid, 256, stream, bp);
                     return s2;
                 };
                 if constexpr (!SOFTCAP && !DROPOUT) {
@@ -105,15 +83,14 @@ int run_bwd(fa::BParams bp, int rows_q_max, int rows_k_max, hipStream_t stream) 
                     st = two(std::integral_constant<int, 256>{});
                 }
             } else {
-                st = one_block ? launch_kernel(fa::bwd_dkdv_kernel<T, D, 1, SOFTCAP, DROPOUT>, fa::smem_bytes_dkdv<D>(), attr1, bp.grid, 256, bp, stream)
-                               : launch_kernel(fa::bwd_dkdv_kernel<T, D, NBK2, SOFTCAP, DROPOUT>, fa::smem_bytes_dkdv<D>(), attr, bp.grid, 256, bp, stream);
+                st = one_block ? fa::launch_kernel<fa::bwd_dkdv_kernel<T, D, 1, SOFTCAP, DROPOUT>>(fa::smem_bytes_dkdv<D>(), bp.grid, 256, stream, bp)
+                               : fa::launch_kernel<fa::bwd_dkdv_kernel<T, D, NBK2, SOFTCAP, DROPOUT>>(fa::smem_bytes_dkdv<D>(), bp.grid, 256, stream, bp);
             }
             if (st != FA_OK) return st;
         }
     }
     // 3. dQ
     {
-        static std::atomic<uint64_t> attr{0};
         bp.num_blocks = (rows_q_max + 128 * NBQ - 1) / (128 * NBQ);
         const int64_t tiles = (int64_t)bp.num_blocks * bp.h * bp.b;
         if (tiles > 0x7fffffff) return FA_ERR_BAD_SHAPE;
@@ -124,17 +101,15 @@ int run_bwd(fa::BParams bp, int rows_q_max, int rows_k_max, hipStream_t stream) 
             bp.grid = (int32_t)grid;
             int st;
             if constexpr (D == 128 && !SOFTCAP && !DROPOUT) {
-                static std::atomic<uint64_t> attr96{0};
-                st = bp.d <= 96 ? launch_kernel(fa::bwd_dq_kernel<T, D, NBQ, false, false, 96>, fa::smem_bytes_dq<D>(), attr96, bp.grid, 256, bp, stream)
-                                : launch_kernel(fa::bwd_dq_kernel<T, D, NBQ, false, false>, fa::smem_bytes_dq<D>(), attr, bp.grid, 256, bp, stream);
+                st = bp.d <= 96 ? fa::launch_kernel<fa::bwd_dq_kernel<T, D, NBQ, false, false, 96>>(fa::smem_bytes_dq<D>(), bp.grid, 256, stream, bp)
+                                : fa::launch_kernel<fa::bwd_dq_kernel<T, D, NBQ, false, false>>(fa::smem_bytes_dq<D>(), bp.grid, 256, stream, bp);
             } else if constexpr (D == 256 && !SOFTCAP && !DROPOUT) {
-                static std::atomic<uint64_t> attr160{0}, attr192{0};
                 const int w = std::max(bp.d, bp.d_v);
-                st = w <= 160 ? launch_kernel(fa::bwd_dq_kernel<T, D, NBQ, false, false, 160>, fa::smem_bytes_dq<D>(), attr160, bp.grid, 256, bp, stream)
-                   : w <= 192 ? launch_kernel(fa::bwd_dq_kernel<T, D, NBQ, false, false, 192>, fa::smem_bytes_dq<D>(), attr192, bp.grid, 256, bp, stream)
-                                 : launch_kernel(fa::bwd_dq_kernel<T, D, NBQ, false, false>, fa::smem_bytes_dq<D>(), attr, bp.grid, 256, bp, stream);
+                st = w <= 160 ? fa::launch_kernel<fa::bwd_dq_kernel<T, D, NBQ, false, false, 160>>(fa::smem_bytes_dq<D>(), bp.grid, 256, stream, bp)
+                   : w <= 192 ? fa::launch_kernel<fa::bwd_dq_kernel<T, D, NBQ, false, false, 192>>(fa::smem_bytes_dq<D>(), bp.grid, 256, stream, bp)
+                                 : fa::launch_kernel<fa::bwd_dq_kernel<T, D, NBQ, false, false>>(fa::smem_bytes_dq<D>(), bp.grid, 256, stream, bp);
             } else {
-                st = launch_kernel(fa::bwd_dq_kernel<T, D, NBQ, SOFTCAP, DROPOUT>, fa::smem_bytes_dq<D>(), attr, bp.grid, 256, bp, stream);
+                st = fa::launch_kernel<fa::bwd_dq_kernel<T, D, NBQ, SOFTCAP, DROPOUT>>(fa::smem_bytes_dq<D>(), bp.grid, 256, stream, bp);
             }
             if (st != FA_OK) return st;
         }

@@ -9,10 +9,12 @@
 #include "fa_fwd_kernel_fp8.h"
 #include "fa_fwd_kernel_d256.h"
 #include "fa_fwd_kernel_qv.h"
+#include "fa_launch.h"
 
 #include <algorithm>
 #include <atomic>
 #include <cmath>
+#include <cstdio>
 
 namespace {
 
@@ -271,6 +273,11 @@ __global__ __launch_bounds__(256) void sdmask_kernel(const fa::KParams p, T *out
     }
 }
 
+// ---- forward routing ----------------------------------------------------------------------------------------------------
+// plan_fwd() is the one place that decides which kernel a problem runs, with which template arguments, grid, split-KV plan
+// and fp8 workspace.  It is host code without HIP calls: fa_fwd_validate, fa_fwd_workspace_size, fa_fwd and fa_fwd_plan_name
+// (the test hook that names the plan, tests/test_fwd_plan.py) all read the same plan.
+
 int64_t align256(int64_t x) { return (x + 255) & ~int64_t(255); }
 
 struct Fp8Plan {
@@ -286,32 +293,42 @@ Fp8Plan fp8_plan(const fa_fwd_params *p) {
     return pl;
 }
 
-int head_dim_tile(int d);
-int block_m_of(int variant, int d);
+int head_dim_tile(int d) {
+    if (d <= 64) return 64;
+    if (d <= 128) return 128;
+    return 256;
+}
+int block_m_of(int variant, int d) { return (variant == 2 || head_dim_tile(d) == 256) ? 128 : 256; }
 
-// fp8 inputs run natively (fa_fwd_kernel_fp8.h: e4m3 operands straight into the block-scaled MFMA, no expansion pass, no
-// workspace) for the shape BASELINE config 5 names -- head dim 128, dense or varlen, full / causal / right-window masks.  The
-// rest of the fp8 surface (other head dims, softcap, left windows) and an explicit kernel_variant take the exact
-// e4m3 -> bf16 expansion in front of the 16-bit kernels.
 // ABI v12: attention_chunk and a V head dim of its own exist in fwd_kernel only (the compiler-scheduled shape)
 inline bool own_dv(const fa_fwd_params *p) { return p->d_v > 0 && p->d_v != p->d; }
 inline bool generic_only(const fa_fwd_params *p) { return p->attention_chunk > 0 || own_dv(p); }
 inline int wide_dim(const fa_fwd_params *p) { return own_dv(p) ? std::max(p->d, std::min(p->d_v, 256)) : p->d; }  // what the LDS tile has to hold
 // ABI v13: the qv kernel (fa_fwd_kernel_qv.h) serves q/k head dims <= 64 beside a V head dim in [256, 512] -- every call with
-// qv, and without qv the paged / split-KV calls of that shape (the 256-column launches below cannot split or page).  The dense
+// qv, and without qv the paged / split-KV calls of that shape (the 256-column launches cannot split or page).  The dense
 // and varlen calls without qv keep the 256-column launches.
 inline int dv_of(const fa_fwd_params *p) { return p->d_v > 0 ? p->d_v : p->d; }
 inline bool qv_shape(const fa_fwd_params *p) {
     return p->dtype != FA_DTYPE_FP8_E4M3 && p->d <= 64 && dv_of(p) >= 256 && dv_of(p) <= 512;
 }
 inline bool qv_route(const fa_fwd_params *p) { return p->qv || (qv_shape(p) && (p->block_table || p->num_splits > 1)); }
+// a left window that masks anything (the FA2 rule drops one of seqlen_k or more, fa_fwd's window normalisation)
+inline bool left_window(const fa_fwd_params *p) {
+    return p->window_size_left >= 0 && ((p->flags & FA_FLAG_FA3_WINDOW) || p->window_size_left < p->seqlen_k);
+}
+// 1 / (1 - p_dropout) as the kernels get it: the dropout instantiations run exactly when it is not 1
+inline float rp_dropout(const fa_fwd_params *p) { return p->p_dropout > 0.f ? 1.f / (1.f - p->p_dropout) : 1.f; }
 
+// fp8 inputs run natively (fa_fwd_kernel_fp8.h: e4m3 operands straight into the block-scaled MFMA, no expansion pass, no
+// workspace) for the shape BASELINE config 5 names -- head dim 128, dense or varlen, full / causal / right-window masks.  The
+// rest of the fp8 surface (other head dims, softcap, left windows) and an explicit kernel_variant take the exact
+// e4m3 -> bf16 expansion in front of the 16-bit kernels.
 bool fp8_native(const fa_fwd_params *p) {
     if (p->dtype != FA_DTYPE_FP8_E4M3 || p->d != 128 || generic_only(p)) return false;
     const int variant = p->kernel_variant ? p->kernel_variant : g_default_variant.load();
     if (variant != 0) return false;
     if (p->softcap > 0.f || p->alibi_slopes || p->block_table || p->kv_batch_idx || p->leftpad_k || p->p_dropout > 0.f) return false;
-    if (p->window_size_left >= 0 && ((p->flags & FA_FLAG_FA3_WINDOW) || p->window_size_left < p->seqlen_k)) return false;
+    if (left_window(p)) return false;
     const int64_t strides[] = {p->q_row_stride, p->q_head_stride, p->k_row_stride, p->k_head_stride, p->v_row_stride,
                                p->v_head_stride, p->cu_seqlens_q ? 0 : p->q_batch_stride, p->cu_seqlens_q ? 0 : p->k_batch_stride,
                                p->cu_seqlens_q ? 0 : p->v_batch_stride};
@@ -330,23 +347,18 @@ bool fp8_native(const fa_fwd_params *p) {
     return true;
 }
 
-// ---- split-KV plan (role of num_splits_heuristic / set_params_splitkv, csrc/flash_attn/flash_api.cpp:257-329) ---------
-// Only dense (non-varlen) 16-bit problems split.  Heuristic (num_splits == 0): split when the tiles leave most of the
-// 256 CUs idle, so that tiles x splits reaches ~2 workgroups per CU, with at least 4 key blocks (256 keys) per split.
-// Kernel shape for a problem.  0 = the library's choice: the 256-row software-pipelined kernel, except
+// Kernel shape of a 16-bit (or fp8-expanded) problem.  0 = the library's choice: the 256-row software-pipelined kernel, except
 //  * paged caches -> the 64-key-aligned 8-wave shape (variant 1);
 //  * short dense query blocks (seqlen_q <= 128: decode steps, short prefill chunks) -> 4 waves x 32 rows (variant 2):
 //    a 256-row tile would leave 2-3 of its 4 waves without rows, and this shape fits two workgroups per CU
 //    (measured on decode b8 hq32/hkv8 cache 8192: 149 -> 59 us, b32: 255 -> 219 us).
-bool fp8_native(const fa_fwd_params *p);
 int effective_variant(const fa_fwd_params *p) {
-    if (fp8_native(p)) return 0;  // one shape: 4 waves x 64 rows
     int variant = p->kernel_variant ? p->kernel_variant : g_default_variant.load();
     if (variant < 0 || variant > 3) variant = 0;
     if (p->p_dropout > 0.f) return 1;  // dropout lives in the compiler-scheduled shape only
     if (generic_only(p)) {
         // fwd_kernel, EXTRA instantiations: 8 waves x 32 rows (4 x 32 at head-dim tile 256) -- except a V head dim of its own
-        // on the wide tile, which dispatch_variant<T, 256> hands to the generated-loop kernel when the features are plain
+        // on the wide tile, which plan_fwd hands to the generated-loop kernel when the features are plain
         if (p->attention_chunk == 0 && head_dim_tile(wide_dim(p)) == 256 && variant == 0) return 0;
         return 1;
     }
@@ -372,6 +384,9 @@ int effective_variant(const fa_fwd_params *p) {
     return variant;
 }
 
+// ---- split-KV plan (role of num_splits_heuristic / set_params_splitkv, csrc/flash_attn/flash_api.cpp:257-329) ---------
+// Only dense (non-varlen) 16-bit problems split.  Heuristic (num_splits == 0): split when the tiles leave most of the
+// 256 CUs idle, so that tiles x splits reaches ~2 workgroups per CU, with at least 4 key blocks (256 keys) per split.
 struct SplitPlan {
     int splits;
     int64_t o_bytes, lse_bytes, total;  // partial O (fp32, (splits, b, sq, h, d)) and LSE (fp32, (splits, b, h, sq))
@@ -427,7 +442,170 @@ SplitPlan split_plan_qv(const fa_fwd_params *p) {
     sp.total = sp.o_bytes + sp.lse_bytes;
     return sp;
 }
-inline SplitPlan plan_of(const fa_fwd_params *p, int variant) { return qv_route(p) ? split_plan_qv(p) : split_plan(p, variant); }
+
+enum class Family { fp8, qv, w64, d256, generic };  // fwd_kernel_fp8, fwd_kernel_qv, fwd_kernel_w64, fwd_kernel_d256, fwd_kernel
+
+struct FwdPlan {
+    Family family;
+    int d;           // head-dim tile D of fwd_kernel / fwd_kernel_w64 / fwd_kernel_fp8
+    int deff;        // fwd_kernel_w64: DEFF; fwd_kernel_d256: its width W; fwd_kernel_qv: the V tile DVT
+    int waves;
+    bool softcap, alibi, dropout, extra, persist;  // template forms (alibi: fwd_kernel_d256 only)
+    int block_m;     // query rows per workgroup
+    int32_t num_m_blocks;
+    int64_t tiles, unit_tiles, whole_slots, grid;  // scheduling of the row blocks over the XCDs (tile_of_wg)
+    int status;      // FA_ERR_BAD_SHAPE when the grid does not fit 31 bits
+    bool nothing;    // no query or no key: no split, no fp8 expansion, no S_dmask pass
+    SplitPlan split;
+    bool fp8_expand; // fp8 inputs the 16-bit kernels read as bf16 copies, made by expand_fp8_kernel in the workspace
+    Fp8Plan fp8;
+    int cols;        // calls of 256 V columns each (d_v > 256 without the qv kernel); the kernel fields plan the first
+    int64_t workspace;
+};
+
+// The persistent form of the 256-row kernel (fa_fwd_kernel_w64.h, PERSIST): plain dense problems at head dims 97..128 whose
+// every work item sweeps at least three 64-key tiles and whose K / V tensors one 32-bit raw buffer descriptor can span.
+bool persist_ok(const fa_fwd_params *p, const FwdPlan &pl, int num_cus) {
+    const int mode = g_persist_mode.load();
+    if (mode < 0) return false;
+    const bool fp8 = p->dtype == FA_DTYPE_FP8_E4M3;
+    if (p->cu_seqlens_q || p->cu_seqlens_k || p->seqused_q || p->seqused_k || p->leftpad_k || p->kv_batch_idx || p->block_table) return false;
+    if (p->alibi_slopes || (fp8 && (p->q_descale || p->k_descale || p->v_descale)) || pl.split.splits > 1 || rp_dropout(p) != 1.f) return false;
+    if (p->d <= 96 || p->d > 128) return false;   // (left windows: the next item's first tile is its own n_min, round 3)
+    if (p->seqlen_k % 64 != 0 || p->seqlen_k < 192 || p->seqlen_q > p->seqlen_k) return false;  // (causal: bottom-right aligned, shift >= 0)
+    if ((num_cus & ~7) < 8) return false;
+    // the kernel decodes its chain once into 32-bit entries (m_block 12 bits, head 10, batch 10), one lane per round
+    if (pl.grid > 64 * (num_cus & ~7) || pl.num_m_blocks > 4096 || p->h > 1024 || p->b > 1024) return false;
+    // K and V as the kernel reads them: the fp8 expansion leaves contiguous (rows, h_k, d) copies
+    int64_t kbs = p->k_batch_stride, khs = p->k_head_stride, krs = p->k_row_stride;
+    int64_t vbs = p->v_batch_stride, vhs = p->v_head_stride, vrs = p->v_row_stride;
+    if (pl.fp8_expand) {
+        krs = vrs = (int64_t)p->h_k * p->d;
+        khs = vhs = p->d;
+        kbs = vbs = krs * p->seqlen_k;
+    }
+    auto extent = [&](int64_t bs, int64_t hs, int64_t rs, int lead) {
+        return ((int64_t)(p->b - 1) * bs + (int64_t)(p->h_k - 1) * hs + (int64_t)(p->seqlen_k - 1 + lead) * rs + 128) * 2;
+    };
+    if (kbs < 0 || khs < 0 || krs <= 0 || vbs < 0 || vhs < 0 || vrs <= 0) return false;
+    if (extent(kbs, khs, krs, 32) >= (1ll << 32) - 65536 || extent(vbs, vhs, vrs, 0) >= (1ll << 32) - 65536) return false;
+    if ((int64_t)p->seqlen_k * krs >= (1ll << 30) || (int64_t)p->seqlen_k * vrs >= (1ll << 30)) return false;
+    if (mode > 0) return true;
+    // left windows: supported (bit-identical to the hand-over kernel, tests/test_persistent_gpu.py) but measured SLOWER there --
+    // b4 s4096 window (1024, 0) 538 -> 472, (512, 512) 530 -> 469, s16384 (4096, 0) 825 -> 782 TFLOP/s: a windowed item spends its
+    // first tiles on the generic half-step (the left edge), where the cross-item look-ahead stream buys nothing -- not dispatched
+    if (left_window(p)) return false;
+    // chains of one item gain nothing; from two items per CU on the persistent form wins or ties on the whole benchmark grid
+    // (profiles/r3_persist_sweep.txt: non-causal s512 .. 16k +10 / +5 / +2 / 0 %, causal +21 / +26 / +15 / +11 / +3 / +1 %)
+    return pl.grid > (num_cus & ~7);
+}
+
+// The plan of one fa_fwd call on a device of `num_cus` compute units (which decide the persistent form only).  Reads only `p`,
+// `num_cus`, g_default_variant and g_persist_mode.  Safe on parameters fa_fwd_validate has not finished with: it is part of it.
+FwdPlan plan_fwd(const fa_fwd_params *p, int num_cus) {
+    const bool qv = qv_route(p);
+    if (p->d_v > 256 && !qv) {
+        // V head dims above the widest tile (hopper/flash_api.cpp:783-792 allows up to 512 beside q/k <= 64): fa_fwd makes one
+        // call per 256 columns of V and O
+        fa_fwd_params first = *p;
+        first.d_v = 256;
+        FwdPlan pl = plan_fwd(&first, num_cus);
+        pl.cols = (p->d_v + 255) / 256;
+        pl.split = SplitPlan{1, 0, 0, 0};  // (the whole call has a V head dim of its own: never split)
+        pl.workspace = pl.fp8_expand ? pl.fp8.total : 0;
+        return pl;
+    }
+    FwdPlan pl{};
+    pl.cols = 1;
+    pl.status = FA_OK;
+    const bool fp8 = p->dtype == FA_DTYPE_FP8_E4M3, native = fp8_native(p);
+    const bool softcap = p->softcap > 0.f, alibi = p->alibi_slopes != nullptr, dropout = rp_dropout(p) != 1.f;
+    const int variant = native ? 0 : effective_variant(p);  // (fp8 native: one shape, 4 waves x 64 rows)
+    pl.nothing = p->seqlen_q == 0 || p->seqlen_k == 0 || (p->cu_seqlens_q && p->total_q == 0);
+    pl.fp8_expand = fp8 && !native;
+    if (fp8) pl.fp8 = fp8_plan(p);
+    pl.split = pl.nothing ? SplitPlan{1, 0, 0, 0} : qv ? split_plan_qv(p) : split_plan(p, variant);
+    pl.workspace = fp8 ? (native ? 0 : pl.fp8.total) : pl.split.total;
+
+    // softcap or ALiBi at head dims <= 128 (measured b4 s4096: softcap d128 471, d64 322, ALiBi 231 / 182 TFLOP/s through the C++
+    // paths of the 256-row kernel): the generated loops that cap / bias scores exist for the 32-row-per-wave shape only ->
+    // fwd_kernel_d256 at widths 64 / 96 / 128
+    const bool capped = softcap != alibi && variant == 0 && p->d <= 128 && !generic_only(p) && !pl.nothing && pl.split.splits <= 1;
+    const int tile = head_dim_tile(wide_dim(p));
+    pl.block_m = capped ? 128 : block_m_of(variant, wide_dim(p));
+
+    // scheduling (tile_of_wg): whole (batch, kv head) units -- everything that streams one head's K/V stays on one XCD -- for as
+    // many units as deal evenly over the 8 XCDs, the remaining heads by m_block of the GQA group; problems with fewer than two
+    // units per XCD entirely by m_block (fill the chip first, L2 reuse second).  (20 units used to be dealt 3+3+3+3+2+2+2+2:
+    // the launch took as long as 24, tools/hdim_bench.py d192 b2 h10 2.88 ms instead of 2.41.)
+    pl.num_m_blocks = (p->seqlen_q + pl.block_m - 1) / pl.block_m;
+    pl.tiles = (int64_t)pl.num_m_blocks * p->h * p->b;
+    const int h_ratio = p->h / p->h_k;
+    if (h_ratio > 0) {  // (h < h_k fails validation)
+        const int64_t bk_units = (int64_t)p->b * p->h_k, per_kvh = (int64_t)h_ratio * pl.num_m_blocks;
+        const int64_t whole_units = bk_units >= 16 ? bk_units / 8 * 8 : 0;
+        pl.unit_tiles = per_kvh;
+        pl.whole_slots = whole_units / 8 * per_kvh;
+        const int64_t rem_units = (pl.tiles - pl.whole_slots * 8 + h_ratio - 1) / h_ratio;
+        pl.grid = 8 * (pl.whole_slots + (rem_units + 7) / 8 * h_ratio);
+    }
+    if (pl.tiles > 0x7fffffff || pl.whole_slots > 0x7fffffff || pl.grid * pl.split.splits > 0x7fffffff) pl.status = FA_ERR_BAD_SHAPE;
+
+    // the generated-loop kernel of head-dim tile 256 (fa_fwd_kernel_d256.h): plain problems, softcap or ALiBi (not both)
+    const bool d256_ok = (variant == 0 || variant == 3) && !(softcap && alibi) && !p->block_table && pl.split.splits <= 1 &&
+                         !dropout && p->attention_chunk == 0;
+    pl.d = pl.deff = tile;
+    pl.waves = 4;
+    if (native) {  // e4m3 operands straight into the block-scaled MFMA
+        pl.family = Family::fp8;
+    } else if (qv) {
+        pl.family = Family::qv;
+        pl.deff = dv_of(p) <= 256 ? 256 : 512;
+        pl.waves = fa::QV_NWAVES;
+        pl.softcap = softcap;
+    } else if (tile == 256 ? d256_ok : capped) {
+        // 4 waves x 32 rows around FastLoop256: head-dim tiles 160 / 192 / 256 (hopper/tile_size.h:20-45) skip the zero padding,
+        // a V head dim of its own takes the larger of the two (the kernel reads p.dv for V and O)
+        pl.family = Family::d256;
+        const int w = wide_dim(p);
+        pl.deff = tile == 256 ? (w <= 160 ? 160 : w <= 192 ? 192 : 256) : tile == 128 ? (p->d <= 96 ? 96 : 128) : 64;
+        pl.softcap = softcap;
+        pl.alibi = !softcap && alibi;
+    } else if (tile != 256 && (variant == 0 || variant == 3)) {
+        // 4 waves x 64 rows, one wave per SIMD, software-pipelined (fa_fwd_kernel_w64.h) -- the default.  D = 256 does not fit
+        // its register budget (O alone would be 256 registers).
+        pl.family = Family::w64;
+        pl.softcap = softcap;
+        if (!softcap && tile == 128 && p->d <= 96) pl.deff = 96;  // head-dim tile 96 (hopper/tile_size.h:10-54)
+        else if (!softcap && tile == 128) pl.persist = persist_ok(p, pl, num_cus);
+    } else {
+        // the compiler-scheduled shape (fa_fwd_kernel.h): 8 waves x 32 rows (variant 1), 4 x 32 (variant 2 and head-dim tile
+        // 256).  attention_chunk / a V head dim of its own (FA3 surface, ABI v12) run its EXTRA instantiations, dropout (p > 0,
+        // also when its 8-bit threshold keeps everything) its DROPOUT ones -- neither with softcap (fa_fwd_validate).  (A DEFF = 192
+        // instantiation at head-dim tile 256 -- 12 + 12 instead of 16 + 16 MFMAs per 32-key block -- was measured at exactly the
+        // per-workgroup time of the 256 one, tools/hdim_bench.py: this shape is bound by its register-staged K/V rows, which stay
+        // 512 B wide, not by the matrix pipe.)
+        pl.family = Family::generic;
+        pl.waves = (tile == 256 || variant == 2) ? 4 : 8;
+        pl.extra = generic_only(p);
+        pl.dropout = !pl.extra && dropout;
+        pl.softcap = !pl.dropout && softcap;
+    }
+    return pl;
+}
+
+// compute units of the current device (cached per device ordinal)
+int device_cus() {
+    static std::atomic<int> cus[64];
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    int n = cus[dev & 63].load(std::memory_order_relaxed);
+    if (n == 0) {
+        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
+        cus[dev & 63].store(n, std::memory_order_relaxed);
+    }
+    return n;
+}
 
 // ---- split-KV merge: out = sum_s w_s O_s / sum_s w_s, w_s = exp(lse_s - max lse); lse = max + log sum w.  One thread =
 // one 16-byte chunk of one (batch, row, head); splits with LSE = +inf (no key in their range) carry no weight.
@@ -525,227 +703,91 @@ __global__ void combine_partials_kernel(const fa_combine_params p) {
     }
 }
 
-int head_dim_tile(int d) {
-    if (d <= 64) return 64;
-    if (d <= 128) return 128;
-    return 256;
+// ---- the plan -> the template instantiation ------------------------------------------------------------------------------
+template <typename T, int D, int NWAVES, bool SOFTCAP, bool DROPOUT = false, bool EXTRA = false>
+int launch_fwd_kernel(const fa::KParams &kp, hipStream_t stream) {
+    return fa::launch_kernel<fa::fwd_kernel<T, D, NWAVES, SOFTCAP, DROPOUT, D, EXTRA>>(
+        fa::smem_bytes<D, NWAVES>(), (int64_t)kp.grid * kp.num_splits, NWAVES * 64, stream, kp);
 }
-
-template <typename T, int D, int NWAVES, bool SOFTCAP, bool DROPOUT = false, int DEFF = D, bool EXTRA = false>
-int launch(const fa::KParams &kp, hipStream_t stream) {
-    constexpr int smem = fa::smem_bytes<D, NWAVES>();
-    auto kernel = fa::fwd_kernel<T, D, NWAVES, SOFTCAP, DROPOUT, DEFF, EXTRA>;
-    // the > 64 KiB dynamic-LDS opt-in is a per-device attribute of the kernel: one bit per device ordinal
-    static std::atomic<uint64_t> attr_set{0};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    const uint64_t bit = uint64_t(1) << (dev & 63);
-    if (smem > 65536 && !(attr_set.load(std::memory_order_acquire) & bit)) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, smem) != hipSuccess) {
-            (void)hipGetLastError();
-            return FA_ERR_LAUNCH;
-        }
-        attr_set.fetch_or(bit, std::memory_order_release);
+template <typename T, int D>
+int launch_generic(const FwdPlan &pl, const fa::KParams &kp, hipStream_t stream) {
+    constexpr int NW = D == 256 ? 4 : 8;  // (the EXTRA and DROPOUT shapes)
+    if (pl.extra) return pl.softcap ? launch_fwd_kernel<T, D, NW, true, false, true>(kp, stream) : launch_fwd_kernel<T, D, NW, false, false, true>(kp, stream);
+    if (pl.dropout) return launch_fwd_kernel<T, D, NW, false, true>(kp, stream);
+    if constexpr (NW == 8) {
+        if (pl.waves == 8) return pl.softcap ? launch_fwd_kernel<T, D, 8, true>(kp, stream) : launch_fwd_kernel<T, D, 8, false>(kp, stream);
     }
-    hipLaunchKernelGGL(kernel, dim3(kp.grid * (kp.num_splits > 1 ? kp.num_splits : 1)), dim3(NWAVES * 64), smem, stream, kp);
-    if (hipGetLastError() != hipSuccess) return FA_ERR_LAUNCH;
-    return FA_OK;
+    return pl.softcap ? launch_fwd_kernel<T, D, 4, true>(kp, stream) : launch_fwd_kernel<T, D, 4, false>(kp, stream);
 }
 
 template <typename T, int D, bool SOFTCAP, int DEFF = D, bool PERSIST = false>
 int launch_w64(const fa::KParams &kp, hipStream_t stream) {
-    constexpr int smem = fa::smem_bytes_w64<D>();
-    auto kernel = fa::fwd_kernel_w64<T, D, SOFTCAP, DEFF, PERSIST>;
-    // the > 64 KiB dynamic-LDS opt-in is a per-device attribute of the kernel: one bit per device ordinal
-    static std::atomic<uint64_t> attr_set{0};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    const uint64_t bit = uint64_t(1) << (dev & 63);
-    if (smem > 65536 && !(attr_set.load(std::memory_order_acquire) & bit)) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, smem) != hipSuccess) {
-            (void)hipGetLastError();
-            return FA_ERR_LAUNCH;
-        }
-        attr_set.fetch_or(bit, std::memory_order_release);
-    }
     // PERSIST: one workgroup per CU (a multiple of 8: ids go round-robin over the XCDs), each walks its chain of the slot list
-    const int wgs = PERSIST ? std::min(kp.grid, kp.num_cus & ~7) : kp.grid * (kp.num_splits > 1 ? kp.num_splits : 1);
-    hipLaunchKernelGGL(kernel, dim3(wgs), dim3(256), smem, stream, kp);
-    if (hipGetLastError() != hipSuccess) return FA_ERR_LAUNCH;
-    return FA_OK;
+    const int64_t wgs = PERSIST ? std::min(kp.grid, kp.num_cus & ~7) : (int64_t)kp.grid * kp.num_splits;
+    return fa::launch_kernel<fa::fwd_kernel_w64<T, D, SOFTCAP, DEFF, PERSIST>>(fa::smem_bytes_w64<D>(), wgs, 256, stream, kp);
 }
-
-// The persistent form of the 256-row kernel (fa_fwd_kernel_w64.h, PERSIST): plain dense problems at head dims 97..128 whose
-// every work item sweeps at least three 64-key tiles and whose K / V tensors one 32-bit raw buffer descriptor can span.
-bool persist_ok(const fa::KParams &kp) {
-    const int mode = g_persist_mode.load();
-    if (mode < 0) return false;
-    if (kp.cu_seqlens_q || kp.cu_seqlens_k || kp.seqused_q || kp.seqused_k || kp.leftpad_k || kp.kv_batch_idx || kp.block_table) return false;
-    if (kp.alibi || kp.q_descale || kp.k_descale || kp.v_descale || kp.num_splits > 1 || kp.rp_dropout != 1.f) return false;
-    if (kp.d <= 96 || kp.d > 128) return false;   // (left windows: the next item's first tile is its own n_min, round 3)
-    if (kp.seqlen_k % 64 != 0 || kp.seqlen_k < 192 || kp.seqlen_q > kp.seqlen_k) return false;  // (causal: bottom-right aligned, shift >= 0)
-    if ((kp.num_cus & ~7) < 8) return false;
-    // the kernel decodes its chain once into 32-bit entries (m_block 12 bits, head 10, batch 10), one lane per round
-    if (kp.grid > 64 * (kp.num_cus & ~7) || kp.num_m_blocks > 4096 || kp.h > 1024 || kp.b > 1024) return false;
-    auto extent = [&](int64_t bs, int64_t hs, int64_t rs, int lead) {
-        return ((int64_t)(kp.b - 1) * bs + (int64_t)(kp.h_k - 1) * hs + (int64_t)(kp.seqlen_k - 1 + lead) * rs + 128) * 2;
-    };
-    if (kp.k_batch_stride < 0 || kp.k_head_stride < 0 || kp.k_row_stride <= 0 || kp.v_batch_stride < 0 || kp.v_head_stride < 0 || kp.v_row_stride <= 0) return false;
-    if (extent(kp.k_batch_stride, kp.k_head_stride, kp.k_row_stride, 32) >= (1ll << 32) - 65536 ||
-        extent(kp.v_batch_stride, kp.v_head_stride, kp.v_row_stride, 0) >= (1ll << 32) - 65536) return false;
-    if ((int64_t)kp.seqlen_k * kp.k_row_stride >= (1ll << 30) || (int64_t)kp.seqlen_k * kp.v_row_stride >= (1ll << 30)) return false;
-    if (mode > 0) return true;
-    // left windows: supported (bit-identical to the hand-over kernel, tests/test_persistent_gpu.py) but measured SLOWER there --
-    // b4 s4096 window (1024, 0) 538 -> 472, (512, 512) 530 -> 469, s16384 (4096, 0) 825 -> 782 TFLOP/s: a windowed item spends its
-    // first tiles on the generic half-step (the left edge), where the cross-item look-ahead stream buys nothing -- not dispatched
-    if (kp.window_left >= 0) return false;
-    // chains of one item gain nothing; from two items per CU on the persistent form wins or ties on the whole benchmark grid
-    // (profiles/r3_persist_sweep.txt: non-causal s512 .. 16k +10 / +5 / +2 / 0 %, causal +21 / +26 / +15 / +11 / +3 / +1 %)
-    return kp.grid > (kp.num_cus & ~7);
-}
-
-// head dims 129 .. 256, plain features: 4 waves x 32 rows around the generated loop FastLoop256 (fa_fwd_kernel_d256.h)
-template <typename T, int DEFF, bool SOFTCAP = false, bool ALIBI = false>
-int launch_d256(const fa::KParams &kp, hipStream_t stream) {
-    constexpr int smem = fa::smem_bytes_d256();
-    auto kernel = fa::fwd_kernel_d256<T, DEFF, SOFTCAP, ALIBI>;
-    static std::atomic<uint64_t> attr_set{0};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    const uint64_t bit = uint64_t(1) << (dev & 63);
-    if (!(attr_set.load(std::memory_order_acquire) & bit)) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, smem) != hipSuccess) {
-            (void)hipGetLastError();
-            return FA_ERR_LAUNCH;
-        }
-        attr_set.fetch_or(bit, std::memory_order_release);
-    }
-    hipLaunchKernelGGL(kernel, dim3(kp.grid), dim3(256), smem, stream, kp);
-    if (hipGetLastError() != hipSuccess) return FA_ERR_LAUNCH;
-    return FA_OK;
-}
-
-// the 32-row-per-wave kernel (fa_fwd_kernel_d256.h) at head-dim tile W (64 .. 256), plain / softcap / ALiBi form
-template <typename T, int W>
-int launch_d256_form(const fa::KParams &kp, bool softcap, hipStream_t stream) {
-    if (softcap) return launch_d256<T, W, true, false>(kp, stream);
-    if (kp.alibi) return launch_d256<T, W, false, true>(kp, stream);
-    if constexpr (W >= 160) return launch_d256<T, W>(kp, stream);
-    else return FA_ERR_UNSUPPORTED;   // (head dims <= 128 without softcap / ALiBi run the 256-row kernel: never dispatched here)
-}
-template <typename T>
-int launch_d256_wide(const fa::KParams &kp, int w, bool softcap, hipStream_t stream) {
-    if (w <= 160) return launch_d256_form<T, 160>(kp, softcap, stream);
-    if (w <= 192) return launch_d256_form<T, 192>(kp, softcap, stream);
-    return launch_d256_form<T, 256>(kp, softcap, stream);
-}
-
 template <typename T, int D>
-int dispatch_variant(const fa::KParams &kp, bool softcap, int variant, hipStream_t stream) {
-    // variant 0/3: 4 waves x 64 rows, one wave per SIMD, software-pipelined (fa_fwd_kernel_w64.h) -- the default
-    // variant 1  : 8 waves x 32 rows (BLOCK_M 256), two waves per SIMD (fa_fwd_kernel.h)
-    // variant 2  : 4 waves x 32 rows (BLOCK_M 128)
-    // D = 256 does not fit the w64 register budget (O alone would be 256 registers): 4 waves x 32 rows.
-    const bool d256_ok = (variant == 0 || variant == 3) && !(softcap && kp.alibi) && !kp.block_table && kp.num_splits <= 1 &&
-                         kp.rp_dropout == 1.f && kp.chunk == 0;
-    if constexpr (D == 256) {
-        // a V head dim of its own on the wide tile (192 / 128, or q/k <= 64 beside v in (128, 256]) with plain features: the
-        // generated-loop kernel, head-dim tile by the larger of the two (fa_fwd_kernel_d256.h reads p.dv for V and O)
-        if (kp.dv != kp.d && d256_ok) return launch_d256_wide<T>(kp, std::max(kp.d, kp.dv), softcap, stream);
+int launch_w64_form(const FwdPlan &pl, const fa::KParams &kp, hipStream_t stream) {
+    if (pl.softcap) return launch_w64<T, D, true>(kp, stream);
+    if constexpr (D == 128) {
+        if (pl.deff == 96) return launch_w64<T, 128, false, 96>(kp, stream);
+        if (pl.persist) return launch_w64<T, 128, false, 128, true>(kp, stream);
     }
-    if (kp.chunk > 0 || kp.dv != kp.d) {
-        // attention_chunk / a V head dim of its own (FA3 surface, ABI v12): the EXTRA instantiations of the compiler-scheduled
-        // shape, 8 waves x 32 rows (4 at head-dim tile 256); no dropout on that surface (fa_fwd_validate)
-        constexpr int NW = D == 256 ? 4 : 8;
-        if (softcap) return launch<T, D, NW, true, false, D, true>(kp, stream);
-        return launch<T, D, NW, false, false, D, true>(kp, stream);
-    }
-    if (kp.rp_dropout != 1.f) {  // dropout (p > 0, also when its 8-bit threshold keeps everything): its own instantiation of the compiler-scheduled shape (never with softcap)
-        if constexpr (D == 256) return launch<T, D, 4, false, true>(kp, stream);
-        else return launch<T, D, 8, false, true>(kp, stream);
-    }
-    if constexpr (D == 256) {
-        // round 3: the plain problems (dense / varlen, causal / windows, GQA, softcap) run the generated-loop kernel; ALiBi,
-        // paged caches, split-KV and the short-q / explicit shapes keep the compiler-scheduled one
-        // head-dim tiles 160 / 192 / 256 (hopper/tile_size.h:20-45): the zero padding is neither multiplied nor accumulated;
-        // softcap or ALiBi: the forms of the generated loop that cap / bias the fresh scores themselves (round 3)
-        if (d256_ok) return launch_d256_wide<T>(kp, kp.d, softcap, stream);
-        // (a DEFF = 192 instantiation -- 12 + 12 instead of 16 + 16 MFMAs per 32-key block -- was measured at exactly the
-        //  per-workgroup time of the 256 one, tools/hdim_bench.py: this shape is bound by its register-staged K/V rows, which
-        //  stay 512 B wide, not by the matrix pipe; head dims 129..192 therefore keep the 256 instantiation)
-        if (softcap) return launch<T, D, 4, true>(kp, stream);
-        return launch<T, D, 4, false>(kp, stream);
-    } else {
-        // variant 4 (internal, fa_fwd): softcap or ALiBi at head dims <= 128 with otherwise plain features on the head-dim-256
-        // kernel's shape (one 32-row q-block per wave, FastLoop256<T, DEFF <= 128, ...>): the 256-row kernel has no generated
-        // loop under either
-        if constexpr (D == 128) {
-            if (variant == 4) return kp.d <= 96 ? launch_d256_form<T, 96>(kp, softcap, stream) : launch_d256_form<T, 128>(kp, softcap, stream);
-        } else {
-            if (variant == 4) return launch_d256_form<T, 64>(kp, softcap, stream);
-        }
-        if (variant == 0 || variant == 3) {
-            if (softcap) return launch_w64<T, D, true>(kp, stream);
-            if constexpr (D == 128) {
-                if (kp.d <= 96) return launch_w64<T, D, false, 96>(kp, stream);  // head-dim tile 96 (hopper/tile_size.h:10-54)
-                if (persist_ok(kp)) return launch_w64<T, D, false, 128, true>(kp, stream);
-            }
-            return launch_w64<T, D, false>(kp, stream);
-        }
-        if (variant == 2) {
-            if (softcap) return launch<T, D, 4, true>(kp, stream);
-            return launch<T, D, 4, false>(kp, stream);
-        }
-        if (softcap) return launch<T, D, 8, true>(kp, stream);
-        return launch<T, D, 8, false>(kp, stream);
-    }
+    return launch_w64<T, D, false>(kp, stream);
 }
 
-template <typename T>
-int dispatch_hdim(const fa::KParams &kp, bool softcap, int variant, hipStream_t stream) {
-    switch (head_dim_tile(std::max(kp.d, kp.dv))) {
-        case 64: return dispatch_variant<T, 64>(kp, softcap, variant, stream);
-        case 128: return dispatch_variant<T, 128>(kp, softcap, variant, stream);
-        default: return dispatch_variant<T, 256>(kp, softcap, variant, stream);
-    }
+template <typename T, int W>
+int launch_d256_form(const FwdPlan &pl, const fa::KParams &kp, hipStream_t stream) {
+    constexpr int smem = fa::smem_bytes_d256();
+    if (pl.softcap) return fa::launch_kernel<fa::fwd_kernel_d256<T, W, true, false>>(smem, kp.grid, 256, stream, kp);
+    if (pl.alibi) return fa::launch_kernel<fa::fwd_kernel_d256<T, W, false, true>>(smem, kp.grid, 256, stream, kp);
+    if constexpr (W >= 160) return fa::launch_kernel<fa::fwd_kernel_d256<T, W, false, false>>(smem, kp.grid, 256, stream, kp);
+    return FA_ERR_UNSUPPORTED;  // (plain head dims <= 128 run fwd_kernel_w64: never planned)
 }
-
-int block_m_of(int variant, int d) { return (variant == 2 || head_dim_tile(d) == 256) ? 128 : 256; }
 
 template <typename T, int DVT, bool SOFTCAP>
 int launch_qv_form(const fa::QvParams &qa, int64_t grid, hipStream_t stream) {
-    constexpr int smem = fa::smem_bytes_qv<DVT>();
-    auto kernel = fa::fwd_kernel_qv<T, DVT, SOFTCAP>;
-    static std::atomic<uint64_t> attr_set{0};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    const uint64_t bit = uint64_t(1) << (dev & 63);
-    if (smem > 65536 && !(attr_set.load(std::memory_order_acquire) & bit)) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, smem) != hipSuccess) {
-            (void)hipGetLastError();
-            return FA_ERR_LAUNCH;
-        }
-        attr_set.fetch_or(bit, std::memory_order_release);
-    }
-    hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(fa::QV_NWAVES * 64), smem, stream, qa);
-    return hipGetLastError() == hipSuccess ? FA_OK : FA_ERR_LAUNCH;
+    return fa::launch_kernel<fa::fwd_kernel_qv<T, DVT, SOFTCAP>>(fa::smem_bytes_qv<DVT>(), grid, fa::QV_NWAVES * 64, stream, qa);
 }
 // the qv kernel (fa_fwd_kernel_qv.h): V tile 256 (d_v = 256) or 512 columns (d_v in (256, 512])
 template <typename T>
-int launch_qv(const fa_fwd_params *p, const fa::KParams &kp, bool softcap, hipStream_t stream) {
+int launch_qv(const FwdPlan &pl, const fa_fwd_params *p, const fa::KParams &kp, hipStream_t stream) {
     fa::QvParams qa{};
     qa.p = kp;
     qa.qv = p->qv;
     qa.qv_batch_stride = p->qv_batch_stride; qa.qv_row_stride = p->qv_row_stride; qa.qv_head_stride = p->qv_head_stride;
     const int64_t pblocks = ((int64_t)p->seqlen_q * (p->h / p->h_k) + 31) / 32;
-    const int64_t groups = (int64_t)p->b * p->h_k * (kp.num_splits > 1 ? kp.num_splits : 1);
+    const int64_t groups = (int64_t)p->b * p->h_k * kp.num_splits;
     const int64_t grid = (groups + 7) / 8 * 8 * pblocks;
     if (pblocks == 0 || groups == 0) return FA_OK;
     if (grid > 0x7fffffff) return FA_ERR_BAD_SHAPE;
     qa.num_pblocks = (int32_t)pblocks;
     qa.num_groups = (int32_t)groups;
-    if (kp.dv <= 256) return softcap ? launch_qv_form<T, 256, true>(qa, grid, stream) : launch_qv_form<T, 256, false>(qa, grid, stream);
-    return softcap ? launch_qv_form<T, 512, true>(qa, grid, stream) : launch_qv_form<T, 512, false>(qa, grid, stream);
+    if (pl.deff == 256) return pl.softcap ? launch_qv_form<T, 256, true>(qa, grid, stream) : launch_qv_form<T, 256, false>(qa, grid, stream);
+    return pl.softcap ? launch_qv_form<T, 512, true>(qa, grid, stream) : launch_qv_form<T, 512, false>(qa, grid, stream);
+}
+
+template <typename T>
+int launch_plan(const FwdPlan &pl, const fa_fwd_params *p, const fa::KParams &kp, hipStream_t stream) {
+    switch (pl.family) {
+        case Family::fp8: return fa::launch_kernel<fa::fwd_kernel_fp8>(fa::smem_bytes_fp8(), kp.grid, 256, stream, kp);
+        case Family::qv: return launch_qv<T>(pl, p, kp, stream);
+        case Family::w64: return pl.d == 64 ? launch_w64_form<T, 64>(pl, kp, stream) : launch_w64_form<T, 128>(pl, kp, stream);
+        case Family::d256:
+            switch (pl.deff) {
+                case 64: return launch_d256_form<T, 64>(pl, kp, stream);
+                case 96: return launch_d256_form<T, 96>(pl, kp, stream);
+                case 128: return launch_d256_form<T, 128>(pl, kp, stream);
+                case 160: return launch_d256_form<T, 160>(pl, kp, stream);
+                case 192: return launch_d256_form<T, 192>(pl, kp, stream);
+                default: return launch_d256_form<T, 256>(pl, kp, stream);
+            }
+        case Family::generic:
+            if (pl.d == 64) return launch_generic<T, 64>(pl, kp, stream);
+            if (pl.d == 128) return launch_generic<T, 128>(pl, kp, stream);
+            return launch_generic<T, 256>(pl, kp, stream);
+    }
+    return FA_ERR_UNSUPPORTED;
 }
 
 }  // namespace
@@ -899,8 +941,7 @@ int64_t fa_fwd_workspace_size(const fa_fwd_params *p) {
     if (p->abi_version != FA_ABI_VERSION || p->struct_size != sizeof(fa_fwd_params)) return FA_ERR_BAD_ABI;
     if (p->b <= 0 || p->h <= 0 || p->h_k <= 0 || p->d <= 0 || p->seqlen_q < 0 || p->seqlen_k < 0) return FA_ERR_BAD_SHAPE;
     if (p->cu_seqlens_q && (p->total_q < 0 || p->total_k < 0)) return FA_ERR_BAD_SHAPE;
-    if (p->dtype == FA_DTYPE_FP8_E4M3) return fp8_native(p) ? 0 : fp8_plan(p).total;
-    return plan_of(p, effective_variant(p)).total;
+    return plan_fwd(p, 0).workspace;
 }
 
 int fa_fwd_validate(const fa_fwd_params *p) {
@@ -913,14 +954,16 @@ int fa_fwd_validate(const fa_fwd_params *p) {
     if (fp8 && p->d % 16 != 0) return FA_ERR_BAD_HEAD_DIM;  // hopper/flash_api.cpp:854-856
     if (p->attention_chunk < 0) return FA_ERR_BAD_SHAPE;
     if (p->d_v < 0 || p->d_v > 512 || p->d_v % 8 != 0) return FA_ERR_BAD_HEAD_DIM;  // 0 = d
+    const FwdPlan pl = plan_fwd(p, 0);  // (the CU count decides the persistent form only)
     if (p->qv) {  // ABI v13 (hopper/flash_api.cpp:1028-1048): d <= 64, 256 <= d_v <= 512, 16-bit; no ALiBi / dropout in FA3
         if (fp8 || !qv_shape(p) || p->alibi_slopes || p->p_dropout > 0.f) return FA_ERR_UNSUPPORTED;
         if (p->qv_row_stride % 8 != 0 || p->qv_head_stride % 8 != 0 || (!p->cu_seqlens_q && p->qv_batch_stride % 8 != 0) ||
             reinterpret_cast<uintptr_t>(p->qv) % 16 != 0)
             return FA_ERR_BAD_STRIDE;
     }
-    if (own_dv(p) && (fp8 || p->block_table || p->num_splits > 1) && !qv_route(p)) return FA_ERR_UNSUPPORTED;
-    if (qv_route(p) && p->alibi_slopes) return FA_ERR_UNSUPPORTED;
+    const bool qv_kernel = pl.family == Family::qv;
+    if (own_dv(p) && (fp8 || p->block_table || p->num_splits > 1) && !qv_kernel) return FA_ERR_UNSUPPORTED;
+    if (qv_kernel && p->alibi_slopes) return FA_ERR_UNSUPPORTED;
     if (generic_only(p) && p->p_dropout > 0.f) return FA_ERR_UNSUPPORTED;  // (no dropout on the FA3 surface)
     if (p->attention_chunk > 0 && p->s_dmask) return FA_ERR_UNSUPPORTED;  // (the S_dmask pass knows windows only)
     if (p->h % p->h_k != 0) return FA_ERR_BAD_HEADS;
@@ -948,18 +991,12 @@ int fa_fwd_validate(const fa_fwd_params *p) {
     const void *ptrs[] = {p->q, p->k, p->v, p->o};
     for (const void *ptr : ptrs)
         if (reinterpret_cast<uintptr_t>(ptr) % (fp8 && ptr != p->o ? 8 : 16) != 0) return FA_ERR_BAD_STRIDE;
-    if (fp8 && !fp8_native(p) && !empty && p->seqlen_k > 0) {
-        if (!p->workspace || reinterpret_cast<uintptr_t>(p->workspace) % 256 != 0 ||
-            (int64_t)p->workspace_bytes < fp8_plan(p).total)
-            return FA_ERR_WORKSPACE;
-    }
+    auto workspace_short = [&](int64_t bytes) {
+        return !p->workspace || reinterpret_cast<uintptr_t>(p->workspace) % 256 != 0 || (int64_t)p->workspace_bytes < bytes;
+    };
+    if (pl.fp8_expand && !pl.nothing && workspace_short(pl.fp8.total)) return FA_ERR_WORKSPACE;
     if (p->num_splits < 0) return FA_ERR_BAD_SHAPE;
-    if (!fp8 && !empty && p->seqlen_k > 0) {
-        const SplitPlan sp = plan_of(p, effective_variant(p));
-        if (sp.splits > 1 && (!p->workspace || reinterpret_cast<uintptr_t>(p->workspace) % 256 != 0 ||
-                              (int64_t)p->workspace_bytes < sp.total))
-            return FA_ERR_WORKSPACE;
-    }
+    if (pl.split.splits > 1 && workspace_short(pl.split.total)) return FA_ERR_WORKSPACE;
     if (p->softcap < 0.f || std::isnan(p->softcap) || std::isnan(p->softmax_scale)) return FA_ERR_BAD_SHAPE;
     if (p->alibi_slopes && (reinterpret_cast<uintptr_t>(p->alibi_slopes) % 4 != 0 || p->alibi_slopes_batch_stride < 0 ||
                             p->alibi_slopes_batch_stride > 0x7fffffff))
@@ -986,16 +1023,33 @@ int fa_fwd_validate(const fa_fwd_params *p) {
     return FA_OK;
 }
 
+const char *fa_fwd_plan_name(const fa_fwd_params *p, int32_t num_cus) {
+    if (fa_fwd_validate(p) != FA_OK) return nullptr;
+    const FwdPlan pl = plan_fwd(p, num_cus);
+    if (pl.status != FA_OK) return nullptr;
+    static const char *const kernels[] = {"fwd_kernel_fp8 D=", "fwd_kernel_qv DVT=", "fwd_kernel_w64 D=", "fwd_kernel_d256 W=",
+                                          "fwd_kernel D="};
+    const bool by_width = pl.family == Family::qv || pl.family == Family::d256;
+    thread_local char name[160];
+    int n = snprintf(name, sizeof(name), "%s%d", kernels[static_cast<int>(pl.family)], by_width ? pl.deff : pl.d);
+    if (pl.family == Family::w64) n += snprintf(name + n, sizeof(name) - n, " DEFF=%d", pl.deff);
+    n += snprintf(name + n, sizeof(name) - n, " waves=%d%s%s%s%s%s block_m=%d splits=%d%s", pl.waves, pl.softcap ? " SOFTCAP" : "",
+                  pl.alibi ? " ALIBI" : "", pl.dropout ? " DROPOUT" : "", pl.extra ? " EXTRA" : "", pl.persist ? " PERSIST" : "",
+                  pl.block_m, pl.split.splits, pl.fp8_expand ? " fp8_expand" : "");
+    if (pl.cols > 1) snprintf(name + n, sizeof(name) - n, " cols=%d", pl.cols);
+    return name;
+}
+
 int fa_fwd(const fa_fwd_params *p, void *stream_) {
     const int st = fa_fwd_validate(p);
     if (st != FA_OK) return st;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
 
-    const bool qv_kernel = qv_route(p);
-    if (p->d_v > 256 && !qv_kernel) {
-        // V head dims above the widest tile (hopper/flash_api.cpp:783-792 allows up to 512 beside q/k <= 64): one launch per 256
-        // columns of V and O -- the scores are formed again for each (d <= 64: a small part of the work), the LSE is written
-        // by every launch with the same value.  Strides are untouched: the launches differ in the V / O column offset only.
+    const int num_cus = device_cus();
+    const FwdPlan pl = plan_fwd(p, num_cus);
+    if (pl.cols > 1) {
+        // one call per 256 columns of V and O -- the scores are formed again for each (d <= 64: a small part of the work), the LSE
+        // is written by every call with the same value.  Strides are untouched: the calls differ in the V / O column offset only.
         for (int c = 0; c < p->d_v; c += 256) {
             fa_fwd_params part = *p;
             part.v = static_cast<const char *>(p->v) + (size_t)c * 2;
@@ -1006,28 +1060,13 @@ int fa_fwd(const fa_fwd_params *p, void *stream_) {
         }
         return FA_OK;
     }
-    int variant = effective_variant(p);
-    int block_m = block_m_of(variant, wide_dim(p));
-    {   // softcap or ALiBi at head dims <= 128 (measured b4 s4096: softcap d128 471, d64 322, ALiBi 231 / 182 TFLOP/s through the C++
-        // paths of the 256-row kernel): the generated loops that cap / bias scores exist for the 32-row-per-wave shape only ->
-        // its DEFF = 64 / 96 / 128 instantiations
-        const bool nothing_ = p->seqlen_q == 0 || p->seqlen_k == 0 || (p->cu_seqlens_q && p->total_q == 0);
-        if (((p->softcap > 0.f) != (p->alibi_slopes != nullptr)) && variant == 0 && p->d <= 128 && !generic_only(p) &&
-            !p->block_table && p->p_dropout == 0.f && !nothing_ && split_plan(p, variant).splits <= 1 &&
-            !(p->dtype == FA_DTYPE_FP8_E4M3 && fp8_native(p))) {
-            variant = 4;
-            block_m = 128;
-        }
-    }
 
     fa::KParams kp{};
     kp.q = p->q; kp.k = p->k; kp.v = p->v; kp.o = p->o; kp.lse = p->softmax_lse;
     const bool fp8 = p->dtype == FA_DTYPE_FP8_E4M3;
-    const bool nothing = p->seqlen_q == 0 || p->seqlen_k == 0 || (p->cu_seqlens_q && p->total_q == 0);
     int64_t ws_q_row = 0, ws_k_row = 0;
-    const bool native8 = fp8 && fp8_native(p);
-    if (fp8 && !native8 && !nothing) {
-        const Fp8Plan pl = fp8_plan(p);
+    if (pl.fp8_expand && !pl.nothing) {
+        const Fp8Plan &fp = pl.fp8;
         char *ws = static_cast<char *>(p->workspace);
         const int rpb_q = p->cu_seqlens_q ? 0 : p->seqlen_q, rpb_k = p->cu_seqlens_q ? 0 : p->seqlen_k;
         auto expand = [&](const void *src, void *dst, int64_t rows, int rpb, int heads, int64_t bs, int64_t rs, int64_t hs) {
@@ -1037,11 +1076,11 @@ int fa_fwd(const fa_fwd_params *p, void *stream_) {
             hipLaunchKernelGGL(expand_fp8_kernel, dim3(blocks), dim3(256), 0, stream, static_cast<const uint8_t *>(src),
                                static_cast<uint32_t *>(dst), rows, rpb, heads, p->d, bs, rs, hs);
         };
-        expand(p->q, ws, pl.rows_q, rpb_q, p->h, p->q_batch_stride, p->q_row_stride, p->q_head_stride);
-        expand(p->k, ws + pl.q_bytes, pl.rows_k, rpb_k, p->h_k, p->k_batch_stride, p->k_row_stride, p->k_head_stride);
-        expand(p->v, ws + pl.q_bytes + pl.kv_bytes, pl.rows_k, rpb_k, p->h_k, p->v_batch_stride, p->v_row_stride, p->v_head_stride);
+        expand(p->q, ws, fp.rows_q, rpb_q, p->h, p->q_batch_stride, p->q_row_stride, p->q_head_stride);
+        expand(p->k, ws + fp.q_bytes, fp.rows_k, rpb_k, p->h_k, p->k_batch_stride, p->k_row_stride, p->k_head_stride);
+        expand(p->v, ws + fp.q_bytes + fp.kv_bytes, fp.rows_k, rpb_k, p->h_k, p->v_batch_stride, p->v_row_stride, p->v_head_stride);
         if (hipGetLastError() != hipSuccess) return FA_ERR_LAUNCH;
-        kp.q = ws; kp.k = ws + pl.q_bytes; kp.v = ws + pl.q_bytes + pl.kv_bytes;
+        kp.q = ws; kp.k = ws + fp.q_bytes; kp.v = ws + fp.q_bytes + fp.kv_bytes;
         ws_q_row = (int64_t)p->h * p->d;
         ws_k_row = (int64_t)p->h_k * p->d;
     }
@@ -1051,7 +1090,7 @@ int fa_fwd(const fa_fwd_params *p, void *stream_) {
     kp.k_batch_stride = p->k_batch_stride; kp.k_row_stride = p->k_row_stride; kp.k_head_stride = p->k_head_stride;
     kp.v_batch_stride = p->v_batch_stride; kp.v_row_stride = p->v_row_stride; kp.v_head_stride = p->v_head_stride;
     if (fp8) {
-        if (!native8) {  // the expanded copies are contiguous (rows, heads, d)
+        if (pl.fp8_expand) {  // the expanded copies are contiguous (rows, heads, d)
             kp.q_row_stride = ws_q_row; kp.q_head_stride = p->d; kp.q_batch_stride = ws_q_row * p->seqlen_q;
             kp.k_row_stride = kp.v_row_stride = ws_k_row; kp.k_head_stride = kp.v_head_stride = p->d;
             kp.k_batch_stride = kp.v_batch_stride = ws_k_row * p->seqlen_k;
@@ -1067,42 +1106,18 @@ int fa_fwd(const fa_fwd_params *p, void *stream_) {
     kp.dv = own_dv(p) ? p->d_v : p->d;
     kp.chunk = p->attention_chunk;
     kp.h_ratio = p->h / p->h_k;
-    kp.num_m_blocks = (p->seqlen_q + block_m - 1) / block_m;
-    const int64_t tiles = (int64_t)kp.num_m_blocks * p->h * p->b;
-    if (tiles == 0) return FA_OK;  // nothing to compute (seqlen_q == 0)
-    if (tiles > 0x7fffffff) return FA_ERR_BAD_SHAPE;
-    kp.num_tiles = (int32_t)tiles;
-    // scheduling (tile_of_wg): whole (batch, kv head) units -- everything that streams one head's K/V stays on one XCD -- for as
-    // many units as deal evenly over the 8 XCDs, the remaining heads by m_block of the GQA group; problems with fewer than two
-    // units per XCD entirely by m_block (fill the chip first, L2 reuse second).  (20 units used to be dealt 3+3+3+3+2+2+2+2:
-    // the launch took as long as 24, tools/hdim_bench.py d192 b2 h10 2.88 ms instead of 2.41.)
-    const int64_t bk_units = (int64_t)p->b * p->h_k;
-    const int64_t per_kvh = (int64_t)kp.h_ratio * kp.num_m_blocks;
-    const int64_t whole_units = bk_units >= 16 ? bk_units / 8 * 8 : 0;
-    kp.unit_tiles = (int32_t)per_kvh;
-    const int64_t whole_slots = whole_units / 8 * per_kvh;
-    const int64_t rem_units = (tiles - whole_slots * 8 + kp.h_ratio - 1) / kp.h_ratio;
-    const int64_t grid = 8 * (whole_slots + (rem_units + 7) / 8 * kp.h_ratio);
-    if (whole_slots > 0x7fffffff) return FA_ERR_BAD_SHAPE;
-    kp.whole_slots = (int32_t)whole_slots;
-    if (grid > 0x7fffffff) return FA_ERR_BAD_SHAPE;
-    kp.grid = (int32_t)grid;
-    {   // compute units of the current device (cached per device ordinal)
-        static std::atomic<int> cus[64];
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        int n = cus[dev & 63].load(std::memory_order_relaxed);
-        if (n == 0) {
-            if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-            cus[dev & 63].store(n, std::memory_order_relaxed);
-        }
-        kp.num_cus = n;
-    }
+    kp.num_m_blocks = pl.num_m_blocks;
+    if (pl.tiles == 0) return FA_OK;  // nothing to compute (seqlen_q == 0)
+    if (pl.status != FA_OK) return pl.status;
+    kp.num_tiles = (int32_t)pl.tiles;
+    kp.unit_tiles = (int32_t)pl.unit_tiles;
+    kp.whole_slots = (int32_t)pl.whole_slots;
+    kp.grid = (int32_t)pl.grid;
+    kp.num_cus = num_cus;
     // split-KV: `splits` copies of the grid; partial results go to the workspace and are merged below
-    const SplitPlan sp = nothing ? SplitPlan{1, 0, 0, 0} : plan_of(p, variant == 4 ? 0 : variant);
+    const SplitPlan &sp = pl.split;
     kp.num_splits = sp.splits;
     if (sp.splits > 1) {
-        if (grid * sp.splits > 0x7fffffff) return FA_ERR_BAD_SHAPE;
         char *ws = static_cast<char *>(p->workspace);
         kp.o = ws;
         kp.lse = reinterpret_cast<float *>(ws + sp.o_bytes);
@@ -1137,7 +1152,7 @@ int fa_fwd(const fa_fwd_params *p, void *stream_) {
     // (the 8-bit quantisation of the reference's ROCm back-end: any p > 0 gives a threshold <= 254, i.e. at least 1/256 of the
     //  elements are dropped however small p is; the kept ones are scaled by 1 / (1 - p))
     kp.drop_thr = p->p_dropout > 0.f ? (int32_t)std::floor(255.0 * (1.0 - (double)p->p_dropout)) : 255;
-    kp.rp_dropout = p->p_dropout > 0.f ? 1.f / (1.f - p->p_dropout) : 1.f;
+    kp.rp_dropout = rp_dropout(p);
     kp.rng_state = p->rng_state;
     const bool sdmask_signed = (p->flags & FA_FLAG_SDMASK_SIGNED) && p->s_dmask;
     kp.s_dmask = sdmask_signed ? nullptr : p->s_dmask;
@@ -1158,27 +1173,9 @@ int fa_fwd(const fa_fwd_params *p, void *stream_) {
         kp.scale_log2 = p->softmax_scale * kLog2e;
     }
 
-    if (native8) {  // e4m3 operands straight into the block-scaled MFMA (effective_variant() is 0 here: 256-row workgroups)
-        constexpr int smem = fa::smem_bytes_fp8();
-        static std::atomic<uint64_t> attr_set{0};
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        const uint64_t bit = uint64_t(1) << (dev & 63);
-        if (!(attr_set.load(std::memory_order_acquire) & bit)) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void *>(fa::fwd_kernel_fp8), hipFuncAttributeMaxDynamicSharedMemorySize, smem) != hipSuccess) {
-                (void)hipGetLastError();
-                return FA_ERR_LAUNCH;
-            }
-            attr_set.fetch_or(bit, std::memory_order_release);
-        }
-        hipLaunchKernelGGL(fa::fwd_kernel_fp8, dim3(kp.grid), dim3(256), smem, stream, kp);
-        return hipGetLastError() == hipSuccess ? FA_OK : FA_ERR_LAUNCH;
-    }
     const bool bf16 = p->dtype == FA_DTYPE_BF16 || fp8;  // fp8: out is bf16
-    const int st_main = qv_kernel ? (bf16 ? launch_qv<__bf16>(p, kp, softcap, stream) : launch_qv<_Float16>(p, kp, softcap, stream))
-                        : bf16    ? dispatch_hdim<__bf16>(kp, softcap, variant, stream)
-                                  : dispatch_hdim<_Float16>(kp, softcap, variant, stream);
-    if (st_main == FA_OK && sdmask_signed && !nothing) {
+    const int st_main = bf16 ? launch_plan<__bf16>(pl, p, kp, stream) : launch_plan<_Float16>(pl, p, kp, stream);
+    if (st_main == FA_OK && sdmask_signed && !pl.nothing) {
         const int nrb = (p->seqlen_q + 7) / 8;
         const int64_t blocks = (int64_t)nrb * p->h * p->b;
         const int nblk = (p->seqlen_k + p->s_dmask_block_n - 1) / p->s_dmask_block_n;

@@ -221,6 +221,12 @@ int64_t fa_fwd_workspace_size(const fa_fwd_params *params);
 /* Validation only (what mha_fwd's TORCH_CHECKs do); no device access. */
 int fa_fwd_validate(const fa_fwd_params *params);
 
+/* Test hook: a short, stable text naming the forward plan of these params on a device of num_cus compute units -- the kernel,
+ * its template shape and forms, block_m, the split-KV count, the fp8 expansion and the 256-column calls of a wide V (e.g.
+ * "fwd_kernel_w64 D=128 DEFF=128 waves=4 PERSIST block_m=256 splits=1").  NULL when fa_fwd would reject the params.  No
+ * device access; the text lives in thread-local storage until the next call on the same thread. */
+const char *fa_fwd_plan_name(const fa_fwd_params *params, int32_t num_cus);
+
 /* Human-readable text for a status code (static storage). */
 const char *fa_strerror(int status);
 

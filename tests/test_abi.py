@@ -190,6 +190,7 @@ def test_fp8_native_switch_is_pinned_by_workspace_size(built_lib):
         return p
     size = lambda p: built_lib.fa_fwd_workspace_size(ctypes.byref(p))
     assert size(fp8(8192)) == 0                          # BASELINE config 5's shape: native
+    assert built_lib.fa_fwd_plan_name(ctypes.byref(fp8(8192)), 256).startswith(b"fwd_kernel_fp8 ")
     assert size(fp8(8192, d=64)) > 0                     # other head dims: expansion workspace
     assert size(fp8((1 << 31) // (32 * 128) - 1)) == 0   # last row still below 2 GiB
     big = fp8((1 << 31) // (32 * 128))                   # seqlen_k * k_row_stride == 2^31 bytes

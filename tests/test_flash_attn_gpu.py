@@ -97,7 +97,7 @@ def test_alibi(sq, sk, d, causal, per_batch):
     """ALiBi slopes (h) or (b, h), rand * 0.3 as tests/test_flash_attn.py:936-940; oracle bias from
     attn_bias_from_alibi_slopes (:29-56, restated in oracle/ and pinned to the reference by make_golden.py).  The long sweeps
     run the ALIBI form of the generated loop (FastLoop256<T, DEFF, false, true>: the 32-row-per-wave kernel shape at every head
-    dim, fa_fwd_api.hip variant 4 below 129), entered and left at the causal diagonal and the sequence tail."""
+    dim, chosen by plan_fwd in fa_fwd_api.hip below 129), entered and left at the causal diagonal and the sequence tail."""
     fa = _api()
     torch.manual_seed(11)
     b, h, hk = 2, 4, 2
@@ -318,7 +318,7 @@ def test_softcap_head_dim_tile_256(sq, sk, causal, window, d, dtype):
     interleaved tanh chains per score pair) and hands already-capped scores to the generic half-step on a guard trip; scores
     pushed into the tanh knee like hopper/test_flash_attn.py:139-140; rtol 3 with softcap (:194).  LSE included.  One case
     per shape also spikes a key late in the sweep so that the guard trips inside a capped block.  Head dims <= 128 with softcap
-    take the same kernel shape (DEFF = 64 / 96 / 128 instantiations, fa_fwd_api.hip variant 4; short causal sweeps at head dim
+    take the same kernel shape (DEFF = 64 / 96 / 128 instantiations, chosen by plan_fwd in fa_fwd_api.hip; short causal sweeps at head dim
     <= 64 keep the 4-wave x 32-row compiler-scheduled shape)."""
     fa = _api()
     torch.manual_seed(sq + sk + d)

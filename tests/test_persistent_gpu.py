@@ -3,6 +3,8 @@ workgroup per CU walks a chain of work items; the look-ahead K / V stream of an 
 first tiles, its Q is prefetched into the Q image, O leaves straight from the accumulators.  Same arithmetic in the same
 order as the hand-over kernel: results must be BIT-identical to it, and inside the reference's bound against the oracle
 (tests/test_flash_attn.py:1121,1556).  Role in the reference: the persistent tile schedulers, hopper/tile_scheduler.hpp:140-363."""
+import ctypes
+
 import pytest
 import torch
 
@@ -101,6 +103,15 @@ def test_persistent_is_the_default_when_chains_exist():
     from flash_attention_annotated_amd import _lib
     lib = _lib.load()
     q, k, v = (torch.randn(32, 512, 16, 128, device=DEV, dtype=torch.bfloat16) for _ in range(3))
+    p = _lib.new_params()   # the same problem as fa_fwd_params: the plan on this device's CU count is the persistent form
+    for f in ("q", "k", "v", "o", "softmax_lse"):
+        setattr(p, f, q.data_ptr())
+    p.b, p.seqlen_q, p.seqlen_k, p.h, p.h_k, p.d, p.dtype = 32, 512, 512, 16, 16, 128, _lib.FA_DTYPE_BF16
+    for t_ in "qkvo":
+        setattr(p, f"{t_}_batch_stride", q.stride(0)); setattr(p, f"{t_}_row_stride", q.stride(1)); setattr(p, f"{t_}_head_stride", q.stride(2))
+    p.softmax_scale, p.is_causal, p.window_size_left, p.window_size_right = 128 ** -0.5, 1, -1, -1
+    cus = torch.cuda.get_device_properties(DEV).multi_processor_count
+    assert b" PERSIST " in lib.fa_fwd_plan_name(ctypes.byref(p), cus)
 
     def t():
         for _ in range(5):

@@ -402,7 +402,7 @@ def main():
     global DEFF, KSTEPS, NSTEP, SOFTCAP, ALIBI
     for softcap, alibi in ((False, False), (True, False), (False, True)):
         SOFTCAP, ALIBI = softcap, alibi
-        # (DEFF <= 128 exists for softcap / ALiBi only: head dims <= 128 with one of them run this kernel shape, fa_fwd_api.hip variant 4)
+        # (DEFF <= 128 exists for softcap / ALiBi only: head dims <= 128 with one of them run this kernel shape, plan_fwd in fa_fwd_api.hip)
         for deff in ((256, 192, 160, 128, 96, 64) if (softcap or alibi) else (256, 192, 160)):
             DEFF, KSTEPS, NSTEP = deff, deff // 16, 2 * (deff // 32)
             for T, mf, cvt in (("__bf16", "v_mfma_f32_32x32x16_bf16", cvt_bf16), ("_Float16", "v_mfma_f32_32x32x16_f16", cvt_f16)):
