@@ -1,4 +1,7 @@
-"""ctypes binding of the C-ABI in include/fa_fwd.h and include/fa_bwd.h (libfa_fwd_gfx950.so).
+"""Build and loading of the native code: libfa_fwd_gfx950.so (the C-ABI of include/fa_fwd.h and include/fa_bwd.h) and
+the compiled host module flash_attn_2_cuda_C (csrc/torch_binding.cpp), which is the only host path of both operator
+surfaces.  Python launches nothing through ctypes: the struct mirrors below serve the ABI tests, `bench.py --variant`
+and the developer tools, which call the C-ABI directly.
 
 The shared library is the product: there is no Python/CPU fallback.  If it is
 missing or the GPU is absent, every compute entry point raises.
@@ -266,7 +269,9 @@ def load():
         raise RuntimeError(
             f"{LIB_NAME} is not built: run `python -c 'import __graft_entry__ as g; g.build()'` "
             f"(expected at {LIB_PATH}); there is no CPU fallback")
-    lib = ctypes.CDLL(os.environ.get("FA_FWD_LIB", LIB_PATH))  # FA_FWD_LIB: developer override (ablation builds)
+    # FA_FWD_LIB: developer override (ablation / instrumented builds).  RTLD_GLOBAL: the binding, imported after this by
+    # binding(), resolves its fa_* references to this instance
+    lib = ctypes.CDLL(os.environ.get("FA_FWD_LIB", LIB_PATH), mode=ctypes.RTLD_GLOBAL)
     lib.fa_fwd.argtypes = [ctypes.POINTER(FaFwdParams), ctypes.c_void_p]
     lib.fa_fwd.restype = ctypes.c_int
     lib.fa_fwd_validate.argtypes = [ctypes.POINTER(FaFwdParams)]
@@ -324,6 +329,26 @@ def load():
         lib.fa_set_persist_mode(int(os.environ["FA_FWD_PERSIST"]))
     _lib = lib
     return lib
+
+
+_binding = None
+
+
+def binding():
+    """The compiled host module, imported after load(): the ABI / struct-layout checks and the FA_FWD_* overrides apply to
+    the library instance every compiled call goes to.  A binding that does not load raises ImportError: there is no other
+    host path."""
+    global _binding
+    if _binding is None:
+        try:
+            load()
+            from . import flash_attn_2_cuda_C
+        except (ImportError, RuntimeError) as e:
+            raise ImportError(
+                f"flash_attn_2_cuda_C is not built or does not load ({e}): run `python -c 'import __graft_entry__ as g; "
+                f"g.build()'` (expected at {binding_path()}); there is no CPU fallback") from e
+        _binding = flash_attn_2_cuda_C
+    return _binding
 
 
 def strerror(status):

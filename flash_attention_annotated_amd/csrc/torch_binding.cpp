@@ -1,17 +1,23 @@
-// torch_binding.cpp — compiled `flash_attn_2_cuda` surface over the C-ABI (include/fa_fwd.h, include/fa_bwd.h).
+// torch_binding.cpp — compiled `flash_attn_2_cuda` and `flash_attn_3_cuda` surfaces over the C-ABI (include/fa_fwd.h,
+// include/fa_bwd.h).
 //
 // The pybind module of csrc/flash_attn/flash_api.cpp:1478-1485: fwd / varlen_fwd / bwd / varlen_bwd / fwd_kvcache with the
 // reference's positional argument lists, doing the host work of mha_fwd (:350-512), mha_varlen_fwd (:514-755), mha_bwd
 // (:767-971), mha_varlen_bwd (:973-1200) and mha_fwd_kvcache (:1202-1476) -- TORCH_CHECKs with the reference's texts, output /
-// LSE / softmax_d allocation, the params struct -- and enqueueing the gfx950 kernels on torch's current stream.  Host code
-// only: built by plain g++ against the torch headers (no hipify, no device code here), linked to libfa_fwd_gfx950.so.
-// This is the only host path of the FA2 entry points: flash_attn_2_cuda.py re-exports these functions as they are.
+// LSE / softmax_d allocation, the params struct -- and enqueueing the gfx950 kernels on torch's current stream.  Beside them
+// the FA3 operators of hopper/flash_api.cpp: fa3_fwd (mha_fwd, :672-1198), fa3_bwd (mha_bwd, :1259-1570) and
+// fa3_fwd_combine (mha_combine, :1569-1670).  Host code only: built by plain g++ against the torch headers (no hipify, no
+// device code here), linked to libfa_fwd_gfx950.so.  This is the only host path of both surfaces: flash_attn_2_cuda.py and
+// flash_attn_3_cuda.py re-export these functions as they are, flash_attn_3_ops.py registers them under the FA3 op schemas.
 #include <torch/extension.h>
 #include <ATen/hip/impl/HIPGuardImplMasqueradingAsCUDA.h>
 #include <ATen/hip/impl/HIPStreamMasqueradingAsCUDA.h>
 
+#include <algorithm>
 #include <cmath>
 #include <limits>
+#include <string>
+#include <tuple>
 #include <vector>
 
 #include "fa_bwd.h"
@@ -22,8 +28,6 @@ namespace {
 using at::Tensor;
 using OptTensor = c10::optional<at::Tensor>;
 
-thread_local bool g_fa3_window = false;  // FA3 window rule for bwd / varlen_bwd (flash_attn_3_ops._bwd)
-
 #define CHECK_DEVICE(x, name) TORCH_CHECK((x).is_cuda(), name " must be on CUDA")
 #define CHECK_SHAPE(x, name, ...) \
     TORCH_CHECK((x).sizes() == c10::IntArrayRef({__VA_ARGS__}), name " must have shape (" #__VA_ARGS__ ")")
@@ -32,13 +36,15 @@ thread_local bool g_fa3_window = false;  // FA3 window rule for bwd / varlen_bwd
 int dtype_code(const Tensor &t) {
     if (t.scalar_type() == at::kHalf) return FA_DTYPE_FP16;
     if (t.scalar_type() == at::kBFloat16) return FA_DTYPE_BF16;
+    if (t.scalar_type() == at::kFloat8_e4m3fn) return FA_DTYPE_FP8_E4M3;
     TORCH_CHECK(false, "FlashAttention only support fp16 and bf16 data type");
     return -1;
 }
 
-// the kernels move 16-byte vectors: bases and the non-unit strides must keep rows aligned (views that do not are copied)
+// the kernels move 16-byte vectors (the fp8 expansion pass 8-byte ones): bases and the non-unit strides must keep rows
+// aligned (views that do not are copied)
 bool aligned(const Tensor &t) {
-    if (reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 != 0) return false;
+    if (reinterpret_cast<uintptr_t>(t.data_ptr()) % (t.element_size() == 2 ? 16 : 8) != 0) return false;
     for (int64_t i = 0; i + 1 < t.dim(); ++i)
         if (t.stride(i) % 8 != 0) return false;
     return true;
@@ -115,6 +121,10 @@ struct FwdArgs {
     int64_t window_left = -1, window_right = -1;
     OptTensor cu_seqlens_q, cu_seqlens_k, seqused_k, alibi, kv_batch_idx, block_table, leftpad_k, rng_state, s_dmask, qv;
     int num_splits = 1, s_dmask_block_n = 0;
+    // FA3 only (the FA2 entry points leave them unset): per-(batch, kv head) fp8 descales, the FA3 window rule
+    OptTensor seqused_q, q_descale, k_descale, v_descale;
+    bool fa3_window = false;
+    int64_t attention_chunk = 0;
 };
 
 // torch tensors -> fa_fwd_params -> fa_fwd on torch's current stream (q/k/v/out: last stride 1, aligned())
@@ -149,11 +159,20 @@ void launch_fwd(const Tensor &q, const Tensor &k, const Tensor &v, const Tensor 
     p.dtype = dtype_code(q);
     p.cu_seqlens_q = static_cast<const int32_t *>(ptr(a.cu_seqlens_q));
     p.cu_seqlens_k = static_cast<const int32_t *>(ptr(a.cu_seqlens_k));
+    p.seqused_q = static_cast<const int32_t *>(ptr(a.seqused_q));
     p.seqused_k = static_cast<const int32_t *>(ptr(a.seqused_k));
     p.softmax_scale = (float)a.softmax_scale;
     p.softcap = (float)a.softcap;
     p.is_causal = a.causal ? 1 : 0;
     p.window_size_left = (int32_t)a.window_left; p.window_size_right = (int32_t)a.window_right;
+#define FA_SET_DESCALE(name)                                                                                \
+    if (a.name##_descale.has_value()) {  /* (b, h_k) fp32 */                                               \
+        p.name##_descale = static_cast<const float *>(a.name##_descale->data_ptr());                       \
+        p.name##_descale_batch_stride = a.name##_descale->stride(0);                                       \
+        p.name##_descale_head_stride = a.name##_descale->stride(1);                                        \
+    }
+    FA_SET_DESCALE(q) FA_SET_DESCALE(k) FA_SET_DESCALE(v)
+#undef FA_SET_DESCALE
     if (a.alibi.has_value()) {  // (h) or (b, h) fp32
         p.alibi_slopes = static_cast<const float *>(a.alibi->data_ptr());
         p.alibi_slopes_batch_stride = a.alibi->dim() == 2 ? a.alibi->stride(0) : 0;
@@ -163,7 +182,7 @@ void launch_fwd(const Tensor &q, const Tensor &k, const Tensor &v, const Tensor 
     p.p_dropout = (float)a.p_dropout;
     p.rng_state = static_cast<const uint64_t *>(ptr(a.rng_state));
     p.s_dmask = static_cast<uint8_t *>(ptr(a.s_dmask));
-    p.flags = 0;
+    p.flags = a.fa3_window ? FA_FLAG_FA3_WINDOW : 0;  // a missing window side is unbounded (hopper/flash_api.cpp:152-153)
     if (a.s_dmask.has_value() && a.s_dmask_block_n > 0) {
         p.flags |= FA_FLAG_SDMASK_SIGNED;
         p.s_dmask_rows = (int32_t)a.s_dmask->size(-2);
@@ -171,10 +190,12 @@ void launch_fwd(const Tensor &q, const Tensor &k, const Tensor &v, const Tensor 
         p.s_dmask_block_n = a.s_dmask_block_n;
     }
     p.num_splits = a.num_splits;
-    if (v.size(-1) != q.size(-1)) p.d_v = (int32_t)v.size(-1);  // FA3 headdim_v (q/k <= 64 beside v in [256, 512] here)
-    if (a.qv.has_value()) {  // FA3 qv, dense (b, s, h, d_v) like q (ABI v13)
+    p.attention_chunk = (int32_t)a.attention_chunk;
+    if (v.size(-1) != q.size(-1)) p.d_v = (int32_t)v.size(-1);  // FA3 headdim_v (ABI v12)
+    if (a.qv.has_value()) {  // FA3 qv, laid out like q with V's head dim (ABI v13)
         p.qv = a.qv->data_ptr();
-        p.qv_batch_stride = a.qv->stride(0); p.qv_row_stride = a.qv->stride(1); p.qv_head_stride = a.qv->stride(2);
+        p.qv_batch_stride = a.varlen ? 0 : a.qv->stride(0);
+        p.qv_row_stride = a.qv->stride(-3); p.qv_head_stride = a.qv->stride(-2);
     }
     if (paged) {
         p.block_table = static_cast<const int32_t *>(a.block_table->data_ptr());
@@ -184,7 +205,7 @@ void launch_fwd(const Tensor &q, const Tensor &k, const Tensor &v, const Tensor 
     Tensor workspace;
     const int64_t need = fa_fwd_workspace_size(&p);
     TORCH_CHECK(need >= 0, "fa_fwd_workspace_size failed (", need, "): ", fa_strerror((int)need));
-    if (need > 0) {  // split-KV partials: scratch from torch's caching allocator (the callee never allocates)
+    if (need > 0) {  // fp8 expansion / split-KV partials: scratch from torch's caching allocator (the callee never allocates)
         workspace = at::empty({need + 256}, q.options().dtype(at::kByte));
         const uintptr_t base = (reinterpret_cast<uintptr_t>(workspace.data_ptr()) + 255) / 256 * 256;
         p.workspace = reinterpret_cast<void *>(base);
@@ -370,6 +391,7 @@ struct BwdArgs {
     bool causal = false, deterministic = false;
     int64_t window_left = -1, window_right = -1;
     OptTensor cu_seqlens_q, cu_seqlens_k, alibi, rng_state;
+    bool fa3_window = false;  // the window rule of the FA3 surface (fa3_bwd)
 };
 
 void launch_bwd(const Tensor &dout, const Tensor &q, const Tensor &k, const Tensor &v, const Tensor &out, const Tensor &lse,
@@ -395,6 +417,7 @@ void launch_bwd(const Tensor &dout, const Tensor &q, const Tensor &k, const Tens
     } else {
         p.h = (int32_t)q.size(2); p.h_k = (int32_t)k.size(2); p.d = (int32_t)q.size(3);
     }
+    if (v.size(-1) != q.size(-1)) p.d_v = (int32_t)v.size(-1);  // FA3 headdim_v (ABI v12)
     p.softmax_d_row_len = softmax_d.size(-1);
     p.b = (int32_t)a.batch; p.seqlen_q = (int32_t)a.max_seqlen_q; p.seqlen_k = (int32_t)a.max_seqlen_k;
     p.dtype = dtype_code(q);
@@ -407,12 +430,40 @@ void launch_bwd(const Tensor &dout, const Tensor &q, const Tensor &k, const Tens
         p.alibi_slopes = static_cast<const float *>(a.alibi->data_ptr());
         p.alibi_slopes_batch_stride = a.alibi->dim() == 2 ? a.alibi->stride(0) : 0;
     }
-    p.flags = g_fa3_window ? FA_FLAG_FA3_WINDOW : 0;
+    p.flags = a.fa3_window ? FA_FLAG_FA3_WINDOW : 0;
     p.deterministic = a.deterministic ? 1 : 0;
     p.p_dropout = (float)a.p_dropout;
     p.rng_state = static_cast<const uint64_t *>(ptr(a.rng_state));
     const int st = fa_bwd(&p, current_stream(q));
     TORCH_CHECK(st == 0, "fa_bwd failed (", st, "): ", fa_strerror(st));
+}
+
+// What every backward entry point does after its checks: softmax_d (b, h, seqlen_q rounded to 128) or, varlen,
+// (h, total_q + 128 b); aligned copies of the views that are not; the launch when `nonempty` (each entry point keeps its
+// own empty-input condition), zero gradients otherwise; the copy-back into the caller's gradients.
+std::vector<Tensor> run_bwd(const Tensor &dout, const Tensor &q, const Tensor &k, const Tensor &v, const Tensor &out,
+                            const Tensor &softmax_lse, const Tensor &dq, const Tensor &dk, const Tensor &dv, const BwdArgs &a,
+                            bool nonempty, bool zero_tensors = false) {
+    c10::hip::HIPGuardMasqueradingAsCUDA device_guard(q.device());
+    const int64_t num_heads = q.size(-2);
+    Tensor softmax_d = a.varlen ? at::empty({num_heads, q.size(0) + 128 * a.batch}, q.options().dtype(at::kFloat))
+                                : at::empty({a.batch, num_heads, round128(a.max_seqlen_q)}, q.options().dtype(at::kFloat));
+    if (zero_tensors) { dq.zero_(); dk.zero_(); dv.zero_(); softmax_d.zero_(); }
+    if (nonempty) {
+        const Tensor doc = aligned_or_copy(dout), qc = aligned_or_copy(q), kc = aligned_or_copy(k), vc = aligned_or_copy(v),
+                     oc = aligned_or_copy(out);
+        Tensor dqc = aligned(dq) ? dq : at::empty_like(dq, at::MemoryFormat::Contiguous);
+        Tensor dkc = aligned(dk) ? dk : at::empty_like(dk, at::MemoryFormat::Contiguous);
+        Tensor dvc = aligned(dv) ? dv : at::empty_like(dv, at::MemoryFormat::Contiguous);
+        const Tensor lse = softmax_lse.is_contiguous() ? softmax_lse : softmax_lse.contiguous();
+        launch_bwd(doc, qc, kc, vc, oc, lse, dqc, dkc, dvc, softmax_d, a);
+        if (!dqc.is_same(dq)) dq.copy_(dqc);
+        if (!dkc.is_same(dk)) dk.copy_(dkc);
+        if (!dvc.is_same(dv)) dv.copy_(dvc);
+    } else {
+        dq.zero_(); dk.zero_(); dv.zero_(); softmax_d.zero_();  // (:953-958)
+    }
+    return {dq, dk, dv, softmax_d};
 }
 
 void bwd_common_checks(const Tensor &dout, const Tensor &q, const Tensor &k, const Tensor &v, const Tensor &out,
@@ -442,6 +493,8 @@ OptTensor bwd_rng_state(double p_dropout, c10::optional<at::Generator> &gen_, Op
     return rs;
 }
 
+// FA3 = true: the window rule of the FA3 surface (fa3_bwd); the bound `bwd` / `varlen_bwd` are the <false> instances
+template <bool FA3>
 std::vector<Tensor> mha_bwd(const Tensor &dout, const Tensor &q, const Tensor &k, const Tensor &v, const Tensor &out,
                             const Tensor &softmax_lse, OptTensor &dq_, OptTensor &dk_, OptTensor &dv_, OptTensor &alibi_slopes_,
                             const double p_dropout, const double softmax_scale, const bool is_causal, int64_t window_size_left,
@@ -466,29 +519,14 @@ std::vector<Tensor> mha_bwd(const Tensor &dout, const Tensor &q, const Tensor &k
     Tensor dq = grad_out(dq_, q, "dq", {batch_size, seqlen_q, num_heads, head_size});
     Tensor dk = grad_out(dk_, k, "dk", {batch_size, seqlen_k, num_heads_k, head_size});
     Tensor dv = grad_out(dv_, v, "dv", {batch_size, seqlen_k, num_heads_k, head_size});
-    c10::hip::HIPGuardMasqueradingAsCUDA device_guard(q.device());
-    Tensor softmax_d = at::empty({batch_size, num_heads, round128(seqlen_q)}, q.options().dtype(at::kFloat));
-    if (seqlen_q > 0 && seqlen_k > 0) {
-        const Tensor doc = aligned_or_copy(dout), qc = aligned_or_copy(q), kc = aligned_or_copy(k), vc = aligned_or_copy(v),
-                     oc = aligned_or_copy(out);
-        Tensor dqc = aligned(dq) ? dq : at::empty_like(dq, at::MemoryFormat::Contiguous);
-        Tensor dkc = aligned(dk) ? dk : at::empty_like(dk, at::MemoryFormat::Contiguous);
-        Tensor dvc = aligned(dv) ? dv : at::empty_like(dv, at::MemoryFormat::Contiguous);
-        const Tensor lse = softmax_lse.is_contiguous() ? softmax_lse : softmax_lse.contiguous();
-        BwdArgs a;
-        a.batch = batch_size; a.max_seqlen_q = seqlen_q; a.max_seqlen_k = seqlen_k; a.softmax_scale = softmax_scale;
-        a.causal = is_causal; a.window_left = window_size_left; a.window_right = window_size_right; a.softcap = softcap;
-        a.alibi = alibi; a.deterministic = deterministic; a.p_dropout = p_dropout; a.rng_state = rs;
-        launch_bwd(doc, qc, kc, vc, oc, lse, dqc, dkc, dvc, softmax_d, a);
-        if (!dqc.is_same(dq)) dq.copy_(dqc);
-        if (!dkc.is_same(dk)) dk.copy_(dkc);
-        if (!dvc.is_same(dv)) dv.copy_(dvc);
-    } else {
-        dq.zero_(); dk.zero_(); dv.zero_(); softmax_d.zero_();  // (:953-958)
-    }
-    return {dq, dk, dv, softmax_d};
+    BwdArgs a;
+    a.batch = batch_size; a.max_seqlen_q = seqlen_q; a.max_seqlen_k = seqlen_k; a.softmax_scale = softmax_scale;
+    a.causal = is_causal; a.window_left = window_size_left; a.window_right = window_size_right; a.softcap = softcap;
+    a.alibi = alibi; a.deterministic = deterministic; a.p_dropout = p_dropout; a.rng_state = rs; a.fa3_window = FA3;
+    return run_bwd(dout, q, k, v, out, softmax_lse, dq, dk, dv, a, seqlen_q > 0 && seqlen_k > 0);
 }
 
+template <bool FA3>
 std::vector<Tensor> mha_varlen_bwd(const Tensor &dout, const Tensor &q, const Tensor &k, const Tensor &v, const Tensor &out,
                                    const Tensor &softmax_lse, OptTensor &dq_, OptTensor &dk_, OptTensor &dv_,
                                    const Tensor &cu_seqlens_q, const Tensor &cu_seqlens_k, OptTensor &alibi_slopes_,
@@ -523,29 +561,12 @@ std::vector<Tensor> mha_varlen_bwd(const Tensor &dout, const Tensor &q, const Te
     Tensor dq = grad_out(dq_, q, "dq", {total_q, num_heads, head_size});
     Tensor dk = grad_out(dk_, k, "dk", {total_k, num_heads_k, head_size});
     Tensor dv = grad_out(dv_, v, "dv", {total_k, num_heads_k, head_size});
-    c10::hip::HIPGuardMasqueradingAsCUDA device_guard(q.device());
-    Tensor softmax_d = at::empty({num_heads, total_q + 128 * batch_size}, q.options().dtype(at::kFloat));
-    if (zero_tensors) { dq.zero_(); dk.zero_(); dv.zero_(); softmax_d.zero_(); }
-    if (max_seqlen_q > 0 && total_q > 0 && total_k > 0) {
-        const Tensor doc = aligned_or_copy(dout), qc = aligned_or_copy(q), kc = aligned_or_copy(k), vc = aligned_or_copy(v),
-                     oc = aligned_or_copy(out);
-        Tensor dqc = aligned(dq) ? dq : at::empty_like(dq, at::MemoryFormat::Contiguous);
-        Tensor dkc = aligned(dk) ? dk : at::empty_like(dk, at::MemoryFormat::Contiguous);
-        Tensor dvc = aligned(dv) ? dv : at::empty_like(dv, at::MemoryFormat::Contiguous);
-        const Tensor lse = softmax_lse.is_contiguous() ? softmax_lse : softmax_lse.contiguous();
-        BwdArgs a;
-        a.varlen = true; a.batch = batch_size; a.max_seqlen_q = max_seqlen_q; a.max_seqlen_k = max_seqlen_k;
-        a.softmax_scale = softmax_scale; a.causal = is_causal; a.window_left = window_size_left; a.window_right = window_size_right;
-        a.softcap = softcap; a.cu_seqlens_q = cu_seqlens_q; a.cu_seqlens_k = cu_seqlens_k; a.alibi = alibi;
-        a.deterministic = deterministic; a.p_dropout = p_dropout; a.rng_state = rs;
-        launch_bwd(doc, qc, kc, vc, oc, lse, dqc, dkc, dvc, softmax_d, a);
-        if (!dqc.is_same(dq)) dq.copy_(dqc);
-        if (!dkc.is_same(dk)) dk.copy_(dkc);
-        if (!dvc.is_same(dv)) dv.copy_(dvc);
-    } else {
-        dq.zero_(); dk.zero_(); dv.zero_(); softmax_d.zero_();
-    }
-    return {dq, dk, dv, softmax_d};
+    BwdArgs a;
+    a.varlen = true; a.batch = batch_size; a.max_seqlen_q = max_seqlen_q; a.max_seqlen_k = max_seqlen_k;
+    a.softmax_scale = softmax_scale; a.causal = is_causal; a.window_left = window_size_left; a.window_right = window_size_right;
+    a.softcap = softcap; a.cu_seqlens_q = cu_seqlens_q; a.cu_seqlens_k = cu_seqlens_k; a.alibi = alibi;
+    a.deterministic = deterministic; a.p_dropout = p_dropout; a.rng_state = rs; a.fa3_window = FA3;
+    return run_bwd(dout, q, k, v, out, softmax_lse, dq, dk, dv, a, max_seqlen_q > 0 && total_q > 0 && total_k > 0, zero_tensors);
 }
 
 void rotary_apply(const Tensor &src, const Tensor &dst, const Tensor &cos, const Tensor &sin, const Tensor &seqlen_offsets,
@@ -785,20 +806,312 @@ std::vector<Tensor> mha_fwd_kvcache(Tensor &q, const Tensor &kcache, const Tenso
                             softcap, is_rotary_interleaved, num_splits, 256, c10::nullopt, c10::nullopt);  // the reference's page rule (:1265)
 }
 
-bool set_fa3_window_rule(bool on) {
-    const bool prev = g_fa3_window;
-    g_fa3_window = on;
-    return prev;
+// a shape as Python prints a tuple: "(2, 128, 8, 512)", "(7,)"
+std::string tuple_str(c10::IntArrayRef s) {
+    std::string r = "(";
+    for (size_t i = 0; i < s.size(); ++i) r += (i ? ", " : "") + std::to_string(s[i]);
+    return r + (s.size() == 1 ? ",)" : ")");
+}
+
+// window normalisation of the FA3 entry points (hopper/flash_api.cpp:796-797, 1360-1361): a side that cannot mask anything
+// becomes -1 = unbounded and stays unbounded (FA_FLAG_FA3_WINDOW)
+void fa3_window(int64_t seqlen_q, int64_t seqlen_k, int64_t &left, int64_t &right) {
+    if (left >= seqlen_k - 1) left = -1;
+    if (right >= seqlen_q - 1) right = -1;
+}
+
+// flash_attn_3::fwd, hopper/flash_api.cpp:672-1198 (schema :1672-1707): the 34 positional arguments of
+// hopper/flash_attn_interface.py:66, returns (out, softmax_lse, None, None).
+// Built: fp16 / bf16 / fp8 e4m3 inputs (fp8 -> bf16 output, :859), per-(batch, kv head) q/k/v descales (:1115-1146), dense
+// and varlen (`cu_seqlens_*`, `seqused_*`), causal / sliding window / softcap / attention_chunk, GQA, a V head dim of its
+// own.  KV-cache arguments (dense q, 16-bit: k_new / v_new appended in place at seqused_k, page_table of any page size,
+// kv_batch_idx, leftpad_k, rotary) and plain decode over a cache go to fwd_kvcache_impl.  qv (MLA absorbed attention,
+// :1028-1048: scores = (q.k + qv.v) * scale, d <= 64 beside d_v in [256, 512], 16-bit) on every route.  Accepted and
+// rejected by message, like the reference does for compiled-out features (:1148-1165): cu_seqlens_k_new, qv of any other
+// shape or with fp8, KV-cache arguments together with cu_seqlens_q or fp8.  `scheduler_metadata`, `pack_gqa`, `sm_margin`
+// are performance hints and do not change results: ignored.
+std::tuple<Tensor, Tensor, OptTensor, OptTensor> fa3_fwd(
+        const Tensor &q, const Tensor &k, const Tensor &v, const OptTensor &k_new, const OptTensor &v_new, const OptTensor &qv,
+        const OptTensor &out_, const OptTensor &cu_seqlens_q, const OptTensor &cu_seqlens_k, const OptTensor &cu_seqlens_k_new,
+        const OptTensor &seqused_q, const OptTensor &seqused_k, c10::optional<int64_t> max_seqlen_q_,
+        c10::optional<int64_t> max_seqlen_k_, const OptTensor &page_table, const OptTensor &kv_batch_idx,
+        const OptTensor &leftpad_k, const OptTensor &rotary_cos, const OptTensor &rotary_sin, OptTensor seqlens_rotary,
+        const OptTensor &q_descale, const OptTensor &k_descale, const OptTensor &v_descale, c10::optional<double> softmax_scale_,
+        bool is_causal, int64_t window_size_left, int64_t window_size_right, c10::optional<int64_t> attention_chunk_,
+        double softcap, bool is_rotary_interleaved, const OptTensor & /*scheduler_metadata*/, int64_t num_splits,
+        c10::optional<bool> /*pack_gqa*/, int64_t /*sm_margin*/) {
+    const auto q_dtype = q.scalar_type();
+    const bool is_fp8 = q_dtype == at::kFloat8_e4m3fn;
+    TORCH_CHECK(q_dtype == at::kHalf || q_dtype == at::kBFloat16 || is_fp8,
+                "FlashAttention only supports fp16, bf16, and fp8_e4m3 data type");  // hopper/flash_api.cpp:714-722
+    TORCH_CHECK(k.scalar_type() == q_dtype, "query and key must have the same dtype");
+    TORCH_CHECK(v.scalar_type() == q_dtype, "query and value must have the same dtype");
+    CHECK_DEVICE(q, "q"); CHECK_LAST_CONTIGUOUS(q, "Input tensor must have contiguous last dimension");
+    CHECK_DEVICE(k, "k"); CHECK_LAST_CONTIGUOUS(k, "Input tensor must have contiguous last dimension");
+    CHECK_DEVICE(v, "v"); CHECK_LAST_CONTIGUOUS(v, "Input tensor must have contiguous last dimension");
+    TORCH_CHECK(!cu_seqlens_k_new.has_value(), "This flash attention build does not support cu_seqlens_k_new.");
+    const int64_t attention_chunk = attention_chunk_.value_or(0);
+    TORCH_CHECK(attention_chunk >= 0, "attention_chunk must be non-negative");
+    const int64_t head_size = q.size(-1), head_size_v = v.size(-1);  // :764
+    // MLA shape (:783-792, 1028-1048): q/k <= 64 beside a V head dim in [256, 512] -- the qv kernel's
+    const bool wide_v = head_size <= 64 && head_size_v >= 256 && head_size_v <= 512 && head_size_v % 8 == 0 && !is_fp8;
+    std::vector<int64_t> out_shape = q.sizes().vec();  // q's with V's head dim
+    out_shape.back() = head_size_v;
+    if (qv.has_value()) {
+        TORCH_CHECK(wide_v, "This flash attention build does not support qv here: q_v is only supported for head_size <= 64 "
+                            "and hdim_v >= 256 (<= 512), with fp16 / bf16 inputs");
+        TORCH_CHECK(qv->scalar_type() == q_dtype, "q_v must have the same dtype as query");
+        TORCH_CHECK(qv->is_cuda() && qv->device() == q.device(), "q_v must be on the same CUDA device as query");
+        CHECK_LAST_CONTIGUOUS(*qv, "q_v tensor must have contiguous last dimension");
+        TORCH_CHECK(qv->sizes() == c10::IntArrayRef(out_shape), "q_v must have shape ", tuple_str(out_shape));
+    }
+    if (head_size_v != head_size) {  // :782-792 (the "Only Hopper" line is the one check that does not carry over)
+        TORCH_CHECK((head_size > 128 && head_size <= 192 && head_size_v > 96 && head_size_v <= 128) ||
+                        (head_size <= 64 && head_size_v <= 512),
+                    "If V headdim is different from Q/K dim, we only support Q/K headdim in (128, 192] and V headdim in (96, 128], "
+                    "or (Q/K <= 64 and V <= 512).");
+        TORCH_CHECK(!is_fp8, "This flash attention build does not support a V headdim of its own with fp8 inputs.");
+        TORCH_CHECK(head_size_v % 8 == 0, "head_size_v should be a multiple of 8");  // :856
+    }
+    if (seqlens_rotary.has_value()) {  // :1074-1079; only read together with k_new + rotary (hopper/seqlen.h:89)
+        TORCH_CHECK(seqlens_rotary->is_cuda() && seqlens_rotary->is_contiguous(), "seqlens_rotary must be a contiguous CUDA tensor");
+        TORCH_CHECK(seqlens_rotary->scalar_type() == at::kInt, "seqlens_rotary must have dtype torch.int32");
+        TORCH_CHECK(seqlens_rotary->sizes() == c10::IntArrayRef({q.size(0)}), "seqlens_rotary must have shape (batch_size,)");
+        if (!k_new.has_value() || !rotary_cos.has_value()) seqlens_rotary = c10::nullopt;
+    }
+    const double default_scale = std::pow(double(head_size + (qv.has_value() ? head_size_v : 0)), -0.5);
+    if (k_new || v_new || page_table || kv_batch_idx || leftpad_k || rotary_cos || rotary_sin) {
+        // KV-cache step (:736-760, 935-1060): k / v are the cache, seqused_k its fill levels
+        TORCH_CHECK(!cu_seqlens_q && !cu_seqlens_k && !seqused_q,
+                    "This flash attention build does not support KV-cache arguments together with cu_seqlens / seqused_q.");
+        TORCH_CHECK(!is_fp8, "This flash attention build does not support KV-cache arguments with fp8 inputs.");
+        TORCH_CHECK(!attention_chunk && (head_size_v == head_size || wide_v),
+                    "This flash attention build does not support attention_chunk or a V headdim of its own with KV-cache "
+                    "arguments (except Q/K <= 64 beside V in [256, 512]).");
+        TORCH_CHECK(k_new.has_value() == v_new.has_value(), "k_new and v_new must be passed together");
+        TORCH_CHECK(rotary_cos.has_value() == rotary_sin.has_value(), "rotary_cos and rotary_sin must be passed together");
+        if (k_new || leftpad_k) TORCH_CHECK(seqused_k.has_value(), "seqused_k must be provided with k_new / leftpad_k");
+        auto r = fwd_kvcache_impl(q, k, v, k_new, v_new, seqused_k, rotary_cos, rotary_sin, kv_batch_idx, leftpad_k, page_table,
+                                  c10::nullopt, out_, softmax_scale_.value_or(default_scale), is_causal, window_size_left,
+                                  window_size_right, softcap, is_rotary_interleaved, num_splits, 1, seqlens_rotary, qv);
+        return {r[0], r[1], c10::nullopt, c10::nullopt};
+    }
+    if (!cu_seqlens_q && !cu_seqlens_k && !seqused_q && seqused_k && !is_fp8 && q.dim() == 4 && q.size(1) <= 128 &&
+        window_size_left < 0 && (window_size_right < 0 || is_causal) && !out_ && !attention_chunk &&
+        (head_size_v == head_size || wide_v)) {
+        // plain decode over a cache (flash_attn_with_kvcache(q, k_cache, v_cache, cache_seqlens=...)): the same routine as
+        // the append / paged calls, which brings the split-KV heuristic (num_splits = 0) and the (b, 1, h) -> (b, ngroups, h_k)
+        // GQA swap (:935-1060 runs them for every call with seqused_k)
+        auto r = fwd_kvcache_impl(q, k, v, c10::nullopt, c10::nullopt, seqused_k, c10::nullopt, c10::nullopt, c10::nullopt,
+                                  c10::nullopt, c10::nullopt, c10::nullopt, c10::nullopt, softmax_scale_.value_or(default_scale),
+                                  is_causal, -1, -1, softcap, false, num_splits, 1, c10::nullopt, qv);
+        return {r[0], r[1], c10::nullopt, c10::nullopt};
+    }
+    const bool varlen = cu_seqlens_q.has_value();
+    TORCH_CHECK(varlen == cu_seqlens_k.has_value(), "This flash attention build needs cu_seqlens_q and cu_seqlens_k together.");
+    int64_t batch_size, seqlen_q, seqlen_k, total_q, num_heads, num_heads_k;
+    if (varlen) {
+        TORCH_CHECK(cu_seqlens_q->scalar_type() == at::kInt && cu_seqlens_k->scalar_type() == at::kInt,
+                    "cu_seqlens must have dtype torch.int32");
+        TORCH_CHECK(cu_seqlens_q->is_contiguous() && cu_seqlens_k->is_contiguous(), "cu_seqlens must be contiguous");
+        TORCH_CHECK(max_seqlen_q_.has_value() && max_seqlen_k_.has_value(), "max_seqlen_q/k must be provided with cu_seqlens");
+        TORCH_CHECK(q.dim() == 3, "q must have shape (total_q, num_heads, head_size)");
+        total_q = q.size(0); num_heads = q.size(1); num_heads_k = k.size(1);
+        batch_size = cu_seqlens_q->numel() - 1;
+        seqlen_q = *max_seqlen_q_; seqlen_k = *max_seqlen_k_;
+    } else {
+        TORCH_CHECK(q.dim() == 4, "q must have shape (batch_size, seqlen_q, num_heads, head_size)");
+        batch_size = q.size(0); seqlen_q = q.size(1); num_heads = q.size(2);
+        seqlen_k = k.size(1); num_heads_k = k.size(2);
+        total_q = batch_size * seqlen_q;
+    }
+    TORCH_CHECK(batch_size > 0, "batch size must be positive");
+    // CHECK_SHAPE(k, ..., num_heads_k, head_size) / CHECK_SHAPE(v, ..., num_heads_k, head_size_v), :813-819
+    TORCH_CHECK(k.size(-1) == head_size, "k must have shape (..., ", num_heads_k, ", ", head_size, ")");
+    std::vector<int64_t> v_shape = k.sizes().vec();
+    v_shape.back() = head_size_v;
+    TORCH_CHECK(v.sizes() == c10::IntArrayRef(v_shape), "v must have shape ", tuple_str(v_shape));
+    TORCH_CHECK(head_size <= 256, "FlashAttention forward only supports head dimension at most 256");
+    TORCH_CHECK(head_size % (is_fp8 ? 16 : 8) == 0, "head_size should be a multiple of ", is_fp8 ? 16 : 8);  // :854-856
+    TORCH_CHECK(num_heads_k > 0 && num_heads % num_heads_k == 0,
+                "Number of heads in key/value must divide number of heads in query");
+    for (const auto &[t, name] : {std::make_pair(&seqused_q, "seqused_q"), std::make_pair(&seqused_k, "seqused_k")})
+        if (t->has_value())
+            TORCH_CHECK((*t)->scalar_type() == at::kInt && (*t)->is_contiguous() && (*t)->numel() == batch_size, name,
+                        " must be int32 of shape (batch_size,)");
+    for (const auto &[t, name] : {std::make_pair(&q_descale, "q_descale"), std::make_pair(&k_descale, "k_descale"),
+                                  std::make_pair(&v_descale, "v_descale")})
+        if (t->has_value()) {
+            TORCH_CHECK(is_fp8, name, " is only supported with fp8 inputs");
+            TORCH_CHECK((*t)->scalar_type() == at::kFloat && (*t)->sizes() == c10::IntArrayRef({batch_size, num_heads_k}), name,
+                        " must be fp32 (batch_size, num_heads_k)");
+        }
+    const double softmax_scale = softmax_scale_.value_or(default_scale);
+    fa3_window(seqlen_q, seqlen_k, window_size_left, window_size_right);  // :796-805
+    if (seqlen_q == 1 && window_size_left == -1 && window_size_right == -1 && attention_chunk == 0)
+        is_causal = false;  // causal=true is the same as causal=false in this case
+    if (is_causal) window_size_right = 0;
+    const auto out_dtype = is_fp8 ? at::kBFloat16 : q_dtype;  // :859
+    Tensor out;
+    if (out_.has_value()) {
+        out = *out_;
+        TORCH_CHECK(out.scalar_type() == out_dtype,
+                    is_fp8 ? "For FP8 input, output must have dtype BF16" : "Output must have the same dtype as inputs");
+        TORCH_CHECK(out.is_cuda() && out.stride(-1) == 1 && out.sizes() == c10::IntArrayRef(out_shape),
+                    "out must have shape (..., num_heads, head_size_v)");  // :866-870
+    } else {
+        out = at::empty(out_shape, q.options().dtype(out_dtype));  // :872-874
+    }
+    c10::hip::HIPGuardMasqueradingAsCUDA device_guard(q.device());
+    Tensor softmax_lse = varlen ? at::empty({num_heads, total_q}, q.options().dtype(at::kFloat))
+                                : at::empty({batch_size, num_heads, seqlen_q}, q.options().dtype(at::kFloat));
+    if (seqlen_k > 0 && total_q > 0 && seqlen_q > 0) {
+        const Tensor qc = aligned_or_copy(q), kc = aligned_or_copy(k), vc = aligned_or_copy(v);
+        Tensor oc = aligned(out) ? out : at::empty_like(out);
+        FwdArgs a;
+        a.varlen = varlen; a.batch = batch_size; a.max_seqlen_q = seqlen_q; a.max_seqlen_k = seqlen_k;
+        a.softmax_scale = softmax_scale; a.causal = is_causal; a.window_left = window_size_left; a.window_right = window_size_right;
+        a.softcap = softcap; a.cu_seqlens_q = cu_seqlens_q; a.cu_seqlens_k = cu_seqlens_k; a.seqused_q = seqused_q;
+        a.seqused_k = seqused_k; a.q_descale = q_descale; a.k_descale = k_descale; a.v_descale = v_descale;
+        a.fa3_window = true; a.attention_chunk = attention_chunk;
+        if (qv.has_value()) a.qv = aligned_or_copy(*qv);
+        a.num_splits = 1;  // no split-KV: the decode calls of the FA3 surface take the fwd_kvcache_impl routes above
+        launch_fwd(qc, kc, vc, oc, softmax_lse, a);
+        if (!oc.is_same(out)) out.copy_(oc);
+    } else if (total_q > 0) {
+        out.zero_();  // :1190-1194
+        softmax_lse.fill_(std::numeric_limits<float>::infinity());
+    }
+    return {out, softmax_lse, c10::nullopt, c10::nullopt};
+}
+
+// flash_attn_3::bwd, hopper/flash_api.cpp:1259-1570 (22 arguments of the schema), on the FA2-shaped backward of this build
+// (16-bit types).  Returns (dq, dk, dv, softmax_d) and four empty fp32 tensors (softmax_lse_log2, dq/dk/dv_accum: none here).
+std::vector<Tensor> fa3_bwd(const Tensor &dout, const Tensor &q, const Tensor &k, const Tensor &v, const Tensor &out,
+                            const Tensor &softmax_lse, OptTensor dq_, OptTensor dk_, OptTensor dv_, const OptTensor &cu_seqlens_q,
+                            const OptTensor &cu_seqlens_k, const OptTensor &seqused_q, const OptTensor &seqused_k,
+                            c10::optional<int64_t> max_seqlen_q, c10::optional<int64_t> max_seqlen_k,
+                            c10::optional<double> softmax_scale_, bool is_causal, int64_t window_size_left,
+                            int64_t window_size_right, double softcap, bool deterministic, int64_t /*sm_margin*/) {
+    TORCH_CHECK(!seqused_q && !seqused_k, "This flash attention build does not support seqused_q / seqused_k in the backward.");
+    const bool varlen = cu_seqlens_q.has_value();
+    const int64_t d = q.size(-1), d_v = v.size(-1);
+    const bool own_dv = d_v != d;
+    if (own_dv) {  // v / out / dout / dv carry head_size_v (:1345-1369, 1399-1412, 1462-1464); built for max(d, d_v) in (128, 256]
+        TORCH_CHECK(q.scalar_type() == at::kHalf || q.scalar_type() == at::kBFloat16,
+                    "FlashAttention only support fp16 and bf16 data type");
+        TORCH_CHECK(k.scalar_type() == q.scalar_type(), "query and key must have the same dtype");
+        TORCH_CHECK(v.scalar_type() == q.scalar_type(), "query and value must have the same dtype");
+        TORCH_CHECK(out.scalar_type() == q.scalar_type(), "query and out must have the same dtype");
+        TORCH_CHECK(dout.scalar_type() == q.scalar_type(), "query and dout must have the same dtype");
+        TORCH_CHECK(d % 8 == 0, "head_size should be a multiple of 8");
+        TORCH_CHECK(d_v % 8 == 0, "head_size_v should be a multiple of 8");
+        TORCH_CHECK(std::max(d, d_v) <= 256, "FlashAttention backward only supports head dimension at most 256");
+        TORCH_CHECK(std::max(d, d_v) > 128, "This flash attention build supports a V headdim different from the Q/K headdim in "
+                                            "the backward only when the larger of the two is above 128.");
+        TORCH_CHECK(k.size(-1) == d && v.sizes().slice(0, v.dim() - 1) == k.sizes().slice(0, k.dim() - 1),
+                    "k / v shapes do not match");
+        std::vector<int64_t> out_shape = q.sizes().vec();
+        out_shape.back() = d_v;
+        TORCH_CHECK(out.sizes() == c10::IntArrayRef(out_shape) && dout.sizes() == out.sizes(), "out / dout must be (..., head_size_v)");
+    }
+    const double softmax_scale = softmax_scale_.value_or(std::pow(double(d), -0.5));
+    if (varlen) TORCH_CHECK(max_seqlen_q && max_seqlen_k, "max_seqlen_q/k must be provided with cu_seqlens");
+    const int64_t sq_max = varlen ? *max_seqlen_q : q.size(1), sk_max = varlen ? *max_seqlen_k : k.size(1);
+    fa3_window(sq_max, sk_max, window_size_left, window_size_right);
+    if (is_causal) window_size_right = 0;
+    std::vector<Tensor> r;
+    if (!own_dv) {  // the FA2 entry points' checks and texts, with the FA3 window rule
+        OptTensor none;
+        if (varlen) {
+            TORCH_CHECK(cu_seqlens_k.has_value(), "This flash attention build needs cu_seqlens_q and cu_seqlens_k together.");
+            r = mha_varlen_bwd<true>(dout, q, k, v, out, softmax_lse, dq_, dk_, dv_, *cu_seqlens_q, *cu_seqlens_k, none, sq_max,
+                                     sk_max, 0.0, softmax_scale, false, is_causal, window_size_left, window_size_right, softcap,
+                                     deterministic, c10::nullopt, none);
+        } else {
+            r = mha_bwd<true>(dout, q, k, v, out, softmax_lse, dq_, dk_, dv_, none, 0.0, softmax_scale, is_causal,
+                              window_size_left, window_size_right, softcap, deterministic, c10::nullopt, none);
+        }
+    } else {
+        auto grad = [](const OptTensor &given, const Tensor &like, const char *name) {
+            if (!given.has_value()) return at::empty_like(like);
+            TORCH_CHECK(given->scalar_type() == like.scalar_type() && given->is_cuda() && given->stride(-1) == 1 &&
+                            given->sizes() == like.sizes(), name, " must have the dtype, device and shape of its tensor");
+            return *given;
+        };
+        const Tensor dq = grad(dq_, q, "dq"), dk = grad(dk_, k, "dk"), dv = grad(dv_, v, "dv");
+        CHECK_DEVICE(q, "q"); CHECK_DEVICE(k, "k"); CHECK_DEVICE(v, "v"); CHECK_DEVICE(out, "out"); CHECK_DEVICE(dout, "dout");
+        CHECK_DEVICE(softmax_lse, "softmax_lse");
+        BwdArgs a;
+        a.varlen = varlen; a.batch = varlen ? cu_seqlens_q->numel() - 1 : q.size(0); a.max_seqlen_q = sq_max;
+        a.max_seqlen_k = sk_max; a.softmax_scale = softmax_scale; a.causal = is_causal; a.window_left = window_size_left;
+        a.window_right = window_size_right; a.softcap = softcap; a.cu_seqlens_q = cu_seqlens_q; a.cu_seqlens_k = cu_seqlens_k;
+        a.deterministic = deterministic; a.fa3_window = true;
+        r = run_bwd(dout, q, k, v, out, softmax_lse, dq, dk, dv, a, q.numel() > 0 && k.numel() > 0);
+    }
+    for (int i = 0; i < 4; ++i) r.push_back(at::empty({0}, q.options().dtype(at::kFloat)));
+    return r;
+}
+
+// flash_attn_3::fwd_combine, hopper/flash_api.cpp:1569-1670: merge caller-held split-KV partials.  out_partial
+// (num_splits, b, seqlen, h, d) fp32, lse_partial (num_splits, b, seqlen, h) fp32 -> (out, softmax_lse (b, seqlen, h)).
+std::tuple<Tensor, Tensor> fa3_fwd_combine(const Tensor &out_partial, const Tensor &lse_partial, const OptTensor &out_,
+                                           c10::optional<at::ScalarType> out_dtype) {
+    TORCH_CHECK(out_partial.scalar_type() == at::kFloat, "Attention combine function only support fp32 data type");
+    TORCH_CHECK(lse_partial.scalar_type() == at::kFloat, "Attention combine function only support fp32 data type");
+    TORCH_CHECK(out_partial.is_cuda() && lse_partial.is_cuda(), "out_partial must be on CUDA");
+    CHECK_LAST_CONTIGUOUS(out_partial, "Input tensor must have contiguous last dimension");
+    TORCH_CHECK(lse_partial.stride(-2) == 1, "LSE tensor must be contiguous in the seqlen dimension");
+    TORCH_CHECK(out_partial.dim() == 5, "out_partial must have shape (num_splits, batch_size, seqlen, num_heads, head_size)");
+    const int64_t num_splits = out_partial.size(0), batch_size = out_partial.size(1), seqlen = out_partial.size(2),
+                  num_heads = out_partial.size(3), head_size = out_partial.size(4);
+    TORCH_CHECK(num_splits <= 256, "FlashAttention combine only supports num_splits at most 256");
+    CHECK_SHAPE(lse_partial, "lse_partial", num_splits, batch_size, seqlen, num_heads);
+    const auto out_type = out_dtype.value_or(out_partial.scalar_type());
+    TORCH_CHECK(out_type == at::kFloat || out_type == at::kHalf || out_type == at::kBFloat16,
+                "Output type must be FP32, FP16 or BF16");
+    Tensor out;
+    if (out_.has_value()) {
+        out = *out_;
+        TORCH_CHECK(out.scalar_type() == out_type, "out must have the requested output type");
+        CHECK_DEVICE(out, "out");
+        TORCH_CHECK(out.stride(-1) == 1, "Output tensor must have contiguous last dimension");
+        CHECK_SHAPE(out, "out", batch_size, seqlen, num_heads, head_size);
+    } else {
+        out = at::empty({batch_size, seqlen, num_heads, head_size}, out_partial.options().dtype(out_type));
+    }
+    c10::hip::HIPGuardMasqueradingAsCUDA device_guard(out_partial.device());
+    Tensor softmax_lse = at::empty({batch_size, num_heads, seqlen}, out_partial.options()).transpose(1, 2);  // (:1632)
+    if (seqlen > 0 && batch_size > 0) {
+        fa_combine_params p{};
+        p.abi_version = FA_ABI_VERSION;
+        p.struct_size = sizeof(fa_combine_params);
+        p.out_partial = static_cast<const float *>(out_partial.data_ptr());
+        p.lse_partial = static_cast<const float *>(lse_partial.data_ptr());
+        p.out = out.data_ptr(); p.softmax_lse = static_cast<float *>(softmax_lse.data_ptr());
+        p.op_split_stride = out_partial.stride(0); p.op_batch_stride = out_partial.stride(1);
+        p.op_row_stride = out_partial.stride(2); p.op_head_stride = out_partial.stride(3);
+        p.lp_split_stride = lse_partial.stride(0); p.lp_batch_stride = lse_partial.stride(1);
+        p.lp_row_stride = lse_partial.stride(2); p.lp_head_stride = lse_partial.stride(3);
+        p.o_batch_stride = out.stride(0); p.o_row_stride = out.stride(1); p.o_head_stride = out.stride(2);
+        p.lse_batch_stride = softmax_lse.stride(0); p.lse_row_stride = softmax_lse.stride(1); p.lse_head_stride = softmax_lse.stride(2);
+        p.num_splits = (int32_t)num_splits; p.b = (int32_t)batch_size; p.seqlen = (int32_t)seqlen; p.h = (int32_t)num_heads;
+        p.d = (int32_t)head_size;
+        p.out_dtype = out_type == at::kFloat ? FA_DTYPE_FP32 : dtype_code(out);
+        const int st = fa_fwd_combine(&p, current_stream(out));
+        TORCH_CHECK(st == 0, "fa_fwd_combine failed (", st, "): ", fa_strerror(st));
+    }
+    return {out, softmax_lse};
 }
 
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
-    m.doc() = "FlashAttention (MI355X / gfx950 native kernels behind the flash_attn_2_cuda surface)";
+    m.doc() = "FlashAttention (MI355X / gfx950 native kernels behind the flash_attn_2_cuda and flash_attn_3_cuda surfaces)";
     m.def("fwd", &mha_fwd, "Forward pass");
     m.def("varlen_fwd", &mha_varlen_fwd, "Forward pass (variable length)");
-    m.def("bwd", &mha_bwd, "Backward pass");
-    m.def("varlen_bwd", &mha_varlen_bwd, "Backward pass (variable length)");
+    m.def("bwd", &mha_bwd<false>, "Backward pass");
+    m.def("varlen_bwd", &mha_varlen_bwd<false>, "Backward pass (variable length)");
     m.def("fwd_kvcache", &mha_fwd_kvcache, "Forward pass, with KV-cache");
     m.def("_fwd_kvcache_impl", &fwd_kvcache_impl, "fwd_kvcache with the page-size rule of the calling surface (+ FA3 seqlens_rotary)",
           py::arg("q"), py::arg("kcache"), py::arg("vcache"), py::arg("k"), py::arg("v"), py::arg("seqlens_k"), py::arg("rotary_cos"),
@@ -806,5 +1119,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("out"), py::arg("softmax_scale"), py::arg("is_causal"), py::arg("window_size_left"), py::arg("window_size_right"),
           py::arg("softcap"), py::arg("is_rotary_interleaved"), py::arg("num_splits"), py::arg("page_multiple"),
           py::arg("seqlens_rotary") = py::none(), py::arg("qv") = py::none());
-    m.def("_set_fa3_window_rule", &set_fa3_window_rule, "FA3 window rule for the backward entry points (returns the previous value)");
+    m.def("fa3_fwd", &fa3_fwd, "FA3 forward pass (flash_attn_3::fwd)");
+    m.def("fa3_bwd", &fa3_bwd, "FA3 backward pass (flash_attn_3::bwd)");
+    m.def("fa3_fwd_combine", &fa3_fwd_combine, "FA3 merge of split-KV partials (flash_attn_3::fwd_combine)");
 }

@@ -52,6 +52,11 @@ def test_extension_module_is_the_compiled_binding():
         assert getattr(top_level_alias, name) is getattr(flash_attn_2_cuda, name) is getattr(compiled, name), name
         assert type(getattr(top_level_alias, name)).__name__ == "builtin_function_or_method", name
     assert flash_attn_2_cuda._fwd_kvcache_impl is compiled._fwd_kvcache_impl
+    # the FA3 forward (hopper/flash_api.cpp:672-705, 34 arguments) is the compiled function too
+    from flash_attention_annotated_amd import flash_attn_3_cuda
+    assert flash_attn_3_cuda.fwd is compiled.fa3_fwd
+    assert type(flash_attn_3_cuda.fwd).__name__ == "builtin_function_or_method"
+    assert arity(flash_attn_3_cuda.fwd) == 34
     assert [n for n, _ in _params(fa.flash_attn_with_kvcache)] == [
         "q", "k_cache", "v_cache", "k", "v", "rotary_cos", "rotary_sin", "cache_seqlens", "cache_batch_idx",
         "cache_leftpad", "block_table", "softmax_scale", "causal", "window_size", "softcap", "rotary_interleaved",
@@ -80,9 +85,31 @@ def test_no_cpu_fallback():
         lambda: flash_attn_2_cuda.fwd_kvcache(q, q, q, None, None, cache_seqlens, None, None, None, None, None, None, None,
                                               0.125, False, -1, -1, 0.0, False, 0),
     )
+    # the compiled FA3 entry points: forward (dense, varlen), backward (d_v == d, d_v != d), combine
+    from flash_attention_annotated_amd import _lib, flash_attn_3_cuda
+    binding = _lib.binding()
+
+    def fa3_fwd(q, k, v, cu_seqlens=None, max_seqlen=None):
+        return flash_attn_3_cuda.fwd(q, k, v, None, None, None, None, cu_seqlens, cu_seqlens, None, None, None, max_seqlen,
+                                     max_seqlen, None, None, None, None, None, None, None, None, None, None, False, -1, -1, 0,
+                                     0.0, False, None, 1, None, 0)
+
+    def fa3_bwd(q, k, v, out, lse, cu_seqlens=None, max_seqlen=None):
+        return binding.fa3_bwd(out, q, k, v, out, lse, None, None, None, cu_seqlens, cu_seqlens, None, None, max_seqlen,
+                               max_seqlen, None, False, -1, -1, 0.0, False, 0)
+    q192, v128 = torch.randn(1, 16, 2, 192, dtype=torch.bfloat16), torch.randn(1, 16, 2, 128, dtype=torch.bfloat16)
+    calls += (
+        lambda: fa3_fwd(q, q, q),
+        lambda: fa3_fwd(qv, qv, qv, cu, 16),
+        lambda: fa3_bwd(q, q, q, q, lse),
+        lambda: fa3_bwd(q192, q192, v128, v128, lse),
+        lambda: binding.fa3_fwd_combine(torch.randn(2, 1, 16, 2, 64), torch.randn(2, 1, 16, 2), None, None),
+    )
     for call in calls:
         with pytest.raises(RuntimeError, match="must be on CUDA"):
             call()
+    with pytest.raises(RuntimeError, match="FlashAttention only supports fp16, bf16, and fp8_e4m3 data type"):
+        fa3_fwd(q.float(), q.float(), q.float())
 
 
 def test_package_import_does_not_load_the_binding():
@@ -92,8 +119,39 @@ def test_package_import_does_not_load_the_binding():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     code = (f"import sys; sys.path.insert(0, {root!r}); import flash_attention_annotated_amd; "
+            "import flash_attention_annotated_amd.hopper_interface; "
             "assert 'flash_attention_annotated_amd.flash_attn_2_cuda_C' not in sys.modules")
     subprocess.run([sys.executable, "-c", code], check=True)
+
+
+def test_fa_fwd_lib_override_reaches_the_binding(tmp_path):
+    """FA_FWD_LIB (developer override: ablation / instrumented builds) names the library instance that every compiled call
+    resolves to.  In a child process: conftest.py refuses the variable in the test session itself."""
+    import shutil
+    import subprocess
+    import sys
+    from flash_attention_annotated_amd import _lib
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    copy = str(tmp_path / "libfa_override.so")
+    shutil.copyfile(_lib.LIB_PATH, copy)
+    code = (f"import sys, ctypes; sys.path.insert(0, {root!r})\n"
+            "from flash_attention_annotated_amd import flash_attn_2_cuda\n"
+            "flash_attn_2_cuda.fwd\n"
+            "class DlInfo(ctypes.Structure):\n"
+            "    _fields_ = [('dli_fname', ctypes.c_char_p), ('dli_fbase', ctypes.c_void_p), ('dli_sname', ctypes.c_char_p),\n"
+            "                ('dli_saddr', ctypes.c_void_p)]\n"
+            "libdl = ctypes.CDLL(None)\n"
+            "libdl.dlsym.restype = ctypes.c_void_p\n"
+            "libdl.dlsym.argtypes = [ctypes.c_void_p, ctypes.c_char_p]\n"
+            "libdl.dladdr.argtypes = [ctypes.c_void_p, ctypes.POINTER(DlInfo)]\n"
+            "addr = libdl.dlsym(None, b'fa_fwd')  # RTLD_DEFAULT\n"
+            "info = DlInfo()\n"
+            "assert addr and libdl.dladdr(addr, ctypes.byref(info)), 'fa_fwd is not resolvable'\n"
+            "print(info.dli_fname.decode())\n")
+    env = dict(os.environ, FA_FWD_LIB=copy)
+    r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr
+    assert os.path.realpath(r.stdout.strip().splitlines()[-1]) == os.path.realpath(copy), r.stdout
 
 
 def test_unpad_pad_roundtrip():
