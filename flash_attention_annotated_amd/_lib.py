@@ -28,6 +28,7 @@ EXPORTED_SYMBOLS = (
     "fa_fwd_validate",
     "fa_fwd_workspace_size",
     "fa_fwd_plan_name",
+    "fa_fwd_last_plan_name",
     "fa_strerror",
     "fa_fwd_params_size",
     "fa_abi_version",
@@ -280,6 +281,8 @@ def load():
     lib.fa_fwd_workspace_size.restype = ctypes.c_int64
     lib.fa_fwd_plan_name.argtypes = [ctypes.POINTER(FaFwdParams), ctypes.c_int32]
     lib.fa_fwd_plan_name.restype = ctypes.c_char_p
+    lib.fa_fwd_last_plan_name.argtypes = []
+    lib.fa_fwd_last_plan_name.restype = ctypes.c_char_p
     lib.fa_strerror.argtypes = [ctypes.c_int]
     lib.fa_strerror.restype = ctypes.c_char_p
     lib.fa_fwd_params_size.argtypes = []

@@ -594,6 +594,26 @@ FwdPlan plan_fwd(const fa_fwd_params *p, int num_cus) {
     return pl;
 }
 
+// the text of a plan (fa_fwd_plan_name, fa_fwd_last_plan_name); NULL for a plan whose grid does not fit
+const char *plan_text(const FwdPlan &pl, char (&name)[160]) {
+    if (pl.status != FA_OK) return nullptr;
+    static const char *const kernels[] = {"fwd_kernel_fp8 D=", "fwd_kernel_qv DVT=", "fwd_kernel_w64 D=", "fwd_kernel_d256 W=",
+                                          "fwd_kernel D="};
+    const bool by_width = pl.family == Family::qv || pl.family == Family::d256;
+    int n = snprintf(name, sizeof(name), "%s%d", kernels[static_cast<int>(pl.family)], by_width ? pl.deff : pl.d);
+    if (pl.family == Family::w64) n += snprintf(name + n, sizeof(name) - n, " DEFF=%d", pl.deff);
+    n += snprintf(name + n, sizeof(name) - n, " waves=%d%s%s%s%s%s block_m=%d splits=%d%s", pl.waves, pl.softcap ? " SOFTCAP" : "",
+                  pl.alibi ? " ALIBI" : "", pl.dropout ? " DROPOUT" : "", pl.extra ? " EXTRA" : "", pl.persist ? " PERSIST" : "",
+                  pl.block_m, pl.split.splits, pl.fp8_expand ? " fp8_expand" : "");
+    if (pl.cols > 1) snprintf(name + n, sizeof(name) - n, " cols=%d", pl.cols);
+    return name;
+}
+
+// the plan the calling thread's most recent fa_fwd launched (fa_fwd_last_plan_name): a struct copy on the call path, the text
+// is made when asked
+thread_local FwdPlan t_last_plan;
+thread_local bool t_last_plan_set = false;
+
 // compute units of the current device (cached per device ordinal)
 int device_cus() {
     static std::atomic<int> cus[64];
@@ -1025,28 +1045,25 @@ int fa_fwd_validate(const fa_fwd_params *p) {
 
 const char *fa_fwd_plan_name(const fa_fwd_params *p, int32_t num_cus) {
     if (fa_fwd_validate(p) != FA_OK) return nullptr;
-    const FwdPlan pl = plan_fwd(p, num_cus);
-    if (pl.status != FA_OK) return nullptr;
-    static const char *const kernels[] = {"fwd_kernel_fp8 D=", "fwd_kernel_qv DVT=", "fwd_kernel_w64 D=", "fwd_kernel_d256 W=",
-                                          "fwd_kernel D="};
-    const bool by_width = pl.family == Family::qv || pl.family == Family::d256;
     thread_local char name[160];
-    int n = snprintf(name, sizeof(name), "%s%d", kernels[static_cast<int>(pl.family)], by_width ? pl.deff : pl.d);
-    if (pl.family == Family::w64) n += snprintf(name + n, sizeof(name) - n, " DEFF=%d", pl.deff);
-    n += snprintf(name + n, sizeof(name) - n, " waves=%d%s%s%s%s%s block_m=%d splits=%d%s", pl.waves, pl.softcap ? " SOFTCAP" : "",
-                  pl.alibi ? " ALIBI" : "", pl.dropout ? " DROPOUT" : "", pl.extra ? " EXTRA" : "", pl.persist ? " PERSIST" : "",
-                  pl.block_m, pl.split.splits, pl.fp8_expand ? " fp8_expand" : "");
-    if (pl.cols > 1) snprintf(name + n, sizeof(name) - n, " cols=%d", pl.cols);
-    return name;
+    return plan_text(plan_fwd(p, num_cus), name);
+}
+
+const char *fa_fwd_last_plan_name(void) {
+    thread_local char name[160];
+    return t_last_plan_set ? plan_text(t_last_plan, name) : nullptr;
 }
 
 int fa_fwd(const fa_fwd_params *p, void *stream_) {
     const int st = fa_fwd_validate(p);
+    t_last_plan_set = false;
     if (st != FA_OK) return st;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
 
     const int num_cus = device_cus();
     const FwdPlan pl = plan_fwd(p, num_cus);
+    t_last_plan = pl;
+    t_last_plan_set = true;
     if (pl.cols > 1) {
         // one call per 256 columns of V and O -- the scores are formed again for each (d <= 64: a small part of the work), the LSE
         // is written by every call with the same value.  Strides are untouched: the calls differ in the V / O column offset only.
@@ -1058,6 +1075,8 @@ int fa_fwd(const fa_fwd_params *p, void *stream_) {
             const int st_part = fa_fwd(&part, stream_);
             if (st_part != FA_OK) return st_part;
         }
+        t_last_plan = pl;  // (the outer plan, "... cols=2": the parts recorded theirs)
+        t_last_plan_set = true;
         return FA_OK;
     }
 

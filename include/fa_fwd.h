@@ -227,6 +227,13 @@ int fa_fwd_validate(const fa_fwd_params *params);
  * device access; the text lives in thread-local storage until the next call on the same thread. */
 const char *fa_fwd_plan_name(const fa_fwd_params *params, int32_t num_cus);
 
+/* Test hook: the name of the plan the calling thread's most recent fa_fwd() launched (same text as fa_fwd_plan_name on that
+ * call's params and the device's CU count; for a wide V run as several 256-column calls, the outer "... cols=N" plan).  NULL
+ * before the first call or when that call failed validation; unspecified after a call that returned any other error (a failed
+ * 256-column part leaves that part's plan).  fa_fwd keeps a struct copy; the text is made here, in
+ * thread-local storage of its own, valid until the next call on the same thread. */
+const char *fa_fwd_last_plan_name(void);
+
 /* Human-readable text for a status code (static storage). */
 const char *fa_strerror(int status);
 

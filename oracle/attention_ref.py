@@ -105,12 +105,14 @@ def apply_rotary_emb_ref(x, cos, sin, seqlen_offsets, interleaved=False, per_row
 def attention_ref(q, k, v, query_padding_mask=None, key_padding_mask=None, attn_bias=None, causal=False,
                   window_size=(-1, -1), softcap=0.0, upcast=True, reorder_ops=False, return_lse=False,
                   q_descale=None, k_descale=None, v_descale=None, intermediate_dtype=None, key_leftpad=None, dropout_p=0.0, dropout_mask=None,
-                  attention_chunk=0):
+                  attention_chunk=0, qv=None):
     """Exact softmax attention.
 
     q: (b, sq, h, d); k: (b, sk, h_k, d), v: (b, sk, h_k, dv) with h % h_k == 0 (kv head = q head // (h/h_k)); dv may differ
     from d (FA3 headdim_v, hopper/test_util.py:245-246): out is (b, sq, h, dv).  attention_chunk > 0: chunk_mask() on top of the
-    window mask (hopper/test_util.py:310-320).
+    window mask (hopper/test_util.py:310-320).  qv (b, sq, h, dv): the FA3 second query (MLA absorbed attention): the scores
+    gain (qv * scale) @ v^T and the default scale becomes 1 / sqrt(d + dv) (hopper/test_util.py:287-293; the qv term is scaled on
+    the query side in both operation orders, as there).
     upcast=True  -> everything in fp32 ("out_ref" of the reference's tests);
     upcast=False, reorder_ops=True -> same math in the input precision with k scaled instead of q
     ("out_pt", the yardstick of the tolerance contract, tests/test_flash_attn.py:1121).
@@ -123,6 +125,7 @@ def attention_ref(q, k, v, query_padding_mask=None, key_padding_mask=None, attn_
     dtype_og = q.dtype
     if upcast:
         q, k, v = q.float(), k.float(), v.float()
+        qv = qv.float() if qv is not None else None
     # fp8 descales, per (batch, kv head): hopper/test_util.py:272-279
     if q_descale is not None:
         q = (q.float() * q_descale.repeat_interleave(q.shape[2] // k.shape[2], dim=1)[:, None, :, None]).to(q.dtype)
@@ -135,10 +138,13 @@ def attention_ref(q, k, v, query_padding_mask=None, key_padding_mask=None, attn_
     g = h // k.shape[2]
     k = k.repeat_interleave(g, dim=2)
     v = v.repeat_interleave(g, dim=2)
+    d_scale = d if qv is None else d + v.shape[-1]
     if not reorder_ops:
-        scores = torch.einsum("bthd,bshd->bhts", q / math.sqrt(d), k)
+        scores = torch.einsum("bthd,bshd->bhts", q / math.sqrt(d_scale), k)
     else:
-        scores = torch.einsum("bthd,bshd->bhts", q, k / math.sqrt(d))
+        scores = torch.einsum("bthd,bshd->bhts", q, k / math.sqrt(d_scale))
+    if qv is not None:
+        scores = scores + torch.einsum("bthd,bshd->bhts", qv / math.sqrt(d_scale), v)
     if softcap > 0:
         scores = torch.tanh(scores / softcap) * softcap
     if key_padding_mask is not None:

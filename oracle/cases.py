@@ -84,6 +84,19 @@ FA3_CASES = {
 }
 
 
+# The FA3 `qv` argument (MLA absorbed attention: scores += (qv * scale) @ v^T, default scale 1 / sqrt(d + dv),
+# hopper/test_util.py:237,287-293), pinned to the same FA3 oracle and frozen in tests/golden/attention_qv_golden.pt (a file of
+# its own: every fixture stays small).  qv comes from make_qv(): q, k, v are those of make_inputs().
+QV_CASES = {
+    "qv_d64_dv256_causal_gqa": _fa3_case("bf16", 1, 65, 200, 4, 2, 64, dv=256, causal=True, seed=80, store_row_stride=4),
+    "qv_d32_dv384_local_40_7": _fa3_case("fp16", 1, 80, 257, 4, 1, 32, dv=384, window=(40, 7), seed=81, store_row_stride=4),
+    "qv_d64_dv512_softcap15": _fa3_case("bf16", 1, 50, 130, 2, 2, 64, dv=512, softcap=15.0, q_scale=4.0, seed=82,
+                                        store_row_stride=4),
+    "qv_d64_dv256_chunk48_causal": _fa3_case("bf16", 1, 61, 190, 4, 4, 64, dv=256, chunk=48, causal=True, seed=83,
+                                             store_row_stride=4),
+}
+
+
 # Backward fixtures: small problems whose dq/dk/dv (reference oracle + autograd, the way tests/test_flash_attn.py:1071-1105
 # obtains dq_ref / dq_pt) are frozen in tests/golden/attention_grad_golden.pt.  Stored in full (store_row_stride = 1).
 GRAD_CASES = {
@@ -116,6 +129,13 @@ def make_inputs(c):
     if c.get("fp8"):  # values an e4m3 tensor can hold, kept in bf16 for the oracle (the kernel gets .to(float8_e4m3fn))
         q, k, v = (t.to(torch.float8_e4m3fn).to(dt) for t in (q, k, v))
     return q, k, v
+
+
+def make_qv(c):
+    """qv (b, sq, h, dv) ~ N(0, 1) * q_scale in the case's dtype, from a generator of its own."""
+    g = torch.Generator().manual_seed(6000 + c["seed"])
+    qv = torch.randn(c["b"], c["sq"], c["h"], c["dv"], generator=g, dtype=torch.float32) * c["q_scale"]
+    return qv.to(_DT[c["dtype"]])
 
 
 def make_descales(c):

@@ -23,7 +23,7 @@ REF = "/root/reference"
 sys.path.insert(0, ROOT)
 
 from oracle import attention_ref as mine  # noqa: E402
-from oracle.cases import CASES, FA3_CASES, GRAD_CASES, make_grad_output, make_alibi_slopes, make_descales, make_inputs, padding_masks, checksum  # noqa: E402
+from oracle.cases import CASES, FA3_CASES, GRAD_CASES, QV_CASES, make_qv, make_grad_output, make_alibi_slopes, make_descales, make_inputs, padding_masks, checksum  # noqa: E402
 
 
 def import_reference():
@@ -192,6 +192,46 @@ def main():
         print(f"{name:34s} fp32 err {e1:.2e}  pt err {e2:.1e}  probs {e4:.1e}  (FA3 oracle: chunk {c['chunk']}, dv {c['dv']})")
     out_path = os.path.join(ROOT, "tests/golden/attention_fa3_golden.pt")
     torch.save(fa3_golden, out_path)
+    print(f"wrote {out_path} ({os.path.getsize(out_path) / 1e6:.2f} MB)")
+
+    # ---- the FA3 qv argument (hopper/test_util.py:237,273,287-293), pinned to the FA3 oracle called with qv= the way
+    #      hopper/test_flash_attn.py does; the concatenation identity [Q | Qv].[K | V]^T is checked beside it ----------------
+    qv_golden = {}
+    for name, c in QV_CASES.items():
+        q, k, v = make_inputs(c)
+        qv = make_qv(c)
+        kw = dict(causal=c["causal"], window_size=c["window"], softcap=c["softcap"], attention_chunk=c["chunk"])
+        ref_out, ref_attn = fa3.attention_ref(q, k, v, None, None, qv=qv, **kw)
+        ref_pt, _ = fa3.attention_ref(q, k, v, None, None, qv=qv, **kw, upcast=False, reorder_ops=True)
+        ref_out32, _ = fa3.attention_ref(q.float(), k.float(), v.float(), None, None, qv=qv.float(), **kw)
+        my_out, my_attn, my_lse = mine.attention_ref(q, k, v, qv=qv, **kw, return_lse=True)
+        my_pt, _ = mine.attention_ref(q, k, v, qv=qv, **kw, upcast=False, reorder_ops=True)
+        my_out32, _ = mine.attention_ref(q.float(), k.float(), v.float(), qv=qv.float(), **kw)
+        cat_out32, _, cat_lse = mine.attention_ref(torch.cat([q, qv], -1).float(), torch.cat([k, v], -1).float(), v.float(), **kw,
+                                                   return_lse=True)
+        assert tuple(ref_out.shape) == (c["b"], c["sq"], c["h"], c["dv"]), name
+        e1 = (my_out32 - ref_out32).abs().max().item()
+        e2 = (my_pt.float() - ref_pt.float()).abs().max().item()
+        e4 = (my_attn.float() - ref_attn.float()).abs().max().item()
+        e5 = (cat_out32 - ref_out32).abs().max().item()
+        fin = torch.isfinite(my_lse)
+        assert torch.equal(fin, torch.isfinite(cat_lse)), (name, "lse inf pattern")
+        e6 = (cat_lse[fin] - my_lse[fin]).abs().max().item()
+        # (q * scale there, q / sqrt(d + dv) here: fp32 rounding noise; in 16 bits the two roundings differ by an ulp.  The
+        #  identity adds the two products in one fp32 dot product of d + dv terms instead of two: scores of magnitude up to the
+        #  softcap 15 carry an ulp of 1e-6, which the exponential passes on as a relative error of the probabilities: 2e-5)
+        assert e1 <= 5e-6 and e2 <= 1.6e-2 and e4 <= 4e-3 and e5 <= 2e-5 and e6 <= 2e-5, (name, e1, e2, e4, e5, e6)
+        stride = c["store_row_stride"]
+        qv_golden[name] = {
+            "case": {k2: (list(v2) if isinstance(v2, tuple) else v2) for k2, v2 in c.items()},
+            "input_checksum": torch.tensor([checksum(q), checksum(k), checksum(v), checksum(qv)], dtype=torch.float64),
+            "out_ref_fp32": ref_out32[:, ::stride].contiguous(),
+            "out_pt": ref_pt[:, ::stride].contiguous(),
+            "lse": my_lse[:, :, ::stride].contiguous(),
+        }
+        print(f"{name:34s} fp32 err {e1:.2e}  pt err {e2:.1e}  probs {e4:.1e}  identity {e5:.1e}  (FA3 oracle, qv, dv {c['dv']})")
+    out_path = os.path.join(ROOT, "tests/golden/attention_qv_golden.pt")
+    torch.save(qv_golden, out_path)
     print(f"wrote {out_path} ({os.path.getsize(out_path) / 1e6:.2f} MB)")
 
     # ---- left-padded keys (key_leftpad of tests/test_util.py:150-182 and tests/test_flash_attn.py:29-56): restatement

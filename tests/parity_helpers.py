@@ -1,0 +1,83 @@
+"""Helpers shared by the GPU parity tests (a plain module, not collected): row sampling for problems whose full attention
+matrix is too costly for the CPU oracle, and the row-subset comparison of tests/test_full_size_gpu.py (bounds in its docstring).
+Also the one place that reads back which forward plan ran (fa_fwd_last_plan_name, include/fa_fwd.h)."""
+import math
+import re
+
+import torch
+
+from oracle import attention_ref as oracle
+
+FP8 = torch.float8_e4m3fn
+
+
+def last_plan():
+    """Plan name of the calling thread's most recent fa_fwd launch (both compiled bindings call fa_fwd synchronously on the
+    Python thread, out of the library _lib.load() returns)."""
+    from flash_attention_annotated_amd import _lib
+    name = _lib.load().fa_fwd_last_plan_name()
+    assert name is not None, "no forward plan recorded: the entry point did not reach fa_fwd on this thread"
+    return name.decode()
+
+
+def kernel_key(plan, dtype):
+    """(element type, plan name without block_m= / splits= / cols= / fp8_expand): one template instantiation.  fp8 inputs run
+    the native kernel ("fp8") or, expanded, the bf16 instantiations."""
+    key = re.sub(r" (block_m|splits|cols)=\d+| fp8_expand", "", plan)
+    if dtype == FP8:
+        return ("bf16" if " fp8_expand" in plan else "fp8", key)
+    return ({torch.bfloat16: "bf16", torch.float16: "fp16"}[dtype], key)
+
+
+def wave_slice_rows(sq, block_m, seed=0, rows_per_wave=32):
+    """One random row in every `rows_per_wave`-row slice of the first, a middle and the last `block_m`-row m-block (sorted).
+    32 rows is the smallest wave slice of any forward kernel (fwd_kernel_d256: 4 waves x 32 rows; a 64-row wave of the 256-row
+    kernel gets two)."""
+    g = torch.Generator().manual_seed(seed)
+    nblocks = (sq + block_m - 1) // block_m
+    rows = []
+    for mb in sorted({0, nblocks // 2, nblocks - 1}):
+        for lo in range(mb * block_m, min(sq, (mb + 1) * block_m), rows_per_wave):
+            hi = min(sq, lo + rows_per_wave)
+            rows.append(lo + int(torch.randint(0, hi - lo, (1,), generator=g)))
+    return sorted(set(rows))
+
+
+def sample_rows(sq, n=128, block=256, seed=0):
+    """Sorted row indices: ceil(n / #blocks) random rows in every `block`-row m-block (>= n rows in total)."""
+    g = torch.Generator().manual_seed(seed)
+    nblocks = (sq + block - 1) // block
+    per = max(1, -(-n // nblocks))
+    rows = []
+    for mb in range(nblocks):
+        lo, hi = mb * block, min(sq, (mb + 1) * block)
+        rows += (lo + torch.randperm(hi - lo, generator=g)[:per]).tolist()
+    return sorted(set(rows))
+
+
+def causal_bias(rows, sq, sk):
+    """(1, 1, len(rows), sk): 0 where key j <= i + sk - sq (bottom-right aligned causal), -inf elsewhere."""
+    i = torch.tensor(rows, dtype=torch.long).view(-1, 1)
+    j = torch.arange(sk, dtype=torch.long).view(1, -1)
+    return torch.where(j <= i + sk - sq, 0.0, float("-inf")).view(1, 1, len(rows), sk)
+
+
+def _check_rows(out_rows, lse_rows, q_rows, k, v, bias, what, fp8_kw=None, lse_tol=2e-3):
+    kw = dict(attn_bias=bias)
+    if fp8_kw:
+        kw.update(fp8_kw)
+    out_ref, _, lse_ref = oracle.attention_ref(q_rows, k, v, return_lse=True, **kw)
+    if fp8_kw:
+        out_pt, _ = oracle.attention_ref(q_rows, k, v, upcast=False, reorder_ops=True, intermediate_dtype=FP8, **kw)
+        atol = 2 * (out_ref.float() + 0.3 - 0.3 - out_ref.float()).abs().max().item()
+    else:
+        out_pt, _ = oracle.attention_ref(q_rows, k, v, upcast=False, reorder_ops=True, **kw)
+        atol = 1e-5
+    err = (out_rows.float().cpu() - out_ref.float()).abs().max().item()
+    bound = 2 * (out_pt.float() - out_ref.float()).abs().max().item() + atol
+    assert math.isfinite(err) and err <= bound, f"{what}: max err {err:.3e} > bound {bound:.3e}"
+    fin = torch.isfinite(lse_ref)
+    lse_rows = lse_rows.float().cpu()
+    assert torch.equal(torch.isfinite(lse_rows), fin), f"{what}: lse inf pattern"
+    lerr = (lse_rows[fin] - lse_ref[fin]).abs().max().item()
+    assert lerr <= lse_tol, f"{what}: lse err {lerr:.3e}"

@@ -24,6 +24,7 @@ def _header_functions():
 def test_header_symbols_all_exported(built_lib):
     names = _header_functions()
     assert set(names) == set(_lib.EXPORTED_SYMBOLS), "binding list and header disagree"
+    assert "fa_fwd_last_plan_name" in names  # the hook the GPU parity tests read the launched kernel from
     for n in names:
         assert hasattr(built_lib, n), f"{n} declared in include/*.h but not exported"
 

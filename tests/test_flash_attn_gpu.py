@@ -14,6 +14,7 @@ import torch
 
 from oracle import attention_ref as oracle
 from oracle.cases import CASES, checksum, make_alibi_slopes, make_inputs, padding_masks
+from parity_helpers import last_plan
 
 pytestmark = pytest.mark.gpu
 
@@ -549,12 +550,30 @@ def test_empty_keys_dense():
     assert torch.all(out == 0) and torch.all(torch.isposinf(lse))
 
 
+def _sweep_form(feature, d, causal):
+    """The kernel a problem of test_row_block_kernel_random_sweep runs when it does not reach fwd_kernel_d256 (plan_fwd: every
+    seed is split by the FA2 heuristic, and a split problem stays in the 256-row kernel at head dims <= 128 -- the 4-wave
+    compiler-scheduled shape for a causal problem at head dim <= 64 -- and runs the compiler-scheduled shape above 128)."""
+    cap = " SOFTCAP" if feature == "softcap" else ""
+    if d > 128:
+        return "fwd_kernel D=256 waves=4" + cap
+    if d <= 64:
+        return ("fwd_kernel D=64 waves=4" if causal else "fwd_kernel_w64 D=64 DEFF=64 waves=4") + cap
+    return f"fwd_kernel_w64 D=128 DEFF={96 if d <= 96 and not cap else 128} waves=4" + cap
+
+
 @pytest.mark.parametrize("seed", list(range(24)))
 def test_row_block_kernel_random_sweep(seed):
-    """Seeded random problems over everything the 32-row-per-wave kernel (fa_fwd_kernel_d256.h) takes since round 3: head dims
-    40 .. 256 with softcap or ALiBi (its DEFF 64 .. 256 forms), head dims 136 .. 256 plain, causal / windows / neither, GQA,
-    odd lengths, both 16-bit types -- unmasked body, masked body (diagonal, ragged tail, last tile) and the generic half-step
-    (left window edge, guard trips) in one sweep each; out and LSE against the oracle."""
+    """Seeded random problems over what the 32-row-per-wave kernel (fa_fwd_kernel_d256.h) takes since round 3: head dims
+    40 .. 256 with softcap or ALiBi, head dims 136 .. 256 plain, causal / windows / neither, GQA, odd lengths, both 16-bit
+    types -- unmasked body, masked body (diagonal, ragged tail, last tile) and the generic half-step (left window edge, guard
+    trips) in one sweep each; out and LSE against the oracle.  What it reaches is less than that: batch 2 x at most 6 heads
+    is few enough work items for the FA2 entry point's split-KV heuristic to split every one of the 24 seeds (planned on 256
+    CUs), and a split problem never runs fwd_kernel_d256 -- head dims <= 128 stay in the 256-row kernel (fwd_kernel_w64, plain
+    or SOFTCAP), head dims above run the compiler-scheduled shape (fwd_kernel D=256 waves=4); an unsplit causal problem at head
+    dim <= 64 with seqlen_k <= 2048 would run fwd_kernel D=64 waves=4, not fwd_kernel_d256 W=64.  The sweep keeps its problems
+    (what it covers today stays covered) and asserts and prints the plan of every seed; the fwd_kernel_d256 forms are covered
+    by name in tests/test_plan_parity_gpu.py."""
     fa = _api()
     g = torch.Generator().manual_seed(1000 + seed)
     ri = lambda lo, hi: int(torch.randint(lo, hi + 1, (1,), generator=g).item())
@@ -583,6 +602,9 @@ def test_row_block_kernel_random_sweep(seed):
         kw["alibi_slopes"] = slopes.to(DEV)
         okw["attn_bias"] = oracle.attn_bias_from_alibi_slopes(slopes, sq, sk, causal=False)
     out, lse, _ = fa.flash_attn_func(q.to(DEV), k.to(DEV), v.to(DEV), return_attn_probs=True, **kw)
+    plan = last_plan()
+    print(f"seed {seed}: {feature} d{d} {sq}x{sk} {sorted(kw)} -> {plan}")
+    assert plan.startswith(("fwd_kernel_d256 W=", _sweep_form(feature, d, mask == 1) + " block_m=")), plan
     out_ref, out_pt, lse_ref = _dense_ref(q, k, v, **okw)
     err = (out.float().cpu() - out_ref.float()).abs().max().item()
     bound = 3 * (out_pt.float() - out_ref.float()).abs().max().item() + 2 * (out_ref + 0.3 - 0.3 - out_ref).abs().max().item() + 1e-5

@@ -17,50 +17,11 @@ import pytest
 import torch
 
 from oracle import attention_ref as oracle
+from parity_helpers import _check_rows, causal_bias, sample_rows
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 FP8 = torch.float8_e4m3fn
-
-
-def sample_rows(sq, n=128, block=256, seed=0):
-    """Sorted row indices: ceil(n / #blocks) random rows in every `block`-row m-block (>= n rows in total)."""
-    g = torch.Generator().manual_seed(seed)
-    nblocks = (sq + block - 1) // block
-    per = max(1, -(-n // nblocks))
-    rows = []
-    for mb in range(nblocks):
-        lo, hi = mb * block, min(sq, (mb + 1) * block)
-        rows += (lo + torch.randperm(hi - lo, generator=g)[:per]).tolist()
-    return sorted(set(rows))
-
-
-def causal_bias(rows, sq, sk):
-    """(1, 1, len(rows), sk): 0 where key j <= i + sk - sq (bottom-right aligned causal), -inf elsewhere."""
-    i = torch.tensor(rows, dtype=torch.long).view(-1, 1)
-    j = torch.arange(sk, dtype=torch.long).view(1, -1)
-    return torch.where(j <= i + sk - sq, 0.0, float("-inf")).view(1, 1, len(rows), sk)
-
-
-def _check_rows(out_rows, lse_rows, q_rows, k, v, bias, what, fp8_kw=None, lse_tol=2e-3):
-    kw = dict(attn_bias=bias)
-    if fp8_kw:
-        kw.update(fp8_kw)
-    out_ref, _, lse_ref = oracle.attention_ref(q_rows, k, v, return_lse=True, **kw)
-    if fp8_kw:
-        out_pt, _ = oracle.attention_ref(q_rows, k, v, upcast=False, reorder_ops=True, intermediate_dtype=FP8, **kw)
-        atol = 2 * (out_ref.float() + 0.3 - 0.3 - out_ref.float()).abs().max().item()
-    else:
-        out_pt, _ = oracle.attention_ref(q_rows, k, v, upcast=False, reorder_ops=True, **kw)
-        atol = 1e-5
-    err = (out_rows.float().cpu() - out_ref.float()).abs().max().item()
-    bound = 2 * (out_pt.float() - out_ref.float()).abs().max().item() + atol
-    assert math.isfinite(err) and err <= bound, f"{what}: max err {err:.3e} > bound {bound:.3e}"
-    fin = torch.isfinite(lse_ref)
-    lse_rows = lse_rows.float().cpu()
-    assert torch.equal(torch.isfinite(lse_rows), fin), f"{what}: lse inf pattern"
-    lerr = (lse_rows[fin] - lse_ref[fin]).abs().max().item()
-    assert lerr <= lse_tol, f"{what}: lse err {lerr:.3e}"
 
 
 def _api():

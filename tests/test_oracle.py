@@ -8,7 +8,7 @@ import pytest
 import torch
 
 from oracle import attention_ref as oracle
-from oracle.cases import CASES, FA3_CASES, checksum, make_alibi_slopes, make_descales, make_inputs, padding_masks
+from oracle.cases import CASES, FA3_CASES, QV_CASES, make_qv, checksum, make_alibi_slopes, make_descales, make_inputs, padding_masks
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -67,6 +67,34 @@ def test_oracle_reproduces_fa3_golden(name, golden_fa3):
     assert torch.equal(torch.isfinite(lse[:, :, ::st]), fin)
     if fin.any():
         assert (lse[:, :, ::st][fin] - g["lse"][fin]).abs().max().item() <= 1e-5
+
+
+@pytest.mark.parametrize("name", list(QV_CASES))
+def test_oracle_reproduces_qv_golden(name):
+    """tests/golden/attention_qv_golden.pt: the reference's FA3 oracle called with qv= (hopper/test_util.py:237,287-293) on the
+    cases of oracle/cases.py:QV_CASES; and the identity the qv tests used before, [Q | Qv].[K | V]^T with the original V, agrees
+    with the qv= form (one fp32 dot product of d + dv terms instead of two: 2e-5, see oracle/make_golden.py)."""
+    g = torch.load(os.path.join(ROOT, "tests", "golden", "attention_qv_golden.pt"), weights_only=True)[name]
+    c = QV_CASES[name]
+    q, k, v = make_inputs(c)
+    qv = make_qv(c)
+    assert qv.shape == (c["b"], c["sq"], c["h"], c["dv"]) and v.shape[-1] == c["dv"]
+    for t, want in zip((q, k, v, qv), g["input_checksum"].tolist()):
+        assert abs(checksum(t) - want) <= 1e-6 * max(1.0, abs(want)), "seeded inputs differ from the frozen ones"
+    kw = dict(causal=c["causal"], window_size=tuple(c["window"]), softcap=c["softcap"], attention_chunk=c["chunk"])
+    st = c["store_row_stride"]
+    out32, _, lse = oracle.attention_ref(q.float(), k.float(), v.float(), qv=qv.float(), **kw, return_lse=True)
+    out_pt, _ = oracle.attention_ref(q, k, v, qv=qv, **kw, upcast=False, reorder_ops=True)
+    assert (out32[:, ::st] - g["out_ref_fp32"]).abs().max().item() <= 5e-6
+    assert (out_pt[:, ::st].float() - g["out_pt"].float()).abs().max().item() <= 2e-2 + 1e-6
+    fin = torch.isfinite(g["lse"])
+    assert torch.equal(torch.isfinite(lse[:, :, ::st]), fin)
+    assert (lse[:, :, ::st][fin] - g["lse"][fin]).abs().max().item() <= 1e-5
+    cat32, _, cat_lse = oracle.attention_ref(torch.cat([q, qv], -1).float(), torch.cat([k, v], -1).float(), v.float(), **kw,
+                                             return_lse=True)
+    assert (cat32 - out32).abs().max().item() <= 2e-5
+    assert torch.equal(torch.isfinite(cat_lse), torch.isfinite(lse))
+    assert (cat_lse[torch.isfinite(lse)] - lse[torch.isfinite(lse)]).abs().max().item() <= 2e-5
 
 
 def test_chunk_mask_by_definition():

@@ -1,8 +1,10 @@
 """GPU tests of the FA3 qv argument (MLA absorbed attention, hopper/flash_api.cpp:1028-1048) and of d <= 64 beside a V head
 dim in [256, 512] on paged caches / split-KV -- the qv kernel (csrc/fa_fwd_kernel_qv.h).
 
-The oracle is the identity  Q.K^T + Qv.V^T = [Q | Qv].[K | V]^T: qv attention is plain attention with q' = cat(q, qv),
-k' = cat(k, v) and the original v, whose default scale 1 / sqrt(d + d_v) is the reference's (hopper/test_util.py:287-292).
+The oracle is oracle.attention_ref(q, k, v, qv=qv): scores += (qv * scale) @ v^T with the default scale 1 / sqrt(d + d_v),
+pinned to the reference's FA3 oracle (hopper/test_util.py:287-293) by oracle/make_golden.py and tests/golden/attention_qv_golden.pt;
+tests/test_oracle.py keeps the identity  Q.K^T + Qv.V^T = [Q | Qv].[K | V]^T  beside it.  Every call also asserts which kernel ran
+(fa_fwd_last_plan_name).
 Contract as in hopper/test_flash_attn.py:193-194,223:
     |out - out_ref|max <= 2 |out_pt - out_ref|max + fwd_atol,  fwd_atol = 2 |(out_ref + 0.3 - 0.3) - out_ref|max."""
 import math
@@ -11,6 +13,7 @@ import pytest
 import torch
 
 from oracle import attention_ref as oracle
+from parity_helpers import last_plan
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -36,13 +39,19 @@ def _check_lse(lse, lse_ref):
 
 
 def _refs(q, k, v, qv, **kw):
-    """(out_ref, out_pt, lse_ref) of qv attention through the concatenation identity (CPU); the oracle's default scale
-    1 / sqrt(q'.shape[-1]) is the kernel's (d + d_v with qv, d without)."""
-    qq = torch.cat([q, qv], -1) if qv is not None else q
-    kk = torch.cat([k, v], -1) if qv is not None else k
-    out_ref, _, lse_ref = oracle.attention_ref(qq, kk, v, return_lse=True, **kw)
-    out_pt, _ = oracle.attention_ref(qq, kk, v, upcast=False, reorder_ops=True, **kw)
+    """(out_ref, out_pt, lse_ref) of qv attention (CPU); the oracle's default scale is the kernel's (1 / sqrt(d + d_v) with qv,
+    1 / sqrt(d) without)."""
+    out_ref, _, lse_ref = oracle.attention_ref(q, k, v, qv=qv, return_lse=True, **kw)
+    out_pt, _ = oracle.attention_ref(q, k, v, qv=qv, upcast=False, reorder_ops=True, **kw)
     return out_ref, out_pt, lse_ref
+
+
+def _ran(dvt, softcap=False, splits=None):
+    """The call just made launched fwd_kernel_qv with this V tile (and split count, when given)."""
+    plan = last_plan()
+    assert plan.startswith(f"fwd_kernel_qv DVT={dvt} waves=4{' SOFTCAP' if softcap else ''} block_m="), plan
+    if splits is not None:
+        assert f" splits={splits}" in plan, plan
 
 
 DENSE = [  # (dtype, b, sq, sk, h, hk, d, dv, causal, window, softcap, chunk)
@@ -66,6 +75,7 @@ def test_qv_dense(case):
     v = torch.randn(b, sk, hk, dv, dtype=dtype)
     out, lse = _fa3().flash_attn_func(q.to(DEV), k.to(DEV), v.to(DEV), qv=qv.to(DEV), causal=causal, window_size=window,
                                       softcap=softcap, attention_chunk=chunk, return_attn_probs=True)
+    _ran(256 if dv <= 256 else 512, softcap > 0)
     out_ref, out_pt, lse_ref = _refs(q, k, v, qv, causal=causal, window_size=window, softcap=softcap, attention_chunk=chunk)
     assert out.shape == (b, sq, h, dv)
     _check(out, out_ref, out_pt)
@@ -84,6 +94,7 @@ def test_qv_varlen_with_empty_sequence():
     v = torch.randn(sum(lens_k), hk, dv, dtype=torch.bfloat16)
     out, lse = _fa3().flash_attn_varlen_func(q.to(DEV), k.to(DEV), v.to(DEV), cu_q.to(DEV), cu_k.to(DEV), max(lens_q),
                                              max(lens_k), qv=qv.to(DEV), causal=True, return_attn_probs=True)
+    _ran(512, splits=1)
     for i in range(3):
         if lens_q[i] == 0:
             continue
@@ -139,6 +150,7 @@ def test_qv_kvcache_mla(case):
     out, lse, *_ = _fa3().flash_attn_with_kvcache(
         q.to(DEV), cache[..., :d], cache[..., d:], qv=qv.to(DEV), cache_seqlens=seqlens.to(DEV), page_table=table,
         causal=causal, num_splits=splits, return_softmax_lse=True)
+    _ran(512, splits=splits or None)  # (0: the heuristic's count)
     for i in range(b):
         k_i, v_i = _kv_ref(logical, i, 0, int(seqlens[i]), d)
         ref, pt, lse_ref = _refs(q[i:i + 1], k_i, v_i, qv[i:i + 1], causal=causal)
@@ -165,6 +177,7 @@ def test_qv_kvcache_append(rotary):
         q.to(DEV), cache[..., :d], cache[..., d:], k=k_new.to(DEV), v=v_new.to(DEV), qv=qv.to(DEV),
         rotary_cos=None if cos is None else cos.to(DEV), rotary_sin=None if sin is None else sin.to(DEV),
         cache_seqlens=seqlens.to(DEV), causal=True, rotary_interleaved=False, num_splits=1)
+    _ran(512, splits=1)
     k_app = k_new if not rotary else oracle.apply_rotary_emb_ref(k_new, cos, sin, seqlens, interleaved=False)
     q_use = q if not rotary else oracle.apply_rotary_emb_ref(q, cos, sin, seqlens, interleaved=False)
     exp = logical.clone()
@@ -191,6 +204,7 @@ def test_qv_kvcache_batch_idx_and_leftpad():
     seqlens = torch.tensor([400, 123, 301], dtype=torch.int32)
     out = _fa3().flash_attn_with_kvcache(q.to(DEV), cache[..., :d], cache[..., d:], qv=qv.to(DEV),
                                          cache_seqlens=seqlens.to(DEV), cache_batch_idx=idx.to(DEV), num_splits=0)
+    _ran(512)
     for i in range(b):
         k_i, v_i = _kv_ref(logical, int(idx[i]), 0, int(seqlens[i]), d)
         ref, pt, _ = _refs(q[i:i + 1], k_i, v_i, qv[i:i + 1])
@@ -198,6 +212,7 @@ def test_qv_kvcache_batch_idx_and_leftpad():
     lp = torch.tensor([0, 50, 300], dtype=torch.int32)
     out = _fa3().flash_attn_with_kvcache(q.to(DEV), cache[:b, ..., :d], cache[:b, ..., d:], qv=qv.to(DEV),
                                          cache_seqlens=seqlens.to(DEV), cache_leftpad=lp.to(DEV), num_splits=3, causal=True)
+    _ran(512, splits=3)
     for i in range(b):
         k_i, v_i = _kv_ref(logical, i, int(lp[i]), int(seqlens[i]), d)
         ref, pt, _ = _refs(q[i:i + 1], k_i, v_i, qv[i:i + 1], causal=True)
@@ -214,6 +229,7 @@ def test_wide_v_without_qv_paged_and_split(page, splits):
     seqlens = torch.tensor([333, 200], dtype=torch.int32)
     out = _fa3().flash_attn_with_kvcache(q.to(DEV), cache[..., :d], cache[..., d:], cache_seqlens=seqlens.to(DEV),
                                          page_table=table, num_splits=splits, causal=True)
+    _ran(512, splits=splits)
     for i in range(b):
         k_i, v_i = _kv_ref(logical, i, 0, int(seqlens[i]), d)
         ref, pt, _ = _refs(q[i:i + 1], k_i, v_i, None, causal=True)
@@ -234,6 +250,7 @@ def test_qv_deterministic_and_graph(splits):
         return fa3.flash_attn_with_kvcache(q, cache[..., :d], cache[..., d:], qv=qv, cache_seqlens=seqlens, page_table=table,
                                            num_splits=splits)
     first = step()
+    _ran(512, splits=1 if splits == 1 else None)
     for _ in range(19):
         assert torch.equal(step(), first)
     s = torch.cuda.Stream()
@@ -256,6 +273,7 @@ def test_qv_backward_raises_and_bad_shapes_rejected():
     v = torch.randn(1, 8, 1, 512, dtype=torch.bfloat16, device=DEV)
     qv = torch.randn(1, 8, 4, 512, dtype=torch.bfloat16, device=DEV)
     out = fa3.flash_attn_func(q, k, v, qv=qv)
+    _ran(512, splits=1)
     with pytest.raises(AssertionError, match="does not support qv"):
         out.sum().backward()
     with pytest.raises(RuntimeError, match="does not support qv"):
@@ -263,3 +281,141 @@ def test_qv_backward_raises_and_bad_shapes_rejected():
     with pytest.raises(RuntimeError, match="does not support cu_seqlens_k_new"):
         fa3.flash_attn_with_kvcache(q.detach(), k, v, k=k, v=v, qv=qv, cache_seqlens=0,
                                     cu_seqlens_k_new=torch.zeros(2, dtype=torch.int32, device=DEV))
+
+# ---- the kernel's edges: head dims that are multiples of 8 only, GQA packs that cross query rows inside a 32-row block,
+#      clamped loads, empty splits.  Every case asserts the kernel that ran.
+EDGE = [  # (dtype, b, sq, sk, h, hk, d, dv, causal, window, softcap, chunk)
+    (torch.bfloat16, 1, 70, 300, 4, 2, 8, 264, True, (-1, -1), 0.0, 0),
+    (torch.float16, 2, 45, 257, 6, 2, 24, 328, False, (30, 9), 0.0, 0),
+    (torch.bfloat16, 1, 90, 200, 3, 1, 40, 504, True, (-1, -1), 0.0, 0),
+    (torch.float16, 1, 33, 130, 5, 1, 56, 264, False, (-1, -1), 0.0, 0),
+    (torch.float16, 1, 40, 333, 2, 2, 24, 504, False, (-1, -1), 12.0, 0),
+    (torch.bfloat16, 1, 50, 200, 4, 2, 64, 256, False, (-1, -1), 15.0, 0),   # DVT = 256 with softcap
+    (torch.bfloat16, 1, 43, 120, 3, 1, 64, 256, True, (-1, -1), 0.0, 0),     # g = 3: a 32-row block starts mid query row
+    (torch.float16, 2, 29, 150, 5, 1, 32, 384, False, (20, 5), 0.0, 0),      # g = 5 under a two-sided window
+    (torch.bfloat16, 1, 37, 190, 7, 1, 64, 512, True, (-1, -1), 0.0, 48),    # g = 7 under attention_chunk
+]
+
+
+@pytest.mark.parametrize("case", EDGE, ids=[f"d{c[6]}dv{c[7]}g{c[4] // c[5]}c{i}" for i, c in enumerate(EDGE)])
+def test_qv_edges_dense(case):
+    test_qv_dense(case)
+
+
+@pytest.mark.parametrize("dv", [256, 512])
+@pytest.mark.parametrize("page,splits", [(16, 1), (None, 3), (16, 3)])
+def test_wide_v_tiles_without_qv(dv, page, splits):
+    """Both V tiles of the qv kernel without qv: a paged cache of 16-key pages, and three splits."""
+    b, hk, h, d, dtype = 2, 2, 6, 64, torch.bfloat16
+    logical, cache, table = _mla_cache(b, 333, hk, d, dv, dtype, page, seed=51 + dv)
+    torch.manual_seed(52)
+    q = torch.randn(b, 3, h, d, dtype=dtype)
+    seqlens = torch.tensor([333, 200], dtype=torch.int32)
+    out, lse, *_ = _fa3().flash_attn_with_kvcache(q.to(DEV), cache[..., :d], cache[..., d:], cache_seqlens=seqlens.to(DEV),
+                                                  page_table=table, num_splits=splits, causal=True, return_softmax_lse=True)
+    _ran(dv, splits=splits)
+    for i in range(b):
+        k_i, v_i = _kv_ref(logical, i, 0, int(seqlens[i]), d)
+        ref, pt, lse_ref = _refs(q[i:i + 1], k_i, v_i, None, causal=True)
+        _check(out[i:i + 1], ref, pt)
+        _check_lse(lse[i:i + 1], lse_ref)
+
+
+@pytest.mark.parametrize("page", [None, 16])
+def test_qv_clamped_loads_never_leak(page):
+    """Cache rows past cache_seqlens hold NaN (the kernel clamps rows to seqlen - 1: a wrong clamp shows as NaN); the dense
+    cache is a padded row layout -- row stride wider than d + d_v -- with NaN in the gap, next to head dims (24 / 328) whose
+    last column chunks are clamped duplicates."""
+    b, hk, h, d, dv, sk_max, dtype = 2, 1, 6, 24, 328, 300, torch.float16
+    logical, cache, table = _mla_cache(b, sk_max, hk, d, dv, dtype, page, seed=61)
+    seqlens = torch.tensor([211, 77], dtype=torch.int32)
+    if page is None:
+        wide = torch.full((b, sk_max, hk, d + dv + 40), float("nan"), dtype=dtype)
+        wide[..., :d + dv] = logical
+        for i in range(b):
+            wide[i, int(seqlens[i]):] = float("nan")
+        cache = wide.to(DEV)
+    else:
+        pages = cache.cpu()
+        for i in range(b):
+            for r in range(int(seqlens[i]), table.shape[1] * page):
+                pages[int(table[i, r // page]), r % page] = float("nan")
+        cache = pages.to(DEV)
+    torch.manual_seed(62)
+    q = torch.randn(b, 5, h, d, dtype=dtype)
+    qv = torch.randn(b, 5, h, dv, dtype=dtype)
+    out, lse, *_ = _fa3().flash_attn_with_kvcache(q.to(DEV), cache[..., :d], cache[..., d:d + dv], qv=qv.to(DEV),
+                                                  cache_seqlens=seqlens.to(DEV), page_table=table, causal=True, num_splits=1,
+                                                  return_softmax_lse=True)
+    _ran(512, splits=1)
+    assert torch.isfinite(out.float()).all() and torch.isfinite(lse).all()
+    for i in range(b):
+        k_i, v_i = _kv_ref(logical, i, 0, int(seqlens[i]), d)
+        ref, pt, lse_ref = _refs(q[i:i + 1], k_i, v_i, qv[i:i + 1], causal=True)
+        _check(out[i:i + 1], ref, pt)
+        _check_lse(lse[i:i + 1], lse_ref)
+
+
+def test_qv_split_with_empty_splits():
+    """Three splits over a 700-key cache of which one batch entry uses 40 keys: its later splits see no key at all and hand
+    LSE = +inf partials to the merge; out and LSE against the oracle."""
+    b, hk, h, d, dv, dtype = 2, 1, 16, 64, 512, torch.bfloat16
+    logical, cache, _ = _mla_cache(b, 700, hk, d, dv, dtype, None, seed=71)
+    torch.manual_seed(72)
+    q = torch.randn(b, 2, h, d, dtype=dtype)
+    qv = torch.randn(b, 2, h, dv, dtype=dtype)
+    seqlens = torch.tensor([700, 40], dtype=torch.int32)
+    out, lse, *_ = _fa3().flash_attn_with_kvcache(q.to(DEV), cache[..., :d], cache[..., d:], qv=qv.to(DEV),
+                                                  cache_seqlens=seqlens.to(DEV), num_splits=3, causal=True, return_softmax_lse=True)
+    _ran(512, splits=3)
+    for i in range(b):
+        k_i, v_i = _kv_ref(logical, i, 0, int(seqlens[i]), d)
+        ref, pt, lse_ref = _refs(q[i:i + 1], k_i, v_i, qv[i:i + 1], causal=True)
+        _check(out[i:i + 1], ref, pt)
+        _check_lse(lse[i:i + 1], lse_ref)
+
+
+@pytest.mark.parametrize("window", [(-1, -1), (25, 6)])
+def test_qv_varlen_seqused_and_empty_last_sequence(window):
+    """Packed batch, non-causal and windowed, with seqused_q / seqused_k shorter than the cu_seqlens spans and an empty last
+    sequence: the used rows see the used keys only."""
+    torch.manual_seed(81)
+    span_q, span_k, used_q, used_k = [30, 41, 0], [90, 140, 20], [21, 41, 0], [70, 133, 20]
+    h, hk, d, dv = 6, 2, 40, 264
+    cu_q = torch.tensor([0, 30, 71, 71], dtype=torch.int32)
+    cu_k = torch.tensor([0, 90, 230, 250], dtype=torch.int32)
+    q = torch.randn(71, h, d, dtype=torch.bfloat16)
+    qv = torch.randn(71, h, dv, dtype=torch.bfloat16)
+    k = torch.randn(250, hk, d, dtype=torch.bfloat16)
+    v = torch.randn(250, hk, dv, dtype=torch.bfloat16)
+    out, lse = _fa3().flash_attn_varlen_func(
+        q.to(DEV), k.to(DEV), v.to(DEV), cu_q.to(DEV), cu_k.to(DEV), max(span_q), max(span_k),
+        seqused_q=torch.tensor(used_q, dtype=torch.int32, device=DEV), seqused_k=torch.tensor(used_k, dtype=torch.int32, device=DEV),
+        qv=qv.to(DEV), window_size=window, return_attn_probs=True)
+    _ran(512, splits=1)
+    for i in range(2):
+        sl_q = slice(int(cu_q[i]), int(cu_q[i]) + used_q[i])
+        sl_k = slice(int(cu_k[i]), int(cu_k[i]) + used_k[i])
+        ref, pt, lse_ref = _refs(q[sl_q][None], k[sl_k][None], v[sl_k][None], qv[sl_q][None], window_size=window)
+        _check(out[sl_q][None], ref, pt)
+        _check_lse(lse[:, sl_q][None], lse_ref)
+
+
+@pytest.mark.parametrize("d,dv", [(24, 264), (56, 504)])
+def test_qv_split_at_odd_head_dims(d, dv):
+    """Three splits at V head dims that are no multiple of 32: the fp32 split epilogue's column clamp and the merge over
+    d_v / 8 chunks, out and LSE against the oracle."""
+    b, hk, h, dtype = 2, 1, 6, torch.float16
+    logical, cache, _ = _mla_cache(b, 500, hk, d, dv, dtype, None, seed=91 + d)
+    torch.manual_seed(92)
+    q = torch.randn(b, 3, h, d, dtype=dtype)
+    qv = torch.randn(b, 3, h, dv, dtype=dtype)
+    seqlens = torch.tensor([500, 301], dtype=torch.int32)
+    out, lse, *_ = _fa3().flash_attn_with_kvcache(q.to(DEV), cache[..., :d], cache[..., d:], qv=qv.to(DEV),
+                                                  cache_seqlens=seqlens.to(DEV), num_splits=3, causal=True, return_softmax_lse=True)
+    _ran(512, splits=3)
+    for i in range(b):
+        k_i, v_i = _kv_ref(logical, i, 0, int(seqlens[i]), d)
+        ref, pt, lse_ref = _refs(q[i:i + 1], k_i, v_i, qv[i:i + 1], causal=True)
+        _check(out[i:i + 1], ref, pt)
+        _check_lse(lse[i:i + 1], lse_ref)
