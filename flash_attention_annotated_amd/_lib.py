@@ -39,6 +39,10 @@ EXPORTED_SYMBOLS = (
     "fa_kvcache_append_params_size",
     "fa_rotary_apply",
     "fa_rotary_params_size",
+    "fa_kvcache_append_varlen",
+    "fa_kvcache_append_varlen_params_size",
+    "fa_rotary_apply_varlen",
+    "fa_rotary_varlen_params_size",
     "fa_fwd_combine",
     "fa_combine_params_size",
     # include/fa_bwd.h
@@ -166,6 +170,34 @@ class FaRotaryParams(ctypes.Structure):
         + [(f"{t}_{s}_stride", ctypes.c_int64) for t in ("src", "dst") for s in ("batch", "row", "head")]
         + [(n, ctypes.c_int32) for n in ("b", "s", "h", "d", "dtype", "rotary_dim", "rotary_interleaved", "per_row_positions")]
         + [("rotary_cos", ctypes.c_void_p), ("rotary_sin", ctypes.c_void_p), ("seqlen_offsets", ctypes.c_void_p)]
+    )
+
+
+class FaKvcacheAppendVarlenParams(ctypes.Structure):
+    """Field-for-field mirror of `struct fa_kvcache_append_varlen_params` (include/fa_fwd.h)."""
+
+    _fields_ = (
+        [("abi_version", ctypes.c_uint32), ("struct_size", ctypes.c_uint32)]
+        + [(n, ctypes.c_void_p) for n in ("k_new", "v_new", "k_cache", "v_cache")]
+        + [(f"{t}_{s}_stride", ctypes.c_int64) for t in ("knew", "vnew") for s in ("row", "head")]
+        + [(f"{t}_{s}_stride", ctypes.c_int64) for t in ("kcache", "vcache") for s in ("batch", "row", "head")]
+        + [(n, ctypes.c_int32) for n in ("b", "total_k_new", "max_seqlen_k_new", "seqlen_cache", "h_k", "d", "d_v", "dtype")]
+        + [(n, ctypes.c_void_p) for n in ("cu_seqlens_k_new", "cache_seqlens", "cache_batch_idx", "seqused_out", "block_table")]
+        + [("block_table_batch_stride", ctypes.c_int64), ("page_block_size", ctypes.c_int32), ("rotary_dim", ctypes.c_int32)]
+        + [(n, ctypes.c_void_p) for n in ("rotary_cos", "rotary_sin", "rotary_seqlens")]
+        + [("rotary_interleaved", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+    )
+
+
+class FaRotaryVarlenParams(ctypes.Structure):
+    """Field-for-field mirror of `struct fa_rotary_varlen_params` (include/fa_fwd.h)."""
+
+    _fields_ = (
+        [("abi_version", ctypes.c_uint32), ("struct_size", ctypes.c_uint32), ("src", ctypes.c_void_p), ("dst", ctypes.c_void_p)]
+        + [(f"{t}_{s}_stride", ctypes.c_int64) for t in ("src", "dst") for s in ("row", "head")]
+        + [(n, ctypes.c_int32) for n in ("b", "total_q", "max_seqlen_q", "h", "d", "dtype", "rotary_dim", "rotary_interleaved",
+                                         "per_row_positions", "reserved")]
+        + [(n, ctypes.c_void_p) for n in ("rotary_cos", "rotary_sin", "cu_seqlens_q", "offsets")]
     )
 
 
@@ -308,6 +340,18 @@ def load():
     lib.fa_rotary_params_size.restype = ctypes.c_uint32
     if lib.fa_rotary_params_size() != ctypes.sizeof(FaRotaryParams):
         raise RuntimeError("fa_rotary_params layout mismatch between include/fa_fwd.h and _lib")
+    lib.fa_kvcache_append_varlen.argtypes = [ctypes.POINTER(FaKvcacheAppendVarlenParams), ctypes.c_void_p]
+    lib.fa_kvcache_append_varlen.restype = ctypes.c_int
+    lib.fa_kvcache_append_varlen_params_size.argtypes = []
+    lib.fa_kvcache_append_varlen_params_size.restype = ctypes.c_uint32
+    if lib.fa_kvcache_append_varlen_params_size() != ctypes.sizeof(FaKvcacheAppendVarlenParams):
+        raise RuntimeError("fa_kvcache_append_varlen_params layout mismatch between include/fa_fwd.h and _lib")
+    lib.fa_rotary_apply_varlen.argtypes = [ctypes.POINTER(FaRotaryVarlenParams), ctypes.c_void_p]
+    lib.fa_rotary_apply_varlen.restype = ctypes.c_int
+    lib.fa_rotary_varlen_params_size.argtypes = []
+    lib.fa_rotary_varlen_params_size.restype = ctypes.c_uint32
+    if lib.fa_rotary_varlen_params_size() != ctypes.sizeof(FaRotaryVarlenParams):
+        raise RuntimeError("fa_rotary_varlen_params layout mismatch between include/fa_fwd.h and _lib")
     lib.fa_fwd_combine.argtypes = [ctypes.POINTER(FaCombineParams), ctypes.c_void_p]
     lib.fa_fwd_combine.restype = ctypes.c_int
     lib.fa_combine_params_size.argtypes = []

@@ -189,6 +189,126 @@ __global__ void kvcache_append_kernel(const fa_kvcache_append_params p) {
     }
 }
 
+// ---- ragged rows (a (total, h, d) tensor with cu_seqlens) -> wavefronts ------------------------------------------------------
+// Shared by kvcache_append_varlen_kernel and rotary_varlen_kernel.  One workgroup = 4 wavefronts x RAGGED_ROWS_PER_WAVE
+// consecutive rows; a wavefront works on one row at a time, its lanes on the row's 16-byte chunks in address order.  The row,
+// its sequence and everything looked up per sequence (fill level, cache entry, page, rotary position) are wave-uniform:
+// they come from blockIdx and the wave id through readfirstlane, so the lookups are one address per wavefront, not a gather.
+//  * max_len > 0 (the caller knows an upper bound of the lengths): grid (row blocks of max_len) x b, blockIdx.y = sequence;
+//  * max_len == 0: flat row blocks; cu_seqlens (b + 1 entries) is read once per workgroup into LDS and every wavefront
+//    finds the sequence of its row by a binary search there (in global memory past RAGGED_LDS_SEQS sequences).
+// Nothing loops over the batch.  body(seq, i, row) is called with row = cu[seq] + i, i < the sequence's length.
+constexpr int RAGGED_ROWS_PER_WAVE = 4, RAGGED_ROWS_PER_WG = 4 * RAGGED_ROWS_PER_WAVE, RAGGED_LDS_SEQS = 16383;
+
+__device__ __forceinline__ int ragged_find_seq(const int32_t *cu, int b, int row) {
+    int lo = 0, hi = b;  // the last s in [0, b) with cu[s] <= row: empty sequences in front of it are stepped over
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (__builtin_amdgcn_readfirstlane(cu[mid]) <= row) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+
+template <typename F>
+__device__ __forceinline__ void for_ragged_rows(const int32_t *__restrict__ cu, int b, int total, int max_len, F &&body) {
+    extern __shared__ int32_t ragged_cu_lds[];
+    const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
+    const int first = (int)blockIdx.x * RAGGED_ROWS_PER_WG + wave * RAGGED_ROWS_PER_WAVE;
+    if (max_len > 0) {
+        const int seq = blockIdx.y, c0 = cu[seq], len = min(cu[seq + 1], total) - c0;
+        for (int j = 0; j < RAGGED_ROWS_PER_WAVE && first + j < len; ++j) body(seq, first + j, c0 + first + j);
+        return;
+    }
+    const bool in_lds = b <= RAGGED_LDS_SEQS;  // (uniform: a kernel argument)
+    if (in_lds) {
+        for (int t = threadIdx.x; t <= b; t += blockDim.x) ragged_cu_lds[t] = cu[t];
+        __syncthreads();
+    }
+    const int end = min(total, in_lds ? ragged_cu_lds[b] : cu[b]);
+    for (int j = 0; j < RAGGED_ROWS_PER_WAVE && first + j < end; ++j) {
+        const int row = first + j;
+        const int seq = in_lds ? ragged_find_seq(ragged_cu_lds, b, row) : ragged_find_seq(cu, b, row);
+        const int c0 = __builtin_amdgcn_readfirstlane(in_lds ? ragged_cu_lds[seq] : cu[seq]);
+        body(seq, row - c0, row);
+    }
+}
+
+// ---- ragged KV-cache append (fa_kvcache_append_varlen): one pass over the new rows, 16-byte loads and stores, no atomics; the
+// lanes of a wavefront walk one row's (head, slot) items in address order (rotary_slot: two chunks of K, the same of V).
+template <typename T>
+__global__ __launch_bounds__(256) void kvcache_append_varlen_kernel(const fa_kvcache_append_varlen_params p) {
+    const int dv = p.d_v > 0 ? p.d_v : p.d;
+    const int slots = max((p.d / 8 + 1) / 2, (dv / 8 + 1) / 2), chunks = dv >> 3, items = p.h_k * slots;
+    const int lane = threadIdx.x & 63;
+    // the fill levels the attention launch reads: one entry per thread of the first workgroups (the grid holds >= b threads)
+    const int64_t gid = ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * blockDim.x + threadIdx.x;
+    if (gid < p.b) {
+        const int s = (int)gid;
+        p.seqused_out[s] = min(p.cache_seqlens[s] + (p.cu_seqlens_k_new[s + 1] - p.cu_seqlens_k_new[s]), p.seqlen_cache);
+    }
+    for_ragged_rows(p.cu_seqlens_k_new, p.b, p.total_k_new, p.max_seqlen_k_new, [&](int seq, int i, int row) {
+        const int fill = p.cache_seqlens[seq];
+        int dst_row = fill + i;
+        if (dst_row < 0 || dst_row >= p.seqlen_cache) return;  // past the capacity: dropped (wave-uniform)
+        const int pos = (p.rotary_seqlens ? p.rotary_seqlens[seq] : fill) + i;
+        int cb = p.cache_batch_idx ? p.cache_batch_idx[seq] : seq;
+        if (p.block_table) {
+            cb = p.block_table[seq * p.block_table_batch_stride + dst_row / p.page_block_size];
+            dst_row %= p.page_block_size;
+        }
+        const T *ks_row = (const T *)p.k_new + (int64_t)row * p.knew_row_stride;
+        const T *vs_row = (const T *)p.v_new + (int64_t)row * p.vnew_row_stride;
+        T *kd_row = (T *)p.k_cache + cb * p.kcache_batch_stride + dst_row * p.kcache_row_stride;
+        T *vd_row = (T *)p.v_cache + cb * p.vcache_batch_stride + dst_row * p.vcache_row_stride;
+        const int rd = p.rotary_cos ? p.rotary_dim : 0;
+        const T *cr = (const T *)p.rotary_cos + (int64_t)pos * (rd / 2);
+        const T *sr = (const T *)p.rotary_sin + (int64_t)pos * (rd / 2);
+        for (int it = lane; it < items; it += 64) {
+            const int hd = it / slots, slot = it % slots;
+            rotary_slot<T>(ks_row + hd * p.knew_head_stride, kd_row + hd * p.kcache_head_stride, p.d, rd,
+                           p.rotary_interleaved != 0, slot, cr, sr);
+            const T *vs = vs_row + hd * p.vnew_head_stride;
+            T *vd = vd_row + hd * p.vcache_head_stride;
+            const int c0 = 2 * slot, c1 = 2 * slot + 1;
+            if (c0 < chunks) *reinterpret_cast<uint4 *>(vd + c0 * 8) = *reinterpret_cast<const uint4 *>(vs + c0 * 8);
+            if (c1 < chunks) *reinterpret_cast<uint4 *>(vd + c1 * 8) = *reinterpret_cast<const uint4 *>(vs + c1 * 8);
+        }
+    });
+}
+
+// ---- rotary embedding of a ragged tensor (fa_rotary_apply_varlen): the same launch shape and sequence lookup
+template <typename T>
+__global__ __launch_bounds__(256) void rotary_varlen_kernel(const fa_rotary_varlen_params p) {
+    const int slots = (p.d / 8 + 1) / 2, items = p.h * slots;
+    const int lane = threadIdx.x & 63;
+    for_ragged_rows(p.cu_seqlens_q, p.b, p.total_q, p.max_seqlen_q, [&](int seq, int i, int row) {
+        const int pos = p.offsets[seq] + (p.per_row_positions ? i : 0);
+        const T *src_row = (const T *)p.src + (int64_t)row * p.src_row_stride;
+        T *dst_row = (T *)p.dst + (int64_t)row * p.dst_row_stride;
+        const T *cr = (const T *)p.rotary_cos + (int64_t)pos * (p.rotary_dim / 2);
+        const T *sr = (const T *)p.rotary_sin + (int64_t)pos * (p.rotary_dim / 2);
+        for (int it = lane; it < items; it += 64) {
+            const int hd = it / slots, slot = it % slots;
+            rotary_slot<T>(src_row + hd * p.src_head_stride, dst_row + hd * p.dst_head_stride, p.d, p.rotary_dim,
+                           p.rotary_interleaved != 0, slot, cr, sr);
+        }
+    });
+}
+
+// grid and LDS bytes of a for_ragged_rows launch over `total` rows of `b` sequences whose grid also holds `min_threads` threads
+// (the 2-D grid has a workgroup per sequence: at least b threads)
+void ragged_launch_shape(int b, int total, int max_len, int64_t min_threads, dim3 &grid, size_t &smem) {
+    if (max_len > 0) {
+        grid = dim3((unsigned)((max_len + RAGGED_ROWS_PER_WG - 1) / RAGGED_ROWS_PER_WG), (unsigned)b);
+        smem = 0;
+    } else {
+        const int64_t row_blocks = ((int64_t)total + RAGGED_ROWS_PER_WG - 1) / RAGGED_ROWS_PER_WG;
+        grid = dim3((unsigned)std::max<int64_t>({1, row_blocks, (min_threads + 255) / 256}));
+        smem = b <= RAGGED_LDS_SEQS ? sizeof(int32_t) * ((size_t)b + 1) : 0;
+    }
+}
+
 // ---- sign-encoded S_dmask (FA_FLAG_SDMASK_SIGNED, include/fa_fwd.h): what the reference's CUDA forward returns for
 // return_softmax under dropout (csrc/flash_attn/src/flash_fwd_kernel.h:350-360, 412-422; src/dropout.h:26-33), restated as a
 // pass of its own -- a testing aid there and here, not on the hot path.  One workgroup = 8 query rows of one (batch, head);
@@ -385,22 +505,37 @@ int effective_variant(const fa_fwd_params *p) {
 }
 
 // ---- split-KV plan (role of num_splits_heuristic / set_params_splitkv, csrc/flash_attn/flash_api.cpp:257-329) ---------
-// Only dense (non-varlen) 16-bit problems split.  Heuristic (num_splits == 0): split when the tiles leave most of the
+// 16-bit problems over dense K/V split: dense queries, and ragged queries over a batched cache (ragged_cache()); the
+// cu_seqlens_q + cu_seqlens_k problems never do.  Heuristic (num_splits == 0): split when the tiles leave most of the
 // 256 CUs idle, so that tiles x splits reaches ~2 workgroups per CU, with at least 4 key blocks (256 keys) per split.
 struct SplitPlan {
     int splits;
-    int64_t o_bytes, lse_bytes, total;  // partial O (fp32, (splits, b, sq, h, d)) and LSE (fp32, (splits, b, h, sq))
+    // partial O (fp32, (splits, b, sq, h, d); ragged queries (splits, total_q, h, d)) and LSE (fp32, (splits, b, h, sq) / (splits, h, total_q))
+    int64_t o_bytes, lse_bytes, total;
 };
+// ragged queries over a batched / paged cache: cu_seqlens_q without cu_seqlens_k, fill levels in seqused_k (include/fa_fwd.h)
+inline bool ragged_cache(const fa_fwd_params *p) { return p->cu_seqlens_q && !p->cu_seqlens_k; }
+// query rows of the whole problem, and an upper bound of its row blocks of `bm` rows: the host knows total_q and max_seqlen_q
+// of a ragged batch, not the lengths (no sync) -- every non-empty sequence has at most len / bm + 1 blocks, and at most
+// ceil(max_seqlen_q / bm)
+inline int64_t query_rows(const fa_fwd_params *p) { return p->cu_seqlens_q ? p->total_q : (int64_t)p->b * p->seqlen_q; }
+inline int64_t row_blocks_bound(const fa_fwd_params *p, int64_t bm, int64_t rows_per_query = 1) {
+    const int64_t per_seq = (p->seqlen_q * rows_per_query + bm - 1) / bm;
+    if (!p->cu_seqlens_q) return per_seq * p->b;
+    const int64_t seqs = std::min<int64_t>(p->b, p->total_q);
+    return std::min(seqs * per_seq, p->total_q * rows_per_query / bm + seqs);
+}
 SplitPlan split_plan(const fa_fwd_params *p, int variant) {
     SplitPlan sp{1, 0, 0, 0};
-    if (p->cu_seqlens_q || p->dtype == FA_DTYPE_FP8_E4M3 || p->seqlen_q <= 0 || p->seqlen_k <= 0) return sp;
+    if (p->cu_seqlens_k || p->dtype == FA_DTYPE_FP8_E4M3 || p->seqlen_q <= 0 || p->seqlen_k <= 0) return sp;
+    if (p->cu_seqlens_q && p->total_q <= 0) return sp;
     if (p->p_dropout > 0.f) return sp;  // (the reference does not split under dropout either: flash_api.cpp:307)
     if (own_dv(p)) return sp;           // (the partials and the merge are laid out for d columns)
     int n = p->num_splits;
     const int n_blocks = (p->seqlen_k + 63) / 64;
     if (n == 0) {
         const int bm = block_m_of(variant, wide_dim(p));
-        const int64_t tiles = (int64_t)((p->seqlen_q + bm - 1) / bm) * p->h * p->b;
+        const int64_t tiles = row_blocks_bound(p, bm) * p->h;
         // two workgroups of the 4-wave shape fit a CU: aim at ~4 per CU there, ~2 per CU for the 256-row kernel
         const int64_t cap = (variant == 2) ? 512 : 128, target = (variant == 2) ? 1024 : 512;
         n = 1;
@@ -412,23 +547,24 @@ SplitPlan split_plan(const fa_fwd_params *p, int variant) {
     n = std::max(1, std::min(n, std::min(n_blocks, 128)));
     if (n <= 1) return sp;
     sp.splits = n;
-    const int64_t rows = (int64_t)p->b * p->seqlen_q;
+    const int64_t rows = query_rows(p);
     sp.o_bytes = (n * rows * p->h * p->d * 4 + 255) & ~int64_t(255);
     sp.lse_bytes = (n * rows * p->h * 4 + 255) & ~int64_t(255);
     sp.total = sp.o_bytes + sp.lse_bytes;
     return sp;
 }
 
-// Split plan of the qv kernel: dense problems only, like split_plan.  Heuristic (num_splits == 0): one workgroup fills a CU
+// Split plan of the qv kernel: the problems split_plan takes.  Heuristic (num_splits == 0): one workgroup fills a CU
 // (its LDS), so the (batch, kv head, row block) groups are multiplied up to ~2 workgroups per CU of 256, with at least 4 key
-// blocks per split.  Partials: O (splits, b, seqlen_q, h, d_v), LSE (splits, b, h, seqlen_q), fp32.
+// blocks per split.  Partials: O (splits, b, seqlen_q, h, d_v), LSE (splits, b, h, seqlen_q), fp32
+// (ragged queries: (splits, total_q, h, d_v) and (splits, h, total_q)).
 SplitPlan split_plan_qv(const fa_fwd_params *p) {
     SplitPlan sp{1, 0, 0, 0};
-    if (p->cu_seqlens_q || p->seqlen_q <= 0 || p->seqlen_k <= 0) return sp;
+    if (p->cu_seqlens_k || p->seqlen_q <= 0 || p->seqlen_k <= 0 || (p->cu_seqlens_q && p->total_q <= 0)) return sp;
     int n = p->num_splits;
     const int n_blocks = (p->seqlen_k + 63) / 64;
     if (n == 0) {
-        const int64_t groups = (int64_t)p->b * p->h_k * (((int64_t)p->seqlen_q * (p->h / p->h_k) + 31) / 32);
+        const int64_t groups = row_blocks_bound(p, 32, p->h / p->h_k) * p->h_k;
         n = 1;
         if (groups < 512 && n_blocks >= 8) n = (int)std::max<int64_t>(1, std::min<int64_t>((512 + groups - 1) / groups, n_blocks / 4));
         n = std::min(n, 64);
@@ -436,7 +572,7 @@ SplitPlan split_plan_qv(const fa_fwd_params *p) {
     n = std::max(1, std::min(n, std::min(n_blocks, 128)));
     if (n <= 1) return sp;
     sp.splits = n;
-    const int64_t rows = (int64_t)p->b * p->seqlen_q;
+    const int64_t rows = query_rows(p);
     sp.o_bytes = (n * rows * p->h * dv_of(p) * 4 + 255) & ~int64_t(255);
     sp.lse_bytes = (n * rows * p->h * 4 + 255) & ~int64_t(255);
     sp.total = sp.o_bytes + sp.lse_bytes;
@@ -936,6 +1072,74 @@ int fa_rotary_apply(const fa_rotary_params *p, void *stream_) {
     return FA_OK;
 }
 
+uint32_t fa_kvcache_append_varlen_params_size(void) { return (uint32_t)sizeof(fa_kvcache_append_varlen_params); }
+
+int fa_kvcache_append_varlen(const fa_kvcache_append_varlen_params *p, void *stream_) {
+    if (!p) return FA_ERR_NULL_POINTER;
+    if (p->abi_version != FA_ABI_VERSION || p->struct_size != sizeof(fa_kvcache_append_varlen_params)) return FA_ERR_BAD_ABI;
+    if (p->dtype != FA_DTYPE_FP16 && p->dtype != FA_DTYPE_BF16) return FA_ERR_BAD_DTYPE;
+    if (p->b <= 0 || p->h_k <= 0 || p->total_k_new < 0 || p->max_seqlen_k_new < 0 || p->seqlen_cache < 0) return FA_ERR_BAD_SHAPE;
+    if (p->d <= 0 || p->d > 256 || p->d % 8 != 0) return FA_ERR_BAD_HEAD_DIM;
+    if (p->d_v < 0 || p->d_v > 512 || p->d_v % 8 != 0) return FA_ERR_BAD_HEAD_DIM;  // 0 = d
+    if (!p->cu_seqlens_k_new || !p->cache_seqlens || !p->seqused_out) return FA_ERR_NULL_POINTER;
+    if (p->total_k_new > 0 && (!p->k_new || !p->v_new || !p->k_cache || !p->v_cache)) return FA_ERR_NULL_POINTER;
+    if (p->block_table && (p->page_block_size <= 0 || p->cache_batch_idx)) return FA_ERR_BAD_SHAPE;
+    if (p->block_table && (p->block_table_batch_stride < 0 || p->block_table_batch_stride > 0x7fffffff)) return FA_ERR_BAD_STRIDE;
+    if (p->rotary_cos) {
+        if (!p->rotary_sin) return FA_ERR_NULL_POINTER;
+        if (p->rotary_dim <= 0 || p->rotary_dim > p->d || p->rotary_dim % 16 != 0) return FA_ERR_BAD_SHAPE;
+        if (reinterpret_cast<uintptr_t>(p->rotary_cos) % 16 != 0 || reinterpret_cast<uintptr_t>(p->rotary_sin) % 16 != 0)
+            return FA_ERR_BAD_STRIDE;
+    }
+    const int64_t strides[] = {p->knew_row_stride, p->knew_head_stride, p->vnew_row_stride, p->vnew_head_stride,
+                               p->kcache_batch_stride, p->kcache_row_stride, p->kcache_head_stride,
+                               p->vcache_batch_stride, p->vcache_row_stride, p->vcache_head_stride};
+    for (int64_t s : strides)
+        if (s % 8 != 0) return FA_ERR_BAD_STRIDE;
+    const void *ptrs[] = {p->k_new, p->v_new, p->k_cache, p->v_cache};
+    for (const void *ptr : ptrs)
+        if (reinterpret_cast<uintptr_t>(ptr) % 16 != 0) return FA_ERR_BAD_STRIDE;
+    fa_kvcache_append_varlen_params kp = *p;
+    if (kp.b > 65535 || kp.total_k_new == 0) kp.max_seqlen_k_new = 0;  // (grid.y; no rows: the launch only writes seqused_out)
+    dim3 grid;
+    size_t smem;
+    ragged_launch_shape(kp.b, kp.total_k_new, kp.max_seqlen_k_new, kp.b, grid, smem);
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    if (p->dtype == FA_DTYPE_FP16) hipLaunchKernelGGL(kvcache_append_varlen_kernel<_Float16>, grid, dim3(256), smem, stream, kp);
+    else hipLaunchKernelGGL(kvcache_append_varlen_kernel<__bf16>, grid, dim3(256), smem, stream, kp);
+    if (hipGetLastError() != hipSuccess) return FA_ERR_LAUNCH;
+    return FA_OK;
+}
+
+uint32_t fa_rotary_varlen_params_size(void) { return (uint32_t)sizeof(fa_rotary_varlen_params); }
+
+int fa_rotary_apply_varlen(const fa_rotary_varlen_params *p, void *stream_) {
+    if (!p) return FA_ERR_NULL_POINTER;
+    if (p->abi_version != FA_ABI_VERSION || p->struct_size != sizeof(fa_rotary_varlen_params)) return FA_ERR_BAD_ABI;
+    if (p->dtype != FA_DTYPE_FP16 && p->dtype != FA_DTYPE_BF16) return FA_ERR_BAD_DTYPE;
+    if (p->b <= 0 || p->h <= 0 || p->total_q < 0 || p->max_seqlen_q < 0) return FA_ERR_BAD_SHAPE;
+    if (p->d <= 0 || p->d > 256 || p->d % 8 != 0) return FA_ERR_BAD_HEAD_DIM;
+    if (p->rotary_dim <= 0 || p->rotary_dim > p->d || p->rotary_dim % 16 != 0) return FA_ERR_BAD_SHAPE;
+    if (p->total_q == 0) return FA_OK;
+    if (!p->src || !p->dst || !p->rotary_cos || !p->rotary_sin || !p->cu_seqlens_q || !p->offsets) return FA_ERR_NULL_POINTER;
+    const int64_t strides[] = {p->src_row_stride, p->src_head_stride, p->dst_row_stride, p->dst_head_stride};
+    for (int64_t s : strides)
+        if (s % 8 != 0) return FA_ERR_BAD_STRIDE;
+    const void *ptrs[] = {p->src, p->dst, p->rotary_cos, p->rotary_sin};
+    for (const void *ptr : ptrs)
+        if (reinterpret_cast<uintptr_t>(ptr) % 16 != 0) return FA_ERR_BAD_STRIDE;
+    fa_rotary_varlen_params kp = *p;
+    if (kp.b > 65535) kp.max_seqlen_q = 0;  // (grid.y)
+    dim3 grid;
+    size_t smem;
+    ragged_launch_shape(kp.b, kp.total_q, kp.max_seqlen_q, 0, grid, smem);
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    if (p->dtype == FA_DTYPE_FP16) hipLaunchKernelGGL(rotary_varlen_kernel<_Float16>, grid, dim3(256), smem, stream, kp);
+    else hipLaunchKernelGGL(rotary_varlen_kernel<__bf16>, grid, dim3(256), smem, stream, kp);
+    if (hipGetLastError() != hipSuccess) return FA_ERR_LAUNCH;
+    return FA_OK;
+}
+
 uint32_t fa_combine_params_size(void) { return (uint32_t)sizeof(fa_combine_params); }
 
 int fa_fwd_combine(const fa_combine_params *p, void *stream_) {
@@ -987,7 +1191,10 @@ int fa_fwd_validate(const fa_fwd_params *p) {
     if (generic_only(p) && p->p_dropout > 0.f) return FA_ERR_UNSUPPORTED;  // (no dropout on the FA3 surface)
     if (p->attention_chunk > 0 && p->s_dmask) return FA_ERR_UNSUPPORTED;  // (the S_dmask pass knows windows only)
     if (p->h % p->h_k != 0) return FA_ERR_BAD_HEADS;
-    if ((p->cu_seqlens_q == nullptr) != (p->cu_seqlens_k == nullptr)) return FA_ERR_BAD_SHAPE;
+    if (p->cu_seqlens_k && !p->cu_seqlens_q) return FA_ERR_BAD_SHAPE;
+    const bool ragged = ragged_cache(p);  // ragged queries over a batched cache: the fill levels come through seqused_k
+    if (ragged && !p->seqused_k) return FA_ERR_BAD_SHAPE;
+    if (ragged && (fp8 || p->p_dropout > 0.f || p->alibi_slopes)) return FA_ERR_UNSUPPORTED;  // (what the FA3 cache route refuses)
     if (p->cu_seqlens_q && p->total_q < 0) return FA_ERR_BAD_SHAPE;
     const bool empty = (p->seqlen_q == 0) || (p->cu_seqlens_q && p->total_q == 0);
     if (!empty) {
@@ -1007,6 +1214,8 @@ int fa_fwd_validate(const fa_fwd_params *p) {
         const int64_t bs[] = {p->q_batch_stride, p->k_batch_stride, p->v_batch_stride, p->o_batch_stride};
         for (int64_t s : bs)
             if (s % 8 != 0) return FA_ERR_BAD_STRIDE;
+    } else if (ragged && (p->k_batch_stride % 8 != 0 || p->v_batch_stride % 8 != 0)) {
+        return FA_ERR_BAD_STRIDE;
     }
     const void *ptrs[] = {p->q, p->k, p->v, p->o};
     for (const void *ptr : ptrs)
@@ -1033,7 +1242,7 @@ int fa_fwd_validate(const fa_fwd_params *p) {
         if (p->s_dmask_rows < p->seqlen_q || p->s_dmask_cols < p->seqlen_k || p->s_dmask_block_n <= 0) return FA_ERR_BAD_SHAPE;
         if (p->seqlen_k > 32768) return FA_ERR_UNSUPPORTED;  // (one row of scores in LDS)
     }
-    if (p->kv_batch_idx && (p->cu_seqlens_q || fp8)) return FA_ERR_UNSUPPORTED;  // dense 16-bit caches only
+    if (p->kv_batch_idx && (p->cu_seqlens_k || fp8)) return FA_ERR_UNSUPPORTED;  // dense 16-bit caches only (ragged queries included)
     if (p->leftpad_k && (p->block_table || fp8)) return FA_ERR_UNSUPPORTED;  // (:1396 "Paged KV and leftpad_k" not together)
     if (p->block_table) {
         if (fp8 || p->kv_batch_idx) return FA_ERR_UNSUPPORTED;  // "Paged KVcache does not support cache_batch_idx" (:1247)
@@ -1143,6 +1352,10 @@ int fa_fwd(const fa_fwd_params *p, void *stream_) {
         kp.o_row_stride = (int64_t)p->h * dv_of(p); kp.o_head_stride = dv_of(p); kp.o_batch_stride = kp.o_row_stride * p->seqlen_q;
         kp.o_split_stride = kp.o_batch_stride * p->b;
         kp.lse_split_stride = (int64_t)p->b * p->h * p->seqlen_q;
+        if (p->cu_seqlens_q) {  // ragged queries: (splits, total_q, h, d_v) and (splits, h, total_q)
+            kp.o_split_stride = kp.o_row_stride * p->total_q;
+            kp.lse_split_stride = (int64_t)p->h * p->total_q;
+        }
     }
 
     // window normalisation: csrc/flash_attn/flash_api.cpp:396-402
@@ -1175,7 +1388,7 @@ int fa_fwd(const fa_fwd_params *p, void *stream_) {
     kp.rng_state = p->rng_state;
     const bool sdmask_signed = (p->flags & FA_FLAG_SDMASK_SIGNED) && p->s_dmask;
     kp.s_dmask = sdmask_signed ? nullptr : p->s_dmask;
-    kp.kv_batch_idx = p->cu_seqlens_q ? nullptr : p->kv_batch_idx;
+    kp.kv_batch_idx = p->kv_batch_idx;  // (dense K/V only: fa_fwd_validate)
     kp.block_table = p->block_table;
     kp.bt_bs = (int32_t)p->block_table_batch_stride;
     kp.page_size = p->page_block_size;
@@ -1216,18 +1429,20 @@ int fa_fwd(const fa_fwd_params *p, void *stream_) {
         if (st_sd != FA_OK) return st_sd;
     }
     if (st_main != FA_OK || sp.splits <= 1) return st_main;
-    // merge the partial results into the caller's out / softmax_lse
+    // merge the partial results into the caller's out / softmax_lse.  Ragged queries are one "batch" of total_q rows to the
+    // merge: its partials are then (splits, 1, total_q, h, d) / (splits, 1, h, total_q) and out / lse (total_q, h, d) / (h, total_q)
     const int dw = dv_of(p);  // (= d on every path but the qv kernel's: the others never split with a V head dim of its own)
-    const int64_t total = (int64_t)p->b * p->seqlen_q * p->h * (dw / 8);
+    const int mb = p->cu_seqlens_q ? 1 : p->b, msq = p->cu_seqlens_q ? p->total_q : p->seqlen_q;
+    const int64_t total = (int64_t)mb * msq * p->h * (dw / 8);
     const int blocks = (int)std::min<int64_t>((total + 255) / 256, 256 * 8);
     if (bf16)
         hipLaunchKernelGGL(combine_splits_kernel<__bf16>, dim3(blocks), dim3(256), 0, stream, static_cast<const float *>(kp.o),
-                           kp.lse, static_cast<__bf16 *>(p->o), p->softmax_lse, sp.splits, p->b, p->seqlen_q, p->h, dw,
+                           kp.lse, static_cast<__bf16 *>(p->o), p->softmax_lse, sp.splits, mb, msq, p->h, dw,
                            p->o_batch_stride, p->o_row_stride, p->o_head_stride);
     else
         hipLaunchKernelGGL(combine_splits_kernel<_Float16>, dim3(blocks), dim3(256), 0, stream,
                            static_cast<const float *>(kp.o), kp.lse, static_cast<_Float16 *>(p->o), p->softmax_lse,
-                           sp.splits, p->b, p->seqlen_q, p->h, dw, p->o_batch_stride, p->o_row_stride, p->o_head_stride);
+                           sp.splits, mb, msq, p->h, dw, p->o_batch_stride, p->o_row_stride, p->o_head_stride);
     if (hipGetLastError() != hipSuccess) return FA_ERR_LAUNCH;
     return FA_OK;
 }

@@ -379,8 +379,8 @@ __global__ __launch_bounds__(QV_NWAVES * 64, 1) void fwd_kernel_qv(const QvParam
     if (!row_ok) return;
     const int64_t row_o = p.cu_seqlens_q ? (int64_t)(q0 + my_row) : (int64_t)my_row;
     if (wave == 0 && hh == 0) {
-        const int64_t li = p.cu_seqlens_q ? (int64_t)head * p.total_q + row_o
-                                          : ((int64_t)batch * p.h + head) * p.seqlen_q + my_row + split * p.lse_split_stride;
+        const int64_t li = (p.cu_seqlens_q ? (int64_t)head * p.total_q + row_o : ((int64_t)batch * p.h + head) * p.seqlen_q + my_row) +
+                           split * p.lse_split_stride;
         p.lse[li] = empty ? INFINITY : m_run * sc.scale + __logf(l_tot);
     }
     const int64_t o_off = (p.cu_seqlens_q ? 0 : (int64_t)batch * p.o_batch_stride) + row_o * p.o_row_stride +

@@ -138,7 +138,7 @@ void launch_fwd(const Tensor &q, const Tensor &k, const Tensor &v, const Tensor 
     if (a.varlen) {
         p.q_row_stride = q.stride(0); p.q_head_stride = q.stride(1);
         p.o_row_stride = out.stride(0); p.o_head_stride = out.stride(1);
-        if (paged) {  // k, v: (num_blocks, page_block_size, h_k, d)
+        if (paged || k.dim() == 4) {  // k, v: (num_blocks, page_block_size, h_k, d), or a batched cache under ragged queries
             p.k_batch_stride = k.stride(0); p.k_row_stride = k.stride(1); p.k_head_stride = k.stride(2);
             p.v_batch_stride = v.stride(0); p.v_row_stride = v.stride(1); p.v_head_stride = v.stride(2);
         } else {
@@ -146,7 +146,7 @@ void launch_fwd(const Tensor &q, const Tensor &k, const Tensor &v, const Tensor 
             p.v_row_stride = v.stride(0); p.v_head_stride = v.stride(1);
         }
         p.total_q = (int32_t)q.size(0);
-        p.total_k = paged ? 0 : (int32_t)k.size(0);
+        p.total_k = k.dim() == 4 ? 0 : (int32_t)k.size(0);
         p.h = (int32_t)q.size(1); p.h_k = (int32_t)k.size(-2); p.d = (int32_t)q.size(2);
     } else {
         p.q_batch_stride = q.stride(0); p.q_row_stride = q.stride(1); p.q_head_stride = q.stride(2);
@@ -622,6 +622,65 @@ void kvcache_append(const Tensor &k_new, const Tensor &v_new, const Tensor &k_ca
     TORCH_CHECK(st == 0, "fa_kvcache_append failed (", st, "): ", fa_strerror(st));
 }
 
+void kvcache_append_varlen(const Tensor &k_new, const Tensor &v_new, const Tensor &cu_seqlens_k_new, const Tensor &k_cache,
+                           const Tensor &v_cache, const Tensor &cache_seqlens, const Tensor &seqused_out,
+                           const OptTensor &cache_batch_idx, const OptTensor &block_table, const OptTensor &rotary_cos,
+                           const OptTensor &rotary_sin, bool rotary_interleaved, const OptTensor &rotary_seqlens) {
+    fa_kvcache_append_varlen_params p{};
+    p.abi_version = FA_ABI_VERSION;
+    p.struct_size = sizeof(fa_kvcache_append_varlen_params);
+    p.k_new = k_new.data_ptr(); p.v_new = v_new.data_ptr(); p.k_cache = k_cache.data_ptr(); p.v_cache = v_cache.data_ptr();
+    p.knew_row_stride = k_new.stride(0); p.knew_head_stride = k_new.stride(1);
+    p.vnew_row_stride = v_new.stride(0); p.vnew_head_stride = v_new.stride(1);
+    p.kcache_batch_stride = k_cache.stride(0); p.kcache_row_stride = k_cache.stride(1); p.kcache_head_stride = k_cache.stride(2);
+    p.vcache_batch_stride = v_cache.stride(0); p.vcache_row_stride = v_cache.stride(1); p.vcache_head_stride = v_cache.stride(2);
+    p.b = (int32_t)cache_seqlens.numel(); p.total_k_new = (int32_t)k_new.size(0); p.h_k = (int32_t)k_new.size(1);
+    p.d = (int32_t)k_new.size(2);
+    p.max_seqlen_k_new = 0;  // (the FA3 call carries no bound of the new lengths, hopper/flash_api.cpp:948: the launch searches)
+    p.seqlen_cache = (int32_t)k_cache.size(1);
+    if (v_cache.size(3) != k_cache.size(3)) p.d_v = (int32_t)v_cache.size(3);
+    if (block_table.has_value()) {
+        p.block_table = static_cast<const int32_t *>(block_table->data_ptr());
+        p.block_table_batch_stride = block_table->stride(0);
+        p.page_block_size = (int32_t)k_cache.size(1);
+        p.seqlen_cache = (int32_t)(block_table->size(1) * k_cache.size(1));
+    }
+    p.cu_seqlens_k_new = static_cast<const int32_t *>(cu_seqlens_k_new.data_ptr());
+    p.cache_seqlens = static_cast<const int32_t *>(cache_seqlens.data_ptr());
+    p.cache_batch_idx = static_cast<const int32_t *>(ptr(cache_batch_idx));
+    p.seqused_out = static_cast<int32_t *>(seqused_out.data_ptr());
+    p.dtype = dtype_code(k_new);
+    if (rotary_cos.has_value()) {
+        p.rotary_cos = rotary_cos->data_ptr(); p.rotary_sin = rotary_sin->data_ptr();
+        p.rotary_dim = (int32_t)rotary_cos->size(1) * 2;
+        p.rotary_interleaved = rotary_interleaved ? 1 : 0;
+        p.rotary_seqlens = static_cast<const int32_t *>(ptr(rotary_seqlens));
+    }
+    const int st = fa_kvcache_append_varlen(&p, current_stream(k_new));
+    TORCH_CHECK(st == 0, "fa_kvcache_append_varlen failed (", st, "): ", fa_strerror(st));
+}
+
+void rotary_apply_varlen(const Tensor &src, const Tensor &dst, const Tensor &cu_seqlens_q, int64_t max_seqlen_q, const Tensor &cos,
+                         const Tensor &sin, const Tensor &offsets, bool interleaved, bool per_row_positions) {
+    fa_rotary_varlen_params p{};
+    p.abi_version = FA_ABI_VERSION;
+    p.struct_size = sizeof(fa_rotary_varlen_params);
+    p.src = src.data_ptr(); p.dst = dst.data_ptr();
+    p.src_row_stride = src.stride(0); p.src_head_stride = src.stride(1);
+    p.dst_row_stride = dst.stride(0); p.dst_head_stride = dst.stride(1);
+    p.b = (int32_t)offsets.numel(); p.total_q = (int32_t)src.size(0); p.max_seqlen_q = (int32_t)max_seqlen_q;
+    p.h = (int32_t)src.size(1); p.d = (int32_t)src.size(2);
+    p.dtype = dtype_code(src);
+    p.rotary_dim = (int32_t)cos.size(1) * 2;
+    p.rotary_interleaved = interleaved ? 1 : 0;
+    p.per_row_positions = per_row_positions ? 1 : 0;
+    p.rotary_cos = cos.data_ptr(); p.rotary_sin = sin.data_ptr();
+    p.cu_seqlens_q = static_cast<const int32_t *>(cu_seqlens_q.data_ptr());
+    p.offsets = static_cast<const int32_t *>(offsets.data_ptr());
+    const int st = fa_rotary_apply_varlen(&p, current_stream(src));
+    TORCH_CHECK(st == 0, "fa_rotary_apply_varlen failed (", st, "): ", fa_strerror(st));
+}
+
 // mha_fwd_kvcache, csrc/flash_attn/flash_api.cpp:1202-1476 (+ the page-size rule of the calling surface: FA2 256, FA3 any)
 std::vector<Tensor> fwd_kvcache_impl(Tensor q, const Tensor &kcache, const Tensor &vcache, OptTensor k_, OptTensor v_,
                                      OptTensor seqlens_k_, OptTensor rotary_cos_, OptTensor rotary_sin_,
@@ -820,15 +879,191 @@ void fa3_window(int64_t seqlen_q, int64_t seqlen_k, int64_t &left, int64_t &righ
     if (right >= seqlen_q - 1) right = -1;
 }
 
+// One continuous-batching step over a KV cache (flash_attn_with_kvcache(..., cu_seqlens_q=, cu_seqlens_k_new=, max_seqlen_q=),
+// hopper/flash_api.cpp:736-760, 929-975): q is ragged (total_q, h, d) with cu_seqlens_q, k / v the batched or paged cache with
+// its fill levels in seqused_k, the new keys / values dense (b, s_new, h_k, .) or ragged with cu_seqlens_k_new.  The append
+// (fa_kvcache_append_varlen writes the new fill levels on the device) and the rotary pass of q run in front of one fa_fwd
+// on the ragged-queries-over-a-cache form; nothing here reads device data, so the step can be captured in a graph.
+// max_seqlen_q == 1 with total_q == batch_size is, by shapes alone, one query row per sequence: q is viewed as (b, 1, h, d)
+// and the step takes the dense decode route (its GQA swap and split heuristic), the results viewed back to the ragged shapes.
+std::tuple<Tensor, Tensor> fwd_kvcache_ragged(const Tensor &q, const Tensor &kcache, const Tensor &vcache, const OptTensor &k_new,
+                                              const OptTensor &v_new, const OptTensor &qv, const OptTensor &out_,
+                                              const Tensor &cu_seqlens_q, const OptTensor &cu_seqlens_k_new,
+                                              const OptTensor &seqused_q, const OptTensor &seqused_k, int64_t max_seqlen_q,
+                                              const OptTensor &page_table, const OptTensor &kv_batch_idx, const OptTensor &leftpad_k,
+                                              const OptTensor &rotary_cos, const OptTensor &rotary_sin, const OptTensor &seqlens_rotary,
+                                              double softmax_scale, bool is_causal, int64_t window_size_left,
+                                              int64_t window_size_right, double softcap, bool is_rotary_interleaved, int64_t num_splits) {
+    const auto q_dtype = q.scalar_type();
+    CHECK_DEVICE(cu_seqlens_q, "cu_seqlens_q");
+    TORCH_CHECK(cu_seqlens_q.is_contiguous(), "cu_seqlens_q must be contiguous");
+    TORCH_CHECK(cu_seqlens_q.scalar_type() == at::kInt, "cu_seqlens_q must have dtype torch.int32");  // :744
+    TORCH_CHECK(max_seqlen_q >= 0, "max_seqlen_q must be provided if cu_seqlens_q is provided");      // :745
+    TORCH_CHECK(q.dim() == 3, "q must have shape (total_q, num_heads, head_size)");
+    TORCH_CHECK(seqused_k.has_value(), "seqused_k must be provided for a KV-cache call with cu_seqlens_q");
+    const bool paged = page_table.has_value();
+    if (paged) TORCH_CHECK(!kv_batch_idx.has_value(), "Paged KVcache does not support cache_batch_idx");
+    TORCH_CHECK(kcache.dim() == 4 && vcache.dim() == 4, "kcache, vcache must have 4 dimensions");
+    const int64_t total_q = q.size(0), num_heads = q.size(1), head_size = q.size(2);
+    const int64_t batch_size = cu_seqlens_q.numel() - 1;
+    const int64_t num_heads_k = kcache.size(2), head_size_v = vcache.size(3);
+    TORCH_CHECK(batch_size > 0, "batch size must be positive");
+    TORCH_CHECK(head_size <= 256, "FlashAttention forward only supports head dimension at most 256");
+    TORCH_CHECK(head_size % 8 == 0, "head_size should be a multiple of 8");
+    TORCH_CHECK(num_heads_k > 0 && num_heads % num_heads_k == 0, "Number of heads in key/value must divide number of heads in query");
+    int64_t seqlen_k = kcache.size(1), batch_size_c = kcache.size(0);
+    if (paged) {
+        auto pr = check_block_table(*page_table, kcache, batch_size, 1);
+        seqlen_k = pr.second * pr.first; batch_size_c = batch_size;
+        CHECK_SHAPE(kcache, "kcache", kcache.size(0), pr.first, num_heads_k, head_size);
+        CHECK_SHAPE(vcache, "vcache", kcache.size(0), pr.first, num_heads_k, head_size_v);
+    } else {
+        CHECK_SHAPE(kcache, "kcache", batch_size_c, seqlen_k, num_heads_k, head_size);
+        CHECK_SHAPE(vcache, "vcache", batch_size_c, seqlen_k, num_heads_k, head_size_v);
+    }
+    for (const auto &[t, name] : {std::make_pair(&seqused_q, "seqused_q"), std::make_pair(&seqused_k, "seqused_k")})
+        if (t->has_value()) {
+            TORCH_CHECK((*t)->scalar_type() == at::kInt, name, " must have dtype int32");  // :830, :836
+            TORCH_CHECK((*t)->is_cuda() && (*t)->is_contiguous() && (*t)->dim() == 1 && (*t)->numel() == batch_size, name,
+                        " must be a contiguous CUDA tensor of shape (batch_size,)");
+        }
+    check_leftpad(leftpad_k, batch_size, paged);
+    if (kv_batch_idx.has_value()) {
+        CHECK_DEVICE(*kv_batch_idx, "kv_batch_idx");
+        TORCH_CHECK(kv_batch_idx->is_contiguous(), "kv_batch_idx must be contiguous");
+        TORCH_CHECK(kv_batch_idx->scalar_type() == at::kInt, "kv_batch_idx must have dtype int32");  // :1088
+        CHECK_SHAPE(*kv_batch_idx, "kv_batch_idx", batch_size);
+    } else {
+        TORCH_CHECK(batch_size_c >= batch_size, "the KV cache must have at least batch_size entries");
+    }
+    TORCH_CHECK(aligned(kcache) && aligned(vcache),
+                "the KV cache must be 16-byte aligned with row/head/batch strides that are multiples of 8");
+    const bool ragged_new = cu_seqlens_k_new.has_value();
+    if (k_new.has_value()) {  // :929-975
+        TORCH_CHECK(k_new->scalar_type() == q_dtype, "k_new must have the same dtype as query");
+        TORCH_CHECK(v_new->scalar_type() == q_dtype, "v_new must have the same dtype as query");
+        CHECK_DEVICE(*k_new, "k_new"); CHECK_DEVICE(*v_new, "v_new");
+        TORCH_CHECK(k_new->stride(-1) == 1, "k_new tensor must have contiguous last dimension");
+        TORCH_CHECK(v_new->stride(-1) == 1, "v_new tensor must have contiguous last dimension");
+        if (ragged_new) {
+            CHECK_DEVICE(*cu_seqlens_k_new, "cu_seqlens_k_new");
+            TORCH_CHECK(cu_seqlens_k_new->is_contiguous(), "cu_seqlens_k_new must be contiguous");
+            TORCH_CHECK(cu_seqlens_k_new->scalar_type() == at::kInt, "cu_seqlens_k_new must have dtype torch.int32");  // :939
+            TORCH_CHECK(k_new->dim() == 3, "k_new must have shape (total_k_new, num_heads_k, head_size) with cu_seqlens_k_new");
+            CHECK_SHAPE(*k_new, "k_new", k_new->size(0), num_heads_k, head_size);
+            CHECK_SHAPE(*v_new, "v_new", k_new->size(0), num_heads_k, head_size_v);
+            CHECK_SHAPE(*cu_seqlens_k_new, "cu_seqlens_k_new", batch_size + 1);
+        } else {
+            TORCH_CHECK(k_new->dim() == 4, "k_new must have shape (batch_size, seqlen_k_new, num_heads_k, head_size) without cu_seqlens_k_new");
+            CHECK_SHAPE(*k_new, "k_new", batch_size, k_new->size(1), num_heads_k, head_size);
+            CHECK_SHAPE(*v_new, "v_new", batch_size, k_new->size(1), num_heads_k, head_size_v);
+        }
+    } else {
+        TORCH_CHECK(!ragged_new, "cu_seqlens_k_new needs k_new and v_new");
+    }
+    const bool rotary = rotary_cos.has_value();
+    if (rotary) {  // (:1050-1072; the texts of the dense route)
+        TORCH_CHECK(k_new.has_value(), "If rotary cos/sin are provided, new key / value to be appended to KV cache must also be provided");
+        CHECK_DEVICE(*rotary_cos, "rotary_cos"); CHECK_DEVICE(*rotary_sin, "rotary_sin");
+        TORCH_CHECK(rotary_cos->dim() == 2 && rotary_sin->sizes() == rotary_cos->sizes(), "rotary_cos / rotary_sin must have shape (seqlen_ro, rotary_dim / 2)");
+        const int64_t rotary_dim = rotary_cos->size(1) * 2;
+        TORCH_CHECK(rotary_dim <= head_size, "rotary_dim must be <= headdim");
+        TORCH_CHECK(rotary_dim % 16 == 0, "Only rotary dimensions divisible by 16 are currently supported");
+        TORCH_CHECK(rotary_cos->size(0) >= seqlen_k, "cos/sin seqlen must be at least the seqlen of KV cache");
+        TORCH_CHECK(rotary_cos->is_contiguous() && rotary_sin->is_contiguous(), "rotary_cos / rotary_sin must be contiguous");
+        TORCH_CHECK(rotary_cos->scalar_type() == q_dtype && rotary_sin->scalar_type() == q_dtype,
+                    "rotary_cos / rotary_sin must have the same dtype as query");
+    }
+    std::vector<int64_t> out_shape = {total_q, num_heads, head_size_v};
+    if (out_.has_value()) {
+        TORCH_CHECK(out_->scalar_type() == q_dtype, "Output must have the same dtype as inputs");
+        TORCH_CHECK(out_->is_cuda() && out_->stride(-1) == 1 && out_->sizes() == c10::IntArrayRef(out_shape),
+                    "out must have shape (..., num_heads, head_size_v)");
+    }
+    c10::hip::HIPGuardMasqueradingAsCUDA device_guard(q.device());
+    const auto int_opts = q.options().dtype(at::kInt);
+
+    // ---- the append: new fill levels stay on the device
+    Tensor seqused = *seqused_k;
+    bool appended = false;
+    const bool single_token = max_seqlen_q == 1 && total_q == batch_size && !seqused_q.has_value();
+    if (k_new.has_value() && ragged_new) {
+        const Tensor kn = aligned_or_copy(*k_new), vn = aligned_or_copy(*v_new);
+        seqused = at::empty({batch_size}, int_opts);
+        kvcache_append_varlen(kn, vn, *cu_seqlens_k_new, kcache, vcache, *seqused_k, seqused, kv_batch_idx, page_table, rotary_cos,
+                              rotary_sin, is_rotary_interleaved, seqlens_rotary);
+        appended = true;
+    } else if (k_new.has_value() && !single_token && k_new->size(1) > 0) {
+        const Tensor kn = aligned_or_copy(*k_new), vn = aligned_or_copy(*v_new);
+        kvcache_append(kn, vn, kcache, vcache, *seqused_k, kv_batch_idx, page_table, rotary_cos, rotary_sin, is_rotary_interleaved,
+                       seqlens_rotary);
+        seqused = *seqused_k + k_new->size(1);
+        appended = true;
+    }
+    if (single_token && !appended) {
+        // a pure decode step in ragged clothes: exactly the dense FA3 call on q viewed as (b, 1, h, d)
+        OptTensor out4, qv4;
+        if (out_.has_value()) out4 = out_->unsqueeze(1);
+        if (qv.has_value()) qv4 = qv->unsqueeze(1);
+        auto r = fwd_kvcache_impl(q.unsqueeze(1), kcache, vcache, k_new, v_new, seqused_k, rotary_cos, rotary_sin, kv_batch_idx, leftpad_k,
+                                  page_table, c10::nullopt, out4, softmax_scale, is_causal, window_size_left, window_size_right,
+                                  softcap, is_rotary_interleaved, num_splits, 1, seqlens_rotary, qv4);
+        return {r[0].reshape(out_shape), r[1].reshape({batch_size, num_heads}).transpose(0, 1)};
+    }
+    Tensor qc = aligned_or_copy(q);
+    if (rotary && total_q > 0) {
+        // the dense route's rule per sequence: causal / local -> row i at the old fill level (or seqlens_rotary) + i, otherwise
+        // every row at that level
+        const bool per_row = is_causal || window_size_left >= 0 || window_size_right >= 0;
+        Tensor q_ro = at::empty_like(qc, at::MemoryFormat::Contiguous);
+        rotary_apply_varlen(qc, q_ro, cu_seqlens_q, max_seqlen_q, *rotary_cos, *rotary_sin,
+                            seqlens_rotary.has_value() ? *seqlens_rotary : *seqused_k, is_rotary_interleaved, per_row);
+        qc = q_ro;
+    }
+    if (single_token) {
+        // one row per sequence behind a ragged append: the dense decode route on the fill levels the append wrote
+        OptTensor out4, qv4;
+        if (out_.has_value()) out4 = out_->unsqueeze(1);
+        if (qv.has_value()) qv4 = qv->unsqueeze(1);
+        auto r = fwd_kvcache_impl(qc.unsqueeze(1), kcache, vcache, c10::nullopt, c10::nullopt, seqused, c10::nullopt, c10::nullopt,
+                                  kv_batch_idx, leftpad_k, page_table, c10::nullopt, out4, softmax_scale, is_causal, window_size_left,
+                                  window_size_right, softcap, false, num_splits, 1, c10::nullopt, qv4);
+        return {r[0].reshape(out_shape), r[1].reshape({batch_size, num_heads}).transpose(0, 1)};
+    }
+    Tensor out = out_.has_value() ? *out_ : at::empty(out_shape, q.options());
+    Tensor softmax_lse = at::empty({num_heads, total_q}, q.options().dtype(at::kFloat));
+    if (total_q == 0) return {out, softmax_lse};
+    if (seqlen_k > 0 && max_seqlen_q > 0) {
+        fa3_window(max_seqlen_q, seqlen_k, window_size_left, window_size_right);  // :796-805, on the bounds of the lengths
+        if (is_causal) window_size_right = 0;
+        Tensor oc = aligned(out) ? out : at::empty_like(out, at::MemoryFormat::Contiguous);
+        FwdArgs a;
+        a.varlen = true; a.batch = batch_size; a.max_seqlen_q = max_seqlen_q; a.max_seqlen_k = seqlen_k;
+        a.softmax_scale = softmax_scale; a.causal = is_causal; a.window_left = window_size_left; a.window_right = window_size_right;
+        a.softcap = softcap; a.cu_seqlens_q = cu_seqlens_q; a.seqused_q = seqused_q; a.seqused_k = seqused;
+        a.kv_batch_idx = kv_batch_idx; a.block_table = page_table; a.leftpad_k = leftpad_k; a.fa3_window = true;
+        a.num_splits = (int)num_splits;
+        if (qv.has_value()) a.qv = aligned_or_copy(*qv);
+        launch_fwd(qc, kcache, vcache, oc, softmax_lse, a);
+        if (!oc.is_same(out)) out.copy_(oc);
+    } else {
+        out.zero_();
+        softmax_lse.fill_(std::numeric_limits<float>::infinity());
+    }
+    return {out, softmax_lse};
+}
+
 // flash_attn_3::fwd, hopper/flash_api.cpp:672-1198 (schema :1672-1707): the 34 positional arguments of
 // hopper/flash_attn_interface.py:66, returns (out, softmax_lse, None, None).
 // Built: fp16 / bf16 / fp8 e4m3 inputs (fp8 -> bf16 output, :859), per-(batch, kv head) q/k/v descales (:1115-1146), dense
 // and varlen (`cu_seqlens_*`, `seqused_*`), causal / sliding window / softcap / attention_chunk, GQA, a V head dim of its
 // own.  KV-cache arguments (dense q, 16-bit: k_new / v_new appended in place at seqused_k, page_table of any page size,
-// kv_batch_idx, leftpad_k, rotary) and plain decode over a cache go to fwd_kvcache_impl.  qv (MLA absorbed attention,
-// :1028-1048: scores = (q.k + qv.v) * scale, d <= 64 beside d_v in [256, 512], 16-bit) on every route.  Accepted and
-// rejected by message, like the reference does for compiled-out features (:1148-1165): cu_seqlens_k_new, qv of any other
-// shape or with fp8, KV-cache arguments together with cu_seqlens_q or fp8.  `scheduler_metadata`, `pack_gqa`, `sm_margin`
+// kv_batch_idx, leftpad_k, rotary) and plain decode over a cache go to fwd_kvcache_impl; the same arguments with ragged
+// queries (cu_seqlens_q + max_seqlen_q, k_new dense or ragged with cu_seqlens_k_new, seqused_q) to fwd_kvcache_ragged.  qv
+// (MLA absorbed attention, :1028-1048: scores = (q.k + qv.v) * scale, d <= 64 beside d_v in [256, 512], 16-bit) on every
+// route.  Accepted and rejected by message, like the reference does for compiled-out features (:1148-1165):
+// cu_seqlens_k_new without cu_seqlens_q, qv of any other shape or with fp8, KV-cache arguments together with cu_seqlens_k,
+// attention_chunk or fp8.  `scheduler_metadata`, `pack_gqa`, `sm_margin`
 // are performance hints and do not change results: ignored.
 std::tuple<Tensor, Tensor, OptTensor, OptTensor> fa3_fwd(
         const Tensor &q, const Tensor &k, const Tensor &v, const OptTensor &k_new, const OptTensor &v_new, const OptTensor &qv,
@@ -849,7 +1084,8 @@ std::tuple<Tensor, Tensor, OptTensor, OptTensor> fa3_fwd(
     CHECK_DEVICE(q, "q"); CHECK_LAST_CONTIGUOUS(q, "Input tensor must have contiguous last dimension");
     CHECK_DEVICE(k, "k"); CHECK_LAST_CONTIGUOUS(k, "Input tensor must have contiguous last dimension");
     CHECK_DEVICE(v, "v"); CHECK_LAST_CONTIGUOUS(v, "Input tensor must have contiguous last dimension");
-    TORCH_CHECK(!cu_seqlens_k_new.has_value(), "This flash attention build does not support cu_seqlens_k_new.");
+    TORCH_CHECK(!cu_seqlens_k_new.has_value() || cu_seqlens_q.has_value(),
+                "This flash attention build does not support cu_seqlens_k_new without cu_seqlens_q.");
     const int64_t attention_chunk = attention_chunk_.value_or(0);
     TORCH_CHECK(attention_chunk >= 0, "attention_chunk must be non-negative");
     const int64_t head_size = q.size(-1), head_size_v = v.size(-1);  // :764
@@ -876,14 +1112,18 @@ std::tuple<Tensor, Tensor, OptTensor, OptTensor> fa3_fwd(
     if (seqlens_rotary.has_value()) {  // :1074-1079; only read together with k_new + rotary (hopper/seqlen.h:89)
         TORCH_CHECK(seqlens_rotary->is_cuda() && seqlens_rotary->is_contiguous(), "seqlens_rotary must be a contiguous CUDA tensor");
         TORCH_CHECK(seqlens_rotary->scalar_type() == at::kInt, "seqlens_rotary must have dtype torch.int32");
-        TORCH_CHECK(seqlens_rotary->sizes() == c10::IntArrayRef({q.size(0)}), "seqlens_rotary must have shape (batch_size,)");
+        TORCH_CHECK(seqlens_rotary->sizes() == c10::IntArrayRef({cu_seqlens_q.has_value() ? cu_seqlens_q->numel() - 1 : q.size(0)}),
+                    "seqlens_rotary must have shape (batch_size,)");
         if (!k_new.has_value() || !rotary_cos.has_value()) seqlens_rotary = c10::nullopt;
     }
     const double default_scale = std::pow(double(head_size + (qv.has_value() ? head_size_v : 0)), -0.5);
-    if (k_new || v_new || page_table || kv_batch_idx || leftpad_k || rotary_cos || rotary_sin) {
+    // (ragged queries over a 4-D cache with its fill levels are a KV-cache step with or without any of the other arguments)
+    const bool ragged_cache = cu_seqlens_q.has_value() && !cu_seqlens_k.has_value() && seqused_k.has_value() && k.dim() == 4;
+    if (k_new || v_new || page_table || kv_batch_idx || leftpad_k || rotary_cos || rotary_sin || ragged_cache) {
         // KV-cache step (:736-760, 935-1060): k / v are the cache, seqused_k its fill levels
-        TORCH_CHECK(!cu_seqlens_q && !cu_seqlens_k && !seqused_q,
-                    "This flash attention build does not support KV-cache arguments together with cu_seqlens / seqused_q.");
+        TORCH_CHECK(!cu_seqlens_k, "This flash attention build does not support KV-cache arguments together with cu_seqlens_k.");
+        TORCH_CHECK(cu_seqlens_q.has_value() || !seqused_q,
+                    "This flash attention build does not support KV-cache arguments together with seqused_q without cu_seqlens_q.");
         TORCH_CHECK(!is_fp8, "This flash attention build does not support KV-cache arguments with fp8 inputs.");
         TORCH_CHECK(!attention_chunk && (head_size_v == head_size || wide_v),
                     "This flash attention build does not support attention_chunk or a V headdim of its own with KV-cache "
@@ -891,6 +1131,13 @@ std::tuple<Tensor, Tensor, OptTensor, OptTensor> fa3_fwd(
         TORCH_CHECK(k_new.has_value() == v_new.has_value(), "k_new and v_new must be passed together");
         TORCH_CHECK(rotary_cos.has_value() == rotary_sin.has_value(), "rotary_cos and rotary_sin must be passed together");
         if (k_new || leftpad_k) TORCH_CHECK(seqused_k.has_value(), "seqused_k must be provided with k_new / leftpad_k");
+        if (cu_seqlens_q.has_value()) {  // ragged queries: one continuous-batching step
+            auto r = fwd_kvcache_ragged(q, k, v, k_new, v_new, qv, out_, *cu_seqlens_q, cu_seqlens_k_new, seqused_q, seqused_k,
+                                        max_seqlen_q_.value_or(-1), page_table, kv_batch_idx, leftpad_k, rotary_cos, rotary_sin,
+                                        seqlens_rotary, softmax_scale_.value_or(default_scale), is_causal, window_size_left,
+                                        window_size_right, softcap, is_rotary_interleaved, num_splits);
+            return {std::get<0>(r), std::get<1>(r), c10::nullopt, c10::nullopt};
+        }
         auto r = fwd_kvcache_impl(q, k, v, k_new, v_new, seqused_k, rotary_cos, rotary_sin, kv_batch_idx, leftpad_k, page_table,
                                   c10::nullopt, out_, softmax_scale_.value_or(default_scale), is_causal, window_size_left,
                                   window_size_right, softcap, is_rotary_interleaved, num_splits, 1, seqlens_rotary, qv);

@@ -79,7 +79,24 @@ def _get_scheduler_metadata(batch_size, max_seqlen_q, max_seqlen_k, num_heads, n
     return torch.zeros(1, dtype=torch.int32, device=seqused_k.device)
 
 
+def _fwd_meta(q, k, v, k_new=None, v_new=None, q_v=None, out=None, cu_seqlens_q=None, cu_seqlens_k=None, cu_seqlens_k_new=None,
+              seqused_q=None, seqused_k=None, max_seqlen_q=None, max_seqlen_k=None, page_table=None, kv_batch_idx=None,
+              leftpad_k=None, rotary_cos=None, rotary_sin=None, seqlens_rotary=None, q_descale=None, k_descale=None,
+              v_descale=None, softmax_scale=None, is_causal=False, window_size_left=-1, window_size_right=-1,
+              attention_chunk=0, softcap=0.0, is_rotary_interleaved=False, scheduler_metadata=None, num_splits=0,
+              pack_gqa=None, sm_margin=0):
+    """Shapes of `fwd` for tracing (meta / fake tensors): out is q's shape with V's head dim (bf16 for fp8 inputs), the LSE
+    (b, h, seqlen_q) for dense queries and (h, total_q) for ragged ones -- with cu_seqlens_k (varlen) as well as over a KV
+    cache (cu_seqlens_q + seqused_k, k_new dense or ragged with cu_seqlens_k_new)."""
+    out_dtype = torch.bfloat16 if q.dtype == torch.float8_e4m3fn else q.dtype
+    o = out if out is not None else q.new_empty((*q.shape[:-1], v.shape[-1]), dtype=out_dtype)
+    lse_shape = (q.shape[1], q.shape[0]) if q.dim() == 3 else (q.shape[0], q.shape[2], q.shape[1])
+    empty = q.new_empty((0,), dtype=torch.float32)
+    return o, q.new_empty(lse_shape, dtype=torch.float32), empty, empty
+
+
 _ops.impl("fwd", _fwd, "CUDA")
+_ops.impl("fwd", _fwd_meta, "Meta")
 _ops.impl("bwd", _bwd, "CUDA")
 _ops.impl("fwd_combine", _fwd_combine, "CUDA")
 _ops.impl("get_scheduler_metadata", _get_scheduler_metadata, "CUDA")

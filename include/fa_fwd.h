@@ -26,6 +26,10 @@
  *   - varlen layout q:(total_q, h, d) k,v:(total_k, h_k, d), cu_seqlens_{q,k}
  *     int32 (b+1) device arrays, softmax_lse:(h, total_q) fp32
  *     (csrc/flash_attn/flash_api.cpp:652); *_batch_stride is ignored;
+ *   - ragged queries over a batched cache (flash_attn_with_kvcache(..., cu_seqlens_q=), hopper/flash_api.cpp:736-760):
+ *     cu_seqlens_q set, cu_seqlens_k NULL, seqused_k set.  q / o / qv and softmax_lse are varlen ((total_q, h, .),
+ *     (h, total_q)); k / v are the dense cache (b_cache, seqlen_k, h_k, .) addressed by *_batch_stride and kv_batch_idx,
+ *     or pages behind block_table; seqlen_k is the cache capacity, seqused_k the fill levels (see fa_fwd_params);
  *   - the callee never allocates, never synchronises and launches on `stream`;
  *   - outputs are written in place; inputs are borrowed.
  */
@@ -101,7 +105,7 @@ typedef struct fa_fwd_params {
 
     /* varlen bookkeeping (NULL => dense); BlockInfo csrc/flash_attn/src/block_info.h:12-45 */
     const int32_t *cu_seqlens_q; /* (b+1) */
-    const int32_t *cu_seqlens_k; /* (b+1) */
+    const int32_t *cu_seqlens_k; /* (b+1); NULL beside cu_seqlens_q = ragged queries over a batched cache (below) */
     const int32_t *seqused_q;    /* (b) optional: rows actually used (FA3 hopper/seqlen.h:32-93) */
     const int32_t *seqused_k;    /* (b) optional: keys actually used */
 
@@ -141,8 +145,14 @@ typedef struct fa_fwd_params {
     int64_t alibi_slopes_batch_stride;
 
     /* KV-cache decode (mha_fwd_kvcache csrc/flash_attn/flash_api.cpp:1202-1476; FA3 kv_batch_idx
-     * hopper/flash_api.cpp:686): dense layout only; batch i reads k/v rows of cache entry kv_batch_idx[i]
-     * (NULL = i).  The valid length of each cache entry is given through seqused_k. */
+     * hopper/flash_api.cpp:686): dense K/V layout only; batch i reads k/v rows of cache entry kv_batch_idx[i]
+     * (NULL = i).  The valid length of each cache entry is given through seqused_k.
+     * Ragged queries over the cache -- one serving step that mixes prefill chunks with single-token decodes: cu_seqlens_q
+     * set, cu_seqlens_k NULL, seqused_k set (required).  q, o, qv: (total_q, h, .) with q/o/qv_batch_stride ignored,
+     * softmax_lse (h, total_q); k, v: the cache, (b_cache, seqlen_k, h_k, .) through k/v_batch_stride and kv_batch_idx, or
+     * paged through block_table; seqlen_k = the cache capacity (it bounds the key tiles), seqlen_q = max_seqlen_q;
+     * leftpad_k as on the dense route.  Every 16-bit mask (causal, windows, softcap), seqused_q, qv (on the qv kernel) and
+     * split-KV.  FA_ERR_UNSUPPORTED with fp8, dropout or ALiBi.  cu_seqlens_k without cu_seqlens_q: FA_ERR_BAD_SHAPE. */
     const int32_t *kv_batch_idx;
 
     /* Paged KV cache (csrc/flash_attn/flash_api.cpp:1245-1266, 538-560; src/flash_fwd_kernel.h:560-576): k and v are
@@ -154,8 +164,10 @@ typedef struct fa_fwd_params {
     int32_t page_block_size;
     /* Split-KV (set_params_splitkv / num_splits_heuristic csrc/flash_attn/flash_api.cpp:257-329, combine kernel
      * src/flash_fwd_kernel.h:1108-1290): 1 = off, N > 1 = the key range of every tile is cut into N parts computed by
-     * N workgroups and merged by a second launch, 0 = library heuristic (splits only dense problems with few tiles,
-     * i.e. decode).  Needs params->workspace of fa_fwd_workspace_size() bytes when the effective value is > 1 (the partial
+     * N workgroups and merged by a second launch, 0 = library heuristic (splits only dense problems and ragged queries
+     * over a cache with few tiles, i.e. decode; the tiles of a ragged batch are counted from total_q and seqlen_q, never from
+     * device data).  cu_seqlens_q + cu_seqlens_k problems never split.  Ragged queries over a cache keep partials of
+     * (splits, total_q, h, d_v) + (splits, h, total_q) fp32.  Needs params->workspace of fa_fwd_workspace_size() bytes when the effective value is > 1 (the partial
      * outputs and LSEs of the parts, both fp32 like the reference's out_accum / softmax_lse_accum).
      * The default-initialised struct (0) therefore may split: callers without a workspace must pass 1. */
     int32_t num_splits;
@@ -317,6 +329,82 @@ typedef struct fa_rotary_params {
 
 int fa_rotary_apply(const fa_rotary_params *params, void *stream);
 uint32_t fa_rotary_params_size(void);
+
+/*
+ * Ragged in-place append: one serving step's new keys / values, packed (total_k_new, h_k, .) with cu_seqlens_k_new like a
+ * varlen tensor (flash_attn_with_kvcache(..., cu_seqlens_k_new=), hopper/flash_api.cpp:935-975), into a batched or paged
+ * cache.  Row i of sequence s goes to cache row cache_seqlens[s] + i of entry cache_batch_idx[s] (NULL = s) or of its page;
+ * rows that would fall past seqlen_cache are dropped.  Keys are rotated at position
+ * (rotary_seqlens ? rotary_seqlens[s] : cache_seqlens[s]) + i by the rules of fa_kvcache_append; values are copied.  The same
+ * launch writes seqused_out[s] = min(cache_seqlens[s] + (cu_seqlens_k_new[s+1] - cu_seqlens_k_new[s]), seqlen_cache) -- the
+ * fill levels the attention launch reads as seqused_k (never past the capacity: the dropped rows are not there).
+ * seqused_out must not alias cache_seqlens.  One HBM-bound launch, one wavefront per new row: with max_seqlen_k_new > 0
+ * (an upper bound of the lengths) the grid is (row blocks of the longest sequence) x b; with 0 the rows are dealt flat and
+ * every wavefront finds its sequence by a binary search in cu_seqlens_k_new (held in LDS up to 16383 sequences).
+ * 16-bit elements, head_dim stride 1, d % 8 == 0, d_v <= 512, 16-byte aligned rows; block_table not with cache_batch_idx.
+ */
+typedef struct fa_kvcache_append_varlen_params {
+    uint32_t abi_version; /* FA_ABI_VERSION */
+    uint32_t struct_size; /* sizeof(fa_kvcache_append_varlen_params) */
+    const void *k_new; /* (total_k_new, h_k, d) */
+    const void *v_new; /* (total_k_new, h_k, d_v) */
+    void *k_cache;     /* (b_cache, seqlen_cache, h_k, d) or pages (num_pages, page_block_size, h_k, d) */
+    void *v_cache;
+    int64_t knew_row_stride, knew_head_stride;
+    int64_t vnew_row_stride, vnew_head_stride;
+    int64_t kcache_batch_stride, kcache_row_stride, kcache_head_stride;
+    int64_t vcache_batch_stride, vcache_row_stride, vcache_head_stride;
+    int32_t b;                /* sequences */
+    int32_t total_k_new;      /* rows of k_new / v_new (>= cu_seqlens_k_new[b]; rows behind it are ignored) */
+    int32_t max_seqlen_k_new; /* upper bound of the new lengths, or 0 = not known (search in cu_seqlens_k_new) */
+    int32_t seqlen_cache;     /* capacity; paged: pages per sequence x page_block_size */
+    int32_t h_k, d;
+    int32_t d_v;   /* head dim of v_new / v_cache; 0 = d */
+    int32_t dtype; /* enum fa_dtype (16-bit types) */
+    const int32_t *cu_seqlens_k_new; /* (b + 1) */
+    const int32_t *cache_seqlens;    /* (b) rows already valid in each sequence's cache */
+    const int32_t *cache_batch_idx;  /* (b) or NULL */
+    int32_t *seqused_out;            /* (b) written by the launch */
+    const int32_t *block_table;      /* paged cache (see fa_fwd_params) or NULL */
+    int64_t block_table_batch_stride;
+    int32_t page_block_size;
+    int32_t rotary_dim;         /* % 16 == 0, <= d; only read when rotary_cos is set */
+    const void *rotary_cos;     /* (seqlen_ro, rotary_dim / 2), the dtype of k; NULL = no rotary */
+    const void *rotary_sin;
+    const int32_t *rotary_seqlens; /* (b) or NULL = cache_seqlens */
+    int32_t rotary_interleaved;
+    int32_t reserved;
+} fa_kvcache_append_varlen_params;
+
+int fa_kvcache_append_varlen(const fa_kvcache_append_varlen_params *params, void *stream);
+uint32_t fa_kvcache_append_varlen_params_size(void);
+
+/*
+ * Rotary embedding of a ragged (total_q, h, d) tensor into `dst` (same shape; dst may alias src): row i of sequence s is
+ * rotated at position offsets[s] + (per_row_positions ? i : 0) -- the query side of a ragged KV-cache step.  Same launch
+ * shape and sequence lookup as fa_kvcache_append_varlen (max_seqlen_q > 0: a 2-D grid, 0: a search in cu_seqlens_q).
+ */
+typedef struct fa_rotary_varlen_params {
+    uint32_t abi_version;
+    uint32_t struct_size;
+    const void *src;
+    void *dst;
+    int64_t src_row_stride, src_head_stride;
+    int64_t dst_row_stride, dst_head_stride;
+    int32_t b, total_q, max_seqlen_q, h, d;
+    int32_t dtype; /* FA_DTYPE_FP16 / FA_DTYPE_BF16 */
+    int32_t rotary_dim;
+    int32_t rotary_interleaved;
+    int32_t per_row_positions;
+    int32_t reserved;
+    const void *rotary_cos; /* (seqlen_ro, rotary_dim / 2) */
+    const void *rotary_sin;
+    const int32_t *cu_seqlens_q; /* (b + 1) */
+    const int32_t *offsets;      /* (b) */
+} fa_rotary_varlen_params;
+
+int fa_rotary_apply_varlen(const fa_rotary_varlen_params *params, void *stream);
+uint32_t fa_rotary_varlen_params_size(void);
 
 /* Merge of split-KV partial results given by the caller: mha_combine / flash_attn_3::fwd_combine
  * (hopper/flash_api.cpp:1569-1670, hopper/flash_fwd_combine_kernel.h).
