@@ -20,7 +20,7 @@ INCLUDE = os.path.join(os.path.dirname(_HERE), "include")
 FA_ABI_VERSION = 13
 FA_FLAG_FA3_WINDOW = 1
 FA_FLAG_SDMASK_SIGNED = 2
-FA_DTYPE_FP16, FA_DTYPE_BF16, FA_DTYPE_FP8_E4M3 = 0, 1, 2
+FA_DTYPE_FP16, FA_DTYPE_BF16, FA_DTYPE_FP8_E4M3, FA_DTYPE_FP32 = 0, 1, 2, 3
 
 # every symbol include/fa_fwd.h declares (tests check the .so exports all of them)
 EXPORTED_SYMBOLS = (
@@ -45,10 +45,16 @@ EXPORTED_SYMBOLS = (
     "fa_rotary_varlen_params_size",
     "fa_fwd_combine",
     "fa_combine_params_size",
+    "fa_fwd_sink",
+    "fa_fwd_sink_validate",
+    "fa_sink_params_size",
     # include/fa_bwd.h
     "fa_bwd",
     "fa_bwd_validate",
     "fa_bwd_params_size",
+    "fa_sink_grad",
+    "fa_sink_grad_validate",
+    "fa_sink_grad_params_size",
 )
 
 
@@ -220,6 +226,26 @@ class FaBwdParams(ctypes.Structure):
     )
 
 
+class FaSinkParams(ctypes.Structure):
+    """Field-for-field mirror of `struct fa_sink_params` (include/fa_fwd.h)."""
+
+    _fields_ = (
+        [("abi_version", ctypes.c_uint32), ("struct_size", ctypes.c_uint32), ("learnable_sink", ctypes.c_void_p)]
+        + [(n, ctypes.c_int32) for n in ("sink_dtype", "sink_head_stride", "sink_row_stride", "reserved")]
+    )
+
+
+class FaSinkGradParams(ctypes.Structure):
+    """Field-for-field mirror of `struct fa_sink_grad_params` (include/fa_bwd.h)."""
+
+    _fields_ = (
+        [("abi_version", ctypes.c_uint32), ("struct_size", ctypes.c_uint32)]
+        + [(n, ctypes.c_void_p) for n in ("softmax_lse", "softmax_d", "learnable_sink", "dsink", "cu_seqlens_q", "seqused_q")]
+        + [("softmax_d_row_len", ctypes.c_int64)]
+        + [(n, ctypes.c_int32) for n in ("b", "seqlen_q", "h", "total_q", "sink_dtype", "reserved")]
+    )
+
+
 HASH_PATH = os.path.join(_HERE, "libfa_fwd_gfx950.srchash")
 
 
@@ -358,6 +384,22 @@ def load():
     lib.fa_combine_params_size.restype = ctypes.c_uint32
     if lib.fa_combine_params_size() != ctypes.sizeof(FaCombineParams):
         raise RuntimeError("fa_combine_params layout mismatch between include/fa_fwd.h and _lib")
+    lib.fa_fwd_sink.argtypes = [ctypes.POINTER(FaFwdParams), ctypes.POINTER(FaSinkParams), ctypes.c_void_p]
+    lib.fa_fwd_sink.restype = ctypes.c_int
+    lib.fa_fwd_sink_validate.argtypes = [ctypes.POINTER(FaFwdParams), ctypes.POINTER(FaSinkParams)]
+    lib.fa_fwd_sink_validate.restype = ctypes.c_int
+    lib.fa_sink_params_size.argtypes = []
+    lib.fa_sink_params_size.restype = ctypes.c_uint32
+    if lib.fa_sink_params_size() != ctypes.sizeof(FaSinkParams):
+        raise RuntimeError("fa_sink_params layout mismatch between include/fa_fwd.h and _lib")
+    lib.fa_sink_grad.argtypes = [ctypes.POINTER(FaSinkGradParams), ctypes.c_void_p]
+    lib.fa_sink_grad.restype = ctypes.c_int
+    lib.fa_sink_grad_validate.argtypes = [ctypes.POINTER(FaSinkGradParams)]
+    lib.fa_sink_grad_validate.restype = ctypes.c_int
+    lib.fa_sink_grad_params_size.argtypes = []
+    lib.fa_sink_grad_params_size.restype = ctypes.c_uint32
+    if lib.fa_sink_grad_params_size() != ctypes.sizeof(FaSinkGradParams):
+        raise RuntimeError("fa_sink_grad_params layout mismatch between include/fa_bwd.h and _lib.FaSinkGradParams")
     lib.fa_bwd.argtypes = [ctypes.POINTER(FaBwdParams), ctypes.c_void_p]
     lib.fa_bwd.restype = ctypes.c_int
     lib.fa_bwd_validate.argtypes = [ctypes.POINTER(FaBwdParams)]
@@ -406,6 +448,23 @@ def new_bwd_params():
     p = FaBwdParams()
     p.abi_version = FA_ABI_VERSION
     p.struct_size = ctypes.sizeof(FaBwdParams)
+    return p
+
+
+def new_sink_params():
+    p = FaSinkParams()
+    p.abi_version = FA_ABI_VERSION
+    p.struct_size = ctypes.sizeof(FaSinkParams)
+    p.sink_dtype = FA_DTYPE_BF16
+    p.sink_head_stride = 1
+    return p
+
+
+def new_sink_grad_params():
+    p = FaSinkGradParams()
+    p.abi_version = FA_ABI_VERSION
+    p.struct_size = ctypes.sizeof(FaSinkGradParams)
+    p.sink_dtype = FA_DTYPE_BF16
     return p
 
 

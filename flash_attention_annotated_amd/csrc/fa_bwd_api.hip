@@ -10,6 +10,47 @@
 #include <algorithm>
 #include <cmath>
 
+namespace fa {
+
+// ---- dsink[h] = - sum over the valid rows of exp(z_h - LSE) * D (include/fa_bwd.h).  One workgroup per head.  Memory-bound:
+// two fp32 streams, read once; the threads of a workgroup walk one sequence's rows side by side (consecutive lanes,
+// consecutive addresses: whole cache lines per wavefront), sequence after sequence.  Every thread adds its rows in a fixed
+// order, then a butterfly inside each wavefront and a serial sum of the four wavefront totals: no atomics, the same bits on
+// every run.
+__global__ __launch_bounds__(256) void sink_grad_kernel(const fa_sink_grad_params p) {
+    __shared__ float wave_sum[4];
+    const int head = blockIdx.x, tid = threadIdx.x;
+    const float z = p.sink_dtype == FA_DTYPE_FP32
+                        ? ((const float *)p.learnable_sink)[head]
+                        : __uint_as_float((uint32_t)((const uint16_t *)p.learnable_sink)[head] << 16);
+    float acc = 0.f;
+    if (z != -INFINITY) {  // (no sink: its weight is 0 everywhere)
+        for (int bb = 0; bb < p.b; ++bb) {
+            int len;
+            int64_t lse_off, d_off;
+            if (p.cu_seqlens_q) {
+                const int q0 = p.cu_seqlens_q[bb];
+                len = min(p.cu_seqlens_q[bb + 1], p.total_q) - q0;
+                lse_off = (int64_t)head * p.total_q + q0;
+                d_off = (int64_t)head * p.softmax_d_row_len + q0;
+            } else {
+                len = p.seqlen_q;
+                lse_off = ((int64_t)bb * p.h + head) * p.seqlen_q;
+                d_off = ((int64_t)bb * p.h + head) * p.softmax_d_row_len;
+            }
+            if (p.seqused_q) len = min(len, p.seqused_q[bb]);
+            for (int r = tid; r < len; r += 256) acc += __expf(z - p.softmax_lse[lse_off + r]) * p.softmax_d[d_off + r];
+        }
+    }
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) acc += __shfl_xor(acc, m, 64);
+    if ((tid & 63) == 0) wave_sum[tid >> 6] = acc;
+    __syncthreads();
+    if (tid == 0) p.dsink[head] = -(((wave_sum[0] + wave_sum[1]) + wave_sum[2]) + wave_sum[3]);
+}
+
+}  // namespace fa
+
 namespace {
 
 int head_dim_tile_b(int d) {
@@ -242,6 +283,33 @@ int fa_bwd(const fa_bwd_params *p, void *stream_) {
     // seqlen_q == 0: dK = dV = 0 is written by the dK/dV pass (no query tile is visible); seqlen_k == 0: dQ = 0 likewise
     if (p->dtype == FA_DTYPE_BF16) return dispatch_bwd<__bf16>(bp, softcap, p->seqlen_q, p->seqlen_k, stream);
     return dispatch_bwd<_Float16>(bp, softcap, p->seqlen_q, p->seqlen_k, stream);
+}
+
+uint32_t fa_sink_grad_params_size(void) { return (uint32_t)sizeof(fa_sink_grad_params); }
+
+int fa_sink_grad_validate(const fa_sink_grad_params *p) {
+    if (!p) return FA_ERR_NULL_POINTER;
+    if (p->abi_version != FA_ABI_VERSION || p->struct_size != sizeof(fa_sink_grad_params)) return FA_ERR_BAD_ABI;
+    if (p->sink_dtype != FA_DTYPE_BF16 && p->sink_dtype != FA_DTYPE_FP32) return FA_ERR_BAD_DTYPE;
+    if (p->b <= 0 || p->h <= 0 || p->seqlen_q < 0) return FA_ERR_BAD_SHAPE;
+    if (p->cu_seqlens_q && p->total_q < 0) return FA_ERR_BAD_SHAPE;
+    if (!p->learnable_sink || !p->dsink) return FA_ERR_NULL_POINTER;
+    const int64_t rows = p->cu_seqlens_q ? (int64_t)p->total_q : (int64_t)p->seqlen_q;
+    if (rows > 0 && (!p->softmax_lse || !p->softmax_d)) return FA_ERR_NULL_POINTER;
+    if (p->softmax_d_row_len < rows) return FA_ERR_BAD_SHAPE;
+    if (reinterpret_cast<uintptr_t>(p->learnable_sink) % (p->sink_dtype == FA_DTYPE_FP32 ? 4 : 2) != 0 ||
+        reinterpret_cast<uintptr_t>(p->dsink) % 4 != 0 || reinterpret_cast<uintptr_t>(p->softmax_lse) % 4 != 0 ||
+        reinterpret_cast<uintptr_t>(p->softmax_d) % 4 != 0)
+        return FA_ERR_BAD_STRIDE;
+    return FA_OK;
+}
+
+int fa_sink_grad(const fa_sink_grad_params *p, void *stream_) {
+    const int st = fa_sink_grad_validate(p);
+    if (st != FA_OK) return st;
+    hipLaunchKernelGGL(fa::sink_grad_kernel, dim3((unsigned)p->h), dim3(256), 0, static_cast<hipStream_t>(stream_), *p);
+    if (hipGetLastError() != hipSuccess) return FA_ERR_LAUNCH;
+    return FA_OK;
 }
 
 }  // extern "C"

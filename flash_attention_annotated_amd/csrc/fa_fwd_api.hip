@@ -765,10 +765,12 @@ int device_cus() {
 
 // ---- split-KV merge: out = sum_s w_s O_s / sum_s w_s, w_s = exp(lse_s - max lse); lse = max + log sum w.  One thread =
 // one 16-byte chunk of one (batch, row, head); splits with LSE = +inf (no key in their range) carry no weight.
+// A learnable sink (fa_fwd_sink) joins here, once: the splits wrote sink-free partials, the merge takes the sink's logit as
+// one more weight without a value, rebased like the others on the largest of them (fa::sink_finalize's rule).
 template <typename T>
 __global__ void combine_splits_kernel(const float *__restrict__ o_acc, const float *__restrict__ lse_acc, T *__restrict__ out,
                                       float *__restrict__ lse_out, int splits, int b, int sq, int h, int d,
-                                      int64_t o_bs, int64_t o_rs, int64_t o_hs) {
+                                      int64_t o_bs, int64_t o_rs, int64_t o_hs, const fa::KParams sk) {
     const int chunks = d >> 3;
     const int64_t total = (int64_t)b * sq * h * chunks;
     const int64_t o_split = (int64_t)b * sq * h * d, lse_split = (int64_t)b * h * sq;
@@ -785,9 +787,13 @@ __global__ void combine_splits_kernel(const float *__restrict__ o_acc, const flo
             const float l = lse_acc[s * lse_split + lse_idx];
             if (l != INFINITY) mx = fmaxf(mx, l);
         }
+        const float z = sk.sink ? fa::load_sink(sk, hd, row) : -INFINITY;
+        const bool with_sink = z != -INFINITY;  // (z = -inf: the merge without a sink, bit for bit)
+        const bool keyless = mx == -INFINITY;
+        if (with_sink) mx = fmaxf(mx, z);
         float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        float wsum = 0.f;
-        if (mx != -INFINITY) {
+        float wsum = with_sink ? __expf(z - mx) : 0.f;
+        if (!keyless) {
             for (int s = 0; s < splits; ++s) {
                 const float l = lse_acc[s * lse_split + lse_idx];
                 if (l == INFINITY) continue;
@@ -804,7 +810,7 @@ __global__ void combine_splits_kernel(const float *__restrict__ o_acc, const flo
             for (int j = 0; j < 8; ++j) acc[j] *= inv;
         }
         *reinterpret_cast<uint4 *>(out + bb * o_bs + row * o_rs + hd * o_hs + c * 8) = pack8<T>(acc);
-        if (c == 0) lse_out[lse_idx] = (mx == -INFINITY) ? INFINITY : mx + __logf(wsum);
+        if (c == 0) lse_out[lse_idx] = (mx == -INFINITY) ? INFINITY : keyless ? z : mx + __logf(wsum);
     }
 }
 
@@ -1263,8 +1269,39 @@ const char *fa_fwd_last_plan_name(void) {
     return t_last_plan_set ? plan_text(t_last_plan, name) : nullptr;
 }
 
-int fa_fwd(const fa_fwd_params *p, void *stream_) {
+uint32_t fa_sink_params_size(void) { return (uint32_t)sizeof(fa_sink_params); }
+
+// The sink's own checks come first: what a sink cannot go with is refused as such, whatever else those params lack.
+int fa_fwd_sink_validate(const fa_fwd_params *p, const fa_sink_params *s) {
+    if (!p || !s) return FA_ERR_NULL_POINTER;
+    if (p->abi_version != FA_ABI_VERSION || p->struct_size != sizeof(fa_fwd_params)) return FA_ERR_BAD_ABI;
+    if (s->abi_version != FA_ABI_VERSION || s->struct_size != sizeof(fa_sink_params)) return FA_ERR_BAD_ABI;
+    if (!s->learnable_sink) return FA_ERR_NULL_POINTER;
+    if (s->sink_dtype != FA_DTYPE_BF16 && s->sink_dtype != FA_DTYPE_FP32) return FA_ERR_BAD_DTYPE;
+    if (reinterpret_cast<uintptr_t>(s->learnable_sink) % (s->sink_dtype == FA_DTYPE_FP32 ? 4 : 2) != 0) return FA_ERR_BAD_STRIDE;
+    if (s->sink_head_stride < 0 || s->sink_row_stride < 0) return FA_ERR_BAD_STRIDE;
+    if (s->sink_row_stride != 0 && p->cu_seqlens_q) return FA_ERR_BAD_STRIDE;  // (rows of a ragged batch are not rows of a GQA group)
+    // the reference's sink surface has none of these (flash_attn/cute/interface.py)
+    if (p->dtype == FA_DTYPE_FP8_E4M3 || p->qv || p->p_dropout > 0.f || p->alibi_slopes || p->s_dmask) return FA_ERR_UNSUPPORTED;
     const int st = fa_fwd_validate(p);
+    if (st != FA_OK) return st;
+    const Family f = plan_fwd(p, 0).family;  // (q/k <= 64 beside a paged or split V of 256..512 columns runs the qv kernel)
+    if (f == Family::qv || f == Family::fp8) return FA_ERR_UNSUPPORTED;
+    return FA_OK;
+}
+
+static int fwd_run(const fa_fwd_params *p, const fa_sink_params *sink, void *stream_);
+
+int fa_fwd(const fa_fwd_params *p, void *stream_) { return fwd_run(p, nullptr, stream_); }
+
+int fa_fwd_sink(const fa_fwd_params *p, const fa_sink_params *sink, void *stream_) {
+    if (!sink) return FA_ERR_NULL_POINTER;
+    return fwd_run(p, sink, stream_);
+}
+
+// fa_fwd and fa_fwd_sink: the plan is made from `p` alone -- a sink never changes it
+static int fwd_run(const fa_fwd_params *p, const fa_sink_params *sink, void *stream_) {
+    const int st = sink ? fa_fwd_sink_validate(p, sink) : fa_fwd_validate(p);
     t_last_plan_set = false;
     if (st != FA_OK) return st;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
@@ -1281,7 +1318,7 @@ int fa_fwd(const fa_fwd_params *p, void *stream_) {
             part.v = static_cast<const char *>(p->v) + (size_t)c * 2;
             part.o = static_cast<char *>(p->o) + (size_t)c * 2;
             part.d_v = std::min(256, p->d_v - c);
-            const int st_part = fa_fwd(&part, stream_);
+            const int st_part = fwd_run(&part, sink, stream_);
             if (st_part != FA_OK) return st_part;
         }
         t_last_plan = pl;  // (the outer plan, "... cols=2": the parts recorded theirs)
@@ -1392,6 +1429,16 @@ int fa_fwd(const fa_fwd_params *p, void *stream_) {
     kp.block_table = p->block_table;
     kp.bt_bs = (int32_t)p->block_table_batch_stride;
     kp.page_size = p->page_block_size;
+    // the sink: an epilogue term of the kernel, or -- split-KV: the parts write sink-free partials -- of the merge
+    fa::KParams sink_kp{};
+    if (sink) {
+        sink_kp.sink = sink->learnable_sink;
+        sink_kp.sink_hs = sink->sink_head_stride; sink_kp.sink_rs = sink->sink_row_stride;
+        sink_kp.sink_fp32 = sink->sink_dtype == FA_DTYPE_FP32;
+        if (sp.splits <= 1) {
+            kp.sink = sink_kp.sink; kp.sink_hs = sink_kp.sink_hs; kp.sink_rs = sink_kp.sink_rs; kp.sink_fp32 = sink_kp.sink_fp32;
+        }
+    }
 
     const bool softcap = p->softcap > 0.f;
     constexpr float kLog2e = 1.4426950408889634f;
@@ -1438,11 +1485,11 @@ int fa_fwd(const fa_fwd_params *p, void *stream_) {
     if (bf16)
         hipLaunchKernelGGL(combine_splits_kernel<__bf16>, dim3(blocks), dim3(256), 0, stream, static_cast<const float *>(kp.o),
                            kp.lse, static_cast<__bf16 *>(p->o), p->softmax_lse, sp.splits, mb, msq, p->h, dw,
-                           p->o_batch_stride, p->o_row_stride, p->o_head_stride);
+                           p->o_batch_stride, p->o_row_stride, p->o_head_stride, sink_kp);
     else
         hipLaunchKernelGGL(combine_splits_kernel<_Float16>, dim3(blocks), dim3(256), 0, stream,
                            static_cast<const float *>(kp.o), kp.lse, static_cast<_Float16 *>(p->o), p->softmax_lse,
-                           sp.splits, mb, msq, p->h, dw, p->o_batch_stride, p->o_row_stride, p->o_head_stride);
+                           sp.splits, mb, msq, p->h, dw, p->o_batch_stride, p->o_row_stride, p->o_head_stride, sink_kp);
     if (hipGetLastError() != hipSuccess) return FA_ERR_LAUNCH;
     return FA_OK;
 }

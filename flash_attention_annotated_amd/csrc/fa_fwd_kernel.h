@@ -83,6 +83,10 @@ struct KParams {
     // hopper/flash_api.cpp:764,782-792; = d everywhere else) and attention_chunk (hopper/mask.h:116-119; 0 = off)
     int32_t dv;
     int32_t chunk;
+    // learnable attention sink (fa_fwd_sink, include/fa_fwd.h; NULL = off): a logit per head, in natural-log units, that joins
+    // the softmax denominator and carries no value.  Row r of kernel head g reads sink[g * sink_hs + r * sink_rs] (bf16 or fp32)
+    const void *sink;
+    int32_t sink_hs, sink_rs, sink_fp32;
 };
 
 // floor(x / c) * c for c > 0 and any sign of x: first key of the attention chunk of diagonal position x (flash::round_down on
@@ -144,6 +148,32 @@ __device__ __forceinline__ Scales load_scales(const KParams &p, int batch, int k
     }
     s.v_descale = vd;
     return s;
+}
+
+// ---- learnable sink: an epilogue term.  Read behind the key sweep (nothing of it is alive across the generated loops).
+__device__ __forceinline__ float load_sink(const KParams &p, int head, int row) {
+    const int64_t i = (int64_t)head * p.sink_hs + (int64_t)row * p.sink_rs;
+    if (p.sink_fp32) return ((const float *)p.sink)[i];
+    return __uint_as_float((uint32_t)((const uint16_t *)p.sink)[i] << 16);
+}
+// A finished row -- ms = m_run * scale, the offset its sum l_tot = sum_j exp(s_j - ms) was taken at (any offset the kernel
+// kept: a stale maximum is as good), `empty` = no visible key -- takes the sink z like one more key without a value: the
+// pair is rebased on the larger of ms and z, so exp() never sees a positive argument (z far above every score gives
+// LSE ~ z, not inf).  In: inv = 1 / l_tot and lse of the row without the sink; out: with it.  z = -inf leaves both as they
+// are (the call without a sink, bit for bit); an empty row gets LSE = z and keeps O = 0.
+__device__ __forceinline__ void sink_finalize(float z, float ms, float l_tot, bool empty, float &inv, float &lse) {
+    if (z == -INFINITY) return;
+    if (empty) {
+        lse = z;
+    } else if (z > ms) {
+        const float e = __expf(ms - z), l2 = l_tot * e + 1.f;
+        inv = e / l2;
+        lse = z + __logf(l2);
+    } else {
+        const float l2 = l_tot + __expf(z - ms);
+        inv = 1.f / l2;
+        lse = ms + __logf(l2);
+    }
 }
 
 template <typename T> struct Elem;
@@ -634,12 +664,13 @@ __global__ __launch_bounds__(NWAVES * 64, (D <= 128 ? 2 : 1)) void fwd_kernel(co
     // (the loop's last barrier has retired every K/V read, so the region can be reused)
     const float l_tot = half_swap_sum(l_run);
     const bool empty = (l_tot == 0.f) || (l_tot != l_tot);
-    const float inv = (empty ? 1.f : 1.f / l_tot) * sc.v_descale * p.rp_dropout;
+    float inv = (empty ? 1.f : 1.f / l_tot) * sc.v_descale * p.rp_dropout;
+    // csrc/flash_attn/src/softmax.h:178-180: +inf for rows with no valid key
+    float lse_row = empty ? INFINITY : m_run * sc.scale + __logf(l_tot);
+    if (p.sink)  // (never with descales or dropout: fa_fwd_sink_validate)
+        sink_finalize(my_row < sq ? load_sink(p, head, my_row) : -INFINITY, m_run * sc.scale, l_tot, empty, inv, lse_row);
     if (wave_active) {
-        if (hh == 0 && my_row < sq) {
-            // csrc/flash_attn/src/softmax.h:178-180: +inf for rows with no valid key
-            p.lse[lse_base + my_row] = empty ? INFINITY : m_run * sc.scale + __logf(l_tot);
-        }
+        if (hh == 0 && my_row < sq) p.lse[lse_base + my_row] = lse_row;
         if (p.num_splits > 1) {
             // split-KV partial: fp32 in the caller's workspace (role of out_accum, csrc/flash_attn/flash_api.cpp:297-318), straight
             // from the accumulators -- 4 consecutive head dims = one 16-byte store per lane; the merge launch rounds once

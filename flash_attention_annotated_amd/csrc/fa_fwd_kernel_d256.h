@@ -476,10 +476,12 @@ __global__ __launch_bounds__(256, 1) void fwd_kernel_d256(const KParams p) {
     const int row_e = wrow + r_e;
     const float lt = half_swap_sum(l_run);
     const bool empty = (lt == 0.f) || (lt != lt);
-    const float inv = (empty ? 1.f : 1.f / lt) * vdesc_e;
+    float inv = (empty ? 1.f : 1.f / lt) * vdesc_e;
+    float lse_row = empty ? INFINITY : m_run * scale_e + __logf(lt);
+    if (p.sink) sink_finalize(row_e < sq ? load_sink(p, head, row_e) : -INFINITY, m_run * scale_e, lt, empty, inv, lse_row);
     const bool wave_active = wrow < sq;
     if (wave_active) {
-        if (hh_e == 0 && row_e < sq) p.lse[lse_base + row_e] = empty ? INFINITY : m_run * scale_e + __logf(lt);
+        if (hh_e == 0 && row_e < sq) p.lse[lse_base + row_e] = lse_row;
         char *obuf = smem + wave * (32 * O_ROW_BYTES);
 #pragma unroll
         for (int db = 0; db < DB_EFF; ++db)

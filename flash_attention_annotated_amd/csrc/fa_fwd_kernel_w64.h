@@ -942,11 +942,16 @@ __global__ __launch_bounds__(256, 1) void fwd_kernel_w64(const KParams p) {
         const int row_a_e = wrow + r_e, row_b_e = wrow + 32 + r_e;
         const float lt_a = half_swap_sum(l_a), lt_b = half_swap_sum(l_b);
         const bool e_a = (lt_a == 0.f) || (lt_a != lt_a), e_b = (lt_b == 0.f) || (lt_b != lt_b);
-        const float inv_a = (e_a ? 1.f : 1.f / lt_a) * vdesc_e, inv_b = (e_b ? 1.f : 1.f / lt_b) * vdesc_e;
+        float inv_a = (e_a ? 1.f : 1.f / lt_a) * vdesc_e, inv_b = (e_b ? 1.f : 1.f / lt_b) * vdesc_e;
         if (wrow >= sq) return;
+        float lse_a = e_a ? INFINITY : m_a * scale_e + __logf(lt_a), lse_b = e_b ? INFINITY : m_b * scale_e + __logf(lt_b);
+        if (p.sink) {  // this item's head: the switch to the next item comes behind this epilogue
+            sink_finalize(row_a_e < sq ? load_sink(p, head, row_a_e) : -INFINITY, m_a * scale_e, lt_a, e_a, inv_a, lse_a);
+            sink_finalize(row_b_e < sq ? load_sink(p, head, row_b_e) : -INFINITY, m_b * scale_e, lt_b, e_b, inv_b, lse_b);
+        }
         if (hh_e == 0) {
-            if (row_a_e < sq) p.lse[lse_base + row_a_e] = e_a ? INFINITY : m_a * scale_e + __logf(lt_a);
-            if (row_b_e < sq) p.lse[lse_base + row_b_e] = e_b ? INFINITY : m_b * scale_e + __logf(lt_b);
+            if (row_a_e < sq) p.lse[lse_base + row_a_e] = lse_a;
+            if (row_b_e < sq) p.lse[lse_base + row_b_e] = lse_b;
         }
         FA_PSTAMP(58);  // LSE written
         const int rows_here = min(sq - wrow, 64);
@@ -1549,12 +1554,17 @@ __global__ __launch_bounds__(256, 1) void fwd_kernel_w64(const KParams p) {
         const int row_a_e = wrow + r_e, row_b_e = wrow + 32 + r_e;
         const float lt_a = half_swap_sum(l_a), lt_b = half_swap_sum(l_b);
         const bool e_a = (lt_a == 0.f) || (lt_a != lt_a), e_b = (lt_b == 0.f) || (lt_b != lt_b);
-        const float inv_a = (e_a ? 1.f : 1.f / lt_a) * vdesc_e, inv_b = (e_b ? 1.f : 1.f / lt_b) * vdesc_e;
+        float inv_a = (e_a ? 1.f : 1.f / lt_a) * vdesc_e, inv_b = (e_b ? 1.f : 1.f / lt_b) * vdesc_e;
+        float lse_a = e_a ? INFINITY : m_a * scale_e + __logf(lt_a), lse_b = e_b ? INFINITY : m_b * scale_e + __logf(lt_b);
+        if (p.sink) {
+            sink_finalize(row_a_e < sq ? load_sink(p, head, row_a_e) : -INFINITY, m_a * scale_e, lt_a, e_a, inv_a, lse_a);
+            sink_finalize(row_b_e < sq ? load_sink(p, head, row_b_e) : -INFINITY, m_b * scale_e, lt_b, e_b, inv_b, lse_b);
+        }
         const bool wave_active = wrow < sq;
         if (wave_active) {
             if (hh_e == 0) {
-                if (row_a_e < sq) p.lse[lse_base + row_a_e] = e_a ? INFINITY : m_a * scale_e + __logf(lt_a);
-                if (row_b_e < sq) p.lse[lse_base + row_b_e] = e_b ? INFINITY : m_b * scale_e + __logf(lt_b);
+                if (row_a_e < sq) p.lse[lse_base + row_a_e] = lse_a;
+                if (row_b_e < sq) p.lse[lse_base + row_b_e] = lse_b;
             }
             if (!PERSIST && p.num_splits > 1) {
                 // split-KV partial: fp32 in the caller's workspace (role of out_accum, csrc/flash_attn/flash_api.cpp:297-318), straight

@@ -125,6 +125,10 @@ struct FwdArgs {
     OptTensor seqused_q, q_descale, k_descale, v_descale;
     bool fa3_window = false;
     int64_t attention_chunk = 0;
+    // cute surface only: the learnable sink, (num_heads,) bf16 or fp32, and how the kernel's (head, row) finds its logit --
+    // (1, 0), or (ngroups, 1) when the decode route has folded the GQA group into the rows (include/fa_fwd.h)
+    OptTensor sink;
+    int sink_head_stride = 1, sink_row_stride = 0;
 };
 
 // torch tensors -> fa_fwd_params -> fa_fwd on torch's current stream (q/k/v/out: last stride 1, aligned())
@@ -210,6 +214,17 @@ void launch_fwd(const Tensor &q, const Tensor &k, const Tensor &v, const Tensor 
         const uintptr_t base = (reinterpret_cast<uintptr_t>(workspace.data_ptr()) + 255) / 256 * 256;
         p.workspace = reinterpret_cast<void *>(base);
         p.workspace_bytes = (uint64_t)need;
+    }
+    if (a.sink.has_value()) {  // same params, same plan, same workspace: the sink rides in a struct of its own
+        fa_sink_params s{};
+        s.abi_version = FA_ABI_VERSION;
+        s.struct_size = sizeof(fa_sink_params);
+        s.learnable_sink = a.sink->data_ptr();
+        s.sink_dtype = a.sink->scalar_type() == at::kFloat ? FA_DTYPE_FP32 : FA_DTYPE_BF16;
+        s.sink_head_stride = a.sink_head_stride; s.sink_row_stride = a.sink_row_stride;
+        const int st = fa_fwd_sink(&p, &s, current_stream(q));
+        TORCH_CHECK(st == 0, "fa_fwd_sink failed (", st, "): ", fa_strerror(st));
+        return;
     }
     const int st = fa_fwd(&p, current_stream(q));
     TORCH_CHECK(st == 0, "fa_fwd failed (", st, "): ", fa_strerror(st));
@@ -682,13 +697,14 @@ void rotary_apply_varlen(const Tensor &src, const Tensor &dst, const Tensor &cu_
 }
 
 // mha_fwd_kvcache, csrc/flash_attn/flash_api.cpp:1202-1476 (+ the page-size rule of the calling surface: FA2 256, FA3 any)
-std::vector<Tensor> fwd_kvcache_impl(Tensor q, const Tensor &kcache, const Tensor &vcache, OptTensor k_, OptTensor v_,
+// (`sink_`: the cute surface's learnable sink, (num_heads,) -- checked by its caller; no other surface passes one)
+std::vector<Tensor> fwd_kvcache_core(Tensor q, const Tensor &kcache, const Tensor &vcache, OptTensor k_, OptTensor v_,
                                      OptTensor seqlens_k_, OptTensor rotary_cos_, OptTensor rotary_sin_,
                                      OptTensor cache_batch_idx_, OptTensor leftpad_k_, OptTensor block_table_,
                                      OptTensor alibi_slopes_, OptTensor out_, const double softmax_scale, bool is_causal,
                                      int64_t window_size_left, int64_t window_size_right, const double softcap,
                                      bool is_rotary_interleaved, int64_t num_splits, int64_t page_multiple,
-                                     OptTensor seqlens_rotary_, OptTensor qv_) {
+                                     OptTensor seqlens_rotary_, OptTensor qv_, OptTensor sink_) {
     const auto q_dtype = q.scalar_type();
     TORCH_CHECK(q_dtype == at::kHalf || q_dtype == at::kBFloat16, "FlashAttention only support fp16 and bf16 data type");
     TORCH_CHECK(kcache.scalar_type() == q_dtype, "query and key must have the same dtype");
@@ -833,11 +849,19 @@ std::vector<Tensor> fwd_kvcache_impl(Tensor q, const Tensor &kcache, const Tenso
         a.seqused_k = seqused; a.alibi = alibi; a.kv_batch_idx = cache_batch_idx_; a.block_table = block_table_;
         a.num_splits = (int)num_splits; a.leftpad_k = leftpad_k_;
         if (qv_.has_value()) a.qv = aligned_or_copy(*qv_);
+        if (sink_.has_value()) {
+            a.sink = sink_;
+            if (swapped) {  // kernel head g, row r = query head g * ngroups + r
+                a.sink_head_stride = (int)seqlen_q; a.sink_row_stride = 1;
+            }
+        }
         launch_fwd(qc, kcache, vcache, oc, softmax_lse, a);
         if (!oc.is_same(out)) out.copy_(oc);
     } else {
         out.zero_();
         softmax_lse.fill_(std::numeric_limits<float>::infinity());
+        if (sink_.has_value())  // no key at all: the logsumexp of the sink alone (swapped: heads lie along (h_k, ngroups))
+            softmax_lse.copy_(swapped ? sink_->to(at::kFloat).view({1, num_heads, seqlen_q}) : sink_->to(at::kFloat).view({1, num_heads, 1}));
     }
     if (swapped) {
         out = out.transpose(1, 2).reshape({batch_size, 1, num_heads_k * seqlen_q, head_size_v});
@@ -848,6 +872,18 @@ std::vector<Tensor> fwd_kvcache_impl(Tensor q, const Tensor &kcache, const Tenso
         }
     }
     return {out, softmax_lse};
+}
+
+std::vector<Tensor> fwd_kvcache_impl(Tensor q, const Tensor &kcache, const Tensor &vcache, OptTensor k_, OptTensor v_,
+                                     OptTensor seqlens_k_, OptTensor rotary_cos_, OptTensor rotary_sin_,
+                                     OptTensor cache_batch_idx_, OptTensor leftpad_k_, OptTensor block_table_,
+                                     OptTensor alibi_slopes_, OptTensor out_, const double softmax_scale, bool is_causal,
+                                     int64_t window_size_left, int64_t window_size_right, const double softcap,
+                                     bool is_rotary_interleaved, int64_t num_splits, int64_t page_multiple,
+                                     OptTensor seqlens_rotary_, OptTensor qv_) {
+    return fwd_kvcache_core(q, kcache, vcache, k_, v_, seqlens_k_, rotary_cos_, rotary_sin_, cache_batch_idx_, leftpad_k_,
+                            block_table_, alibi_slopes_, out_, softmax_scale, is_causal, window_size_left, window_size_right, softcap,
+                            is_rotary_interleaved, num_splits, page_multiple, seqlens_rotary_, qv_, c10::nullopt);
 }
 
 std::vector<Tensor> mha_fwd_kvcache(Tensor &q, const Tensor &kcache, const Tensor &vcache, OptTensor &k_, OptTensor &v_,
@@ -893,7 +929,8 @@ std::tuple<Tensor, Tensor> fwd_kvcache_ragged(const Tensor &q, const Tensor &kca
                                               const OptTensor &page_table, const OptTensor &kv_batch_idx, const OptTensor &leftpad_k,
                                               const OptTensor &rotary_cos, const OptTensor &rotary_sin, const OptTensor &seqlens_rotary,
                                               double softmax_scale, bool is_causal, int64_t window_size_left,
-                                              int64_t window_size_right, double softcap, bool is_rotary_interleaved, int64_t num_splits) {
+                                              int64_t window_size_right, double softcap, bool is_rotary_interleaved, int64_t num_splits,
+                                              const OptTensor &sink = c10::nullopt) {
     const auto q_dtype = q.scalar_type();
     CHECK_DEVICE(cu_seqlens_q, "cu_seqlens_q");
     TORCH_CHECK(cu_seqlens_q.is_contiguous(), "cu_seqlens_q must be contiguous");
@@ -1005,9 +1042,9 @@ std::tuple<Tensor, Tensor> fwd_kvcache_ragged(const Tensor &q, const Tensor &kca
         OptTensor out4, qv4;
         if (out_.has_value()) out4 = out_->unsqueeze(1);
         if (qv.has_value()) qv4 = qv->unsqueeze(1);
-        auto r = fwd_kvcache_impl(q.unsqueeze(1), kcache, vcache, k_new, v_new, seqused_k, rotary_cos, rotary_sin, kv_batch_idx, leftpad_k,
+        auto r = fwd_kvcache_core(q.unsqueeze(1), kcache, vcache, k_new, v_new, seqused_k, rotary_cos, rotary_sin, kv_batch_idx, leftpad_k,
                                   page_table, c10::nullopt, out4, softmax_scale, is_causal, window_size_left, window_size_right,
-                                  softcap, is_rotary_interleaved, num_splits, 1, seqlens_rotary, qv4);
+                                  softcap, is_rotary_interleaved, num_splits, 1, seqlens_rotary, qv4, sink);
         return {r[0].reshape(out_shape), r[1].reshape({batch_size, num_heads}).transpose(0, 1)};
     }
     Tensor qc = aligned_or_copy(q);
@@ -1025,9 +1062,9 @@ std::tuple<Tensor, Tensor> fwd_kvcache_ragged(const Tensor &q, const Tensor &kca
         OptTensor out4, qv4;
         if (out_.has_value()) out4 = out_->unsqueeze(1);
         if (qv.has_value()) qv4 = qv->unsqueeze(1);
-        auto r = fwd_kvcache_impl(qc.unsqueeze(1), kcache, vcache, c10::nullopt, c10::nullopt, seqused, c10::nullopt, c10::nullopt,
+        auto r = fwd_kvcache_core(qc.unsqueeze(1), kcache, vcache, c10::nullopt, c10::nullopt, seqused, c10::nullopt, c10::nullopt,
                                   kv_batch_idx, leftpad_k, page_table, c10::nullopt, out4, softmax_scale, is_causal, window_size_left,
-                                  window_size_right, softcap, false, num_splits, 1, c10::nullopt, qv4);
+                                  window_size_right, softcap, false, num_splits, 1, c10::nullopt, qv4, sink);
         return {r[0].reshape(out_shape), r[1].reshape({batch_size, num_heads}).transpose(0, 1)};
     }
     Tensor out = out_.has_value() ? *out_ : at::empty(out_shape, q.options());
@@ -1042,13 +1079,14 @@ std::tuple<Tensor, Tensor> fwd_kvcache_ragged(const Tensor &q, const Tensor &kca
         a.softmax_scale = softmax_scale; a.causal = is_causal; a.window_left = window_size_left; a.window_right = window_size_right;
         a.softcap = softcap; a.cu_seqlens_q = cu_seqlens_q; a.seqused_q = seqused_q; a.seqused_k = seqused;
         a.kv_batch_idx = kv_batch_idx; a.block_table = page_table; a.leftpad_k = leftpad_k; a.fa3_window = true;
-        a.num_splits = (int)num_splits;
+        a.num_splits = (int)num_splits; a.sink = sink;
         if (qv.has_value()) a.qv = aligned_or_copy(*qv);
         launch_fwd(qc, kcache, vcache, oc, softmax_lse, a);
         if (!oc.is_same(out)) out.copy_(oc);
     } else {
         out.zero_();
         softmax_lse.fill_(std::numeric_limits<float>::infinity());
+        if (sink.has_value()) softmax_lse.copy_(sink->to(at::kFloat).view({num_heads, 1}));
     }
     return {out, softmax_lse};
 }
@@ -1065,7 +1103,8 @@ std::tuple<Tensor, Tensor> fwd_kvcache_ragged(const Tensor &q, const Tensor &kca
 // cu_seqlens_k_new without cu_seqlens_q, qv of any other shape or with fp8, KV-cache arguments together with cu_seqlens_k,
 // attention_chunk or fp8.  `scheduler_metadata`, `pack_gqa`, `sm_margin`
 // are performance hints and do not change results: ignored.
-std::tuple<Tensor, Tensor, OptTensor, OptTensor> fa3_fwd(
+// (`sink`, `cute`: the cute surface, below -- its learnable sink, and num_splits honoured on the dense route too)
+std::tuple<Tensor, Tensor, OptTensor, OptTensor> fa3_fwd_core(
         const Tensor &q, const Tensor &k, const Tensor &v, const OptTensor &k_new, const OptTensor &v_new, const OptTensor &qv,
         const OptTensor &out_, const OptTensor &cu_seqlens_q, const OptTensor &cu_seqlens_k, const OptTensor &cu_seqlens_k_new,
         const OptTensor &seqused_q, const OptTensor &seqused_k, c10::optional<int64_t> max_seqlen_q_,
@@ -1074,7 +1113,7 @@ std::tuple<Tensor, Tensor, OptTensor, OptTensor> fa3_fwd(
         const OptTensor &q_descale, const OptTensor &k_descale, const OptTensor &v_descale, c10::optional<double> softmax_scale_,
         bool is_causal, int64_t window_size_left, int64_t window_size_right, c10::optional<int64_t> attention_chunk_,
         double softcap, bool is_rotary_interleaved, const OptTensor & /*scheduler_metadata*/, int64_t num_splits,
-        c10::optional<bool> /*pack_gqa*/, int64_t /*sm_margin*/) {
+        c10::optional<bool> /*pack_gqa*/, int64_t /*sm_margin*/, const OptTensor &sink, bool cute) {
     const auto q_dtype = q.scalar_type();
     const bool is_fp8 = q_dtype == at::kFloat8_e4m3fn;
     TORCH_CHECK(q_dtype == at::kHalf || q_dtype == at::kBFloat16 || is_fp8,
@@ -1135,12 +1174,12 @@ std::tuple<Tensor, Tensor, OptTensor, OptTensor> fa3_fwd(
             auto r = fwd_kvcache_ragged(q, k, v, k_new, v_new, qv, out_, *cu_seqlens_q, cu_seqlens_k_new, seqused_q, seqused_k,
                                         max_seqlen_q_.value_or(-1), page_table, kv_batch_idx, leftpad_k, rotary_cos, rotary_sin,
                                         seqlens_rotary, softmax_scale_.value_or(default_scale), is_causal, window_size_left,
-                                        window_size_right, softcap, is_rotary_interleaved, num_splits);
+                                        window_size_right, softcap, is_rotary_interleaved, num_splits, sink);
             return {std::get<0>(r), std::get<1>(r), c10::nullopt, c10::nullopt};
         }
-        auto r = fwd_kvcache_impl(q, k, v, k_new, v_new, seqused_k, rotary_cos, rotary_sin, kv_batch_idx, leftpad_k, page_table,
+        auto r = fwd_kvcache_core(q, k, v, k_new, v_new, seqused_k, rotary_cos, rotary_sin, kv_batch_idx, leftpad_k, page_table,
                                   c10::nullopt, out_, softmax_scale_.value_or(default_scale), is_causal, window_size_left,
-                                  window_size_right, softcap, is_rotary_interleaved, num_splits, 1, seqlens_rotary, qv);
+                                  window_size_right, softcap, is_rotary_interleaved, num_splits, 1, seqlens_rotary, qv, sink);
         return {r[0], r[1], c10::nullopt, c10::nullopt};
     }
     if (!cu_seqlens_q && !cu_seqlens_k && !seqused_q && seqused_k && !is_fp8 && q.dim() == 4 && q.size(1) <= 128 &&
@@ -1149,9 +1188,9 @@ std::tuple<Tensor, Tensor, OptTensor, OptTensor> fa3_fwd(
         // plain decode over a cache (flash_attn_with_kvcache(q, k_cache, v_cache, cache_seqlens=...)): the same routine as
         // the append / paged calls, which brings the split-KV heuristic (num_splits = 0) and the (b, 1, h) -> (b, ngroups, h_k)
         // GQA swap (:935-1060 runs them for every call with seqused_k)
-        auto r = fwd_kvcache_impl(q, k, v, c10::nullopt, c10::nullopt, seqused_k, c10::nullopt, c10::nullopt, c10::nullopt,
+        auto r = fwd_kvcache_core(q, k, v, c10::nullopt, c10::nullopt, seqused_k, c10::nullopt, c10::nullopt, c10::nullopt,
                                   c10::nullopt, c10::nullopt, c10::nullopt, c10::nullopt, softmax_scale_.value_or(default_scale),
-                                  is_causal, -1, -1, softcap, false, num_splits, 1, c10::nullopt, qv);
+                                  is_causal, -1, -1, softcap, false, num_splits, 1, c10::nullopt, qv, sink);
         return {r[0], r[1], c10::nullopt, c10::nullopt};
     }
     const bool varlen = cu_seqlens_q.has_value();
@@ -1222,14 +1261,33 @@ std::tuple<Tensor, Tensor, OptTensor, OptTensor> fa3_fwd(
         a.seqused_k = seqused_k; a.q_descale = q_descale; a.k_descale = k_descale; a.v_descale = v_descale;
         a.fa3_window = true; a.attention_chunk = attention_chunk;
         if (qv.has_value()) a.qv = aligned_or_copy(*qv);
-        a.num_splits = 1;  // no split-KV: the decode calls of the FA3 surface take the fwd_kvcache_impl routes above
+        a.num_splits = cute ? (int)num_splits : 1;  // no split-KV: the decode calls of the FA3 surface take the fwd_kvcache_impl routes above
+        a.sink = sink;
         launch_fwd(qc, kc, vc, oc, softmax_lse, a);
         if (!oc.is_same(out)) out.copy_(oc);
     } else if (total_q > 0) {
         out.zero_();  // :1190-1194
         softmax_lse.fill_(std::numeric_limits<float>::infinity());
+        if (sink.has_value()) softmax_lse.copy_(varlen ? sink->to(at::kFloat).view({num_heads, 1}) : sink->to(at::kFloat).view({1, num_heads, 1}));
     }
     return {out, softmax_lse, c10::nullopt, c10::nullopt};
+}
+
+std::tuple<Tensor, Tensor, OptTensor, OptTensor> fa3_fwd(
+        const Tensor &q, const Tensor &k, const Tensor &v, const OptTensor &k_new, const OptTensor &v_new, const OptTensor &qv,
+        const OptTensor &out_, const OptTensor &cu_seqlens_q, const OptTensor &cu_seqlens_k, const OptTensor &cu_seqlens_k_new,
+        const OptTensor &seqused_q, const OptTensor &seqused_k, c10::optional<int64_t> max_seqlen_q_,
+        c10::optional<int64_t> max_seqlen_k_, const OptTensor &page_table, const OptTensor &kv_batch_idx,
+        const OptTensor &leftpad_k, const OptTensor &rotary_cos, const OptTensor &rotary_sin, OptTensor seqlens_rotary,
+        const OptTensor &q_descale, const OptTensor &k_descale, const OptTensor &v_descale, c10::optional<double> softmax_scale_,
+        bool is_causal, int64_t window_size_left, int64_t window_size_right, c10::optional<int64_t> attention_chunk_,
+        double softcap, bool is_rotary_interleaved, const OptTensor &scheduler_metadata, int64_t num_splits,
+        c10::optional<bool> pack_gqa, int64_t sm_margin) {
+    return fa3_fwd_core(q, k, v, k_new, v_new, qv, out_, cu_seqlens_q, cu_seqlens_k, cu_seqlens_k_new, seqused_q, seqused_k,
+                        max_seqlen_q_, max_seqlen_k_, page_table, kv_batch_idx, leftpad_k, rotary_cos, rotary_sin, seqlens_rotary,
+                        q_descale, k_descale, v_descale, softmax_scale_, is_causal, window_size_left, window_size_right,
+                        attention_chunk_, softcap, is_rotary_interleaved, scheduler_metadata, num_splits, pack_gqa, sm_margin,
+                        c10::nullopt, false);
 }
 
 // flash_attn_3::bwd, hopper/flash_api.cpp:1259-1570 (22 arguments of the schema), on the FA2-shaped backward of this build
@@ -1298,6 +1356,88 @@ std::vector<Tensor> fa3_bwd(const Tensor &dout, const Tensor &q, const Tensor &k
     }
     for (int i = 0; i < 4; ++i) r.push_back(at::empty({0}, q.options().dtype(at::kFloat)));
     return r;
+}
+
+// ---- the cute surface (flash_attn/cute/interface.py:1141-1210): flash_attn_func / flash_attn_varlen_func with learnable_sink ----
+// The sink is (num_heads,) bf16 (the reference's) or fp32, on q's device, contiguous; cute_interface.py has the reference's
+// checks and texts, these are the ones the launch depends on.
+void check_sink(const OptTensor &sink, const Tensor &q) {
+    if (!sink.has_value()) return;
+    TORCH_CHECK(sink->is_cuda() && sink->device() == q.device(), "inputs must be on CUDA device");
+    TORCH_CHECK(sink->scalar_type() == at::kBFloat16 || sink->scalar_type() == at::kFloat, "learnable_sink must be bfloat16 (or float32)");
+    TORCH_CHECK(sink->dim() == 1 && sink->size(0) == q.size(-2) && sink->is_contiguous(), "learnable_sink must be contiguous of shape (num_head,)");
+}
+
+// Routes like fa3_fwd (KV-cache steps with their GQA swap and split heuristic, ragged queries over a cache, dense, varlen);
+// max_seqlen_q / max_seqlen_k are upper bounds the caller derives from shapes (the cute signatures carry none): the grid
+// is made from them, the kernels read the lengths on the device.  Returns (out, softmax_lse).
+std::tuple<Tensor, Tensor> cute_fwd(const Tensor &q, const Tensor &k, const Tensor &v, const OptTensor &cu_seqlens_q,
+                                    const OptTensor &cu_seqlens_k, const OptTensor &seqused_q, const OptTensor &seqused_k,
+                                    c10::optional<int64_t> max_seqlen_q, c10::optional<int64_t> max_seqlen_k,
+                                    const OptTensor &page_table, c10::optional<double> softmax_scale, bool is_causal,
+                                    int64_t window_size_left, int64_t window_size_right, const OptTensor &learnable_sink,
+                                    double softcap, int64_t num_splits) {
+    check_sink(learnable_sink, q);
+    const OptTensor none;
+    auto r = fa3_fwd_core(q, k, v, none, none, none, none, cu_seqlens_q, cu_seqlens_k, none, seqused_q, seqused_k, max_seqlen_q,
+                          max_seqlen_k, page_table, none, none, none, none, none, none, none, none, softmax_scale, is_causal,
+                          window_size_left, window_size_right, c10::nullopt, softcap, false, none, num_splits, c10::nullopt, 0,
+                          learnable_sink, true);
+    return {std::get<0>(r), std::get<1>(r)};
+}
+
+// dsink (num_heads,) fp32 from the LSE of a forward with a sink and the softmax_d of its fa_bwd (include/fa_bwd.h)
+Tensor sink_grad(const Tensor &softmax_lse, const Tensor &softmax_d, const Tensor &learnable_sink, const OptTensor &cu_seqlens_q,
+                 const OptTensor &seqused_q, int64_t batch, int64_t seqlen_q) {
+    TORCH_CHECK(softmax_lse.scalar_type() == at::kFloat && softmax_d.scalar_type() == at::kFloat, "softmax_lse / softmax_d must be fp32");
+    TORCH_CHECK(softmax_lse.is_cuda() && softmax_d.is_cuda() && learnable_sink.is_cuda(), "inputs must be on CUDA device");
+    TORCH_CHECK(softmax_d.is_contiguous(), "softmax_d must be contiguous");
+    const bool varlen = cu_seqlens_q.has_value();
+    TORCH_CHECK(softmax_lse.dim() == (varlen ? 2 : 3), "softmax_lse must be (b, h, seqlen_q) or, varlen, (h, total_q)");
+    const int64_t h = learnable_sink.size(0);
+    c10::hip::HIPGuardMasqueradingAsCUDA device_guard(softmax_lse.device());
+    const Tensor lse = softmax_lse.is_contiguous() ? softmax_lse : softmax_lse.contiguous();
+    Tensor dsink = at::empty({h}, softmax_lse.options());
+    fa_sink_grad_params p{};
+    p.abi_version = FA_ABI_VERSION;
+    p.struct_size = sizeof(fa_sink_grad_params);
+    p.softmax_lse = static_cast<const float *>(lse.data_ptr());
+    p.softmax_d = static_cast<const float *>(softmax_d.data_ptr());
+    p.learnable_sink = learnable_sink.data_ptr();
+    p.dsink = static_cast<float *>(dsink.data_ptr());
+    p.cu_seqlens_q = static_cast<const int32_t *>(ptr(cu_seqlens_q));
+    p.seqused_q = static_cast<const int32_t *>(ptr(seqused_q));
+    p.softmax_d_row_len = softmax_d.size(-1);
+    p.b = (int32_t)batch; p.seqlen_q = (int32_t)seqlen_q; p.h = (int32_t)h;
+    p.total_q = varlen ? (int32_t)lse.size(1) : 0;
+    p.sink_dtype = learnable_sink.scalar_type() == at::kFloat ? FA_DTYPE_FP32 : FA_DTYPE_BF16;
+    const int st = fa_sink_grad(&p, current_stream(lse));
+    TORCH_CHECK(st == 0, "fa_sink_grad failed (", st, "): ", fa_strerror(st));
+    return dsink;
+}
+
+// The backward of cute_fwd's dense and varlen calls: fa3_bwd as it stands -- the LSE holds the sink, and the sink's column has
+// no value -- and, with a sink, its own gradient in the sink's dtype.  Returns (dq, dk, dv, dsink or None).
+std::tuple<Tensor, Tensor, Tensor, OptTensor> cute_bwd(const Tensor &dout, const Tensor &q, const Tensor &k, const Tensor &v,
+                                                       const Tensor &out, const Tensor &softmax_lse, const OptTensor &cu_seqlens_q,
+                                                       const OptTensor &cu_seqlens_k, c10::optional<int64_t> max_seqlen_q,
+                                                       c10::optional<int64_t> max_seqlen_k, c10::optional<double> softmax_scale,
+                                                       bool is_causal, int64_t window_size_left, int64_t window_size_right,
+                                                       double softcap, const OptTensor &learnable_sink) {
+    check_sink(learnable_sink, q);
+    const OptTensor none;
+    auto r = fa3_bwd(dout, q, k, v, out, softmax_lse, none, none, none, cu_seqlens_q, cu_seqlens_k, none, none, max_seqlen_q,
+                     max_seqlen_k, softmax_scale, is_causal, window_size_left, window_size_right, softcap, true, 0);
+    OptTensor dsink;
+    if (learnable_sink.has_value()) {
+        const bool varlen = cu_seqlens_q.has_value();
+        const int64_t batch = varlen ? cu_seqlens_q->numel() - 1 : q.size(0);
+        if (q.numel() > 0)
+            dsink = sink_grad(softmax_lse, r[3], *learnable_sink, cu_seqlens_q, none, batch, varlen ? 0 : q.size(1)).to(learnable_sink->scalar_type());
+        else
+            dsink = at::zeros_like(*learnable_sink);
+    }
+    return {r[0], r[1], r[2], dsink};
 }
 
 // flash_attn_3::fwd_combine, hopper/flash_api.cpp:1569-1670: merge caller-held split-KV partials.  out_partial
@@ -1369,4 +1509,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("fa3_fwd", &fa3_fwd, "FA3 forward pass (flash_attn_3::fwd)");
     m.def("fa3_bwd", &fa3_bwd, "FA3 backward pass (flash_attn_3::bwd)");
     m.def("fa3_fwd_combine", &fa3_fwd_combine, "FA3 merge of split-KV partials (flash_attn_3::fwd_combine)");
+    m.def("cute_fwd", &cute_fwd, "cute surface forward (flash_attn.cute.interface, with learnable_sink)");
+    m.def("cute_bwd", &cute_bwd, "cute surface backward: (dq, dk, dv, dsink)");
+    m.def("sink_grad", &sink_grad, "gradient of a learnable sink from softmax_lse and softmax_d");
 }

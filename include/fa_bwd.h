@@ -90,6 +90,33 @@ int fa_bwd_validate(const fa_bwd_params *params);
 /* sizeof(fa_bwd_params) as compiled, for binding self-checks. */
 uint32_t fa_bwd_params_size(void);
 
+/*
+ * Gradient of a learnable attention sink (fa_fwd_sink, include/fa_fwd.h).  With the sink inside the stored LSE,
+ * P = exp(S - LSE) and D_i = sum_d dO.O = sum_j P_ij dP_ij (the sink's column has no value: it adds nothing to D), so
+ * fa_bwd gives dq, dk, dv of a call with a sink as it stands; the sink's own gradient is
+ *     dsink[h] = - sum_{b, i} exp(z_h - LSE[b, h, i]) * D[b, h, i]
+ * over the valid rows of the softmax_d fa_bwd has written (run this behind it, on the same stream).  One workgroup per
+ * head, every partial sum in a fixed order, no atomics: bit-reproducible like the rest of the backward.  No workspace.
+ */
+typedef struct fa_sink_grad_params {
+    uint32_t abi_version; /* FA_ABI_VERSION */
+    uint32_t struct_size; /* sizeof(fa_sink_grad_params) */
+    const float *softmax_lse;   /* as fa_fwd_sink wrote it: (b, h, seqlen_q) or varlen (h, total_q) */
+    const float *softmax_d;     /* as fa_bwd wrote it: (b, h, softmax_d_row_len) or varlen (h, softmax_d_row_len) */
+    const void *learnable_sink; /* (h), contiguous */
+    float *dsink;               /* (h) fp32, written (not accumulated) */
+    const int32_t *cu_seqlens_q; /* (b + 1) or NULL = dense */
+    const int32_t *seqused_q;    /* (b) or NULL: rows of each sequence that count */
+    int64_t softmax_d_row_len;
+    int32_t b, seqlen_q, h, total_q;
+    int32_t sink_dtype; /* FA_DTYPE_BF16 / FA_DTYPE_FP32 */
+    int32_t reserved;
+} fa_sink_grad_params;
+
+int fa_sink_grad(const fa_sink_grad_params *params, void *stream);
+int fa_sink_grad_validate(const fa_sink_grad_params *params);
+uint32_t fa_sink_grad_params_size(void);
+
 #ifdef __cplusplus
 }
 #endif

@@ -246,6 +246,43 @@ const char *fa_fwd_plan_name(const fa_fwd_params *params, int32_t num_cus);
  * thread-local storage of its own, valid until the next call on the same thread. */
 const char *fa_fwd_last_plan_name(void);
 
+/*
+ * Learnable attention sink -- `learnable_sink=` of flash_attn.cute.interface.flash_attn_func / flash_attn_varlen_func
+ * (flash_attn/cute/interface.py:1141-1210; kernel side flash_attn/cute/softmax.py:111-141; oracle
+ * flash_attn/cute/testing.py:376-387): one logit z per query head, in natural-log units (neither scaled by softmax_scale nor
+ * soft-capped), that joins the softmax denominator and carries no value.  For query row i with final scores s_ij:
+ *     m' = max(max_j s_ij, z)     l' = sum_j exp(s_ij - m') + exp(z - m')
+ *     P_ij = exp(s_ij - m') / l'  O_i = sum_j P_ij v_j      LSE_i = m' + log l'   (the sink included)
+ * The pair is rebased on the larger of the row maximum and the sink, so a sink far above every score gives LSE ~ z, never
+ * inf.  A row without a visible key gives O = 0 and LSE = z (without a sink such rows keep +inf).  z = -inf is the call
+ * without a sink, bit for bit in O and LSE.
+ * fa_fwd_params has no room for a pointer (its size is pinned), so the sink travels in a struct of its own.  A sink never
+ * changes the plan: fa_fwd_workspace_size, fa_fwd_plan_name and fa_fwd_last_plan_name read fa_fwd_params alone and mean
+ * the same with and without one -- the sink is a run-time term of the kernels' epilogues (fwd_kernel, fwd_kernel_w64,
+ * fwd_kernel_d256) and, under split-KV, of the merge (the parts write sink-free partials; fa_fwd_combine over caller-held
+ * partials knows no sink).
+ * Accepted: everything the 16-bit kernels take -- causal, both window sides, softcap, attention_chunk, d_v != d, varlen,
+ * seqused_q/k, leftpad_k, kv_batch_idx, paged K/V, split-KV, ragged queries over a cache.  FA_ERR_UNSUPPORTED: fp8 inputs,
+ * qv (and the other calls the qv kernel runs), dropout, ALiBi, s_dmask.
+ */
+typedef struct fa_sink_params {
+    uint32_t abi_version; /* FA_ABI_VERSION */
+    uint32_t struct_size; /* sizeof(fa_sink_params) */
+    const void *learnable_sink; /* device pointer, (h) logits through the strides below */
+    int32_t sink_dtype;         /* FA_DTYPE_BF16 (the reference's) or FA_DTYPE_FP32 */
+    /* row r of head g (as fa_fwd_params counts heads and rows) reads learnable_sink[g * sink_head_stride + r * sink_row_stride]:
+     * (1, 0) normally; (h / h_k, 1) when the caller has folded the GQA group of a one-row decode step into the rows
+     * ((b, 1, h, d) viewed as (b, h / h_k, h_k, d)).  sink_row_stride must be 0 with cu_seqlens_q.  Both >= 0. */
+    int32_t sink_head_stride, sink_row_stride;
+    int32_t reserved;
+} fa_sink_params;
+
+/* fa_fwd with a sink: same params, same plan, same workspace.  `sink` must not be NULL (use fa_fwd). */
+int fa_fwd_sink(const fa_fwd_params *params, const fa_sink_params *sink, void *stream);
+/* Validation only; the sink's own refusals are looked at before fa_fwd_validate's. */
+int fa_fwd_sink_validate(const fa_fwd_params *params, const fa_sink_params *sink);
+uint32_t fa_sink_params_size(void);
+
 /* Human-readable text for a status code (static storage). */
 const char *fa_strerror(int status);
 
