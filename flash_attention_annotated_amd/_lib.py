@@ -48,6 +48,9 @@ EXPORTED_SYMBOLS = (
     "fa_fwd_sink",
     "fa_fwd_sink_validate",
     "fa_sink_params_size",
+    "fa_fwd_block_sparse",
+    "fa_fwd_block_sparse_validate",
+    "fa_block_sparse_params_size",
     # include/fa_bwd.h
     "fa_bwd",
     "fa_bwd_validate",
@@ -235,6 +238,17 @@ class FaSinkParams(ctypes.Structure):
     )
 
 
+class FaBlockSparseParams(ctypes.Structure):
+    """Field-for-field mirror of `struct fa_block_sparse_params` (include/fa_fwd.h)."""
+
+    _fields_ = (
+        [("abi_version", ctypes.c_uint32), ("struct_size", ctypes.c_uint32)]
+        + [(n, ctypes.c_void_p) for n in ("full_block_cnt", "full_block_idx", "mask_block_cnt", "mask_block_idx")]
+        + [(n, ctypes.c_int64 * 4) for n in ("full_cnt_stride", "full_idx_stride", "mask_cnt_stride", "mask_idx_stride")]
+        + [("block_m", ctypes.c_int32), ("block_n", ctypes.c_int32)]
+    )
+
+
 class FaSinkGradParams(ctypes.Structure):
     """Field-for-field mirror of `struct fa_sink_grad_params` (include/fa_bwd.h)."""
 
@@ -392,6 +406,16 @@ def load():
     lib.fa_sink_params_size.restype = ctypes.c_uint32
     if lib.fa_sink_params_size() != ctypes.sizeof(FaSinkParams):
         raise RuntimeError("fa_sink_params layout mismatch between include/fa_fwd.h and _lib")
+    lib.fa_fwd_block_sparse.argtypes = [ctypes.POINTER(FaFwdParams), ctypes.POINTER(FaBlockSparseParams),
+                                        ctypes.POINTER(FaSinkParams), ctypes.c_void_p]
+    lib.fa_fwd_block_sparse.restype = ctypes.c_int
+    lib.fa_fwd_block_sparse_validate.argtypes = [ctypes.POINTER(FaFwdParams), ctypes.POINTER(FaBlockSparseParams),
+                                                 ctypes.POINTER(FaSinkParams)]
+    lib.fa_fwd_block_sparse_validate.restype = ctypes.c_int
+    lib.fa_block_sparse_params_size.argtypes = []
+    lib.fa_block_sparse_params_size.restype = ctypes.c_uint32
+    if lib.fa_block_sparse_params_size() != ctypes.sizeof(FaBlockSparseParams):
+        raise RuntimeError("fa_block_sparse_params layout mismatch between include/fa_fwd.h and _lib")
     lib.fa_sink_grad.argtypes = [ctypes.POINTER(FaSinkGradParams), ctypes.c_void_p]
     lib.fa_sink_grad.restype = ctypes.c_int
     lib.fa_sink_grad_validate.argtypes = [ctypes.POINTER(FaSinkGradParams)]
@@ -457,6 +481,14 @@ def new_sink_params():
     p.struct_size = ctypes.sizeof(FaSinkParams)
     p.sink_dtype = FA_DTYPE_BF16
     p.sink_head_stride = 1
+    return p
+
+
+def new_block_sparse_params():
+    p = FaBlockSparseParams()
+    p.abi_version = FA_ABI_VERSION
+    p.struct_size = ctypes.sizeof(FaBlockSparseParams)
+    p.block_m = p.block_n = 128
     return p
 
 

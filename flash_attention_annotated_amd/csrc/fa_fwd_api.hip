@@ -9,6 +9,7 @@
 #include "fa_fwd_kernel_fp8.h"
 #include "fa_fwd_kernel_d256.h"
 #include "fa_fwd_kernel_qv.h"
+#include "fa_fwd_kernel_bs.h"
 #include "fa_launch.h"
 
 #include <algorithm>
@@ -749,6 +750,9 @@ const char *plan_text(const FwdPlan &pl, char (&name)[160]) {
 // is made when asked
 thread_local FwdPlan t_last_plan;
 thread_local bool t_last_plan_set = false;
+// ... or, when that call was fa_fwd_block_sparse, the head-dim tile of its bs_fwd_kernel (0 = it was not) and its softcap form
+thread_local int t_last_bs_tile = 0;
+thread_local bool t_last_bs_softcap = false;
 
 // compute units of the current device (cached per device ordinal)
 int device_cus() {
@@ -1266,6 +1270,11 @@ const char *fa_fwd_plan_name(const fa_fwd_params *p, int32_t num_cus) {
 
 const char *fa_fwd_last_plan_name(void) {
     thread_local char name[160];
+    if (t_last_bs_tile) {  // the block-sparse kernel has one shape: 4 waves x 32 rows = one 128-row block, never split
+        snprintf(name, sizeof(name), "bs_fwd_kernel D=%d waves=%d%s block_m=%d splits=1", t_last_bs_tile, fa::BS_NWAVES,
+                 t_last_bs_softcap ? " SOFTCAP" : "", fa::BS_BLOCK);
+        return name;
+    }
     return t_last_plan_set ? plan_text(t_last_plan, name) : nullptr;
 }
 
@@ -1303,6 +1312,7 @@ int fa_fwd_sink(const fa_fwd_params *p, const fa_sink_params *sink, void *stream
 static int fwd_run(const fa_fwd_params *p, const fa_sink_params *sink, void *stream_) {
     const int st = sink ? fa_fwd_sink_validate(p, sink) : fa_fwd_validate(p);
     t_last_plan_set = false;
+    t_last_bs_tile = 0;
     if (st != FA_OK) return st;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
 
@@ -1492,6 +1502,138 @@ static int fwd_run(const fa_fwd_params *p, const fa_sink_params *sink, void *str
                            sp.splits, mb, msq, p->h, dw, p->o_batch_stride, p->o_row_stride, p->o_head_stride, sink_kp);
     if (hipGetLastError() != hipSuccess) return FA_ERR_LAUNCH;
     return FA_OK;
+}
+
+// ---- block-sparse forward (include/fa_fwd.h, fa_fwd_kernel_bs.h) ---------------------------------------------------------
+uint32_t fa_block_sparse_params_size(void) { return (uint32_t)sizeof(fa_block_sparse_params); }
+
+// the params as the block-sparse launch reads them: never split (num_splits 0 / 1 both mean one part)
+static fa_fwd_params bs_dense_params(const fa_fwd_params *p) {
+    fa_fwd_params q = *p;
+    q.num_splits = 1;
+    return q;
+}
+
+// The refusals come first: what block sparsity cannot go with is refused as such, whatever else those params lack.
+int fa_fwd_block_sparse_validate(const fa_fwd_params *p, const fa_block_sparse_params *s, const fa_sink_params *sink) {
+    if (!p || !s) return FA_ERR_NULL_POINTER;
+    if (p->abi_version != FA_ABI_VERSION || p->struct_size != sizeof(fa_fwd_params)) return FA_ERR_BAD_ABI;
+    if (s->abi_version != FA_ABI_VERSION || s->struct_size != sizeof(fa_block_sparse_params)) return FA_ERR_BAD_ABI;
+    if (s->block_m != fa::BS_BLOCK || s->block_n != fa::BS_BLOCK) return FA_ERR_UNSUPPORTED;
+    // the reference refuses block sparsity with varlen too (flash_attn/cute/interface.py); the others have no list semantics here
+    if (p->cu_seqlens_q || p->cu_seqlens_k || p->seqused_q || p->seqused_k || p->block_table || p->kv_batch_idx || p->leftpad_k)
+        return FA_ERR_UNSUPPORTED;
+    if (p->dtype == FA_DTYPE_FP8_E4M3 || p->qv || p->p_dropout > 0.f || p->s_dmask || p->alibi_slopes || p->attention_chunk != 0 ||
+        p->num_splits > 1 || p->d_v > 256)
+        return FA_ERR_UNSUPPORTED;
+    if (!s->mask_block_cnt || !s->mask_block_idx) return FA_ERR_NULL_POINTER;
+    if ((s->full_block_cnt == nullptr) != (s->full_block_idx == nullptr)) return FA_ERR_NULL_POINTER;
+    const void *lists[] = {s->full_block_cnt, s->full_block_idx, s->mask_block_cnt, s->mask_block_idx};
+    for (const void *l : lists)
+        if (reinterpret_cast<uintptr_t>(l) % 4 != 0) return FA_ERR_BAD_STRIDE;
+    const int64_t *strides[] = {s->full_cnt_stride, s->full_idx_stride, s->mask_cnt_stride, s->mask_idx_stride};
+    for (const int64_t *st : strides)
+        for (int i = 0; i < 4; ++i)
+            if (st[i] < 0) return FA_ERR_BAD_STRIDE;
+    const fa_fwd_params dense = bs_dense_params(p);
+    return sink ? fa_fwd_sink_validate(&dense, sink) : fa_fwd_validate(&dense);
+}
+
+}  // extern "C"
+
+namespace {
+template <typename T>
+int launch_bs(int tile, bool softcap, const fa::BsParams &bp, hipStream_t stream) {
+    const int64_t grid = bp.p.grid;
+    constexpr int NT = fa::BS_NWAVES * 64;
+#define FA_BS_LAUNCH(D)                                                                                                        \
+    return softcap ? fa::launch_kernel<fa::bs_fwd_kernel<T, D, true>>(fa::smem_bytes<D, fa::BS_NWAVES>(), grid, NT, stream, bp) \
+                   : fa::launch_kernel<fa::bs_fwd_kernel<T, D, false>>(fa::smem_bytes<D, fa::BS_NWAVES>(), grid, NT, stream, bp)
+    if (tile == 64) { FA_BS_LAUNCH(64); }
+    if (tile == 128) { FA_BS_LAUNCH(128); }
+    FA_BS_LAUNCH(256);
+#undef FA_BS_LAUNCH
+}
+}  // namespace
+
+extern "C" {
+
+int fa_fwd_block_sparse(const fa_fwd_params *p_, const fa_block_sparse_params *s, const fa_sink_params *sink, void *stream_) {
+    const int st = fa_fwd_block_sparse_validate(p_, s, sink);
+    t_last_plan_set = false;
+    t_last_bs_tile = 0;
+    if (st != FA_OK) return st;
+    const fa_fwd_params dense = bs_dense_params(p_), *p = &dense;
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+
+    fa::BsParams bp{};
+    fa::KParams &kp = bp.p;
+    kp.q = p->q; kp.k = p->k; kp.v = p->v; kp.o = p->o; kp.lse = p->softmax_lse;
+    kp.q_batch_stride = p->q_batch_stride; kp.q_row_stride = p->q_row_stride; kp.q_head_stride = p->q_head_stride;
+    kp.k_batch_stride = p->k_batch_stride; kp.k_row_stride = p->k_row_stride; kp.k_head_stride = p->k_head_stride;
+    kp.v_batch_stride = p->v_batch_stride; kp.v_row_stride = p->v_row_stride; kp.v_head_stride = p->v_head_stride;
+    kp.o_batch_stride = p->o_batch_stride; kp.o_row_stride = p->o_row_stride; kp.o_head_stride = p->o_head_stride;
+    kp.b = p->b; kp.seqlen_q = p->seqlen_q; kp.seqlen_k = p->seqlen_k; kp.h = p->h; kp.h_k = p->h_k; kp.d = p->d;
+    kp.dv = dv_of(p);
+    kp.h_ratio = p->h / p->h_k;
+    kp.num_splits = 1;
+    kp.rp_dropout = 1.f;
+    kp.drop_thr = 255;
+    kp.num_cus = device_cus();
+    // one work item per (batch, head, 128-row block): fwd_kernel's scheduling (tile_of_wg) with block_m = 128
+    const int64_t nm = ((int64_t)p->seqlen_q + fa::BS_BLOCK - 1) / fa::BS_BLOCK;
+    const int64_t tiles = nm * p->h * p->b;
+    if (tiles == 0) return FA_OK;  // no query row
+    const int64_t bk_units = (int64_t)p->b * p->h_k, per_kvh = (int64_t)kp.h_ratio * nm;
+    const int64_t whole_units = bk_units >= 16 ? bk_units / 8 * 8 : 0;
+    const int64_t whole_slots = whole_units / 8 * per_kvh;
+    const int64_t rem_units = (tiles - whole_slots * 8 + kp.h_ratio - 1) / kp.h_ratio;
+    const int64_t grid = 8 * (whole_slots + (rem_units + 7) / 8 * kp.h_ratio);
+    if (tiles > 0x7fffffff || grid > 0x7fffffff) return FA_ERR_BAD_SHAPE;
+    kp.num_m_blocks = (int32_t)nm;
+    kp.num_tiles = (int32_t)tiles;
+    kp.unit_tiles = (int32_t)per_kvh;
+    kp.whole_slots = (int32_t)whole_slots;
+    kp.grid = (int32_t)grid;
+
+    // the call's own mask, bottom-right aligned: fa_fwd's window normalisation
+    int wl = p->window_size_left, wr = p->window_size_right;
+    if (p->is_causal) wr = 0;
+    if (!(p->flags & FA_FLAG_FA3_WINDOW)) {
+        if (wl >= p->seqlen_k) wl = -1;
+        if (wr >= p->seqlen_k) wr = -1;
+        if (p->is_causal) wr = 0;
+        if (wl >= 0 && wr < 0) wr = p->seqlen_k;
+    }
+    kp.window_left = wl;
+    kp.window_right = wr;
+    if (sink) {
+        kp.sink = sink->learnable_sink;
+        kp.sink_hs = sink->sink_head_stride; kp.sink_rs = sink->sink_row_stride;
+        kp.sink_fp32 = sink->sink_dtype == FA_DTYPE_FP32;
+    }
+    const bool softcap = p->softcap > 0.f;
+    constexpr float kLog2e = 1.4426950408889634f;
+    if (softcap) {
+        kp.softcap_pre = p->softmax_scale / p->softcap;
+        kp.scale = p->softcap;
+        kp.scale_log2 = p->softcap * kLog2e;
+    } else {
+        kp.scale = p->softmax_scale;
+        kp.scale_log2 = p->softmax_scale * kLog2e;
+    }
+
+    auto list = [](const int32_t *cnt, const int32_t *idx, const int64_t *cs, const int64_t *is) {
+        return fa::BsList{cnt, idx, cs[0], cs[1], cs[2], is[0], is[1], is[2], is[3]};
+    };
+    bp.full = list(s->full_block_cnt, s->full_block_idx, s->full_cnt_stride, s->full_idx_stride);
+    bp.mask = list(s->mask_block_cnt, s->mask_block_idx, s->mask_cnt_stride, s->mask_idx_stride);
+    bp.nk = (int32_t)(((int64_t)p->seqlen_k + fa::BS_BLOCK - 1) / fa::BS_BLOCK);
+
+    const int tile = head_dim_tile(std::max(p->d, dv_of(p)));
+    t_last_bs_tile = tile;
+    t_last_bs_softcap = softcap;
+    return p->dtype == FA_DTYPE_BF16 ? launch_bs<__bf16>(tile, softcap, bp, stream) : launch_bs<_Float16>(tile, softcap, bp, stream);
 }
 
 }  // extern "C"

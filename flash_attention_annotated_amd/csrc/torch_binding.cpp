@@ -1386,6 +1386,102 @@ std::tuple<Tensor, Tensor> cute_fwd(const Tensor &q, const Tensor &k, const Tens
     return {std::get<0>(r), std::get<1>(r)};
 }
 
+// ---- block-sparse forward of the cute surface (include/fa_fwd.h fa_fwd_block_sparse): flash_attn_func with
+// full_block_cnt / full_block_idx / mask_block_cnt / mask_block_idx.  The checks of normalize_block_sparse_tensors
+// (flash_attn/cute/block_sparsity.py:33-115) on shapes and dtypes; the lists are handed over through their strides -- a size-1
+// batch / head dimension as stride 0 -- and never read, copied or expanded here.  Allocates out and lse, nothing else (q / k / v
+// views whose rows are not 16-byte aligned are copied, as on every surface).
+void check_block_list(const OptTensor &cnt, const OptTensor &idx, const char *name, const Tensor &q, int64_t nm, int64_t nk) {
+    TORCH_CHECK(cnt.has_value() == idx.has_value(), name, "_block_cnt and ", name, "_block_idx must be specified together");
+    if (!cnt.has_value()) return;
+    TORCH_CHECK(cnt->scalar_type() == at::kInt && idx->scalar_type() == at::kInt, name, "_block_cnt and ", name, "_block_idx must be int32");
+    TORCH_CHECK(cnt->is_cuda() && idx->is_cuda() && cnt->device() == q.device() && idx->device() == q.device(),
+                name, "_block_cnt and ", name, "_block_idx must be on the device of q");
+    const int64_t b = q.size(0), h = q.size(2);
+    TORCH_CHECK(cnt->dim() == 3 && (cnt->size(0) == b || cnt->size(0) == 1) && (cnt->size(1) == h || cnt->size(1) == 1) && cnt->size(2) == nm,
+                name, "_block_cnt must have shape (", b, " or 1, ", h, " or 1, ", nm, "), got ", cnt->sizes());
+    TORCH_CHECK(idx->dim() == 4 && (idx->size(0) == b || idx->size(0) == 1) && (idx->size(1) == h || idx->size(1) == 1) && idx->size(2) == nm &&
+                    idx->size(3) == nk,
+                name, "_block_idx must have shape (", b, " or 1, ", h, " or 1, ", nm, ", ", nk, "), got ", idx->sizes());
+}
+void set_list_strides(const Tensor &t, int64_t (&st)[4]) {
+    for (int64_t i = 0; i < 4; ++i) st[i] = i < t.dim() ? t.stride(i) : 0;
+    if (t.size(0) == 1) st[0] = 0;  // broadcast over the batch / the heads
+    if (t.size(1) == 1) st[1] = 0;
+}
+
+std::tuple<Tensor, Tensor> cute_fwd_block_sparse(const Tensor &q_, const Tensor &k_, const Tensor &v_, double softmax_scale, bool is_causal,
+                                                 int64_t window_size_left, int64_t window_size_right, const OptTensor &learnable_sink,
+                                                 double softcap, int64_t num_splits, const OptTensor &full_block_cnt,
+                                                 const OptTensor &full_block_idx, const OptTensor &mask_block_cnt,
+                                                 const OptTensor &mask_block_idx) {
+    CHECK_DEVICE(q_, "q"); CHECK_DEVICE(k_, "k"); CHECK_DEVICE(v_, "v");
+    TORCH_CHECK(q_.dim() == 4 && k_.dim() == 4 && v_.dim() == 4, "block sparsity needs dense q (b, sq, h, d) and k / v (b, sk, h_k, d)");
+    TORCH_CHECK(q_.scalar_type() == at::kHalf || q_.scalar_type() == at::kBFloat16, "inputs must be float16 or bfloat16");
+    TORCH_CHECK(k_.scalar_type() == q_.scalar_type() && v_.scalar_type() == q_.scalar_type(), "inputs must have the same dtype");
+    CHECK_LAST_CONTIGUOUS(q_, "q must have contiguous last dimension");
+    CHECK_LAST_CONTIGUOUS(k_, "k must have contiguous last dimension");
+    CHECK_LAST_CONTIGUOUS(v_, "v must have contiguous last dimension");
+    const int64_t b = q_.size(0), sq = q_.size(1), h = q_.size(2), d = q_.size(3), sk = k_.size(1), h_k = k_.size(2), dv = v_.size(3);
+    TORCH_CHECK(k_.size(0) == b && v_.size(0) == b && v_.size(1) == sk && v_.size(2) == h_k && k_.size(3) == d, "q, k, v shapes do not match");
+    TORCH_CHECK(mask_block_cnt.has_value() && mask_block_idx.has_value(), "mask_block_cnt and mask_block_idx are required");
+    check_sink(learnable_sink, q_);
+    const int64_t nm = (sq + 127) / 128, nk = (sk + 127) / 128;
+    check_block_list(mask_block_cnt, mask_block_idx, "mask", q_, nm, nk);
+    check_block_list(full_block_cnt, full_block_idx, "full", q_, nm, nk);
+    c10::hip::HIPGuardMasqueradingAsCUDA device_guard(q_.device());
+    const Tensor q = aligned_or_copy(q_), k = aligned_or_copy(k_), v = aligned_or_copy(v_);
+    Tensor out = at::empty({b, sq, h, dv}, q.options());
+    Tensor lse = at::empty({b, h, sq}, q.options().dtype(at::kFloat));
+
+    fa_fwd_params p{};
+    p.abi_version = FA_ABI_VERSION;
+    p.struct_size = sizeof(fa_fwd_params);
+    p.q = q.data_ptr(); p.k = k.data_ptr(); p.v = v.data_ptr(); p.o = out.data_ptr();
+    p.softmax_lse = static_cast<float *>(lse.data_ptr());
+    p.q_batch_stride = q.stride(0); p.q_row_stride = q.stride(1); p.q_head_stride = q.stride(2);
+    p.k_batch_stride = k.stride(0); p.k_row_stride = k.stride(1); p.k_head_stride = k.stride(2);
+    p.v_batch_stride = v.stride(0); p.v_row_stride = v.stride(1); p.v_head_stride = v.stride(2);
+    p.o_batch_stride = out.stride(0); p.o_row_stride = out.stride(1); p.o_head_stride = out.stride(2);
+    p.b = (int32_t)b; p.seqlen_q = (int32_t)sq; p.seqlen_k = (int32_t)sk; p.h = (int32_t)h; p.h_k = (int32_t)h_k; p.d = (int32_t)d;
+    if (dv != d) p.d_v = (int32_t)dv;
+    p.dtype = dtype_code(q);
+    p.softmax_scale = (float)softmax_scale;
+    p.softcap = (float)softcap;
+    p.is_causal = is_causal ? 1 : 0;
+    p.window_size_left = (int32_t)window_size_left; p.window_size_right = (int32_t)window_size_right;
+    p.flags = FA_FLAG_FA3_WINDOW;  // a missing window side is unbounded, as on the rest of this surface
+    p.num_splits = (int32_t)num_splits;
+
+    fa_block_sparse_params s{};
+    s.abi_version = FA_ABI_VERSION;
+    s.struct_size = sizeof(fa_block_sparse_params);
+    s.block_m = s.block_n = 128;
+    s.mask_block_cnt = static_cast<const int32_t *>(mask_block_cnt->data_ptr());
+    s.mask_block_idx = static_cast<const int32_t *>(mask_block_idx->data_ptr());
+    set_list_strides(*mask_block_cnt, s.mask_cnt_stride);
+    set_list_strides(*mask_block_idx, s.mask_idx_stride);
+    if (full_block_cnt.has_value()) {
+        s.full_block_cnt = static_cast<const int32_t *>(full_block_cnt->data_ptr());
+        s.full_block_idx = static_cast<const int32_t *>(full_block_idx->data_ptr());
+        set_list_strides(*full_block_cnt, s.full_cnt_stride);
+        set_list_strides(*full_block_idx, s.full_idx_stride);
+    }
+    fa_sink_params sink{};
+    if (learnable_sink.has_value()) {
+        sink.abi_version = FA_ABI_VERSION;
+        sink.struct_size = sizeof(fa_sink_params);
+        sink.learnable_sink = learnable_sink->data_ptr();
+        sink.sink_dtype = learnable_sink->scalar_type() == at::kFloat ? FA_DTYPE_FP32 : FA_DTYPE_BF16;
+        sink.sink_head_stride = 1;
+    }
+    const int st = fa_fwd_block_sparse(&p, &s, learnable_sink.has_value() ? &sink : nullptr, current_stream(q));
+    TORCH_CHECK(st != FA_ERR_UNSUPPORTED, "fa_fwd_block_sparse: block sparsity does not go with this call (num_splits > 1, or a head dim "
+                "of V above 256): ", fa_strerror(st));
+    TORCH_CHECK(st == 0, "fa_fwd_block_sparse failed (", st, "): ", fa_strerror(st));
+    return {out, lse};
+}
+
 // dsink (num_heads,) fp32 from the LSE of a forward with a sink and the softmax_d of its fa_bwd (include/fa_bwd.h)
 Tensor sink_grad(const Tensor &softmax_lse, const Tensor &softmax_d, const Tensor &learnable_sink, const OptTensor &cu_seqlens_q,
                  const OptTensor &seqused_q, int64_t batch, int64_t seqlen_q) {
@@ -1510,6 +1606,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("fa3_bwd", &fa3_bwd, "FA3 backward pass (flash_attn_3::bwd)");
     m.def("fa3_fwd_combine", &fa3_fwd_combine, "FA3 merge of split-KV partials (flash_attn_3::fwd_combine)");
     m.def("cute_fwd", &cute_fwd, "cute surface forward (flash_attn.cute.interface, with learnable_sink)");
+    m.def("cute_fwd_block_sparse", &cute_fwd_block_sparse, "cute surface forward restricted to listed 128 x 128 blocks");
     m.def("cute_bwd", &cute_bwd, "cute surface backward: (dq, dk, dv, dsink)");
     m.def("sink_grad", &sink_grad, "gradient of a learnable sink from softmax_lse and softmax_d");
 }

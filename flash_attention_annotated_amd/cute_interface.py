@@ -5,6 +5,11 @@ carries `learnable_sink`: one logit per query head that joins the softmax denomi
 differentiable; with a sink that requires grad the backward also returns its gradient (the reference's sink is
 forward-only).
 
+`flash_attn_func` also takes the reference's block-sparse tensors (`full_block_cnt / full_block_idx / mask_block_cnt /
+mask_block_idx`, 128 x 128 blocks; include/fa_fwd.h fa_fwd_block_sparse has the definition, DESIGN.md §4.13 the kernel) and
+`block_sparse_from_mask` makes them from a block mask.  That route is forward-only; `mask_mod`, a CuTe-DSL callable, is not
+supported.
+
 Routing is the FA3 surface's (csrc/torch_binding.cpp cute_fwd -> fa3_fwd_core): dense and varlen calls, decode steps over
 a paged cache with their GQA swap and split-KV, ragged queries over a cache.  The cute signatures carry no max_seqlen:
 the grid is made from bounds the shapes give (total_q / total_k), nothing is read from the device.
@@ -21,11 +26,74 @@ def maybe_contiguous(x):
 
 
 def _check_block_sparse(mask_mod=None, **tensors):
+    """True when the call is block-sparse.  mask_mod (a CuTe-DSL callable) and full_block_* without mask_block_* are not
+    supported; cnt and idx of a pair come together."""
     given = [n for n, t in dict(mask_mod=mask_mod, **tensors).items() if t is not None]
-    if given:
+    if not given:
+        return False
+    if mask_mod is not None or (tensors["mask_block_cnt"] is None and tensors["mask_block_idx"] is None):
         raise NotImplementedError(
-            f"This flash attention build does not support {', '.join(given)} (mask_mod and the block-sparse tensors "
-            f"full_block_cnt / full_block_idx / mask_block_cnt / mask_block_idx)")
+            f"This flash attention build does not support {', '.join(given)} (mask_mod, and the block-sparse tensors "
+            f"full_block_cnt / full_block_idx without mask_block_cnt / mask_block_idx)")
+    for pair in ("mask", "full"):
+        if (tensors[f"{pair}_block_cnt"] is None) != (tensors[f"{pair}_block_idx"] is None):
+            raise ValueError(f"{pair}_block_cnt and {pair}_block_idx must be specified together")
+    return True
+
+
+def block_sparse_from_mask(block_mask, full=None):
+    """Block lists from a block mask -- the role of the reference's compute_block_sparsity for callers who have the mask.
+    block_mask: bool (b | 1, h | 1, nm, nk), True = query block m visits key block n (128 x 128 blocks).  full: optional
+    bool tensor of the same shape, the visited blocks that go to the full list (those the caller promises need no
+    element-wise mask); the others go to the mask list.  Returns (full_block_cnt, full_block_idx, mask_block_cnt,
+    mask_block_idx), int32, cnt (b | 1, h | 1, nm), idx (b | 1, h | 1, nm, nk): indices ascending, tails zero.  Pure torch,
+    on the device of block_mask."""
+    assert block_mask.dim() == 4 and block_mask.dtype == torch.bool, "block_mask must be a bool tensor (b, h, nm, nk)"
+    if full is None:
+        full = torch.zeros_like(block_mask)
+    assert full.shape == block_mask.shape and full.dtype == torch.bool, "full must be a bool tensor of block_mask's shape"
+    nk = block_mask.shape[-1]
+    col = torch.arange(nk, device=block_mask.device)
+
+    def lists(m):
+        cnt = m.sum(-1, dtype=torch.int32)
+        # a stable sort on "not visited" brings the visited indices to the front in ascending order
+        idx = torch.sort((~m).to(torch.int8), dim=-1, stable=True).indices.to(torch.int32)
+        return cnt, torch.where(col < cnt[..., None], idx, torch.zeros_like(idx))
+
+    full_cnt, full_idx = lists(block_mask & full)
+    mask_cnt, mask_idx = lists(block_mask & ~full)
+    return full_cnt, full_idx, mask_cnt, mask_idx
+
+
+def _flash_attn_fwd_block_sparse(q, k, v, softmax_scale, causal, window_size, learnable_sink, softcap, num_splits,
+                                 full_block_cnt, full_block_idx, mask_block_cnt, mask_block_idx):
+    """The checks of normalize_block_sparse_tensors (flash_attn/cute/block_sparsity.py:33-115) and the launch.  Nothing of
+    the lists is read on the host: the call can be captured in a HIP graph."""
+    q, k, v = [maybe_contiguous(t) for t in (q, k, v)]
+    assert q.dim() == 4, "block sparsity needs q of shape (batch_size, seqlen_q, num_head, head_dim)"
+    _checks(q, k, v, None, None, None, None, None, learnable_sink)
+    if num_splits not in (0, 1):
+        raise NotImplementedError("block sparsity does not support num_splits > 1 (split-KV over block lists)")
+    if v.shape[-1] > 256:
+        raise NotImplementedError("block sparsity does not support a head dim of V above 256")
+    b, sq, h = q.shape[:3]
+    nm, nk = (sq + 127) // 128, (k.shape[1] + 127) // 128
+    for name, cnt, idx in (("mask", mask_block_cnt, mask_block_idx), ("full", full_block_cnt, full_block_idx)):
+        if cnt is None:
+            continue
+        for t, tname, tail in ((cnt, f"{name}_block_cnt", (nm,)), (idx, f"{name}_block_idx", (nm, nk))):
+            if t.dtype != torch.int32:
+                raise ValueError(f"{tname} must be int32")
+            if t.device != q.device:
+                raise ValueError(f"{tname} must be on the device of q")
+            if t.dim() != 2 + len(tail) or t.shape[0] not in (1, b) or t.shape[1] not in (1, h) or tuple(t.shape[2:]) != tail:
+                raise ValueError(f"{tname} must have shape ({b} or 1, {h} or 1, {', '.join(map(str, tail))}), "
+                                 f"got {tuple(t.shape)}")
+    left, right = _window(window_size)
+    sink = learnable_sink.detach().contiguous() if learnable_sink is not None else None
+    return _lib.binding().cute_fwd_block_sparse(q, k, v, softmax_scale, causal, left, right, sink, softcap or 0.0, num_splits,
+                                                full_block_cnt, full_block_idx, mask_block_cnt, mask_block_idx)
 
 
 def _window(window_size):
@@ -108,12 +176,16 @@ class FlashAttnFunc(torch.autograd.Function):
     def forward(ctx, q, k, v, softmax_scale=None, causal=False, window_size=(None, None), learnable_sink=None, softcap=0.0,
                 num_splits=1, pack_gqa=None, mask_mod=None, full_block_cnt=None, full_block_idx=None, mask_block_cnt=None,
                 mask_block_idx=None):
-        _check_block_sparse(mask_mod, full_block_cnt=full_block_cnt, full_block_idx=full_block_idx,
-                            mask_block_cnt=mask_block_cnt, mask_block_idx=mask_block_idx)
+        ctx.block_sparse = _check_block_sparse(mask_mod, full_block_cnt=full_block_cnt, full_block_idx=full_block_idx,
+                                               mask_block_cnt=mask_block_cnt, mask_block_idx=mask_block_idx)
         if softmax_scale is None:
             softmax_scale = 1.0 / math.sqrt(q.shape[-1])
-        out, lse = _flash_attn_fwd(q, k, v, softmax_scale=softmax_scale, causal=causal, window_size=window_size,
-                                   learnable_sink=learnable_sink, softcap=softcap, num_splits=num_splits)
+        if ctx.block_sparse:
+            out, lse = _flash_attn_fwd_block_sparse(q, k, v, softmax_scale, causal, window_size, learnable_sink, softcap, num_splits,
+                                                    full_block_cnt, full_block_idx, mask_block_cnt, mask_block_idx)
+        else:
+            out, lse = _flash_attn_fwd(q, k, v, softmax_scale=softmax_scale, causal=causal, window_size=window_size,
+                                       learnable_sink=learnable_sink, softcap=softcap, num_splits=num_splits)
         ctx.save_for_backward(q, k, v, out, lse, learnable_sink)
         ctx.softmax_scale, ctx.causal, ctx.window_size, ctx.softcap = softmax_scale, causal, window_size, softcap
         ctx.mark_non_differentiable(lse)
@@ -121,6 +193,8 @@ class FlashAttnFunc(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dout, *args):
+        if ctx.block_sparse:  # (the reference returns the DENSE gradient here, flash_attn/cute/interface.py:1055-1069)
+            raise NotImplementedError("block-sparse backward")
         q, k, v, out, lse, sink = ctx.saved_tensors
         dq, dk, dv, dsink = _flash_attn_bwd(dout, q, k, v, out, lse, None, None, ctx.softmax_scale, ctx.causal,
                                             ctx.window_size, ctx.softcap, sink)
@@ -165,8 +239,17 @@ def flash_attn_func(q, k, v, softmax_scale=None, causal=False, window_size=(None
                     num_splits=1, pack_gqa=None, mask_mod=None, full_block_cnt=None, full_block_idx=None, mask_block_cnt=None,
                     mask_block_idx=None):
     """q (b, sq, h, d), k / v (b, sk, h_k, d[_v]) -> (out, lse (b, h, sq)).  learnable_sink: (h,) bf16 or fp32.  num_splits:
-    1 = no split-KV, N > 1 = N parts, 0 = the library's heuristic.  pack_gqa is accepted and ignored; mask_mod and the
-    block-sparse tensors must be None."""
+    1 = no split-KV, N > 1 = N parts, 0 = the library's heuristic.  pack_gqa is accepted and ignored; mask_mod must be None.
+
+    Block sparsity: mask_block_cnt (b | 1, h | 1, nm) and mask_block_idx (b | 1, h | 1, nm, nk), int32, on q's device, with
+    nm = ceil(sq / 128), nk = ceil(sk / 128), and optionally full_block_cnt / full_block_idx of the same shapes
+    (block_sparse_from_mask makes all four from a block mask).  Query block m attends to the first cnt[.., m] key blocks of
+    idx[.., m, :] of both lists, and inside them to what causal / window_size allow; distinct in-range indices are the
+    caller's duty.  Rows without a visible key give out = 0 and lse = +inf (the sink with learnable_sink).  Not with
+    num_splits > 1 or a V head dim above 256; forward only (the backward raises NotImplementedError).
+    Measured on one MI355X at b4 h16 s8192 d128 bf16 (profiles/block_sparse.jsonl): time is proportional to the listed blocks,
+    all of them listed cost 1.46 x the plain dense call, so block sparsity pays below about 0.68 of the blocks (0.40 x the
+    dense time at a quarter of them)."""
     return FlashAttnFunc.apply(q, k, v, softmax_scale, causal, window_size, learnable_sink, softcap, num_splits, pack_gqa,
                                mask_mod, full_block_cnt, full_block_idx, mask_block_cnt, mask_block_idx)
 

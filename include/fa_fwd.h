@@ -283,6 +283,56 @@ int fa_fwd_sink(const fa_fwd_params *params, const fa_sink_params *sink, void *s
 int fa_fwd_sink_validate(const fa_fwd_params *params, const fa_sink_params *sink);
 uint32_t fa_sink_params_size(void);
 
+/*
+ * Block-sparse forward -- `full_block_cnt / full_block_idx / mask_block_cnt / mask_block_idx` of
+ * flash_attn.cute.interface.flash_attn_func (flash_attn/cute/interface.py:262-273, 377-385, 1004-1053; the list format
+ * flash_attn/cute/block_sparsity.py:33-115; the kernel side flash_attn/cute/block_sparse_utils.py:265-419): the caller says
+ * which key blocks each query block attends to.
+ * Blocks are 128 query rows x 128 keys (the reference's m_block_size / n_block_size under block sparsity), whatever tile the
+ * kernel uses inside.  nm = ceil(seqlen_q / 128), nk = ceil(seqlen_k / 128).
+ *   *_block_cnt  int32, logical shape (b, h, nm)       h = QUERY heads
+ *   *_block_idx  int32, logical shape (b, h, nm, nk)
+ * read through the element strides below; a batch or head dimension of size 1 is given stride 0 (no expanded copy).
+ * Query block m of (batch, head) visits the first mask_block_cnt[.., m] entries of mask_block_idx[.., m, :] and the first
+ * full_block_cnt[.., m] entries of full_block_idx[.., m, :].  Entries past the count are never read for their meaning.  The
+ * visited indices of one query block must be distinct and inside [0, nk): a duplicate, an index in both lists or one outside
+ * the range is the caller's error with an undefined result (the kernel does not read K / V outside seqlen_k for any list
+ * content; counts are clamped to [0, nk]).  The host never reads the lists.  The order of a list does not matter beyond rounding.
+ * The output is dense attention restricted to the visited blocks: the pair (i, j) counts iff key block j / 128 is visited
+ * for query block i / 128 AND the call's own mask allows it -- the seqlen_k bound, is_causal and window_size_left / right,
+ * bottom-right aligned as everywhere here.  The call's mask applies inside "full" blocks as well (the reference's does,
+ * flash_attn/cute/flash_fwd.py:1985-1994), so the two lists differ as a hint only: a full block is one the caller promises
+ * needs no element-wise mask.  This kernel decides per 64-key tile from the call's mask alone and ignores the hint; a causal
+ * diagonal block in the full list is therefore handled correctly.
+ * A row without a visible key -- a query block whose two counts are 0 included -- gives O = 0 and LSE = +inf, or, with a
+ * learnable sink z, O = 0 and LSE = z (fa_sink_params above).
+ * Accepted: fp16 / bf16, d <= 256, d_v != d up to 256, MHA / GQA / MQA, is_causal, both window sides, softcap, a learnable
+ * sink, arbitrary q / k / v / o strides.  num_splits 0 and 1 both mean no split.  FA_ERR_UNSUPPORTED: cu_seqlens_*, seqused_*,
+ * block_table (the reference refuses block sparsity with varlen too), kv_batch_idx, leftpad_k, fp8, qv, dropout, s_dmask,
+ * ALiBi, attention_chunk, num_splits > 1, d_v > 256, block_m / block_n other than 128.  These are checked before anything the
+ * params may lack.  fa_fwd_params is untouched (its size is pinned): the lists travel in a struct of their own.
+ * fa_fwd_plan_name and fa_fwd_workspace_size keep their meaning for plain params; fa_fwd_last_plan_name() names such a call
+ * "bs_fwd_kernel D=<head-dim tile> waves=4[ SOFTCAP] block_m=128 splits=1".  No workspace.
+ */
+typedef struct fa_block_sparse_params {
+    uint32_t abi_version; /* FA_ABI_VERSION */
+    uint32_t struct_size; /* sizeof(fa_block_sparse_params) */
+    const int32_t *full_block_cnt; /* device pointers; full_* NULL together = no full list */
+    const int32_t *full_block_idx;
+    const int32_t *mask_block_cnt; /* required */
+    const int32_t *mask_block_idx;
+    /* element strides, >= 0: cnt (batch, head, m, unused = 0), idx (batch, head, m, n) */
+    int64_t full_cnt_stride[4], full_idx_stride[4];
+    int64_t mask_cnt_stride[4], mask_idx_stride[4];
+    int32_t block_m, block_n; /* 128, 128 */
+} fa_block_sparse_params;
+
+/* fa_fwd restricted to the listed blocks; `sink` may be NULL. */
+int fa_fwd_block_sparse(const fa_fwd_params *params, const fa_block_sparse_params *sparse, const fa_sink_params *sink, void *stream);
+/* Validation only; no device access. */
+int fa_fwd_block_sparse_validate(const fa_fwd_params *params, const fa_block_sparse_params *sparse, const fa_sink_params *sink);
+uint32_t fa_block_sparse_params_size(void);
+
 /* Human-readable text for a status code (static storage). */
 const char *fa_strerror(int status);
 
