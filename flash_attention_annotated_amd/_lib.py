@@ -55,6 +55,8 @@ EXPORTED_SYMBOLS = (
     "fa_bwd",
     "fa_bwd_validate",
     "fa_bwd_params_size",
+    "fa_bwd_plan_name",
+    "fa_bwd_last_plan_name",
     "fa_sink_grad",
     "fa_sink_grad_validate",
     "fa_sink_grad_params_size",
@@ -430,6 +432,10 @@ def load():
     lib.fa_bwd_validate.restype = ctypes.c_int
     lib.fa_bwd_params_size.argtypes = []
     lib.fa_bwd_params_size.restype = ctypes.c_uint32
+    lib.fa_bwd_plan_name.argtypes = [ctypes.POINTER(FaBwdParams)]
+    lib.fa_bwd_plan_name.restype = ctypes.c_char_p
+    lib.fa_bwd_last_plan_name.argtypes = []
+    lib.fa_bwd_last_plan_name.restype = ctypes.c_char_p
     if lib.fa_bwd_params_size() != ctypes.sizeof(FaBwdParams):
         raise RuntimeError("fa_bwd_params layout mismatch between include/fa_bwd.h and _lib.FaBwdParams")
     if lib.fa_fwd_params_size() != ctypes.sizeof(FaFwdParams):

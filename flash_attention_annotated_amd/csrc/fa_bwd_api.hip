@@ -9,6 +9,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstdio>
 
 namespace fa {
 
@@ -68,109 +69,174 @@ int64_t unit_grid(int64_t tiles, int blocks, int32_t &whole_slots) {
     return 8 * (ws + (tiles - ws * 8 + 7) / 8);
 }
 
+// ---- backward routing ---------------------------------------------------------------------------------------------------
+// plan_bwd() is the one place that decides which instantiation of each of the three kernels a problem runs.  Host code without
+// HIP calls: fa_bwd launches from the plan, fa_bwd_plan_name / fa_bwd_last_plan_name (the test hooks, tests/test_bwd_plan.py)
+// print the same plan.
+//
+// 32-wide blocks per wave (NB; every LDS fragment feeds NB MFMAs): two wherever accumulators + resident operands fit
+// the 512-register budget of a lone wave.  dQ: 2 for D <= 128; dK/dV (two accumulator sets + K and V): 2 for D = 64
+// (at D = 128 two blocks would fill all 256 AGPRs with accumulators; hipcc then rotates the whole AGPR file
+//  through v_accvgpr_mov to find temporaries -- measured 3x slower and not worth fighting).
+//  At D = 64 the plain problem -- no softcap / dropout / ALiBi -- takes the one-block form as well: that is the shape of the
+//  generated tile loop, tools/gen_bwd_loop.py.
+// DEFF (plain problems only): head dims <= 96 on the 128-wide tiles and <= 160 / <= 192 on the 256-wide ones run the
+// instantiations that skip the zero padding.  Head-dim tile 256: dV and dK by a launch each (PART 1 / 2, fa_bwd_kernel.h) -- one
+// accumulator set per sweep.
+struct BwdPlan {
+    int32_t dtype;          // FA_DTYPE_FP16 / FA_DTYPE_BF16
+    int tile;               // head-dim tile D: 64 / 128 / 256
+    bool softcap, dropout;
+    int lpr;                // bwd_dot_kernel: lanes per (row, head)
+    int nbk, deffk;         // bwd_dkdv_kernel
+    bool two_parts;         //   PART 1 (dV) then PART 2 (dK) instead of one sweep
+    int nbq, deffq;         // bwd_dq_kernel
+    bool run_dot, run_dkdv, run_dq;  // a launch without work items is left out
+};
+
+BwdPlan plan_bwd(const fa_bwd_params *p) {
+    BwdPlan pl{};
+    const int d_v = p->d_v > 0 ? p->d_v : p->d, w = std::max(p->d, d_v);
+    pl.dtype = p->dtype;
+    pl.tile = head_dim_tile_b(w);
+    pl.softcap = p->softcap > 0.f;
+    pl.dropout = p->p_dropout > 0.f;  // (never together with softcap: fa_bwd_validate)
+    const bool plain = !pl.softcap && !pl.dropout;
+    pl.lpr = std::min(pl.tile / 8, 32);
+    pl.nbk = pl.tile == 64 && !(plain && !p->alibi_slopes) ? 2 : 1;
+    pl.nbq = pl.tile <= 128 ? 2 : 1;
+    int deff = pl.tile;
+    if (plain && pl.tile == 128 && p->d <= 96) deff = 96;
+    if (plain && pl.tile == 256) deff = w <= 160 ? 160 : w <= 192 ? 192 : 256;
+    pl.deffk = pl.deffq = deff;
+    pl.two_parts = pl.tile == 256;
+    const int64_t rows_q = p->cu_seqlens_q ? (int64_t)p->total_q : (int64_t)p->b * p->seqlen_q;
+    const bool no_q = (p->seqlen_q == 0) || (p->cu_seqlens_q && p->total_q == 0);
+    const bool no_k = (p->seqlen_k == 0) || (p->cu_seqlens_q && p->total_k == 0);
+    const bool any = !(no_q && no_k);   // (nothing to do: fa_bwd returns before the first launch)
+    pl.run_dot = any && rows_q > 0;
+    pl.run_dkdv = any && p->seqlen_k > 0;  // seqlen_q == 0: dK = dV = 0 is written by the dK/dV pass
+    pl.run_dq = any && p->seqlen_q > 0;    // seqlen_k == 0: dQ = 0 likewise
+    return pl;
+}
+
+// the text of a plan: one segment per launched kernel, in launch order
+const char *plan_text(const BwdPlan &pl, char (&name)[320]) {
+    int n = 0;
+    name[0] = 0;
+    auto seg = [&](const char *kernel, int nb, int deff, int part) {
+        n += snprintf(name + n, sizeof(name) - n, "%s%s D=%d NB=%d DEFF=%d", n ? " | " : "", kernel, pl.tile, nb, deff);
+        if (part) n += snprintf(name + n, sizeof(name) - n, " PART=%d", part);
+        n += snprintf(name + n, sizeof(name) - n, "%s%s", pl.softcap ? " SOFTCAP" : "", pl.dropout ? " DROPOUT" : "");
+    };
+    if (pl.run_dot) n += snprintf(name + n, sizeof(name) - n, "bwd_dot LPR=%d", pl.lpr);
+    if (pl.run_dkdv) {
+        seg("bwd_dkdv", pl.nbk, pl.deffk, pl.two_parts ? 1 : 0);
+        if (pl.two_parts) seg("bwd_dkdv", pl.nbk, pl.deffk, 2);
+    }
+    if (pl.run_dq) seg("bwd_dq", pl.nbq, pl.deffq, 0);
+    return name;
+}
+
+// the plan the calling thread's most recent fa_bwd launched (fa_bwd_last_plan_name)
+thread_local BwdPlan t_last_plan;
+thread_local bool t_last_plan_set = false;
+
 template <typename T, int D, bool SOFTCAP, bool DROPOUT = false>
-int run_bwd(fa::BParams bp, int rows_q_max, int rows_k_max, hipStream_t stream) {
-    // 32-wide blocks per wave (every LDS fragment feeds NB MFMAs): two wherever accumulators + resident operands fit
-    // the 512-register budget of a lone wave.  dQ: 2 for D <= 128; dK/dV (two accumulator sets + K and V): 2 for D = 64
-    // (at D = 128 two blocks would fill all 256 AGPRs with accumulators; hipcc then rotates the whole AGPR file
-    //  through v_accvgpr_mov to find temporaries -- measured 3x slower and not worth fighting).
-    //  At D = 64 the plain problem -- no softcap / dropout / ALiBi -- takes the one-block form as well: that is the shape of the
-    //  generated tile loop, tools/gen_bwd_loop.py.)
+int run_bwd(const BwdPlan &pl, fa::BParams bp, int rows_q_max, int rows_k_max, hipStream_t stream) {
     constexpr int NBQ = D <= 128 ? 2 : 1;
     constexpr int NBK2 = D <= 64 ? 2 : 1;
-    const bool one_block = D == 64 && !SOFTCAP && !DROPOUT && !bp.alibi;
+    constexpr int LPR = D / 8 > 32 ? 32 : D / 8;
+    // what this instantiation can launch; a plan outside it is a routing bug, never another kernel
+    if (pl.tile != D || pl.softcap != SOFTCAP || pl.dropout != DROPOUT || pl.lpr != LPR || pl.nbq != NBQ ||
+        (pl.nbk != 1 && pl.nbk != NBK2) || pl.two_parts != (D == 256))
+        return FA_ERR_UNSUPPORTED;
     // 1. D = rowsum(dO * O)
-    {
+    if (pl.run_dot) {
         const int64_t rows = bp.cu_seqlens_q ? (int64_t)bp.total_q : (int64_t)bp.b * bp.seqlen_q;
         const int64_t items = rows * bp.h;
-        constexpr int LPR = D / 8 > 32 ? 32 : D / 8;  // lanes per (row, head)
         const int per_block = 256 / LPR;
         const int grid = (int)std::min<int64_t>((items + per_block - 1) / per_block, 256 * 16);
-        if (items > 0) {
-            hipLaunchKernelGGL((fa::bwd_dot_kernel<T, LPR>), dim3(grid), dim3(256), 0, stream, bp);
-            if (hipGetLastError() != hipSuccess) return FA_ERR_LAUNCH;
-        }
+        hipLaunchKernelGGL((fa::bwd_dot_kernel<T, LPR>), dim3(grid), dim3(256), 0, stream, bp);
+        if (hipGetLastError() != hipSuccess) return FA_ERR_LAUNCH;
     }
     // 2. dK, dV
-    {
-        const int NBK = one_block ? 1 : NBK2;
-        bp.num_blocks = (rows_k_max + 128 * NBK - 1) / (128 * NBK);
+    if (pl.run_dkdv) {
+        bp.num_blocks = (rows_k_max + 128 * pl.nbk - 1) / (128 * pl.nbk);
         const int64_t tiles = (int64_t)bp.num_blocks * bp.h_k * bp.b;
         if (tiles > 0x7fffffff) return FA_ERR_BAD_SHAPE;
-        if (tiles > 0) {
-            bp.num_tiles = (int32_t)tiles;
-            const int64_t grid = unit_grid(tiles, bp.num_blocks, bp.whole_slots);
-            if (grid > 0x7fffffff) return FA_ERR_BAD_SHAPE;
-            bp.grid = (int32_t)grid;
-            int st;
-            if constexpr (D == 128 && !SOFTCAP && !DROPOUT) {
-                // head dims <= 96 on the 128-wide tiles: the instantiation whose generated loop skips the zero padding
-                st = bp.d <= 96 ? fa::launch_kernel<fa::bwd_dkdv_kernel<T, D, 1, false, false, 96>>(fa::smem_bytes_dkdv<D>(), bp.grid, 256, stream, bp)
-                                : fa::launch_kernel<fa::bwd_dkdv_kernel<T, D, 1, false, false>>(fa::smem_bytes_dkdv<D>(), bp.grid, 256, stream, bp);
-            } else if constexpr (D == 256) {
-                // head-dim tile 256: dV and dK by a launch each (PART 1 / 2, fa_bwd_kernel.h) -- one accumulator set per sweep;
-                // head dims <= 160 / <= 192 on the instantiations that skip the zero padding (DEFF)
-                auto two = [&](auto deff_c) {
-                    constexpr int DEFF = decltype(deff_c)::value;
-                    int s2 = fa::launch_kernel<fa::bwd_dkdv_kernel<T, D, 1, SOFTCAP, DROPOUT, DEFF, 1>>(fa::smem_bytes_dkdv<D>(), bp.grid, 256, stream, bp);
-                    if (s2 == FA_OK)
-                        s2 = fa::launch_kernel<fa::bwd_dkdv_kernel<T, D, 1, SOFTCAP, DROPOUT, DEFF, 2>>(fa::smem_bytes_dkdv<D>(), bp.grid, 256, stream, bp);
-                    return s2;
-                };
-                if constexpr (!SOFTCAP && !DROPOUT) {
-                    const int w = std::max(bp.d, bp.d_v);
-                    st = w <= 160 ? two(std::integral_constant<int, 160>{}) : w <= 192 ? two(std::integral_constant<int, 192>{}) : two(std::integral_constant<int, 256>{});
-                } else {
-                    st = two(std::integral_constant<int, 256>{});
-                }
+        bp.num_tiles = (int32_t)tiles;
+        const int64_t grid = unit_grid(tiles, bp.num_blocks, bp.whole_slots);
+        if (grid > 0x7fffffff) return FA_ERR_BAD_SHAPE;
+        bp.grid = (int32_t)grid;
+        int st;
+        if constexpr (D == 128 && !SOFTCAP && !DROPOUT) {
+            st = pl.deffk == 96 ? fa::launch_kernel<fa::bwd_dkdv_kernel<T, D, 1, false, false, 96>>(fa::smem_bytes_dkdv<D>(), bp.grid, 256, stream, bp)
+               : pl.deffk == D  ? fa::launch_kernel<fa::bwd_dkdv_kernel<T, D, 1, false, false>>(fa::smem_bytes_dkdv<D>(), bp.grid, 256, stream, bp)
+                                : FA_ERR_UNSUPPORTED;
+        } else if constexpr (D == 256) {
+            auto two = [&](auto deff_c) {
+                constexpr int DEFF = decltype(deff_c)::value;
+                int s2 = fa::launch_kernel<fa::bwd_dkdv_kernel<T, D, 1, SOFTCAP, DROPOUT, DEFF, 1>>(fa::smem_bytes_dkdv<D>(), bp.grid, 256, stream, bp);
+                if (s2 == FA_OK)
+                    s2 = fa::launch_kernel<fa::bwd_dkdv_kernel<T, D, 1, SOFTCAP, DROPOUT, DEFF, 2>>(fa::smem_bytes_dkdv<D>(), bp.grid, 256, stream, bp);
+                return s2;
+            };
+            if constexpr (!SOFTCAP && !DROPOUT) {
+                st = pl.deffk == 160 ? two(std::integral_constant<int, 160>{})
+                   : pl.deffk == 192 ? two(std::integral_constant<int, 192>{})
+                   : pl.deffk == D   ? two(std::integral_constant<int, 256>{})
+                                     : FA_ERR_UNSUPPORTED;
             } else {
-                st = one_block ? fa::launch_kernel<fa::bwd_dkdv_kernel<T, D, 1, SOFTCAP, DROPOUT>>(fa::smem_bytes_dkdv<D>(), bp.grid, 256, stream, bp)
-                               : fa::launch_kernel<fa::bwd_dkdv_kernel<T, D, NBK2, SOFTCAP, DROPOUT>>(fa::smem_bytes_dkdv<D>(), bp.grid, 256, stream, bp);
+                st = pl.deffk == D ? two(std::integral_constant<int, 256>{}) : FA_ERR_UNSUPPORTED;
             }
-            if (st != FA_OK) return st;
+        } else {
+            st = pl.deffk != D ? FA_ERR_UNSUPPORTED
+               : pl.nbk == 1   ? fa::launch_kernel<fa::bwd_dkdv_kernel<T, D, 1, SOFTCAP, DROPOUT>>(fa::smem_bytes_dkdv<D>(), bp.grid, 256, stream, bp)
+                               : fa::launch_kernel<fa::bwd_dkdv_kernel<T, D, NBK2, SOFTCAP, DROPOUT>>(fa::smem_bytes_dkdv<D>(), bp.grid, 256, stream, bp);
         }
+        if (st != FA_OK) return st;
     }
     // 3. dQ
-    {
+    if (pl.run_dq) {
         bp.num_blocks = (rows_q_max + 128 * NBQ - 1) / (128 * NBQ);
         const int64_t tiles = (int64_t)bp.num_blocks * bp.h * bp.b;
         if (tiles > 0x7fffffff) return FA_ERR_BAD_SHAPE;
-        if (tiles > 0) {
-            bp.num_tiles = (int32_t)tiles;
-            const int64_t grid = unit_grid(tiles, bp.num_blocks, bp.whole_slots);
-            if (grid > 0x7fffffff) return FA_ERR_BAD_SHAPE;
-            bp.grid = (int32_t)grid;
-            int st;
-            if constexpr (D == 128 && !SOFTCAP && !DROPOUT) {
-                st = bp.d <= 96 ? fa::launch_kernel<fa::bwd_dq_kernel<T, D, NBQ, false, false, 96>>(fa::smem_bytes_dq<D>(), bp.grid, 256, stream, bp)
-                                : fa::launch_kernel<fa::bwd_dq_kernel<T, D, NBQ, false, false>>(fa::smem_bytes_dq<D>(), bp.grid, 256, stream, bp);
-            } else if constexpr (D == 256 && !SOFTCAP && !DROPOUT) {
-                const int w = std::max(bp.d, bp.d_v);
-                st = w <= 160 ? fa::launch_kernel<fa::bwd_dq_kernel<T, D, NBQ, false, false, 160>>(fa::smem_bytes_dq<D>(), bp.grid, 256, stream, bp)
-                   : w <= 192 ? fa::launch_kernel<fa::bwd_dq_kernel<T, D, NBQ, false, false, 192>>(fa::smem_bytes_dq<D>(), bp.grid, 256, stream, bp)
-                                 : fa::launch_kernel<fa::bwd_dq_kernel<T, D, NBQ, false, false>>(fa::smem_bytes_dq<D>(), bp.grid, 256, stream, bp);
-            } else {
-                st = fa::launch_kernel<fa::bwd_dq_kernel<T, D, NBQ, SOFTCAP, DROPOUT>>(fa::smem_bytes_dq<D>(), bp.grid, 256, stream, bp);
-            }
-            if (st != FA_OK) return st;
+        bp.num_tiles = (int32_t)tiles;
+        const int64_t grid = unit_grid(tiles, bp.num_blocks, bp.whole_slots);
+        if (grid > 0x7fffffff) return FA_ERR_BAD_SHAPE;
+        bp.grid = (int32_t)grid;
+        int st;
+        if constexpr (D == 128 && !SOFTCAP && !DROPOUT) {
+            st = pl.deffq == 96 ? fa::launch_kernel<fa::bwd_dq_kernel<T, D, NBQ, false, false, 96>>(fa::smem_bytes_dq<D>(), bp.grid, 256, stream, bp)
+               : pl.deffq == D  ? fa::launch_kernel<fa::bwd_dq_kernel<T, D, NBQ, false, false>>(fa::smem_bytes_dq<D>(), bp.grid, 256, stream, bp)
+                                : FA_ERR_UNSUPPORTED;
+        } else if constexpr (D == 256 && !SOFTCAP && !DROPOUT) {
+            st = pl.deffq == 160 ? fa::launch_kernel<fa::bwd_dq_kernel<T, D, NBQ, false, false, 160>>(fa::smem_bytes_dq<D>(), bp.grid, 256, stream, bp)
+               : pl.deffq == 192 ? fa::launch_kernel<fa::bwd_dq_kernel<T, D, NBQ, false, false, 192>>(fa::smem_bytes_dq<D>(), bp.grid, 256, stream, bp)
+               : pl.deffq == D   ? fa::launch_kernel<fa::bwd_dq_kernel<T, D, NBQ, false, false>>(fa::smem_bytes_dq<D>(), bp.grid, 256, stream, bp)
+                                 : FA_ERR_UNSUPPORTED;
+        } else {
+            st = pl.deffq == D ? fa::launch_kernel<fa::bwd_dq_kernel<T, D, NBQ, SOFTCAP, DROPOUT>>(fa::smem_bytes_dq<D>(), bp.grid, 256, stream, bp)
+                               : FA_ERR_UNSUPPORTED;
         }
+        if (st != FA_OK) return st;
     }
     return FA_OK;
 }
 
 template <typename T>
-int dispatch_bwd(const fa::BParams &bp, bool softcap, int sq, int sk, hipStream_t stream) {
-    const bool drop = bp.rp_dropout != 1.f;  // p > 0 (never together with softcap: fa_bwd_validate)
-    switch (head_dim_tile_b(std::max(bp.d, bp.d_v))) {
+int dispatch_bwd(const BwdPlan &pl, const fa::BParams &bp, int sq, int sk, hipStream_t stream) {
+    switch (pl.tile) {
         case 64:
-            if (drop) return run_bwd<T, 64, false, true>(bp, sq, sk, stream);
-            return softcap ? run_bwd<T, 64, true>(bp, sq, sk, stream) : run_bwd<T, 64, false>(bp, sq, sk, stream);
+            if (pl.dropout) return run_bwd<T, 64, false, true>(pl, bp, sq, sk, stream);
+            return pl.softcap ? run_bwd<T, 64, true>(pl, bp, sq, sk, stream) : run_bwd<T, 64, false>(pl, bp, sq, sk, stream);
         case 128:
-            if (drop) return run_bwd<T, 128, false, true>(bp, sq, sk, stream);
-            return softcap ? run_bwd<T, 128, true>(bp, sq, sk, stream) : run_bwd<T, 128, false>(bp, sq, sk, stream);
+            if (pl.dropout) return run_bwd<T, 128, false, true>(pl, bp, sq, sk, stream);
+            return pl.softcap ? run_bwd<T, 128, true>(pl, bp, sq, sk, stream) : run_bwd<T, 128, false>(pl, bp, sq, sk, stream);
         default:
-            if (drop) return run_bwd<T, 256, false, true>(bp, sq, sk, stream);
-            return softcap ? run_bwd<T, 256, true>(bp, sq, sk, stream) : run_bwd<T, 256, false>(bp, sq, sk, stream);
+            if (pl.dropout) return run_bwd<T, 256, false, true>(pl, bp, sq, sk, stream);
+            return pl.softcap ? run_bwd<T, 256, true>(pl, bp, sq, sk, stream) : run_bwd<T, 256, false>(pl, bp, sq, sk, stream);
     }
 }
 
@@ -226,13 +292,26 @@ int fa_bwd_validate(const fa_bwd_params *p) {
     return FA_OK;
 }
 
+const char *fa_bwd_plan_name(const fa_bwd_params *p) {
+    if (fa_bwd_validate(p) != FA_OK) return nullptr;
+    thread_local char name[320];
+    return plan_text(plan_bwd(p), name);
+}
+
+const char *fa_bwd_last_plan_name(void) {
+    thread_local char name[320];
+    return t_last_plan_set ? plan_text(t_last_plan, name) : nullptr;
+}
+
 int fa_bwd(const fa_bwd_params *p, void *stream_) {
     const int st = fa_bwd_validate(p);
+    t_last_plan_set = false;
     if (st != FA_OK) return st;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    const bool no_q = (p->seqlen_q == 0) || (p->cu_seqlens_q && p->total_q == 0);
-    const bool no_k = (p->seqlen_k == 0) || (p->cu_seqlens_q && p->total_k == 0);
-    if (no_q && no_k) return FA_OK;
+    const BwdPlan pl = plan_bwd(p);
+    t_last_plan = pl;
+    t_last_plan_set = true;
+    if (!pl.run_dot && !pl.run_dkdv && !pl.run_dq) return FA_OK;  // no queries and no keys
 
     fa::BParams bp{};
     bp.q = p->q; bp.k = p->k; bp.v = p->v; bp.o = p->o; bp.dout = p->dout; bp.lse = p->softmax_lse;
@@ -281,8 +360,8 @@ int fa_bwd(const fa_bwd_params *p, void *stream_) {
     bp.rng_state = p->rng_state;
 
     // seqlen_q == 0: dK = dV = 0 is written by the dK/dV pass (no query tile is visible); seqlen_k == 0: dQ = 0 likewise
-    if (p->dtype == FA_DTYPE_BF16) return dispatch_bwd<__bf16>(bp, softcap, p->seqlen_q, p->seqlen_k, stream);
-    return dispatch_bwd<_Float16>(bp, softcap, p->seqlen_q, p->seqlen_k, stream);
+    if (pl.dtype == FA_DTYPE_BF16) return dispatch_bwd<__bf16>(pl, bp, p->seqlen_q, p->seqlen_k, stream);
+    return dispatch_bwd<_Float16>(pl, bp, p->seqlen_q, p->seqlen_k, stream);
 }
 
 uint32_t fa_sink_grad_params_size(void) { return (uint32_t)sizeof(fa_sink_grad_params); }

@@ -90,6 +90,18 @@ int fa_bwd_validate(const fa_bwd_params *params);
 /* sizeof(fa_bwd_params) as compiled, for binding self-checks. */
 uint32_t fa_bwd_params_size(void);
 
+/* Test hook: the kernels fa_bwd would launch for `params`, without launching (no device access; NULL when fa_bwd_validate
+ * refuses them).  One segment per launched kernel, in launch order, e.g.
+ *     "bwd_dot LPR=16 | bwd_dkdv D=128 NB=1 DEFF=96 | bwd_dq D=128 NB=2 DEFF=96"
+ * D = head-dim tile, NB = 32-wide blocks per wave, DEFF = columns of the tile the products cover; flags SOFTCAP / DROPOUT; the
+ * 256 tile shows its two dK/dV launches as PART=1 and PART=2.  A launch without work items (no query rows: bwd_dot, bwd_dq; no
+ * keys: bwd_dkdv) has no segment.  The string lives in thread-local storage until the thread's next call. */
+const char *fa_bwd_plan_name(const fa_bwd_params *params);
+
+/* Test hook: the plan of the calling thread's most recent fa_bwd() (same text; NULL before the first call and after a call
+ * that failed validation).  Tests read it to tie a gradient to the kernels that produced it. */
+const char *fa_bwd_last_plan_name(void);
+
 /*
  * Gradient of a learnable attention sink (fa_fwd_sink, include/fa_fwd.h).  With the sink inside the stored LSE,
  * P = exp(S - LSE) and D_i = sum_d dO.O = sum_j P_ij dP_ij (the sink's column has no value: it adds nothing to D), so

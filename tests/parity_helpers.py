@@ -1,6 +1,7 @@
 """Helpers shared by the GPU parity tests (a plain module, not collected): row sampling for problems whose full attention
 matrix is too costly for the CPU oracle, and the row-subset comparison of tests/test_full_size_gpu.py (bounds in its docstring).
-Also the one place that reads back which forward plan ran (fa_fwd_last_plan_name, include/fa_fwd.h)."""
+Also the one place that reads back which forward plan ran (fa_fwd_last_plan_name, include/fa_fwd.h) and which backward
+kernels (fa_bwd_last_plan_name, include/fa_bwd.h)."""
 import math
 import re
 
@@ -18,6 +19,24 @@ def last_plan():
     name = _lib.load().fa_fwd_last_plan_name()
     assert name is not None, "no forward plan recorded: the entry point did not reach fa_fwd on this thread"
     return name.decode()
+
+
+def last_bwd_plan():
+    """Plan text of the calling thread's most recent fa_bwd launch: one segment per launched kernel."""
+    from flash_attention_annotated_amd import _lib
+    name = _lib.load().fa_bwd_last_plan_name()
+    assert name is not None, "no backward plan recorded: the entry point did not reach fa_bwd on this thread"
+    return name.decode()
+
+
+def record_bwd_plan(out):
+    """-> a list that receives the plan text of the backward of `out` (an output of one of the autograd Functions).  autograd
+    runs the backward node of a GPU tensor on the engine's thread for that device, not on the thread that calls
+    torch.autograd.grad, and fa_bwd_last_plan_name() is per thread: a hook on the node reads it there, right behind the
+    node's fa_bwd."""
+    seen = []
+    out.grad_fn.register_hook(lambda *_: seen.append(last_bwd_plan()))
+    return seen
 
 
 def kernel_key(plan, dtype):

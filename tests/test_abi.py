@@ -25,6 +25,7 @@ def test_header_symbols_all_exported(built_lib):
     names = _header_functions()
     assert set(names) == set(_lib.EXPORTED_SYMBOLS), "binding list and header disagree"
     assert "fa_fwd_last_plan_name" in names  # the hook the GPU parity tests read the launched kernel from
+    assert {"fa_bwd_plan_name", "fa_bwd_last_plan_name"} <= set(names)  # ... and the backward's
     for n in names:
         assert hasattr(built_lib, n), f"{n} declared in include/*.h but not exported"
 
@@ -33,6 +34,14 @@ def test_struct_layout_and_version(built_lib):
     assert built_lib.fa_fwd_params_size() == ctypes.sizeof(_lib.FaFwdParams)
     assert built_lib.fa_bwd_params_size() == ctypes.sizeof(_lib.FaBwdParams)
     assert built_lib.fa_abi_version() == _lib.FA_ABI_VERSION
+
+
+def test_bwd_plan_hooks_are_additive(built_lib):
+    """fa_bwd_plan_name / fa_bwd_last_plan_name came without an ABI bump: version 13, fa_bwd_params still 408 bytes; NULL in,
+    NULL out."""
+    assert built_lib.fa_bwd_plan_name(None) is None
+    assert built_lib.fa_abi_version() == 13
+    assert built_lib.fa_bwd_params_size() == 408
 
 
 def _good():

@@ -48,7 +48,8 @@ def test_every_tile_once_and_xcds_balanced(b, h_k, h_ratio, m):
         assert len({xcd_of[t] for t in range(t0, t0 + h_ratio)}) == 1
 
 
-@pytest.mark.parametrize("units,blocks", [(1, 1), (20, 64), (42, 32), (12, 7), (64, 32), (17, 5), (40, 3), (16, 9)])
+@pytest.mark.parametrize("units,blocks", [(1, 1), (20, 64), (42, 32), (12, 7), (64, 32), (17, 5), (40, 3), (16, 9),
+                                          (18, 4), (36, 2)])  # the many-units cases of tests/bwd_plan_universe.py: dK/dV, dQ
 def test_backward_block_map(units, blocks):
     """decode_block() of the backward kernels (csrc/fa_bwd_kernel.h) with unit_grid() (csrc/fa_bwd_api.hip)."""
     tiles = units * blocks
@@ -63,6 +64,24 @@ def test_backward_block_map(units, blocks):
             per_xcd[xcd] += 1
     assert sorted(seen) == list(range(tiles))
     assert max(per_xcd) - min(per_xcd) <= 1
+
+
+@pytest.mark.parametrize("units,blocks", [(18, 4), (36, 2)])
+def test_backward_block_map_many_units(units, blocks):
+    """The many-units cases of tests/bwd_plan_universe.py (b 3, h 12, h_k 6: 18 units of 4 key blocks in the dK/dV launch, 36
+    units of 2 query blocks in the dQ launch): both parts of decode_block() get tiles -- whole units through the whole_slots
+    branch, the units behind them block by block -- and every unit is served by exactly one of the two."""
+    tiles = units * blocks
+    ws = units // 8 * blocks if units >= 16 else 0
+    grid = 8 * (ws + (tiles - ws * 8 + 7) // 8)
+    whole, rest = set(), set()
+    for wg in range(grid):
+        xcd, slot = wg & 7, wg >> 3
+        t = ((slot // blocks) * 8 + xcd) * blocks + slot % blocks if slot < ws else slot * 8 + xcd
+        if t < tiles:
+            (whole if slot < ws else rest).add(t // blocks)
+    assert ws > 0 and whole == set(range(ws * 8 // blocks)) and len(whole) >= 16
+    assert rest == set(range(len(whole), units)) and rest
 
 
 @pytest.mark.parametrize("b,h_k,h_ratio,m,cus", [(4, 16, 1, 32, 256), (32, 16, 1, 2, 256), (8, 16, 1, 8, 256), (2, 21, 1, 32, 256),
