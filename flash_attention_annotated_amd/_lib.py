@@ -60,6 +60,9 @@ EXPORTED_SYMBOLS = (
     "fa_sink_grad",
     "fa_sink_grad_validate",
     "fa_sink_grad_params_size",
+    "fa_bwd_block_sparse",
+    "fa_bwd_block_sparse_validate",
+    "fa_block_sparse_bwd_params_size",
 )
 
 
@@ -251,6 +254,17 @@ class FaBlockSparseParams(ctypes.Structure):
     )
 
 
+class FaBlockSparseBwdParams(ctypes.Structure):
+    """Field-for-field mirror of `struct fa_block_sparse_bwd_params` (include/fa_bwd.h)."""
+
+    _fields_ = (
+        [("abi_version", ctypes.c_uint32), ("struct_size", ctypes.c_uint32)]
+        + [(n, ctypes.c_void_p) for n in ("q_block_cnt", "q_block_idx")]
+        + [(n, ctypes.c_int64 * 4) for n in ("q_cnt_stride", "q_idx_stride")]
+        + [("block_m", ctypes.c_int32), ("block_n", ctypes.c_int32)]
+    )
+
+
 class FaSinkGradParams(ctypes.Structure):
     """Field-for-field mirror of `struct fa_sink_grad_params` (include/fa_bwd.h)."""
 
@@ -290,7 +304,7 @@ def is_stale():
 
 def build(force=False, verbose=False):
     """Compile csrc/ for gfx950 into the in-tree shared library (hipcc cross-compiles without a GPU)."""
-    srcs = [os.path.join(CSRC, "fa_fwd_api.hip"), os.path.join(CSRC, "fa_bwd_api.hip")]
+    srcs = [os.path.join(CSRC, "fa_fwd_api.hip"), os.path.join(CSRC, "fa_bwd_api.hip"), os.path.join(CSRC, "fa_bwd_bs_api.hip")]
     if not force and not is_stale():
         return LIB_PATH
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -426,6 +440,16 @@ def load():
     lib.fa_sink_grad_params_size.restype = ctypes.c_uint32
     if lib.fa_sink_grad_params_size() != ctypes.sizeof(FaSinkGradParams):
         raise RuntimeError("fa_sink_grad_params layout mismatch between include/fa_bwd.h and _lib.FaSinkGradParams")
+    lib.fa_bwd_block_sparse.argtypes = [ctypes.POINTER(FaBwdParams), ctypes.POINTER(FaBlockSparseParams),
+                                        ctypes.POINTER(FaBlockSparseBwdParams), ctypes.c_void_p]
+    lib.fa_bwd_block_sparse.restype = ctypes.c_int
+    lib.fa_bwd_block_sparse_validate.argtypes = [ctypes.POINTER(FaBwdParams), ctypes.POINTER(FaBlockSparseParams),
+                                                 ctypes.POINTER(FaBlockSparseBwdParams)]
+    lib.fa_bwd_block_sparse_validate.restype = ctypes.c_int
+    lib.fa_block_sparse_bwd_params_size.argtypes = []
+    lib.fa_block_sparse_bwd_params_size.restype = ctypes.c_uint32
+    if lib.fa_block_sparse_bwd_params_size() != ctypes.sizeof(FaBlockSparseBwdParams):
+        raise RuntimeError("fa_block_sparse_bwd_params layout mismatch between include/fa_bwd.h and _lib.FaBlockSparseBwdParams")
     lib.fa_bwd.argtypes = [ctypes.POINTER(FaBwdParams), ctypes.c_void_p]
     lib.fa_bwd.restype = ctypes.c_int
     lib.fa_bwd_validate.argtypes = [ctypes.POINTER(FaBwdParams)]
@@ -494,6 +518,14 @@ def new_block_sparse_params():
     p = FaBlockSparseParams()
     p.abi_version = FA_ABI_VERSION
     p.struct_size = ctypes.sizeof(FaBlockSparseParams)
+    p.block_m = p.block_n = 128
+    return p
+
+
+def new_block_sparse_bwd_params():
+    p = FaBlockSparseBwdParams()
+    p.abi_version = FA_ABI_VERSION
+    p.struct_size = ctypes.sizeof(FaBlockSparseBwdParams)
     p.block_m = p.block_n = 128
     return p
 

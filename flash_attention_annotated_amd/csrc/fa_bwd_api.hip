@@ -4,6 +4,7 @@
 // set_params_dgrad (:161-221) and run_mha_bwd (:757-765): validate, fill the kernel params, launch the three
 // kernels on the caller's stream.  No allocation, no synchronisation.
 #include "fa_bwd.h"
+#include "fa_bwd_internal.h"
 #include "fa_bwd_kernel.h"
 #include "fa_launch.h"
 
@@ -138,9 +139,11 @@ const char *plan_text(const BwdPlan &pl, char (&name)[320]) {
     return name;
 }
 
-// the plan the calling thread's most recent fa_bwd launched (fa_bwd_last_plan_name)
+// the plan the calling thread's most recent fa_bwd launched (fa_bwd_last_plan_name) ...
 thread_local BwdPlan t_last_plan;
 thread_local bool t_last_plan_set = false;
+// ... or, when that call was fa_bwd_block_sparse, the text it left (fa::bwd_set_last_plan_text; empty = it was not)
+thread_local char t_last_text[320] = "";
 
 template <typename T, int D, bool SOFTCAP, bool DROPOUT = false>
 int run_bwd(const BwdPlan &pl, fa::BParams bp, int rows_q_max, int rows_k_max, hipStream_t stream) {
@@ -242,6 +245,84 @@ int dispatch_bwd(const BwdPlan &pl, const fa::BParams &bp, int sq, int sk, hipSt
 
 }  // namespace
 
+// ---- what fa_bwd_block_sparse (fa_bwd_bs_api.hip) shares with fa_bwd: fa_bwd_internal.h -----------------------------------
+namespace fa {
+
+void bwd_fill_params(const fa_bwd_params *p, BParams &bp) {
+    bp.q = p->q; bp.k = p->k; bp.v = p->v; bp.o = p->o; bp.dout = p->dout; bp.lse = p->softmax_lse;
+    bp.dq = p->dq; bp.dk = p->dk; bp.dv = p->dv; bp.dsum = p->softmax_d;
+    bp.cu_seqlens_q = p->cu_seqlens_q; bp.cu_seqlens_k = p->cu_seqlens_k;
+    bp.q_batch_stride = p->q_batch_stride; bp.q_row_stride = p->q_row_stride; bp.q_head_stride = p->q_head_stride;
+    bp.k_batch_stride = p->k_batch_stride; bp.k_row_stride = p->k_row_stride; bp.k_head_stride = p->k_head_stride;
+    bp.v_batch_stride = p->v_batch_stride; bp.v_row_stride = p->v_row_stride; bp.v_head_stride = p->v_head_stride;
+    bp.o_batch_stride = p->o_batch_stride; bp.o_row_stride = p->o_row_stride; bp.o_head_stride = p->o_head_stride;
+    bp.do_batch_stride = p->do_batch_stride; bp.do_row_stride = p->do_row_stride; bp.do_head_stride = p->do_head_stride;
+    bp.dq_batch_stride = p->dq_batch_stride; bp.dq_row_stride = p->dq_row_stride; bp.dq_head_stride = p->dq_head_stride;
+    bp.dk_batch_stride = p->dk_batch_stride; bp.dk_row_stride = p->dk_row_stride; bp.dk_head_stride = p->dk_head_stride;
+    bp.dv_batch_stride = p->dv_batch_stride; bp.dv_row_stride = p->dv_row_stride; bp.dv_head_stride = p->dv_head_stride;
+    bp.dsum_row_len = p->softmax_d_row_len;
+    bp.b = p->b; bp.seqlen_q = p->seqlen_q; bp.seqlen_k = p->seqlen_k; bp.h = p->h; bp.h_k = p->h_k; bp.d = p->d;
+    bp.d_v = (p->d_v > 0) ? p->d_v : p->d;
+    bp.total_q = p->total_q;
+    bp.h_ratio = p->h / p->h_k;
+
+    // window normalisation exactly as the forward (fa_fwd_api.hip; csrc/flash_attn/flash_api.cpp:790,836-837)
+    int wl = p->window_size_left, wr = p->window_size_right;
+    if (p->is_causal) wr = 0;
+    if (!(p->flags & FA_FLAG_FA3_WINDOW)) {  // (FA3 rule: a negative side is unbounded, include/fa_fwd.h)
+        if (wl >= p->seqlen_k) wl = -1;
+        if (wr >= p->seqlen_k) wr = -1;
+        if (p->is_causal) wr = 0;
+        if (wl >= 0 && wr < 0) wr = p->seqlen_k;
+    }
+    bp.window_left = wl;
+    bp.window_right = wr;
+
+    const bool softcap = p->softcap > 0.f;
+    constexpr float kLog2e = 1.4426950408889634f;
+    if (softcap) {
+        bp.softcap_pre = p->softmax_scale / p->softcap;
+        bp.scale_log2 = p->softcap * kLog2e;
+    } else {
+        bp.softcap_pre = 0.f;
+        bp.scale_log2 = p->softmax_scale * kLog2e;
+    }
+    bp.out_scale = p->softmax_scale;
+    bp.alibi = p->alibi_slopes;
+    bp.alibi_bs = (int32_t)p->alibi_slopes_batch_stride;
+    bp.drop_thr = p->p_dropout > 0.f ? (int)std::floor(255.0 * (1.0 - (double)p->p_dropout)) : 255;  // as fa_fwd
+    bp.rp_dropout = p->p_dropout > 0.f ? 1.f / (1.f - p->p_dropout) : 1.f;
+    bp.rng_state = p->rng_state;
+}
+
+int bwd_launch_dot(const BParams &bp, int32_t dtype, int tile, hipStream_t stream) {
+    const int64_t rows = bp.cu_seqlens_q ? (int64_t)bp.total_q : (int64_t)bp.b * bp.seqlen_q;
+    const int64_t items = rows * bp.h;
+    const int lpr = std::min(tile / 8, 32), per_block = 256 / lpr;
+    const int grid = (int)std::min<int64_t>((items + per_block - 1) / per_block, 256 * 16);
+    const bool bf16 = dtype == FA_DTYPE_BF16;
+    if (lpr == 8) {
+        if (bf16) hipLaunchKernelGGL((bwd_dot_kernel<__bf16, 8>), dim3(grid), dim3(256), 0, stream, bp);
+        else hipLaunchKernelGGL((bwd_dot_kernel<_Float16, 8>), dim3(grid), dim3(256), 0, stream, bp);
+    } else if (lpr == 16) {
+        if (bf16) hipLaunchKernelGGL((bwd_dot_kernel<__bf16, 16>), dim3(grid), dim3(256), 0, stream, bp);
+        else hipLaunchKernelGGL((bwd_dot_kernel<_Float16, 16>), dim3(grid), dim3(256), 0, stream, bp);
+    } else {
+        if (bf16) hipLaunchKernelGGL((bwd_dot_kernel<__bf16, 32>), dim3(grid), dim3(256), 0, stream, bp);
+        else hipLaunchKernelGGL((bwd_dot_kernel<_Float16, 32>), dim3(grid), dim3(256), 0, stream, bp);
+    }
+    return hipGetLastError() == hipSuccess ? FA_OK : FA_ERR_LAUNCH;
+}
+
+int64_t bwd_unit_grid(int64_t tiles, int blocks, int32_t &whole_slots) { return unit_grid(tiles, blocks, whole_slots); }
+
+void bwd_set_last_plan_text(const char *text) {
+    t_last_plan_set = false;
+    snprintf(t_last_text, sizeof(t_last_text), "%s", text ? text : "");
+}
+
+}  // namespace fa
+
 extern "C" {
 
 uint32_t fa_bwd_params_size(void) { return (uint32_t)sizeof(fa_bwd_params); }
@@ -300,12 +381,14 @@ const char *fa_bwd_plan_name(const fa_bwd_params *p) {
 
 const char *fa_bwd_last_plan_name(void) {
     thread_local char name[320];
+    if (t_last_text[0]) return t_last_text;
     return t_last_plan_set ? plan_text(t_last_plan, name) : nullptr;
 }
 
 int fa_bwd(const fa_bwd_params *p, void *stream_) {
     const int st = fa_bwd_validate(p);
     t_last_plan_set = false;
+    t_last_text[0] = 0;
     if (st != FA_OK) return st;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     const BwdPlan pl = plan_bwd(p);
@@ -314,50 +397,7 @@ int fa_bwd(const fa_bwd_params *p, void *stream_) {
     if (!pl.run_dot && !pl.run_dkdv && !pl.run_dq) return FA_OK;  // no queries and no keys
 
     fa::BParams bp{};
-    bp.q = p->q; bp.k = p->k; bp.v = p->v; bp.o = p->o; bp.dout = p->dout; bp.lse = p->softmax_lse;
-    bp.dq = p->dq; bp.dk = p->dk; bp.dv = p->dv; bp.dsum = p->softmax_d;
-    bp.cu_seqlens_q = p->cu_seqlens_q; bp.cu_seqlens_k = p->cu_seqlens_k;
-    bp.q_batch_stride = p->q_batch_stride; bp.q_row_stride = p->q_row_stride; bp.q_head_stride = p->q_head_stride;
-    bp.k_batch_stride = p->k_batch_stride; bp.k_row_stride = p->k_row_stride; bp.k_head_stride = p->k_head_stride;
-    bp.v_batch_stride = p->v_batch_stride; bp.v_row_stride = p->v_row_stride; bp.v_head_stride = p->v_head_stride;
-    bp.o_batch_stride = p->o_batch_stride; bp.o_row_stride = p->o_row_stride; bp.o_head_stride = p->o_head_stride;
-    bp.do_batch_stride = p->do_batch_stride; bp.do_row_stride = p->do_row_stride; bp.do_head_stride = p->do_head_stride;
-    bp.dq_batch_stride = p->dq_batch_stride; bp.dq_row_stride = p->dq_row_stride; bp.dq_head_stride = p->dq_head_stride;
-    bp.dk_batch_stride = p->dk_batch_stride; bp.dk_row_stride = p->dk_row_stride; bp.dk_head_stride = p->dk_head_stride;
-    bp.dv_batch_stride = p->dv_batch_stride; bp.dv_row_stride = p->dv_row_stride; bp.dv_head_stride = p->dv_head_stride;
-    bp.dsum_row_len = p->softmax_d_row_len;
-    bp.b = p->b; bp.seqlen_q = p->seqlen_q; bp.seqlen_k = p->seqlen_k; bp.h = p->h; bp.h_k = p->h_k; bp.d = p->d;
-    bp.d_v = (p->d_v > 0) ? p->d_v : p->d;
-    bp.total_q = p->total_q;
-    bp.h_ratio = p->h / p->h_k;
-
-    // window normalisation exactly as the forward (fa_fwd_api.hip; csrc/flash_attn/flash_api.cpp:790,836-837)
-    int wl = p->window_size_left, wr = p->window_size_right;
-    if (p->is_causal) wr = 0;
-    if (!(p->flags & FA_FLAG_FA3_WINDOW)) {  // (FA3 rule: a negative side is unbounded, include/fa_fwd.h)
-        if (wl >= p->seqlen_k) wl = -1;
-        if (wr >= p->seqlen_k) wr = -1;
-        if (p->is_causal) wr = 0;
-        if (wl >= 0 && wr < 0) wr = p->seqlen_k;
-    }
-    bp.window_left = wl;
-    bp.window_right = wr;
-
-    const bool softcap = p->softcap > 0.f;
-    constexpr float kLog2e = 1.4426950408889634f;
-    if (softcap) {
-        bp.softcap_pre = p->softmax_scale / p->softcap;
-        bp.scale_log2 = p->softcap * kLog2e;
-    } else {
-        bp.softcap_pre = 0.f;
-        bp.scale_log2 = p->softmax_scale * kLog2e;
-    }
-    bp.out_scale = p->softmax_scale;
-    bp.alibi = p->alibi_slopes;
-    bp.alibi_bs = (int32_t)p->alibi_slopes_batch_stride;
-    bp.drop_thr = p->p_dropout > 0.f ? (int)std::floor(255.0 * (1.0 - (double)p->p_dropout)) : 255;  // as fa_fwd
-    bp.rp_dropout = p->p_dropout > 0.f ? 1.f / (1.f - p->p_dropout) : 1.f;
-    bp.rng_state = p->rng_state;
+    fa::bwd_fill_params(p, bp);
 
     // seqlen_q == 0: dK = dV = 0 is written by the dK/dV pass (no query tile is visible); seqlen_k == 0: dQ = 0 likewise
     if (pl.dtype == FA_DTYPE_BF16) return dispatch_bwd<__bf16>(pl, bp, p->seqlen_q, p->seqlen_k, stream);

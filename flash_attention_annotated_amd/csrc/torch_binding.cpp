@@ -409,8 +409,9 @@ struct BwdArgs {
     bool fa3_window = false;  // the window rule of the FA3 surface (fa3_bwd)
 };
 
-void launch_bwd(const Tensor &dout, const Tensor &q, const Tensor &k, const Tensor &v, const Tensor &out, const Tensor &lse,
-                const Tensor &dq, const Tensor &dk, const Tensor &dv, const Tensor &softmax_d, const BwdArgs &a) {
+// fa_bwd_params of one backward call (every entry point's filler, the block-sparse one's too)
+fa_bwd_params fill_bwd_params(const Tensor &dout, const Tensor &q, const Tensor &k, const Tensor &v, const Tensor &out, const Tensor &lse,
+                              const Tensor &dq, const Tensor &dk, const Tensor &dv, const Tensor &softmax_d, const BwdArgs &a) {
     fa_bwd_params p{};
     p.abi_version = FA_ABI_VERSION;
     p.struct_size = sizeof(fa_bwd_params);
@@ -449,6 +450,12 @@ void launch_bwd(const Tensor &dout, const Tensor &q, const Tensor &k, const Tens
     p.deterministic = a.deterministic ? 1 : 0;
     p.p_dropout = (float)a.p_dropout;
     p.rng_state = static_cast<const uint64_t *>(ptr(a.rng_state));
+    return p;
+}
+
+void launch_bwd(const Tensor &dout, const Tensor &q, const Tensor &k, const Tensor &v, const Tensor &out, const Tensor &lse,
+                const Tensor &dq, const Tensor &dk, const Tensor &dv, const Tensor &softmax_d, const BwdArgs &a) {
+    const fa_bwd_params p = fill_bwd_params(dout, q, k, v, out, lse, dq, dk, dv, softmax_d, a);
     const int st = fa_bwd(&p, current_stream(q));
     TORCH_CHECK(st == 0, "fa_bwd failed (", st, "): ", fa_strerror(st));
 }
@@ -1536,6 +1543,82 @@ std::tuple<Tensor, Tensor, Tensor, OptTensor> cute_bwd(const Tensor &dout, const
     return {r[0], r[1], r[2], dsink};
 }
 
+// The backward of cute_fwd_block_sparse (include/fa_bwd.h fa_bwd_block_sparse): the forward's four lists for the dQ sweep and
+// the caller's key-major lists q_block_cnt (b | 1, h | 1, nk) / q_block_idx (b | 1, h | 1, nk, nm) for the dK / dV sweep, all
+// handed over through their strides and never read here.  With a sink, its gradient from the LSE and the D this call wrote.
+// Returns (dq, dk, dv, dsink or None).
+std::tuple<Tensor, Tensor, Tensor, OptTensor> cute_bwd_block_sparse(
+    const Tensor &dout_, const Tensor &q_, const Tensor &k_, const Tensor &v_, const Tensor &out_, const Tensor &softmax_lse,
+    double softmax_scale, bool is_causal, int64_t window_size_left, int64_t window_size_right, double softcap,
+    const OptTensor &learnable_sink, const OptTensor &full_block_cnt, const OptTensor &full_block_idx,
+    const OptTensor &mask_block_cnt, const OptTensor &mask_block_idx, const OptTensor &q_block_cnt, const OptTensor &q_block_idx) {
+    CHECK_DEVICE(q_, "q"); CHECK_DEVICE(k_, "k"); CHECK_DEVICE(v_, "v"); CHECK_DEVICE(out_, "out"); CHECK_DEVICE(dout_, "dout");
+    CHECK_DEVICE(softmax_lse, "softmax_lse");
+    TORCH_CHECK(q_.dim() == 4 && k_.dim() == 4 && v_.dim() == 4, "block sparsity needs dense q (b, sq, h, d) and k / v (b, sk, h_k, d)");
+    bwd_common_checks(dout_, q_, k_, v_, out_, softmax_lse);
+    const int64_t b = q_.size(0), sq = q_.size(1), h = q_.size(2), d = q_.size(3), sk = k_.size(1), h_k = k_.size(2);
+    TORCH_CHECK(d <= 128 && v_.size(3) == d, "the block-sparse backward supports head dims up to 128 with the same head dim for V");
+    TORCH_CHECK(k_.size(0) == b && k_.size(3) == d && v_.sizes() == k_.sizes() && out_.sizes() == q_.sizes() && dout_.sizes() == q_.sizes(),
+                "q, k, v, out, dout shapes do not match");
+    TORCH_CHECK(softmax_lse.scalar_type() == at::kFloat && softmax_lse.dim() == 3 && softmax_lse.size(0) == b &&
+                    softmax_lse.size(1) == h && softmax_lse.size(2) == sq, "softmax_lse must be fp32 (b, h, seqlen_q)");
+    TORCH_CHECK(mask_block_cnt.has_value() && mask_block_idx.has_value(), "mask_block_cnt and mask_block_idx are required");
+    TORCH_CHECK(q_block_cnt.has_value() && q_block_idx.has_value(), "q_block_cnt and q_block_idx are required");
+    check_sink(learnable_sink, q_);
+    const int64_t nm = (sq + 127) / 128, nk = (sk + 127) / 128;
+    check_block_list(mask_block_cnt, mask_block_idx, "mask", q_, nm, nk);
+    check_block_list(full_block_cnt, full_block_idx, "full", q_, nm, nk);
+    check_block_list(q_block_cnt, q_block_idx, "q", q_, nk, nm);
+    c10::hip::HIPGuardMasqueradingAsCUDA device_guard(q_.device());
+    const Tensor dout = aligned_or_copy(dout_), q = aligned_or_copy(q_), k = aligned_or_copy(k_), v = aligned_or_copy(v_),
+                 out = aligned_or_copy(out_);
+    const Tensor lse = softmax_lse.is_contiguous() ? softmax_lse : softmax_lse.contiguous();
+    Tensor dq = at::empty_like(q, at::MemoryFormat::Contiguous), dk = at::empty_like(k, at::MemoryFormat::Contiguous),
+           dv = at::empty_like(v, at::MemoryFormat::Contiguous);
+    Tensor softmax_d = at::empty({b, h, round128(sq)}, q.options().dtype(at::kFloat));
+    OptTensor dsink;
+    if (q.numel() == 0 || k.numel() == 0) {
+        dq.zero_(); dk.zero_(); dv.zero_();
+        if (learnable_sink.has_value()) dsink = at::zeros_like(*learnable_sink);
+        return {dq, dk, dv, dsink};
+    }
+    BwdArgs a;
+    a.batch = b; a.max_seqlen_q = sq; a.max_seqlen_k = sk; a.softmax_scale = softmax_scale; a.causal = is_causal;
+    a.window_left = window_size_left; a.window_right = window_size_right; a.softcap = softcap; a.deterministic = true;
+    a.fa3_window = true;  // a missing window side is unbounded, as in the forward
+    const fa_bwd_params p = fill_bwd_params(dout, q, k, v, out, lse, dq, dk, dv, softmax_d, a);
+
+    fa_block_sparse_params s{};
+    s.abi_version = FA_ABI_VERSION;
+    s.struct_size = sizeof(fa_block_sparse_params);
+    s.block_m = s.block_n = 128;
+    s.mask_block_cnt = static_cast<const int32_t *>(mask_block_cnt->data_ptr());
+    s.mask_block_idx = static_cast<const int32_t *>(mask_block_idx->data_ptr());
+    set_list_strides(*mask_block_cnt, s.mask_cnt_stride);
+    set_list_strides(*mask_block_idx, s.mask_idx_stride);
+    if (full_block_cnt.has_value()) {
+        s.full_block_cnt = static_cast<const int32_t *>(full_block_cnt->data_ptr());
+        s.full_block_idx = static_cast<const int32_t *>(full_block_idx->data_ptr());
+        set_list_strides(*full_block_cnt, s.full_cnt_stride);
+        set_list_strides(*full_block_idx, s.full_idx_stride);
+    }
+    fa_block_sparse_bwd_params kl{};
+    kl.abi_version = FA_ABI_VERSION;
+    kl.struct_size = sizeof(fa_block_sparse_bwd_params);
+    kl.block_m = kl.block_n = 128;
+    kl.q_block_cnt = static_cast<const int32_t *>(q_block_cnt->data_ptr());
+    kl.q_block_idx = static_cast<const int32_t *>(q_block_idx->data_ptr());
+    set_list_strides(*q_block_cnt, kl.q_cnt_stride);
+    set_list_strides(*q_block_idx, kl.q_idx_stride);
+    const int st = fa_bwd_block_sparse(&p, &s, &kl, current_stream(q));
+    TORCH_CHECK(st == 0, "fa_bwd_block_sparse failed (", st, "): ", fa_strerror(st));
+    if (learnable_sink.has_value()) {
+        const OptTensor none;
+        dsink = sink_grad(lse, softmax_d, *learnable_sink, none, none, b, sq).to(learnable_sink->scalar_type());
+    }
+    return {dq, dk, dv, dsink};
+}
+
 // flash_attn_3::fwd_combine, hopper/flash_api.cpp:1569-1670: merge caller-held split-KV partials.  out_partial
 // (num_splits, b, seqlen, h, d) fp32, lse_partial (num_splits, b, seqlen, h) fp32 -> (out, softmax_lse (b, seqlen, h)).
 std::tuple<Tensor, Tensor> fa3_fwd_combine(const Tensor &out_partial, const Tensor &lse_partial, const OptTensor &out_,
@@ -1608,5 +1691,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("cute_fwd", &cute_fwd, "cute surface forward (flash_attn.cute.interface, with learnable_sink)");
     m.def("cute_fwd_block_sparse", &cute_fwd_block_sparse, "cute surface forward restricted to listed 128 x 128 blocks");
     m.def("cute_bwd", &cute_bwd, "cute surface backward: (dq, dk, dv, dsink)");
+    m.def("cute_bwd_block_sparse", &cute_bwd_block_sparse, "cute surface backward over listed 128 x 128 blocks: (dq, dk, dv, dsink)");
     m.def("sink_grad", &sink_grad, "gradient of a learnable sink from softmax_lse and softmax_d");
 }

@@ -7,8 +7,10 @@ forward-only).
 
 `flash_attn_func` also takes the reference's block-sparse tensors (`full_block_cnt / full_block_idx / mask_block_cnt /
 mask_block_idx`, 128 x 128 blocks; include/fa_fwd.h fa_fwd_block_sparse has the definition, DESIGN.md §4.13 the kernel) and
-`block_sparse_from_mask` makes them from a block mask.  That route is forward-only; `mask_mod`, a CuTe-DSL callable, is not
-supported.
+`block_sparse_from_mask` makes them from a block mask.  That route is differentiable when the caller also passes the
+key-major lists `q_block_cnt / q_block_idx` the dK / dV sweep walks (`block_sparse_bwd_lists` makes them from the four
+forward lists; include/fa_bwd.h fa_bwd_block_sparse; head dims up to 128); without them the backward raises.
+`mask_mod`, a CuTe-DSL callable, is not supported.
 
 Routing is the FA3 surface's (csrc/torch_binding.cpp cute_fwd -> fa3_fwd_core): dense and varlen calls, decode steps over
 a paged cache with their GQA swap and split-KV, ragged queries over a cache.  The cute signatures carry no max_seqlen:
@@ -64,6 +66,46 @@ def block_sparse_from_mask(block_mask, full=None):
     full_cnt, full_idx = lists(block_mask & full)
     mask_cnt, mask_idx = lists(block_mask & ~full)
     return full_cnt, full_idx, mask_cnt, mask_idx
+
+
+def block_sparse_bwd_lists(full_block_cnt, full_block_idx, mask_block_cnt, mask_block_idx):
+    """The key-major lists of the block-sparse backward from the forward's lists: (q_block_cnt (b | 1, h | 1, nk), q_block_idx
+    (b | 1, h | 1, nk, nm)), int32 -- key block n is visited by the first q_block_cnt[.., n] query blocks of q_block_idx[.., n, :].
+    One merged list of both forward lists (full_* may be None), counts respected, tails ignored; indices ascending, tails
+    zero.  A batch / head dimension of size 1 is kept when both lists broadcast there.  Pure torch on the lists' device,
+    nothing is read on the host; a pattern that stays fixed needs this once.  From a block mask,
+    block_sparse_from_mask(block_mask.transpose(-1, -2))[2:] gives the same."""
+    nm, nk = mask_block_idx.shape[-2:]
+    col = torch.arange(nk, device=mask_block_idx.device)
+    visited = None
+    for cnt, idx in ((full_block_cnt, full_block_idx), (mask_block_cnt, mask_block_idx)):
+        if cnt is None:
+            continue
+        used, at = torch.broadcast_tensors(col < cnt[..., None], idx.long())  # entries in front of the count
+        rows = torch.zeros(*at.shape[:-1], nk + 1, dtype=torch.bool, device=idx.device)
+        # (column nk swallows the tail and any index outside [0, nk), which names no block)
+        rows.scatter_(-1, torch.where(used & (at >= 0) & (at < nk), at, torch.full_like(at, nk)), True)
+        rows = rows[..., :nk]
+        visited = rows if visited is None else visited | rows
+    return block_sparse_from_mask(visited.transpose(-1, -2))[2:]
+
+
+def _check_key_lists(q, k, q_block_cnt, q_block_idx):
+    """Both or neither; dtype / device / shape as the forward's lists, with the roles of nm and nk swapped."""
+    if (q_block_cnt is None) != (q_block_idx is None):
+        raise ValueError("q_block_cnt and q_block_idx must be specified together")
+    if q_block_cnt is None:
+        return False
+    b, sq, h = q.shape[:3]
+    nm, nk = (sq + 127) // 128, (k.shape[1] + 127) // 128
+    for t, tname, tail in ((q_block_cnt, "q_block_cnt", (nk,)), (q_block_idx, "q_block_idx", (nk, nm))):
+        if t.dtype != torch.int32:
+            raise ValueError(f"{tname} must be int32")
+        if t.device != q.device:
+            raise ValueError(f"{tname} must be on the device of q")
+        if t.dim() != 2 + len(tail) or t.shape[0] not in (1, b) or t.shape[1] not in (1, h) or tuple(t.shape[2:]) != tail:
+            raise ValueError(f"{tname} must have shape ({b} or 1, {h} or 1, {', '.join(map(str, tail))}), got {tuple(t.shape)}")
+    return True
 
 
 def _flash_attn_fwd_block_sparse(q, k, v, softmax_scale, causal, window_size, learnable_sink, softcap, num_splits,
@@ -158,6 +200,17 @@ def _flash_attn_fwd(q, k, v, cu_seqlens_q=None, cu_seqlens_k=None, seqused_q=Non
                                    page_table, softmax_scale, causal, left, right, sink, softcap or 0.0, num_splits)
 
 
+def _flash_attn_bwd_block_sparse(dout, q, k, v, out, lse, softmax_scale, causal, window_size, softcap, learnable_sink, lists):
+    if q.shape[-1] > 128 or v.shape[-1] != q.shape[-1]:
+        raise NotImplementedError("block-sparse backward: head dims up to 128 with the same head dim for V "
+                                  f"(got {q.shape[-1]} / {v.shape[-1]})")
+    dout, q, k, v, out = [maybe_contiguous(t) for t in (dout, q, k, v, out)]
+    left, right = _window(window_size)
+    sink = learnable_sink.detach().contiguous() if learnable_sink is not None else None
+    return _lib.binding().cute_bwd_block_sparse(dout, q, k, v, out, lse, softmax_scale, causal, left, right, softcap or 0.0,
+                                                sink, *lists)
+
+
 def _flash_attn_bwd(dout, q, k, v, out, lse, cu_seqlens_q, cu_seqlens_k, softmax_scale, causal, window_size, softcap,
                     learnable_sink):
     dout, q, k, v, out = [maybe_contiguous(t) for t in (dout, q, k, v, out)]
@@ -175,9 +228,12 @@ class FlashAttnFunc(torch.autograd.Function):
     @staticmethod
     def forward(ctx, q, k, v, softmax_scale=None, causal=False, window_size=(None, None), learnable_sink=None, softcap=0.0,
                 num_splits=1, pack_gqa=None, mask_mod=None, full_block_cnt=None, full_block_idx=None, mask_block_cnt=None,
-                mask_block_idx=None):
+                mask_block_idx=None, q_block_cnt=None, q_block_idx=None):
         ctx.block_sparse = _check_block_sparse(mask_mod, full_block_cnt=full_block_cnt, full_block_idx=full_block_idx,
                                                mask_block_cnt=mask_block_cnt, mask_block_idx=mask_block_idx)
+        if not ctx.block_sparse and (q_block_cnt is not None or q_block_idx is not None):
+            raise ValueError("q_block_cnt / q_block_idx are only valid with mask_block_cnt / mask_block_idx")
+        ctx.key_lists = ctx.block_sparse and _check_key_lists(q, k, q_block_cnt, q_block_idx)
         if softmax_scale is None:
             softmax_scale = 1.0 / math.sqrt(q.shape[-1])
         if ctx.block_sparse:
@@ -186,21 +242,27 @@ class FlashAttnFunc(torch.autograd.Function):
         else:
             out, lse = _flash_attn_fwd(q, k, v, softmax_scale=softmax_scale, causal=causal, window_size=window_size,
                                        learnable_sink=learnable_sink, softcap=softcap, num_splits=num_splits)
-        ctx.save_for_backward(q, k, v, out, lse, learnable_sink)
+        lists = (full_block_cnt, full_block_idx, mask_block_cnt, mask_block_idx, q_block_cnt, q_block_idx) if ctx.key_lists else ()
+        ctx.save_for_backward(q, k, v, out, lse, learnable_sink, *lists)
         ctx.softmax_scale, ctx.causal, ctx.window_size, ctx.softcap = softmax_scale, causal, window_size, softcap
         ctx.mark_non_differentiable(lse)
         return out, lse
 
     @staticmethod
     def backward(ctx, dout, *args):
-        if ctx.block_sparse:  # (the reference returns the DENSE gradient here, flash_attn/cute/interface.py:1055-1069)
-            raise NotImplementedError("block-sparse backward")
-        q, k, v, out, lse, sink = ctx.saved_tensors
-        dq, dk, dv, dsink = _flash_attn_bwd(dout, q, k, v, out, lse, None, None, ctx.softmax_scale, ctx.causal,
-                                            ctx.window_size, ctx.softcap, sink)
+        # (the reference returns the DENSE gradient for a block-sparse forward, flash_attn/cute/interface.py:1055-1069)
+        if ctx.block_sparse and not ctx.key_lists:
+            raise NotImplementedError("block-sparse backward")  # needs q_block_cnt / q_block_idx (block_sparse_bwd_lists)
+        q, k, v, out, lse, sink = ctx.saved_tensors[:6]
+        if ctx.block_sparse:
+            dq, dk, dv, dsink = _flash_attn_bwd_block_sparse(dout, q, k, v, out, lse, ctx.softmax_scale, ctx.causal, ctx.window_size,
+                                                             ctx.softcap, sink, ctx.saved_tensors[6:])
+        else:
+            dq, dk, dv, dsink = _flash_attn_bwd(dout, q, k, v, out, lse, None, None, ctx.softmax_scale, ctx.causal,
+                                                ctx.window_size, ctx.softcap, sink)
         if sink is None or not ctx.needs_input_grad[6]:
             dsink = None
-        return (dq, dk, dv, None, None, None, dsink) + (None,) * 8
+        return (dq, dk, dv, None, None, None, dsink) + (None,) * 10
 
 
 class FlashAttnVarlenFunc(torch.autograd.Function):
@@ -237,7 +299,7 @@ class FlashAttnVarlenFunc(torch.autograd.Function):
 
 def flash_attn_func(q, k, v, softmax_scale=None, causal=False, window_size=(None, None), learnable_sink=None, softcap=0.0,
                     num_splits=1, pack_gqa=None, mask_mod=None, full_block_cnt=None, full_block_idx=None, mask_block_cnt=None,
-                    mask_block_idx=None):
+                    mask_block_idx=None, q_block_cnt=None, q_block_idx=None):
     """q (b, sq, h, d), k / v (b, sk, h_k, d[_v]) -> (out, lse (b, h, sq)).  learnable_sink: (h,) bf16 or fp32.  num_splits:
     1 = no split-KV, N > 1 = N parts, 0 = the library's heuristic.  pack_gqa is accepted and ignored; mask_mod must be None.
 
@@ -246,12 +308,19 @@ def flash_attn_func(q, k, v, softmax_scale=None, causal=False, window_size=(None
     (block_sparse_from_mask makes all four from a block mask).  Query block m attends to the first cnt[.., m] key blocks of
     idx[.., m, :] of both lists, and inside them to what causal / window_size allow; distinct in-range indices are the
     caller's duty.  Rows without a visible key give out = 0 and lse = +inf (the sink with learnable_sink).  Not with
-    num_splits > 1 or a V head dim above 256; forward only (the backward raises NotImplementedError).
+    num_splits > 1 or a V head dim above 256.
+    The backward of a block-sparse call needs the same pattern key-major: q_block_cnt (b | 1, h | 1, nk) and q_block_idx
+    (b | 1, h | 1, nk, nm), int32 -- key block n is visited by the first cnt[.., n] query blocks of idx[.., n, :], indexed by
+    the query head, one merged list (block_sparse_bwd_lists makes them from the four forward lists, once per pattern).  That
+    they name the same (query block, key block) pairs as the forward lists is the caller's duty.  dq walks the forward
+    lists, dk / dv the key-major ones, in list order: no atomics, equal lists give bit-equal gradients; learnable_sink gets
+    its gradient.  Without q_block_* the backward raises NotImplementedError("block-sparse backward"), and so it does
+    for a head dim above 128 or a V head dim that differs.
     Measured on one MI355X at b4 h16 s8192 d128 bf16 (profiles/block_sparse.jsonl): time is proportional to the listed blocks,
     all of them listed cost 1.46 x the plain dense call, so block sparsity pays below about 0.68 of the blocks (0.40 x the
     dense time at a quarter of them)."""
     return FlashAttnFunc.apply(q, k, v, softmax_scale, causal, window_size, learnable_sink, softcap, num_splits, pack_gqa,
-                               mask_mod, full_block_cnt, full_block_idx, mask_block_cnt, mask_block_idx)
+                               mask_mod, full_block_cnt, full_block_idx, mask_block_cnt, mask_block_idx, q_block_cnt, q_block_idx)
 
 
 def flash_attn_varlen_func(q, k, v, cu_seqlens_q=None, cu_seqlens_k=None, seqused_q=None, seqused_k=None, page_table=None,

@@ -129,6 +129,56 @@ int fa_sink_grad(const fa_sink_grad_params *params, void *stream);
 int fa_sink_grad_validate(const fa_sink_grad_params *params);
 uint32_t fa_sink_grad_params_size(void);
 
+/*
+ * Block-sparse backward: the gradient of fa_fwd_block_sparse (include/fa_fwd.h).  The function differentiated is the
+ * forward's: dense attention restricted to the visited 128 x 128 blocks and, inside them, to what is_causal /
+ * window_size_left / right (bottom-right aligned) and the sequence ends allow.  (The reference has no such backward: its
+ * cute surface returns the dense gradient for a block-sparse forward, flash_attn/cute/interface.py:1055-1069.)
+ * Three launches like fa_bwd, one producer per output element, no atomics, no workspace, bit-reproducible:
+ *   D      bwd_dot_kernel over all rows (softmax_d is written for every row: fa_sink_grad reads it);
+ *   dK/dV  one workgroup per 128-key block of a (batch, kv head).  It owns a key block and needs the query blocks that visit
+ *          it -- the transpose of the forward's lists, which the CALLER passes as key-major lists (a sparsity pattern is
+ *          normally fixed across layers and steps: built once, not in every call):
+ *            q_block_cnt  int32, logical shape (b, h, nk)        h = QUERY heads, as the forward's lists
+ *            q_block_idx  int32, logical shape (b, h, nk, nm)
+ *          read through element strides, stride 0 for a broadcast dimension.  Key block n of query head h is visited by the
+ *          first q_block_cnt[.., n] query blocks of q_block_idx[.., n, :].  One merged list: the full / mask split is a hint
+ *          the kernels ignore.  For every query head of the GQA group in ascending order the workgroup walks that list;
+ *   dQ     one workgroup per 128-row query block; it walks `fwd_lists` (the full list first) exactly as the forward does.
+ * That the key-major lists and the forward's lists describe the same set of (query block, key block) pairs is the caller's
+ * duty, as are distinct indices inside [0, nm) / [0, nk); the result of anything else is undefined, but no list content makes
+ * a kernel read or write out of bounds: counts are clamped to [0, nm] / [0, nk], and a listed pair that cannot hold a visible
+ * (row, key) -- an index outside the range, a tile past seqlen_q / seqlen_k or outside the causal / window range of the
+ * block -- is neither loaded nor computed.  The host never reads the lists.  The accumulation order is the list order, so
+ * equal lists give bit-equal gradients.
+ * Rows with LSE = +inf (no visible key, no sink) have P = 0: dq = 0 there, never NaN.  A key block nobody visits gets
+ * dk = dv = 0 written, a query block with both counts 0 gets dq = 0 written.  With a learnable sink nothing changes here (the
+ * LSE holds it); fa_sink_grad behind this call gives the sink's gradient.
+ * Accepted: fp16 / bf16, d <= 128 with d_v = d (0 or d), MHA / GQA / MQA, is_causal, both window sides, softcap, arbitrary
+ * strides.  FA_ERR_UNSUPPORTED, checked before anything the params may lack: cu_seqlens_*, ALiBi, dropout, d > 128, d_v set and
+ * != d, block_m / block_n other than 128 (in either list struct).  NULL or misaligned list pointers and negative strides
+ * return fa_fwd_block_sparse_validate's codes.
+ * fa_bwd_params is untouched (its size is pinned).  fa_bwd_plan_name of plain params means what it meant;
+ * fa_bwd_last_plan_name() answers for this call e.g. "bwd_dot LPR=16 | bs_bwd_dkdv D=128 | bs_bwd_dq D=128 SOFTCAP"
+ * (D = head-dim tile 64 / 128; a launch without work items has no segment).
+ */
+typedef struct fa_block_sparse_bwd_params {
+    uint32_t abi_version; /* FA_ABI_VERSION */
+    uint32_t struct_size; /* sizeof(fa_block_sparse_bwd_params) */
+    const int32_t *q_block_cnt; /* device pointers, both required */
+    const int32_t *q_block_idx;
+    /* element strides, >= 0: cnt (batch, head, n, unused = 0), idx (batch, head, n, m) */
+    int64_t q_cnt_stride[4], q_idx_stride[4];
+    int32_t block_m, block_n; /* 128, 128 */
+} fa_block_sparse_bwd_params;
+
+int fa_bwd_block_sparse(const fa_bwd_params *params, const fa_block_sparse_params *fwd_lists,
+                        const fa_block_sparse_bwd_params *key_lists, void *stream);
+/* Validation only; no device access. */
+int fa_bwd_block_sparse_validate(const fa_bwd_params *params, const fa_block_sparse_params *fwd_lists,
+                                 const fa_block_sparse_bwd_params *key_lists);
+uint32_t fa_block_sparse_bwd_params_size(void);
+
 #ifdef __cplusplus
 }
 #endif
