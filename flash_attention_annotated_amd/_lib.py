@@ -20,6 +20,7 @@ INCLUDE = os.path.join(os.path.dirname(_HERE), "include")
 FA_ABI_VERSION = 13
 FA_FLAG_FA3_WINDOW = 1
 FA_FLAG_SDMASK_SIGNED = 2
+FA_FLAG_PACK_GQA = 4
 FA_DTYPE_FP16, FA_DTYPE_BF16, FA_DTYPE_FP8_E4M3, FA_DTYPE_FP32 = 0, 1, 2, 3
 
 # every symbol include/fa_fwd.h declares (tests check the .so exports all of them)

@@ -10,6 +10,7 @@
 #include "fa_fwd_kernel_d256.h"
 #include "fa_fwd_kernel_qv.h"
 #include "fa_fwd_kernel_bs.h"
+#include "fa_fwd_kernel_pk.h"
 #include "fa_launch.h"
 
 #include <algorithm>
@@ -437,6 +438,15 @@ inline bool qv_route(const fa_fwd_params *p) { return p->qv || (qv_shape(p) && (
 inline bool left_window(const fa_fwd_params *p) {
     return p->window_size_left >= 0 && ((p->flags & FA_FLAG_FA3_WINDOW) || p->window_size_left < p->seqlen_k);
 }
+// FA_FLAG_PACK_GQA is a hint: the pk kernel (fa_fwd_kernel_pk.h) honours it for GQA / MQA calls of 16-bit types at head dims
+// <= 128 without ALiBi, dropout, attention_chunk, a V head dim of its own or qv; every other call is planned as without it.
+// (The kernel counts packed rows in 32 bits.)
+inline bool pk_route(const fa_fwd_params *p) {
+    if (!(p->flags & FA_FLAG_PACK_GQA) || p->h_k <= 0 || p->h % p->h_k != 0 || p->h / p->h_k <= 1) return false;
+    if (p->dtype == FA_DTYPE_FP8_E4M3 || p->d > 128 || p->alibi_slopes || p->p_dropout > 0.f || generic_only(p)) return false;
+    if ((int64_t)p->seqlen_q * (p->h / p->h_k) > 0x7fffffff) return false;
+    return !qv_route(p);
+}
 // 1 / (1 - p_dropout) as the kernels get it: the dropout instantiations run exactly when it is not 1
 inline float rp_dropout(const fa_fwd_params *p) { return p->p_dropout > 0.f ? 1.f / (1.f - p->p_dropout) : 1.f; }
 
@@ -526,7 +536,7 @@ inline int64_t row_blocks_bound(const fa_fwd_params *p, int64_t bm, int64_t rows
     const int64_t seqs = std::min<int64_t>(p->b, p->total_q);
     return std::min(seqs * per_seq, p->total_q * rows_per_query / bm + seqs);
 }
-SplitPlan split_plan(const fa_fwd_params *p, int variant) {
+SplitPlan split_plan(const fa_fwd_params *p, int variant, bool pk = false) {
     SplitPlan sp{1, 0, 0, 0};
     if (p->cu_seqlens_k || p->dtype == FA_DTYPE_FP8_E4M3 || p->seqlen_q <= 0 || p->seqlen_k <= 0) return sp;
     if (p->cu_seqlens_q && p->total_q <= 0) return sp;
@@ -536,7 +546,8 @@ SplitPlan split_plan(const fa_fwd_params *p, int variant) {
     const int n_blocks = (p->seqlen_k + 63) / 64;
     if (n == 0) {
         const int bm = block_m_of(variant, wide_dim(p));
-        const int64_t tiles = row_blocks_bound(p, bm) * p->h;
+        // (the pk kernel: blocks of packed rows per kv head, in the 4-wave shape -- the caller passes variant 2)
+        const int64_t tiles = pk ? row_blocks_bound(p, bm, p->h / p->h_k) * p->h_k : row_blocks_bound(p, bm) * p->h;
         // two workgroups of the 4-wave shape fit a CU: aim at ~4 per CU there, ~2 per CU for the 256-row kernel
         const int64_t cap = (variant == 2) ? 512 : 128, target = (variant == 2) ? 1024 : 512;
         n = 1;
@@ -580,7 +591,7 @@ SplitPlan split_plan_qv(const fa_fwd_params *p) {
     return sp;
 }
 
-enum class Family { fp8, qv, w64, d256, generic };  // fwd_kernel_fp8, fwd_kernel_qv, fwd_kernel_w64, fwd_kernel_d256, fwd_kernel
+enum class Family { fp8, qv, w64, d256, generic, pk };  // fwd_kernel_fp8, fwd_kernel_qv, fwd_kernel_w64, fwd_kernel_d256, fwd_kernel, pk_fwd_kernel
 
 struct FwdPlan {
     Family family;
@@ -590,7 +601,7 @@ struct FwdPlan {
     bool softcap, alibi, dropout, extra, persist;  // template forms (alibi: fwd_kernel_d256 only)
     int block_m;     // query rows per workgroup
     int32_t num_m_blocks;
-    int64_t tiles, unit_tiles, whole_slots, grid;  // scheduling of the row blocks over the XCDs (tile_of_wg)
+    int64_t tiles, unit_tiles, whole_slots, grid;  // scheduling of the row blocks over the XCDs (tile_of_wg; pk: grid holds the splits too)
     int status;      // FA_ERR_BAD_SHAPE when the grid does not fit 31 bits
     bool nothing;    // no query or no key: no split, no fp8 expansion, no S_dmask pass
     SplitPlan split;
@@ -657,12 +668,30 @@ FwdPlan plan_fwd(const fa_fwd_params *p, int num_cus) {
     pl.status = FA_OK;
     const bool fp8 = p->dtype == FA_DTYPE_FP8_E4M3, native = fp8_native(p);
     const bool softcap = p->softcap > 0.f, alibi = p->alibi_slopes != nullptr, dropout = rp_dropout(p) != 1.f;
-    const int variant = native ? 0 : effective_variant(p);  // (fp8 native: one shape, 4 waves x 64 rows)
+    const bool pk = pk_route(p);
+    const int variant = native ? 0 : pk ? 2 : effective_variant(p);  // (fp8 native: one shape, 4 waves x 64 rows; pk: 4 x 32)
     pl.nothing = p->seqlen_q == 0 || p->seqlen_k == 0 || (p->cu_seqlens_q && p->total_q == 0);
     pl.fp8_expand = fp8 && !native;
     if (fp8) pl.fp8 = fp8_plan(p);
-    pl.split = pl.nothing ? SplitPlan{1, 0, 0, 0} : qv ? split_plan_qv(p) : split_plan(p, variant);
+    pl.split = pl.nothing ? SplitPlan{1, 0, 0, 0} : qv ? split_plan_qv(p) : split_plan(p, variant, pk);
     pl.workspace = fp8 ? (native ? 0 : pl.fp8.total) : pl.split.total;
+
+    if (pk) {
+        // pk_fwd_kernel: blocks of PK_BLOCK_M packed rows (query row x head of the GQA group) per (batch, kv head, split) group;
+        // the groups are dealt over the 8 XCDs, the blocks of a group stay on one (fwd_kernel_qv's scheduling)
+        pl.family = Family::pk;
+        pl.d = pl.deff = head_dim_tile(p->d);
+        pl.waves = fa::PK_NWAVES;
+        pl.softcap = softcap;
+        pl.block_m = fa::PK_BLOCK_M;
+        const int64_t pblocks = ((int64_t)p->seqlen_q * (p->h / p->h_k) + fa::PK_BLOCK_M - 1) / fa::PK_BLOCK_M;
+        const int64_t groups = (int64_t)p->b * p->h_k * pl.split.splits;
+        pl.tiles = pblocks * p->h_k * p->b;
+        pl.grid = (groups + 7) / 8 * 8 * pblocks;
+        if (pblocks > 0x7fffffff || groups > 0x7fffffff || pl.grid > 0x7fffffff) pl.status = FA_ERR_BAD_SHAPE;
+        pl.num_m_blocks = pl.status == FA_OK ? (int32_t)pblocks : 0;
+        return pl;
+    }
 
     // softcap or ALiBi at head dims <= 128 (measured b4 s4096: softcap d128 471, d64 322, ALiBi 231 / 182 TFLOP/s through the C++
     // paths of the 256-row kernel): the generated loops that cap / bias scores exist for the 32-row-per-wave shape only ->
@@ -735,7 +764,7 @@ FwdPlan plan_fwd(const fa_fwd_params *p, int num_cus) {
 const char *plan_text(const FwdPlan &pl, char (&name)[160]) {
     if (pl.status != FA_OK) return nullptr;
     static const char *const kernels[] = {"fwd_kernel_fp8 D=", "fwd_kernel_qv DVT=", "fwd_kernel_w64 D=", "fwd_kernel_d256 W=",
-                                          "fwd_kernel D="};
+                                          "fwd_kernel D=", "pk_fwd_kernel D="};
     const bool by_width = pl.family == Family::qv || pl.family == Family::d256;
     int n = snprintf(name, sizeof(name), "%s%d", kernels[static_cast<int>(pl.family)], by_width ? pl.deff : pl.d);
     if (pl.family == Family::w64) n += snprintf(name + n, sizeof(name) - n, " DEFF=%d", pl.deff);
@@ -933,9 +962,26 @@ int launch_qv(const FwdPlan &pl, const fa_fwd_params *p, const fa::KParams &kp, 
     return pl.softcap ? launch_qv_form<T, 512, true>(qa, grid, stream) : launch_qv_form<T, 512, false>(qa, grid, stream);
 }
 
+// the pk kernel (fa_fwd_kernel_pk.h): head-dim tile 64 or 128, plain or softcap
+template <typename T, int D>
+int launch_pk_form(const FwdPlan &pl, const fa::PkParams &pa, hipStream_t stream) {
+    constexpr int smem = fa::smem_bytes<D, fa::PK_NWAVES>(), NT = fa::PK_NWAVES * 64;
+    return pl.softcap ? fa::launch_kernel<fa::pk_fwd_kernel<T, D, true>>(smem, pl.grid, NT, stream, pa)
+                      : fa::launch_kernel<fa::pk_fwd_kernel<T, D, false>>(smem, pl.grid, NT, stream, pa);
+}
+template <typename T>
+int launch_pk(const FwdPlan &pl, const fa::KParams &kp, hipStream_t stream) {
+    fa::PkParams pa{};
+    pa.p = kp;
+    pa.num_pblocks = pl.num_m_blocks;
+    pa.num_groups = kp.b * kp.h_k * kp.num_splits;
+    return pl.d == 64 ? launch_pk_form<T, 64>(pl, pa, stream) : launch_pk_form<T, 128>(pl, pa, stream);
+}
+
 template <typename T>
 int launch_plan(const FwdPlan &pl, const fa_fwd_params *p, const fa::KParams &kp, hipStream_t stream) {
     switch (pl.family) {
+        case Family::pk: return launch_pk<T>(pl, kp, stream);
         case Family::fp8: return fa::launch_kernel<fa::fwd_kernel_fp8>(fa::smem_bytes_fp8(), kp.grid, 256, stream, kp);
         case Family::qv: return launch_qv<T>(pl, p, kp, stream);
         case Family::w64: return pl.d == 64 ? launch_w64_form<T, 64>(pl, kp, stream) : launch_w64_form<T, 128>(pl, kp, stream);

@@ -1,0 +1,394 @@
+// fa_fwd_kernel_pk.h — gfx950 forward with the GQA group packed into the rows of a tile (PackGQA).
+//
+// Role of the reference's PackGQA (hopper/pack_gqa.h:18-255; requested through `pack_gqa`, FA_FLAG_PACK_GQA here): the
+// g = h / h_k query heads of one kv head share one pass over that head's K/V.  A workgroup owns a block of PACKED rows of one
+// (batch, kv head[, split]): packed row pr is query row pr / g of head kv_head * g + pr % g, prows = seqlen_q(batch) * g.
+// Short query ranges (a verify step of a few tokens, the decode rows of a mixed step, short ragged prompts) fill a tile with
+// g times as many valid rows, and K/V are streamed and multiplied once per kv head instead of once per query head.
+//
+// The tile loop is fwd_kernel's 4-wave x 32-row shape (fa_fwd_kernel.h: lane owns a row, S^T = K.Q^T, O^T = V^T.P^T, 64-key
+// tiles double-buffered in LDS, two workgroups per CU); what differs is everything that reads the row mapping:
+//   * work item: (batch, kv head, split) groups dealt round-robin over the 8 XCDs, the row blocks of one group on one XCD
+//     (fwd_kernel_qv's decode);
+//   * Q load: per-lane address from (query row, head);
+//   * key range of a block / tile classification of a wave: from the first and last QUERY row in it;
+//   * element masks: the lane's query row, never the packed row;
+//   * sink logit: the lane's own head; load_scales stays per kv head;
+//   * epilogue: O and LSE address (query row, head).  Split partials use the layouts of fwd_kernel, so the merge is shared.
+// Not here (the plan keeps such calls on the other kernels): fp8, ALiBi, dropout, attention_chunk, a V head dim of its own,
+// qv, head dims above 128.
+#pragma once
+
+#include "fa_fwd_kernel.h"
+
+namespace fa {
+
+constexpr int PK_NWAVES = 4;
+constexpr int PK_BLOCK_M = PK_NWAVES * 32;  // packed rows per workgroup
+
+struct PkParams {
+    KParams p;
+    int32_t num_pblocks;  // PK_BLOCK_M-row blocks of packed rows per (batch, kv head): ceil(seqlen_q * g / PK_BLOCK_M)
+    int32_t num_groups;   // b * h_k * splits: (batch, kv head, split) work groups
+};
+
+template <typename T, int D, bool SOFTCAP>
+__global__ __launch_bounds__(PK_NWAVES * 64, 2) void pk_fwd_kernel(const PkParams pa) {
+    const KParams &p = pa.p;
+    constexpr int NT = PK_NWAVES * 64;
+    constexpr int KSTEPS = D / 16;
+    constexpr int DBLOCKS = D / 32;
+    constexpr int CH_PER_ROW = D / 8;
+    constexpr int TILE_BYTES = BLOCK_N * D * 2;
+    constexpr int CHUNKS = BLOCK_N * CH_PER_ROW;
+    constexpr int LD_PER_THREAD = CHUNKS / NT;
+    static_assert(CHUNKS % NT == 0, "tile must divide over the workgroup");
+    constexpr int O_ROW_BYTES = D * 2 + 16;    // padded epilogue row; the padding carries the row's O offset
+
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    // [K0 | K1 | V0 | V1]; the epilogue reuses the whole region as PK_NWAVES x [32][O_ROW_BYTES]
+
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int r = lane & 31;
+    const int hh = lane >> 5;
+
+    // ---- work item (fwd_kernel_qv's decode) --------------------------------------------------------------------------------
+    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
+    const int group = (slot / pa.num_pblocks) * 8 + xcd, pb = slot % pa.num_pblocks;
+    if (group >= pa.num_groups) return;  // whole workgroup (padding)
+    const int splits = p.num_splits > 1 ? p.num_splits : 1;
+    const int unit = group / splits, split = group % splits;
+    const int batch = unit / p.h_k, kv_head = unit % p.h_k;
+    const int g = p.h_ratio;
+
+    // ---- sequence bookkeeping ----------------------------------------------------------------------------------------------
+    int sq, sk, q0 = 0;
+    int64_t k_base, v_base;
+    if (p.cu_seqlens_q) {
+        q0 = p.cu_seqlens_q[batch];
+        sq = p.seqused_q ? p.seqused_q[batch] : p.cu_seqlens_q[batch + 1] - q0;
+    } else {
+        sq = p.seqused_q ? p.seqused_q[batch] : p.seqlen_q;
+    }
+    if (p.cu_seqlens_k) {
+        const int k0 = p.cu_seqlens_k[batch];
+        sk = p.seqused_k ? p.seqused_k[batch] : p.cu_seqlens_k[batch + 1] - k0;
+        k_base = (int64_t)k0 * p.k_row_stride;
+        v_base = (int64_t)k0 * p.v_row_stride;
+    } else {
+        sk = p.seqused_k ? p.seqused_k[batch] : p.seqlen_k;
+        const int kv_batch = p.kv_batch_idx ? p.kv_batch_idx[batch] : batch;
+        k_base = (int64_t)kv_batch * p.k_batch_stride;
+        v_base = (int64_t)kv_batch * p.v_batch_stride;
+    }
+    const int prows = sq * g;  // packed rows of this (batch, kv head); the host keeps seqlen_q * g below 2^31
+    const int pr_lo = pb * PK_BLOCK_M;
+    if (pr_lo >= prows) return;  // whole workgroup: nothing to do (varlen / padded grid)
+    if (p.leftpad_k) {
+        const int lp = p.leftpad_k[batch];
+        sk = max(sk - lp, 0);
+        k_base += (int64_t)lp * p.k_row_stride;
+        v_base += (int64_t)lp * p.v_row_stride;
+    }
+    if (p.block_table) k_base = v_base = 0;  // paged: the page supplies the batch offset
+    const int32_t *pages = p.block_table ? p.block_table + (int64_t)batch * p.bt_bs : nullptr;
+    const T *kp = (const T *)p.k + k_base + (int64_t)kv_head * p.k_head_stride;
+    const T *vp = (const T *)p.v + v_base + (int64_t)kv_head * p.v_head_stride;
+    const Scales sc = load_scales(p, batch, kv_head);
+
+    // ---- the wave's packed rows, the lane's query row and head -----------------------------------------------------------------
+    const int wpr = pr_lo + wave * 32;            // first packed row of this wave
+    const bool wave_active = wpr < prows;
+    const int wq_lo = wpr / g;                    // first and last query row of the wave (inclusive)
+    const int wq_hi = min(prows - 1, wpr + 31) / g;
+    const int pr = wpr + r;
+    const bool row_ok = pr < prows;
+    const int prc = min(pr, prows - 1);
+    const int my_row = prc / g;                   // the query row this lane owns (masks)
+    const int head = kv_head * g + (prc - my_row * g);
+    const int64_t row_g = (int64_t)q0 + my_row;   // row of q / o (ragged: in the whole batch)
+    const int64_t bq = p.cu_seqlens_q ? 0 : batch;
+
+    // ---- key range of this block: from its first and last query row --------------------------------------------------------
+    const int shift = sk - sq;  // bottom-right aligned masks
+    const int qr_lo = pr_lo / g, qr_hi = min(prows - 1, pr_lo + PK_BLOCK_M - 1) / g;
+    int key_hi = sk, key_lo = 0;
+    if (p.window_right >= 0) key_hi = min(sk, qr_hi + 1 + shift + p.window_right);
+    if (p.window_left >= 0) key_lo = max(0, qr_lo + shift - p.window_left);
+    int n_min = key_lo / BLOCK_N;
+    int n_max = key_hi > 0 ? (key_hi + BLOCK_N - 1) / BLOCK_N : 0;
+    split_range(p, split, n_min, n_max);
+
+    // ---- Q fragments: B operand of S^T = K.Q^T; lane (r,hh) holds Q[row r][16ks + 8hh .. +8] (branch-free, zeroed by selects)
+    u32x4 qf[KSTEPS];
+    {
+        const T *qr = (const T *)p.q + bq * p.q_batch_stride + row_g * p.q_row_stride + (int64_t)head * p.q_head_stride;
+#pragma unroll
+        for (int ks = 0; ks < KSTEPS; ++ks) {
+            const int d0 = ks * 16 + hh * 8;
+            qf[ks] = *(const u32x4 *)(qr + (d0 < p.d ? d0 : 0));
+        }
+        const u32x4 z4 = {0, 0, 0, 0};
+#pragma unroll
+        for (int ks = 0; ks < KSTEPS; ++ks) qf[ks] = (ks * 16 + hh * 8 < p.d && row_ok) ? qf[ks] : z4;
+    }
+
+    f32x16 o_acc[DBLOCKS];
+#pragma unroll
+    for (int db = 0; db < DBLOCKS; ++db)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) o_acc[db][i] = 0.f;
+    float m_run = -INFINITY;  // running row max (unscaled scores), same in both lane halves
+    float l_run = 0.f;        // running row sum, PARTIAL per lane half (combined in the epilogue)
+
+    // ---- K/V staging (fwd_kernel's: clamped rows / chunks, the duplicates are masked or meet zero Q columns) --------------
+    u32x4 kreg[LD_PER_THREAD], vreg[LD_PER_THREAD];
+    static_assert(NT % CH_PER_ROW == 0, "a pass of the workgroup covers whole rows");
+    constexpr int ROWS_PER_PASS = NT / CH_PER_ROW;
+    const int ld_row0 = tid / CH_PER_ROW;
+    const int ld_col0 = ((tid % CH_PER_ROW) * 8 < p.d) ? (tid % CH_PER_ROW) * 8 : 0;
+    const int k_rs = (int)p.k_row_stride, v_rs = (int)p.v_row_stride;  // host guarantees 64 * stride < 2^31
+    auto load_tile = [&](int n) {
+        const int k0 = n * BLOCK_N;
+        const T *kt = kp + (int64_t)k0 * p.k_row_stride;
+        const T *vt = vp + (int64_t)k0 * p.v_row_stride;
+        const int last = sk - 1 - k0;                     // >= 0 for every tile in [n_min, n_max)
+        if (pages) {
+            if (p.page_size % BLOCK_N == 0) {  // a 64-key tile lies inside one page
+                const int page = pages[k0 / p.page_size], in_page = k0 % p.page_size;
+                kt = kp + (int64_t)page * p.k_batch_stride + (int64_t)in_page * p.k_row_stride;
+                vt = vp + (int64_t)page * p.v_batch_stride + (int64_t)in_page * p.v_row_stride;
+            } else {  // any other page size: the page is looked up per row
+#pragma unroll
+                for (int i = 0; i < LD_PER_THREAD; ++i) {
+                    const int row = k0 + min(ld_row0 + i * ROWS_PER_PASS, last);
+                    const int pi = row / p.page_size;
+                    const int64_t page = pages[pi];
+                    const int in_page = row - pi * p.page_size;
+                    kreg[i] = *(const u32x4 *)(kp + page * p.k_batch_stride + (int64_t)in_page * p.k_row_stride + ld_col0);
+                    vreg[i] = *(const u32x4 *)(vp + page * p.v_batch_stride + (int64_t)in_page * p.v_row_stride + ld_col0);
+                }
+                return;
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < LD_PER_THREAD; ++i) {
+            const int row = min(ld_row0 + i * ROWS_PER_PASS, last);
+            kreg[i] = *(const u32x4 *)(kt + (uint32_t)(row * k_rs + ld_col0));
+            vreg[i] = *(const u32x4 *)(vt + (uint32_t)(row * v_rs + ld_col0));
+        }
+    };
+    auto store_tile = [&](int buf) {
+#pragma unroll
+        for (int i = 0; i < LD_PER_THREAD; ++i) {
+            const int c = tid + i * NT;
+            const int off = lds_off<D>(c / CH_PER_ROW, c % CH_PER_ROW);
+            *(u32x4 *)(smem + buf * TILE_BYTES + off) = kreg[i];
+            *(u32x4 *)(smem + (2 + buf) * TILE_BYTES + off) = vreg[i];
+        }
+    };
+
+    // lane-constant pieces of the LDS read addresses (fa_fwd_kernel.h)
+    const int i16 = lane & 15;
+    const int g1 = (lane >> 4) & 1;
+    const int kbase = lds_off<D>(r, hh);
+    const int vbase = lds_off<D>(4 * hh + (i16 >> 2), 2 * g1 + ((i16 >> 1) & 1)) + 8 * (i16 & 1);
+
+    if (n_min < n_max) {
+        load_tile(n_min);
+        store_tile(0);
+    }
+    __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): Q retired here, not in front of the first MFMA of every tile
+    __syncthreads();
+
+    for (int n = n_min; n < n_max; ++n) {
+        const int cur = (n - n_min) & 1;
+        const bool has_next = (n + 1 < n_max);
+        if (has_next) load_tile(n + 1);
+
+        const int k0 = n * BLOCK_N;
+        // wave-uniform tile classification from the wave's first and last query row
+        bool skip = !wave_active;
+        bool need_mask = (k0 + BLOCK_N > sk);
+        if (p.window_right >= 0) {
+            skip = skip || (k0 > wq_hi + shift + p.window_right);
+            need_mask = need_mask || (k0 + BLOCK_N - 1 > wq_lo + shift + p.window_right);
+        }
+        if (p.window_left >= 0) {
+            skip = skip || (k0 + BLOCK_N - 1 < wq_lo + shift - p.window_left);
+            need_mask = need_mask || (k0 < wq_hi + shift - p.window_left);
+        }
+
+        if (!skip) {
+            const char *kbuf = smem + cur * TILE_BYTES;
+            const char *vbuf = smem + (2 + cur) * TILE_BYTES;
+
+            // ---- S^T = K.Q^T : two 32-key blocks --------------------------------------------------------------------------
+            f32x16 s[2];
+#pragma unroll
+            for (int i = 0; i < 16; ++i) { s[0][i] = 0.f; s[1][i] = 0.f; }
+#pragma unroll
+            for (int ks = 0; ks < KSTEPS; ++ks) {
+                const int off = kbase ^ (32 * ks);  // = lds_off<D>(r, 2 ks + hh)
+                const u32x4 kf0 = *(const u32x4 *)(kbuf + off);
+                const u32x4 kf1 = *(const u32x4 *)(kbuf + off + 32 * D * 2);
+                s[0] = Elem<T>::mma(kf0, qf[ks], s[0]);
+                s[1] = Elem<T>::mma(kf1, qf[ks], s[1]);
+            }
+
+            if constexpr (SOFTCAP) {
+#pragma unroll
+                for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+                    for (int i = 0; i < 16; ++i) s[kb][i] = fast_tanh(s[kb][i] * sc.softcap_pre);
+            }
+
+            // ---- mask (boundary tiles only): the lane's QUERY row ----------------------------------------------------------
+            if (need_mask) {
+                int lim_hi = sk;  // exclusive
+                int lim_lo = 0;   // inclusive
+                if (p.window_right >= 0) lim_hi = min(sk, my_row + shift + p.window_right + 1);
+                if (p.window_left >= 0) lim_lo = max(0, my_row + shift - p.window_left);
+#pragma unroll
+                for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+                    for (int i = 0; i < 16; ++i) {
+                        const int key = k0 + kb * 32 + (i & 3) + 8 * (i >> 2) + 4 * hh;
+                        if (key >= lim_hi || key < lim_lo) s[kb][i] = -INFINITY;
+                    }
+            }
+
+            // ---- online softmax (per lane = per packed row) ---------------------------------------------------------------
+            float mx = max3(s[0][0], s[1][0], m_run);
+#pragma unroll
+            for (int i = 1; i < 16; ++i) mx = max3(mx, s[0][i], s[1][i]);
+            const float m_new = half_swap_max(mx);  // >= m_run (m_run is identical in both halves)
+            const float m_use = (m_new == -INFINITY) ? 0.f : m_new;  // fully masked so far
+            const float mc = m_use * sc.scale_log2;
+            if (__any(m_new > m_run)) {  // wave-uniform; bit-identical to always rescaling
+                const float alpha = __builtin_amdgcn_exp2f(m_run * sc.scale_log2 - mc);
+                l_run *= alpha;
+#pragma unroll
+                for (int db = 0; db < DBLOCKS; ++db)
+#pragma unroll
+                    for (int i = 0; i < 16; ++i) o_acc[db][i] *= alpha;
+            }
+            m_run = m_new;
+            float psum = 0.f;
+#pragma unroll
+            for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+                for (int i = 0; i < 16; ++i) {
+                    const float pv = __builtin_amdgcn_exp2f(s[kb][i] * sc.scale_log2 - mc);
+                    s[kb][i] = pv;
+                    psum += pv;
+                }
+            l_run += psum;
+
+            // ---- P^T fragments: accumulator registers ARE the B operand of O^T += V^T.P^T ------------------------------------
+            u32x4 pf[4];
+#pragma unroll
+            for (int st = 0; st < 4; ++st) {
+                const int kb = st >> 1, b8 = (st & 1) * 8;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) pf[st][j] = Elem<T>::pack2(s[kb][b8 + 2 * j], s[kb][b8 + 2 * j + 1]);
+            }
+
+            // ---- O^T += V^T.P^T -------------------------------------------------------------------------------------------
+#pragma unroll
+            for (int db = 0; db < DBLOCKS; ++db) {
+#pragma unroll
+                for (int st = 0; st < 4; ++st) {
+                    u32x4 vf;
+#pragma unroll
+                    for (int j2 = 0; j2 < 2; ++j2) {
+                        const int off = (vbase ^ (64 * db + 32 * j2)) + (16 * st + 8 * j2) * (D * 2);
+                        const s16x4 t = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
+                            (__attribute__((address_space(3))) s16x4 *)(vbuf + off));
+                        const u32x2 t2 = __builtin_bit_cast(u32x2, t);
+                        vf[2 * j2] = t2[0];
+                        vf[2 * j2 + 1] = t2[1];
+                    }
+                    o_acc[db] = Elem<T>::mma(vf, pf[st], o_acc[db]);
+                }
+            }
+        }
+
+        if (has_next) store_tile(cur ^ 1);
+        __syncthreads();
+    }
+
+    // ---- epilogue: normalise, LSE, O^T regs -> LDS -> 16-byte stores of (query row, head) rows -----------------------------
+    // (the loop's last barrier has retired every K/V read, so the region can be reused)
+    const float l_tot = half_swap_sum(l_run);
+    const bool empty = (l_tot == 0.f) || (l_tot != l_tot);
+    float inv = empty ? 1.f : 1.f / l_tot;
+    float lse_row = empty ? INFINITY : m_run * sc.scale + __logf(l_tot);  // +inf for rows with no valid key, as fwd_kernel
+    if (p.sink)  // the lane's own head
+        sink_finalize(row_ok ? load_sink(p, head, my_row) : -INFINITY, m_run * sc.scale, l_tot, empty, inv, lse_row);
+    const int64_t o_off = bq * p.o_batch_stride + row_g * p.o_row_stride + (int64_t)head * p.o_head_stride;
+    if (wave_active) {
+        if (hh == 0 && row_ok) {
+            const int64_t li = p.cu_seqlens_q ? (int64_t)head * p.total_q + row_g : ((int64_t)batch * p.h + head) * p.seqlen_q + my_row;
+            p.lse[li + split * p.lse_split_stride] = lse_row;
+        }
+        if (p.num_splits > 1) {
+            // split-KV partial: fp32 in the caller's workspace, straight from the accumulators (fwd_kernel's layout)
+            float *opf = (float *)p.o + split * p.o_split_stride + o_off;
+            if (row_ok) {
+#pragma unroll
+                for (int db = 0; db < DBLOCKS; ++db)
+#pragma unroll
+                    for (int g4 = 0; g4 < 4; ++g4) {
+                        const int col = db * 32 + 8 * g4 + 4 * hh;
+                        if (col < p.d)
+                            *(float4 *)(opf + col) = make_float4(o_acc[db][4 * g4] * inv, o_acc[db][4 * g4 + 1] * inv,
+                                                                 o_acc[db][4 * g4 + 2] * inv, o_acc[db][4 * g4 + 3] * inv);
+                    }
+            }
+        } else {
+            char *obuf = smem + wave * (32 * O_ROW_BYTES);
+#pragma unroll
+            for (int db = 0; db < DBLOCKS; ++db)
+#pragma unroll
+                for (int g4 = 0; g4 < 4; ++g4) {
+                    u32x2 w;
+                    w[0] = Elem<T>::pack2(o_acc[db][4 * g4] * inv, o_acc[db][4 * g4 + 1] * inv);
+                    w[1] = Elem<T>::pack2(o_acc[db][4 * g4 + 2] * inv, o_acc[db][4 * g4 + 3] * inv);
+                    *(u32x2 *)(obuf + r * O_ROW_BYTES + (db * 32 + 8 * g4 + 4 * hh) * 2) = w;
+                }
+            // the row's destination rides in the padding of its LDS row: the lanes that store a row are not the lane that owns it
+            if (hh == 0) {
+                *(int64_t *)(obuf + r * O_ROW_BYTES + D * 2) = o_off;
+                *(int32_t *)(obuf + r * O_ROW_BYTES + D * 2 + 8) = row_ok ? 1 : 0;
+            }
+        }
+    }
+    if (p.num_splits > 1) return;  // (uniform over the launch: no wave is left waiting at the barrier below)
+    __syncthreads();
+    if (wave_active) {
+        const char *obuf = smem + wave * (32 * O_ROW_BYTES);
+        // (LDS reads outside the predicate: all of them are issued before the first store)
+        constexpr int NCH = (32 * CH_PER_ROW) / 64;
+        u32x4 val[NCH];
+        int64_t dst[NCH];
+        int32_t ok[NCH];
+#pragma unroll
+        for (int i = 0; i < NCH; ++i) {
+            const int c = lane + i * 64;
+            const char *row = obuf + (c / CH_PER_ROW) * O_ROW_BYTES;
+            val[i] = *(const u32x4 *)(row + (c % CH_PER_ROW) * 16);
+            dst[i] = *(const int64_t *)(row + D * 2);
+            ok[i] = *(const int32_t *)(row + D * 2 + 8);
+        }
+#pragma unroll
+        for (int i = 0; i < NCH; ++i) {
+            const int ch = (lane + i * 64) % CH_PER_ROW;
+            if (ok[i] && ch * 8 < p.d) *(u32x4 *)((T *)p.o + dst[i] + ch * 8) = val[i];
+        }
+    }
+}
+
+}  // namespace fa

@@ -129,6 +129,8 @@ struct FwdArgs {
     // (1, 0), or (ngroups, 1) when the decode route has folded the GQA group into the rows (include/fa_fwd.h)
     OptTensor sink;
     int sink_head_stride = 1, sink_row_stride = 0;
+    // FA3 / cute pack_gqa = True: FA_FLAG_PACK_GQA, a hint the plan honours where the pk kernel serves the call (include/fa_fwd.h)
+    bool pack_gqa = false;
 };
 
 // torch tensors -> fa_fwd_params -> fa_fwd on torch's current stream (q/k/v/out: last stride 1, aligned())
@@ -187,6 +189,7 @@ void launch_fwd(const Tensor &q, const Tensor &k, const Tensor &v, const Tensor 
     p.rng_state = static_cast<const uint64_t *>(ptr(a.rng_state));
     p.s_dmask = static_cast<uint8_t *>(ptr(a.s_dmask));
     p.flags = a.fa3_window ? FA_FLAG_FA3_WINDOW : 0;  // a missing window side is unbounded (hopper/flash_api.cpp:152-153)
+    if (a.pack_gqa) p.flags |= FA_FLAG_PACK_GQA;
     if (a.s_dmask.has_value() && a.s_dmask_block_n > 0) {
         p.flags |= FA_FLAG_SDMASK_SIGNED;
         p.s_dmask_rows = (int32_t)a.s_dmask->size(-2);
@@ -711,7 +714,7 @@ std::vector<Tensor> fwd_kvcache_core(Tensor q, const Tensor &kcache, const Tenso
                                      OptTensor alibi_slopes_, OptTensor out_, const double softmax_scale, bool is_causal,
                                      int64_t window_size_left, int64_t window_size_right, const double softcap,
                                      bool is_rotary_interleaved, int64_t num_splits, int64_t page_multiple,
-                                     OptTensor seqlens_rotary_, OptTensor qv_, OptTensor sink_) {
+                                     OptTensor seqlens_rotary_, OptTensor qv_, OptTensor sink_, bool pack_gqa = false) {
     const auto q_dtype = q.scalar_type();
     TORCH_CHECK(q_dtype == at::kHalf || q_dtype == at::kBFloat16, "FlashAttention only support fp16 and bf16 data type");
     TORCH_CHECK(kcache.scalar_type() == q_dtype, "query and key must have the same dtype");
@@ -855,6 +858,7 @@ std::vector<Tensor> fwd_kvcache_core(Tensor q, const Tensor &kcache, const Tenso
         a.causal = is_causal; a.window_left = window_size_left; a.window_right = window_size_right; a.softcap = softcap;
         a.seqused_k = seqused; a.alibi = alibi; a.kv_batch_idx = cache_batch_idx_; a.block_table = block_table_;
         a.num_splits = (int)num_splits; a.leftpad_k = leftpad_k_;
+        a.pack_gqa = pack_gqa;  // (behind the single-token GQA swap h == h_k: the hint has nothing to pack there)
         if (qv_.has_value()) a.qv = aligned_or_copy(*qv_);
         if (sink_.has_value()) {
             a.sink = sink_;
@@ -937,7 +941,7 @@ std::tuple<Tensor, Tensor> fwd_kvcache_ragged(const Tensor &q, const Tensor &kca
                                               const OptTensor &rotary_cos, const OptTensor &rotary_sin, const OptTensor &seqlens_rotary,
                                               double softmax_scale, bool is_causal, int64_t window_size_left,
                                               int64_t window_size_right, double softcap, bool is_rotary_interleaved, int64_t num_splits,
-                                              const OptTensor &sink = c10::nullopt) {
+                                              const OptTensor &sink = c10::nullopt, bool pack_gqa = false) {
     const auto q_dtype = q.scalar_type();
     CHECK_DEVICE(cu_seqlens_q, "cu_seqlens_q");
     TORCH_CHECK(cu_seqlens_q.is_contiguous(), "cu_seqlens_q must be contiguous");
@@ -1051,7 +1055,7 @@ std::tuple<Tensor, Tensor> fwd_kvcache_ragged(const Tensor &q, const Tensor &kca
         if (qv.has_value()) qv4 = qv->unsqueeze(1);
         auto r = fwd_kvcache_core(q.unsqueeze(1), kcache, vcache, k_new, v_new, seqused_k, rotary_cos, rotary_sin, kv_batch_idx, leftpad_k,
                                   page_table, c10::nullopt, out4, softmax_scale, is_causal, window_size_left, window_size_right,
-                                  softcap, is_rotary_interleaved, num_splits, 1, seqlens_rotary, qv4, sink);
+                                  softcap, is_rotary_interleaved, num_splits, 1, seqlens_rotary, qv4, sink, pack_gqa);
         return {r[0].reshape(out_shape), r[1].reshape({batch_size, num_heads}).transpose(0, 1)};
     }
     Tensor qc = aligned_or_copy(q);
@@ -1071,7 +1075,7 @@ std::tuple<Tensor, Tensor> fwd_kvcache_ragged(const Tensor &q, const Tensor &kca
         if (qv.has_value()) qv4 = qv->unsqueeze(1);
         auto r = fwd_kvcache_core(qc.unsqueeze(1), kcache, vcache, c10::nullopt, c10::nullopt, seqused, c10::nullopt, c10::nullopt,
                                   kv_batch_idx, leftpad_k, page_table, c10::nullopt, out4, softmax_scale, is_causal, window_size_left,
-                                  window_size_right, softcap, false, num_splits, 1, c10::nullopt, qv4, sink);
+                                  window_size_right, softcap, false, num_splits, 1, c10::nullopt, qv4, sink, pack_gqa);
         return {r[0].reshape(out_shape), r[1].reshape({batch_size, num_heads}).transpose(0, 1)};
     }
     Tensor out = out_.has_value() ? *out_ : at::empty(out_shape, q.options());
@@ -1086,7 +1090,7 @@ std::tuple<Tensor, Tensor> fwd_kvcache_ragged(const Tensor &q, const Tensor &kca
         a.softmax_scale = softmax_scale; a.causal = is_causal; a.window_left = window_size_left; a.window_right = window_size_right;
         a.softcap = softcap; a.cu_seqlens_q = cu_seqlens_q; a.seqused_q = seqused_q; a.seqused_k = seqused;
         a.kv_batch_idx = kv_batch_idx; a.block_table = page_table; a.leftpad_k = leftpad_k; a.fa3_window = true;
-        a.num_splits = (int)num_splits; a.sink = sink;
+        a.num_splits = (int)num_splits; a.sink = sink; a.pack_gqa = pack_gqa;
         if (qv.has_value()) a.qv = aligned_or_copy(*qv);
         launch_fwd(qc, kcache, vcache, oc, softmax_lse, a);
         if (!oc.is_same(out)) out.copy_(oc);
@@ -1108,8 +1112,10 @@ std::tuple<Tensor, Tensor> fwd_kvcache_ragged(const Tensor &q, const Tensor &kca
 // (MLA absorbed attention, :1028-1048: scores = (q.k + qv.v) * scale, d <= 64 beside d_v in [256, 512], 16-bit) on every
 // route.  Accepted and rejected by message, like the reference does for compiled-out features (:1148-1165):
 // cu_seqlens_k_new without cu_seqlens_q, qv of any other shape or with fp8, KV-cache arguments together with cu_seqlens_k,
-// attention_chunk or fp8.  `scheduler_metadata`, `pack_gqa`, `sm_margin`
-// are performance hints and do not change results: ignored.
+// attention_chunk or fp8.  `scheduler_metadata` and `sm_margin` are performance hints and do not change results: ignored.
+// `pack_gqa` is a hint too: True asks every route below for the pk kernel (FA_FLAG_PACK_GQA: honoured for GQA / MQA calls of
+// 16-bit types at head dims <= 128 without attention_chunk, a V head dim of its own or qv; a no-op elsewhere and behind the
+// single-token GQA swap); False and None keep the unpacked routes (no automatic rule yet).
 // (`sink`, `cute`: the cute surface, below -- its learnable sink, and num_splits honoured on the dense route too)
 std::tuple<Tensor, Tensor, OptTensor, OptTensor> fa3_fwd_core(
         const Tensor &q, const Tensor &k, const Tensor &v, const OptTensor &k_new, const OptTensor &v_new, const OptTensor &qv,
@@ -1120,7 +1126,8 @@ std::tuple<Tensor, Tensor, OptTensor, OptTensor> fa3_fwd_core(
         const OptTensor &q_descale, const OptTensor &k_descale, const OptTensor &v_descale, c10::optional<double> softmax_scale_,
         bool is_causal, int64_t window_size_left, int64_t window_size_right, c10::optional<int64_t> attention_chunk_,
         double softcap, bool is_rotary_interleaved, const OptTensor & /*scheduler_metadata*/, int64_t num_splits,
-        c10::optional<bool> /*pack_gqa*/, int64_t /*sm_margin*/, const OptTensor &sink, bool cute) {
+        c10::optional<bool> pack_gqa_, int64_t /*sm_margin*/, const OptTensor &sink, bool cute) {
+    const bool pack_gqa = pack_gqa_.value_or(false);
     const auto q_dtype = q.scalar_type();
     const bool is_fp8 = q_dtype == at::kFloat8_e4m3fn;
     TORCH_CHECK(q_dtype == at::kHalf || q_dtype == at::kBFloat16 || is_fp8,
@@ -1181,12 +1188,12 @@ std::tuple<Tensor, Tensor, OptTensor, OptTensor> fa3_fwd_core(
             auto r = fwd_kvcache_ragged(q, k, v, k_new, v_new, qv, out_, *cu_seqlens_q, cu_seqlens_k_new, seqused_q, seqused_k,
                                         max_seqlen_q_.value_or(-1), page_table, kv_batch_idx, leftpad_k, rotary_cos, rotary_sin,
                                         seqlens_rotary, softmax_scale_.value_or(default_scale), is_causal, window_size_left,
-                                        window_size_right, softcap, is_rotary_interleaved, num_splits, sink);
+                                        window_size_right, softcap, is_rotary_interleaved, num_splits, sink, pack_gqa);
             return {std::get<0>(r), std::get<1>(r), c10::nullopt, c10::nullopt};
         }
         auto r = fwd_kvcache_core(q, k, v, k_new, v_new, seqused_k, rotary_cos, rotary_sin, kv_batch_idx, leftpad_k, page_table,
                                   c10::nullopt, out_, softmax_scale_.value_or(default_scale), is_causal, window_size_left,
-                                  window_size_right, softcap, is_rotary_interleaved, num_splits, 1, seqlens_rotary, qv, sink);
+                                  window_size_right, softcap, is_rotary_interleaved, num_splits, 1, seqlens_rotary, qv, sink, pack_gqa);
         return {r[0], r[1], c10::nullopt, c10::nullopt};
     }
     if (!cu_seqlens_q && !cu_seqlens_k && !seqused_q && seqused_k && !is_fp8 && q.dim() == 4 && q.size(1) <= 128 &&
@@ -1197,7 +1204,7 @@ std::tuple<Tensor, Tensor, OptTensor, OptTensor> fa3_fwd_core(
         // GQA swap (:935-1060 runs them for every call with seqused_k)
         auto r = fwd_kvcache_core(q, k, v, c10::nullopt, c10::nullopt, seqused_k, c10::nullopt, c10::nullopt, c10::nullopt,
                                   c10::nullopt, c10::nullopt, c10::nullopt, c10::nullopt, softmax_scale_.value_or(default_scale),
-                                  is_causal, -1, -1, softcap, false, num_splits, 1, c10::nullopt, qv, sink);
+                                  is_causal, -1, -1, softcap, false, num_splits, 1, c10::nullopt, qv, sink, pack_gqa);
         return {r[0], r[1], c10::nullopt, c10::nullopt};
     }
     const bool varlen = cu_seqlens_q.has_value();
@@ -1269,7 +1276,7 @@ std::tuple<Tensor, Tensor, OptTensor, OptTensor> fa3_fwd_core(
         a.fa3_window = true; a.attention_chunk = attention_chunk;
         if (qv.has_value()) a.qv = aligned_or_copy(*qv);
         a.num_splits = cute ? (int)num_splits : 1;  // no split-KV: the decode calls of the FA3 surface take the fwd_kvcache_impl routes above
-        a.sink = sink;
+        a.sink = sink; a.pack_gqa = pack_gqa;
         launch_fwd(qc, kc, vc, oc, softmax_lse, a);
         if (!oc.is_same(out)) out.copy_(oc);
     } else if (total_q > 0) {
@@ -1376,19 +1383,19 @@ void check_sink(const OptTensor &sink, const Tensor &q) {
 }
 
 // Routes like fa3_fwd (KV-cache steps with their GQA swap and split heuristic, ragged queries over a cache, dense, varlen);
-// max_seqlen_q / max_seqlen_k are upper bounds the caller derives from shapes (the cute signatures carry none): the grid
+// pack_gqa: fa3_fwd_core's hint (True = FA_FLAG_PACK_GQA).  max_seqlen_q / max_seqlen_k are upper bounds the caller derives from shapes (the cute signatures carry none): the grid
 // is made from them, the kernels read the lengths on the device.  Returns (out, softmax_lse).
 std::tuple<Tensor, Tensor> cute_fwd(const Tensor &q, const Tensor &k, const Tensor &v, const OptTensor &cu_seqlens_q,
                                     const OptTensor &cu_seqlens_k, const OptTensor &seqused_q, const OptTensor &seqused_k,
                                     c10::optional<int64_t> max_seqlen_q, c10::optional<int64_t> max_seqlen_k,
                                     const OptTensor &page_table, c10::optional<double> softmax_scale, bool is_causal,
                                     int64_t window_size_left, int64_t window_size_right, const OptTensor &learnable_sink,
-                                    double softcap, int64_t num_splits) {
+                                    double softcap, int64_t num_splits, c10::optional<bool> pack_gqa) {
     check_sink(learnable_sink, q);
     const OptTensor none;
     auto r = fa3_fwd_core(q, k, v, none, none, none, none, cu_seqlens_q, cu_seqlens_k, none, seqused_q, seqused_k, max_seqlen_q,
                           max_seqlen_k, page_table, none, none, none, none, none, none, none, none, softmax_scale, is_causal,
-                          window_size_left, window_size_right, c10::nullopt, softcap, false, none, num_splits, c10::nullopt, 0,
+                          window_size_left, window_size_right, c10::nullopt, softcap, false, none, num_splits, pack_gqa, 0,
                           learnable_sink, true);
     return {std::get<0>(r), std::get<1>(r)};
 }
@@ -1688,7 +1695,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("fa3_fwd", &fa3_fwd, "FA3 forward pass (flash_attn_3::fwd)");
     m.def("fa3_bwd", &fa3_bwd, "FA3 backward pass (flash_attn_3::bwd)");
     m.def("fa3_fwd_combine", &fa3_fwd_combine, "FA3 merge of split-KV partials (flash_attn_3::fwd_combine)");
-    m.def("cute_fwd", &cute_fwd, "cute surface forward (flash_attn.cute.interface, with learnable_sink)");
+    m.def("cute_fwd", &cute_fwd, "cute surface forward (flash_attn.cute.interface, with learnable_sink)", py::arg("q"), py::arg("k"),
+          py::arg("v"), py::arg("cu_seqlens_q"), py::arg("cu_seqlens_k"), py::arg("seqused_q"), py::arg("seqused_k"),
+          py::arg("max_seqlen_q"), py::arg("max_seqlen_k"), py::arg("page_table"), py::arg("softmax_scale"), py::arg("is_causal"),
+          py::arg("window_size_left"), py::arg("window_size_right"), py::arg("learnable_sink"), py::arg("softcap"),
+          py::arg("num_splits"), py::arg("pack_gqa") = py::none());
     m.def("cute_fwd_block_sparse", &cute_fwd_block_sparse, "cute surface forward restricted to listed 128 x 128 blocks");
     m.def("cute_bwd", &cute_bwd, "cute surface backward: (dq, dk, dv, dsink)");
     m.def("cute_bwd_block_sparse", &cute_bwd_block_sparse, "cute surface backward over listed 128 x 128 blocks: (dq, dk, dv, dsink)");

@@ -186,7 +186,7 @@ def _checks(q, k, v, cu_seqlens_q, cu_seqlens_k, seqused_q, seqused_k, page_tabl
 
 def _flash_attn_fwd(q, k, v, cu_seqlens_q=None, cu_seqlens_k=None, seqused_q=None, seqused_k=None, page_table=None,
                     softmax_scale=None, causal=False, window_size=(None, None), learnable_sink=None, softcap=0.0,
-                    num_splits=1):
+                    num_splits=1, pack_gqa=None):
     q, k, v = [maybe_contiguous(t) for t in (q, k, v)]
     _checks(q, k, v, cu_seqlens_q, cu_seqlens_k, seqused_q, seqused_k, page_table, learnable_sink)
     if softmax_scale is None:
@@ -197,7 +197,7 @@ def _flash_attn_fwd(q, k, v, cu_seqlens_q=None, cu_seqlens_k=None, seqused_q=Non
     max_seqlen_k = k.shape[0] if cu_seqlens_k is not None else None
     sink = learnable_sink.detach().contiguous() if learnable_sink is not None else None
     return _lib.binding().cute_fwd(q, k, v, cu_seqlens_q, cu_seqlens_k, seqused_q, seqused_k, max_seqlen_q, max_seqlen_k,
-                                   page_table, softmax_scale, causal, left, right, sink, softcap or 0.0, num_splits)
+                                   page_table, softmax_scale, causal, left, right, sink, softcap or 0.0, num_splits, pack_gqa)
 
 
 def _flash_attn_bwd_block_sparse(dout, q, k, v, out, lse, softmax_scale, causal, window_size, softcap, learnable_sink, lists):
@@ -241,7 +241,7 @@ class FlashAttnFunc(torch.autograd.Function):
                                                     full_block_cnt, full_block_idx, mask_block_cnt, mask_block_idx)
         else:
             out, lse = _flash_attn_fwd(q, k, v, softmax_scale=softmax_scale, causal=causal, window_size=window_size,
-                                       learnable_sink=learnable_sink, softcap=softcap, num_splits=num_splits)
+                                       learnable_sink=learnable_sink, softcap=softcap, num_splits=num_splits, pack_gqa=pack_gqa)
         lists = (full_block_cnt, full_block_idx, mask_block_cnt, mask_block_idx, q_block_cnt, q_block_idx) if ctx.key_lists else ()
         ctx.save_for_backward(q, k, v, out, lse, learnable_sink, *lists)
         ctx.softmax_scale, ctx.causal, ctx.window_size, ctx.softcap = softmax_scale, causal, window_size, softcap
@@ -275,7 +275,7 @@ class FlashAttnVarlenFunc(torch.autograd.Function):
         if softmax_scale is None:
             softmax_scale = 1.0 / math.sqrt(q.shape[-1])
         out, lse = _flash_attn_fwd(q, k, v, cu_seqlens_q, cu_seqlens_k, seqused_q, seqused_k, page_table, softmax_scale, causal,
-                                   window_size, learnable_sink, softcap, num_splits)
+                                   window_size, learnable_sink, softcap, num_splits, pack_gqa)
         ctx.save_for_backward(q, k, v, out, lse, cu_seqlens_q, cu_seqlens_k, learnable_sink)
         ctx.softmax_scale, ctx.causal, ctx.window_size, ctx.softcap = softmax_scale, causal, window_size, softcap
         # the backward is the training one: dense, or cu_seqlens_q with cu_seqlens_k
@@ -301,7 +301,10 @@ def flash_attn_func(q, k, v, softmax_scale=None, causal=False, window_size=(None
                     num_splits=1, pack_gqa=None, mask_mod=None, full_block_cnt=None, full_block_idx=None, mask_block_cnt=None,
                     mask_block_idx=None, q_block_cnt=None, q_block_idx=None):
     """q (b, sq, h, d), k / v (b, sk, h_k, d[_v]) -> (out, lse (b, h, sq)).  learnable_sink: (h,) bf16 or fp32.  num_splits:
-    1 = no split-KV, N > 1 = N parts, 0 = the library's heuristic.  pack_gqa is accepted and ignored; mask_mod must be None.
+    1 = no split-KV, N > 1 = N parts, 0 = the library's heuristic.  mask_mod must be None.
+    pack_gqa: True packs the h / h_k query heads of a kv head into the rows of a tile, one pass over K / V per kv head
+    (pk_fwd_kernel: h > h_k, head dims <= 128, same head dim for V; a no-op on other calls and on block-sparse ones); False and
+    None run one workgroup per query head, as before -- None does not pack by itself yet.  A hint: results agree to rounding.
 
     Block sparsity: mask_block_cnt (b | 1, h | 1, nm) and mask_block_idx (b | 1, h | 1, nm, nk), int32, on q's device, with
     nm = ceil(sq / 128), nk = ceil(sk / 128), and optionally full_block_cnt / full_block_idx of the same shapes
@@ -328,6 +331,7 @@ def flash_attn_varlen_func(q, k, v, cu_seqlens_q=None, cu_seqlens_k=None, sequse
                            num_splits=1, pack_gqa=None):
     """q (total_q, h, d) with cu_seqlens_q, or dense (b, sq, h, d) without -- the decode call: sq = 1, page_table, seqused_k.
     k / v: (total_k, h_k, .) with cu_seqlens_k, a batched cache (b, sk, h_k, .), or pages (num_pages, page_size, h_k, .)
-    behind page_table.  Returns (out, lse): lse (h, total_q) with cu_seqlens_q, (b, h, sq) without."""
+    behind page_table.  Returns (out, lse): lse (h, total_q) with cu_seqlens_q, (b, h, sq) without.  pack_gqa: as in
+    flash_attn_func (True = the pk kernel on every one of these forms; the single-token decode step keeps its own GQA swap)."""
     return FlashAttnVarlenFunc.apply(q, k, v, cu_seqlens_q, cu_seqlens_k, seqused_q, seqused_k, page_table, softmax_scale, causal,
                                      window_size, learnable_sink, softcap, num_splits, pack_gqa)

@@ -166,7 +166,11 @@ def flash_attn_func(q, k, v, softmax_scale=None, causal=False, qv=None, q_descal
                     deterministic=False, sm_margin=0, return_attn_probs=False):
     """hopper/flash_attn_interface.py:507-585.  q: (batch, seqlen, nheads, headdim); k, v: (batch, seqlen_k, nheads_k,
     headdim); fp16 / bf16 (differentiable) / fp8 e4m3 (forward only, bf16 output).
-    Returns out, or (out, softmax_lse (batch, nheads, seqlen)) when return_attn_probs."""
+    Returns out, or (out, softmax_lse (batch, nheads, seqlen)) when return_attn_probs.
+    pack_gqa: True packs the nheads / nheads_k query heads of a kv head into the rows of a tile, one pass over K / V per kv head
+    (pk_fwd_kernel: nheads > nheads_k, 16-bit inputs, headdim <= 128, no attention_chunk, qv or V headdim of its own; a no-op
+    on every other call).  False and None run one workgroup per query head, as before: None does not pack by itself yet.  A
+    performance hint: results agree to rounding, the backward is unaffected."""
     return FlashAttnFunc.apply(q, k, v, softmax_scale, causal, qv, q_descale, k_descale, v_descale, window_size,
                                attention_chunk, softcap, num_splits, pack_gqa, deterministic, sm_margin, return_attn_probs)
 
@@ -176,7 +180,8 @@ def flash_attn_varlen_func(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, ma
                            v_descale=None, window_size=(-1, -1), attention_chunk=0, softcap=0.0, num_splits=1,
                            pack_gqa=None, deterministic=False, sm_margin=0, return_attn_probs=False):
     """hopper/flash_attn_interface.py:588-633.  q: (total_q, nheads, headdim); k, v: (total_k, nheads_k, headdim);
-    cu_seqlens_*: (batch+1,) int32; seqused_*: (batch,) int32, the part of each sequence that is actually used."""
+    cu_seqlens_*: (batch+1,) int32; seqused_*: (batch,) int32, the part of each sequence that is actually used.
+    pack_gqa: as in flash_attn_func (True = the PackGQA kernel, made for many short sequences; False / None = unpacked)."""
     return FlashAttnVarlenFunc.apply(q, k, v, cu_seqlens_q, cu_seqlens_k, seqused_q, seqused_k, max_seqlen_q, max_seqlen_k,
                                      softmax_scale, causal, qv, q_descale, k_descale, v_descale, window_size,
                                      attention_chunk, softcap, num_splits, pack_gqa, deterministic, sm_margin,
@@ -195,7 +200,10 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, qv=None, rotary
                             window_size=(-1, -1), attention_chunk=0, softcap=0.0, rotary_interleaved=True,
                             scheduler_metadata=None, num_splits=0, pack_gqa=None, sm_margin=0, return_softmax_lse=False):
     """reference hopper/flash_attn_interface.py:640-800: attention over a KV cache, optionally appending k / v in place
-    (rotated by rotary_cos / rotary_sin) first.  Paged caches: any page size."""
+    (rotated by rotary_cos / rotary_sin) first.  Paged caches: any page size.
+    pack_gqa: True runs the PackGQA kernel on the attention of the step -- dense or ragged (cu_seqlens_q) queries, batched or
+    paged cache, split-KV -- so that a verify step of a few tokens or the decode rows of a mixed step share one pass over the
+    cache per kv head; a single-token step keeps its own GQA fold and is unaffected.  False / None: unpacked, as before."""
     assert k_cache.stride(-1) == 1, "k_cache must have contiguous last dimension"
     assert v_cache.stride(-1) == 1, "v_cache must have contiguous last dimension"
     if softmax_scale is None:

@@ -46,6 +46,7 @@ extern "C" {
 
 #define FA_FLAG_FA3_WINDOW 1
 #define FA_FLAG_SDMASK_SIGNED 2   /* s_dmask is the reference's sign-encoded probability tensor (below), not random bytes */
+#define FA_FLAG_PACK_GQA 4        /* hint (FA3 pack_gqa = True): pack the h / h_k query heads of a kv head into the rows of a tile */
 
 /* element types of q/k/v (o has the same type; fp8 inputs produce bf16 o) */
 enum fa_dtype {
@@ -188,7 +189,13 @@ typedef struct fa_fwd_params {
     float p_dropout;
     /* FA_FLAG_* bits.  FA_FLAG_FA3_WINDOW: window sides follow the FA3 rule (hopper/flash_api.cpp:152-153, 589-590): a
      * negative side is UNBOUNDED and stays so; without the flag a one-sided window gets seqlen_k on the other side as
-     * set_params_fprop does (csrc/flash_attn/flash_api.cpp:141-142), which masks rows when seqlen_q > seqlen_k. */
+     * set_params_fprop does (csrc/flash_attn/flash_api.cpp:141-142), which masks rows when seqlen_q > seqlen_k.
+     * FA_FLAG_PACK_GQA (hopper/pack_gqa.h; no ABI change: a bit of this field): a performance hint that never changes what is
+     * computed.  Honoured -- one workgroup per block of (query row, head of the GQA group) pairs of one kv head, pk_fwd_kernel
+     * in fa_fwd_plan_name -- exactly when h > h_k, the type is 16-bit, d <= 128, and the call has no ALiBi, dropout,
+     * attention_chunk, V head dim of its own or qv; every other call runs as without the bit.  Dense, varlen, seqused_*, caches
+     * (kv_batch_idx, leftpad_k, paged), ragged queries over a cache, split-KV, softcap and fa_fwd_sink are all served.
+     * fa_fwd_block_sparse ignores it. */
     int32_t flags;
     const uint64_t *rng_state;
     uint8_t *s_dmask;
