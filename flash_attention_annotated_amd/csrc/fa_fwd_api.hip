@@ -541,7 +541,10 @@ SplitPlan split_plan(const fa_fwd_params *p, int variant, bool pk = false) {
     if (p->cu_seqlens_k || p->dtype == FA_DTYPE_FP8_E4M3 || p->seqlen_q <= 0 || p->seqlen_k <= 0) return sp;
     if (p->cu_seqlens_q && p->total_q <= 0) return sp;
     if (p->p_dropout > 0.f) return sp;  // (the reference does not split under dropout either: flash_api.cpp:307)
-    if (own_dv(p)) return sp;           // (the partials and the merge are laid out for d columns)
+    // attention_chunk / a V head dim of its own (the EXTRA instantiations): never split.  The partials and the merge are laid
+    // out for d columns, and no entry point asks for a split beside attention_chunk (the dense FA3 route plans one part): like
+    // dropout, a num_splits above 1 is planned as 1 rather than run on a store path nothing exercises
+    if (generic_only(p)) return sp;
     int n = p->num_splits;
     const int n_blocks = (p->seqlen_k + 63) / 64;
     if (n == 0) {

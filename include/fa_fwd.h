@@ -167,7 +167,8 @@ typedef struct fa_fwd_params {
      * src/flash_fwd_kernel.h:1108-1290): 1 = off, N > 1 = the key range of every tile is cut into N parts computed by
      * N workgroups and merged by a second launch, 0 = library heuristic (splits only dense problems and ragged queries
      * over a cache with few tiles, i.e. decode; the tiles of a ragged batch are counted from total_q and seqlen_q, never from
-     * device data).  cu_seqlens_q + cu_seqlens_k problems never split.  Ragged queries over a cache keep partials of
+     * device data).  cu_seqlens_q + cu_seqlens_k problems never split, nor do dropout, fp8 and attention_chunk problems
+     * (any num_splits is planned as 1 there).  Ragged queries over a cache keep partials of
      * (splits, total_q, h, d_v) + (splits, h, total_q) fp32.  Needs params->workspace of fa_fwd_workspace_size() bytes when the effective value is > 1 (the partial
      * outputs and LSEs of the parts, both fp32 like the reference's out_accum / softmax_lse_accum).
      * The default-initialised struct (0) therefore may split: callers without a workspace must pass 1. */

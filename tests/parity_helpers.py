@@ -40,12 +40,29 @@ def record_bwd_plan(out):
 
 
 def kernel_key(plan, dtype):
-    """(element type, plan name without block_m= / splits= / cols= / fp8_expand): one template instantiation.  fp8 inputs run
-    the native kernel ("fp8") or, expanded, the bf16 instantiations."""
-    key = re.sub(r" (block_m|splits|cols)=\d+| fp8_expand", "", plan)
-    if dtype == FP8:
-        return ("bf16" if " fp8_expand" in plan else "fp8", key)
-    return ({torch.bfloat16: "bf16", torch.float16: "fp16"}[dtype], key)
+    """(element type, plan name without block_m= / splits= / cols= / fp8_expand, epilogue): one template instantiation and the
+    store path the launch took in it -- "direct" for `splits=1`, "partial" (fp32 partials + the merge) for any other count.
+    fp8 inputs run the native kernel ("fp8") or, expanded, the bf16 instantiations."""
+    return plan_key(plan, "fp8" if dtype == FP8 else {torch.bfloat16: "bf16", torch.float16: "fp16"}[dtype])
+
+
+def plan_key(plan, dt):
+    """kernel_key for an element type by name ("bf16", "fp16", "fp8"): needs no tensor type, the CPU tests use it as well."""
+    form = re.sub(r" (block_m|splits|cols)=\d+| fp8_expand", "", plan)
+    splits = re.search(r" splits=(\d+)", plan)
+    assert splits, f"{plan!r} names no split count"
+    epilogue = "direct" if splits.group(1) == "1" else "partial"
+    if dt == "fp8" and " fp8_expand" in plan:
+        dt = "bf16"
+    return (dt, form, epilogue)
+
+
+def sparse_lists(case):
+    """((full_cnt, full_idx, mask_cnt, mask_idx), visited) of a block-sparse case of tests/plan_universe.py: seeded lists as
+    tests/test_block_sparse_gpu.py::test_random_subsets builds them, 1 .. nk - 1 visited key blocks per query block."""
+    import block_sparse_oracle as bso
+    nm, nk = -(-case["sq"] // bso.BLOCK), -(-case["sk"] // bso.BLOCK)
+    return bso.random_lists(case["lists"], case["b"], case["h"], nm, nk, min_visited=1, max_visited=nk - 1)
 
 
 def wave_slice_rows(sq, block_m, seed=0, rows_per_wave=32):
@@ -81,7 +98,8 @@ def causal_bias(rows, sq, sk):
     return torch.where(j <= i + sk - sq, 0.0, float("-inf")).view(1, 1, len(rows), sk)
 
 
-def _check_rows(out_rows, lse_rows, q_rows, k, v, bias, what, fp8_kw=None, lse_tol=2e-3):
+def _check_rows(out_rows, lse_rows, q_rows, k, v, bias, what, fp8_kw=None, lse_tol=2e-3, record=None):
+    """`record(out_rows, out_ref, out_pt, atol)`, when given, sees the terms of the bound before anything is asserted."""
     kw = dict(attn_bias=bias)
     if fp8_kw:
         kw.update(fp8_kw)
@@ -92,6 +110,8 @@ def _check_rows(out_rows, lse_rows, q_rows, k, v, bias, what, fp8_kw=None, lse_t
     else:
         out_pt, _ = oracle.attention_ref(q_rows, k, v, upcast=False, reorder_ops=True, **kw)
         atol = 1e-5
+    if record is not None:
+        record(out_rows, out_ref, out_pt, atol)
     err = (out_rows.float().cpu() - out_ref.float()).abs().max().item()
     bound = 2 * (out_pt.float() - out_ref.float()).abs().max().item() + atol
     assert math.isfinite(err) and err <= bound, f"{what}: max err {err:.3e} > bound {bound:.3e}"

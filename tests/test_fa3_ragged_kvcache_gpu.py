@@ -265,6 +265,27 @@ def test_ragged_append_rotary_bits_and_oracle(layout, interleaved, rot_seqlens):
         _check(step, out, lse, *step.reference(causal), f"rotary causal={causal}")
 
 
+@pytest.mark.parametrize("lens_new", [LENS_NEW, [0] * 6], ids=["append", "empty_append"])
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16], ids=["bf16", "fp16"])
+def test_ragged_append_rotary_both_types(dtype, lens_new):
+    """kvcache_append_varlen_kernel and rotary_varlen_kernel in both element types (the tests above rotate bf16 only) against
+    plain torch: the cache equals a Python scatter of the rows rotated by oracle.apply_rotary_emb_ref, bit for bit, and the
+    attention over it follows the oracle with q rotated the same way.  342 new rows and 469 query rows in 6 sequences, two
+    of them without rows: no multiple of the 16 rows of a workgroup, sequences cut inside a wave's 4 rows.  `empty_append`:
+    the empty input -- k_new / v_new of no rows at all: every byte of the cache stays what it was, q is still rotated, and
+    the result has its shape, no non-finite element, and follows the oracle over the old fill levels."""
+    step = Step(LENS_Q, FILLS, lens_new, d=128, dtype=dtype, rotary=(64, False), seed=43)
+    assert (sum(LENS_Q) % 16, sum(LENS_NEW) % 16) == (5, 6)
+    kd, vd = step.device_cache()
+    out, lse = step.call(kd, vd, causal=True)
+    assert last_plan() == W64_128
+    _check_cache(step, kd, vd)
+    if not sum(lens_new):
+        assert step.k_new.shape[0] == 0 and torch.equal(kd.cpu(), step.kc) and torch.equal(vd.cpu(), step.vc)
+        assert out.dtype == dtype and torch.isfinite(out).all()
+    _check(step, out, lse, *step.reference(True), f"rotary {dtype} new rows {sum(lens_new)}")
+
+
 @pytest.mark.parametrize("layout", ["contig", "page64"])
 def test_ragged_append_drops_rows_past_capacity(layout):
     """Sequences whose new rows do not fit: the rows past the capacity are dropped, nothing else is touched, and the attention

@@ -175,5 +175,5 @@ def test_device_code_has_exactly_the_eight_instantiations():
         assert m, s
         got.add(({"DF16b": "bf16", "DF16_": "fp16"}[m.group(1)], int(m.group(2)), m.group(3) == "1"))
     assert got == PK_KERNELS
-    # the name keeps the new kernels out of the `fwd_kernel...` universe of tests/plan_universe.py
+    # (a family of its own in tests/plan_universe.py: the names do not collide with the `fwd_kernel...` symbols)
     assert not any(re.match(r"_ZN2fa\d+fwd_kernel", s) for s in syms)

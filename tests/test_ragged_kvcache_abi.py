@@ -14,7 +14,7 @@ from plan_universe import UNIVERSE
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ADDR = 0x100000  # aligned dummy address: nothing is dereferenced
-KEYS = {key for _, key in UNIVERSE}
+KEYS = {form for _, form, _ in UNIVERSE}
 
 
 def _ragged(b=6, total_q=900, max_sq=512, h=8, h_k=2, cap=4096, d=128, d_v=0, b_cache=None, **fields):

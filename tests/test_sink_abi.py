@@ -9,7 +9,7 @@ from flash_attention_annotated_amd import _lib
 from plan_universe import UNIVERSE
 
 ADDR = 0x100000  # aligned dummy address: nothing is dereferenced
-KEYS = {key for _, key in UNIVERSE}
+KEYS = {form for _, form, _ in UNIVERSE}
 UNSUPPORTED, NULL_POINTER, BAD_DTYPE, BAD_SHAPE, BAD_STRIDE, BAD_ABI = -7, -1, -2, -5, -6, -9
 
 
