@@ -52,6 +52,10 @@ EXPORTED_SYMBOLS = (
     "fa_fwd_block_sparse",
     "fa_fwd_block_sparse_validate",
     "fa_block_sparse_params_size",
+    "fa_fwd_kv8",
+    "fa_fwd_kv8_validate",
+    "fa_fwd_kv8_workspace_size",
+    "fa_fwd_kv8_plan_name",
     # include/fa_bwd.h
     "fa_bwd",
     "fa_bwd_validate",
@@ -305,7 +309,7 @@ def is_stale():
 
 def build(force=False, verbose=False):
     """Compile csrc/ for gfx950 into the in-tree shared library (hipcc cross-compiles without a GPU)."""
-    srcs = [os.path.join(CSRC, "fa_fwd_api.hip"), os.path.join(CSRC, "fa_bwd_api.hip"), os.path.join(CSRC, "fa_bwd_bs_api.hip")]
+    srcs = [os.path.join(CSRC, f) for f in ("fa_fwd_api.hip", "fa_fwd_kv8_api.hip", "fa_bwd_api.hip", "fa_bwd_bs_api.hip")]
     if not force and not is_stale():
         return LIB_PATH
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -433,6 +437,14 @@ def load():
     lib.fa_block_sparse_params_size.restype = ctypes.c_uint32
     if lib.fa_block_sparse_params_size() != ctypes.sizeof(FaBlockSparseParams):
         raise RuntimeError("fa_block_sparse_params layout mismatch between include/fa_fwd.h and _lib")
+    lib.fa_fwd_kv8.argtypes = [ctypes.POINTER(FaFwdParams), ctypes.c_void_p]
+    lib.fa_fwd_kv8.restype = ctypes.c_int
+    lib.fa_fwd_kv8_validate.argtypes = [ctypes.POINTER(FaFwdParams)]
+    lib.fa_fwd_kv8_validate.restype = ctypes.c_int
+    lib.fa_fwd_kv8_workspace_size.argtypes = [ctypes.POINTER(FaFwdParams)]
+    lib.fa_fwd_kv8_workspace_size.restype = ctypes.c_int64
+    lib.fa_fwd_kv8_plan_name.argtypes = [ctypes.POINTER(FaFwdParams), ctypes.c_int32]
+    lib.fa_fwd_kv8_plan_name.restype = ctypes.c_char_p
     lib.fa_sink_grad.argtypes = [ctypes.POINTER(FaSinkGradParams), ctypes.c_void_p]
     lib.fa_sink_grad.restype = ctypes.c_int
     lib.fa_sink_grad_validate.argtypes = [ctypes.POINTER(FaSinkGradParams)]

@@ -11,6 +11,7 @@
 #include "fa_fwd_kernel_qv.h"
 #include "fa_fwd_kernel_bs.h"
 #include "fa_fwd_kernel_pk.h"
+#include "fa_fwd_internal.h"
 #include "fa_launch.h"
 
 #include <algorithm>
@@ -785,6 +786,8 @@ thread_local bool t_last_plan_set = false;
 // ... or, when that call was fa_fwd_block_sparse, the head-dim tile of its bs_fwd_kernel (0 = it was not) and its softcap form
 thread_local int t_last_bs_tile = 0;
 thread_local bool t_last_bs_softcap = false;
+// ... or the text an entry point of another translation unit left (fa::fwd_set_last_plan_text: fa_fwd_kv8); "" = none
+thread_local char t_last_ext_text[160] = "";
 
 // compute units of the current device (cached per device ordinal)
 int device_cus() {
@@ -1006,6 +1009,19 @@ int launch_plan(const FwdPlan &pl, const fa_fwd_params *p, const fa::KParams &kp
 }
 
 }  // namespace
+
+// ---- fa_fwd_internal.h: what fa_fwd_kv8_api.hip shares with this file ---------------------------------------------------------
+namespace fa {
+int fwd_pk_split_count(const fa_fwd_params *p) { return split_plan(p, 2, true).splits; }
+void fwd_set_last_plan_text(const char *text) {
+    snprintf(t_last_ext_text, sizeof(t_last_ext_text), "%s", text ? text : "");
+    if (t_last_ext_text[0]) {
+        t_last_plan_set = false;
+        t_last_bs_tile = 0;
+    }
+}
+int fwd_device_cus() { return device_cus(); }
+}  // namespace fa
 
 extern "C" {
 
@@ -1319,6 +1335,7 @@ const char *fa_fwd_plan_name(const fa_fwd_params *p, int32_t num_cus) {
 
 const char *fa_fwd_last_plan_name(void) {
     thread_local char name[160];
+    if (t_last_ext_text[0]) return t_last_ext_text;
     if (t_last_bs_tile) {  // the block-sparse kernel has one shape: 4 waves x 32 rows = one 128-row block, never split
         snprintf(name, sizeof(name), "bs_fwd_kernel D=%d waves=%d%s block_m=%d splits=1", t_last_bs_tile, fa::BS_NWAVES,
                  t_last_bs_softcap ? " SOFTCAP" : "", fa::BS_BLOCK);
@@ -1362,6 +1379,7 @@ static int fwd_run(const fa_fwd_params *p, const fa_sink_params *sink, void *str
     const int st = sink ? fa_fwd_sink_validate(p, sink) : fa_fwd_validate(p);
     t_last_plan_set = false;
     t_last_bs_tile = 0;
+    t_last_ext_text[0] = 0;
     if (st != FA_OK) return st;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
 
@@ -1611,6 +1629,7 @@ int fa_fwd_block_sparse(const fa_fwd_params *p_, const fa_block_sparse_params *s
     const int st = fa_fwd_block_sparse_validate(p_, s, sink);
     t_last_plan_set = false;
     t_last_bs_tile = 0;
+    t_last_ext_text[0] = 0;
     if (st != FA_OK) return st;
     const fa_fwd_params dense = bs_dense_params(p_), *p = &dense;
     hipStream_t stream = static_cast<hipStream_t>(stream_);

@@ -1102,6 +1102,147 @@ std::tuple<Tensor, Tensor> fwd_kvcache_ragged(const Tensor &q, const Tensor &kca
     return {out, softmax_lse};
 }
 
+// 16-bit queries over an fp8 (e4m3) KV cache -- kv_cache_dtype = fp8 of a serving stack (include/fa_fwd.h, fa_fwd_kv8): q and
+// out fp16 / bf16, k / v the cache as Float8_e4m3fn, (b_cache, seqlen_k, h_k, d) or pages behind page_table, k_descale /
+// v_descale fp32 (b, h_k).  Dense q (b, seqlen_q, h, d) or ragged q (total_q, h, d) with cu_seqlens_q; cache_seqlens in
+// seqused_k.  One kernel for every h / h_k (it packs the GQA group into its rows itself: no swap, pack_gqa is moot).
+// The caller has refused what the route does not serve (new rows, rotary, qv, attention_chunk, head dims).
+std::tuple<Tensor, Tensor> fwd_kv8(const Tensor &q, const Tensor &k, const Tensor &v, const OptTensor &out_,
+                                   const OptTensor &cu_seqlens_q, const OptTensor &seqused_q, const OptTensor &seqused_k,
+                                   c10::optional<int64_t> max_seqlen_q_, const OptTensor &page_table, const OptTensor &kv_batch_idx,
+                                   const OptTensor &leftpad_k, const OptTensor &k_descale, const OptTensor &v_descale,
+                                   double softmax_scale, bool is_causal, int64_t window_size_left, int64_t window_size_right,
+                                   double softcap, int64_t num_splits) {
+    CHECK_DEVICE(q, "q"); CHECK_LAST_CONTIGUOUS(q, "Input tensor must have contiguous last dimension");
+    CHECK_DEVICE(k, "k"); CHECK_LAST_CONTIGUOUS(k, "Input tensor must have contiguous last dimension");
+    CHECK_DEVICE(v, "v"); CHECK_LAST_CONTIGUOUS(v, "Input tensor must have contiguous last dimension");
+    const bool ragged = cu_seqlens_q.has_value(), paged = page_table.has_value();
+    TORCH_CHECK(k.dim() == 4 && v.dim() == 4,
+                "an fp8 k / v must be a KV cache of shape (batch or num_pages, seqlen or page_size, num_heads_k, head_size)");
+    TORCH_CHECK(q.dim() == (ragged ? 3 : 4), ragged ? "q must have shape (total_q, num_heads, head_size) with cu_seqlens_q"
+                                                    : "q must have shape (batch_size, seqlen_q, num_heads, head_size)");
+    const int64_t head_size = q.size(-1), num_heads = q.size(-2), num_heads_k = k.size(2);
+    int64_t batch_size, seqlen_q, total_q;
+    if (ragged) {
+        TORCH_CHECK(cu_seqlens_q->scalar_type() == at::kInt && cu_seqlens_q->is_contiguous() && cu_seqlens_q->is_cuda(),
+                    "cu_seqlens_q must be a contiguous int32 CUDA tensor");
+        TORCH_CHECK(max_seqlen_q_.has_value() && *max_seqlen_q_ > 0, "max_seqlen_q must be provided with cu_seqlens_q");
+        TORCH_CHECK(seqused_k.has_value(), "seqused_k (the cache fill levels) must be provided with cu_seqlens_q over a KV cache");
+        batch_size = cu_seqlens_q->numel() - 1; seqlen_q = *max_seqlen_q_; total_q = q.size(0);
+    } else {
+        TORCH_CHECK(!seqused_q.has_value(),
+                    "This flash attention build does not support KV-cache arguments together with seqused_q without cu_seqlens_q.");
+        batch_size = q.size(0); seqlen_q = q.size(1); total_q = batch_size * seqlen_q;
+    }
+    TORCH_CHECK(batch_size > 0, "batch size must be positive");
+    TORCH_CHECK(num_heads_k > 0 && num_heads % num_heads_k == 0, "Number of heads in key/value must divide number of heads in query");
+    if (paged) TORCH_CHECK(!kv_batch_idx.has_value(), "Paged KVcache does not support cache_batch_idx");
+    int64_t seqlen_k = k.size(1), batch_size_c = k.size(0);
+    if (paged) {
+        const auto pr = check_block_table(*page_table, k, batch_size, 1);
+        seqlen_k = pr.second * pr.first; batch_size_c = batch_size;
+    }
+    TORCH_CHECK(k.size(3) == head_size, "k must have shape (..., ", num_heads_k, ", ", head_size, ")");
+    TORCH_CHECK(v.sizes() == k.sizes(), "v must have the shape of k");
+    for (const auto &[t, name] : {std::make_pair(&seqused_q, "seqused_q"), std::make_pair(&seqused_k, "seqused_k")})
+        if (t->has_value())
+            TORCH_CHECK((*t)->is_cuda() && (*t)->scalar_type() == at::kInt && (*t)->is_contiguous() && (*t)->numel() == batch_size,
+                        name, " must be int32 of shape (batch_size,)");
+    check_leftpad(leftpad_k, batch_size, paged);
+    if (leftpad_k.has_value()) TORCH_CHECK(seqused_k.has_value(), "seqused_k must be provided with k_new / leftpad_k");
+    if (kv_batch_idx.has_value()) {
+        CHECK_DEVICE(*kv_batch_idx, "cache_batch_idx");
+        TORCH_CHECK(kv_batch_idx->is_contiguous() && kv_batch_idx->numel() == batch_size, "cache_batch_idx must be contiguous, (batch_size,)");
+        TORCH_CHECK(kv_batch_idx->scalar_type() == at::kInt, "cache_batch_idx must have dtype int32");
+    } else {
+        TORCH_CHECK(batch_size_c >= batch_size, "the KV cache must have at least batch_size entries");
+    }
+    for (const auto &[t, name] : {std::make_pair(&k_descale, "k_descale"), std::make_pair(&v_descale, "v_descale")})
+        if (t->has_value())
+            TORCH_CHECK((*t)->is_cuda() && (*t)->scalar_type() == at::kFloat && (*t)->sizes() == c10::IntArrayRef({batch_size, num_heads_k}),
+                        name, " must be fp32 (batch_size, num_heads_k)");
+    for (const Tensor *t : {&k, &v}) {
+        bool ok = reinterpret_cast<uintptr_t>(t->data_ptr()) % 16 == 0;
+        for (int64_t i = 0; i < 3; ++i) ok = ok && t->stride(i) % 16 == 0;
+        TORCH_CHECK(ok, "the fp8 KV cache must be 16-byte aligned with row/head/batch strides that are multiples of 16");
+    }
+    Tensor out;
+    if (out_.has_value()) {
+        out = *out_;
+        TORCH_CHECK(out.scalar_type() == q.scalar_type(), "Output must have the same dtype as the query");
+        TORCH_CHECK(out.is_cuda() && out.stride(-1) == 1 && out.sizes() == q.sizes(), "out must have the shape of q");
+    } else {
+        out = at::empty(q.sizes(), q.options());
+    }
+    c10::hip::HIPGuardMasqueradingAsCUDA device_guard(q.device());
+    Tensor softmax_lse = ragged ? at::empty({num_heads, total_q}, q.options().dtype(at::kFloat))
+                                : at::empty({batch_size, num_heads, seqlen_q}, q.options().dtype(at::kFloat));
+    if (total_q == 0) return {out, softmax_lse};
+    if (seqlen_k == 0 || seqlen_q == 0) {
+        out.zero_();
+        softmax_lse.fill_(std::numeric_limits<float>::infinity());
+        return {out, softmax_lse};
+    }
+    const Tensor qc = aligned_or_copy(q);
+    Tensor oc = aligned(out) ? out : at::empty_like(out);
+    fa_fwd_params p{};
+    p.abi_version = FA_ABI_VERSION;
+    p.struct_size = sizeof(fa_fwd_params);
+    p.q = qc.data_ptr(); p.k = k.data_ptr(); p.v = v.data_ptr(); p.o = oc.data_ptr();
+    p.softmax_lse = static_cast<float *>(softmax_lse.data_ptr());
+    if (ragged) {
+        p.q_row_stride = qc.stride(0); p.q_head_stride = qc.stride(1);
+        p.o_row_stride = oc.stride(0); p.o_head_stride = oc.stride(1);
+        p.total_q = (int32_t)total_q;
+    } else {
+        p.q_batch_stride = qc.stride(0); p.q_row_stride = qc.stride(1); p.q_head_stride = qc.stride(2);
+        p.o_batch_stride = oc.stride(0); p.o_row_stride = oc.stride(1); p.o_head_stride = oc.stride(2);
+    }
+    p.k_batch_stride = k.stride(0); p.k_row_stride = k.stride(1); p.k_head_stride = k.stride(2);  // (elements = bytes)
+    p.v_batch_stride = v.stride(0); p.v_row_stride = v.stride(1); p.v_head_stride = v.stride(2);
+    p.b = (int32_t)batch_size; p.seqlen_q = (int32_t)seqlen_q; p.seqlen_k = (int32_t)seqlen_k;
+    p.h = (int32_t)num_heads; p.h_k = (int32_t)num_heads_k; p.d = (int32_t)head_size;
+    p.dtype = dtype_code(q);
+    p.cu_seqlens_q = static_cast<const int32_t *>(ptr(cu_seqlens_q));
+    p.seqused_q = static_cast<const int32_t *>(ptr(seqused_q));
+    p.seqused_k = static_cast<const int32_t *>(ptr(seqused_k));
+    p.softmax_scale = (float)softmax_scale;
+    p.softcap = (float)softcap;
+    p.is_causal = is_causal ? 1 : 0;
+    p.window_size_left = (int32_t)std::max<int64_t>(window_size_left, -1);
+    p.window_size_right = (int32_t)std::max<int64_t>(window_size_right, -1);
+    p.flags = FA_FLAG_FA3_WINDOW;
+    if (k_descale.has_value()) {
+        p.k_descale = static_cast<const float *>(k_descale->data_ptr());
+        p.k_descale_batch_stride = k_descale->stride(0); p.k_descale_head_stride = k_descale->stride(1);
+    }
+    if (v_descale.has_value()) {
+        p.v_descale = static_cast<const float *>(v_descale->data_ptr());
+        p.v_descale_batch_stride = v_descale->stride(0); p.v_descale_head_stride = v_descale->stride(1);
+    }
+    p.kv_batch_idx = static_cast<const int32_t *>(ptr(kv_batch_idx));
+    p.leftpad_k = static_cast<const int32_t *>(ptr(leftpad_k));
+    if (paged) {
+        p.block_table = static_cast<const int32_t *>(page_table->data_ptr());
+        p.block_table_batch_stride = page_table->stride(0);
+        p.page_block_size = (int32_t)k.size(1);
+    }
+    p.num_splits = (int32_t)std::max<int64_t>(num_splits, 0);
+    Tensor workspace;
+    const int64_t need = fa_fwd_kv8_workspace_size(&p);
+    TORCH_CHECK(need >= 0, "fa_fwd_kv8_workspace_size failed (", need, "): ", fa_strerror((int)need));
+    if (need > 0) {  // split-KV partials: scratch from torch's caching allocator (the callee never allocates)
+        workspace = at::empty({need + 256}, q.options().dtype(at::kByte));
+        const uintptr_t base = (reinterpret_cast<uintptr_t>(workspace.data_ptr()) + 255) / 256 * 256;
+        p.workspace = reinterpret_cast<void *>(base);
+        p.workspace_bytes = (uint64_t)need;
+    }
+    const int st = fa_fwd_kv8(&p, current_stream(q));
+    TORCH_CHECK(st == 0, "fa_fwd_kv8 failed (", st, "): ", fa_strerror(st));
+    if (!oc.is_same(out)) out.copy_(oc);
+    return {out, softmax_lse};
+}
+
 // flash_attn_3::fwd, hopper/flash_api.cpp:672-1198 (schema :1672-1707): the 34 positional arguments of
 // hopper/flash_attn_interface.py:66, returns (out, softmax_lse, None, None).
 // Built: fp16 / bf16 / fp8 e4m3 inputs (fp8 -> bf16 output, :859), per-(batch, kv head) q/k/v descales (:1115-1146), dense
@@ -1113,6 +1254,7 @@ std::tuple<Tensor, Tensor> fwd_kvcache_ragged(const Tensor &q, const Tensor &kca
 // route.  Accepted and rejected by message, like the reference does for compiled-out features (:1148-1165):
 // cu_seqlens_k_new without cu_seqlens_q, qv of any other shape or with fp8, KV-cache arguments together with cu_seqlens_k,
 // attention_chunk or fp8.  `scheduler_metadata` and `sm_margin` are performance hints and do not change results: ignored.
+// 16-bit q beside a Float8_e4m3fn k / v (an fp8 KV cache with k_descale / v_descale, out in q's dtype): fwd_kv8 above.
 // `pack_gqa` is a hint too: True asks every route below for the pk kernel (FA_FLAG_PACK_GQA: honoured for GQA / MQA calls of
 // 16-bit types at head dims <= 128 without attention_chunk, a V head dim of its own or qv; a no-op elsewhere and behind the
 // single-token GQA swap); False and None keep the unpacked routes (no automatic rule yet).
@@ -1132,6 +1274,26 @@ std::tuple<Tensor, Tensor, OptTensor, OptTensor> fa3_fwd_core(
     const bool is_fp8 = q_dtype == at::kFloat8_e4m3fn;
     TORCH_CHECK(q_dtype == at::kHalf || q_dtype == at::kBFloat16 || is_fp8,
                 "FlashAttention only supports fp16, bf16, and fp8_e4m3 data type");  // hopper/flash_api.cpp:714-722
+    if (!is_fp8 && k.scalar_type() == at::kFloat8_e4m3fn && v.scalar_type() == at::kFloat8_e4m3fn) {
+        // 16-bit queries over an fp8 KV cache: the kv8 route (fwd_kv8).  What it does not serve is refused by argument.
+        TORCH_CHECK(!k_new.has_value() && !v_new.has_value() && !cu_seqlens_k_new.has_value(),
+                    "This flash attention build does not support k_new / v_new with an fp8 KV cache: appending to it (quantising "
+                    "the new rows) is the caller's job.");
+        TORCH_CHECK(!rotary_cos.has_value() && !rotary_sin.has_value(),
+                    "This flash attention build does not support rotary_cos / rotary_sin with an fp8 KV cache.");
+        TORCH_CHECK(!qv.has_value(), "This flash attention build does not support qv with an fp8 KV cache.");
+        TORCH_CHECK(v.size(-1) == q.size(-1),
+                    "This flash attention build does not support a V headdim of its own with an fp8 KV cache.");
+        TORCH_CHECK(attention_chunk_.value_or(0) == 0, "This flash attention build does not support attention_chunk with an fp8 KV cache.");
+        TORCH_CHECK(q.size(-1) <= 128 && q.size(-1) % 16 == 0,
+                    "This flash attention build supports an fp8 KV cache for head_size <= 128 that is a multiple of 16, got ", q.size(-1));
+        TORCH_CHECK(!cu_seqlens_k.has_value(), "This flash attention build does not support cu_seqlens_k with an fp8 KV cache.");
+        TORCH_CHECK(!sink.has_value(), "This flash attention build does not support a learnable sink with an fp8 KV cache.");
+        auto r = fwd_kv8(q, k, v, out_, cu_seqlens_q, seqused_q, seqused_k, max_seqlen_q_, page_table, kv_batch_idx, leftpad_k,
+                         k_descale, v_descale, softmax_scale_.value_or(std::pow(double(q.size(-1)), -0.5)), is_causal,
+                         window_size_left, window_size_right, softcap, num_splits);
+        return {std::get<0>(r), std::get<1>(r), c10::nullopt, c10::nullopt};
+    }
     TORCH_CHECK(k.scalar_type() == q_dtype, "query and key must have the same dtype");
     TORCH_CHECK(v.scalar_type() == q_dtype, "query and value must have the same dtype");
     CHECK_DEVICE(q, "q"); CHECK_LAST_CONTIGUOUS(q, "Input tensor must have contiguous last dimension");

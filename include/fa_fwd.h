@@ -16,6 +16,8 @@
  *   flash_attention_forward(FlashAttentionParams&, cudaStream_t)
  *                    standalone/include/flash_api.h:222-225       fa_fwd(const fa_fwd_params*, void*)
  *   mha_fwd_kvcache  csrc/flash_attn/flash_api.cpp:1202-1476      fa_kvcache_append + fa_fwd (seqused_k, kv_batch_idx)
+ *   mha_fwd (FA3) over an fp8 KV cache, 16-bit q
+ *                    hopper/flash_api.cpp:714-760, 1115-1146      fa_fwd_kv8 (k / v e4m3 bytes + k / v descale)
  *   error codes      standalone/src/flash_api.cu:403-426          FA_ERR_* / fa_strerror
  *
  * Conventions (same as the reference's params struct):
@@ -247,7 +249,7 @@ int fa_fwd_validate(const fa_fwd_params *params);
  * device access; the text lives in thread-local storage until the next call on the same thread. */
 const char *fa_fwd_plan_name(const fa_fwd_params *params, int32_t num_cus);
 
-/* Test hook: the name of the plan the calling thread's most recent fa_fwd() launched (same text as fa_fwd_plan_name on that
+/* Test hook: the name of the plan the calling thread's most recent fa_fwd() (or fa_fwd_sink, fa_fwd_block_sparse, fa_fwd_kv8) launched (same text as fa_fwd_plan_name on that
  * call's params and the device's CU count; for a wide V run as several 256-column calls, the outer "... cols=N" plan).  NULL
  * before the first call or when that call failed validation; unspecified after a call that returned any other error (a failed
  * 256-column part leaves that part's plan).  fa_fwd keeps a struct copy; the text is made here, in
@@ -340,6 +342,40 @@ int fa_fwd_block_sparse(const fa_fwd_params *params, const fa_block_sparse_param
 /* Validation only; no device access. */
 int fa_fwd_block_sparse_validate(const fa_fwd_params *params, const fa_block_sparse_params *sparse, const fa_sink_params *sink);
 uint32_t fa_block_sparse_params_size(void);
+
+/*
+ * 16-bit queries over an fp8 (OCP e4m3fn) KV cache -- what a serving stack runs with kv_cache_dtype = fp8: q and o are fp16 /
+ * bf16 (params->dtype), k and v point at e4m3 BYTES, k / v_*_stride are in elements = bytes, and k_descale / v_descale are
+ * the fp32 dequantisation factors per (batch, kv head) through their strides (NULL = 1.0).  The result is attention over the
+ * dequantised cache: k_descale multiplies the score scale -- under softcap it acts BEFORE the tanh -- and v_descale the final
+ * normalisation; q_descale is ignored (q is not quantised).  The bytes are converted to q's type on the way to the MFMA
+ * (exact: every finite e4m3 value is a bf16 and an fp16 value), both products are the 16-bit MFMAs with fp32 accumulation.
+ * The NaN bytes 0x7f / 0xff are unspecified.  fa_fwd_params is untouched (its size is pinned): the entry point is its own,
+ * and fa_fwd / fa_fwd_validate keep refusing the all-fp8 call (dtype = FA_DTYPE_FP8_E4M3) beside KV-cache arguments.
+ * One kernel, kv8_fwd_kernel (csrc/fa_fwd_kernel_kv8.h), in the work shape of pk_fwd_kernel: a workgroup owns a block of 128
+ * (query row, head of the GQA group) pairs of one kv head, so K / V stream once per kv head for any h / h_k
+ * (FA_FLAG_PACK_GQA is meaningless here: the kernel always packs).
+ * Served: a dense cache (b_cache, seqlen_k, h_k, d) with seqused_k, kv_batch_idx and leftpad_k; a paged cache through
+ * block_table with any page_block_size >= 1; dense queries of any seqlen_q and ragged queries over the cache (cu_seqlens_q
+ * without cu_seqlens_k, seqused_k required, seqused_q); is_causal, both window sides (FA_FLAG_FA3_WINDOW as in fa_fwd),
+ * softcap; head dims <= 128 that are multiples of 16 (an e4m3 row keeps 16-byte alignment); split-KV.
+ * num_splits: 1 = off, N > 1 = N parts, 0 = fa_fwd's heuristic for the pk shape, counted from shapes only.  The parts write
+ * fp32 partial O (splits, b, seqlen_q, h, d) and LSE (splits, b, h, seqlen_q) -- ragged queries (splits, total_q, h, d) and
+ * (splits, h, total_q) -- into params->workspace (fa_fwd_kv8_workspace_size() bytes, 256-byte aligned; 0 unsplit), and the
+ * merge is one fa_fwd_combine launch over them.  A row without a visible key gives O = 0, LSE = +inf, split or not.
+ * FA_ERR_UNSUPPORTED, checked before anything the params may lack and before anything is launched: dtype fp8, d > 128 or
+ * d % 16 != 0, d_v set and != d, qv, ALiBi, dropout, attention_chunk, s_dmask, cu_seqlens_k (and, as in fa_fwd, block_table
+ * beside kv_batch_idx or leftpad_k).  k / v strides must be multiples of 16 bytes, the row strides below 2^24 bytes; the
+ * kernel rebuilds a 64-bit base per 64-key tile, so a cache entry of 2 GiB or more is served, not refused.
+ * The callee never allocates and never synchronises: the call can be captured into a HIP graph.
+ * fa_fwd_last_plan_name() names such a call "kv8_fwd_kernel D=<64|128> waves=4[ SOFTCAP] block_m=128 splits=<N>" (splits=1:
+ * the kernel stores O itself; N > 1: N parts and the merge); fa_fwd_kv8_plan_name gives the same text from params alone
+ * (num_cus is accepted for symmetry with fa_fwd_plan_name and decides nothing), NULL when fa_fwd_kv8 would reject them.
+ */
+int fa_fwd_kv8(const fa_fwd_params *params, void *stream);
+int fa_fwd_kv8_validate(const fa_fwd_params *params);
+int64_t fa_fwd_kv8_workspace_size(const fa_fwd_params *params);
+const char *fa_fwd_kv8_plan_name(const fa_fwd_params *params, int32_t num_cus);
 
 /* Human-readable text for a status code (static storage). */
 const char *fa_strerror(int status);
