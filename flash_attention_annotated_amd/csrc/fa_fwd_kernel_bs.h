@@ -16,11 +16,15 @@
 //     rule of fwd_kernel.  That rule does not look at which list a block came from: a causal diagonal block in the full list
 //     is masked all the same (the reference masks inside full blocks too, flash_attn/cute/flash_fwd.py:1985-1994);
 //   * rows without a visible key -- both counts 0 included -- end with l = 0: O = 0 and LSE = +inf, or the sink.
-// Staging, swizzle, softmax and epilogue are fwd_kernel's, restated here so that fwd_kernel's own instantiations stay
-// byte for byte what they were (tests/test_fwd_plan.py counts them).
+// The per-tile step -- softcap, element mask, online softmax, P^T pack, the 16-bit score and PV products, the pack of O into
+// LDS rows -- is fa_fwd_tile_step.h's, shared with the pk / kv8 / qv kernels.  This file owns the walk: the list chase and
+// liveness, the tile classification, fwd_kernel's staging (dv-aware V columns), the Q_IN_AGPR score product of D = 256 (asm
+// MFMAs on AGPR-pinned Q: scores_16 serves the other head dims) and fwd_kernel's epilogue (sink, rows stored by the wave's
+// own row index, no destination in the row padding).  fwd_kernel itself does not use the shared step, so its own
+// instantiations stay byte for byte what they were (tests/test_fwd_plan.py counts them).
 #pragma once
 
-#include "fa_fwd_kernel.h"
+#include "fa_fwd_tile_step.h"
 
 namespace fa {
 
@@ -205,29 +209,22 @@ __global__ __launch_bounds__(BS_NWAVES * 64, (D <= 128 ? 2 : 1)) void bs_fwd_ker
 
             // ---- S^T = K.Q^T : two 32-key blocks ------------------------------------------------
             f32x16 s[2];
+            zero_scores(s);
+            if constexpr (Q_IN_AGPR) {
 #pragma unroll
-            for (int i = 0; i < 16; ++i) { s[0][i] = 0.f; s[1][i] = 0.f; }
-#pragma unroll
-            for (int ks = 0; ks < KSTEPS; ++ks) {
-                const int off = kbase ^ (32 * ks);
-                const u32x4 kf0 = *(const u32x4 *)(kbuf + off);
-                const u32x4 kf1 = *(const u32x4 *)(kbuf + off + 32 * D * 2);
-                if constexpr (Q_IN_AGPR) {
+                for (int ks = 0; ks < KSTEPS; ++ks) {
+                    const int off = kbase ^ (32 * ks);
+                    const u32x4 kf0 = *(const u32x4 *)(kbuf + off);
+                    const u32x4 kf1 = *(const u32x4 *)(kbuf + off + 32 * D * 2);
                     Elem<T>::mma_qa(s[0], kf0, qf[ks]);
                     Elem<T>::mma_qa(s[1], kf1, qf[ks]);
-                } else {
-                    s[0] = Elem<T>::mma(kf0, qf[ks], s[0]);
-                    s[1] = Elem<T>::mma(kf1, qf[ks], s[1]);
                 }
+                asm volatile("s_nop 15\n\ts_nop 7" : "+v"(s[0]), "+v"(s[1]));  // asm MFMA results -> VALU
+            } else {
+                scores_16<T, D>(kbuf, kbase, qf, s);
             }
-            if constexpr (Q_IN_AGPR) asm volatile("s_nop 15\n\ts_nop 7" : "+v"(s[0]), "+v"(s[1]));  // asm MFMA results -> VALU
 
-            if constexpr (SOFTCAP) {
-#pragma unroll
-                for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-                    for (int i = 0; i < 16; ++i) s[kb][i] = fast_tanh(s[kb][i] * sc.softcap_pre);
-            }
+            if constexpr (SOFTCAP) softcap_scores(s, sc);
 
             // ---- the call's own mask (boundary tiles only) ------------------------------------------
             if (need_mask) {
@@ -235,69 +232,13 @@ __global__ __launch_bounds__(BS_NWAVES * 64, (D <= 128 ? 2 : 1)) void bs_fwd_ker
                 int lim_lo = 0;   // inclusive
                 if (p.window_right >= 0) lim_hi = min(sk, my_row + shift + p.window_right + 1);
                 if (p.window_left >= 0) lim_lo = max(0, my_row + shift - p.window_left);
-#pragma unroll
-                for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-                    for (int i = 0; i < 16; ++i) {
-                        const int key = k0 + kb * 32 + (i & 3) + 8 * (i >> 2) + 4 * hh;
-                        if (key >= lim_hi || key < lim_lo) s[kb][i] = -INFINITY;
-                    }
+                mask_scores(s, k0, hh, lim_lo, lim_hi);
             }
 
-            // ---- online softmax (per lane = per query row) ----------------------------------------
-            float mx = max3(s[0][0], s[1][0], m_run);
+            u32x4 pf[4];  // online softmax (per lane = per query row), then O^T += V^T.P^T
+            softmax_step<T, DBLOCKS>(s, m_run, l_run, o_acc, sc, pf);
 #pragma unroll
-            for (int i = 1; i < 16; ++i) mx = max3(mx, s[0][i], s[1][i]);
-            const float m_new = half_swap_max(mx);
-            const float m_use = (m_new == -INFINITY) ? 0.f : m_new;  // fully masked so far
-            const float mc = m_use * sc.scale_log2;
-            if (__any(m_new > m_run)) {  // wave-uniform; bit-identical to always rescaling
-                const float alpha = __builtin_amdgcn_exp2f(m_run * sc.scale_log2 - mc);
-                l_run *= alpha;
-#pragma unroll
-                for (int db = 0; db < DBLOCKS; ++db)
-#pragma unroll
-                    for (int i = 0; i < 16; ++i) o_acc[db][i] *= alpha;
-            }
-            m_run = m_new;
-            float psum = 0.f;
-#pragma unroll
-            for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-                for (int i = 0; i < 16; ++i) {
-                    const float pv = __builtin_amdgcn_exp2f(s[kb][i] * sc.scale_log2 - mc);
-                    s[kb][i] = pv;
-                    psum += pv;
-                }
-            l_run += psum;
-
-            // ---- P^T fragments: accumulator registers ARE the B operand of O^T += V^T.P^T ------------
-            u32x4 pf[4];
-#pragma unroll
-            for (int st = 0; st < 4; ++st) {
-                const int kb = st >> 1, b8 = (st & 1) * 8;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) pf[st][j] = Elem<T>::pack2(s[kb][b8 + 2 * j], s[kb][b8 + 2 * j + 1]);
-            }
-
-            // ---- O^T += V^T.P^T ----------------------------------------------------------------
-#pragma unroll
-            for (int db = 0; db < DBLOCKS; ++db) {
-#pragma unroll
-                for (int st = 0; st < 4; ++st) {
-                    u32x4 vf;
-#pragma unroll
-                    for (int j2 = 0; j2 < 2; ++j2) {
-                        const int off = (vbase ^ (64 * db + 32 * j2)) + (16 * st + 8 * j2) * (D * 2);
-                        const s16x4 tr = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-                            (__attribute__((address_space(3))) s16x4 *)(vbuf + off));
-                        const u32x2 t2 = __builtin_bit_cast(u32x2, tr);
-                        vf[2 * j2] = t2[0];
-                        vf[2 * j2 + 1] = t2[1];
-                    }
-                    o_acc[db] = Elem<T>::mma(vf, pf[st], o_acc[db]);
-                }
-            }
+            for (int db = 0; db < DBLOCKS; ++db) pv_16<T, D * 2>(vbuf, vbase, db, pf, o_acc[db]);
         }
 
         if (has_next) store_tile(cur ^ 1);
@@ -316,15 +257,7 @@ __global__ __launch_bounds__(BS_NWAVES * 64, (D <= 128 ? 2 : 1)) void bs_fwd_ker
     if (wave_active) {
         if (hh == 0 && my_row < sq) p.lse[lse_base + my_row] = lse_row;
         char *obuf = smem + wave * (32 * O_ROW_BYTES);
-#pragma unroll
-        for (int db = 0; db < DBLOCKS; ++db)
-#pragma unroll
-            for (int g4 = 0; g4 < 4; ++g4) {
-                u32x2 w;
-                w[0] = Elem<T>::pack2(o_acc[db][4 * g4] * inv, o_acc[db][4 * g4 + 1] * inv);
-                w[1] = Elem<T>::pack2(o_acc[db][4 * g4 + 2] * inv, o_acc[db][4 * g4 + 3] * inv);
-                *(u32x2 *)(obuf + r * O_ROW_BYTES + (db * 32 + 8 * g4 + 4 * hh) * 2) = w;
-            }
+        stage_o_rows<T, D>(obuf, r, hh, o_acc, inv);
     }
     __syncthreads();
     if (wave_active) {

@@ -1,4 +1,5 @@
-// fa_fwd_kernel_pk.h — gfx950 forward with the GQA group packed into the rows of a tile (PackGQA).
+// fa_fwd_kernel_pk.h — gfx950 forward with the GQA group packed into the rows of a tile (PackGQA), and the body it shares
+// with the forward over an fp8 KV cache (kv8_fwd_kernel, fa_fwd_kernel_kv8.h).
 //
 // Role of the reference's PackGQA (hopper/pack_gqa.h:18-255; requested through `pack_gqa`, FA_FLAG_PACK_GQA here): the
 // g = h / h_k query heads of one kv head share one pass over that head's K/V.  A workgroup owns a block of PACKED rows of one
@@ -7,19 +8,24 @@
 // g times as many valid rows, and K/V are streamed and multiplied once per kv head instead of once per query head.
 //
 // The tile loop is fwd_kernel's 4-wave x 32-row shape (fa_fwd_kernel.h: lane owns a row, S^T = K.Q^T, O^T = V^T.P^T, 64-key
-// tiles double-buffered in LDS, two workgroups per CU); what differs is everything that reads the row mapping:
+// tiles double-buffered in LDS, two workgroups per CU); its per-tile step and the row-staged epilogue are the shared pieces
+// of fa_fwd_tile_step.h.  packed_rows_fwd owns everything that reads the row mapping:
 //   * work item: (batch, kv head, split) groups dealt round-robin over the 8 XCDs, the row blocks of one group on one XCD
 //     (fwd_kernel_qv's decode);
 //   * Q load: per-lane address from (query row, head);
 //   * key range of a block / tile classification of a wave: from the first and last QUERY row in it;
 //   * element masks: the lane's query row, never the packed row;
 //   * sink logit: the lane's own head; load_scales stays per kv head;
-//   * epilogue: O and LSE address (query row, head).  Split partials use the layouts of fwd_kernel, so the merge is shared.
-// Not here (the plan keeps such calls on the other kernels): fp8, ALiBi, dropout, attention_chunk, a V head dim of its own,
-// qv, head dims above 128.
+//   * epilogue: O and LSE address (query row, head).  Split partials use the layouts of fwd_kernel, so the merge is shared;
+// and the dense / paged staging of a K/V tile.  What a staged tile IS -- element type, LDS image, the Q columns a k-step
+// contracts, the two operand products -- comes from the policy KV: Kv16 below (pk_fwd_kernel: K/V of type T, fwd_kernel's
+// tile) or Kv8 (fa_fwd_kernel_kv8.h: e4m3 bytes).  KV::FP8_CACHE also selects, at compile time, the contract of the entry
+// point a kernel serves; every use says what differs.
+// Not here (the plan keeps such calls on the other kernels): all-fp8, ALiBi, dropout, attention_chunk, a V head dim of its
+// own, qv, head dims above 128.
 #pragma once
 
-#include "fa_fwd_kernel.h"
+#include "fa_fwd_tile_step.h"
 
 namespace fa {
 
@@ -32,21 +38,43 @@ struct PkParams {
     int32_t num_groups;   // b * h_k * splits: (batch, kv head, split) work groups
 };
 
-template <typename T, int D, bool SOFTCAP>
-__global__ __launch_bounds__(PK_NWAVES * 64, 2) void pk_fwd_kernel(const PkParams pa) {
+// K/V tile of pk_fwd_kernel: [64][D] elements of T, the LDS image and the operand reads of fwd_kernel
+template <typename T, int D>
+struct Kv16 {
+    typedef T E;  // staged element
+    static constexpr bool FP8_CACHE = false;
+    static __device__ __forceinline__ int off(int row, int ch) { return lds_off<D>(row, ch); }
+    static __device__ __forceinline__ int q_col(int ks, int hh) { return ks * 16 + hh * 8; }  // Q columns of k-step ks: + [0, 8)
+    static __device__ __forceinline__ int kbase(int r, int hh) { return lds_off<D>(r, hh); }
+    static __device__ __forceinline__ int vbase(int lane) {
+        const int i16 = lane & 15, g1 = (lane >> 4) & 1, hh = lane >> 5;
+        return lds_off<D>(4 * hh + (i16 >> 2), 2 * g1 + ((i16 >> 1) & 1)) + 8 * (i16 & 1);
+    }
+    static __device__ __forceinline__ void scores(const char *kbuf, int kb, const u32x4 (&qf)[D / 16], f32x16 (&s)[2]) {
+        scores_16<T, D>(kbuf, kb, qf, s);
+    }
+    static __device__ __forceinline__ void pv(const char *vbuf, int vb, int db, const u32x4 (&pf)[4], f32x16 &o) {
+        pv_16<T, D * 2>(vbuf, vb, db, pf, o);
+    }
+};
+
+template <typename T, int D, bool SOFTCAP, typename KV>
+__device__ __forceinline__ void packed_rows_fwd(const PkParams &pa) {
+    typedef typename KV::E E;
     const KParams &p = pa.p;
     constexpr int NT = PK_NWAVES * 64;
     constexpr int KSTEPS = D / 16;
     constexpr int DBLOCKS = D / 32;
-    constexpr int CH_PER_ROW = D / 8;
-    constexpr int TILE_BYTES = BLOCK_N * D * 2;
+    constexpr int EPC = 16 / (int)sizeof(E);   // staged elements per 16-byte chunk
+    constexpr int CH_PER_ROW = D / EPC;        // 16-byte chunks of a key row
+    constexpr int TILE_BYTES = BLOCK_N * D * (int)sizeof(E);
     constexpr int CHUNKS = BLOCK_N * CH_PER_ROW;
     constexpr int LD_PER_THREAD = CHUNKS / NT;
     static_assert(CHUNKS % NT == 0, "tile must divide over the workgroup");
-    constexpr int O_ROW_BYTES = D * 2 + 16;    // padded epilogue row; the padding carries the row's O offset
+    constexpr int O_ROW_BYTES = o_row_bytes(D);  // padded epilogue row; the padding carries the row's O offset
 
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    // [K0 | K1 | V0 | V1]; the epilogue reuses the whole region as PK_NWAVES x [32][O_ROW_BYTES]
+    // [K0 | K1 | V0 | V1]; the epilogue reuses the region as PK_NWAVES x [32][O_ROW_BYTES] (the launch sizes it for the larger)
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -72,13 +100,16 @@ __global__ __launch_bounds__(PK_NWAVES * 64, 2) void pk_fwd_kernel(const PkParam
     } else {
         sq = p.seqused_q ? p.seqused_q[batch] : p.seqlen_q;
     }
-    if (p.cu_seqlens_k) {
+    bool ragged_k = false;
+    if constexpr (!KV::FP8_CACHE) ragged_k = p.cu_seqlens_k != nullptr;  // (fa_fwd_kv8_validate refuses cu_seqlens_k)
+    if (ragged_k) {
         const int k0 = p.cu_seqlens_k[batch];
         sk = p.seqused_k ? p.seqused_k[batch] : p.cu_seqlens_k[batch + 1] - k0;
         k_base = (int64_t)k0 * p.k_row_stride;
         v_base = (int64_t)k0 * p.v_row_stride;
     } else {
         sk = p.seqused_k ? p.seqused_k[batch] : p.seqlen_k;
+        if constexpr (KV::FP8_CACHE) sk = min(sk, p.seqlen_k);  // a cache: never past the capacity
         const int kv_batch = p.kv_batch_idx ? p.kv_batch_idx[batch] : batch;
         k_base = (int64_t)kv_batch * p.k_batch_stride;
         v_base = (int64_t)kv_batch * p.v_batch_stride;
@@ -94,8 +125,8 @@ __global__ __launch_bounds__(PK_NWAVES * 64, 2) void pk_fwd_kernel(const PkParam
     }
     if (p.block_table) k_base = v_base = 0;  // paged: the page supplies the batch offset
     const int32_t *pages = p.block_table ? p.block_table + (int64_t)batch * p.bt_bs : nullptr;
-    const T *kp = (const T *)p.k + k_base + (int64_t)kv_head * p.k_head_stride;
-    const T *vp = (const T *)p.v + v_base + (int64_t)kv_head * p.v_head_stride;
+    const E *kp = (const E *)p.k + k_base + (int64_t)kv_head * p.k_head_stride;
+    const E *vp = (const E *)p.v + v_base + (int64_t)kv_head * p.v_head_stride;
     const Scales sc = load_scales(p, batch, kv_head);
 
     // ---- the wave's packed rows, the lane's query row and head -----------------------------------------------------------------
@@ -121,18 +152,25 @@ __global__ __launch_bounds__(PK_NWAVES * 64, 2) void pk_fwd_kernel(const PkParam
     int n_max = key_hi > 0 ? (key_hi + BLOCK_N - 1) / BLOCK_N : 0;
     split_range(p, split, n_min, n_max);
 
-    // ---- Q fragments: B operand of S^T = K.Q^T; lane (r,hh) holds Q[row r][16ks + 8hh .. +8] (branch-free, zeroed by selects)
+    // the lane's own key range [lim_lo, lim_hi), from its QUERY row: the element mask of the boundary tiles, and (the fp8
+    // cache's split convention below) whether the row sees a key at all
+    int lim_hi = sk, lim_lo = 0;
+    if (p.window_right >= 0) lim_hi = min(sk, my_row + shift + p.window_right + 1);
+    if (p.window_left >= 0) lim_lo = max(0, my_row + shift - p.window_left);
+
+    // ---- Q fragments: B operand of S^T = K.Q^T; k-step ks of lane (r, hh) holds Q[row r][KV::q_col(ks, hh) .. + 8]
+    // (branch-free, zeroed by selects)
     u32x4 qf[KSTEPS];
     {
         const T *qr = (const T *)p.q + bq * p.q_batch_stride + row_g * p.q_row_stride + (int64_t)head * p.q_head_stride;
 #pragma unroll
         for (int ks = 0; ks < KSTEPS; ++ks) {
-            const int d0 = ks * 16 + hh * 8;
+            const int d0 = KV::q_col(ks, hh);
             qf[ks] = *(const u32x4 *)(qr + (d0 < p.d ? d0 : 0));
         }
         const u32x4 z4 = {0, 0, 0, 0};
 #pragma unroll
-        for (int ks = 0; ks < KSTEPS; ++ks) qf[ks] = (ks * 16 + hh * 8 < p.d && row_ok) ? qf[ks] : z4;
+        for (int ks = 0; ks < KSTEPS; ++ks) qf[ks] = (KV::q_col(ks, hh) < p.d && row_ok) ? qf[ks] : z4;
     }
 
     f32x16 o_acc[DBLOCKS];
@@ -143,17 +181,19 @@ __global__ __launch_bounds__(PK_NWAVES * 64, 2) void pk_fwd_kernel(const PkParam
     float m_run = -INFINITY;  // running row max (unscaled scores), same in both lane halves
     float l_run = 0.f;        // running row sum, PARTIAL per lane half (combined in the epilogue)
 
-    // ---- K/V staging (fwd_kernel's: clamped rows / chunks, the duplicates are masked or meet zero Q columns) --------------
+    // ---- K/V staging, 16 bytes per load (fwd_kernel's: clamped rows / chunks, the duplicates are masked or meet zero Q
+    // columns; every staged chunk comes from a valid key row).  Every tile is addressed from a 64-bit base that is rebuilt per
+    // tile (cache entry or page, first key row of the tile, kv head); the lane offset inside a tile is 32-bit ---------------
     u32x4 kreg[LD_PER_THREAD], vreg[LD_PER_THREAD];
     static_assert(NT % CH_PER_ROW == 0, "a pass of the workgroup covers whole rows");
     constexpr int ROWS_PER_PASS = NT / CH_PER_ROW;
     const int ld_row0 = tid / CH_PER_ROW;
-    const int ld_col0 = ((tid % CH_PER_ROW) * 8 < p.d) ? (tid % CH_PER_ROW) * 8 : 0;
+    const int ld_col0 = ((tid % CH_PER_ROW) * EPC < p.d) ? (tid % CH_PER_ROW) * EPC : 0;
     const int k_rs = (int)p.k_row_stride, v_rs = (int)p.v_row_stride;  // host guarantees 64 * stride < 2^31
     auto load_tile = [&](int n) {
         const int k0 = n * BLOCK_N;
-        const T *kt = kp + (int64_t)k0 * p.k_row_stride;
-        const T *vt = vp + (int64_t)k0 * p.v_row_stride;
+        const E *kt = kp + (int64_t)k0 * p.k_row_stride;
+        const E *vt = vp + (int64_t)k0 * p.v_row_stride;
         const int last = sk - 1 - k0;                     // >= 0 for every tile in [n_min, n_max)
         if (pages) {
             if (p.page_size % BLOCK_N == 0) {  // a 64-key tile lies inside one page
@@ -184,17 +224,15 @@ __global__ __launch_bounds__(PK_NWAVES * 64, 2) void pk_fwd_kernel(const PkParam
 #pragma unroll
         for (int i = 0; i < LD_PER_THREAD; ++i) {
             const int c = tid + i * NT;
-            const int off = lds_off<D>(c / CH_PER_ROW, c % CH_PER_ROW);
+            const int off = KV::off(c / CH_PER_ROW, c % CH_PER_ROW);
             *(u32x4 *)(smem + buf * TILE_BYTES + off) = kreg[i];
             *(u32x4 *)(smem + (2 + buf) * TILE_BYTES + off) = vreg[i];
         }
     };
 
-    // lane-constant pieces of the LDS read addresses (fa_fwd_kernel.h)
-    const int i16 = lane & 15;
-    const int g1 = (lane >> 4) & 1;
-    const int kbase = lds_off<D>(r, hh);
-    const int vbase = lds_off<D>(4 * hh + (i16 >> 2), 2 * g1 + ((i16 >> 1) & 1)) + 8 * (i16 & 1);
+    // lane-constant pieces of the LDS read addresses
+    const int kbase = KV::kbase(r, hh);
+    const int vbase = KV::vbase(lane);
 
     if (n_min < n_max) {
         load_tile(n_min);
@@ -221,99 +259,19 @@ __global__ __launch_bounds__(PK_NWAVES * 64, 2) void pk_fwd_kernel(const PkParam
             need_mask = need_mask || (k0 < wq_hi + shift - p.window_left);
         }
 
-        if (!skip) {
+        if (!skip) {  // (wave-uniform: EXEC is full at the transposed reads)
             const char *kbuf = smem + cur * TILE_BYTES;
             const char *vbuf = smem + (2 + cur) * TILE_BYTES;
 
-            // ---- S^T = K.Q^T : two 32-key blocks --------------------------------------------------------------------------
-            f32x16 s[2];
-#pragma unroll
-            for (int i = 0; i < 16; ++i) { s[0][i] = 0.f; s[1][i] = 0.f; }
-#pragma unroll
-            for (int ks = 0; ks < KSTEPS; ++ks) {
-                const int off = kbase ^ (32 * ks);  // = lds_off<D>(r, 2 ks + hh)
-                const u32x4 kf0 = *(const u32x4 *)(kbuf + off);
-                const u32x4 kf1 = *(const u32x4 *)(kbuf + off + 32 * D * 2);
-                s[0] = Elem<T>::mma(kf0, qf[ks], s[0]);
-                s[1] = Elem<T>::mma(kf1, qf[ks], s[1]);
-            }
-
-            if constexpr (SOFTCAP) {
-#pragma unroll
-                for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-                    for (int i = 0; i < 16; ++i) s[kb][i] = fast_tanh(s[kb][i] * sc.softcap_pre);
-            }
-
-            // ---- mask (boundary tiles only): the lane's QUERY row ----------------------------------------------------------
-            if (need_mask) {
-                int lim_hi = sk;  // exclusive
-                int lim_lo = 0;   // inclusive
-                if (p.window_right >= 0) lim_hi = min(sk, my_row + shift + p.window_right + 1);
-                if (p.window_left >= 0) lim_lo = max(0, my_row + shift - p.window_left);
-#pragma unroll
-                for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-                    for (int i = 0; i < 16; ++i) {
-                        const int key = k0 + kb * 32 + (i & 3) + 8 * (i >> 2) + 4 * hh;
-                        if (key >= lim_hi || key < lim_lo) s[kb][i] = -INFINITY;
-                    }
-            }
-
-            // ---- online softmax (per lane = per packed row) ---------------------------------------------------------------
-            float mx = max3(s[0][0], s[1][0], m_run);
-#pragma unroll
-            for (int i = 1; i < 16; ++i) mx = max3(mx, s[0][i], s[1][i]);
-            const float m_new = half_swap_max(mx);  // >= m_run (m_run is identical in both halves)
-            const float m_use = (m_new == -INFINITY) ? 0.f : m_new;  // fully masked so far
-            const float mc = m_use * sc.scale_log2;
-            if (__any(m_new > m_run)) {  // wave-uniform; bit-identical to always rescaling
-                const float alpha = __builtin_amdgcn_exp2f(m_run * sc.scale_log2 - mc);
-                l_run *= alpha;
-#pragma unroll
-                for (int db = 0; db < DBLOCKS; ++db)
-#pragma unroll
-                    for (int i = 0; i < 16; ++i) o_acc[db][i] *= alpha;
-            }
-            m_run = m_new;
-            float psum = 0.f;
-#pragma unroll
-            for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-                for (int i = 0; i < 16; ++i) {
-                    const float pv = __builtin_amdgcn_exp2f(s[kb][i] * sc.scale_log2 - mc);
-                    s[kb][i] = pv;
-                    psum += pv;
-                }
-            l_run += psum;
-
-            // ---- P^T fragments: accumulator registers ARE the B operand of O^T += V^T.P^T ------------------------------------
+            f32x16 s[2];  // S^T = K.Q^T : two 32-key blocks
+            zero_scores(s);
+            KV::scores(kbuf, kbase, qf, s);
+            if constexpr (SOFTCAP) softcap_scores(s, sc);
+            if (need_mask) mask_scores(s, k0, hh, lim_lo, lim_hi);  // boundary tiles only
             u32x4 pf[4];
+            softmax_step<T, DBLOCKS>(s, m_run, l_run, o_acc, sc, pf);
 #pragma unroll
-            for (int st = 0; st < 4; ++st) {
-                const int kb = st >> 1, b8 = (st & 1) * 8;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) pf[st][j] = Elem<T>::pack2(s[kb][b8 + 2 * j], s[kb][b8 + 2 * j + 1]);
-            }
-
-            // ---- O^T += V^T.P^T -------------------------------------------------------------------------------------------
-#pragma unroll
-            for (int db = 0; db < DBLOCKS; ++db) {
-#pragma unroll
-                for (int st = 0; st < 4; ++st) {
-                    u32x4 vf;
-#pragma unroll
-                    for (int j2 = 0; j2 < 2; ++j2) {
-                        const int off = (vbase ^ (64 * db + 32 * j2)) + (16 * st + 8 * j2) * (D * 2);
-                        const s16x4 t = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-                            (__attribute__((address_space(3))) s16x4 *)(vbuf + off));
-                        const u32x2 t2 = __builtin_bit_cast(u32x2, t);
-                        vf[2 * j2] = t2[0];
-                        vf[2 * j2 + 1] = t2[1];
-                    }
-                    o_acc[db] = Elem<T>::mma(vf, pf[st], o_acc[db]);
-                }
-            }
+            for (int db = 0; db < DBLOCKS; ++db) KV::pv(vbuf, vbase, db, pf, o_acc[db]);  // O^T += V^T.P^T
         }
 
         if (has_next) store_tile(cur ^ 1);
@@ -324,10 +282,18 @@ __global__ __launch_bounds__(PK_NWAVES * 64, 2) void pk_fwd_kernel(const PkParam
     // (the loop's last barrier has retired every K/V read, so the region can be reused)
     const float l_tot = half_swap_sum(l_run);
     const bool empty = (l_tot == 0.f) || (l_tot != l_tot);
-    float inv = empty ? 1.f : 1.f / l_tot;
+    float inv;
     float lse_row = empty ? INFINITY : m_run * sc.scale + __logf(l_tot);  // +inf for rows with no valid key, as fwd_kernel
-    if (p.sink)  // the lane's own head
-        sink_finalize(row_ok ? load_sink(p, head, my_row) : -INFINITY, m_run * sc.scale, l_tot, empty, inv, lse_row);
+    if constexpr (KV::FP8_CACHE) {
+        inv = empty ? 0.f : sc.v_descale / l_tot;  // v_descale rides in the factor
+        // split-KV partials follow fa_fwd_combine's convention (the merge of fa_fwd_kv8 is that entry point): a part that holds
+        // none of the row's keys carries no weight (-inf); a row without any key keeps +inf.  No sink (fa_fwd_kv8_validate)
+        if (p.num_splits > 1 && empty && lim_lo < lim_hi) lse_row = -INFINITY;
+    } else {
+        inv = empty ? 1.f : 1.f / l_tot;
+        if (p.sink)  // the lane's own head
+            sink_finalize(row_ok ? load_sink(p, head, my_row) : -INFINITY, m_run * sc.scale, l_tot, empty, inv, lse_row);
+    }
     const int64_t o_off = bq * p.o_batch_stride + row_g * p.o_row_stride + (int64_t)head * p.o_head_stride;
     if (wave_active) {
         if (hh == 0 && row_ok) {
@@ -335,60 +301,21 @@ __global__ __launch_bounds__(PK_NWAVES * 64, 2) void pk_fwd_kernel(const PkParam
             p.lse[li + split * p.lse_split_stride] = lse_row;
         }
         if (p.num_splits > 1) {
-            // split-KV partial: fp32 in the caller's workspace, straight from the accumulators (fwd_kernel's layout)
-            float *opf = (float *)p.o + split * p.o_split_stride + o_off;
-            if (row_ok) {
-#pragma unroll
-                for (int db = 0; db < DBLOCKS; ++db)
-#pragma unroll
-                    for (int g4 = 0; g4 < 4; ++g4) {
-                        const int col = db * 32 + 8 * g4 + 4 * hh;
-                        if (col < p.d)
-                            *(float4 *)(opf + col) = make_float4(o_acc[db][4 * g4] * inv, o_acc[db][4 * g4 + 1] * inv,
-                                                                 o_acc[db][4 * g4 + 2] * inv, o_acc[db][4 * g4 + 3] * inv);
-                    }
-            }
+            if (row_ok) store_split_partial((float *)p.o + split * p.o_split_stride + o_off, o_acc, inv, 0, hh, p.d);
         } else {
             char *obuf = smem + wave * (32 * O_ROW_BYTES);
-#pragma unroll
-            for (int db = 0; db < DBLOCKS; ++db)
-#pragma unroll
-                for (int g4 = 0; g4 < 4; ++g4) {
-                    u32x2 w;
-                    w[0] = Elem<T>::pack2(o_acc[db][4 * g4] * inv, o_acc[db][4 * g4 + 1] * inv);
-                    w[1] = Elem<T>::pack2(o_acc[db][4 * g4 + 2] * inv, o_acc[db][4 * g4 + 3] * inv);
-                    *(u32x2 *)(obuf + r * O_ROW_BYTES + (db * 32 + 8 * g4 + 4 * hh) * 2) = w;
-                }
-            // the row's destination rides in the padding of its LDS row: the lanes that store a row are not the lane that owns it
-            if (hh == 0) {
-                *(int64_t *)(obuf + r * O_ROW_BYTES + D * 2) = o_off;
-                *(int32_t *)(obuf + r * O_ROW_BYTES + D * 2 + 8) = row_ok ? 1 : 0;
-            }
+            stage_o_rows<T, D>(obuf, r, hh, o_acc, inv);
+            if (hh == 0) stage_o_dest<D>(obuf, r, o_off, row_ok);
         }
     }
     if (p.num_splits > 1) return;  // (uniform over the launch: no wave is left waiting at the barrier below)
     __syncthreads();
-    if (wave_active) {
-        const char *obuf = smem + wave * (32 * O_ROW_BYTES);
-        // (LDS reads outside the predicate: all of them are issued before the first store)
-        constexpr int NCH = (32 * CH_PER_ROW) / 64;
-        u32x4 val[NCH];
-        int64_t dst[NCH];
-        int32_t ok[NCH];
-#pragma unroll
-        for (int i = 0; i < NCH; ++i) {
-            const int c = lane + i * 64;
-            const char *row = obuf + (c / CH_PER_ROW) * O_ROW_BYTES;
-            val[i] = *(const u32x4 *)(row + (c % CH_PER_ROW) * 16);
-            dst[i] = *(const int64_t *)(row + D * 2);
-            ok[i] = *(const int32_t *)(row + D * 2 + 8);
-        }
-#pragma unroll
-        for (int i = 0; i < NCH; ++i) {
-            const int ch = (lane + i * 64) % CH_PER_ROW;
-            if (ok[i] && ch * 8 < p.d) *(u32x4 *)((T *)p.o + dst[i] + ch * 8) = val[i];
-        }
-    }
+    if (wave_active) store_staged_rows<T, D>(smem + wave * (32 * O_ROW_BYTES), lane, (T *)p.o, p.d);
+}
+
+template <typename T, int D, bool SOFTCAP>
+__global__ __launch_bounds__(PK_NWAVES * 64, 2) void pk_fwd_kernel(const PkParams pa) {
+    packed_rows_fwd<T, D, SOFTCAP, Kv16<T, D>>(pa);
 }
 
 }  // namespace fa

@@ -17,9 +17,14 @@
 //   * wave w accumulates O^T for its DVT/4 columns of all 32 rows: 4 (DVT 512) or 2 (DVT 256) f32x16 accumulators.
 //   * the next tile's K/V rows are loaded into registers before the compute of the current one and written to LDS behind
 //     it (single LDS buffer, barriers between the phases).
+// Softcap, element mask, online softmax, P^T pack, the transposed PV product of a column block and the fp32 split-partial
+// store are fa_fwd_tile_step.h's, shared with the pk / kv8 / bs kernels.  This file owns the rest: the work-item decode, the
+// K + V staging of different widths, the per-wave partial score products (one K step, KSV steps along V rows: not scores_16's
+// D / 16 steps over one tile) and their meeting in LDS behind a barrier of its own, the attention_chunk limits, and the
+// epilogue that stores O rows straight from the accumulators.
 #pragma once
 
-#include "fa_fwd_kernel.h"
+#include "fa_fwd_tile_step.h"
 
 namespace fa {
 
@@ -248,8 +253,7 @@ __global__ __launch_bounds__(QV_NWAVES * 64, 1) void fwd_kernel_qv(const QvParam
         if (!skip) {
             // ---- partial S^T of this wave: K step `wave` + its quarter of the V columns --------------------------------
             f32x16 s[2];
-#pragma unroll
-            for (int i = 0; i < 16; ++i) { s[0][i] = 0.f; s[1][i] = 0.f; }
+            zero_scores(s);
             {
                 const u32x4 kf0 = *(const u32x4 *)(kbuf + kbase);
                 const u32x4 kf1 = *(const u32x4 *)(kbuf + kbase + 32 * 64 * 2);
@@ -286,12 +290,7 @@ __global__ __launch_bounds__(QV_NWAVES * 64, 1) void fwd_kernel_qv(const QvParam
                 s[j >> 2][b4] = a.x; s[j >> 2][b4 + 1] = a.y; s[j >> 2][b4 + 2] = a.z; s[j >> 2][b4 + 3] = a.w;
             }
 
-            if constexpr (SOFTCAP) {
-#pragma unroll
-                for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-                    for (int i = 0; i < 16; ++i) s[kb][i] = fast_tanh(s[kb][i] * sc.softcap_pre);
-            }
+            if constexpr (SOFTCAP) softcap_scores(s, sc);
             if (need_mask) {
                 int lim_hi = sk, lim_lo = 0;
                 if (p.window_right >= 0) lim_hi = min(sk, my_row + shift + p.window_right + 1);
@@ -301,69 +300,14 @@ __global__ __launch_bounds__(QV_NWAVES * 64, 1) void fwd_kernel_qv(const QvParam
                     lim_lo = max(lim_lo, c_lo);
                     lim_hi = min(lim_hi, c_lo + p.chunk);
                 }
-#pragma unroll
-                for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-                    for (int i = 0; i < 16; ++i) {
-                        const int key = k0 + kb * 32 + (i & 3) + 8 * (i >> 2) + 4 * hh;
-                        if (key >= lim_hi || key < lim_lo) s[kb][i] = -INFINITY;
-                    }
+                mask_scores(s, k0, hh, lim_lo, lim_hi);
             }
 
-            // ---- online softmax (lane = packed row) ---------------------------------------------------------------------
-            float mx = max3(s[0][0], s[1][0], m_run);
-#pragma unroll
-            for (int i = 1; i < 16; ++i) mx = max3(mx, s[0][i], s[1][i]);
-            const float m_new = half_swap_max(mx);
-            const float m_use = (m_new == -INFINITY) ? 0.f : m_new;
-            const float mc = m_use * sc.scale_log2;
-            if (__any(m_new > m_run)) {
-                const float alpha = __builtin_amdgcn_exp2f(m_run * sc.scale_log2 - mc);
-                l_run *= alpha;
-#pragma unroll
-                for (int db = 0; db < DBW; ++db)
-#pragma unroll
-                    for (int i = 0; i < 16; ++i) o_acc[db][i] *= alpha;
-            }
-            m_run = m_new;
-            float psum = 0.f;
-#pragma unroll
-            for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-                for (int i = 0; i < 16; ++i) {
-                    const float pv = __builtin_amdgcn_exp2f(s[kb][i] * sc.scale_log2 - mc);
-                    s[kb][i] = pv;
-                    psum += pv;
-                }
-            l_run += psum;
-
-            u32x4 pf[4];
-#pragma unroll
-            for (int st = 0; st < 4; ++st) {
-                const int kb = st >> 1, b8 = (st & 1) * 8;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) pf[st][j] = Elem<T>::pack2(s[kb][b8 + 2 * j], s[kb][b8 + 2 * j + 1]);
-            }
-
+            u32x4 pf[4];  // online softmax (lane = packed row; identical in every wave)
+            softmax_step<T, DBW>(s, m_run, l_run, o_acc, sc, pf);
             // ---- O^T += V^T.P^T over this wave's column blocks ----------------------------------------------------------
 #pragma unroll
-            for (int dbl = 0; dbl < DBW; ++dbl) {
-                const int db = DBW * wave + dbl;
-#pragma unroll
-                for (int st = 0; st < 4; ++st) {
-                    u32x4 vf;
-#pragma unroll
-                    for (int j2 = 0; j2 < 2; ++j2) {
-                        const int off = (vbase ^ (64 * db + 32 * j2)) + (16 * st + 8 * j2) * (DVT * 2);
-                        const s16x4 t = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-                            (__attribute__((address_space(3))) s16x4 *)(vbuf + off));
-                        const u32x2 t2 = __builtin_bit_cast(u32x2, t);
-                        vf[2 * j2] = t2[0];
-                        vf[2 * j2 + 1] = t2[1];
-                    }
-                    o_acc[dbl] = Elem<T>::mma(vf, pf[st], o_acc[dbl]);
-                }
-            }
+            for (int dbl = 0; dbl < DBW; ++dbl) pv_16<T, DVT * 2>(vbuf, vbase, DBW * wave + dbl, pf, o_acc[dbl]);
         }
         __syncthreads();  // every read of the K/V tile and of the partial scores is done
         if (has_next) {
@@ -386,16 +330,7 @@ __global__ __launch_bounds__(QV_NWAVES * 64, 1) void fwd_kernel_qv(const QvParam
     const int64_t o_off = (p.cu_seqlens_q ? 0 : (int64_t)batch * p.o_batch_stride) + row_o * p.o_row_stride +
                           (int64_t)head * p.o_head_stride;
     if (p.num_splits > 1) {
-        float *opf = (float *)p.o + split * p.o_split_stride + o_off;
-#pragma unroll
-        for (int dbl = 0; dbl < DBW; ++dbl)
-#pragma unroll
-            for (int g4 = 0; g4 < 4; ++g4) {
-                const int col = CPW * wave + dbl * 32 + 8 * g4 + 4 * hh;
-                if (col < p.dv)
-                    *(float4 *)(opf + col) = make_float4(o_acc[dbl][4 * g4] * inv, o_acc[dbl][4 * g4 + 1] * inv,
-                                                         o_acc[dbl][4 * g4 + 2] * inv, o_acc[dbl][4 * g4 + 3] * inv);
-            }
+        store_split_partial((float *)p.o + split * p.o_split_stride + o_off, o_acc, inv, CPW * wave, hh, p.dv);
     } else {
         T *op = (T *)p.o + o_off;
 #pragma unroll
