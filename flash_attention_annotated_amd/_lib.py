@@ -56,6 +56,9 @@ EXPORTED_SYMBOLS = (
     "fa_fwd_kv8_validate",
     "fa_fwd_kv8_workspace_size",
     "fa_fwd_kv8_plan_name",
+    "fa_kvcache_append_kv8",
+    "fa_kvcache_append_kv8_validate",
+    "fa_kvcache_append_kv8_params_size",
     # include/fa_bwd.h
     "fa_bwd",
     "fa_bwd_validate",
@@ -208,6 +211,23 @@ class FaKvcacheAppendVarlenParams(ctypes.Structure):
     )
 
 
+class FaKvcacheAppendKv8Params(ctypes.Structure):
+    """Field-for-field mirror of `struct fa_kvcache_append_kv8_params` (include/fa_fwd.h)."""
+
+    _fields_ = (
+        [("abi_version", ctypes.c_uint32), ("struct_size", ctypes.c_uint32)]
+        + [(n, ctypes.c_void_p) for n in ("k_new", "v_new", "k_cache", "v_cache")]
+        + [(f"{t}_{s}_stride", ctypes.c_int64) for t in ("knew", "vnew", "kcache", "vcache")
+           for s in ("batch", "row", "head")]
+        + [(n, ctypes.c_int32) for n in ("b", "seqlen_new", "total_k_new", "max_seqlen_k_new", "seqlen_cache", "h_k", "d", "d_v",
+                                         "dtype", "page_block_size", "rotary_dim", "rotary_interleaved")]
+        + [(n, ctypes.c_void_p) for n in ("cu_seqlens_k_new", "cache_seqlens", "cache_batch_idx", "seqused_out", "block_table")]
+        + [("block_table_batch_stride", ctypes.c_int64)]
+        + [(n, ctypes.c_void_p) for n in ("rotary_cos", "rotary_sin", "rotary_seqlens", "k_descale", "v_descale")]
+        + [(f"{t}_descale_{s}_stride", ctypes.c_int64) for t in ("k", "v") for s in ("batch", "head")]
+    )
+
+
 class FaRotaryVarlenParams(ctypes.Structure):
     """Field-for-field mirror of `struct fa_rotary_varlen_params` (include/fa_fwd.h)."""
 
@@ -309,7 +329,8 @@ def is_stale():
 
 def build(force=False, verbose=False):
     """Compile csrc/ for gfx950 into the in-tree shared library (hipcc cross-compiles without a GPU)."""
-    srcs = [os.path.join(CSRC, f) for f in ("fa_fwd_api.hip", "fa_fwd_kv8_api.hip", "fa_bwd_api.hip", "fa_bwd_bs_api.hip")]
+    srcs = [os.path.join(CSRC, f) for f in ("fa_fwd_api.hip", "fa_fwd_kv8_api.hip", "fa_kvcache_append_kv8.hip", "fa_bwd_api.hip",
+                                              "fa_bwd_bs_api.hip")]
     if not force and not is_stale():
         return LIB_PATH
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -445,6 +466,14 @@ def load():
     lib.fa_fwd_kv8_workspace_size.restype = ctypes.c_int64
     lib.fa_fwd_kv8_plan_name.argtypes = [ctypes.POINTER(FaFwdParams), ctypes.c_int32]
     lib.fa_fwd_kv8_plan_name.restype = ctypes.c_char_p
+    lib.fa_kvcache_append_kv8.argtypes = [ctypes.POINTER(FaKvcacheAppendKv8Params), ctypes.c_void_p]
+    lib.fa_kvcache_append_kv8.restype = ctypes.c_int
+    lib.fa_kvcache_append_kv8_validate.argtypes = [ctypes.POINTER(FaKvcacheAppendKv8Params)]
+    lib.fa_kvcache_append_kv8_validate.restype = ctypes.c_int
+    lib.fa_kvcache_append_kv8_params_size.argtypes = []
+    lib.fa_kvcache_append_kv8_params_size.restype = ctypes.c_uint32
+    if lib.fa_kvcache_append_kv8_params_size() != ctypes.sizeof(FaKvcacheAppendKv8Params):
+        raise RuntimeError("fa_kvcache_append_kv8_params layout mismatch between include/fa_fwd.h and _lib")
     lib.fa_sink_grad.argtypes = [ctypes.POINTER(FaSinkGradParams), ctypes.c_void_p]
     lib.fa_sink_grad.restype = ctypes.c_int
     lib.fa_sink_grad_validate.argtypes = [ctypes.POINTER(FaSinkGradParams)]
@@ -548,6 +577,14 @@ def new_sink_grad_params():
     p.abi_version = FA_ABI_VERSION
     p.struct_size = ctypes.sizeof(FaSinkGradParams)
     p.sink_dtype = FA_DTYPE_BF16
+    return p
+
+
+def new_kvcache_append_kv8_params():
+    p = FaKvcacheAppendKv8Params()
+    p.abi_version = FA_ABI_VERSION
+    p.struct_size = ctypes.sizeof(FaKvcacheAppendKv8Params)
+    p.dtype = FA_DTYPE_BF16
     return p
 
 

@@ -1106,7 +1106,8 @@ std::tuple<Tensor, Tensor> fwd_kvcache_ragged(const Tensor &q, const Tensor &kca
 // out fp16 / bf16, k / v the cache as Float8_e4m3fn, (b_cache, seqlen_k, h_k, d) or pages behind page_table, k_descale /
 // v_descale fp32 (b, h_k).  Dense q (b, seqlen_q, h, d) or ragged q (total_q, h, d) with cu_seqlens_q; cache_seqlens in
 // seqused_k.  One kernel for every h / h_k (it packs the GQA group into its rows itself: no swap, pack_gqa is moot).
-// The caller has refused what the route does not serve (new rows, rotary, qv, attention_chunk, head dims).
+// The caller has appended the step's new rows and rotated q (fa3_fwd_core) and refused what the route does not serve (qv,
+// attention_chunk, head dims).
 std::tuple<Tensor, Tensor> fwd_kv8(const Tensor &q, const Tensor &k, const Tensor &v, const OptTensor &out_,
                                    const OptTensor &cu_seqlens_q, const OptTensor &seqused_q, const OptTensor &seqused_k,
                                    c10::optional<int64_t> max_seqlen_q_, const OptTensor &page_table, const OptTensor &kv_batch_idx,
@@ -1243,6 +1244,147 @@ std::tuple<Tensor, Tensor> fwd_kv8(const Tensor &q, const Tensor &k, const Tenso
     return {out, softmax_lse};
 }
 
+// The write half of an fp8 (e4m3) KV cache (include/fa_fwd.h, fa_kvcache_append_kv8): new 16-bit rows -- dense (b, s_new, h_k, d)
+// or ragged (total_k_new, h_k, d) with cu_seqlens_k_new -- are rotated (keys), divided by the descale of their (sequence, kv
+// head), converted to e4m3 and stored at cache_seqlens[s] + i of the batched or paged cache.  Every check runs before the one
+// launch; nothing reads device data.  Returns the new fill levels min(cache_seqlens + new rows, capacity), written by the launch.
+Tensor kvcache_append_kv8(const Tensor &k_cache, const Tensor &v_cache, const Tensor &k_new, const Tensor &v_new,
+                          const Tensor &cache_seqlens, const Tensor &k_descale, const Tensor &v_descale,
+                          const OptTensor &cu_seqlens_k_new, int64_t max_seqlen_k_new, const OptTensor &cache_batch_idx,
+                          const OptTensor &page_table, const OptTensor &rotary_cos, const OptTensor &rotary_sin,
+                          const OptTensor &rotary_seqlens, bool rotary_interleaved) {
+    TORCH_CHECK(k_cache.scalar_type() == at::kFloat8_e4m3fn && v_cache.scalar_type() == at::kFloat8_e4m3fn,
+                "the fp8 KV cache must have dtype torch.float8_e4m3fn");
+    TORCH_CHECK(k_new.scalar_type() != at::kFloat8_e4m3fn && v_new.scalar_type() != at::kFloat8_e4m3fn,
+                "This flash attention build does not support fp8 k_new / v_new with an fp8 KV cache: the new rows are fp16 / "
+                "bf16 and are quantised by the append.");
+    const auto new_dtype = k_new.scalar_type();
+    TORCH_CHECK(new_dtype == at::kHalf || new_dtype == at::kBFloat16, "k_new / v_new must be fp16 or bf16");
+    TORCH_CHECK(v_new.scalar_type() == new_dtype, "k_new and v_new must have the same dtype");
+    CHECK_DEVICE(k_cache, "k_cache"); CHECK_DEVICE(v_cache, "v_cache"); CHECK_DEVICE(k_new, "k_new"); CHECK_DEVICE(v_new, "v_new");
+    TORCH_CHECK(k_cache.dim() == 4 && v_cache.dim() == 4,
+                "an fp8 k / v must be a KV cache of shape (batch or num_pages, seqlen or page_size, num_heads_k, head_size)");
+    TORCH_CHECK(v_cache.sizes() == k_cache.sizes(), "v must have the shape of k");
+    CHECK_LAST_CONTIGUOUS(k_cache, "Input tensor must have contiguous last dimension");
+    CHECK_LAST_CONTIGUOUS(v_cache, "Input tensor must have contiguous last dimension");
+    TORCH_CHECK(k_new.stride(-1) == 1, "k_new tensor must have contiguous last dimension");
+    TORCH_CHECK(v_new.stride(-1) == 1, "v_new tensor must have contiguous last dimension");
+    const int64_t num_heads_k = k_cache.size(2), head_size = k_cache.size(3);
+    TORCH_CHECK(head_size <= 128 && head_size % 16 == 0,
+                "This flash attention build supports an fp8 KV cache for head_size <= 128 that is a multiple of 16, got ", head_size);
+    TORCH_CHECK(cache_seqlens.is_cuda() && cache_seqlens.scalar_type() == at::kInt && cache_seqlens.is_contiguous() &&
+                    cache_seqlens.dim() == 1 && cache_seqlens.numel() > 0,
+                "cache_seqlens must be a contiguous int32 CUDA tensor of shape (batch_size,)");
+    const int64_t batch_size = cache_seqlens.numel();
+    const bool ragged = cu_seqlens_k_new.has_value(), paged = page_table.has_value();
+    if (ragged) {
+        CHECK_DEVICE(*cu_seqlens_k_new, "cu_seqlens_k_new");
+        TORCH_CHECK(cu_seqlens_k_new->is_contiguous(), "cu_seqlens_k_new must be contiguous");
+        TORCH_CHECK(cu_seqlens_k_new->scalar_type() == at::kInt, "cu_seqlens_k_new must have dtype torch.int32");
+        TORCH_CHECK(k_new.dim() == 3, "k_new must have shape (total_k_new, num_heads_k, head_size) with cu_seqlens_k_new");
+        CHECK_SHAPE(k_new, "k_new", k_new.size(0), num_heads_k, head_size);
+        CHECK_SHAPE(v_new, "v_new", k_new.size(0), num_heads_k, head_size);
+        CHECK_SHAPE(*cu_seqlens_k_new, "cu_seqlens_k_new", batch_size + 1);
+        TORCH_CHECK(max_seqlen_k_new >= 0, "max_seqlen_k_new must be non-negative");
+    } else {
+        TORCH_CHECK(k_new.dim() == 4, "k_new must have shape (batch_size, seqlen_k_new, num_heads_k, head_size) without cu_seqlens_k_new");
+        CHECK_SHAPE(k_new, "k_new", batch_size, k_new.size(1), num_heads_k, head_size);
+        CHECK_SHAPE(v_new, "v_new", batch_size, k_new.size(1), num_heads_k, head_size);
+    }
+    int64_t seqlen_cache = k_cache.size(1);
+    if (paged) {
+        TORCH_CHECK(!cache_batch_idx.has_value(), "Paged KVcache does not support cache_batch_idx");
+        const auto pr = check_block_table(*page_table, k_cache, batch_size, 1);
+        seqlen_cache = pr.first * pr.second;
+    } else if (cache_batch_idx.has_value()) {
+        CHECK_DEVICE(*cache_batch_idx, "cache_batch_idx");
+        TORCH_CHECK(cache_batch_idx->is_contiguous() && cache_batch_idx->numel() == batch_size, "cache_batch_idx must be contiguous, (batch_size,)");
+        TORCH_CHECK(cache_batch_idx->scalar_type() == at::kInt, "cache_batch_idx must have dtype int32");
+    } else {
+        TORCH_CHECK(k_cache.size(0) >= batch_size, "the KV cache must have at least batch_size entries");
+    }
+    for (const auto &[t, name] : {std::make_pair(&k_descale, "k_descale"), std::make_pair(&v_descale, "v_descale")})
+        TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kFloat && t->sizes() == c10::IntArrayRef({batch_size, num_heads_k}),
+                    name, " must be fp32 (batch_size, num_heads_k)");
+    for (const Tensor *t : {&k_cache, &v_cache}) {
+        bool ok = reinterpret_cast<uintptr_t>(t->data_ptr()) % 8 == 0;
+        for (int64_t i = 0; i < 3; ++i) ok = ok && t->stride(i) % 8 == 0;
+        TORCH_CHECK(ok, "the fp8 KV cache must be 8-byte aligned with row/head/batch strides that are multiples of 8 to be appended to");
+    }
+    TORCH_CHECK(rotary_cos.has_value() == rotary_sin.has_value(), "rotary_cos and rotary_sin must be passed together");
+    if (rotary_cos.has_value()) {  // (the texts of the 16-bit routes)
+        CHECK_DEVICE(*rotary_cos, "rotary_cos"); CHECK_DEVICE(*rotary_sin, "rotary_sin");
+        TORCH_CHECK(rotary_cos->dim() == 2 && rotary_sin->sizes() == rotary_cos->sizes(), "rotary_cos / rotary_sin must have shape (seqlen_ro, rotary_dim / 2)");
+        const int64_t rotary_dim = rotary_cos->size(1) * 2;
+        TORCH_CHECK(rotary_dim <= head_size, "rotary_dim must be <= headdim");
+        TORCH_CHECK(rotary_dim % 16 == 0, "Only rotary dimensions divisible by 16 are currently supported");
+        TORCH_CHECK(rotary_cos->size(0) >= seqlen_cache, "cos/sin seqlen must be at least the seqlen of KV cache");
+        TORCH_CHECK(rotary_cos->is_contiguous() && rotary_sin->is_contiguous(), "rotary_cos / rotary_sin must be contiguous");
+        TORCH_CHECK(rotary_cos->scalar_type() == new_dtype && rotary_sin->scalar_type() == new_dtype,
+                    "rotary_cos / rotary_sin must have the same dtype as k_new");
+    }
+    if (rotary_seqlens.has_value()) {
+        TORCH_CHECK(rotary_seqlens->is_cuda() && rotary_seqlens->is_contiguous(), "seqlens_rotary must be a contiguous CUDA tensor");
+        TORCH_CHECK(rotary_seqlens->scalar_type() == at::kInt, "seqlens_rotary must have dtype torch.int32");
+        TORCH_CHECK(rotary_seqlens->sizes() == c10::IntArrayRef({batch_size}), "seqlens_rotary must have shape (batch_size,)");
+    }
+    c10::hip::HIPGuardMasqueradingAsCUDA device_guard(k_cache.device());
+    const Tensor kn = aligned_or_copy(k_new), vn = aligned_or_copy(v_new);
+    Tensor seqused_out = at::empty({batch_size}, cache_seqlens.options());
+    fa_kvcache_append_kv8_params p{};
+    p.abi_version = FA_ABI_VERSION;
+    p.struct_size = sizeof(fa_kvcache_append_kv8_params);
+    p.k_new = kn.data_ptr(); p.v_new = vn.data_ptr(); p.k_cache = k_cache.data_ptr(); p.v_cache = v_cache.data_ptr();
+    if (ragged) {
+        p.knew_row_stride = kn.stride(0); p.knew_head_stride = kn.stride(1);
+        p.vnew_row_stride = vn.stride(0); p.vnew_head_stride = vn.stride(1);
+        p.total_k_new = (int32_t)kn.size(0);
+        p.max_seqlen_k_new = (int32_t)max_seqlen_k_new;
+        p.cu_seqlens_k_new = static_cast<const int32_t *>(cu_seqlens_k_new->data_ptr());
+    } else {
+        p.knew_batch_stride = kn.stride(0); p.knew_row_stride = kn.stride(1); p.knew_head_stride = kn.stride(2);
+        p.vnew_batch_stride = vn.stride(0); p.vnew_row_stride = vn.stride(1); p.vnew_head_stride = vn.stride(2);
+        p.seqlen_new = (int32_t)kn.size(1);
+    }
+    p.kcache_batch_stride = k_cache.stride(0); p.kcache_row_stride = k_cache.stride(1); p.kcache_head_stride = k_cache.stride(2);  // (bytes)
+    p.vcache_batch_stride = v_cache.stride(0); p.vcache_row_stride = v_cache.stride(1); p.vcache_head_stride = v_cache.stride(2);
+    p.b = (int32_t)batch_size; p.seqlen_cache = (int32_t)seqlen_cache; p.h_k = (int32_t)num_heads_k; p.d = (int32_t)head_size;
+    p.dtype = dtype_code(kn);
+    if (paged) {
+        p.block_table = static_cast<const int32_t *>(page_table->data_ptr());
+        p.block_table_batch_stride = page_table->stride(0);
+        p.page_block_size = (int32_t)k_cache.size(1);
+    }
+    p.cache_seqlens = static_cast<const int32_t *>(cache_seqlens.data_ptr());
+    p.cache_batch_idx = static_cast<const int32_t *>(ptr(cache_batch_idx));
+    p.seqused_out = static_cast<int32_t *>(seqused_out.data_ptr());
+    if (rotary_cos.has_value()) {
+        p.rotary_cos = rotary_cos->data_ptr(); p.rotary_sin = rotary_sin->data_ptr();
+        p.rotary_dim = (int32_t)rotary_cos->size(1) * 2;
+        p.rotary_interleaved = rotary_interleaved ? 1 : 0;
+        p.rotary_seqlens = static_cast<const int32_t *>(ptr(rotary_seqlens));
+    }
+    p.k_descale = static_cast<const float *>(k_descale.data_ptr());
+    p.k_descale_batch_stride = k_descale.stride(0); p.k_descale_head_stride = k_descale.stride(1);
+    p.v_descale = static_cast<const float *>(v_descale.data_ptr());
+    p.v_descale_batch_stride = v_descale.stride(0); p.v_descale_head_stride = v_descale.stride(1);
+    const int st = fa_kvcache_append_kv8(&p, current_stream(k_cache));
+    TORCH_CHECK(st == 0, "fa_kvcache_append_kv8 failed (", st, "): ", fa_strerror(st));
+    return seqused_out;
+}
+
+// hopper_interface.kvcache_append_fp8 / torch.ops.flash_attn_3.kvcache_append_fp8: the append alone, for stacks that fill the
+// cache apart from attention.
+Tensor kvcache_append_fp8(const Tensor &k_cache, const Tensor &v_cache, const Tensor &k, const Tensor &v, const Tensor &cache_seqlens,
+                          const Tensor &k_descale, const Tensor &v_descale, const OptTensor &cu_seqlens_k_new,
+                          c10::optional<int64_t> max_seqlen_k_new, const OptTensor &cache_batch_idx, const OptTensor &page_table,
+                          const OptTensor &rotary_cos, const OptTensor &rotary_sin, const OptTensor &rotary_seqlens,
+                          bool rotary_interleaved) {
+    return kvcache_append_kv8(k_cache, v_cache, k, v, cache_seqlens, k_descale, v_descale, cu_seqlens_k_new,
+                              max_seqlen_k_new.value_or(0), cache_batch_idx, page_table, rotary_cos, rotary_sin, rotary_seqlens,
+                              rotary_interleaved);
+}
+
 // flash_attn_3::fwd, hopper/flash_api.cpp:672-1198 (schema :1672-1707): the 34 positional arguments of
 // hopper/flash_attn_interface.py:66, returns (out, softmax_lse, None, None).
 // Built: fp16 / bf16 / fp8 e4m3 inputs (fp8 -> bf16 output, :859), per-(batch, kv head) q/k/v descales (:1115-1146), dense
@@ -1254,7 +1396,11 @@ std::tuple<Tensor, Tensor> fwd_kv8(const Tensor &q, const Tensor &k, const Tenso
 // route.  Accepted and rejected by message, like the reference does for compiled-out features (:1148-1165):
 // cu_seqlens_k_new without cu_seqlens_q, qv of any other shape or with fp8, KV-cache arguments together with cu_seqlens_k,
 // attention_chunk or fp8.  `scheduler_metadata` and `sm_margin` are performance hints and do not change results: ignored.
-// 16-bit q beside a Float8_e4m3fn k / v (an fp8 KV cache with k_descale / v_descale, out in q's dtype): fwd_kv8 above.
+// 16-bit q beside a Float8_e4m3fn k / v (an fp8 KV cache with k_descale / v_descale, out in q's dtype): fwd_kv8 above.  With
+// both descales the same KV-cache arguments as on the 16-bit routes are served there -- k_new / v_new (16-bit, dense or ragged
+// with cu_seqlens_k_new beside cu_seqlens_q) quantised into the cache in place by kvcache_append_kv8, rotary_cos / rotary_sin,
+// seqlens_rotary, is_rotary_interleaved -- in front of the read on the new fill levels; without both they stay refused, as do
+// fp8 new rows, qv, a V head dim of its own, attention_chunk, cu_seqlens_k and a sink.
 // `pack_gqa` is a hint too: True asks every route below for the pk kernel (FA_FLAG_PACK_GQA: honoured for GQA / MQA calls of
 // 16-bit types at head dims <= 128 without attention_chunk, a V head dim of its own or qv; a no-op elsewhere and behind the
 // single-token GQA swap); False and None keep the unpacked routes (no automatic rule yet).
@@ -1276,11 +1422,17 @@ std::tuple<Tensor, Tensor, OptTensor, OptTensor> fa3_fwd_core(
                 "FlashAttention only supports fp16, bf16, and fp8_e4m3 data type");  // hopper/flash_api.cpp:714-722
     if (!is_fp8 && k.scalar_type() == at::kFloat8_e4m3fn && v.scalar_type() == at::kFloat8_e4m3fn) {
         // 16-bit queries over an fp8 KV cache: the kv8 route (fwd_kv8).  What it does not serve is refused by argument.
-        TORCH_CHECK(!k_new.has_value() && !v_new.has_value() && !cu_seqlens_k_new.has_value(),
-                    "This flash attention build does not support k_new / v_new with an fp8 KV cache: appending to it (quantising "
-                    "the new rows) is the caller's job.");
-        TORCH_CHECK(!rotary_cos.has_value() && !rotary_sin.has_value(),
-                    "This flash attention build does not support rotary_cos / rotary_sin with an fp8 KV cache.");
+        // With both descales the step may write as well: new rows are quantised into the cache (kvcache_append_kv8), q is rotated
+        // by the 16-bit pass, and the read runs on the new fill levels.  Without them the scale of the new rows would be an
+        // implied 1, which is almost never meant: those calls keep their refusals.
+        const bool can_append = k_descale.has_value() && v_descale.has_value();
+        if (!can_append) {
+            TORCH_CHECK(!k_new.has_value() && !v_new.has_value() && !cu_seqlens_k_new.has_value(),
+                        "This flash attention build does not support k_new / v_new with an fp8 KV cache: appending to it (quantising "
+                        "the new rows) is the caller's job.");
+            TORCH_CHECK(!rotary_cos.has_value() && !rotary_sin.has_value(),
+                        "This flash attention build does not support rotary_cos / rotary_sin with an fp8 KV cache.");
+        }
         TORCH_CHECK(!qv.has_value(), "This flash attention build does not support qv with an fp8 KV cache.");
         TORCH_CHECK(v.size(-1) == q.size(-1),
                     "This flash attention build does not support a V headdim of its own with an fp8 KV cache.");
@@ -1289,7 +1441,54 @@ std::tuple<Tensor, Tensor, OptTensor, OptTensor> fa3_fwd_core(
                     "This flash attention build supports an fp8 KV cache for head_size <= 128 that is a multiple of 16, got ", q.size(-1));
         TORCH_CHECK(!cu_seqlens_k.has_value(), "This flash attention build does not support cu_seqlens_k with an fp8 KV cache.");
         TORCH_CHECK(!sink.has_value(), "This flash attention build does not support a learnable sink with an fp8 KV cache.");
-        auto r = fwd_kv8(q, k, v, out_, cu_seqlens_q, seqused_q, seqused_k, max_seqlen_q_, page_table, kv_batch_idx, leftpad_k,
+        OptTensor fill = seqused_k;
+        Tensor qc = q;
+        if (k_new || v_new || cu_seqlens_k_new || rotary_cos || rotary_sin) {
+            TORCH_CHECK(k_new.has_value() && v_new.has_value(),
+                        rotary_cos || rotary_sin
+                            ? "If rotary cos/sin are provided, new key / value to be appended to KV cache must also be provided"
+                            : "k_new and v_new must be passed together");
+            TORCH_CHECK(rotary_cos.has_value() == rotary_sin.has_value(), "rotary_cos and rotary_sin must be passed together");
+            TORCH_CHECK(!cu_seqlens_k_new.has_value() || cu_seqlens_q.has_value(),
+                        "This flash attention build does not support cu_seqlens_k_new without cu_seqlens_q.");
+            TORCH_CHECK(k_new->scalar_type() == at::kFloat8_e4m3fn || (k_new->scalar_type() == q_dtype && v_new->scalar_type() == q_dtype),
+                        "k_new and v_new must have the same dtype as query");
+            TORCH_CHECK(seqused_k.has_value(), "seqused_k must be provided with k_new / leftpad_k");
+            const bool ragged = cu_seqlens_q.has_value();
+            CHECK_DEVICE(q, "q"); CHECK_LAST_CONTIGUOUS(q, "Input tensor must have contiguous last dimension");
+            TORCH_CHECK(q.dim() == (ragged ? 3 : 4), ragged ? "q must have shape (total_q, num_heads, head_size) with cu_seqlens_q"
+                                                            : "q must have shape (batch_size, seqlen_q, num_heads, head_size)");
+            if (ragged) {
+                TORCH_CHECK(cu_seqlens_q->scalar_type() == at::kInt && cu_seqlens_q->is_contiguous() && cu_seqlens_q->is_cuda(),
+                            "cu_seqlens_q must be a contiguous int32 CUDA tensor");
+                TORCH_CHECK(max_seqlen_q_.has_value() && *max_seqlen_q_ > 0, "max_seqlen_q must be provided with cu_seqlens_q");
+            }
+            const int64_t batch_size = ragged ? cu_seqlens_q->numel() - 1 : q.size(0);
+            TORCH_CHECK(seqused_k->dim() == 1 && seqused_k->numel() == batch_size, "seqused_k must be int32 of shape (batch_size,)");
+            TORCH_CHECK(k.dim() == 4 && k.size(3) == q.size(-1) && k.size(2) > 0 && q.size(-2) % k.size(2) == 0,
+                        "Number of heads in key/value must divide number of heads in query");
+            check_leftpad(leftpad_k, batch_size, page_table.has_value());
+            if (seqlens_rotary.has_value() && !rotary_cos.has_value()) seqlens_rotary = c10::nullopt;  // (only read with rotary)
+            // the append first: what the read sees are the new fill levels -- dense rows: seqused_k + seqlen_new, like the 16-bit
+            // route; ragged rows: what the launch wrote
+            const Tensor written = kvcache_append_kv8(k, v, *k_new, *v_new, *seqused_k, *k_descale, *v_descale, cu_seqlens_k_new, 0,
+                                                      kv_batch_idx, page_table, rotary_cos, rotary_sin, seqlens_rotary,
+                                                      is_rotary_interleaved);
+            fill = cu_seqlens_k_new.has_value() ? written : *seqused_k + k_new->size(-3);
+            if (rotary_cos.has_value() && q.numel() > 0) {
+                // the 16-bit routes' rule: causal / local -> row i at the old fill level (or seqlens_rotary) + i, otherwise every
+                // row at that level
+                const bool per_row = is_causal || window_size_left >= 0 || window_size_right >= 0;
+                const Tensor qa = aligned_or_copy(q);
+                Tensor q_ro = at::empty_like(qa, at::MemoryFormat::Contiguous);
+                const Tensor &offsets = seqlens_rotary.has_value() ? *seqlens_rotary : *seqused_k;
+                c10::hip::HIPGuardMasqueradingAsCUDA device_guard(q.device());
+                if (ragged) rotary_apply_varlen(qa, q_ro, *cu_seqlens_q, *max_seqlen_q_, *rotary_cos, *rotary_sin, offsets, is_rotary_interleaved, per_row);
+                else rotary_apply(qa, q_ro, *rotary_cos, *rotary_sin, offsets, is_rotary_interleaved, per_row);
+                qc = q_ro;
+            }
+        }
+        auto r = fwd_kv8(qc, k, v, out_, cu_seqlens_q, seqused_q, fill, max_seqlen_q_, page_table, kv_batch_idx, leftpad_k,
                          k_descale, v_descale, softmax_scale_.value_or(std::pow(double(q.size(-1)), -0.5)), is_causal,
                          window_size_left, window_size_right, softcap, num_splits);
         return {std::get<0>(r), std::get<1>(r), c10::nullopt, c10::nullopt};
@@ -1855,6 +2054,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("softcap"), py::arg("is_rotary_interleaved"), py::arg("num_splits"), py::arg("page_multiple"),
           py::arg("seqlens_rotary") = py::none(), py::arg("qv") = py::none());
     m.def("fa3_fwd", &fa3_fwd, "FA3 forward pass (flash_attn_3::fwd)");
+    m.def("kvcache_append_fp8", &kvcache_append_fp8, "quantising in-place append of 16-bit rows to an fp8 (e4m3) KV cache; returns the new fill levels",
+          py::arg("k_cache"), py::arg("v_cache"), py::arg("k"), py::arg("v"), py::arg("cache_seqlens"), py::arg("k_descale"),
+          py::arg("v_descale"), py::arg("cu_seqlens_k_new") = py::none(), py::arg("max_seqlen_k_new") = py::none(),
+          py::arg("cache_batch_idx") = py::none(), py::arg("page_table") = py::none(), py::arg("rotary_cos") = py::none(),
+          py::arg("rotary_sin") = py::none(), py::arg("rotary_seqlens") = py::none(), py::arg("rotary_interleaved") = true);
     m.def("fa3_bwd", &fa3_bwd, "FA3 backward pass (flash_attn_3::bwd)");
     m.def("fa3_fwd_combine", &fa3_fwd_combine, "FA3 merge of split-KV partials (flash_attn_3::fwd_combine)");
     m.def("cute_fwd", &cute_fwd, "cute surface forward (flash_attn.cute.interface, with learnable_sink)", py::arg("q"), py::arg("k"),

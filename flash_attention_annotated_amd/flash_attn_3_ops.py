@@ -35,8 +35,15 @@ METADATA_SCHEMA = (
     "int max_seqlen_k_new = 0, bool is_causal = False, int window_size_left = -1, int window_size_right = -1, "
     "int attention_chunk = 0, bool has_softcap = False, int num_splits = 0, bool? pack_gqa = None, int sm_margin = 0) -> Tensor")
 
+# not in the reference's library: the write half of an fp8 KV cache as an op of its own (the role of a `reshape_and_cache` op)
+APPEND_FP8_SCHEMA = (
+    "kvcache_append_fp8(Tensor(a!) k_cache, Tensor(b!) v_cache, Tensor k, Tensor v, Tensor cache_seqlens, Tensor k_descale, "
+    "Tensor v_descale, Tensor? cu_seqlens_k_new = None, int? max_seqlen_k_new = None, Tensor? cache_batch_idx = None, "
+    "Tensor? page_table = None, Tensor? rotary_cos = None, Tensor? rotary_sin = None, Tensor? rotary_seqlens = None, "
+    "bool rotary_interleaved = True) -> Tensor")
+
 _ops = torch.library.Library("flash_attn_3", "DEF")
-for _schema in (FWD_SCHEMA, BWD_SCHEMA, COMBINE_SCHEMA, METADATA_SCHEMA):
+for _schema in (FWD_SCHEMA, BWD_SCHEMA, COMBINE_SCHEMA, METADATA_SCHEMA, APPEND_FP8_SCHEMA):
     _ops.define(_schema)
 
 
@@ -67,6 +74,21 @@ def _bwd(dout, q, k, v, out, softmax_lse, dq=None, dk=None, dv=None, cu_seqlens_
 def _fwd_combine(out_partial, lse_partial, out=None, out_dtype=None):
     """mha_combine, hopper/flash_api.cpp:1569-1670: the binding's fa3_fwd_combine."""
     return _lib.binding().fa3_fwd_combine(out_partial, lse_partial, out, out_dtype)
+
+
+def _kvcache_append_fp8(k_cache, v_cache, k, v, cache_seqlens, k_descale, v_descale, cu_seqlens_k_new=None, max_seqlen_k_new=None,
+                        cache_batch_idx=None, page_table=None, rotary_cos=None, rotary_sin=None, rotary_seqlens=None,
+                        rotary_interleaved=True):
+    """The binding's kvcache_append_fp8 (fa_kvcache_append_kv8): one launch, returns the new fill levels."""
+    return _lib.binding().kvcache_append_fp8(k_cache, v_cache, k, v, cache_seqlens, k_descale, v_descale, cu_seqlens_k_new,
+                                             max_seqlen_k_new, cache_batch_idx, page_table, rotary_cos, rotary_sin,
+                                             rotary_seqlens, rotary_interleaved)
+
+
+def _kvcache_append_fp8_meta(k_cache, v_cache, k, v, cache_seqlens, k_descale, v_descale, cu_seqlens_k_new=None,
+                             max_seqlen_k_new=None, cache_batch_idx=None, page_table=None, rotary_cos=None, rotary_sin=None,
+                             rotary_seqlens=None, rotary_interleaved=True):
+    return torch.empty_like(cache_seqlens)
 
 
 def _get_scheduler_metadata(batch_size, max_seqlen_q, max_seqlen_k, num_heads, num_heads_k, headdim, headdim_v, qkv_dtype,
@@ -100,3 +122,5 @@ _ops.impl("fwd", _fwd_meta, "Meta")
 _ops.impl("bwd", _bwd, "CUDA")
 _ops.impl("fwd_combine", _fwd_combine, "CUDA")
 _ops.impl("get_scheduler_metadata", _get_scheduler_metadata, "CUDA")
+_ops.impl("kvcache_append_fp8", _kvcache_append_fp8, "CUDA")
+_ops.impl("kvcache_append_fp8", _kvcache_append_fp8_meta, "Meta")

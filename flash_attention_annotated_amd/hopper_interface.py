@@ -201,6 +201,9 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, qv=None, rotary
                             scheduler_metadata=None, num_splits=0, pack_gqa=None, sm_margin=0, return_softmax_lse=False):
     """reference hopper/flash_attn_interface.py:640-800: attention over a KV cache, optionally appending k / v in place
     (rotated by rotary_cos / rotary_sin) first.  Paged caches: any page size.
+    An fp8 cache (torch.float8_e4m3fn k_cache / v_cache under fp16 / bf16 q) is read through k_descale / v_descale, fp32
+    (batch, nheads_k); with both given, k / v (fp16 / bf16, dense or ragged) are quantised into it in place first and
+    rotary_cos / rotary_sin / rotary_seqlens apply as on a 16-bit cache (kvcache_append_fp8 below is that append alone).
     pack_gqa: True runs the PackGQA kernel on the attention of the step -- dense or ragged (cu_seqlens_q) queries, batched or
     paged cache, split-KV -- so that a verify step of a few tokens or the decode rows of a mixed step share one pass over the
     cache per kv head; a single-token step keeps its own GQA fold and is unaffected.  False / None: unpacked, as before."""
@@ -217,6 +220,23 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, qv=None, rotary
         rotary_interleaved=rotary_interleaved, scheduler_metadata=scheduler_metadata, num_splits=num_splits,
         pack_gqa=pack_gqa, sm_margin=sm_margin)
     return (out, softmax_lse, *rest) if return_softmax_lse else out
+
+
+def kvcache_append_fp8(k_cache, v_cache, k, v, cache_seqlens, k_descale, v_descale, *, cu_seqlens_k_new=None,
+                       max_seqlen_k_new=None, cache_batch_idx=None, page_table=None, rotary_cos=None, rotary_sin=None,
+                       rotary_seqlens=None, rotary_interleaved=True):
+    """The write half of an fp8 KV cache on its own (the role of a `reshape_and_cache` op): the fp16 / bf16 rows k / v --
+    (batch, seqlen_new, nheads_k, headdim), or (total_k_new, nheads_k, headdim) with cu_seqlens_k_new -- are quantised into the
+    torch.float8_e4m3fn caches in place at cache_seqlens[b] + i (through cache_batch_idx or page_table, any page size): keys
+    rotated like the 16-bit append rotates them, then x / descale[b, head] clamped to +-448 and rounded to nearest even.  Rows
+    past the capacity are dropped.  k_descale / v_descale: fp32 (batch, nheads_k), the factors flash_attn_with_kvcache
+    dequantises by.  One launch, no host sync (HIP-graph capturable).  Returns the new fill levels
+    min(cache_seqlens + new rows, capacity), int32 (batch,) on the device; cache_seqlens itself is not modified.
+    flash_attn_with_kvcache(q, k_cache, v_cache, k=, v=, k_descale=, v_descale=, ...) runs the same append in front of the
+    attention."""
+    return torch.ops.flash_attn_3.kvcache_append_fp8(k_cache, v_cache, k, v, cache_seqlens, k_descale, v_descale,
+                                                     cu_seqlens_k_new, max_seqlen_k_new, cache_batch_idx, page_table,
+                                                     rotary_cos, rotary_sin, rotary_seqlens, rotary_interleaved)
 
 
 def get_scheduler_metadata(batch_size, max_seqlen_q, max_seqlen_k, num_heads_q, num_heads_kv, headdim, cache_seqlens,

@@ -18,6 +18,7 @@
  *   mha_fwd_kvcache  csrc/flash_attn/flash_api.cpp:1202-1476      fa_kvcache_append + fa_fwd (seqused_k, kv_batch_idx)
  *   mha_fwd (FA3) over an fp8 KV cache, 16-bit q
  *                    hopper/flash_api.cpp:714-760, 1115-1146      fa_fwd_kv8 (k / v e4m3 bytes + k / v descale)
+ *   ... with k_new / v_new, rotary (the append into that cache)   fa_kvcache_append_kv8 (16-bit rows -> e4m3 bytes)
  *   error codes      standalone/src/flash_api.cu:403-426          FA_ERR_* / fa_strerror
  *
  * Conventions (same as the reference's params struct):
@@ -536,6 +537,73 @@ typedef struct fa_rotary_varlen_params {
 
 int fa_rotary_apply_varlen(const fa_rotary_varlen_params *params, void *stream);
 uint32_t fa_rotary_varlen_params_size(void);
+
+/*
+ * Quantising in-place append to an fp8 (OCP e4m3fn) KV cache -- the write half of what fa_fwd_kv8 reads: new 16-bit keys /
+ * values go into a cache of e4m3 BYTES at the rows fa_kvcache_append / fa_kvcache_append_varlen would have written in a 16-bit
+ * cache.  One struct, both forms: cu_seqlens_k_new == NULL is the dense form, new rows (b, seqlen_new, h_k, d) through the
+ * batch strides; otherwise the rows are ragged, (total_k_new, h_k, d) with cu_seqlens_k_new and max_seqlen_k_new (0 = a search
+ * in cu_seqlens_k_new), as in fa_kvcache_append_varlen.
+ * An element x of sequence s (the index of the call, the one fa_fwd_kv8 reads descales by -- not the cache entry) and kv head g:
+ *     inv  = 1.0f / ds           ds = k_descale[s, g] for keys, v_descale[s, g] for values (NULL = 1.0); IEEE fp32, once
+ *     y    = float(x) * inv      one fp32 multiply
+ *     byte = e4m3fn_rne(min(max(y, -448), 448))      round to nearest even, saturating; +-inf -> +-448; -0 keeps its sign
+ * Keys are rotated first, by the code of the 16-bit appends (fp32 arithmetic, position (rotary_seqlens ? rotary_seqlens[s] :
+ * cache_seqlens[s]) + i, interleaved or not, columns >= rotary_dim passed through), the result rounded to the 16-bit type and
+ * then quantised: the bytes are the quantisation of what the 16-bit appends write.  Values are never rotated.  NaN inputs are
+ * unspecified.  Row i of sequence s goes to cache row cache_seqlens[s] + i of entry cache_batch_idx[s] (NULL = s) or of its
+ * page (any page size); rows at or past seqlen_cache are dropped; nothing but the d bytes per head of the appended rows is
+ * written.  seqused_out[s] = min(cache_seqlens[s] + new rows of s, seqlen_cache) is written by the same launch: required in
+ * the ragged form, optional (NULL) in the dense one; it must not alias cache_seqlens.
+ * One kernel, kvcache_append_kv8_kernel (csrc/fa_kvcache_append_kv8.hip): a wavefront per new row, 16-byte loads, 8-byte
+ * stores, 64-bit addresses from a per-row base (a cache entry of 2 GiB and more is served), no atomics, no allocation, no
+ * synchronisation: the call can be captured into a HIP graph.
+ * d % 16 == 0 and d <= 128 (what fa_fwd_kv8 serves), d_v 0 or d; new rows 16-byte aligned (pointers, strides % 8 elements);
+ * the cache 8-byte aligned (pointers, strides % 8 bytes); rotary_dim % 16 == 0, <= d, cos and sin together, 16-byte aligned;
+ * block_table not with cache_batch_idx.  The status codes are those of the 16-bit appends for the same faults
+ * (FA_ERR_BAD_SHAPE for seqused_out == cache_seqlens).
+ */
+typedef struct fa_kvcache_append_kv8_params {
+    uint32_t abi_version; /* FA_ABI_VERSION */
+    uint32_t struct_size; /* sizeof(fa_kvcache_append_kv8_params) */
+    const void *k_new; /* 16-bit: (b, seqlen_new, h_k, d) or (total_k_new, h_k, d) */
+    const void *v_new;
+    void *k_cache;     /* e4m3 bytes: (b_cache, seqlen_cache, h_k, d) or pages (num_pages, page_block_size, h_k, d) */
+    void *v_cache;
+    int64_t knew_batch_stride, knew_row_stride, knew_head_stride; /* elements; the batch stride is read in the dense form only */
+    int64_t vnew_batch_stride, vnew_row_stride, vnew_head_stride;
+    int64_t kcache_batch_stride, kcache_row_stride, kcache_head_stride; /* bytes; paged: the batch stride is the page stride */
+    int64_t vcache_batch_stride, vcache_row_stride, vcache_head_stride;
+    int32_t b;                /* sequences */
+    int32_t seqlen_new;       /* dense form: new rows per sequence */
+    int32_t total_k_new;      /* ragged form: rows of k_new / v_new (>= cu_seqlens_k_new[b]) */
+    int32_t max_seqlen_k_new; /* ragged form: upper bound of the new lengths, or 0 = not known */
+    int32_t seqlen_cache;     /* capacity; paged: pages per sequence x page_block_size */
+    int32_t h_k, d;
+    int32_t d_v;              /* 0 or d */
+    int32_t dtype;            /* of the new rows and of rotary_cos / rotary_sin: FA_DTYPE_FP16 / FA_DTYPE_BF16 */
+    int32_t page_block_size;
+    int32_t rotary_dim;       /* only read when rotary_cos is set */
+    int32_t rotary_interleaved;
+    const int32_t *cu_seqlens_k_new; /* (b + 1), or NULL = the dense form */
+    const int32_t *cache_seqlens;    /* (b) rows already valid in each sequence's cache */
+    const int32_t *cache_batch_idx;  /* (b) or NULL */
+    int32_t *seqused_out;            /* (b) written by the launch; may be NULL in the dense form */
+    const int32_t *block_table;      /* paged cache (see fa_fwd_params) or NULL */
+    int64_t block_table_batch_stride;
+    const void *rotary_cos;          /* (seqlen_ro, rotary_dim / 2), contiguous, `dtype`; NULL = no rotary */
+    const void *rotary_sin;
+    const int32_t *rotary_seqlens;   /* (b) or NULL = cache_seqlens */
+    const float *k_descale;          /* fp32 per (sequence, kv head) through the strides below; NULL = 1.0 */
+    const float *v_descale;
+    int64_t k_descale_batch_stride, k_descale_head_stride;
+    int64_t v_descale_batch_stride, v_descale_head_stride;
+} fa_kvcache_append_kv8_params;
+
+int fa_kvcache_append_kv8(const fa_kvcache_append_kv8_params *params, void *stream);
+/* Validation only; no device access. */
+int fa_kvcache_append_kv8_validate(const fa_kvcache_append_kv8_params *params);
+uint32_t fa_kvcache_append_kv8_params_size(void);
 
 /* Merge of split-KV partial results given by the caller: mha_combine / flash_attn_3::fwd_combine
  * (hopper/flash_api.cpp:1569-1670, hopper/flash_fwd_combine_kernel.h).
