@@ -594,40 +594,127 @@ std::vector<Tensor> mha_varlen_bwd(const Tensor &dout, const Tensor &q, const Te
     return run_bwd(dout, q, k, v, out, softmax_lse, dq, dk, dv, a, max_seqlen_q > 0 && total_q > 0 && total_k > 0, zero_tensors);
 }
 
-void rotary_apply(const Tensor &src, const Tensor &dst, const Tensor &cos, const Tensor &sin, const Tensor &seqlen_offsets,
-                  bool interleaved, bool per_row_positions) {
-    fa_rotary_params p{};
-    p.abi_version = FA_ABI_VERSION;
-    p.struct_size = sizeof(fa_rotary_params);
-    p.src = src.data_ptr(); p.dst = dst.data_ptr();
-    p.src_batch_stride = src.stride(0); p.src_row_stride = src.stride(1); p.src_head_stride = src.stride(2);
-    p.dst_batch_stride = dst.stride(0); p.dst_row_stride = dst.stride(1); p.dst_head_stride = dst.stride(2);
-    p.b = (int32_t)src.size(0); p.s = (int32_t)src.size(1); p.h = (int32_t)src.size(2); p.d = (int32_t)src.size(3);
-    p.dtype = dtype_code(src);
-    p.rotary_dim = (int32_t)cos.size(1) * 2;
-    p.rotary_interleaved = interleaved ? 1 : 0;
-    p.per_row_positions = per_row_positions ? 1 : 0;
-    p.rotary_cos = cos.data_ptr(); p.rotary_sin = sin.data_ptr();
-    p.seqlen_offsets = static_cast<const int32_t *>(seqlen_offsets.data_ptr());
-    const int st = fa_rotary_apply(&p, current_stream(src));
-    TORCH_CHECK(st == 0, "fa_rotary_apply failed (", st, "): ", fa_strerror(st));
+// ---- the KV-cache host path: what its routes share (the dense step fwd_kvcache_core, the ragged step fwd_kvcache_ragged, the
+// fp8 read fwd_kv8, the fp8 append kvcache_append_kv8 and the fp8 step fwd_kv8_step) ----------------------------------------------
+
+// The cache side of one call as check_cache found it: batched (batch_size_c entries of seqlen_k rows, picked by an optional
+// batch index) or pages behind a page table (then seqlen_k is the capacity of one sequence's pages and batch_size_c the batch:
+// csrc :1266-1268).
+struct CacheSide {
+    bool paged = false;
+    int64_t batch_size_c = 0, seqlen_k = 0, page_block_size = 0, num_heads_k = 0, head_size = 0, head_size_v = 0;
+};
+
+// What differs between the routes: the page-size rule, what the kernels need of the cache's memory (base address and
+// non-unit strides, in elements' bytes), and the wording of the refusals, which callers know and which therefore stays.
+struct CacheRules {
+    int64_t page_multiple = 1, base_grain = 16, stride_grain = 8;
+    const char *misaligned = "the KV cache must be 16-byte aligned with row/head/batch strides that are multiples of 8";
+    std::string k_shape, v_shape;                                    // whole texts
+    const char *fill_name = "seqused_k";
+    const char *fill_dtype, *fill_device, *fill_contiguous, *fill_shape;  // follow the name of the fill levels
+    bool fill_any_dims = false;                                      // the fp8 read only counts the elements
+    const char *idx_name = "cache_batch_idx";
+    const char *idx_contiguous = " must be contiguous", *idx_length = " must have shape (batch_size)";
+    bool idx_longer_ok = false;                                      // the dense 16-bit route serves a longer index today
+};
+
+// fill levels (seqlens_k / seqused_q / seqused_k / cache_seqlens): int32, on the device, contiguous, one per sequence
+void check_fill_levels(const Tensor &t, const std::string &name, int64_t batch_size, const CacheRules &r) {
+    TORCH_CHECK(t.scalar_type() == at::kInt, name, r.fill_dtype);
+    TORCH_CHECK(t.is_cuda(), name, r.fill_device);
+    TORCH_CHECK(t.is_contiguous(), name, r.fill_contiguous);
+    TORCH_CHECK((r.fill_any_dims || t.dim() == 1) && t.numel() == batch_size, name, r.fill_shape);
 }
 
-void kvcache_append(const Tensor &k_new, const Tensor &v_new, const Tensor &k_cache, const Tensor &v_cache,
-                    const Tensor &cache_seqlens, const OptTensor &cache_batch_idx, const OptTensor &block_table,
-                    const OptTensor &rotary_cos, const OptTensor &rotary_sin, bool rotary_interleaved,
-                    const OptTensor &rotary_seqlens = c10::nullopt) {
-    fa_kvcache_append_params p{};
+bool cache_aligned(const Tensor &t, int64_t base_grain, int64_t stride_grain) {
+    bool ok = reinterpret_cast<uintptr_t>(t.data_ptr()) % base_grain == 0;
+    for (int64_t i = 0; i < 3; ++i) ok = ok && t.stride(i) % stride_grain == 0;
+    return ok;
+}
+
+// Every check of the cache side, once, in one order: the fill levels, paging, the shapes of k and v, leftpad_k, the batch index
+// (or an entry per sequence), alignment.  k and v are 4-D (each route says that under its own text first).
+CacheSide check_cache(const Tensor &k, const Tensor &v, const OptTensor &page_table, const OptTensor &batch_idx, const OptTensor &fill,
+                      const OptTensor &leftpad_k, int64_t batch_size, int64_t head_size, int64_t head_size_v, const CacheRules &r) {
+    if (fill.has_value()) check_fill_levels(*fill, r.fill_name, batch_size, r);
+    CacheSide c;
+    c.paged = page_table.has_value();
+    if (c.paged) TORCH_CHECK(!batch_idx.has_value(), "Paged KVcache does not support cache_batch_idx");
+    c.batch_size_c = k.size(0); c.seqlen_k = k.size(1); c.num_heads_k = k.size(2); c.head_size = head_size; c.head_size_v = head_size_v;
+    if (c.paged) {
+        const auto pr = check_block_table(*page_table, k, batch_size, r.page_multiple);
+        c.page_block_size = pr.first;
+        c.seqlen_k = pr.second * pr.first; c.batch_size_c = batch_size;
+    }
+    TORCH_CHECK(k.size(3) == head_size, r.k_shape);
+    TORCH_CHECK(v.sizes() == c10::IntArrayRef({k.size(0), k.size(1), k.size(2), head_size_v}), r.v_shape);
+    check_leftpad(leftpad_k, batch_size, c.paged);
+    if (batch_idx.has_value()) {
+        TORCH_CHECK(batch_idx->is_cuda(), r.idx_name, " must be on CUDA");
+        TORCH_CHECK(batch_idx->is_contiguous(), r.idx_name, r.idx_contiguous);
+        TORCH_CHECK(batch_idx->scalar_type() == at::kInt, r.idx_name, " must have dtype int32");
+        TORCH_CHECK(batch_idx->numel() == batch_size || (r.idx_longer_ok && batch_idx->numel() > batch_size), r.idx_name, r.idx_length);
+    } else {
+        TORCH_CHECK(c.batch_size_c >= batch_size, "the KV cache must have at least batch_size entries");
+    }
+    TORCH_CHECK(cache_aligned(k, r.base_grain, r.stride_grain) && cache_aligned(v, r.base_grain, r.stride_grain), r.misaligned);
+    return c;
+}
+
+// New rows beside cu_seqlens_k_new (ragged, (total_k_new, h_k, d)) or without (dense, (b, s_new, h_k, d)); hopper :929-975.
+// `size_of_k_new`: how the route's text spells k_new's own extent ("k_new->size" / "k_new.size"); `v_dim`: its name of V's width.
+void check_new_rows(const Tensor &k_new, const Tensor &v_new, const OptTensor &cu_seqlens_k_new, int64_t batch_size, int64_t num_heads_k,
+                    int64_t head_size, int64_t head_size_v, const char *size_of_k_new, const char *v_dim) {
+    if (cu_seqlens_k_new.has_value()) {
+        CHECK_DEVICE(*cu_seqlens_k_new, "cu_seqlens_k_new");
+        TORCH_CHECK(cu_seqlens_k_new->is_contiguous(), "cu_seqlens_k_new must be contiguous");
+        TORCH_CHECK(cu_seqlens_k_new->scalar_type() == at::kInt, "cu_seqlens_k_new must have dtype torch.int32");  // :939
+        TORCH_CHECK(k_new.dim() == 3, "k_new must have shape (total_k_new, num_heads_k, head_size) with cu_seqlens_k_new");
+        TORCH_CHECK(k_new.sizes() == c10::IntArrayRef({k_new.size(0), num_heads_k, head_size}), "k_new must have shape (", size_of_k_new,
+                    "(0), num_heads_k, head_size)");
+        TORCH_CHECK(v_new.sizes() == c10::IntArrayRef({k_new.size(0), num_heads_k, head_size_v}), "v_new must have shape (", size_of_k_new,
+                    "(0), num_heads_k, ", v_dim, ")");
+        CHECK_SHAPE(*cu_seqlens_k_new, "cu_seqlens_k_new", batch_size + 1);
+    } else {
+        TORCH_CHECK(k_new.dim() == 4, "k_new must have shape (batch_size, seqlen_k_new, num_heads_k, head_size) without cu_seqlens_k_new");
+        TORCH_CHECK(k_new.sizes() == c10::IntArrayRef({batch_size, k_new.size(1), num_heads_k, head_size}), "k_new must have shape (batch_size, ",
+                    size_of_k_new, "(1), num_heads_k, head_size)");
+        TORCH_CHECK(v_new.sizes() == c10::IntArrayRef({batch_size, k_new.size(1), num_heads_k, head_size_v}), "v_new must have shape (batch_size, ",
+                    size_of_k_new, "(1), num_heads_k, ", v_dim, ")");
+    }
+}
+
+// rotary_cos / rotary_sin (seqlen_ro, rotary_dim / 2) against the head dim, the cache's capacity and the dtype of `like` (the
+// tensor they rotate: "query", "k_new"); hopper :1050-1072.  per_tensor: the reference's texts (csrc :1404-1428), which name one
+// table each -- and rotary_cos for the dtype of either.
+void check_rotary_tables(const Tensor &cos, const Tensor &sin, int64_t head_size, int64_t capacity, at::ScalarType dtype, const char *like,
+                         bool per_tensor = false) {
+    const auto text = [&](const char *table, const char *rule) { return std::string(per_tensor ? table : "rotary_cos / rotary_sin") + rule; };
+    CHECK_DEVICE(cos, "rotary_cos"); CHECK_DEVICE(sin, "rotary_sin");
+    TORCH_CHECK(cos.dim() == 2, text("rotary_cos", " must have shape (seqlen_ro, rotary_dim / 2)"));
+    TORCH_CHECK(sin.sizes() == cos.sizes(), text("rotary_sin", " must have shape (seqlen_ro, rotary_dim / 2)"));
+    const int64_t rotary_dim = cos.size(1) * 2;
+    TORCH_CHECK(rotary_dim <= head_size, "rotary_dim must be <= headdim");
+    TORCH_CHECK(rotary_dim % 16 == 0, "Only rotary dimensions divisible by 16 are currently supported");
+    TORCH_CHECK(cos.size(0) >= capacity, "cos/sin seqlen must be at least the seqlen of KV cache");
+    TORCH_CHECK(cos.is_contiguous(), text("rotary_cos", " must be contiguous"));
+    TORCH_CHECK(sin.is_contiguous(), text("rotary_sin", " must be contiguous"));
+    TORCH_CHECK(cos.scalar_type() == dtype && sin.scalar_type() == dtype, text("rotary_cos", " must have the same dtype as "), like);
+}
+
+// What the three append structs (fa_kvcache_append_params, fa_kvcache_append_varlen_params, fa_kvcache_append_kv8_params) name
+// alike: the cache and its strides, the paging fields, the fill levels, the batch index and the rotary group.
+template <class P>
+void fill_append_common(P &p, const Tensor &k_cache, const Tensor &v_cache, const Tensor &cache_seqlens, const OptTensor &cache_batch_idx,
+                        const OptTensor &block_table, const OptTensor &rotary_cos, const OptTensor &rotary_sin, bool rotary_interleaved,
+                        const OptTensor &rotary_seqlens) {
     p.abi_version = FA_ABI_VERSION;
-    p.struct_size = sizeof(fa_kvcache_append_params);
-    p.k_new = k_new.data_ptr(); p.v_new = v_new.data_ptr(); p.k_cache = k_cache.data_ptr(); p.v_cache = v_cache.data_ptr();
-    p.knew_batch_stride = k_new.stride(0); p.knew_row_stride = k_new.stride(1); p.knew_head_stride = k_new.stride(2);
-    p.vnew_batch_stride = v_new.stride(0); p.vnew_row_stride = v_new.stride(1); p.vnew_head_stride = v_new.stride(2);
+    p.struct_size = sizeof(P);
+    p.k_cache = k_cache.data_ptr(); p.v_cache = v_cache.data_ptr();
     p.kcache_batch_stride = k_cache.stride(0); p.kcache_row_stride = k_cache.stride(1); p.kcache_head_stride = k_cache.stride(2);
     p.vcache_batch_stride = v_cache.stride(0); p.vcache_row_stride = v_cache.stride(1); p.vcache_head_stride = v_cache.stride(2);
-    p.b = (int32_t)k_new.size(0); p.seqlen_new = (int32_t)k_new.size(1); p.h_k = (int32_t)k_new.size(2); p.d = (int32_t)k_new.size(3);
     p.seqlen_cache = (int32_t)k_cache.size(1);
-    if (v_cache.size(3) != k_cache.size(3)) p.d_v = (int32_t)v_cache.size(3);  // V rows of their own width (ABI v13)
     if (block_table.has_value()) {
         p.block_table = static_cast<const int32_t *>(block_table->data_ptr());
         p.block_table_batch_stride = block_table->stride(0);
@@ -636,13 +723,27 @@ void kvcache_append(const Tensor &k_new, const Tensor &v_new, const Tensor &k_ca
     }
     p.cache_seqlens = static_cast<const int32_t *>(cache_seqlens.data_ptr());
     p.cache_batch_idx = static_cast<const int32_t *>(ptr(cache_batch_idx));
-    p.dtype = dtype_code(k_new);
     if (rotary_cos.has_value()) {
         p.rotary_cos = rotary_cos->data_ptr(); p.rotary_sin = rotary_sin->data_ptr();
         p.rotary_dim = (int32_t)rotary_cos->size(1) * 2;
         p.rotary_interleaved = rotary_interleaved ? 1 : 0;
         p.rotary_seqlens = static_cast<const int32_t *>(ptr(rotary_seqlens));   // FA3 seqlens_rotary (NULL: the cache fill levels)
     }
+}
+
+void kvcache_append(const Tensor &k_new, const Tensor &v_new, const Tensor &k_cache, const Tensor &v_cache,
+                    const Tensor &cache_seqlens, const OptTensor &cache_batch_idx, const OptTensor &block_table,
+                    const OptTensor &rotary_cos, const OptTensor &rotary_sin, bool rotary_interleaved,
+                    const OptTensor &rotary_seqlens) {
+    fa_kvcache_append_params p{};
+    fill_append_common(p, k_cache, v_cache, cache_seqlens, cache_batch_idx, block_table, rotary_cos, rotary_sin, rotary_interleaved,
+                       rotary_seqlens);
+    p.k_new = k_new.data_ptr(); p.v_new = v_new.data_ptr();
+    p.knew_batch_stride = k_new.stride(0); p.knew_row_stride = k_new.stride(1); p.knew_head_stride = k_new.stride(2);
+    p.vnew_batch_stride = v_new.stride(0); p.vnew_row_stride = v_new.stride(1); p.vnew_head_stride = v_new.stride(2);
+    p.b = (int32_t)k_new.size(0); p.seqlen_new = (int32_t)k_new.size(1); p.h_k = (int32_t)k_new.size(2); p.d = (int32_t)k_new.size(3);
+    if (v_cache.size(3) != k_cache.size(3)) p.d_v = (int32_t)v_cache.size(3);  // V rows of their own width (ABI v13)
+    p.dtype = dtype_code(k_new);
     const int st = fa_kvcache_append(&p, current_stream(k_new));
     TORCH_CHECK(st == 0, "fa_kvcache_append failed (", st, "): ", fa_strerror(st));
 }
@@ -652,69 +753,89 @@ void kvcache_append_varlen(const Tensor &k_new, const Tensor &v_new, const Tenso
                            const OptTensor &cache_batch_idx, const OptTensor &block_table, const OptTensor &rotary_cos,
                            const OptTensor &rotary_sin, bool rotary_interleaved, const OptTensor &rotary_seqlens) {
     fa_kvcache_append_varlen_params p{};
-    p.abi_version = FA_ABI_VERSION;
-    p.struct_size = sizeof(fa_kvcache_append_varlen_params);
-    p.k_new = k_new.data_ptr(); p.v_new = v_new.data_ptr(); p.k_cache = k_cache.data_ptr(); p.v_cache = v_cache.data_ptr();
+    fill_append_common(p, k_cache, v_cache, cache_seqlens, cache_batch_idx, block_table, rotary_cos, rotary_sin, rotary_interleaved,
+                       rotary_seqlens);
+    p.k_new = k_new.data_ptr(); p.v_new = v_new.data_ptr();
     p.knew_row_stride = k_new.stride(0); p.knew_head_stride = k_new.stride(1);
     p.vnew_row_stride = v_new.stride(0); p.vnew_head_stride = v_new.stride(1);
-    p.kcache_batch_stride = k_cache.stride(0); p.kcache_row_stride = k_cache.stride(1); p.kcache_head_stride = k_cache.stride(2);
-    p.vcache_batch_stride = v_cache.stride(0); p.vcache_row_stride = v_cache.stride(1); p.vcache_head_stride = v_cache.stride(2);
     p.b = (int32_t)cache_seqlens.numel(); p.total_k_new = (int32_t)k_new.size(0); p.h_k = (int32_t)k_new.size(1);
     p.d = (int32_t)k_new.size(2);
     p.max_seqlen_k_new = 0;  // (the FA3 call carries no bound of the new lengths, hopper/flash_api.cpp:948: the launch searches)
-    p.seqlen_cache = (int32_t)k_cache.size(1);
     if (v_cache.size(3) != k_cache.size(3)) p.d_v = (int32_t)v_cache.size(3);
-    if (block_table.has_value()) {
-        p.block_table = static_cast<const int32_t *>(block_table->data_ptr());
-        p.block_table_batch_stride = block_table->stride(0);
-        p.page_block_size = (int32_t)k_cache.size(1);
-        p.seqlen_cache = (int32_t)(block_table->size(1) * k_cache.size(1));
-    }
     p.cu_seqlens_k_new = static_cast<const int32_t *>(cu_seqlens_k_new.data_ptr());
-    p.cache_seqlens = static_cast<const int32_t *>(cache_seqlens.data_ptr());
-    p.cache_batch_idx = static_cast<const int32_t *>(ptr(cache_batch_idx));
     p.seqused_out = static_cast<int32_t *>(seqused_out.data_ptr());
     p.dtype = dtype_code(k_new);
-    if (rotary_cos.has_value()) {
-        p.rotary_cos = rotary_cos->data_ptr(); p.rotary_sin = rotary_sin->data_ptr();
-        p.rotary_dim = (int32_t)rotary_cos->size(1) * 2;
-        p.rotary_interleaved = rotary_interleaved ? 1 : 0;
-        p.rotary_seqlens = static_cast<const int32_t *>(ptr(rotary_seqlens));
-    }
     const int st = fa_kvcache_append_varlen(&p, current_stream(k_new));
     TORCH_CHECK(st == 0, "fa_kvcache_append_varlen failed (", st, "): ", fa_strerror(st));
 }
 
-void rotary_apply_varlen(const Tensor &src, const Tensor &dst, const Tensor &cu_seqlens_q, int64_t max_seqlen_q, const Tensor &cos,
-                         const Tensor &sin, const Tensor &offsets, bool interleaved, bool per_row_positions) {
-    fa_rotary_varlen_params p{};
+// what fa_rotary_params and fa_rotary_varlen_params name alike
+template <class P>
+void fill_rotary_common(P &p, const Tensor &src, const Tensor &dst, const Tensor &cos, const Tensor &sin, bool interleaved, bool per_row) {
     p.abi_version = FA_ABI_VERSION;
-    p.struct_size = sizeof(fa_rotary_varlen_params);
+    p.struct_size = sizeof(P);
     p.src = src.data_ptr(); p.dst = dst.data_ptr();
-    p.src_row_stride = src.stride(0); p.src_head_stride = src.stride(1);
-    p.dst_row_stride = dst.stride(0); p.dst_head_stride = dst.stride(1);
-    p.b = (int32_t)offsets.numel(); p.total_q = (int32_t)src.size(0); p.max_seqlen_q = (int32_t)max_seqlen_q;
-    p.h = (int32_t)src.size(1); p.d = (int32_t)src.size(2);
     p.dtype = dtype_code(src);
     p.rotary_dim = (int32_t)cos.size(1) * 2;
     p.rotary_interleaved = interleaved ? 1 : 0;
-    p.per_row_positions = per_row_positions ? 1 : 0;
+    p.per_row_positions = per_row ? 1 : 0;
     p.rotary_cos = cos.data_ptr(); p.rotary_sin = sin.data_ptr();
-    p.cu_seqlens_q = static_cast<const int32_t *>(cu_seqlens_q.data_ptr());
-    p.offsets = static_cast<const int32_t *>(offsets.data_ptr());
-    const int st = fa_rotary_apply_varlen(&p, current_stream(src));
-    TORCH_CHECK(st == 0, "fa_rotary_apply_varlen failed (", st, "): ", fa_strerror(st));
 }
 
-// mha_fwd_kvcache, csrc/flash_attn/flash_api.cpp:1202-1476 (+ the page-size rule of the calling surface: FA2 256, FA3 any)
-// (`sink_`: the cute surface's learnable sink, (num_heads,) -- checked by its caller; no other surface passes one)
-std::vector<Tensor> fwd_kvcache_core(Tensor q, const Tensor &kcache, const Tensor &vcache, OptTensor k_, OptTensor v_,
-                                     OptTensor seqlens_k_, OptTensor rotary_cos_, OptTensor rotary_sin_,
-                                     OptTensor cache_batch_idx_, OptTensor leftpad_k_, OptTensor block_table_,
-                                     OptTensor alibi_slopes_, OptTensor out_, const double softmax_scale, bool is_causal,
-                                     int64_t window_size_left, int64_t window_size_right, const double softcap,
-                                     bool is_rotary_interleaved, int64_t num_splits, int64_t page_multiple,
-                                     OptTensor seqlens_rotary_, OptTensor qv_, OptTensor sink_, bool pack_gqa = false) {
+// q rotated for this step, as a copy: dense (b, s, h, d), or ragged (total_q, h, d) with cu_seqlens_q.  Positions: causal / local ->
+// row i of a sequence sits at its offset + i, otherwise every row at the offset (flash_attn/flash_attn_interface.py:1516-1524,
+// src/flash_fwd_kernel.h:753-775); the offset is seqlens_rotary where given, else the fill level in front of the append.
+Tensor rotate_q(const Tensor &q, const OptTensor &cu_seqlens_q, int64_t max_seqlen_q, const Tensor &cos, const Tensor &sin,
+                const OptTensor &seqlens_rotary, const Tensor &fill, bool interleaved, bool is_causal, int64_t window_size_left,
+                int64_t window_size_right) {
+    const bool per_row = is_causal || window_size_left >= 0 || window_size_right >= 0;
+    const Tensor &offsets = seqlens_rotary.has_value() ? *seqlens_rotary : fill;
+    Tensor dst = at::empty_like(q, at::MemoryFormat::Contiguous);
+    if (cu_seqlens_q.has_value()) {
+        fa_rotary_varlen_params p{};
+        fill_rotary_common(p, q, dst, cos, sin, interleaved, per_row);
+        p.src_row_stride = q.stride(0); p.src_head_stride = q.stride(1);
+        p.dst_row_stride = dst.stride(0); p.dst_head_stride = dst.stride(1);
+        p.b = (int32_t)offsets.numel(); p.total_q = (int32_t)q.size(0); p.max_seqlen_q = (int32_t)max_seqlen_q;
+        p.h = (int32_t)q.size(1); p.d = (int32_t)q.size(2);
+        p.cu_seqlens_q = static_cast<const int32_t *>(cu_seqlens_q->data_ptr());
+        p.offsets = static_cast<const int32_t *>(offsets.data_ptr());
+        const int st = fa_rotary_apply_varlen(&p, current_stream(q));
+        TORCH_CHECK(st == 0, "fa_rotary_apply_varlen failed (", st, "): ", fa_strerror(st));
+    } else {
+        fa_rotary_params p{};
+        fill_rotary_common(p, q, dst, cos, sin, interleaved, per_row);
+        p.src_batch_stride = q.stride(0); p.src_row_stride = q.stride(1); p.src_head_stride = q.stride(2);
+        p.dst_batch_stride = dst.stride(0); p.dst_row_stride = dst.stride(1); p.dst_head_stride = dst.stride(2);
+        p.b = (int32_t)q.size(0); p.s = (int32_t)q.size(1); p.h = (int32_t)q.size(2); p.d = (int32_t)q.size(3);
+        p.seqlen_offsets = static_cast<const int32_t *>(offsets.data_ptr());
+        const int st = fa_rotary_apply(&p, current_stream(q));
+        TORCH_CHECK(st == 0, "fa_rotary_apply failed (", st, "): ", fa_strerror(st));
+    }
+    return dst;
+}
+
+// The arguments of the dense cache step beside q and the cache; what a caller leaves unset is not passed.
+struct KvcacheArgs {
+    OptTensor k_new, v_new, seqlens_k, rotary_cos, rotary_sin, cache_batch_idx, leftpad_k, block_table, alibi_slopes, out;
+    double softmax_scale = 1.0, softcap = 0.0;
+    bool is_causal = false, is_rotary_interleaved = false;
+    int64_t window_size_left = -1, window_size_right = -1, num_splits = 0;
+    int64_t page_multiple = 1;  // the page-size rule of the calling surface: FA2 256, FA3 any
+    OptTensor seqlens_rotary, qv;  // FA3
+    OptTensor sink;  // the cute surface's learnable sink, (num_heads,) -- checked by its caller; no other surface passes one
+    bool pack_gqa = false;
+};
+
+// mha_fwd_kvcache, csrc/flash_attn/flash_api.cpp:1202-1476
+std::vector<Tensor> fwd_kvcache_core(Tensor q, const Tensor &kcache, const Tensor &vcache, const KvcacheArgs &args) {
+    const OptTensor &k_ = args.k_new, &v_ = args.v_new, &seqlens_k_ = args.seqlens_k, &rotary_cos_ = args.rotary_cos,
+                    &rotary_sin_ = args.rotary_sin, &cache_batch_idx_ = args.cache_batch_idx, &leftpad_k_ = args.leftpad_k,
+                    &block_table_ = args.block_table, &out_ = args.out, &seqlens_rotary_ = args.seqlens_rotary, &qv_ = args.qv,
+                    &sink_ = args.sink;
+    bool is_causal = args.is_causal;
+    const int64_t window_size_left = args.window_size_left;
+    int64_t window_size_right = args.window_size_right;
     const auto q_dtype = q.scalar_type();
     TORCH_CHECK(q_dtype == at::kHalf || q_dtype == at::kBFloat16, "FlashAttention only support fp16 and bf16 data type");
     TORCH_CHECK(kcache.scalar_type() == q_dtype, "query and key must have the same dtype");
@@ -723,12 +844,9 @@ std::vector<Tensor> fwd_kvcache_core(Tensor q, const Tensor &kcache, const Tenso
     CHECK_LAST_CONTIGUOUS(q, "Input tensor must have contiguous last dimension");
     CHECK_LAST_CONTIGUOUS(kcache, "Input tensor must have contiguous last dimension");
     CHECK_LAST_CONTIGUOUS(vcache, "Input tensor must have contiguous last dimension");
-    const bool paged = block_table_.has_value();
-    if (paged) TORCH_CHECK(!cache_batch_idx_.has_value(), "Paged KVcache does not support cache_batch_idx");
     TORCH_CHECK(q.dim() == 4 && kcache.dim() == 4, "q, kcache must have 4 dimensions");
     const int64_t batch_size = q.size(0), head_size_og = q.size(3);
     int64_t seqlen_q = q.size(1), num_heads = q.size(2);
-    int64_t batch_size_c = kcache.size(0), seqlen_k = kcache.size(1);
     const int64_t num_heads_k = kcache.size(2);
     // FA3: V head dim of its own for q/k <= 64 beside v in [256, 512] (MLA: the qv kernel), hopper/flash_api.cpp:783-792
     const int64_t head_size_v = vcache.dim() == 4 ? vcache.size(3) : head_size_og;
@@ -744,17 +862,21 @@ std::vector<Tensor> fwd_kvcache_core(Tensor q, const Tensor &kcache, const Tenso
         CHECK_LAST_CONTIGUOUS(*qv_, "q_v tensor must have contiguous last dimension");
         CHECK_SHAPE(*qv_, "q_v", q.size(0), q.size(1), q.size(2), head_size_v);
     }
-    int64_t page_block_size = 0;
-    if (paged) {
-        auto pr = check_block_table(*block_table_, kcache, batch_size, page_multiple);
-        page_block_size = pr.first;
-        seqlen_k = pr.second * page_block_size; batch_size_c = batch_size;  // (:1266-1268)
-    }
     TORCH_CHECK(batch_size > 0, "batch size must be positive");
     TORCH_CHECK(head_size_og <= 256, "FlashAttention forward only supports head dimension at most 256");
     TORCH_CHECK(head_size_og % 8 == 0, "This flash attention build needs head_size to be a multiple of 8 in fwd_kvcache");
     TORCH_CHECK(num_heads % num_heads_k == 0, "Number of heads in key/value must divide number of heads in query");
-    const OptTensor alibi = check_alibi(alibi_slopes_, batch_size, num_heads);
+    CacheRules rules;  // (the reference's texts: its CHECK_SHAPE prints the expression it compares with)
+    rules.page_multiple = args.page_multiple;
+    const std::string rows = block_table_.has_value() ? "(kcache.size(0), page_block_size, num_heads_k, " : "(batch_size_c, seqlen_k, num_heads_k, ";
+    rules.k_shape = "kcache must have shape " + rows + "head_size_og)"; rules.v_shape = "vcache must have shape " + rows + "head_size_v)";
+    rules.fill_name = "seqlens_k"; rules.fill_dtype = " must have dtype int32"; rules.fill_device = " must be on CUDA";
+    rules.fill_contiguous = " must be contiguous"; rules.fill_shape = " must have shape (batch_size)";
+    rules.idx_longer_ok = true;
+    const CacheSide cache = check_cache(kcache, vcache, block_table_, cache_batch_idx_, seqlens_k_, leftpad_k_, batch_size, head_size_og,
+                                        head_size_v, rules);
+    const int64_t seqlen_k = cache.seqlen_k;
+    const OptTensor alibi = check_alibi(args.alibi_slopes, batch_size, num_heads);
     if (seqlen_q == 1 && !alibi.has_value()) is_causal = false;  // (:1270)
     if (is_causal) window_size_right = 0;
     // (b, 1, (h_k ngroups), d) -> (b, ngroups, h_k, d): one pass over the cache serves the whole GQA group (:1272-1285)
@@ -767,13 +889,6 @@ std::vector<Tensor> fwd_kvcache_core(Tensor q, const Tensor &kcache, const Tenso
         seqlen_q = ngroups; num_heads = num_heads_k;
     }
     CHECK_SHAPE(q, "q", batch_size, seqlen_q, num_heads, head_size_og);
-    if (paged) {
-        CHECK_SHAPE(kcache, "kcache", kcache.size(0), page_block_size, num_heads_k, head_size_og);
-        CHECK_SHAPE(vcache, "vcache", kcache.size(0), page_block_size, num_heads_k, head_size_v);
-    } else {
-        CHECK_SHAPE(kcache, "kcache", batch_size_c, seqlen_k, num_heads_k, head_size_og);
-        CHECK_SHAPE(vcache, "vcache", batch_size_c, seqlen_k, num_heads_k, head_size_v);
-    }
     Tensor out;
     if (out_.has_value() && !swapped) {
         out = out_.value();
@@ -798,67 +913,33 @@ std::vector<Tensor> fwd_kvcache_core(Tensor q, const Tensor &kcache, const Tenso
         CHECK_SHAPE(*k_, "k", batch_size, seqlen_knew, num_heads_k, head_size_og);
         CHECK_SHAPE(*v_, "v", batch_size, seqlen_knew, num_heads_k, head_size_v);
     }
-    if (seqlens_k_.has_value()) {
-        TORCH_CHECK(seqlens_k_->scalar_type() == at::kInt, "seqlens_k must have dtype int32");
-        CHECK_DEVICE(*seqlens_k_, "seqlens_k");
-        TORCH_CHECK(seqlens_k_->is_contiguous(), "seqlens_k must be contiguous");
-        CHECK_SHAPE(*seqlens_k_, "seqlens_k", batch_size);
-    }
-    check_leftpad(leftpad_k_, batch_size, paged);
-    if (cache_batch_idx_.has_value()) {
-        CHECK_DEVICE(*cache_batch_idx_, "cache_batch_idx");
-        TORCH_CHECK(cache_batch_idx_->is_contiguous(), "cache_batch_idx must be contiguous");
-        TORCH_CHECK(cache_batch_idx_->scalar_type() == at::kInt, "cache_batch_idx must have dtype int32");
-    } else {
-        TORCH_CHECK(batch_size_c >= batch_size, "the KV cache must have at least batch_size entries");
-    }
-    TORCH_CHECK(aligned(kcache) && aligned(vcache),
-                "the KV cache must be 16-byte aligned with row/head/batch strides that are multiples of 8");
     const bool rotary = rotary_cos_.has_value();
-    if (rotary) {  // (:1404-1428)
+    if (rotary) {
         TORCH_CHECK(k_.has_value(), "If rotary cos/sin are provided, new key / value to be appended to KV cache must also be provided");
-        CHECK_DEVICE(*rotary_cos_, "rotary_cos");
-        const int64_t rotary_dim = rotary_cos_->size(1) * 2;
-        TORCH_CHECK(rotary_dim <= head_size_og, "rotary_dim must be <= headdim");
-        TORCH_CHECK(rotary_dim % 16 == 0, "Only rotary dimensions divisible by 16 are currently supported");
-        const int64_t seqlen_ro = rotary_cos_->size(0);
-        TORCH_CHECK(seqlen_ro >= seqlen_k, "cos/sin seqlen must be at least the seqlen of KV cache");
-        CHECK_SHAPE(*rotary_cos_, "rotary_cos", seqlen_ro, rotary_dim / 2);
-        TORCH_CHECK(rotary_cos_->is_contiguous(), "rotary_cos must be contiguous");
-        TORCH_CHECK(rotary_cos_->scalar_type() == q_dtype, "rotary_cos must have the same dtype as query");
         TORCH_CHECK(rotary_sin_.has_value(), "If rotary cos is provided, rotary sin must also be provided");
-        CHECK_DEVICE(*rotary_sin_, "rotary_sin");
-        CHECK_SHAPE(*rotary_sin_, "rotary_sin", seqlen_ro, rotary_dim / 2);
-        TORCH_CHECK(rotary_sin_->is_contiguous(), "rotary_sin must be contiguous");
-        TORCH_CHECK(rotary_sin_->scalar_type() == q_dtype, "rotary_cos must have the same dtype as query");
+        check_rotary_tables(*rotary_cos_, *rotary_sin_, head_size_og, seqlen_k, q_dtype, "query", /*per_tensor=*/true);
     }
     c10::hip::HIPGuardMasqueradingAsCUDA device_guard(q.device());
     Tensor softmax_lse = at::empty({batch_size, num_heads, seqlen_q}, q.options().dtype(at::kFloat));
     OptTensor seqused = seqlens_k_;
     if (seqlen_knew > 0) {  // "Append_KV": new rows land at [seqlens_k, seqlens_k + seqlen_knew) of each cache entry
         const Tensor kn = aligned_or_copy(*k_), vn = aligned_or_copy(*v_);
-        kvcache_append(kn, vn, kcache, vcache, *seqlens_k_, cache_batch_idx_, block_table_, rotary_cos_, rotary_sin_, is_rotary_interleaved,
-                       seqlens_rotary_);
+        kvcache_append(kn, vn, kcache, vcache, *seqlens_k_, cache_batch_idx_, block_table_, rotary_cos_, rotary_sin_,
+                       args.is_rotary_interleaved, seqlens_rotary_);
         seqused = *seqlens_k_ + seqlen_knew;
     }
     Tensor qc = aligned_or_copy(q);
-    if (rotary) {
-        // causal / local: query row i sits at position seqlens_k + i; otherwise every row at seqlens_k
-        // (flash_attn/flash_attn_interface.py:1516-1524, src/flash_fwd_kernel.h:753-775)
-        const bool per_row = is_causal || window_size_left >= 0 || window_size_right >= 0;
-        Tensor q_ro = at::empty_like(qc, at::MemoryFormat::Contiguous);
-        rotary_apply(qc, q_ro, *rotary_cos_, *rotary_sin_, seqlens_rotary_.has_value() ? *seqlens_rotary_ : *seqlens_k_,
-                     is_rotary_interleaved, per_row);
-        qc = q_ro;
-    }
+    if (rotary)
+        qc = rotate_q(qc, c10::nullopt, 0, *rotary_cos_, *rotary_sin_, seqlens_rotary_, *seqlens_k_, args.is_rotary_interleaved, is_causal,
+                      window_size_left, window_size_right);
     Tensor oc = aligned(out) ? out : at::empty_like(out, at::MemoryFormat::Contiguous);
     if (seqlen_k > 0) {
         FwdArgs a;
-        a.batch = batch_size; a.max_seqlen_q = seqlen_q; a.max_seqlen_k = seqlen_k; a.softmax_scale = softmax_scale;
-        a.causal = is_causal; a.window_left = window_size_left; a.window_right = window_size_right; a.softcap = softcap;
+        a.batch = batch_size; a.max_seqlen_q = seqlen_q; a.max_seqlen_k = seqlen_k; a.softmax_scale = args.softmax_scale;
+        a.causal = is_causal; a.window_left = window_size_left; a.window_right = window_size_right; a.softcap = args.softcap;
         a.seqused_k = seqused; a.alibi = alibi; a.kv_batch_idx = cache_batch_idx_; a.block_table = block_table_;
-        a.num_splits = (int)num_splits; a.leftpad_k = leftpad_k_;
-        a.pack_gqa = pack_gqa;  // (behind the single-token GQA swap h == h_k: the hint has nothing to pack there)
+        a.num_splits = (int)args.num_splits; a.leftpad_k = leftpad_k_;
+        a.pack_gqa = args.pack_gqa;  // (behind the single-token GQA swap h == h_k: the hint has nothing to pack there)
         if (qv_.has_value()) a.qv = aligned_or_copy(*qv_);
         if (sink_.has_value()) {
             a.sink = sink_;
@@ -885,18 +966,6 @@ std::vector<Tensor> fwd_kvcache_core(Tensor q, const Tensor &kcache, const Tenso
     return {out, softmax_lse};
 }
 
-std::vector<Tensor> fwd_kvcache_impl(Tensor q, const Tensor &kcache, const Tensor &vcache, OptTensor k_, OptTensor v_,
-                                     OptTensor seqlens_k_, OptTensor rotary_cos_, OptTensor rotary_sin_,
-                                     OptTensor cache_batch_idx_, OptTensor leftpad_k_, OptTensor block_table_,
-                                     OptTensor alibi_slopes_, OptTensor out_, const double softmax_scale, bool is_causal,
-                                     int64_t window_size_left, int64_t window_size_right, const double softcap,
-                                     bool is_rotary_interleaved, int64_t num_splits, int64_t page_multiple,
-                                     OptTensor seqlens_rotary_, OptTensor qv_) {
-    return fwd_kvcache_core(q, kcache, vcache, k_, v_, seqlens_k_, rotary_cos_, rotary_sin_, cache_batch_idx_, leftpad_k_,
-                            block_table_, alibi_slopes_, out_, softmax_scale, is_causal, window_size_left, window_size_right, softcap,
-                            is_rotary_interleaved, num_splits, page_multiple, seqlens_rotary_, qv_, c10::nullopt);
-}
-
 std::vector<Tensor> mha_fwd_kvcache(Tensor &q, const Tensor &kcache, const Tensor &vcache, OptTensor &k_, OptTensor &v_,
                                     OptTensor &seqlens_k_, OptTensor &rotary_cos_, OptTensor &rotary_sin_,
                                     OptTensor &cache_batch_idx_, OptTensor &leftpad_k_, OptTensor &block_table_,
@@ -907,9 +976,14 @@ std::vector<Tensor> mha_fwd_kvcache(Tensor &q, const Tensor &kcache, const Tenso
     if (vcache.dim() == 4 && kcache.dim() == 4 && vcache.size(3) != kcache.size(3))
         TORCH_CHECK(false, block_table_.has_value() ? "vcache must have shape (kcache.size(0), page_block_size, num_heads_k, head_size_og)"
                                                     : "vcache must have shape (batch_size_c, seqlen_k, num_heads_k, head_size_og)");
-    return fwd_kvcache_impl(q, kcache, vcache, k_, v_, seqlens_k_, rotary_cos_, rotary_sin_, cache_batch_idx_, leftpad_k_,
-                            block_table_, alibi_slopes_, out_, softmax_scale, is_causal, window_size_left, window_size_right,
-                            softcap, is_rotary_interleaved, num_splits, 256, c10::nullopt, c10::nullopt);  // the reference's page rule (:1265)
+    KvcacheArgs a;
+    a.k_new = k_; a.v_new = v_; a.seqlens_k = seqlens_k_; a.rotary_cos = rotary_cos_; a.rotary_sin = rotary_sin_;
+    a.cache_batch_idx = cache_batch_idx_; a.leftpad_k = leftpad_k_; a.block_table = block_table_; a.alibi_slopes = alibi_slopes_;
+    a.out = out_; a.softmax_scale = softmax_scale; a.is_causal = is_causal; a.window_size_left = window_size_left;
+    a.window_size_right = window_size_right; a.softcap = softcap; a.is_rotary_interleaved = is_rotary_interleaved;
+    a.num_splits = num_splits;
+    a.page_multiple = 256;  // the reference's page rule (:1265)
+    return fwd_kvcache_core(q, kcache, vcache, a);
 }
 
 // a shape as Python prints a tuple: "(2, 128, 8, 512)", "(7,)"
@@ -924,6 +998,13 @@ std::string tuple_str(c10::IntArrayRef s) {
 void fa3_window(int64_t seqlen_q, int64_t seqlen_k, int64_t &left, int64_t &right) {
     if (left >= seqlen_k - 1) left = -1;
     if (right >= seqlen_q - 1) right = -1;
+}
+
+// seqlens_rotary (hopper/flash_api.cpp:1074-1079): the rotary positions where they are not the cache fill levels
+void check_seqlens_rotary(const Tensor &t, int64_t batch_size) {
+    TORCH_CHECK(t.is_cuda() && t.is_contiguous(), "seqlens_rotary must be a contiguous CUDA tensor");
+    TORCH_CHECK(t.scalar_type() == at::kInt, "seqlens_rotary must have dtype torch.int32");
+    TORCH_CHECK(t.sizes() == c10::IntArrayRef({batch_size}), "seqlens_rotary must have shape (batch_size,)");
 }
 
 // One continuous-batching step over a KV cache (flash_attn_with_kvcache(..., cu_seqlens_q=, cu_seqlens_k_new=, max_seqlen_q=),
@@ -949,8 +1030,6 @@ std::tuple<Tensor, Tensor> fwd_kvcache_ragged(const Tensor &q, const Tensor &kca
     TORCH_CHECK(max_seqlen_q >= 0, "max_seqlen_q must be provided if cu_seqlens_q is provided");      // :745
     TORCH_CHECK(q.dim() == 3, "q must have shape (total_q, num_heads, head_size)");
     TORCH_CHECK(seqused_k.has_value(), "seqused_k must be provided for a KV-cache call with cu_seqlens_q");
-    const bool paged = page_table.has_value();
-    if (paged) TORCH_CHECK(!kv_batch_idx.has_value(), "Paged KVcache does not support cache_batch_idx");
     TORCH_CHECK(kcache.dim() == 4 && vcache.dim() == 4, "kcache, vcache must have 4 dimensions");
     const int64_t total_q = q.size(0), num_heads = q.size(1), head_size = q.size(2);
     const int64_t batch_size = cu_seqlens_q.numel() - 1;
@@ -959,33 +1038,15 @@ std::tuple<Tensor, Tensor> fwd_kvcache_ragged(const Tensor &q, const Tensor &kca
     TORCH_CHECK(head_size <= 256, "FlashAttention forward only supports head dimension at most 256");
     TORCH_CHECK(head_size % 8 == 0, "head_size should be a multiple of 8");
     TORCH_CHECK(num_heads_k > 0 && num_heads % num_heads_k == 0, "Number of heads in key/value must divide number of heads in query");
-    int64_t seqlen_k = kcache.size(1), batch_size_c = kcache.size(0);
-    if (paged) {
-        auto pr = check_block_table(*page_table, kcache, batch_size, 1);
-        seqlen_k = pr.second * pr.first; batch_size_c = batch_size;
-        CHECK_SHAPE(kcache, "kcache", kcache.size(0), pr.first, num_heads_k, head_size);
-        CHECK_SHAPE(vcache, "vcache", kcache.size(0), pr.first, num_heads_k, head_size_v);
-    } else {
-        CHECK_SHAPE(kcache, "kcache", batch_size_c, seqlen_k, num_heads_k, head_size);
-        CHECK_SHAPE(vcache, "vcache", batch_size_c, seqlen_k, num_heads_k, head_size_v);
-    }
-    for (const auto &[t, name] : {std::make_pair(&seqused_q, "seqused_q"), std::make_pair(&seqused_k, "seqused_k")})
-        if (t->has_value()) {
-            TORCH_CHECK((*t)->scalar_type() == at::kInt, name, " must have dtype int32");  // :830, :836
-            TORCH_CHECK((*t)->is_cuda() && (*t)->is_contiguous() && (*t)->dim() == 1 && (*t)->numel() == batch_size, name,
-                        " must be a contiguous CUDA tensor of shape (batch_size,)");
-        }
-    check_leftpad(leftpad_k, batch_size, paged);
-    if (kv_batch_idx.has_value()) {
-        CHECK_DEVICE(*kv_batch_idx, "kv_batch_idx");
-        TORCH_CHECK(kv_batch_idx->is_contiguous(), "kv_batch_idx must be contiguous");
-        TORCH_CHECK(kv_batch_idx->scalar_type() == at::kInt, "kv_batch_idx must have dtype int32");  // :1088
-        CHECK_SHAPE(*kv_batch_idx, "kv_batch_idx", batch_size);
-    } else {
-        TORCH_CHECK(batch_size_c >= batch_size, "the KV cache must have at least batch_size entries");
-    }
-    TORCH_CHECK(aligned(kcache) && aligned(vcache),
-                "the KV cache must be 16-byte aligned with row/head/batch strides that are multiples of 8");
+    CacheRules rules;  // (user-visible legacy texts: "pr.first" was the page size in the expression an older CHECK_SHAPE printed)
+    const std::string rows = page_table.has_value() ? "(kcache.size(0), pr.first, num_heads_k, " : "(batch_size_c, seqlen_k, num_heads_k, ";
+    rules.k_shape = "kcache must have shape " + rows + "head_size)"; rules.v_shape = "vcache must have shape " + rows + "head_size_v)";
+    rules.fill_dtype = " must have dtype int32";  // :830, :836
+    rules.fill_device = rules.fill_contiguous = rules.fill_shape = " must be a contiguous CUDA tensor of shape (batch_size,)";
+    rules.idx_name = "kv_batch_idx";  // :1088
+    if (seqused_q.has_value()) check_fill_levels(*seqused_q, "seqused_q", batch_size, rules);
+    const CacheSide cache = check_cache(kcache, vcache, page_table, kv_batch_idx, seqused_k, leftpad_k, batch_size, head_size, head_size_v, rules);
+    const int64_t seqlen_k = cache.seqlen_k;
     const bool ragged_new = cu_seqlens_k_new.has_value();
     if (k_new.has_value()) {  // :929-975
         TORCH_CHECK(k_new->scalar_type() == q_dtype, "k_new must have the same dtype as query");
@@ -993,34 +1054,14 @@ std::tuple<Tensor, Tensor> fwd_kvcache_ragged(const Tensor &q, const Tensor &kca
         CHECK_DEVICE(*k_new, "k_new"); CHECK_DEVICE(*v_new, "v_new");
         TORCH_CHECK(k_new->stride(-1) == 1, "k_new tensor must have contiguous last dimension");
         TORCH_CHECK(v_new->stride(-1) == 1, "v_new tensor must have contiguous last dimension");
-        if (ragged_new) {
-            CHECK_DEVICE(*cu_seqlens_k_new, "cu_seqlens_k_new");
-            TORCH_CHECK(cu_seqlens_k_new->is_contiguous(), "cu_seqlens_k_new must be contiguous");
-            TORCH_CHECK(cu_seqlens_k_new->scalar_type() == at::kInt, "cu_seqlens_k_new must have dtype torch.int32");  // :939
-            TORCH_CHECK(k_new->dim() == 3, "k_new must have shape (total_k_new, num_heads_k, head_size) with cu_seqlens_k_new");
-            CHECK_SHAPE(*k_new, "k_new", k_new->size(0), num_heads_k, head_size);
-            CHECK_SHAPE(*v_new, "v_new", k_new->size(0), num_heads_k, head_size_v);
-            CHECK_SHAPE(*cu_seqlens_k_new, "cu_seqlens_k_new", batch_size + 1);
-        } else {
-            TORCH_CHECK(k_new->dim() == 4, "k_new must have shape (batch_size, seqlen_k_new, num_heads_k, head_size) without cu_seqlens_k_new");
-            CHECK_SHAPE(*k_new, "k_new", batch_size, k_new->size(1), num_heads_k, head_size);
-            CHECK_SHAPE(*v_new, "v_new", batch_size, k_new->size(1), num_heads_k, head_size_v);
-        }
+        check_new_rows(*k_new, *v_new, cu_seqlens_k_new, batch_size, num_heads_k, head_size, head_size_v, "k_new->size", "head_size_v");
     } else {
         TORCH_CHECK(!ragged_new, "cu_seqlens_k_new needs k_new and v_new");
     }
     const bool rotary = rotary_cos.has_value();
-    if (rotary) {  // (:1050-1072; the texts of the dense route)
+    if (rotary) {
         TORCH_CHECK(k_new.has_value(), "If rotary cos/sin are provided, new key / value to be appended to KV cache must also be provided");
-        CHECK_DEVICE(*rotary_cos, "rotary_cos"); CHECK_DEVICE(*rotary_sin, "rotary_sin");
-        TORCH_CHECK(rotary_cos->dim() == 2 && rotary_sin->sizes() == rotary_cos->sizes(), "rotary_cos / rotary_sin must have shape (seqlen_ro, rotary_dim / 2)");
-        const int64_t rotary_dim = rotary_cos->size(1) * 2;
-        TORCH_CHECK(rotary_dim <= head_size, "rotary_dim must be <= headdim");
-        TORCH_CHECK(rotary_dim % 16 == 0, "Only rotary dimensions divisible by 16 are currently supported");
-        TORCH_CHECK(rotary_cos->size(0) >= seqlen_k, "cos/sin seqlen must be at least the seqlen of KV cache");
-        TORCH_CHECK(rotary_cos->is_contiguous() && rotary_sin->is_contiguous(), "rotary_cos / rotary_sin must be contiguous");
-        TORCH_CHECK(rotary_cos->scalar_type() == q_dtype && rotary_sin->scalar_type() == q_dtype,
-                    "rotary_cos / rotary_sin must have the same dtype as query");
+        check_rotary_tables(*rotary_cos, *rotary_sin, head_size, seqlen_k, q_dtype, "query");
     }
     std::vector<int64_t> out_shape = {total_q, num_heads, head_size_v};
     if (out_.has_value()) {
@@ -1048,35 +1089,31 @@ std::tuple<Tensor, Tensor> fwd_kvcache_ragged(const Tensor &q, const Tensor &kca
         seqused = *seqused_k + k_new->size(1);
         appended = true;
     }
-    if (single_token && !appended) {
-        // a pure decode step in ragged clothes: exactly the dense FA3 call on q viewed as (b, 1, h, d)
-        OptTensor out4, qv4;
-        if (out_.has_value()) out4 = out_->unsqueeze(1);
-        if (qv.has_value()) qv4 = qv->unsqueeze(1);
-        auto r = fwd_kvcache_core(q.unsqueeze(1), kcache, vcache, k_new, v_new, seqused_k, rotary_cos, rotary_sin, kv_batch_idx, leftpad_k,
-                                  page_table, c10::nullopt, out4, softmax_scale, is_causal, window_size_left, window_size_right,
-                                  softcap, is_rotary_interleaved, num_splits, 1, seqlens_rotary, qv4, sink, pack_gqa);
+    // one row per sequence: the dense decode route on q viewed as (b, 1, h, d), its results viewed back.  `decode`: what both uses pass
+    KvcacheArgs decode;
+    if (single_token) {
+        if (out_.has_value()) decode.out = out_->unsqueeze(1);
+        if (qv.has_value()) decode.qv = qv->unsqueeze(1);
+        decode.cache_batch_idx = kv_batch_idx; decode.leftpad_k = leftpad_k; decode.block_table = page_table;
+        decode.softmax_scale = softmax_scale; decode.is_causal = is_causal; decode.window_size_left = window_size_left;
+        decode.window_size_right = window_size_right; decode.softcap = softcap; decode.num_splits = num_splits;
+        decode.sink = sink; decode.pack_gqa = pack_gqa;
+    }
+    const auto as_ragged = [&](const std::vector<Tensor> &r) -> std::tuple<Tensor, Tensor> {
         return {r[0].reshape(out_shape), r[1].reshape({batch_size, num_heads}).transpose(0, 1)};
+    };
+    if (single_token && !appended) {  // a pure decode step in ragged clothes: exactly the dense FA3 call, its append and rotary included
+        decode.k_new = k_new; decode.v_new = v_new; decode.seqlens_k = seqused_k; decode.rotary_cos = rotary_cos;
+        decode.rotary_sin = rotary_sin; decode.is_rotary_interleaved = is_rotary_interleaved; decode.seqlens_rotary = seqlens_rotary;
+        return as_ragged(fwd_kvcache_core(q.unsqueeze(1), kcache, vcache, decode));
     }
     Tensor qc = aligned_or_copy(q);
-    if (rotary && total_q > 0) {
-        // the dense route's rule per sequence: causal / local -> row i at the old fill level (or seqlens_rotary) + i, otherwise
-        // every row at that level
-        const bool per_row = is_causal || window_size_left >= 0 || window_size_right >= 0;
-        Tensor q_ro = at::empty_like(qc, at::MemoryFormat::Contiguous);
-        rotary_apply_varlen(qc, q_ro, cu_seqlens_q, max_seqlen_q, *rotary_cos, *rotary_sin,
-                            seqlens_rotary.has_value() ? *seqlens_rotary : *seqused_k, is_rotary_interleaved, per_row);
-        qc = q_ro;
-    }
-    if (single_token) {
-        // one row per sequence behind a ragged append: the dense decode route on the fill levels the append wrote
-        OptTensor out4, qv4;
-        if (out_.has_value()) out4 = out_->unsqueeze(1);
-        if (qv.has_value()) qv4 = qv->unsqueeze(1);
-        auto r = fwd_kvcache_core(qc.unsqueeze(1), kcache, vcache, c10::nullopt, c10::nullopt, seqused, c10::nullopt, c10::nullopt,
-                                  kv_batch_idx, leftpad_k, page_table, c10::nullopt, out4, softmax_scale, is_causal, window_size_left,
-                                  window_size_right, softcap, false, num_splits, 1, c10::nullopt, qv4, sink, pack_gqa);
-        return {r[0].reshape(out_shape), r[1].reshape({batch_size, num_heads}).transpose(0, 1)};
+    if (rotary && total_q > 0)
+        qc = rotate_q(qc, cu_seqlens_q, max_seqlen_q, *rotary_cos, *rotary_sin, seqlens_rotary, *seqused_k, is_rotary_interleaved, is_causal,
+                      window_size_left, window_size_right);
+    if (single_token) {  // behind a ragged append: the read alone, on the fill levels the append wrote
+        decode.seqlens_k = seqused;
+        return as_ragged(fwd_kvcache_core(qc.unsqueeze(1), kcache, vcache, decode));
     }
     Tensor out = out_.has_value() ? *out_ : at::empty(out_shape, q.options());
     Tensor softmax_lse = at::empty({num_heads, total_q}, q.options().dtype(at::kFloat));
@@ -1102,32 +1139,31 @@ std::tuple<Tensor, Tensor> fwd_kvcache_ragged(const Tensor &q, const Tensor &kca
     return {out, softmax_lse};
 }
 
+void check_kv8_descale(const Tensor &t, const char *name, int64_t batch_size, int64_t num_heads_k) {
+    TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kFloat && t.sizes() == c10::IntArrayRef({batch_size, num_heads_k}), name,
+                " must be fp32 (batch_size, num_heads_k)");
+}
+
 // 16-bit queries over an fp8 (e4m3) KV cache -- kv_cache_dtype = fp8 of a serving stack (include/fa_fwd.h, fa_fwd_kv8): q and
 // out fp16 / bf16, k / v the cache as Float8_e4m3fn, (b_cache, seqlen_k, h_k, d) or pages behind page_table, k_descale /
 // v_descale fp32 (b, h_k).  Dense q (b, seqlen_q, h, d) or ragged q (total_q, h, d) with cu_seqlens_q; cache_seqlens in
 // seqused_k.  One kernel for every h / h_k (it packs the GQA group into its rows itself: no swap, pack_gqa is moot).
-// The caller has appended the step's new rows and rotated q (fa3_fwd_core) and refused what the route does not serve (qv,
-// attention_chunk, head dims).
+// The read half of fwd_kv8_step below, which has checked q and cu_seqlens_q, appended the step's new rows, rotated q and
+// refused what the route does not serve (qv, attention_chunk, head dims).
 std::tuple<Tensor, Tensor> fwd_kv8(const Tensor &q, const Tensor &k, const Tensor &v, const OptTensor &out_,
                                    const OptTensor &cu_seqlens_q, const OptTensor &seqused_q, const OptTensor &seqused_k,
                                    c10::optional<int64_t> max_seqlen_q_, const OptTensor &page_table, const OptTensor &kv_batch_idx,
                                    const OptTensor &leftpad_k, const OptTensor &k_descale, const OptTensor &v_descale,
                                    double softmax_scale, bool is_causal, int64_t window_size_left, int64_t window_size_right,
                                    double softcap, int64_t num_splits) {
-    CHECK_DEVICE(q, "q"); CHECK_LAST_CONTIGUOUS(q, "Input tensor must have contiguous last dimension");
     CHECK_DEVICE(k, "k"); CHECK_LAST_CONTIGUOUS(k, "Input tensor must have contiguous last dimension");
     CHECK_DEVICE(v, "v"); CHECK_LAST_CONTIGUOUS(v, "Input tensor must have contiguous last dimension");
-    const bool ragged = cu_seqlens_q.has_value(), paged = page_table.has_value();
+    const bool ragged = cu_seqlens_q.has_value();
     TORCH_CHECK(k.dim() == 4 && v.dim() == 4,
                 "an fp8 k / v must be a KV cache of shape (batch or num_pages, seqlen or page_size, num_heads_k, head_size)");
-    TORCH_CHECK(q.dim() == (ragged ? 3 : 4), ragged ? "q must have shape (total_q, num_heads, head_size) with cu_seqlens_q"
-                                                    : "q must have shape (batch_size, seqlen_q, num_heads, head_size)");
     const int64_t head_size = q.size(-1), num_heads = q.size(-2), num_heads_k = k.size(2);
     int64_t batch_size, seqlen_q, total_q;
     if (ragged) {
-        TORCH_CHECK(cu_seqlens_q->scalar_type() == at::kInt && cu_seqlens_q->is_contiguous() && cu_seqlens_q->is_cuda(),
-                    "cu_seqlens_q must be a contiguous int32 CUDA tensor");
-        TORCH_CHECK(max_seqlen_q_.has_value() && *max_seqlen_q_ > 0, "max_seqlen_q must be provided with cu_seqlens_q");
         TORCH_CHECK(seqused_k.has_value(), "seqused_k (the cache fill levels) must be provided with cu_seqlens_q over a KV cache");
         batch_size = cu_seqlens_q->numel() - 1; seqlen_q = *max_seqlen_q_; total_q = q.size(0);
     } else {
@@ -1137,36 +1173,20 @@ std::tuple<Tensor, Tensor> fwd_kv8(const Tensor &q, const Tensor &k, const Tenso
     }
     TORCH_CHECK(batch_size > 0, "batch size must be positive");
     TORCH_CHECK(num_heads_k > 0 && num_heads % num_heads_k == 0, "Number of heads in key/value must divide number of heads in query");
-    if (paged) TORCH_CHECK(!kv_batch_idx.has_value(), "Paged KVcache does not support cache_batch_idx");
-    int64_t seqlen_k = k.size(1), batch_size_c = k.size(0);
-    if (paged) {
-        const auto pr = check_block_table(*page_table, k, batch_size, 1);
-        seqlen_k = pr.second * pr.first; batch_size_c = batch_size;
-    }
-    TORCH_CHECK(k.size(3) == head_size, "k must have shape (..., ", num_heads_k, ", ", head_size, ")");
-    TORCH_CHECK(v.sizes() == k.sizes(), "v must have the shape of k");
-    for (const auto &[t, name] : {std::make_pair(&seqused_q, "seqused_q"), std::make_pair(&seqused_k, "seqused_k")})
-        if (t->has_value())
-            TORCH_CHECK((*t)->is_cuda() && (*t)->scalar_type() == at::kInt && (*t)->is_contiguous() && (*t)->numel() == batch_size,
-                        name, " must be int32 of shape (batch_size,)");
-    check_leftpad(leftpad_k, batch_size, paged);
+    CacheRules rules;
+    rules.base_grain = rules.stride_grain = 16;
+    rules.misaligned = "the fp8 KV cache must be 16-byte aligned with row/head/batch strides that are multiples of 16";
+    rules.k_shape = "k must have shape (..., " + std::to_string(num_heads_k) + ", " + std::to_string(head_size) + ")";
+    rules.v_shape = "v must have the shape of k";
+    rules.fill_dtype = rules.fill_device = rules.fill_contiguous = rules.fill_shape = " must be int32 of shape (batch_size,)";
+    rules.fill_any_dims = true;
+    rules.idx_contiguous = rules.idx_length = " must be contiguous, (batch_size,)";
+    if (seqused_q.has_value()) check_fill_levels(*seqused_q, "seqused_q", batch_size, rules);
+    const CacheSide cache = check_cache(k, v, page_table, kv_batch_idx, seqused_k, leftpad_k, batch_size, head_size, head_size, rules);
+    const int64_t seqlen_k = cache.seqlen_k;
     if (leftpad_k.has_value()) TORCH_CHECK(seqused_k.has_value(), "seqused_k must be provided with k_new / leftpad_k");
-    if (kv_batch_idx.has_value()) {
-        CHECK_DEVICE(*kv_batch_idx, "cache_batch_idx");
-        TORCH_CHECK(kv_batch_idx->is_contiguous() && kv_batch_idx->numel() == batch_size, "cache_batch_idx must be contiguous, (batch_size,)");
-        TORCH_CHECK(kv_batch_idx->scalar_type() == at::kInt, "cache_batch_idx must have dtype int32");
-    } else {
-        TORCH_CHECK(batch_size_c >= batch_size, "the KV cache must have at least batch_size entries");
-    }
     for (const auto &[t, name] : {std::make_pair(&k_descale, "k_descale"), std::make_pair(&v_descale, "v_descale")})
-        if (t->has_value())
-            TORCH_CHECK((*t)->is_cuda() && (*t)->scalar_type() == at::kFloat && (*t)->sizes() == c10::IntArrayRef({batch_size, num_heads_k}),
-                        name, " must be fp32 (batch_size, num_heads_k)");
-    for (const Tensor *t : {&k, &v}) {
-        bool ok = reinterpret_cast<uintptr_t>(t->data_ptr()) % 16 == 0;
-        for (int64_t i = 0; i < 3; ++i) ok = ok && t->stride(i) % 16 == 0;
-        TORCH_CHECK(ok, "the fp8 KV cache must be 16-byte aligned with row/head/batch strides that are multiples of 16");
-    }
+        if (t->has_value()) check_kv8_descale(**t, name, batch_size, num_heads_k);
     Tensor out;
     if (out_.has_value()) {
         out = *out_;
@@ -1223,7 +1243,7 @@ std::tuple<Tensor, Tensor> fwd_kv8(const Tensor &q, const Tensor &k, const Tenso
     }
     p.kv_batch_idx = static_cast<const int32_t *>(ptr(kv_batch_idx));
     p.leftpad_k = static_cast<const int32_t *>(ptr(leftpad_k));
-    if (paged) {
+    if (cache.paged) {
         p.block_table = static_cast<const int32_t *>(page_table->data_ptr());
         p.block_table_batch_stride = page_table->stride(0);
         p.page_block_size = (int32_t)k.size(1);
@@ -1264,7 +1284,6 @@ Tensor kvcache_append_kv8(const Tensor &k_cache, const Tensor &v_cache, const Te
     CHECK_DEVICE(k_cache, "k_cache"); CHECK_DEVICE(v_cache, "v_cache"); CHECK_DEVICE(k_new, "k_new"); CHECK_DEVICE(v_new, "v_new");
     TORCH_CHECK(k_cache.dim() == 4 && v_cache.dim() == 4,
                 "an fp8 k / v must be a KV cache of shape (batch or num_pages, seqlen or page_size, num_heads_k, head_size)");
-    TORCH_CHECK(v_cache.sizes() == k_cache.sizes(), "v must have the shape of k");
     CHECK_LAST_CONTIGUOUS(k_cache, "Input tensor must have contiguous last dimension");
     CHECK_LAST_CONTIGUOUS(v_cache, "Input tensor must have contiguous last dimension");
     TORCH_CHECK(k_new.stride(-1) == 1, "k_new tensor must have contiguous last dimension");
@@ -1272,69 +1291,33 @@ Tensor kvcache_append_kv8(const Tensor &k_cache, const Tensor &v_cache, const Te
     const int64_t num_heads_k = k_cache.size(2), head_size = k_cache.size(3);
     TORCH_CHECK(head_size <= 128 && head_size % 16 == 0,
                 "This flash attention build supports an fp8 KV cache for head_size <= 128 that is a multiple of 16, got ", head_size);
-    TORCH_CHECK(cache_seqlens.is_cuda() && cache_seqlens.scalar_type() == at::kInt && cache_seqlens.is_contiguous() &&
-                    cache_seqlens.dim() == 1 && cache_seqlens.numel() > 0,
-                "cache_seqlens must be a contiguous int32 CUDA tensor of shape (batch_size,)");
-    const int64_t batch_size = cache_seqlens.numel();
-    const bool ragged = cu_seqlens_k_new.has_value(), paged = page_table.has_value();
-    if (ragged) {
-        CHECK_DEVICE(*cu_seqlens_k_new, "cu_seqlens_k_new");
-        TORCH_CHECK(cu_seqlens_k_new->is_contiguous(), "cu_seqlens_k_new must be contiguous");
-        TORCH_CHECK(cu_seqlens_k_new->scalar_type() == at::kInt, "cu_seqlens_k_new must have dtype torch.int32");
-        TORCH_CHECK(k_new.dim() == 3, "k_new must have shape (total_k_new, num_heads_k, head_size) with cu_seqlens_k_new");
-        CHECK_SHAPE(k_new, "k_new", k_new.size(0), num_heads_k, head_size);
-        CHECK_SHAPE(v_new, "v_new", k_new.size(0), num_heads_k, head_size);
-        CHECK_SHAPE(*cu_seqlens_k_new, "cu_seqlens_k_new", batch_size + 1);
-        TORCH_CHECK(max_seqlen_k_new >= 0, "max_seqlen_k_new must be non-negative");
-    } else {
-        TORCH_CHECK(k_new.dim() == 4, "k_new must have shape (batch_size, seqlen_k_new, num_heads_k, head_size) without cu_seqlens_k_new");
-        CHECK_SHAPE(k_new, "k_new", batch_size, k_new.size(1), num_heads_k, head_size);
-        CHECK_SHAPE(v_new, "v_new", batch_size, k_new.size(1), num_heads_k, head_size);
-    }
-    int64_t seqlen_cache = k_cache.size(1);
-    if (paged) {
-        TORCH_CHECK(!cache_batch_idx.has_value(), "Paged KVcache does not support cache_batch_idx");
-        const auto pr = check_block_table(*page_table, k_cache, batch_size, 1);
-        seqlen_cache = pr.first * pr.second;
-    } else if (cache_batch_idx.has_value()) {
-        CHECK_DEVICE(*cache_batch_idx, "cache_batch_idx");
-        TORCH_CHECK(cache_batch_idx->is_contiguous() && cache_batch_idx->numel() == batch_size, "cache_batch_idx must be contiguous, (batch_size,)");
-        TORCH_CHECK(cache_batch_idx->scalar_type() == at::kInt, "cache_batch_idx must have dtype int32");
-    } else {
-        TORCH_CHECK(k_cache.size(0) >= batch_size, "the KV cache must have at least batch_size entries");
-    }
-    for (const auto &[t, name] : {std::make_pair(&k_descale, "k_descale"), std::make_pair(&v_descale, "v_descale")})
-        TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kFloat && t->sizes() == c10::IntArrayRef({batch_size, num_heads_k}),
-                    name, " must be fp32 (batch_size, num_heads_k)");
-    for (const Tensor *t : {&k_cache, &v_cache}) {
-        bool ok = reinterpret_cast<uintptr_t>(t->data_ptr()) % 8 == 0;
-        for (int64_t i = 0; i < 3; ++i) ok = ok && t->stride(i) % 8 == 0;
-        TORCH_CHECK(ok, "the fp8 KV cache must be 8-byte aligned with row/head/batch strides that are multiples of 8 to be appended to");
-    }
+    CacheRules rules;
+    rules.base_grain = 8;
+    rules.misaligned = "the fp8 KV cache must be 8-byte aligned with row/head/batch strides that are multiples of 8 to be appended to";
+    rules.v_shape = "v must have the shape of k";
+    rules.fill_name = "cache_seqlens";
+    rules.fill_dtype = rules.fill_device = rules.fill_contiguous = rules.fill_shape =
+        " must be a contiguous int32 CUDA tensor of shape (batch_size,)";
+    rules.idx_contiguous = rules.idx_length = " must be contiguous, (batch_size,)";
+    // (the batch is the number of fill levels, one at the least)
+    const int64_t batch_size = std::max<int64_t>(cache_seqlens.numel(), 1);
+    const CacheSide cache = check_cache(k_cache, v_cache, page_table, cache_batch_idx, cache_seqlens, c10::nullopt, batch_size, head_size,
+                                        head_size, rules);
+    const bool ragged = cu_seqlens_k_new.has_value();
+    check_new_rows(k_new, v_new, cu_seqlens_k_new, batch_size, num_heads_k, head_size, head_size, "k_new.size", "head_size");
+    if (ragged) TORCH_CHECK(max_seqlen_k_new >= 0, "max_seqlen_k_new must be non-negative");
+    check_kv8_descale(k_descale, "k_descale", batch_size, num_heads_k);
+    check_kv8_descale(v_descale, "v_descale", batch_size, num_heads_k);
     TORCH_CHECK(rotary_cos.has_value() == rotary_sin.has_value(), "rotary_cos and rotary_sin must be passed together");
-    if (rotary_cos.has_value()) {  // (the texts of the 16-bit routes)
-        CHECK_DEVICE(*rotary_cos, "rotary_cos"); CHECK_DEVICE(*rotary_sin, "rotary_sin");
-        TORCH_CHECK(rotary_cos->dim() == 2 && rotary_sin->sizes() == rotary_cos->sizes(), "rotary_cos / rotary_sin must have shape (seqlen_ro, rotary_dim / 2)");
-        const int64_t rotary_dim = rotary_cos->size(1) * 2;
-        TORCH_CHECK(rotary_dim <= head_size, "rotary_dim must be <= headdim");
-        TORCH_CHECK(rotary_dim % 16 == 0, "Only rotary dimensions divisible by 16 are currently supported");
-        TORCH_CHECK(rotary_cos->size(0) >= seqlen_cache, "cos/sin seqlen must be at least the seqlen of KV cache");
-        TORCH_CHECK(rotary_cos->is_contiguous() && rotary_sin->is_contiguous(), "rotary_cos / rotary_sin must be contiguous");
-        TORCH_CHECK(rotary_cos->scalar_type() == new_dtype && rotary_sin->scalar_type() == new_dtype,
-                    "rotary_cos / rotary_sin must have the same dtype as k_new");
-    }
-    if (rotary_seqlens.has_value()) {
-        TORCH_CHECK(rotary_seqlens->is_cuda() && rotary_seqlens->is_contiguous(), "seqlens_rotary must be a contiguous CUDA tensor");
-        TORCH_CHECK(rotary_seqlens->scalar_type() == at::kInt, "seqlens_rotary must have dtype torch.int32");
-        TORCH_CHECK(rotary_seqlens->sizes() == c10::IntArrayRef({batch_size}), "seqlens_rotary must have shape (batch_size,)");
-    }
+    if (rotary_cos.has_value()) check_rotary_tables(*rotary_cos, *rotary_sin, head_size, cache.seqlen_k, new_dtype, "k_new");
+    if (rotary_seqlens.has_value()) check_seqlens_rotary(*rotary_seqlens, batch_size);
     c10::hip::HIPGuardMasqueradingAsCUDA device_guard(k_cache.device());
     const Tensor kn = aligned_or_copy(k_new), vn = aligned_or_copy(v_new);
     Tensor seqused_out = at::empty({batch_size}, cache_seqlens.options());
     fa_kvcache_append_kv8_params p{};
-    p.abi_version = FA_ABI_VERSION;
-    p.struct_size = sizeof(fa_kvcache_append_kv8_params);
-    p.k_new = kn.data_ptr(); p.v_new = vn.data_ptr(); p.k_cache = k_cache.data_ptr(); p.v_cache = v_cache.data_ptr();
+    fill_append_common(p, k_cache, v_cache, cache_seqlens, cache_batch_idx, page_table, rotary_cos, rotary_sin, rotary_interleaved,
+                       rotary_seqlens);  // (cache strides: elements = bytes)
+    p.k_new = kn.data_ptr(); p.v_new = vn.data_ptr();
     if (ragged) {
         p.knew_row_stride = kn.stride(0); p.knew_head_stride = kn.stride(1);
         p.vnew_row_stride = vn.stride(0); p.vnew_head_stride = vn.stride(1);
@@ -1346,24 +1329,9 @@ Tensor kvcache_append_kv8(const Tensor &k_cache, const Tensor &v_cache, const Te
         p.vnew_batch_stride = vn.stride(0); p.vnew_row_stride = vn.stride(1); p.vnew_head_stride = vn.stride(2);
         p.seqlen_new = (int32_t)kn.size(1);
     }
-    p.kcache_batch_stride = k_cache.stride(0); p.kcache_row_stride = k_cache.stride(1); p.kcache_head_stride = k_cache.stride(2);  // (bytes)
-    p.vcache_batch_stride = v_cache.stride(0); p.vcache_row_stride = v_cache.stride(1); p.vcache_head_stride = v_cache.stride(2);
-    p.b = (int32_t)batch_size; p.seqlen_cache = (int32_t)seqlen_cache; p.h_k = (int32_t)num_heads_k; p.d = (int32_t)head_size;
+    p.b = (int32_t)batch_size; p.h_k = (int32_t)num_heads_k; p.d = (int32_t)head_size;
     p.dtype = dtype_code(kn);
-    if (paged) {
-        p.block_table = static_cast<const int32_t *>(page_table->data_ptr());
-        p.block_table_batch_stride = page_table->stride(0);
-        p.page_block_size = (int32_t)k_cache.size(1);
-    }
-    p.cache_seqlens = static_cast<const int32_t *>(cache_seqlens.data_ptr());
-    p.cache_batch_idx = static_cast<const int32_t *>(ptr(cache_batch_idx));
     p.seqused_out = static_cast<int32_t *>(seqused_out.data_ptr());
-    if (rotary_cos.has_value()) {
-        p.rotary_cos = rotary_cos->data_ptr(); p.rotary_sin = rotary_sin->data_ptr();
-        p.rotary_dim = (int32_t)rotary_cos->size(1) * 2;
-        p.rotary_interleaved = rotary_interleaved ? 1 : 0;
-        p.rotary_seqlens = static_cast<const int32_t *>(ptr(rotary_seqlens));
-    }
     p.k_descale = static_cast<const float *>(k_descale.data_ptr());
     p.k_descale_batch_stride = k_descale.stride(0); p.k_descale_head_stride = k_descale.stride(1);
     p.v_descale = static_cast<const float *>(v_descale.data_ptr());
@@ -1385,22 +1353,98 @@ Tensor kvcache_append_fp8(const Tensor &k_cache, const Tensor &v_cache, const Te
                               rotary_interleaved);
 }
 
+// One serving step of 16-bit queries over an fp8 KV cache, the counterpart of fwd_kvcache_core / fwd_kvcache_ragged: refusals by
+// argument, the quantising append, the rotary pass of q, the read (fwd_kv8) on the new fill levels.
+// With both descales the step may write: new rows (16-bit, dense or ragged with cu_seqlens_k_new beside cu_seqlens_q) are
+// quantised into the cache in place (kvcache_append_kv8) and q is rotated by the 16-bit pass.  Without them the scale of the
+// new rows would be an implied 1, which is almost never meant: those calls keep their refusals.
+std::tuple<Tensor, Tensor> fwd_kv8_step(const Tensor &q, const Tensor &k, const Tensor &v, const OptTensor &k_new, const OptTensor &v_new,
+                                        const OptTensor &qv, const OptTensor &out_, const OptTensor &cu_seqlens_q,
+                                        const OptTensor &cu_seqlens_k, const OptTensor &cu_seqlens_k_new, const OptTensor &seqused_q,
+                                        const OptTensor &seqused_k, c10::optional<int64_t> max_seqlen_q_, const OptTensor &page_table,
+                                        const OptTensor &kv_batch_idx, const OptTensor &leftpad_k, const OptTensor &rotary_cos,
+                                        const OptTensor &rotary_sin, OptTensor seqlens_rotary, const OptTensor &k_descale,
+                                        const OptTensor &v_descale, double softmax_scale, bool is_causal, int64_t window_size_left,
+                                        int64_t window_size_right, int64_t attention_chunk, double softcap, bool is_rotary_interleaved,
+                                        int64_t num_splits, const OptTensor &sink) {
+    const auto q_dtype = q.scalar_type();
+    if (!(k_descale.has_value() && v_descale.has_value())) {
+        TORCH_CHECK(!k_new.has_value() && !v_new.has_value() && !cu_seqlens_k_new.has_value(),
+                    "This flash attention build does not support k_new / v_new with an fp8 KV cache: appending to it (quantising "
+                    "the new rows) is the caller's job.");
+        TORCH_CHECK(!rotary_cos.has_value() && !rotary_sin.has_value(),
+                    "This flash attention build does not support rotary_cos / rotary_sin with an fp8 KV cache.");
+    }
+    TORCH_CHECK(!qv.has_value(), "This flash attention build does not support qv with an fp8 KV cache.");
+    TORCH_CHECK(v.size(-1) == q.size(-1),
+                "This flash attention build does not support a V headdim of its own with an fp8 KV cache.");
+    TORCH_CHECK(attention_chunk == 0, "This flash attention build does not support attention_chunk with an fp8 KV cache.");
+    TORCH_CHECK(q.size(-1) <= 128 && q.size(-1) % 16 == 0,
+                "This flash attention build supports an fp8 KV cache for head_size <= 128 that is a multiple of 16, got ", q.size(-1));
+    TORCH_CHECK(!cu_seqlens_k.has_value(), "This flash attention build does not support cu_seqlens_k with an fp8 KV cache.");
+    TORCH_CHECK(!sink.has_value(), "This flash attention build does not support a learnable sink with an fp8 KV cache.");
+    const bool appends = k_new || v_new || cu_seqlens_k_new || rotary_cos || rotary_sin;
+    if (appends) {
+        TORCH_CHECK(k_new.has_value() && v_new.has_value(),
+                    rotary_cos || rotary_sin
+                        ? "If rotary cos/sin are provided, new key / value to be appended to KV cache must also be provided"
+                        : "k_new and v_new must be passed together");
+        TORCH_CHECK(rotary_cos.has_value() == rotary_sin.has_value(), "rotary_cos and rotary_sin must be passed together");
+        TORCH_CHECK(!cu_seqlens_k_new.has_value() || cu_seqlens_q.has_value(),
+                    "This flash attention build does not support cu_seqlens_k_new without cu_seqlens_q.");
+        TORCH_CHECK(k_new->scalar_type() == at::kFloat8_e4m3fn || (k_new->scalar_type() == q_dtype && v_new->scalar_type() == q_dtype),
+                    "k_new and v_new must have the same dtype as query");
+        TORCH_CHECK(seqused_k.has_value(), "seqused_k must be provided with k_new / leftpad_k");
+    }
+    // q and cu_seqlens_q, once for the append, the rotary pass and the read
+    const bool ragged = cu_seqlens_q.has_value();
+    CHECK_DEVICE(q, "q"); CHECK_LAST_CONTIGUOUS(q, "Input tensor must have contiguous last dimension");
+    TORCH_CHECK(q.dim() == (ragged ? 3 : 4), ragged ? "q must have shape (total_q, num_heads, head_size) with cu_seqlens_q"
+                                                    : "q must have shape (batch_size, seqlen_q, num_heads, head_size)");
+    if (ragged) {
+        TORCH_CHECK(cu_seqlens_q->scalar_type() == at::kInt && cu_seqlens_q->is_contiguous() && cu_seqlens_q->is_cuda(),
+                    "cu_seqlens_q must be a contiguous int32 CUDA tensor");
+        TORCH_CHECK(max_seqlen_q_.has_value() && *max_seqlen_q_ > 0, "max_seqlen_q must be provided with cu_seqlens_q");
+    }
+    OptTensor fill = seqused_k;
+    Tensor qc = q;
+    if (appends) {
+        const int64_t batch_size = ragged ? cu_seqlens_q->numel() - 1 : q.size(0);
+        TORCH_CHECK(seqused_k->dim() == 1 && seqused_k->numel() == batch_size, "seqused_k must be int32 of shape (batch_size,)");
+        TORCH_CHECK(k.dim() == 4 && k.size(3) == q.size(-1) && k.size(2) > 0 && q.size(-2) % k.size(2) == 0,
+                    "Number of heads in key/value must divide number of heads in query");
+        check_leftpad(leftpad_k, batch_size, page_table.has_value());
+        if (!rotary_cos.has_value()) seqlens_rotary = c10::nullopt;  // (only read with rotary)
+        // the append first: what the read sees are the new fill levels -- dense rows: seqused_k + seqlen_new, like the 16-bit
+        // route; ragged rows: what the launch wrote
+        const Tensor written = kvcache_append_kv8(k, v, *k_new, *v_new, *seqused_k, *k_descale, *v_descale, cu_seqlens_k_new, 0,
+                                                  kv_batch_idx, page_table, rotary_cos, rotary_sin, seqlens_rotary,
+                                                  is_rotary_interleaved);
+        fill = cu_seqlens_k_new.has_value() ? written : *seqused_k + k_new->size(-3);
+        if (rotary_cos.has_value() && q.numel() > 0) {
+            const Tensor qa = aligned_or_copy(q);
+            c10::hip::HIPGuardMasqueradingAsCUDA device_guard(q.device());
+            qc = rotate_q(qa, cu_seqlens_q, max_seqlen_q_.value_or(0), *rotary_cos, *rotary_sin, seqlens_rotary, *seqused_k,
+                          is_rotary_interleaved, is_causal, window_size_left, window_size_right);
+        }
+    }
+    return fwd_kv8(qc, k, v, out_, cu_seqlens_q, seqused_q, fill, max_seqlen_q_, page_table, kv_batch_idx, leftpad_k, k_descale,
+                   v_descale, softmax_scale, is_causal, window_size_left, window_size_right, softcap, num_splits);
+}
+
 // flash_attn_3::fwd, hopper/flash_api.cpp:672-1198 (schema :1672-1707): the 34 positional arguments of
 // hopper/flash_attn_interface.py:66, returns (out, softmax_lse, None, None).
 // Built: fp16 / bf16 / fp8 e4m3 inputs (fp8 -> bf16 output, :859), per-(batch, kv head) q/k/v descales (:1115-1146), dense
 // and varlen (`cu_seqlens_*`, `seqused_*`), causal / sliding window / softcap / attention_chunk, GQA, a V head dim of its
 // own.  KV-cache arguments (dense q, 16-bit: k_new / v_new appended in place at seqused_k, page_table of any page size,
-// kv_batch_idx, leftpad_k, rotary) and plain decode over a cache go to fwd_kvcache_impl; the same arguments with ragged
+// kv_batch_idx, leftpad_k, rotary) and plain decode over a cache go to fwd_kvcache_core; the same arguments with ragged
 // queries (cu_seqlens_q + max_seqlen_q, k_new dense or ragged with cu_seqlens_k_new, seqused_q) to fwd_kvcache_ragged.  qv
 // (MLA absorbed attention, :1028-1048: scores = (q.k + qv.v) * scale, d <= 64 beside d_v in [256, 512], 16-bit) on every
 // route.  Accepted and rejected by message, like the reference does for compiled-out features (:1148-1165):
 // cu_seqlens_k_new without cu_seqlens_q, qv of any other shape or with fp8, KV-cache arguments together with cu_seqlens_k,
 // attention_chunk or fp8.  `scheduler_metadata` and `sm_margin` are performance hints and do not change results: ignored.
-// 16-bit q beside a Float8_e4m3fn k / v (an fp8 KV cache with k_descale / v_descale, out in q's dtype): fwd_kv8 above.  With
-// both descales the same KV-cache arguments as on the 16-bit routes are served there -- k_new / v_new (16-bit, dense or ragged
-// with cu_seqlens_k_new beside cu_seqlens_q) quantised into the cache in place by kvcache_append_kv8, rotary_cos / rotary_sin,
-// seqlens_rotary, is_rotary_interleaved -- in front of the read on the new fill levels; without both they stay refused, as do
-// fp8 new rows, qv, a V head dim of its own, attention_chunk, cu_seqlens_k and a sink.
+// 16-bit q beside a Float8_e4m3fn k / v (an fp8 KV cache with k_descale / v_descale, out in q's dtype): recognised here and
+// served by fwd_kv8_step above, the fp8 counterpart of the two 16-bit cache steps (its refusals, append, rotary pass and read).
 // `pack_gqa` is a hint too: True asks every route below for the pk kernel (FA_FLAG_PACK_GQA: honoured for GQA / MQA calls of
 // 16-bit types at head dims <= 128 without attention_chunk, a V head dim of its own or qv; a no-op elsewhere and behind the
 // single-token GQA swap); False and None keep the unpacked routes (no automatic rule yet).
@@ -1421,76 +1465,11 @@ std::tuple<Tensor, Tensor, OptTensor, OptTensor> fa3_fwd_core(
     TORCH_CHECK(q_dtype == at::kHalf || q_dtype == at::kBFloat16 || is_fp8,
                 "FlashAttention only supports fp16, bf16, and fp8_e4m3 data type");  // hopper/flash_api.cpp:714-722
     if (!is_fp8 && k.scalar_type() == at::kFloat8_e4m3fn && v.scalar_type() == at::kFloat8_e4m3fn) {
-        // 16-bit queries over an fp8 KV cache: the kv8 route (fwd_kv8).  What it does not serve is refused by argument.
-        // With both descales the step may write as well: new rows are quantised into the cache (kvcache_append_kv8), q is rotated
-        // by the 16-bit pass, and the read runs on the new fill levels.  Without them the scale of the new rows would be an
-        // implied 1, which is almost never meant: those calls keep their refusals.
-        const bool can_append = k_descale.has_value() && v_descale.has_value();
-        if (!can_append) {
-            TORCH_CHECK(!k_new.has_value() && !v_new.has_value() && !cu_seqlens_k_new.has_value(),
-                        "This flash attention build does not support k_new / v_new with an fp8 KV cache: appending to it (quantising "
-                        "the new rows) is the caller's job.");
-            TORCH_CHECK(!rotary_cos.has_value() && !rotary_sin.has_value(),
-                        "This flash attention build does not support rotary_cos / rotary_sin with an fp8 KV cache.");
-        }
-        TORCH_CHECK(!qv.has_value(), "This flash attention build does not support qv with an fp8 KV cache.");
-        TORCH_CHECK(v.size(-1) == q.size(-1),
-                    "This flash attention build does not support a V headdim of its own with an fp8 KV cache.");
-        TORCH_CHECK(attention_chunk_.value_or(0) == 0, "This flash attention build does not support attention_chunk with an fp8 KV cache.");
-        TORCH_CHECK(q.size(-1) <= 128 && q.size(-1) % 16 == 0,
-                    "This flash attention build supports an fp8 KV cache for head_size <= 128 that is a multiple of 16, got ", q.size(-1));
-        TORCH_CHECK(!cu_seqlens_k.has_value(), "This flash attention build does not support cu_seqlens_k with an fp8 KV cache.");
-        TORCH_CHECK(!sink.has_value(), "This flash attention build does not support a learnable sink with an fp8 KV cache.");
-        OptTensor fill = seqused_k;
-        Tensor qc = q;
-        if (k_new || v_new || cu_seqlens_k_new || rotary_cos || rotary_sin) {
-            TORCH_CHECK(k_new.has_value() && v_new.has_value(),
-                        rotary_cos || rotary_sin
-                            ? "If rotary cos/sin are provided, new key / value to be appended to KV cache must also be provided"
-                            : "k_new and v_new must be passed together");
-            TORCH_CHECK(rotary_cos.has_value() == rotary_sin.has_value(), "rotary_cos and rotary_sin must be passed together");
-            TORCH_CHECK(!cu_seqlens_k_new.has_value() || cu_seqlens_q.has_value(),
-                        "This flash attention build does not support cu_seqlens_k_new without cu_seqlens_q.");
-            TORCH_CHECK(k_new->scalar_type() == at::kFloat8_e4m3fn || (k_new->scalar_type() == q_dtype && v_new->scalar_type() == q_dtype),
-                        "k_new and v_new must have the same dtype as query");
-            TORCH_CHECK(seqused_k.has_value(), "seqused_k must be provided with k_new / leftpad_k");
-            const bool ragged = cu_seqlens_q.has_value();
-            CHECK_DEVICE(q, "q"); CHECK_LAST_CONTIGUOUS(q, "Input tensor must have contiguous last dimension");
-            TORCH_CHECK(q.dim() == (ragged ? 3 : 4), ragged ? "q must have shape (total_q, num_heads, head_size) with cu_seqlens_q"
-                                                            : "q must have shape (batch_size, seqlen_q, num_heads, head_size)");
-            if (ragged) {
-                TORCH_CHECK(cu_seqlens_q->scalar_type() == at::kInt && cu_seqlens_q->is_contiguous() && cu_seqlens_q->is_cuda(),
-                            "cu_seqlens_q must be a contiguous int32 CUDA tensor");
-                TORCH_CHECK(max_seqlen_q_.has_value() && *max_seqlen_q_ > 0, "max_seqlen_q must be provided with cu_seqlens_q");
-            }
-            const int64_t batch_size = ragged ? cu_seqlens_q->numel() - 1 : q.size(0);
-            TORCH_CHECK(seqused_k->dim() == 1 && seqused_k->numel() == batch_size, "seqused_k must be int32 of shape (batch_size,)");
-            TORCH_CHECK(k.dim() == 4 && k.size(3) == q.size(-1) && k.size(2) > 0 && q.size(-2) % k.size(2) == 0,
-                        "Number of heads in key/value must divide number of heads in query");
-            check_leftpad(leftpad_k, batch_size, page_table.has_value());
-            if (seqlens_rotary.has_value() && !rotary_cos.has_value()) seqlens_rotary = c10::nullopt;  // (only read with rotary)
-            // the append first: what the read sees are the new fill levels -- dense rows: seqused_k + seqlen_new, like the 16-bit
-            // route; ragged rows: what the launch wrote
-            const Tensor written = kvcache_append_kv8(k, v, *k_new, *v_new, *seqused_k, *k_descale, *v_descale, cu_seqlens_k_new, 0,
-                                                      kv_batch_idx, page_table, rotary_cos, rotary_sin, seqlens_rotary,
-                                                      is_rotary_interleaved);
-            fill = cu_seqlens_k_new.has_value() ? written : *seqused_k + k_new->size(-3);
-            if (rotary_cos.has_value() && q.numel() > 0) {
-                // the 16-bit routes' rule: causal / local -> row i at the old fill level (or seqlens_rotary) + i, otherwise every
-                // row at that level
-                const bool per_row = is_causal || window_size_left >= 0 || window_size_right >= 0;
-                const Tensor qa = aligned_or_copy(q);
-                Tensor q_ro = at::empty_like(qa, at::MemoryFormat::Contiguous);
-                const Tensor &offsets = seqlens_rotary.has_value() ? *seqlens_rotary : *seqused_k;
-                c10::hip::HIPGuardMasqueradingAsCUDA device_guard(q.device());
-                if (ragged) rotary_apply_varlen(qa, q_ro, *cu_seqlens_q, *max_seqlen_q_, *rotary_cos, *rotary_sin, offsets, is_rotary_interleaved, per_row);
-                else rotary_apply(qa, q_ro, *rotary_cos, *rotary_sin, offsets, is_rotary_interleaved, per_row);
-                qc = q_ro;
-            }
-        }
-        auto r = fwd_kv8(qc, k, v, out_, cu_seqlens_q, seqused_q, fill, max_seqlen_q_, page_table, kv_batch_idx, leftpad_k,
-                         k_descale, v_descale, softmax_scale_.value_or(std::pow(double(q.size(-1)), -0.5)), is_causal,
-                         window_size_left, window_size_right, softcap, num_splits);
+        // 16-bit queries over an fp8 KV cache: the kv8 step (what it does not serve is refused by argument there)
+        auto r = fwd_kv8_step(q, k, v, k_new, v_new, qv, out_, cu_seqlens_q, cu_seqlens_k, cu_seqlens_k_new, seqused_q, seqused_k,
+                              max_seqlen_q_, page_table, kv_batch_idx, leftpad_k, rotary_cos, rotary_sin, seqlens_rotary, k_descale,
+                              v_descale, softmax_scale_.value_or(std::pow(double(q.size(-1)), -0.5)), is_causal, window_size_left,
+                              window_size_right, attention_chunk_.value_or(0), softcap, is_rotary_interleaved, num_splits, sink);
         return {std::get<0>(r), std::get<1>(r), c10::nullopt, c10::nullopt};
     }
     TORCH_CHECK(k.scalar_type() == q_dtype, "query and key must have the same dtype");
@@ -1524,10 +1503,7 @@ std::tuple<Tensor, Tensor, OptTensor, OptTensor> fa3_fwd_core(
         TORCH_CHECK(head_size_v % 8 == 0, "head_size_v should be a multiple of 8");  // :856
     }
     if (seqlens_rotary.has_value()) {  // :1074-1079; only read together with k_new + rotary (hopper/seqlen.h:89)
-        TORCH_CHECK(seqlens_rotary->is_cuda() && seqlens_rotary->is_contiguous(), "seqlens_rotary must be a contiguous CUDA tensor");
-        TORCH_CHECK(seqlens_rotary->scalar_type() == at::kInt, "seqlens_rotary must have dtype torch.int32");
-        TORCH_CHECK(seqlens_rotary->sizes() == c10::IntArrayRef({cu_seqlens_q.has_value() ? cu_seqlens_q->numel() - 1 : q.size(0)}),
-                    "seqlens_rotary must have shape (batch_size,)");
+        check_seqlens_rotary(*seqlens_rotary, cu_seqlens_q.has_value() ? cu_seqlens_q->numel() - 1 : q.size(0));
         if (!k_new.has_value() || !rotary_cos.has_value()) seqlens_rotary = c10::nullopt;
     }
     const double default_scale = std::pow(double(head_size + (qv.has_value() ? head_size_v : 0)), -0.5);
@@ -1552,9 +1528,13 @@ std::tuple<Tensor, Tensor, OptTensor, OptTensor> fa3_fwd_core(
                                         window_size_right, softcap, is_rotary_interleaved, num_splits, sink, pack_gqa);
             return {std::get<0>(r), std::get<1>(r), c10::nullopt, c10::nullopt};
         }
-        auto r = fwd_kvcache_core(q, k, v, k_new, v_new, seqused_k, rotary_cos, rotary_sin, kv_batch_idx, leftpad_k, page_table,
-                                  c10::nullopt, out_, softmax_scale_.value_or(default_scale), is_causal, window_size_left,
-                                  window_size_right, softcap, is_rotary_interleaved, num_splits, 1, seqlens_rotary, qv, sink, pack_gqa);
+        KvcacheArgs a;
+        a.k_new = k_new; a.v_new = v_new; a.seqlens_k = seqused_k; a.rotary_cos = rotary_cos; a.rotary_sin = rotary_sin;
+        a.cache_batch_idx = kv_batch_idx; a.leftpad_k = leftpad_k; a.block_table = page_table; a.out = out_;
+        a.softmax_scale = softmax_scale_.value_or(default_scale); a.is_causal = is_causal; a.window_size_left = window_size_left;
+        a.window_size_right = window_size_right; a.softcap = softcap; a.is_rotary_interleaved = is_rotary_interleaved;
+        a.num_splits = num_splits; a.seqlens_rotary = seqlens_rotary; a.qv = qv; a.sink = sink; a.pack_gqa = pack_gqa;
+        auto r = fwd_kvcache_core(q, k, v, a);
         return {r[0], r[1], c10::nullopt, c10::nullopt};
     }
     if (!cu_seqlens_q && !cu_seqlens_k && !seqused_q && seqused_k && !is_fp8 && q.dim() == 4 && q.size(1) <= 128 &&
@@ -1563,9 +1543,10 @@ std::tuple<Tensor, Tensor, OptTensor, OptTensor> fa3_fwd_core(
         // plain decode over a cache (flash_attn_with_kvcache(q, k_cache, v_cache, cache_seqlens=...)): the same routine as
         // the append / paged calls, which brings the split-KV heuristic (num_splits = 0) and the (b, 1, h) -> (b, ngroups, h_k)
         // GQA swap (:935-1060 runs them for every call with seqused_k)
-        auto r = fwd_kvcache_core(q, k, v, c10::nullopt, c10::nullopt, seqused_k, c10::nullopt, c10::nullopt, c10::nullopt,
-                                  c10::nullopt, c10::nullopt, c10::nullopt, c10::nullopt, softmax_scale_.value_or(default_scale),
-                                  is_causal, -1, -1, softcap, false, num_splits, 1, c10::nullopt, qv, sink, pack_gqa);
+        KvcacheArgs a;
+        a.seqlens_k = seqused_k; a.softmax_scale = softmax_scale_.value_or(default_scale); a.is_causal = is_causal; a.softcap = softcap;
+        a.num_splits = num_splits; a.qv = qv; a.sink = sink; a.pack_gqa = pack_gqa;
+        auto r = fwd_kvcache_core(q, k, v, a);
         return {r[0], r[1], c10::nullopt, c10::nullopt};
     }
     const bool varlen = cu_seqlens_q.has_value();
@@ -1636,7 +1617,7 @@ std::tuple<Tensor, Tensor, OptTensor, OptTensor> fa3_fwd_core(
         a.seqused_k = seqused_k; a.q_descale = q_descale; a.k_descale = k_descale; a.v_descale = v_descale;
         a.fa3_window = true; a.attention_chunk = attention_chunk;
         if (qv.has_value()) a.qv = aligned_or_copy(*qv);
-        a.num_splits = cute ? (int)num_splits : 1;  // no split-KV: the decode calls of the FA3 surface take the fwd_kvcache_impl routes above
+        a.num_splits = cute ? (int)num_splits : 1;  // no split-KV: the decode calls of the FA3 surface take the fwd_kvcache_core routes above
         a.sink = sink; a.pack_gqa = pack_gqa;
         launch_fwd(qc, kc, vc, oc, softmax_lse, a);
         if (!oc.is_same(out)) out.copy_(oc);
@@ -2047,7 +2028,20 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("bwd", &mha_bwd<false>, "Backward pass");
     m.def("varlen_bwd", &mha_varlen_bwd<false>, "Backward pass (variable length)");
     m.def("fwd_kvcache", &mha_fwd_kvcache, "Forward pass, with KV-cache");
-    m.def("_fwd_kvcache_impl", &fwd_kvcache_impl, "fwd_kvcache with the page-size rule of the calling surface (+ FA3 seqlens_rotary)",
+    m.def("_fwd_kvcache_impl",  // fwd_kvcache_core under the positional list the Python surfaces call it by
+          [](Tensor q, const Tensor &kcache, const Tensor &vcache, OptTensor k, OptTensor v, OptTensor seqlens_k, OptTensor rotary_cos,
+             OptTensor rotary_sin, OptTensor cache_batch_idx, OptTensor leftpad_k, OptTensor block_table, OptTensor alibi_slopes,
+             OptTensor out, double softmax_scale, bool is_causal, int64_t window_size_left, int64_t window_size_right, double softcap,
+             bool is_rotary_interleaved, int64_t num_splits, int64_t page_multiple, OptTensor seqlens_rotary, OptTensor qv) {
+              KvcacheArgs a;
+              a.k_new = k; a.v_new = v; a.seqlens_k = seqlens_k; a.rotary_cos = rotary_cos; a.rotary_sin = rotary_sin;
+              a.cache_batch_idx = cache_batch_idx; a.leftpad_k = leftpad_k; a.block_table = block_table; a.alibi_slopes = alibi_slopes;
+              a.out = out; a.softmax_scale = softmax_scale; a.is_causal = is_causal; a.window_size_left = window_size_left;
+              a.window_size_right = window_size_right; a.softcap = softcap; a.is_rotary_interleaved = is_rotary_interleaved;
+              a.num_splits = num_splits; a.page_multiple = page_multiple; a.seqlens_rotary = seqlens_rotary; a.qv = qv;
+              return fwd_kvcache_core(q, kcache, vcache, a);
+          },
+          "fwd_kvcache with the page-size rule of the calling surface (+ FA3 seqlens_rotary)",
           py::arg("q"), py::arg("kcache"), py::arg("vcache"), py::arg("k"), py::arg("v"), py::arg("seqlens_k"), py::arg("rotary_cos"),
           py::arg("rotary_sin"), py::arg("cache_batch_idx"), py::arg("leftpad_k"), py::arg("block_table"), py::arg("alibi_slopes"),
           py::arg("out"), py::arg("softmax_scale"), py::arg("is_causal"), py::arg("window_size_left"), py::arg("window_size_right"),
