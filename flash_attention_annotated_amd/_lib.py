@@ -56,6 +56,10 @@ EXPORTED_SYMBOLS = (
     "fa_fwd_kv8_validate",
     "fa_fwd_kv8_workspace_size",
     "fa_fwd_kv8_plan_name",
+    "fa_fwd_qv8",
+    "fa_fwd_qv8_validate",
+    "fa_fwd_qv8_workspace_size",
+    "fa_fwd_qv8_plan_name",
     "fa_kvcache_append_kv8",
     "fa_kvcache_append_kv8_validate",
     "fa_kvcache_append_kv8_params_size",
@@ -329,8 +333,8 @@ def is_stale():
 
 def build(force=False, verbose=False):
     """Compile csrc/ for gfx950 into the in-tree shared library (hipcc cross-compiles without a GPU)."""
-    srcs = [os.path.join(CSRC, f) for f in ("fa_fwd_api.hip", "fa_fwd_kv8_api.hip", "fa_kvcache_append_kv8.hip", "fa_bwd_api.hip",
-                                              "fa_bwd_bs_api.hip")]
+    srcs = [os.path.join(CSRC, f) for f in ("fa_fwd_api.hip", "fa_fwd_kv8_api.hip", "fa_fwd_qv8_api.hip", "fa_kvcache_append_kv8.hip",
+                                              "fa_bwd_api.hip", "fa_bwd_bs_api.hip")]
     if not force and not is_stale():
         return LIB_PATH
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -466,6 +470,14 @@ def load():
     lib.fa_fwd_kv8_workspace_size.restype = ctypes.c_int64
     lib.fa_fwd_kv8_plan_name.argtypes = [ctypes.POINTER(FaFwdParams), ctypes.c_int32]
     lib.fa_fwd_kv8_plan_name.restype = ctypes.c_char_p
+    lib.fa_fwd_qv8.argtypes = [ctypes.POINTER(FaFwdParams), ctypes.c_void_p]
+    lib.fa_fwd_qv8.restype = ctypes.c_int
+    lib.fa_fwd_qv8_validate.argtypes = [ctypes.POINTER(FaFwdParams)]
+    lib.fa_fwd_qv8_validate.restype = ctypes.c_int
+    lib.fa_fwd_qv8_workspace_size.argtypes = [ctypes.POINTER(FaFwdParams)]
+    lib.fa_fwd_qv8_workspace_size.restype = ctypes.c_int64
+    lib.fa_fwd_qv8_plan_name.argtypes = [ctypes.POINTER(FaFwdParams), ctypes.c_int32]
+    lib.fa_fwd_qv8_plan_name.restype = ctypes.c_char_p
     lib.fa_kvcache_append_kv8.argtypes = [ctypes.POINTER(FaKvcacheAppendKv8Params), ctypes.c_void_p]
     lib.fa_kvcache_append_kv8.restype = ctypes.c_int
     lib.fa_kvcache_append_kv8_validate.argtypes = [ctypes.POINTER(FaKvcacheAppendKv8Params)]

@@ -880,9 +880,10 @@ int launch_plan(const FwdPlan &pl, const fa_fwd_params *p, const fa::KParams &kp
 
 }  // namespace
 
-// ---- fa_fwd_internal.h: what fa_fwd_kv8_api.hip shares with this file ---------------------------------------------------------
+// ---- fa_fwd_internal.h: what fa_fwd_kv8_api.hip and fa_fwd_qv8_api.hip share with this file ---------------------------------------------------------
 namespace fa {
 int fwd_pk_split_count(const fa_fwd_params *p) { return split_plan(p, 2, true).splits; }
+int fwd_qv_split_count(const fa_fwd_params *p) { return split_plan_qv(p).splits; }
 void fwd_set_last_plan_text(const char *text) {
     snprintf(t_last_ext_text, sizeof(t_last_ext_text), "%s", text ? text : "");
     if (t_last_ext_text[0]) {

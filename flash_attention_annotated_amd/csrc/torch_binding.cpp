@@ -1150,18 +1150,23 @@ void check_kv8_descale(const Tensor &t, const char *name, int64_t batch_size, in
 // seqused_k.  One kernel for every h / h_k (it packs the GQA group into its rows itself: no swap, pack_gqa is moot).
 // The read half of fwd_kv8_step below, which has checked q and cu_seqlens_q, appended the step's new rows, rotated q and
 // refused what the route does not serve (qv, attention_chunk, head dims).
+// mla: the MLA decode shape (fa_fwd_qv8: head_size <= 64 beside v.size(-1) in [256, 512], qv optional, out (..., h, d_v)); every
+// other argument is handled alike, so fwd_qv8 below is this function with mla set.
 std::tuple<Tensor, Tensor> fwd_kv8(const Tensor &q, const Tensor &k, const Tensor &v, const OptTensor &out_,
                                    const OptTensor &cu_seqlens_q, const OptTensor &seqused_q, const OptTensor &seqused_k,
                                    c10::optional<int64_t> max_seqlen_q_, const OptTensor &page_table, const OptTensor &kv_batch_idx,
                                    const OptTensor &leftpad_k, const OptTensor &k_descale, const OptTensor &v_descale,
                                    double softmax_scale, bool is_causal, int64_t window_size_left, int64_t window_size_right,
-                                   double softcap, int64_t num_splits) {
+                                   double softcap, int64_t num_splits, const OptTensor &qv = c10::nullopt, bool mla = false) {
     CHECK_DEVICE(k, "k"); CHECK_LAST_CONTIGUOUS(k, "Input tensor must have contiguous last dimension");
     CHECK_DEVICE(v, "v"); CHECK_LAST_CONTIGUOUS(v, "Input tensor must have contiguous last dimension");
     const bool ragged = cu_seqlens_q.has_value();
     TORCH_CHECK(k.dim() == 4 && v.dim() == 4,
                 "an fp8 k / v must be a KV cache of shape (batch or num_pages, seqlen or page_size, num_heads_k, head_size)");
     const int64_t head_size = q.size(-1), num_heads = q.size(-2), num_heads_k = k.size(2);
+    const int64_t head_size_v = mla ? v.size(3) : head_size;
+    std::vector<int64_t> out_shape = q.sizes().vec();  // q's with V's head dim
+    out_shape.back() = head_size_v;
     int64_t batch_size, seqlen_q, total_q;
     if (ragged) {
         TORCH_CHECK(seqused_k.has_value(), "seqused_k (the cache fill levels) must be provided with cu_seqlens_q over a KV cache");
@@ -1177,12 +1182,18 @@ std::tuple<Tensor, Tensor> fwd_kv8(const Tensor &q, const Tensor &k, const Tenso
     rules.base_grain = rules.stride_grain = 16;
     rules.misaligned = "the fp8 KV cache must be 16-byte aligned with row/head/batch strides that are multiples of 16";
     rules.k_shape = "k must have shape (..., " + std::to_string(num_heads_k) + ", " + std::to_string(head_size) + ")";
-    rules.v_shape = "v must have the shape of k";
+    rules.v_shape = mla ? "v must have the shape of k with its own head_size_v" : "v must have the shape of k";
     rules.fill_dtype = rules.fill_device = rules.fill_contiguous = rules.fill_shape = " must be int32 of shape (batch_size,)";
     rules.fill_any_dims = true;
     rules.idx_contiguous = rules.idx_length = " must be contiguous, (batch_size,)";
     if (seqused_q.has_value()) check_fill_levels(*seqused_q, "seqused_q", batch_size, rules);
-    const CacheSide cache = check_cache(k, v, page_table, kv_batch_idx, seqused_k, leftpad_k, batch_size, head_size, head_size, rules);
+    const CacheSide cache = check_cache(k, v, page_table, kv_batch_idx, seqused_k, leftpad_k, batch_size, head_size, head_size_v, rules);
+    if (qv.has_value()) {
+        TORCH_CHECK(qv->scalar_type() == q.scalar_type(), "q_v must have the same dtype as query");
+        TORCH_CHECK(qv->is_cuda() && qv->device() == q.device(), "q_v must be on the same CUDA device as query");
+        CHECK_LAST_CONTIGUOUS(*qv, "q_v tensor must have contiguous last dimension");
+        TORCH_CHECK(qv->sizes() == c10::IntArrayRef(out_shape), "q_v must have shape ", tuple_str(out_shape));
+    }
     const int64_t seqlen_k = cache.seqlen_k;
     if (leftpad_k.has_value()) TORCH_CHECK(seqused_k.has_value(), "seqused_k must be provided with k_new / leftpad_k");
     for (const auto &[t, name] : {std::make_pair(&k_descale, "k_descale"), std::make_pair(&v_descale, "v_descale")})
@@ -1191,9 +1202,10 @@ std::tuple<Tensor, Tensor> fwd_kv8(const Tensor &q, const Tensor &k, const Tenso
     if (out_.has_value()) {
         out = *out_;
         TORCH_CHECK(out.scalar_type() == q.scalar_type(), "Output must have the same dtype as the query");
-        TORCH_CHECK(out.is_cuda() && out.stride(-1) == 1 && out.sizes() == q.sizes(), "out must have the shape of q");
+        TORCH_CHECK(out.is_cuda() && out.stride(-1) == 1 && out.sizes() == c10::IntArrayRef(out_shape),
+                    mla ? "out must have the shape of q with the head dim of v" : "out must have the shape of q");
     } else {
-        out = at::empty(q.sizes(), q.options());
+        out = at::empty(out_shape, q.options());
     }
     c10::hip::HIPGuardMasqueradingAsCUDA device_guard(q.device());
     Tensor softmax_lse = ragged ? at::empty({num_heads, total_q}, q.options().dtype(at::kFloat))
@@ -1206,11 +1218,19 @@ std::tuple<Tensor, Tensor> fwd_kv8(const Tensor &q, const Tensor &k, const Tenso
     }
     const Tensor qc = aligned_or_copy(q);
     Tensor oc = aligned(out) ? out : at::empty_like(out);
+    Tensor qvc;
     fa_fwd_params p{};
     p.abi_version = FA_ABI_VERSION;
     p.struct_size = sizeof(fa_fwd_params);
     p.q = qc.data_ptr(); p.k = k.data_ptr(); p.v = v.data_ptr(); p.o = oc.data_ptr();
     p.softmax_lse = static_cast<float *>(softmax_lse.data_ptr());
+    if (mla) p.d_v = (int32_t)head_size_v;
+    if (qv.has_value()) {
+        qvc = aligned_or_copy(*qv);
+        p.qv = qvc.data_ptr();
+        p.qv_batch_stride = ragged ? 0 : qvc.stride(0);
+        p.qv_row_stride = qvc.stride(-3); p.qv_head_stride = qvc.stride(-2);
+    }
     if (ragged) {
         p.q_row_stride = qc.stride(0); p.q_head_stride = qc.stride(1);
         p.o_row_stride = oc.stride(0); p.o_head_stride = oc.stride(1);
@@ -1250,18 +1270,32 @@ std::tuple<Tensor, Tensor> fwd_kv8(const Tensor &q, const Tensor &k, const Tenso
     }
     p.num_splits = (int32_t)std::max<int64_t>(num_splits, 0);
     Tensor workspace;
-    const int64_t need = fa_fwd_kv8_workspace_size(&p);
-    TORCH_CHECK(need >= 0, "fa_fwd_kv8_workspace_size failed (", need, "): ", fa_strerror((int)need));
+    const char *entry = mla ? "fa_fwd_qv8" : "fa_fwd_kv8";
+    const int64_t need = mla ? fa_fwd_qv8_workspace_size(&p) : fa_fwd_kv8_workspace_size(&p);
+    TORCH_CHECK(need >= 0, entry, "_workspace_size failed (", need, "): ", fa_strerror((int)need));
     if (need > 0) {  // split-KV partials: scratch from torch's caching allocator (the callee never allocates)
         workspace = at::empty({need + 256}, q.options().dtype(at::kByte));
         const uintptr_t base = (reinterpret_cast<uintptr_t>(workspace.data_ptr()) + 255) / 256 * 256;
         p.workspace = reinterpret_cast<void *>(base);
         p.workspace_bytes = (uint64_t)need;
     }
-    const int st = fa_fwd_kv8(&p, current_stream(q));
-    TORCH_CHECK(st == 0, "fa_fwd_kv8 failed (", st, "): ", fa_strerror(st));
+    const int st = mla ? fa_fwd_qv8(&p, current_stream(q)) : fa_fwd_kv8(&p, current_stream(q));
+    TORCH_CHECK(st == 0, entry, " failed (", st, "): ", fa_strerror(st));
     if (!oc.is_same(out)) out.copy_(oc);
     return {out, softmax_lse};
+}
+
+// The MLA decode shape over an fp8 KV cache (include/fa_fwd.h, fa_fwd_qv8): q (.., h, d <= 64) and the optional qv (.., h, d_v)
+// fp16 / bf16, k (.., h_k, d) and v (.., h_k, d_v in [256, 512]) Float8_e4m3fn, out (.., h, d_v) in q's dtype.  Descales,
+// num_splits and the workspace as fwd_kv8 handles them: it is that function.
+std::tuple<Tensor, Tensor> fwd_qv8(const Tensor &q, const Tensor &k, const Tensor &v, const OptTensor &qv, const OptTensor &out_,
+                                   const OptTensor &cu_seqlens_q, const OptTensor &seqused_q, const OptTensor &seqused_k,
+                                   c10::optional<int64_t> max_seqlen_q_, const OptTensor &page_table, const OptTensor &kv_batch_idx,
+                                   const OptTensor &leftpad_k, const OptTensor &k_descale, const OptTensor &v_descale,
+                                   double softmax_scale, bool is_causal, int64_t window_size_left, int64_t window_size_right,
+                                   double softcap, int64_t num_splits) {
+    return fwd_kv8(q, k, v, out_, cu_seqlens_q, seqused_q, seqused_k, max_seqlen_q_, page_table, kv_batch_idx, leftpad_k, k_descale,
+                   v_descale, softmax_scale, is_causal, window_size_left, window_size_right, softcap, num_splits, qv, true);
 }
 
 // The write half of an fp8 (e4m3) KV cache (include/fa_fwd.h, fa_kvcache_append_kv8): new 16-bit rows -- dense (b, s_new, h_k, d)
@@ -1368,6 +1402,16 @@ std::tuple<Tensor, Tensor> fwd_kv8_step(const Tensor &q, const Tensor &k, const 
                                         int64_t window_size_right, int64_t attention_chunk, double softcap, bool is_rotary_interleaved,
                                         int64_t num_splits, const OptTensor &sink) {
     const auto q_dtype = q.scalar_type();
+    // the MLA decode shape (fa_fwd_qv8): q/k head dim <= 64 beside a V / latent head dim in [256, 512], qv optional
+    const bool mla = q.size(-1) <= 64 && q.size(-1) % 16 == 0 && v.size(-1) >= 256 && v.size(-1) <= 512 && v.size(-1) % 16 == 0;
+    if (mla) {  // the quantising append serves d <= 128 with d_v = d: this shape only reads
+        TORCH_CHECK(!k_new.has_value() && !v_new.has_value() && !cu_seqlens_k_new.has_value(),
+                    "This flash attention build does not support k_new / v_new with an fp8 KV cache of the MLA shape (head_size <= 64 "
+                    "beside head_size_v in [256, 512]): it is read only.");
+        TORCH_CHECK(!rotary_cos.has_value() && !rotary_sin.has_value(),
+                    "This flash attention build does not support rotary_cos / rotary_sin with an fp8 KV cache of the MLA shape "
+                    "(head_size <= 64 beside head_size_v in [256, 512]): it is read only.");
+    }
     if (!(k_descale.has_value() && v_descale.has_value())) {
         TORCH_CHECK(!k_new.has_value() && !v_new.has_value() && !cu_seqlens_k_new.has_value(),
                     "This flash attention build does not support k_new / v_new with an fp8 KV cache: appending to it (quantising "
@@ -1375,8 +1419,8 @@ std::tuple<Tensor, Tensor> fwd_kv8_step(const Tensor &q, const Tensor &k, const 
         TORCH_CHECK(!rotary_cos.has_value() && !rotary_sin.has_value(),
                     "This flash attention build does not support rotary_cos / rotary_sin with an fp8 KV cache.");
     }
-    TORCH_CHECK(!qv.has_value(), "This flash attention build does not support qv with an fp8 KV cache.");
-    TORCH_CHECK(v.size(-1) == q.size(-1),
+    TORCH_CHECK(mla || !qv.has_value(), "This flash attention build does not support qv with an fp8 KV cache.");
+    TORCH_CHECK(mla || v.size(-1) == q.size(-1),
                 "This flash attention build does not support a V headdim of its own with an fp8 KV cache.");
     TORCH_CHECK(attention_chunk == 0, "This flash attention build does not support attention_chunk with an fp8 KV cache.");
     TORCH_CHECK(q.size(-1) <= 128 && q.size(-1) % 16 == 0,
@@ -1406,6 +1450,9 @@ std::tuple<Tensor, Tensor> fwd_kv8_step(const Tensor &q, const Tensor &k, const 
                     "cu_seqlens_q must be a contiguous int32 CUDA tensor");
         TORCH_CHECK(max_seqlen_q_.has_value() && *max_seqlen_q_ > 0, "max_seqlen_q must be provided with cu_seqlens_q");
     }
+    if (mla)
+        return fwd_qv8(q, k, v, qv, out_, cu_seqlens_q, seqused_q, seqused_k, max_seqlen_q_, page_table, kv_batch_idx, leftpad_k, k_descale,
+                       v_descale, softmax_scale, is_causal, window_size_left, window_size_right, softcap, num_splits);
     OptTensor fill = seqused_k;
     Tensor qc = q;
     if (appends) {
@@ -1445,6 +1492,7 @@ std::tuple<Tensor, Tensor> fwd_kv8_step(const Tensor &q, const Tensor &k, const 
 // attention_chunk or fp8.  `scheduler_metadata` and `sm_margin` are performance hints and do not change results: ignored.
 // 16-bit q beside a Float8_e4m3fn k / v (an fp8 KV cache with k_descale / v_descale, out in q's dtype): recognised here and
 // served by fwd_kv8_step above, the fp8 counterpart of the two 16-bit cache steps (its refusals, append, rotary pass and read).
+// The MLA shape over that cache (head_size <= 64 beside head_size_v in [256, 512], qv optional) is read by fwd_qv8 (fa_fwd_qv8).
 // `pack_gqa` is a hint too: True asks every route below for the pk kernel (FA_FLAG_PACK_GQA: honoured for GQA / MQA calls of
 // 16-bit types at head dims <= 128 without attention_chunk, a V head dim of its own or qv; a no-op elsewhere and behind the
 // single-token GQA swap); False and None keep the unpacked routes (no automatic rule yet).
@@ -1468,7 +1516,8 @@ std::tuple<Tensor, Tensor, OptTensor, OptTensor> fa3_fwd_core(
         // 16-bit queries over an fp8 KV cache: the kv8 step (what it does not serve is refused by argument there)
         auto r = fwd_kv8_step(q, k, v, k_new, v_new, qv, out_, cu_seqlens_q, cu_seqlens_k, cu_seqlens_k_new, seqused_q, seqused_k,
                               max_seqlen_q_, page_table, kv_batch_idx, leftpad_k, rotary_cos, rotary_sin, seqlens_rotary, k_descale,
-                              v_descale, softmax_scale_.value_or(std::pow(double(q.size(-1)), -0.5)), is_causal, window_size_left,
+                              v_descale, softmax_scale_.value_or(std::pow(double(q.size(-1) + (qv.has_value() ? v.size(-1) : 0)), -0.5)), is_causal,
+                              window_size_left,
                               window_size_right, attention_chunk_.value_or(0), softcap, is_rotary_interleaved, num_splits, sink);
         return {std::get<0>(r), std::get<1>(r), c10::nullopt, c10::nullopt};
     }

@@ -250,7 +250,7 @@ int fa_fwd_validate(const fa_fwd_params *params);
  * device access; the text lives in thread-local storage until the next call on the same thread. */
 const char *fa_fwd_plan_name(const fa_fwd_params *params, int32_t num_cus);
 
-/* Test hook: the name of the plan the calling thread's most recent fa_fwd() (or fa_fwd_sink, fa_fwd_block_sparse, fa_fwd_kv8) launched (same text as fa_fwd_plan_name on that
+/* Test hook: the name of the plan the calling thread's most recent fa_fwd() (or fa_fwd_sink, fa_fwd_block_sparse, fa_fwd_kv8, fa_fwd_qv8) launched (same text as fa_fwd_plan_name on that
  * call's params and the device's CU count; for a wide V run as several 256-column calls, the outer "... cols=N" plan).  NULL
  * before the first call or when that call failed validation; unspecified after a call that returned any other error (a failed
  * 256-column part leaves that part's plan).  fa_fwd keeps a struct copy; the text is made here, in
@@ -377,6 +377,34 @@ int fa_fwd_kv8(const fa_fwd_params *params, void *stream);
 int fa_fwd_kv8_validate(const fa_fwd_params *params);
 int64_t fa_fwd_kv8_workspace_size(const fa_fwd_params *params);
 const char *fa_fwd_kv8_plan_name(const fa_fwd_params *params, int32_t num_cus);
+
+/*
+ * The MLA decode shape over an fp8 (OCP e4m3fn) KV cache: fa_fwd_kv8's contract for a q/k head dim d <= 64 beside a V / latent
+ * head dim d_v in [256, 512] (required), with the optional second score term params->qv (16-bit (.., h, d_v) rows beside q,
+ * qv_*_stride in elements; NULL = the same shape without it).  q, qv and o are fp16 / bf16 (params->dtype), k and v point at
+ * e4m3 BYTES with strides in bytes.  Descales act in fp32 on the products, never on a 16-bit operand:
+ *     S = (k_descale . Q.K8^T + v_descale . Qv.V8^T) . softmax_scale        O = v_descale . P.V8 / l
+ * with k_descale / v_descale per (batch, kv head), NULL = 1.0; under softcap both factors act in front of the tanh; q_descale is
+ * ignored.  One kernel, qv8_fwd_kernel (csrc/fa_fwd_kernel_qv8.h), in the work shape of fwd_kernel_qv: 32 (query row, head of
+ * the GQA group) pairs of one kv head per workgroup.
+ * Served: what fa_fwd_kv8 serves (dense cache with seqused_k -- clamped to the capacity --, kv_batch_idx, leftpad_k; paged cache
+ * with any page_block_size >= 1; dense and ragged queries; is_causal, both window sides, softcap; split-KV), for d % 16 == 0,
+ * d_v % 16 == 0.  num_splits: 1 = off, N > 1 = N parts, 0 = what fa_fwd's qv kernel splits the 16-bit call of the same shape
+ * into.  The parts write fp32 partial O (splits, b, seqlen_q, h, d_v) and LSE (splits, b, h, seqlen_q) -- ragged queries
+ * (splits, total_q, h, d_v) and (splits, h, total_q) -- into params->workspace (fa_fwd_qv8_workspace_size() bytes, 256-byte
+ * aligned), merged by one fa_fwd_combine launch with d = d_v.  A row without a visible key gives O = 0, LSE = +inf, split or not.
+ * FA_ERR_UNSUPPORTED, checked first: dtype fp8, d > 64, d % 16 != 0, d_v outside [256, 512] or d_v % 16 != 0, ALiBi, dropout,
+ * attention_chunk, s_dmask, cu_seqlens_k (and block_table beside kv_batch_idx or leftpad_k).  There is no sink argument.  q / o /
+ * qv strides are multiples of 8 elements, k / v strides multiples of 16 bytes with the row strides in [0, 2^24); pointers are
+ * 16-byte aligned.  A cache entry of 2 GiB or more is served (64-bit base per 64-key tile).  FA_ERR_WORKSPACE when a split call
+ * lacks its workspace.  The callee never allocates and never synchronises.  fa_fwd_kv8_validate keeps refusing qv and a wide V.
+ * fa_fwd_last_plan_name() names such a call "qv8_fwd_kernel DVT=<256|512> waves=4[ SOFTCAP] block_m=32 splits=<N>";
+ * fa_fwd_qv8_plan_name gives the same text from params alone (num_cus decides nothing), NULL when fa_fwd_qv8 would reject them.
+ */
+int fa_fwd_qv8(const fa_fwd_params *params, void *stream);
+int fa_fwd_qv8_validate(const fa_fwd_params *params);
+int64_t fa_fwd_qv8_workspace_size(const fa_fwd_params *params);
+const char *fa_fwd_qv8_plan_name(const fa_fwd_params *params, int32_t num_cus);
 
 /* Human-readable text for a status code (static storage). */
 const char *fa_strerror(int status);
