@@ -1,8 +1,11 @@
 """Helpers shared by the GPU parity tests (a plain module, not collected): row sampling for problems whose full attention
 matrix is too costly for the CPU oracle, and the row-subset comparison of tests/test_full_size_gpu.py (bounds in its docstring).
-Also the one place that reads back which forward plan ran (fa_fwd_last_plan_name, include/fa_fwd.h) and which backward
-kernels (fa_bwd_last_plan_name, include/fa_bwd.h)."""
+Tiles / _emit record the per-tile err / bound ratios of the plan-keyed parity files (tests/test_plan_parity_gpu.py,
+tests/test_kv8_plan_parity_gpu.py).  Also the one place that reads back which forward plan ran (fa_fwd_last_plan_name,
+include/fa_fwd.h) and which backward kernels (fa_bwd_last_plan_name, include/fa_bwd.h)."""
+import json
 import math
+import os
 import re
 
 import torch
@@ -10,6 +13,7 @@ import torch
 from oracle import attention_ref as oracle
 
 FP8 = torch.float8_e4m3fn
+SLICE = 32  # rows of the smallest wave slice of any forward kernel
 
 
 def last_plan():
@@ -96,6 +100,42 @@ def causal_bias(rows, sq, sk):
     i = torch.tensor(rows, dtype=torch.long).view(-1, 1)
     j = torch.arange(sk, dtype=torch.long).view(1, -1)
     return torch.where(j <= i + sk - sq, 0.0, float("-inf")).view(1, 1, len(rows), sk)
+
+
+class Tiles:
+    """The worst err / bound of a case per (batch, head, row slice), over every comparison the case makes."""
+
+    def __init__(self):
+        self.worst = None
+
+    def add(self, out, ref, pt, rtol, atol, rows_per_tile=SLICE, batch=0):
+        """out / ref / pt (b, rows, h, d).  atol: a number, or None = 2 |(ref + 0.3 - 0.3) - ref|max of the tile."""
+        out, ref, pt = out.float().cpu(), ref.float(), pt.float()
+
+        def tiles(x):  # (b, rows, h, d) -> (b, h, slices): max over the slice's rows and the columns
+            x = x.amax(-1)
+            x = torch.nn.functional.pad(x, (0, 0, 0, -x.shape[1] % rows_per_tile))
+            return x.view(x.shape[0], -1, rows_per_tile, x.shape[-1]).amax(2).transpose(1, 2)
+        err = tiles((out - ref).abs().nan_to_num(nan=float("inf")))
+        bound = rtol * tiles((pt - ref).abs()) + (2 * tiles((ref + 0.3 - 0.3 - ref).abs()) if atol is None else atol)
+        ratio = torch.where(err == 0, torch.zeros_like(err), err / bound)  # (a tile without error has ratio 0, also at bound 0)
+        at = int(ratio.argmax())
+        b, h, s = (int(i) for i in torch.unravel_index(torch.tensor(at), ratio.shape))
+        got = dict(ratio=float(ratio.flatten()[at]), batch=b + batch, head=h, slice=s, err=float(err[b, h, s]), bound=float(bound[b, h, s]))
+        if self.worst is None or got["ratio"] > self.worst["ratio"]:
+            self.worst = got
+
+
+def _emit(cid, plan, tiles, env="FA_FWD_PARITY_JSONL"):
+    """One JSON line for the case: printed, and appended to the file the environment variable `env` names when it is set."""
+    w = tiles.worst or {}
+    line = json.dumps(dict(case=cid, plan=plan, rows_per_tile=SLICE,
+                           **{k: (v if not isinstance(v, float) or math.isfinite(v) else str(v)) for k, v in w.items()}))
+    print(line)
+    path = os.environ.get(env)
+    if path:
+        with open(path, "a") as f:
+            f.write(line + "\n")
 
 
 def _check_rows(out_rows, lse_rows, q_rows, k, v, bias, what, fp8_kw=None, lse_tol=2e-3, record=None):

@@ -2,7 +2,9 @@
 parity case that runs it (tests/test_plan_parity_gpu.py), and every other kernel of the forward device code with the GPU test
 that compares it with a reference (AUX).  A plain module, imported by tests/test_fwd_plan.py (which checks the tables against
 the kernel symbols of the compiled device code: a kernel added without a row here fails on the CPU) and by the parity test
-(which asserts that every case launches exactly its key).
+(which asserts that every case launches exactly its key).  The two forward units over an fp8 (e4m3) KV cache --
+csrc/fa_fwd_kv8_api.hip and csrc/fa_fwd_qv8_api.hip, with plans of their own -- and the append unit beside them have the sibling
+module tests/kv8_plan_universe.py (tests/test_kv8_plan.py, tests/test_kv8_plan_parity_gpu.py).
 
 Kernel key = (element type, kernel form, epilogue).  The form is the plan name of fa_fwd_plan_name without `block_m=`,
 `splits=`, `cols=` and `fp8_expand`: one template instantiation.  The epilogue is the store path the launch takes inside it,

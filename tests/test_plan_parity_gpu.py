@@ -23,9 +23,7 @@ place for such a run).  The whole-tensor bound above takes its two maxima anywhe
 factor 2 has no margin on the forward (an emulation of the kernels' arithmetic on the CPU -- online softmax over 64-key tiles,
 P rounded to the input type, fp32 accumulation -- reaches a ratio of exactly 1.00 on a bf16 causal sq = sk = 300 problem), so a ratio above 1
 in the file is no finding by itself."""
-import json
 import math
-import os
 import re
 
 import pytest
@@ -33,52 +31,16 @@ import torch
 
 import block_sparse_oracle as bso
 from oracle import attention_ref as oracle
-from parity_helpers import FP8, _check_rows, causal_bias, kernel_key, last_plan, sparse_lists, wave_slice_rows
+from parity_helpers import FP8, SLICE, Tiles, _check_rows, _emit, causal_bias, kernel_key, last_plan, sparse_lists, wave_slice_rows
 from plan_universe import FORMS, HOOK_ONLY, UNIVERSE, UNREACHABLE, case_id, cases
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 DTYPES = {"bf16": torch.bfloat16, "fp16": torch.float16, "fp8": FP8}
 PAGE = 256  # (the FA2 entry point's page rule)
-SLICE = 32  # rows of the smallest wave slice of any forward kernel
 
 CASES = cases()
 SEEN = set()  # kernel keys launched by the cases of this session
-
-
-class Tiles:
-    """The worst err / bound of a case per (batch, head, row slice), over every comparison the case makes."""
-
-    def __init__(self):
-        self.worst = None
-
-    def add(self, out, ref, pt, rtol, atol, rows_per_tile=SLICE, batch=0):
-        """out / ref / pt (b, rows, h, d).  atol: a number, or None = 2 |(ref + 0.3 - 0.3) - ref|max of the tile."""
-        out, ref, pt = out.float().cpu(), ref.float(), pt.float()
-
-        def tiles(x):  # (b, rows, h, d) -> (b, h, slices): max over the slice's rows and the columns
-            x = x.amax(-1)
-            x = torch.nn.functional.pad(x, (0, 0, 0, -x.shape[1] % rows_per_tile))
-            return x.view(x.shape[0], -1, rows_per_tile, x.shape[-1]).amax(2).transpose(1, 2)
-        err = tiles((out - ref).abs().nan_to_num(nan=float("inf")))
-        bound = rtol * tiles((pt - ref).abs()) + (2 * tiles((ref + 0.3 - 0.3 - ref).abs()) if atol is None else atol)
-        ratio = torch.where(err == 0, torch.zeros_like(err), err / bound)  # (a tile without error has ratio 0, also at bound 0)
-        at = int(ratio.argmax())
-        b, h, s = (int(i) for i in torch.unravel_index(torch.tensor(at), ratio.shape))
-        got = dict(ratio=float(ratio.flatten()[at]), batch=b + batch, head=h, slice=s, err=float(err[b, h, s]), bound=float(bound[b, h, s]))
-        if self.worst is None or got["ratio"] > self.worst["ratio"]:
-            self.worst = got
-
-
-def _emit(cid, plan, tiles):
-    w = tiles.worst or {}
-    line = json.dumps(dict(case=cid, plan=plan, rows_per_tile=SLICE,
-                           **{k: (v if not isinstance(v, float) or math.isfinite(v) else str(v)) for k, v in w.items()}))
-    print(line)
-    path = os.environ.get("FA_FWD_PARITY_JSONL")
-    if path:
-        with open(path, "a") as f:
-            f.write(line + "\n")
 
 
 def _inputs(case, dtype, seed):

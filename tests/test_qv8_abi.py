@@ -220,22 +220,10 @@ def test_qv8_symbols_are_exported():
         assert name in _lib.EXPORTED_SYMBOLS and hasattr(lib, name)
 
 
-TYPES = {"DF16b": "bf16", "DF16_": "fp16"}
-
-
 def _qv8_kernels():
-    """{(type, DVT, SOFTCAP): private segment bytes} of the device code of fa_fwd_qv8_api.hip."""
-    from device_asm import device_asm
-    text = open(device_asm("fa_fwd_qv8_api.hip")).read()
-    out = {}
-    for m in re.finditer(r"^\s*\.amdhsa_kernel (\S+)$(.*?)^\s*\.end_amdhsa_kernel", text, re.M | re.S):
-        sym, body = m.group(1), m.group(2)
-        k = re.match(r"_ZN2fa14qv8_fwd_kernelI(DF16b|DF16_)Li(\d+)ELb([01])EEEvNS_8QvParamsE$", sym)
-        assert k, f"a kernel in fa_fwd_qv8_api.hip that is no qv8_fwd_kernel: {sym}"
-        key = (TYPES[k.group(1)], int(k.group(2)), bool(int(k.group(3))))
-        assert key not in out
-        out[key] = int(re.search(r"\.amdhsa_private_segment_fixed_size (\d+)", body).group(1))
-    return out
+    """{(type, DVT, SOFTCAP): private segment bytes} of the device code of fa_fwd_qv8_api.hip (any other kernel in it is an error)."""
+    from device_asm import fp8_cache_kernels
+    return fp8_cache_kernels("fa_fwd_qv8_api.hip", "qv8_fwd_kernel", "QvParams")
 
 
 def test_qv8_instantiations_and_no_scratch():
