@@ -6,6 +6,7 @@
 #include "fa_bwd.h"
 #include "fa_bwd_internal.h"
 #include "fa_bwd_kernel.h"
+#include "fa_fwd_internal.h"
 #include "fa_launch.h"
 
 #include <algorithm>
@@ -266,27 +267,13 @@ void bwd_fill_params(const fa_bwd_params *p, BParams &bp) {
     bp.total_q = p->total_q;
     bp.h_ratio = p->h / p->h_k;
 
-    // window normalisation exactly as the forward (fa_fwd_api.hip; csrc/flash_attn/flash_api.cpp:790,836-837)
-    int wl = p->window_size_left, wr = p->window_size_right;
-    if (p->is_causal) wr = 0;
-    if (!(p->flags & FA_FLAG_FA3_WINDOW)) {  // (FA3 rule: a negative side is unbounded, include/fa_fwd.h)
-        if (wl >= p->seqlen_k) wl = -1;
-        if (wr >= p->seqlen_k) wr = -1;
-        if (p->is_causal) wr = 0;
-        if (wl >= 0 && wr < 0) wr = p->seqlen_k;
-    }
-    bp.window_left = wl;
-    bp.window_right = wr;
-
-    const bool softcap = p->softcap > 0.f;
-    constexpr float kLog2e = 1.4426950408889634f;
-    if (softcap) {
-        bp.softcap_pre = p->softmax_scale / p->softcap;
-        bp.scale_log2 = p->softcap * kLog2e;
-    } else {
-        bp.softcap_pre = 0.f;
-        bp.scale_log2 = p->softmax_scale * kLog2e;
-    }
+    // the forward's window rule and softmax scales (fa_fwd_internal.h; csrc/flash_attn/flash_api.cpp:790,836-837)
+    bp.window_left = p->window_size_left;
+    bp.window_right = p->window_size_right;
+    normalise_window(p->is_causal, p->flags, p->seqlen_k, bp.window_left, bp.window_right);
+    const SoftmaxScales sc = softmax_scales(p->softmax_scale, p->softcap);
+    bp.softcap_pre = sc.softcap_pre;
+    bp.scale_log2 = sc.scale_log2;
     bp.out_scale = p->softmax_scale;
     bp.alibi = p->alibi_slopes;
     bp.alibi_bs = (int32_t)p->alibi_slopes_batch_stride;

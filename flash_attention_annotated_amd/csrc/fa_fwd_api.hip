@@ -3,6 +3,8 @@
 // Host-side role of mha_fwd / mha_varlen_fwd (csrc/flash_attn/flash_api.cpp:350-512, 514-755),
 // set_params_fprop (:26-159) and run_mha_fwd (:243-255): validate, fill the kernel params,
 // pick the instantiation, launch on the caller's stream.  No allocation, no synchronisation.
+// What every forward route does the same way -- the params fill, the window rule, the softmax scales, the split-KV workspace
+// layout, the packed-row grid -- is in fa_fwd_internal.h.
 #include "fa_fwd.h"
 #include "fa_fwd_kernel.h"
 #include "fa_fwd_kernel_w64.h"
@@ -62,6 +64,9 @@ using fa::pack8;
 using fa::rotary_slot;
 using fa::for_ragged_rows;
 using fa::ragged_launch_shape;
+using fa::SplitPlan;
+using fa::align256;
+using fa::query_rows;
 
 template <typename T>
 __global__ void rotary_kernel(const fa_rotary_params p) {
@@ -271,8 +276,6 @@ __global__ __launch_bounds__(256) void sdmask_kernel(const fa::KParams p, T *out
 // and fp8 workspace.  It is host code without HIP calls: fa_fwd_validate, fa_fwd_workspace_size, fa_fwd and fa_fwd_plan_name
 // (the test hook that names the plan, tests/test_fwd_plan.py) all read the same plan.
 
-int64_t align256(int64_t x) { return (x + 255) & ~int64_t(255); }
-
 struct Fp8Plan {
     int64_t rows_q, rows_k, q_bytes, kv_bytes, total;
 };
@@ -305,9 +308,11 @@ inline bool qv_shape(const fa_fwd_params *p) {
     return p->dtype != FA_DTYPE_FP8_E4M3 && p->d <= 64 && dv_of(p) >= 256 && dv_of(p) <= 512;
 }
 inline bool qv_route(const fa_fwd_params *p) { return p->qv || (qv_shape(p) && (p->block_table || p->num_splits > 1)); }
-// a left window that masks anything (the FA2 rule drops one of seqlen_k or more, fa_fwd's window normalisation)
+// a left window that masks anything (the FA2 rule drops one of seqlen_k or more: fa::normalise_window)
 inline bool left_window(const fa_fwd_params *p) {
-    return p->window_size_left >= 0 && ((p->flags & FA_FLAG_FA3_WINDOW) || p->window_size_left < p->seqlen_k);
+    int32_t wl = p->window_size_left, wr = p->window_size_right;
+    fa::normalise_window(p->is_causal, p->flags, p->seqlen_k, wl, wr);
+    return wl >= 0;
 }
 // FA_FLAG_PACK_GQA is a hint: the pk kernel (fa_fwd_kernel_pk.h) honours it for GQA / MQA calls of 16-bit types at head dims
 // <= 128 without ALiBi, dropout, attention_chunk, a V head dim of its own or qv; every other call is planned as without it.
@@ -390,17 +395,11 @@ int effective_variant(const fa_fwd_params *p) {
 // 16-bit problems over dense K/V split: dense queries, and ragged queries over a batched cache (ragged_cache()); the
 // cu_seqlens_q + cu_seqlens_k problems never do.  Heuristic (num_splits == 0): split when the tiles leave most of the
 // 256 CUs idle, so that tiles x splits reaches ~2 workgroups per CU, with at least 4 key blocks (256 keys) per split.
-struct SplitPlan {
-    int splits;
-    // partial O (fp32, (splits, b, sq, h, d); ragged queries (splits, total_q, h, d)) and LSE (fp32, (splits, b, h, sq) / (splits, h, total_q))
-    int64_t o_bytes, lse_bytes, total;
-};
+// The partials: fa::split_layout.
 // ragged queries over a batched / paged cache: cu_seqlens_q without cu_seqlens_k, fill levels in seqused_k (include/fa_fwd.h)
 inline bool ragged_cache(const fa_fwd_params *p) { return p->cu_seqlens_q && !p->cu_seqlens_k; }
-// query rows of the whole problem, and an upper bound of its row blocks of `bm` rows: the host knows total_q and max_seqlen_q
-// of a ragged batch, not the lengths (no sync) -- every non-empty sequence has at most len / bm + 1 blocks, and at most
-// ceil(max_seqlen_q / bm)
-inline int64_t query_rows(const fa_fwd_params *p) { return p->cu_seqlens_q ? p->total_q : (int64_t)p->b * p->seqlen_q; }
+// an upper bound of the problem's row blocks of `bm` rows: the host knows total_q and max_seqlen_q of a ragged batch, not the
+// lengths (no sync) -- every non-empty sequence has at most len / bm + 1 blocks, and at most ceil(max_seqlen_q / bm)
 inline int64_t row_blocks_bound(const fa_fwd_params *p, int64_t bm, int64_t rows_per_query = 1) {
     const int64_t per_seq = (p->seqlen_q * rows_per_query + bm - 1) / bm;
     if (!p->cu_seqlens_q) return per_seq * p->b;
@@ -430,14 +429,7 @@ SplitPlan split_plan(const fa_fwd_params *p, int variant, bool pk = false) {
             n = std::max(1, std::min(n, 64));
         }
     }
-    n = std::max(1, std::min(n, std::min(n_blocks, 128)));
-    if (n <= 1) return sp;
-    sp.splits = n;
-    const int64_t rows = query_rows(p);
-    sp.o_bytes = (n * rows * p->h * p->d * 4 + 255) & ~int64_t(255);
-    sp.lse_bytes = (n * rows * p->h * 4 + 255) & ~int64_t(255);
-    sp.total = sp.o_bytes + sp.lse_bytes;
-    return sp;
+    return fa::split_layout(p, std::min(n, std::min(n_blocks, 128)), p->d);
 }
 
 // Split plan of the qv kernel: the problems split_plan takes.  Heuristic (num_splits == 0): one workgroup fills a CU
@@ -455,14 +447,7 @@ SplitPlan split_plan_qv(const fa_fwd_params *p) {
         if (groups < 512 && n_blocks >= 8) n = (int)std::max<int64_t>(1, std::min<int64_t>((512 + groups - 1) / groups, n_blocks / 4));
         n = std::min(n, 64);
     }
-    n = std::max(1, std::min(n, std::min(n_blocks, 128)));
-    if (n <= 1) return sp;
-    sp.splits = n;
-    const int64_t rows = query_rows(p);
-    sp.o_bytes = (n * rows * p->h * dv_of(p) * 4 + 255) & ~int64_t(255);
-    sp.lse_bytes = (n * rows * p->h * 4 + 255) & ~int64_t(255);
-    sp.total = sp.o_bytes + sp.lse_bytes;
-    return sp;
+    return fa::split_layout(p, std::min(n, std::min(n_blocks, 128)), dv_of(p));
 }
 
 enum class Family { fp8, qv, w64, d256, generic, pk };  // fwd_kernel_fp8, fwd_kernel_qv, fwd_kernel_w64, fwd_kernel_d256, fwd_kernel, pk_fwd_kernel
@@ -551,19 +536,17 @@ FwdPlan plan_fwd(const fa_fwd_params *p, int num_cus) {
     pl.workspace = fp8 ? (native ? 0 : pl.fp8.total) : pl.split.total;
 
     if (pk) {
-        // pk_fwd_kernel: blocks of PK_BLOCK_M packed rows (query row x head of the GQA group) per (batch, kv head, split) group;
-        // the groups are dealt over the 8 XCDs, the blocks of a group stay on one (fwd_kernel_qv's scheduling)
+        // pk_fwd_kernel: blocks of PK_BLOCK_M packed rows per (batch, kv head, split) group (fa::packed_grid)
         pl.family = Family::pk;
         pl.d = pl.deff = head_dim_tile(p->d);
         pl.waves = fa::PK_NWAVES;
         pl.softcap = softcap;
         pl.block_m = fa::PK_BLOCK_M;
-        const int64_t pblocks = ((int64_t)p->seqlen_q * (p->h / p->h_k) + fa::PK_BLOCK_M - 1) / fa::PK_BLOCK_M;
-        const int64_t groups = (int64_t)p->b * p->h_k * pl.split.splits;
-        pl.tiles = pblocks * p->h_k * p->b;
-        pl.grid = (groups + 7) / 8 * 8 * pblocks;
-        if (pblocks > 0x7fffffff || groups > 0x7fffffff || pl.grid > 0x7fffffff) pl.status = FA_ERR_BAD_SHAPE;
-        pl.num_m_blocks = pl.status == FA_OK ? (int32_t)pblocks : 0;
+        const fa::PackedGrid g = fa::packed_grid(p, fa::PK_BLOCK_M, pl.split.splits);
+        pl.tiles = g.pblocks * p->h_k * p->b;
+        pl.grid = g.grid;
+        pl.status = g.status;
+        pl.num_m_blocks = pl.status == FA_OK ? (int32_t)g.pblocks : 0;
         return pl;
     }
 
@@ -827,15 +810,13 @@ int launch_qv(const FwdPlan &pl, const fa_fwd_params *p, const fa::KParams &kp, 
     qa.p = kp;
     qa.qv = p->qv;
     qa.qv_batch_stride = p->qv_batch_stride; qa.qv_row_stride = p->qv_row_stride; qa.qv_head_stride = p->qv_head_stride;
-    const int64_t pblocks = ((int64_t)p->seqlen_q * (p->h / p->h_k) + 31) / 32;
-    const int64_t groups = (int64_t)p->b * p->h_k * kp.num_splits;
-    const int64_t grid = (groups + 7) / 8 * 8 * pblocks;
-    if (pblocks == 0 || groups == 0) return FA_OK;
-    if (grid > 0x7fffffff) return FA_ERR_BAD_SHAPE;
-    qa.num_pblocks = (int32_t)pblocks;
-    qa.num_groups = (int32_t)groups;
-    if (pl.deff == 256) return pl.softcap ? launch_qv_form<T, 256, true>(qa, grid, stream) : launch_qv_form<T, 256, false>(qa, grid, stream);
-    return pl.softcap ? launch_qv_form<T, 512, true>(qa, grid, stream) : launch_qv_form<T, 512, false>(qa, grid, stream);
+    const fa::PackedGrid g = fa::packed_grid(p, 32, kp.num_splits);
+    if (g.pblocks == 0 || g.groups == 0) return FA_OK;
+    if (g.status != FA_OK) return g.status;
+    qa.num_pblocks = (int32_t)g.pblocks;
+    qa.num_groups = (int32_t)g.groups;
+    if (pl.deff == 256) return pl.softcap ? launch_qv_form<T, 256, true>(qa, g.grid, stream) : launch_qv_form<T, 256, false>(qa, g.grid, stream);
+    return pl.softcap ? launch_qv_form<T, 512, true>(qa, g.grid, stream) : launch_qv_form<T, 512, false>(qa, g.grid, stream);
 }
 
 // the pk kernel (fa_fwd_kernel_pk.h): head-dim tile 64 or 128, plain or softcap
@@ -1166,12 +1147,9 @@ int fa_fwd_validate(const fa_fwd_params *p) {
     const void *ptrs[] = {p->q, p->k, p->v, p->o};
     for (const void *ptr : ptrs)
         if (reinterpret_cast<uintptr_t>(ptr) % (fp8 && ptr != p->o ? 8 : 16) != 0) return FA_ERR_BAD_STRIDE;
-    auto workspace_short = [&](int64_t bytes) {
-        return !p->workspace || reinterpret_cast<uintptr_t>(p->workspace) % 256 != 0 || (int64_t)p->workspace_bytes < bytes;
-    };
-    if (pl.fp8_expand && !pl.nothing && workspace_short(pl.fp8.total)) return FA_ERR_WORKSPACE;
+    if (pl.fp8_expand && !pl.nothing && fa::workspace_short(p, pl.fp8.total)) return FA_ERR_WORKSPACE;
     if (p->num_splits < 0) return FA_ERR_BAD_SHAPE;
-    if (pl.split.splits > 1 && workspace_short(pl.split.total)) return FA_ERR_WORKSPACE;
+    if (pl.split.splits > 1 && fa::workspace_short(p, pl.split.total)) return FA_ERR_WORKSPACE;
     if (p->softcap < 0.f || std::isnan(p->softcap) || std::isnan(p->softmax_scale)) return FA_ERR_BAD_SHAPE;
     if (p->alibi_slopes && (reinterpret_cast<uintptr_t>(p->alibi_slopes) % 4 != 0 || p->alibi_slopes_batch_stride < 0 ||
                             p->alibi_slopes_batch_stride > 0x7fffffff))
@@ -1275,7 +1253,7 @@ static int fwd_run(const fa_fwd_params *p, const fa_sink_params *sink, void *str
     }
 
     fa::KParams kp{};
-    kp.q = p->q; kp.k = p->k; kp.v = p->v; kp.o = p->o; kp.lse = p->softmax_lse;
+    fa::fwd_fill_params(p, own_dv(p) ? p->d_v : p->d, kp);
     const bool fp8 = p->dtype == FA_DTYPE_FP8_E4M3;
     int64_t ws_q_row = 0, ws_k_row = 0;
     if (pl.fp8_expand && !pl.nothing) {
@@ -1297,28 +1275,17 @@ static int fwd_run(const fa_fwd_params *p, const fa_sink_params *sink, void *str
         ws_q_row = (int64_t)p->h * p->d;
         ws_k_row = (int64_t)p->h_k * p->d;
     }
-    kp.cu_seqlens_q = p->cu_seqlens_q; kp.cu_seqlens_k = p->cu_seqlens_k;
-    kp.seqused_q = p->seqused_q; kp.seqused_k = p->seqused_k;
-    kp.q_batch_stride = p->q_batch_stride; kp.q_row_stride = p->q_row_stride; kp.q_head_stride = p->q_head_stride;
-    kp.k_batch_stride = p->k_batch_stride; kp.k_row_stride = p->k_row_stride; kp.k_head_stride = p->k_head_stride;
-    kp.v_batch_stride = p->v_batch_stride; kp.v_row_stride = p->v_row_stride; kp.v_head_stride = p->v_head_stride;
     if (fp8) {
         if (pl.fp8_expand) {  // the expanded copies are contiguous (rows, heads, d)
             kp.q_row_stride = ws_q_row; kp.q_head_stride = p->d; kp.q_batch_stride = ws_q_row * p->seqlen_q;
             kp.k_row_stride = kp.v_row_stride = ws_k_row; kp.k_head_stride = kp.v_head_stride = p->d;
             kp.k_batch_stride = kp.v_batch_stride = ws_k_row * p->seqlen_k;
         }
-        kp.q_descale = p->q_descale; kp.k_descale = p->k_descale; kp.v_descale = p->v_descale;
+        kp.q_descale = p->q_descale;  // (16-bit calls: the kernels get no descales, whatever the caller's fields hold)
         kp.qd_bs = (int32_t)p->q_descale_batch_stride; kp.qd_hs = (int32_t)p->q_descale_head_stride;
-        kp.kd_bs = (int32_t)p->k_descale_batch_stride; kp.kd_hs = (int32_t)p->k_descale_head_stride;
-        kp.vd_bs = (int32_t)p->v_descale_batch_stride; kp.vd_hs = (int32_t)p->v_descale_head_stride;
+        fa::fwd_fill_kv_descales(p, kp);
     }
-    kp.o_batch_stride = p->o_batch_stride; kp.o_row_stride = p->o_row_stride; kp.o_head_stride = p->o_head_stride;
-    kp.b = p->b; kp.seqlen_q = p->seqlen_q; kp.seqlen_k = p->seqlen_k; kp.h = p->h; kp.h_k = p->h_k; kp.d = p->d;
-    kp.total_q = p->total_q;
-    kp.dv = own_dv(p) ? p->d_v : p->d;
     kp.chunk = p->attention_chunk;
-    kp.h_ratio = p->h / p->h_k;
     kp.num_m_blocks = pl.num_m_blocks;
     if (pl.tiles == 0) return FA_OK;  // nothing to compute (seqlen_q == 0)
     if (pl.status != FA_OK) return pl.status;
@@ -1328,43 +1295,13 @@ static int fwd_run(const fa_fwd_params *p, const fa_sink_params *sink, void *str
     kp.grid = (int32_t)pl.grid;
     kp.num_cus = num_cus;
     // split-KV: `splits` copies of the grid; partial results go to the workspace and are merged below
+    // (kp.dv columns: d_v on the qv kernel's path, d on the others -- they never split with a V head dim of its own)
     const SplitPlan &sp = pl.split;
     kp.num_splits = sp.splits;
-    if (sp.splits > 1) {
-        char *ws = static_cast<char *>(p->workspace);
-        kp.o = ws;
-        kp.lse = reinterpret_cast<float *>(ws + sp.o_bytes);
-        kp.o_row_stride = (int64_t)p->h * dv_of(p); kp.o_head_stride = dv_of(p); kp.o_batch_stride = kp.o_row_stride * p->seqlen_q;
-        kp.o_split_stride = kp.o_batch_stride * p->b;
-        kp.lse_split_stride = (int64_t)p->b * p->h * p->seqlen_q;
-        if (p->cu_seqlens_q) {  // ragged queries: (splits, total_q, h, d_v) and (splits, h, total_q)
-            kp.o_split_stride = kp.o_row_stride * p->total_q;
-            kp.lse_split_stride = (int64_t)p->h * p->total_q;
-        }
-    }
-
-    // window normalisation: csrc/flash_attn/flash_api.cpp:396-402
-    int wl = p->window_size_left, wr = p->window_size_right;
-    if (p->is_causal) wr = 0;
-    if (p->flags & FA_FLAG_FA3_WINDOW) {
-        // FA3 rule (hopper/flash_api.cpp:152-153, 589-590): a missing side becomes seqlen_k - 1 / seqlen_q - 1, which never
-        // masks anything = unbounded here; sides are taken as given otherwise
-    } else {
-        if (wl >= p->seqlen_k) wl = -1;
-        if (wr >= p->seqlen_k) wr = -1;
-        if (p->is_causal) wr = 0;
-        // set_params_fprop csrc/flash_attn/flash_api.cpp:141-142: a one-sided window gets seqlen_k on the other side.
-        // For a left-only window that is NOT the same as unbounded when seqlen_q > seqlen_k (the bottom-right aligned
-        // diagonal starts left of key 0), so it is mirrored.  The symmetric rule (right-only -> left = seqlen_k) never
-        // masks anything (row + sk - sq - seqlen_k < 0 for every row) and is left as "unbounded".
-        if (wl >= 0 && wr < 0) wr = p->seqlen_k;
-    }
-    kp.window_left = wl;
-    kp.window_right = wr;
+    if (sp.splits > 1) fa::split_redirect(p, sp, kp);
 
     kp.alibi = p->alibi_slopes;
     kp.alibi_bs = (int32_t)p->alibi_slopes_batch_stride;
-    kp.leftpad_k = p->leftpad_k;
     // dropout: keep iff randval <= floor(255 (1 - p)); 255 = everything kept = the branch is off
     // (the 8-bit quantisation of the reference's ROCm back-end: any p > 0 gives a threshold <= 254, i.e. at least 1/256 of the
     //  elements are dropped however small p is; the kept ones are scaled by 1 / (1 - p))
@@ -1373,10 +1310,6 @@ static int fwd_run(const fa_fwd_params *p, const fa_sink_params *sink, void *str
     kp.rng_state = p->rng_state;
     const bool sdmask_signed = (p->flags & FA_FLAG_SDMASK_SIGNED) && p->s_dmask;
     kp.s_dmask = sdmask_signed ? nullptr : p->s_dmask;
-    kp.kv_batch_idx = p->kv_batch_idx;  // (dense K/V only: fa_fwd_validate)
-    kp.block_table = p->block_table;
-    kp.bt_bs = (int32_t)p->block_table_batch_stride;
-    kp.page_size = p->page_block_size;
     // the sink: an epilogue term of the kernel, or -- split-KV: the parts write sink-free partials -- of the merge
     fa::KParams sink_kp{};
     if (sink) {
@@ -1386,18 +1319,6 @@ static int fwd_run(const fa_fwd_params *p, const fa_sink_params *sink, void *str
         if (sp.splits <= 1) {
             kp.sink = sink_kp.sink; kp.sink_hs = sink_kp.sink_hs; kp.sink_rs = sink_kp.sink_rs; kp.sink_fp32 = sink_kp.sink_fp32;
         }
-    }
-
-    const bool softcap = p->softcap > 0.f;
-    constexpr float kLog2e = 1.4426950408889634f;
-    if (softcap) {  // set_params_fprop csrc/flash_attn/flash_api.cpp:103-117
-        kp.softcap_pre = p->softmax_scale / p->softcap;
-        kp.scale = p->softcap;
-        kp.scale_log2 = p->softcap * kLog2e;
-    } else {
-        kp.softcap_pre = 0.f;
-        kp.scale = p->softmax_scale;
-        kp.scale_log2 = p->softmax_scale * kLog2e;
     }
 
     const bool bf16 = p->dtype == FA_DTYPE_BF16 || fp8;  // fp8: out is bf16
@@ -1507,17 +1428,10 @@ int fa_fwd_block_sparse(const fa_fwd_params *p_, const fa_block_sparse_params *s
 
     fa::BsParams bp{};
     fa::KParams &kp = bp.p;
-    kp.q = p->q; kp.k = p->k; kp.v = p->v; kp.o = p->o; kp.lse = p->softmax_lse;
-    kp.q_batch_stride = p->q_batch_stride; kp.q_row_stride = p->q_row_stride; kp.q_head_stride = p->q_head_stride;
-    kp.k_batch_stride = p->k_batch_stride; kp.k_row_stride = p->k_row_stride; kp.k_head_stride = p->k_head_stride;
-    kp.v_batch_stride = p->v_batch_stride; kp.v_row_stride = p->v_row_stride; kp.v_head_stride = p->v_head_stride;
-    kp.o_batch_stride = p->o_batch_stride; kp.o_row_stride = p->o_row_stride; kp.o_head_stride = p->o_head_stride;
-    kp.b = p->b; kp.seqlen_q = p->seqlen_q; kp.seqlen_k = p->seqlen_k; kp.h = p->h; kp.h_k = p->h_k; kp.d = p->d;
-    kp.dv = dv_of(p);
-    kp.h_ratio = p->h / p->h_k;
+    // (the call's own mask is bottom-right aligned, fa_fwd's window rule; the sequence-length and cache fields validate has
+    // seen NULL, and bs_fwd_kernel reads neither them nor total_q / bt_bs / page_size)
+    fa::fwd_fill_params(p, dv_of(p), kp);
     kp.num_splits = 1;
-    kp.rp_dropout = 1.f;
-    kp.drop_thr = 255;
     kp.num_cus = device_cus();
     // one work item per (batch, head, 128-row block): fwd_kernel's scheduling (tile_of_wg) with block_m = 128
     const int64_t nm = ((int64_t)p->seqlen_q + fa::BS_BLOCK - 1) / fa::BS_BLOCK;
@@ -1535,32 +1449,12 @@ int fa_fwd_block_sparse(const fa_fwd_params *p_, const fa_block_sparse_params *s
     kp.whole_slots = (int32_t)whole_slots;
     kp.grid = (int32_t)grid;
 
-    // the call's own mask, bottom-right aligned: fa_fwd's window normalisation
-    int wl = p->window_size_left, wr = p->window_size_right;
-    if (p->is_causal) wr = 0;
-    if (!(p->flags & FA_FLAG_FA3_WINDOW)) {
-        if (wl >= p->seqlen_k) wl = -1;
-        if (wr >= p->seqlen_k) wr = -1;
-        if (p->is_causal) wr = 0;
-        if (wl >= 0 && wr < 0) wr = p->seqlen_k;
-    }
-    kp.window_left = wl;
-    kp.window_right = wr;
     if (sink) {
         kp.sink = sink->learnable_sink;
         kp.sink_hs = sink->sink_head_stride; kp.sink_rs = sink->sink_row_stride;
         kp.sink_fp32 = sink->sink_dtype == FA_DTYPE_FP32;
     }
     const bool softcap = p->softcap > 0.f;
-    constexpr float kLog2e = 1.4426950408889634f;
-    if (softcap) {
-        kp.softcap_pre = p->softmax_scale / p->softcap;
-        kp.scale = p->softcap;
-        kp.scale_log2 = p->softcap * kLog2e;
-    } else {
-        kp.scale = p->softmax_scale;
-        kp.scale_log2 = p->softmax_scale * kLog2e;
-    }
 
     auto list = [](const int32_t *cnt, const int32_t *idx, const int64_t *cs, const int64_t *is) {
         return fa::BsList{cnt, idx, cs[0], cs[1], cs[2], is[0], is[1], is[2], is[3]};
