@@ -63,6 +63,8 @@ EXPORTED_SYMBOLS = (
     "fa_kvcache_append_kv8",
     "fa_kvcache_append_kv8_validate",
     "fa_kvcache_append_kv8_params_size",
+    "fa_kvcache_append_qv8",
+    "fa_kvcache_append_qv8_validate",
     # include/fa_bwd.h
     "fa_bwd",
     "fa_bwd_validate",
@@ -334,7 +336,7 @@ def is_stale():
 def build(force=False, verbose=False):
     """Compile csrc/ for gfx950 into the in-tree shared library (hipcc cross-compiles without a GPU)."""
     srcs = [os.path.join(CSRC, f) for f in ("fa_fwd_api.hip", "fa_fwd_kv8_api.hip", "fa_fwd_qv8_api.hip", "fa_kvcache_append_kv8.hip",
-                                              "fa_bwd_api.hip", "fa_bwd_bs_api.hip")]
+                                              "fa_kvcache_append_qv8.hip", "fa_bwd_api.hip", "fa_bwd_bs_api.hip")]
     if not force and not is_stale():
         return LIB_PATH
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -486,6 +488,10 @@ def load():
     lib.fa_kvcache_append_kv8_params_size.restype = ctypes.c_uint32
     if lib.fa_kvcache_append_kv8_params_size() != ctypes.sizeof(FaKvcacheAppendKv8Params):
         raise RuntimeError("fa_kvcache_append_kv8_params layout mismatch between include/fa_fwd.h and _lib")
+    lib.fa_kvcache_append_qv8.argtypes = [ctypes.POINTER(FaKvcacheAppendKv8Params), ctypes.c_void_p]
+    lib.fa_kvcache_append_qv8.restype = ctypes.c_int
+    lib.fa_kvcache_append_qv8_validate.argtypes = [ctypes.POINTER(FaKvcacheAppendKv8Params)]
+    lib.fa_kvcache_append_qv8_validate.restype = ctypes.c_int
     lib.fa_sink_grad.argtypes = [ctypes.POINTER(FaSinkGradParams), ctypes.c_void_p]
     lib.fa_sink_grad.restype = ctypes.c_int
     lib.fa_sink_grad_validate.argtypes = [ctypes.POINTER(FaSinkGradParams)]

@@ -2,27 +2,9 @@
 // keys / values are rotated (keys only, the rotation code of the 16-bit appends: fa_rotary.h), divided by the descale of their
 // (sequence, kv head), clamped to +-448, converted to e4m3 with round-to-nearest-even and stored at the rows the 16-bit appends
 // would have written.  A translation unit of its own: fa_fwd_api.hip and fa_fwd_kv8_api.hip have their kernel sets pinned.
-#include "fa_fwd.h"
-#include "fa_rotary.h"
-
-#include <algorithm>
+#include "fa_kvcache_append_kv8.h"
 
 namespace {
-
-// 8 elements of T (one 16-byte chunk) -> 8 e4m3 bytes:  byte = e4m3fn_rne(min(max(float(x) * inv, -448), 448)).
-// v_med3_f32 is the clamp (+-inf -> +-448, -0 keeps its sign), v_cvt_pk_fp8_f32 rounds to nearest even (subnormals included).
-template <typename T>
-__device__ __forceinline__ uint2 quantise8(uint4 w, float inv) {
-    float x[8];
-    fa::unpack8<T>(w, x);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) x[j] = __builtin_amdgcn_fmed3f(x[j] * inv, -448.0f, 448.0f);
-    int lo = __builtin_amdgcn_cvt_pk_fp8_f32(x[0], x[1], 0, false);
-    lo = __builtin_amdgcn_cvt_pk_fp8_f32(x[2], x[3], lo, true);
-    int hi = __builtin_amdgcn_cvt_pk_fp8_f32(x[4], x[5], 0, false);
-    hi = __builtin_amdgcn_cvt_pk_fp8_f32(x[6], x[7], hi, true);
-    return make_uint2((uint32_t)lo, (uint32_t)hi);
-}
 
 // One new row by one wavefront: its lanes on the row's (head, slot) items in address order (rotary_slot_to: two 16-byte chunks
 // of K, the same chunks of V; 8-byte stores).  Everything looked up per sequence -- fill level, cache entry, page, rotary
@@ -30,72 +12,33 @@ __device__ __forceinline__ uint2 quantise8(uint4 w, float inv) {
 template <typename T>
 __device__ __forceinline__ void append_row_kv8(const fa_kvcache_append_kv8_params &p, int lane, int seq, int i, int64_t k_off,
                                                int64_t v_off) {
+    fa::Kv8AppendRow<T> r;
+    if (!fa::kv8_append_row<T>(p, seq, i, k_off, v_off, r)) return;  // past the capacity: dropped (wave-uniform)
     const int slots = (p.d / 8 + 1) / 2, chunks = p.d >> 3, items = p.h_k * slots;
-    const int fill = p.cache_seqlens[seq];
-    int dst_row = fill + i;
-    if (dst_row < 0 || dst_row >= p.seqlen_cache) return;  // past the capacity: dropped (wave-uniform)
-    const int pos = (p.rotary_seqlens ? p.rotary_seqlens[seq] : fill) + i;
-    int cb = p.cache_batch_idx ? p.cache_batch_idx[seq] : seq;
-    if (p.block_table) {
-        cb = p.block_table[seq * p.block_table_batch_stride + dst_row / p.page_block_size];
-        dst_row %= p.page_block_size;
-    }
-    const T *ks_row = (const T *)p.k_new + k_off;
-    const T *vs_row = (const T *)p.v_new + v_off;
-    uint8_t *kd_row = (uint8_t *)p.k_cache + (int64_t)cb * p.kcache_batch_stride + (int64_t)dst_row * p.kcache_row_stride;
-    uint8_t *vd_row = (uint8_t *)p.v_cache + (int64_t)cb * p.vcache_batch_stride + (int64_t)dst_row * p.vcache_row_stride;
-    const int rd = p.rotary_cos ? p.rotary_dim : 0;
-    const T *cr = (const T *)p.rotary_cos + (int64_t)pos * (rd / 2);
-    const T *sr = (const T *)p.rotary_sin + (int64_t)pos * (rd / 2);
-    const float *kds = p.k_descale ? p.k_descale + seq * p.k_descale_batch_stride : nullptr;
-    const float *vds = p.v_descale ? p.v_descale + seq * p.v_descale_batch_stride : nullptr;
     for (int it = lane; it < items; it += 64) {
         const int hd = it / slots, slot = it % slots;
-        const float k_inv = 1.0f / (kds ? kds[hd * p.k_descale_head_stride] : 1.0f);
-        const float v_inv = 1.0f / (vds ? vds[hd * p.v_descale_head_stride] : 1.0f);
-        uint8_t *kd = kd_row + hd * p.kcache_head_stride;
-        fa::rotary_slot_to<T>(ks_row + hd * p.knew_head_stride, p.d, rd, p.rotary_interleaved != 0, slot, cr, sr,
-                              [&](int c, uint4 w) { *reinterpret_cast<uint2 *>(kd + c * 8) = quantise8<T>(w, k_inv); });
+        const float k_inv = 1.0f / (r.kds ? r.kds[hd * p.k_descale_head_stride] : 1.0f);
+        const float v_inv = 1.0f / (r.vds ? r.vds[hd * p.v_descale_head_stride] : 1.0f);
+        uint8_t *kd = r.kd + hd * p.kcache_head_stride;
+        fa::rotary_slot_to<T>(r.ks + hd * p.knew_head_stride, p.d, r.rd, p.rotary_interleaved != 0, slot, r.cr, r.sr,
+                              [&](int c, uint4 w) { *reinterpret_cast<uint2 *>(kd + c * 8) = fa::quantise8<T>(w, k_inv); });
         // V: the same enumeration without a rotary part (slot -> chunks 2 slot, 2 slot + 1)
-        const T *vs = vs_row + hd * p.vnew_head_stride;
-        uint8_t *vd = vd_row + hd * p.vcache_head_stride;
+        const T *vs = r.vs + hd * p.vnew_head_stride;
+        uint8_t *vd = r.vd + hd * p.vcache_head_stride;
         const int c0 = 2 * slot, c1 = 2 * slot + 1;
-        if (c0 < chunks) *reinterpret_cast<uint2 *>(vd + c0 * 8) = quantise8<T>(*reinterpret_cast<const uint4 *>(vs + c0 * 8), v_inv);
-        if (c1 < chunks) *reinterpret_cast<uint2 *>(vd + c1 * 8) = quantise8<T>(*reinterpret_cast<const uint4 *>(vs + c1 * 8), v_inv);
+        if (c0 < chunks) *reinterpret_cast<uint2 *>(vd + c0 * 8) = fa::quantise8<T>(*reinterpret_cast<const uint4 *>(vs + c0 * 8), v_inv);
+        if (c1 < chunks) *reinterpret_cast<uint2 *>(vd + c1 * 8) = fa::quantise8<T>(*reinterpret_cast<const uint4 *>(vs + c1 * 8), v_inv);
     }
 }
 
-// Dense rows (cu_seqlens_k_new == NULL): the wavefronts of a flat grid stride over the b * seqlen_new rows; ragged rows:
-// for_ragged_rows, the launch shapes of fa_kvcache_append_varlen.
+// (the rows over the wavefronts: fa::kv8_append_rows)
 template <typename T>
 __global__ __launch_bounds__(256) void kvcache_append_kv8_kernel(const fa_kvcache_append_kv8_params p) {
     const int lane = threadIdx.x & 63;
-    const bool ragged = p.cu_seqlens_k_new != nullptr;
-    // the fill levels behind the append: one entry per thread of the first workgroups (the grid holds >= b threads)
-    const int64_t gid = ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * blockDim.x + threadIdx.x;
-    if (p.seqused_out && gid < p.b) {
-        const int s = (int)gid;
-        const int len = ragged ? p.cu_seqlens_k_new[s + 1] - p.cu_seqlens_k_new[s] : p.seqlen_new;
-        p.seqused_out[s] = min(p.cache_seqlens[s] + len, p.seqlen_cache);
-    }
-    if (ragged) {
-        // (always_inline: for_ragged_rows calls its body from several places, and a call would put the params on the stack)
-        fa::for_ragged_rows(p.cu_seqlens_k_new, p.b, p.total_k_new, p.max_seqlen_k_new,
-                            [&](int seq, int i, int row) __attribute__((always_inline)) {
-            append_row_kv8<T>(p, lane, seq, i, (int64_t)row * p.knew_row_stride, (int64_t)row * p.vnew_row_stride);
-        });
-        return;
-    }
-    const int64_t rows = (int64_t)p.b * p.seqlen_new, waves = (int64_t)gridDim.x * 4;
-    const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
-    for (int64_t r = (int64_t)blockIdx.x * 4 + wave; r < rows; r += waves) {
-        const int seq = (int)(r / p.seqlen_new), i = (int)(r % p.seqlen_new);
-        append_row_kv8<T>(p, lane, seq, i, seq * p.knew_batch_stride + i * p.knew_row_stride,
-                          seq * p.vnew_batch_stride + i * p.vnew_row_stride);
-    }
+    fa::kv8_append_rows(p, [&](int seq, int i, int64_t k_off, int64_t v_off) __attribute__((always_inline)) {
+        append_row_kv8<T>(p, lane, seq, i, k_off, v_off);
+    });
 }
-
-bool misaligned(const void *ptr, uintptr_t to) { return reinterpret_cast<uintptr_t>(ptr) % to != 0; }
 
 }  // namespace
 
@@ -103,62 +46,12 @@ extern "C" {
 
 uint32_t fa_kvcache_append_kv8_params_size(void) { return (uint32_t)sizeof(fa_kvcache_append_kv8_params); }
 
-int fa_kvcache_append_kv8_validate(const fa_kvcache_append_kv8_params *p) {
-    if (!p) return FA_ERR_NULL_POINTER;
-    if (p->abi_version != FA_ABI_VERSION || p->struct_size != sizeof(fa_kvcache_append_kv8_params)) return FA_ERR_BAD_ABI;
-    if (p->dtype != FA_DTYPE_FP16 && p->dtype != FA_DTYPE_BF16) return FA_ERR_BAD_DTYPE;
-    const bool ragged = p->cu_seqlens_k_new != nullptr;
-    if (p->b <= 0 || p->h_k <= 0 || p->seqlen_cache < 0) return FA_ERR_BAD_SHAPE;
-    if (ragged ? (p->total_k_new < 0 || p->max_seqlen_k_new < 0) : p->seqlen_new < 0) return FA_ERR_BAD_SHAPE;
-    if (p->d <= 0 || p->d > 128 || p->d % 16 != 0) return FA_ERR_BAD_HEAD_DIM;  // (what fa_fwd_kv8 reads)
-    if (p->d_v != 0 && p->d_v != p->d) return FA_ERR_BAD_HEAD_DIM;
-    if (!p->cache_seqlens || (ragged && !p->seqused_out)) return FA_ERR_NULL_POINTER;
-    if (p->seqused_out == p->cache_seqlens) return FA_ERR_BAD_SHAPE;
-    const int64_t rows = ragged ? p->total_k_new : (int64_t)p->b * p->seqlen_new;
-    if (rows > 0 && (!p->k_new || !p->v_new || !p->k_cache || !p->v_cache)) return FA_ERR_NULL_POINTER;
-    if (p->block_table && (p->page_block_size <= 0 || p->cache_batch_idx)) return FA_ERR_BAD_SHAPE;
-    if (p->block_table && (p->block_table_batch_stride < 0 || p->block_table_batch_stride > 0x7fffffff)) return FA_ERR_BAD_STRIDE;
-    if (p->rotary_cos || p->rotary_sin) {
-        if (!p->rotary_cos || !p->rotary_sin) return FA_ERR_NULL_POINTER;
-        if (p->rotary_dim <= 0 || p->rotary_dim > p->d || p->rotary_dim % 16 != 0) return FA_ERR_BAD_SHAPE;
-        if (misaligned(p->rotary_cos, 16) || misaligned(p->rotary_sin, 16)) return FA_ERR_BAD_STRIDE;
-    }
-    // new rows: 16-byte chunks of 16-bit elements (the batch strides are read in the dense form only)
-    const int64_t new_strides[] = {p->knew_row_stride, p->knew_head_stride, p->vnew_row_stride, p->vnew_head_stride,
-                                   ragged ? 0 : p->knew_batch_stride, ragged ? 0 : p->vnew_batch_stride};
-    for (int64_t s : new_strides)
-        if (s % 8 != 0) return FA_ERR_BAD_STRIDE;
-    if (misaligned(p->k_new, 16) || misaligned(p->v_new, 16)) return FA_ERR_BAD_STRIDE;
-    // the cache: 8-byte stores of e4m3 bytes, strides in bytes
-    const int64_t cache_strides[] = {p->kcache_batch_stride, p->kcache_row_stride, p->kcache_head_stride,
-                                     p->vcache_batch_stride, p->vcache_row_stride, p->vcache_head_stride};
-    for (int64_t s : cache_strides)
-        if (s % 8 != 0) return FA_ERR_BAD_STRIDE;
-    if (misaligned(p->k_cache, 8) || misaligned(p->v_cache, 8)) return FA_ERR_BAD_STRIDE;
-    return FA_OK;
-}
+int fa_kvcache_append_kv8_validate(const fa_kvcache_append_kv8_params *p) { return fa::kv8_append_validate(p, false); }
 
-int fa_kvcache_append_kv8(const fa_kvcache_append_kv8_params *p, void *stream_) {
+int fa_kvcache_append_kv8(const fa_kvcache_append_kv8_params *p, void *stream) {
     const int st = fa_kvcache_append_kv8_validate(p);
     if (st != FA_OK) return st;
-    fa_kvcache_append_kv8_params kp = *p;
-    const bool ragged = kp.cu_seqlens_k_new != nullptr;
-    dim3 grid;
-    size_t smem = 0;
-    if (ragged) {
-        if (kp.b > 65535 || kp.total_k_new == 0) kp.max_seqlen_k_new = 0;  // (grid.y; no rows: the launch only writes seqused_out)
-        fa::ragged_launch_shape(kp.b, kp.total_k_new, kp.max_seqlen_k_new, kp.b, grid, smem);
-    } else {
-        const int64_t rows = (int64_t)kp.b * kp.seqlen_new;
-        if (rows == 0 && !kp.seqused_out) return FA_OK;
-        const int64_t fill_blocks = kp.seqused_out ? ((int64_t)kp.b + 255) / 256 : 0;  // (seqused_out: >= b threads)
-        grid = dim3((unsigned)std::max<int64_t>({1, std::min<int64_t>((rows + 3) / 4, 256 * 8), fill_blocks}));
-    }
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    if (kp.dtype == FA_DTYPE_FP16) hipLaunchKernelGGL(kvcache_append_kv8_kernel<_Float16>, grid, dim3(256), smem, stream, kp);
-    else hipLaunchKernelGGL(kvcache_append_kv8_kernel<__bf16>, grid, dim3(256), smem, stream, kp);
-    if (hipGetLastError() != hipSuccess) return FA_ERR_LAUNCH;
-    return FA_OK;
+    return fa::kv8_append_launch(p, kvcache_append_kv8_kernel<_Float16>, kvcache_append_kv8_kernel<__bf16>, stream);
 }
 
 }  // extern "C"

@@ -1302,6 +1302,8 @@ std::tuple<Tensor, Tensor> fwd_qv8(const Tensor &q, const Tensor &k, const Tenso
 // or ragged (total_k_new, h_k, d) with cu_seqlens_k_new -- are rotated (keys), divided by the descale of their (sequence, kv
 // head), converted to e4m3 and stored at cache_seqlens[s] + i of the batched or paged cache.  Every check runs before the one
 // launch; nothing reads device data.  Returns the new fill levels min(cache_seqlens + new rows, capacity), written by the launch.
+// A cache of the MLA shape (head_size <= 64 beside a latent / V head dim in [256, 512], the shape fwd_qv8 reads) goes to
+// fa_kvcache_append_qv8 under the same checks: k_new is the k_pe row, v_new the latent row.
 Tensor kvcache_append_kv8(const Tensor &k_cache, const Tensor &v_cache, const Tensor &k_new, const Tensor &v_new,
                           const Tensor &cache_seqlens, const Tensor &k_descale, const Tensor &v_descale,
                           const OptTensor &cu_seqlens_k_new, int64_t max_seqlen_k_new, const OptTensor &cache_batch_idx,
@@ -1325,6 +1327,11 @@ Tensor kvcache_append_kv8(const Tensor &k_cache, const Tensor &v_cache, const Te
     const int64_t num_heads_k = k_cache.size(2), head_size = k_cache.size(3);
     TORCH_CHECK(head_size <= 128 && head_size % 16 == 0,
                 "This flash attention build supports an fp8 KV cache for head_size <= 128 that is a multiple of 16, got ", head_size);
+    // the MLA shape (what fa_fwd_qv8 reads): a latent / V head dim in [256, 512] beside head_size <= 64, pages / rows / heads
+    // those of K; any other V that is not K's shape keeps its refusal below
+    const bool mla = head_size <= 64 && v_cache.size(3) >= 256 && v_cache.size(3) <= 512 && v_cache.size(3) % 16 == 0 &&
+                     v_cache.sizes().slice(0, 3) == k_cache.sizes().slice(0, 3);
+    const int64_t head_size_v = mla ? v_cache.size(3) : head_size;
     CacheRules rules;
     rules.base_grain = 8;
     rules.misaligned = "the fp8 KV cache must be 8-byte aligned with row/head/batch strides that are multiples of 8 to be appended to";
@@ -1336,9 +1343,10 @@ Tensor kvcache_append_kv8(const Tensor &k_cache, const Tensor &v_cache, const Te
     // (the batch is the number of fill levels, one at the least)
     const int64_t batch_size = std::max<int64_t>(cache_seqlens.numel(), 1);
     const CacheSide cache = check_cache(k_cache, v_cache, page_table, cache_batch_idx, cache_seqlens, c10::nullopt, batch_size, head_size,
-                                        head_size, rules);
+                                        head_size_v, rules);
     const bool ragged = cu_seqlens_k_new.has_value();
-    check_new_rows(k_new, v_new, cu_seqlens_k_new, batch_size, num_heads_k, head_size, head_size, "k_new.size", "head_size");
+    check_new_rows(k_new, v_new, cu_seqlens_k_new, batch_size, num_heads_k, head_size, head_size_v, "k_new.size",
+                   mla ? "head_size_v" : "head_size");
     if (ragged) TORCH_CHECK(max_seqlen_k_new >= 0, "max_seqlen_k_new must be non-negative");
     check_kv8_descale(k_descale, "k_descale", batch_size, num_heads_k);
     check_kv8_descale(v_descale, "v_descale", batch_size, num_heads_k);
@@ -1370,8 +1378,9 @@ Tensor kvcache_append_kv8(const Tensor &k_cache, const Tensor &v_cache, const Te
     p.k_descale_batch_stride = k_descale.stride(0); p.k_descale_head_stride = k_descale.stride(1);
     p.v_descale = static_cast<const float *>(v_descale.data_ptr());
     p.v_descale_batch_stride = v_descale.stride(0); p.v_descale_head_stride = v_descale.stride(1);
-    const int st = fa_kvcache_append_kv8(&p, current_stream(k_cache));
-    TORCH_CHECK(st == 0, "fa_kvcache_append_kv8 failed (", st, "): ", fa_strerror(st));
+    if (mla) p.d_v = (int32_t)head_size_v;
+    const int st = mla ? fa_kvcache_append_qv8(&p, current_stream(k_cache)) : fa_kvcache_append_kv8(&p, current_stream(k_cache));
+    TORCH_CHECK(st == 0, mla ? "fa_kvcache_append_qv8 failed (" : "fa_kvcache_append_kv8 failed (", st, "): ", fa_strerror(st));
     return seqused_out;
 }
 
@@ -1404,7 +1413,8 @@ std::tuple<Tensor, Tensor> fwd_kv8_step(const Tensor &q, const Tensor &k, const 
     const auto q_dtype = q.scalar_type();
     // the MLA decode shape (fa_fwd_qv8): q/k head dim <= 64 beside a V / latent head dim in [256, 512], qv optional
     const bool mla = q.size(-1) <= 64 && q.size(-1) % 16 == 0 && v.size(-1) >= 256 && v.size(-1) <= 512 && v.size(-1) % 16 == 0;
-    if (mla) {  // the quantising append serves d <= 128 with d_v = d: this shape only reads
+    if (mla) {  // the fused call only reads this shape; its step is two calls: kvcache_append_fp8 (fa_kvcache_append_qv8: k_pe
+                // rotated and quantised, the latent quantised), then this read on the fill levels that call returns
         TORCH_CHECK(!k_new.has_value() && !v_new.has_value() && !cu_seqlens_k_new.has_value(),
                     "This flash attention build does not support k_new / v_new with an fp8 KV cache of the MLA shape (head_size <= 64 "
                     "beside head_size_v in [256, 512]): it is read only.");

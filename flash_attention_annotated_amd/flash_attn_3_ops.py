@@ -79,7 +79,8 @@ def _fwd_combine(out_partial, lse_partial, out=None, out_dtype=None):
 def _kvcache_append_fp8(k_cache, v_cache, k, v, cache_seqlens, k_descale, v_descale, cu_seqlens_k_new=None, max_seqlen_k_new=None,
                         cache_batch_idx=None, page_table=None, rotary_cos=None, rotary_sin=None, rotary_seqlens=None,
                         rotary_interleaved=True):
-    """The binding's kvcache_append_fp8 (fa_kvcache_append_kv8): one launch, returns the new fill levels."""
+    """The binding's kvcache_append_fp8 (fa_kvcache_append_kv8; the MLA shape: fa_kvcache_append_qv8): one launch, returns the new
+    fill levels."""
     return _lib.binding().kvcache_append_fp8(k_cache, v_cache, k, v, cache_seqlens, k_descale, v_descale, cu_seqlens_k_new,
                                              max_seqlen_k_new, cache_batch_idx, page_table, rotary_cos, rotary_sin,
                                              rotary_seqlens, rotary_interleaved)

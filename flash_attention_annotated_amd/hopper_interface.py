@@ -204,6 +204,8 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, qv=None, rotary
     An fp8 cache (torch.float8_e4m3fn k_cache / v_cache under fp16 / bf16 q) is read through k_descale / v_descale, fp32
     (batch, nheads_k); with both given, k / v (fp16 / bf16, dense or ragged) are quantised into it in place first and
     rotary_cos / rotary_sin / rotary_seqlens apply as on a 16-bit cache (kvcache_append_fp8 below is that append alone).
+    An fp8 cache of the MLA shape (headdim <= 64 beside headdim_v in [256, 512], qv optional) is read only by this call:
+    kvcache_append_fp8 writes its rows, and the step is that call followed by this one on the fill levels it returns.
     pack_gqa: True runs the PackGQA kernel on the attention of the step -- dense or ragged (cu_seqlens_q) queries, batched or
     paged cache, split-KV -- so that a verify step of a few tokens or the decode rows of a mixed step share one pass over the
     cache per kv head; a single-token step keeps its own GQA fold and is unaffected.  False / None: unpacked, as before."""
@@ -233,7 +235,13 @@ def kvcache_append_fp8(k_cache, v_cache, k, v, cache_seqlens, k_descale, v_desca
     dequantises by.  One launch, no host sync (HIP-graph capturable).  Returns the new fill levels
     min(cache_seqlens + new rows, capacity), int32 (batch,) on the device; cache_seqlens itself is not modified.
     flash_attn_with_kvcache(q, k_cache, v_cache, k=, v=, k_descale=, v_descale=, ...) runs the same append in front of the
-    attention."""
+    attention.
+    The MLA shape -- k_cache (..., nheads_k, headdim <= 64) beside v_cache (..., nheads_k, headdim_v in [256, 512]), k the k_pe
+    rows and v the latent rows of headdim_v -- is appended by a kernel of its own under the same rules.  There the fused call
+    only reads, so a step is two calls, without a host sync in between:
+        fill = kvcache_append_fp8(k_cache, v_cache, k_pe, latent, cache_seqlens, k_descale, v_descale, rotary_cos=, ...)
+        out = flash_attn_with_kvcache(q, k_cache, v_cache, qv=, cache_seqlens=fill, k_descale=, v_descale=, ...)
+    with q rotated by the caller."""
     return torch.ops.flash_attn_3.kvcache_append_fp8(k_cache, v_cache, k, v, cache_seqlens, k_descale, v_descale,
                                                      cu_seqlens_k_new, max_seqlen_k_new, cache_batch_idx, page_table,
                                                      rotary_cos, rotary_sin, rotary_seqlens, rotary_interleaved)

@@ -19,6 +19,7 @@
  *   mha_fwd (FA3) over an fp8 KV cache, 16-bit q
  *                    hopper/flash_api.cpp:714-760, 1115-1146      fa_fwd_kv8 (k / v e4m3 bytes + k / v descale)
  *   ... with k_new / v_new, rotary (the append into that cache)   fa_kvcache_append_kv8 (16-bit rows -> e4m3 bytes)
+ *   ... the append into a cache of the MLA shape                   fa_kvcache_append_qv8
  *   error codes      standalone/src/flash_api.cu:403-426          FA_ERR_* / fa_strerror
  *
  * Conventions (same as the reference's params struct):
@@ -608,7 +609,7 @@ typedef struct fa_kvcache_append_kv8_params {
     int32_t max_seqlen_k_new; /* ragged form: upper bound of the new lengths, or 0 = not known */
     int32_t seqlen_cache;     /* capacity; paged: pages per sequence x page_block_size */
     int32_t h_k, d;
-    int32_t d_v;              /* 0 or d */
+    int32_t d_v;              /* 0 or d; fa_kvcache_append_qv8: the latent / V head dim, in [256, 512] */
     int32_t dtype;            /* of the new rows and of rotary_cos / rotary_sin: FA_DTYPE_FP16 / FA_DTYPE_BF16 */
     int32_t page_block_size;
     int32_t rotary_dim;       /* only read when rotary_cos is set */
@@ -632,6 +633,19 @@ int fa_kvcache_append_kv8(const fa_kvcache_append_kv8_params *params, void *stre
 /* Validation only; no device access. */
 int fa_kvcache_append_kv8_validate(const fa_kvcache_append_kv8_params *params);
 uint32_t fa_kvcache_append_kv8_params_size(void);
+
+/*
+ * The same append for the MLA shape of the fp8 KV cache -- the write half of what fa_fwd_qv8 reads: a rotated k_pe row (head dim
+ * d <= 64, d % 16 == 0) into k_cache and the latent row (d_v in [256, 512], d_v % 16 == 0, required here) into v_cache, as e4m3
+ * bytes, in place.  The struct, the quantisation (keys by k_descale, the latent by v_descale), the rotation of the keys, the
+ * placement, seqused_out, the alignment rules and the status codes are those of fa_kvcache_append_kv8, rule for rule
+ * (FA_ERR_BAD_HEAD_DIM for any d / d_v outside the shape above); per appended row and head d bytes of K and d_v bytes of V are
+ * written and nothing else.  One kernel, kvcache_append_qv8_kernel (csrc/fa_kvcache_append_qv8.hip): a wavefront per new row,
+ * its lanes on 64 consecutive 16-byte chunks of V per pass, the few K chunks on the lanes at the other end of the same pass.
+ */
+int fa_kvcache_append_qv8(const fa_kvcache_append_kv8_params *params, void *stream);
+/* Validation only; no device access. */
+int fa_kvcache_append_qv8_validate(const fa_kvcache_append_kv8_params *params);
 
 /* Merge of split-KV partial results given by the caller: mha_combine / flash_attn_3::fwd_combine
  * (hopper/flash_api.cpp:1569-1670, hopper/flash_fwd_combine_kernel.h).
