@@ -49,7 +49,8 @@ bool aligned(const Tensor &t) {
         if (t.stride(i) % 8 != 0) return false;
     return true;
 }
-Tensor aligned_or_copy(const Tensor &t) { return aligned(t) ? t : t.contiguous(); }
+// (clone, not contiguous(): a contiguous tensor whose base is off the boundary must move to a fresh allocation as well)
+Tensor aligned_or_copy(const Tensor &t) { return aligned(t) ? t : t.clone(at::MemoryFormat::Contiguous); }
 
 void *ptr(const OptTensor &t) { return t.has_value() ? t->data_ptr() : nullptr; }
 void *ptr(const Tensor &t) { return t.data_ptr(); }
@@ -1804,7 +1805,7 @@ std::tuple<Tensor, Tensor> cute_fwd(const Tensor &q, const Tensor &k, const Tens
 // ---- block-sparse forward of the cute surface (include/fa_fwd.h fa_fwd_block_sparse): flash_attn_func with
 // full_block_cnt / full_block_idx / mask_block_cnt / mask_block_idx.  The checks of normalize_block_sparse_tensors
 // (flash_attn/cute/block_sparsity.py:33-115) on shapes and dtypes; the lists are handed over through their strides -- a size-1
-// batch / head dimension as stride 0 -- and never read, copied or expanded here.  Allocates out and lse, nothing else (q / k / v
+// batch / head dimension as stride 0 -- and never read, copied or expanded here.  Allocates lse, and out unless the caller passes one (q / k / v
 // views whose rows are not 16-byte aligned are copied, as on every surface).
 void check_block_list(const OptTensor &cnt, const OptTensor &idx, const char *name, const Tensor &q, int64_t nm, int64_t nk) {
     TORCH_CHECK(cnt.has_value() == idx.has_value(), name, "_block_cnt and ", name, "_block_idx must be specified together");
@@ -1829,7 +1830,7 @@ std::tuple<Tensor, Tensor> cute_fwd_block_sparse(const Tensor &q_, const Tensor 
                                                  int64_t window_size_left, int64_t window_size_right, const OptTensor &learnable_sink,
                                                  double softcap, int64_t num_splits, const OptTensor &full_block_cnt,
                                                  const OptTensor &full_block_idx, const OptTensor &mask_block_cnt,
-                                                 const OptTensor &mask_block_idx) {
+                                                 const OptTensor &mask_block_idx, const OptTensor &out_) {
     CHECK_DEVICE(q_, "q"); CHECK_DEVICE(k_, "k"); CHECK_DEVICE(v_, "v");
     TORCH_CHECK(q_.dim() == 4 && k_.dim() == 4 && v_.dim() == 4, "block sparsity needs dense q (b, sq, h, d) and k / v (b, sk, h_k, d)");
     TORCH_CHECK(q_.scalar_type() == at::kHalf || q_.scalar_type() == at::kBFloat16, "inputs must be float16 or bfloat16");
@@ -1846,7 +1847,16 @@ std::tuple<Tensor, Tensor> cute_fwd_block_sparse(const Tensor &q_, const Tensor 
     check_block_list(full_block_cnt, full_block_idx, "full", q_, nm, nk);
     c10::hip::HIPGuardMasqueradingAsCUDA device_guard(q_.device());
     const Tensor q = aligned_or_copy(q_), k = aligned_or_copy(k_), v = aligned_or_copy(v_);
-    Tensor out = at::empty({b, sq, h, dv}, q.options());
+    Tensor given;  // the caller's out (as every forward entry point takes one); a view that is not aligned() is filled by a copy
+    if (out_.has_value()) {
+        given = *out_;
+        TORCH_CHECK(given.scalar_type() == q.scalar_type(), "Output must have the same dtype as inputs");
+        TORCH_CHECK(given.is_cuda() && given.stride(-1) == 1 && given.sizes() == c10::IntArrayRef({b, sq, h, dv}),
+                    "out must have shape (batch_size, seqlen_q, num_head, head_dim_v)");
+    } else {
+        given = at::empty({b, sq, h, dv}, q.options());
+    }
+    Tensor out = aligned(given) ? given : at::empty({b, sq, h, dv}, q.options());
     Tensor lse = at::empty({b, h, sq}, q.options().dtype(at::kFloat));
 
     fa_fwd_params p{};
@@ -1894,7 +1904,8 @@ std::tuple<Tensor, Tensor> cute_fwd_block_sparse(const Tensor &q_, const Tensor 
     TORCH_CHECK(st != FA_ERR_UNSUPPORTED, "fa_fwd_block_sparse: block sparsity does not go with this call (num_splits > 1, or a head dim "
                 "of V above 256): ", fa_strerror(st));
     TORCH_CHECK(st == 0, "fa_fwd_block_sparse failed (", st, "): ", fa_strerror(st));
-    return {out, lse};
+    if (!out.is_same(given)) given.copy_(out);
+    return {given, lse};
 }
 
 // dsink (num_heads,) fp32 from the LSE of a forward with a sink and the softmax_d of its fa_bwd (include/fa_bwd.h)
@@ -2119,7 +2130,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("max_seqlen_q"), py::arg("max_seqlen_k"), py::arg("page_table"), py::arg("softmax_scale"), py::arg("is_causal"),
           py::arg("window_size_left"), py::arg("window_size_right"), py::arg("learnable_sink"), py::arg("softcap"),
           py::arg("num_splits"), py::arg("pack_gqa") = py::none());
-    m.def("cute_fwd_block_sparse", &cute_fwd_block_sparse, "cute surface forward restricted to listed 128 x 128 blocks");
+    m.def("cute_fwd_block_sparse", &cute_fwd_block_sparse, "cute surface forward restricted to listed 128 x 128 blocks", py::arg("q"),
+          py::arg("k"), py::arg("v"), py::arg("softmax_scale"), py::arg("causal"), py::arg("window_size_left"), py::arg("window_size_right"),
+          py::arg("learnable_sink"), py::arg("softcap"), py::arg("num_splits"), py::arg("full_block_cnt"), py::arg("full_block_idx"),
+          py::arg("mask_block_cnt"), py::arg("mask_block_idx"), py::arg("out") = py::none());
     m.def("cute_bwd", &cute_bwd, "cute surface backward: (dq, dk, dv, dsink)");
     m.def("cute_bwd_block_sparse", &cute_bwd_block_sparse, "cute surface backward over listed 128 x 128 blocks: (dq, dk, dv, dsink)");
     m.def("sink_grad", &sink_grad, "gradient of a learnable sink from softmax_lse and softmax_d");

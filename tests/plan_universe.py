@@ -203,6 +203,13 @@ AUX = {
     "expand_fp8_kernel": ("tests/test_fp8_fa3_gpu.py::test_fp8_expansion_path_equals_bf16_path", None),
 }
 
+# The kernels of AUX that take strides of their own for the caller's tensors -> the GPU test that runs them on strided operands
+# (bit-equality with the contiguous call, sentinels around the cache views).  Beside AUX, not in it: that test compares with the
+# contiguous call, not with a reference, so AUX keeps naming where the kernel's effect is compared with one.
+AUX_STRIDED = {kernel: "tests/test_layout_parity_gpu.py::test_aux_layout_parity"
+               for kernel in ("kvcache_append_kernel", "kvcache_append_varlen_kernel", "rotary_kernel", "rotary_varlen_kernel")}
+AUX_STRIDED["combine_splits_kernel"] = "tests/test_layout_parity_gpu.py::test_fwd_layout_parity"
+
 
 def case_id(form, epilogue, dtype):
     """"<form>-<type>" for the direct case (the ids this table had before it knew epilogues), "<form>-partial-<type>"."""

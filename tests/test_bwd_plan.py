@@ -26,6 +26,7 @@ import threading
 
 import pytest
 
+import layouts
 from flash_attention_annotated_amd import _lib
 from bwd_plan_universe import CASES, DTYPES, LOOP_SEGMENTS, SINK_KEY, UNIVERSE, UNREACHABLE, segments, sequences
 from bwd_run_model import dkdv_steps, dq_steps, neighbours, normalize_window, runs
@@ -170,6 +171,34 @@ def test_universe_case_is_planned_on_its_plan(built_lib, name):
         p = _case_params(case, DT[dt])
         assert built_lib.fa_bwd_validate(ctypes.byref(p)) == 0
         assert built_lib.fa_bwd_plan_name(ctypes.byref(p)).decode() == plan
+
+
+def _set_layout_strides(p, case, assignment):
+    """The eight stride triples of the mixed assignment `assignment` (tests/layouts.py) in place of the contiguous ones."""
+    a = layouts.ASSIGNMENTS[assignment]
+    dv = case.get("dv", case["d"])
+    lq, lk = ((sum(case["lens_q"]),), (sum(case["lens_k"]),)) if "lens_q" in case else ((case["b"], case["sq"]), (case["b"], case["sk"]))
+    q, k, v, o = (*lq, case["h"], case["d"]), (*lk, case["hk"], case["d"]), (*lk, case["hk"], dv), (*lq, case["h"], dv)
+    for n, shape in dict(q=q, k=k, v=v, o=o, do=o, dq=q, dk=k, dv=v).items():
+        st = layouts.geometry(shape, 2, a[n])[2]
+        for field, stride in zip(("batch", "row", "head"), st if len(shape) == 4 else (0, *st)):
+            setattr(p, f"{n}_{field}_stride", stride)
+
+
+# layouts plan_bwd legitimately moves to other kernels: (case, assignment) -> (plan, the rule's text).  None: plan_bwd reads no stride.
+LAYOUT_MOVES = {}
+
+
+@pytest.mark.parametrize("assignment", range(len(layouts.ASSIGNMENTS)))
+@pytest.mark.parametrize("name", list(CASES))
+def test_universe_case_keeps_its_plan_on_strided_operands(built_lib, name, assignment):
+    """fa_bwd_plan_name answers the case's plan when its strides are those of a mixed assignment of tests/layouts.py."""
+    plan, case = CASES[name]
+    for dt in DTYPES:
+        p = _case_params(case, DT[dt])
+        _set_layout_strides(p, case, assignment)
+        assert built_lib.fa_bwd_validate(ctypes.byref(p)) == 0
+        assert built_lib.fa_bwd_plan_name(ctypes.byref(p)).decode() == LAYOUT_MOVES.get((name, assignment), (plan,))[0]
 
 
 def test_every_distinct_plan_has_a_case():

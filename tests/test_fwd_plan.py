@@ -8,9 +8,10 @@ import threading
 import pytest
 
 from flash_attention_annotated_amd import _lib
+import layouts
 import plan_universe
 from parity_helpers import plan_key, sparse_lists
-from plan_universe import AUX, EPILOGUES, FORMS, FP8_FORM, UNIVERSE, UNREACHABLE, cases, case_id
+from plan_universe import AUX, AUX_STRIDED, EPILOGUES, FORMS, FP8_FORM, UNIVERSE, UNREACHABLE, cases, case_id
 
 ADDR = 0x10000  # an aligned dummy address: nothing is dereferenced
 
@@ -263,6 +264,16 @@ def test_every_other_forward_kernel_is_named_in_aux():
     assert compiled == listed, (sorted(compiled - listed, key=str), sorted(listed - compiled, key=str))
 
 
+@pytest.mark.parametrize("kernel", list(AUX_STRIDED))
+def test_aux_strided_test_exists(kernel):
+    import importlib
+    assert kernel in AUX
+    path, _, name = AUX_STRIDED[kernel].partition("::")
+    module = importlib.import_module(path[len("tests/"):-len(".py")])
+    assert callable(getattr(module, name, None)), f"{AUX_STRIDED[kernel]} does not exist"
+    assert "gpu" in [m.name for m in [getattr(module, "pytestmark", None)] if m is not None]
+
+
 @pytest.mark.parametrize("kernel", list(AUX))
 def test_aux_test_exists(kernel):
     import importlib
@@ -336,6 +347,55 @@ def test_universe_case_is_planned_on_its_kernel(built_lib, form, case):
             assert splits == 3 and -(-sk // 64) // splits >= 3, name
 
 
+def _set_layout_strides(p, case, assignment, itemsize=2, names=("q", "k", "v", "o", "qv")):
+    """The strides of the mixed assignment `assignment` (tests/layouts.py) in place of the contiguous ones."""
+    a = layouts.ASSIGNMENTS[assignment]
+    b, dv, paged = case["b"], case.get("dv", case["d"]), case["api"] == "fa2_paged"
+    kv = (b * -(-case["sk"] // 256), 256) if paged else (b, case["sk"])
+    shapes = dict(q=(b, case["sq"], case["h"], case["d"]), k=(*kv, case["hk"], case["d"]), v=(*kv, case["hk"], dv),
+                  o=(b, case["sq"], case["h"], dv), qv=(b, case["sq"], case["h"], dv))
+    for n in names:
+        if n == "qv" and not case.get("qv"):
+            continue
+        key = f"{n}_pages" if paged and n in "kv" else n
+        st = layouts.geometry(shapes[n], 2 if n == "o" and itemsize == 1 else itemsize, a[key])[2]
+        for field, stride in zip(("batch", "row", "head"), st):
+            setattr(p, f"{n}_{field}_stride", stride)
+
+
+# layouts the routing legitimately moves to another form: (form, epilogue, assignment) -> (form it moves to, the rule's text).
+# None today: at the universe's shapes the extent guards of persist_ok / d256_ok (32-bit offsets) hold for every layout.
+LAYOUT_MOVES = {}
+
+
+@pytest.mark.parametrize("assignment", range(len(layouts.ASSIGNMENTS)))
+@pytest.mark.parametrize("form,case", [(f, c) for f, c in PLANNED if c["api"] != "bs"], ids=lambda x: x if isinstance(x, str) else "")
+def test_universe_case_keeps_its_plan_on_strided_operands(built_lib, form, case, assignment):
+    """fa_fwd_plan_name answers the same text when the strides of a universe case are those of a mixed assignment of
+    tests/layouts.py (LAYOUT_MOVES lists the exceptions with their rule; tests/test_layout_parity_gpu.py runs them)."""
+    form, ep = (form[:-len(" partial")], "partial") if form.endswith(" partial") else (form, "direct")
+    for dt, dtype in _dtypes(form):
+        p = _case_params(case, dtype)
+        if dt == "fp8":  # (the bindings always hand over the descales' own strides)
+            for n in "qkv":
+                setattr(p, f"{n}_descale", ADDR)
+                setattr(p, f"{n}_descale_batch_stride", case["hk"])
+                setattr(p, f"{n}_descale_head_stride", 1)
+        want = built_lib.fa_fwd_plan_name(ctypes.byref(p), 256).decode()
+        _set_layout_strides(p, case, assignment, 1 if dt == "fp8" else 2)
+        if dt == "fp8":  # a row-padded, a transposed and a padded transposed table, as tests/test_layout_parity_gpu.py::_descale
+            for n, (bs, hs) in zip("qkv", ((case["hk"] + 3, 1), (1, case["b"] + 3), (1, case["b"] + 3))):
+                setattr(p, f"{n}_descale_batch_stride", bs)
+                setattr(p, f"{n}_descale_head_stride", hs)
+        assert built_lib.fa_fwd_validate(ctypes.byref(p)) == 0
+        name = built_lib.fa_fwd_plan_name(ctypes.byref(p), 256).decode()
+        moved = LAYOUT_MOVES.get((form, ep, assignment))
+        if moved:
+            assert plan_key(name, dt) == (dt, moved[0], ep), name
+        else:
+            assert name == want, f"{want!r} on contiguous operands"
+
+
 def _sparse_params(case):
     """fa_block_sparse_params of a universe block-sparse case: dummy list addresses, the strides of contiguous (b, h, nm[, nk])."""
     nm, nk = -(-case["sq"] // 128), -(-case["sk"] // 128)
@@ -345,6 +405,19 @@ def _sparse_params(case):
         getattr(s, f"{name}_cnt_stride")[:] = [case["h"] * nm, nm, 1, 0]
         getattr(s, f"{name}_idx_stride")[:] = [case["h"] * nm * nk, nm * nk, nk, 1]
     return s
+
+
+@pytest.mark.parametrize("assignment", range(len(layouts.ASSIGNMENTS)))
+@pytest.mark.parametrize("form", [f for f in FORMS if f.startswith("bs_fwd_kernel ")])
+def test_block_sparse_case_validates_on_strided_operands(built_lib, form, assignment):
+    """The block-sparse cases have no fa_fwd_params plan (one kernel shape): fa_fwd_block_sparse_validate accepts their params with
+    the strides of each mixed assignment, as it does the contiguous ones."""
+    case = FORMS[form]["direct"]
+    for _, dtype in _dtypes(form):
+        p = _case_params(case, dtype)
+        assert built_lib.fa_fwd_block_sparse_validate(ctypes.byref(p), ctypes.byref(_sparse_params(case)), None) == 0
+        _set_layout_strides(p, case, assignment)
+        assert built_lib.fa_fwd_block_sparse_validate(ctypes.byref(p), ctypes.byref(_sparse_params(case)), None) == 0
 
 
 @pytest.mark.parametrize("form,ep", list(UNREACHABLE), ids=[case_id(f, ep, "") for f, ep in UNREACHABLE])

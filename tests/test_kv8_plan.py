@@ -9,6 +9,7 @@ import re
 import pytest
 
 import kv8_plan_universe as U
+import layouts
 from device_asm import TYPES, fp8_cache_kernels, kernel_bodies
 from flash_attention_annotated_amd import _lib
 from parity_helpers import plan_key
@@ -91,6 +92,35 @@ def test_universe_case_is_planned_on_its_key(form, ep, dt, case):
     assert form.startswith(case["kernel"] + "_fwd_kernel")
     assert int(re.search(r"block_m=(\d+)", name).group(1)) == U.block_m(case["kernel"])
     assert int(re.search(r"splits=(\d+)", name).group(1)) == case["splits"] == (3 if ep == "partial" else 1)
+
+
+# layouts either plan legitimately moves to another form: (form, epilogue, assignment) -> (form, the rule's text).  None: plan_kv8 /
+# plan_qv8 read no stride.
+LAYOUT_MOVES = {}
+
+
+@pytest.mark.parametrize("assignment", range(len(layouts.ASSIGNMENTS)))
+@pytest.mark.parametrize("form,ep,dt,case", CASES, ids=IDS)
+def test_universe_case_keeps_its_plan_on_strided_operands(form, ep, dt, case, assignment):
+    """The plan text is the same when the strides of a case are those of a mixed assignment of tests/layouts.py: q / o / qv in
+    elements, the cache in bytes, the descales transposed."""
+    lib = _lib.load()
+    p = _case_params(case, dt)
+    validate, plan_name = ((lib.fa_fwd_kv8_validate, lib.fa_fwd_kv8_plan_name) if case["kernel"] == "kv8" else
+                           (lib.fa_fwd_qv8_validate, lib.fa_fwd_qv8_plan_name))
+    want = plan_name(p, 256).decode()
+    a, b, dv = layouts.ASSIGNMENTS[assignment], case["b"], case.get("dv", case["d"])
+    shapes = dict(q=(b, case["sq"], case["h"], case["d"]), k=(b, case["cap"], case["hk"], case["d"]), v=(b, case["cap"], case["hk"], dv),
+                  o=(b, case["sq"], case["h"], dv), qv=(b, case["sq"], case["h"], dv))
+    for n, shape in shapes.items():
+        if n == "qv" and case["kernel"] != "qv8":
+            continue
+        for field, stride in zip(("batch", "row", "head"), layouts.geometry(shape, 1 if n in "kv" else 2, a[n])[2]):
+            setattr(p, f"{n}_{field}_stride", stride)
+    p.k_descale_batch_stride, p.k_descale_head_stride, p.v_descale_batch_stride, p.v_descale_head_stride = 1, b + 3, case["hk"] + 3, 1
+    assert validate(p) == 0
+    name = plan_name(p, 256).decode()
+    assert LAYOUT_MOVES.get((form, ep, assignment)) is None and name == want, f"{name!r}, {want!r} on contiguous operands"
 
 
 # ---- geometry -----------------------------------------------------------------------------------------------------------------
