@@ -62,15 +62,6 @@ int head_dim_tile_b(int d) {
     return 256;
 }
 
-// grid of decode_block(): whole units of `blocks` workgroups for as many (batch, head) units as deal evenly over the 8 XCDs,
-// the remaining heads block by block (any head count loads the XCDs equally; fewer than 16 units: everything block by block)
-int64_t unit_grid(int64_t tiles, int blocks, int32_t &whole_slots) {
-    const int64_t units = tiles / blocks;
-    const int64_t ws = units >= 16 ? units / 8 * blocks : 0;
-    whole_slots = (int32_t)ws;
-    return 8 * (ws + (tiles - ws * 8 + 7) / 8);
-}
-
 // ---- backward routing ---------------------------------------------------------------------------------------------------
 // plan_bwd() is the one place that decides which instantiation of each of the three kernels a problem runs.  Host code without
 // HIP calls: fa_bwd launches from the plan, fa_bwd_plan_name / fa_bwd_last_plan_name (the test hooks, tests/test_bwd_plan.py)
@@ -155,25 +146,12 @@ int run_bwd(const BwdPlan &pl, fa::BParams bp, int rows_q_max, int rows_k_max, h
     if (pl.tile != D || pl.softcap != SOFTCAP || pl.dropout != DROPOUT || pl.lpr != LPR || pl.nbq != NBQ ||
         (pl.nbk != 1 && pl.nbk != NBK2) || pl.two_parts != (D == 256))
         return FA_ERR_UNSUPPORTED;
+    int st;
     // 1. D = rowsum(dO * O)
-    if (pl.run_dot) {
-        const int64_t rows = bp.cu_seqlens_q ? (int64_t)bp.total_q : (int64_t)bp.b * bp.seqlen_q;
-        const int64_t items = rows * bp.h;
-        const int per_block = 256 / LPR;
-        const int grid = (int)std::min<int64_t>((items + per_block - 1) / per_block, 256 * 16);
-        hipLaunchKernelGGL((fa::bwd_dot_kernel<T, LPR>), dim3(grid), dim3(256), 0, stream, bp);
-        if (hipGetLastError() != hipSuccess) return FA_ERR_LAUNCH;
-    }
+    if (pl.run_dot && (st = fa::bwd_launch_dot(bp, pl.dtype, D, stream)) != FA_OK) return st;
     // 2. dK, dV
     if (pl.run_dkdv) {
-        bp.num_blocks = (rows_k_max + 128 * pl.nbk - 1) / (128 * pl.nbk);
-        const int64_t tiles = (int64_t)bp.num_blocks * bp.h_k * bp.b;
-        if (tiles > 0x7fffffff) return FA_ERR_BAD_SHAPE;
-        bp.num_tiles = (int32_t)tiles;
-        const int64_t grid = unit_grid(tiles, bp.num_blocks, bp.whole_slots);
-        if (grid > 0x7fffffff) return FA_ERR_BAD_SHAPE;
-        bp.grid = (int32_t)grid;
-        int st;
+        if ((st = fa::bwd_set_grid(bp, (rows_k_max + 128 * pl.nbk - 1) / (128 * pl.nbk), bp.h_k)) != FA_OK) return st;
         if constexpr (D == 128 && !SOFTCAP && !DROPOUT) {
             st = pl.deffk == 96 ? fa::launch_kernel<fa::bwd_dkdv_kernel<T, D, 1, false, false, 96>>(fa::smem_bytes_dkdv<D>(), bp.grid, 256, stream, bp)
                : pl.deffk == D  ? fa::launch_kernel<fa::bwd_dkdv_kernel<T, D, 1, false, false>>(fa::smem_bytes_dkdv<D>(), bp.grid, 256, stream, bp)
@@ -203,14 +181,7 @@ int run_bwd(const BwdPlan &pl, fa::BParams bp, int rows_q_max, int rows_k_max, h
     }
     // 3. dQ
     if (pl.run_dq) {
-        bp.num_blocks = (rows_q_max + 128 * NBQ - 1) / (128 * NBQ);
-        const int64_t tiles = (int64_t)bp.num_blocks * bp.h * bp.b;
-        if (tiles > 0x7fffffff) return FA_ERR_BAD_SHAPE;
-        bp.num_tiles = (int32_t)tiles;
-        const int64_t grid = unit_grid(tiles, bp.num_blocks, bp.whole_slots);
-        if (grid > 0x7fffffff) return FA_ERR_BAD_SHAPE;
-        bp.grid = (int32_t)grid;
-        int st;
+        if ((st = fa::bwd_set_grid(bp, (rows_q_max + 128 * NBQ - 1) / (128 * NBQ), bp.h)) != FA_OK) return st;
         if constexpr (D == 128 && !SOFTCAP && !DROPOUT) {
             st = pl.deffq == 96 ? fa::launch_kernel<fa::bwd_dq_kernel<T, D, NBQ, false, false, 96>>(fa::smem_bytes_dq<D>(), bp.grid, 256, stream, bp)
                : pl.deffq == D  ? fa::launch_kernel<fa::bwd_dq_kernel<T, D, NBQ, false, false>>(fa::smem_bytes_dq<D>(), bp.grid, 256, stream, bp)
@@ -301,7 +272,21 @@ int bwd_launch_dot(const BParams &bp, int32_t dtype, int tile, hipStream_t strea
     return hipGetLastError() == hipSuccess ? FA_OK : FA_ERR_LAUNCH;
 }
 
-int64_t bwd_unit_grid(int64_t tiles, int blocks, int32_t &whole_slots) { return unit_grid(tiles, blocks, whole_slots); }
+// grid of decode_block(): whole units of `blocks` workgroups for as many (batch, head) units as deal evenly over the 8 XCDs,
+// the remaining heads block by block (any head count loads the XCDs equally; fewer than 16 units: everything block by block)
+int bwd_set_grid(BParams &bp, int64_t blocks, int64_t heads) {
+    const int64_t tiles = blocks * heads * bp.b;
+    if (tiles > 0x7fffffff) return FA_ERR_BAD_SHAPE;
+    bp.num_blocks = (int32_t)blocks;
+    bp.num_tiles = (int32_t)tiles;
+    const int64_t units = tiles / blocks;
+    const int64_t ws = units >= 16 ? units / 8 * blocks : 0;
+    const int64_t grid = 8 * (ws + (tiles - ws * 8 + 7) / 8);
+    if (grid > 0x7fffffff) return FA_ERR_BAD_SHAPE;
+    bp.whole_slots = (int32_t)ws;
+    bp.grid = (int32_t)grid;
+    return FA_OK;
+}
 
 void bwd_set_last_plan_text(const char *text) {
     t_last_plan_set = false;

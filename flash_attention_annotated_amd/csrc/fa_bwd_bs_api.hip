@@ -20,18 +20,6 @@ int launch_bs_bwd(bool softcap, bool dkdv, const fa::BsBwdParams &bp, hipStream_
                    : fa::launch_kernel<fa::bs_bwd_dq_kernel<T, D, false>>(fa::smem_bytes_bs_dq<D>(), bp.p.grid, 256, stream, bp);
 }
 
-// one work item per (batch, head, block): decode_block()'s grid
-int set_grid(fa::BParams &p, int64_t blocks, int64_t heads) {
-    const int64_t tiles = blocks * heads * p.b;
-    if (tiles > 0x7fffffff) return FA_ERR_BAD_SHAPE;
-    p.num_blocks = (int32_t)blocks;
-    p.num_tiles = (int32_t)tiles;
-    const int64_t grid = fa::bwd_unit_grid(tiles, p.num_blocks, p.whole_slots);
-    if (grid > 0x7fffffff) return FA_ERR_BAD_SHAPE;
-    p.grid = (int32_t)grid;
-    return FA_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -100,10 +88,10 @@ int fa_bwd_block_sparse(const fa_bwd_params *p, const fa_block_sparse_params *s,
     int rc;
     if (run_dot && (rc = fa::bwd_launch_dot(bp.p, p->dtype, tile, stream)) != FA_OK) return rc;
     if (run_dkdv) {
-        if ((rc = set_grid(bp.p, nk, p->h_k)) != FA_OK || (rc = launch(true)) != FA_OK) return rc;
+        if ((rc = fa::bwd_set_grid(bp.p, nk, p->h_k)) != FA_OK || (rc = launch(true)) != FA_OK) return rc;
     }
     if (run_dq) {
-        if ((rc = set_grid(bp.p, nm, p->h)) != FA_OK || (rc = launch(false)) != FA_OK) return rc;
+        if ((rc = fa::bwd_set_grid(bp.p, nm, p->h)) != FA_OK || (rc = launch(false)) != FA_OK) return rc;
     }
     return FA_OK;
 }

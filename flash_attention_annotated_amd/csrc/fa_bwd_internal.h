@@ -19,8 +19,9 @@ void bwd_fill_params(const fa_bwd_params *p, BParams &bp);
 // D = rowsum(dO * O) for all rows: bwd_dot_kernel<T, LPR> of head-dim tile `tile` (LPR = min(tile / 8, 32)).  FA_OK / FA_ERR_LAUNCH.
 int bwd_launch_dot(const BParams &bp, int32_t dtype, int tile, hipStream_t stream);
 
-// Grid of decode_block() for `tiles` work items in units of `blocks` (fa_bwd_api.hip unit_grid).
-int64_t bwd_unit_grid(int64_t tiles, int blocks, int32_t &whole_slots);
+// The launch fields of decode_block()'s grid, one work item per (batch, head, block): num_blocks = blocks, num_tiles =
+// blocks * heads * b, whole_slots and grid.  FA_OK, or FA_ERR_BAD_SHAPE when a count does not fit 31 bits.
+int bwd_set_grid(BParams &bp, int64_t blocks, int64_t heads);
 
 // What fa_bwd_last_plan_name() answers for the calling thread until its next fa_bwd / fa_bwd_block_sparse; NULL or "" = nothing.
 void bwd_set_last_plan_text(const char *text);

@@ -385,62 +385,46 @@ __global__ __launch_bounds__(256, 1) void bwd_dkdv_kernel(const BParams p) {
     // ---- Q / dO tile staging: rows clamped into the sequence (clamped rows are masked).  LDS-DMA
     //      (global_load_lds_dwordx4, no staging registers, swizzle applied on the source side: see
     //      fa_fwd_kernel_w64.h), 2 / 4 / 8 pieces per wave at head-dim tiles 64 / 128 / 256. ------------------------------
-    constexpr bool DMA = LD_PER_THREAD <= 8;   // (round 3: the 256 tile's 8 pieces per wave go by LDS-DMA too)
-    constexpr int NSTAGE = DMA ? 1 : LD_PER_THREAD;
-    u32x4 qreg[NSTAGE], greg[NSTAGE];
+    static_assert(LD_PER_THREAD <= 8, "lds_dma pieces per wave");
     float stat_reg = 0.f;
     auto tile_head = [&](int it) { return kv_head * p.h_ratio + it / num_m; };
     auto tile_row0 = [&](int it) { return (m_min + it % num_m) * BM; };
     int dma_row[LD_PER_THREAD], dma_col[LD_PER_THREAD], dma_colv[LD_PER_THREAD];
     uint32_t q_off[LD_PER_THREAD], g_off[LD_PER_THREAD];  // byte offsets of this lane's chunks inside an in-range tile
     const int q_rs = (int)p.q_row_stride, g_rs = (int)p.do_row_stride;  // host guarantees < 2^24
-    if constexpr (DMA) {
 #pragma unroll
-        for (int i = 0; i < LD_PER_THREAD; ++i) {
-            const int slot = wave * (LD_PER_THREAD * 64) + i * 64 + lane;  // 16-byte slot inside the tile image
-            const int row = slot / CH_PER_ROW;
-            int ch;  // inverse of lds_off<D>: the chunk stored at this slot
-            if constexpr (D == 64) ch = (slot % CH_PER_ROW) ^ ((((row >> 1) & 1) << 2) | ((row >> 2) & 3));
-            else ch = (slot % CH_PER_ROW) ^ (((row & 3) << 2) | ((row >> 2) & 3));
-            dma_row[i] = row;
-            dma_col[i] = (ch * 8 < p.d) ? ch * 8 : 0;
-            // dO has d_v columns (= d unless the FA3 headdim_v differs: wide tile only, no second table elsewhere)
-            dma_colv[i] = D == 256 ? ((ch * 8 < p.d_v) ? ch * 8 : 0) : dma_col[i];
-            q_off[i] = (uint32_t)(row * q_rs + dma_col[i]) * 2u;
-            g_off[i] = (uint32_t)(row * g_rs + dma_colv[i]) * 2u;
-        }
+    for (int i = 0; i < LD_PER_THREAD; ++i) {
+        const int slot = wave * (LD_PER_THREAD * 64) + i * 64 + lane;  // 16-byte slot inside the tile image
+        const int row = slot / CH_PER_ROW;
+        int ch;  // inverse of lds_off<D>: the chunk stored at this slot
+        if constexpr (D == 64) ch = (slot % CH_PER_ROW) ^ ((((row >> 1) & 1) << 2) | ((row >> 2) & 3));
+        else ch = (slot % CH_PER_ROW) ^ (((row & 3) << 2) | ((row >> 2) & 3));
+        dma_row[i] = row;
+        dma_col[i] = (ch * 8 < p.d) ? ch * 8 : 0;
+        // dO has d_v columns (= d unless the FA3 headdim_v differs: wide tile only, no second table elsewhere)
+        dma_colv[i] = D == 256 ? ((ch * 8 < p.d_v) ? ch * 8 : 0) : dma_col[i];
+        q_off[i] = (uint32_t)(row * q_rs + dma_col[i]) * 2u;
+        g_off[i] = (uint32_t)(row * g_rs + dma_colv[i]) * 2u;
     }
     const uint32_t lds_wave = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char *)smem + wave * (LD_PER_THREAD * 1024);
     auto load_tile = [&](int it, int buf) {
         const int head = tile_head(it), row0 = tile_row0(it);
         const T *qp = (const T *)p.q + sq_.q_base + (int64_t)head * p.q_head_stride;
         const T *gp = (const T *)p.dout + sq_.do_base + (int64_t)head * p.do_head_stride;
-        if constexpr (DMA) {
-            const T *qt = qp + (int64_t)row0 * p.q_row_stride, *gt = gp + (int64_t)row0 * p.do_row_stride;  // wave-uniform
-            if (row0 + BM <= sq) {
-                lds_dma<LD_PER_THREAD>(lds_wave + buf * TILE_BYTES, qt, q_off);
-                lds_dma<LD_PER_THREAD>(lds_wave + (2 + buf) * TILE_BYTES, gt, g_off);
-            } else {
-                uint32_t qo[LD_PER_THREAD], go[LD_PER_THREAD];
-#pragma unroll
-                for (int i = 0; i < LD_PER_THREAD; ++i) {
-                    const int rel = min(row0 + dma_row[i], sq - 1) - row0;
-                    qo[i] = (uint32_t)(rel * q_rs + dma_col[i]) * 2u;
-                    go[i] = (uint32_t)(rel * g_rs + dma_colv[i]) * 2u;
-                }
-                lds_dma<LD_PER_THREAD>(lds_wave + buf * TILE_BYTES, qt, qo);
-                lds_dma<LD_PER_THREAD>(lds_wave + (2 + buf) * TILE_BYTES, gt, go);
-            }
+        const T *qt = qp + (int64_t)row0 * p.q_row_stride, *gt = gp + (int64_t)row0 * p.do_row_stride;  // wave-uniform
+        if (row0 + BM <= sq) {
+            lds_dma<LD_PER_THREAD>(lds_wave + buf * TILE_BYTES, qt, q_off);
+            lds_dma<LD_PER_THREAD>(lds_wave + (2 + buf) * TILE_BYTES, gt, g_off);
         } else {
+            uint32_t qo[LD_PER_THREAD], go[LD_PER_THREAD];
 #pragma unroll
-            for (int i = 0; i < NSTAGE; ++i) {
-                const int c = tid + i * NT;
-                const int row = min(row0 + c / CH_PER_ROW, sq - 1);
-                const int ch = c % CH_PER_ROW;
-                const int col = (ch * 8 < p.d) ? ch * 8 : 0, colg = (ch * 8 < p.d_v) ? ch * 8 : 0;
-                qreg[i] = *(const u32x4 *)(qp + (int64_t)row * p.q_row_stride + col);
-                greg[i] = *(const u32x4 *)(gp + (int64_t)row * p.do_row_stride + colg);
+            for (int i = 0; i < LD_PER_THREAD; ++i) {
+                const int rel = min(row0 + dma_row[i], sq - 1) - row0;
+                qo[i] = (uint32_t)(rel * q_rs + dma_col[i]) * 2u;
+                go[i] = (uint32_t)(rel * g_rs + dma_colv[i]) * 2u;
             }
+            lds_dma<LD_PER_THREAD>(lds_wave + buf * TILE_BYTES, qt, qo);
+            lds_dma<LD_PER_THREAD>(lds_wave + (2 + buf) * TILE_BYTES, gt, go);
         }
         if (tid < 2 * BM) {  // threads 0..63: LSE (log2 units), 64..127: D
             const int row = min(row0 + (tid & (BM - 1)), sq - 1);
@@ -452,23 +436,14 @@ __global__ __launch_bounds__(256, 1) void bwd_dkdv_kernel(const BParams p) {
             }
         }
     };
-    auto store_tile = [&](int buf) {
-        if constexpr (!DMA) {
-#pragma unroll
-            for (int i = 0; i < NSTAGE; ++i) {
-                const int c = tid + i * NT;
-                const int off = lds_off<D>(c / CH_PER_ROW, c % CH_PER_ROW);
-                *(u32x4 *)(smem + buf * TILE_BYTES + off) = qreg[i];
-                *(u32x4 *)(smem + (2 + buf) * TILE_BYTES + off) = greg[i];
-            }
-        }
+    auto store_stats = [&](int buf) {
         if (tid < BM) lse_s[buf * BM + tid] = stat_reg;
         else if (tid < 2 * BM) dsum_s[buf * BM + tid - BM] = stat_reg;
     };
 
     if (total_it > 0) {
         load_tile(0, 0);
-        store_tile(0);
+        store_stats(0);
     }
     __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): see fa_fwd_kernel.h
     tile_barrier<0>();                   // asm LDS-DMA pieces landed + workgroup barrier
@@ -479,7 +454,7 @@ __global__ __launch_bounds__(256, 1) void bwd_dkdv_kernel(const BParams p) {
         // the generated asm block (fa_bwd_loop_gen.h; same LDS layout and barrier protocol, so the four waves choose
         // independently).  The tile behind a run must belong to the same head (the block prefetches it through the head's
         // buffer descriptors); the run's tiles lie fully inside the sequence.
-        if constexpr ((D == 128 || D == 64) && NB == 1 && !SOFTCAP && !DROPOUT && DMA && PART == 0 && !(FA_BWD_ABLATE & 1)) {
+        if constexpr ((D == 128 || D == 64) && NB == 1 && !SOFTCAP && !DROPOUT && PART == 0 && !(FA_BWD_ABLATE & 1)) {
             const int row0 = tile_row0(it);
             const int left = num_m - it % num_m;  // tiles of this head from `it` on
             int hi_row = sq - BM;
@@ -696,7 +671,7 @@ __global__ __launch_bounds__(256, 1) void bwd_dkdv_kernel(const BParams p) {
             }
         }
 
-        if (has_next) store_tile(cur ^ 1);
+        if (has_next) store_stats(cur ^ 1);
         tile_barrier<0>();  // next tile's LDS-DMA landed (vmcnt(0)), LDS writes visible, workgroup barrier
     }
 
@@ -841,74 +816,44 @@ __global__ __launch_bounds__(256, 1) void bwd_dq_kernel(const BParams p) {
     }
 
     // ---- K/V staging: clamped rows, by LDS-DMA (2 / 4 / 8 pieces per wave at head-dim tiles 64 / 128 / 256) ----------
-    constexpr bool DMA = LD_PER_THREAD <= 8;   // (round 3: the 256 tile's 8 pieces per wave go by LDS-DMA too)
-    constexpr int NSTAGE = DMA ? 1 : LD_PER_THREAD;
-    u32x4 kreg[NSTAGE], vreg[NSTAGE];
+    static_assert(LD_PER_THREAD <= 8, "lds_dma pieces per wave");
     int dma_row[LD_PER_THREAD], dma_col[LD_PER_THREAD], dma_colv[LD_PER_THREAD];
     uint32_t k_off[LD_PER_THREAD], v_off[LD_PER_THREAD];
     const int k_rs = (int)p.k_row_stride, v_rs = (int)p.v_row_stride;  // host guarantees < 2^24
-    if constexpr (DMA) {
 #pragma unroll
-        for (int i = 0; i < LD_PER_THREAD; ++i) {
-            const int slot = wave * (LD_PER_THREAD * 64) + i * 64 + lane;
-            const int row = slot / CH_PER_ROW;
-            int ch;
-            if constexpr (D == 64) ch = (slot % CH_PER_ROW) ^ ((((row >> 1) & 1) << 2) | ((row >> 2) & 3));
-            else ch = (slot % CH_PER_ROW) ^ (((row & 3) << 2) | ((row >> 2) & 3));
-            dma_row[i] = row;
-            dma_col[i] = (ch * 8 < p.d) ? ch * 8 : 0;
-            dma_colv[i] = D == 256 ? ((ch * 8 < p.d_v) ? ch * 8 : 0) : dma_col[i];
-            k_off[i] = (uint32_t)(row * k_rs + dma_col[i]) * 2u;
-            v_off[i] = (uint32_t)(row * v_rs + dma_colv[i]) * 2u;
-        }
+    for (int i = 0; i < LD_PER_THREAD; ++i) {
+        const int slot = wave * (LD_PER_THREAD * 64) + i * 64 + lane;
+        const int row = slot / CH_PER_ROW;
+        int ch;
+        if constexpr (D == 64) ch = (slot % CH_PER_ROW) ^ ((((row >> 1) & 1) << 2) | ((row >> 2) & 3));
+        else ch = (slot % CH_PER_ROW) ^ (((row & 3) << 2) | ((row >> 2) & 3));
+        dma_row[i] = row;
+        dma_col[i] = (ch * 8 < p.d) ? ch * 8 : 0;
+        dma_colv[i] = D == 256 ? ((ch * 8 < p.d_v) ? ch * 8 : 0) : dma_col[i];
+        k_off[i] = (uint32_t)(row * k_rs + dma_col[i]) * 2u;
+        v_off[i] = (uint32_t)(row * v_rs + dma_colv[i]) * 2u;
     }
     const uint32_t lds_wave = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char *)smem + wave * (LD_PER_THREAD * 1024);
     auto load_tile = [&](int n, int buf) {
         const int k0 = n * BLOCK_N;
-        if constexpr (DMA) {
-            const T *kt = kp + (int64_t)k0 * p.k_row_stride, *vt = vp + (int64_t)k0 * p.v_row_stride;  // wave-uniform
-            if (k0 + BLOCK_N <= sk) {
-                lds_dma<LD_PER_THREAD>(lds_wave + buf * TILE_BYTES, kt, k_off);
-                lds_dma<LD_PER_THREAD>(lds_wave + (NBUF + buf) * TILE_BYTES, vt, v_off);
-            } else {
-                uint32_t ko[LD_PER_THREAD], vo[LD_PER_THREAD];
-#pragma unroll
-                for (int i = 0; i < LD_PER_THREAD; ++i) {
-                    const int rel = min(k0 + dma_row[i], sk - 1) - k0;
-                    ko[i] = (uint32_t)(rel * k_rs + dma_col[i]) * 2u;
-                    vo[i] = (uint32_t)(rel * v_rs + dma_colv[i]) * 2u;
-                }
-                lds_dma<LD_PER_THREAD>(lds_wave + buf * TILE_BYTES, kt, ko);
-                lds_dma<LD_PER_THREAD>(lds_wave + (NBUF + buf) * TILE_BYTES, vt, vo);
-            }
+        const T *kt = kp + (int64_t)k0 * p.k_row_stride, *vt = vp + (int64_t)k0 * p.v_row_stride;  // wave-uniform
+        if (k0 + BLOCK_N <= sk) {
+            lds_dma<LD_PER_THREAD>(lds_wave + buf * TILE_BYTES, kt, k_off);
+            lds_dma<LD_PER_THREAD>(lds_wave + (NBUF + buf) * TILE_BYTES, vt, v_off);
         } else {
+            uint32_t ko[LD_PER_THREAD], vo[LD_PER_THREAD];
 #pragma unroll
-            for (int i = 0; i < NSTAGE; ++i) {
-                const int c = tid + i * NT;
-                const int row = min(k0 + c / CH_PER_ROW, sk - 1);
-                const int ch = c % CH_PER_ROW;
-                const int col = (ch * 8 < p.d) ? ch * 8 : 0, colv = (ch * 8 < p.d_v) ? ch * 8 : 0;
-                kreg[i] = *(const u32x4 *)(kp + (int64_t)row * p.k_row_stride + col);
-                vreg[i] = *(const u32x4 *)(vp + (int64_t)row * p.v_row_stride + colv);
+            for (int i = 0; i < LD_PER_THREAD; ++i) {
+                const int rel = min(k0 + dma_row[i], sk - 1) - k0;
+                ko[i] = (uint32_t)(rel * k_rs + dma_col[i]) * 2u;
+                vo[i] = (uint32_t)(rel * v_rs + dma_colv[i]) * 2u;
             }
-        }
-    };
-    auto store_tile = [&](int buf) {
-        if constexpr (!DMA) {
-#pragma unroll
-            for (int i = 0; i < NSTAGE; ++i) {
-                const int c = tid + i * NT;
-                const int off = lds_off<D>(c / CH_PER_ROW, c % CH_PER_ROW);
-                *(u32x4 *)(smem + buf * TILE_BYTES + off) = kreg[i];
-                *(u32x4 *)(smem + (NBUF + buf) * TILE_BYTES + off) = vreg[i];
-            }
+            lds_dma<LD_PER_THREAD>(lds_wave + buf * TILE_BYTES, kt, ko);
+            lds_dma<LD_PER_THREAD>(lds_wave + (NBUF + buf) * TILE_BYTES, vt, vo);
         }
     };
 
-    if (n_min < n_max) {
-        load_tile(n_min, 0);
-        store_tile(0);
-    }
+    if (n_min < n_max) load_tile(n_min, 0);
     __builtin_amdgcn_s_waitcnt(0x0F70);
     tile_barrier<0>();
 
@@ -917,7 +862,7 @@ __global__ __launch_bounds__(256, 1) void bwd_dq_kernel(const BParams p) {
         const int nxt = (cur + 1) % NBUF;
         // The bulk of the sweep at head dim 128: runs of tiles with nothing to mask for this wave's rows go through the
         // generated asm block (fa_bwd_dq_loop_gen.h; same barrier / LDS-DMA protocol, so the four waves choose independently).
-        if constexpr ((D == 128 || D == 64) && NB == 2 && !SOFTCAP && !DROPOUT && DMA && !(FA_BWD_ABLATE & 2)) {
+        if constexpr ((D == 128 || D == 64) && NB == 2 && !SOFTCAP && !DROPOUT && !(FA_BWD_ABLATE & 2)) {
             int n_hi = sk / BLOCK_N - 1;  // last tile fully inside the keys
             if (p.window_right >= 0) {
                 const int lim = wrow + shift + p.window_right - (BLOCK_N - 1);  // first key of the tile <= lim
@@ -964,8 +909,7 @@ __global__ __launch_bounds__(256, 1) void bwd_dq_kernel(const BParams p) {
                 continue;
             }
         }
-        const bool has_next = n + 1 < n_max;
-        if (has_next) load_tile(n + 1, nxt);
+        if (n + 1 < n_max) load_tile(n + 1, nxt);
 
         const int k0 = n * BLOCK_N;
         bool skip = !wave_active;
@@ -1074,7 +1018,6 @@ __global__ __launch_bounds__(256, 1) void bwd_dq_kernel(const BParams p) {
             }
         }
 
-        if (has_next) store_tile(nxt);
         tile_barrier<0>();
     }
 

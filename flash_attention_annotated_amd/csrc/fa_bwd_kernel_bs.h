@@ -20,8 +20,10 @@
 //     at zero and the epilogue always runs.
 // The accumulation order is the list order: equal lists give bit-equal gradients.
 // Both kernels are the NB = 1 C++ tile paths of bwd_dq_kernel / bwd_dkdv_kernel (staging by LDS-DMA, swizzle, bwd_point, the
-// register -> LDS -> coalesced-row epilogue), restated here so that fa_bwd_api.hip's instantiations stay what they were
-// (tests/test_bwd_plan.py counts them).  No generated asm block.
+// register -> LDS -> coalesced-row epilogue) without dropout and ALiBi and with d_v == d, restated here: a fix to the mask
+// rule, the swizzle or the epilogue has to be made in both files.  (That they are instantiated in a unit of their own,
+// fa_bwd_bs_api.hip, keeps fa_bwd_api.hip's kernels what tests/test_bwd_plan.py counts; it does not ask for the copy.  A shared
+// header was cut and kept out for its code objects: profiles/bwd_tile_step_refactor.md.)  No generated asm block.
 #pragma once
 
 #include "fa_bwd_kernel.h"

@@ -51,7 +51,7 @@ def test_every_tile_once_and_xcds_balanced(b, h_k, h_ratio, m):
 @pytest.mark.parametrize("units,blocks", [(1, 1), (20, 64), (42, 32), (12, 7), (64, 32), (17, 5), (40, 3), (16, 9),
                                           (18, 4), (36, 2)])  # the many-units cases of tests/bwd_plan_universe.py: dK/dV, dQ
 def test_backward_block_map(units, blocks):
-    """decode_block() of the backward kernels (csrc/fa_bwd_kernel.h) with unit_grid() (csrc/fa_bwd_api.hip)."""
+    """decode_block() of the backward kernels (csrc/fa_bwd_kernel.h) with the grid of bwd_set_grid() (csrc/fa_bwd_api.hip)."""
     tiles = units * blocks
     ws = units // 8 * blocks if units >= 16 else 0
     grid = 8 * (ws + (tiles - ws * 8 + 7) // 8)
