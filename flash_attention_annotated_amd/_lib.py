@@ -65,6 +65,11 @@ EXPORTED_SYMBOLS = (
     "fa_kvcache_append_kv8_params_size",
     "fa_kvcache_append_qv8",
     "fa_kvcache_append_qv8_validate",
+    "fa_fwd_sparse_kv",
+    "fa_fwd_sparse_kv_validate",
+    "fa_fwd_sparse_kv_workspace_size",
+    "fa_fwd_sparse_kv_plan_name",
+    "fa_sparse_kv_params_size",
     # include/fa_bwd.h
     "fa_bwd",
     "fa_bwd_validate",
@@ -285,6 +290,16 @@ class FaBlockSparseParams(ctypes.Structure):
     )
 
 
+class FaSparseKvParams(ctypes.Structure):
+    """Field-for-field mirror of `struct fa_sparse_kv_params` (include/fa_fwd.h)."""
+
+    _fields_ = (
+        [("abi_version", ctypes.c_uint32), ("struct_size", ctypes.c_uint32), ("block_cnt", ctypes.c_void_p), ("block_idx", ctypes.c_void_p)]
+        + [(n, ctypes.c_int64) for n in ("cnt_batch_stride", "cnt_head_stride", "idx_batch_stride", "idx_head_stride")]
+        + [(n, ctypes.c_int32) for n in ("max_blocks", "block_size", "fp8_cache", "reserved")]
+    )
+
+
 class FaBlockSparseBwdParams(ctypes.Structure):
     """Field-for-field mirror of `struct fa_block_sparse_bwd_params` (include/fa_bwd.h)."""
 
@@ -335,7 +350,7 @@ def is_stale():
 
 def build(force=False, verbose=False):
     """Compile csrc/ for gfx950 into the in-tree shared library (hipcc cross-compiles without a GPU)."""
-    srcs = [os.path.join(CSRC, f) for f in ("fa_fwd_api.hip", "fa_fwd_kv8_api.hip", "fa_fwd_qv8_api.hip", "fa_kvcache_append_kv8.hip",
+    srcs = [os.path.join(CSRC, f) for f in ("fa_fwd_api.hip", "fa_fwd_kv8_api.hip", "fa_fwd_qv8_api.hip", "fa_fwd_sparse_kv_api.hip", "fa_kvcache_append_kv8.hip",
                                               "fa_kvcache_append_qv8.hip", "fa_bwd_api.hip", "fa_bwd_bs_api.hip")]
     if not force and not is_stale():
         return LIB_PATH
@@ -492,6 +507,19 @@ def load():
     lib.fa_kvcache_append_qv8.restype = ctypes.c_int
     lib.fa_kvcache_append_qv8_validate.argtypes = [ctypes.POINTER(FaKvcacheAppendKv8Params)]
     lib.fa_kvcache_append_qv8_validate.restype = ctypes.c_int
+    sparse_kv = [ctypes.POINTER(FaFwdParams), ctypes.POINTER(FaSparseKvParams)]
+    lib.fa_fwd_sparse_kv.argtypes = sparse_kv + [ctypes.c_void_p]
+    lib.fa_fwd_sparse_kv.restype = ctypes.c_int
+    lib.fa_fwd_sparse_kv_validate.argtypes = sparse_kv
+    lib.fa_fwd_sparse_kv_validate.restype = ctypes.c_int
+    lib.fa_fwd_sparse_kv_workspace_size.argtypes = sparse_kv
+    lib.fa_fwd_sparse_kv_workspace_size.restype = ctypes.c_int64
+    lib.fa_fwd_sparse_kv_plan_name.argtypes = sparse_kv + [ctypes.c_int32]
+    lib.fa_fwd_sparse_kv_plan_name.restype = ctypes.c_char_p
+    lib.fa_sparse_kv_params_size.argtypes = []
+    lib.fa_sparse_kv_params_size.restype = ctypes.c_uint32
+    if lib.fa_sparse_kv_params_size() != ctypes.sizeof(FaSparseKvParams):
+        raise RuntimeError("fa_sparse_kv_params layout mismatch between include/fa_fwd.h and _lib")
     lib.fa_sink_grad.argtypes = [ctypes.POINTER(FaSinkGradParams), ctypes.c_void_p]
     lib.fa_sink_grad.restype = ctypes.c_int
     lib.fa_sink_grad_validate.argtypes = [ctypes.POINTER(FaSinkGradParams)]
@@ -587,6 +615,14 @@ def new_block_sparse_bwd_params():
     p.abi_version = FA_ABI_VERSION
     p.struct_size = ctypes.sizeof(FaBlockSparseBwdParams)
     p.block_m = p.block_n = 128
+    return p
+
+
+def new_sparse_kv_params():
+    p = FaSparseKvParams()
+    p.abi_version = FA_ABI_VERSION
+    p.struct_size = ctypes.sizeof(FaSparseKvParams)
+    p.block_size = 128
     return p
 
 

@@ -21,6 +21,9 @@
 // contracts, the two operand products -- comes from the policy KV: Kv16 below (pk_fwd_kernel: K/V of type T, fwd_kernel's
 // tile) or Kv8 (fa_fwd_kernel_kv8.h: e4m3 bytes).  KV::FP8_CACHE also selects, at compile time, the contract of the entry
 // point a kernel serves; every use says what differs.
+// What WALKS the key tiles is the policy WALK: RangeWalk (pk_fwd_kernel, kv8_fwd_kernel: every 64-key tile of the block's key
+// range, in order) or ListWalk (sp_fwd_kernel, fa_fwd_kernel_sp.h: the tiles of the key blocks a per-kv-head list names, in list
+// order).  Both run the same load_tile / tile step / store_tile; every use of WALK::SPARSE says what differs.
 // Not here (the plan keeps such calls on the other kernels): all-fp8, ALiBi, dropout, attention_chunk, a V head dim of its
 // own, qv, head dims above 128.
 #pragma once
@@ -58,8 +61,25 @@ struct Kv16 {
     }
 };
 
-template <typename T, int D, bool SOFTCAP, typename KV>
-__device__ __forceinline__ void packed_rows_fwd(const PkParams &pa) {
+// ---- the walk over the key tiles of a (batch, kv head[, split]) -------------------------------------------------------------
+// every tile of the block's key range [n_min, n_max), ascending; split-KV partitions that range
+struct RangeWalk {
+    static constexpr bool SPARSE = false;
+};
+// Block-sparse: kv head `g` of batch `b` reads the first min(block_cnt[b, g], max_blocks) entries of block_idx[b, g, :], each a
+// block of block_size keys (a multiple of BLOCK_N) = block_size / BLOCK_N tiles.  List position t maps to entry t / sub,
+// sub-tile t % sub, logical tile n = entry * sub + t % sub; split-KV partitions the positions.  An entry outside
+// [0, ceil(sk / block_size)) and a tile outside the block's key range are passed over before anything is loaded for them;
+// entries at or behind the count are never read for their meaning.  Lists are int32 behind element strides (0 = broadcast).
+struct ListWalk {
+    static constexpr bool SPARSE = true;
+    const int32_t *block_cnt, *block_idx;
+    int64_t cnt_batch_stride, cnt_head_stride, idx_batch_stride, idx_head_stride;
+    int32_t max_blocks, block_size;
+};
+
+template <typename T, int D, bool SOFTCAP, typename KV, typename WALK = RangeWalk>
+__device__ __forceinline__ void packed_rows_fwd(const PkParams &pa, const WALK &walk = WALK()) {
     typedef typename KV::E E;
     const KParams &p = pa.p;
     constexpr int NT = PK_NWAVES * 64;
@@ -101,7 +121,7 @@ __device__ __forceinline__ void packed_rows_fwd(const PkParams &pa) {
         sq = p.seqused_q ? p.seqused_q[batch] : p.seqlen_q;
     }
     bool ragged_k = false;
-    if constexpr (!KV::FP8_CACHE) ragged_k = p.cu_seqlens_k != nullptr;  // (fa_fwd_kv8_validate refuses cu_seqlens_k)
+    if constexpr (!KV::FP8_CACHE && !WALK::SPARSE) ragged_k = p.cu_seqlens_k != nullptr;  // (fa_fwd_kv8_validate / fa_fwd_sparse_kv_validate refuse cu_seqlens_k)
     if (ragged_k) {
         const int k0 = p.cu_seqlens_k[batch];
         sk = p.seqused_k ? p.seqused_k[batch] : p.cu_seqlens_k[batch + 1] - k0;
@@ -109,7 +129,7 @@ __device__ __forceinline__ void packed_rows_fwd(const PkParams &pa) {
         v_base = (int64_t)k0 * p.v_row_stride;
     } else {
         sk = p.seqused_k ? p.seqused_k[batch] : p.seqlen_k;
-        if constexpr (KV::FP8_CACHE) sk = min(sk, p.seqlen_k);  // a cache: never past the capacity
+        if constexpr (KV::FP8_CACHE || WALK::SPARSE) sk = min(sk, p.seqlen_k);  // a cache: never past the capacity
         const int kv_batch = p.kv_batch_idx ? p.kv_batch_idx[batch] : batch;
         k_base = (int64_t)kv_batch * p.k_batch_stride;
         v_base = (int64_t)kv_batch * p.v_batch_stride;
@@ -150,7 +170,20 @@ __device__ __forceinline__ void packed_rows_fwd(const PkParams &pa) {
     if (p.window_left >= 0) key_lo = max(0, qr_lo + shift - p.window_left);
     int n_min = key_lo / BLOCK_N;
     int n_max = key_hi > 0 ? (key_hi + BLOCK_N - 1) / BLOCK_N : 0;
-    split_range(p, split, n_min, n_max);
+    // ListWalk: [n_min, n_max) stays the block's key range (what a listed tile is checked against) and the parts of a split
+    // call are ranges of list positions [t_lo, t_hi)
+    int t_lo = 0, t_hi = 0, sub = 1, nblk = 0;
+    const int32_t *list = nullptr;
+    if constexpr (WALK::SPARSE) {
+        sub = walk.block_size / BLOCK_N;
+        nblk = sk > 0 ? (sk + walk.block_size - 1) / walk.block_size : 0;
+        const int cnt = walk.block_cnt[(int64_t)batch * walk.cnt_batch_stride + (int64_t)kv_head * walk.cnt_head_stride];
+        list = walk.block_idx + (int64_t)batch * walk.idx_batch_stride + (int64_t)kv_head * walk.idx_head_stride;
+        t_hi = max(min(cnt, walk.max_blocks), 0) * sub;  // (the host keeps max_blocks * block_size below 2^31)
+        split_range(p, split, t_lo, t_hi);
+    } else {
+        split_range(p, split, n_min, n_max);
+    }
 
     // the lane's own key range [lim_lo, lim_hi), from its QUERY row: the element mask of the boundary tiles, and (the fp8
     // cache's split convention below) whether the row sees a key at all
@@ -234,17 +267,66 @@ __device__ __forceinline__ void packed_rows_fwd(const PkParams &pa) {
     const int kbase = KV::kbase(r, hh);
     const int vbase = KV::vbase(lane);
 
-    if (n_min < n_max) {
-        load_tile(n_min);
+    // ---- the walk: n_first() / the loop head below give the tile to compute and the one to stage beside it.  RangeWalk: n,
+    // n + 1 of [n_min, n_max).  ListWalk (all of it uniform over the workgroup: scalar loads and scalar compares): next_tile()
+    // gives the logical tile of the next list position that is to be read, or -1 behind the last; positions whose entry lies
+    // outside [0, nblk) or whose tile lies outside the block's key range [n_min, n_max) are passed over there, before any load
+    // is issued for them (so load_tile's `last` stays >= 0).  The entry of the NEXT list slot is fetched when the walk enters a
+    // slot -- one step ahead, beside the K/V loads of the tile in flight -- so the tile address never waits for it.  That
+    // fetch is a VECTOR load on purpose (a scalar load is not to be had behind the loop's barrier, and a uniform vector load
+    // is made scalar where it is issued, which waits for it there): the opaque zero `vz` keeps its address per-lane in the
+    // compiler's eyes, the value stays in a VGPR over the step, and the wait sits at the readfirstlane that consumes it.
+    int t = t_lo, ent = t_lo / sub, st = t_lo - ent * sub;
+    int e_cur = 0, e_next = 0, vz = 0;
+    bool enter = true;
+    if constexpr (WALK::SPARSE) {
+        asm volatile("" : "+v"(vz));
+        e_next = (t_lo < t_hi) ? list[ent + vz] : 0;
+    }
+    auto next_tile = [&]() -> int {
+        while (t < t_hi) {
+            if (enter) {
+                e_cur = __builtin_amdgcn_readfirstlane(e_next);
+                if ((ent + 1) * sub < t_hi) e_next = list[ent + 1 + vz];  // (a slot in front of the count)
+                enter = false;
+            }
+            const bool inside = (uint32_t)e_cur < (uint32_t)nblk;
+            const int n = inside ? e_cur * sub + st : -1;
+            ++t;
+            if (++st == sub) {
+                st = 0;
+                ++ent;
+                enter = true;
+            }
+            if (n >= n_min && n < n_max) return n;
+        }
+        return -1;
+    };
+
+    int n_first = n_min;
+    if constexpr (WALK::SPARSE) n_first = next_tile();
+    if (WALK::SPARSE ? n_first >= 0 : n_min < n_max) {
+        load_tile(n_first);
         store_tile(0);
     }
     __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): Q retired here, not in front of the first MFMA of every tile
     __syncthreads();
 
-    for (int n = n_min; n < n_max; ++n) {
-        const int cur = (n - n_min) & 1;
-        const bool has_next = (n + 1 < n_max);
-        if (has_next) load_tile(n + 1);
+    int n_next = -1, parity = 0;  // (ListWalk only)
+    for (int n = n_first; WALK::SPARSE ? n >= 0 : n < n_max; n = WALK::SPARSE ? n_next : n + 1) {
+        int cur;
+        bool has_next;
+        if constexpr (WALK::SPARSE) {
+            cur = parity;
+            parity ^= 1;
+            n_next = next_tile();
+            has_next = n_next >= 0;
+            if (has_next) load_tile(n_next);
+        } else {
+            cur = (n - n_min) & 1;
+            has_next = (n + 1 < n_max);
+            if (has_next) load_tile(n + 1);
+        }
 
         const int k0 = n * BLOCK_N;
         // wave-uniform tile classification from the wave's first and last query row
@@ -286,11 +368,27 @@ __device__ __forceinline__ void packed_rows_fwd(const PkParams &pa) {
     float lse_row = empty ? INFINITY : m_run * sc.scale + __logf(l_tot);  // +inf for rows with no valid key, as fwd_kernel
     if constexpr (KV::FP8_CACHE) {
         inv = empty ? 0.f : sc.v_descale / l_tot;  // v_descale rides in the factor
+    } else {
+        inv = empty ? 1.f : 1.f / l_tot;
+    }
+    if constexpr (WALK::SPARSE) {
+        // kv8's split convention below, for both cache types (the merge is fa_fwd_combine); "the row sees a key" means a
+        // LISTED key here: an empty part looks through the whole list (uniform addresses, entries in front of the count
+        // only) for a block in range that meets the row's key range.  Rare: only the rows of a part that found nothing
+        if (p.num_splits > 1 && empty && lim_lo < lim_hi) {
+            bool seen = false;
+            const int slots = max(min(walk.block_cnt[(int64_t)batch * walk.cnt_batch_stride + (int64_t)kv_head * walk.cnt_head_stride], walk.max_blocks), 0);
+            for (int i = 0; i < slots && !seen; ++i) {
+                const int e = list[i];
+                if ((uint32_t)e < (uint32_t)nblk) seen = max(e * walk.block_size, lim_lo) < min((e + 1) * walk.block_size, lim_hi);
+            }
+            if (seen) lse_row = -INFINITY;
+        }
+    } else if constexpr (KV::FP8_CACHE) {
         // split-KV partials follow fa_fwd_combine's convention (the merge of fa_fwd_kv8 is that entry point): a part that holds
         // none of the row's keys carries no weight (-inf); a row without any key keeps +inf.  No sink (fa_fwd_kv8_validate)
         if (p.num_splits > 1 && empty && lim_lo < lim_hi) lse_row = -INFINITY;
     } else {
-        inv = empty ? 1.f : 1.f / l_tot;
         if (p.sink)  // the lane's own head
             sink_finalize(row_ok ? load_sink(p, head, my_row) : -INFINITY, m_run * sc.scale, l_tot, empty, inv, lse_row);
     }

@@ -1145,6 +1145,13 @@ void check_kv8_descale(const Tensor &t, const char *name, int64_t batch_size, in
                 " must be fp32 (batch_size, num_heads_k)");
 }
 
+// The block lists of fwd_kvcache_sparse (include/fa_fwd.h, fa_sparse_kv_params), checked there
+struct SparseLists {
+    Tensor cnt, idx;     // int32 (b | 1, h_k | 1) and (b | 1, h_k | 1, max_blocks)
+    int64_t block_size;  // B
+    bool fp8_cache;      // e4m3 caches (else 16-bit caches of q's dtype)
+};
+
 // 16-bit queries over an fp8 (e4m3) KV cache -- kv_cache_dtype = fp8 of a serving stack (include/fa_fwd.h, fa_fwd_kv8): q and
 // out fp16 / bf16, k / v the cache as Float8_e4m3fn, (b_cache, seqlen_k, h_k, d) or pages behind page_table, k_descale /
 // v_descale fp32 (b, h_k).  Dense q (b, seqlen_q, h, d) or ragged q (total_q, h, d) with cu_seqlens_q; cache_seqlens in
@@ -1153,17 +1160,21 @@ void check_kv8_descale(const Tensor &t, const char *name, int64_t batch_size, in
 // refused what the route does not serve (qv, attention_chunk, head dims).
 // mla: the MLA decode shape (fa_fwd_qv8: head_size <= 64 beside v.size(-1) in [256, 512], qv optional, out (..., h, d_v)); every
 // other argument is handled alike, so fwd_qv8 below is this function with mla set.
+// sparse: the block-sparse read (fa_fwd_sparse_kv) of fwd_kvcache_sparse below, over an e4m3 cache or -- the one case where k / v
+// are 16-bit here -- a cache of q's dtype; the lists ride beside the same params, everything else is handled alike.
 std::tuple<Tensor, Tensor> fwd_kv8(const Tensor &q, const Tensor &k, const Tensor &v, const OptTensor &out_,
                                    const OptTensor &cu_seqlens_q, const OptTensor &seqused_q, const OptTensor &seqused_k,
                                    c10::optional<int64_t> max_seqlen_q_, const OptTensor &page_table, const OptTensor &kv_batch_idx,
                                    const OptTensor &leftpad_k, const OptTensor &k_descale, const OptTensor &v_descale,
                                    double softmax_scale, bool is_causal, int64_t window_size_left, int64_t window_size_right,
-                                   double softcap, int64_t num_splits, const OptTensor &qv = c10::nullopt, bool mla = false) {
+                                   double softcap, int64_t num_splits, const OptTensor &qv = c10::nullopt, bool mla = false,
+                                   const SparseLists *sparse = nullptr) {
+    const bool wide_cache = sparse && !sparse->fp8_cache;  // 16-bit k / v: strides in 2-byte elements
     CHECK_DEVICE(k, "k"); CHECK_LAST_CONTIGUOUS(k, "Input tensor must have contiguous last dimension");
     CHECK_DEVICE(v, "v"); CHECK_LAST_CONTIGUOUS(v, "Input tensor must have contiguous last dimension");
     const bool ragged = cu_seqlens_q.has_value();
-    TORCH_CHECK(k.dim() == 4 && v.dim() == 4,
-                "an fp8 k / v must be a KV cache of shape (batch or num_pages, seqlen or page_size, num_heads_k, head_size)");
+    TORCH_CHECK(k.dim() == 4 && v.dim() == 4, sparse ? "k / v" : "an fp8 k / v",
+                " must be a KV cache of shape (batch or num_pages, seqlen or page_size, num_heads_k, head_size)");
     const int64_t head_size = q.size(-1), num_heads = q.size(-2), num_heads_k = k.size(2);
     const int64_t head_size_v = mla ? v.size(3) : head_size;
     std::vector<int64_t> out_shape = q.sizes().vec();  // q's with V's head dim
@@ -1180,8 +1191,10 @@ std::tuple<Tensor, Tensor> fwd_kv8(const Tensor &q, const Tensor &k, const Tenso
     TORCH_CHECK(batch_size > 0, "batch size must be positive");
     TORCH_CHECK(num_heads_k > 0 && num_heads % num_heads_k == 0, "Number of heads in key/value must divide number of heads in query");
     CacheRules rules;
-    rules.base_grain = rules.stride_grain = 16;
-    rules.misaligned = "the fp8 KV cache must be 16-byte aligned with row/head/batch strides that are multiples of 16";
+    if (!wide_cache) {
+        rules.base_grain = rules.stride_grain = 16;
+        rules.misaligned = "the fp8 KV cache must be 16-byte aligned with row/head/batch strides that are multiples of 16";
+    }
     rules.k_shape = "k must have shape (..., " + std::to_string(num_heads_k) + ", " + std::to_string(head_size) + ")";
     rules.v_shape = mla ? "v must have the shape of k with its own head_size_v" : "v must have the shape of k";
     rules.fill_dtype = rules.fill_device = rules.fill_contiguous = rules.fill_shape = " must be int32 of shape (batch_size,)";
@@ -1212,6 +1225,12 @@ std::tuple<Tensor, Tensor> fwd_kv8(const Tensor &q, const Tensor &k, const Tenso
     Tensor softmax_lse = ragged ? at::empty({num_heads, total_q}, q.options().dtype(at::kFloat))
                                 : at::empty({batch_size, num_heads, seqlen_q}, q.options().dtype(at::kFloat));
     if (total_q == 0) return {out, softmax_lse};
+    if (sparse) {  // one list per kv head, or one for all of a dimension of size 1
+        TORCH_CHECK(sparse->cnt.size(0) == 1 || sparse->cnt.size(0) == batch_size, "kv_block_cnt must have shape (batch_size | 1, num_heads_k | 1)");
+        TORCH_CHECK(sparse->cnt.size(1) == 1 || sparse->cnt.size(1) == num_heads_k, "kv_block_cnt must have shape (batch_size | 1, num_heads_k | 1)");
+        TORCH_CHECK(sparse->idx.size(0) == 1 || sparse->idx.size(0) == batch_size, "kv_block_idx must have shape (batch_size | 1, num_heads_k | 1, max_blocks)");
+        TORCH_CHECK(sparse->idx.size(1) == 1 || sparse->idx.size(1) == num_heads_k, "kv_block_idx must have shape (batch_size | 1, num_heads_k | 1, max_blocks)");
+    }
     if (seqlen_k == 0 || seqlen_q == 0) {
         out.zero_();
         softmax_lse.fill_(std::numeric_limits<float>::infinity());
@@ -1270,9 +1289,23 @@ std::tuple<Tensor, Tensor> fwd_kv8(const Tensor &q, const Tensor &k, const Tenso
         p.page_block_size = (int32_t)k.size(1);
     }
     p.num_splits = (int32_t)std::max<int64_t>(num_splits, 0);
+    fa_sparse_kv_params sp{};
+    if (sparse) {
+        sp.abi_version = FA_ABI_VERSION;
+        sp.struct_size = sizeof(fa_sparse_kv_params);
+        sp.block_cnt = static_cast<const int32_t *>(sparse->cnt.data_ptr());
+        sp.block_idx = static_cast<const int32_t *>(sparse->idx.data_ptr());
+        sp.cnt_batch_stride = sparse->cnt.size(0) == 1 ? 0 : sparse->cnt.stride(0);
+        sp.cnt_head_stride = sparse->cnt.size(1) == 1 ? 0 : sparse->cnt.stride(1);
+        sp.idx_batch_stride = sparse->idx.size(0) == 1 ? 0 : sparse->idx.stride(0);
+        sp.idx_head_stride = sparse->idx.size(1) == 1 ? 0 : sparse->idx.stride(1);
+        sp.max_blocks = (int32_t)sparse->idx.size(2);
+        sp.block_size = (int32_t)sparse->block_size;
+        sp.fp8_cache = sparse->fp8_cache ? 1 : 0;
+    }
     Tensor workspace;
-    const char *entry = mla ? "fa_fwd_qv8" : "fa_fwd_kv8";
-    const int64_t need = mla ? fa_fwd_qv8_workspace_size(&p) : fa_fwd_kv8_workspace_size(&p);
+    const char *entry = sparse ? "fa_fwd_sparse_kv" : mla ? "fa_fwd_qv8" : "fa_fwd_kv8";
+    const int64_t need = sparse ? fa_fwd_sparse_kv_workspace_size(&p, &sp) : mla ? fa_fwd_qv8_workspace_size(&p) : fa_fwd_kv8_workspace_size(&p);
     TORCH_CHECK(need >= 0, entry, "_workspace_size failed (", need, "): ", fa_strerror((int)need));
     if (need > 0) {  // split-KV partials: scratch from torch's caching allocator (the callee never allocates)
         workspace = at::empty({need + 256}, q.options().dtype(at::kByte));
@@ -1280,10 +1313,64 @@ std::tuple<Tensor, Tensor> fwd_kv8(const Tensor &q, const Tensor &k, const Tenso
         p.workspace = reinterpret_cast<void *>(base);
         p.workspace_bytes = (uint64_t)need;
     }
-    const int st = mla ? fa_fwd_qv8(&p, current_stream(q)) : fa_fwd_kv8(&p, current_stream(q));
+    const int st = sparse ? fa_fwd_sparse_kv(&p, &sp, current_stream(q)) : mla ? fa_fwd_qv8(&p, current_stream(q)) : fa_fwd_kv8(&p, current_stream(q));
     TORCH_CHECK(st == 0, entry, " failed (", st, "): ", fa_strerror(st));
     if (!oc.is_same(out)) out.copy_(oc);
     return {out, softmax_lse};
+}
+
+// hopper_interface.flash_attn_with_kvcache_sparse / torch.ops.flash_attn_3.fwd_kvcache_sparse: attention of a decode, verify or
+// ragged serving step over the key blocks of the cache that kv_block_cnt / kv_block_idx list per kv head (include/fa_fwd.h,
+// fa_fwd_sparse_kv).  16-bit caches of q's dtype or e4m3 caches with both descales; read-only (the appends are the other calls').
+// The refusals by argument stand here; the cache side, out, the workspace and the launch are fwd_kv8's.  Nothing of the lists is
+// read on the host.
+std::tuple<Tensor, Tensor> fwd_kvcache_sparse(const Tensor &q, const Tensor &k, const Tensor &v, const Tensor &kv_block_cnt,
+                                              const Tensor &kv_block_idx, int64_t kv_block_size, const OptTensor &seqused_k,
+                                              const OptTensor &kv_batch_idx, const OptTensor &leftpad_k, const OptTensor &page_table,
+                                              const OptTensor &cu_seqlens_q, c10::optional<int64_t> max_seqlen_q_,
+                                              const OptTensor &k_descale, const OptTensor &v_descale, c10::optional<double> softmax_scale_,
+                                              bool is_causal, int64_t window_size_left, int64_t window_size_right, double softcap,
+                                              int64_t num_splits) {
+    const auto q_dtype = q.scalar_type();
+    TORCH_CHECK(q_dtype == at::kHalf || q_dtype == at::kBFloat16,
+                "This flash attention build supports block-sparse attention over a KV cache for fp16 / bf16 queries only");
+    TORCH_CHECK(k.scalar_type() == v.scalar_type(), "k_cache and v_cache must have the same dtype");
+    const bool fp8_cache = k.scalar_type() == at::kFloat8_e4m3fn;
+    TORCH_CHECK(fp8_cache || k.scalar_type() == q_dtype,
+                "k_cache / v_cache must have the dtype of the query or be torch.float8_e4m3fn under an fp16 / bf16 query");
+    if (fp8_cache) {
+        TORCH_CHECK(k_descale.has_value() && v_descale.has_value(), "k_descale and v_descale must be provided with an fp8 KV cache");
+    } else {
+        TORCH_CHECK(!k_descale.has_value() && !v_descale.has_value(), "k_descale / v_descale belong to an fp8 KV cache");
+    }
+    TORCH_CHECK(kv_block_size > 0 && kv_block_size % 64 == 0, "kv_block_size must be a positive multiple of 64, got ", kv_block_size);
+    for (const auto &[t, name] : {std::make_pair(&kv_block_cnt, "kv_block_cnt"), std::make_pair(&kv_block_idx, "kv_block_idx")}) {
+        TORCH_CHECK(t->scalar_type() == at::kInt, name, " must have dtype int32");
+        TORCH_CHECK(t->is_cuda() && t->device() == q.device(), name, " must be on the same CUDA device as query");
+    }
+    TORCH_CHECK(kv_block_cnt.dim() == 2, "kv_block_cnt must have shape (batch_size | 1, num_heads_k | 1)");
+    TORCH_CHECK(kv_block_idx.dim() == 3, "kv_block_idx must have shape (batch_size | 1, num_heads_k | 1, max_blocks)");
+    TORCH_CHECK(kv_block_idx.size(2) == 0 || kv_block_idx.stride(2) == 1, "kv_block_idx must have contiguous last dimension");
+    TORCH_CHECK(kv_block_idx.size(2) * kv_block_size <= 0x7fffffff, "max_blocks * kv_block_size must stay below 2^31");
+    TORCH_CHECK(k.dim() == 4 && v.dim() == 4 && v.size(-1) == q.size(-1) && k.size(-1) == q.size(-1),
+                "This flash attention build does not support a V headdim of its own with block-sparse attention over a KV cache.");
+    TORCH_CHECK(q.size(-1) <= 128 && q.size(-1) % 16 == 0,
+                "This flash attention build supports block-sparse attention over a KV cache for head_size <= 128 that is a multiple "
+                "of 16, got ", q.size(-1));
+    const bool ragged = cu_seqlens_q.has_value();
+    CHECK_DEVICE(q, "q"); CHECK_LAST_CONTIGUOUS(q, "Input tensor must have contiguous last dimension");
+    TORCH_CHECK(q.dim() == (ragged ? 3 : 4), ragged ? "q must have shape (total_q, num_heads, head_size) with cu_seqlens_q"
+                                                    : "q must have shape (batch_size, seqlen_q, num_heads, head_size)");
+    if (ragged) {
+        TORCH_CHECK(cu_seqlens_q->scalar_type() == at::kInt && cu_seqlens_q->is_contiguous() && cu_seqlens_q->is_cuda(),
+                    "cu_seqlens_q must be a contiguous int32 CUDA tensor");
+        TORCH_CHECK(max_seqlen_q_.has_value() && *max_seqlen_q_ > 0, "max_seqlen_q must be provided with cu_seqlens_q");
+    }
+    const double softmax_scale = softmax_scale_.has_value() ? *softmax_scale_ : 1.0 / std::sqrt((double)q.size(-1));
+    const SparseLists lists{kv_block_cnt, kv_block_idx, kv_block_size, fp8_cache};
+    return fwd_kv8(q, k, v, c10::nullopt, cu_seqlens_q, c10::nullopt, seqused_k, max_seqlen_q_, page_table, kv_batch_idx, leftpad_k,
+                   k_descale, v_descale, softmax_scale, is_causal, window_size_left, window_size_right, softcap, num_splits, c10::nullopt,
+                   false, &lists);
 }
 
 // The MLA decode shape over an fp8 KV cache (include/fa_fwd.h, fa_fwd_qv8): q (.., h, d <= 64) and the optional qv (.., h, d_v)
@@ -2123,6 +2210,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("v_descale"), py::arg("cu_seqlens_k_new") = py::none(), py::arg("max_seqlen_k_new") = py::none(),
           py::arg("cache_batch_idx") = py::none(), py::arg("page_table") = py::none(), py::arg("rotary_cos") = py::none(),
           py::arg("rotary_sin") = py::none(), py::arg("rotary_seqlens") = py::none(), py::arg("rotary_interleaved") = true);
+    m.def("fwd_kvcache_sparse", &fwd_kvcache_sparse,
+          "block-sparse attention over a KV cache: only the key blocks listed per kv head are read; returns (out, softmax_lse)",
+          py::arg("q"), py::arg("k_cache"), py::arg("v_cache"), py::arg("kv_block_cnt"), py::arg("kv_block_idx"), py::arg("kv_block_size") = 128,
+          py::arg("cache_seqlens") = py::none(), py::arg("cache_batch_idx") = py::none(), py::arg("cache_leftpad") = py::none(),
+          py::arg("page_table") = py::none(), py::arg("cu_seqlens_q") = py::none(), py::arg("max_seqlen_q") = py::none(),
+          py::arg("k_descale") = py::none(), py::arg("v_descale") = py::none(), py::arg("softmax_scale") = py::none(),
+          py::arg("is_causal") = false, py::arg("window_size_left") = -1, py::arg("window_size_right") = -1, py::arg("softcap") = 0.0,
+          py::arg("num_splits") = 0);
     m.def("fa3_bwd", &fa3_bwd, "FA3 backward pass (flash_attn_3::bwd)");
     m.def("fa3_fwd_combine", &fa3_fwd_combine, "FA3 merge of split-KV partials (flash_attn_3::fwd_combine)");
     m.def("cute_fwd", &cute_fwd, "cute surface forward (flash_attn.cute.interface, with learnable_sink)", py::arg("q"), py::arg("k"),

@@ -41,9 +41,16 @@ APPEND_FP8_SCHEMA = (
     "Tensor v_descale, Tensor? cu_seqlens_k_new = None, int? max_seqlen_k_new = None, Tensor? cache_batch_idx = None, "
     "Tensor? page_table = None, Tensor? rotary_cos = None, Tensor? rotary_sin = None, Tensor? rotary_seqlens = None, "
     "bool rotary_interleaved = True) -> Tensor")
+# not in the reference's library either: block-sparse attention over a KV cache (key blocks listed per kv head), read-only
+KVCACHE_SPARSE_SCHEMA = (
+    "fwd_kvcache_sparse(Tensor q, Tensor k_cache, Tensor v_cache, Tensor kv_block_cnt, Tensor kv_block_idx, int kv_block_size = 128, "
+    "Tensor? cache_seqlens = None, Tensor? cache_batch_idx = None, Tensor? cache_leftpad = None, Tensor? page_table = None, "
+    "Tensor? cu_seqlens_q = None, int? max_seqlen_q = None, Tensor? k_descale = None, Tensor? v_descale = None, "
+    "float? softmax_scale = None, bool is_causal = False, int window_size_left = -1, int window_size_right = -1, "
+    "float softcap = 0.0, int num_splits = 0) -> (Tensor, Tensor)")
 
 _ops = torch.library.Library("flash_attn_3", "DEF")
-for _schema in (FWD_SCHEMA, BWD_SCHEMA, COMBINE_SCHEMA, METADATA_SCHEMA, APPEND_FP8_SCHEMA):
+for _schema in (FWD_SCHEMA, BWD_SCHEMA, COMBINE_SCHEMA, METADATA_SCHEMA, APPEND_FP8_SCHEMA, KVCACHE_SPARSE_SCHEMA):
     _ops.define(_schema)
 
 
@@ -92,6 +99,25 @@ def _kvcache_append_fp8_meta(k_cache, v_cache, k, v, cache_seqlens, k_descale, v
     return torch.empty_like(cache_seqlens)
 
 
+def _fwd_kvcache_sparse(q, k_cache, v_cache, kv_block_cnt, kv_block_idx, kv_block_size=128, cache_seqlens=None, cache_batch_idx=None,
+                        cache_leftpad=None, page_table=None, cu_seqlens_q=None, max_seqlen_q=None, k_descale=None, v_descale=None,
+                        softmax_scale=None, is_causal=False, window_size_left=-1, window_size_right=-1, softcap=0.0, num_splits=0):
+    """The binding's fwd_kvcache_sparse (fa_fwd_sparse_kv): one launch (+ the merge of a split call), no host sync."""
+    out, lse = _lib.binding().fwd_kvcache_sparse(q, k_cache, v_cache, kv_block_cnt, kv_block_idx, kv_block_size, cache_seqlens,
+                                                 cache_batch_idx, cache_leftpad, page_table, cu_seqlens_q, max_seqlen_q, k_descale,
+                                                 v_descale, softmax_scale, is_causal, window_size_left, window_size_right, softcap,
+                                                 num_splits)
+    return out, lse
+
+
+def _fwd_kvcache_sparse_meta(q, k_cache, v_cache, kv_block_cnt, kv_block_idx, kv_block_size=128, cache_seqlens=None,
+                             cache_batch_idx=None, cache_leftpad=None, page_table=None, cu_seqlens_q=None, max_seqlen_q=None,
+                             k_descale=None, v_descale=None, softmax_scale=None, is_causal=False, window_size_left=-1,
+                             window_size_right=-1, softcap=0.0, num_splits=0):
+    lse_shape = (q.shape[1], q.shape[0]) if q.dim() == 3 else (q.shape[0], q.shape[2], q.shape[1])
+    return torch.empty_like(q), q.new_empty(lse_shape, dtype=torch.float32)
+
+
 def _get_scheduler_metadata(batch_size, max_seqlen_q, max_seqlen_k, num_heads, num_heads_k, headdim, headdim_v, qkv_dtype,
                             seqused_k, cu_seqlens_q=None, cu_seqlens_k=None, cu_seqlens_k_new=None, seqused_q=None,
                             leftpad_k=None, page_size=None, max_seqlen_k_new=0, is_causal=False, window_size_left=-1,
@@ -125,3 +151,5 @@ _ops.impl("fwd_combine", _fwd_combine, "CUDA")
 _ops.impl("get_scheduler_metadata", _get_scheduler_metadata, "CUDA")
 _ops.impl("kvcache_append_fp8", _kvcache_append_fp8, "CUDA")
 _ops.impl("kvcache_append_fp8", _kvcache_append_fp8_meta, "Meta")
+_ops.impl("fwd_kvcache_sparse", _fwd_kvcache_sparse, "CUDA")
+_ops.impl("fwd_kvcache_sparse", _fwd_kvcache_sparse_meta, "Meta")

@@ -224,6 +224,50 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, qv=None, rotary
     return (out, softmax_lse, *rest) if return_softmax_lse else out
 
 
+def flash_attn_with_kvcache_sparse(q, k_cache, v_cache, kv_block_cnt, kv_block_idx, *, kv_block_size=128, cache_seqlens=None,
+                                   cache_batch_idx=None, cache_leftpad=None, page_table=None, cu_seqlens_q=None, max_seqlen_q=None,
+                                   k_descale=None, v_descale=None, softmax_scale=None, causal=False, window_size=(-1, -1),
+                                   softcap=0.0, num_splits=0, return_softmax_lse=False):
+    """Block-sparse attention over a KV cache: a decode, verify or ragged serving step that reads only the key blocks a
+    selection step listed (Quest-style page selection, NSA-style selected blocks shared by a GQA group).  Not in the reference.
+    q: (batch, seqlen_q, nheads, headdim), or (total_q, nheads, headdim) with cu_seqlens_q + max_seqlen_q; fp16 / bf16,
+    headdim <= 128 and a multiple of 16.  k_cache / v_cache: as in flash_attn_with_kvcache (batched with cache_batch_idx /
+    cache_leftpad, or pages of any size behind page_table), of q's dtype or torch.float8_e4m3fn; the fp8 case takes both
+    k_descale / v_descale, fp32 (batch, nheads_k).
+    kv_block_cnt: int32 (batch | 1, nheads_k | 1); kv_block_idx: int32 (batch | 1, nheads_k | 1, max_blocks), on the device; a
+    dimension of size 1 is shared.  With B = kv_block_size (a multiple of 64), g = nheads / nheads_k and sk(b) the fill level
+    of batch entry b (cache_seqlens, clamped to the capacity, minus cache_leftpad), key j of batch b is visible to query row i of
+    head h iff
+      * j < sk(b),
+      * causal / window_size / softcap allow (i, j) exactly as in flash_attn_with_kvcache (bottom-right aligned on sk(b)), and
+      * j // B is among the first min(kv_block_cnt[b, h // g], max_blocks) entries of kv_block_idx[b, h // g, :].
+    Lists are per KV head: every query row of the call and every head of the GQA group share them, and with them one pass over
+    the listed blocks.  Entries may come in any order (rounding only).  An entry outside [0, ceil(sk(b) / B)) is skipped without
+    touching memory, entries at or behind the count are never used as addresses; distinct entries are the caller's duty (a
+    duplicate counts twice).  A row with no visible key gives out = 0, lse = +inf.
+    The walk: list position t in [0, cnt * B / 64) is entry t // (B / 64), 64-key sub-tile t % (B / 64); the next entry is
+    fetched one step ahead.  num_splits: 1 = off, N = N parts of the list POSITIONS (not of the key range), 0 = the count the
+    PackGQA shape gets for a key length of max_blocks * B -- from shapes only.  Nothing of the lists is read on the host and
+    nothing synchronises: the call can be captured into a HIP graph, and a replay after the lists were overwritten in place
+    computes the new selection.
+    Read-only: append with flash_attn_with_kvcache(k=, v=) or kvcache_append_fp8 first, then call this on the new fill levels.
+    No qv, learnable sink, attention_chunk or V headdim of its own, and no backward.
+    Cost, measured on MI355X (tools/sparse_kv_decode_bench.py, profiles/sparse_kv_decode.jsonl; hq32 / hkv8 d128, page 64,
+    B = 128, cache 8192 / 32768, batch 1 / 8 / 64): time ~ fixed cost (15 - 27 us) + listed bytes (4.0 - 5.6 TB/s at cache 32768, batch 64).
+    Over an fp8 cache, all blocks listed costs 1.01 - 1.09 x flash_attn_with_kvcache on the same cache (the price of the walk)
+    and this call wins below a listed fraction of 0.85 - 0.99; over a bf16 cache it is 0.78 - 0.91 x that call (whose decode
+    is the GQA-folded kernel, not the packed-row one) even with every block listed.  DESIGN.md section 4.20.
+    Returns out, or (out, softmax_lse) when return_softmax_lse: (batch, nheads, seqlen_q), ragged (nheads, total_q)."""
+    assert k_cache.stride(-1) == 1, "k_cache must have contiguous last dimension"
+    assert v_cache.stride(-1) == 1, "v_cache must have contiguous last dimension"
+    if cache_seqlens is not None and isinstance(cache_seqlens, int):
+        cache_seqlens = torch.full((q.shape[0],), cache_seqlens, dtype=torch.int32, device=k_cache.device)
+    out, softmax_lse = torch.ops.flash_attn_3.fwd_kvcache_sparse(
+        q, k_cache, v_cache, kv_block_cnt, kv_block_idx, kv_block_size, cache_seqlens, cache_batch_idx, cache_leftpad, page_table,
+        cu_seqlens_q, max_seqlen_q, k_descale, v_descale, softmax_scale, causal, window_size[0], window_size[1], softcap, num_splits)
+    return (out, softmax_lse) if return_softmax_lse else out
+
+
 def kvcache_append_fp8(k_cache, v_cache, k, v, cache_seqlens, k_descale, v_descale, *, cu_seqlens_k_new=None,
                        max_seqlen_k_new=None, cache_batch_idx=None, page_table=None, rotary_cos=None, rotary_sin=None,
                        rotary_seqlens=None, rotary_interleaved=True):

@@ -251,7 +251,7 @@ int fa_fwd_validate(const fa_fwd_params *params);
  * device access; the text lives in thread-local storage until the next call on the same thread. */
 const char *fa_fwd_plan_name(const fa_fwd_params *params, int32_t num_cus);
 
-/* Test hook: the name of the plan the calling thread's most recent fa_fwd() (or fa_fwd_sink, fa_fwd_block_sparse, fa_fwd_kv8, fa_fwd_qv8) launched (same text as fa_fwd_plan_name on that
+/* Test hook: the name of the plan the calling thread's most recent fa_fwd() (or fa_fwd_sink, fa_fwd_block_sparse, fa_fwd_kv8, fa_fwd_qv8, fa_fwd_sparse_kv) launched (same text as fa_fwd_plan_name on that
  * call's params and the device's CU count; for a wide V run as several 256-column calls, the outer "... cols=N" plan).  NULL
  * before the first call or when that call failed validation; unspecified after a call that returned any other error (a failed
  * 256-column part leaves that part's plan).  fa_fwd keeps a struct copy; the text is made here, in
@@ -406,6 +406,64 @@ int fa_fwd_qv8(const fa_fwd_params *params, void *stream);
 int fa_fwd_qv8_validate(const fa_fwd_params *params);
 int64_t fa_fwd_qv8_workspace_size(const fa_fwd_params *params);
 const char *fa_fwd_qv8_plan_name(const fa_fwd_params *params, int32_t num_cus);
+
+/*
+ * Block-sparse forward over a KV cache: a decode, verify or ragged serving step that reads only the key blocks a selection step
+ * listed (Quest-style page selection, NSA-style selected blocks shared by a GQA group).  B = block_size keys per block, a
+ * positive multiple of 64; g = h / h_k; sk(b) = the fill level of batch entry b as the non-sparse routes compute it (seqused_k,
+ * clamped to the capacity, minus leftpad_k).
+ *   block_cnt  int32, logical shape (b | 1, h_k | 1)
+ *   block_idx  int32, logical shape (b | 1, h_k | 1, max_blocks), innermost stride 1
+ * on the device, read through the element strides below; a broadcast dimension is given stride 0.
+ * Key j of batch b is visible to query row i of head hd iff  j < sk(b)  AND  is_causal / window / softcap allow (i, j) exactly as
+ * on the non-sparse routes (bottom-right aligned on sk(b), FA_FLAG_FA3_WINDOW)  AND  j / B is among the first
+ * min(block_cnt[b, hd / g], max_blocks) entries of block_idx[b, hd / g, :].
+ * Lists are per KV head, shared by every query row of the call and every head of the GQA group (which is what lets the group
+ * share one pass over the cache).  Entries may come in any order (results differ by rounding only).  An entry outside
+ * [0, ceil(sk(b) / B)) is skipped without touching memory; entries at or behind the count are never used as addresses.  Distinct
+ * entries are the caller's duty: a duplicate counts twice.  A row with no visible key gives O = 0, LSE = +inf, split or not.
+ * The host never reads the lists: the call can be captured into a HIP graph, and a replay after the lists changed computes the
+ * new selection.  The callee never allocates and never synchronises.
+ * params->dtype names q / o (fp16 / bf16).  fp8_cache = 0: k / v are 16-bit elements of that type, strides in elements, descales
+ * ignored.  fp8_cache != 0: k / v point at e4m3 BYTES with byte strides, and k_descale / v_descale (fa_fwd_kv8's meaning) are
+ * both required.
+ * One kernel, sp_fwd_kernel (csrc/fa_fwd_kernel_sp.h): the packed-row body of pk_fwd_kernel / kv8_fwd_kernel walking the list in
+ * place of the key range.  List position t in [0, cnt * B / 64) is entry t / (B / 64), sub-tile t % (B / 64); the next entry is
+ * fetched one step ahead.  Served: a dense cache with seqused_k, kv_batch_idx and leftpad_k; a paged cache with any
+ * page_block_size >= 1; dense and ragged queries (cu_seqlens_q without cu_seqlens_k, seqused_k required); is_causal, both window
+ * sides, softcap; head dims <= 128 that are multiples of 16; split-KV.
+ * num_splits: 1 = off, N > 1 = N parts, 0 = what fa_fwd's heuristic gives the pk shape for a key length of max_blocks * B
+ * (shapes only).  The parts are ranges of LIST POSITIONS, not of key tiles; partials, workspace layout and the merge (one
+ * fa_fwd_combine launch) are fa_fwd_kv8's, for both cache types.
+ * FA_ERR_UNSUPPORTED, checked before anything the params may lack: dtype fp8 (the all-fp8 call), d > 128 or d % 16 != 0, d_v
+ * set and != d, qv, ALiBi, dropout, attention_chunk, s_dmask, cu_seqlens_k (and block_table beside kv_batch_idx or leftpad_k).
+ * There is no sink argument.  FA_ERR_BAD_SHAPE: block_size not a positive multiple of 64, max_blocks < 0, max_blocks *
+ * block_size >= 2^31.  FA_ERR_NULL_POINTER: a NULL list, a missing descale with fp8_cache.  FA_ERR_WORKSPACE when a split call
+ * lacks its workspace (fa_fwd_sparse_kv_workspace_size() bytes, 256-byte aligned; 0 unsplit).
+ * fa_fwd_last_plan_name() names such a call
+ *   "sp_fwd_kernel D=<64|128> waves=4[ SOFTCAP] KV=<16|e4m3> B=<block_size> block_m=128 splits=<N>";
+ * fa_fwd_sparse_kv_plan_name gives the same text from the two structs alone (num_cus decides nothing), NULL when
+ * fa_fwd_sparse_kv would reject them.
+ */
+typedef struct fa_sparse_kv_params {
+    uint32_t abi_version; /* FA_ABI_VERSION */
+    uint32_t struct_size; /* sizeof(fa_sparse_kv_params) */
+    const int32_t *block_cnt; /* device pointers, both required */
+    const int32_t *block_idx;
+    int64_t cnt_batch_stride, cnt_head_stride; /* element strides, >= 0, 0 = broadcast */
+    int64_t idx_batch_stride, idx_head_stride;
+    int32_t max_blocks; /* entries per list, >= 0 */
+    int32_t block_size; /* B: keys per block, a positive multiple of 64 */
+    int32_t fp8_cache;  /* 0: 16-bit k / v; != 0: e4m3 bytes + descales */
+    int32_t reserved;
+} fa_sparse_kv_params;
+
+int fa_fwd_sparse_kv(const fa_fwd_params *params, const fa_sparse_kv_params *sparse, void *stream);
+/* Validation only; no device access. */
+int fa_fwd_sparse_kv_validate(const fa_fwd_params *params, const fa_sparse_kv_params *sparse);
+int64_t fa_fwd_sparse_kv_workspace_size(const fa_fwd_params *params, const fa_sparse_kv_params *sparse);
+const char *fa_fwd_sparse_kv_plan_name(const fa_fwd_params *params, const fa_sparse_kv_params *sparse, int32_t num_cus);
+uint32_t fa_sparse_kv_params_size(void);
 
 /* Human-readable text for a status code (static storage). */
 const char *fa_strerror(int status);
