@@ -134,8 +134,9 @@ struct FwdArgs {
     bool pack_gqa = false;
 };
 
-// torch tensors -> fa_fwd_params -> fa_fwd on torch's current stream (q/k/v/out: last stride 1, aligned())
-void launch_fwd(const Tensor &q, const Tensor &k, const Tensor &v, const Tensor &out, const Tensor &lse, const FwdArgs &a) {
+// fa_fwd_params of one forward call: every entry point's filler -- the 16-bit and fp8 routes, the fp8-cache reads and the
+// block-sparse ones alike (q/k/v/out: last stride 1, aligned(); a KV cache: cache_aligned())
+fa_fwd_params fill_fwd_params(const Tensor &q, const Tensor &k, const Tensor &v, const Tensor &out, const Tensor &lse, const FwdArgs &a) {
     fa_fwd_params p{};
     p.abi_version = FA_ABI_VERSION;
     p.struct_size = sizeof(fa_fwd_params);
@@ -210,28 +211,70 @@ void launch_fwd(const Tensor &q, const Tensor &k, const Tensor &v, const Tensor 
         p.block_table_batch_stride = a.block_table->stride(0);
         p.page_block_size = (int32_t)k.size(1);
     }
+    return p;
+}
+
+// `need` bytes of scratch (what the entry's _workspace_size answered: fp8 expansion, split-KV partials) from torch's caching
+// allocator -- the callee never allocates -- on a 256-byte boundary; the tensor returned keeps them alive over the launch
+Tensor set_workspace(fa_fwd_params &p, int64_t need, const Tensor &like) {
     Tensor workspace;
-    const int64_t need = fa_fwd_workspace_size(&p);
-    TORCH_CHECK(need >= 0, "fa_fwd_workspace_size failed (", need, "): ", fa_strerror((int)need));
-    if (need > 0) {  // fp8 expansion / split-KV partials: scratch from torch's caching allocator (the callee never allocates)
-        workspace = at::empty({need + 256}, q.options().dtype(at::kByte));
+    if (need > 0) {
+        workspace = at::empty({need + 256}, like.options().dtype(at::kByte));
         const uintptr_t base = (reinterpret_cast<uintptr_t>(workspace.data_ptr()) + 255) / 256 * 256;
         p.workspace = reinterpret_cast<void *>(base);
         p.workspace_bytes = (uint64_t)need;
     }
-    if (a.sink.has_value()) {  // same params, same plan, same workspace: the sink rides in a struct of its own
-        fa_sink_params s{};
-        s.abi_version = FA_ABI_VERSION;
-        s.struct_size = sizeof(fa_sink_params);
-        s.learnable_sink = a.sink->data_ptr();
-        s.sink_dtype = a.sink->scalar_type() == at::kFloat ? FA_DTYPE_FP32 : FA_DTYPE_BF16;
-        s.sink_head_stride = a.sink_head_stride; s.sink_row_stride = a.sink_row_stride;
+    return workspace;
+}
+
+// the learnable sink beside the forward params: (1, 0), or the strides of FwdArgs behind the decode route's GQA swap
+fa_sink_params fill_sink_params(const Tensor &sink, int head_stride = 1, int row_stride = 0) {
+    fa_sink_params s{};
+    s.abi_version = FA_ABI_VERSION;
+    s.struct_size = sizeof(fa_sink_params);
+    s.learnable_sink = sink.data_ptr();
+    s.sink_dtype = sink.scalar_type() == at::kFloat ? FA_DTYPE_FP32 : FA_DTYPE_BF16;
+    s.sink_head_stride = head_stride; s.sink_row_stride = row_stride;
+    return s;
+}
+
+// torch tensors -> fa_fwd_params -> fa_fwd (with a sink: fa_fwd_sink, same params, same plan, same workspace) on torch's
+// current stream
+void launch_fwd(const Tensor &q, const Tensor &k, const Tensor &v, const Tensor &out, const Tensor &lse, const FwdArgs &a) {
+    fa_fwd_params p = fill_fwd_params(q, k, v, out, lse, a);
+    const int64_t need = fa_fwd_workspace_size(&p);
+    TORCH_CHECK(need >= 0, "fa_fwd_workspace_size failed (", need, "): ", fa_strerror((int)need));
+    const Tensor workspace = set_workspace(p, need, q);
+    if (a.sink.has_value()) {
+        const fa_sink_params s = fill_sink_params(*a.sink, a.sink_head_stride, a.sink_row_stride);
         const int st = fa_fwd_sink(&p, &s, current_stream(q));
         TORCH_CHECK(st == 0, "fa_fwd_sink failed (", st, "): ", fa_strerror(st));
         return;
     }
     const int st = fa_fwd(&p, current_stream(q));
     TORCH_CHECK(st == 0, "fa_fwd failed (", st, "): ", fa_strerror(st));
+}
+
+// A forward's out: the caller's tensor and the one the kernel writes -- the caller's own where it is aligned(), else a fresh
+// contiguous one of its shape and dtype (aligned() for every head dim the entry points admit: a multiple of 8 on a fresh
+// allocation), which finish() copies back
+struct OutPath {
+    Tensor given, work;
+    explicit OutPath(const Tensor &out) : given(out), work(aligned(out) ? out : at::empty(out.sizes(), out.options())) {}
+    void finish() const {
+        if (!work.is_same(given)) given.copy_(work);
+    }
+};
+
+constexpr float kInf = std::numeric_limits<float>::infinity();
+
+// The result of a problem without keys: zeros, LSE = +inf -- with a sink the logsumexp of the sink alone, its (num_heads,)
+// viewed as `lse_layout` to broadcast over the rows of this route's LSE: (1, h, 1), ragged (h, 1), behind the decode swap
+// (1, h_k, ngroups)
+void fill_empty(const Tensor &out, const Tensor &lse, const OptTensor &sink = c10::nullopt, c10::IntArrayRef lse_layout = {}) {
+    out.zero_();
+    lse.fill_(kInf);
+    if (sink.has_value()) lse.copy_(sink->to(at::kFloat).view(lse_layout));
 }
 
 std::vector<Tensor> mha_fwd(Tensor &q, const Tensor &k, const Tensor &v, OptTensor &out_, OptTensor &alibi_slopes_,
@@ -278,7 +321,7 @@ std::vector<Tensor> mha_fwd(Tensor &q, const Tensor &k, const Tensor &v, OptTens
     Tensor rng_state = dropout_state(p_dropout, gen_, q);
     if (seqlen_k > 0 && seqlen_q > 0) {
         const Tensor qc = aligned_or_copy(q), kc = aligned_or_copy(k), vc = aligned_or_copy(v);
-        Tensor oc = aligned(out) ? out : at::empty_like(qc);
+        const OutPath o(out);
         FwdArgs a;
         a.batch = batch_size; a.max_seqlen_q = seqlen_q; a.max_seqlen_k = seqlen_k;
         a.softmax_scale = softmax_scale; a.causal = is_causal; a.window_left = window_size_left; a.window_right = window_size_right;
@@ -287,11 +330,10 @@ std::vector<Tensor> mha_fwd(Tensor &q, const Tensor &k, const Tensor &v, OptTens
         if (return_softmax) a.s_dmask = p;
         a.s_dmask_block_n = sdmask_block_n(head_size, p_dropout > 0, is_causal);
         a.num_splits = p_dropout == 0.0 ? 0 : 1;  // the split heuristic runs whenever there is no dropout (:453-456)
-        launch_fwd(qc, kc, vc, oc, softmax_lse, a);
-        if (!oc.is_same(out)) out.copy_(oc);
+        launch_fwd(qc, kc, vc, o.work, softmax_lse, a);
+        o.finish();
     } else if (seqlen_q > 0) {
-        out.zero_();  // seqlen_k == 0: empty attention (:499-504)
-        softmax_lse.fill_(std::numeric_limits<float>::infinity());
+        fill_empty(out, softmax_lse);  // seqlen_k == 0: empty attention (:499-504)
     }
     return {out, softmax_lse, p, rng_state};
 }
@@ -372,11 +414,11 @@ std::vector<Tensor> mha_varlen_fwd(Tensor &q, const Tensor &k, const Tensor &v, 
     Tensor rng_state = dropout_state(p_dropout, gen_, q);
     if (zero_tensors) {
         out.zero_();
-        softmax_lse.fill_(-std::numeric_limits<float>::infinity());
+        softmax_lse.fill_(-kInf);
     }
     if (max_seqlen_k > 0 && total_q > 0 && max_seqlen_q > 0) {
         const Tensor qc = aligned_or_copy(q), kc = aligned_or_copy(k), vc = aligned_or_copy(v);
-        Tensor oc = aligned(out) ? out : at::empty_like(qc);
+        const OutPath o(out);
         FwdArgs a;
         a.varlen = true; a.batch = batch_size; a.max_seqlen_q = max_seqlen_q; a.max_seqlen_k = max_seqlen_k;
         a.softmax_scale = softmax_scale; a.causal = is_causal; a.window_left = window_size_left; a.window_right = window_size_right;
@@ -385,11 +427,10 @@ std::vector<Tensor> mha_varlen_fwd(Tensor &q, const Tensor &k, const Tensor &v, 
         if (p_dropout > 0) a.rng_state = rng_state;
         if (return_softmax) a.s_dmask = p;
         a.s_dmask_block_n = sdmask_block_n(head_size, p_dropout > 0, is_causal);
-        launch_fwd(qc, kc, vc, oc, softmax_lse, a);
-        if (!oc.is_same(out)) out.copy_(oc);
+        launch_fwd(qc, kc, vc, o.work, softmax_lse, a);
+        o.finish();
     } else if (total_q > 0) {
-        out.zero_();
-        softmax_lse.fill_(std::numeric_limits<float>::infinity());
+        fill_empty(out, softmax_lse);
     }
     return {out, softmax_lse, p, rng_state};
 }
@@ -933,8 +974,8 @@ std::vector<Tensor> fwd_kvcache_core(Tensor q, const Tensor &kcache, const Tenso
     if (rotary)
         qc = rotate_q(qc, c10::nullopt, 0, *rotary_cos_, *rotary_sin_, seqlens_rotary_, *seqlens_k_, args.is_rotary_interleaved, is_causal,
                       window_size_left, window_size_right);
-    Tensor oc = aligned(out) ? out : at::empty_like(out, at::MemoryFormat::Contiguous);
     if (seqlen_k > 0) {
+        const OutPath o(out);
         FwdArgs a;
         a.batch = batch_size; a.max_seqlen_q = seqlen_q; a.max_seqlen_k = seqlen_k; a.softmax_scale = args.softmax_scale;
         a.causal = is_causal; a.window_left = window_size_left; a.window_right = window_size_right; a.softcap = args.softcap;
@@ -948,13 +989,10 @@ std::vector<Tensor> fwd_kvcache_core(Tensor q, const Tensor &kcache, const Tenso
                 a.sink_head_stride = (int)seqlen_q; a.sink_row_stride = 1;
             }
         }
-        launch_fwd(qc, kcache, vcache, oc, softmax_lse, a);
-        if (!oc.is_same(out)) out.copy_(oc);
-    } else {
-        out.zero_();
-        softmax_lse.fill_(std::numeric_limits<float>::infinity());
-        if (sink_.has_value())  // no key at all: the logsumexp of the sink alone (swapped: heads lie along (h_k, ngroups))
-            softmax_lse.copy_(swapped ? sink_->to(at::kFloat).view({1, num_heads, seqlen_q}) : sink_->to(at::kFloat).view({1, num_heads, 1}));
+        launch_fwd(qc, kcache, vcache, o.work, softmax_lse, a);
+        o.finish();
+    } else {  // (swapped: the heads lie along (h_k, ngroups))
+        fill_empty(out, softmax_lse, sink_, {1, num_heads, swapped ? seqlen_q : 1});
     }
     if (swapped) {
         out = out.transpose(1, 2).reshape({batch_size, 1, num_heads_k * seqlen_q, head_size_v});
@@ -1122,7 +1160,7 @@ std::tuple<Tensor, Tensor> fwd_kvcache_ragged(const Tensor &q, const Tensor &kca
     if (seqlen_k > 0 && max_seqlen_q > 0) {
         fa3_window(max_seqlen_q, seqlen_k, window_size_left, window_size_right);  // :796-805, on the bounds of the lengths
         if (is_causal) window_size_right = 0;
-        Tensor oc = aligned(out) ? out : at::empty_like(out, at::MemoryFormat::Contiguous);
+        const OutPath o(out);
         FwdArgs a;
         a.varlen = true; a.batch = batch_size; a.max_seqlen_q = max_seqlen_q; a.max_seqlen_k = seqlen_k;
         a.softmax_scale = softmax_scale; a.causal = is_causal; a.window_left = window_size_left; a.window_right = window_size_right;
@@ -1130,14 +1168,26 @@ std::tuple<Tensor, Tensor> fwd_kvcache_ragged(const Tensor &q, const Tensor &kca
         a.kv_batch_idx = kv_batch_idx; a.block_table = page_table; a.leftpad_k = leftpad_k; a.fa3_window = true;
         a.num_splits = (int)num_splits; a.sink = sink; a.pack_gqa = pack_gqa;
         if (qv.has_value()) a.qv = aligned_or_copy(*qv);
-        launch_fwd(qc, kcache, vcache, oc, softmax_lse, a);
-        if (!oc.is_same(out)) out.copy_(oc);
+        launch_fwd(qc, kcache, vcache, o.work, softmax_lse, a);
+        o.finish();
     } else {
-        out.zero_();
-        softmax_lse.fill_(std::numeric_limits<float>::infinity());
-        if (sink.has_value()) softmax_lse.copy_(sink->to(at::kFloat).view({num_heads, 1}));
+        fill_empty(out, softmax_lse, sink, {num_heads, 1});
     }
     return {out, softmax_lse};
+}
+
+// q of the fp8-cache step and of the block-sparse read over a cache: dense (b, s, h, d), or ragged (total_q, h, d) beside
+// cu_seqlens_q and a bound of its lengths.  (fwd_kvcache_ragged says the same under the reference's texts and keeps them.)
+void check_ragged_q(const Tensor &q, const OptTensor &cu_seqlens_q, c10::optional<int64_t> max_seqlen_q_) {
+    const bool ragged = cu_seqlens_q.has_value();
+    CHECK_DEVICE(q, "q"); CHECK_LAST_CONTIGUOUS(q, "Input tensor must have contiguous last dimension");
+    TORCH_CHECK(q.dim() == (ragged ? 3 : 4), ragged ? "q must have shape (total_q, num_heads, head_size) with cu_seqlens_q"
+                                                    : "q must have shape (batch_size, seqlen_q, num_heads, head_size)");
+    if (ragged) {
+        TORCH_CHECK(cu_seqlens_q->scalar_type() == at::kInt && cu_seqlens_q->is_contiguous() && cu_seqlens_q->is_cuda(),
+                    "cu_seqlens_q must be a contiguous int32 CUDA tensor");
+        TORCH_CHECK(max_seqlen_q_.has_value() && *max_seqlen_q_ > 0, "max_seqlen_q must be provided with cu_seqlens_q");
+    }
 }
 
 void check_kv8_descale(const Tensor &t, const char *name, int64_t batch_size, int64_t num_heads_k) {
@@ -1232,63 +1282,20 @@ std::tuple<Tensor, Tensor> fwd_kv8(const Tensor &q, const Tensor &k, const Tenso
         TORCH_CHECK(sparse->idx.size(1) == 1 || sparse->idx.size(1) == num_heads_k, "kv_block_idx must have shape (batch_size | 1, num_heads_k | 1, max_blocks)");
     }
     if (seqlen_k == 0 || seqlen_q == 0) {
-        out.zero_();
-        softmax_lse.fill_(std::numeric_limits<float>::infinity());
+        fill_empty(out, softmax_lse);
         return {out, softmax_lse};
     }
     const Tensor qc = aligned_or_copy(q);
-    Tensor oc = aligned(out) ? out : at::empty_like(out);
-    Tensor qvc;
-    fa_fwd_params p{};
-    p.abi_version = FA_ABI_VERSION;
-    p.struct_size = sizeof(fa_fwd_params);
-    p.q = qc.data_ptr(); p.k = k.data_ptr(); p.v = v.data_ptr(); p.o = oc.data_ptr();
-    p.softmax_lse = static_cast<float *>(softmax_lse.data_ptr());
-    if (mla) p.d_v = (int32_t)head_size_v;
-    if (qv.has_value()) {
-        qvc = aligned_or_copy(*qv);
-        p.qv = qvc.data_ptr();
-        p.qv_batch_stride = ragged ? 0 : qvc.stride(0);
-        p.qv_row_stride = qvc.stride(-3); p.qv_head_stride = qvc.stride(-2);
-    }
-    if (ragged) {
-        p.q_row_stride = qc.stride(0); p.q_head_stride = qc.stride(1);
-        p.o_row_stride = oc.stride(0); p.o_head_stride = oc.stride(1);
-        p.total_q = (int32_t)total_q;
-    } else {
-        p.q_batch_stride = qc.stride(0); p.q_row_stride = qc.stride(1); p.q_head_stride = qc.stride(2);
-        p.o_batch_stride = oc.stride(0); p.o_row_stride = oc.stride(1); p.o_head_stride = oc.stride(2);
-    }
-    p.k_batch_stride = k.stride(0); p.k_row_stride = k.stride(1); p.k_head_stride = k.stride(2);  // (elements = bytes)
-    p.v_batch_stride = v.stride(0); p.v_row_stride = v.stride(1); p.v_head_stride = v.stride(2);
-    p.b = (int32_t)batch_size; p.seqlen_q = (int32_t)seqlen_q; p.seqlen_k = (int32_t)seqlen_k;
-    p.h = (int32_t)num_heads; p.h_k = (int32_t)num_heads_k; p.d = (int32_t)head_size;
-    p.dtype = dtype_code(q);
-    p.cu_seqlens_q = static_cast<const int32_t *>(ptr(cu_seqlens_q));
-    p.seqused_q = static_cast<const int32_t *>(ptr(seqused_q));
-    p.seqused_k = static_cast<const int32_t *>(ptr(seqused_k));
-    p.softmax_scale = (float)softmax_scale;
-    p.softcap = (float)softcap;
-    p.is_causal = is_causal ? 1 : 0;
-    p.window_size_left = (int32_t)std::max<int64_t>(window_size_left, -1);
-    p.window_size_right = (int32_t)std::max<int64_t>(window_size_right, -1);
-    p.flags = FA_FLAG_FA3_WINDOW;
-    if (k_descale.has_value()) {
-        p.k_descale = static_cast<const float *>(k_descale->data_ptr());
-        p.k_descale_batch_stride = k_descale->stride(0); p.k_descale_head_stride = k_descale->stride(1);
-    }
-    if (v_descale.has_value()) {
-        p.v_descale = static_cast<const float *>(v_descale->data_ptr());
-        p.v_descale_batch_stride = v_descale->stride(0); p.v_descale_head_stride = v_descale->stride(1);
-    }
-    p.kv_batch_idx = static_cast<const int32_t *>(ptr(kv_batch_idx));
-    p.leftpad_k = static_cast<const int32_t *>(ptr(leftpad_k));
-    if (cache.paged) {
-        p.block_table = static_cast<const int32_t *>(page_table->data_ptr());
-        p.block_table_batch_stride = page_table->stride(0);
-        p.page_block_size = (int32_t)k.size(1);
-    }
-    p.num_splits = (int32_t)std::max<int64_t>(num_splits, 0);
+    const OutPath o(out);
+    FwdArgs a;  // (the cache's strides count elements = bytes; its 4 dims take the batched-cache branch under ragged queries)
+    a.varlen = ragged; a.batch = batch_size; a.max_seqlen_q = seqlen_q; a.max_seqlen_k = seqlen_k;
+    a.softmax_scale = softmax_scale; a.softcap = softcap; a.causal = is_causal; a.fa3_window = true;
+    a.window_left = std::max<int64_t>(window_size_left, -1); a.window_right = std::max<int64_t>(window_size_right, -1);
+    a.cu_seqlens_q = cu_seqlens_q; a.seqused_q = seqused_q; a.seqused_k = seqused_k; a.k_descale = k_descale; a.v_descale = v_descale;
+    a.kv_batch_idx = kv_batch_idx; a.leftpad_k = leftpad_k; a.block_table = page_table;
+    a.num_splits = (int)std::max<int64_t>(num_splits, 0);
+    if (qv.has_value()) a.qv = aligned_or_copy(*qv);
+    fa_fwd_params p = fill_fwd_params(qc, k, v, o.work, softmax_lse, a);
     fa_sparse_kv_params sp{};
     if (sparse) {
         sp.abi_version = FA_ABI_VERSION;
@@ -1303,19 +1310,13 @@ std::tuple<Tensor, Tensor> fwd_kv8(const Tensor &q, const Tensor &k, const Tenso
         sp.block_size = (int32_t)sparse->block_size;
         sp.fp8_cache = sparse->fp8_cache ? 1 : 0;
     }
-    Tensor workspace;
     const char *entry = sparse ? "fa_fwd_sparse_kv" : mla ? "fa_fwd_qv8" : "fa_fwd_kv8";
     const int64_t need = sparse ? fa_fwd_sparse_kv_workspace_size(&p, &sp) : mla ? fa_fwd_qv8_workspace_size(&p) : fa_fwd_kv8_workspace_size(&p);
     TORCH_CHECK(need >= 0, entry, "_workspace_size failed (", need, "): ", fa_strerror((int)need));
-    if (need > 0) {  // split-KV partials: scratch from torch's caching allocator (the callee never allocates)
-        workspace = at::empty({need + 256}, q.options().dtype(at::kByte));
-        const uintptr_t base = (reinterpret_cast<uintptr_t>(workspace.data_ptr()) + 255) / 256 * 256;
-        p.workspace = reinterpret_cast<void *>(base);
-        p.workspace_bytes = (uint64_t)need;
-    }
+    const Tensor workspace = set_workspace(p, need, q);  // split-KV partials
     const int st = sparse ? fa_fwd_sparse_kv(&p, &sp, current_stream(q)) : mla ? fa_fwd_qv8(&p, current_stream(q)) : fa_fwd_kv8(&p, current_stream(q));
     TORCH_CHECK(st == 0, entry, " failed (", st, "): ", fa_strerror(st));
-    if (!oc.is_same(out)) out.copy_(oc);
+    o.finish();
     return {out, softmax_lse};
 }
 
@@ -1357,15 +1358,7 @@ std::tuple<Tensor, Tensor> fwd_kvcache_sparse(const Tensor &q, const Tensor &k, 
     TORCH_CHECK(q.size(-1) <= 128 && q.size(-1) % 16 == 0,
                 "This flash attention build supports block-sparse attention over a KV cache for head_size <= 128 that is a multiple "
                 "of 16, got ", q.size(-1));
-    const bool ragged = cu_seqlens_q.has_value();
-    CHECK_DEVICE(q, "q"); CHECK_LAST_CONTIGUOUS(q, "Input tensor must have contiguous last dimension");
-    TORCH_CHECK(q.dim() == (ragged ? 3 : 4), ragged ? "q must have shape (total_q, num_heads, head_size) with cu_seqlens_q"
-                                                    : "q must have shape (batch_size, seqlen_q, num_heads, head_size)");
-    if (ragged) {
-        TORCH_CHECK(cu_seqlens_q->scalar_type() == at::kInt && cu_seqlens_q->is_contiguous() && cu_seqlens_q->is_cuda(),
-                    "cu_seqlens_q must be a contiguous int32 CUDA tensor");
-        TORCH_CHECK(max_seqlen_q_.has_value() && *max_seqlen_q_ > 0, "max_seqlen_q must be provided with cu_seqlens_q");
-    }
+    check_ragged_q(q, cu_seqlens_q, max_seqlen_q_);
     const double softmax_scale = softmax_scale_.has_value() ? *softmax_scale_ : 1.0 / std::sqrt((double)q.size(-1));
     const SparseLists lists{kv_block_cnt, kv_block_idx, kv_block_size, fp8_cache};
     return fwd_kv8(q, k, v, c10::nullopt, cu_seqlens_q, c10::nullopt, seqused_k, max_seqlen_q_, page_table, kv_batch_idx, leftpad_k,
@@ -1540,14 +1533,7 @@ std::tuple<Tensor, Tensor> fwd_kv8_step(const Tensor &q, const Tensor &k, const 
     }
     // q and cu_seqlens_q, once for the append, the rotary pass and the read
     const bool ragged = cu_seqlens_q.has_value();
-    CHECK_DEVICE(q, "q"); CHECK_LAST_CONTIGUOUS(q, "Input tensor must have contiguous last dimension");
-    TORCH_CHECK(q.dim() == (ragged ? 3 : 4), ragged ? "q must have shape (total_q, num_heads, head_size) with cu_seqlens_q"
-                                                    : "q must have shape (batch_size, seqlen_q, num_heads, head_size)");
-    if (ragged) {
-        TORCH_CHECK(cu_seqlens_q->scalar_type() == at::kInt && cu_seqlens_q->is_contiguous() && cu_seqlens_q->is_cuda(),
-                    "cu_seqlens_q must be a contiguous int32 CUDA tensor");
-        TORCH_CHECK(max_seqlen_q_.has_value() && *max_seqlen_q_ > 0, "max_seqlen_q must be provided with cu_seqlens_q");
-    }
+    check_ragged_q(q, cu_seqlens_q, max_seqlen_q_);
     if (mla)
         return fwd_qv8(q, k, v, qv, out_, cu_seqlens_q, seqused_q, seqused_k, max_seqlen_q_, page_table, kv_batch_idx, leftpad_k, k_descale,
                        v_descale, softmax_scale, is_causal, window_size_left, window_size_right, softcap, num_splits);
@@ -1756,7 +1742,7 @@ std::tuple<Tensor, Tensor, OptTensor, OptTensor> fa3_fwd_core(
                                 : at::empty({batch_size, num_heads, seqlen_q}, q.options().dtype(at::kFloat));
     if (seqlen_k > 0 && total_q > 0 && seqlen_q > 0) {
         const Tensor qc = aligned_or_copy(q), kc = aligned_or_copy(k), vc = aligned_or_copy(v);
-        Tensor oc = aligned(out) ? out : at::empty_like(out);
+        const OutPath o(out);
         FwdArgs a;
         a.varlen = varlen; a.batch = batch_size; a.max_seqlen_q = seqlen_q; a.max_seqlen_k = seqlen_k;
         a.softmax_scale = softmax_scale; a.causal = is_causal; a.window_left = window_size_left; a.window_right = window_size_right;
@@ -1766,12 +1752,10 @@ std::tuple<Tensor, Tensor, OptTensor, OptTensor> fa3_fwd_core(
         if (qv.has_value()) a.qv = aligned_or_copy(*qv);
         a.num_splits = cute ? (int)num_splits : 1;  // no split-KV: the decode calls of the FA3 surface take the fwd_kvcache_core routes above
         a.sink = sink; a.pack_gqa = pack_gqa;
-        launch_fwd(qc, kc, vc, oc, softmax_lse, a);
-        if (!oc.is_same(out)) out.copy_(oc);
-    } else if (total_q > 0) {
-        out.zero_();  // :1190-1194
-        softmax_lse.fill_(std::numeric_limits<float>::infinity());
-        if (sink.has_value()) softmax_lse.copy_(varlen ? sink->to(at::kFloat).view({num_heads, 1}) : sink->to(at::kFloat).view({1, num_heads, 1}));
+        launch_fwd(qc, kc, vc, o.work, softmax_lse, a);
+        o.finish();
+    } else if (total_q > 0) {  // :1190-1194
+        fill_empty(out, softmax_lse, sink, varlen ? std::vector<int64_t>{num_heads, 1} : std::vector<int64_t>{1, num_heads, 1});
     }
     return {out, softmax_lse, c10::nullopt, c10::nullopt};
 }
@@ -1943,27 +1927,15 @@ std::tuple<Tensor, Tensor> cute_fwd_block_sparse(const Tensor &q_, const Tensor 
     } else {
         given = at::empty({b, sq, h, dv}, q.options());
     }
-    Tensor out = aligned(given) ? given : at::empty({b, sq, h, dv}, q.options());
+    const OutPath o(given);
     Tensor lse = at::empty({b, h, sq}, q.options().dtype(at::kFloat));
 
-    fa_fwd_params p{};
-    p.abi_version = FA_ABI_VERSION;
-    p.struct_size = sizeof(fa_fwd_params);
-    p.q = q.data_ptr(); p.k = k.data_ptr(); p.v = v.data_ptr(); p.o = out.data_ptr();
-    p.softmax_lse = static_cast<float *>(lse.data_ptr());
-    p.q_batch_stride = q.stride(0); p.q_row_stride = q.stride(1); p.q_head_stride = q.stride(2);
-    p.k_batch_stride = k.stride(0); p.k_row_stride = k.stride(1); p.k_head_stride = k.stride(2);
-    p.v_batch_stride = v.stride(0); p.v_row_stride = v.stride(1); p.v_head_stride = v.stride(2);
-    p.o_batch_stride = out.stride(0); p.o_row_stride = out.stride(1); p.o_head_stride = out.stride(2);
-    p.b = (int32_t)b; p.seqlen_q = (int32_t)sq; p.seqlen_k = (int32_t)sk; p.h = (int32_t)h; p.h_k = (int32_t)h_k; p.d = (int32_t)d;
-    if (dv != d) p.d_v = (int32_t)dv;
-    p.dtype = dtype_code(q);
-    p.softmax_scale = (float)softmax_scale;
-    p.softcap = (float)softcap;
-    p.is_causal = is_causal ? 1 : 0;
-    p.window_size_left = (int32_t)window_size_left; p.window_size_right = (int32_t)window_size_right;
-    p.flags = FA_FLAG_FA3_WINDOW;  // a missing window side is unbounded, as on the rest of this surface
-    p.num_splits = (int32_t)num_splits;
+    FwdArgs a;
+    a.batch = b; a.max_seqlen_q = sq; a.max_seqlen_k = sk; a.softmax_scale = softmax_scale; a.softcap = softcap; a.causal = is_causal;
+    a.window_left = window_size_left; a.window_right = window_size_right;
+    a.fa3_window = true;  // a missing window side is unbounded, as on the rest of this surface
+    a.num_splits = (int)num_splits;
+    const fa_fwd_params p = fill_fwd_params(q, k, v, o.work, lse, a);
 
     fa_block_sparse_params s{};
     s.abi_version = FA_ABI_VERSION;
@@ -1980,18 +1952,12 @@ std::tuple<Tensor, Tensor> cute_fwd_block_sparse(const Tensor &q_, const Tensor 
         set_list_strides(*full_block_idx, s.full_idx_stride);
     }
     fa_sink_params sink{};
-    if (learnable_sink.has_value()) {
-        sink.abi_version = FA_ABI_VERSION;
-        sink.struct_size = sizeof(fa_sink_params);
-        sink.learnable_sink = learnable_sink->data_ptr();
-        sink.sink_dtype = learnable_sink->scalar_type() == at::kFloat ? FA_DTYPE_FP32 : FA_DTYPE_BF16;
-        sink.sink_head_stride = 1;
-    }
+    if (learnable_sink.has_value()) sink = fill_sink_params(*learnable_sink);
     const int st = fa_fwd_block_sparse(&p, &s, learnable_sink.has_value() ? &sink : nullptr, current_stream(q));
     TORCH_CHECK(st != FA_ERR_UNSUPPORTED, "fa_fwd_block_sparse: block sparsity does not go with this call (num_splits > 1, or a head dim "
                 "of V above 256): ", fa_strerror(st));
     TORCH_CHECK(st == 0, "fa_fwd_block_sparse failed (", st, "): ", fa_strerror(st));
-    if (!out.is_same(given)) given.copy_(out);
+    o.finish();
     return {given, lse};
 }
 

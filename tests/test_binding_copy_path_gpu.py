@@ -5,7 +5,11 @@ flash_attn_2_cuda.fwd_kvcache (q / out / k_new / v_new) and torch.ops.flash_attn
 tests/layouts.py (4 spare columns, or a base 4 elements off) on one operand at a time: the result is bit-equal to the contiguous
 call's, lies in the tensor the caller passed, and the sentinels around it are intact.  The KV cache itself is never copied: a
 misaligned cache raises (cache_aligned), which launches nothing.  Misaligned views only ever reach the binding here, never the
-C ABI."""
+C ABI.
+The forward routes that share that path (FwdArgs -> fill_fwd_params, OutPath) have a case each below the cache step: ragged
+queries over a 16-bit cache (fwd_kvcache_ragged), the fp8-cache read (fa_fwd_kv8), the MLA read (fa_fwd_qv8),
+fwd_kvcache_sparse over both cache types, and the cute forward with a sink and with block lists.  There q, qv and o take
+both misaligned layouts in turn; fwd_kvcache_sparse and cute_fwd take no out, so their out is compared only."""
 import pytest
 import torch
 
@@ -27,7 +31,8 @@ def _same(a, b):
 
 
 def _cases(names, outputs):
-    """[(operand that is misaligned, layout)]: every input and every output of the entry point, both misaligned layouts in turn."""
+    """[(operand that is misaligned, layout)]: every input and every output of the entry point, both misaligned layouts in turn
+    (the names in `outputs` get both layouts each: the newer cases list q and qv there too)."""
     return [(n, MIS[i % 2]) for i, n in enumerate(names + outputs)] + [(n, MIS[(i + 1) % 2]) for i, n in enumerate(outputs)]
 
 
@@ -49,8 +54,8 @@ def _run(call, t, outputs, which, layout):
         assert g.data_ptr() == outs[n].view.data_ptr() and g.stride() == outs[n].view.stride(), f"{n} is not the caller's tensor"
         assert outs[n].intact(), f"sentinels around {n} were overwritten"
         assert _same(g, w), f"{n} differs from the contiguous call with {which} {layout}"
-    for g, w in zip(got[len(outputs):], want[len(outputs):]):  # (softmax_lse)
-        assert torch.equal(g, w)
+    for g, w in zip(got[len(outputs):], want[len(outputs):]):  # (softmax_lse; out where the entry point takes none to fill)
+        assert _same(g, w) if g.dtype == torch.bfloat16 else torch.equal(g, w)
     for n, p in placed.items():
         assert p.holds(t[n]) and p.intact(), f"input {n} was written"
 
@@ -143,6 +148,90 @@ def test_kvcache_step(which, layout):
     assert _same(caches[0][0], caches[1][0]) and _same(caches[0][1], caches[1][1])
     for bi, n in enumerate(FILL):
         assert _same(caches[1][0][bi, n:n + NEW].cpu(), t["k_new"][bi]) and _same(caches[1][1][bi, n:n + NEW].cpu(), t["v_new"][bi])
+
+
+F8 = torch.float8_e4m3fn
+DV = 256                     # the latent / V head dim of the MLA shape
+
+
+def _cache(d=D, hk=HK, sk=SK, seed=3, dtype=torch.bfloat16):
+    """An aligned KV cache on the device (never misaligned here: it is never copied)."""
+    return _rand(B, sk, hk, d, seed=seed).to(dtype).to(DEV)
+
+
+def _descales(hk=HK):
+    return dict(k_descale=torch.tensor([0.5, 2.0, 1.0, 0.25], device=DEV)[:B * hk].view(B, hk),
+                v_descale=torch.tensor([2.0, 0.5, 0.25, 1.0], device=DEV)[:B * hk].view(B, hk))
+
+
+def _fa3_fwd(o, k, v, **kw):
+    from flash_attention_annotated_amd import flash_attn_3_ops  # noqa: F401
+    return torch.ops.flash_attn_3.fwd(o["q"], k, v, q_v=o.get("qv"), out=o["o"], softmax_scale=D ** -0.5, is_causal=True, **kw)[:2]
+
+
+@pytest.mark.parametrize("which,layout", _cases([], ["q", "o"]))
+def test_ragged_queries_over_cache(which, layout):
+    """fwd_kvcache_ragged: ragged q (3 and 5 rows) over a batched 16-bit cache with its fill levels."""
+    lens = (3, 5)
+    t = dict(q=_rand(sum(lens), H, D, seed=0))
+    k, v, fill = _cache(seed=3), _cache(seed=4), torch.tensor(FILL, dtype=torch.int32, device=DEV)
+    call = lambda o: _fa3_fwd(o, k, v, cu_seqlens_q=_cu(lens), seqused_k=fill, max_seqlen_q=max(lens))  # noqa: E731
+    _run(call, t, dict(o=(sum(lens), H, D)), which, layout)
+
+
+@pytest.mark.parametrize("which,layout", _cases([], ["q", "o"]))
+def test_fp8_cache_read(which, layout):
+    """fwd_kv8 (fa_fwd_kv8): 16-bit q over an e4m3 cache with both descales."""
+    t = dict(q=_rand(B, NEW, H, D, seed=0))
+    k, v, fill = _cache(seed=3, dtype=F8), _cache(seed=4, dtype=F8), torch.tensor(FILL, dtype=torch.int32, device=DEV)
+    call = lambda o: _fa3_fwd(o, k, v, seqused_k=fill, **_descales())  # noqa: E731
+    _run(call, t, dict(o=(B, NEW, H, D)), which, layout)
+
+
+@pytest.mark.parametrize("which,layout", _cases([], ["q", "qv", "o"]))
+def test_mla_read(which, layout):
+    """fwd_qv8 (fa_fwd_qv8): q (.., 64) and qv (.., 256) over an e4m3 k (.., 64) / v (.., 256) of one kv head."""
+    t = dict(q=_rand(B, 1, H, D, seed=0), qv=_rand(B, 1, H, DV, seed=1))
+    k, v = _cache(hk=1, seed=3, dtype=F8), _cache(d=DV, hk=1, seed=4, dtype=F8)
+    call = lambda o: _fa3_fwd(o, k, v, **_descales(hk=1))  # noqa: E731
+    _run(call, t, dict(o=(B, 1, H, DV)), which, layout)
+
+
+@pytest.mark.parametrize("which,layout", _cases([], ["q"]))
+@pytest.mark.parametrize("dtype", [torch.bfloat16, F8], ids=["16bit", "e4m3"])
+def test_kvcache_sparse(dtype, which, layout):
+    """fwd_kvcache_sparse (fa_fwd_sparse_kv): blocks 0 and 2 of the three 64-key blocks of the cache, one list for every kv head."""
+    from flash_attention_annotated_amd import flash_attn_3_ops  # noqa: F401
+    t = dict(q=_rand(B, NEW, H, D, seed=0))
+    k, v = _cache(sk=192, seed=3, dtype=dtype), _cache(sk=192, seed=4, dtype=dtype)
+    cnt, idx = torch.tensor([[2]], dtype=torch.int32, device=DEV), torch.tensor([[[0, 2]]], dtype=torch.int32, device=DEV)
+    kw = _descales() if dtype == F8 else {}
+    call = lambda o: torch.ops.flash_attn_3.fwd_kvcache_sparse(o["q"], k, v, cnt, idx, 64, softmax_scale=D ** -0.5, is_causal=True, **kw)  # noqa: E731
+    _run(call, t, {}, which, layout)
+
+
+@pytest.mark.parametrize("which,layout", _cases(["k", "v"], ["q"]))
+def test_cute_forward_with_sink(which, layout):
+    """cute_fwd under the positional list of cute_interface.py: the dense route of fa3_fwd_core with a learnable sink."""
+    from flash_attention_annotated_amd import _lib
+    t = {n: _rand(*s, seed=i) for i, (n, s) in enumerate(DENSE.items())}
+    sink = _rand(H, seed=7).to(DEV)
+    call = lambda o: _lib.binding().cute_fwd(o["q"], o["k"], o["v"], None, None, None, None, None, None, None, D ** -0.5, True, -1, -1,  # noqa: E731
+                                             sink, 0.0, 1, None)
+    _run(call, t, {}, which, layout)
+
+
+@pytest.mark.parametrize("which,layout", _cases(["k", "v"], ["q", "o"]))
+def test_cute_block_sparse_forward(which, layout):
+    """cute_fwd_block_sparse under the positional list of cute_interface.py (+ out): one mask list for every batch entry and head
+    that names both 128-key blocks of the one 128-row block, so every row has its answer."""
+    from flash_attention_annotated_amd import _lib
+    t = {n: _rand(*s, seed=i) for i, (n, s) in enumerate(DENSE.items())}
+    cnt = torch.tensor([[[2]]], dtype=torch.int32, device=DEV)
+    idx = torch.tensor([[[[0, 1]]]], dtype=torch.int32, device=DEV)
+    call = lambda o: _lib.binding().cute_fwd_block_sparse(o["q"], o["k"], o["v"], D ** -0.5, True, -1, -1, None, 0.0, 1, None, None,  # noqa: E731
+                                                          cnt, idx, o["o"])
+    _run(call, t, dict(o=DENSE["q"]), which, layout)
 
 
 @pytest.mark.parametrize("layout", MIS)
