@@ -1,4 +1,4 @@
-"""Build and loading of the native code: libfa_fwd_gfx950.so (the C-ABI of include/fa_fwd.h and include/fa_bwd.h) and
+"""Build and loading of the native code: libfa_fwd_gfx950.so (the C-ABI of include/fa_fwd.h, fa_bwd.h and fa_rotary.h) and
 the compiled host module flash_attn_2_cuda_C (csrc/torch_binding.cpp), which is the only host path of both operator
 surfaces.  Python launches nothing through ctypes: the struct mirrors below serve the ABI tests, `bench.py --variant`
 and the developer tools, which call the C-ABI directly.
@@ -83,6 +83,8 @@ EXPORTED_SYMBOLS = (
     "fa_bwd_block_sparse_validate",
     "fa_block_sparse_bwd_params_size",
 )
+# every symbol include/fa_rotary.h declares (csrc/fa_rotary_emb.hip)
+ROTARY_EMB_SYMBOLS = ("fa_rotary_emb", "fa_rotary_emb_validate", "fa_rotary_emb_params_size")
 
 
 class FaFwdParams(ctypes.Structure):
@@ -251,6 +253,19 @@ class FaRotaryVarlenParams(ctypes.Structure):
     )
 
 
+class FaRotaryEmbParams(ctypes.Structure):
+    """Field-for-field mirror of `struct fa_rotary_emb_params` (include/fa_rotary.h)."""
+
+    _fields_ = (
+        [("abi_version", ctypes.c_uint32), ("struct_size", ctypes.c_uint32), ("x", ctypes.c_void_p), ("out", ctypes.c_void_p)]
+        + [(f"{t}_{s}_stride", ctypes.c_int64) for t in ("x", "out") for s in ("batch", "row", "head", "dim")]
+        + [(n, ctypes.c_void_p) for n in ("cos", "sin", "cu_seqlens", "seqlen_offsets")]
+        + [("seqlen_offset", ctypes.c_int64)]
+        + [(n, ctypes.c_int32) for n in ("b", "seqlen", "total", "max_seqlen", "h", "d", "rotary_dim", "seqlen_ro", "dtype",
+                                         "cos_dtype", "sin_dtype", "offsets_int64", "interleaved", "conjugate")]
+    )
+
+
 class FaBwdParams(ctypes.Structure):
     """Field-for-field mirror of `struct fa_bwd_params` (include/fa_bwd.h)."""
 
@@ -327,7 +342,7 @@ HASH_PATH = os.path.join(_HERE, "libfa_fwd_gfx950.srchash")
 
 def _deps():
     return sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h", ".cpp"))) + [
-        os.path.join(INCLUDE, "fa_fwd.h"), os.path.join(INCLUDE, "fa_bwd.h")]
+        os.path.join(INCLUDE, "fa_fwd.h"), os.path.join(INCLUDE, "fa_bwd.h"), os.path.join(INCLUDE, "fa_rotary.h")]
 
 
 def source_hash():
@@ -351,7 +366,7 @@ def is_stale():
 def build(force=False, verbose=False):
     """Compile csrc/ for gfx950 into the in-tree shared library (hipcc cross-compiles without a GPU)."""
     srcs = [os.path.join(CSRC, f) for f in ("fa_fwd_api.hip", "fa_fwd_kv8_api.hip", "fa_fwd_qv8_api.hip", "fa_fwd_sparse_kv_api.hip", "fa_kvcache_append_kv8.hip",
-                                              "fa_kvcache_append_qv8.hip", "fa_bwd_api.hip", "fa_bwd_bs_api.hip")]
+                                              "fa_kvcache_append_qv8.hip", "fa_bwd_api.hip", "fa_bwd_bs_api.hip", "fa_rotary_emb.hip")]
     if not force and not is_stale():
         return LIB_PATH
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -538,6 +553,14 @@ def load():
     lib.fa_block_sparse_bwd_params_size.restype = ctypes.c_uint32
     if lib.fa_block_sparse_bwd_params_size() != ctypes.sizeof(FaBlockSparseBwdParams):
         raise RuntimeError("fa_block_sparse_bwd_params layout mismatch between include/fa_bwd.h and _lib.FaBlockSparseBwdParams")
+    lib.fa_rotary_emb.argtypes = [ctypes.POINTER(FaRotaryEmbParams), ctypes.c_void_p]
+    lib.fa_rotary_emb.restype = ctypes.c_int
+    lib.fa_rotary_emb_validate.argtypes = [ctypes.POINTER(FaRotaryEmbParams)]
+    lib.fa_rotary_emb_validate.restype = ctypes.c_int
+    lib.fa_rotary_emb_params_size.argtypes = []
+    lib.fa_rotary_emb_params_size.restype = ctypes.c_uint32
+    if lib.fa_rotary_emb_params_size() != ctypes.sizeof(FaRotaryEmbParams):
+        raise RuntimeError("fa_rotary_emb_params layout mismatch between include/fa_rotary.h and _lib.FaRotaryEmbParams")
     lib.fa_bwd.argtypes = [ctypes.POINTER(FaBwdParams), ctypes.c_void_p]
     lib.fa_bwd.restype = ctypes.c_int
     lib.fa_bwd_validate.argtypes = [ctypes.POINTER(FaBwdParams)]
@@ -639,6 +662,15 @@ def new_kvcache_append_kv8_params():
     p.abi_version = FA_ABI_VERSION
     p.struct_size = ctypes.sizeof(FaKvcacheAppendKv8Params)
     p.dtype = FA_DTYPE_BF16
+    return p
+
+
+def new_rotary_emb_params():
+    p = FaRotaryEmbParams()
+    p.abi_version = FA_ABI_VERSION
+    p.struct_size = ctypes.sizeof(FaRotaryEmbParams)
+    p.dtype = p.cos_dtype = p.sin_dtype = FA_DTYPE_BF16
+    p.x_dim_stride = p.out_dim_stride = 1
     return p
 
 

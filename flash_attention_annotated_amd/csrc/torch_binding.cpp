@@ -18,10 +18,12 @@
 #include <limits>
 #include <string>
 #include <tuple>
+#include <variant>
 #include <vector>
 
 #include "fa_bwd.h"
 #include "fa_fwd.h"
+#include "../../include/fa_rotary.h"  // ("fa_rotary.h" from here is the device header next to this file)
 
 namespace {
 
@@ -2142,6 +2144,79 @@ std::tuple<Tensor, Tensor> fa3_fwd_combine(const Tensor &out_partial, const Tens
     return {out, softmax_lse};
 }
 
+// The rotary embedding layer (flash_attn.layers.rotary -> apply_rotary, flash_attn/ops/triton/rotary.py:102-185): x (b, s, h, d), or
+// (total, h, d) with cu_seqlens and max_seqlen; cos / sin (seqlen_ro, rotary_dim / 2); seqlen_offsets an int or a (b) tensor of
+// int32 / int64 that stays on the device.  One launch on the current stream, no synchronisation, nothing allocated but `out`
+// (x itself with inplace): capturable in a HIP graph.  conjugate: the gradient of the rotation.
+Tensor rotary_emb(const Tensor &x, const Tensor &cos_, const Tensor &sin_, const std::variant<Tensor, int64_t> &seqlen_offsets,
+                  const OptTensor &cu_seqlens_, c10::optional<int64_t> max_seqlen, bool interleaved, bool inplace, bool conjugate) {
+    CHECK_DEVICE(x, "x"); CHECK_DEVICE(cos_, "cos"); CHECK_DEVICE(sin_, "sin");
+    const auto type = x.scalar_type();
+    TORCH_CHECK(type == at::kHalf || type == at::kBFloat16 || type == at::kFloat, "rotary_emb only supports fp16, bf16 and fp32 x");
+    const bool varlen = cu_seqlens_.has_value();
+    int64_t batch, seqlen;
+    Tensor cu_seqlens;
+    if (!varlen) {
+        TORCH_CHECK(x.dim() == 4, "x must have shape (batch, seqlen, nheads, headdim)");
+        batch = x.size(0); seqlen = x.size(1);
+    } else {
+        TORCH_CHECK(max_seqlen.has_value(), "If cu_seqlens is passed in, then max_seqlen must be passed");
+        TORCH_CHECK(x.dim() == 3, "x must have shape (total_seqlen, nheads, headdim) with cu_seqlens");
+        CHECK_DEVICE(*cu_seqlens_, "cu_seqlens");
+        TORCH_CHECK(cu_seqlens_->scalar_type() == at::kInt && cu_seqlens_->dim() == 1 && cu_seqlens_->numel() >= 1,
+                    "cu_seqlens must be an int32 tensor of shape (batch + 1)");
+        cu_seqlens = cu_seqlens_->contiguous();
+        batch = cu_seqlens.numel() - 1; seqlen = *max_seqlen;
+        TORCH_CHECK(seqlen > 0, "max_seqlen must be positive");
+    }
+    const int64_t nheads = x.size(-2), headdim = x.size(-1);
+    TORCH_CHECK(cos_.dim() == 2, "cos must have shape (seqlen_ro, rotary_dim / 2)");
+    TORCH_CHECK(sin_.sizes() == cos_.sizes(), "sin must have the shape of cos");
+    TORCH_CHECK(cos_.scalar_type() == sin_.scalar_type(), "cos and sin must have the same dtype");
+    TORCH_CHECK(cos_.scalar_type() == type || cos_.scalar_type() == at::kFloat, "cos and sin must have the dtype of x or fp32");
+    const int64_t seqlen_ro = cos_.size(0), rotary_dim = 2 * cos_.size(1);
+    TORCH_CHECK(rotary_dim > 0, "rotary_dim must be positive");
+    TORCH_CHECK(rotary_dim <= headdim, "rotary_dim must be <= headdim");
+    TORCH_CHECK(headdim <= 256, "Only support headdim <= 256");
+    TORCH_CHECK(seqlen_ro >= seqlen, "seqlen_ro must be >= seqlen");
+    TORCH_CHECK(x.numel() == 0 || (batch <= INT32_MAX && seqlen <= INT32_MAX && x.size(0) <= INT32_MAX && nheads <= INT32_MAX &&
+                                   seqlen_ro <= INT32_MAX), "rotary_emb: a dimension of 2^31 or more");
+    c10::hip::HIPGuardMasqueradingAsCUDA device_guard(x.device());
+    const Tensor cos = cos_.contiguous(), sin = sin_.contiguous();
+    Tensor offsets;
+    fa_rotary_emb_params p{};
+    if (const Tensor *t = std::get_if<Tensor>(&seqlen_offsets)) {
+        CHECK_DEVICE(*t, "seqlen_offsets");
+        TORCH_CHECK(t->dim() == 1 && t->size(0) == batch, "seqlen_offsets must have shape (batch)");
+        TORCH_CHECK(t->scalar_type() == at::kInt || t->scalar_type() == at::kLong, "seqlen_offsets must have dtype int32 or int64");
+        offsets = t->contiguous();
+        p.seqlen_offsets = offsets.data_ptr();
+        p.offsets_int64 = offsets.scalar_type() == at::kLong ? 1 : 0;
+    } else {
+        p.seqlen_offset = std::get<int64_t>(seqlen_offsets);
+        TORCH_CHECK(p.seqlen_offset + seqlen <= seqlen_ro, "seqlen_offsets + seqlen must be <= seqlen_ro");
+    }
+    Tensor out = inplace ? x : at::empty_like(x);
+    if (x.numel() == 0) return out;
+    p.abi_version = FA_ABI_VERSION;
+    p.struct_size = sizeof(fa_rotary_emb_params);
+    p.x = x.data_ptr(); p.out = out.data_ptr();
+    p.x_batch_stride = varlen ? 0 : x.stride(0); p.out_batch_stride = varlen ? 0 : out.stride(0);
+    p.x_row_stride = x.stride(-3); p.x_head_stride = x.stride(-2); p.x_dim_stride = x.stride(-1);
+    p.out_row_stride = out.stride(-3); p.out_head_stride = out.stride(-2); p.out_dim_stride = out.stride(-1);
+    p.cos = cos.data_ptr(); p.sin = sin.data_ptr();
+    p.cu_seqlens = varlen ? static_cast<const int32_t *>(cu_seqlens.data_ptr()) : nullptr;
+    p.b = (int32_t)batch; p.seqlen = varlen ? 0 : (int32_t)seqlen; p.total = varlen ? (int32_t)x.size(0) : 0;
+    p.max_seqlen = varlen ? (int32_t)seqlen : 0;
+    p.h = (int32_t)nheads; p.d = (int32_t)headdim; p.rotary_dim = (int32_t)rotary_dim; p.seqlen_ro = (int32_t)seqlen_ro;
+    p.dtype = type == at::kFloat ? FA_DTYPE_FP32 : dtype_code(x);
+    p.cos_dtype = p.sin_dtype = cos.scalar_type() == at::kFloat ? FA_DTYPE_FP32 : dtype_code(cos);
+    p.interleaved = interleaved ? 1 : 0; p.conjugate = conjugate ? 1 : 0;
+    const int st = fa_rotary_emb(&p, current_stream(x));
+    TORCH_CHECK(st == 0, "fa_rotary_emb failed (", st, "): ", fa_strerror(st));
+    return out;
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -2197,5 +2272,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("mask_block_cnt"), py::arg("mask_block_idx"), py::arg("out") = py::none());
     m.def("cute_bwd", &cute_bwd, "cute surface backward: (dq, dk, dv, dsink)");
     m.def("cute_bwd_block_sparse", &cute_bwd_block_sparse, "cute surface backward over listed 128 x 128 blocks: (dq, dk, dv, dsink)");
+    m.def("rotary_emb", &rotary_emb, "rotary embedding layer (apply_rotary): out = rotate(x), conjugate for the gradient", py::arg("x"),
+          py::arg("cos"), py::arg("sin"), py::arg("seqlen_offsets") = 0, py::arg("cu_seqlens") = py::none(), py::arg("max_seqlen") = py::none(),
+          py::arg("interleaved") = false, py::arg("inplace") = false, py::arg("conjugate") = false);
     m.def("sink_grad", &sink_grad, "gradient of a learnable sink from softmax_lse and softmax_d");
 }

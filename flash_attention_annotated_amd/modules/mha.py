@@ -1,7 +1,8 @@
 """The two attention modules of the reference that sit directly on the hot path:
 `FlashSelfAttention` / `FlashCrossAttention` (reference flash_attn/modules/mha.py:53-141, 144-228).  Same constructor
 arguments, same forward signatures; they only choose between the padded and the packed (cu_seqlens) entry point.
-The rest of that file (the MHA block with projections, rotary and the inference cache) is outside SURVEY.md §8.
+The rest of that file (the MHA block with projections and the inference cache) is outside SURVEY.md §8; the rotary layer it
+imports is `..layers.rotary`.
 """
 import torch
 import torch.nn as nn
