@@ -1,4 +1,4 @@
-"""Build and loading of the native code: libfa_fwd_gfx950.so (the C-ABI of include/fa_fwd.h, fa_bwd.h and fa_rotary.h) and
+"""Build and loading of the native code: libfa_fwd_gfx950.so (the C-ABI of include/fa_fwd.h, fa_bwd.h, fa_rotary.h and fa_norm.h) and
 the compiled host module flash_attn_2_cuda_C (csrc/torch_binding.cpp), which is the only host path of both operator
 surfaces.  Python launches nothing through ctypes: the struct mirrors below serve the ABI tests, `bench.py --variant`
 and the developer tools, which call the C-ABI directly.
@@ -85,6 +85,10 @@ EXPORTED_SYMBOLS = (
 )
 # every symbol include/fa_rotary.h declares (csrc/fa_rotary_emb.hip)
 ROTARY_EMB_SYMBOLS = ("fa_rotary_emb", "fa_rotary_emb_validate", "fa_rotary_emb_params_size")
+# every symbol include/fa_norm.h declares (csrc/fa_norm.hip)
+NORM_SYMBOLS = ("fa_norm_fwd", "fa_norm_fwd_validate", "fa_norm_fwd_params_size", "fa_norm_bwd", "fa_norm_bwd_validate",
+                "fa_norm_bwd_params_size", "fa_norm_bwd_workspace_bytes")
+FA_NORM_RMS, FA_NORM_ZERO_CENTERED = 1, 2
 
 
 class FaFwdParams(ctypes.Structure):
@@ -266,6 +270,34 @@ class FaRotaryEmbParams(ctypes.Structure):
     )
 
 
+class FaNormFwdParams(ctypes.Structure):
+    """Field-for-field mirror of `struct fa_norm_fwd_params` (include/fa_norm.h)."""
+
+    _fields_ = (
+        [("abi_version", ctypes.c_uint32), ("struct_size", ctypes.c_uint32)]
+        + [(n, ctypes.c_void_p) for n in ("x", "residual", "weight", "bias", "rowscale", "y", "residual_out", "mean", "rstd")]
+        + [(f"{t}_row_stride", ctypes.c_int64) for t in ("x", "residual", "y", "residual_out")]
+        + [("M", ctypes.c_int64), ("N", ctypes.c_int32)]
+        + [(f"{t}_dtype", ctypes.c_int32) for t in ("x", "residual", "residual_out", "weight", "bias", "y", "rowscale")]
+        + [("eps", ctypes.c_float), ("flags", ctypes.c_int32)]
+    )
+
+
+class FaNormBwdParams(ctypes.Structure):
+    """Field-for-field mirror of `struct fa_norm_bwd_params` (include/fa_norm.h)."""
+
+    _fields_ = (
+        [("abi_version", ctypes.c_uint32), ("struct_size", ctypes.c_uint32)]
+        + [(n, ctypes.c_void_p) for n in ("x", "dy", "weight", "bias", "dresidual", "rowscale", "mean", "rstd", "dx", "dresidual_in",
+                                          "dw", "db", "y", "workspace")]
+        + [("workspace_bytes", ctypes.c_uint64)]
+        + [(f"{t}_row_stride", ctypes.c_int64) for t in ("x", "dy", "dresidual", "dx", "dresidual_in", "y")]
+        + [("M", ctypes.c_int64), ("N", ctypes.c_int32)]
+        + [(f"{t}_dtype", ctypes.c_int32) for t in ("x", "dy", "weight", "bias", "dresidual", "dresidual_in", "dx", "y", "rowscale")]
+        + [("eps", ctypes.c_float), ("flags", ctypes.c_int32)]
+    )
+
+
 class FaBwdParams(ctypes.Structure):
     """Field-for-field mirror of `struct fa_bwd_params` (include/fa_bwd.h)."""
 
@@ -342,7 +374,8 @@ HASH_PATH = os.path.join(_HERE, "libfa_fwd_gfx950.srchash")
 
 def _deps():
     return sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h", ".cpp"))) + [
-        os.path.join(INCLUDE, "fa_fwd.h"), os.path.join(INCLUDE, "fa_bwd.h"), os.path.join(INCLUDE, "fa_rotary.h")]
+        os.path.join(INCLUDE, "fa_fwd.h"), os.path.join(INCLUDE, "fa_bwd.h"), os.path.join(INCLUDE, "fa_rotary.h"),
+        os.path.join(INCLUDE, "fa_norm.h")]
 
 
 def source_hash():
@@ -366,7 +399,7 @@ def is_stale():
 def build(force=False, verbose=False):
     """Compile csrc/ for gfx950 into the in-tree shared library (hipcc cross-compiles without a GPU)."""
     srcs = [os.path.join(CSRC, f) for f in ("fa_fwd_api.hip", "fa_fwd_kv8_api.hip", "fa_fwd_qv8_api.hip", "fa_fwd_sparse_kv_api.hip", "fa_kvcache_append_kv8.hip",
-                                              "fa_kvcache_append_qv8.hip", "fa_bwd_api.hip", "fa_bwd_bs_api.hip", "fa_rotary_emb.hip")]
+                                              "fa_kvcache_append_qv8.hip", "fa_bwd_api.hip", "fa_bwd_bs_api.hip", "fa_rotary_emb.hip", "fa_norm.hip")]
     if not force and not is_stale():
         return LIB_PATH
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -561,6 +594,17 @@ def load():
     lib.fa_rotary_emb_params_size.restype = ctypes.c_uint32
     if lib.fa_rotary_emb_params_size() != ctypes.sizeof(FaRotaryEmbParams):
         raise RuntimeError("fa_rotary_emb_params layout mismatch between include/fa_rotary.h and _lib.FaRotaryEmbParams")
+    for name, struct in (("fwd", FaNormFwdParams), ("bwd", FaNormBwdParams)):
+        launch, validate, size = (getattr(lib, f"fa_norm_{name}{s}") for s in ("", "_validate", "_params_size"))
+        launch.argtypes = [ctypes.POINTER(struct), ctypes.c_void_p]
+        validate.argtypes = [ctypes.POINTER(struct)]
+        launch.restype = validate.restype = ctypes.c_int
+        size.argtypes = []
+        size.restype = ctypes.c_uint32
+        if size() != ctypes.sizeof(struct):
+            raise RuntimeError(f"fa_norm_{name}_params layout mismatch between include/fa_norm.h and _lib.{struct.__name__}")
+    lib.fa_norm_bwd_workspace_bytes.argtypes = [ctypes.POINTER(FaNormBwdParams)]
+    lib.fa_norm_bwd_workspace_bytes.restype = ctypes.c_uint64
     lib.fa_bwd.argtypes = [ctypes.POINTER(FaBwdParams), ctypes.c_void_p]
     lib.fa_bwd.restype = ctypes.c_int
     lib.fa_bwd_validate.argtypes = [ctypes.POINTER(FaBwdParams)]
@@ -671,6 +715,25 @@ def new_rotary_emb_params():
     p.struct_size = ctypes.sizeof(FaRotaryEmbParams)
     p.dtype = p.cos_dtype = p.sin_dtype = FA_DTYPE_BF16
     p.x_dim_stride = p.out_dim_stride = 1
+    return p
+
+
+def new_norm_fwd_params():
+    p = FaNormFwdParams()
+    p.abi_version = FA_ABI_VERSION
+    p.struct_size = ctypes.sizeof(FaNormFwdParams)
+    for t in ("x", "residual", "residual_out", "weight", "bias", "y", "rowscale"):
+        setattr(p, f"{t}_dtype", FA_DTYPE_BF16)
+    p.eps = 1e-6
+    return p
+
+
+def new_norm_bwd_params():
+    p = FaNormBwdParams()
+    p.abi_version = FA_ABI_VERSION
+    p.struct_size = ctypes.sizeof(FaNormBwdParams)
+    for t in ("x", "dy", "weight", "bias", "dresidual", "dresidual_in", "dx", "y", "rowscale"):
+        setattr(p, f"{t}_dtype", FA_DTYPE_BF16)
     return p
 
 

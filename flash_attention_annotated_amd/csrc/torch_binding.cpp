@@ -24,6 +24,7 @@
 #include "fa_bwd.h"
 #include "fa_fwd.h"
 #include "../../include/fa_rotary.h"  // ("fa_rotary.h" from here is the device header next to this file)
+#include "fa_norm.h"
 
 namespace {
 
@@ -2217,6 +2218,150 @@ Tensor rotary_emb(const Tensor &x, const Tensor &cos_, const Tensor &sin_, const
     return out;
 }
 
+// ---- fused residual-add + LayerNorm / RMSNorm (flash_attn.ops.triton.layer_norm -> _layer_norm_fwd_impl / _layer_norm_bwd_impl,
+// flash_attn/ops/triton/layer_norm.py:355-468, 702-843, without dropout and the parallel form).  Launches on the current stream,
+// no synchronisation; mean / rstd, the gradients and the workspace come from the caching allocator: capturable in a HIP graph.
+int norm_dtype_code(at::ScalarType t, const char *what) {
+    if (t == at::kHalf) return FA_DTYPE_FP16;
+    if (t == at::kBFloat16) return FA_DTYPE_BF16;
+    if (t == at::kFloat) return FA_DTYPE_FP32;
+    TORCH_CHECK(false, "layer_norm: ", what, " must be fp16, bf16 or fp32");
+    return -1;
+}
+
+at::ScalarType norm_scalar_type(int64_t code) {
+    TORCH_CHECK(code == FA_DTYPE_FP16 || code == FA_DTYPE_BF16 || code == FA_DTYPE_FP32, "layer_norm: unknown dtype code");
+    return code == FA_DTYPE_FP16 ? at::kHalf : code == FA_DTYPE_BF16 ? at::kBFloat16 : at::kFloat;
+}
+
+void check_norm_rows(const Tensor &t, const char *name, int64_t M, int64_t N) {
+    TORCH_CHECK(t.is_cuda(), "layer_norm: ", name, " must be on CUDA");
+    TORCH_CHECK(t.dim() == 2 && t.size(0) == M && t.size(1) == N, "layer_norm: ", name, " must have shape (M, N)");
+    TORCH_CHECK(t.stride(-1) == 1, "layer_norm: ", name, " must have contiguous last dimension");
+}
+
+void check_norm_vector(const Tensor &t, const char *name, int64_t n, const char *shape) {
+    TORCH_CHECK(t.is_cuda(), "layer_norm: ", name, " must be on CUDA");
+    TORCH_CHECK(t.dim() == 1 && t.size(0) == n, "layer_norm: ", name, " must have shape ", shape);
+    TORCH_CHECK(t.is_contiguous(), "layer_norm: ", name, " must be contiguous");
+}
+
+void check_norm_width(const Tensor &x) {
+    TORCH_CHECK_WITH(Error, x.size(1) * x.element_size() <= FA_NORM_MAX_ROW_BYTES, "This layer norm doesn't support feature dim >= 64KB.");
+    TORCH_CHECK(x.size(1) >= 1, "layer_norm: the feature dim must be at least 1");
+}
+
+// y and (optionally) residual_out are written in place; returns (mean, rstd), mean empty with is_rms_norm
+std::tuple<Tensor, Tensor> norm_fwd(const Tensor &x, const Tensor &weight, const OptTensor &bias, const OptTensor &residual,
+                                    const OptTensor &rowscale, Tensor out, OptTensor residual_out, double eps,
+                                    bool zero_centered_weight, bool is_rms_norm) {
+    TORCH_CHECK(x.is_cuda(), "layer_norm: x must be on CUDA");
+    TORCH_CHECK(x.dim() == 2, "layer_norm: x must have shape (M, N)");
+    const int64_t M = x.size(0), N = x.size(1);
+    check_norm_rows(x, "x", M, N);
+    check_norm_rows(out, "out", M, N);
+    check_norm_vector(weight, "weight", N, "(N)");
+    if (bias.has_value()) check_norm_vector(*bias, "bias", N, "(N)");
+    if (residual.has_value()) check_norm_rows(*residual, "residual", M, N);
+    if (residual_out.has_value()) check_norm_rows(*residual_out, "residual_out", M, N);
+    if (rowscale.has_value()) check_norm_vector(*rowscale, "rowscale", M, "(M)");
+    check_norm_width(x);
+    fa_norm_fwd_params p{};
+    p.abi_version = FA_ABI_VERSION;
+    p.struct_size = sizeof(fa_norm_fwd_params);
+    p.x_dtype = norm_dtype_code(x.scalar_type(), "x");
+    p.weight_dtype = norm_dtype_code(weight.scalar_type(), "weight");
+    p.y_dtype = norm_dtype_code(out.scalar_type(), "out");
+    p.bias_dtype = bias.has_value() ? norm_dtype_code(bias->scalar_type(), "bias") : p.weight_dtype;
+    p.residual_dtype = residual.has_value() ? norm_dtype_code(residual->scalar_type(), "residual") : p.x_dtype;
+    p.residual_out_dtype = residual_out.has_value() ? norm_dtype_code(residual_out->scalar_type(), "residual_out") : p.x_dtype;
+    p.rowscale_dtype = rowscale.has_value() ? norm_dtype_code(rowscale->scalar_type(), "rowscale") : p.x_dtype;
+    TORCH_CHECK(p.residual_dtype == p.x_dtype || p.residual_dtype == FA_DTYPE_FP32, "layer_norm: residual must have the dtype of x or fp32");
+    TORCH_CHECK(p.residual_out_dtype == p.x_dtype || p.residual_out_dtype == FA_DTYPE_FP32,
+                "layer_norm: residual_out must have the dtype of x or fp32");
+    c10::hip::HIPGuardMasqueradingAsCUDA device_guard(x.device());
+    const auto stats = x.options().dtype(at::kFloat);
+    Tensor mean = at::empty({is_rms_norm ? 0 : M}, stats), rstd = at::empty({M}, stats);
+    if (M == 0) return {mean, rstd};
+    p.x = x.data_ptr(); p.weight = weight.data_ptr(); p.bias = ptr(bias); p.residual = ptr(residual); p.rowscale = ptr(rowscale);
+    p.y = out.data_ptr(); p.residual_out = ptr(residual_out);
+    p.mean = is_rms_norm ? nullptr : static_cast<float *>(mean.data_ptr());
+    p.rstd = static_cast<float *>(rstd.data_ptr());
+    p.x_row_stride = x.stride(0); p.y_row_stride = out.stride(0);
+    p.residual_row_stride = residual.has_value() ? residual->stride(0) : 0;
+    p.residual_out_row_stride = residual_out.has_value() ? residual_out->stride(0) : 0;
+    p.M = M; p.N = (int32_t)N; p.eps = (float)eps;
+    p.flags = (is_rms_norm ? FA_NORM_RMS : 0) | (zero_centered_weight ? FA_NORM_ZERO_CENTERED : 0);
+    const int st = fa_norm_fwd(&p, current_stream(x));
+    TORCH_CHECK(st == 0, "fa_norm_fwd failed (", st, "): ", fa_strerror(st));
+    return {mean, rstd};
+}
+
+// x: what the forward returned as residual_out.  Returns (dx, dw, db, dresidual_in, y); db, dresidual_in and y are empty tensors
+// where there is none (no bias; no residual, or dx serves as dresidual_in; no recompute_output)
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> norm_bwd(const Tensor &dy, const Tensor &x, const Tensor &weight, const OptTensor &bias,
+                                                            const OptTensor &mean, const Tensor &rstd, const OptTensor &dresidual,
+                                                            const OptTensor &rowscale, bool has_residual, bool zero_centered_weight,
+                                                            bool is_rms_norm, int64_t dx_dtype, bool recompute_output) {
+    TORCH_CHECK(x.is_cuda(), "layer_norm: x must be on CUDA");
+    TORCH_CHECK(x.dim() == 2, "layer_norm: x must have shape (M, N)");
+    const int64_t M = x.size(0), N = x.size(1);
+    check_norm_rows(x, "x", M, N);
+    check_norm_rows(dy, "dy", M, N);
+    check_norm_vector(weight, "weight", N, "(N)");
+    if (bias.has_value()) check_norm_vector(*bias, "bias", N, "(N)");
+    if (dresidual.has_value()) check_norm_rows(*dresidual, "dresidual", M, N);
+    if (rowscale.has_value()) check_norm_vector(*rowscale, "rowscale", M, "(M)");
+    TORCH_CHECK(is_rms_norm || mean.has_value(), "layer_norm: mean is required unless is_rms_norm");
+    if (!is_rms_norm) check_norm_vector(*mean, "mean", M, "(M)");
+    check_norm_vector(rstd, "rstd", M, "(M)");
+    TORCH_CHECK(rstd.scalar_type() == at::kFloat && (is_rms_norm || mean->scalar_type() == at::kFloat), "layer_norm: mean and rstd must be fp32");
+    check_norm_width(x);
+    fa_norm_bwd_params p{};
+    p.abi_version = FA_ABI_VERSION;
+    p.struct_size = sizeof(fa_norm_bwd_params);
+    p.x_dtype = norm_dtype_code(x.scalar_type(), "x");
+    p.dy_dtype = norm_dtype_code(dy.scalar_type(), "dy");
+    p.weight_dtype = norm_dtype_code(weight.scalar_type(), "weight");
+    p.bias_dtype = bias.has_value() ? norm_dtype_code(bias->scalar_type(), "bias") : p.weight_dtype;
+    p.dx_dtype = (int32_t)dx_dtype;
+    p.dresidual_dtype = dresidual.has_value() ? norm_dtype_code(dresidual->scalar_type(), "dresidual") : p.x_dtype;
+    p.dresidual_in_dtype = p.x_dtype;
+    p.y_dtype = p.dy_dtype;
+    p.rowscale_dtype = rowscale.has_value() ? norm_dtype_code(rowscale->scalar_type(), "rowscale") : p.x_dtype;
+    TORCH_CHECK(p.dresidual_dtype == p.x_dtype, "layer_norm: dresidual must have the dtype of x");
+    TORCH_CHECK(p.x_dtype == p.dx_dtype || p.x_dtype == FA_DTYPE_FP32, "layer_norm: x must have the dtype of dx or fp32");
+    c10::hip::HIPGuardMasqueradingAsCUDA device_guard(x.device());
+    auto none = [&] { return at::empty({0}, x.options()); };  // (one tensor each: outputs of an op do not alias)
+    Tensor dx = at::empty({M, N}, x.options().dtype(norm_scalar_type(dx_dtype)));
+    // (the reference's rule: where dx has the residual's dtype and is not scaled, it is dresidual_in)
+    const bool own_dresidual = has_residual && (p.dx_dtype != p.x_dtype || rowscale.has_value());
+    Tensor dresidual_in = own_dresidual ? at::empty({M, N}, x.options()) : none();
+    Tensor y = recompute_output ? at::empty({M, N}, dy.options()) : none();
+    Tensor dw = at::empty({N}, weight.options()), db = bias.has_value() ? at::empty({N}, bias->options()) : none();
+    if (M == 0) {  // (empty tensors have no storage to point at: no rows, zero sums, nothing of ours launched)
+        dw.zero_();
+        if (bias.has_value()) db.zero_();
+        return {dx, dw, db, dresidual_in, y};
+    }
+    p.M = M; p.N = (int32_t)N;
+    p.workspace_bytes = fa_norm_bwd_workspace_bytes(&p);
+    Tensor workspace = at::empty({(int64_t)p.workspace_bytes}, x.options().dtype(at::kByte));
+    p.workspace = p.workspace_bytes ? workspace.data_ptr() : nullptr;
+    p.x = x.data_ptr(); p.dy = dy.data_ptr(); p.weight = weight.data_ptr(); p.bias = ptr(bias); p.dresidual = ptr(dresidual);
+    p.rowscale = ptr(rowscale); p.mean = is_rms_norm ? nullptr : static_cast<const float *>(mean->data_ptr());
+    p.rstd = static_cast<const float *>(rstd.data_ptr());
+    p.dx = dx.data_ptr(); p.dresidual_in = own_dresidual ? dresidual_in.data_ptr() : nullptr;
+    p.dw = dw.data_ptr(); p.db = bias.has_value() ? db.data_ptr() : nullptr; p.y = recompute_output ? y.data_ptr() : nullptr;
+    p.x_row_stride = x.stride(0); p.dy_row_stride = dy.stride(0); p.dx_row_stride = N; p.dresidual_in_row_stride = N; p.y_row_stride = N;
+    p.dresidual_row_stride = dresidual.has_value() ? dresidual->stride(0) : 0;
+    p.eps = 0.0f;  // (rstd is read, not formed)
+    p.flags = (is_rms_norm ? FA_NORM_RMS : 0) | (zero_centered_weight ? FA_NORM_ZERO_CENTERED : 0);
+    const int st = fa_norm_bwd(&p, current_stream(x));
+    TORCH_CHECK(st == 0, "fa_norm_bwd failed (", st, "): ", fa_strerror(st));
+    return {dx, dw, db, dresidual_in, y};
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -2275,5 +2420,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("rotary_emb", &rotary_emb, "rotary embedding layer (apply_rotary): out = rotate(x), conjugate for the gradient", py::arg("x"),
           py::arg("cos"), py::arg("sin"), py::arg("seqlen_offsets") = 0, py::arg("cu_seqlens") = py::none(), py::arg("max_seqlen") = py::none(),
           py::arg("interleaved") = false, py::arg("inplace") = false, py::arg("conjugate") = false);
+    m.def("norm_fwd", &norm_fwd, "fused residual-add + LayerNorm / RMSNorm forward: writes out (and residual_out); returns (mean, rstd)",
+          py::arg("x"), py::arg("weight"), py::arg("bias"), py::arg("residual"), py::arg("rowscale"), py::arg("out"),
+          py::arg("residual_out"), py::arg("eps"), py::arg("zero_centered_weight"), py::arg("is_rms_norm"));
+    m.def("norm_bwd", &norm_bwd, "fused LayerNorm / RMSNorm backward: (dx, dw, db, dresidual_in, y)", py::arg("dy"), py::arg("x"),
+          py::arg("weight"), py::arg("bias"), py::arg("mean"), py::arg("rstd"), py::arg("dresidual"), py::arg("rowscale"),
+          py::arg("has_residual"), py::arg("zero_centered_weight"), py::arg("is_rms_norm"), py::arg("dx_dtype"),
+          py::arg("recompute_output"));
     m.def("sink_grad", &sink_grad, "gradient of a learnable sink from softmax_lse and softmax_d");
 }
