@@ -1,4 +1,4 @@
-"""Build and loading of the native code: libfa_fwd_gfx950.so (the C-ABI of include/fa_fwd.h, fa_bwd.h, fa_rotary.h and fa_norm.h) and
+"""Build and loading of the native code: libfa_fwd_gfx950.so (the C-ABI of include/fa_fwd.h, fa_bwd.h, fa_rotary.h, fa_norm.h and fa_xent.h) and
 the compiled host module flash_attn_2_cuda_C (csrc/torch_binding.cpp), which is the only host path of both operator
 surfaces.  Python launches nothing through ctypes: the struct mirrors below serve the ABI tests, `bench.py --variant`
 and the developer tools, which call the C-ABI directly.
@@ -89,6 +89,11 @@ ROTARY_EMB_SYMBOLS = ("fa_rotary_emb", "fa_rotary_emb_validate", "fa_rotary_emb_
 NORM_SYMBOLS = ("fa_norm_fwd", "fa_norm_fwd_validate", "fa_norm_fwd_params_size", "fa_norm_bwd", "fa_norm_bwd_validate",
                 "fa_norm_bwd_params_size", "fa_norm_bwd_workspace_bytes")
 FA_NORM_RMS, FA_NORM_ZERO_CENTERED = 1, 2
+# every symbol include/fa_xent.h declares (csrc/fa_xent.hip)
+XENT_SYMBOLS = ("fa_xent_fwd", "fa_xent_fwd_validate", "fa_xent_fwd_params_size", "fa_xent_bwd", "fa_xent_bwd_validate",
+                "fa_xent_bwd_params_size")
+FA_XENT_PRECOMPUTED_LSE, FA_XENT_SPLIT = 1, 2
+FA_XENT_LABELS_INT64, FA_XENT_LABELS_INT32 = 0, 1
 
 
 class FaFwdParams(ctypes.Structure):
@@ -298,6 +303,33 @@ class FaNormBwdParams(ctypes.Structure):
     )
 
 
+class FaXentFwdParams(ctypes.Structure):
+    """Field-for-field mirror of `struct fa_xent_fwd_params` (include/fa_xent.h)."""
+
+    _fields_ = (
+        [("abi_version", ctypes.c_uint32), ("struct_size", ctypes.c_uint32)]
+        + [(n, ctypes.c_void_p) for n in ("logits", "labels", "losses", "lse", "z_losses")]
+        + [(n, ctypes.c_int64) for n in ("logits_row_stride", "M", "ignore_index", "class_start_idx", "total_classes")]
+        + [(n, ctypes.c_int32) for n in ("N", "logits_dtype", "labels_dtype", "flags")]
+        + [(n, ctypes.c_float) for n in ("smoothing", "logit_scale", "lse_square_scale")]
+        + [("reserved", ctypes.c_int32)]
+    )
+
+
+class FaXentBwdParams(ctypes.Structure):
+    """Field-for-field mirror of `struct fa_xent_bwd_params` (include/fa_xent.h)."""
+
+    _fields_ = (
+        [("abi_version", ctypes.c_uint32), ("struct_size", ctypes.c_uint32)]
+        + [(n, ctypes.c_void_p) for n in ("logits", "labels", "lse", "dloss", "dlogits")]
+        + [(n, ctypes.c_int64) for n in ("logits_row_stride", "dlogits_row_stride", "dloss_stride", "M", "ignore_index",
+                                         "class_start_idx", "total_classes")]
+        + [(n, ctypes.c_int32) for n in ("N", "logits_dtype", "labels_dtype", "flags")]
+        + [(n, ctypes.c_float) for n in ("smoothing", "logit_scale", "lse_square_scale")]
+        + [("reserved", ctypes.c_int32)]
+    )
+
+
 class FaBwdParams(ctypes.Structure):
     """Field-for-field mirror of `struct fa_bwd_params` (include/fa_bwd.h)."""
 
@@ -375,7 +407,7 @@ HASH_PATH = os.path.join(_HERE, "libfa_fwd_gfx950.srchash")
 def _deps():
     return sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h", ".cpp"))) + [
         os.path.join(INCLUDE, "fa_fwd.h"), os.path.join(INCLUDE, "fa_bwd.h"), os.path.join(INCLUDE, "fa_rotary.h"),
-        os.path.join(INCLUDE, "fa_norm.h")]
+        os.path.join(INCLUDE, "fa_norm.h"), os.path.join(INCLUDE, "fa_xent.h")]
 
 
 def source_hash():
@@ -399,7 +431,7 @@ def is_stale():
 def build(force=False, verbose=False):
     """Compile csrc/ for gfx950 into the in-tree shared library (hipcc cross-compiles without a GPU)."""
     srcs = [os.path.join(CSRC, f) for f in ("fa_fwd_api.hip", "fa_fwd_kv8_api.hip", "fa_fwd_qv8_api.hip", "fa_fwd_sparse_kv_api.hip", "fa_kvcache_append_kv8.hip",
-                                              "fa_kvcache_append_qv8.hip", "fa_bwd_api.hip", "fa_bwd_bs_api.hip", "fa_rotary_emb.hip", "fa_norm.hip")]
+                                              "fa_kvcache_append_qv8.hip", "fa_bwd_api.hip", "fa_bwd_bs_api.hip", "fa_rotary_emb.hip", "fa_norm.hip", "fa_xent.hip")]
     if not force and not is_stale():
         return LIB_PATH
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -605,6 +637,15 @@ def load():
             raise RuntimeError(f"fa_norm_{name}_params layout mismatch between include/fa_norm.h and _lib.{struct.__name__}")
     lib.fa_norm_bwd_workspace_bytes.argtypes = [ctypes.POINTER(FaNormBwdParams)]
     lib.fa_norm_bwd_workspace_bytes.restype = ctypes.c_uint64
+    for name, struct in (("fwd", FaXentFwdParams), ("bwd", FaXentBwdParams)):
+        launch, validate, size = (getattr(lib, f"fa_xent_{name}{s}") for s in ("", "_validate", "_params_size"))
+        launch.argtypes = [ctypes.POINTER(struct), ctypes.c_void_p]
+        validate.argtypes = [ctypes.POINTER(struct)]
+        launch.restype = validate.restype = ctypes.c_int
+        size.argtypes = []
+        size.restype = ctypes.c_uint32
+        if size() != ctypes.sizeof(struct):
+            raise RuntimeError(f"fa_xent_{name}_params layout mismatch between include/fa_xent.h and _lib.{struct.__name__}")
     lib.fa_bwd.argtypes = [ctypes.POINTER(FaBwdParams), ctypes.c_void_p]
     lib.fa_bwd.restype = ctypes.c_int
     lib.fa_bwd_validate.argtypes = [ctypes.POINTER(FaBwdParams)]
@@ -735,6 +776,25 @@ def new_norm_bwd_params():
     for t in ("x", "dy", "weight", "bias", "dresidual", "dresidual_in", "dx", "y", "rowscale"):
         setattr(p, f"{t}_dtype", FA_DTYPE_BF16)
     return p
+
+
+def _new_xent_params(struct):
+    p = struct()
+    p.abi_version = FA_ABI_VERSION
+    p.struct_size = ctypes.sizeof(struct)
+    p.logits_dtype = FA_DTYPE_BF16
+    p.labels_dtype = FA_XENT_LABELS_INT64
+    p.ignore_index = -100
+    p.logit_scale = 1.0
+    return p
+
+
+def new_xent_fwd_params():
+    return _new_xent_params(FaXentFwdParams)
+
+
+def new_xent_bwd_params():
+    return _new_xent_params(FaXentBwdParams)
 
 
 def new_params():

@@ -25,6 +25,7 @@
 #include "fa_fwd.h"
 #include "../../include/fa_rotary.h"  // ("fa_rotary.h" from here is the device header next to this file)
 #include "fa_norm.h"
+#include "fa_xent.h"
 
 namespace {
 
@@ -2362,6 +2363,101 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> norm_bwd(const Tensor &dy, co
     return {dx, dw, db, dresidual_in, y};
 }
 
+// ---- fused cross-entropy loss (flash_attn.ops.triton.cross_entropy -> CrossEntropyLoss.forward / backward,
+// flash_attn/ops/triton/cross_entropy.py:149-289; the collectives of a vocabulary split stay in Python).  Launches on the
+// current stream, no synchronisation; losses, lse and z_losses come from the caching allocator: capturable in a HIP graph.
+int xent_dtype_code(at::ScalarType t) {
+    if (t == at::kHalf) return FA_DTYPE_FP16;
+    if (t == at::kBFloat16) return FA_DTYPE_BF16;
+    if (t == at::kFloat) return FA_DTYPE_FP32;
+    TORCH_CHECK(false, "cross_entropy: logits must be fp16, bf16 or fp32");
+    return -1;
+}
+
+int xent_labels_code(at::ScalarType t) {
+    if (t == at::kLong) return FA_XENT_LABELS_INT64;
+    if (t == at::kInt) return FA_XENT_LABELS_INT32;
+    TORCH_CHECK(false, "cross_entropy: labels must be int64 or int32");
+    return -1;
+}
+
+void check_xent_rows(const Tensor &t, const char *name) {
+    TORCH_CHECK(t.is_cuda(), "cross_entropy: ", name, " must be on CUDA");
+    TORCH_CHECK(t.dim() == 2, "cross_entropy: ", name, " must have shape (M, N)");
+    TORCH_CHECK(t.size(1) >= 1 && t.size(1) <= std::numeric_limits<int32_t>::max(), "cross_entropy: ", name, " must have 1 <= N < 2^31 columns");
+    TORCH_CHECK(t.stride(-1) == 1, "cross_entropy: ", name, " must have contiguous last dimension");
+}
+
+void check_xent_vector(const Tensor &t, const char *name, int64_t M, bool contiguous) {
+    TORCH_CHECK(t.is_cuda(), "cross_entropy: ", name, " must be on CUDA");
+    TORCH_CHECK(t.dim() == 1 && t.size(0) == M, "cross_entropy: ", name, " must have shape (M)");
+    TORCH_CHECK(!contiguous || t.is_contiguous(), "cross_entropy: ", name, " must be contiguous");
+}
+
+// (losses, lse, z_losses).  With precomputed_lse that tensor is read and the lse returned is empty; with split the columns are
+// one rank's part of total_classes, losses lack the lse and the z-loss, and the z_losses returned are empty
+std::tuple<Tensor, Tensor, Tensor> xent_fwd(const Tensor &logits, const Tensor &labels, const OptTensor &precomputed_lse, double smoothing,
+                                            double logit_scale, double lse_square_scale, int64_t ignore_index, int64_t class_start_idx,
+                                            int64_t total_classes, bool split) {
+    check_xent_rows(logits, "logits");
+    const int64_t M = logits.size(0), N = logits.size(1);
+    check_xent_vector(labels, "labels", M, true);
+    if (precomputed_lse.has_value()) {
+        check_xent_vector(*precomputed_lse, "precomputed_lse", M, true);
+        TORCH_CHECK(precomputed_lse->scalar_type() == at::kFloat, "cross_entropy: precomputed_lse must be fp32");
+    }
+    fa_xent_fwd_params p{};
+    p.abi_version = FA_ABI_VERSION;
+    p.struct_size = sizeof(fa_xent_fwd_params);
+    p.logits_dtype = xent_dtype_code(logits.scalar_type());
+    p.labels_dtype = xent_labels_code(labels.scalar_type());
+    c10::hip::HIPGuardMasqueradingAsCUDA device_guard(logits.device());
+    const auto fp32 = logits.options().dtype(at::kFloat);
+    Tensor losses = at::empty({M}, fp32), lse = at::empty({precomputed_lse.has_value() ? 0 : M}, fp32), z_losses = at::empty({split ? 0 : M}, fp32);
+    if (M == 0) return {losses, lse, z_losses};
+    p.logits = logits.data_ptr(); p.labels = labels.data_ptr();
+    p.losses = static_cast<float *>(losses.data_ptr());
+    p.lse = static_cast<float *>(precomputed_lse.has_value() ? precomputed_lse->data_ptr() : lse.data_ptr());
+    p.z_losses = split ? nullptr : static_cast<float *>(z_losses.data_ptr());
+    p.logits_row_stride = logits.stride(0);
+    p.M = M; p.N = (int32_t)N;
+    p.ignore_index = ignore_index; p.class_start_idx = class_start_idx; p.total_classes = total_classes;
+    p.smoothing = (float)smoothing; p.logit_scale = (float)logit_scale; p.lse_square_scale = (float)lse_square_scale;
+    p.flags = (precomputed_lse.has_value() ? FA_XENT_PRECOMPUTED_LSE : 0) | (split ? FA_XENT_SPLIT : 0);
+    const int st = fa_xent_fwd(&p, current_stream(logits));
+    TORCH_CHECK(st == 0, "fa_xent_fwd failed (", st, "): ", fa_strerror(st));
+    return {losses, lse, z_losses};
+}
+
+// writes dlogits, which may be logits
+void xent_bwd(const Tensor &dloss, const Tensor &logits, const Tensor &labels, const Tensor &lse, Tensor dlogits, double smoothing,
+              double logit_scale, double lse_square_scale, int64_t ignore_index, int64_t class_start_idx, int64_t total_classes) {
+    check_xent_rows(logits, "logits");
+    check_xent_rows(dlogits, "dlogits");
+    const int64_t M = logits.size(0), N = logits.size(1);
+    TORCH_CHECK(dlogits.size(0) == M && dlogits.size(1) == N, "cross_entropy: dlogits must have the shape of logits");
+    TORCH_CHECK(dlogits.scalar_type() == logits.scalar_type(), "cross_entropy: dlogits must have the dtype of logits");
+    check_xent_vector(labels, "labels", M, true);
+    check_xent_vector(lse, "lse", M, true);
+    check_xent_vector(dloss, "dloss", M, false);
+    TORCH_CHECK(lse.scalar_type() == at::kFloat && dloss.scalar_type() == at::kFloat, "cross_entropy: lse and dloss must be fp32");
+    fa_xent_bwd_params p{};
+    p.abi_version = FA_ABI_VERSION;
+    p.struct_size = sizeof(fa_xent_bwd_params);
+    p.logits_dtype = xent_dtype_code(logits.scalar_type());
+    p.labels_dtype = xent_labels_code(labels.scalar_type());
+    if (M == 0) return;
+    c10::hip::HIPGuardMasqueradingAsCUDA device_guard(logits.device());
+    p.logits = logits.data_ptr(); p.labels = labels.data_ptr(); p.dlogits = dlogits.data_ptr();
+    p.lse = static_cast<const float *>(lse.data_ptr()); p.dloss = static_cast<const float *>(dloss.data_ptr());
+    p.logits_row_stride = logits.stride(0); p.dlogits_row_stride = dlogits.stride(0); p.dloss_stride = dloss.stride(0);
+    p.M = M; p.N = (int32_t)N;
+    p.ignore_index = ignore_index; p.class_start_idx = class_start_idx; p.total_classes = total_classes;
+    p.smoothing = (float)smoothing; p.logit_scale = (float)logit_scale; p.lse_square_scale = (float)lse_square_scale;
+    const int st = fa_xent_bwd(&p, current_stream(logits));
+    TORCH_CHECK(st == 0, "fa_xent_bwd failed (", st, "): ", fa_strerror(st));
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -2427,5 +2523,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("weight"), py::arg("bias"), py::arg("mean"), py::arg("rstd"), py::arg("dresidual"), py::arg("rowscale"),
           py::arg("has_residual"), py::arg("zero_centered_weight"), py::arg("is_rms_norm"), py::arg("dx_dtype"),
           py::arg("recompute_output"));
+    m.def("xent_fwd", &xent_fwd, "fused cross-entropy forward: (losses, lse, z_losses)", py::arg("logits"), py::arg("labels"),
+          py::arg("precomputed_lse"), py::arg("smoothing"), py::arg("logit_scale"), py::arg("lse_square_scale"), py::arg("ignore_index"),
+          py::arg("class_start_idx"), py::arg("total_classes"), py::arg("split"));
+    m.def("xent_bwd", &xent_bwd, "fused cross-entropy backward: writes dlogits, which may be logits", py::arg("dloss"), py::arg("logits"),
+          py::arg("labels"), py::arg("lse"), py::arg("dlogits"), py::arg("smoothing"), py::arg("logit_scale"), py::arg("lse_square_scale"),
+          py::arg("ignore_index"), py::arg("class_start_idx"), py::arg("total_classes"));
     m.def("sink_grad", &sink_grad, "gradient of a learnable sink from softmax_lse and softmax_d");
 }

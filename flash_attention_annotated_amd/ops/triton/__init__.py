@@ -1,1 +1,2 @@
-"""The reference's import path of the fused norm (flash_attn.ops.triton.layer_norm); the kernels behind it are HIP."""
+"""The reference's import paths of the fused norm (flash_attn.ops.triton.layer_norm) and of the fused cross-entropy loss
+(flash_attn.ops.triton.cross_entropy); the kernels behind them are HIP."""
