@@ -87,11 +87,11 @@ EXPORTED_SYMBOLS = (
 ROTARY_EMB_SYMBOLS = ("fa_rotary_emb", "fa_rotary_emb_validate", "fa_rotary_emb_params_size")
 # every symbol include/fa_norm.h declares (csrc/fa_norm.hip)
 NORM_SYMBOLS = ("fa_norm_fwd", "fa_norm_fwd_validate", "fa_norm_fwd_params_size", "fa_norm_bwd", "fa_norm_bwd_validate",
-                "fa_norm_bwd_params_size", "fa_norm_bwd_workspace_bytes")
+                "fa_norm_bwd_params_size", "fa_norm_bwd_workspace_bytes", "fa_norm_fwd_plan", "fa_norm_bwd_plan")
 FA_NORM_RMS, FA_NORM_ZERO_CENTERED = 1, 2
 # every symbol include/fa_xent.h declares (csrc/fa_xent.hip)
 XENT_SYMBOLS = ("fa_xent_fwd", "fa_xent_fwd_validate", "fa_xent_fwd_params_size", "fa_xent_bwd", "fa_xent_bwd_validate",
-                "fa_xent_bwd_params_size")
+                "fa_xent_bwd_params_size", "fa_xent_fwd_plan", "fa_xent_bwd_plan")
 FA_XENT_PRECOMPUTED_LSE, FA_XENT_SPLIT = 1, 2
 FA_XENT_LABELS_INT64, FA_XENT_LABELS_INT32 = 0, 1
 
@@ -301,6 +301,18 @@ class FaNormBwdParams(ctypes.Structure):
         + [(f"{t}_dtype", ctypes.c_int32) for t in ("x", "dy", "weight", "bias", "dresidual", "dresidual_in", "dx", "y", "rowscale")]
         + [("eps", ctypes.c_float), ("flags", ctypes.c_int32)]
     )
+
+
+class FaNormPlan(ctypes.Structure):
+    """Field-for-field mirror of `struct fa_norm_plan` (include/fa_norm.h): the form a norm call takes."""
+
+    _fields_ = [(n, ctypes.c_int32) for n in ("cw", "threads", "team_wave", "wide", "rows_per_wg", "grid_x", "grid_y")]
+
+
+class FaXentPlan(ctypes.Structure):
+    """Field-for-field mirror of `struct fa_xent_plan` (include/fa_xent.h): the form a cross-entropy call takes."""
+
+    _fields_ = [(n, ctypes.c_int32) for n in ("cw", "grid_x", "grid_y", "lse_given")]
 
 
 class FaXentFwdParams(ctypes.Structure):
@@ -635,6 +647,9 @@ def load():
         size.restype = ctypes.c_uint32
         if size() != ctypes.sizeof(struct):
             raise RuntimeError(f"fa_norm_{name}_params layout mismatch between include/fa_norm.h and _lib.{struct.__name__}")
+        plan = getattr(lib, f"fa_norm_{name}_plan")
+        plan.argtypes = [ctypes.POINTER(struct), ctypes.POINTER(FaNormPlan)]
+        plan.restype = ctypes.c_int
     lib.fa_norm_bwd_workspace_bytes.argtypes = [ctypes.POINTER(FaNormBwdParams)]
     lib.fa_norm_bwd_workspace_bytes.restype = ctypes.c_uint64
     for name, struct in (("fwd", FaXentFwdParams), ("bwd", FaXentBwdParams)):
@@ -646,6 +661,9 @@ def load():
         size.restype = ctypes.c_uint32
         if size() != ctypes.sizeof(struct):
             raise RuntimeError(f"fa_xent_{name}_params layout mismatch between include/fa_xent.h and _lib.{struct.__name__}")
+        plan = getattr(lib, f"fa_xent_{name}_plan")
+        plan.argtypes = [ctypes.POINTER(struct), ctypes.POINTER(FaXentPlan)]
+        plan.restype = ctypes.c_int
     lib.fa_bwd.argtypes = [ctypes.POINTER(FaBwdParams), ctypes.c_void_p]
     lib.fa_bwd.restype = ctypes.c_int
     lib.fa_bwd_validate.argtypes = [ctypes.POINTER(FaBwdParams)]

@@ -547,7 +547,8 @@ struct Launch {
     int cw;         // 8 / 4: 16-byte accesses of x; 1: element accesses
     bool wide;      // rows of more than 1024 * cols columns
     int threads;
-    int grid;
+    int grid;       // workgroups of plan.rows_per_wg rows
+    int slabs;      // grid.y: the column slabs of a wide backward, else 1
     Plan plan;
 };
 
@@ -558,6 +559,7 @@ Launch launch_shape(int64_t M, int N, int x_dtype, bool vec, bool backward) {
     l.cw = !vec ? 1 : x_dtype == FA_DTYPE_FP32 ? 4 : 8;
     l.plan.team_wave = N <= WAVE * cols;
     l.wide = N > 1024 * cols;
+    l.slabs = backward && l.wide ? (N + 1024 * cols - 1) / (1024 * cols) : 1;
     if (l.plan.team_wave) l.threads = WAVE * WAVE_TEAMS;
     else l.threads = N <= 256 * cols ? 256 : N <= 512 * cols ? 512 : 1024;
     const int teams = l.plan.team_wave ? WAVE_TEAMS : 1;
@@ -566,6 +568,8 @@ Launch launch_shape(int64_t M, int N, int x_dtype, bool vec, bool backward) {
         rows = (M + BWD_PARTIALS - 1) / BWD_PARTIALS;
         if (rows < BWD_MIN_ROWS) rows = BWD_MIN_ROWS;
         rows = (rows + WAVE_TEAMS - 1) / WAVE_TEAMS * WAVE_TEAMS;
+    } else if (l.wide) {  // one row per workgroup
+        rows = 1;
     } else {  // enough rows to pay for reading weight and bias, enough workgroups to fill the device
         rows = M / (2048 * teams);
         rows = rows < 1 ? 1 : rows > 8 ? 8 : rows;
@@ -574,6 +578,38 @@ Launch launch_shape(int64_t M, int N, int x_dtype, bool vec, bool backward) {
     l.plan.rows_per_wg = (int32_t)rows;
     l.grid = (int)((M + rows - 1) / rows);
     return l;
+}
+
+// the launch of a valid forward call: 16-byte accesses where N and every operand's base and row pitch allow them
+Launch fwd_launch(const fa_norm_fwd_params *p) {
+    const bool vec = p->N % (p->x_dtype == FA_DTYPE_FP32 ? 4 : 8) == 0 && rows_16_bytes(p->x, p->x_dtype, p->x_row_stride) &&
+                     rows_16_bytes(p->residual, p->residual_dtype, p->residual_row_stride) &&
+                     rows_16_bytes(p->y, p->y_dtype, p->y_row_stride) &&
+                     rows_16_bytes(p->residual_out, p->residual_out_dtype, p->residual_out_row_stride) &&
+                     aligned_to(p->weight, 16) && aligned_to(p->bias, 16);
+    return launch_shape(p->M, p->N, p->x_dtype, vec, false);
+}
+
+// ... of a valid backward call (the bias is read only for y)
+Launch bwd_launch(const fa_norm_bwd_params *p) {
+    const bool vec = p->N % (p->x_dtype == FA_DTYPE_FP32 ? 4 : 8) == 0 && rows_16_bytes(p->x, p->x_dtype, p->x_row_stride) &&
+                     rows_16_bytes(p->dy, p->dy_dtype, p->dy_row_stride) &&
+                     rows_16_bytes(p->dresidual, p->dresidual_dtype, p->dresidual_row_stride) &&
+                     rows_16_bytes(p->dx, p->dx_dtype, p->dx_row_stride) &&
+                     rows_16_bytes(p->dresidual_in, p->dresidual_in_dtype, p->dresidual_in_row_stride) &&
+                     rows_16_bytes(p->y, p->y_dtype, p->y_row_stride) && aligned_to(p->weight, 16) &&
+                     (!p->y || aligned_to(p->bias, 16));
+    return launch_shape(p->M, p->N, p->x_dtype, vec, true);
+}
+
+void fill_plan(const Launch &l, fa_norm_plan *plan) {
+    plan->cw = l.cw;
+    plan->threads = l.threads;
+    plan->team_wave = l.plan.team_wave;
+    plan->wide = l.wide;
+    plan->rows_per_wg = l.plan.rows_per_wg;
+    plan->grid_x = l.grid;
+    plan->grid_y = l.slabs;
 }
 
 int64_t bwd_partials(int64_t M, int N) { return launch_shape(M, N, FA_DTYPE_BF16, false, true).grid; }
@@ -618,16 +654,11 @@ int fa_norm_fwd(const fa_norm_fwd_params *p, void *stream_) {
     const int st = fa_norm_fwd_validate(p);
     if (st != FA_OK) return st;
     if (p->M == 0) return FA_OK;  // (no zero grid)
-    const bool vec = p->N % (p->x_dtype == FA_DTYPE_FP32 ? 4 : 8) == 0 && rows_16_bytes(p->x, p->x_dtype, p->x_row_stride) &&
-                     rows_16_bytes(p->residual, p->residual_dtype, p->residual_row_stride) &&
-                     rows_16_bytes(p->y, p->y_dtype, p->y_row_stride) &&
-                     rows_16_bytes(p->residual_out, p->residual_out_dtype, p->residual_out_row_stride) &&
-                     aligned_to(p->weight, 16) && aligned_to(p->bias, 16);
-    const Launch l = launch_shape(p->M, p->N, p->x_dtype, vec, false);
+    const Launch l = fwd_launch(p);
     hipStream_t stream = static_cast<hipStream_t>(stream_);
 #define FA_NORM_FWD_LAUNCH(CW) \
     hipLaunchKernelGGL((norm_fwd_kernel<CW, FWD_COLS / CW>), dim3(l.grid), dim3(l.threads), 0, stream, *p, l.plan)
-#define FA_NORM_FWD_WIDE_LAUNCH(CW) hipLaunchKernelGGL((norm_fwd_wide_kernel<CW>), dim3((unsigned)p->M), dim3(1024), 0, stream, *p)
+#define FA_NORM_FWD_WIDE_LAUNCH(CW) hipLaunchKernelGGL((norm_fwd_wide_kernel<CW>), dim3(l.grid), dim3(l.threads), 0, stream, *p)
     if (l.wide) {  // (16-bit x: a row of fp32 has at most 1024 * FWD_COLS columns)
         if (l.cw == 8) FA_NORM_FWD_WIDE_LAUNCH(8);
         else FA_NORM_FWD_WIDE_LAUNCH(1);
@@ -645,6 +676,14 @@ uint64_t fa_norm_bwd_workspace_bytes(const fa_norm_bwd_params *p) {
     if (!p || p->M <= 0 || p->N < 1) return 0;
     const uint64_t partials = (uint64_t)bwd_partials(p->M, p->N) * (uint64_t)p->N * 2 * sizeof(float);
     return partials + (p->N > 1024 * BWD_COLS ? (uint64_t)p->M * 2 * sizeof(float) : 0);
+}
+
+int fa_norm_fwd_plan(const fa_norm_fwd_params *p, fa_norm_plan *plan) {
+    const int st = fa_norm_fwd_validate(p);
+    if (st != FA_OK) return st;
+    if (!plan) return FA_ERR_NULL_POINTER;
+    fill_plan(fwd_launch(p), plan);
+    return FA_OK;
 }
 
 int fa_norm_bwd_validate(const fa_norm_bwd_params *p) {
@@ -676,26 +715,26 @@ int fa_norm_bwd_validate(const fa_norm_bwd_params *p) {
     return FA_OK;
 }
 
+int fa_norm_bwd_plan(const fa_norm_bwd_params *p, fa_norm_plan *plan) {
+    const int st = fa_norm_bwd_validate(p);
+    if (st != FA_OK) return st;
+    if (!plan) return FA_ERR_NULL_POINTER;
+    fill_plan(bwd_launch(p), plan);
+    return FA_OK;
+}
+
 int fa_norm_bwd(const fa_norm_bwd_params *p, void *stream_) {
     const int st = fa_norm_bwd_validate(p);
     if (st != FA_OK) return st;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     int partials = 0;
     if (p->M > 0) {
-        const bool vec = p->N % (p->x_dtype == FA_DTYPE_FP32 ? 4 : 8) == 0 && rows_16_bytes(p->x, p->x_dtype, p->x_row_stride) &&
-                         rows_16_bytes(p->dy, p->dy_dtype, p->dy_row_stride) &&
-                         rows_16_bytes(p->dresidual, p->dresidual_dtype, p->dresidual_row_stride) &&
-                         rows_16_bytes(p->dx, p->dx_dtype, p->dx_row_stride) &&
-                         rows_16_bytes(p->dresidual_in, p->dresidual_in_dtype, p->dresidual_in_row_stride) &&
-                         rows_16_bytes(p->y, p->y_dtype, p->y_row_stride) && aligned_to(p->weight, 16) &&
-                         (!p->y || aligned_to(p->bias, 16));
-        const Launch l = launch_shape(p->M, p->N, p->x_dtype, vec, true);
+        const Launch l = bwd_launch(p);
         partials = l.grid;
         float *row_sums = nullptr;
-        dim3 grid(l.grid);
+        const dim3 grid(l.grid, l.slabs);
         if (l.wide) {  // the row sums first, then one workgroup per row block and slab of 1024 * BWD_COLS columns
             row_sums = static_cast<float *>(p->workspace) + (int64_t)l.grid * p->N * 2;
-            grid.y = (p->N + 1024 * BWD_COLS - 1) / (1024 * BWD_COLS);
 #define FA_NORM_BWD_SUMS_LAUNCH(CW) \
     hipLaunchKernelGGL((norm_bwd_row_sums_kernel<CW>), dim3((unsigned)p->M), dim3(1024), 0, stream, *p, row_sums)
             if (l.cw == 8) FA_NORM_BWD_SUMS_LAUNCH(8);

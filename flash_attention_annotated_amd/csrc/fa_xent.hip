@@ -26,6 +26,7 @@ constexpr int THREADS = 256;
 constexpr int WAVES = THREADS / WAVE;
 constexpr int FWD_UNROLL = 4;           // body chunks a thread has in flight, and absorbs with one rescale
 constexpr int FWD_MAX_GRID = 1 << 20;   // workgroups of the forward; further rows are walked by the same workgroups
+constexpr int LSE_GIVEN_MAX_GRID = 65536;  // ... of the lse_given forward, 256 rows each
 constexpr int BWD_CHUNKS = 4;           // body chunks per thread and slab
 constexpr int BWD_SLAB = THREADS * BWD_CHUNKS;
 constexpr int BWD_MAX_SLABS = 256;      // grid.x; further slabs are walked
@@ -343,6 +344,37 @@ int check_numbers(int64_t M, int N, int64_t total_classes, float smoothing, floa
     return FA_OK;
 }
 
+// the launch of a valid forward call
+fa_xent_plan fwd_launch(const fa_xent_fwd_params *p) {
+    fa_xent_plan l;
+    l.lse_given = (p->flags & FA_XENT_PRECOMPUTED_LSE) != 0;
+    l.grid_y = 1;
+    if (l.lse_given) {  // a thread per row, one element of it
+        const int64_t wgs = (p->M + THREADS - 1) / THREADS;
+        l.cw = 1;
+        l.grid_x = (int32_t)(wgs < LSE_GIVEN_MAX_GRID ? wgs : LSE_GIVEN_MAX_GRID);
+    } else {
+        l.cw = 16 / esize(p->logits_dtype);
+        l.grid_x = (int32_t)(p->M < FWD_MAX_GRID ? p->M : FWD_MAX_GRID);
+    }
+    return l;
+}
+
+// ... of a valid backward call: 16-byte accesses where every row of logits has the phase of the same row of dlogits
+fa_xent_plan bwd_launch(const fa_xent_bwd_params *p) {
+    fa_xent_plan l;
+    const int es = esize(p->logits_dtype), cw = 16 / es;
+    const bool vec = (reinterpret_cast<uintptr_t>(p->logits) - reinterpret_cast<uintptr_t>(p->dlogits)) % 16 == 0 &&
+                     (p->M == 1 || ((p->logits_row_stride - p->dlogits_row_stride) * es) % 16 == 0);
+    const int64_t chunks = vec ? ((int64_t)p->N + cw - 1) / cw : p->N;  // (at least the body chunks of any row)
+    const int64_t slabs = (chunks + BWD_SLAB - 1) / BWD_SLAB;
+    l.lse_given = 0;
+    l.cw = vec ? cw : 1;
+    l.grid_x = (int32_t)(slabs < BWD_MAX_SLABS ? slabs : BWD_MAX_SLABS);
+    l.grid_y = (int32_t)(p->M < BWD_MAX_ROWS ? p->M : BWD_MAX_ROWS);
+    return l;
+}
+
 }  // namespace
 
 extern "C" {
@@ -369,15 +401,20 @@ int fa_xent_fwd(const fa_xent_fwd_params *p, void *stream_) {
     if (st != FA_OK) return st;
     if (p->M == 0) return FA_OK;  // (no zero grid)
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    if (p->flags & FA_XENT_PRECOMPUTED_LSE) {
-        const int64_t wgs = (p->M + THREADS - 1) / THREADS;
-        hipLaunchKernelGGL(xent_fwd_lse_given_kernel, dim3((unsigned)(wgs < 65536 ? wgs : 65536)), dim3(THREADS), 0, stream, *p);
-    } else {
-        const dim3 grid((unsigned)(p->M < FWD_MAX_GRID ? p->M : FWD_MAX_GRID));
-        if (p->logits_dtype == FA_DTYPE_FP32) hipLaunchKernelGGL((xent_fwd_kernel<4>), grid, dim3(THREADS), 0, stream, *p);
-        else hipLaunchKernelGGL((xent_fwd_kernel<8>), grid, dim3(THREADS), 0, stream, *p);
-    }
+    const fa_xent_plan l = fwd_launch(p);
+    const dim3 grid(l.grid_x, l.grid_y);
+    if (l.lse_given) hipLaunchKernelGGL(xent_fwd_lse_given_kernel, grid, dim3(THREADS), 0, stream, *p);
+    else if (l.cw == 4) hipLaunchKernelGGL((xent_fwd_kernel<4>), grid, dim3(THREADS), 0, stream, *p);
+    else hipLaunchKernelGGL((xent_fwd_kernel<8>), grid, dim3(THREADS), 0, stream, *p);
     if (hipGetLastError() != hipSuccess) return FA_ERR_LAUNCH;
+    return FA_OK;
+}
+
+int fa_xent_fwd_plan(const fa_xent_fwd_params *p, fa_xent_plan *plan) {
+    const int st = fa_xent_fwd_validate(p);
+    if (st != FA_OK) return st;
+    if (!plan) return FA_ERR_NULL_POINTER;
+    *plan = fwd_launch(p);
     return FA_OK;
 }
 
@@ -395,20 +432,23 @@ int fa_xent_bwd_validate(const fa_xent_bwd_params *p) {
     return FA_OK;
 }
 
+int fa_xent_bwd_plan(const fa_xent_bwd_params *p, fa_xent_plan *plan) {
+    const int st = fa_xent_bwd_validate(p);
+    if (st != FA_OK) return st;
+    if (!plan) return FA_ERR_NULL_POINTER;
+    *plan = bwd_launch(p);
+    return FA_OK;
+}
+
 int fa_xent_bwd(const fa_xent_bwd_params *p, void *stream_) {
     const int st = fa_xent_bwd_validate(p);
     if (st != FA_OK) return st;
     if (p->M == 0) return FA_OK;
-    const int es = esize(p->logits_dtype), cw = 16 / es;
-    // 16-byte accesses where every row of logits has the phase of the same row of dlogits
-    const bool vec = (reinterpret_cast<uintptr_t>(p->logits) - reinterpret_cast<uintptr_t>(p->dlogits)) % 16 == 0 &&
-                     (p->M == 1 || ((p->logits_row_stride - p->dlogits_row_stride) * es) % 16 == 0);
-    const int64_t chunks = vec ? ((int64_t)p->N + cw - 1) / cw : p->N;  // (at least the body chunks of any row)
-    const int64_t slabs = (chunks + BWD_SLAB - 1) / BWD_SLAB;
-    const dim3 grid((unsigned)(slabs < BWD_MAX_SLABS ? slabs : BWD_MAX_SLABS), (unsigned)(p->M < BWD_MAX_ROWS ? p->M : BWD_MAX_ROWS));
+    const fa_xent_plan l = bwd_launch(p);
+    const dim3 grid(l.grid_x, l.grid_y);
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    if (!vec) hipLaunchKernelGGL((xent_bwd_kernel<1>), grid, dim3(THREADS), 0, stream, *p);
-    else if (cw == 4) hipLaunchKernelGGL((xent_bwd_kernel<4>), grid, dim3(THREADS), 0, stream, *p);
+    if (l.cw == 1) hipLaunchKernelGGL((xent_bwd_kernel<1>), grid, dim3(THREADS), 0, stream, *p);
+    else if (l.cw == 4) hipLaunchKernelGGL((xent_bwd_kernel<4>), grid, dim3(THREADS), 0, stream, *p);
     else hipLaunchKernelGGL((xent_bwd_kernel<8>), grid, dim3(THREADS), 0, stream, *p);
     if (hipGetLastError() != hipSuccess) return FA_ERR_LAUNCH;
     return FA_OK;

@@ -2252,10 +2252,18 @@ void check_norm_width(const Tensor &x) {
     TORCH_CHECK(x.size(1) >= 1, "layer_norm: the feature dim must be at least 1");
 }
 
-// y and (optionally) residual_out are written in place; returns (mean, rstd), mean empty with is_rms_norm
-std::tuple<Tensor, Tensor> norm_fwd(const Tensor &x, const Tensor &weight, const OptTensor &bias, const OptTensor &residual,
-                                    const OptTensor &rowscale, Tensor out, OptTensor residual_out, double eps,
-                                    bool zero_centered_weight, bool is_rms_norm) {
+py::dict norm_plan_dict(const fa_norm_plan &l) {
+    py::dict d;
+    d["cw"] = l.cw; d["threads"] = l.threads; d["team_wave"] = l.team_wave; d["wide"] = l.wide; d["rows_per_wg"] = l.rows_per_wg;
+    d["grid_x"] = l.grid_x; d["grid_y"] = l.grid_y;
+    return d;
+}
+
+// y and (optionally) residual_out are written in place; returns (mean, rstd), mean empty with is_rms_norm.  With `plan` nothing
+// is launched: the params are filled as for the launch and *plan is what fa_norm_fwd_plan says of them
+std::tuple<Tensor, Tensor> norm_fwd_impl(const Tensor &x, const Tensor &weight, const OptTensor &bias, const OptTensor &residual,
+                                         const OptTensor &rowscale, Tensor out, OptTensor residual_out, double eps,
+                                         bool zero_centered_weight, bool is_rms_norm, fa_norm_plan *plan) {
     TORCH_CHECK(x.is_cuda(), "layer_norm: x must be on CUDA");
     TORCH_CHECK(x.dim() == 2, "layer_norm: x must have shape (M, N)");
     const int64_t M = x.size(0), N = x.size(1);
@@ -2293,17 +2301,37 @@ std::tuple<Tensor, Tensor> norm_fwd(const Tensor &x, const Tensor &weight, const
     p.residual_out_row_stride = residual_out.has_value() ? residual_out->stride(0) : 0;
     p.M = M; p.N = (int32_t)N; p.eps = (float)eps;
     p.flags = (is_rms_norm ? FA_NORM_RMS : 0) | (zero_centered_weight ? FA_NORM_ZERO_CENTERED : 0);
-    const int st = fa_norm_fwd(&p, current_stream(x));
-    TORCH_CHECK(st == 0, "fa_norm_fwd failed (", st, "): ", fa_strerror(st));
+    const int st = plan ? fa_norm_fwd_plan(&p, plan) : fa_norm_fwd(&p, current_stream(x));
+    TORCH_CHECK(st == 0, plan ? "fa_norm_fwd_plan" : "fa_norm_fwd", " failed (", st, "): ", fa_strerror(st));
     return {mean, rstd};
+}
+
+std::tuple<Tensor, Tensor> norm_fwd(const Tensor &x, const Tensor &weight, const OptTensor &bias, const OptTensor &residual,
+                                    const OptTensor &rowscale, Tensor out, OptTensor residual_out, double eps,
+                                    bool zero_centered_weight, bool is_rms_norm) {
+    return norm_fwd_impl(x, weight, bias, residual, rowscale, out, residual_out, eps, zero_centered_weight, is_rms_norm, nullptr);
+}
+
+// the form norm_fwd takes with these arguments (fa_norm_plan as a dict); M >= 1.  A helper of the tests, not of a training step:
+// like norm_bwd_plan below it allocates what the launch would allocate, only to see the alignment the plan depends on
+py::dict norm_fwd_plan(const Tensor &x, const Tensor &weight, const OptTensor &bias, const OptTensor &residual,
+                       const OptTensor &rowscale, Tensor out, OptTensor residual_out, double eps, bool zero_centered_weight,
+                       bool is_rms_norm) {
+    TORCH_CHECK(x.dim() == 2 && x.size(0) >= 1, "layer_norm: a plan needs at least one row");
+    fa_norm_plan plan{};
+    norm_fwd_impl(x, weight, bias, residual, rowscale, out, residual_out, eps, zero_centered_weight, is_rms_norm, &plan);
+    return norm_plan_dict(plan);
 }
 
 // x: what the forward returned as residual_out.  Returns (dx, dw, db, dresidual_in, y); db, dresidual_in and y are empty tensors
 // where there is none (no bias; no residual, or dx serves as dresidual_in; no recompute_output)
-std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> norm_bwd(const Tensor &dy, const Tensor &x, const Tensor &weight, const OptTensor &bias,
-                                                            const OptTensor &mean, const Tensor &rstd, const OptTensor &dresidual,
-                                                            const OptTensor &rowscale, bool has_residual, bool zero_centered_weight,
-                                                            bool is_rms_norm, int64_t dx_dtype, bool recompute_output) {
+// With `plan` nothing is launched: the outputs and the workspace are allocated and the params filled as for the launch, and *plan
+// is what fa_norm_bwd_plan says of them
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> norm_bwd_impl(const Tensor &dy, const Tensor &x, const Tensor &weight, const OptTensor &bias,
+                                                                 const OptTensor &mean, const Tensor &rstd, const OptTensor &dresidual,
+                                                                 const OptTensor &rowscale, bool has_residual, bool zero_centered_weight,
+                                                                 bool is_rms_norm, int64_t dx_dtype, bool recompute_output,
+                                                                 fa_norm_plan *plan) {
     TORCH_CHECK(x.is_cuda(), "layer_norm: x must be on CUDA");
     TORCH_CHECK(x.dim() == 2, "layer_norm: x must have shape (M, N)");
     const int64_t M = x.size(0), N = x.size(1);
@@ -2358,9 +2386,28 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> norm_bwd(const Tensor &dy, co
     p.dresidual_row_stride = dresidual.has_value() ? dresidual->stride(0) : 0;
     p.eps = 0.0f;  // (rstd is read, not formed)
     p.flags = (is_rms_norm ? FA_NORM_RMS : 0) | (zero_centered_weight ? FA_NORM_ZERO_CENTERED : 0);
-    const int st = fa_norm_bwd(&p, current_stream(x));
-    TORCH_CHECK(st == 0, "fa_norm_bwd failed (", st, "): ", fa_strerror(st));
+    const int st = plan ? fa_norm_bwd_plan(&p, plan) : fa_norm_bwd(&p, current_stream(x));
+    TORCH_CHECK(st == 0, plan ? "fa_norm_bwd_plan" : "fa_norm_bwd", " failed (", st, "): ", fa_strerror(st));
     return {dx, dw, db, dresidual_in, y};
+}
+
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> norm_bwd(const Tensor &dy, const Tensor &x, const Tensor &weight, const OptTensor &bias,
+                                                            const OptTensor &mean, const Tensor &rstd, const OptTensor &dresidual,
+                                                            const OptTensor &rowscale, bool has_residual, bool zero_centered_weight,
+                                                            bool is_rms_norm, int64_t dx_dtype, bool recompute_output) {
+    return norm_bwd_impl(dy, x, weight, bias, mean, rstd, dresidual, rowscale, has_residual, zero_centered_weight, is_rms_norm, dx_dtype,
+                         recompute_output, nullptr);
+}
+
+// the form norm_bwd takes with these arguments (fa_norm_plan as a dict); M >= 1
+py::dict norm_bwd_plan(const Tensor &dy, const Tensor &x, const Tensor &weight, const OptTensor &bias, const OptTensor &mean,
+                       const Tensor &rstd, const OptTensor &dresidual, const OptTensor &rowscale, bool has_residual,
+                       bool zero_centered_weight, bool is_rms_norm, int64_t dx_dtype, bool recompute_output) {
+    TORCH_CHECK(x.dim() == 2 && x.size(0) >= 1, "layer_norm: a plan needs at least one row");
+    fa_norm_plan plan{};
+    norm_bwd_impl(dy, x, weight, bias, mean, rstd, dresidual, rowscale, has_residual, zero_centered_weight, is_rms_norm, dx_dtype,
+                  recompute_output, &plan);
+    return norm_plan_dict(plan);
 }
 
 // ---- fused cross-entropy loss (flash_attn.ops.triton.cross_entropy -> CrossEntropyLoss.forward / backward,
@@ -2394,11 +2441,18 @@ void check_xent_vector(const Tensor &t, const char *name, int64_t M, bool contig
     TORCH_CHECK(!contiguous || t.is_contiguous(), "cross_entropy: ", name, " must be contiguous");
 }
 
+py::dict xent_plan_dict(const fa_xent_plan &l) {
+    py::dict d;
+    d["cw"] = l.cw; d["grid_x"] = l.grid_x; d["grid_y"] = l.grid_y; d["lse_given"] = l.lse_given;
+    return d;
+}
+
 // (losses, lse, z_losses).  With precomputed_lse that tensor is read and the lse returned is empty; with split the columns are
 // one rank's part of total_classes, losses lack the lse and the z-loss, and the z_losses returned are empty
-std::tuple<Tensor, Tensor, Tensor> xent_fwd(const Tensor &logits, const Tensor &labels, const OptTensor &precomputed_lse, double smoothing,
-                                            double logit_scale, double lse_square_scale, int64_t ignore_index, int64_t class_start_idx,
-                                            int64_t total_classes, bool split) {
+// With `plan` nothing is launched: *plan is what fa_xent_fwd_plan says of the params the launch would get
+std::tuple<Tensor, Tensor, Tensor> xent_fwd_impl(const Tensor &logits, const Tensor &labels, const OptTensor &precomputed_lse, double smoothing,
+                                                 double logit_scale, double lse_square_scale, int64_t ignore_index, int64_t class_start_idx,
+                                                 int64_t total_classes, bool split, fa_xent_plan *plan) {
     check_xent_rows(logits, "logits");
     const int64_t M = logits.size(0), N = logits.size(1);
     check_xent_vector(labels, "labels", M, true);
@@ -2424,14 +2478,32 @@ std::tuple<Tensor, Tensor, Tensor> xent_fwd(const Tensor &logits, const Tensor &
     p.ignore_index = ignore_index; p.class_start_idx = class_start_idx; p.total_classes = total_classes;
     p.smoothing = (float)smoothing; p.logit_scale = (float)logit_scale; p.lse_square_scale = (float)lse_square_scale;
     p.flags = (precomputed_lse.has_value() ? FA_XENT_PRECOMPUTED_LSE : 0) | (split ? FA_XENT_SPLIT : 0);
-    const int st = fa_xent_fwd(&p, current_stream(logits));
-    TORCH_CHECK(st == 0, "fa_xent_fwd failed (", st, "): ", fa_strerror(st));
+    const int st = plan ? fa_xent_fwd_plan(&p, plan) : fa_xent_fwd(&p, current_stream(logits));
+    TORCH_CHECK(st == 0, plan ? "fa_xent_fwd_plan" : "fa_xent_fwd", " failed (", st, "): ", fa_strerror(st));
     return {losses, lse, z_losses};
 }
 
-// writes dlogits, which may be logits
-void xent_bwd(const Tensor &dloss, const Tensor &logits, const Tensor &labels, const Tensor &lse, Tensor dlogits, double smoothing,
-              double logit_scale, double lse_square_scale, int64_t ignore_index, int64_t class_start_idx, int64_t total_classes) {
+std::tuple<Tensor, Tensor, Tensor> xent_fwd(const Tensor &logits, const Tensor &labels, const OptTensor &precomputed_lse, double smoothing,
+                                            double logit_scale, double lse_square_scale, int64_t ignore_index, int64_t class_start_idx,
+                                            int64_t total_classes, bool split) {
+    return xent_fwd_impl(logits, labels, precomputed_lse, smoothing, logit_scale, lse_square_scale, ignore_index, class_start_idx,
+                         total_classes, split, nullptr);
+}
+
+// the form xent_fwd takes with these arguments (fa_xent_plan as a dict); M >= 1
+py::dict xent_fwd_plan(const Tensor &logits, const Tensor &labels, const OptTensor &precomputed_lse, double smoothing, double logit_scale,
+                       double lse_square_scale, int64_t ignore_index, int64_t class_start_idx, int64_t total_classes, bool split) {
+    TORCH_CHECK(logits.dim() == 2 && logits.size(0) >= 1, "cross_entropy: a plan needs at least one row");
+    fa_xent_plan plan{};
+    xent_fwd_impl(logits, labels, precomputed_lse, smoothing, logit_scale, lse_square_scale, ignore_index, class_start_idx, total_classes,
+                  split, &plan);
+    return xent_plan_dict(plan);
+}
+
+// writes dlogits, which may be logits.  With `plan` nothing is launched: *plan is what fa_xent_bwd_plan says of the params
+void xent_bwd_impl(const Tensor &dloss, const Tensor &logits, const Tensor &labels, const Tensor &lse, Tensor dlogits, double smoothing,
+                   double logit_scale, double lse_square_scale, int64_t ignore_index, int64_t class_start_idx, int64_t total_classes,
+                   fa_xent_plan *plan) {
     check_xent_rows(logits, "logits");
     check_xent_rows(dlogits, "dlogits");
     const int64_t M = logits.size(0), N = logits.size(1);
@@ -2454,8 +2526,24 @@ void xent_bwd(const Tensor &dloss, const Tensor &logits, const Tensor &labels, c
     p.M = M; p.N = (int32_t)N;
     p.ignore_index = ignore_index; p.class_start_idx = class_start_idx; p.total_classes = total_classes;
     p.smoothing = (float)smoothing; p.logit_scale = (float)logit_scale; p.lse_square_scale = (float)lse_square_scale;
-    const int st = fa_xent_bwd(&p, current_stream(logits));
-    TORCH_CHECK(st == 0, "fa_xent_bwd failed (", st, "): ", fa_strerror(st));
+    const int st = plan ? fa_xent_bwd_plan(&p, plan) : fa_xent_bwd(&p, current_stream(logits));
+    TORCH_CHECK(st == 0, plan ? "fa_xent_bwd_plan" : "fa_xent_bwd", " failed (", st, "): ", fa_strerror(st));
+}
+
+void xent_bwd(const Tensor &dloss, const Tensor &logits, const Tensor &labels, const Tensor &lse, Tensor dlogits, double smoothing,
+              double logit_scale, double lse_square_scale, int64_t ignore_index, int64_t class_start_idx, int64_t total_classes) {
+    xent_bwd_impl(dloss, logits, labels, lse, dlogits, smoothing, logit_scale, lse_square_scale, ignore_index, class_start_idx,
+                  total_classes, nullptr);
+}
+
+// the form xent_bwd takes with these arguments (fa_xent_plan as a dict); M >= 1
+py::dict xent_bwd_plan(const Tensor &dloss, const Tensor &logits, const Tensor &labels, const Tensor &lse, Tensor dlogits, double smoothing,
+                       double logit_scale, double lse_square_scale, int64_t ignore_index, int64_t class_start_idx, int64_t total_classes) {
+    TORCH_CHECK(logits.dim() == 2 && logits.size(0) >= 1, "cross_entropy: a plan needs at least one row");
+    fa_xent_plan plan{};
+    xent_bwd_impl(dloss, logits, labels, lse, dlogits, smoothing, logit_scale, lse_square_scale, ignore_index, class_start_idx,
+                  total_classes, &plan);
+    return xent_plan_dict(plan);
 }
 
 }  // namespace
@@ -2529,5 +2617,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("xent_bwd", &xent_bwd, "fused cross-entropy backward: writes dlogits, which may be logits", py::arg("dloss"), py::arg("logits"),
           py::arg("labels"), py::arg("lse"), py::arg("dlogits"), py::arg("smoothing"), py::arg("logit_scale"), py::arg("lse_square_scale"),
           py::arg("ignore_index"), py::arg("class_start_idx"), py::arg("total_classes"));
+    m.def("norm_fwd_plan", &norm_fwd_plan, "the form norm_fwd takes with these arguments: fa_norm_plan as a dict, nothing launched",
+          py::arg("x"), py::arg("weight"), py::arg("bias"), py::arg("residual"), py::arg("rowscale"), py::arg("out"),
+          py::arg("residual_out"), py::arg("eps"), py::arg("zero_centered_weight"), py::arg("is_rms_norm"));
+    m.def("norm_bwd_plan", &norm_bwd_plan, "the form norm_bwd takes with these arguments: fa_norm_plan as a dict, nothing launched",
+          py::arg("dy"), py::arg("x"), py::arg("weight"), py::arg("bias"), py::arg("mean"), py::arg("rstd"), py::arg("dresidual"),
+          py::arg("rowscale"), py::arg("has_residual"), py::arg("zero_centered_weight"), py::arg("is_rms_norm"), py::arg("dx_dtype"),
+          py::arg("recompute_output"));
+    m.def("xent_fwd_plan", &xent_fwd_plan, "the form xent_fwd takes with these arguments: fa_xent_plan as a dict, nothing launched",
+          py::arg("logits"), py::arg("labels"), py::arg("precomputed_lse"), py::arg("smoothing"), py::arg("logit_scale"),
+          py::arg("lse_square_scale"), py::arg("ignore_index"), py::arg("class_start_idx"), py::arg("total_classes"), py::arg("split"));
+    m.def("xent_bwd_plan", &xent_bwd_plan, "the form xent_bwd takes with these arguments: fa_xent_plan as a dict, nothing launched",
+          py::arg("dloss"), py::arg("logits"), py::arg("labels"), py::arg("lse"), py::arg("dlogits"), py::arg("smoothing"),
+          py::arg("logit_scale"), py::arg("lse_square_scale"), py::arg("ignore_index"), py::arg("class_start_idx"),
+          py::arg("total_classes"));
     m.def("sink_grad", &sink_grad, "gradient of a learnable sink from softmax_lse and softmax_d");
 }

@@ -96,12 +96,9 @@ def _flat(t, written=False):
     return t if t.stride(-1) == 1 else t.contiguous()
 
 
-def _launch_forward(x, weight, bias, eps, residual=None, rowscale=None, out_dtype=None, stream_dtype=None,
-                    zero_centered_weight=False, is_rms_norm=False, out=None, residual_out=None):
-    """x (M, N) -> (y, stream, mean, rstd); mean is None for RMS.  `stream` is the new residual stream, x * rowscale + residual
-    in stream_dtype (the residual's dtype where there is one): a tensor of its own when that differs from x in value or dtype,
-    or when the caller gave residual_out; otherwise x itself.  y and the stream are allocated here, not in the custom op,
-    which neither returns an argument nor sees an output that aliases an input."""
+def _forward_operands(x, residual, rowscale, out_dtype, stream_dtype, out, residual_out):
+    """(out, residual_out) of a forward launch: y and the stream are allocated here, not in the custom op, which neither returns
+    an argument nor sees an output that aliases an input.  residual_out stays None where the stream is x itself."""
     _check_width(x)
     if residual is not None:
         stream_dtype = residual.dtype
@@ -114,8 +111,25 @@ def _launch_forward(x, weight, bias, eps, residual=None, rowscale=None, out_dtyp
             raise ValueError(f"residual_out must be of the residual stream's dtype, {stream_dtype}")
     elif residual is not None or stream_dtype != x.dtype or rowscale is not None:
         residual_out = torch.empty_like(x, dtype=stream_dtype)
+    return out, residual_out
+
+
+def _launch_forward(x, weight, bias, eps, residual=None, rowscale=None, out_dtype=None, stream_dtype=None,
+                    zero_centered_weight=False, is_rms_norm=False, out=None, residual_out=None):
+    """x (M, N) -> (y, stream, mean, rstd); mean is None for RMS.  `stream` is the new residual stream, x * rowscale + residual
+    in stream_dtype (the residual's dtype where there is one): a tensor of its own when that differs from x in value or dtype,
+    or when the caller gave residual_out; otherwise x itself."""
+    out, residual_out = _forward_operands(x, residual, rowscale, out_dtype, stream_dtype, out, residual_out)
     mean, rstd = _norm_fwd(x, weight, bias, residual, rowscale, out, residual_out, eps, zero_centered_weight, is_rms_norm)
     return out, x if residual_out is None else residual_out, None if is_rms_norm else mean, rstd
+
+
+def _plan_forward(x, weight, bias, eps, residual=None, rowscale=None, out_dtype=None, stream_dtype=None,
+                  zero_centered_weight=False, is_rms_norm=False, out=None, residual_out=None):
+    """The form _launch_forward takes with these tensors, launching nothing: fa_norm_plan (include/fa_norm.h) as a dict.  Outputs
+    not given are allocated as the launch allocates them: the plan depends on the alignment of every operand."""
+    out, residual_out = _forward_operands(x, residual, rowscale, out_dtype, stream_dtype, out, residual_out)
+    return _binding().norm_fwd_plan(x, weight, bias, residual, rowscale, out, residual_out, eps, zero_centered_weight, is_rms_norm)
 
 
 def _launch_backward(dy, stream, weight, bias, mean, rstd, dresidual=None, rowscale=None, has_residual=False,
@@ -131,6 +145,14 @@ def _launch_backward(dy, stream, weight, bias, mean, rstd, dresidual=None, rowsc
     elif not _own_dresidual(has_residual, stream, code, rowscale):
         dresidual_in = dx
     return dx, dw, db if bias is not None else None, dresidual_in, y if recompute_output else None
+
+
+def _plan_backward(dy, stream, weight, bias, mean, rstd, dresidual=None, rowscale=None, has_residual=False,
+                   zero_centered_weight=False, is_rms_norm=False, dx_dtype=None, recompute_output=False):
+    """The form _launch_backward takes with these tensors, launching nothing: fa_norm_plan as a dict (grid_y: the column slabs)."""
+    _check_width(stream)
+    return _binding().norm_bwd_plan(_flat(dy), stream, weight, bias, mean, rstd, _flat(dresidual), rowscale, has_residual,
+                                    zero_centered_weight, is_rms_norm, _DTYPE_CODE[dx_dtype or stream.dtype], recompute_output)
 
 
 # ---- pure torch: the oracle ---------------------------------------------------------------------------------------------------

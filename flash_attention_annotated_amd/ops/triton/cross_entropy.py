@@ -72,6 +72,22 @@ def _xent_bwd_inplace_fake(dloss, logits, labels, lse, smoothing, logit_scale, l
     return None
 
 
+def _plan_forward(logits, labels, precomputed_lse=None, smoothing=0.0, logit_scale=1.0, lse_square_scale=0.0, ignore_index=-100,
+                  class_start_idx=0, total_classes=None, split=False):
+    """The form _xent_fwd takes with these tensors, launching nothing: fa_xent_plan (include/fa_xent.h) as a dict."""
+    total_classes = logits.shape[1] if total_classes is None else total_classes
+    return _binding().xent_fwd_plan(logits, labels, precomputed_lse, smoothing, logit_scale, lse_square_scale, ignore_index,
+                                    class_start_idx, total_classes, split)
+
+
+def _plan_backward(dloss, logits, labels, lse, dlogits, smoothing=0.0, logit_scale=1.0, lse_square_scale=0.0, ignore_index=-100,
+                   class_start_idx=0, total_classes=None):
+    """The form the backward takes writing into `dlogits` (logits itself: in place), launching nothing: fa_xent_plan as a dict."""
+    total_classes = logits.shape[1] if total_classes is None else total_classes
+    return _binding().xent_bwd_plan(dloss, logits, labels, lse, dlogits, smoothing, logit_scale, lse_square_scale, ignore_index,
+                                    class_start_idx, total_classes)
+
+
 # ---- pure torch: the oracle --------------------------------------------------------------------------------------------------
 def _working(logits):
     return logits if logits.dtype == torch.float64 else logits.float()

@@ -102,6 +102,19 @@ uint64_t fa_norm_bwd_workspace_bytes(const fa_norm_bwd_params *params);
 uint32_t fa_norm_fwd_params_size(void);
 uint32_t fa_norm_bwd_params_size(void);
 
+/* The form a call takes, filled by the host function the launch itself consumes; no device.  cw: 8 / 4 (16-byte accesses of a
+ * 16-bit / fp32 x) or 1 (element accesses).  threads: of a workgroup; team_wave: a row is the work of one wavefront of it, else
+ * of all of it.  wide: rows beyond the registers of 1024 threads (one row per workgroup in the forward; row sums in a launch of
+ * their own and column slabs in the backward).  grid_x workgroups of rows_per_wg rows; grid_y: column slabs, 1 unless wide
+ * backward. */
+typedef struct fa_norm_plan {
+    int32_t cw, threads, team_wave, wide, rows_per_wg, grid_x, grid_y;
+} fa_norm_plan;
+/* validate first: its status on failure, and *plan untouched.  M = 0 is valid and launches nothing of the rows: the plan then
+ * has grid_x = 0 */
+int fa_norm_fwd_plan(const fa_norm_fwd_params *params, fa_norm_plan *plan);
+int fa_norm_bwd_plan(const fa_norm_bwd_params *params, fa_norm_plan *plan);
+
 #ifdef __cplusplus
 }
 #endif

@@ -105,6 +105,18 @@ int fa_xent_bwd(const fa_xent_bwd_params *params, void *stream);
 uint32_t fa_xent_fwd_params_size(void);
 uint32_t fa_xent_bwd_params_size(void);
 
+/* The form a call takes, filled by the host function the launch itself consumes; no device.  cw: elements per body chunk (8 / 4:
+ * 16-byte accesses with an element head and tail; 1: element accesses, and the one load of the lse_given kernel).  Forward:
+ * grid_x workgroups walk the rows, grid_y = 1.  Backward: grid_x slabs of 1024 chunks, grid_y rows; what is beyond is walked. */
+typedef struct fa_xent_plan {
+    int32_t cw, grid_x, grid_y;
+    int32_t lse_given; /* forward with FA_XENT_PRECOMPUTED_LSE: a thread per row */
+} fa_xent_plan;
+/* validate first: its status on failure, and *plan untouched.  M = 0 is valid and launches nothing: the plan then has no rows,
+ * grid_x = 0 forward and grid_y = 0 backward */
+int fa_xent_fwd_plan(const fa_xent_fwd_params *params, fa_xent_plan *plan);
+int fa_xent_bwd_plan(const fa_xent_bwd_params *params, fa_xent_plan *plan);
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,7 +13,7 @@ ADDR = 0x10000  # an aligned dummy address: nothing is dereferenced
 OK, NULLP, BAD_DTYPE, BAD_SHAPE, BAD_STRIDE, BAD_ABI, WORKSPACE = 0, -1, -2, -5, -6, -9, -11
 BF16, FP16, FP32, FP8 = _lib.FA_DTYPE_BF16, _lib.FA_DTYPE_FP16, _lib.FA_DTYPE_FP32, _lib.FA_DTYPE_FP8_E4M3
 SYMBOLS = ("fa_norm_fwd", "fa_norm_fwd_validate", "fa_norm_fwd_params_size", "fa_norm_bwd", "fa_norm_bwd_validate",
-           "fa_norm_bwd_params_size", "fa_norm_bwd_workspace_bytes")
+           "fa_norm_bwd_params_size", "fa_norm_bwd_workspace_bytes", "fa_norm_fwd_plan", "fa_norm_bwd_plan")
 
 
 def _fwd(M=111, N=192, **fields):

@@ -15,7 +15,7 @@ BF16, FP16, FP32, FP8 = _lib.FA_DTYPE_BF16, _lib.FA_DTYPE_FP16, _lib.FA_DTYPE_FP
 INT64, INT32 = _lib.FA_XENT_LABELS_INT64, _lib.FA_XENT_LABELS_INT32
 GIVEN, SPLIT = _lib.FA_XENT_PRECOMPUTED_LSE, _lib.FA_XENT_SPLIT
 SYMBOLS = ("fa_xent_fwd", "fa_xent_fwd_validate", "fa_xent_fwd_params_size", "fa_xent_bwd", "fa_xent_bwd_validate",
-           "fa_xent_bwd_params_size")
+           "fa_xent_bwd_params_size", "fa_xent_fwd_plan", "fa_xent_bwd_plan")
 
 
 def _fwd(M=37, N=4096, **fields):
