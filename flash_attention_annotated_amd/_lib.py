@@ -1,4 +1,4 @@
-"""Build and loading of the native code: libfa_fwd_gfx950.so (the C-ABI of include/fa_fwd.h, fa_bwd.h, fa_rotary.h, fa_norm.h and fa_xent.h) and
+"""Build and loading of the native code: libfa_fwd_gfx950.so (the C-ABI of include/fa_fwd.h, fa_bwd.h, fa_rotary.h, fa_norm.h, fa_xent.h and fa_act.h) and
 the compiled host module flash_attn_2_cuda_C (csrc/torch_binding.cpp), which is the only host path of both operator
 surfaces.  Python launches nothing through ctypes: the struct mirrors below serve the ABI tests, `bench.py --variant`
 and the developer tools, which call the C-ABI directly.
@@ -94,6 +94,11 @@ XENT_SYMBOLS = ("fa_xent_fwd", "fa_xent_fwd_validate", "fa_xent_fwd_params_size"
                 "fa_xent_bwd_params_size", "fa_xent_fwd_plan", "fa_xent_bwd_plan")
 FA_XENT_PRECOMPUTED_LSE, FA_XENT_SPLIT = 1, 2
 FA_XENT_LABELS_INT64, FA_XENT_LABELS_INT32 = 0, 1
+# every symbol include/fa_act.h declares (csrc/fa_act.hip)
+ACT_SYMBOLS = ("fa_act_fwd", "fa_act_fwd_validate", "fa_act_fwd_params_size", "fa_act_bwd", "fa_act_bwd_validate",
+               "fa_act_bwd_params_size", "fa_act_bwd_workspace_bytes", "fa_act_fwd_plan", "fa_act_bwd_plan")
+FA_ACT_GELU_TANH, FA_ACT_GELU_ERF, FA_ACT_RELU, FA_ACT_SQRELU, FA_ACT_SILU, FA_ACT_SIGMOID, FA_ACT_IDENTITY = range(7)
+FA_ACT_GATED = 1
 
 
 class FaFwdParams(ctypes.Structure):
@@ -342,6 +347,36 @@ class FaXentBwdParams(ctypes.Structure):
     )
 
 
+class FaActPlan(ctypes.Structure):
+    """Field-for-field mirror of `struct fa_act_plan` (include/fa_act.h): the form an activation call takes."""
+
+    _fields_ = [(n, ctypes.c_int32) for n in ("cw", "threads", "grid_x", "grid_y", "rows_per_wg")]
+
+
+class FaActFwdParams(ctypes.Structure):
+    """Field-for-field mirror of `struct fa_act_fwd_params` (include/fa_act.h)."""
+
+    _fields_ = (
+        [("abi_version", ctypes.c_uint32), ("struct_size", ctypes.c_uint32)]
+        + [(n, ctypes.c_void_p) for n in ("pre", "up", "bias", "out")]
+        + [(n, ctypes.c_int64) for n in ("pre_row_stride", "out_row_stride", "M")]
+        + [(n, ctypes.c_int32) for n in ("H", "activation", "flags", "pre_dtype", "up_dtype", "bias_dtype", "out_dtype", "reserved")]
+    )
+
+
+class FaActBwdParams(ctypes.Structure):
+    """Field-for-field mirror of `struct fa_act_bwd_params` (include/fa_act.h)."""
+
+    _fields_ = (
+        [("abi_version", ctypes.c_uint32), ("struct_size", ctypes.c_uint32)]
+        + [(n, ctypes.c_void_p) for n in ("pre", "up", "bias", "dout", "dpre", "dup", "dbias", "recompute_out", "workspace")]
+        + [("workspace_bytes", ctypes.c_uint64)]
+        + [(n, ctypes.c_int64) for n in ("pre_row_stride", "dout_row_stride", "dpre_row_stride", "out_row_stride", "M")]
+        + [(n, ctypes.c_int32) for n in ("H", "activation", "flags", "pre_dtype", "up_dtype", "bias_dtype", "dout_dtype", "dpre_dtype",
+                                         "dup_dtype", "dbias_dtype", "out_dtype", "reserved")]
+    )
+
+
 class FaBwdParams(ctypes.Structure):
     """Field-for-field mirror of `struct fa_bwd_params` (include/fa_bwd.h)."""
 
@@ -419,7 +454,7 @@ HASH_PATH = os.path.join(_HERE, "libfa_fwd_gfx950.srchash")
 def _deps():
     return sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h", ".cpp"))) + [
         os.path.join(INCLUDE, "fa_fwd.h"), os.path.join(INCLUDE, "fa_bwd.h"), os.path.join(INCLUDE, "fa_rotary.h"),
-        os.path.join(INCLUDE, "fa_norm.h"), os.path.join(INCLUDE, "fa_xent.h")]
+        os.path.join(INCLUDE, "fa_norm.h"), os.path.join(INCLUDE, "fa_xent.h"), os.path.join(INCLUDE, "fa_act.h")]
 
 
 def source_hash():
@@ -443,7 +478,7 @@ def is_stale():
 def build(force=False, verbose=False):
     """Compile csrc/ for gfx950 into the in-tree shared library (hipcc cross-compiles without a GPU)."""
     srcs = [os.path.join(CSRC, f) for f in ("fa_fwd_api.hip", "fa_fwd_kv8_api.hip", "fa_fwd_qv8_api.hip", "fa_fwd_sparse_kv_api.hip", "fa_kvcache_append_kv8.hip",
-                                              "fa_kvcache_append_qv8.hip", "fa_bwd_api.hip", "fa_bwd_bs_api.hip", "fa_rotary_emb.hip", "fa_norm.hip", "fa_xent.hip")]
+                                              "fa_kvcache_append_qv8.hip", "fa_bwd_api.hip", "fa_bwd_bs_api.hip", "fa_rotary_emb.hip", "fa_norm.hip", "fa_xent.hip", "fa_act.hip")]
     if not force and not is_stale():
         return LIB_PATH
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -664,6 +699,20 @@ def load():
         plan = getattr(lib, f"fa_xent_{name}_plan")
         plan.argtypes = [ctypes.POINTER(struct), ctypes.POINTER(FaXentPlan)]
         plan.restype = ctypes.c_int
+    for name, struct in (("fwd", FaActFwdParams), ("bwd", FaActBwdParams)):
+        launch, validate, size = (getattr(lib, f"fa_act_{name}{s}") for s in ("", "_validate", "_params_size"))
+        launch.argtypes = [ctypes.POINTER(struct), ctypes.c_void_p]
+        validate.argtypes = [ctypes.POINTER(struct)]
+        launch.restype = validate.restype = ctypes.c_int
+        size.argtypes = []
+        size.restype = ctypes.c_uint32
+        if size() != ctypes.sizeof(struct):
+            raise RuntimeError(f"fa_act_{name}_params layout mismatch between include/fa_act.h and _lib.{struct.__name__}")
+        plan = getattr(lib, f"fa_act_{name}_plan")
+        plan.argtypes = [ctypes.POINTER(struct), ctypes.POINTER(FaActPlan)]
+        plan.restype = ctypes.c_int
+    lib.fa_act_bwd_workspace_bytes.argtypes = [ctypes.POINTER(FaActBwdParams)]
+    lib.fa_act_bwd_workspace_bytes.restype = ctypes.c_uint64
     lib.fa_bwd.argtypes = [ctypes.POINTER(FaBwdParams), ctypes.c_void_p]
     lib.fa_bwd.restype = ctypes.c_int
     lib.fa_bwd_validate.argtypes = [ctypes.POINTER(FaBwdParams)]
@@ -813,6 +862,23 @@ def new_xent_fwd_params():
 
 def new_xent_bwd_params():
     return _new_xent_params(FaXentBwdParams)
+
+
+def _new_act_params(struct, dtypes):
+    p = struct()
+    p.abi_version = FA_ABI_VERSION
+    p.struct_size = ctypes.sizeof(struct)
+    for t in dtypes:
+        setattr(p, f"{t}_dtype", FA_DTYPE_BF16)
+    return p
+
+
+def new_act_fwd_params():
+    return _new_act_params(FaActFwdParams, ("pre", "up", "bias", "out"))
+
+
+def new_act_bwd_params():
+    return _new_act_params(FaActBwdParams, ("pre", "up", "bias", "dout", "dpre", "dup", "dbias", "out"))
 
 
 def new_params():

@@ -26,6 +26,7 @@
 #include "../../include/fa_rotary.h"  // ("fa_rotary.h" from here is the device header next to this file)
 #include "fa_norm.h"
 #include "fa_xent.h"
+#include "fa_act.h"
 
 namespace {
 
@@ -2546,6 +2547,139 @@ py::dict xent_bwd_plan(const Tensor &dloss, const Tensor &logits, const Tensor &
     return xent_plan_dict(plan);
 }
 
+// ---- fused MLP activations (flash_attn.ops.activations, the epilogues of flash_attn.ops.fused_dense; include/fa_act.h).
+// Launches on the current stream, no synchronisation; outputs and the dbias workspace come from the caching allocator:
+// capturable in a HIP graph.
+int act_dtype_code(at::ScalarType t, const char *what) {
+    if (t == at::kHalf) return FA_DTYPE_FP16;
+    if (t == at::kBFloat16) return FA_DTYPE_BF16;
+    if (t == at::kFloat) return FA_DTYPE_FP32;
+    TORCH_CHECK(false, "activation: ", what, " must be fp16, bf16 or fp32");
+    return -1;
+}
+
+void check_act_rows(const Tensor &t, const char *name, int64_t M, int64_t H, at::ScalarType dtype) {
+    TORCH_CHECK(t.is_cuda(), "activation: ", name, " must be on CUDA");
+    TORCH_CHECK(t.dim() == 2 && t.size(0) == M && t.size(1) == H, "activation: ", name, " must have shape (M, H)");
+    TORCH_CHECK(t.stride(-1) == 1, "activation: ", name, " must have contiguous last dimension");
+    TORCH_CHECK(t.scalar_type() == dtype, "activation: ", name, " must have the dtype of pre");
+}
+
+void check_act_bias(const Tensor &t, int64_t H, at::ScalarType dtype) {
+    TORCH_CHECK(t.is_cuda(), "activation: bias must be on CUDA");
+    TORCH_CHECK(t.dim() == 1 && t.size(0) == H && t.is_contiguous(), "activation: bias must have shape (H) and be contiguous");
+    TORCH_CHECK(t.scalar_type() == dtype || t.scalar_type() == at::kFloat, "activation: bias must have the dtype of pre or fp32");
+}
+
+// what both directions check of pre, up and bias; returns (M, H)
+std::pair<int64_t, int64_t> check_act_inputs(const Tensor &pre, const OptTensor &up, const OptTensor &bias) {
+    TORCH_CHECK(pre.is_cuda(), "activation: pre must be on CUDA");
+    TORCH_CHECK(pre.dim() == 2, "activation: pre must have shape (M, H)");
+    const int64_t M = pre.size(0), H = pre.size(1);
+    TORCH_CHECK(H >= 1 && H <= std::numeric_limits<int32_t>::max(), "activation: pre must have 1 <= H < 2^31 columns");
+    act_dtype_code(pre.scalar_type(), "pre");
+    check_act_rows(pre, "pre", M, H, pre.scalar_type());
+    if (up.has_value()) {
+        check_act_rows(*up, "up", M, H, pre.scalar_type());
+        TORCH_CHECK(M <= 1 || up->stride(0) == pre.stride(0), "activation: gate and up must have the same row stride");
+        TORCH_CHECK(!bias.has_value(), "activation: the gated form takes no bias");
+    }
+    if (bias.has_value()) check_act_bias(*bias, H, pre.scalar_type());
+    return {M, H};
+}
+
+py::dict act_plan_dict(const fa_act_plan &l) {
+    py::dict d;
+    d["cw"] = l.cw; d["threads"] = l.threads; d["grid_x"] = l.grid_x; d["grid_y"] = l.grid_y; d["rows_per_wg"] = l.rows_per_wg;
+    return d;
+}
+
+// out (M, H) = act(pre + bias), or act(pre) * up with `up` (pre is then the gate).  With `plan` nothing is launched: *plan is
+// what fa_act_fwd_plan says of the params the launch would get
+Tensor act_fwd_impl(const Tensor &pre, const OptTensor &up, const OptTensor &bias, int64_t activation, fa_act_plan *plan) {
+    const auto [M, H] = check_act_inputs(pre, up, bias);
+    fa_act_fwd_params p{};
+    p.abi_version = FA_ABI_VERSION;
+    p.struct_size = sizeof(fa_act_fwd_params);
+    p.pre_dtype = p.up_dtype = p.out_dtype = act_dtype_code(pre.scalar_type(), "pre");
+    p.bias_dtype = bias.has_value() ? act_dtype_code(bias->scalar_type(), "bias") : p.pre_dtype;
+    c10::hip::HIPGuardMasqueradingAsCUDA device_guard(pre.device());
+    Tensor out = at::empty({M, H}, pre.options());
+    if (M == 0) return out;
+    p.pre = pre.data_ptr(); p.up = ptr(up); p.bias = ptr(bias); p.out = out.data_ptr();
+    p.pre_row_stride = pre.stride(0); p.out_row_stride = H;
+    p.M = M; p.H = (int32_t)H; p.activation = (int32_t)activation; p.flags = up.has_value() ? FA_ACT_GATED : 0;
+    const int st = plan ? fa_act_fwd_plan(&p, plan) : fa_act_fwd(&p, current_stream(pre));
+    TORCH_CHECK(st == 0, plan ? "fa_act_fwd_plan" : "fa_act_fwd", " failed (", st, "): ", fa_strerror(st));
+    return out;
+}
+
+Tensor act_fwd(const Tensor &pre, const OptTensor &up, const OptTensor &bias, int64_t activation) {
+    return act_fwd_impl(pre, up, bias, activation, nullptr);
+}
+
+py::dict act_fwd_plan(const Tensor &pre, const OptTensor &up, const OptTensor &bias, int64_t activation) {
+    TORCH_CHECK(pre.dim() == 2 && pre.size(0) >= 1, "activation: a plan needs at least one row");
+    fa_act_plan plan{};
+    act_fwd_impl(pre, up, bias, activation, &plan);
+    return act_plan_dict(plan);
+}
+
+// (dpre, dup, dbias, out).  Plain: dpre (M, H); dup empty.  Gated: dpre is dgate and dup (M, H) each, or with `packed` dpre is one
+// (M, 2H) tensor whose first half is dup and whose second half is dgate (the order of F.glu: value, gate) and dup is empty.
+// dbias (H, the dtype of bias, or of pre without one) with want_dbias, out (M, H) with recompute_out; empty otherwise
+std::tuple<Tensor, Tensor, Tensor, Tensor> act_bwd_impl(const Tensor &dout, const Tensor &pre, const OptTensor &up, const OptTensor &bias,
+                                                        int64_t activation, bool want_dbias, bool recompute_out, bool packed,
+                                                        fa_act_plan *plan) {
+    const auto [M, H] = check_act_inputs(pre, up, bias);
+    check_act_rows(dout, "dout", M, H, pre.scalar_type());
+    const bool gated = up.has_value();
+    TORCH_CHECK(!(gated && want_dbias), "activation: the gated form has no dbias");
+    TORCH_CHECK(gated || !packed, "activation: a packed gradient needs the gated form");
+    fa_act_bwd_params p{};
+    p.abi_version = FA_ABI_VERSION;
+    p.struct_size = sizeof(fa_act_bwd_params);
+    p.pre_dtype = p.up_dtype = p.dout_dtype = p.dpre_dtype = p.dup_dtype = p.out_dtype = act_dtype_code(pre.scalar_type(), "pre");
+    p.bias_dtype = p.dbias_dtype = bias.has_value() ? act_dtype_code(bias->scalar_type(), "bias") : p.pre_dtype;
+    c10::hip::HIPGuardMasqueradingAsCUDA device_guard(pre.device());
+    auto none = [&] { return at::empty({0}, pre.options()); };  // (one tensor each: outputs of an op do not alias)
+    Tensor dpre = at::empty({M, packed ? 2 * H : H}, pre.options());
+    Tensor dup = gated && !packed ? at::empty({M, H}, pre.options()) : none();
+    Tensor dbias = want_dbias ? at::empty({H}, bias.has_value() ? bias->options() : pre.options()) : none();
+    Tensor out = recompute_out ? at::empty({M, H}, pre.options()) : none();
+    if (M == 0) {  // (no rows, a zero sum, nothing of ours launched)
+        if (want_dbias) dbias.zero_();
+        return {dpre, dup, dbias, out};
+    }
+    p.M = M; p.H = (int32_t)H; p.activation = (int32_t)activation; p.flags = gated ? FA_ACT_GATED : 0;
+    p.dbias = want_dbias ? dbias.data_ptr() : nullptr;
+    p.workspace_bytes = fa_act_bwd_workspace_bytes(&p);
+    Tensor workspace = at::empty({(int64_t)p.workspace_bytes}, pre.options().dtype(at::kByte));
+    p.workspace = p.workspace_bytes ? workspace.data_ptr() : nullptr;
+    p.pre = pre.data_ptr(); p.up = ptr(up); p.bias = ptr(bias); p.dout = dout.data_ptr();
+    const int64_t es = pre.element_size();
+    p.dpre = packed ? static_cast<char *>(dpre.data_ptr()) + H * es : dpre.data_ptr();
+    p.dup = !gated ? nullptr : packed ? dpre.data_ptr() : dup.data_ptr();
+    p.recompute_out = recompute_out ? out.data_ptr() : nullptr;
+    p.pre_row_stride = pre.stride(0); p.dout_row_stride = dout.stride(0); p.dpre_row_stride = packed ? 2 * H : H; p.out_row_stride = H;
+    const int st = plan ? fa_act_bwd_plan(&p, plan) : fa_act_bwd(&p, current_stream(pre));
+    TORCH_CHECK(st == 0, plan ? "fa_act_bwd_plan" : "fa_act_bwd", " failed (", st, "): ", fa_strerror(st));
+    return {dpre, dup, dbias, out};
+}
+
+std::tuple<Tensor, Tensor, Tensor, Tensor> act_bwd(const Tensor &dout, const Tensor &pre, const OptTensor &up, const OptTensor &bias,
+                                                   int64_t activation, bool want_dbias, bool recompute_out, bool packed) {
+    return act_bwd_impl(dout, pre, up, bias, activation, want_dbias, recompute_out, packed, nullptr);
+}
+
+py::dict act_bwd_plan(const Tensor &dout, const Tensor &pre, const OptTensor &up, const OptTensor &bias, int64_t activation,
+                      bool want_dbias, bool recompute_out, bool packed) {
+    TORCH_CHECK(pre.dim() == 2 && pre.size(0) >= 1, "activation: a plan needs at least one row");
+    fa_act_plan plan{};
+    act_bwd_impl(dout, pre, up, bias, activation, want_dbias, recompute_out, packed, &plan);
+    return act_plan_dict(plan);
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -2631,5 +2765,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("dloss"), py::arg("logits"), py::arg("labels"), py::arg("lse"), py::arg("dlogits"), py::arg("smoothing"),
           py::arg("logit_scale"), py::arg("lse_square_scale"), py::arg("ignore_index"), py::arg("class_start_idx"),
           py::arg("total_classes"));
+    m.def("act_fwd", &act_fwd, "fused MLP activation forward: act(pre + bias), or act(pre) * up", py::arg("pre"), py::arg("up"),
+          py::arg("bias"), py::arg("activation"));
+    m.def("act_bwd", &act_bwd, "fused MLP activation backward: (dpre, dup, dbias, out)", py::arg("dout"), py::arg("pre"), py::arg("up"),
+          py::arg("bias"), py::arg("activation"), py::arg("want_dbias"), py::arg("recompute_out"), py::arg("packed"));
+    m.def("act_fwd_plan", &act_fwd_plan, "the form act_fwd takes with these arguments: fa_act_plan as a dict, nothing launched",
+          py::arg("pre"), py::arg("up"), py::arg("bias"), py::arg("activation"));
+    m.def("act_bwd_plan", &act_bwd_plan, "the form act_bwd takes with these arguments: fa_act_plan as a dict, nothing launched",
+          py::arg("dout"), py::arg("pre"), py::arg("up"), py::arg("bias"), py::arg("activation"), py::arg("want_dbias"),
+          py::arg("recompute_out"), py::arg("packed"));
     m.def("sink_grad", &sink_grad, "gradient of a learnable sink from softmax_lse and softmax_d");
 }
