@@ -1,4 +1,4 @@
-"""Build and loading of the native code: libfa_fwd_gfx950.so (the C-ABI of include/fa_fwd.h, fa_bwd.h, fa_rotary.h, fa_norm.h, fa_xent.h and fa_act.h) and
+"""Build and loading of the native code: libfa_fwd_gfx950.so (the C-ABI of include/fa_fwd.h, fa_bwd.h, fa_rotary.h, fa_norm.h, fa_xent.h, fa_act.h and fa_gemm_act.h) and
 the compiled host module flash_attn_2_cuda_C (csrc/torch_binding.cpp), which is the only host path of both operator
 surfaces.  Python launches nothing through ctypes: the struct mirrors below serve the ABI tests, `bench.py --variant`
 and the developer tools, which call the C-ABI directly.
@@ -99,6 +99,10 @@ ACT_SYMBOLS = ("fa_act_fwd", "fa_act_fwd_validate", "fa_act_fwd_params_size", "f
                "fa_act_bwd_params_size", "fa_act_bwd_workspace_bytes", "fa_act_fwd_plan", "fa_act_bwd_plan")
 FA_ACT_GELU_TANH, FA_ACT_GELU_ERF, FA_ACT_RELU, FA_ACT_SQRELU, FA_ACT_SILU, FA_ACT_SIGMOID, FA_ACT_IDENTITY = range(7)
 FA_ACT_GATED = 1
+# every symbol include/fa_gemm_act.h declares (csrc/fa_gemm_act.hip)
+GEMM_ACT_SYMBOLS = ("fa_gemm_act_fwd", "fa_gemm_act_fwd_validate", "fa_gemm_act_fwd_params_size", "fa_gemm_act_dgrad",
+                    "fa_gemm_act_dgrad_validate", "fa_gemm_act_dgrad_params_size", "fa_gemm_act_dgrad_workspace_bytes",
+                    "fa_gemm_act_fwd_plan", "fa_gemm_act_dgrad_plan")
 
 
 class FaFwdParams(ctypes.Structure):
@@ -377,6 +381,39 @@ class FaActBwdParams(ctypes.Structure):
     )
 
 
+class FaGemmActPlan(ctypes.Structure):
+    """Field-for-field mirror of `struct fa_gemm_act_plan` (include/fa_gemm_act.h): the form a fused GEMM call takes."""
+
+    _fields_ = [(n, ctypes.c_int32) for n in ("tile_m", "tile_n", "tile_k", "threads", "tiles_m", "tiles_n", "grid_x", "k_steps",
+                                              "ragged_m", "ragged_n", "ragged_k", "group_m", "partial_rows", "reduce_grid_x",
+                                              "dtype", "dgrad")]
+
+
+class FaGemmActFwdParams(ctypes.Structure):
+    """Field-for-field mirror of `struct fa_gemm_act_fwd_params` (include/fa_gemm_act.h)."""
+
+    _fields_ = (
+        [("abi_version", ctypes.c_uint32), ("struct_size", ctypes.c_uint32)]
+        + [(n, ctypes.c_void_p) for n in ("x", "weight", "bias", "out", "act_input")]
+        + [(n, ctypes.c_int64) for n in ("x_row_stride", "weight_row_stride", "out_row_stride", "act_input_row_stride", "M")]
+        + [(n, ctypes.c_int32) for n in ("N", "K", "activation", "x_dtype", "weight_dtype", "bias_dtype", "out_dtype",
+                                         "act_input_dtype")]
+    )
+
+
+class FaGemmActDgradParams(ctypes.Structure):
+    """Field-for-field mirror of `struct fa_gemm_act_dgrad_params` (include/fa_gemm_act.h)."""
+
+    _fields_ = (
+        [("abi_version", ctypes.c_uint32), ("struct_size", ctypes.c_uint32)]
+        + [(n, ctypes.c_void_p) for n in ("grad_out", "weight", "act_input", "grad_in", "dbias", "workspace")]
+        + [("workspace_bytes", ctypes.c_uint64)]
+        + [(n, ctypes.c_int64) for n in ("grad_out_row_stride", "weight_row_stride", "act_input_row_stride", "grad_in_row_stride", "M")]
+        + [(n, ctypes.c_int32) for n in ("N", "K", "activation", "grad_out_dtype", "weight_dtype", "act_input_dtype", "grad_in_dtype",
+                                         "dbias_dtype")]
+    )
+
+
 class FaBwdParams(ctypes.Structure):
     """Field-for-field mirror of `struct fa_bwd_params` (include/fa_bwd.h)."""
 
@@ -454,7 +491,8 @@ HASH_PATH = os.path.join(_HERE, "libfa_fwd_gfx950.srchash")
 def _deps():
     return sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h", ".cpp"))) + [
         os.path.join(INCLUDE, "fa_fwd.h"), os.path.join(INCLUDE, "fa_bwd.h"), os.path.join(INCLUDE, "fa_rotary.h"),
-        os.path.join(INCLUDE, "fa_norm.h"), os.path.join(INCLUDE, "fa_xent.h"), os.path.join(INCLUDE, "fa_act.h")]
+        os.path.join(INCLUDE, "fa_norm.h"), os.path.join(INCLUDE, "fa_xent.h"), os.path.join(INCLUDE, "fa_act.h"),
+        os.path.join(INCLUDE, "fa_gemm_act.h")]
 
 
 def source_hash():
@@ -478,7 +516,7 @@ def is_stale():
 def build(force=False, verbose=False):
     """Compile csrc/ for gfx950 into the in-tree shared library (hipcc cross-compiles without a GPU)."""
     srcs = [os.path.join(CSRC, f) for f in ("fa_fwd_api.hip", "fa_fwd_kv8_api.hip", "fa_fwd_qv8_api.hip", "fa_fwd_sparse_kv_api.hip", "fa_kvcache_append_kv8.hip",
-                                              "fa_kvcache_append_qv8.hip", "fa_bwd_api.hip", "fa_bwd_bs_api.hip", "fa_rotary_emb.hip", "fa_norm.hip", "fa_xent.hip", "fa_act.hip")]
+                                              "fa_kvcache_append_qv8.hip", "fa_bwd_api.hip", "fa_bwd_bs_api.hip", "fa_rotary_emb.hip", "fa_norm.hip", "fa_xent.hip", "fa_act.hip", "fa_gemm_act.hip")]
     if not force and not is_stale():
         return LIB_PATH
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -713,6 +751,20 @@ def load():
         plan.restype = ctypes.c_int
     lib.fa_act_bwd_workspace_bytes.argtypes = [ctypes.POINTER(FaActBwdParams)]
     lib.fa_act_bwd_workspace_bytes.restype = ctypes.c_uint64
+    for name, struct in (("fwd", FaGemmActFwdParams), ("dgrad", FaGemmActDgradParams)):
+        launch, validate, size = (getattr(lib, f"fa_gemm_act_{name}{s}") for s in ("", "_validate", "_params_size"))
+        launch.argtypes = [ctypes.POINTER(struct), ctypes.c_void_p]
+        validate.argtypes = [ctypes.POINTER(struct)]
+        launch.restype = validate.restype = ctypes.c_int
+        size.argtypes = []
+        size.restype = ctypes.c_uint32
+        if size() != ctypes.sizeof(struct):
+            raise RuntimeError(f"fa_gemm_act_{name}_params layout mismatch between include/fa_gemm_act.h and _lib.{struct.__name__}")
+        plan = getattr(lib, f"fa_gemm_act_{name}_plan")
+        plan.argtypes = [ctypes.POINTER(struct), ctypes.POINTER(FaGemmActPlan)]
+        plan.restype = ctypes.c_int
+    lib.fa_gemm_act_dgrad_workspace_bytes.argtypes = [ctypes.POINTER(FaGemmActDgradParams)]
+    lib.fa_gemm_act_dgrad_workspace_bytes.restype = ctypes.c_uint64
     lib.fa_bwd.argtypes = [ctypes.POINTER(FaBwdParams), ctypes.c_void_p]
     lib.fa_bwd.restype = ctypes.c_int
     lib.fa_bwd_validate.argtypes = [ctypes.POINTER(FaBwdParams)]
@@ -879,6 +931,14 @@ def new_act_fwd_params():
 
 def new_act_bwd_params():
     return _new_act_params(FaActBwdParams, ("pre", "up", "bias", "dout", "dpre", "dup", "dbias", "out"))
+
+
+def new_gemm_act_fwd_params():
+    return _new_act_params(FaGemmActFwdParams, ("x", "weight", "bias", "out", "act_input"))
+
+
+def new_gemm_act_dgrad_params():
+    return _new_act_params(FaGemmActDgradParams, ("grad_out", "weight", "act_input", "grad_in", "dbias"))
 
 
 def new_params():

@@ -27,6 +27,7 @@
 #include "fa_norm.h"
 #include "fa_xent.h"
 #include "fa_act.h"
+#include "fa_gemm_act.h"
 
 namespace {
 
@@ -2680,6 +2681,115 @@ py::dict act_bwd_plan(const Tensor &dout, const Tensor &pre, const OptTensor &up
     return act_plan_dict(plan);
 }
 
+// ---- GEMM with a fused bias + activation epilogue (flash_attn.ops.triton.linear; include/fa_gemm_act.h).  Launches on the
+// current stream, no synchronisation; outputs and the dbias workspace come from the caching allocator: capturable in a HIP graph.
+int gemm_act_dtype_code(at::ScalarType t) {
+    TORCH_CHECK(t == at::kHalf || t == at::kBFloat16, "gemm_act: tensors must be fp16 or bf16");
+    return t == at::kHalf ? FA_DTYPE_FP16 : FA_DTYPE_BF16;
+}
+
+void check_gemm_act_matrix(const Tensor &t, const char *name, int64_t rows, int64_t cols, const Tensor &like) {
+    TORCH_CHECK(t.is_cuda() && t.device() == like.device(), "gemm_act: ", name, " must be on the device of the first operand");
+    TORCH_CHECK(t.dim() == 2 && t.size(0) == rows && t.size(1) == cols, "gemm_act: ", name, " has the wrong shape");
+    TORCH_CHECK(t.stride(-1) == 1, "gemm_act: ", name, " must have contiguous last dimension");
+    TORCH_CHECK(t.scalar_type() == like.scalar_type(), "gemm_act: ", name, " must have the dtype of the first operand");
+}
+
+py::dict gemm_act_plan_dict(const fa_gemm_act_plan &l) {
+    py::dict d;
+    d["tile_m"] = l.tile_m; d["tile_n"] = l.tile_n; d["tile_k"] = l.tile_k; d["threads"] = l.threads;
+    d["tiles_m"] = l.tiles_m; d["tiles_n"] = l.tiles_n; d["grid_x"] = l.grid_x; d["k_steps"] = l.k_steps;
+    d["ragged_m"] = l.ragged_m; d["ragged_n"] = l.ragged_n; d["ragged_k"] = l.ragged_k; d["group_m"] = l.group_m;
+    d["partial_rows"] = l.partial_rows; d["reduce_grid_x"] = l.reduce_grid_x; d["dtype"] = l.dtype; d["dgrad"] = l.dgrad;
+    return d;
+}
+
+// (out, act_input) = act(x · weightᵀ + bias) and, with save_act_input, its argument; act_input is empty otherwise.  With `plan`
+// nothing is launched: *plan is what fa_gemm_act_fwd_plan says of the params the launch would get
+std::tuple<Tensor, Tensor> gemm_act_fwd_impl(const Tensor &x, const Tensor &weight, const OptTensor &bias, int64_t activation,
+                                             bool save_act_input, fa_gemm_act_plan *plan) {
+    TORCH_CHECK(x.is_cuda(), "gemm_act: x must be on CUDA");
+    TORCH_CHECK(x.dim() == 2 && weight.dim() == 2, "gemm_act: x must have shape (M, K) and weight (N, K)");
+    const int64_t M = x.size(0), K = x.size(1), N = weight.size(0);
+    TORCH_CHECK(N <= std::numeric_limits<int32_t>::max() && K <= std::numeric_limits<int32_t>::max(), "gemm_act: N and K must be below 2^31");
+    check_gemm_act_matrix(x, "x", M, K, x);
+    check_gemm_act_matrix(weight, "weight", N, K, x);
+    if (bias.has_value()) {
+        TORCH_CHECK(bias->is_cuda() && bias->dim() == 1 && bias->size(0) == N && bias->is_contiguous(), "gemm_act: bias must have shape (N) and be contiguous");
+        TORCH_CHECK(bias->scalar_type() == x.scalar_type(), "gemm_act: bias must have the dtype of x");
+    }
+    fa_gemm_act_fwd_params p{};
+    p.abi_version = FA_ABI_VERSION;
+    p.struct_size = sizeof(fa_gemm_act_fwd_params);
+    p.x_dtype = p.weight_dtype = p.bias_dtype = p.out_dtype = p.act_input_dtype = gemm_act_dtype_code(x.scalar_type());
+    c10::hip::HIPGuardMasqueradingAsCUDA device_guard(x.device());
+    Tensor out = at::empty({M, N}, x.options());
+    Tensor act_input = save_act_input ? at::empty({M, N}, x.options()) : at::empty({0}, x.options());
+    if (M == 0 && !plan) return {out, act_input};
+    p.x = x.data_ptr(); p.weight = weight.data_ptr(); p.bias = ptr(bias); p.out = out.data_ptr();
+    p.act_input = save_act_input ? act_input.data_ptr() : nullptr;
+    p.x_row_stride = x.stride(0); p.weight_row_stride = weight.stride(0); p.out_row_stride = N; p.act_input_row_stride = N;
+    p.M = M; p.N = (int32_t)N; p.K = (int32_t)K; p.activation = (int32_t)activation;
+    const int st = plan ? fa_gemm_act_fwd_plan(&p, plan) : fa_gemm_act_fwd(&p, current_stream(x));
+    TORCH_CHECK(st == 0, plan ? "fa_gemm_act_fwd_plan" : "fa_gemm_act_fwd", " failed (", st, "): ", fa_strerror(st));
+    return {out, act_input};
+}
+
+std::tuple<Tensor, Tensor> gemm_act_fwd(const Tensor &x, const Tensor &weight, const OptTensor &bias, int64_t activation, bool save_act_input) {
+    return gemm_act_fwd_impl(x, weight, bias, activation, save_act_input, nullptr);
+}
+
+py::dict gemm_act_fwd_plan(const Tensor &x, const Tensor &weight, const OptTensor &bias, int64_t activation, bool save_act_input) {
+    fa_gemm_act_plan plan{};
+    gemm_act_fwd_impl(x, weight, bias, activation, save_act_input, &plan);
+    return gemm_act_plan_dict(plan);
+}
+
+// (grad_in, dbias) = (grad_out · weight) ∘ act'(act_input) and, with want_dbias, its column sums; dbias is empty otherwise
+std::tuple<Tensor, Tensor> gemm_act_dgrad_impl(const Tensor &grad_out, const Tensor &weight, const OptTensor &act_input, int64_t activation,
+                                               bool want_dbias, fa_gemm_act_plan *plan) {
+    TORCH_CHECK(grad_out.is_cuda(), "gemm_act: grad_out must be on CUDA");
+    TORCH_CHECK(grad_out.dim() == 2 && weight.dim() == 2, "gemm_act: grad_out must have shape (M, K) and weight (K, N)");
+    const int64_t M = grad_out.size(0), K = grad_out.size(1), N = weight.size(1);
+    TORCH_CHECK(N <= std::numeric_limits<int32_t>::max() && K <= std::numeric_limits<int32_t>::max(), "gemm_act: N and K must be below 2^31");
+    check_gemm_act_matrix(grad_out, "grad_out", M, K, grad_out);
+    check_gemm_act_matrix(weight, "weight", K, N, grad_out);
+    if (act_input.has_value()) check_gemm_act_matrix(*act_input, "act_input", M, N, grad_out);
+    fa_gemm_act_dgrad_params p{};
+    p.abi_version = FA_ABI_VERSION;
+    p.struct_size = sizeof(fa_gemm_act_dgrad_params);
+    p.grad_out_dtype = p.weight_dtype = p.act_input_dtype = p.grad_in_dtype = p.dbias_dtype = gemm_act_dtype_code(grad_out.scalar_type());
+    c10::hip::HIPGuardMasqueradingAsCUDA device_guard(grad_out.device());
+    Tensor grad_in = at::empty({M, N}, grad_out.options());
+    Tensor dbias = want_dbias ? at::empty({N}, grad_out.options()) : at::empty({0}, grad_out.options());
+    if (M == 0 && !plan) {  // (no rows, a zero sum, nothing of ours launched)
+        if (want_dbias) dbias.zero_();
+        return {grad_in, dbias};
+    }
+    p.M = M; p.N = (int32_t)N; p.K = (int32_t)K; p.activation = (int32_t)activation;
+    p.dbias = want_dbias ? dbias.data_ptr() : nullptr;
+    p.workspace_bytes = fa_gemm_act_dgrad_workspace_bytes(&p);
+    Tensor workspace = at::empty({(int64_t)p.workspace_bytes}, grad_out.options().dtype(at::kByte));
+    p.workspace = p.workspace_bytes ? workspace.data_ptr() : nullptr;
+    p.grad_out = grad_out.data_ptr(); p.weight = weight.data_ptr(); p.act_input = ptr(act_input); p.grad_in = grad_in.data_ptr();
+    p.grad_out_row_stride = grad_out.stride(0); p.weight_row_stride = weight.stride(0);
+    p.act_input_row_stride = act_input.has_value() ? act_input->stride(0) : N; p.grad_in_row_stride = N;
+    const int st = plan ? fa_gemm_act_dgrad_plan(&p, plan) : fa_gemm_act_dgrad(&p, current_stream(grad_out));
+    TORCH_CHECK(st == 0, plan ? "fa_gemm_act_dgrad_plan" : "fa_gemm_act_dgrad", " failed (", st, "): ", fa_strerror(st));
+    return {grad_in, dbias};
+}
+
+std::tuple<Tensor, Tensor> gemm_act_dgrad(const Tensor &grad_out, const Tensor &weight, const OptTensor &act_input, int64_t activation,
+                                          bool want_dbias) {
+    return gemm_act_dgrad_impl(grad_out, weight, act_input, activation, want_dbias, nullptr);
+}
+
+py::dict gemm_act_dgrad_plan(const Tensor &grad_out, const Tensor &weight, const OptTensor &act_input, int64_t activation, bool want_dbias) {
+    fa_gemm_act_plan plan{};
+    gemm_act_dgrad_impl(grad_out, weight, act_input, activation, want_dbias, &plan);
+    return gemm_act_plan_dict(plan);
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -2774,5 +2884,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("act_bwd_plan", &act_bwd_plan, "the form act_bwd takes with these arguments: fa_act_plan as a dict, nothing launched",
           py::arg("dout"), py::arg("pre"), py::arg("up"), py::arg("bias"), py::arg("activation"), py::arg("want_dbias"),
           py::arg("recompute_out"), py::arg("packed"));
+    m.def("gemm_act_fwd", &gemm_act_fwd, "GEMM with fused bias + activation: (out, act_input) of act(x @ weight.T + bias)", py::arg("x"),
+          py::arg("weight"), py::arg("bias"), py::arg("activation"), py::arg("save_act_input"));
+    m.def("gemm_act_dgrad", &gemm_act_dgrad, "GEMM with the activation's derivative fused: (grad_in, dbias) of (grad_out @ weight) * act'(act_input)",
+          py::arg("grad_out"), py::arg("weight"), py::arg("act_input"), py::arg("activation"), py::arg("want_dbias"));
+    m.def("gemm_act_fwd_plan", &gemm_act_fwd_plan, "the form gemm_act_fwd takes with these arguments: fa_gemm_act_plan as a dict, nothing launched",
+          py::arg("x"), py::arg("weight"), py::arg("bias"), py::arg("activation"), py::arg("save_act_input"));
+    m.def("gemm_act_dgrad_plan", &gemm_act_dgrad_plan, "the form gemm_act_dgrad takes with these arguments: fa_gemm_act_plan as a dict, nothing launched",
+          py::arg("grad_out"), py::arg("weight"), py::arg("act_input"), py::arg("activation"), py::arg("want_dbias"));
     m.def("sink_grad", &sink_grad, "gradient of a learnable sink from softmax_lse and softmax_d");
 }
