@@ -1,4 +1,4 @@
-"""Build and loading of the native code: libfa_fwd_gfx950.so (the C-ABI of include/fa_fwd.h, fa_bwd.h, fa_rotary.h, fa_norm.h, fa_xent.h, fa_act.h and fa_gemm_act.h) and
+"""Build and loading of the native code: libfa_fwd_gfx950.so (the C-ABI of include/fa_fwd.h, fa_bwd.h, fa_rotary.h, fa_norm.h, fa_xent.h, fa_act.h, fa_gemm_act.h and fa_dropout_norm.h) and
 the compiled host module flash_attn_2_cuda_C (csrc/torch_binding.cpp), which is the only host path of both operator
 surfaces.  Python launches nothing through ctypes: the struct mirrors below serve the ABI tests, `bench.py --variant`
 and the developer tools, which call the C-ABI directly.
@@ -103,6 +103,11 @@ FA_ACT_GATED = 1
 GEMM_ACT_SYMBOLS = ("fa_gemm_act_fwd", "fa_gemm_act_fwd_validate", "fa_gemm_act_fwd_params_size", "fa_gemm_act_dgrad",
                     "fa_gemm_act_dgrad_validate", "fa_gemm_act_dgrad_params_size", "fa_gemm_act_dgrad_workspace_bytes",
                     "fa_gemm_act_fwd_plan", "fa_gemm_act_dgrad_plan")
+# every symbol include/fa_dropout_norm.h declares (csrc/fa_dropout_norm.hip)
+DROPOUT_NORM_SYMBOLS = ("fa_dropout_norm_fwd", "fa_dropout_norm_fwd_validate", "fa_dropout_norm_fwd_params_size",
+                        "fa_dropout_norm_bwd", "fa_dropout_norm_bwd_validate", "fa_dropout_norm_bwd_params_size",
+                        "fa_dropout_norm_bwd_workspace_bytes", "fa_dropout_norm_fwd_plan", "fa_dropout_norm_bwd_plan")
+FA_DROPOUT_NORM_RMS = 1
 
 
 class FaFwdParams(ctypes.Structure):
@@ -318,6 +323,43 @@ class FaNormPlan(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in ("cw", "threads", "team_wave", "wide", "rows_per_wg", "grid_x", "grid_y")]
 
 
+class FaDropoutNormFwdParams(ctypes.Structure):
+    """Field-for-field mirror of `struct fa_dropout_norm_fwd_params` (include/fa_dropout_norm.h)."""
+
+    _fields_ = (
+        [("abi_version", ctypes.c_uint32), ("struct_size", ctypes.c_uint32)]
+        + [(n, ctypes.c_void_p) for n in ("x0", "x1", "residual", "weight0", "bias0", "weight1", "bias1", "rowscale", "colscale",
+                                          "rng_state", "z0", "z1", "x", "dmask0", "dmask1", "mu", "rsigma")]
+        + [(f"{t}_row_stride", ctypes.c_int64) for t in ("x0", "x1", "residual", "z0", "z1", "x")]
+        + [("M", ctypes.c_int64), ("N", ctypes.c_int32)]
+        + [(f"{t}_dtype", ctypes.c_int32) for t in ("x0", "residual", "x", "weight", "z", "rowscale", "colscale")]
+        + [("eps", ctypes.c_float), ("p_dropout", ctypes.c_float), ("flags", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+    )
+
+
+class FaDropoutNormBwdParams(ctypes.Structure):
+    """Field-for-field mirror of `struct fa_dropout_norm_bwd_params` (include/fa_dropout_norm.h)."""
+
+    _fields_ = (
+        [("abi_version", ctypes.c_uint32), ("struct_size", ctypes.c_uint32)]
+        + [(n, ctypes.c_void_p) for n in ("dz0", "dz1", "dx", "x", "x0", "weight0", "weight1", "rowscale", "colscale", "rng_state",
+                                          "mu", "rsigma", "dx0", "dx1", "dresidual", "dw0", "db0", "dw1", "db1", "dcolscale",
+                                          "workspace")]
+        + [("workspace_bytes", ctypes.c_uint64)]
+        + [(f"{t}_row_stride", ctypes.c_int64) for t in ("dz0", "dz1", "dx", "x", "x0", "dx0", "dx1", "dresidual")]
+        + [("M", ctypes.c_int64), ("N", ctypes.c_int32)]
+        + [(f"{t}_dtype", ctypes.c_int32) for t in ("dz", "x", "x0", "weight", "rowscale", "colscale")]
+        + [("p_dropout", ctypes.c_float), ("flags", ctypes.c_int32)]
+    )
+
+
+class FaDropoutNormPlan(ctypes.Structure):
+    """Field-for-field mirror of `struct fa_dropout_norm_plan` (include/fa_dropout_norm.h): the form a call takes."""
+
+    _fields_ = [(n, ctypes.c_int32) for n in ("cw", "threads", "wide", "dropout", "two_weights", "sums", "rows_per_wg", "grid_x",
+                                              "grid_y")]
+
+
 class FaXentPlan(ctypes.Structure):
     """Field-for-field mirror of `struct fa_xent_plan` (include/fa_xent.h): the form a cross-entropy call takes."""
 
@@ -492,7 +534,7 @@ def _deps():
     return sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h", ".cpp"))) + [
         os.path.join(INCLUDE, "fa_fwd.h"), os.path.join(INCLUDE, "fa_bwd.h"), os.path.join(INCLUDE, "fa_rotary.h"),
         os.path.join(INCLUDE, "fa_norm.h"), os.path.join(INCLUDE, "fa_xent.h"), os.path.join(INCLUDE, "fa_act.h"),
-        os.path.join(INCLUDE, "fa_gemm_act.h")]
+        os.path.join(INCLUDE, "fa_gemm_act.h"), os.path.join(INCLUDE, "fa_dropout_norm.h")]
 
 
 def source_hash():
@@ -516,7 +558,8 @@ def is_stale():
 def build(force=False, verbose=False):
     """Compile csrc/ for gfx950 into the in-tree shared library (hipcc cross-compiles without a GPU)."""
     srcs = [os.path.join(CSRC, f) for f in ("fa_fwd_api.hip", "fa_fwd_kv8_api.hip", "fa_fwd_qv8_api.hip", "fa_fwd_sparse_kv_api.hip", "fa_kvcache_append_kv8.hip",
-                                              "fa_kvcache_append_qv8.hip", "fa_bwd_api.hip", "fa_bwd_bs_api.hip", "fa_rotary_emb.hip", "fa_norm.hip", "fa_xent.hip", "fa_act.hip", "fa_gemm_act.hip")]
+                                              "fa_kvcache_append_qv8.hip", "fa_bwd_api.hip", "fa_bwd_bs_api.hip", "fa_rotary_emb.hip", "fa_norm.hip", "fa_xent.hip", "fa_act.hip", "fa_gemm_act.hip",
+                                              "fa_dropout_norm.hip")]
     if not force and not is_stale():
         return LIB_PATH
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -765,6 +808,20 @@ def load():
         plan.restype = ctypes.c_int
     lib.fa_gemm_act_dgrad_workspace_bytes.argtypes = [ctypes.POINTER(FaGemmActDgradParams)]
     lib.fa_gemm_act_dgrad_workspace_bytes.restype = ctypes.c_uint64
+    for name, struct in (("fwd", FaDropoutNormFwdParams), ("bwd", FaDropoutNormBwdParams)):
+        launch, validate, size = (getattr(lib, f"fa_dropout_norm_{name}{s}") for s in ("", "_validate", "_params_size"))
+        launch.argtypes = [ctypes.POINTER(struct), ctypes.c_void_p]
+        validate.argtypes = [ctypes.POINTER(struct)]
+        launch.restype = validate.restype = ctypes.c_int
+        size.argtypes = []
+        size.restype = ctypes.c_uint32
+        if size() != ctypes.sizeof(struct):
+            raise RuntimeError(f"fa_dropout_norm_{name}_params layout mismatch between include/fa_dropout_norm.h and _lib.{struct.__name__}")
+        plan = getattr(lib, f"fa_dropout_norm_{name}_plan")
+        plan.argtypes = [ctypes.POINTER(struct), ctypes.POINTER(FaDropoutNormPlan)]
+        plan.restype = ctypes.c_int
+    lib.fa_dropout_norm_bwd_workspace_bytes.argtypes = [ctypes.POINTER(FaDropoutNormBwdParams)]
+    lib.fa_dropout_norm_bwd_workspace_bytes.restype = ctypes.c_uint64
     lib.fa_bwd.argtypes = [ctypes.POINTER(FaBwdParams), ctypes.c_void_p]
     lib.fa_bwd.restype = ctypes.c_int
     lib.fa_bwd_validate.argtypes = [ctypes.POINTER(FaBwdParams)]
@@ -893,6 +950,25 @@ def new_norm_bwd_params():
     p.abi_version = FA_ABI_VERSION
     p.struct_size = ctypes.sizeof(FaNormBwdParams)
     for t in ("x", "dy", "weight", "bias", "dresidual", "dresidual_in", "dx", "y", "rowscale"):
+        setattr(p, f"{t}_dtype", FA_DTYPE_BF16)
+    return p
+
+
+def new_dropout_norm_fwd_params():
+    p = FaDropoutNormFwdParams()
+    p.abi_version = FA_ABI_VERSION
+    p.struct_size = ctypes.sizeof(FaDropoutNormFwdParams)
+    for t in ("x0", "residual", "x", "weight", "z", "rowscale", "colscale"):
+        setattr(p, f"{t}_dtype", FA_DTYPE_BF16)
+    p.eps = 1e-6
+    return p
+
+
+def new_dropout_norm_bwd_params():
+    p = FaDropoutNormBwdParams()
+    p.abi_version = FA_ABI_VERSION
+    p.struct_size = ctypes.sizeof(FaDropoutNormBwdParams)
+    for t in ("dz", "x", "x0", "weight", "rowscale", "colscale"):
         setattr(p, f"{t}_dtype", FA_DTYPE_BF16)
     return p
 

@@ -28,6 +28,7 @@
 #include "fa_xent.h"
 #include "fa_act.h"
 #include "fa_gemm_act.h"
+#include "fa_dropout_norm.h"
 
 namespace {
 
@@ -2412,6 +2413,229 @@ py::dict norm_bwd_plan(const Tensor &dy, const Tensor &x, const Tensor &weight, 
     return norm_plan_dict(plan);
 }
 
+// ---- fused dropout + residual-add + LayerNorm / RMSNorm (flash_attn.ops.layer_norm -> dropout_layer_norm.dropout_add_ln_fwd /
+// _bwd and the parallel_residual forms, flash_attn/ops/layer_norm.py:16-108, 212-308, without the subset form).  Launches on the
+// current stream, no synchronisation; (seed, offset) are drawn on the device as the attention forward draws them, and every
+// output comes from the caching allocator: capturable in a HIP graph.
+py::dict dropout_norm_plan_dict(const fa_dropout_norm_plan &l) {
+    py::dict d;
+    d["cw"] = l.cw; d["threads"] = l.threads; d["wide"] = l.wide; d["dropout"] = l.dropout; d["two_weights"] = l.two_weights;
+    d["sums"] = l.sums; d["rows_per_wg"] = l.rows_per_wg; d["grid_x"] = l.grid_x; d["grid_y"] = l.grid_y;
+    return d;
+}
+
+using DropoutNormFwdOut = std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor>;
+
+// -> (z0, z1, x, dmask0, dmask1, mu, rsigma, rng_state); an output there is none of is an empty tensor: z1 without weight1, x
+// where the stream is x0 itself and want_x does not ask for it, the masks unless return_dmask and p > 0 (dmask1: and x1), mu
+// with is_rms_norm.  With `plan` nothing is launched and no (seed, offset) is drawn
+DropoutNormFwdOut dropout_norm_fwd_impl(const Tensor &x0, const OptTensor &x1, const OptTensor &residual, const Tensor &weight0,
+                                        const OptTensor &bias0, const OptTensor &weight1, const OptTensor &bias1,
+                                        const OptTensor &rowscale, const OptTensor &colscale, double p_dropout, double eps,
+                                        bool residual_in_fp32, bool is_rms_norm, bool want_x, bool return_dmask,
+                                        fa_dropout_norm_plan *plan) {
+    TORCH_CHECK(x0.is_cuda(), "dropout_add_layer_norm: x0 must be on CUDA");
+    TORCH_CHECK(x0.dim() == 2, "dropout_add_layer_norm: x0 must have shape (M, N)");
+    TORCH_CHECK(p_dropout >= 0.0 && p_dropout < 1.0, "dropout_add_layer_norm: dropout_p must be in [0, 1)");
+    const int64_t M = x0.size(0), N = x0.size(1);
+    check_norm_rows(x0, "x0", M, N);
+    if (x1.has_value()) check_norm_rows(*x1, "x1", M, N);
+    if (residual.has_value()) check_norm_rows(*residual, "residual", M, N);
+    check_norm_vector(weight0, "weight0", N, "(N)");
+    for (const OptTensor *t : {&bias0, &weight1, &bias1}) {
+        if (!t->has_value()) continue;
+        check_norm_vector(**t, "bias0 / weight1 / bias1", N, "(N)");
+        TORCH_CHECK((*t)->scalar_type() == weight0.scalar_type(), "dropout_add_layer_norm: the weights and biases must have one dtype");
+    }
+    if (rowscale.has_value()) check_norm_vector(*rowscale, "rowscale", M, "(M)");
+    if (colscale.has_value()) check_norm_vector(*colscale, "colscale", N, "(N)");
+    TORCH_CHECK(!(x1.has_value() || weight1.has_value()) || !(rowscale.has_value() || colscale.has_value()),
+                "dropout_add_layer_norm: rowscale / colscale are not supported with the parallel form");
+    TORCH_CHECK(!bias1.has_value() || weight1.has_value(), "dropout_add_layer_norm: bias1 needs weight1");
+    TORCH_CHECK(!x1.has_value() || x1->scalar_type() == x0.scalar_type(), "dropout_add_layer_norm: x1 must have the dtype of x0");
+    check_norm_width(x0);
+    fa_dropout_norm_fwd_params p{};
+    p.abi_version = FA_ABI_VERSION;
+    p.struct_size = sizeof(fa_dropout_norm_fwd_params);
+    p.x0_dtype = norm_dtype_code(x0.scalar_type(), "x0");
+    p.weight_dtype = norm_dtype_code(weight0.scalar_type(), "weight0");
+    p.z_dtype = p.x0_dtype;
+    p.residual_dtype = residual.has_value() ? norm_dtype_code(residual->scalar_type(), "residual") : p.x0_dtype;
+    p.x_dtype = residual.has_value() ? p.residual_dtype : residual_in_fp32 ? FA_DTYPE_FP32 : p.x0_dtype;
+    p.rowscale_dtype = rowscale.has_value() ? norm_dtype_code(rowscale->scalar_type(), "rowscale") : p.x0_dtype;
+    p.colscale_dtype = colscale.has_value() ? norm_dtype_code(colscale->scalar_type(), "colscale") : p.x0_dtype;
+    TORCH_CHECK(p.x_dtype == p.x0_dtype || p.x_dtype == FA_DTYPE_FP32, "dropout_add_layer_norm: residual must have the dtype of x0 or fp32");
+    const at::ScalarType stream_type = norm_scalar_type(p.x_dtype);
+    TORCH_CHECK_WITH(Error, N * (int64_t)c10::elementSize(stream_type) <= FA_NORM_MAX_ROW_BYTES,
+                     "This layer norm doesn't support feature dim >= 64KB.");
+    c10::hip::HIPGuardMasqueradingAsCUDA device_guard(x0.device());
+    const bool dropout = p_dropout > 0.0;
+    const bool own_x = want_x || dropout || residual.has_value() || x1.has_value() || rowscale.has_value() || colscale.has_value() ||
+                       p.x_dtype != p.x0_dtype;
+    auto none = [&](at::ScalarType t) { return at::empty({0}, x0.options().dtype(t)); };  // (one tensor each: outputs do not alias)
+    const auto stats = x0.options().dtype(at::kFloat);
+    Tensor z0 = at::empty({M, N}, x0.options()), z1 = weight1.has_value() ? at::empty({M, N}, x0.options()) : none(x0.scalar_type());
+    Tensor x = own_x ? at::empty({M, N}, x0.options().dtype(stream_type)) : none(stream_type);
+    Tensor dmask0 = return_dmask && dropout ? at::empty({M, N}, x0.options().dtype(at::kByte)) : none(at::kByte);
+    Tensor dmask1 = return_dmask && dropout && x1.has_value() ? at::empty({M, N}, x0.options().dtype(at::kByte)) : none(at::kByte);
+    Tensor mu = at::empty({is_rms_norm ? 0 : M}, stats), rsigma = at::empty({M}, stats);
+    Tensor rng_state = plan ? at::zeros({2}, x0.options().dtype(at::kLong)) : dropout_state(p_dropout, c10::nullopt, x0);
+    if (M == 0) return {z0, z1, x, dmask0, dmask1, mu, rsigma, rng_state};
+    p.x0 = x0.data_ptr(); p.x1 = ptr(x1); p.residual = ptr(residual); p.weight0 = weight0.data_ptr(); p.bias0 = ptr(bias0);
+    p.weight1 = ptr(weight1); p.bias1 = ptr(bias1); p.rowscale = ptr(rowscale); p.colscale = ptr(colscale);
+    p.rng_state = dropout ? static_cast<const uint64_t *>(rng_state.data_ptr()) : nullptr;
+    p.z0 = z0.data_ptr(); p.z1 = weight1.has_value() ? z1.data_ptr() : nullptr; p.x = own_x ? x.data_ptr() : nullptr;
+    p.dmask0 = dmask0.numel() ? static_cast<uint8_t *>(dmask0.data_ptr()) : nullptr;
+    p.dmask1 = dmask1.numel() ? static_cast<uint8_t *>(dmask1.data_ptr()) : nullptr;
+    p.mu = is_rms_norm ? nullptr : static_cast<float *>(mu.data_ptr());
+    p.rsigma = static_cast<float *>(rsigma.data_ptr());
+    p.x0_row_stride = x0.stride(0); p.x1_row_stride = x1.has_value() ? x1->stride(0) : 0;
+    p.residual_row_stride = residual.has_value() ? residual->stride(0) : 0;
+    p.z0_row_stride = N; p.z1_row_stride = N; p.x_row_stride = N;
+    p.M = M; p.N = (int32_t)N; p.eps = (float)eps; p.p_dropout = (float)p_dropout;
+    p.flags = is_rms_norm ? FA_DROPOUT_NORM_RMS : 0;
+    const int st = plan ? fa_dropout_norm_fwd_plan(&p, plan) : fa_dropout_norm_fwd(&p, current_stream(x0));
+    TORCH_CHECK(st == 0, plan ? "fa_dropout_norm_fwd_plan" : "fa_dropout_norm_fwd", " failed (", st, "): ", fa_strerror(st));
+    return {z0, z1, x, dmask0, dmask1, mu, rsigma, rng_state};
+}
+
+DropoutNormFwdOut dropout_norm_fwd(const Tensor &x0, const OptTensor &x1, const OptTensor &residual, const Tensor &weight0,
+                                   const OptTensor &bias0, const OptTensor &weight1, const OptTensor &bias1, const OptTensor &rowscale,
+                                   const OptTensor &colscale, double p_dropout, double eps, bool residual_in_fp32, bool is_rms_norm,
+                                   bool want_x, bool return_dmask) {
+    return dropout_norm_fwd_impl(x0, x1, residual, weight0, bias0, weight1, bias1, rowscale, colscale, p_dropout, eps, residual_in_fp32,
+                                 is_rms_norm, want_x, return_dmask, nullptr);
+}
+
+// the form dropout_norm_fwd takes with these arguments (fa_dropout_norm_plan as a dict); M >= 1.  A helper of the tests: it
+// allocates what the launch would allocate, only to see the alignment the plan depends on
+py::dict dropout_norm_fwd_plan(const Tensor &x0, const OptTensor &x1, const OptTensor &residual, const Tensor &weight0,
+                               const OptTensor &bias0, const OptTensor &weight1, const OptTensor &bias1, const OptTensor &rowscale,
+                               const OptTensor &colscale, double p_dropout, double eps, bool residual_in_fp32, bool is_rms_norm,
+                               bool want_x, bool return_dmask) {
+    TORCH_CHECK(x0.dim() == 2 && x0.size(0) >= 1, "dropout_add_layer_norm: a plan needs at least one row");
+    fa_dropout_norm_plan plan{};
+    dropout_norm_fwd_impl(x0, x1, residual, weight0, bias0, weight1, bias1, rowscale, colscale, p_dropout, eps, residual_in_fp32,
+                          is_rms_norm, want_x, return_dmask, &plan);
+    return dropout_norm_plan_dict(plan);
+}
+
+using DropoutNormBwdOut = std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor>;
+
+// x: the stream of the forward (its x, or x0 where it returned none).  -> (dx0, dx1, dresidual, dw0, db0, dw1, db1, dcolscale);
+// empty tensors where there is none: dx1 without has_x1, dresidual without has_residual or where dx0 serves (the reference's
+// rule: no dropout, no scale, one dtype), db0 / db1 without has_bias, dw1 / db1 without weight1, dcolscale without colscale
+DropoutNormBwdOut dropout_norm_bwd_impl(const Tensor &dz0, const OptTensor &dz1, const OptTensor &dx, const Tensor &x,
+                                        const OptTensor &x0, const OptTensor &mu, const Tensor &rsigma, const Tensor &weight0,
+                                        const OptTensor &weight1, const OptTensor &rowscale, const OptTensor &colscale,
+                                        const Tensor &rng_state, double p_dropout, bool has_x1, bool has_residual, bool has_bias,
+                                        bool is_rms_norm, int64_t x0_dtype, fa_dropout_norm_plan *plan) {
+    TORCH_CHECK(x.is_cuda(), "dropout_add_layer_norm: x must be on CUDA");
+    TORCH_CHECK(x.dim() == 2, "dropout_add_layer_norm: x must have shape (M, N)");
+    const int64_t M = x.size(0), N = x.size(1);
+    check_norm_rows(x, "x", M, N);
+    check_norm_rows(dz0, "dz0", M, N);
+    TORCH_CHECK(dz1.has_value() == weight1.has_value(), "dropout_add_layer_norm: dz1 goes with weight1");
+    if (dz1.has_value()) {
+        check_norm_rows(*dz1, "dz1", M, N);
+        TORCH_CHECK(dz1->scalar_type() == dz0.scalar_type(), "dropout_add_layer_norm: dz1 must have the dtype of dz0");
+        check_norm_vector(*weight1, "weight1", N, "(N)");
+        TORCH_CHECK(weight1->scalar_type() == weight0.scalar_type(), "dropout_add_layer_norm: the weights must have one dtype");
+    }
+    if (dx.has_value()) {
+        check_norm_rows(*dx, "dx", M, N);
+        TORCH_CHECK(dx->scalar_type() == x.scalar_type(), "dropout_add_layer_norm: dx must have the dtype of x");
+    }
+    check_norm_vector(weight0, "weight0", N, "(N)");
+    if (rowscale.has_value()) check_norm_vector(*rowscale, "rowscale", M, "(M)");
+    if (colscale.has_value()) {
+        check_norm_vector(*colscale, "colscale", N, "(N)");
+        TORCH_CHECK(x0.has_value(), "dropout_add_layer_norm: x0 is required to compute the gradient of colscale");
+        check_norm_rows(*x0, "x0", M, N);
+        TORCH_CHECK(norm_dtype_code(x0->scalar_type(), "x0") == x0_dtype, "dropout_add_layer_norm: x0 must have the dtype x0_dtype names");
+    }
+    TORCH_CHECK(!(has_x1 || weight1.has_value()) || !(rowscale.has_value() || colscale.has_value()),
+                "dropout_add_layer_norm: rowscale / colscale are not supported with the parallel form");
+    TORCH_CHECK(is_rms_norm || mu.has_value(), "dropout_add_layer_norm: mu is required unless is_rms_norm");
+    if (!is_rms_norm) check_norm_vector(*mu, "mu", M, "(M)");
+    check_norm_vector(rsigma, "rsigma", M, "(M)");
+    TORCH_CHECK(rsigma.scalar_type() == at::kFloat && (is_rms_norm || mu->scalar_type() == at::kFloat),
+                "dropout_add_layer_norm: mu and rsigma must be fp32");
+    TORCH_CHECK(rng_state.is_cuda() && rng_state.scalar_type() == at::kLong && rng_state.numel() == 2 && rng_state.is_contiguous(),
+                "dropout_add_layer_norm: rng_state must be two int64 on the device");
+    TORCH_CHECK(p_dropout >= 0.0 && p_dropout < 1.0, "dropout_add_layer_norm: dropout_p must be in [0, 1)");
+    check_norm_width(x);
+    fa_dropout_norm_bwd_params p{};
+    p.abi_version = FA_ABI_VERSION;
+    p.struct_size = sizeof(fa_dropout_norm_bwd_params);
+    p.x_dtype = norm_dtype_code(x.scalar_type(), "x");
+    p.dz_dtype = norm_dtype_code(dz0.scalar_type(), "dz0");
+    p.weight_dtype = norm_dtype_code(weight0.scalar_type(), "weight0");
+    p.x0_dtype = (int32_t)x0_dtype;
+    p.rowscale_dtype = rowscale.has_value() ? norm_dtype_code(rowscale->scalar_type(), "rowscale") : p.x0_dtype;
+    p.colscale_dtype = colscale.has_value() ? norm_dtype_code(colscale->scalar_type(), "colscale") : p.x0_dtype;
+    const at::ScalarType in_type = norm_scalar_type(x0_dtype);
+    TORCH_CHECK(p.x_dtype == p.x0_dtype || p.x_dtype == FA_DTYPE_FP32, "dropout_add_layer_norm: x must have the dtype of x0 or fp32");
+    c10::hip::HIPGuardMasqueradingAsCUDA device_guard(x.device());
+    const bool dropout = p_dropout > 0.0;
+    const bool own_dresidual = has_residual && (dropout || rowscale.has_value() || colscale.has_value() || p.x_dtype != p.x0_dtype);
+    auto none = [&](const Tensor &like) { return at::empty({0}, like.options()); };
+    Tensor dx0 = at::empty({M, N}, x.options().dtype(in_type));
+    Tensor dx1 = has_x1 ? at::empty({M, N}, x.options().dtype(in_type)) : none(dx0);
+    Tensor dresidual = own_dresidual ? at::empty({M, N}, x.options()) : none(x);
+    Tensor dw0 = at::empty({N}, weight0.options()), db0 = has_bias ? at::empty({N}, weight0.options()) : none(weight0);
+    Tensor dw1 = weight1.has_value() ? at::empty({N}, weight0.options()) : none(weight0);
+    Tensor db1 = weight1.has_value() && has_bias ? at::empty({N}, weight0.options()) : none(weight0);
+    Tensor dcolscale = colscale.has_value() ? at::empty({N}, colscale->options()) : none(weight0);
+    if (M == 0) {  // (empty tensors have no storage to point at: no rows, zero sums, nothing of ours launched)
+        for (Tensor *t : {&dw0, &db0, &dw1, &db1, &dcolscale}) t->zero_();
+        return {dx0, dx1, dresidual, dw0, db0, dw1, db1, dcolscale};
+    }
+    p.M = M; p.N = (int32_t)N;
+    p.weight1 = ptr(weight1); p.colscale = ptr(colscale);  // (the workspace depends on which sums there are)
+    p.workspace_bytes = fa_dropout_norm_bwd_workspace_bytes(&p);
+    Tensor workspace = at::empty({(int64_t)p.workspace_bytes}, x.options().dtype(at::kByte));
+    p.workspace = p.workspace_bytes ? workspace.data_ptr() : nullptr;
+    p.dz0 = dz0.data_ptr(); p.dz1 = ptr(dz1); p.dx = ptr(dx); p.x = x.data_ptr(); p.x0 = colscale.has_value() ? ptr(x0) : nullptr;
+    p.weight0 = weight0.data_ptr(); p.rowscale = ptr(rowscale);
+    p.rng_state = dropout ? static_cast<const uint64_t *>(rng_state.data_ptr()) : nullptr;
+    p.mu = is_rms_norm ? nullptr : static_cast<const float *>(mu->data_ptr());
+    p.rsigma = static_cast<const float *>(rsigma.data_ptr());
+    p.dx0 = dx0.data_ptr(); p.dx1 = has_x1 ? dx1.data_ptr() : nullptr; p.dresidual = own_dresidual ? dresidual.data_ptr() : nullptr;
+    p.dw0 = dw0.data_ptr(); p.db0 = has_bias ? db0.data_ptr() : nullptr;
+    p.dw1 = weight1.has_value() ? dw1.data_ptr() : nullptr; p.db1 = weight1.has_value() && has_bias ? db1.data_ptr() : nullptr;
+    p.dcolscale = colscale.has_value() ? dcolscale.data_ptr() : nullptr;
+    p.dz0_row_stride = dz0.stride(0); p.dz1_row_stride = dz1.has_value() ? dz1->stride(0) : 0;
+    p.dx_row_stride = dx.has_value() ? dx->stride(0) : 0; p.x_row_stride = x.stride(0);
+    p.x0_row_stride = colscale.has_value() ? x0->stride(0) : 0;
+    p.dx0_row_stride = N; p.dx1_row_stride = N; p.dresidual_row_stride = N;
+    p.p_dropout = (float)p_dropout;
+    p.flags = is_rms_norm ? FA_DROPOUT_NORM_RMS : 0;
+    const int st = plan ? fa_dropout_norm_bwd_plan(&p, plan) : fa_dropout_norm_bwd(&p, current_stream(x));
+    TORCH_CHECK(st == 0, plan ? "fa_dropout_norm_bwd_plan" : "fa_dropout_norm_bwd", " failed (", st, "): ", fa_strerror(st));
+    return {dx0, dx1, dresidual, dw0, db0, dw1, db1, dcolscale};
+}
+
+DropoutNormBwdOut dropout_norm_bwd(const Tensor &dz0, const OptTensor &dz1, const OptTensor &dx, const Tensor &x, const OptTensor &x0,
+                                   const OptTensor &mu, const Tensor &rsigma, const Tensor &weight0, const OptTensor &weight1,
+                                   const OptTensor &rowscale, const OptTensor &colscale, const Tensor &rng_state, double p_dropout,
+                                   bool has_x1, bool has_residual, bool has_bias, bool is_rms_norm, int64_t x0_dtype) {
+    return dropout_norm_bwd_impl(dz0, dz1, dx, x, x0, mu, rsigma, weight0, weight1, rowscale, colscale, rng_state, p_dropout, has_x1,
+                                 has_residual, has_bias, is_rms_norm, x0_dtype, nullptr);
+}
+
+// the form dropout_norm_bwd takes with these arguments (fa_dropout_norm_plan as a dict); M >= 1
+py::dict dropout_norm_bwd_plan(const Tensor &dz0, const OptTensor &dz1, const OptTensor &dx, const Tensor &x, const OptTensor &x0,
+                               const OptTensor &mu, const Tensor &rsigma, const Tensor &weight0, const OptTensor &weight1,
+                               const OptTensor &rowscale, const OptTensor &colscale, const Tensor &rng_state, double p_dropout,
+                               bool has_x1, bool has_residual, bool has_bias, bool is_rms_norm, int64_t x0_dtype) {
+    TORCH_CHECK(x.dim() == 2 && x.size(0) >= 1, "dropout_add_layer_norm: a plan needs at least one row");
+    fa_dropout_norm_plan plan{};
+    dropout_norm_bwd_impl(dz0, dz1, dx, x, x0, mu, rsigma, weight0, weight1, rowscale, colscale, rng_state, p_dropout, has_x1,
+                          has_residual, has_bias, is_rms_norm, x0_dtype, &plan);
+    return dropout_norm_plan_dict(plan);
+}
+
 // ---- fused cross-entropy loss (flash_attn.ops.triton.cross_entropy -> CrossEntropyLoss.forward / backward,
 // flash_attn/ops/triton/cross_entropy.py:149-289; the collectives of a vocabulary split stay in Python).  Launches on the
 // current stream, no synchronisation; losses, lse and z_losses come from the caching allocator: capturable in a HIP graph.
@@ -2892,5 +3116,25 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("x"), py::arg("weight"), py::arg("bias"), py::arg("activation"), py::arg("save_act_input"));
     m.def("gemm_act_dgrad_plan", &gemm_act_dgrad_plan, "the form gemm_act_dgrad takes with these arguments: fa_gemm_act_plan as a dict, nothing launched",
           py::arg("grad_out"), py::arg("weight"), py::arg("act_input"), py::arg("activation"), py::arg("want_dbias"));
+    m.def("dropout_norm_fwd", &dropout_norm_fwd,
+          "fused dropout + residual-add + LayerNorm / RMSNorm forward: (z0, z1, x, dmask0, dmask1, mu, rsigma, rng_state)",
+          py::arg("x0"), py::arg("x1"), py::arg("residual"), py::arg("weight0"), py::arg("bias0"), py::arg("weight1"),
+          py::arg("bias1"), py::arg("rowscale"), py::arg("colscale"), py::arg("p_dropout"), py::arg("eps"), py::arg("residual_in_fp32"),
+          py::arg("is_rms_norm"), py::arg("want_x"), py::arg("return_dmask"));
+    m.def("dropout_norm_bwd", &dropout_norm_bwd,
+          "fused dropout + residual-add + LayerNorm / RMSNorm backward: (dx0, dx1, dresidual, dw0, db0, dw1, db1, dcolscale)",
+          py::arg("dz0"), py::arg("dz1"), py::arg("dx"), py::arg("x"), py::arg("x0"), py::arg("mu"), py::arg("rsigma"),
+          py::arg("weight0"), py::arg("weight1"), py::arg("rowscale"), py::arg("colscale"), py::arg("rng_state"), py::arg("p_dropout"),
+          py::arg("has_x1"), py::arg("has_residual"), py::arg("has_bias"), py::arg("is_rms_norm"), py::arg("x0_dtype"));
+    m.def("dropout_norm_fwd_plan", &dropout_norm_fwd_plan,
+          "the form dropout_norm_fwd takes with these arguments: fa_dropout_norm_plan as a dict, nothing launched",
+          py::arg("x0"), py::arg("x1"), py::arg("residual"), py::arg("weight0"), py::arg("bias0"), py::arg("weight1"),
+          py::arg("bias1"), py::arg("rowscale"), py::arg("colscale"), py::arg("p_dropout"), py::arg("eps"), py::arg("residual_in_fp32"),
+          py::arg("is_rms_norm"), py::arg("want_x"), py::arg("return_dmask"));
+    m.def("dropout_norm_bwd_plan", &dropout_norm_bwd_plan,
+          "the form dropout_norm_bwd takes with these arguments: fa_dropout_norm_plan as a dict, nothing launched",
+          py::arg("dz0"), py::arg("dz1"), py::arg("dx"), py::arg("x"), py::arg("x0"), py::arg("mu"), py::arg("rsigma"),
+          py::arg("weight0"), py::arg("weight1"), py::arg("rowscale"), py::arg("colscale"), py::arg("rng_state"), py::arg("p_dropout"),
+          py::arg("has_x1"), py::arg("has_residual"), py::arg("has_bias"), py::arg("is_rms_norm"), py::arg("x0_dtype"));
     m.def("sink_grad", &sink_grad, "gradient of a learnable sink from softmax_lse and softmax_d");
 }
