@@ -531,10 +531,8 @@ HASH_PATH = os.path.join(_HERE, "libfa_fwd_gfx950.srchash")
 
 
 def _deps():
-    return sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h", ".cpp"))) + [
-        os.path.join(INCLUDE, "fa_fwd.h"), os.path.join(INCLUDE, "fa_bwd.h"), os.path.join(INCLUDE, "fa_rotary.h"),
-        os.path.join(INCLUDE, "fa_norm.h"), os.path.join(INCLUDE, "fa_xent.h"), os.path.join(INCLUDE, "fa_act.h"),
-        os.path.join(INCLUDE, "fa_gemm_act.h"), os.path.join(INCLUDE, "fa_dropout_norm.h")]
+    return sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h", ".cpp"))) + sorted(
+        os.path.join(INCLUDE, f) for f in os.listdir(INCLUDE) if f.endswith(".h"))
 
 
 def source_hash():
@@ -599,6 +597,25 @@ def build_binding(verbose=False):
         print(" ".join(cmd), file=sys.stderr)
     subprocess.run(cmd, check=True)
     return binding_path()
+
+
+def _declare_unit(lib, prefix, structs, plan_struct, workspace_struct):
+    """The prototypes of one row unit (include/`prefix`.h): per (direction, params struct) the launch, _validate, _params_size
+    (checked against the mirror) and _plan; `workspace_struct`: the struct of the direction that has a _workspace_bytes."""
+    for name, struct in structs:
+        launch, validate, size, plan = (getattr(lib, f"{prefix}_{name}{s}") for s in ("", "_validate", "_params_size", "_plan"))
+        launch.argtypes = [ctypes.POINTER(struct), ctypes.c_void_p]
+        validate.argtypes = [ctypes.POINTER(struct)]
+        plan.argtypes = [ctypes.POINTER(struct), ctypes.POINTER(plan_struct)]
+        launch.restype = validate.restype = plan.restype = ctypes.c_int
+        size.argtypes = []
+        size.restype = ctypes.c_uint32
+        if size() != ctypes.sizeof(struct):
+            raise RuntimeError(f"{prefix}_{name}_params layout mismatch between include/{prefix}.h and _lib.{struct.__name__}")
+        if struct is workspace_struct:
+            workspace = getattr(lib, f"{prefix}_{name}_workspace_bytes")
+            workspace.argtypes = [ctypes.POINTER(struct)]
+            workspace.restype = ctypes.c_uint64
 
 
 _lib = None
@@ -754,74 +771,13 @@ def load():
     lib.fa_rotary_emb_params_size.restype = ctypes.c_uint32
     if lib.fa_rotary_emb_params_size() != ctypes.sizeof(FaRotaryEmbParams):
         raise RuntimeError("fa_rotary_emb_params layout mismatch between include/fa_rotary.h and _lib.FaRotaryEmbParams")
-    for name, struct in (("fwd", FaNormFwdParams), ("bwd", FaNormBwdParams)):
-        launch, validate, size = (getattr(lib, f"fa_norm_{name}{s}") for s in ("", "_validate", "_params_size"))
-        launch.argtypes = [ctypes.POINTER(struct), ctypes.c_void_p]
-        validate.argtypes = [ctypes.POINTER(struct)]
-        launch.restype = validate.restype = ctypes.c_int
-        size.argtypes = []
-        size.restype = ctypes.c_uint32
-        if size() != ctypes.sizeof(struct):
-            raise RuntimeError(f"fa_norm_{name}_params layout mismatch between include/fa_norm.h and _lib.{struct.__name__}")
-        plan = getattr(lib, f"fa_norm_{name}_plan")
-        plan.argtypes = [ctypes.POINTER(struct), ctypes.POINTER(FaNormPlan)]
-        plan.restype = ctypes.c_int
-    lib.fa_norm_bwd_workspace_bytes.argtypes = [ctypes.POINTER(FaNormBwdParams)]
-    lib.fa_norm_bwd_workspace_bytes.restype = ctypes.c_uint64
-    for name, struct in (("fwd", FaXentFwdParams), ("bwd", FaXentBwdParams)):
-        launch, validate, size = (getattr(lib, f"fa_xent_{name}{s}") for s in ("", "_validate", "_params_size"))
-        launch.argtypes = [ctypes.POINTER(struct), ctypes.c_void_p]
-        validate.argtypes = [ctypes.POINTER(struct)]
-        launch.restype = validate.restype = ctypes.c_int
-        size.argtypes = []
-        size.restype = ctypes.c_uint32
-        if size() != ctypes.sizeof(struct):
-            raise RuntimeError(f"fa_xent_{name}_params layout mismatch between include/fa_xent.h and _lib.{struct.__name__}")
-        plan = getattr(lib, f"fa_xent_{name}_plan")
-        plan.argtypes = [ctypes.POINTER(struct), ctypes.POINTER(FaXentPlan)]
-        plan.restype = ctypes.c_int
-    for name, struct in (("fwd", FaActFwdParams), ("bwd", FaActBwdParams)):
-        launch, validate, size = (getattr(lib, f"fa_act_{name}{s}") for s in ("", "_validate", "_params_size"))
-        launch.argtypes = [ctypes.POINTER(struct), ctypes.c_void_p]
-        validate.argtypes = [ctypes.POINTER(struct)]
-        launch.restype = validate.restype = ctypes.c_int
-        size.argtypes = []
-        size.restype = ctypes.c_uint32
-        if size() != ctypes.sizeof(struct):
-            raise RuntimeError(f"fa_act_{name}_params layout mismatch between include/fa_act.h and _lib.{struct.__name__}")
-        plan = getattr(lib, f"fa_act_{name}_plan")
-        plan.argtypes = [ctypes.POINTER(struct), ctypes.POINTER(FaActPlan)]
-        plan.restype = ctypes.c_int
-    lib.fa_act_bwd_workspace_bytes.argtypes = [ctypes.POINTER(FaActBwdParams)]
-    lib.fa_act_bwd_workspace_bytes.restype = ctypes.c_uint64
-    for name, struct in (("fwd", FaGemmActFwdParams), ("dgrad", FaGemmActDgradParams)):
-        launch, validate, size = (getattr(lib, f"fa_gemm_act_{name}{s}") for s in ("", "_validate", "_params_size"))
-        launch.argtypes = [ctypes.POINTER(struct), ctypes.c_void_p]
-        validate.argtypes = [ctypes.POINTER(struct)]
-        launch.restype = validate.restype = ctypes.c_int
-        size.argtypes = []
-        size.restype = ctypes.c_uint32
-        if size() != ctypes.sizeof(struct):
-            raise RuntimeError(f"fa_gemm_act_{name}_params layout mismatch between include/fa_gemm_act.h and _lib.{struct.__name__}")
-        plan = getattr(lib, f"fa_gemm_act_{name}_plan")
-        plan.argtypes = [ctypes.POINTER(struct), ctypes.POINTER(FaGemmActPlan)]
-        plan.restype = ctypes.c_int
-    lib.fa_gemm_act_dgrad_workspace_bytes.argtypes = [ctypes.POINTER(FaGemmActDgradParams)]
-    lib.fa_gemm_act_dgrad_workspace_bytes.restype = ctypes.c_uint64
-    for name, struct in (("fwd", FaDropoutNormFwdParams), ("bwd", FaDropoutNormBwdParams)):
-        launch, validate, size = (getattr(lib, f"fa_dropout_norm_{name}{s}") for s in ("", "_validate", "_params_size"))
-        launch.argtypes = [ctypes.POINTER(struct), ctypes.c_void_p]
-        validate.argtypes = [ctypes.POINTER(struct)]
-        launch.restype = validate.restype = ctypes.c_int
-        size.argtypes = []
-        size.restype = ctypes.c_uint32
-        if size() != ctypes.sizeof(struct):
-            raise RuntimeError(f"fa_dropout_norm_{name}_params layout mismatch between include/fa_dropout_norm.h and _lib.{struct.__name__}")
-        plan = getattr(lib, f"fa_dropout_norm_{name}_plan")
-        plan.argtypes = [ctypes.POINTER(struct), ctypes.POINTER(FaDropoutNormPlan)]
-        plan.restype = ctypes.c_int
-    lib.fa_dropout_norm_bwd_workspace_bytes.argtypes = [ctypes.POINTER(FaDropoutNormBwdParams)]
-    lib.fa_dropout_norm_bwd_workspace_bytes.restype = ctypes.c_uint64
+    _declare_unit(lib, "fa_norm", (("fwd", FaNormFwdParams), ("bwd", FaNormBwdParams)), FaNormPlan, FaNormBwdParams)
+    _declare_unit(lib, "fa_xent", (("fwd", FaXentFwdParams), ("bwd", FaXentBwdParams)), FaXentPlan, None)
+    _declare_unit(lib, "fa_act", (("fwd", FaActFwdParams), ("bwd", FaActBwdParams)), FaActPlan, FaActBwdParams)
+    _declare_unit(lib, "fa_gemm_act", (("fwd", FaGemmActFwdParams), ("dgrad", FaGemmActDgradParams)), FaGemmActPlan,
+                  FaGemmActDgradParams)
+    _declare_unit(lib, "fa_dropout_norm", (("fwd", FaDropoutNormFwdParams), ("bwd", FaDropoutNormBwdParams)), FaDropoutNormPlan,
+                  FaDropoutNormBwdParams)
     lib.fa_bwd.argtypes = [ctypes.POINTER(FaBwdParams), ctypes.c_void_p]
     lib.fa_bwd.restype = ctypes.c_int
     lib.fa_bwd_validate.argtypes = [ctypes.POINTER(FaBwdParams)]

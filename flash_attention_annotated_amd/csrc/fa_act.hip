@@ -1,6 +1,8 @@
 // fa_act.hip — fa_act_fwd / fa_act_bwd (include/fa_act.h): the activation between the two GEMMs of an MLP, plain
-// (act(pre + bias)) and gated (act(gate) * up), forward and backward.  A translation unit of its own with nothing from the
-// other units (the chunk loads and stores restate those of fa_xent.hip): the kernel sets of the other units are pinned.
+// (act(pre + bias)) and gated (act(gate) * up), forward and backward.  A translation unit of its own: no kernel comes from
+// another unit or goes to one, because the kernel set of every unit is pinned by its tests.  That rule is about kernels.  The
+// chunk loads and stores and the host predicates are the inline functions of fa_rowwise.h, shared with the other row units,
+// and the activations are those of fa_act_math.h, the one definition this unit and fa_gemm_act.hip have.
 //
 // A pure stream.  A row is H / CW chunks of 16 bytes (CW = 8 elements of a 16-bit dtype, 4 of fp32) and an element tail of
 // H % CW columns, where every tensor of the call is 16-byte aligned in every row; otherwise every column is an element
@@ -13,12 +15,13 @@
 // Dtype, activation, gating, bias, dbias and recompute are kernel arguments, hence wave-uniform: the kernels are
 // instantiated by CW only.  No atomics, no LDS.
 #include "../../include/fa_act.h"
-
-#include <hip/hip_runtime.h>
-
-#include <cmath>
+#include "fa_act_math.h"
+#include "fa_rowwise.h"
 
 namespace {
+
+using namespace fa_row;
+using namespace fa_act_math;
 
 constexpr int THREADS = 256;
 constexpr int FWD_ROWS = 4;          // rows of a forward block, all in flight
@@ -27,148 +30,6 @@ constexpr int BWD_UNROLL = 2;        // ... of which in flight
 constexpr int MAX_SLABS = 256;       // grid.x; further slabs are walked
 constexpr int FWD_MAX_BLOCKS = 65535;  // grid.y of the forward; further row blocks are walked
 constexpr int BWD_MAX_BLOCKS = 1024;   // ... of the backward: at most 1024 partial rows
-
-__host__ __device__ __forceinline__ int esize(int dt) { return dt == FA_DTYPE_FP32 ? 4 : 2; }
-
-// CW elements of dtype `dt` at q, as fp32: 16-byte accesses where CW > 1
-template <int CW>
-__device__ __forceinline__ void load_chunk(const char *q, int dt, float (&v)[CW]) {
-    if (dt == FA_DTYPE_FP32) {
-        const float *p = reinterpret_cast<const float *>(q);
-        if constexpr (CW == 1) {
-            v[0] = *p;
-        } else {
-#pragma unroll
-            for (int i = 0; i < CW; i += 4) {
-                const float4 f = *reinterpret_cast<const float4 *>(p + i);
-                v[i] = f.x; v[i + 1] = f.y; v[i + 2] = f.z; v[i + 3] = f.w;
-            }
-        }
-        return;
-    }
-    uint32_t h[CW];
-    if constexpr (CW == 8) {
-        const uint4 f = *reinterpret_cast<const uint4 *>(q);
-        h[0] = f.x & 0xffffu; h[1] = f.x >> 16; h[2] = f.y & 0xffffu; h[3] = f.y >> 16;
-        h[4] = f.z & 0xffffu; h[5] = f.z >> 16; h[6] = f.w & 0xffffu; h[7] = f.w >> 16;
-    } else if constexpr (CW == 4) {
-        const uint2 f = *reinterpret_cast<const uint2 *>(q);
-        h[0] = f.x & 0xffffu; h[1] = f.x >> 16; h[2] = f.y & 0xffffu; h[3] = f.y >> 16;
-    } else {
-        h[0] = *reinterpret_cast<const uint16_t *>(q);
-    }
-    if (dt == FA_DTYPE_BF16) {
-#pragma unroll
-        for (int i = 0; i < CW; ++i) v[i] = __uint_as_float(h[i] << 16);
-    } else {
-#pragma unroll
-        for (int i = 0; i < CW; ++i) v[i] = (float)__builtin_bit_cast(_Float16, (uint16_t)h[i]);
-    }
-}
-
-// ... and back: one rounding to nearest even
-template <int CW>
-__device__ __forceinline__ void store_chunk(char *q, int dt, const float (&v)[CW]) {
-    if (dt == FA_DTYPE_FP32) {
-        float *p = reinterpret_cast<float *>(q);
-        if constexpr (CW == 1) {
-            *p = v[0];
-        } else {
-#pragma unroll
-            for (int i = 0; i < CW; i += 4) *reinterpret_cast<float4 *>(p + i) = make_float4(v[i], v[i + 1], v[i + 2], v[i + 3]);
-        }
-        return;
-    }
-    uint32_t h[CW];
-    if (dt == FA_DTYPE_BF16) {
-#pragma unroll
-        for (int i = 0; i < CW; ++i) h[i] = __builtin_bit_cast(uint16_t, (__bf16)v[i]);
-    } else {
-#pragma unroll
-        for (int i = 0; i < CW; ++i) h[i] = __builtin_bit_cast(uint16_t, (_Float16)v[i]);
-    }
-    if constexpr (CW == 8) {
-        *reinterpret_cast<uint4 *>(q) = make_uint4(h[0] | h[1] << 16, h[2] | h[3] << 16, h[4] | h[5] << 16, h[6] | h[7] << 16);
-    } else if constexpr (CW == 4) {
-        *reinterpret_cast<uint2 *>(q) = make_uint2(h[0] | h[1] << 16, h[2] | h[3] << 16);
-    } else {
-        *reinterpret_cast<uint16_t *>(q) = (uint16_t)h[0];
-    }
-}
-
-// ---- the activations ----------------------------------------------------------------------------------------------------------
-// a = act(x) and dg = act'(x) * g for a downstream factor g (include/fa_act.h).  One definition for the forward and the backward, with contraction off: the backward's
-// recomputed output has the forward's bits.
-struct Sig {
-    float s, c;  // sigmoid(z) and 1 - sigmoid(z), neither by a subtraction
-};
-
-__device__ __forceinline__ Sig sigmoid_parts(float z) {
-#pragma clang fp contract(off)
-    const float e = expf(-fabsf(z));  // in [0, 1]: never overflows, 0 at saturation
-    const float hi = 1.0f / (1.0f + e), lo = e * hi;
-    Sig g;
-    g.s = z >= 0.0f ? hi : lo;
-    g.c = z >= 0.0f ? lo : hi;
-    return g;
-}
-
-template <int ACT>
-__device__ __forceinline__ void eval(float x, float g, float &a, float &dg) {
-#pragma clang fp contract(off)
-    float da;
-    if constexpr (ACT == FA_ACT_GELU_TANH) {
-        const float x2 = x * x;  // inf once |x| > 1.8e19: z is then +-inf, s (1 - s) is 0 and the second term is dropped
-        const Sig g = sigmoid_parts((1.59576912f * x) * (1.0f + 0.044715f * x2));
-        const float w = g.s * g.c;
-        a = x * g.s;
-        da = g.s + (w > 0.0f ? (x * w) * (1.59576912f + 0.2140644486f * x2) : 0.0f);
-    } else if constexpr (ACT == FA_ACT_GELU_ERF) {
-        const float y = x * 0.70710678118654752f;
-        const float phi = x >= 0.0f ? 0.5f * (1.0f + erff(y)) : 0.5f * erfcf(-y);
-        a = x * phi;
-        da = phi + x * (0.39894228040143268f * expf(-0.5f * (x * x)));  // (x^2 = inf: exp is 0 and x is finite)
-    } else if constexpr (ACT == FA_ACT_RELU) {
-        a = x > 0.0f ? x : (x == x ? 0.0f : x);  // (NaN stays NaN)
-        da = x > 0.0f ? 1.0f : 0.0f;
-    } else if constexpr (ACT == FA_ACT_SQRELU) {
-        const float r = x > 0.0f ? x : (x == x ? 0.0f : x);
-        a = r * r;
-        dg = (r * g) * 2.0f;  // (2 r alone overflows for r above half the largest value, where the product with g may not)
-        return;
-    } else if constexpr (ACT == FA_ACT_SILU) {
-        const Sig g = sigmoid_parts(x);
-        a = x * g.s;
-        da = g.s + x * (g.s * g.c);
-    } else if constexpr (ACT == FA_ACT_SIGMOID) {
-        const Sig g = sigmoid_parts(x);
-        a = g.s;
-        da = g.s * g.c;
-    } else {
-        a = x;
-        da = 1.0f;
-    }
-    dg = da * g;
-}
-
-template <int NC>
-__device__ __forceinline__ void eval_chunk(int act, const float (&x)[NC], const float (&g)[NC], float (&a)[NC], float (&dg)[NC]) {
-#define FA_ACT_CASE(A)                                        \
-    case A:                                                   \
-        _Pragma("unroll") for (int i = 0; i < NC; ++i) eval<A>(x[i], g[i], a[i], dg[i]); \
-        break;
-    switch (act) {
-        FA_ACT_CASE(FA_ACT_GELU_TANH)
-        FA_ACT_CASE(FA_ACT_GELU_ERF)
-        FA_ACT_CASE(FA_ACT_RELU)
-        FA_ACT_CASE(FA_ACT_SQRELU)
-        FA_ACT_CASE(FA_ACT_SILU)
-        FA_ACT_CASE(FA_ACT_SIGMOID)
-    default:
-        _Pragma("unroll") for (int i = 0; i < NC; ++i) eval<FA_ACT_IDENTITY>(x[i], g[i], a[i], dg[i]);
-    }
-#undef FA_ACT_CASE
-}
 
 // the forward's value of one element: the one rounding follows in store_chunk
 __device__ __forceinline__ float out_of(float a, float u, bool gated) {
@@ -308,12 +169,8 @@ __global__ __launch_bounds__(THREADS) void act_dbias_reduce_kernel(const float *
 }
 
 // ---- host -------------------------------------------------------------------------------------------------------------------
-bool known_dtype(int dt) { return dt == FA_DTYPE_FP16 || dt == FA_DTYPE_BF16 || dt == FA_DTYPE_FP32; }
-bool known_activation(int a) { return a >= FA_ACT_GELU_TANH && a <= FA_ACT_IDENTITY; }
-bool aligned_to(const void *q, int bytes) { return reinterpret_cast<uintptr_t>(q) % bytes == 0; }
-
 // a tensor of rows: 16-byte accesses need its base and (more than one row) its pitch in bytes to be multiples of 16
-bool rows_allow_16(const void *q, int64_t row_stride, int es, int64_t M) { return !q || (aligned_to(q, 16) && (M <= 1 || (row_stride * es) % 16 == 0)); }
+bool rows_allow_16(const void *q, int dt, int64_t row_stride, int64_t M) { return M <= 1 ? aligned_to(q, 16) : rows_16_bytes(q, dt, row_stride); }
 
 int32_t slabs_of(int H, int cw) {
     const int64_t chunks = (int64_t)H / cw, slabs = (chunks + THREADS - 1) / THREADS;
@@ -327,10 +184,10 @@ int32_t blocks_of(int64_t M, int rows, int cap) {
 
 // the launch of a valid forward call
 fa_act_plan fwd_launch(const fa_act_fwd_params *p) {
-    const int es = esize(p->pre_dtype);
+    const int dt = p->pre_dtype, es = esize(dt);
     const void *up = (p->flags & FA_ACT_GATED) ? p->up : nullptr;  // (the plain form ignores the field, whatever it holds)
-    const bool vec = rows_allow_16(p->pre, p->pre_row_stride, es, p->M) && rows_allow_16(up, p->pre_row_stride, es, p->M) &&
-                     rows_allow_16(p->out, p->out_row_stride, es, p->M) && aligned_to(p->bias, 16);
+    const bool vec = rows_allow_16(p->pre, dt, p->pre_row_stride, p->M) && rows_allow_16(up, dt, p->pre_row_stride, p->M) &&
+                     rows_allow_16(p->out, dt, p->out_row_stride, p->M) && aligned_to(p->bias, 16);
     fa_act_plan l;
     l.cw = vec ? 16 / es : 1;
     l.threads = THREADS;
@@ -342,12 +199,12 @@ fa_act_plan fwd_launch(const fa_act_fwd_params *p) {
 
 // ... of a valid backward call (the workspace is 16-byte aligned by validation, and its partial rows by their pitch)
 fa_act_plan bwd_launch(const fa_act_bwd_params *p) {
-    const int es = esize(p->pre_dtype);
+    const int dt = p->pre_dtype, es = esize(dt);
     const bool gated = (p->flags & FA_ACT_GATED) != 0;  // (the plain form ignores up and dup, whatever the fields hold)
     const void *up = gated ? p->up : nullptr, *dup = gated ? p->dup : nullptr;
-    const bool vec = rows_allow_16(p->pre, p->pre_row_stride, es, p->M) && rows_allow_16(up, p->pre_row_stride, es, p->M) &&
-                     rows_allow_16(p->dout, p->dout_row_stride, es, p->M) && rows_allow_16(p->dpre, p->dpre_row_stride, es, p->M) &&
-                     rows_allow_16(dup, p->dpre_row_stride, es, p->M) && rows_allow_16(p->recompute_out, p->out_row_stride, es, p->M) &&
+    const bool vec = rows_allow_16(p->pre, dt, p->pre_row_stride, p->M) && rows_allow_16(up, dt, p->pre_row_stride, p->M) &&
+                     rows_allow_16(p->dout, dt, p->dout_row_stride, p->M) && rows_allow_16(p->dpre, dt, p->dpre_row_stride, p->M) &&
+                     rows_allow_16(dup, dt, p->dpre_row_stride, p->M) && rows_allow_16(p->recompute_out, dt, p->out_row_stride, p->M) &&
                      aligned_to(p->bias, 16);
     fa_act_plan l;
     l.cw = vec ? 16 / es : 1;

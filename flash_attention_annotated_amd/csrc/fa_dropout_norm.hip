@@ -1,7 +1,9 @@
 // fa_dropout_norm.hip — fa_dropout_norm_fwd / fa_dropout_norm_bwd (include/fa_dropout_norm.h): dropout on the branch output(s)
-// fused into the residual add and the LayerNorm / RMSNorm, forward and backward.  A translation unit of its own with nothing
-// from the attention units or from fa_norm.hip: their kernel sets are pinned.  The access helpers and the counter hash of
-// DESIGN 4.6 are restated here.
+// fused into the residual add and the LayerNorm / RMSNorm, forward and backward.  A translation unit of its own: no kernel
+// comes from another unit or goes to one, fa_norm.hip included, because the kernel set of every unit is pinned by its tests.
+// That rule is about kernels: the chunk loads and stores, the sums, the ordered reduce of partial rows and the host predicates
+// are the inline functions of fa_rowwise.h, shared with the other row units.  The counter hash stays here: its avalanche is
+// that of DESIGN 4.6, its keying (a key per row, groups of 4 columns) is this unit's own.
 //
 // A workgroup of 64 / 256 / 512 / 1024 threads (the smallest that gives a thread at most C columns) takes one row at a
 // time out of a contiguous block of rows; C = 16 / 8 / 2 (CW = 8 / 4 / 1) in the forward, 8 / 4 / 2 in the backward.  Thread t of `ts` owns the chunks
@@ -21,13 +23,12 @@
 // (plan.wide), the backward takes the row sums in a launch of their own (dropout_norm_bwd_row_sums_kernel) and then splits the
 // columns into slabs of 1024 * C over blockIdx.y of the same dropout_norm_bwd_kernel.  No atomics anywhere.
 #include "../../include/fa_dropout_norm.h"
-
-#include <hip/hip_runtime.h>
+#include "fa_rowwise.h"
 
 namespace {
 
-constexpr int WAVE = 64;
-constexpr int MAX_WAVES = 16;       // of a workgroup
+using namespace fa_row;
+
 // columns per thread: of the forward, and of the backward, which keeps six values per column.  Fewer with the narrower
 // accesses: a thread has that many more chunks in flight, and their addresses and loads must fit beside the row
 __host__ __device__ constexpr int fwd_cols(int cw) { return cw == 8 ? 16 : cw == 4 ? 8 : 2; }
@@ -35,7 +36,6 @@ __host__ __device__ constexpr int bwd_cols(int cw) { return cw == 8 ? 8 : cw == 
 constexpr int MIN_FWD_COLS = 2, MIN_BWD_COLS = 2;
 constexpr int BWD_PARTIALS = 1024;  // the backward aims at this many workgroups ...
 constexpr int BWD_MIN_ROWS = 16;    // ... of at least this many rows each
-constexpr int REDUCE_COLS = 64;     // columns per workgroup of dropout_norm_reduce_kernel
 constexpr int MAX_SUMS = 4;         // column sums of a backward
 
 struct Plan {
@@ -44,101 +44,6 @@ struct Plan {
     uint32_t keep_max;    // an element is kept iff its byte <= keep_max
     float inv_keep;       // 1 / (1 - p)
 };
-
-__host__ __device__ __forceinline__ int esize(int dt) { return dt == FA_DTYPE_FP32 ? 4 : 2; }
-
-__device__ __forceinline__ const char *row_of(const void *base, int dt, int64_t row, int64_t stride) {
-    return static_cast<const char *>(base) + row * stride * esize(dt);
-}
-__device__ __forceinline__ char *row_of(void *base, int dt, int64_t row, int64_t stride) {
-    return static_cast<char *>(base) + row * stride * esize(dt);
-}
-
-// CW elements at column ucol + lcol of a row of dtype `dt`, as fp32.  ucol is the wave-uniform part of the column
-template <int CW>
-__device__ __forceinline__ void load_chunk(const void *row, int dt, int ucol, int lcol, float (&v)[CW]) {
-    if (dt == FA_DTYPE_FP32) {
-        const float *p = static_cast<const float *>(row) + ucol + (uint32_t)lcol;
-        if constexpr (CW == 1) {
-            v[0] = *p;
-        } else {
-#pragma unroll
-            for (int i = 0; i < CW; i += 4) {
-                const float4 q = *reinterpret_cast<const float4 *>(p + i);
-                v[i] = q.x; v[i + 1] = q.y; v[i + 2] = q.z; v[i + 3] = q.w;
-            }
-        }
-        return;
-    }
-    const uint16_t *p = static_cast<const uint16_t *>(row) + ucol + (uint32_t)lcol;
-    uint32_t h[CW];
-    if constexpr (CW == 8) {
-        const uint4 q = *reinterpret_cast<const uint4 *>(p);
-        h[0] = q.x & 0xffffu; h[1] = q.x >> 16; h[2] = q.y & 0xffffu; h[3] = q.y >> 16;
-        h[4] = q.z & 0xffffu; h[5] = q.z >> 16; h[6] = q.w & 0xffffu; h[7] = q.w >> 16;
-    } else if constexpr (CW == 4) {
-        const uint2 q = *reinterpret_cast<const uint2 *>(p);
-        h[0] = q.x & 0xffffu; h[1] = q.x >> 16; h[2] = q.y & 0xffffu; h[3] = q.y >> 16;
-    } else {
-        h[0] = *p;
-    }
-    if (dt == FA_DTYPE_BF16) {
-#pragma unroll
-        for (int i = 0; i < CW; ++i) v[i] = __uint_as_float(h[i] << 16);
-    } else {
-#pragma unroll
-        for (int i = 0; i < CW; ++i) v[i] = (float)__builtin_bit_cast(_Float16, (uint16_t)h[i]);
-    }
-}
-
-// ... and back: one rounding to nearest even
-template <int CW>
-__device__ __forceinline__ void store_chunk(void *row, int dt, int ucol, int lcol, const float (&v)[CW]) {
-    if (dt == FA_DTYPE_FP32) {
-        float *p = static_cast<float *>(row) + ucol + (uint32_t)lcol;
-        if constexpr (CW == 1) {
-            *p = v[0];
-        } else {
-#pragma unroll
-            for (int i = 0; i < CW; i += 4) *reinterpret_cast<float4 *>(p + i) = make_float4(v[i], v[i + 1], v[i + 2], v[i + 3]);
-        }
-        return;
-    }
-    uint32_t h[CW];
-    if (dt == FA_DTYPE_BF16) {
-#pragma unroll
-        for (int i = 0; i < CW; ++i) h[i] = __builtin_bit_cast(uint16_t, (__bf16)v[i]);
-    } else {
-#pragma unroll
-        for (int i = 0; i < CW; ++i) h[i] = __builtin_bit_cast(uint16_t, (_Float16)v[i]);
-    }
-    uint16_t *p = static_cast<uint16_t *>(row) + ucol + (uint32_t)lcol;
-    if constexpr (CW == 8) {
-        *reinterpret_cast<uint4 *>(p) = make_uint4(h[0] | h[1] << 16, h[2] | h[3] << 16, h[4] | h[5] << 16, h[6] | h[7] << 16);
-    } else if constexpr (CW == 4) {
-        *reinterpret_cast<uint2 *>(p) = make_uint2(h[0] | h[1] << 16, h[2] | h[3] << 16);
-    } else {
-        *p = (uint16_t)h[0];
-    }
-}
-
-// v as the value a tensor of dtype `dt` holds after one rounding
-template <int CW>
-__device__ __forceinline__ void round_to(int dt, float (&v)[CW]) {
-    if (dt == FA_DTYPE_BF16) {
-#pragma unroll
-        for (int i = 0; i < CW; ++i) v[i] = (float)(__bf16)v[i];
-    } else if (dt == FA_DTYPE_FP16) {
-#pragma unroll
-        for (int i = 0; i < CW; ++i) v[i] = (float)(_Float16)v[i];
-    }
-}
-
-__device__ __forceinline__ float load_one(const void *base, int dt, int64_t i) {
-    float v[1];
-    load_chunk<1>(static_cast<const char *>(base) + i * esize(dt), dt, 0, 0, v);
-    return v[0];
-}
 
 // ---- dropout decisions (restated) ---------------------------------------------------------------------------------
 __device__ __forceinline__ uint32_t lowbias32(uint32_t x) {
@@ -191,34 +96,6 @@ __device__ __forceinline__ void store_mask(uint8_t *row, int col, const bool (&k
         if constexpr (CW == 8) *reinterpret_cast<uint2 *>(row + col) = make_uint2(w[0], w[1]);
         else *reinterpret_cast<uint32_t *>(row + col) = w[0];
     }
-}
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = WAVE / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, WAVE);
-    return v;
-}
-
-// every thread of the workgroup gets the workgroup's sums of v[0..NV).  `phase` picks the LDS slot, the two in turn, so that a
-// slot is not written again before every wavefront has passed the barrier of the sum after the one that read it
-template <int NV>
-__device__ __forceinline__ void group_sum(float (&v)[NV], float (&red)[2][NV][MAX_WAVES], int &phase) {
-#pragma unroll
-    for (int i = 0; i < NV; ++i) v[i] = wave_sum(v[i]);
-    const int wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    if (nw == 1) return;
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int i = 0; i < NV; ++i) red[phase][i][wave] = v[i];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-        float s = 0.0f;
-        for (int w = 0; w < nw; ++w) s += red[phase][i][w];
-        v[i] = s;
-    }
-    phase ^= 1;
 }
 
 // ---- forward ----------------------------------------------------------------------------------------------------------------
@@ -322,7 +199,7 @@ __device__ __forceinline__ void fwd_wide_row(const fa_dropout_norm_fwd_params &p
 #pragma unroll
             for (int i = 0; i < CW; ++i) sum[0] += v[i];
         }
-        group_sum<1>(sum, red, phase);
+        team_sum<1, true>(sum, false, red, phase);
         mu = sum[0] * inv_n;
     }
     float sq[1] = {0.0f};
@@ -332,7 +209,7 @@ __device__ __forceinline__ void fwd_wide_row(const fa_dropout_norm_fwd_params &p
 #pragma unroll
         for (int i = 0; i < CW; ++i) sq[0] += (v[i] - mu) * (v[i] - mu);
     }
-    group_sum<1>(sq, red, phase);
+    team_sum<1, true>(sq, false, red, phase);
     const float rsigma = 1.0f / sqrtf(sq[0] * inv_n + p.eps);
     if (tid == 0) {
         if (!rms) p.mu[r] = mu;
@@ -386,7 +263,7 @@ __global__ __launch_bounds__(1024) void dropout_norm_fwd_kernel(const fa_dropout
         }
         float mu = 0.0f;
         if (!rms) {
-            group_sum<1>(sum, red, phase);
+            team_sum<1, true>(sum, false, red, phase);
             mu = sum[0] * inv_n;
         }
         float sq[1] = {0.0f};
@@ -400,7 +277,7 @@ __global__ __launch_bounds__(1024) void dropout_norm_fwd_kernel(const fa_dropout
                 }
             }
         }
-        group_sum<1>(sq, red, phase);
+        team_sum<1, true>(sq, false, red, phase);
         const float rsigma = 1.0f / sqrtf(sq[0] * inv_n + p.eps);
         if (tid == 0) {
             if (!rms) p.mu[r] = mu;
@@ -454,7 +331,7 @@ __global__ __launch_bounds__(1024) void dropout_norm_bwd_row_sums_kernel(const f
         }
     }
     int phase = 0;
-    group_sum<2>(c, red, phase);
+    team_sum<2, true>(c, false, red, phase);
     if (tid == 0) {
         row_sums[2 * r] = c[0];
         row_sums[2 * r + 1] = c[1];
@@ -527,7 +404,7 @@ __global__ __launch_bounds__(1024) void dropout_norm_bwd_kernel(const fa_dropout
             c[0] = row_sums[2 * r];
             c[1] = row_sums[2 * r + 1];
         } else {
-            group_sum<2>(c, red, phase);
+            team_sum<2, true>(c, false, red, phase);
         }
         const float c1 = c[0] * inv_n, c2 = rms ? 0.0f : c[1] * inv_n;
         const uint32_t key0 = DROP ? row_key(mix, r, 0u) : 0u, key1 = DROP ? row_key(mix, r, 1u) : 0u;
@@ -612,38 +489,19 @@ struct Reduce {
     int32_t dtype[MAX_SUMS];
 };
 
-// dst[s][col] = sum over the P partial rows of sum s: wavefront v of 16 adds the rows v, v + 16, ..., the 16 sums are added in
-// wave order.  A fixed order: the same bits every time.
+// dst[s][col] = sum over the P partial rows of sum s, in the fixed order of reduce_partial_rows
 __global__ __launch_bounds__(1024) void dropout_norm_reduce_kernel(const float *workspace, int P, int N, int sums, const Reduce out) {
     __shared__ float comb[MAX_WAVES][REDUCE_COLS];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, col = blockIdx.x * REDUCE_COLS + lane;
 #pragma unroll
     for (int which = 0; which < MAX_SUMS; ++which) {
         if (which >= sums || !out.dst[which]) continue;
-        const float *src = workspace + (int64_t)which * P * N;
-        float s = 0.0f;
-        if (col < N)
-            for (int q = wave; q < P; q += MAX_WAVES) s += src[(int64_t)q * N + col];
-        comb[wave][lane] = s;
-        __syncthreads();
-        if (wave == 0 && col < N) {
-            float total[1] = {0.0f};
-            for (int v = 0; v < MAX_WAVES; ++v) total[0] += comb[v][lane];
-            store_chunk<1>(out.dst[which], out.dtype[which], 0, col, total);
-        }
-        __syncthreads();
+        reduce_partial_rows(workspace + (int64_t)which * P * N, P, N, out.dst[which], out.dtype[which], comb);
     }
 }
 
 // ---- host -------------------------------------------------------------------------------------------------------------------
-bool known_dtype(int dt) { return dt == FA_DTYPE_FP16 || dt == FA_DTYPE_BF16 || dt == FA_DTYPE_FP32; }
-
-// NULL passes: an absent tensor constrains nothing
-bool aligned_to(const void *q, int bytes) { return reinterpret_cast<uintptr_t>(q) % bytes == 0; }
-bool rows_16_bytes(const void *q, int dt, int64_t stride, int N) {
-    return !q || (aligned_to(q, 16) && (stride * esize(dt)) % 16 == 0 && ((int64_t)N * esize(dt)) % 16 == 0);
-}
-bool vector_16_bytes(const void *q, int dt, int N) { return !q || (aligned_to(q, 16) && ((int64_t)N * esize(dt)) % 16 == 0); }
+// a tensor of rows that are N wide, no element tail
+bool rows_16_bytes(const void *q, int dt, int64_t stride, int N) { return fa_row::rows_16_bytes(q, dt, stride) && vector_16_bytes(q, dt, N); }
 bool mask_16_bytes(const void *q, int N) { return !q || (aligned_to(q, 16) && N % 16 == 0); }
 
 struct Launch {

@@ -1,7 +1,9 @@
 // fa_gemm_act.hip — fa_gemm_act_fwd / fa_gemm_act_dgrad (include/fa_gemm_act.h): a 16-bit GEMM on MFMA with the bias, the
 // activation (forward) or the activation's derivative and the dbias sums (dgrad) in its epilogue.  A translation unit of its
-// own with nothing from the other units: their kernel sets are pinned.  The activations restate those of fa_act.hip, the same
-// fp32 expressions with contraction off (tests/test_gemm_act_gpu.py pins the two to each other bit for bit).
+// own: no kernel comes from another unit or goes to one, because the kernel set of every unit is pinned by its tests.  That
+// rule is about kernels: the activations are the inline functions of fa_act_math.h, the one definition this unit and
+// fa_act.hip have (tests/test_gemm_act_gpu.py pins the two units to each other bit for bit).  Of fa_rowwise.h this unit needs
+// nothing: its accesses are 16-byte chunks of one 16-bit dtype, a template argument here.
 //
 // Both directions are C(M, N) = A(M, K) · B, A row-major: forward B[k][n] = weight[n][k] (rows of K), dgrad B[k][n] =
 // weight[k][n] (rows of N).  A workgroup of 256 threads (4 waves as 2 x 2) owns one BM x 128 tile of C, BM = 128 or (M <= 64)
@@ -17,13 +19,11 @@
 // partial row tile_m; gemm_act_dbias_reduce_kernel adds the partial rows in their order.  No atomics.
 // Block -> tile: blockIdx.x is made contiguous per XCD (a bijective remap) and then walks GROUP_M row tiles per column tile.
 #include "../../include/fa_gemm_act.h"
-#include "../../include/fa_act.h"
-
-#include <hip/hip_runtime.h>
-
-#include <cmath>
+#include "fa_act_math.h"
 
 namespace {
+
+using namespace fa_act_math;
 
 constexpr int THREADS = 256;
 constexpr int BN = 128;      // columns of a tile
@@ -52,78 +52,6 @@ struct GemmArgs {
     int64_t M;
     int32_t N, K, activation, tiles_m, tiles_n;
 };
-
-// ---- the activations (fa_act.hip) ---------------------------------------------------------------------------------------------
-struct Sig {
-    float s, c;
-};
-
-__device__ __forceinline__ Sig sigmoid_parts(float z) {
-#pragma clang fp contract(off)
-    const float e = expf(-fabsf(z));
-    const float hi = 1.0f / (1.0f + e), lo = e * hi;
-    Sig g;
-    g.s = z >= 0.0f ? hi : lo;
-    g.c = z >= 0.0f ? lo : hi;
-    return g;
-}
-
-// a = act(x) and dg = act'(x) * g
-template <int ACT>
-__device__ __forceinline__ void eval(float x, float g, float &a, float &dg) {
-#pragma clang fp contract(off)
-    float da;
-    if constexpr (ACT == FA_ACT_GELU_TANH) {
-        const float x2 = x * x;
-        const Sig g = sigmoid_parts((1.59576912f * x) * (1.0f + 0.044715f * x2));
-        const float w = g.s * g.c;
-        a = x * g.s;
-        da = g.s + (w > 0.0f ? (x * w) * (1.59576912f + 0.2140644486f * x2) : 0.0f);
-    } else if constexpr (ACT == FA_ACT_GELU_ERF) {
-        const float y = x * 0.70710678118654752f;
-        const float phi = x >= 0.0f ? 0.5f * (1.0f + erff(y)) : 0.5f * erfcf(-y);
-        a = x * phi;
-        da = phi + x * (0.39894228040143268f * expf(-0.5f * (x * x)));
-    } else if constexpr (ACT == FA_ACT_RELU) {
-        a = x > 0.0f ? x : (x == x ? 0.0f : x);
-        da = x > 0.0f ? 1.0f : 0.0f;
-    } else if constexpr (ACT == FA_ACT_SQRELU) {
-        const float r = x > 0.0f ? x : (x == x ? 0.0f : x);
-        a = r * r;
-        dg = (r * g) * 2.0f;
-        return;
-    } else if constexpr (ACT == FA_ACT_SILU) {
-        const Sig g = sigmoid_parts(x);
-        a = x * g.s;
-        da = g.s + x * (g.s * g.c);
-    } else if constexpr (ACT == FA_ACT_SIGMOID) {
-        const Sig g = sigmoid_parts(x);
-        a = g.s;
-        da = g.s * g.c;
-    } else {
-        a = x;
-        da = 1.0f;
-    }
-    dg = da * g;
-}
-
-__device__ __forceinline__ void eval_chunk(int act, const float (&x)[8], const float (&g)[8], float (&a)[8], float (&dg)[8]) {
-#define FA_GEMM_ACT_CASE(A)                                                             \
-    case A:                                                                             \
-        _Pragma("unroll") for (int i = 0; i < 8; ++i) eval<A>(x[i], g[i], a[i], dg[i]); \
-        break;
-    switch (act) {
-        FA_GEMM_ACT_CASE(FA_ACT_GELU_TANH)
-        FA_GEMM_ACT_CASE(FA_ACT_GELU_ERF)
-        FA_GEMM_ACT_CASE(FA_ACT_RELU)
-        FA_GEMM_ACT_CASE(FA_ACT_SQRELU)
-        FA_GEMM_ACT_CASE(FA_ACT_SILU)
-        FA_GEMM_ACT_CASE(FA_ACT_SIGMOID)
-    default:
-        _Pragma("unroll") for (int i = 0; i < 8; ++i) eval<FA_ACT_IDENTITY>(x[i], g[i], a[i], dg[i]);
-    }
-#undef FA_GEMM_ACT_CASE
-}
 
 // ---- 16-byte chunks of 8 elements ------------------------------------------------------------------------------------------------
 template <int DT>
@@ -386,7 +314,6 @@ __global__ __launch_bounds__(REDUCE_THREADS) void gemm_act_dbias_reduce_kernel(c
 
 // ---- host -------------------------------------------------------------------------------------------------------------------
 bool half_dtype(int dt) { return dt == FA_DTYPE_FP16 || dt == FA_DTYPE_BF16; }
-bool known_activation(int a) { return a >= FA_ACT_GELU_TANH && a <= FA_ACT_IDENTITY; }
 bool aligned16(const void *q) { return reinterpret_cast<uintptr_t>(q) % 16 == 0; }
 // rows of `len` elements at a pitch of `stride`: 16-byte rows (one row needs no pitch)
 bool rows_ok(int64_t stride, int64_t len, int64_t rows) { return rows <= 1 || (stride >= len && stride % 8 == 0); }

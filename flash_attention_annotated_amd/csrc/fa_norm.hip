@@ -1,5 +1,7 @@
 // fa_norm.hip — fa_norm_fwd / fa_norm_bwd (include/fa_norm.h): fused residual-add + LayerNorm / RMSNorm, forward and backward.
-// A translation unit of its own with nothing from the attention units: the kernel sets of the other units are pinned.
+// A translation unit of its own: no kernel comes from another unit or goes to one, because the kernel set of every unit is
+// pinned by its tests.  That rule is about kernels: the chunk loads and stores, the wavefront and team sums, the ordered
+// reduce of partial rows and the host predicates are the inline functions of fa_rowwise.h, shared with the other row units.
 //
 // A row is the work of a *team*: one wavefront where a lane has at most C columns (four teams, so four rows at a time, in a
 // workgroup of 256), else the whole workgroup of 256 / 512 / 1024 threads (the smallest that gives a thread at most C columns);
@@ -21,138 +23,23 @@
 // the forward walks such a row three times (norm_fwd_wide_kernel), the backward takes the row sums in a launch of their own
 // (norm_bwd_row_sums_kernel) and then splits the columns into slabs of 1024 * C over blockIdx.y of the same norm_bwd_kernel.
 #include "../../include/fa_norm.h"
-
-#include <hip/hip_runtime.h>
+#include "fa_rowwise.h"
 
 namespace {
 
-constexpr int WAVE = 64;
-constexpr int MAX_WAVES = 16;         // of a workgroup
+using namespace fa_row;
+
 constexpr int WAVE_TEAMS = 4;         // wavefronts (rows in flight) of a workgroup of wavefront teams
 constexpr int FWD_COLS = 16;          // columns per thread of the forward forms that keep weight and bias in registers
 constexpr int BWD_COLS = 8;           // ... of the backward forms that keep xhat, w * dy and the weight in registers
 constexpr int BWD_WAVE_ROW_N = WAVE * BWD_COLS;  // the widest row a single wavefront takes in the backward
 constexpr int BWD_PARTIALS = 1024;    // the backward aims at this many workgroups ...
 constexpr int BWD_MIN_ROWS = 16;      // ... of at least this many rows each
-constexpr int REDUCE_COLS = 64;       // columns per workgroup of norm_reduce_kernel
 
 struct Plan {
     int32_t team_wave;    // a team is a wavefront (else the workgroup)
     int32_t rows_per_wg;  // the contiguous block of rows of a workgroup
 };
-
-__host__ __device__ __forceinline__ int esize(int dt) { return dt == FA_DTYPE_FP32 ? 4 : 2; }
-
-__device__ __forceinline__ const char *row_of(const void *base, int dt, int64_t row, int64_t stride) {
-    return static_cast<const char *>(base) + row * stride * esize(dt);
-}
-__device__ __forceinline__ char *row_of(void *base, int dt, int64_t row, int64_t stride) {
-    return static_cast<char *>(base) + row * stride * esize(dt);
-}
-
-// CW elements at column ucol + lcol of a row of dtype `dt`, as fp32.  ucol is the wave-uniform part of the column: with a
-// uniform row it goes into the scalar base of the access, and the lane's part is one 32-bit offset for all chunks of a thread
-template <int CW>
-__device__ __forceinline__ void load_chunk(const void *row, int dt, int ucol, int lcol, float (&v)[CW]) {
-    if (dt == FA_DTYPE_FP32) {
-        const float *p = static_cast<const float *>(row) + ucol + (uint32_t)lcol;
-        if constexpr (CW == 1) {
-            v[0] = *p;
-        } else {
-#pragma unroll
-            for (int i = 0; i < CW; i += 4) {
-                const float4 q = *reinterpret_cast<const float4 *>(p + i);
-                v[i] = q.x; v[i + 1] = q.y; v[i + 2] = q.z; v[i + 3] = q.w;
-            }
-        }
-        return;
-    }
-    const uint16_t *p = static_cast<const uint16_t *>(row) + ucol + (uint32_t)lcol;
-    uint32_t h[CW];
-    if constexpr (CW == 8) {
-        const uint4 q = *reinterpret_cast<const uint4 *>(p);
-        h[0] = q.x & 0xffffu; h[1] = q.x >> 16; h[2] = q.y & 0xffffu; h[3] = q.y >> 16;
-        h[4] = q.z & 0xffffu; h[5] = q.z >> 16; h[6] = q.w & 0xffffu; h[7] = q.w >> 16;
-    } else if constexpr (CW == 4) {
-        const uint2 q = *reinterpret_cast<const uint2 *>(p);
-        h[0] = q.x & 0xffffu; h[1] = q.x >> 16; h[2] = q.y & 0xffffu; h[3] = q.y >> 16;
-    } else {
-        h[0] = *p;
-    }
-    if (dt == FA_DTYPE_BF16) {
-#pragma unroll
-        for (int i = 0; i < CW; ++i) v[i] = __uint_as_float(h[i] << 16);
-    } else {
-#pragma unroll
-        for (int i = 0; i < CW; ++i) v[i] = (float)__builtin_bit_cast(_Float16, (uint16_t)h[i]);
-    }
-}
-
-// ... and back: one rounding to nearest even
-template <int CW>
-__device__ __forceinline__ void store_chunk(void *row, int dt, int ucol, int lcol, const float (&v)[CW]) {
-    if (dt == FA_DTYPE_FP32) {
-        float *p = static_cast<float *>(row) + ucol + (uint32_t)lcol;
-        if constexpr (CW == 1) {
-            *p = v[0];
-        } else {
-#pragma unroll
-            for (int i = 0; i < CW; i += 4) *reinterpret_cast<float4 *>(p + i) = make_float4(v[i], v[i + 1], v[i + 2], v[i + 3]);
-        }
-        return;
-    }
-    uint32_t h[CW];
-    if (dt == FA_DTYPE_BF16) {
-#pragma unroll
-        for (int i = 0; i < CW; ++i) h[i] = __builtin_bit_cast(uint16_t, (__bf16)v[i]);
-    } else {
-#pragma unroll
-        for (int i = 0; i < CW; ++i) h[i] = __builtin_bit_cast(uint16_t, (_Float16)v[i]);
-    }
-    uint16_t *p = static_cast<uint16_t *>(row) + ucol + (uint32_t)lcol;
-    if constexpr (CW == 8) {
-        *reinterpret_cast<uint4 *>(p) = make_uint4(h[0] | h[1] << 16, h[2] | h[3] << 16, h[4] | h[5] << 16, h[6] | h[7] << 16);
-    } else if constexpr (CW == 4) {
-        *reinterpret_cast<uint2 *>(p) = make_uint2(h[0] | h[1] << 16, h[2] | h[3] << 16);
-    } else {
-        *p = (uint16_t)h[0];
-    }
-}
-
-__device__ __forceinline__ float load_one(const void *base, int dt, int64_t i) {
-    float v[1];
-    load_chunk<1>(static_cast<const char *>(base) + i * esize(dt), dt, 0, 0, v);
-    return v[0];
-}
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = WAVE / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, WAVE);
-    return v;
-}
-
-// every thread of the team gets the team's sums of v[0..NV).  Called by all threads of the workgroup together; `phase` picks
-// the LDS slot, the two in turn, so that a slot is not written again before every wavefront has passed the barrier of the sum
-// after the one that read it
-template <int NV>
-__device__ __forceinline__ void team_sum(float (&v)[NV], bool team_wave, float (&red)[2][NV][MAX_WAVES], int &phase) {
-#pragma unroll
-    for (int i = 0; i < NV; ++i) v[i] = wave_sum(v[i]);
-    if (team_wave) return;
-    const int wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int i = 0; i < NV; ++i) red[phase][i][wave] = v[i];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-        float s = 0.0f;
-        for (int w = 0; w < nw; ++w) s += red[phase][i][w];
-        v[i] = s;
-    }
-    phase ^= 1;
-}
 
 // the team of this thread and the rows it takes: r = first, first + step, ... < last
 struct Team {
@@ -511,38 +398,19 @@ __global__ __launch_bounds__(1024) void norm_bwd_kernel(const fa_norm_bwd_params
     }
 }
 
-// dw[col] = sum over the P partial rows, db likewise: wavefront v of 16 adds the rows v, v + 16, ..., the 16 sums are added in
-// wave order.  A fixed order: the same bits every time.
+// dw[col] = sum over the P partial rows, db likewise, in the fixed order of reduce_partial_rows
 __global__ __launch_bounds__(1024) void norm_reduce_kernel(const float *workspace, int P, int N, void *dw, int dw_dtype, void *db,
                                                            int db_dtype) {
     __shared__ float comb[MAX_WAVES][REDUCE_COLS];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, col = blockIdx.x * REDUCE_COLS + lane;
 #pragma unroll
     for (int which = 0; which < 2; ++which) {
         void *dst = which ? db : dw;
         if (!dst) continue;
-        const float *src = workspace + (int64_t)which * P * N;
-        float s = 0.0f;
-        if (col < N)
-            for (int q = wave; q < P; q += MAX_WAVES) s += src[(int64_t)q * N + col];
-        comb[wave][lane] = s;
-        __syncthreads();
-        if (wave == 0 && col < N) {
-            float total[1] = {0.0f};
-            for (int v = 0; v < MAX_WAVES; ++v) total[0] += comb[v][lane];
-            store_chunk<1>(dst, which ? db_dtype : dw_dtype, 0, col, total);
-        }
-        __syncthreads();
+        reduce_partial_rows(workspace + (int64_t)which * P * N, P, N, dst, which ? db_dtype : dw_dtype, comb);
     }
 }
 
 // ---- host -------------------------------------------------------------------------------------------------------------------
-bool known_dtype(int dt) { return dt == FA_DTYPE_FP16 || dt == FA_DTYPE_BF16 || dt == FA_DTYPE_FP32; }
-
-// NULL passes: an absent tensor constrains nothing
-bool aligned_to(const void *q, int bytes) { return reinterpret_cast<uintptr_t>(q) % bytes == 0; }
-bool rows_16_bytes(const void *q, int dt, int64_t stride) { return !q || (aligned_to(q, 16) && (stride * esize(dt)) % 16 == 0); }
-
 struct Launch {
     int cw;         // 8 / 4: 16-byte accesses of x; 1: element accesses
     bool wide;      // rows of more than 1024 * cols columns

@@ -1,6 +1,7 @@
 // fa_xent.hip — fa_xent_fwd / fa_xent_bwd (include/fa_xent.h): the fused cross-entropy loss, forward and backward.
-// A translation unit of its own with nothing from the other units (the chunk loads and stores restate those of fa_norm.hip):
-// the kernel sets of the other units are pinned.
+// A translation unit of its own: no kernel comes from another unit or goes to one, because the kernel set of every unit is
+// pinned by its tests.  That rule is about kernels: the chunk loads and stores and the host predicates are the inline
+// functions of fa_rowwise.h, shared with the other row units.
 //
 // A row of any pitch and base is three pieces: an element *head* up to the first 16-byte boundary (at most CW - 1 elements), a
 // *body* of 16-byte chunks of CW elements (8 of a 16-bit dtype, 4 of fp32), and an element *tail* (at most CW - 1).  The head is
@@ -14,14 +15,14 @@
 // loads its BWD_CHUNKS chunks, then computes and stores them: in place it overwrites only what it has read.  The rows of a
 // slab column are consecutive workgroups.  No atomics anywhere.
 #include "../../include/fa_xent.h"
-
-#include <hip/hip_runtime.h>
+#include "fa_rowwise.h"
 
 #include <cmath>
 
 namespace {
 
-constexpr int WAVE = 64;
+using namespace fa_row;
+
 constexpr int THREADS = 256;
 constexpr int WAVES = THREADS / WAVE;
 constexpr int FWD_UNROLL = 4;           // body chunks a thread has in flight, and absorbs with one rescale
@@ -32,80 +33,6 @@ constexpr int BWD_SLAB = THREADS * BWD_CHUNKS;
 constexpr int BWD_MAX_SLABS = 256;      // grid.x; further slabs are walked
 constexpr int BWD_MAX_ROWS = 65535;     // grid.y; further rows are walked
 constexpr float LOG2E = 1.44269504088896340736f, LN2 = 0.69314718055994530942f;
-
-__host__ __device__ __forceinline__ int esize(int dt) { return dt == FA_DTYPE_FP32 ? 4 : 2; }
-
-// CW elements of dtype `dt` at q, as fp32: one 16-byte access where CW > 1
-template <int CW>
-__device__ __forceinline__ void load_chunk(const char *q, int dt, float (&v)[CW]) {
-    if (dt == FA_DTYPE_FP32) {
-        const float *p = reinterpret_cast<const float *>(q);
-        if constexpr (CW == 1) {
-            v[0] = *p;
-        } else {
-#pragma unroll
-            for (int i = 0; i < CW; i += 4) {
-                const float4 f = *reinterpret_cast<const float4 *>(p + i);
-                v[i] = f.x; v[i + 1] = f.y; v[i + 2] = f.z; v[i + 3] = f.w;
-            }
-        }
-        return;
-    }
-    uint32_t h[CW];
-    if constexpr (CW == 8) {
-        const uint4 f = *reinterpret_cast<const uint4 *>(q);
-        h[0] = f.x & 0xffffu; h[1] = f.x >> 16; h[2] = f.y & 0xffffu; h[3] = f.y >> 16;
-        h[4] = f.z & 0xffffu; h[5] = f.z >> 16; h[6] = f.w & 0xffffu; h[7] = f.w >> 16;
-    } else if constexpr (CW == 4) {
-        const uint2 f = *reinterpret_cast<const uint2 *>(q);
-        h[0] = f.x & 0xffffu; h[1] = f.x >> 16; h[2] = f.y & 0xffffu; h[3] = f.y >> 16;
-    } else {
-        h[0] = *reinterpret_cast<const uint16_t *>(q);
-    }
-    if (dt == FA_DTYPE_BF16) {
-#pragma unroll
-        for (int i = 0; i < CW; ++i) v[i] = __uint_as_float(h[i] << 16);
-    } else {
-#pragma unroll
-        for (int i = 0; i < CW; ++i) v[i] = (float)__builtin_bit_cast(_Float16, (uint16_t)h[i]);
-    }
-}
-
-// ... and back: one rounding to nearest even
-template <int CW>
-__device__ __forceinline__ void store_chunk(char *q, int dt, const float (&v)[CW]) {
-    if (dt == FA_DTYPE_FP32) {
-        float *p = reinterpret_cast<float *>(q);
-        if constexpr (CW == 1) {
-            *p = v[0];
-        } else {
-#pragma unroll
-            for (int i = 0; i < CW; i += 4) *reinterpret_cast<float4 *>(p + i) = make_float4(v[i], v[i + 1], v[i + 2], v[i + 3]);
-        }
-        return;
-    }
-    uint32_t h[CW];
-    if (dt == FA_DTYPE_BF16) {
-#pragma unroll
-        for (int i = 0; i < CW; ++i) h[i] = __builtin_bit_cast(uint16_t, (__bf16)v[i]);
-    } else {
-#pragma unroll
-        for (int i = 0; i < CW; ++i) h[i] = __builtin_bit_cast(uint16_t, (_Float16)v[i]);
-    }
-    if constexpr (CW == 8) {
-        *reinterpret_cast<uint4 *>(q) = make_uint4(h[0] | h[1] << 16, h[2] | h[3] << 16, h[4] | h[5] << 16, h[6] | h[7] << 16);
-    } else if constexpr (CW == 4) {
-        *reinterpret_cast<uint2 *>(q) = make_uint2(h[0] | h[1] << 16, h[2] | h[3] << 16);
-    } else {
-        *reinterpret_cast<uint16_t *>(q) = (uint16_t)h[0];
-    }
-}
-
-__device__ __forceinline__ float load_one(const char *row, int dt, int64_t col) {
-    float v[1];
-    load_chunk<1>(row + col * esize(dt), dt, v);
-    return v[0];
-}
 
 __device__ __forceinline__ int64_t load_label(const void *labels, int dt, int64_t r) {
     return dt == FA_XENT_LABELS_INT32 ? (int64_t) static_cast<const int32_t *>(labels)[r] : static_cast<const int64_t *>(labels)[r];
@@ -334,9 +261,7 @@ __global__ __launch_bounds__(THREADS) void xent_bwd_kernel(const fa_xent_bwd_par
 }
 
 // ---- host -------------------------------------------------------------------------------------------------------------------
-bool known_dtype(int dt) { return dt == FA_DTYPE_FP16 || dt == FA_DTYPE_BF16 || dt == FA_DTYPE_FP32; }
 bool known_labels(int dt) { return dt == FA_XENT_LABELS_INT64 || dt == FA_XENT_LABELS_INT32; }
-bool aligned_to(const void *q, int bytes) { return reinterpret_cast<uintptr_t>(q) % bytes == 0; }
 
 int check_numbers(int64_t M, int N, int64_t total_classes, float smoothing, float logit_scale) {
     if (M < 0 || N < 1 || total_classes < N) return FA_ERR_BAD_SHAPE;

@@ -2225,11 +2225,13 @@ Tensor rotary_emb(const Tensor &x, const Tensor &cos_, const Tensor &sin_, const
 // ---- fused residual-add + LayerNorm / RMSNorm (flash_attn.ops.triton.layer_norm -> _layer_norm_fwd_impl / _layer_norm_bwd_impl,
 // flash_attn/ops/triton/layer_norm.py:355-468, 702-843, without dropout and the parallel form).  Launches on the current stream,
 // no synchronisation; mean / rstd, the gradients and the workspace come from the caching allocator: capturable in a HIP graph.
-int norm_dtype_code(at::ScalarType t, const char *what) {
+// The dtype code of a tensor of the row operators (norm, cross-entropy, activations, GEMM + activation), and the shape checks
+// they share; `prefix` is the operator's name as its messages start
+int row_dtype_code(const char *prefix, at::ScalarType t, const char *what, bool fp32 = true) {
     if (t == at::kHalf) return FA_DTYPE_FP16;
     if (t == at::kBFloat16) return FA_DTYPE_BF16;
-    if (t == at::kFloat) return FA_DTYPE_FP32;
-    TORCH_CHECK(false, "layer_norm: ", what, " must be fp16, bf16 or fp32");
+    if (t == at::kFloat && fp32) return FA_DTYPE_FP32;
+    TORCH_CHECK(false, prefix, what, fp32 ? " must be fp16, bf16 or fp32" : " must be fp16 or bf16");
     return -1;
 }
 
@@ -2238,16 +2240,16 @@ at::ScalarType norm_scalar_type(int64_t code) {
     return code == FA_DTYPE_FP16 ? at::kHalf : code == FA_DTYPE_BF16 ? at::kBFloat16 : at::kFloat;
 }
 
-void check_norm_rows(const Tensor &t, const char *name, int64_t M, int64_t N) {
-    TORCH_CHECK(t.is_cuda(), "layer_norm: ", name, " must be on CUDA");
-    TORCH_CHECK(t.dim() == 2 && t.size(0) == M && t.size(1) == N, "layer_norm: ", name, " must have shape (M, N)");
-    TORCH_CHECK(t.stride(-1) == 1, "layer_norm: ", name, " must have contiguous last dimension");
+void check_rows(const char *prefix, const char *shape, const Tensor &t, const char *name, int64_t M, int64_t N) {
+    TORCH_CHECK(t.is_cuda(), prefix, name, " must be on CUDA");
+    TORCH_CHECK(t.dim() == 2 && t.size(0) == M && t.size(1) == N, prefix, name, " must have shape ", shape);
+    TORCH_CHECK(t.stride(-1) == 1, prefix, name, " must have contiguous last dimension");
 }
 
-void check_norm_vector(const Tensor &t, const char *name, int64_t n, const char *shape) {
-    TORCH_CHECK(t.is_cuda(), "layer_norm: ", name, " must be on CUDA");
-    TORCH_CHECK(t.dim() == 1 && t.size(0) == n, "layer_norm: ", name, " must have shape ", shape);
-    TORCH_CHECK(t.is_contiguous(), "layer_norm: ", name, " must be contiguous");
+void check_vector(const char *prefix, const Tensor &t, const char *name, int64_t n, const char *shape, bool contiguous = true) {
+    TORCH_CHECK(t.is_cuda(), prefix, name, " must be on CUDA");
+    TORCH_CHECK(t.dim() == 1 && t.size(0) == n, prefix, name, " must have shape ", shape);
+    TORCH_CHECK(!contiguous || t.is_contiguous(), prefix, name, " must be contiguous");
 }
 
 void check_norm_width(const Tensor &x) {
@@ -2270,24 +2272,24 @@ std::tuple<Tensor, Tensor> norm_fwd_impl(const Tensor &x, const Tensor &weight, 
     TORCH_CHECK(x.is_cuda(), "layer_norm: x must be on CUDA");
     TORCH_CHECK(x.dim() == 2, "layer_norm: x must have shape (M, N)");
     const int64_t M = x.size(0), N = x.size(1);
-    check_norm_rows(x, "x", M, N);
-    check_norm_rows(out, "out", M, N);
-    check_norm_vector(weight, "weight", N, "(N)");
-    if (bias.has_value()) check_norm_vector(*bias, "bias", N, "(N)");
-    if (residual.has_value()) check_norm_rows(*residual, "residual", M, N);
-    if (residual_out.has_value()) check_norm_rows(*residual_out, "residual_out", M, N);
-    if (rowscale.has_value()) check_norm_vector(*rowscale, "rowscale", M, "(M)");
+    check_rows("layer_norm: ", "(M, N)", x, "x", M, N);
+    check_rows("layer_norm: ", "(M, N)", out, "out", M, N);
+    check_vector("layer_norm: ", weight, "weight", N, "(N)");
+    if (bias.has_value()) check_vector("layer_norm: ", *bias, "bias", N, "(N)");
+    if (residual.has_value()) check_rows("layer_norm: ", "(M, N)", *residual, "residual", M, N);
+    if (residual_out.has_value()) check_rows("layer_norm: ", "(M, N)", *residual_out, "residual_out", M, N);
+    if (rowscale.has_value()) check_vector("layer_norm: ", *rowscale, "rowscale", M, "(M)");
     check_norm_width(x);
     fa_norm_fwd_params p{};
     p.abi_version = FA_ABI_VERSION;
     p.struct_size = sizeof(fa_norm_fwd_params);
-    p.x_dtype = norm_dtype_code(x.scalar_type(), "x");
-    p.weight_dtype = norm_dtype_code(weight.scalar_type(), "weight");
-    p.y_dtype = norm_dtype_code(out.scalar_type(), "out");
-    p.bias_dtype = bias.has_value() ? norm_dtype_code(bias->scalar_type(), "bias") : p.weight_dtype;
-    p.residual_dtype = residual.has_value() ? norm_dtype_code(residual->scalar_type(), "residual") : p.x_dtype;
-    p.residual_out_dtype = residual_out.has_value() ? norm_dtype_code(residual_out->scalar_type(), "residual_out") : p.x_dtype;
-    p.rowscale_dtype = rowscale.has_value() ? norm_dtype_code(rowscale->scalar_type(), "rowscale") : p.x_dtype;
+    p.x_dtype = row_dtype_code("layer_norm: ", x.scalar_type(), "x");
+    p.weight_dtype = row_dtype_code("layer_norm: ", weight.scalar_type(), "weight");
+    p.y_dtype = row_dtype_code("layer_norm: ", out.scalar_type(), "out");
+    p.bias_dtype = bias.has_value() ? row_dtype_code("layer_norm: ", bias->scalar_type(), "bias") : p.weight_dtype;
+    p.residual_dtype = residual.has_value() ? row_dtype_code("layer_norm: ", residual->scalar_type(), "residual") : p.x_dtype;
+    p.residual_out_dtype = residual_out.has_value() ? row_dtype_code("layer_norm: ", residual_out->scalar_type(), "residual_out") : p.x_dtype;
+    p.rowscale_dtype = rowscale.has_value() ? row_dtype_code("layer_norm: ", rowscale->scalar_type(), "rowscale") : p.x_dtype;
     TORCH_CHECK(p.residual_dtype == p.x_dtype || p.residual_dtype == FA_DTYPE_FP32, "layer_norm: residual must have the dtype of x or fp32");
     TORCH_CHECK(p.residual_out_dtype == p.x_dtype || p.residual_out_dtype == FA_DTYPE_FP32,
                 "layer_norm: residual_out must have the dtype of x or fp32");
@@ -2338,29 +2340,29 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> norm_bwd_impl(const Tensor &d
     TORCH_CHECK(x.is_cuda(), "layer_norm: x must be on CUDA");
     TORCH_CHECK(x.dim() == 2, "layer_norm: x must have shape (M, N)");
     const int64_t M = x.size(0), N = x.size(1);
-    check_norm_rows(x, "x", M, N);
-    check_norm_rows(dy, "dy", M, N);
-    check_norm_vector(weight, "weight", N, "(N)");
-    if (bias.has_value()) check_norm_vector(*bias, "bias", N, "(N)");
-    if (dresidual.has_value()) check_norm_rows(*dresidual, "dresidual", M, N);
-    if (rowscale.has_value()) check_norm_vector(*rowscale, "rowscale", M, "(M)");
+    check_rows("layer_norm: ", "(M, N)", x, "x", M, N);
+    check_rows("layer_norm: ", "(M, N)", dy, "dy", M, N);
+    check_vector("layer_norm: ", weight, "weight", N, "(N)");
+    if (bias.has_value()) check_vector("layer_norm: ", *bias, "bias", N, "(N)");
+    if (dresidual.has_value()) check_rows("layer_norm: ", "(M, N)", *dresidual, "dresidual", M, N);
+    if (rowscale.has_value()) check_vector("layer_norm: ", *rowscale, "rowscale", M, "(M)");
     TORCH_CHECK(is_rms_norm || mean.has_value(), "layer_norm: mean is required unless is_rms_norm");
-    if (!is_rms_norm) check_norm_vector(*mean, "mean", M, "(M)");
-    check_norm_vector(rstd, "rstd", M, "(M)");
+    if (!is_rms_norm) check_vector("layer_norm: ", *mean, "mean", M, "(M)");
+    check_vector("layer_norm: ", rstd, "rstd", M, "(M)");
     TORCH_CHECK(rstd.scalar_type() == at::kFloat && (is_rms_norm || mean->scalar_type() == at::kFloat), "layer_norm: mean and rstd must be fp32");
     check_norm_width(x);
     fa_norm_bwd_params p{};
     p.abi_version = FA_ABI_VERSION;
     p.struct_size = sizeof(fa_norm_bwd_params);
-    p.x_dtype = norm_dtype_code(x.scalar_type(), "x");
-    p.dy_dtype = norm_dtype_code(dy.scalar_type(), "dy");
-    p.weight_dtype = norm_dtype_code(weight.scalar_type(), "weight");
-    p.bias_dtype = bias.has_value() ? norm_dtype_code(bias->scalar_type(), "bias") : p.weight_dtype;
+    p.x_dtype = row_dtype_code("layer_norm: ", x.scalar_type(), "x");
+    p.dy_dtype = row_dtype_code("layer_norm: ", dy.scalar_type(), "dy");
+    p.weight_dtype = row_dtype_code("layer_norm: ", weight.scalar_type(), "weight");
+    p.bias_dtype = bias.has_value() ? row_dtype_code("layer_norm: ", bias->scalar_type(), "bias") : p.weight_dtype;
     p.dx_dtype = (int32_t)dx_dtype;
-    p.dresidual_dtype = dresidual.has_value() ? norm_dtype_code(dresidual->scalar_type(), "dresidual") : p.x_dtype;
+    p.dresidual_dtype = dresidual.has_value() ? row_dtype_code("layer_norm: ", dresidual->scalar_type(), "dresidual") : p.x_dtype;
     p.dresidual_in_dtype = p.x_dtype;
     p.y_dtype = p.dy_dtype;
-    p.rowscale_dtype = rowscale.has_value() ? norm_dtype_code(rowscale->scalar_type(), "rowscale") : p.x_dtype;
+    p.rowscale_dtype = rowscale.has_value() ? row_dtype_code("layer_norm: ", rowscale->scalar_type(), "rowscale") : p.x_dtype;
     TORCH_CHECK(p.dresidual_dtype == p.x_dtype, "layer_norm: dresidual must have the dtype of x");
     TORCH_CHECK(p.x_dtype == p.dx_dtype || p.x_dtype == FA_DTYPE_FP32, "layer_norm: x must have the dtype of dx or fp32");
     c10::hip::HIPGuardMasqueradingAsCUDA device_guard(x.device());
@@ -2438,17 +2440,17 @@ DropoutNormFwdOut dropout_norm_fwd_impl(const Tensor &x0, const OptTensor &x1, c
     TORCH_CHECK(x0.dim() == 2, "dropout_add_layer_norm: x0 must have shape (M, N)");
     TORCH_CHECK(p_dropout >= 0.0 && p_dropout < 1.0, "dropout_add_layer_norm: dropout_p must be in [0, 1)");
     const int64_t M = x0.size(0), N = x0.size(1);
-    check_norm_rows(x0, "x0", M, N);
-    if (x1.has_value()) check_norm_rows(*x1, "x1", M, N);
-    if (residual.has_value()) check_norm_rows(*residual, "residual", M, N);
-    check_norm_vector(weight0, "weight0", N, "(N)");
+    check_rows("layer_norm: ", "(M, N)", x0, "x0", M, N);
+    if (x1.has_value()) check_rows("layer_norm: ", "(M, N)", *x1, "x1", M, N);
+    if (residual.has_value()) check_rows("layer_norm: ", "(M, N)", *residual, "residual", M, N);
+    check_vector("layer_norm: ", weight0, "weight0", N, "(N)");
     for (const OptTensor *t : {&bias0, &weight1, &bias1}) {
         if (!t->has_value()) continue;
-        check_norm_vector(**t, "bias0 / weight1 / bias1", N, "(N)");
+        check_vector("layer_norm: ", **t, "bias0 / weight1 / bias1", N, "(N)");
         TORCH_CHECK((*t)->scalar_type() == weight0.scalar_type(), "dropout_add_layer_norm: the weights and biases must have one dtype");
     }
-    if (rowscale.has_value()) check_norm_vector(*rowscale, "rowscale", M, "(M)");
-    if (colscale.has_value()) check_norm_vector(*colscale, "colscale", N, "(N)");
+    if (rowscale.has_value()) check_vector("layer_norm: ", *rowscale, "rowscale", M, "(M)");
+    if (colscale.has_value()) check_vector("layer_norm: ", *colscale, "colscale", N, "(N)");
     TORCH_CHECK(!(x1.has_value() || weight1.has_value()) || !(rowscale.has_value() || colscale.has_value()),
                 "dropout_add_layer_norm: rowscale / colscale are not supported with the parallel form");
     TORCH_CHECK(!bias1.has_value() || weight1.has_value(), "dropout_add_layer_norm: bias1 needs weight1");
@@ -2457,13 +2459,13 @@ DropoutNormFwdOut dropout_norm_fwd_impl(const Tensor &x0, const OptTensor &x1, c
     fa_dropout_norm_fwd_params p{};
     p.abi_version = FA_ABI_VERSION;
     p.struct_size = sizeof(fa_dropout_norm_fwd_params);
-    p.x0_dtype = norm_dtype_code(x0.scalar_type(), "x0");
-    p.weight_dtype = norm_dtype_code(weight0.scalar_type(), "weight0");
+    p.x0_dtype = row_dtype_code("layer_norm: ", x0.scalar_type(), "x0");
+    p.weight_dtype = row_dtype_code("layer_norm: ", weight0.scalar_type(), "weight0");
     p.z_dtype = p.x0_dtype;
-    p.residual_dtype = residual.has_value() ? norm_dtype_code(residual->scalar_type(), "residual") : p.x0_dtype;
+    p.residual_dtype = residual.has_value() ? row_dtype_code("layer_norm: ", residual->scalar_type(), "residual") : p.x0_dtype;
     p.x_dtype = residual.has_value() ? p.residual_dtype : residual_in_fp32 ? FA_DTYPE_FP32 : p.x0_dtype;
-    p.rowscale_dtype = rowscale.has_value() ? norm_dtype_code(rowscale->scalar_type(), "rowscale") : p.x0_dtype;
-    p.colscale_dtype = colscale.has_value() ? norm_dtype_code(colscale->scalar_type(), "colscale") : p.x0_dtype;
+    p.rowscale_dtype = rowscale.has_value() ? row_dtype_code("layer_norm: ", rowscale->scalar_type(), "rowscale") : p.x0_dtype;
+    p.colscale_dtype = colscale.has_value() ? row_dtype_code("layer_norm: ", colscale->scalar_type(), "colscale") : p.x0_dtype;
     TORCH_CHECK(p.x_dtype == p.x0_dtype || p.x_dtype == FA_DTYPE_FP32, "dropout_add_layer_norm: residual must have the dtype of x0 or fp32");
     const at::ScalarType stream_type = norm_scalar_type(p.x_dtype);
     TORCH_CHECK_WITH(Error, N * (int64_t)c10::elementSize(stream_type) <= FA_NORM_MAX_ROW_BYTES,
@@ -2533,32 +2535,32 @@ DropoutNormBwdOut dropout_norm_bwd_impl(const Tensor &dz0, const OptTensor &dz1,
     TORCH_CHECK(x.is_cuda(), "dropout_add_layer_norm: x must be on CUDA");
     TORCH_CHECK(x.dim() == 2, "dropout_add_layer_norm: x must have shape (M, N)");
     const int64_t M = x.size(0), N = x.size(1);
-    check_norm_rows(x, "x", M, N);
-    check_norm_rows(dz0, "dz0", M, N);
+    check_rows("layer_norm: ", "(M, N)", x, "x", M, N);
+    check_rows("layer_norm: ", "(M, N)", dz0, "dz0", M, N);
     TORCH_CHECK(dz1.has_value() == weight1.has_value(), "dropout_add_layer_norm: dz1 goes with weight1");
     if (dz1.has_value()) {
-        check_norm_rows(*dz1, "dz1", M, N);
+        check_rows("layer_norm: ", "(M, N)", *dz1, "dz1", M, N);
         TORCH_CHECK(dz1->scalar_type() == dz0.scalar_type(), "dropout_add_layer_norm: dz1 must have the dtype of dz0");
-        check_norm_vector(*weight1, "weight1", N, "(N)");
+        check_vector("layer_norm: ", *weight1, "weight1", N, "(N)");
         TORCH_CHECK(weight1->scalar_type() == weight0.scalar_type(), "dropout_add_layer_norm: the weights must have one dtype");
     }
     if (dx.has_value()) {
-        check_norm_rows(*dx, "dx", M, N);
+        check_rows("layer_norm: ", "(M, N)", *dx, "dx", M, N);
         TORCH_CHECK(dx->scalar_type() == x.scalar_type(), "dropout_add_layer_norm: dx must have the dtype of x");
     }
-    check_norm_vector(weight0, "weight0", N, "(N)");
-    if (rowscale.has_value()) check_norm_vector(*rowscale, "rowscale", M, "(M)");
+    check_vector("layer_norm: ", weight0, "weight0", N, "(N)");
+    if (rowscale.has_value()) check_vector("layer_norm: ", *rowscale, "rowscale", M, "(M)");
     if (colscale.has_value()) {
-        check_norm_vector(*colscale, "colscale", N, "(N)");
+        check_vector("layer_norm: ", *colscale, "colscale", N, "(N)");
         TORCH_CHECK(x0.has_value(), "dropout_add_layer_norm: x0 is required to compute the gradient of colscale");
-        check_norm_rows(*x0, "x0", M, N);
-        TORCH_CHECK(norm_dtype_code(x0->scalar_type(), "x0") == x0_dtype, "dropout_add_layer_norm: x0 must have the dtype x0_dtype names");
+        check_rows("layer_norm: ", "(M, N)", *x0, "x0", M, N);
+        TORCH_CHECK(row_dtype_code("layer_norm: ", x0->scalar_type(), "x0") == x0_dtype, "dropout_add_layer_norm: x0 must have the dtype x0_dtype names");
     }
     TORCH_CHECK(!(has_x1 || weight1.has_value()) || !(rowscale.has_value() || colscale.has_value()),
                 "dropout_add_layer_norm: rowscale / colscale are not supported with the parallel form");
     TORCH_CHECK(is_rms_norm || mu.has_value(), "dropout_add_layer_norm: mu is required unless is_rms_norm");
-    if (!is_rms_norm) check_norm_vector(*mu, "mu", M, "(M)");
-    check_norm_vector(rsigma, "rsigma", M, "(M)");
+    if (!is_rms_norm) check_vector("layer_norm: ", *mu, "mu", M, "(M)");
+    check_vector("layer_norm: ", rsigma, "rsigma", M, "(M)");
     TORCH_CHECK(rsigma.scalar_type() == at::kFloat && (is_rms_norm || mu->scalar_type() == at::kFloat),
                 "dropout_add_layer_norm: mu and rsigma must be fp32");
     TORCH_CHECK(rng_state.is_cuda() && rng_state.scalar_type() == at::kLong && rng_state.numel() == 2 && rng_state.is_contiguous(),
@@ -2568,12 +2570,12 @@ DropoutNormBwdOut dropout_norm_bwd_impl(const Tensor &dz0, const OptTensor &dz1,
     fa_dropout_norm_bwd_params p{};
     p.abi_version = FA_ABI_VERSION;
     p.struct_size = sizeof(fa_dropout_norm_bwd_params);
-    p.x_dtype = norm_dtype_code(x.scalar_type(), "x");
-    p.dz_dtype = norm_dtype_code(dz0.scalar_type(), "dz0");
-    p.weight_dtype = norm_dtype_code(weight0.scalar_type(), "weight0");
+    p.x_dtype = row_dtype_code("layer_norm: ", x.scalar_type(), "x");
+    p.dz_dtype = row_dtype_code("layer_norm: ", dz0.scalar_type(), "dz0");
+    p.weight_dtype = row_dtype_code("layer_norm: ", weight0.scalar_type(), "weight0");
     p.x0_dtype = (int32_t)x0_dtype;
-    p.rowscale_dtype = rowscale.has_value() ? norm_dtype_code(rowscale->scalar_type(), "rowscale") : p.x0_dtype;
-    p.colscale_dtype = colscale.has_value() ? norm_dtype_code(colscale->scalar_type(), "colscale") : p.x0_dtype;
+    p.rowscale_dtype = rowscale.has_value() ? row_dtype_code("layer_norm: ", rowscale->scalar_type(), "rowscale") : p.x0_dtype;
+    p.colscale_dtype = colscale.has_value() ? row_dtype_code("layer_norm: ", colscale->scalar_type(), "colscale") : p.x0_dtype;
     const at::ScalarType in_type = norm_scalar_type(x0_dtype);
     TORCH_CHECK(p.x_dtype == p.x0_dtype || p.x_dtype == FA_DTYPE_FP32, "dropout_add_layer_norm: x must have the dtype of x0 or fp32");
     c10::hip::HIPGuardMasqueradingAsCUDA device_guard(x.device());
@@ -2639,14 +2641,6 @@ py::dict dropout_norm_bwd_plan(const Tensor &dz0, const OptTensor &dz1, const Op
 // ---- fused cross-entropy loss (flash_attn.ops.triton.cross_entropy -> CrossEntropyLoss.forward / backward,
 // flash_attn/ops/triton/cross_entropy.py:149-289; the collectives of a vocabulary split stay in Python).  Launches on the
 // current stream, no synchronisation; losses, lse and z_losses come from the caching allocator: capturable in a HIP graph.
-int xent_dtype_code(at::ScalarType t) {
-    if (t == at::kHalf) return FA_DTYPE_FP16;
-    if (t == at::kBFloat16) return FA_DTYPE_BF16;
-    if (t == at::kFloat) return FA_DTYPE_FP32;
-    TORCH_CHECK(false, "cross_entropy: logits must be fp16, bf16 or fp32");
-    return -1;
-}
-
 int xent_labels_code(at::ScalarType t) {
     if (t == at::kLong) return FA_XENT_LABELS_INT64;
     if (t == at::kInt) return FA_XENT_LABELS_INT32;
@@ -2659,12 +2653,6 @@ void check_xent_rows(const Tensor &t, const char *name) {
     TORCH_CHECK(t.dim() == 2, "cross_entropy: ", name, " must have shape (M, N)");
     TORCH_CHECK(t.size(1) >= 1 && t.size(1) <= std::numeric_limits<int32_t>::max(), "cross_entropy: ", name, " must have 1 <= N < 2^31 columns");
     TORCH_CHECK(t.stride(-1) == 1, "cross_entropy: ", name, " must have contiguous last dimension");
-}
-
-void check_xent_vector(const Tensor &t, const char *name, int64_t M, bool contiguous) {
-    TORCH_CHECK(t.is_cuda(), "cross_entropy: ", name, " must be on CUDA");
-    TORCH_CHECK(t.dim() == 1 && t.size(0) == M, "cross_entropy: ", name, " must have shape (M)");
-    TORCH_CHECK(!contiguous || t.is_contiguous(), "cross_entropy: ", name, " must be contiguous");
 }
 
 py::dict xent_plan_dict(const fa_xent_plan &l) {
@@ -2681,15 +2669,15 @@ std::tuple<Tensor, Tensor, Tensor> xent_fwd_impl(const Tensor &logits, const Ten
                                                  int64_t total_classes, bool split, fa_xent_plan *plan) {
     check_xent_rows(logits, "logits");
     const int64_t M = logits.size(0), N = logits.size(1);
-    check_xent_vector(labels, "labels", M, true);
+    check_vector("cross_entropy: ", labels, "labels", M, "(M)", true);
     if (precomputed_lse.has_value()) {
-        check_xent_vector(*precomputed_lse, "precomputed_lse", M, true);
+        check_vector("cross_entropy: ", *precomputed_lse, "precomputed_lse", M, "(M)", true);
         TORCH_CHECK(precomputed_lse->scalar_type() == at::kFloat, "cross_entropy: precomputed_lse must be fp32");
     }
     fa_xent_fwd_params p{};
     p.abi_version = FA_ABI_VERSION;
     p.struct_size = sizeof(fa_xent_fwd_params);
-    p.logits_dtype = xent_dtype_code(logits.scalar_type());
+    p.logits_dtype = row_dtype_code("cross_entropy: ", logits.scalar_type(), "logits");
     p.labels_dtype = xent_labels_code(labels.scalar_type());
     c10::hip::HIPGuardMasqueradingAsCUDA device_guard(logits.device());
     const auto fp32 = logits.options().dtype(at::kFloat);
@@ -2735,14 +2723,14 @@ void xent_bwd_impl(const Tensor &dloss, const Tensor &logits, const Tensor &labe
     const int64_t M = logits.size(0), N = logits.size(1);
     TORCH_CHECK(dlogits.size(0) == M && dlogits.size(1) == N, "cross_entropy: dlogits must have the shape of logits");
     TORCH_CHECK(dlogits.scalar_type() == logits.scalar_type(), "cross_entropy: dlogits must have the dtype of logits");
-    check_xent_vector(labels, "labels", M, true);
-    check_xent_vector(lse, "lse", M, true);
-    check_xent_vector(dloss, "dloss", M, false);
+    check_vector("cross_entropy: ", labels, "labels", M, "(M)", true);
+    check_vector("cross_entropy: ", lse, "lse", M, "(M)", true);
+    check_vector("cross_entropy: ", dloss, "dloss", M, "(M)", false);
     TORCH_CHECK(lse.scalar_type() == at::kFloat && dloss.scalar_type() == at::kFloat, "cross_entropy: lse and dloss must be fp32");
     fa_xent_bwd_params p{};
     p.abi_version = FA_ABI_VERSION;
     p.struct_size = sizeof(fa_xent_bwd_params);
-    p.logits_dtype = xent_dtype_code(logits.scalar_type());
+    p.logits_dtype = row_dtype_code("cross_entropy: ", logits.scalar_type(), "logits");
     p.labels_dtype = xent_labels_code(labels.scalar_type());
     if (M == 0) return;
     c10::hip::HIPGuardMasqueradingAsCUDA device_guard(logits.device());
@@ -2775,18 +2763,8 @@ py::dict xent_bwd_plan(const Tensor &dloss, const Tensor &logits, const Tensor &
 // ---- fused MLP activations (flash_attn.ops.activations, the epilogues of flash_attn.ops.fused_dense; include/fa_act.h).
 // Launches on the current stream, no synchronisation; outputs and the dbias workspace come from the caching allocator:
 // capturable in a HIP graph.
-int act_dtype_code(at::ScalarType t, const char *what) {
-    if (t == at::kHalf) return FA_DTYPE_FP16;
-    if (t == at::kBFloat16) return FA_DTYPE_BF16;
-    if (t == at::kFloat) return FA_DTYPE_FP32;
-    TORCH_CHECK(false, "activation: ", what, " must be fp16, bf16 or fp32");
-    return -1;
-}
-
 void check_act_rows(const Tensor &t, const char *name, int64_t M, int64_t H, at::ScalarType dtype) {
-    TORCH_CHECK(t.is_cuda(), "activation: ", name, " must be on CUDA");
-    TORCH_CHECK(t.dim() == 2 && t.size(0) == M && t.size(1) == H, "activation: ", name, " must have shape (M, H)");
-    TORCH_CHECK(t.stride(-1) == 1, "activation: ", name, " must have contiguous last dimension");
+    check_rows("activation: ", "(M, H)", t, name, M, H);
     TORCH_CHECK(t.scalar_type() == dtype, "activation: ", name, " must have the dtype of pre");
 }
 
@@ -2802,7 +2780,7 @@ std::pair<int64_t, int64_t> check_act_inputs(const Tensor &pre, const OptTensor 
     TORCH_CHECK(pre.dim() == 2, "activation: pre must have shape (M, H)");
     const int64_t M = pre.size(0), H = pre.size(1);
     TORCH_CHECK(H >= 1 && H <= std::numeric_limits<int32_t>::max(), "activation: pre must have 1 <= H < 2^31 columns");
-    act_dtype_code(pre.scalar_type(), "pre");
+    row_dtype_code("activation: ", pre.scalar_type(), "pre");
     check_act_rows(pre, "pre", M, H, pre.scalar_type());
     if (up.has_value()) {
         check_act_rows(*up, "up", M, H, pre.scalar_type());
@@ -2826,8 +2804,8 @@ Tensor act_fwd_impl(const Tensor &pre, const OptTensor &up, const OptTensor &bia
     fa_act_fwd_params p{};
     p.abi_version = FA_ABI_VERSION;
     p.struct_size = sizeof(fa_act_fwd_params);
-    p.pre_dtype = p.up_dtype = p.out_dtype = act_dtype_code(pre.scalar_type(), "pre");
-    p.bias_dtype = bias.has_value() ? act_dtype_code(bias->scalar_type(), "bias") : p.pre_dtype;
+    p.pre_dtype = p.up_dtype = p.out_dtype = row_dtype_code("activation: ", pre.scalar_type(), "pre");
+    p.bias_dtype = bias.has_value() ? row_dtype_code("activation: ", bias->scalar_type(), "bias") : p.pre_dtype;
     c10::hip::HIPGuardMasqueradingAsCUDA device_guard(pre.device());
     Tensor out = at::empty({M, H}, pre.options());
     if (M == 0) return out;
@@ -2864,8 +2842,8 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> act_bwd_impl(const Tensor &dout, cons
     fa_act_bwd_params p{};
     p.abi_version = FA_ABI_VERSION;
     p.struct_size = sizeof(fa_act_bwd_params);
-    p.pre_dtype = p.up_dtype = p.dout_dtype = p.dpre_dtype = p.dup_dtype = p.out_dtype = act_dtype_code(pre.scalar_type(), "pre");
-    p.bias_dtype = p.dbias_dtype = bias.has_value() ? act_dtype_code(bias->scalar_type(), "bias") : p.pre_dtype;
+    p.pre_dtype = p.up_dtype = p.dout_dtype = p.dpre_dtype = p.dup_dtype = p.out_dtype = row_dtype_code("activation: ", pre.scalar_type(), "pre");
+    p.bias_dtype = p.dbias_dtype = bias.has_value() ? row_dtype_code("activation: ", bias->scalar_type(), "bias") : p.pre_dtype;
     c10::hip::HIPGuardMasqueradingAsCUDA device_guard(pre.device());
     auto none = [&] { return at::empty({0}, pre.options()); };  // (one tensor each: outputs of an op do not alias)
     Tensor dpre = at::empty({M, packed ? 2 * H : H}, pre.options());
@@ -2907,11 +2885,6 @@ py::dict act_bwd_plan(const Tensor &dout, const Tensor &pre, const OptTensor &up
 
 // ---- GEMM with a fused bias + activation epilogue (flash_attn.ops.triton.linear; include/fa_gemm_act.h).  Launches on the
 // current stream, no synchronisation; outputs and the dbias workspace come from the caching allocator: capturable in a HIP graph.
-int gemm_act_dtype_code(at::ScalarType t) {
-    TORCH_CHECK(t == at::kHalf || t == at::kBFloat16, "gemm_act: tensors must be fp16 or bf16");
-    return t == at::kHalf ? FA_DTYPE_FP16 : FA_DTYPE_BF16;
-}
-
 void check_gemm_act_matrix(const Tensor &t, const char *name, int64_t rows, int64_t cols, const Tensor &like) {
     TORCH_CHECK(t.is_cuda() && t.device() == like.device(), "gemm_act: ", name, " must be on the device of the first operand");
     TORCH_CHECK(t.dim() == 2 && t.size(0) == rows && t.size(1) == cols, "gemm_act: ", name, " has the wrong shape");
@@ -2945,7 +2918,7 @@ std::tuple<Tensor, Tensor> gemm_act_fwd_impl(const Tensor &x, const Tensor &weig
     fa_gemm_act_fwd_params p{};
     p.abi_version = FA_ABI_VERSION;
     p.struct_size = sizeof(fa_gemm_act_fwd_params);
-    p.x_dtype = p.weight_dtype = p.bias_dtype = p.out_dtype = p.act_input_dtype = gemm_act_dtype_code(x.scalar_type());
+    p.x_dtype = p.weight_dtype = p.bias_dtype = p.out_dtype = p.act_input_dtype = row_dtype_code("gemm_act: ", x.scalar_type(), "tensors", false);
     c10::hip::HIPGuardMasqueradingAsCUDA device_guard(x.device());
     Tensor out = at::empty({M, N}, x.options());
     Tensor act_input = save_act_input ? at::empty({M, N}, x.options()) : at::empty({0}, x.options());
@@ -2982,7 +2955,7 @@ std::tuple<Tensor, Tensor> gemm_act_dgrad_impl(const Tensor &grad_out, const Ten
     fa_gemm_act_dgrad_params p{};
     p.abi_version = FA_ABI_VERSION;
     p.struct_size = sizeof(fa_gemm_act_dgrad_params);
-    p.grad_out_dtype = p.weight_dtype = p.act_input_dtype = p.grad_in_dtype = p.dbias_dtype = gemm_act_dtype_code(grad_out.scalar_type());
+    p.grad_out_dtype = p.weight_dtype = p.act_input_dtype = p.grad_in_dtype = p.dbias_dtype = row_dtype_code("gemm_act: ", grad_out.scalar_type(), "tensors", false);
     c10::hip::HIPGuardMasqueradingAsCUDA device_guard(grad_out.device());
     Tensor grad_in = at::empty({M, N}, grad_out.options());
     Tensor dbias = want_dbias ? at::empty({N}, grad_out.options()) : at::empty({0}, grad_out.options());
