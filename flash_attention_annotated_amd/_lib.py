@@ -1,4 +1,4 @@
-"""Build and loading of the native code: libfa_fwd_gfx950.so (the C-ABI of include/fa_fwd.h, fa_bwd.h, fa_rotary.h, fa_norm.h, fa_xent.h, fa_act.h, fa_gemm_act.h and fa_dropout_norm.h) and
+"""Build and loading of the native code: libfa_fwd_gfx950.so (the C-ABI of include/fa_fwd.h, fa_bwd.h, fa_rotary.h, fa_norm.h, fa_xent.h, fa_act.h, fa_gemm_act.h, fa_dropout_norm.h and fa_sample.h) and
 the compiled host module flash_attn_2_cuda_C (csrc/torch_binding.cpp), which is the only host path of both operator
 surfaces.  Python launches nothing through ctypes: the struct mirrors below serve the ABI tests, `bench.py --variant`
 and the developer tools, which call the C-ABI directly.
@@ -108,6 +108,9 @@ DROPOUT_NORM_SYMBOLS = ("fa_dropout_norm_fwd", "fa_dropout_norm_fwd_validate", "
                         "fa_dropout_norm_bwd", "fa_dropout_norm_bwd_validate", "fa_dropout_norm_bwd_params_size",
                         "fa_dropout_norm_bwd_workspace_bytes", "fa_dropout_norm_fwd_plan", "fa_dropout_norm_bwd_plan")
 FA_DROPOUT_NORM_RMS = 1
+# every symbol include/fa_sample.h declares (csrc/fa_sample.hip)
+SAMPLE_SYMBOLS = ("fa_sample", "fa_sample_validate", "fa_sample_params_size", "fa_sample_plan")
+FA_SAMPLE_DRAW, FA_SAMPLE_FILTER = 0, 1
 
 
 class FaFwdParams(ctypes.Structure):
@@ -393,6 +396,25 @@ class FaXentBwdParams(ctypes.Structure):
     )
 
 
+class FaSampleParams(ctypes.Structure):
+    """Field-for-field mirror of `struct fa_sample_params` (include/fa_sample.h)."""
+
+    _fields_ = (
+        [("abi_version", ctypes.c_uint32), ("struct_size", ctypes.c_uint32)]
+        + [(n, ctypes.c_void_p) for n in ("logits", "u", "rng_state", "token", "kept", "mass")]
+        + [("logits_row_stride", ctypes.c_int64), ("B", ctypes.c_int64)]
+        + [(n, ctypes.c_int32) for n in ("V", "logits_dtype", "mode", "top_k")]
+        + [("top_p", ctypes.c_float), ("temperature", ctypes.c_float)]
+    )
+
+
+class FaSampleForm(ctypes.Structure):
+    """Field-for-field mirror of `struct fa_sample_form` (include/fa_sample.h): the form a sampling call takes."""
+
+    _fields_ = [(n, ctypes.c_int32) for n in ("cw", "threads", "mode", "greedy", "topk", "topp", "draw", "k", "key_bits",
+                                              "key_passes", "index_bits", "index_passes", "frac_bits", "grid_x")]
+
+
 class FaActPlan(ctypes.Structure):
     """Field-for-field mirror of `struct fa_act_plan` (include/fa_act.h): the form an activation call takes."""
 
@@ -557,7 +579,7 @@ def build(force=False, verbose=False):
     """Compile csrc/ for gfx950 into the in-tree shared library (hipcc cross-compiles without a GPU)."""
     srcs = [os.path.join(CSRC, f) for f in ("fa_fwd_api.hip", "fa_fwd_kv8_api.hip", "fa_fwd_qv8_api.hip", "fa_fwd_sparse_kv_api.hip", "fa_kvcache_append_kv8.hip",
                                               "fa_kvcache_append_qv8.hip", "fa_bwd_api.hip", "fa_bwd_bs_api.hip", "fa_rotary_emb.hip", "fa_norm.hip", "fa_xent.hip", "fa_act.hip", "fa_gemm_act.hip",
-                                              "fa_dropout_norm.hip")]
+                                              "fa_dropout_norm.hip", "fa_sample.hip")]
     if not force and not is_stale():
         return LIB_PATH
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -778,6 +800,14 @@ def load():
                   FaGemmActDgradParams)
     _declare_unit(lib, "fa_dropout_norm", (("fwd", FaDropoutNormFwdParams), ("bwd", FaDropoutNormBwdParams)), FaDropoutNormPlan,
                   FaDropoutNormBwdParams)
+    lib.fa_sample.argtypes = [ctypes.POINTER(FaSampleParams), ctypes.c_void_p]
+    lib.fa_sample_validate.argtypes = [ctypes.POINTER(FaSampleParams)]
+    lib.fa_sample_plan.argtypes = [ctypes.POINTER(FaSampleParams), ctypes.POINTER(FaSampleForm)]
+    lib.fa_sample.restype = lib.fa_sample_validate.restype = lib.fa_sample_plan.restype = ctypes.c_int
+    lib.fa_sample_params_size.argtypes = []
+    lib.fa_sample_params_size.restype = ctypes.c_uint32
+    if lib.fa_sample_params_size() != ctypes.sizeof(FaSampleParams):
+        raise RuntimeError("fa_sample_params layout mismatch between include/fa_sample.h and _lib.FaSampleParams")
     lib.fa_bwd.argtypes = [ctypes.POINTER(FaBwdParams), ctypes.c_void_p]
     lib.fa_bwd.restype = ctypes.c_int
     lib.fa_bwd_validate.argtypes = [ctypes.POINTER(FaBwdParams)]
@@ -946,6 +976,16 @@ def new_xent_fwd_params():
 
 def new_xent_bwd_params():
     return _new_xent_params(FaXentBwdParams)
+
+
+def new_sample_params():
+    p = FaSampleParams()
+    p.abi_version = FA_ABI_VERSION
+    p.struct_size = ctypes.sizeof(FaSampleParams)
+    p.logits_dtype = FA_DTYPE_BF16
+    p.mode = FA_SAMPLE_DRAW
+    p.temperature = 1.0
+    return p
 
 
 def _new_act_params(struct, dtypes):

@@ -2,8 +2,8 @@
 // fused into the residual add and the LayerNorm / RMSNorm, forward and backward.  A translation unit of its own: no kernel
 // comes from another unit or goes to one, fa_norm.hip included, because the kernel set of every unit is pinned by its tests.
 // That rule is about kernels: the chunk loads and stores, the sums, the ordered reduce of partial rows and the host predicates
-// are the inline functions of fa_rowwise.h, shared with the other row units.  The counter hash stays here: its avalanche is
-// that of DESIGN 4.6, its keying (a key per row, groups of 4 columns) is this unit's own.
+// are the inline functions of fa_rowwise.h, shared with the other row units.  The avalanche of the counter hash and the
+// mix of (seed, offset) are there too; the keying (a key per row, groups of 4 columns) is this unit's own.
 //
 // A workgroup of 64 / 256 / 512 / 1024 threads (the smallest that gives a thread at most C columns) takes one row at a
 // time out of a contiguous block of rows; C = 16 / 8 / 2 (CW = 8 / 4 / 1) in the forward, 8 / 4 / 2 in the backward.  Thread t of `ts` owns the chunks
@@ -46,18 +46,6 @@ struct Plan {
 };
 
 // ---- dropout decisions (restated) ---------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t lowbias32(uint32_t x) {
-    x ^= x >> 16; x *= 0x7FEB352Du;
-    x ^= x >> 15; x *= 0x846CA68Bu;
-    x ^= x >> 16;
-    return x;
-}
-__device__ __forceinline__ uint32_t seed_mix(const uint64_t *rng_state) {
-    const uint64_t seed = rng_state[0], off = rng_state[1];
-    uint32_t x = (uint32_t)seed ^ (uint32_t)(seed >> 32) * 0x27D4EB2Fu ^ (uint32_t)off * 0xC2B2AE3Du ^ (uint32_t)(off >> 32);
-    x ^= x >> 15; x *= 0x2C1B3C6Du; x ^= x >> 12;
-    return x;
-}
 // the key of (row, stream): a bijection of the row's lower half for a given seed, upper half and stream, so two rows of a
 // call differ in their keys
 __device__ __forceinline__ uint32_t row_key(uint32_t mix, int64_t row, uint32_t stream) {

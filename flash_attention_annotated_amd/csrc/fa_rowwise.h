@@ -1,6 +1,7 @@
-// fa_rowwise.h — what the row-streaming units (fa_norm.hip, fa_dropout_norm.hip, fa_xent.hip, fa_act.hip) share: the chunk
-// loads and stores between a tensor's dtype and fp32 registers, the sums over a wavefront and a workgroup, the ordered reduce
-// of fp32 partial rows, and the host's dtype and alignment predicates.  Everything here is an inline function: including it
+// fa_rowwise.h — what the row-streaming units (fa_norm.hip, fa_dropout_norm.hip, fa_xent.hip, fa_act.hip, fa_sample.hip) share: the chunk
+// loads and stores between a tensor's dtype and fp32 registers, the sums over a wavefront and a workgroup, the exclusive scan
+// over a workgroup, the avalanche of the counter hashes, the ordered reduce of fp32 partial rows, and the host's dtype and
+// alignment predicates.  Everything here is an inline function: including it
 // adds no kernel to a unit and renames none, so the kernel set of every unit stays what its tests pin.
 #pragma once
 
@@ -151,6 +152,49 @@ __device__ __forceinline__ void team_sum(float (&v)[NV], bool team_wave, float (
         v[i] = s;
     }
     phase ^= 1;
+}
+
+// the exclusive prefix sum of v over the threads of the workgroup (whole wavefronts) in thread order, and the sum over all of
+// them in `total`; every thread calls it together.  64-bit integers: the sums are exact, whatever the order.  `part` is free
+// again on return
+__device__ __forceinline__ uint64_t shfl_up_64(uint64_t v, int o) {
+    const uint32_t lo = __shfl_up((uint32_t)v, o, WAVE), hi = __shfl_up((uint32_t)(v >> 32), o, WAVE);
+    return (uint64_t)hi << 32 | lo;
+}
+__device__ __forceinline__ uint64_t wg_exclusive_scan(uint64_t v, uint64_t (&part)[MAX_WAVES], uint64_t &total) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    uint64_t inc = v;
+#pragma unroll
+    for (int o = 1; o < WAVE; o <<= 1) {
+        const uint64_t up = shfl_up_64(inc, o);
+        if (lane >= o) inc += up;
+    }
+    if (lane == WAVE - 1) part[wave] = inc;
+    __syncthreads();
+    uint64_t before = 0, all = 0;
+    for (int w = 0; w < nw; ++w) {
+        const uint64_t s = part[w];
+        before += w < wave ? s : 0;
+        all += s;
+    }
+    __syncthreads();
+    total = all;
+    return before + inc - v;
+}
+
+// ---- counters to bits ------------------------------------------------------------------------------------------
+__device__ __forceinline__ uint32_t lowbias32(uint32_t x) {
+    x ^= x >> 16; x *= 0x7FEB352Du;
+    x ^= x >> 15; x *= 0x846CA68Bu;
+    x ^= x >> 16;
+    return x;
+}
+// rng_state = {seed, offset} on the device as one word
+__device__ __forceinline__ uint32_t seed_mix(const uint64_t *rng_state) {
+    const uint64_t seed = rng_state[0], off = rng_state[1];
+    uint32_t x = (uint32_t)seed ^ (uint32_t)(seed >> 32) * 0x27D4EB2Fu ^ (uint32_t)off * 0xC2B2AE3Du ^ (uint32_t)(off >> 32);
+    x ^= x >> 15; x *= 0x2C1B3C6Du; x ^= x >> 12;
+    return x;
 }
 
 constexpr int REDUCE_COLS = 64;  // columns per workgroup of an ordered reduce

@@ -26,6 +26,7 @@
 #include "../../include/fa_rotary.h"  // ("fa_rotary.h" from here is the device header next to this file)
 #include "fa_norm.h"
 #include "fa_xent.h"
+#include "fa_sample.h"
 #include "fa_act.h"
 #include "fa_gemm_act.h"
 #include "fa_dropout_norm.h"
@@ -2760,6 +2761,89 @@ py::dict xent_bwd_plan(const Tensor &dloss, const Tensor &logits, const Tensor &
     return xent_plan_dict(plan);
 }
 
+// ---- fused top-k / top-p token sampling (flash_attn.utils.generation: sample, modify_logits_for_top_k_filtering,
+// modify_logits_for_top_p_filtering, flash_attn/utils/generation.py:45-95; include/fa_sample.h).  Launches on the current
+// stream, no synchronisation; token, kept and mass come from the caching allocator: capturable in a HIP graph.
+py::dict sample_plan_dict(const fa_sample_form &l) {
+    py::dict d;
+    d["cw"] = l.cw; d["threads"] = l.threads; d["mode"] = l.mode; d["greedy"] = l.greedy;
+    d["topk"] = l.topk; d["topp"] = l.topp; d["draw"] = l.draw; d["k"] = l.k;
+    d["key_bits"] = l.key_bits; d["key_passes"] = l.key_passes; d["index_bits"] = l.index_bits; d["index_passes"] = l.index_passes;
+    d["frac_bits"] = l.frac_bits; d["grid_x"] = l.grid_x;
+    return d;
+}
+
+// (token, kept, mass); kept and mass are empty without `stats`, token is empty in the filter mode.  A draw (top_k != 1) takes
+// the uniforms `u`, or `rng_state` = (seed, offset) on the device, or with neither draws that pair on the device from the default
+// generator.  With `plan` nothing is launched and nothing is drawn: *plan is what fa_sample_plan says of the params the launch
+// would get
+std::tuple<Tensor, Tensor, Tensor> sample_impl(const Tensor &logits, int64_t top_k, double top_p, double temperature, const OptTensor &u,
+                                               const OptTensor &rng_state, bool stats, int mode, fa_sample_form *plan) {
+    TORCH_CHECK(logits.is_cuda(), "sample: logits must be on CUDA");
+    TORCH_CHECK(logits.dim() == 2, "sample: logits must have shape (batch_size, vocab_size)");
+    TORCH_CHECK(logits.size(1) >= 1 && logits.size(1) <= std::numeric_limits<int32_t>::max(), "sample: logits must have 1 <= vocab_size < 2^31 columns");
+    TORCH_CHECK(logits.stride(-1) == 1 || logits.size(1) == 1, "sample: logits must have contiguous last dimension");
+    TORCH_CHECK(top_k >= 0 && top_k <= std::numeric_limits<int32_t>::max(), "sample: top_k must be in [0, 2^31)");
+    const int64_t B = logits.size(0), V = logits.size(1);
+    const bool draw = mode == FA_SAMPLE_DRAW, greedy = draw && top_k == 1;
+    TORCH_CHECK(!(u.has_value() && rng_state.has_value()), "sample: u and rng_state exclude each other");
+    if (u.has_value()) {
+        check_vector("sample: ", *u, "u", B, "(batch_size)", true);
+        TORCH_CHECK(u->scalar_type() == at::kFloat, "sample: u must be fp32");
+    }
+    if (rng_state.has_value())
+        TORCH_CHECK(rng_state->is_cuda() && rng_state->scalar_type() == at::kLong && rng_state->numel() == 2 && rng_state->is_contiguous(),
+                    "sample: rng_state must be two int64 on the device");
+    fa_sample_params p{};
+    p.abi_version = FA_ABI_VERSION;
+    p.struct_size = sizeof(fa_sample_params);
+    p.logits_dtype = row_dtype_code("sample: ", logits.scalar_type(), "logits");
+    c10::hip::HIPGuardMasqueradingAsCUDA device_guard(logits.device());
+    stats = stats && !greedy;
+    Tensor token = at::empty({draw ? B : 0}, logits.options().dtype(at::kLong));
+    Tensor kept = at::empty({stats ? B : 0}, logits.options().dtype(at::kInt)), mass = at::empty({stats ? B : 0}, logits.options().dtype(at::kFloat));
+    if (B == 0) return {token, kept, mass};
+    Tensor state;  // (kept alive to the launch)
+    if (draw && !greedy) {
+        if (u.has_value()) p.u = static_cast<const float *>(u->data_ptr());
+        else if (rng_state.has_value()) p.rng_state = static_cast<const uint64_t *>(rng_state->data_ptr());
+        else if (plan) p.rng_state = reinterpret_cast<const uint64_t *>(uintptr_t(16));  // (a plan reads no memory)
+        else {
+            state = dropout_state(1.0, c10::nullopt, logits);
+            p.rng_state = static_cast<const uint64_t *>(state.data_ptr());
+        }
+    }
+    p.logits = logits.data_ptr();
+    p.token = draw ? static_cast<int64_t *>(token.data_ptr()) : nullptr;
+    p.kept = stats ? static_cast<int32_t *>(kept.data_ptr()) : nullptr;
+    p.mass = stats ? static_cast<float *>(mass.data_ptr()) : nullptr;
+    p.logits_row_stride = logits.stride(0);
+    p.B = B; p.V = (int32_t)V;
+    p.mode = mode; p.top_k = (int32_t)top_k; p.top_p = (float)top_p; p.temperature = (float)temperature;
+    const int st = plan ? fa_sample_plan(&p, plan) : fa_sample(&p, current_stream(logits));
+    TORCH_CHECK(st == 0, plan ? "fa_sample_plan" : "fa_sample", " failed (", st, "): ", fa_strerror(st));
+    return {token, kept, mass};
+}
+
+std::tuple<Tensor, Tensor, Tensor> sample(const Tensor &logits, int64_t top_k, double top_p, double temperature, const OptTensor &u,
+                                          const OptTensor &rng_state, bool stats) {
+    return sample_impl(logits, top_k, top_p, temperature, u, rng_state, stats, FA_SAMPLE_DRAW, nullptr);
+}
+
+// -inf over the entries of logits that top-k (all ties of the k-th value stay) and then top-p remove, in place; (kept, mass)
+std::tuple<Tensor, Tensor> sample_filter_(Tensor logits, int64_t top_k, double top_p, bool stats) {
+    auto out = sample_impl(logits, top_k, top_p, 1.0, c10::nullopt, c10::nullopt, stats, FA_SAMPLE_FILTER, nullptr);
+    return {std::get<1>(out), std::get<2>(out)};
+}
+
+// the form sample (filter: sample_filter_) takes with these arguments (fa_sample_form as a dict); at least one row
+py::dict sample_plan(const Tensor &logits, int64_t top_k, double top_p, double temperature, bool filter, bool stats) {
+    TORCH_CHECK(logits.dim() == 2 && logits.size(0) >= 1, "sample: a plan needs at least one row");
+    fa_sample_form plan{};
+    sample_impl(logits, top_k, top_p, temperature, c10::nullopt, c10::nullopt, stats, filter ? FA_SAMPLE_FILTER : FA_SAMPLE_DRAW, &plan);
+    return sample_plan_dict(plan);
+}
+
 // ---- fused MLP activations (flash_attn.ops.activations, the epilogues of flash_attn.ops.fused_dense; include/fa_act.h).
 // Launches on the current stream, no synchronisation; outputs and the dbias workspace come from the caching allocator:
 // capturable in a HIP graph.
@@ -3109,5 +3193,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("dz0"), py::arg("dz1"), py::arg("dx"), py::arg("x"), py::arg("x0"), py::arg("mu"), py::arg("rsigma"),
           py::arg("weight0"), py::arg("weight1"), py::arg("rowscale"), py::arg("colscale"), py::arg("rng_state"), py::arg("p_dropout"),
           py::arg("has_x1"), py::arg("has_residual"), py::arg("has_bias"), py::arg("is_rms_norm"), py::arg("x0_dtype"));
+    m.def("sample", &sample, "fused top-k / top-p sampling of a token per row: (token, kept, mass)", py::arg("logits"), py::arg("top_k"),
+          py::arg("top_p"), py::arg("temperature"), py::arg("u"), py::arg("rng_state"), py::arg("stats"));
+    m.def("sample_filter_", &sample_filter_, "-inf over the entries top-k and top-p remove, in place: (kept, mass)", py::arg("logits"),
+          py::arg("top_k"), py::arg("top_p"), py::arg("stats"));
+    m.def("sample_plan", &sample_plan, "the form sample / sample_filter_ takes with these arguments: fa_sample_form as a dict, nothing launched",
+          py::arg("logits"), py::arg("top_k"), py::arg("top_p"), py::arg("temperature"), py::arg("filter"), py::arg("stats"));
     m.def("sink_grad", &sink_grad, "gradient of a learnable sink from softmax_lse and softmax_d");
 }
