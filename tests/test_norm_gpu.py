@@ -140,9 +140,10 @@ FP32_ROUNDINGS = 8  # see assert_one_ulp
 
 
 def ulp16(t):
-    """the spacing of t's 16-bit dtype at |t|, in fp64"""
-    mant = 7 if t.dtype == BF16 else 10
-    return torch.exp2(torch.frexp(t.double()).exponent.double() - 1 - mant)
+    """the spacing of t's 16-bit dtype at |t|, in fp64: 2^(e - mant) among the normal values, the one spacing of the subnormal
+    ones below them (2^-24 in fp16, where a result under 2^-14 is met in practice)"""
+    mant, least = (7, 2.0 ** -133) if t.dtype == BF16 else (10, 2.0 ** -24)
+    return torch.exp2(torch.frexp(t.double()).exponent.double() - 1 - mant).clamp_min(least)
 
 
 def assert_one_ulp(y, want, bias=None, what="y"):
