@@ -621,24 +621,87 @@ def build_binding(verbose=False):
     return binding_path()
 
 
-def _declare_unit(lib, prefix, structs, plan_struct, workspace_struct):
-    """The prototypes of one row unit (include/`prefix`.h): per (direction, params struct) the launch, _validate, _params_size
-    (checked against the mirror) and _plan; `workspace_struct`: the struct of the direction that has a _workspace_bytes."""
-    for name, struct in structs:
-        launch, validate, size, plan = (getattr(lib, f"{prefix}_{name}{s}") for s in ("", "_validate", "_params_size", "_plan"))
-        launch.argtypes = [ctypes.POINTER(struct), ctypes.c_void_p]
-        validate.argtypes = [ctypes.POINTER(struct)]
-        plan.argtypes = [ctypes.POINTER(struct), ctypes.POINTER(plan_struct)]
-        launch.restype = validate.restype = plan.restype = ctypes.c_int
-        size.argtypes = []
-        size.restype = ctypes.c_uint32
-        if size() != ctypes.sizeof(struct):
-            raise RuntimeError(f"{prefix}_{name}_params layout mismatch between include/{prefix}.h and _lib.{struct.__name__}")
-        if struct is workspace_struct:
-            workspace = getattr(lib, f"{prefix}_{name}_workspace_bytes")
-            workspace.argtypes = [ctypes.POINTER(struct)]
-            workspace.restype = ctypes.c_uint64
+_P, _VOID, _INT, _STR = ctypes.POINTER, ctypes.c_void_p, ctypes.c_int, ctypes.c_char_p
+_I32, _I64, _U64 = ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64
 
+
+def _unit(prefix, structs, plan_struct, workspace_struct=None):
+    """The prototype rows of one row unit (include/`prefix`.h): per (direction, params struct) the launch with its _params_size,
+    _validate and _plan; `workspace_struct`: the struct of the direction that has a _workspace_bytes."""
+    for name, struct in structs:
+        yield f"{prefix}_{name}", [_P(struct), _VOID], _INT, f"{prefix}_{name}_params_size", struct
+        yield f"{prefix}_{name}_validate", [_P(struct)], _INT
+        yield f"{prefix}_{name}_plan", [_P(struct), _P(plan_struct)], _INT
+        if struct is workspace_struct:
+            yield f"{prefix}_{name}_workspace_bytes", [_P(struct)], _U64
+
+
+_FWD, _BWD, _KV8 = _P(FaFwdParams), _P(FaBwdParams), _P(FaKvcacheAppendKv8Params)
+_SINK, _BS, _BS_BWD, _SPARSE_KV = _P(FaSinkParams), _P(FaBlockSparseParams), _P(FaBlockSparseBwdParams), _P(FaSparseKvParams)
+# every C entry point, by header: (symbol, argtypes, restype); a row whose params struct has a `*_params_size` also names that
+# symbol and the mirror it is checked against (the `*_params_size` symbols themselves are all `uint32_t (void)`)
+_PROTOTYPES = {
+    "fa_fwd.h": (
+        ("fa_fwd", [_FWD, _VOID], _INT, "fa_fwd_params_size", FaFwdParams),
+        ("fa_fwd_validate", [_FWD], _INT),
+        ("fa_fwd_workspace_size", [_FWD], _I64),
+        ("fa_fwd_plan_name", [_FWD, _I32], _STR),
+        ("fa_fwd_last_plan_name", [], _STR),
+        ("fa_strerror", [_INT], _STR),
+        ("fa_abi_version", [], ctypes.c_uint32),
+        ("fa_fwd_tile_shape", [_I32, _I32, _I32, _P(_I32), _P(_I32)], _INT),
+        ("fa_set_default_variant", [_I32], None),
+        ("fa_set_persist_mode", [_I32], None),
+        ("fa_kvcache_append", [_P(FaKvcacheAppendParams), _VOID], _INT, "fa_kvcache_append_params_size", FaKvcacheAppendParams),
+        ("fa_rotary_apply", [_P(FaRotaryParams), _VOID], _INT, "fa_rotary_params_size", FaRotaryParams),
+        ("fa_kvcache_append_varlen", [_P(FaKvcacheAppendVarlenParams), _VOID], _INT, "fa_kvcache_append_varlen_params_size",
+         FaKvcacheAppendVarlenParams),
+        ("fa_rotary_apply_varlen", [_P(FaRotaryVarlenParams), _VOID], _INT, "fa_rotary_varlen_params_size", FaRotaryVarlenParams),
+        ("fa_fwd_combine", [_P(FaCombineParams), _VOID], _INT, "fa_combine_params_size", FaCombineParams),
+        ("fa_fwd_sink", [_FWD, _SINK, _VOID], _INT, "fa_sink_params_size", FaSinkParams),
+        ("fa_fwd_sink_validate", [_FWD, _SINK], _INT),
+        ("fa_fwd_block_sparse", [_FWD, _BS, _SINK, _VOID], _INT, "fa_block_sparse_params_size", FaBlockSparseParams),
+        ("fa_fwd_block_sparse_validate", [_FWD, _BS, _SINK], _INT),
+        ("fa_fwd_kv8", [_FWD, _VOID], _INT),
+        ("fa_fwd_kv8_validate", [_FWD], _INT),
+        ("fa_fwd_kv8_workspace_size", [_FWD], _I64),
+        ("fa_fwd_kv8_plan_name", [_FWD, _I32], _STR),
+        ("fa_fwd_qv8", [_FWD, _VOID], _INT),
+        ("fa_fwd_qv8_validate", [_FWD], _INT),
+        ("fa_fwd_qv8_workspace_size", [_FWD], _I64),
+        ("fa_fwd_qv8_plan_name", [_FWD, _I32], _STR),
+        ("fa_kvcache_append_kv8", [_KV8, _VOID], _INT, "fa_kvcache_append_kv8_params_size", FaKvcacheAppendKv8Params),
+        ("fa_kvcache_append_kv8_validate", [_KV8], _INT),
+        ("fa_kvcache_append_qv8", [_KV8, _VOID], _INT),
+        ("fa_kvcache_append_qv8_validate", [_KV8], _INT),
+        ("fa_fwd_sparse_kv", [_FWD, _SPARSE_KV, _VOID], _INT, "fa_sparse_kv_params_size", FaSparseKvParams),
+        ("fa_fwd_sparse_kv_validate", [_FWD, _SPARSE_KV], _INT),
+        ("fa_fwd_sparse_kv_workspace_size", [_FWD, _SPARSE_KV], _I64),
+        ("fa_fwd_sparse_kv_plan_name", [_FWD, _SPARSE_KV, _I32], _STR),
+    ),
+    "fa_bwd.h": (
+        ("fa_bwd", [_BWD, _VOID], _INT, "fa_bwd_params_size", FaBwdParams),
+        ("fa_bwd_validate", [_BWD], _INT),
+        ("fa_bwd_plan_name", [_BWD], _STR),
+        ("fa_bwd_last_plan_name", [], _STR),
+        ("fa_sink_grad", [_P(FaSinkGradParams), _VOID], _INT, "fa_sink_grad_params_size", FaSinkGradParams),
+        ("fa_sink_grad_validate", [_P(FaSinkGradParams)], _INT),
+        ("fa_bwd_block_sparse", [_BWD, _BS, _BS_BWD, _VOID], _INT, "fa_block_sparse_bwd_params_size", FaBlockSparseBwdParams),
+        ("fa_bwd_block_sparse_validate", [_BWD, _BS, _BS_BWD], _INT),
+    ),
+    "fa_rotary.h": (
+        ("fa_rotary_emb", [_P(FaRotaryEmbParams), _VOID], _INT, "fa_rotary_emb_params_size", FaRotaryEmbParams),
+        ("fa_rotary_emb_validate", [_P(FaRotaryEmbParams)], _INT),
+    ),
+    "fa_norm.h": tuple(_unit("fa_norm", (("fwd", FaNormFwdParams), ("bwd", FaNormBwdParams)), FaNormPlan, FaNormBwdParams)),
+    "fa_xent.h": tuple(_unit("fa_xent", (("fwd", FaXentFwdParams), ("bwd", FaXentBwdParams)), FaXentPlan)),
+    "fa_act.h": tuple(_unit("fa_act", (("fwd", FaActFwdParams), ("bwd", FaActBwdParams)), FaActPlan, FaActBwdParams)),
+    "fa_gemm_act.h": tuple(_unit("fa_gemm_act", (("fwd", FaGemmActFwdParams), ("dgrad", FaGemmActDgradParams)), FaGemmActPlan,
+                                 FaGemmActDgradParams)),
+    "fa_dropout_norm.h": tuple(_unit("fa_dropout_norm", (("fwd", FaDropoutNormFwdParams), ("bwd", FaDropoutNormBwdParams)),
+                                     FaDropoutNormPlan, FaDropoutNormBwdParams)),
+    "fa_sample.h": tuple(_unit("fa", (("sample", FaSampleParams),), FaSampleForm)),
+}
 
 _lib = None
 
@@ -655,173 +718,16 @@ def load():
     # FA_FWD_LIB: developer override (ablation / instrumented builds).  RTLD_GLOBAL: the binding, imported after this by
     # binding(), resolves its fa_* references to this instance
     lib = ctypes.CDLL(os.environ.get("FA_FWD_LIB", LIB_PATH), mode=ctypes.RTLD_GLOBAL)
-    lib.fa_fwd.argtypes = [ctypes.POINTER(FaFwdParams), ctypes.c_void_p]
-    lib.fa_fwd.restype = ctypes.c_int
-    lib.fa_fwd_validate.argtypes = [ctypes.POINTER(FaFwdParams)]
-    lib.fa_fwd_validate.restype = ctypes.c_int
-    lib.fa_fwd_workspace_size.argtypes = [ctypes.POINTER(FaFwdParams)]
-    lib.fa_fwd_workspace_size.restype = ctypes.c_int64
-    lib.fa_fwd_plan_name.argtypes = [ctypes.POINTER(FaFwdParams), ctypes.c_int32]
-    lib.fa_fwd_plan_name.restype = ctypes.c_char_p
-    lib.fa_fwd_last_plan_name.argtypes = []
-    lib.fa_fwd_last_plan_name.restype = ctypes.c_char_p
-    lib.fa_strerror.argtypes = [ctypes.c_int]
-    lib.fa_strerror.restype = ctypes.c_char_p
-    lib.fa_fwd_params_size.argtypes = []
-    lib.fa_fwd_params_size.restype = ctypes.c_uint32
-    lib.fa_abi_version.argtypes = []
-    lib.fa_abi_version.restype = ctypes.c_uint32
-    lib.fa_fwd_tile_shape.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
-                                      ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]
-    lib.fa_fwd_tile_shape.restype = ctypes.c_int
-    lib.fa_set_default_variant.argtypes = [ctypes.c_int32]
-    lib.fa_set_default_variant.restype = None
-    lib.fa_set_persist_mode.argtypes = [ctypes.c_int32]
-    lib.fa_set_persist_mode.restype = None
-    lib.fa_kvcache_append.argtypes = [ctypes.POINTER(FaKvcacheAppendParams), ctypes.c_void_p]
-    lib.fa_kvcache_append.restype = ctypes.c_int
-    lib.fa_kvcache_append_params_size.argtypes = []
-    lib.fa_kvcache_append_params_size.restype = ctypes.c_uint32
-    if lib.fa_kvcache_append_params_size() != ctypes.sizeof(FaKvcacheAppendParams):
-        raise RuntimeError("fa_kvcache_append_params layout mismatch between include/fa_fwd.h and _lib")
-    lib.fa_rotary_apply.argtypes = [ctypes.POINTER(FaRotaryParams), ctypes.c_void_p]
-    lib.fa_rotary_apply.restype = ctypes.c_int
-    lib.fa_rotary_params_size.argtypes = []
-    lib.fa_rotary_params_size.restype = ctypes.c_uint32
-    if lib.fa_rotary_params_size() != ctypes.sizeof(FaRotaryParams):
-        raise RuntimeError("fa_rotary_params layout mismatch between include/fa_fwd.h and _lib")
-    lib.fa_kvcache_append_varlen.argtypes = [ctypes.POINTER(FaKvcacheAppendVarlenParams), ctypes.c_void_p]
-    lib.fa_kvcache_append_varlen.restype = ctypes.c_int
-    lib.fa_kvcache_append_varlen_params_size.argtypes = []
-    lib.fa_kvcache_append_varlen_params_size.restype = ctypes.c_uint32
-    if lib.fa_kvcache_append_varlen_params_size() != ctypes.sizeof(FaKvcacheAppendVarlenParams):
-        raise RuntimeError("fa_kvcache_append_varlen_params layout mismatch between include/fa_fwd.h and _lib")
-    lib.fa_rotary_apply_varlen.argtypes = [ctypes.POINTER(FaRotaryVarlenParams), ctypes.c_void_p]
-    lib.fa_rotary_apply_varlen.restype = ctypes.c_int
-    lib.fa_rotary_varlen_params_size.argtypes = []
-    lib.fa_rotary_varlen_params_size.restype = ctypes.c_uint32
-    if lib.fa_rotary_varlen_params_size() != ctypes.sizeof(FaRotaryVarlenParams):
-        raise RuntimeError("fa_rotary_varlen_params layout mismatch between include/fa_fwd.h and _lib")
-    lib.fa_fwd_combine.argtypes = [ctypes.POINTER(FaCombineParams), ctypes.c_void_p]
-    lib.fa_fwd_combine.restype = ctypes.c_int
-    lib.fa_combine_params_size.argtypes = []
-    lib.fa_combine_params_size.restype = ctypes.c_uint32
-    if lib.fa_combine_params_size() != ctypes.sizeof(FaCombineParams):
-        raise RuntimeError("fa_combine_params layout mismatch between include/fa_fwd.h and _lib")
-    lib.fa_fwd_sink.argtypes = [ctypes.POINTER(FaFwdParams), ctypes.POINTER(FaSinkParams), ctypes.c_void_p]
-    lib.fa_fwd_sink.restype = ctypes.c_int
-    lib.fa_fwd_sink_validate.argtypes = [ctypes.POINTER(FaFwdParams), ctypes.POINTER(FaSinkParams)]
-    lib.fa_fwd_sink_validate.restype = ctypes.c_int
-    lib.fa_sink_params_size.argtypes = []
-    lib.fa_sink_params_size.restype = ctypes.c_uint32
-    if lib.fa_sink_params_size() != ctypes.sizeof(FaSinkParams):
-        raise RuntimeError("fa_sink_params layout mismatch between include/fa_fwd.h and _lib")
-    lib.fa_fwd_block_sparse.argtypes = [ctypes.POINTER(FaFwdParams), ctypes.POINTER(FaBlockSparseParams),
-                                        ctypes.POINTER(FaSinkParams), ctypes.c_void_p]
-    lib.fa_fwd_block_sparse.restype = ctypes.c_int
-    lib.fa_fwd_block_sparse_validate.argtypes = [ctypes.POINTER(FaFwdParams), ctypes.POINTER(FaBlockSparseParams),
-                                                 ctypes.POINTER(FaSinkParams)]
-    lib.fa_fwd_block_sparse_validate.restype = ctypes.c_int
-    lib.fa_block_sparse_params_size.argtypes = []
-    lib.fa_block_sparse_params_size.restype = ctypes.c_uint32
-    if lib.fa_block_sparse_params_size() != ctypes.sizeof(FaBlockSparseParams):
-        raise RuntimeError("fa_block_sparse_params layout mismatch between include/fa_fwd.h and _lib")
-    lib.fa_fwd_kv8.argtypes = [ctypes.POINTER(FaFwdParams), ctypes.c_void_p]
-    lib.fa_fwd_kv8.restype = ctypes.c_int
-    lib.fa_fwd_kv8_validate.argtypes = [ctypes.POINTER(FaFwdParams)]
-    lib.fa_fwd_kv8_validate.restype = ctypes.c_int
-    lib.fa_fwd_kv8_workspace_size.argtypes = [ctypes.POINTER(FaFwdParams)]
-    lib.fa_fwd_kv8_workspace_size.restype = ctypes.c_int64
-    lib.fa_fwd_kv8_plan_name.argtypes = [ctypes.POINTER(FaFwdParams), ctypes.c_int32]
-    lib.fa_fwd_kv8_plan_name.restype = ctypes.c_char_p
-    lib.fa_fwd_qv8.argtypes = [ctypes.POINTER(FaFwdParams), ctypes.c_void_p]
-    lib.fa_fwd_qv8.restype = ctypes.c_int
-    lib.fa_fwd_qv8_validate.argtypes = [ctypes.POINTER(FaFwdParams)]
-    lib.fa_fwd_qv8_validate.restype = ctypes.c_int
-    lib.fa_fwd_qv8_workspace_size.argtypes = [ctypes.POINTER(FaFwdParams)]
-    lib.fa_fwd_qv8_workspace_size.restype = ctypes.c_int64
-    lib.fa_fwd_qv8_plan_name.argtypes = [ctypes.POINTER(FaFwdParams), ctypes.c_int32]
-    lib.fa_fwd_qv8_plan_name.restype = ctypes.c_char_p
-    lib.fa_kvcache_append_kv8.argtypes = [ctypes.POINTER(FaKvcacheAppendKv8Params), ctypes.c_void_p]
-    lib.fa_kvcache_append_kv8.restype = ctypes.c_int
-    lib.fa_kvcache_append_kv8_validate.argtypes = [ctypes.POINTER(FaKvcacheAppendKv8Params)]
-    lib.fa_kvcache_append_kv8_validate.restype = ctypes.c_int
-    lib.fa_kvcache_append_kv8_params_size.argtypes = []
-    lib.fa_kvcache_append_kv8_params_size.restype = ctypes.c_uint32
-    if lib.fa_kvcache_append_kv8_params_size() != ctypes.sizeof(FaKvcacheAppendKv8Params):
-        raise RuntimeError("fa_kvcache_append_kv8_params layout mismatch between include/fa_fwd.h and _lib")
-    lib.fa_kvcache_append_qv8.argtypes = [ctypes.POINTER(FaKvcacheAppendKv8Params), ctypes.c_void_p]
-    lib.fa_kvcache_append_qv8.restype = ctypes.c_int
-    lib.fa_kvcache_append_qv8_validate.argtypes = [ctypes.POINTER(FaKvcacheAppendKv8Params)]
-    lib.fa_kvcache_append_qv8_validate.restype = ctypes.c_int
-    sparse_kv = [ctypes.POINTER(FaFwdParams), ctypes.POINTER(FaSparseKvParams)]
-    lib.fa_fwd_sparse_kv.argtypes = sparse_kv + [ctypes.c_void_p]
-    lib.fa_fwd_sparse_kv.restype = ctypes.c_int
-    lib.fa_fwd_sparse_kv_validate.argtypes = sparse_kv
-    lib.fa_fwd_sparse_kv_validate.restype = ctypes.c_int
-    lib.fa_fwd_sparse_kv_workspace_size.argtypes = sparse_kv
-    lib.fa_fwd_sparse_kv_workspace_size.restype = ctypes.c_int64
-    lib.fa_fwd_sparse_kv_plan_name.argtypes = sparse_kv + [ctypes.c_int32]
-    lib.fa_fwd_sparse_kv_plan_name.restype = ctypes.c_char_p
-    lib.fa_sparse_kv_params_size.argtypes = []
-    lib.fa_sparse_kv_params_size.restype = ctypes.c_uint32
-    if lib.fa_sparse_kv_params_size() != ctypes.sizeof(FaSparseKvParams):
-        raise RuntimeError("fa_sparse_kv_params layout mismatch between include/fa_fwd.h and _lib")
-    lib.fa_sink_grad.argtypes = [ctypes.POINTER(FaSinkGradParams), ctypes.c_void_p]
-    lib.fa_sink_grad.restype = ctypes.c_int
-    lib.fa_sink_grad_validate.argtypes = [ctypes.POINTER(FaSinkGradParams)]
-    lib.fa_sink_grad_validate.restype = ctypes.c_int
-    lib.fa_sink_grad_params_size.argtypes = []
-    lib.fa_sink_grad_params_size.restype = ctypes.c_uint32
-    if lib.fa_sink_grad_params_size() != ctypes.sizeof(FaSinkGradParams):
-        raise RuntimeError("fa_sink_grad_params layout mismatch between include/fa_bwd.h and _lib.FaSinkGradParams")
-    lib.fa_bwd_block_sparse.argtypes = [ctypes.POINTER(FaBwdParams), ctypes.POINTER(FaBlockSparseParams),
-                                        ctypes.POINTER(FaBlockSparseBwdParams), ctypes.c_void_p]
-    lib.fa_bwd_block_sparse.restype = ctypes.c_int
-    lib.fa_bwd_block_sparse_validate.argtypes = [ctypes.POINTER(FaBwdParams), ctypes.POINTER(FaBlockSparseParams),
-                                                 ctypes.POINTER(FaBlockSparseBwdParams)]
-    lib.fa_bwd_block_sparse_validate.restype = ctypes.c_int
-    lib.fa_block_sparse_bwd_params_size.argtypes = []
-    lib.fa_block_sparse_bwd_params_size.restype = ctypes.c_uint32
-    if lib.fa_block_sparse_bwd_params_size() != ctypes.sizeof(FaBlockSparseBwdParams):
-        raise RuntimeError("fa_block_sparse_bwd_params layout mismatch between include/fa_bwd.h and _lib.FaBlockSparseBwdParams")
-    lib.fa_rotary_emb.argtypes = [ctypes.POINTER(FaRotaryEmbParams), ctypes.c_void_p]
-    lib.fa_rotary_emb.restype = ctypes.c_int
-    lib.fa_rotary_emb_validate.argtypes = [ctypes.POINTER(FaRotaryEmbParams)]
-    lib.fa_rotary_emb_validate.restype = ctypes.c_int
-    lib.fa_rotary_emb_params_size.argtypes = []
-    lib.fa_rotary_emb_params_size.restype = ctypes.c_uint32
-    if lib.fa_rotary_emb_params_size() != ctypes.sizeof(FaRotaryEmbParams):
-        raise RuntimeError("fa_rotary_emb_params layout mismatch between include/fa_rotary.h and _lib.FaRotaryEmbParams")
-    _declare_unit(lib, "fa_norm", (("fwd", FaNormFwdParams), ("bwd", FaNormBwdParams)), FaNormPlan, FaNormBwdParams)
-    _declare_unit(lib, "fa_xent", (("fwd", FaXentFwdParams), ("bwd", FaXentBwdParams)), FaXentPlan, None)
-    _declare_unit(lib, "fa_act", (("fwd", FaActFwdParams), ("bwd", FaActBwdParams)), FaActPlan, FaActBwdParams)
-    _declare_unit(lib, "fa_gemm_act", (("fwd", FaGemmActFwdParams), ("dgrad", FaGemmActDgradParams)), FaGemmActPlan,
-                  FaGemmActDgradParams)
-    _declare_unit(lib, "fa_dropout_norm", (("fwd", FaDropoutNormFwdParams), ("bwd", FaDropoutNormBwdParams)), FaDropoutNormPlan,
-                  FaDropoutNormBwdParams)
-    lib.fa_sample.argtypes = [ctypes.POINTER(FaSampleParams), ctypes.c_void_p]
-    lib.fa_sample_validate.argtypes = [ctypes.POINTER(FaSampleParams)]
-    lib.fa_sample_plan.argtypes = [ctypes.POINTER(FaSampleParams), ctypes.POINTER(FaSampleForm)]
-    lib.fa_sample.restype = lib.fa_sample_validate.restype = lib.fa_sample_plan.restype = ctypes.c_int
-    lib.fa_sample_params_size.argtypes = []
-    lib.fa_sample_params_size.restype = ctypes.c_uint32
-    if lib.fa_sample_params_size() != ctypes.sizeof(FaSampleParams):
-        raise RuntimeError("fa_sample_params layout mismatch between include/fa_sample.h and _lib.FaSampleParams")
-    lib.fa_bwd.argtypes = [ctypes.POINTER(FaBwdParams), ctypes.c_void_p]
-    lib.fa_bwd.restype = ctypes.c_int
-    lib.fa_bwd_validate.argtypes = [ctypes.POINTER(FaBwdParams)]
-    lib.fa_bwd_validate.restype = ctypes.c_int
-    lib.fa_bwd_params_size.argtypes = []
-    lib.fa_bwd_params_size.restype = ctypes.c_uint32
-    lib.fa_bwd_plan_name.argtypes = [ctypes.POINTER(FaBwdParams)]
-    lib.fa_bwd_plan_name.restype = ctypes.c_char_p
-    lib.fa_bwd_last_plan_name.argtypes = []
-    lib.fa_bwd_last_plan_name.restype = ctypes.c_char_p
-    if lib.fa_bwd_params_size() != ctypes.sizeof(FaBwdParams):
-        raise RuntimeError("fa_bwd_params layout mismatch between include/fa_bwd.h and _lib.FaBwdParams")
-    if lib.fa_fwd_params_size() != ctypes.sizeof(FaFwdParams):
-        raise RuntimeError("fa_fwd_params layout mismatch between include/fa_fwd.h and _lib.FaFwdParams")
+    for header, rows in _PROTOTYPES.items():
+        for symbol, argtypes, restype, *sized in rows:
+            fn = getattr(lib, symbol)
+            fn.argtypes, fn.restype = argtypes, restype
+            if sized:
+                size, struct = getattr(lib, sized[0]), sized[1]
+                size.argtypes, size.restype = [], ctypes.c_uint32
+                if size() != ctypes.sizeof(struct):
+                    raise RuntimeError(f"{sized[0][:-len('_size')]} layout mismatch between include/{header} and "
+                                       f"_lib.{struct.__name__}")
     if lib.fa_abi_version() != FA_ABI_VERSION:
         raise RuntimeError("fa_fwd ABI version mismatch")
     if os.environ.get("FA_FWD_VARIANT"):  # developer override of the kernel shape (never changes results)
@@ -856,165 +762,87 @@ def strerror(status):
     return load().fa_strerror(status).decode()
 
 
-def new_bwd_params():
-    p = FaBwdParams()
-    p.abi_version = FA_ABI_VERSION
-    p.struct_size = ctypes.sizeof(FaBwdParams)
-    return p
-
-
-def new_sink_params():
-    p = FaSinkParams()
-    p.abi_version = FA_ABI_VERSION
-    p.struct_size = ctypes.sizeof(FaSinkParams)
-    p.sink_dtype = FA_DTYPE_BF16
-    p.sink_head_stride = 1
-    return p
-
-
-def new_block_sparse_params():
-    p = FaBlockSparseParams()
-    p.abi_version = FA_ABI_VERSION
-    p.struct_size = ctypes.sizeof(FaBlockSparseParams)
-    p.block_m = p.block_n = 128
-    return p
-
-
-def new_block_sparse_bwd_params():
-    p = FaBlockSparseBwdParams()
-    p.abi_version = FA_ABI_VERSION
-    p.struct_size = ctypes.sizeof(FaBlockSparseBwdParams)
-    p.block_m = p.block_n = 128
-    return p
-
-
-def new_sparse_kv_params():
-    p = FaSparseKvParams()
-    p.abi_version = FA_ABI_VERSION
-    p.struct_size = ctypes.sizeof(FaSparseKvParams)
-    p.block_size = 128
-    return p
-
-
-def new_sink_grad_params():
-    p = FaSinkGradParams()
-    p.abi_version = FA_ABI_VERSION
-    p.struct_size = ctypes.sizeof(FaSinkGradParams)
-    p.sink_dtype = FA_DTYPE_BF16
-    return p
-
-
-def new_kvcache_append_kv8_params():
-    p = FaKvcacheAppendKv8Params()
-    p.abi_version = FA_ABI_VERSION
-    p.struct_size = ctypes.sizeof(FaKvcacheAppendKv8Params)
-    p.dtype = FA_DTYPE_BF16
-    return p
-
-
-def new_rotary_emb_params():
-    p = FaRotaryEmbParams()
-    p.abi_version = FA_ABI_VERSION
-    p.struct_size = ctypes.sizeof(FaRotaryEmbParams)
-    p.dtype = p.cos_dtype = p.sin_dtype = FA_DTYPE_BF16
-    p.x_dim_stride = p.out_dim_stride = 1
-    return p
-
-
-def new_norm_fwd_params():
-    p = FaNormFwdParams()
-    p.abi_version = FA_ABI_VERSION
-    p.struct_size = ctypes.sizeof(FaNormFwdParams)
-    for t in ("x", "residual", "residual_out", "weight", "bias", "y", "rowscale"):
-        setattr(p, f"{t}_dtype", FA_DTYPE_BF16)
-    p.eps = 1e-6
-    return p
-
-
-def new_norm_bwd_params():
-    p = FaNormBwdParams()
-    p.abi_version = FA_ABI_VERSION
-    p.struct_size = ctypes.sizeof(FaNormBwdParams)
-    for t in ("x", "dy", "weight", "bias", "dresidual", "dresidual_in", "dx", "y", "rowscale"):
-        setattr(p, f"{t}_dtype", FA_DTYPE_BF16)
-    return p
-
-
-def new_dropout_norm_fwd_params():
-    p = FaDropoutNormFwdParams()
-    p.abi_version = FA_ABI_VERSION
-    p.struct_size = ctypes.sizeof(FaDropoutNormFwdParams)
-    for t in ("x0", "residual", "x", "weight", "z", "rowscale", "colscale"):
-        setattr(p, f"{t}_dtype", FA_DTYPE_BF16)
-    p.eps = 1e-6
-    return p
-
-
-def new_dropout_norm_bwd_params():
-    p = FaDropoutNormBwdParams()
-    p.abi_version = FA_ABI_VERSION
-    p.struct_size = ctypes.sizeof(FaDropoutNormBwdParams)
-    for t in ("dz", "x", "x0", "weight", "rowscale", "colscale"):
-        setattr(p, f"{t}_dtype", FA_DTYPE_BF16)
-    return p
-
-
-def _new_xent_params(struct):
-    p = struct()
-    p.abi_version = FA_ABI_VERSION
-    p.struct_size = ctypes.sizeof(struct)
-    p.logits_dtype = FA_DTYPE_BF16
-    p.labels_dtype = FA_XENT_LABELS_INT64
-    p.ignore_index = -100
-    p.logit_scale = 1.0
-    return p
-
-
-def new_xent_fwd_params():
-    return _new_xent_params(FaXentFwdParams)
-
-
-def new_xent_bwd_params():
-    return _new_xent_params(FaXentBwdParams)
-
-
-def new_sample_params():
-    p = FaSampleParams()
-    p.abi_version = FA_ABI_VERSION
-    p.struct_size = ctypes.sizeof(FaSampleParams)
-    p.logits_dtype = FA_DTYPE_BF16
-    p.mode = FA_SAMPLE_DRAW
-    p.temperature = 1.0
-    return p
-
-
-def _new_act_params(struct, dtypes):
-    p = struct()
-    p.abi_version = FA_ABI_VERSION
-    p.struct_size = ctypes.sizeof(struct)
-    for t in dtypes:
-        setattr(p, f"{t}_dtype", FA_DTYPE_BF16)
-    return p
-
-
-def new_act_fwd_params():
-    return _new_act_params(FaActFwdParams, ("pre", "up", "bias", "out"))
-
-
-def new_act_bwd_params():
-    return _new_act_params(FaActBwdParams, ("pre", "up", "bias", "dout", "dpre", "dup", "dbias", "out"))
-
-
-def new_gemm_act_fwd_params():
-    return _new_act_params(FaGemmActFwdParams, ("x", "weight", "bias", "out", "act_input"))
-
-
-def new_gemm_act_dgrad_params():
-    return _new_act_params(FaGemmActDgradParams, ("grad_out", "weight", "act_input", "grad_in", "dbias"))
+def _new(struct, dtypes=(), **defaults):
+    """A params struct with its ABI header, the listed `*_dtype` fields bf16 and the given defaults."""
+    return struct(abi_version=FA_ABI_VERSION, struct_size=ctypes.sizeof(struct), **{f"{t}_dtype": FA_DTYPE_BF16 for t in dtypes},
+                  **defaults)
 
 
 def new_params():
-    p = FaFwdParams()
-    p.abi_version = FA_ABI_VERSION
-    p.struct_size = ctypes.sizeof(FaFwdParams)
-    return p
+    return _new(FaFwdParams)
+
+
+def new_bwd_params():
+    return _new(FaBwdParams)
+
+
+def new_sink_params():
+    return _new(FaSinkParams, ("sink",), sink_head_stride=1)
+
+
+def new_block_sparse_params():
+    return _new(FaBlockSparseParams, block_m=128, block_n=128)
+
+
+def new_block_sparse_bwd_params():
+    return _new(FaBlockSparseBwdParams, block_m=128, block_n=128)
+
+
+def new_sparse_kv_params():
+    return _new(FaSparseKvParams, block_size=128)
+
+
+def new_sink_grad_params():
+    return _new(FaSinkGradParams, ("sink",))
+
+
+def new_kvcache_append_kv8_params():
+    return _new(FaKvcacheAppendKv8Params, dtype=FA_DTYPE_BF16)
+
+
+def new_rotary_emb_params():
+    return _new(FaRotaryEmbParams, ("cos", "sin"), dtype=FA_DTYPE_BF16, x_dim_stride=1, out_dim_stride=1)
+
+
+def new_norm_fwd_params():
+    return _new(FaNormFwdParams, ("x", "residual", "residual_out", "weight", "bias", "y", "rowscale"), eps=1e-6)
+
+
+def new_norm_bwd_params():
+    return _new(FaNormBwdParams, ("x", "dy", "weight", "bias", "dresidual", "dresidual_in", "dx", "y", "rowscale"))
+
+
+def new_dropout_norm_fwd_params():
+    return _new(FaDropoutNormFwdParams, ("x0", "residual", "x", "weight", "z", "rowscale", "colscale"), eps=1e-6)
+
+
+def new_dropout_norm_bwd_params():
+    return _new(FaDropoutNormBwdParams, ("dz", "x", "x0", "weight", "rowscale", "colscale"))
+
+
+def new_xent_fwd_params():
+    return _new(FaXentFwdParams, ("logits",), labels_dtype=FA_XENT_LABELS_INT64, ignore_index=-100, logit_scale=1.0)
+
+
+def new_xent_bwd_params():
+    return _new(FaXentBwdParams, ("logits",), labels_dtype=FA_XENT_LABELS_INT64, ignore_index=-100, logit_scale=1.0)
+
+
+def new_sample_params():
+    return _new(FaSampleParams, ("logits",), mode=FA_SAMPLE_DRAW, temperature=1.0)
+
+
+def new_act_fwd_params():
+    return _new(FaActFwdParams, ("pre", "up", "bias", "out"))
+
+
+def new_act_bwd_params():
+    return _new(FaActBwdParams, ("pre", "up", "bias", "dout", "dpre", "dup", "dbias", "out"))
+
+
+def new_gemm_act_fwd_params():
+    return _new(FaGemmActFwdParams, ("x", "weight", "bias", "out", "act_input"))
+
+
+def new_gemm_act_dgrad_params():
+    return _new(FaGemmActDgradParams, ("grad_out", "weight", "act_input", "grad_in", "dbias"))

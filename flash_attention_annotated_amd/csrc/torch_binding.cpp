@@ -2258,11 +2258,39 @@ void check_norm_width(const Tensor &x) {
     TORCH_CHECK(x.size(1) >= 1, "layer_norm: the feature dim must be at least 1");
 }
 
-py::dict norm_plan_dict(const fa_norm_plan &l) {
+// what every X_impl below is made with.  X_impl(args..., plan *) is the one definition of a row operator: with plan == nullptr
+// it launches, with a plan it allocates and fills the params as for the launch and only asks the C entry point for the form.
+// def_row_op (before the module, below) makes the module's `X` and `X_plan` of it
+template <class P> P new_params() {
+    P p{};
+    p.abi_version = FA_ABI_VERSION;
+    p.struct_size = sizeof(P);
+    return p;
+}
+
+// the launch on the current stream of `on`, or with `plan` the form; `name`: the C entry point of the launch
+template <class P, class Plan>
+void launch_or_plan(const char *name, int (*launch)(const P *, void *), int (*form)(const P *, Plan *), const P &p, Plan *plan,
+                    const Tensor &on) {
+    const int st = plan ? form(&p, plan) : launch(&p, current_stream(on));
+    TORCH_CHECK(st == 0, name, plan ? "_plan" : "", " failed (", st, "): ", fa_strerror(st));
+}
+
+// the placeholder of an output there is none of (one tensor each: outputs of an op do not alias)
+Tensor none(const at::TensorOptions &options) { return at::empty({0}, options); }
+
+// a plan struct (all int32_t fields, as the _lib.Fa*Plan mirrors have them) as a dict in the order of `names`, its fields
+template <class Plan, size_t N> py::dict plan_dict(const Plan &plan, const char *const (&names)[N]) {
+    static_assert(sizeof(Plan) == N * sizeof(int32_t), "a field was added to the plan struct and not to its list of names");
+    int32_t fields[N];
+    std::memcpy(fields, &plan, sizeof(fields));
     py::dict d;
-    d["cw"] = l.cw; d["threads"] = l.threads; d["team_wave"] = l.team_wave; d["wide"] = l.wide; d["rows_per_wg"] = l.rows_per_wg;
-    d["grid_x"] = l.grid_x; d["grid_y"] = l.grid_y;
+    for (size_t i = 0; i < N; ++i) d[names[i]] = fields[i];
     return d;
+}
+
+py::dict norm_plan_dict(const fa_norm_plan &l) {
+    return plan_dict(l, {"cw", "threads", "team_wave", "wide", "rows_per_wg", "grid_x", "grid_y"});
 }
 
 // y and (optionally) residual_out are written in place; returns (mean, rstd), mean empty with is_rms_norm.  With `plan` nothing
@@ -2281,9 +2309,7 @@ std::tuple<Tensor, Tensor> norm_fwd_impl(const Tensor &x, const Tensor &weight, 
     if (residual_out.has_value()) check_rows("layer_norm: ", "(M, N)", *residual_out, "residual_out", M, N);
     if (rowscale.has_value()) check_vector("layer_norm: ", *rowscale, "rowscale", M, "(M)");
     check_norm_width(x);
-    fa_norm_fwd_params p{};
-    p.abi_version = FA_ABI_VERSION;
-    p.struct_size = sizeof(fa_norm_fwd_params);
+    auto p = new_params<fa_norm_fwd_params>();
     p.x_dtype = row_dtype_code("layer_norm: ", x.scalar_type(), "x");
     p.weight_dtype = row_dtype_code("layer_norm: ", weight.scalar_type(), "weight");
     p.y_dtype = row_dtype_code("layer_norm: ", out.scalar_type(), "out");
@@ -2297,6 +2323,7 @@ std::tuple<Tensor, Tensor> norm_fwd_impl(const Tensor &x, const Tensor &weight, 
     c10::hip::HIPGuardMasqueradingAsCUDA device_guard(x.device());
     const auto stats = x.options().dtype(at::kFloat);
     Tensor mean = at::empty({is_rms_norm ? 0 : M}, stats), rstd = at::empty({M}, stats);
+    TORCH_CHECK(M > 0 || !plan, "layer_norm: a plan needs at least one row");
     if (M == 0) return {mean, rstd};
     p.x = x.data_ptr(); p.weight = weight.data_ptr(); p.bias = ptr(bias); p.residual = ptr(residual); p.rowscale = ptr(rowscale);
     p.y = out.data_ptr(); p.residual_out = ptr(residual_out);
@@ -2307,26 +2334,8 @@ std::tuple<Tensor, Tensor> norm_fwd_impl(const Tensor &x, const Tensor &weight, 
     p.residual_out_row_stride = residual_out.has_value() ? residual_out->stride(0) : 0;
     p.M = M; p.N = (int32_t)N; p.eps = (float)eps;
     p.flags = (is_rms_norm ? FA_NORM_RMS : 0) | (zero_centered_weight ? FA_NORM_ZERO_CENTERED : 0);
-    const int st = plan ? fa_norm_fwd_plan(&p, plan) : fa_norm_fwd(&p, current_stream(x));
-    TORCH_CHECK(st == 0, plan ? "fa_norm_fwd_plan" : "fa_norm_fwd", " failed (", st, "): ", fa_strerror(st));
+    launch_or_plan("fa_norm_fwd", fa_norm_fwd, fa_norm_fwd_plan, p, plan, x);
     return {mean, rstd};
-}
-
-std::tuple<Tensor, Tensor> norm_fwd(const Tensor &x, const Tensor &weight, const OptTensor &bias, const OptTensor &residual,
-                                    const OptTensor &rowscale, Tensor out, OptTensor residual_out, double eps,
-                                    bool zero_centered_weight, bool is_rms_norm) {
-    return norm_fwd_impl(x, weight, bias, residual, rowscale, out, residual_out, eps, zero_centered_weight, is_rms_norm, nullptr);
-}
-
-// the form norm_fwd takes with these arguments (fa_norm_plan as a dict); M >= 1.  A helper of the tests, not of a training step:
-// like norm_bwd_plan below it allocates what the launch would allocate, only to see the alignment the plan depends on
-py::dict norm_fwd_plan(const Tensor &x, const Tensor &weight, const OptTensor &bias, const OptTensor &residual,
-                       const OptTensor &rowscale, Tensor out, OptTensor residual_out, double eps, bool zero_centered_weight,
-                       bool is_rms_norm) {
-    TORCH_CHECK(x.dim() == 2 && x.size(0) >= 1, "layer_norm: a plan needs at least one row");
-    fa_norm_plan plan{};
-    norm_fwd_impl(x, weight, bias, residual, rowscale, out, residual_out, eps, zero_centered_weight, is_rms_norm, &plan);
-    return norm_plan_dict(plan);
 }
 
 // x: what the forward returned as residual_out.  Returns (dx, dw, db, dresidual_in, y); db, dresidual_in and y are empty tensors
@@ -2352,9 +2361,7 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> norm_bwd_impl(const Tensor &d
     check_vector("layer_norm: ", rstd, "rstd", M, "(M)");
     TORCH_CHECK(rstd.scalar_type() == at::kFloat && (is_rms_norm || mean->scalar_type() == at::kFloat), "layer_norm: mean and rstd must be fp32");
     check_norm_width(x);
-    fa_norm_bwd_params p{};
-    p.abi_version = FA_ABI_VERSION;
-    p.struct_size = sizeof(fa_norm_bwd_params);
+    auto p = new_params<fa_norm_bwd_params>();
     p.x_dtype = row_dtype_code("layer_norm: ", x.scalar_type(), "x");
     p.dy_dtype = row_dtype_code("layer_norm: ", dy.scalar_type(), "dy");
     p.weight_dtype = row_dtype_code("layer_norm: ", weight.scalar_type(), "weight");
@@ -2367,13 +2374,13 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> norm_bwd_impl(const Tensor &d
     TORCH_CHECK(p.dresidual_dtype == p.x_dtype, "layer_norm: dresidual must have the dtype of x");
     TORCH_CHECK(p.x_dtype == p.dx_dtype || p.x_dtype == FA_DTYPE_FP32, "layer_norm: x must have the dtype of dx or fp32");
     c10::hip::HIPGuardMasqueradingAsCUDA device_guard(x.device());
-    auto none = [&] { return at::empty({0}, x.options()); };  // (one tensor each: outputs of an op do not alias)
     Tensor dx = at::empty({M, N}, x.options().dtype(norm_scalar_type(dx_dtype)));
     // (the reference's rule: where dx has the residual's dtype and is not scaled, it is dresidual_in)
     const bool own_dresidual = has_residual && (p.dx_dtype != p.x_dtype || rowscale.has_value());
-    Tensor dresidual_in = own_dresidual ? at::empty({M, N}, x.options()) : none();
-    Tensor y = recompute_output ? at::empty({M, N}, dy.options()) : none();
-    Tensor dw = at::empty({N}, weight.options()), db = bias.has_value() ? at::empty({N}, bias->options()) : none();
+    Tensor dresidual_in = own_dresidual ? at::empty({M, N}, x.options()) : none(x.options());
+    Tensor y = recompute_output ? at::empty({M, N}, dy.options()) : none(x.options());
+    Tensor dw = at::empty({N}, weight.options()), db = bias.has_value() ? at::empty({N}, bias->options()) : none(x.options());
+    TORCH_CHECK(M > 0 || !plan, "layer_norm: a plan needs at least one row");
     if (M == 0) {  // (empty tensors have no storage to point at: no rows, zero sums, nothing of ours launched)
         dw.zero_();
         if (bias.has_value()) db.zero_();
@@ -2392,28 +2399,8 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> norm_bwd_impl(const Tensor &d
     p.dresidual_row_stride = dresidual.has_value() ? dresidual->stride(0) : 0;
     p.eps = 0.0f;  // (rstd is read, not formed)
     p.flags = (is_rms_norm ? FA_NORM_RMS : 0) | (zero_centered_weight ? FA_NORM_ZERO_CENTERED : 0);
-    const int st = plan ? fa_norm_bwd_plan(&p, plan) : fa_norm_bwd(&p, current_stream(x));
-    TORCH_CHECK(st == 0, plan ? "fa_norm_bwd_plan" : "fa_norm_bwd", " failed (", st, "): ", fa_strerror(st));
+    launch_or_plan("fa_norm_bwd", fa_norm_bwd, fa_norm_bwd_plan, p, plan, x);
     return {dx, dw, db, dresidual_in, y};
-}
-
-std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> norm_bwd(const Tensor &dy, const Tensor &x, const Tensor &weight, const OptTensor &bias,
-                                                            const OptTensor &mean, const Tensor &rstd, const OptTensor &dresidual,
-                                                            const OptTensor &rowscale, bool has_residual, bool zero_centered_weight,
-                                                            bool is_rms_norm, int64_t dx_dtype, bool recompute_output) {
-    return norm_bwd_impl(dy, x, weight, bias, mean, rstd, dresidual, rowscale, has_residual, zero_centered_weight, is_rms_norm, dx_dtype,
-                         recompute_output, nullptr);
-}
-
-// the form norm_bwd takes with these arguments (fa_norm_plan as a dict); M >= 1
-py::dict norm_bwd_plan(const Tensor &dy, const Tensor &x, const Tensor &weight, const OptTensor &bias, const OptTensor &mean,
-                       const Tensor &rstd, const OptTensor &dresidual, const OptTensor &rowscale, bool has_residual,
-                       bool zero_centered_weight, bool is_rms_norm, int64_t dx_dtype, bool recompute_output) {
-    TORCH_CHECK(x.dim() == 2 && x.size(0) >= 1, "layer_norm: a plan needs at least one row");
-    fa_norm_plan plan{};
-    norm_bwd_impl(dy, x, weight, bias, mean, rstd, dresidual, rowscale, has_residual, zero_centered_weight, is_rms_norm, dx_dtype,
-                  recompute_output, &plan);
-    return norm_plan_dict(plan);
 }
 
 // ---- fused dropout + residual-add + LayerNorm / RMSNorm (flash_attn.ops.layer_norm -> dropout_layer_norm.dropout_add_ln_fwd /
@@ -2421,10 +2408,7 @@ py::dict norm_bwd_plan(const Tensor &dy, const Tensor &x, const Tensor &weight, 
 // current stream, no synchronisation; (seed, offset) are drawn on the device as the attention forward draws them, and every
 // output comes from the caching allocator: capturable in a HIP graph.
 py::dict dropout_norm_plan_dict(const fa_dropout_norm_plan &l) {
-    py::dict d;
-    d["cw"] = l.cw; d["threads"] = l.threads; d["wide"] = l.wide; d["dropout"] = l.dropout; d["two_weights"] = l.two_weights;
-    d["sums"] = l.sums; d["rows_per_wg"] = l.rows_per_wg; d["grid_x"] = l.grid_x; d["grid_y"] = l.grid_y;
-    return d;
+    return plan_dict(l, {"cw", "threads", "wide", "dropout", "two_weights", "sums", "rows_per_wg", "grid_x", "grid_y"});
 }
 
 using DropoutNormFwdOut = std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor>;
@@ -2457,9 +2441,7 @@ DropoutNormFwdOut dropout_norm_fwd_impl(const Tensor &x0, const OptTensor &x1, c
     TORCH_CHECK(!bias1.has_value() || weight1.has_value(), "dropout_add_layer_norm: bias1 needs weight1");
     TORCH_CHECK(!x1.has_value() || x1->scalar_type() == x0.scalar_type(), "dropout_add_layer_norm: x1 must have the dtype of x0");
     check_norm_width(x0);
-    fa_dropout_norm_fwd_params p{};
-    p.abi_version = FA_ABI_VERSION;
-    p.struct_size = sizeof(fa_dropout_norm_fwd_params);
+    auto p = new_params<fa_dropout_norm_fwd_params>();
     p.x0_dtype = row_dtype_code("layer_norm: ", x0.scalar_type(), "x0");
     p.weight_dtype = row_dtype_code("layer_norm: ", weight0.scalar_type(), "weight0");
     p.z_dtype = p.x0_dtype;
@@ -2475,14 +2457,14 @@ DropoutNormFwdOut dropout_norm_fwd_impl(const Tensor &x0, const OptTensor &x1, c
     const bool dropout = p_dropout > 0.0;
     const bool own_x = want_x || dropout || residual.has_value() || x1.has_value() || rowscale.has_value() || colscale.has_value() ||
                        p.x_dtype != p.x0_dtype;
-    auto none = [&](at::ScalarType t) { return at::empty({0}, x0.options().dtype(t)); };  // (one tensor each: outputs do not alias)
-    const auto stats = x0.options().dtype(at::kFloat);
-    Tensor z0 = at::empty({M, N}, x0.options()), z1 = weight1.has_value() ? at::empty({M, N}, x0.options()) : none(x0.scalar_type());
-    Tensor x = own_x ? at::empty({M, N}, x0.options().dtype(stream_type)) : none(stream_type);
-    Tensor dmask0 = return_dmask && dropout ? at::empty({M, N}, x0.options().dtype(at::kByte)) : none(at::kByte);
-    Tensor dmask1 = return_dmask && dropout && x1.has_value() ? at::empty({M, N}, x0.options().dtype(at::kByte)) : none(at::kByte);
+    const auto stats = x0.options().dtype(at::kFloat), bytes = x0.options().dtype(at::kByte);
+    Tensor z0 = at::empty({M, N}, x0.options()), z1 = weight1.has_value() ? at::empty({M, N}, x0.options()) : none(x0.options());
+    Tensor x = own_x ? at::empty({M, N}, x0.options().dtype(stream_type)) : none(x0.options().dtype(stream_type));
+    Tensor dmask0 = return_dmask && dropout ? at::empty({M, N}, bytes) : none(bytes);
+    Tensor dmask1 = return_dmask && dropout && x1.has_value() ? at::empty({M, N}, bytes) : none(bytes);
     Tensor mu = at::empty({is_rms_norm ? 0 : M}, stats), rsigma = at::empty({M}, stats);
     Tensor rng_state = plan ? at::zeros({2}, x0.options().dtype(at::kLong)) : dropout_state(p_dropout, c10::nullopt, x0);
+    TORCH_CHECK(M > 0 || !plan, "dropout_add_layer_norm: a plan needs at least one row");
     if (M == 0) return {z0, z1, x, dmask0, dmask1, mu, rsigma, rng_state};
     p.x0 = x0.data_ptr(); p.x1 = ptr(x1); p.residual = ptr(residual); p.weight0 = weight0.data_ptr(); p.bias0 = ptr(bias0);
     p.weight1 = ptr(weight1); p.bias1 = ptr(bias1); p.rowscale = ptr(rowscale); p.colscale = ptr(colscale);
@@ -2497,30 +2479,8 @@ DropoutNormFwdOut dropout_norm_fwd_impl(const Tensor &x0, const OptTensor &x1, c
     p.z0_row_stride = N; p.z1_row_stride = N; p.x_row_stride = N;
     p.M = M; p.N = (int32_t)N; p.eps = (float)eps; p.p_dropout = (float)p_dropout;
     p.flags = is_rms_norm ? FA_DROPOUT_NORM_RMS : 0;
-    const int st = plan ? fa_dropout_norm_fwd_plan(&p, plan) : fa_dropout_norm_fwd(&p, current_stream(x0));
-    TORCH_CHECK(st == 0, plan ? "fa_dropout_norm_fwd_plan" : "fa_dropout_norm_fwd", " failed (", st, "): ", fa_strerror(st));
+    launch_or_plan("fa_dropout_norm_fwd", fa_dropout_norm_fwd, fa_dropout_norm_fwd_plan, p, plan, x0);
     return {z0, z1, x, dmask0, dmask1, mu, rsigma, rng_state};
-}
-
-DropoutNormFwdOut dropout_norm_fwd(const Tensor &x0, const OptTensor &x1, const OptTensor &residual, const Tensor &weight0,
-                                   const OptTensor &bias0, const OptTensor &weight1, const OptTensor &bias1, const OptTensor &rowscale,
-                                   const OptTensor &colscale, double p_dropout, double eps, bool residual_in_fp32, bool is_rms_norm,
-                                   bool want_x, bool return_dmask) {
-    return dropout_norm_fwd_impl(x0, x1, residual, weight0, bias0, weight1, bias1, rowscale, colscale, p_dropout, eps, residual_in_fp32,
-                                 is_rms_norm, want_x, return_dmask, nullptr);
-}
-
-// the form dropout_norm_fwd takes with these arguments (fa_dropout_norm_plan as a dict); M >= 1.  A helper of the tests: it
-// allocates what the launch would allocate, only to see the alignment the plan depends on
-py::dict dropout_norm_fwd_plan(const Tensor &x0, const OptTensor &x1, const OptTensor &residual, const Tensor &weight0,
-                               const OptTensor &bias0, const OptTensor &weight1, const OptTensor &bias1, const OptTensor &rowscale,
-                               const OptTensor &colscale, double p_dropout, double eps, bool residual_in_fp32, bool is_rms_norm,
-                               bool want_x, bool return_dmask) {
-    TORCH_CHECK(x0.dim() == 2 && x0.size(0) >= 1, "dropout_add_layer_norm: a plan needs at least one row");
-    fa_dropout_norm_plan plan{};
-    dropout_norm_fwd_impl(x0, x1, residual, weight0, bias0, weight1, bias1, rowscale, colscale, p_dropout, eps, residual_in_fp32,
-                          is_rms_norm, want_x, return_dmask, &plan);
-    return dropout_norm_plan_dict(plan);
 }
 
 using DropoutNormBwdOut = std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor>;
@@ -2568,9 +2528,7 @@ DropoutNormBwdOut dropout_norm_bwd_impl(const Tensor &dz0, const OptTensor &dz1,
                 "dropout_add_layer_norm: rng_state must be two int64 on the device");
     TORCH_CHECK(p_dropout >= 0.0 && p_dropout < 1.0, "dropout_add_layer_norm: dropout_p must be in [0, 1)");
     check_norm_width(x);
-    fa_dropout_norm_bwd_params p{};
-    p.abi_version = FA_ABI_VERSION;
-    p.struct_size = sizeof(fa_dropout_norm_bwd_params);
+    auto p = new_params<fa_dropout_norm_bwd_params>();
     p.x_dtype = row_dtype_code("layer_norm: ", x.scalar_type(), "x");
     p.dz_dtype = row_dtype_code("layer_norm: ", dz0.scalar_type(), "dz0");
     p.weight_dtype = row_dtype_code("layer_norm: ", weight0.scalar_type(), "weight0");
@@ -2582,14 +2540,15 @@ DropoutNormBwdOut dropout_norm_bwd_impl(const Tensor &dz0, const OptTensor &dz1,
     c10::hip::HIPGuardMasqueradingAsCUDA device_guard(x.device());
     const bool dropout = p_dropout > 0.0;
     const bool own_dresidual = has_residual && (dropout || rowscale.has_value() || colscale.has_value() || p.x_dtype != p.x0_dtype);
-    auto none = [&](const Tensor &like) { return at::empty({0}, like.options()); };
-    Tensor dx0 = at::empty({M, N}, x.options().dtype(in_type));
-    Tensor dx1 = has_x1 ? at::empty({M, N}, x.options().dtype(in_type)) : none(dx0);
-    Tensor dresidual = own_dresidual ? at::empty({M, N}, x.options()) : none(x);
-    Tensor dw0 = at::empty({N}, weight0.options()), db0 = has_bias ? at::empty({N}, weight0.options()) : none(weight0);
-    Tensor dw1 = weight1.has_value() ? at::empty({N}, weight0.options()) : none(weight0);
-    Tensor db1 = weight1.has_value() && has_bias ? at::empty({N}, weight0.options()) : none(weight0);
-    Tensor dcolscale = colscale.has_value() ? at::empty({N}, colscale->options()) : none(weight0);
+    const auto in = x.options().dtype(in_type), w = weight0.options();
+    Tensor dx0 = at::empty({M, N}, in);
+    Tensor dx1 = has_x1 ? at::empty({M, N}, in) : none(in);
+    Tensor dresidual = own_dresidual ? at::empty({M, N}, x.options()) : none(x.options());
+    Tensor dw0 = at::empty({N}, w), db0 = has_bias ? at::empty({N}, w) : none(w);
+    Tensor dw1 = weight1.has_value() ? at::empty({N}, w) : none(w);
+    Tensor db1 = weight1.has_value() && has_bias ? at::empty({N}, w) : none(w);
+    Tensor dcolscale = colscale.has_value() ? at::empty({N}, colscale->options()) : none(w);
+    TORCH_CHECK(M > 0 || !plan, "dropout_add_layer_norm: a plan needs at least one row");
     if (M == 0) {  // (empty tensors have no storage to point at: no rows, zero sums, nothing of ours launched)
         for (Tensor *t : {&dw0, &db0, &dw1, &db1, &dcolscale}) t->zero_();
         return {dx0, dx1, dresidual, dw0, db0, dw1, db1, dcolscale};
@@ -2614,29 +2573,8 @@ DropoutNormBwdOut dropout_norm_bwd_impl(const Tensor &dz0, const OptTensor &dz1,
     p.dx0_row_stride = N; p.dx1_row_stride = N; p.dresidual_row_stride = N;
     p.p_dropout = (float)p_dropout;
     p.flags = is_rms_norm ? FA_DROPOUT_NORM_RMS : 0;
-    const int st = plan ? fa_dropout_norm_bwd_plan(&p, plan) : fa_dropout_norm_bwd(&p, current_stream(x));
-    TORCH_CHECK(st == 0, plan ? "fa_dropout_norm_bwd_plan" : "fa_dropout_norm_bwd", " failed (", st, "): ", fa_strerror(st));
+    launch_or_plan("fa_dropout_norm_bwd", fa_dropout_norm_bwd, fa_dropout_norm_bwd_plan, p, plan, x);
     return {dx0, dx1, dresidual, dw0, db0, dw1, db1, dcolscale};
-}
-
-DropoutNormBwdOut dropout_norm_bwd(const Tensor &dz0, const OptTensor &dz1, const OptTensor &dx, const Tensor &x, const OptTensor &x0,
-                                   const OptTensor &mu, const Tensor &rsigma, const Tensor &weight0, const OptTensor &weight1,
-                                   const OptTensor &rowscale, const OptTensor &colscale, const Tensor &rng_state, double p_dropout,
-                                   bool has_x1, bool has_residual, bool has_bias, bool is_rms_norm, int64_t x0_dtype) {
-    return dropout_norm_bwd_impl(dz0, dz1, dx, x, x0, mu, rsigma, weight0, weight1, rowscale, colscale, rng_state, p_dropout, has_x1,
-                                 has_residual, has_bias, is_rms_norm, x0_dtype, nullptr);
-}
-
-// the form dropout_norm_bwd takes with these arguments (fa_dropout_norm_plan as a dict); M >= 1
-py::dict dropout_norm_bwd_plan(const Tensor &dz0, const OptTensor &dz1, const OptTensor &dx, const Tensor &x, const OptTensor &x0,
-                               const OptTensor &mu, const Tensor &rsigma, const Tensor &weight0, const OptTensor &weight1,
-                               const OptTensor &rowscale, const OptTensor &colscale, const Tensor &rng_state, double p_dropout,
-                               bool has_x1, bool has_residual, bool has_bias, bool is_rms_norm, int64_t x0_dtype) {
-    TORCH_CHECK(x.dim() == 2 && x.size(0) >= 1, "dropout_add_layer_norm: a plan needs at least one row");
-    fa_dropout_norm_plan plan{};
-    dropout_norm_bwd_impl(dz0, dz1, dx, x, x0, mu, rsigma, weight0, weight1, rowscale, colscale, rng_state, p_dropout, has_x1,
-                          has_residual, has_bias, is_rms_norm, x0_dtype, &plan);
-    return dropout_norm_plan_dict(plan);
 }
 
 // ---- fused cross-entropy loss (flash_attn.ops.triton.cross_entropy -> CrossEntropyLoss.forward / backward,
@@ -2656,11 +2594,7 @@ void check_xent_rows(const Tensor &t, const char *name) {
     TORCH_CHECK(t.stride(-1) == 1, "cross_entropy: ", name, " must have contiguous last dimension");
 }
 
-py::dict xent_plan_dict(const fa_xent_plan &l) {
-    py::dict d;
-    d["cw"] = l.cw; d["grid_x"] = l.grid_x; d["grid_y"] = l.grid_y; d["lse_given"] = l.lse_given;
-    return d;
-}
+py::dict xent_plan_dict(const fa_xent_plan &l) { return plan_dict(l, {"cw", "grid_x", "grid_y", "lse_given"}); }
 
 // (losses, lse, z_losses).  With precomputed_lse that tensor is read and the lse returned is empty; with split the columns are
 // one rank's part of total_classes, losses lack the lse and the z-loss, and the z_losses returned are empty
@@ -2675,14 +2609,13 @@ std::tuple<Tensor, Tensor, Tensor> xent_fwd_impl(const Tensor &logits, const Ten
         check_vector("cross_entropy: ", *precomputed_lse, "precomputed_lse", M, "(M)", true);
         TORCH_CHECK(precomputed_lse->scalar_type() == at::kFloat, "cross_entropy: precomputed_lse must be fp32");
     }
-    fa_xent_fwd_params p{};
-    p.abi_version = FA_ABI_VERSION;
-    p.struct_size = sizeof(fa_xent_fwd_params);
+    auto p = new_params<fa_xent_fwd_params>();
     p.logits_dtype = row_dtype_code("cross_entropy: ", logits.scalar_type(), "logits");
     p.labels_dtype = xent_labels_code(labels.scalar_type());
     c10::hip::HIPGuardMasqueradingAsCUDA device_guard(logits.device());
     const auto fp32 = logits.options().dtype(at::kFloat);
     Tensor losses = at::empty({M}, fp32), lse = at::empty({precomputed_lse.has_value() ? 0 : M}, fp32), z_losses = at::empty({split ? 0 : M}, fp32);
+    TORCH_CHECK(M > 0 || !plan, "cross_entropy: a plan needs at least one row");
     if (M == 0) return {losses, lse, z_losses};
     p.logits = logits.data_ptr(); p.labels = labels.data_ptr();
     p.losses = static_cast<float *>(losses.data_ptr());
@@ -2693,26 +2626,8 @@ std::tuple<Tensor, Tensor, Tensor> xent_fwd_impl(const Tensor &logits, const Ten
     p.ignore_index = ignore_index; p.class_start_idx = class_start_idx; p.total_classes = total_classes;
     p.smoothing = (float)smoothing; p.logit_scale = (float)logit_scale; p.lse_square_scale = (float)lse_square_scale;
     p.flags = (precomputed_lse.has_value() ? FA_XENT_PRECOMPUTED_LSE : 0) | (split ? FA_XENT_SPLIT : 0);
-    const int st = plan ? fa_xent_fwd_plan(&p, plan) : fa_xent_fwd(&p, current_stream(logits));
-    TORCH_CHECK(st == 0, plan ? "fa_xent_fwd_plan" : "fa_xent_fwd", " failed (", st, "): ", fa_strerror(st));
+    launch_or_plan("fa_xent_fwd", fa_xent_fwd, fa_xent_fwd_plan, p, plan, logits);
     return {losses, lse, z_losses};
-}
-
-std::tuple<Tensor, Tensor, Tensor> xent_fwd(const Tensor &logits, const Tensor &labels, const OptTensor &precomputed_lse, double smoothing,
-                                            double logit_scale, double lse_square_scale, int64_t ignore_index, int64_t class_start_idx,
-                                            int64_t total_classes, bool split) {
-    return xent_fwd_impl(logits, labels, precomputed_lse, smoothing, logit_scale, lse_square_scale, ignore_index, class_start_idx,
-                         total_classes, split, nullptr);
-}
-
-// the form xent_fwd takes with these arguments (fa_xent_plan as a dict); M >= 1
-py::dict xent_fwd_plan(const Tensor &logits, const Tensor &labels, const OptTensor &precomputed_lse, double smoothing, double logit_scale,
-                       double lse_square_scale, int64_t ignore_index, int64_t class_start_idx, int64_t total_classes, bool split) {
-    TORCH_CHECK(logits.dim() == 2 && logits.size(0) >= 1, "cross_entropy: a plan needs at least one row");
-    fa_xent_plan plan{};
-    xent_fwd_impl(logits, labels, precomputed_lse, smoothing, logit_scale, lse_square_scale, ignore_index, class_start_idx, total_classes,
-                  split, &plan);
-    return xent_plan_dict(plan);
 }
 
 // writes dlogits, which may be logits.  With `plan` nothing is launched: *plan is what fa_xent_bwd_plan says of the params
@@ -2728,11 +2643,10 @@ void xent_bwd_impl(const Tensor &dloss, const Tensor &logits, const Tensor &labe
     check_vector("cross_entropy: ", lse, "lse", M, "(M)", true);
     check_vector("cross_entropy: ", dloss, "dloss", M, "(M)", false);
     TORCH_CHECK(lse.scalar_type() == at::kFloat && dloss.scalar_type() == at::kFloat, "cross_entropy: lse and dloss must be fp32");
-    fa_xent_bwd_params p{};
-    p.abi_version = FA_ABI_VERSION;
-    p.struct_size = sizeof(fa_xent_bwd_params);
+    auto p = new_params<fa_xent_bwd_params>();
     p.logits_dtype = row_dtype_code("cross_entropy: ", logits.scalar_type(), "logits");
     p.labels_dtype = xent_labels_code(labels.scalar_type());
+    TORCH_CHECK(M > 0 || !plan, "cross_entropy: a plan needs at least one row");
     if (M == 0) return;
     c10::hip::HIPGuardMasqueradingAsCUDA device_guard(logits.device());
     p.logits = logits.data_ptr(); p.labels = labels.data_ptr(); p.dlogits = dlogits.data_ptr();
@@ -2741,36 +2655,15 @@ void xent_bwd_impl(const Tensor &dloss, const Tensor &logits, const Tensor &labe
     p.M = M; p.N = (int32_t)N;
     p.ignore_index = ignore_index; p.class_start_idx = class_start_idx; p.total_classes = total_classes;
     p.smoothing = (float)smoothing; p.logit_scale = (float)logit_scale; p.lse_square_scale = (float)lse_square_scale;
-    const int st = plan ? fa_xent_bwd_plan(&p, plan) : fa_xent_bwd(&p, current_stream(logits));
-    TORCH_CHECK(st == 0, plan ? "fa_xent_bwd_plan" : "fa_xent_bwd", " failed (", st, "): ", fa_strerror(st));
-}
-
-void xent_bwd(const Tensor &dloss, const Tensor &logits, const Tensor &labels, const Tensor &lse, Tensor dlogits, double smoothing,
-              double logit_scale, double lse_square_scale, int64_t ignore_index, int64_t class_start_idx, int64_t total_classes) {
-    xent_bwd_impl(dloss, logits, labels, lse, dlogits, smoothing, logit_scale, lse_square_scale, ignore_index, class_start_idx,
-                  total_classes, nullptr);
-}
-
-// the form xent_bwd takes with these arguments (fa_xent_plan as a dict); M >= 1
-py::dict xent_bwd_plan(const Tensor &dloss, const Tensor &logits, const Tensor &labels, const Tensor &lse, Tensor dlogits, double smoothing,
-                       double logit_scale, double lse_square_scale, int64_t ignore_index, int64_t class_start_idx, int64_t total_classes) {
-    TORCH_CHECK(logits.dim() == 2 && logits.size(0) >= 1, "cross_entropy: a plan needs at least one row");
-    fa_xent_plan plan{};
-    xent_bwd_impl(dloss, logits, labels, lse, dlogits, smoothing, logit_scale, lse_square_scale, ignore_index, class_start_idx,
-                  total_classes, &plan);
-    return xent_plan_dict(plan);
+    launch_or_plan("fa_xent_bwd", fa_xent_bwd, fa_xent_bwd_plan, p, plan, logits);
 }
 
 // ---- fused top-k / top-p token sampling (flash_attn.utils.generation: sample, modify_logits_for_top_k_filtering,
 // modify_logits_for_top_p_filtering, flash_attn/utils/generation.py:45-95; include/fa_sample.h).  Launches on the current
 // stream, no synchronisation; token, kept and mass come from the caching allocator: capturable in a HIP graph.
 py::dict sample_plan_dict(const fa_sample_form &l) {
-    py::dict d;
-    d["cw"] = l.cw; d["threads"] = l.threads; d["mode"] = l.mode; d["greedy"] = l.greedy;
-    d["topk"] = l.topk; d["topp"] = l.topp; d["draw"] = l.draw; d["k"] = l.k;
-    d["key_bits"] = l.key_bits; d["key_passes"] = l.key_passes; d["index_bits"] = l.index_bits; d["index_passes"] = l.index_passes;
-    d["frac_bits"] = l.frac_bits; d["grid_x"] = l.grid_x;
-    return d;
+    return plan_dict(l, {"cw", "threads", "mode", "greedy", "topk", "topp", "draw", "k", "key_bits", "key_passes", "index_bits",
+                         "index_passes", "frac_bits", "grid_x"});
 }
 
 // (token, kept, mass); kept and mass are empty without `stats`, token is empty in the filter mode.  A draw (top_k != 1) takes
@@ -2794,14 +2687,13 @@ std::tuple<Tensor, Tensor, Tensor> sample_impl(const Tensor &logits, int64_t top
     if (rng_state.has_value())
         TORCH_CHECK(rng_state->is_cuda() && rng_state->scalar_type() == at::kLong && rng_state->numel() == 2 && rng_state->is_contiguous(),
                     "sample: rng_state must be two int64 on the device");
-    fa_sample_params p{};
-    p.abi_version = FA_ABI_VERSION;
-    p.struct_size = sizeof(fa_sample_params);
+    auto p = new_params<fa_sample_params>();
     p.logits_dtype = row_dtype_code("sample: ", logits.scalar_type(), "logits");
     c10::hip::HIPGuardMasqueradingAsCUDA device_guard(logits.device());
     stats = stats && !greedy;
     Tensor token = at::empty({draw ? B : 0}, logits.options().dtype(at::kLong));
     Tensor kept = at::empty({stats ? B : 0}, logits.options().dtype(at::kInt)), mass = at::empty({stats ? B : 0}, logits.options().dtype(at::kFloat));
+    TORCH_CHECK(B > 0 || !plan, "sample: a plan needs at least one row");
     if (B == 0) return {token, kept, mass};
     Tensor state;  // (kept alive to the launch)
     if (draw && !greedy) {
@@ -2820,8 +2712,7 @@ std::tuple<Tensor, Tensor, Tensor> sample_impl(const Tensor &logits, int64_t top
     p.logits_row_stride = logits.stride(0);
     p.B = B; p.V = (int32_t)V;
     p.mode = mode; p.top_k = (int32_t)top_k; p.top_p = (float)top_p; p.temperature = (float)temperature;
-    const int st = plan ? fa_sample_plan(&p, plan) : fa_sample(&p, current_stream(logits));
-    TORCH_CHECK(st == 0, plan ? "fa_sample_plan" : "fa_sample", " failed (", st, "): ", fa_strerror(st));
+    launch_or_plan("fa_sample", fa_sample, fa_sample_plan, p, plan, logits);
     return {token, kept, mass};
 }
 
@@ -2838,7 +2729,6 @@ std::tuple<Tensor, Tensor> sample_filter_(Tensor logits, int64_t top_k, double t
 
 // the form sample (filter: sample_filter_) takes with these arguments (fa_sample_form as a dict); at least one row
 py::dict sample_plan(const Tensor &logits, int64_t top_k, double top_p, double temperature, bool filter, bool stats) {
-    TORCH_CHECK(logits.dim() == 2 && logits.size(0) >= 1, "sample: a plan needs at least one row");
     fa_sample_form plan{};
     sample_impl(logits, top_k, top_p, temperature, c10::nullopt, c10::nullopt, stats, filter ? FA_SAMPLE_FILTER : FA_SAMPLE_DRAW, &plan);
     return sample_plan_dict(plan);
@@ -2875,41 +2765,24 @@ std::pair<int64_t, int64_t> check_act_inputs(const Tensor &pre, const OptTensor 
     return {M, H};
 }
 
-py::dict act_plan_dict(const fa_act_plan &l) {
-    py::dict d;
-    d["cw"] = l.cw; d["threads"] = l.threads; d["grid_x"] = l.grid_x; d["grid_y"] = l.grid_y; d["rows_per_wg"] = l.rows_per_wg;
-    return d;
-}
+py::dict act_plan_dict(const fa_act_plan &l) { return plan_dict(l, {"cw", "threads", "grid_x", "grid_y", "rows_per_wg"}); }
 
 // out (M, H) = act(pre + bias), or act(pre) * up with `up` (pre is then the gate).  With `plan` nothing is launched: *plan is
 // what fa_act_fwd_plan says of the params the launch would get
 Tensor act_fwd_impl(const Tensor &pre, const OptTensor &up, const OptTensor &bias, int64_t activation, fa_act_plan *plan) {
     const auto [M, H] = check_act_inputs(pre, up, bias);
-    fa_act_fwd_params p{};
-    p.abi_version = FA_ABI_VERSION;
-    p.struct_size = sizeof(fa_act_fwd_params);
+    auto p = new_params<fa_act_fwd_params>();
     p.pre_dtype = p.up_dtype = p.out_dtype = row_dtype_code("activation: ", pre.scalar_type(), "pre");
     p.bias_dtype = bias.has_value() ? row_dtype_code("activation: ", bias->scalar_type(), "bias") : p.pre_dtype;
     c10::hip::HIPGuardMasqueradingAsCUDA device_guard(pre.device());
     Tensor out = at::empty({M, H}, pre.options());
+    TORCH_CHECK(M > 0 || !plan, "activation: a plan needs at least one row");
     if (M == 0) return out;
     p.pre = pre.data_ptr(); p.up = ptr(up); p.bias = ptr(bias); p.out = out.data_ptr();
     p.pre_row_stride = pre.stride(0); p.out_row_stride = H;
     p.M = M; p.H = (int32_t)H; p.activation = (int32_t)activation; p.flags = up.has_value() ? FA_ACT_GATED : 0;
-    const int st = plan ? fa_act_fwd_plan(&p, plan) : fa_act_fwd(&p, current_stream(pre));
-    TORCH_CHECK(st == 0, plan ? "fa_act_fwd_plan" : "fa_act_fwd", " failed (", st, "): ", fa_strerror(st));
+    launch_or_plan("fa_act_fwd", fa_act_fwd, fa_act_fwd_plan, p, plan, pre);
     return out;
-}
-
-Tensor act_fwd(const Tensor &pre, const OptTensor &up, const OptTensor &bias, int64_t activation) {
-    return act_fwd_impl(pre, up, bias, activation, nullptr);
-}
-
-py::dict act_fwd_plan(const Tensor &pre, const OptTensor &up, const OptTensor &bias, int64_t activation) {
-    TORCH_CHECK(pre.dim() == 2 && pre.size(0) >= 1, "activation: a plan needs at least one row");
-    fa_act_plan plan{};
-    act_fwd_impl(pre, up, bias, activation, &plan);
-    return act_plan_dict(plan);
 }
 
 // (dpre, dup, dbias, out).  Plain: dpre (M, H); dup empty.  Gated: dpre is dgate and dup (M, H) each, or with `packed` dpre is one
@@ -2923,17 +2796,15 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> act_bwd_impl(const Tensor &dout, cons
     const bool gated = up.has_value();
     TORCH_CHECK(!(gated && want_dbias), "activation: the gated form has no dbias");
     TORCH_CHECK(gated || !packed, "activation: a packed gradient needs the gated form");
-    fa_act_bwd_params p{};
-    p.abi_version = FA_ABI_VERSION;
-    p.struct_size = sizeof(fa_act_bwd_params);
+    auto p = new_params<fa_act_bwd_params>();
     p.pre_dtype = p.up_dtype = p.dout_dtype = p.dpre_dtype = p.dup_dtype = p.out_dtype = row_dtype_code("activation: ", pre.scalar_type(), "pre");
     p.bias_dtype = p.dbias_dtype = bias.has_value() ? row_dtype_code("activation: ", bias->scalar_type(), "bias") : p.pre_dtype;
     c10::hip::HIPGuardMasqueradingAsCUDA device_guard(pre.device());
-    auto none = [&] { return at::empty({0}, pre.options()); };  // (one tensor each: outputs of an op do not alias)
     Tensor dpre = at::empty({M, packed ? 2 * H : H}, pre.options());
-    Tensor dup = gated && !packed ? at::empty({M, H}, pre.options()) : none();
-    Tensor dbias = want_dbias ? at::empty({H}, bias.has_value() ? bias->options() : pre.options()) : none();
-    Tensor out = recompute_out ? at::empty({M, H}, pre.options()) : none();
+    Tensor dup = gated && !packed ? at::empty({M, H}, pre.options()) : none(pre.options());
+    Tensor dbias = want_dbias ? at::empty({H}, bias.has_value() ? bias->options() : pre.options()) : none(pre.options());
+    Tensor out = recompute_out ? at::empty({M, H}, pre.options()) : none(pre.options());
+    TORCH_CHECK(M > 0 || !plan, "activation: a plan needs at least one row");
     if (M == 0) {  // (no rows, a zero sum, nothing of ours launched)
         if (want_dbias) dbias.zero_();
         return {dpre, dup, dbias, out};
@@ -2949,22 +2820,8 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> act_bwd_impl(const Tensor &dout, cons
     p.dup = !gated ? nullptr : packed ? dpre.data_ptr() : dup.data_ptr();
     p.recompute_out = recompute_out ? out.data_ptr() : nullptr;
     p.pre_row_stride = pre.stride(0); p.dout_row_stride = dout.stride(0); p.dpre_row_stride = packed ? 2 * H : H; p.out_row_stride = H;
-    const int st = plan ? fa_act_bwd_plan(&p, plan) : fa_act_bwd(&p, current_stream(pre));
-    TORCH_CHECK(st == 0, plan ? "fa_act_bwd_plan" : "fa_act_bwd", " failed (", st, "): ", fa_strerror(st));
+    launch_or_plan("fa_act_bwd", fa_act_bwd, fa_act_bwd_plan, p, plan, pre);
     return {dpre, dup, dbias, out};
-}
-
-std::tuple<Tensor, Tensor, Tensor, Tensor> act_bwd(const Tensor &dout, const Tensor &pre, const OptTensor &up, const OptTensor &bias,
-                                                   int64_t activation, bool want_dbias, bool recompute_out, bool packed) {
-    return act_bwd_impl(dout, pre, up, bias, activation, want_dbias, recompute_out, packed, nullptr);
-}
-
-py::dict act_bwd_plan(const Tensor &dout, const Tensor &pre, const OptTensor &up, const OptTensor &bias, int64_t activation,
-                      bool want_dbias, bool recompute_out, bool packed) {
-    TORCH_CHECK(pre.dim() == 2 && pre.size(0) >= 1, "activation: a plan needs at least one row");
-    fa_act_plan plan{};
-    act_bwd_impl(dout, pre, up, bias, activation, want_dbias, recompute_out, packed, &plan);
-    return act_plan_dict(plan);
 }
 
 // ---- GEMM with a fused bias + activation epilogue (flash_attn.ops.triton.linear; include/fa_gemm_act.h).  Launches on the
@@ -2977,12 +2834,8 @@ void check_gemm_act_matrix(const Tensor &t, const char *name, int64_t rows, int6
 }
 
 py::dict gemm_act_plan_dict(const fa_gemm_act_plan &l) {
-    py::dict d;
-    d["tile_m"] = l.tile_m; d["tile_n"] = l.tile_n; d["tile_k"] = l.tile_k; d["threads"] = l.threads;
-    d["tiles_m"] = l.tiles_m; d["tiles_n"] = l.tiles_n; d["grid_x"] = l.grid_x; d["k_steps"] = l.k_steps;
-    d["ragged_m"] = l.ragged_m; d["ragged_n"] = l.ragged_n; d["ragged_k"] = l.ragged_k; d["group_m"] = l.group_m;
-    d["partial_rows"] = l.partial_rows; d["reduce_grid_x"] = l.reduce_grid_x; d["dtype"] = l.dtype; d["dgrad"] = l.dgrad;
-    return d;
+    return plan_dict(l, {"tile_m", "tile_n", "tile_k", "threads", "tiles_m", "tiles_n", "grid_x", "k_steps", "ragged_m", "ragged_n",
+                         "ragged_k", "group_m", "partial_rows", "reduce_grid_x", "dtype", "dgrad"});
 }
 
 // (out, act_input) = act(x · weightᵀ + bias) and, with save_act_input, its argument; act_input is empty otherwise.  With `plan`
@@ -2999,31 +2852,19 @@ std::tuple<Tensor, Tensor> gemm_act_fwd_impl(const Tensor &x, const Tensor &weig
         TORCH_CHECK(bias->is_cuda() && bias->dim() == 1 && bias->size(0) == N && bias->is_contiguous(), "gemm_act: bias must have shape (N) and be contiguous");
         TORCH_CHECK(bias->scalar_type() == x.scalar_type(), "gemm_act: bias must have the dtype of x");
     }
-    fa_gemm_act_fwd_params p{};
-    p.abi_version = FA_ABI_VERSION;
-    p.struct_size = sizeof(fa_gemm_act_fwd_params);
+    auto p = new_params<fa_gemm_act_fwd_params>();
     p.x_dtype = p.weight_dtype = p.bias_dtype = p.out_dtype = p.act_input_dtype = row_dtype_code("gemm_act: ", x.scalar_type(), "tensors", false);
     c10::hip::HIPGuardMasqueradingAsCUDA device_guard(x.device());
     Tensor out = at::empty({M, N}, x.options());
-    Tensor act_input = save_act_input ? at::empty({M, N}, x.options()) : at::empty({0}, x.options());
-    if (M == 0 && !plan) return {out, act_input};
+    Tensor act_input = save_act_input ? at::empty({M, N}, x.options()) : none(x.options());
+    if (M == 0 && !plan) return {out, act_input};  // (the GEMM alone has a plan without a row, in both directions: no tiles)
     p.x = x.data_ptr(); p.weight = weight.data_ptr(); p.bias = ptr(bias); p.out = out.data_ptr();
     p.act_input = save_act_input ? act_input.data_ptr() : nullptr;
+    if (M == 0) p.x = p.out = weight.data_ptr();  // (a plan: without a row x and out have no storage to point at, and it reads none)
     p.x_row_stride = x.stride(0); p.weight_row_stride = weight.stride(0); p.out_row_stride = N; p.act_input_row_stride = N;
     p.M = M; p.N = (int32_t)N; p.K = (int32_t)K; p.activation = (int32_t)activation;
-    const int st = plan ? fa_gemm_act_fwd_plan(&p, plan) : fa_gemm_act_fwd(&p, current_stream(x));
-    TORCH_CHECK(st == 0, plan ? "fa_gemm_act_fwd_plan" : "fa_gemm_act_fwd", " failed (", st, "): ", fa_strerror(st));
+    launch_or_plan("fa_gemm_act_fwd", fa_gemm_act_fwd, fa_gemm_act_fwd_plan, p, plan, x);
     return {out, act_input};
-}
-
-std::tuple<Tensor, Tensor> gemm_act_fwd(const Tensor &x, const Tensor &weight, const OptTensor &bias, int64_t activation, bool save_act_input) {
-    return gemm_act_fwd_impl(x, weight, bias, activation, save_act_input, nullptr);
-}
-
-py::dict gemm_act_fwd_plan(const Tensor &x, const Tensor &weight, const OptTensor &bias, int64_t activation, bool save_act_input) {
-    fa_gemm_act_plan plan{};
-    gemm_act_fwd_impl(x, weight, bias, activation, save_act_input, &plan);
-    return gemm_act_plan_dict(plan);
 }
 
 // (grad_in, dbias) = (grad_out · weight) ∘ act'(act_input) and, with want_dbias, its column sums; dbias is empty otherwise
@@ -3036,13 +2877,11 @@ std::tuple<Tensor, Tensor> gemm_act_dgrad_impl(const Tensor &grad_out, const Ten
     check_gemm_act_matrix(grad_out, "grad_out", M, K, grad_out);
     check_gemm_act_matrix(weight, "weight", K, N, grad_out);
     if (act_input.has_value()) check_gemm_act_matrix(*act_input, "act_input", M, N, grad_out);
-    fa_gemm_act_dgrad_params p{};
-    p.abi_version = FA_ABI_VERSION;
-    p.struct_size = sizeof(fa_gemm_act_dgrad_params);
+    auto p = new_params<fa_gemm_act_dgrad_params>();
     p.grad_out_dtype = p.weight_dtype = p.act_input_dtype = p.grad_in_dtype = p.dbias_dtype = row_dtype_code("gemm_act: ", grad_out.scalar_type(), "tensors", false);
     c10::hip::HIPGuardMasqueradingAsCUDA device_guard(grad_out.device());
     Tensor grad_in = at::empty({M, N}, grad_out.options());
-    Tensor dbias = want_dbias ? at::empty({N}, grad_out.options()) : at::empty({0}, grad_out.options());
+    Tensor dbias = want_dbias ? at::empty({N}, grad_out.options()) : none(grad_out.options());
     if (M == 0 && !plan) {  // (no rows, a zero sum, nothing of ours launched)
         if (want_dbias) dbias.zero_();
         return {grad_in, dbias};
@@ -3053,22 +2892,40 @@ std::tuple<Tensor, Tensor> gemm_act_dgrad_impl(const Tensor &grad_out, const Ten
     Tensor workspace = at::empty({(int64_t)p.workspace_bytes}, grad_out.options().dtype(at::kByte));
     p.workspace = p.workspace_bytes ? workspace.data_ptr() : nullptr;
     p.grad_out = grad_out.data_ptr(); p.weight = weight.data_ptr(); p.act_input = ptr(act_input); p.grad_in = grad_in.data_ptr();
+    if (M == 0) {  // (a plan, as in the forward: the tensors without a row have no storage to point at, and it reads none)
+        p.grad_out = p.grad_in = weight.data_ptr();
+        if (act_input.has_value()) p.act_input = weight.data_ptr();
+    }
     p.grad_out_row_stride = grad_out.stride(0); p.weight_row_stride = weight.stride(0);
     p.act_input_row_stride = act_input.has_value() ? act_input->stride(0) : N; p.grad_in_row_stride = N;
-    const int st = plan ? fa_gemm_act_dgrad_plan(&p, plan) : fa_gemm_act_dgrad(&p, current_stream(grad_out));
-    TORCH_CHECK(st == 0, plan ? "fa_gemm_act_dgrad_plan" : "fa_gemm_act_dgrad", " failed (", st, "): ", fa_strerror(st));
+    launch_or_plan("fa_gemm_act_dgrad", fa_gemm_act_dgrad, fa_gemm_act_dgrad_plan, p, plan, grad_out);
     return {grad_in, dbias};
 }
 
-std::tuple<Tensor, Tensor> gemm_act_dgrad(const Tensor &grad_out, const Tensor &weight, const OptTensor &act_input, int64_t activation,
-                                          bool want_dbias) {
-    return gemm_act_dgrad_impl(grad_out, weight, act_input, activation, want_dbias, nullptr);
+// ---- the module's two entries of a row operator, both made of its one X_impl(args..., Plan *): `name` forwards args... and no
+// plan; `name_plan` forwards the same args... and a zeroed Plan and returns it as a dict.  The signatures, the py::arg names
+// and the arguments X_impl sees are those of one list, so "the plan of this call" cannot describe another call.
+// (A parameter pack before a trailing parameter is not deduced: A... is the whole list and I... the positions before Plan *)
+template <size_t... I, class R, class... A, class Plan, class... PyArg>
+void def_row_op_at(std::index_sequence<I...>, py::module_ &m, const std::string &name, R (*impl)(A...),
+                   py::dict (*to_dict)(const Plan &), const char *doc, const PyArg &...args) {
+    using List = std::tuple<A...>;
+    static_assert(sizeof...(A) == sizeof...(I) + 1 && std::is_same_v<std::tuple_element_t<sizeof...(I), List>, Plan *>,
+                  "a row operator is X_impl(one argument per py::arg..., Plan *)");
+    m.def(name.c_str(), [impl](std::tuple_element_t<I, List>... a) { return impl(std::forward<std::tuple_element_t<I, List>>(a)..., nullptr); },
+          doc, args...);
+    m.def((name + "_plan").c_str(),
+          [impl, to_dict](std::tuple_element_t<I, List>... a) {
+              Plan plan{};
+              impl(std::forward<std::tuple_element_t<I, List>>(a)..., &plan);
+              return to_dict(plan);
+          },
+          ("the form " + name + " takes with these arguments: its plan struct as a dict, nothing launched").c_str(), args...);
 }
 
-py::dict gemm_act_dgrad_plan(const Tensor &grad_out, const Tensor &weight, const OptTensor &act_input, int64_t activation, bool want_dbias) {
-    fa_gemm_act_plan plan{};
-    gemm_act_dgrad_impl(grad_out, weight, act_input, activation, want_dbias, &plan);
-    return gemm_act_plan_dict(plan);
+template <class Impl, class ToDict, class... PyArg>
+void def_row_op(py::module_ &m, const char *name, Impl impl, ToDict to_dict, const char *doc, const PyArg &...args) {
+    def_row_op_at(std::index_sequence_for<PyArg...>{}, m, name, impl, to_dict, doc, args...);
 }
 
 }  // namespace
@@ -3129,70 +2986,43 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("rotary_emb", &rotary_emb, "rotary embedding layer (apply_rotary): out = rotate(x), conjugate for the gradient", py::arg("x"),
           py::arg("cos"), py::arg("sin"), py::arg("seqlen_offsets") = 0, py::arg("cu_seqlens") = py::none(), py::arg("max_seqlen") = py::none(),
           py::arg("interleaved") = false, py::arg("inplace") = false, py::arg("conjugate") = false);
-    m.def("norm_fwd", &norm_fwd, "fused residual-add + LayerNorm / RMSNorm forward: writes out (and residual_out); returns (mean, rstd)",
-          py::arg("x"), py::arg("weight"), py::arg("bias"), py::arg("residual"), py::arg("rowscale"), py::arg("out"),
-          py::arg("residual_out"), py::arg("eps"), py::arg("zero_centered_weight"), py::arg("is_rms_norm"));
-    m.def("norm_bwd", &norm_bwd, "fused LayerNorm / RMSNorm backward: (dx, dw, db, dresidual_in, y)", py::arg("dy"), py::arg("x"),
-          py::arg("weight"), py::arg("bias"), py::arg("mean"), py::arg("rstd"), py::arg("dresidual"), py::arg("rowscale"),
-          py::arg("has_residual"), py::arg("zero_centered_weight"), py::arg("is_rms_norm"), py::arg("dx_dtype"),
-          py::arg("recompute_output"));
-    m.def("xent_fwd", &xent_fwd, "fused cross-entropy forward: (losses, lse, z_losses)", py::arg("logits"), py::arg("labels"),
-          py::arg("precomputed_lse"), py::arg("smoothing"), py::arg("logit_scale"), py::arg("lse_square_scale"), py::arg("ignore_index"),
-          py::arg("class_start_idx"), py::arg("total_classes"), py::arg("split"));
-    m.def("xent_bwd", &xent_bwd, "fused cross-entropy backward: writes dlogits, which may be logits", py::arg("dloss"), py::arg("logits"),
-          py::arg("labels"), py::arg("lse"), py::arg("dlogits"), py::arg("smoothing"), py::arg("logit_scale"), py::arg("lse_square_scale"),
-          py::arg("ignore_index"), py::arg("class_start_idx"), py::arg("total_classes"));
-    m.def("norm_fwd_plan", &norm_fwd_plan, "the form norm_fwd takes with these arguments: fa_norm_plan as a dict, nothing launched",
-          py::arg("x"), py::arg("weight"), py::arg("bias"), py::arg("residual"), py::arg("rowscale"), py::arg("out"),
-          py::arg("residual_out"), py::arg("eps"), py::arg("zero_centered_weight"), py::arg("is_rms_norm"));
-    m.def("norm_bwd_plan", &norm_bwd_plan, "the form norm_bwd takes with these arguments: fa_norm_plan as a dict, nothing launched",
-          py::arg("dy"), py::arg("x"), py::arg("weight"), py::arg("bias"), py::arg("mean"), py::arg("rstd"), py::arg("dresidual"),
-          py::arg("rowscale"), py::arg("has_residual"), py::arg("zero_centered_weight"), py::arg("is_rms_norm"), py::arg("dx_dtype"),
-          py::arg("recompute_output"));
-    m.def("xent_fwd_plan", &xent_fwd_plan, "the form xent_fwd takes with these arguments: fa_xent_plan as a dict, nothing launched",
-          py::arg("logits"), py::arg("labels"), py::arg("precomputed_lse"), py::arg("smoothing"), py::arg("logit_scale"),
-          py::arg("lse_square_scale"), py::arg("ignore_index"), py::arg("class_start_idx"), py::arg("total_classes"), py::arg("split"));
-    m.def("xent_bwd_plan", &xent_bwd_plan, "the form xent_bwd takes with these arguments: fa_xent_plan as a dict, nothing launched",
-          py::arg("dloss"), py::arg("logits"), py::arg("labels"), py::arg("lse"), py::arg("dlogits"), py::arg("smoothing"),
-          py::arg("logit_scale"), py::arg("lse_square_scale"), py::arg("ignore_index"), py::arg("class_start_idx"),
-          py::arg("total_classes"));
-    m.def("act_fwd", &act_fwd, "fused MLP activation forward: act(pre + bias), or act(pre) * up", py::arg("pre"), py::arg("up"),
-          py::arg("bias"), py::arg("activation"));
-    m.def("act_bwd", &act_bwd, "fused MLP activation backward: (dpre, dup, dbias, out)", py::arg("dout"), py::arg("pre"), py::arg("up"),
-          py::arg("bias"), py::arg("activation"), py::arg("want_dbias"), py::arg("recompute_out"), py::arg("packed"));
-    m.def("act_fwd_plan", &act_fwd_plan, "the form act_fwd takes with these arguments: fa_act_plan as a dict, nothing launched",
-          py::arg("pre"), py::arg("up"), py::arg("bias"), py::arg("activation"));
-    m.def("act_bwd_plan", &act_bwd_plan, "the form act_bwd takes with these arguments: fa_act_plan as a dict, nothing launched",
-          py::arg("dout"), py::arg("pre"), py::arg("up"), py::arg("bias"), py::arg("activation"), py::arg("want_dbias"),
-          py::arg("recompute_out"), py::arg("packed"));
-    m.def("gemm_act_fwd", &gemm_act_fwd, "GEMM with fused bias + activation: (out, act_input) of act(x @ weight.T + bias)", py::arg("x"),
-          py::arg("weight"), py::arg("bias"), py::arg("activation"), py::arg("save_act_input"));
-    m.def("gemm_act_dgrad", &gemm_act_dgrad, "GEMM with the activation's derivative fused: (grad_in, dbias) of (grad_out @ weight) * act'(act_input)",
-          py::arg("grad_out"), py::arg("weight"), py::arg("act_input"), py::arg("activation"), py::arg("want_dbias"));
-    m.def("gemm_act_fwd_plan", &gemm_act_fwd_plan, "the form gemm_act_fwd takes with these arguments: fa_gemm_act_plan as a dict, nothing launched",
-          py::arg("x"), py::arg("weight"), py::arg("bias"), py::arg("activation"), py::arg("save_act_input"));
-    m.def("gemm_act_dgrad_plan", &gemm_act_dgrad_plan, "the form gemm_act_dgrad takes with these arguments: fa_gemm_act_plan as a dict, nothing launched",
-          py::arg("grad_out"), py::arg("weight"), py::arg("act_input"), py::arg("activation"), py::arg("want_dbias"));
-    m.def("dropout_norm_fwd", &dropout_norm_fwd,
-          "fused dropout + residual-add + LayerNorm / RMSNorm forward: (z0, z1, x, dmask0, dmask1, mu, rsigma, rng_state)",
-          py::arg("x0"), py::arg("x1"), py::arg("residual"), py::arg("weight0"), py::arg("bias0"), py::arg("weight1"),
-          py::arg("bias1"), py::arg("rowscale"), py::arg("colscale"), py::arg("p_dropout"), py::arg("eps"), py::arg("residual_in_fp32"),
-          py::arg("is_rms_norm"), py::arg("want_x"), py::arg("return_dmask"));
-    m.def("dropout_norm_bwd", &dropout_norm_bwd,
-          "fused dropout + residual-add + LayerNorm / RMSNorm backward: (dx0, dx1, dresidual, dw0, db0, dw1, db1, dcolscale)",
-          py::arg("dz0"), py::arg("dz1"), py::arg("dx"), py::arg("x"), py::arg("x0"), py::arg("mu"), py::arg("rsigma"),
-          py::arg("weight0"), py::arg("weight1"), py::arg("rowscale"), py::arg("colscale"), py::arg("rng_state"), py::arg("p_dropout"),
-          py::arg("has_x1"), py::arg("has_residual"), py::arg("has_bias"), py::arg("is_rms_norm"), py::arg("x0_dtype"));
-    m.def("dropout_norm_fwd_plan", &dropout_norm_fwd_plan,
-          "the form dropout_norm_fwd takes with these arguments: fa_dropout_norm_plan as a dict, nothing launched",
-          py::arg("x0"), py::arg("x1"), py::arg("residual"), py::arg("weight0"), py::arg("bias0"), py::arg("weight1"),
-          py::arg("bias1"), py::arg("rowscale"), py::arg("colscale"), py::arg("p_dropout"), py::arg("eps"), py::arg("residual_in_fp32"),
-          py::arg("is_rms_norm"), py::arg("want_x"), py::arg("return_dmask"));
-    m.def("dropout_norm_bwd_plan", &dropout_norm_bwd_plan,
-          "the form dropout_norm_bwd takes with these arguments: fa_dropout_norm_plan as a dict, nothing launched",
-          py::arg("dz0"), py::arg("dz1"), py::arg("dx"), py::arg("x"), py::arg("x0"), py::arg("mu"), py::arg("rsigma"),
-          py::arg("weight0"), py::arg("weight1"), py::arg("rowscale"), py::arg("colscale"), py::arg("rng_state"), py::arg("p_dropout"),
-          py::arg("has_x1"), py::arg("has_residual"), py::arg("has_bias"), py::arg("is_rms_norm"), py::arg("x0_dtype"));
+    def_row_op(m, "norm_fwd", norm_fwd_impl, norm_plan_dict,
+               "fused residual-add + LayerNorm / RMSNorm forward: writes out (and residual_out); returns (mean, rstd)", py::arg("x"),
+               py::arg("weight"), py::arg("bias"), py::arg("residual"), py::arg("rowscale"), py::arg("out"), py::arg("residual_out"),
+               py::arg("eps"), py::arg("zero_centered_weight"), py::arg("is_rms_norm"));
+    def_row_op(m, "norm_bwd", norm_bwd_impl, norm_plan_dict, "fused LayerNorm / RMSNorm backward: (dx, dw, db, dresidual_in, y)",
+               py::arg("dy"), py::arg("x"), py::arg("weight"), py::arg("bias"), py::arg("mean"), py::arg("rstd"), py::arg("dresidual"),
+               py::arg("rowscale"), py::arg("has_residual"), py::arg("zero_centered_weight"), py::arg("is_rms_norm"),
+               py::arg("dx_dtype"), py::arg("recompute_output"));
+    def_row_op(m, "xent_fwd", xent_fwd_impl, xent_plan_dict, "fused cross-entropy forward: (losses, lse, z_losses)", py::arg("logits"),
+               py::arg("labels"), py::arg("precomputed_lse"), py::arg("smoothing"), py::arg("logit_scale"), py::arg("lse_square_scale"),
+               py::arg("ignore_index"), py::arg("class_start_idx"), py::arg("total_classes"), py::arg("split"));
+    def_row_op(m, "xent_bwd", xent_bwd_impl, xent_plan_dict, "fused cross-entropy backward: writes dlogits, which may be logits",
+               py::arg("dloss"), py::arg("logits"), py::arg("labels"), py::arg("lse"), py::arg("dlogits"), py::arg("smoothing"),
+               py::arg("logit_scale"), py::arg("lse_square_scale"), py::arg("ignore_index"), py::arg("class_start_idx"),
+               py::arg("total_classes"));
+    def_row_op(m, "act_fwd", act_fwd_impl, act_plan_dict, "fused MLP activation forward: act(pre + bias), or act(pre) * up",
+               py::arg("pre"), py::arg("up"), py::arg("bias"), py::arg("activation"));
+    def_row_op(m, "act_bwd", act_bwd_impl, act_plan_dict, "fused MLP activation backward: (dpre, dup, dbias, out)", py::arg("dout"),
+               py::arg("pre"), py::arg("up"), py::arg("bias"), py::arg("activation"), py::arg("want_dbias"), py::arg("recompute_out"),
+               py::arg("packed"));
+    def_row_op(m, "gemm_act_fwd", gemm_act_fwd_impl, gemm_act_plan_dict,
+               "GEMM with fused bias + activation: (out, act_input) of act(x @ weight.T + bias)", py::arg("x"), py::arg("weight"),
+               py::arg("bias"), py::arg("activation"), py::arg("save_act_input"));
+    def_row_op(m, "gemm_act_dgrad", gemm_act_dgrad_impl, gemm_act_plan_dict,
+               "GEMM with the activation's derivative fused: (grad_in, dbias) of (grad_out @ weight) * act'(act_input)",
+               py::arg("grad_out"), py::arg("weight"), py::arg("act_input"), py::arg("activation"), py::arg("want_dbias"));
+    def_row_op(m, "dropout_norm_fwd", dropout_norm_fwd_impl, dropout_norm_plan_dict,
+               "fused dropout + residual-add + LayerNorm / RMSNorm forward: (z0, z1, x, dmask0, dmask1, mu, rsigma, rng_state)",
+               py::arg("x0"), py::arg("x1"), py::arg("residual"), py::arg("weight0"), py::arg("bias0"), py::arg("weight1"),
+               py::arg("bias1"), py::arg("rowscale"), py::arg("colscale"), py::arg("p_dropout"), py::arg("eps"),
+               py::arg("residual_in_fp32"), py::arg("is_rms_norm"), py::arg("want_x"), py::arg("return_dmask"));
+    def_row_op(m, "dropout_norm_bwd", dropout_norm_bwd_impl, dropout_norm_plan_dict,
+               "fused dropout + residual-add + LayerNorm / RMSNorm backward: (dx0, dx1, dresidual, dw0, db0, dw1, db1, dcolscale)",
+               py::arg("dz0"), py::arg("dz1"), py::arg("dx"), py::arg("x"), py::arg("x0"), py::arg("mu"), py::arg("rsigma"),
+               py::arg("weight0"), py::arg("weight1"), py::arg("rowscale"), py::arg("colscale"), py::arg("rng_state"),
+               py::arg("p_dropout"), py::arg("has_x1"), py::arg("has_residual"), py::arg("has_bias"), py::arg("is_rms_norm"),
+               py::arg("x0_dtype"));
     m.def("sample", &sample, "fused top-k / top-p sampling of a token per row: (token, kept, mass)", py::arg("logits"), py::arg("top_k"),
           py::arg("top_p"), py::arg("temperature"), py::arg("u"), py::arg("rng_state"), py::arg("stats"));
     m.def("sample_filter_", &sample_filter_, "-inf over the entries top-k and top-p remove, in place: (kept, mass)", py::arg("logits"),
