@@ -1,4 +1,4 @@
-"""Build and loading of the native code: libfa_fwd_gfx950.so (the C-ABI of include/fa_fwd.h, fa_bwd.h, fa_rotary.h, fa_norm.h, fa_xent.h, fa_act.h, fa_gemm_act.h, fa_dropout_norm.h and fa_sample.h) and
+"""Build and loading of the native code: libfa_fwd_gfx950.so (the C-ABI of include/fa_fwd.h, fa_bwd.h, fa_rotary.h, fa_norm.h, fa_xent.h, fa_act.h, fa_gemm_act.h, fa_dropout_norm.h, fa_sample.h and fa_spec_sample.h) and
 the compiled host module flash_attn_2_cuda_C (csrc/torch_binding.cpp), which is the only host path of both operator
 surfaces.  Python launches nothing through ctypes: the struct mirrors below serve the ABI tests, `bench.py --variant`
 and the developer tools, which call the C-ABI directly.
@@ -111,6 +111,11 @@ FA_DROPOUT_NORM_RMS = 1
 # every symbol include/fa_sample.h declares (csrc/fa_sample.hip)
 SAMPLE_SYMBOLS = ("fa_sample", "fa_sample_validate", "fa_sample_params_size", "fa_sample_plan")
 FA_SAMPLE_DRAW, FA_SAMPLE_FILTER = 0, 1
+# every symbol include/fa_spec_sample.h declares (csrc/fa_spec_sample.hip)
+SPEC_SAMPLE_SYMBOLS = ("fa_spec_sample", "fa_spec_sample_validate", "fa_spec_sample_params_size", "fa_spec_sample_workspace_size",
+                       "fa_spec_sample_plan")
+FA_SPEC_TOKENS_INT32, FA_SPEC_TOKENS_INT64 = 0, 1
+FA_SPEC_RECORD_BYTES = 24
 
 
 class FaFwdParams(ctypes.Structure):
@@ -415,6 +420,27 @@ class FaSampleForm(ctypes.Structure):
                                               "key_passes", "index_bits", "index_passes", "frac_bits", "grid_x")]
 
 
+class FaSpecSampleParams(ctypes.Structure):
+    """Field-for-field mirror of `struct fa_spec_sample_params` (include/fa_spec_sample.h)."""
+
+    _fields_ = (
+        [("abi_version", ctypes.c_uint32), ("struct_size", ctypes.c_uint32)]
+        + [(n, ctypes.c_void_p) for n in ("logits", "logits_draft", "tokens_draft", "u_acc", "u_res", "rng_state", "workspace", "tokens",
+                                          "num_generated", "p_tok", "q_tok", "accepted")]
+        + [(n, ctypes.c_int64) for n in ("logits_batch_stride", "logits_pos_stride", "draft_batch_stride", "draft_pos_stride",
+                                         "tokens_draft_batch_stride", "workspace_bytes", "B")]
+        + [(n, ctypes.c_int32) for n in ("S", "V", "logits_dtype", "tokens_dtype", "top_k")]
+        + [("top_p", ctypes.c_float), ("temperature", ctypes.c_float), ("reserved", ctypes.c_int32)]
+    )
+
+
+class FaSpecSampleForm(ctypes.Structure):
+    """Field-for-field mirror of `struct fa_spec_sample_form` (include/fa_spec_sample.h): the form a verification call takes."""
+
+    _fields_ = [(n, ctypes.c_int32) for n in ("cw", "threads", "topk", "topp", "k", "key_bits", "key_passes", "index_bits",
+                                              "index_passes", "frac_bits", "grid_a", "grid_b")]
+
+
 class FaActPlan(ctypes.Structure):
     """Field-for-field mirror of `struct fa_act_plan` (include/fa_act.h): the form an activation call takes."""
 
@@ -579,7 +605,7 @@ def build(force=False, verbose=False):
     """Compile csrc/ for gfx950 into the in-tree shared library (hipcc cross-compiles without a GPU)."""
     srcs = [os.path.join(CSRC, f) for f in ("fa_fwd_api.hip", "fa_fwd_kv8_api.hip", "fa_fwd_qv8_api.hip", "fa_fwd_sparse_kv_api.hip", "fa_kvcache_append_kv8.hip",
                                               "fa_kvcache_append_qv8.hip", "fa_bwd_api.hip", "fa_bwd_bs_api.hip", "fa_rotary_emb.hip", "fa_norm.hip", "fa_xent.hip", "fa_act.hip", "fa_gemm_act.hip",
-                                              "fa_dropout_norm.hip", "fa_sample.hip")]
+                                              "fa_dropout_norm.hip", "fa_sample.hip", "fa_spec_sample.hip")]
     if not force and not is_stale():
         return LIB_PATH
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -701,6 +727,8 @@ _PROTOTYPES = {
     "fa_dropout_norm.h": tuple(_unit("fa_dropout_norm", (("fwd", FaDropoutNormFwdParams), ("bwd", FaDropoutNormBwdParams)),
                                      FaDropoutNormPlan, FaDropoutNormBwdParams)),
     "fa_sample.h": tuple(_unit("fa", (("sample", FaSampleParams),), FaSampleForm)),
+    "fa_spec_sample.h": tuple(_unit("fa_spec", (("sample", FaSpecSampleParams),), FaSpecSampleForm))
+    + (("fa_spec_sample_workspace_size", [_I64, _I32], _I64),),
 }
 
 _lib = None
@@ -830,6 +858,10 @@ def new_xent_bwd_params():
 
 def new_sample_params():
     return _new(FaSampleParams, ("logits",), mode=FA_SAMPLE_DRAW, temperature=1.0)
+
+
+def new_spec_sample_params():
+    return _new(FaSpecSampleParams, ("logits",), tokens_dtype=FA_SPEC_TOKENS_INT64, temperature=1.0)
 
 
 def new_act_fwd_params():

@@ -27,6 +27,7 @@
 #include "fa_norm.h"
 #include "fa_xent.h"
 #include "fa_sample.h"
+#include "fa_spec_sample.h"
 #include "fa_act.h"
 #include "fa_gemm_act.h"
 #include "fa_dropout_norm.h"
@@ -2734,6 +2735,91 @@ py::dict sample_plan(const Tensor &logits, int64_t top_k, double top_p, double t
     return sample_plan_dict(plan);
 }
 
+// ---- fused verification of speculative sampling (flash_attn.utils.generation.sample_speculative,
+// flash_attn/utils/generation.py:209-265; include/fa_spec_sample.h).  Launches on the current stream, no synchronisation; the
+// outputs and the records' workspace come from the caching allocator: capturable in a HIP graph.
+py::dict spec_sample_plan_dict(const fa_spec_sample_form &l) {
+    return plan_dict(l, {"cw", "threads", "topk", "topp", "k", "key_bits", "key_passes", "index_bits", "index_passes", "frac_bits",
+                         "grid_a", "grid_b"});
+}
+
+// (tokens (B, S + 1) of the dtype of tokens_draft, num_generated (B) int64, p_tok, q_tok (B, S) fp32, accepted (B, S) int32); the
+// last three are empty without `stats`.  The uniforms are (u_acc, u_res), or `rng_state` = (seed, offset) on the device, or with
+// neither that pair drawn on the device from the default generator
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> sample_speculative_impl(const Tensor &logits, const Tensor &logits_draft,
+                                                                           const Tensor &tokens_draft, int64_t top_k, double top_p,
+                                                                           double temperature, const OptTensor &u_acc, const OptTensor &u_res,
+                                                                           const OptTensor &rng_state, bool stats, fa_spec_sample_form *plan) {
+    const char *op = "sample_speculative: ";
+    TORCH_CHECK(logits.is_cuda() && logits_draft.is_cuda() && tokens_draft.is_cuda(), op, "logits, logits_draft and tokens_draft must be on CUDA");
+    TORCH_CHECK(logits.dim() == 3 && logits.size(1) >= 1, op, "logits must have shape (batch_size, seqlen + 1, vocab_size)");
+    const int64_t B = logits.size(0), S = logits.size(1) - 1, V = logits.size(2);
+    TORCH_CHECK(V >= 1 && V <= std::numeric_limits<int32_t>::max(), op, "logits must have 1 <= vocab_size < 2^31 columns");
+    TORCH_CHECK(B * (2 * S + 1) <= std::numeric_limits<int32_t>::max(), op, "batch_size * (2 seqlen + 1) must be below 2^31");
+    TORCH_CHECK(logits_draft.dim() == 3 && logits_draft.size(0) == B && logits_draft.size(1) == S && logits_draft.size(2) == V, op,
+                "logits_draft must have shape (batch_size, seqlen, vocab_size)");
+    TORCH_CHECK(tokens_draft.dim() == 2 && tokens_draft.size(0) == B && tokens_draft.size(1) == S, op,
+                "tokens_draft must have shape (batch_size, seqlen)");
+    TORCH_CHECK(logits.stride(-1) == 1 || V == 1, op, "logits must have contiguous last dimension");
+    TORCH_CHECK(logits_draft.stride(-1) == 1 || V == 1, op, "logits_draft must have contiguous last dimension");
+    TORCH_CHECK(tokens_draft.stride(-1) == 1 || S <= 1, op, "tokens_draft must have contiguous last dimension");
+    TORCH_CHECK(logits_draft.scalar_type() == logits.scalar_type(), op, "logits_draft must have the dtype of logits");
+    TORCH_CHECK(tokens_draft.scalar_type() == at::kLong || tokens_draft.scalar_type() == at::kInt, op, "tokens_draft must be int32 or int64");
+    TORCH_CHECK(top_k >= 0 && top_k <= std::numeric_limits<int32_t>::max(), op, "top_k must be in [0, 2^31)");
+    TORCH_CHECK(u_acc.has_value() == u_res.has_value(), op, "u_acc and u_res come together");
+    TORCH_CHECK(!(u_res.has_value() && rng_state.has_value()), op, "u and rng_state exclude each other");
+    if (u_res.has_value()) {
+        check_vector(op, *u_res, "u_res", B, "(batch_size)", true);
+        TORCH_CHECK(u_acc->is_cuda() && u_acc->dim() == 2 && u_acc->size(0) == B && u_acc->size(1) == S && u_acc->is_contiguous(), op,
+                    "u_acc must have shape (batch_size, seqlen) and be contiguous");
+        TORCH_CHECK(u_res->scalar_type() == at::kFloat && u_acc->scalar_type() == at::kFloat, op, "u_acc and u_res must be fp32");
+    }
+    if (rng_state.has_value())
+        TORCH_CHECK(rng_state->is_cuda() && rng_state->scalar_type() == at::kLong && rng_state->numel() == 2 && rng_state->is_contiguous(),
+                    op, "rng_state must be two int64 on the device");
+    auto p = new_params<fa_spec_sample_params>();
+    p.logits_dtype = row_dtype_code(op, logits.scalar_type(), "logits");
+    p.tokens_dtype = tokens_draft.scalar_type() == at::kLong ? FA_SPEC_TOKENS_INT64 : FA_SPEC_TOKENS_INT32;
+    c10::hip::HIPGuardMasqueradingAsCUDA device_guard(logits.device());
+    const auto f32 = logits.options().dtype(at::kFloat);
+    Tensor tokens = at::empty({B, S + 1}, tokens_draft.options()), num = at::empty({B}, logits.options().dtype(at::kLong));
+    Tensor p_tok = stats ? at::empty({B, S}, f32) : none(f32), q_tok = stats ? at::empty({B, S}, f32) : none(f32);
+    Tensor accepted = stats ? at::empty({B, S}, logits.options().dtype(at::kInt)) : none(logits.options().dtype(at::kInt));
+    TORCH_CHECK(B > 0 || !plan, op, "a plan needs at least one sequence");
+    if (B == 0) return {tokens, num, p_tok, q_tok, accepted};
+    Tensor state;  // (kept alive to the launch)
+    if (u_res.has_value()) {
+        p.u_res = static_cast<const float *>(u_res->data_ptr());
+        p.u_acc = S > 0 ? static_cast<const float *>(u_acc->data_ptr()) : nullptr;
+    } else if (rng_state.has_value()) {
+        p.rng_state = static_cast<const uint64_t *>(rng_state->data_ptr());
+    } else if (plan) {
+        p.rng_state = reinterpret_cast<const uint64_t *>(uintptr_t(16));  // (a plan reads no memory)
+    } else {
+        state = dropout_state(1.0, c10::nullopt, logits);
+        p.rng_state = static_cast<const uint64_t *>(state.data_ptr());
+    }
+    p.workspace_bytes = fa_spec_sample_workspace_size(B, (int32_t)S);
+    Tensor workspace = at::empty({p.workspace_bytes}, logits.options().dtype(at::kByte));
+    p.workspace = workspace.data_ptr();
+    p.logits = logits.data_ptr();
+    p.logits_draft = S > 0 ? logits_draft.data_ptr() : nullptr;
+    p.tokens_draft = S > 0 ? tokens_draft.data_ptr() : nullptr;
+    p.tokens = tokens.data_ptr();
+    p.num_generated = static_cast<int64_t *>(num.data_ptr());
+    if (stats && S > 0) {
+        p.p_tok = static_cast<float *>(p_tok.data_ptr()); p.q_tok = static_cast<float *>(q_tok.data_ptr());
+        p.accepted = static_cast<int32_t *>(accepted.data_ptr());
+    }
+    p.logits_batch_stride = logits.stride(0); p.logits_pos_stride = logits.stride(1);
+    p.draft_batch_stride = logits_draft.stride(0); p.draft_pos_stride = logits_draft.stride(1);
+    p.tokens_draft_batch_stride = tokens_draft.stride(0);
+    p.B = B; p.S = (int32_t)S; p.V = (int32_t)V;
+    p.top_k = (int32_t)top_k; p.top_p = (float)top_p; p.temperature = (float)temperature;
+    launch_or_plan("fa_spec_sample", fa_spec_sample, fa_spec_sample_plan, p, plan, logits);
+    return {tokens, num, p_tok, q_tok, accepted};
+}
+
 // ---- fused MLP activations (flash_attn.ops.activations, the epilogues of flash_attn.ops.fused_dense; include/fa_act.h).
 // Launches on the current stream, no synchronisation; outputs and the dbias workspace come from the caching allocator:
 // capturable in a HIP graph.
@@ -3023,6 +3109,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
                py::arg("weight0"), py::arg("weight1"), py::arg("rowscale"), py::arg("colscale"), py::arg("rng_state"),
                py::arg("p_dropout"), py::arg("has_x1"), py::arg("has_residual"), py::arg("has_bias"), py::arg("is_rms_norm"),
                py::arg("x0_dtype"));
+    def_row_op(m, "sample_speculative", sample_speculative_impl, spec_sample_plan_dict,
+               "fused verification of draft tokens (speculative sampling): (tokens, num_generated, p_tok, q_tok, accepted)",
+               py::arg("logits"), py::arg("logits_draft"), py::arg("tokens_draft"), py::arg("top_k"), py::arg("top_p"),
+               py::arg("temperature"), py::arg("u_acc"), py::arg("u_res"), py::arg("rng_state"), py::arg("stats"));
     m.def("sample", &sample, "fused top-k / top-p sampling of a token per row: (token, kept, mass)", py::arg("logits"), py::arg("top_k"),
           py::arg("top_p"), py::arg("temperature"), py::arg("u"), py::arg("rng_state"), py::arg("stats"));
     m.def("sample_filter_", &sample_filter_, "-inf over the entries top-k and top-p remove, in place: (kept, mass)", py::arg("logits"),

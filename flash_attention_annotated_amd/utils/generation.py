@@ -4,20 +4,30 @@
     modify_logits_for_top_k_filtering                      :45-48
     modify_logits_for_top_p_filtering                      :53-66
     sample                                                 :69-95
+    sample_speculative                                     :209-265
     sample_ref, filter_ref, uniform_ref          pure torch: the contract of include/fa_sample.h, the CPU oracle
+    sample_speculative_ref                       pure torch: the contract of include/fa_spec_sample.h, the CPU oracle
 
-Same signatures and defaults; `sample` has two keyword-only additions, `generator` and `u`.  Where the reference chains topk,
+Same signatures and defaults; `sample` and `sample_speculative` have two keyword-only additions, `generator` and `u`.  Where the reference chains topk,
 a full sort, softmax, cumsum, scatter, masked_fill and multinomial, CUDA tensors here take one launch of the HIP kernels of
 csrc/fa_sample.hip through `flash_attn_2_cuda_C.sample` / `sample_filter_`, wrapped in torch.library custom ops with fake
 implementations, so torch.compile traces them.  There is no eager fall-back on the device: without the built library the ops
 raise.  CPU tensors take the oracle.
+
+`sample_speculative` is Algorithm 1 of Leviathan et al. (arXiv 2211.17192): it verifies `seqlen` draft tokens against the target
+model's logits, accepts a prefix and resamples the first rejected position from max(p - q, 0).  CUDA tensors take the two
+launches of csrc/fa_spec_sample.hip through `flash_attn_2_cuda_C.sample_speculative`; the rule is written out in
+include/fa_spec_sample.h.  One thing differs from the reference on purpose: the reference ends with
+`tokens[:, first_rejected_idx] = resample`, which for a batch of more than one sequence sets whole columns (every sequence gets
+the other sequences' resampled tokens at their rejection columns).  Here the write is per row, `tokens[b, first_rejected_idx[b]]
+= resample[b]`, which is what the algorithm means; the tokens up to `num_generated` are the valid ones either way.
 
 The rule is written out in include/fa_sample.h.  Unlike the reference's, it leaves no tie open: the token is a function of
 (logits, top_k, top_p, temperature, u).  Without `u` the uniforms come from a counter hash of (row, seed, offset), and (seed,
 offset) are drawn on the device from torch's generator: `torch.manual_seed` reproduces the tokens, nothing synchronises, and a
 HIP graph captures the call.
 
-Not here: the reference's `decode` loop, its CUDA-graph cache (`update_graph_cache`, `capture_graph`), `GenerationMixin` and the
+Not here: the reference's `decode` and `decode_speculative` loops, its CUDA-graph cache (`update_graph_cache`, `capture_graph`), `GenerationMixin` and the
 HuggingFace output classes.
 """
 from dataclasses import dataclass, field
@@ -29,7 +39,7 @@ from torch import Tensor
 from .._lib import binding as _binding
 
 __all__ = ["InferenceParams", "modify_logits_for_top_k_filtering", "modify_logits_for_top_p_filtering", "sample", "sample_ref",
-           "filter_ref", "uniform_ref"]
+           "filter_ref", "uniform_ref", "sample_speculative", "sample_speculative_ref"]
 
 _custom_op = torch.library.custom_op
 _register_fake = torch.library.register_fake
@@ -81,6 +91,30 @@ def _sample_filter_(logits: Tensor, top_k: int, top_p: float) -> None:
 @_register_fake("flash_attn_amd::_sample_filter_")
 def _sample_filter_fake(logits, top_k, top_p):
     return None
+
+
+@_custom_op("flash_attn_amd::_sample_speculative", mutates_args=(), device_types="cuda")
+def _sample_speculative(logits: Tensor, logits_draft: Tensor, tokens_draft: Tensor, top_k: int, top_p: float, temperature: float,
+                        u_acc: Optional[Tensor], u_res: Optional[Tensor], rng_state: Optional[Tensor],
+                        stats: bool) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """(tokens (batch, seqlen + 1) of the dtype of tokens_draft, num_generated (batch,) int64, p_tok, q_tok (batch, seqlen) fp32,
+    accepted (batch, seqlen) int32); the last three are empty without `stats`.  The uniforms are (`u_acc`, `u_res`), else
+    `rng_state` = (seed, offset) on the device; `sample_speculative` always passes one of them: the op has no hidden state."""
+    return _binding().sample_speculative(logits, logits_draft, tokens_draft, top_k, top_p, temperature, u_acc, u_res, rng_state, stats)
+
+
+@_register_fake("flash_attn_amd::_sample_speculative")
+def _sample_speculative_fake(logits, logits_draft, tokens_draft, top_k, top_p, temperature, u_acc, u_res, rng_state, stats):
+    b, s = tokens_draft.shape
+    shape = (b, s) if stats else (0,)
+    return (tokens_draft.new_empty((b, s + 1)), logits.new_empty((b,), dtype=torch.int64), logits.new_empty(shape, dtype=torch.float32),
+            logits.new_empty(shape, dtype=torch.float32), logits.new_empty(shape, dtype=torch.int32))
+
+
+def _plan_sample_speculative(logits, logits_draft, tokens_draft, top_k=1, top_p=0.0, temperature=1.0):
+    """The form `sample_speculative` takes with these tensors, launching nothing: fa_spec_sample_form (include/fa_spec_sample.h)
+    as a dict."""
+    return _binding().sample_speculative_plan(logits, logits_draft, tokens_draft, top_k, top_p, temperature, None, None, None, False)
 
 
 def _plan_sample(logits, top_k=1, top_p=0.0, temperature=1.0, filter=False, stats=False):
@@ -185,6 +219,91 @@ def filter_ref(logits, top_k, top_p, stats=False):
             torch.where(none, torch.zeros_like(p[:, 0]), p.masked_fill(~keep, 0.0).sum(dim=1)), margin)
 
 
+def _kept_probs(rows, top_k, top_p, temperature):
+    """-> (probabilities (N, V) over the kept set of each row of logits (N, V), 0 outside; the top-p margin (N)).  The kept set
+    is what FA_SAMPLE_FILTER leaves of s = rows / temperature: all ties of the k-th value stay"""
+    s = _scaled(rows, temperature)
+    if 0 < top_k < s.shape[1]:  # (what _top_k_members(s, top_k, ties=True) gives: with ties the set needs no order, so no sort)
+        members = s >= torch.topk(s, top_k, dim=1).values[:, -1:]
+    else:
+        members = torch.ones_like(s, dtype=torch.bool)
+    keep, margin = _top_p_keep(_softmax_over(s, members), members, top_p)
+    # e / Z_kept with e = exp(s - m), as the contract has it: two rows whose kept entries have the same s - m in the same
+    # columns get the same probabilities bit for bit, in every precision, and a residual of exactly 0
+    m = s.max(dim=1, keepdim=True).values
+    e = torch.exp(s - torch.where(torch.isinf(m), torch.zeros_like(m), m)).masked_fill(~keep, 0.0)
+    z = e.sum(dim=1, keepdim=True)
+    return e / torch.where(z > 0, z, torch.ones_like(z)), margin
+
+
+def sample_speculative_ref(logits, logits_draft, tokens_draft, top_k, top_p, temperature, u, stats=False):
+    """The contract of include/fa_spec_sample.h in torch, literally and with stable sorts: (tokens (B, S + 1) of the dtype of
+    tokens_draft, num_generated (B,) int64) from logits (B, S + 1, V), logits_draft (B, S, V), tokens_draft (B, S) and the
+    uniforms u = (u_acc (B, S), u_res (B,)); in fp64 where logits are fp64 and in fp32 otherwise.  With `stats`: (tokens,
+    num_generated, p_tok, q_tok, accepted, margin).  margin (B,) is the least distance of a comparison made for the sequence
+    from the value it compares with: the top-p cumulative sums of the rows up to the first rejected position n_b, the acceptance
+    tests up to n_b (|u q - p| relative to max(p, q)), the sum of the residual weights (compared with 0) and the cumulative sums
+    of the resample's weights (compared with u_res times their total).  Sequences where it is small are those whose result
+    rounding may change.  With stats == "positions" two more follow, both (B, S): the lesser top-p margin of the two rows of a
+    position, on which its p_tok and q_tok rest, and the margin of its acceptance test, whatever n_b is."""
+    b, s1, v = logits.shape
+    s = s1 - 1
+    dev = logits.device
+    u_acc, u_res = u
+    P, mp = _kept_probs(logits.reshape(b * s1, v), top_k, top_p, temperature)
+    P, mp = P.view(b, s1, v), mp.view(b, s1)
+    dt = P.dtype
+    inf = torch.tensor(float("inf"), dtype=dt, device=dev)
+    rows = torch.arange(b, device=dev)
+    if s > 0:
+        Q, mq = _kept_probs(logits_draft.reshape(b * s, v), top_k, top_p, temperature)
+        Q, mq = Q.view(b, s, v), mq.view(b, s)
+        x = tokens_draft.long()
+        inside = (x >= 0) & (x < v)  # a token outside [0, V) is rejected, and nothing is read for it
+        xc = x.clamp(0, v - 1)[..., None]
+        zero = torch.zeros((), dtype=dt, device=dev)
+        p_tok = torch.where(inside, P[:, :s].gather(2, xc)[..., 0], zero)
+        q_tok = torch.where(inside, Q.gather(2, xc)[..., 0], zero)
+        lhs = u_acc.to(dt) * q_tok
+        accepted = (lhs <= p_tok) & inside
+        n = torch.where(accepted.all(dim=1), s, (~accepted).int().argmax(dim=1))
+        Pn = P[rows, n]
+        residual = (Pn - Q[rows, n.clamp(max=s - 1)]).clamp_min(0.0)
+        from_p = (n == s) | (residual.sum(dim=1) <= 0)  # no draft row, or no residual weight: p_n itself
+        w = torch.where(from_p[:, None], Pn, residual)
+    else:
+        p_tok = q_tok = torch.zeros(b, 0, dtype=dt, device=dev)
+        accepted = torch.zeros(b, 0, dtype=torch.bool, device=dev)
+        n = torch.zeros(b, dtype=torch.int64, device=dev)
+        w = P[:, 0]
+    total = w.sum(dim=1)
+    cum, at = w.cumsum(dim=1), (u_res.to(dt) * total)[:, None]  # (the share exceeds u where the sum exceeds u * total)
+    positive = w > 0
+    hit = (cum > at) & positive
+    last = v - 1 - positive.flip(1).int().argmax(dim=1)
+    token = torch.where(hit.any(dim=1), hit.int().argmax(dim=1), last)
+    token = torch.where(total > 0, token, torch.zeros_like(token))  # (a target row of nothing but -inf)
+    tokens = torch.cat([tokens_draft, tokens_draft.new_zeros(b, 1)], dim=1)
+    tokens[rows, n] = token.to(tokens.dtype)  # per row; the reference's tokens[:, n] = token writes whole columns
+    if not stats:
+        return tokens, n + 1
+    upto = torch.arange(s1, device=dev)[None, :] <= n[:, None]
+    margin = torch.where(upto, mp, inf).min(dim=1).values
+    margin = torch.minimum(margin, (cum - at).abs().masked_fill(~positive, float("inf")).min(dim=1).values)
+    if s > 0:
+        # the residual weights' sum is compared with 0; a sum of exactly 0 is that of two rows equal in the sense of _kept_probs
+        margin = torch.minimum(margin, torch.where((n < s) & ~from_p, total, inf))
+        margin = torch.minimum(margin, torch.where(upto[:, :s], mq, inf).min(dim=1).values)
+        larger = torch.maximum(p_tok, q_tok)
+        m_acc = torch.where(inside & (larger > 0), (lhs - p_tok).abs() / torch.where(larger > 0, larger, torch.ones_like(larger)), inf)
+        margin = torch.minimum(margin, torch.where(upto[:, :s], m_acc, inf).min(dim=1).values)
+    if stats != "positions":
+        return tokens, n + 1, p_tok, q_tok, accepted.int(), margin
+    if s == 0:
+        return tokens, n + 1, p_tok, q_tok, accepted.int(), margin, p_tok, p_tok
+    return tokens, n + 1, p_tok, q_tok, accepted.int(), margin, torch.minimum(mp[:, :s], mq), m_acc
+
+
 def _lowbias32(x):
     x = x ^ (x >> 16)
     x = (x * 0x7FEB352D) & 0xFFFFFFFF
@@ -254,3 +373,46 @@ def sample(logits, top_k=1, top_p=0.0, temperature=1.0, *, generator=None, u=Non
     if u is None and top_k != 1:  # drawn here, not inside the op: the op is a function of its arguments
         rng_state = torch.randint(-(1 << 62), 1 << 62, (2,), generator=generator, device=logits.device, dtype=torch.int64)
     return _sample(logits, top_k, top_p, temperature, None if top_k == 1 else u, rng_state, False)[0]
+
+
+def sample_speculative(logits, logits_draft, tokens_draft, top_k=1, top_p=0.0, temperature=1.0, *, generator=None, u=None):
+    """Verify `seqlen` draft tokens per sequence against the target model and emit the accepted prefix plus one more token
+    (speculative sampling: Leviathan, Kalman, Matias, arXiv 2211.17192, Algorithm 1).  The rule is in include/fa_spec_sample.h.
+
+    logits        (batch, seqlen + 1, vocab) target logits, fp16 / bf16 / fp32, any batch and position stride
+    logits_draft  (batch, seqlen, vocab) draft logits of the same dtype
+    tokens_draft  (batch, seqlen) int32 or int64: the tokens the draft model proposed
+    top_k, top_p, temperature: as in `sample`, applied to both models' rows with the filter's top-k rule (ties stay)
+    generator     the torch.Generator (of the logits' device) that (seed, offset) are drawn from; default: the device's own
+    u             (u_acc (batch, seqlen), u_res (batch,)) fp32 uniforms in [0, 1) to accept and to resample with, instead of a
+                  generator
+
+    -> (tokens (batch, seqlen + 1) of the dtype of tokens_draft, num_generated (batch,) int64 in [1, seqlen + 1]).  Of row b the
+    first num_generated[b] tokens are valid: the accepted drafts and, at column num_generated[b] - 1, the token drawn there.
+    That token is written to its own row only (the module docstring says how the reference differs).  Nothing is modified.
+    """
+    if logits.dim() != 3 or logits.shape[1] < 1:
+        raise ValueError("logits must have shape (batch, seqlen + 1, vocab)")
+    b, v = logits.shape[0], logits.shape[2]
+    s = logits.shape[1] - 1
+    if tuple(logits_draft.shape) != (b, s, v) or tuple(tokens_draft.shape) != (b, s):
+        raise ValueError(f"logits_draft must have shape {(b, s, v)} and tokens_draft {(b, s)}: got {tuple(logits_draft.shape)} and "
+                         f"{tuple(tokens_draft.shape)}")
+    if tokens_draft.dtype not in (torch.int32, torch.int64):
+        raise TypeError("tokens_draft must be int32 or int64")
+    if top_p > 1.0:
+        raise ValueError("top_p must be at most 1")
+    top_p = max(float(top_p), 0.0)
+    if not logits.is_cuda:
+        if u is None:
+            u = (torch.rand(b, s, generator=generator, device=logits.device), torch.rand(b, generator=generator, device=logits.device))
+        return sample_speculative_ref(logits, logits_draft, tokens_draft, top_k, top_p, temperature, u)
+    if v > 1 and (logits.stride(-1) != 1 or logits_draft.stride(-1) != 1):
+        raise ValueError("logits and logits_draft must have a contiguous last dimension")
+    if s > 1 and tokens_draft.stride(-1) != 1:
+        tokens_draft = tokens_draft.contiguous()
+    rng_state = None
+    if u is None:  # drawn here, not inside the op: the op is a function of its arguments
+        rng_state = torch.randint(-(1 << 62), 1 << 62, (2,), generator=generator, device=logits.device, dtype=torch.int64)
+    u_acc, u_res = u if u is not None else (None, None)
+    return _sample_speculative(logits, logits_draft, tokens_draft, top_k, top_p, temperature, u_acc, u_res, rng_state, False)[:2]
