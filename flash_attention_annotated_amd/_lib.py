@@ -1,4 +1,4 @@
-"""Build and loading of the native code: libfa_fwd_gfx950.so (the C-ABI of include/fa_fwd.h, fa_bwd.h, fa_rotary.h, fa_norm.h, fa_xent.h, fa_act.h, fa_gemm_act.h, fa_dropout_norm.h, fa_sample.h and fa_spec_sample.h) and
+"""Build and loading of the native code: libfa_fwd_gfx950.so (the C-ABI of include/fa_fwd.h, fa_bwd.h, fa_rotary.h, fa_norm.h, fa_xent.h, fa_act.h, fa_gemm_act.h, fa_dropout_norm.h, fa_sample.h, fa_spec_sample.h and fa_block_select.h) and
 the compiled host module flash_attn_2_cuda_C (csrc/torch_binding.cpp), which is the only host path of both operator
 surfaces.  Python launches nothing through ctypes: the struct mirrors below serve the ABI tests, `bench.py --variant`
 and the developer tools, which call the C-ABI directly.
@@ -116,6 +116,12 @@ SPEC_SAMPLE_SYMBOLS = ("fa_spec_sample", "fa_spec_sample_validate", "fa_spec_sam
                        "fa_spec_sample_plan")
 FA_SPEC_TOKENS_INT32, FA_SPEC_TOKENS_INT64 = 0, 1
 FA_SPEC_RECORD_BYTES = 24
+# every symbol include/fa_block_select.h declares (csrc/fa_block_select.hip)
+BLOCK_SELECT_SYMBOLS = tuple(f"fa_block_{unit}{suffix}" for unit in ("summary_update", "select")
+                             for suffix in ("", "_validate", "_workspace_size", "_plan_name")) + (
+    "fa_block_summary_params_size", "fa_block_select_params_size")
+FA_BLOCK_REDUCE_MAX, FA_BLOCK_REDUCE_SUM = 0, 1
+FA_BLOCK_SELECT_MAX_BLOCKS, FA_BLOCK_SELECT_MAX_ROWS = 8192, 128
 
 
 class FaFwdParams(ctypes.Structure):
@@ -441,6 +447,36 @@ class FaSpecSampleForm(ctypes.Structure):
                                               "index_passes", "frac_bits", "grid_a", "grid_b")]
 
 
+class FaBlockSummaryParams(ctypes.Structure):
+    """Field-for-field mirror of `struct fa_block_summary_params` (include/fa_block_select.h)."""
+
+    _fields_ = (
+        [("abi_version", ctypes.c_uint32), ("struct_size", ctypes.c_uint32)]
+        + [(n, ctypes.c_void_p) for n in ("k_summary", "k_cache", "seqlens_old", "seqlens_new", "cache_batch_idx", "page_table",
+                                          "cache_leftpad", "cu_seqlens_k_new")]
+        + [(f"sum_{s}_stride", ctypes.c_int64) for s in ("slot", "block", "side", "head")]
+        + [(f"cache_{s}_stride", ctypes.c_int64) for s in ("batch", "row", "head")]
+        + [("page_table_batch_stride", ctypes.c_int64)]
+        + [(n, ctypes.c_int32) for n in ("b", "capacity", "h_k", "d", "max_blocks", "block_size", "page_size", "max_seqlen_new",
+                                         "summary_dtype", "cache_dtype")]
+    )
+
+
+class FaBlockSelectParams(ctypes.Structure):
+    """Field-for-field mirror of `struct fa_block_select_params` (include/fa_block_select.h)."""
+
+    _fields_ = (
+        [("abi_version", ctypes.c_uint32), ("struct_size", ctypes.c_uint32)]
+        + [(n, ctypes.c_void_p) for n in ("q", "k_summary", "cache_seqlens", "cache_batch_idx", "cu_seqlens_q", "cache_leftpad",
+                                          "scores", "block_cnt", "block_idx")]
+        + [(f"q_{s}_stride", ctypes.c_int64) for s in ("batch", "row", "head")]
+        + [(f"sum_{s}_stride", ctypes.c_int64) for s in ("slot", "block", "side", "head")]
+        + [(f"{t}_{s}_stride", ctypes.c_int64) for t in ("scores", "cnt", "idx") for s in ("batch", "head")]
+        + [(n, ctypes.c_int32) for n in ("b", "s_q", "h", "h_k", "d", "max_blocks", "list_width", "block_size", "num_blocks",
+                                         "sink_blocks", "local_blocks", "group_reduce", "dtype", "reserved")]
+    )
+
+
 class FaActPlan(ctypes.Structure):
     """Field-for-field mirror of `struct fa_act_plan` (include/fa_act.h): the form an activation call takes."""
 
@@ -605,7 +641,7 @@ def build(force=False, verbose=False):
     """Compile csrc/ for gfx950 into the in-tree shared library (hipcc cross-compiles without a GPU)."""
     srcs = [os.path.join(CSRC, f) for f in ("fa_fwd_api.hip", "fa_fwd_kv8_api.hip", "fa_fwd_qv8_api.hip", "fa_fwd_sparse_kv_api.hip", "fa_kvcache_append_kv8.hip",
                                               "fa_kvcache_append_qv8.hip", "fa_bwd_api.hip", "fa_bwd_bs_api.hip", "fa_rotary_emb.hip", "fa_norm.hip", "fa_xent.hip", "fa_act.hip", "fa_gemm_act.hip",
-                                              "fa_dropout_norm.hip", "fa_sample.hip", "fa_spec_sample.hip")]
+                                              "fa_dropout_norm.hip", "fa_sample.hip", "fa_spec_sample.hip", "fa_block_select.hip")]
     if not force and not is_stale():
         return LIB_PATH
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -729,6 +765,11 @@ _PROTOTYPES = {
     "fa_sample.h": tuple(_unit("fa", (("sample", FaSampleParams),), FaSampleForm)),
     "fa_spec_sample.h": tuple(_unit("fa_spec", (("sample", FaSpecSampleParams),), FaSpecSampleForm))
     + (("fa_spec_sample_workspace_size", [_I64, _I32], _I64),),
+    "fa_block_select.h": tuple(
+        row for unit, struct, size in (("fa_block_summary_update", FaBlockSummaryParams, "fa_block_summary_params_size"),
+                                       ("fa_block_select", FaBlockSelectParams, "fa_block_select_params_size"))
+        for row in ((unit, [_P(struct), _VOID], _INT, size, struct), (f"{unit}_validate", [_P(struct)], _INT),
+                    (f"{unit}_workspace_size", [_P(struct)], _I64), (f"{unit}_plan_name", [_P(struct)], _STR))),
 }
 
 _lib = None
@@ -862,6 +903,14 @@ def new_sample_params():
 
 def new_spec_sample_params():
     return _new(FaSpecSampleParams, ("logits",), tokens_dtype=FA_SPEC_TOKENS_INT64, temperature=1.0)
+
+
+def new_block_summary_params():
+    return _new(FaBlockSummaryParams, ("summary", "cache"), block_size=128)
+
+
+def new_block_select_params():
+    return _new(FaBlockSelectParams, dtype=FA_DTYPE_BF16, block_size=128, sink_blocks=1, local_blocks=1)
 
 
 def new_act_fwd_params():

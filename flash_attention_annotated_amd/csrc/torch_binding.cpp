@@ -28,6 +28,7 @@
 #include "fa_xent.h"
 #include "fa_sample.h"
 #include "fa_spec_sample.h"
+#include "fa_block_select.h"
 #include "fa_act.h"
 #include "fa_gemm_act.h"
 #include "fa_dropout_norm.h"
@@ -2820,6 +2821,141 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> sample_speculative_impl(const
     return {tokens, num, p_tok, q_tok, accepted};
 }
 
+// ---- block summaries of the keys and the Quest block selection (hopper_interface.kvcache_block_summary_update /
+// kvcache_select_blocks; include/fa_block_select.h): what produces the lists fwd_kvcache_sparse reads.  Launches on the current
+// stream, nothing is read on the host; every tensor the launches write is an argument: capturable in a HIP graph.  plan: the
+// form the call takes as text, and nothing is launched.
+void check_fill(const Tensor &t, const char *name, int64_t batch_size, const Tensor &on) {
+    TORCH_CHECK(t.scalar_type() == at::kInt && t.is_cuda() && t.device() == on.device() && t.dim() == 1 && t.size(0) == batch_size &&
+                    t.is_contiguous(),
+                name, " must be a contiguous int32 CUDA tensor of shape (batch_size,)");
+}
+
+void check_summary(const Tensor &s, int64_t block_size) {
+    TORCH_CHECK(block_size > 0 && block_size % 64 == 0, "kv_block_size must be a positive multiple of 64, got ", block_size);
+    TORCH_CHECK(s.is_cuda() && s.dim() == 5 && s.size(2) == 2, "k_summary must be a CUDA tensor of shape (slots, max_blocks, 2, num_heads_k, head_size)");
+    TORCH_CHECK(s.scalar_type() == at::kHalf || s.scalar_type() == at::kBFloat16, "k_summary must be fp16 or bf16");
+    TORCH_CHECK(s.stride(-1) == 1, "k_summary must have contiguous last dimension");
+    TORCH_CHECK(s.size(4) <= 128 && s.size(4) % 16 == 0, "k_summary: head_size must be a multiple of 16, at most 128, got ", s.size(4));
+}
+
+std::string block_summary_update_impl(const Tensor &k_summary, const Tensor &k_cache, const OptTensor &seqlens_old,
+                                      const Tensor &seqlens_new, int64_t kv_block_size, c10::optional<int64_t> max_seqlen_new,
+                                      const OptTensor &cache_batch_idx, const OptTensor &page_table, bool plan) {
+    check_summary(k_summary, kv_block_size);
+    const bool fp8 = k_cache.scalar_type() == at::kFloat8_e4m3fn;
+    TORCH_CHECK(fp8 || k_cache.scalar_type() == k_summary.scalar_type(), "k_cache must have the dtype of k_summary or be torch.float8_e4m3fn");
+    TORCH_CHECK(k_cache.is_cuda() && k_cache.device() == k_summary.device() && k_cache.dim() == 4,
+                "k_cache must be a KV cache of shape (batch or num_pages, seqlen or page_size, num_heads_k, head_size) on the device of k_summary");
+    CHECK_LAST_CONTIGUOUS(k_cache, "k_cache must have contiguous last dimension");
+    TORCH_CHECK(k_cache.size(2) == k_summary.size(3) && k_cache.size(3) == k_summary.size(4), "k_summary must have the heads and the head_size of k_cache");
+    const int64_t batch_size = seqlens_new.numel();
+    check_fill(seqlens_new, "seqlens_new", batch_size, k_summary);
+    if (seqlens_old.has_value()) check_fill(*seqlens_old, "seqlens_old", batch_size, k_summary);
+    int64_t capacity;
+    if (page_table.has_value()) {
+        TORCH_CHECK(!cache_batch_idx.has_value(), "Paged KVcache does not support cache_batch_idx");
+        capacity = check_block_table(*page_table, k_cache, batch_size, 1).second * k_cache.size(1);
+        TORCH_CHECK(k_summary.size(0) == batch_size, "k_summary of a paged cache must have one slot per batch entry");
+    } else {
+        capacity = k_cache.size(1);
+        TORCH_CHECK(k_summary.size(0) == k_cache.size(0), "k_summary must have one slot per slot of the cache");
+        if (cache_batch_idx.has_value()) check_fill(*cache_batch_idx, "cache_batch_idx", batch_size, k_summary);
+        else TORCH_CHECK(batch_size <= k_cache.size(0), "the batch must fit the cache without cache_batch_idx");
+    }
+    TORCH_CHECK(capacity <= 0x7fffffff, "the capacity must stay below 2^31");
+    TORCH_CHECK(k_summary.size(1) * kv_block_size >= capacity, "k_summary: max_blocks * kv_block_size must cover the capacity (", capacity, ")");
+    const int64_t bound = max_seqlen_new.value_or(capacity);
+    TORCH_CHECK(bound >= 0, "max_seqlen_new must be non-negative");
+    auto p = new_params<fa_block_summary_params>();
+    p.k_summary = k_summary.data_ptr(); p.k_cache = k_cache.data_ptr();
+    p.seqlens_old = static_cast<const int32_t *>(ptr(seqlens_old));
+    p.seqlens_new = static_cast<const int32_t *>(seqlens_new.data_ptr());
+    p.cache_batch_idx = static_cast<const int32_t *>(ptr(cache_batch_idx));
+    p.page_table = static_cast<const int32_t *>(ptr(page_table));
+    p.sum_slot_stride = k_summary.stride(0); p.sum_block_stride = k_summary.stride(1); p.sum_side_stride = k_summary.stride(2);
+    p.sum_head_stride = k_summary.stride(3);
+    p.cache_batch_stride = k_cache.stride(0); p.cache_row_stride = k_cache.stride(1); p.cache_head_stride = k_cache.stride(2);
+    if (page_table.has_value()) { p.page_table_batch_stride = page_table->stride(0); p.page_size = (int32_t)k_cache.size(1); }
+    p.b = (int32_t)batch_size; p.capacity = (int32_t)capacity; p.h_k = (int32_t)k_cache.size(2); p.d = (int32_t)k_cache.size(3);
+    p.max_blocks = (int32_t)k_summary.size(1); p.block_size = (int32_t)kv_block_size;
+    p.max_seqlen_new = (int32_t)std::min<int64_t>(bound, capacity);
+    p.summary_dtype = dtype_code(k_summary); p.cache_dtype = dtype_code(k_cache);
+    if (plan) {
+        const char *name = fa_block_summary_update_plan_name(&p);
+        TORCH_CHECK(name, "fa_block_summary_update refused (", fa_block_summary_update_validate(&p), "): ",
+                    fa_strerror(fa_block_summary_update_validate(&p)));
+        return name;
+    }
+    c10::hip::HIPGuardMasqueradingAsCUDA device_guard(k_summary.device());
+    const int st = fa_block_summary_update(&p, current_stream(k_summary));
+    TORCH_CHECK(st == 0, "fa_block_summary_update failed (", st, "): ", fa_strerror(st));
+    return {};
+}
+
+std::string block_select_impl(const Tensor &q, const Tensor &k_summary, const Tensor &cache_seqlens, int64_t num_blocks,
+                              int64_t kv_block_size, int64_t sink_blocks, int64_t local_blocks, const std::string &group_reduce,
+                              const OptTensor &cache_batch_idx, const Tensor &kv_block_cnt, const Tensor &kv_block_idx,
+                              const Tensor &scores, bool plan) {
+    check_summary(k_summary, kv_block_size);
+    TORCH_CHECK(q.is_cuda() && q.device() == k_summary.device() && q.scalar_type() == k_summary.scalar_type(),
+                "q must be on the device of k_summary and have its dtype");
+    TORCH_CHECK(q.dim() == 4, "q must have shape (batch_size, seqlen_q, num_heads, head_size); ragged queries are not supported");
+    CHECK_LAST_CONTIGUOUS(q, "q must have contiguous last dimension");
+    const int64_t batch_size = q.size(0), seqlen_q = q.size(1), num_heads = q.size(2), head_size = q.size(3);
+    const int64_t max_blocks = k_summary.size(1), num_heads_k = k_summary.size(3);
+    TORCH_CHECK(head_size == k_summary.size(4), "q must have the head_size of k_summary");
+    TORCH_CHECK(num_heads_k > 0 && num_heads % num_heads_k == 0, "Number of heads in key/value must divide number of heads in query");
+    TORCH_CHECK(seqlen_q >= 1 && seqlen_q * (num_heads / num_heads_k) <= FA_BLOCK_SELECT_MAX_ROWS,
+                "seqlen_q * (num_heads / num_heads_k) must be in [1, ", FA_BLOCK_SELECT_MAX_ROWS, "]");
+    TORCH_CHECK(max_blocks >= 1 && max_blocks <= FA_BLOCK_SELECT_MAX_BLOCKS, "k_summary: max_blocks must be in [1, ", FA_BLOCK_SELECT_MAX_BLOCKS,
+                "], got ", max_blocks);
+    TORCH_CHECK(group_reduce == "max" || group_reduce == "sum", "group_reduce must be \"max\" or \"sum\", got \"", group_reduce, "\"");
+    TORCH_CHECK(sink_blocks >= 0 && local_blocks >= 0 && num_blocks >= sink_blocks + local_blocks,
+                "num_blocks must be at least sink_blocks + local_blocks, both non-negative");
+    check_fill(cache_seqlens, "cache_seqlens", batch_size, q);
+    if (cache_batch_idx.has_value()) check_fill(*cache_batch_idx, "cache_batch_idx", batch_size, q);
+    else TORCH_CHECK(batch_size <= k_summary.size(0), "the batch must fit the slots of k_summary without cache_batch_idx");
+    for (const auto &[t, name] : {std::make_pair(&kv_block_cnt, "kv_block_cnt"), std::make_pair(&kv_block_idx, "kv_block_idx")})
+        TORCH_CHECK(t->scalar_type() == at::kInt && t->is_cuda() && t->device() == q.device(), name, " must be an int32 tensor on the device of q");
+    TORCH_CHECK(kv_block_cnt.sizes() == c10::IntArrayRef({batch_size, num_heads_k}), "kv_block_cnt must have shape (batch_size, num_heads_k)");
+    TORCH_CHECK(kv_block_idx.dim() == 3 && kv_block_idx.size(0) == batch_size && kv_block_idx.size(1) == num_heads_k &&
+                    (kv_block_idx.size(2) == 0 || kv_block_idx.stride(2) == 1),
+                "kv_block_idx must have shape (batch_size, num_heads_k, width) with contiguous last dimension");
+    TORCH_CHECK(kv_block_idx.size(2) >= num_blocks, "kv_block_idx must be at least num_blocks (", num_blocks, ") wide");
+    TORCH_CHECK(scores.scalar_type() == at::kFloat && scores.is_cuda() && scores.device() == q.device() &&
+                    scores.sizes() == c10::IntArrayRef({batch_size, num_heads_k, max_blocks}) && scores.stride(2) == 1,
+                "scores must be fp32 (batch_size, num_heads_k, max_blocks) with contiguous last dimension");
+    const Tensor qc = aligned_or_copy(q);
+    auto p = new_params<fa_block_select_params>();
+    p.q = qc.data_ptr(); p.k_summary = k_summary.data_ptr();
+    p.cache_seqlens = static_cast<const int32_t *>(cache_seqlens.data_ptr());
+    p.cache_batch_idx = static_cast<const int32_t *>(ptr(cache_batch_idx));
+    p.scores = static_cast<float *>(scores.data_ptr());
+    p.block_cnt = static_cast<int32_t *>(kv_block_cnt.data_ptr()); p.block_idx = static_cast<int32_t *>(kv_block_idx.data_ptr());
+    p.q_batch_stride = qc.stride(0); p.q_row_stride = qc.stride(1); p.q_head_stride = qc.stride(2);
+    p.sum_slot_stride = k_summary.stride(0); p.sum_block_stride = k_summary.stride(1); p.sum_side_stride = k_summary.stride(2);
+    p.sum_head_stride = k_summary.stride(3);
+    p.scores_batch_stride = scores.stride(0); p.scores_head_stride = scores.stride(1);
+    p.cnt_batch_stride = kv_block_cnt.stride(0); p.cnt_head_stride = kv_block_cnt.stride(1);
+    p.idx_batch_stride = kv_block_idx.stride(0); p.idx_head_stride = kv_block_idx.stride(1);
+    p.b = (int32_t)batch_size; p.s_q = (int32_t)seqlen_q; p.h = (int32_t)num_heads; p.h_k = (int32_t)num_heads_k; p.d = (int32_t)head_size;
+    p.max_blocks = (int32_t)max_blocks; p.list_width = (int32_t)kv_block_idx.size(2); p.block_size = (int32_t)kv_block_size;
+    p.num_blocks = (int32_t)std::min<int64_t>(num_blocks, 0x7fffffff);
+    p.sink_blocks = (int32_t)std::min<int64_t>(sink_blocks, 0x7fffffff); p.local_blocks = (int32_t)std::min<int64_t>(local_blocks, 0x7fffffff);
+    p.group_reduce = group_reduce == "max" ? FA_BLOCK_REDUCE_MAX : FA_BLOCK_REDUCE_SUM;
+    p.dtype = dtype_code(q);
+    if (plan) {
+        const char *name = fa_block_select_plan_name(&p);
+        TORCH_CHECK(name, "fa_block_select refused (", fa_block_select_validate(&p), "): ", fa_strerror(fa_block_select_validate(&p)));
+        return name;
+    }
+    c10::hip::HIPGuardMasqueradingAsCUDA device_guard(q.device());
+    const int st = fa_block_select(&p, current_stream(q));
+    TORCH_CHECK(st == 0, "fa_block_select failed (", st, "): ", fa_strerror(st));
+    return {};
+}
+
 // ---- fused MLP activations (flash_attn.ops.activations, the epilogues of flash_attn.ops.fused_dense; include/fa_act.h).
 // Launches on the current stream, no synchronisation; outputs and the dbias workspace come from the caching allocator:
 // capturable in a HIP graph.
@@ -3056,6 +3192,31 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("k_descale") = py::none(), py::arg("v_descale") = py::none(), py::arg("softmax_scale") = py::none(),
           py::arg("is_causal") = false, py::arg("window_size_left") = -1, py::arg("window_size_right") = -1, py::arg("softcap") = 0.0,
           py::arg("num_splits") = 0);
+    for (const bool plan : {false, true}) {
+        m.def(plan ? "kvcache_block_summary_update_plan" : "kvcache_block_summary_update",
+              [plan](const Tensor &k_summary, const Tensor &k_cache, const OptTensor &seqlens_old, const Tensor &seqlens_new,
+                     int64_t kv_block_size, c10::optional<int64_t> max_seqlen_new, const OptTensor &cache_batch_idx,
+                     const OptTensor &page_table) {
+                  return block_summary_update_impl(k_summary, k_cache, seqlens_old, seqlens_new, kv_block_size, max_seqlen_new,
+                                                   cache_batch_idx, page_table, plan);
+              },
+              plan ? "the form kvcache_block_summary_update takes with these arguments, as text; nothing is launched"
+                   : "per-block min / max summaries of the keys, updated in place for the rows [seqlens_old, seqlens_new) of a KV cache",
+              py::arg("k_summary"), py::arg("k_cache"), py::arg("seqlens_old"), py::arg("seqlens_new"), py::arg("kv_block_size") = 128,
+              py::arg("max_seqlen_new") = py::none(), py::arg("cache_batch_idx") = py::none(), py::arg("page_table") = py::none());
+        m.def(plan ? "kvcache_select_blocks_plan" : "kvcache_select_blocks",
+              [plan](const Tensor &q, const Tensor &k_summary, const Tensor &cache_seqlens, int64_t num_blocks, int64_t kv_block_size,
+                     int64_t sink_blocks, int64_t local_blocks, const std::string &group_reduce, const OptTensor &cache_batch_idx,
+                     const Tensor &kv_block_cnt, const Tensor &kv_block_idx, const Tensor &scores) {
+                  return block_select_impl(q, k_summary, cache_seqlens, num_blocks, kv_block_size, sink_blocks, local_blocks, group_reduce,
+                                           cache_batch_idx, kv_block_cnt, kv_block_idx, scores, plan);
+              },
+              plan ? "the form kvcache_select_blocks takes with these arguments, as text; nothing is launched"
+                   : "Quest selection of key blocks from the block summaries: writes kv_block_cnt, kv_block_idx and scores",
+              py::arg("q"), py::arg("k_summary"), py::arg("cache_seqlens"), py::arg("num_blocks"), py::arg("kv_block_size"),
+              py::arg("sink_blocks"), py::arg("local_blocks"), py::arg("group_reduce"), py::arg("cache_batch_idx"),
+              py::arg("kv_block_cnt"), py::arg("kv_block_idx"), py::arg("scores"));
+    }
     m.def("fa3_bwd", &fa3_bwd, "FA3 backward pass (flash_attn_3::bwd)");
     m.def("fa3_fwd_combine", &fa3_fwd_combine, "FA3 merge of split-KV partials (flash_attn_3::fwd_combine)");
     m.def("cute_fwd", &cute_fwd, "cute surface forward (flash_attn.cute.interface, with learnable_sink)", py::arg("q"), py::arg("k"),

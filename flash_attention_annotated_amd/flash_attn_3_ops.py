@@ -48,9 +48,20 @@ KVCACHE_SPARSE_SCHEMA = (
     "Tensor? cu_seqlens_q = None, int? max_seqlen_q = None, Tensor? k_descale = None, Tensor? v_descale = None, "
     "float? softmax_scale = None, bool is_causal = False, int window_size_left = -1, int window_size_right = -1, "
     "float softcap = 0.0, int num_splits = 0) -> (Tensor, Tensor)")
+# ... nor what produces its lists (include/fa_block_select.h): the block summaries of the keys, updated in place on append, and
+# the Quest selection.  Every tensor the launches write is a mutated argument and nothing is returned, so that a traced graph
+# holds no alias of an input; hopper_interface allocates what the caller does not give
+BLOCK_SUMMARY_SCHEMA = (
+    "kvcache_block_summary_update(Tensor(a!) k_summary, Tensor k_cache, Tensor? seqlens_old, Tensor seqlens_new, "
+    "int kv_block_size = 128, int? max_seqlen_new = None, Tensor? cache_batch_idx = None, Tensor? page_table = None) -> ()")
+SELECT_BLOCKS_SCHEMA = (
+    "kvcache_select_blocks(Tensor q, Tensor k_summary, Tensor cache_seqlens, int num_blocks, int kv_block_size, int sink_blocks, "
+    "int local_blocks, str group_reduce, Tensor? cache_batch_idx, Tensor(a!) kv_block_cnt, Tensor(b!) kv_block_idx, "
+    "Tensor(c!) scores) -> ()")
 
 _ops = torch.library.Library("flash_attn_3", "DEF")
-for _schema in (FWD_SCHEMA, BWD_SCHEMA, COMBINE_SCHEMA, METADATA_SCHEMA, APPEND_FP8_SCHEMA, KVCACHE_SPARSE_SCHEMA):
+for _schema in (FWD_SCHEMA, BWD_SCHEMA, COMBINE_SCHEMA, METADATA_SCHEMA, APPEND_FP8_SCHEMA, KVCACHE_SPARSE_SCHEMA, BLOCK_SUMMARY_SCHEMA,
+                SELECT_BLOCKS_SCHEMA):
     _ops.define(_schema)
 
 
@@ -118,6 +129,24 @@ def _fwd_kvcache_sparse_meta(q, k_cache, v_cache, kv_block_cnt, kv_block_idx, kv
     return torch.empty_like(q), q.new_empty(lse_shape, dtype=torch.float32)
 
 
+def _kvcache_block_summary_update(k_summary, k_cache, seqlens_old, seqlens_new, kv_block_size=128, max_seqlen_new=None,
+                                  cache_batch_idx=None, page_table=None):
+    """The binding's kvcache_block_summary_update (fa_block_summary_update): one launch, in place."""
+    _lib.binding().kvcache_block_summary_update(k_summary, k_cache, seqlens_old, seqlens_new, kv_block_size, max_seqlen_new,
+                                                cache_batch_idx, page_table)
+
+
+def _kvcache_select_blocks(q, k_summary, cache_seqlens, num_blocks, kv_block_size, sink_blocks, local_blocks, group_reduce,
+                           cache_batch_idx, kv_block_cnt, kv_block_idx, scores):
+    """The binding's kvcache_select_blocks (fa_block_select): the scoring launch and the selection launch, no host sync."""
+    _lib.binding().kvcache_select_blocks(q, k_summary, cache_seqlens, num_blocks, kv_block_size, sink_blocks, local_blocks,
+                                         group_reduce, cache_batch_idx, kv_block_cnt, kv_block_idx, scores)
+
+
+def _nothing(*args, **kwargs):
+    """The fake of an op that only mutates its arguments."""
+
+
 def _get_scheduler_metadata(batch_size, max_seqlen_q, max_seqlen_k, num_heads, num_heads_k, headdim, headdim_v, qkv_dtype,
                             seqused_k, cu_seqlens_q=None, cu_seqlens_k=None, cu_seqlens_k_new=None, seqused_q=None,
                             leftpad_k=None, page_size=None, max_seqlen_k_new=0, is_causal=False, window_size_left=-1,
@@ -153,3 +182,7 @@ _ops.impl("kvcache_append_fp8", _kvcache_append_fp8, "CUDA")
 _ops.impl("kvcache_append_fp8", _kvcache_append_fp8_meta, "Meta")
 _ops.impl("fwd_kvcache_sparse", _fwd_kvcache_sparse, "CUDA")
 _ops.impl("fwd_kvcache_sparse", _fwd_kvcache_sparse_meta, "Meta")
+_ops.impl("kvcache_block_summary_update", _kvcache_block_summary_update, "CUDA")
+_ops.impl("kvcache_block_summary_update", _nothing, "Meta")
+_ops.impl("kvcache_select_blocks", _kvcache_select_blocks, "CUDA")
+_ops.impl("kvcache_select_blocks", _nothing, "Meta")

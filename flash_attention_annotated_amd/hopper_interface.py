@@ -2,6 +2,8 @@
 (`flash_attn_func` :507-585, `flash_attn_varlen_func` :588-633) on top of `torch.ops.flash_attn_3.fwd`
 (flash_attn_3_ops.py registers the library with the reference's schema; :10-14 of the reference does the same lookup).
 This is the surface that carries fp8 e4m3 inputs with per-(batch, kv head) descales (BASELINE config 5)."""
+from typing import NamedTuple
+
 import torch
 
 from . import flash_attn_3_ops  # noqa: F401  (defines torch.ops.flash_attn_3)
@@ -289,6 +291,149 @@ def kvcache_append_fp8(k_cache, v_cache, k, v, cache_seqlens, k_descale, v_desca
     return torch.ops.flash_attn_3.kvcache_append_fp8(k_cache, v_cache, k, v, cache_seqlens, k_descale, v_descale,
                                                      cu_seqlens_k_new, max_seqlen_k_new, cache_batch_idx, page_table,
                                                      rotary_cos, rotary_sin, rotary_seqlens, rotary_interleaved)
+
+
+def kvcache_block_summary_update(k_summary, k_cache, seqlens_old, seqlens_new, *, kv_block_size=128, max_seqlen_new=None,
+                                 cache_batch_idx=None, page_table=None):
+    """Keeps the per-block summaries of the keys of a KV cache up to date: what kvcache_select_blocks ranks blocks by.  Not in the
+    reference.  One launch, in place, no host sync (HIP-graph capturable); include/fa_block_select.h pins the rule.
+    k_summary: (slots, max_blocks, 2, nheads_k, headdim) fp16 / bf16 (the dtype of the queries), last dimension contiguous;
+    [s, j, 0] / [s, j, 1] are the channel-wise minimum / maximum over the filled rows of block j (kv_block_size rows, a multiple of
+    64) of slot s.  Dense cache: slots = k_cache.shape[0] and entry b uses slot cache_batch_idx[b] (or b).  Paged cache: slots = the
+    batch, blocks are logical (any page size; a block may span pages).  max_blocks * kv_block_size must cover the capacity.
+    k_cache: of k_summary's dtype, or torch.float8_e4m3fn, whose stored values count as they are (no descale: a positive factor
+    per (batch, head) changes no ranking).  Call it after the append: it reads what attention will read, rotated and quantised.
+    seqlens_old / seqlens_new: int32 (batch,) on the device; rows [old, new) were just written.  seqlens_old=None: 0, a rebuild.
+    A block that begins inside the range is set from its rows, the block the range begins in is merged (min / max) with what is
+    stored, blocks outside the range are not written.  max_seqlen_new: a host bound of new - old that sizes the grid (None: the
+    capacity; give 1 in a decode step).  Minimum and maximum are exact: the result equals block_summary_ref bit for bit.
+    CPU tensors take block_summary_ref.  Returns k_summary."""
+    if not k_summary.is_cuda:
+        return block_summary_ref(k_summary, k_cache, seqlens_old, seqlens_new, kv_block_size=kv_block_size,
+                                 cache_batch_idx=cache_batch_idx, page_table=page_table)
+    torch.ops.flash_attn_3.kvcache_block_summary_update(k_summary, k_cache, seqlens_old, seqlens_new, kv_block_size, max_seqlen_new,
+                                                        cache_batch_idx, page_table)
+    return k_summary
+
+
+def kvcache_select_blocks(q, k_summary, cache_seqlens, num_blocks, *, kv_block_size=128, sink_blocks=1, local_blocks=1,
+                          group_reduce="max", cache_batch_idx=None, kv_block_cnt=None, kv_block_idx=None, return_scores=False):
+    """Quest selection (arXiv 2406.10774) of the key blocks a decode or verify step reads: the lists flash_attn_with_kvcache_sparse
+    takes, from the queries and the summaries kvcache_block_summary_update keeps.  Not in the reference.  Two launches (scores split
+    over chunks of blocks, so that batch 1 fills the chip; then one workgroup per (batch, kv head) selects), no host sync, no sort;
+    HIP-graph capturable with kv_block_cnt / kv_block_idx given.  include/fa_block_select.h pins the rule.
+    q: (batch, seqlen_q, nheads, headdim) fp16 / bf16, headdim <= 128 and a multiple of 16, seqlen_q * nheads / nheads_k <= 128.
+    With B = kv_block_size, sk(b) = cache_seqlens[b] clamped to max_blocks * B and n = ceil(sk / B): the score of block j for kv
+    head hk is U = sum_c max(q_c * min_c, q_c * max_c) (an upper bound of q . k over the block's keys; fp32, unscaled) reduced over
+    the seqlen_q * nheads / nheads_k query rows of hk by group_reduce, "max" or "sum".  K = min(num_blocks, n) blocks are chosen:
+    the first sink_blocks and the last local_blocks always, the rest by the highest score, equal scores by the lower index.
+    Returns (kv_block_cnt, kv_block_idx): int32 (batch, nheads_k) = K and (batch, nheads_k, width >= num_blocks) holding the chosen
+    blocks ascending, then -1; fresh tensors (width = num_blocks) or the buffers given.  return_scores: also scores, fp32
+    (batch, nheads_k, max_blocks), -inf at and behind n.  max_blocks <= 8192.  CPU tensors take select_blocks_ref.
+    Cost, measured on MI355X: tools/block_select_bench.py, profiles/block_select.jsonl, DESIGN.md section 4.29."""
+    b, h_k, max_blocks = q.shape[0], k_summary.shape[3], k_summary.shape[1]
+    if kv_block_cnt is None:
+        kv_block_cnt = torch.empty((b, h_k), dtype=torch.int32, device=q.device)
+    if kv_block_idx is None:
+        kv_block_idx = torch.empty((b, h_k, num_blocks), dtype=torch.int32, device=q.device)
+    if not q.is_cuda:
+        ref = select_blocks_ref(q, k_summary, cache_seqlens, num_blocks, kv_block_size=kv_block_size, sink_blocks=sink_blocks,
+                                local_blocks=local_blocks, group_reduce=group_reduce, cache_batch_idx=cache_batch_idx,
+                                width=kv_block_idx.shape[2])
+        kv_block_cnt.copy_(ref.cnt), kv_block_idx.copy_(ref.idx)
+        return (kv_block_cnt, kv_block_idx, ref.scores.float()) if return_scores else (kv_block_cnt, kv_block_idx)
+    scores = torch.empty((b, h_k, max_blocks), dtype=torch.float32, device=q.device)
+    torch.ops.flash_attn_3.kvcache_select_blocks(q, k_summary, cache_seqlens, num_blocks, kv_block_size, sink_blocks, local_blocks,
+                                                 group_reduce, cache_batch_idx, kv_block_cnt, kv_block_idx, scores)
+    return (kv_block_cnt, kv_block_idx, scores) if return_scores else (kv_block_cnt, kv_block_idx)
+
+
+def _check_blocks(kv_block_size, num_blocks=0, sink_blocks=0, local_blocks=0, group_reduce="max"):
+    assert kv_block_size > 0 and kv_block_size % 64 == 0, "kv_block_size must be a positive multiple of 64"
+    assert group_reduce in ("max", "sum"), 'group_reduce must be "max" or "sum"'
+    assert sink_blocks >= 0 and local_blocks >= 0 and num_blocks >= sink_blocks + local_blocks, \
+        "num_blocks must be at least sink_blocks + local_blocks"
+
+
+def block_summary_ref(k_summary, k_cache, seqlens_old, seqlens_new, *, kv_block_size=128, cache_batch_idx=None, page_table=None):
+    """The oracle of kvcache_block_summary_update in plain torch, on any device, in place: a host loop over batch entries and
+    blocks.  Minimum and maximum are exact, so the kernel's result equals this one."""
+    _check_blocks(kv_block_size)
+    B, paged = kv_block_size, page_table is not None
+    capacity = page_table.shape[1] * k_cache.shape[1] if paged else k_cache.shape[1]
+    assert k_summary.shape[1] * B >= capacity, "k_summary: max_blocks * kv_block_size must cover the capacity"
+    raw = k_cache.view(torch.uint8) if k_cache.dtype == torch.float8_e4m3fn else k_cache  # (indexing needs no fp8 kernel)
+    for b in range(seqlens_new.numel()):
+        new = min(max(int(seqlens_new[b]), 0), capacity)
+        old = 0 if seqlens_old is None else min(max(int(seqlens_old[b]), 0), new)
+        slot = b if paged or cache_batch_idx is None else int(cache_batch_idx[b])
+        for j in range(old // B, -(-new // B) if old < new else 0):
+            lo, hi = max(old, j * B), min(new, (j + 1) * B)
+            if paged:
+                t = torch.arange(lo, hi, device=k_cache.device)
+                rows = raw[page_table[b].long()[t // k_cache.shape[1]], t % k_cache.shape[1]]
+            else:
+                rows = raw[slot, lo:hi]
+            rows = rows.view(k_cache.dtype).float()  # every fp16 / bf16 / e4m3 value is an fp32 value
+            mn, mx = rows.amin(0), rows.amax(0)
+            if old > j * B:
+                mn, mx = torch.minimum(mn, k_summary[slot, j, 0].float()), torch.maximum(mx, k_summary[slot, j, 1].float())
+            k_summary[slot, j, 0], k_summary[slot, j, 1] = mn.to(k_summary.dtype), mx.to(k_summary.dtype)
+    return k_summary
+
+
+class SelectedBlocks(NamedTuple):
+    """select_blocks_ref's result.  U, A: fp64 (batch, nheads_k, rows, max_blocks), rows = seqlen_q * nheads / nheads_k in the
+    order (query row, head of the group): the Quest bound of every row, and A = sum_c max(|q_c min_c|, |q_c max_c|), what an fp32
+    sum of the terms of U errs in proportion to; both 0 at and behind n.  scores: fp64 (batch, nheads_k, max_blocks), U reduced
+    over the rows, -inf at and behind n."""
+    cnt: torch.Tensor
+    idx: torch.Tensor
+    scores: torch.Tensor
+    U: torch.Tensor
+    A: torch.Tensor
+
+
+def select_blocks_ref(q, k_summary, cache_seqlens, num_blocks, *, kv_block_size=128, sink_blocks=1, local_blocks=1,
+                      group_reduce="max", cache_batch_idx=None, width=None):
+    """The oracle of kvcache_select_blocks in plain torch, on any device: U in fp64, the choice by a stable sort."""
+    _check_blocks(kv_block_size, num_blocks, sink_blocks, local_blocks, group_reduce)
+    b, s_q, h, d = q.shape
+    max_blocks, h_k = k_summary.shape[1], k_summary.shape[3]
+    g = h // h_k
+    assert h % h_k == 0 and 1 <= s_q * g <= 128 and d == k_summary.shape[4]
+    width = num_blocks if width is None else width
+    assert width >= num_blocks, "the list must be at least num_blocks wide"
+    dev = q.device
+    cnt = torch.zeros((b, h_k), dtype=torch.int32, device=dev)
+    idx = torch.full((b, h_k, width), -1, dtype=torch.int32, device=dev)
+    scores = torch.full((b, h_k, max_blocks), float("-inf"), dtype=torch.float64, device=dev)
+    U = torch.zeros((b, h_k, s_q * g, max_blocks), dtype=torch.float64, device=dev)
+    A = torch.zeros_like(U)
+    for i in range(b):
+        sk = min(max(int(cache_seqlens[i]), 0), max_blocks * kv_block_size)
+        n = -(-sk // kv_block_size)
+        if n == 0:
+            continue
+        slot = i if cache_batch_idx is None else int(cache_batch_idx[i])
+        K = min(num_blocks, n)
+        forced = torch.zeros(n, dtype=torch.bool, device=dev)
+        forced[:min(sink_blocks, n)] = True
+        forced[max(n - local_blocks, 0):] = True
+        for hk in range(h_k):
+            rows = q[i, :, hk * g:(hk + 1) * g].reshape(s_q * g, 1, d).double()
+            lo, hi = k_summary[slot, :n, 0, hk].double(), k_summary[slot, :n, 1, hk].double()  # (n, d)
+            U[i, hk, :, :n] = torch.maximum(rows * lo, rows * hi).sum(-1)
+            A[i, hk, :, :n] = torch.maximum((rows * lo).abs(), (rows * hi).abs()).sum(-1)
+            u = U[i, hk, :, :n].amax(0) if group_reduce == "max" else U[i, hk, :, :n].sum(0)
+            scores[i, hk, :n] = u
+            free = (~forced).nonzero().flatten()
+            order = torch.sort(-u[free], stable=True).indices[:K - int(forced.sum())]  # equal scores: the lower index first
+            chosen = forced.clone()
+            chosen[free[order]] = True
+            cnt[i, hk] = K
+            idx[i, hk, :K] = chosen.nonzero().flatten().int()
+    return SelectedBlocks(cnt, idx, scores, U, A)
 
 
 def get_scheduler_metadata(batch_size, max_seqlen_q, max_seqlen_k, num_heads_q, num_heads_kv, headdim, cache_seqlens,
