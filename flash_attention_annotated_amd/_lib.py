@@ -1,4 +1,4 @@
-"""Build and loading of the native code: libfa_fwd_gfx950.so (the C-ABI of include/fa_fwd.h, fa_bwd.h, fa_rotary.h, fa_norm.h, fa_xent.h, fa_act.h, fa_gemm_act.h, fa_dropout_norm.h, fa_sample.h, fa_spec_sample.h and fa_block_select.h) and
+"""Build and loading of the native code: libfa_fwd_gfx950.so (the C-ABI of include/fa_fwd.h, fa_bwd.h, fa_rotary.h, fa_norm.h, fa_xent.h, fa_act.h, fa_gemm_act.h, fa_dropout_norm.h, fa_sample.h, fa_spec_sample.h, fa_block_select.h and fa_block_pattern.h) and
 the compiled host module flash_attn_2_cuda_C (csrc/torch_binding.cpp), which is the only host path of both operator
 surfaces.  Python launches nothing through ctypes: the struct mirrors below serve the ABI tests, `bench.py --variant`
 and the developer tools, which call the C-ABI directly.
@@ -122,6 +122,10 @@ BLOCK_SELECT_SYMBOLS = tuple(f"fa_block_{unit}{suffix}" for unit in ("summary_up
     "fa_block_summary_params_size", "fa_block_select_params_size")
 FA_BLOCK_REDUCE_MAX, FA_BLOCK_REDUCE_SUM = 0, 1
 FA_BLOCK_SELECT_MAX_BLOCKS, FA_BLOCK_SELECT_MAX_ROWS = 8192, 128
+# every symbol include/fa_block_pattern.h declares (csrc/fa_block_pattern.hip)
+BLOCK_PATTERN_SYMBOLS = ("fa_block_pattern", "fa_block_pattern_validate", "fa_block_pattern_workspace_size", "fa_block_pattern_plan_name",
+                         "fa_block_pattern_params_size")
+FA_BLOCK_PATTERN_BLOCK, FA_BLOCK_PATTERN_MAX_BLOCKS = 128, 8192
 
 
 class FaFwdParams(ctypes.Structure):
@@ -477,6 +481,20 @@ class FaBlockSelectParams(ctypes.Structure):
     )
 
 
+class FaBlockPatternParams(ctypes.Structure):
+    """Field-for-field mirror of `struct fa_block_pattern_params` (include/fa_block_pattern.h)."""
+
+    _fields_ = (
+        [("abi_version", ctypes.c_uint32), ("struct_size", ctypes.c_uint32)]
+        + [(n, ctypes.c_void_p) for n in ("q", "k", "full_block_cnt", "full_block_idx", "mask_block_cnt", "mask_block_idx", "q_block_cnt",
+                                          "q_block_idx", "scores", "workspace")]
+        + [("workspace_bytes", ctypes.c_uint64)]
+        + [(f"{t}_{s}_stride", ctypes.c_int64) for t in ("q", "k") for s in ("batch", "row", "head")]
+        + [(n, ctypes.c_int32) for n in ("b", "sq", "sk", "h", "h_k", "d", "num_blocks", "sink_blocks", "local_blocks", "is_causal",
+                                         "window_size_left", "window_size_right", "dtype", "reserved")]
+    )
+
+
 class FaActPlan(ctypes.Structure):
     """Field-for-field mirror of `struct fa_act_plan` (include/fa_act.h): the form an activation call takes."""
 
@@ -641,7 +659,8 @@ def build(force=False, verbose=False):
     """Compile csrc/ for gfx950 into the in-tree shared library (hipcc cross-compiles without a GPU)."""
     srcs = [os.path.join(CSRC, f) for f in ("fa_fwd_api.hip", "fa_fwd_kv8_api.hip", "fa_fwd_qv8_api.hip", "fa_fwd_sparse_kv_api.hip", "fa_kvcache_append_kv8.hip",
                                               "fa_kvcache_append_qv8.hip", "fa_bwd_api.hip", "fa_bwd_bs_api.hip", "fa_rotary_emb.hip", "fa_norm.hip", "fa_xent.hip", "fa_act.hip", "fa_gemm_act.hip",
-                                              "fa_dropout_norm.hip", "fa_sample.hip", "fa_spec_sample.hip", "fa_block_select.hip")]
+                                              "fa_dropout_norm.hip", "fa_sample.hip", "fa_spec_sample.hip", "fa_block_select.hip",
+                                              "fa_block_pattern.hip")]
     if not force and not is_stale():
         return LIB_PATH
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -770,6 +789,12 @@ _PROTOTYPES = {
                                        ("fa_block_select", FaBlockSelectParams, "fa_block_select_params_size"))
         for row in ((unit, [_P(struct), _VOID], _INT, size, struct), (f"{unit}_validate", [_P(struct)], _INT),
                     (f"{unit}_workspace_size", [_P(struct)], _I64), (f"{unit}_plan_name", [_P(struct)], _STR))),
+    "fa_block_pattern.h": (
+        ("fa_block_pattern", [_P(FaBlockPatternParams), _VOID], _INT, "fa_block_pattern_params_size", FaBlockPatternParams),
+        ("fa_block_pattern_validate", [_P(FaBlockPatternParams)], _INT),
+        ("fa_block_pattern_workspace_size", [_P(FaBlockPatternParams)], _I64),
+        ("fa_block_pattern_plan_name", [_P(FaBlockPatternParams)], _STR),
+    ),
 }
 
 _lib = None
@@ -911,6 +936,10 @@ def new_block_summary_params():
 
 def new_block_select_params():
     return _new(FaBlockSelectParams, dtype=FA_DTYPE_BF16, block_size=128, sink_blocks=1, local_blocks=1)
+
+
+def new_block_pattern_params():
+    return _new(FaBlockPatternParams, dtype=FA_DTYPE_BF16, sink_blocks=1, local_blocks=1, window_size_left=-1, window_size_right=-1)
 
 
 def new_act_fwd_params():

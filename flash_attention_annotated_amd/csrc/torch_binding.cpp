@@ -29,6 +29,7 @@
 #include "fa_sample.h"
 #include "fa_spec_sample.h"
 #include "fa_block_select.h"
+#include "fa_block_pattern.h"
 #include "fa_act.h"
 #include "fa_gemm_act.h"
 #include "fa_dropout_norm.h"
@@ -2956,6 +2957,64 @@ std::string block_select_impl(const Tensor &q, const Tensor &k_summary, const Te
     return {};
 }
 
+// ---- block-sparse prefill patterns (cute_interface.block_sparse_select; include/fa_block_pattern.h): what produces the lists
+// cute_fwd_block_sparse / cute_bwd_block_sparse read.  Launches on the current stream, nothing is read on the host; every tensor
+// the launches write, the workspace included, is an argument: capturable in a HIP graph.  The params of a call, checked; the
+// three entries below launch with them, name their form, or size the workspace (`workspace` absent).
+fa_block_pattern_params block_pattern_params(const Tensor &q, const Tensor &k, const Tensor &full_block_cnt, const Tensor &full_block_idx,
+                                             const Tensor &mask_block_cnt, const Tensor &mask_block_idx, const OptTensor &q_block_cnt,
+                                             const OptTensor &q_block_idx, const OptTensor &scores, const OptTensor &workspace,
+                                             int64_t num_blocks, bool causal, int64_t window_left, int64_t window_right,
+                                             int64_t sink_blocks, int64_t local_blocks) {
+    TORCH_CHECK(q.is_cuda() && k.is_cuda() && k.device() == q.device(), "q and k must be on the same CUDA device");
+    TORCH_CHECK(q.scalar_type() == at::kHalf || q.scalar_type() == at::kBFloat16, "q must be fp16 or bf16");
+    TORCH_CHECK(k.scalar_type() == q.scalar_type(), "q and k must have the same dtype");
+    TORCH_CHECK(q.dim() == 4 && k.dim() == 4, "q must have shape (batch_size, seqlen_q, num_heads, head_size), k (batch_size, seqlen_k, num_heads_k, head_size)");
+    CHECK_LAST_CONTIGUOUS(q, "q must have contiguous last dimension");
+    CHECK_LAST_CONTIGUOUS(k, "k must have contiguous last dimension");
+    const int64_t b = q.size(0), sq = q.size(1), h = q.size(2), d = q.size(3), sk = k.size(1), h_k = k.size(2);
+    TORCH_CHECK(k.size(0) == b && k.size(3) == d, "k must have the batch size and the head_size of q");
+    TORCH_CHECK(d <= 128 && d % 16 == 0, "head_size must be a multiple of 16, at most 128, got ", d);
+    TORCH_CHECK(h_k > 0 && h % h_k == 0, "Number of heads in key/value must divide number of heads in query");
+    TORCH_CHECK(sq >= 1 && sk >= 1 && sq <= 0x7fffff00, "seqlen_q and seqlen_k must be at least 1, seqlen_q below 2^31 - 256");
+    const int64_t B = FA_BLOCK_PATTERN_BLOCK, nm = (sq + B - 1) / B, nk = (sk + B - 1) / B;
+    TORCH_CHECK(nk <= FA_BLOCK_PATTERN_MAX_BLOCKS, "seqlen_k must give at most ", FA_BLOCK_PATTERN_MAX_BLOCKS, " key blocks, got ", nk);
+    TORCH_CHECK(sink_blocks >= 0 && local_blocks >= 0 && num_blocks >= sink_blocks + local_blocks,
+                "num_blocks must be at least sink_blocks + local_blocks, both non-negative");
+    const auto check_out = [&](const Tensor &t, const char *name, at::ScalarType dtype, c10::IntArrayRef shape) {
+        TORCH_CHECK(t.scalar_type() == dtype && t.is_cuda() && t.device() == q.device() && t.sizes() == shape && t.is_contiguous(), name,
+                    " must be a contiguous ", dtype, " tensor of shape ", shape, " on the device of q");
+    };
+    check_out(full_block_cnt, "full_block_cnt", at::kInt, {b, h, nm});
+    check_out(full_block_idx, "full_block_idx", at::kInt, {b, h, nm, nk});
+    check_out(mask_block_cnt, "mask_block_cnt", at::kInt, {b, h, nm});
+    check_out(mask_block_idx, "mask_block_idx", at::kInt, {b, h, nm, nk});
+    TORCH_CHECK(q_block_cnt.has_value() == q_block_idx.has_value(), "q_block_cnt and q_block_idx must be specified together");
+    if (q_block_cnt.has_value()) {
+        check_out(*q_block_cnt, "q_block_cnt", at::kInt, {b, h, nk});
+        check_out(*q_block_idx, "q_block_idx", at::kInt, {b, h, nk, nm});
+    }
+    if (scores.has_value()) check_out(*scores, "scores", at::kFloat, {b, h, nm, nk});
+    if (workspace.has_value())
+        TORCH_CHECK(workspace->is_cuda() && workspace->device() == q.device() && workspace->is_contiguous() && workspace->scalar_type() == at::kByte,
+                    "workspace must be a contiguous uint8 tensor on the device of q");
+    const auto clamp32 = [](int64_t v) { return (int32_t)std::max<int64_t>(std::min<int64_t>(v, 0x7fffffff), -1); };
+    auto p = new_params<fa_block_pattern_params>();
+    p.q = q.data_ptr(); p.k = k.data_ptr();
+    p.full_block_cnt = static_cast<int32_t *>(full_block_cnt.data_ptr()); p.full_block_idx = static_cast<int32_t *>(full_block_idx.data_ptr());
+    p.mask_block_cnt = static_cast<int32_t *>(mask_block_cnt.data_ptr()); p.mask_block_idx = static_cast<int32_t *>(mask_block_idx.data_ptr());
+    p.q_block_cnt = static_cast<int32_t *>(ptr(q_block_cnt)); p.q_block_idx = static_cast<int32_t *>(ptr(q_block_idx));
+    p.scores = static_cast<float *>(ptr(scores));
+    p.workspace = ptr(workspace); p.workspace_bytes = workspace.has_value() ? (uint64_t)workspace->numel() : 0;
+    p.q_batch_stride = q.stride(0); p.q_row_stride = q.stride(1); p.q_head_stride = q.stride(2);
+    p.k_batch_stride = k.stride(0); p.k_row_stride = k.stride(1); p.k_head_stride = k.stride(2);
+    p.b = (int32_t)b; p.sq = (int32_t)sq; p.sk = (int32_t)sk; p.h = (int32_t)h; p.h_k = (int32_t)h_k; p.d = (int32_t)d;
+    p.num_blocks = clamp32(num_blocks); p.sink_blocks = clamp32(sink_blocks); p.local_blocks = clamp32(local_blocks);
+    p.is_causal = causal; p.window_size_left = clamp32(window_left); p.window_size_right = clamp32(window_right);
+    p.dtype = dtype_code(q);
+    return p;
+}
+
 // ---- fused MLP activations (flash_attn.ops.activations, the epilogues of flash_attn.ops.fused_dense; include/fa_act.h).
 // Launches on the current stream, no synchronisation; outputs and the dbias workspace come from the caching allocator:
 // capturable in a HIP graph.
@@ -3216,6 +3275,34 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
               py::arg("q"), py::arg("k_summary"), py::arg("cache_seqlens"), py::arg("num_blocks"), py::arg("kv_block_size"),
               py::arg("sink_blocks"), py::arg("local_blocks"), py::arg("group_reduce"), py::arg("cache_batch_idx"),
               py::arg("kv_block_cnt"), py::arg("kv_block_idx"), py::arg("scores"));
+    }
+    for (const int mode : {0, 1, 2}) {  // the launch, the form, the workspace's bytes
+        m.def(mode == 0 ? "block_pattern" : mode == 1 ? "block_pattern_plan" : "block_pattern_workspace_size",
+              [mode](const Tensor &q, const Tensor &k, const Tensor &full_block_cnt, const Tensor &full_block_idx, const Tensor &mask_block_cnt,
+                     const Tensor &mask_block_idx, const OptTensor &q_block_cnt, const OptTensor &q_block_idx, const OptTensor &scores,
+                     const OptTensor &workspace, int64_t num_blocks, bool causal, int64_t window_size_left, int64_t window_size_right,
+                     int64_t sink_blocks, int64_t local_blocks) -> py::object {
+                  const auto p = block_pattern_params(q, k, full_block_cnt, full_block_idx, mask_block_cnt, mask_block_idx, q_block_cnt, q_block_idx,
+                                                      scores, workspace, num_blocks, causal, window_size_left, window_size_right, sink_blocks,
+                                                      local_blocks);
+                  if (mode == 0) {
+                      c10::hip::HIPGuardMasqueradingAsCUDA device_guard(q.device());
+                      const int st = fa_block_pattern(&p, current_stream(q));
+                      TORCH_CHECK(st == 0, "fa_block_pattern failed (", st, "): ", fa_strerror(st));
+                      return py::none();
+                  }
+                  const int64_t bytes = fa_block_pattern_workspace_size(&p);
+                  TORCH_CHECK(bytes >= 0, "fa_block_pattern refused (", bytes, "): ", fa_strerror((int)bytes));
+                  if (mode == 2) return py::int_(bytes);
+                  return py::str(fa_block_pattern_plan_name(&p));
+              },
+              mode == 0   ? "block-sparse pattern from pooled q . k scores: writes the forward lists, and the key-major lists and scores where given"
+              : mode == 1 ? "the form block_pattern takes with these arguments, as text; nothing is launched"
+                          : "the bytes of the workspace block_pattern needs with these arguments; nothing is launched",
+              py::arg("q"), py::arg("k"), py::arg("full_block_cnt"), py::arg("full_block_idx"), py::arg("mask_block_cnt"),
+              py::arg("mask_block_idx"), py::arg("q_block_cnt"), py::arg("q_block_idx"), py::arg("scores"), py::arg("workspace"),
+              py::arg("num_blocks"), py::arg("causal"), py::arg("window_size_left"), py::arg("window_size_right"), py::arg("sink_blocks"),
+              py::arg("local_blocks"));
     }
     m.def("fa3_bwd", &fa3_bwd, "FA3 backward pass (flash_attn_3::bwd)");
     m.def("fa3_fwd_combine", &fa3_fwd_combine, "FA3 merge of split-KV partials (flash_attn_3::fwd_combine)");

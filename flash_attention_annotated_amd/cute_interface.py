@@ -10,15 +10,20 @@ mask_block_idx`, 128 x 128 blocks; include/fa_fwd.h fa_fwd_block_sparse has the 
 `block_sparse_from_mask` makes them from a block mask.  That route is differentiable when the caller also passes the
 key-major lists `q_block_cnt / q_block_idx` the dK / dV sweep walks (`block_sparse_bwd_lists` makes them from the four
 forward lists; include/fa_bwd.h fa_bwd_block_sparse; head dims up to 128); without them the backward raises.
-`mask_mod`, a CuTe-DSL callable, is not supported.
+`mask_mod`, a CuTe-DSL callable, is not supported.  `block_sparse_select` makes all six lists on the device from q and k: pooled
+block scores, a top-k per query block with forced sink and local blocks (include/fa_block_pattern.h, DESIGN.md §4.30);
+`block_sparse_select_ref` is its torch oracle.
 
 Routing is the FA3 surface's (csrc/torch_binding.cpp cute_fwd -> fa3_fwd_core): dense and varlen calls, decode steps over
 a paged cache with their GQA swap and split-KV, ragged queries over a cache.  The cute signatures carry no max_seqlen:
 the grid is made from bounds the shapes give (total_q / total_k), nothing is read from the device.
 """
+import collections
 import math
+from typing import Tuple
 
 import torch
+from torch import Tensor
 
 from . import _lib
 
@@ -88,6 +93,140 @@ def block_sparse_bwd_lists(full_block_cnt, full_block_idx, mask_block_cnt, mask_
         rows = rows[..., :nk]
         visited = rows if visited is None else visited | rows
     return block_sparse_from_mask(visited.transpose(-1, -2))[2:]
+
+
+BlockSparseSelection = collections.namedtuple(
+    "BlockSparseSelection", "full_block_cnt full_block_idx mask_block_cnt mask_block_idx q_block_cnt q_block_idx scores")
+
+
+def _selection_outputs(q, k, with_bwd_lists, return_scores):
+    """The seven tensors of a selection, uninitialised; what was not asked for is an empty tensor."""
+    b, sq, h = q.shape[:3]
+    nm, nk = (sq + 127) // 128, (k.shape[1] + 127) // 128
+    new = lambda *shape, dtype=torch.int32: q.new_empty(shape, dtype=dtype)  # noqa: E731
+    return (new(b, h, nm), new(b, h, nm, nk), new(b, h, nm), new(b, h, nm, nk),
+            new(b, h, nk) if with_bwd_lists else new(0), new(b, h, nk, nm) if with_bwd_lists else new(0),
+            new(b, h, nm, nk, dtype=torch.float32) if return_scores else new(0, dtype=torch.float32))
+
+
+@torch.library.custom_op("flash_attn_amd::_block_sparse_select", mutates_args=(), device_types="cuda")
+def _block_sparse_select(q: Tensor, k: Tensor, num_blocks: int, causal: bool, window_left: int, window_right: int, sink_blocks: int,
+                         local_blocks: int, with_bwd_lists: bool, return_scores: bool) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """The binding's block_pattern (fa_block_pattern): two launches, three with the key-major lists; no host sync.  The outputs
+    and the workspace are allocated here, from the caching allocator."""
+    outs = _selection_outputs(q, k, with_bwd_lists, return_scores)
+    args = (q, k, *outs[:4], *(outs[4:6] if with_bwd_lists else (None, None)), outs[6] if return_scores else None)
+    rule = (num_blocks, causal, window_left, window_right, sink_blocks, local_blocks)
+    workspace = q.new_empty(_lib.binding().block_pattern_workspace_size(*args, None, *rule), dtype=torch.uint8)
+    _lib.binding().block_pattern(*args, workspace, *rule)
+    return outs
+
+
+@torch.library.register_fake("flash_attn_amd::_block_sparse_select")
+def _block_sparse_select_fake(q, k, num_blocks, causal, window_left, window_right, sink_blocks, local_blocks, with_bwd_lists,
+                              return_scores):
+    return _selection_outputs(q, k, with_bwd_lists, return_scores)
+
+
+def _check_select(q, k, num_blocks, sink_blocks, local_blocks):
+    assert q.dim() == 4 and k.dim() == 4, "q must have shape (batch_size, seqlen_q, num_head, head_dim), k (batch_size, seqlen_k, num_head_kv, head_dim)"
+    assert q.shape[0] == k.shape[0] and q.shape[3] == k.shape[3], "q and k must have the same batch size and head_dim"
+    assert q.shape[2] % k.shape[2] == 0, "num_head must be divisible by num_head_kv"
+    assert q.shape[1] >= 1 and k.shape[1] >= 1, "seqlen_q and seqlen_k must be at least 1"
+    if sink_blocks < 0 or local_blocks < 0 or num_blocks < sink_blocks + local_blocks:
+        raise ValueError(f"num_blocks ({num_blocks}) must be at least sink_blocks + local_blocks ({sink_blocks} + {local_blocks}), "
+                         f"both non-negative")
+
+
+def block_sparse_select(q, k, num_blocks, *, causal=False, window_size=(None, None), sink_blocks=1, local_blocks=1,
+                        with_bwd_lists=False, return_scores=False):
+    """Block top-k pattern for block-sparse attention, made on the device -- the producer of the lists flash_attn_func takes.
+    Not in the reference.  include/fa_block_pattern.h pins the rule; in short, with 128 x 128 blocks: the score of (query block
+    m, key block n) is the dot product of the fp32 sum of the rows of m and the fp32 mean of the keys of n (no softmax scale);
+    of the key blocks the call's own mask (causal / window_size, bottom-right aligned) lets query block m see, the first
+    sink_blocks and the last local_blocks are always chosen, and the other num_blocks - sink_blocks - local_blocks places go to
+    the highest scores, ties to the lower index.  A chosen block goes to the full list when the mask hides nothing in it and all
+    128 of its keys exist (a ragged last key block never does), else to the mask list.
+
+    q (b, sq, h, d), k (b, sk, h_k, d): fp16 / bf16, any strides with a unit last one, d a multiple of 16, at most 128;
+    at most 8192 key blocks.  Returns a BlockSparseSelection: full_block_cnt (b, h, nm), full_block_idx (b, h, nm, nk),
+    mask_block_cnt, mask_block_idx of the same shapes; with with_bwd_lists q_block_cnt (b, h, nk), q_block_idx (b, h, nk, nm),
+    the key-major lists the backward needs (else None); with return_scores scores (b, h, nm, nk) fp32, -inf at blocks the mask
+    hides (else None).  Lists are int32, indices ascending, tails zero: the conventions of block_sparse_from_mask /
+    block_sparse_bwd_lists, so `flash_attn_func(q, k, v, causal=..., window_size=..., **sel._asdict())` without `scores` runs.
+    Two launches (three with the key-major lists), nothing is read on the host, HIP-graph capturable; given the scores the
+    lists equal block_sparse_select_ref(..., scores=scores) bit for bit.  CPU tensors take block_sparse_select_ref.
+    Cost, measured on one MI355X at hq32 / hkv8, d128, bf16, causal, num_blocks = nk / 8 (tools/block_pattern_bench.py,
+    profiles/block_pattern.jsonl): 0.09 - 0.30 x the torch composition of the same rule, and 0.22 - 0.26 x
+    (s 8192), 0.07 - 0.08 x (s 32768), 0.03 x (s 131072) of the sparse forward the lists feed."""
+    _check_select(q, k, num_blocks, sink_blocks, local_blocks)
+    if not q.is_cuda:
+        return block_sparse_select_ref(q, k, num_blocks, causal=causal, window_size=window_size, sink_blocks=sink_blocks,
+                                       local_blocks=local_blocks, with_bwd_lists=with_bwd_lists, return_scores=return_scores)
+    assert q.dtype in (torch.float16, torch.bfloat16) and k.dtype == q.dtype, "q and k must be float16 or bfloat16, of one dtype"
+    q, k = maybe_contiguous(q), maybe_contiguous(k)
+    left, right = _window(window_size)
+    outs = torch.ops.flash_attn_amd._block_sparse_select(q, k, num_blocks, causal, left, right, sink_blocks, local_blocks,
+                                                         with_bwd_lists, return_scores)
+    return BlockSparseSelection(*outs[:4], *(outs[4:6] if with_bwd_lists else (None, None)), outs[6] if return_scores else None)
+
+
+def block_sparse_visibility(sq, sk, causal=False, window_size=(None, None), device=None):
+    """(visible, full), bool (nm, nk): whether query block m sees key block n under the call's own mask (some existing pair is
+    visible), and whether the block is full (every existing pair is visible and all 128 keys exist).  Pure torch."""
+    left, right = _window(window_size)
+    if causal:
+        right = 0
+    nm, nk, off = (sq + 127) // 128, (sk + 127) // 128, sk - sq
+    i_lo = torch.arange(nm, device=device)[:, None] * 128
+    i_hi = torch.clamp(i_lo + 128, max=sq) - 1
+    j_lo = torch.arange(nk, device=device)[None, :] * 128
+    j_hi = torch.clamp(j_lo + 128, max=sk) - 1
+    visible = torch.ones(nm, nk, dtype=torch.bool, device=device)
+    full = (j_lo + 128 <= sk).expand(nm, nk).clone()
+    if right >= 0:
+        visible &= j_lo <= i_hi + off + right
+        full &= j_hi <= i_lo + off + right
+    if left >= 0:
+        visible &= j_hi >= i_lo + off - left
+        full &= j_lo >= i_hi + off - left
+    return visible, full & visible
+
+
+def block_sparse_select_ref(q, k, num_blocks, *, causal=False, window_size=(None, None), sink_blocks=1, local_blocks=1,
+                            with_bwd_lists=False, return_scores=False, scores=None):
+    """The oracle of block_sparse_select in plain torch, on any device and of any floating dtype: sums and scores in fp64 where
+    q is fp64, else in fp32 (in torch's order, not the kernels').  scores: optional (b, h, nm, nk), taken in place of the pooled
+    scores (what the mask hides is ignored): given the kernels' scores, the lists are the kernels' bit for bit."""
+    _check_select(q, k, num_blocks, sink_blocks, local_blocks)
+    b, sq, h, d = q.shape
+    sk, h_k = k.shape[1:3]
+    nm, nk = (sq + 127) // 128, (sk + 127) // 128
+    visible, full = block_sparse_visibility(sq, sk, causal, window_size, q.device)
+    if scores is None:
+        ct = torch.float64 if q.dtype == torch.float64 else torch.float32
+
+        def pooled(x, n):  # (b, blocks, heads, d): the sums over the rows that exist
+            x = torch.nn.functional.pad(x.to(ct), (0, 0, 0, 0, 0, n * 128 - x.shape[1]))
+            return x.view(b, n, 128, x.shape[2], d).sum(2)
+
+        count = torch.clamp(sk - torch.arange(nk, device=q.device) * 128, max=128).to(ct)
+        qs, km = pooled(q, nm), pooled(k, nk) * (1 / count)[None, :, None, None]
+        scores = torch.einsum("bmhc,bnhc->bhmn", qs, km.repeat_interleave(h // h_k, dim=2))
+    u = torch.where(visible, scores + 0.0, torch.full_like(scores, float("-inf")))  # (-0 equals +0)
+    # the places of a row: forced blocks, then the other visible ones by score (a stable sort: of equal ones the lower index),
+    # then what the mask hides
+    seen = visible.cumsum(-1)
+    cnt = seen[:, -1:]
+    forced = visible & ((seen - 1 < sink_blocks) | (cnt - seen < local_blocks))
+    by_score = torch.sort(u, dim=-1, descending=True, stable=True).indices
+    rank = torch.where(forced, 0, torch.where(visible, 1, 2)).expand(b, h, nm, nk)
+    order = by_score.gather(-1, torch.sort(rank.gather(-1, by_score), dim=-1, stable=True).indices)
+    place = torch.empty_like(order).scatter_(-1, order, torch.arange(nk, device=q.device).expand(b, h, nm, nk))
+    chosen = place < torch.clamp(cnt, max=num_blocks)
+    lists = block_sparse_from_mask(chosen, full.expand(b, h, nm, nk))
+    key_lists = block_sparse_bwd_lists(*lists) if with_bwd_lists else (None, None)
+    return BlockSparseSelection(*lists, *key_lists, u if return_scores else None)
 
 
 def _check_key_lists(q, k, q_block_cnt, q_block_idx):
