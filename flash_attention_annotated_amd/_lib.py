@@ -70,6 +70,11 @@ EXPORTED_SYMBOLS = (
     "fa_fwd_sparse_kv_workspace_size",
     "fa_fwd_sparse_kv_plan_name",
     "fa_sparse_kv_params_size",
+    "fa_fwd_tree",
+    "fa_fwd_tree_validate",
+    "fa_fwd_tree_workspace_size",
+    "fa_fwd_tree_plan_name",
+    "fa_tree_params_size",
     # include/fa_bwd.h
     "fa_bwd",
     "fa_bwd_validate",
@@ -607,6 +612,13 @@ class FaSparseKvParams(ctypes.Structure):
     )
 
 
+class FaTreeParams(ctypes.Structure):
+    """Field-for-field mirror of `struct fa_tree_params` (include/fa_fwd.h)."""
+
+    _fields_ = [("abi_version", ctypes.c_uint32), ("struct_size", ctypes.c_uint32), ("tree_mask", ctypes.c_void_p),
+                ("batch_stride", ctypes.c_int64), ("row_stride", ctypes.c_int64), ("fp8_cache", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
 class FaBlockSparseBwdParams(ctypes.Structure):
     """Field-for-field mirror of `struct fa_block_sparse_bwd_params` (include/fa_bwd.h)."""
 
@@ -657,7 +669,7 @@ def is_stale():
 
 def build(force=False, verbose=False):
     """Compile csrc/ for gfx950 into the in-tree shared library (hipcc cross-compiles without a GPU)."""
-    srcs = [os.path.join(CSRC, f) for f in ("fa_fwd_api.hip", "fa_fwd_kv8_api.hip", "fa_fwd_qv8_api.hip", "fa_fwd_sparse_kv_api.hip", "fa_kvcache_append_kv8.hip",
+    srcs = [os.path.join(CSRC, f) for f in ("fa_fwd_api.hip", "fa_fwd_kv8_api.hip", "fa_fwd_qv8_api.hip", "fa_fwd_sparse_kv_api.hip", "fa_fwd_tree_api.hip", "fa_kvcache_append_kv8.hip",
                                               "fa_kvcache_append_qv8.hip", "fa_bwd_api.hip", "fa_bwd_bs_api.hip", "fa_rotary_emb.hip", "fa_norm.hip", "fa_xent.hip", "fa_act.hip", "fa_gemm_act.hip",
                                               "fa_dropout_norm.hip", "fa_sample.hip", "fa_spec_sample.hip", "fa_block_select.hip",
                                               "fa_block_pattern.hip")]
@@ -719,6 +731,7 @@ def _unit(prefix, structs, plan_struct, workspace_struct=None):
 
 _FWD, _BWD, _KV8 = _P(FaFwdParams), _P(FaBwdParams), _P(FaKvcacheAppendKv8Params)
 _SINK, _BS, _BS_BWD, _SPARSE_KV = _P(FaSinkParams), _P(FaBlockSparseParams), _P(FaBlockSparseBwdParams), _P(FaSparseKvParams)
+_TREE = _P(FaTreeParams)
 # every C entry point, by header: (symbol, argtypes, restype); a row whose params struct has a `*_params_size` also names that
 # symbol and the mirror it is checked against (the `*_params_size` symbols themselves are all `uint32_t (void)`)
 _PROTOTYPES = {
@@ -759,6 +772,10 @@ _PROTOTYPES = {
         ("fa_fwd_sparse_kv_validate", [_FWD, _SPARSE_KV], _INT),
         ("fa_fwd_sparse_kv_workspace_size", [_FWD, _SPARSE_KV], _I64),
         ("fa_fwd_sparse_kv_plan_name", [_FWD, _SPARSE_KV, _I32], _STR),
+        ("fa_fwd_tree", [_FWD, _TREE, _VOID], _INT, "fa_tree_params_size", FaTreeParams),
+        ("fa_fwd_tree_validate", [_FWD, _TREE], _INT),
+        ("fa_fwd_tree_workspace_size", [_FWD, _TREE], _I64),
+        ("fa_fwd_tree_plan_name", [_FWD, _TREE, _I32], _STR),
     ),
     "fa_bwd.h": (
         ("fa_bwd", [_BWD, _VOID], _INT, "fa_bwd_params_size", FaBwdParams),
@@ -884,6 +901,10 @@ def new_block_sparse_bwd_params():
 
 def new_sparse_kv_params():
     return _new(FaSparseKvParams, block_size=128)
+
+
+def new_tree_params():
+    return _new(FaTreeParams, row_stride=1)
 
 
 def new_sink_grad_params():

@@ -221,6 +221,38 @@ inline int validate_fp8_cache(const fa_fwd_params *p, Fp8CachePlan (*plan)(const
     return sp.splits > 1 && workspace_short(p, sp.total) ? FA_ERR_WORKSPACE : FA_OK;
 }
 
+// The same for the routes that also read a 16-bit cache through the packed-row body (fa_fwd_sparse_kv, fa_fwd_tree):
+// validate_fp8_cache's rules with k / v strides in 16-bit elements and no descales; the workspace check is the route's
+inline int validate_16bit_cache(const fa_fwd_params *p) {
+    const bool ragged = p->cu_seqlens_q != nullptr;
+    if (ragged && (!p->seqused_k || p->total_q < 0)) return FA_ERR_BAD_SHAPE;
+    const bool empty = p->seqlen_q == 0 || (ragged && p->total_q == 0);
+    if (!empty) {
+        if (!p->q || !p->o || !p->softmax_lse) return FA_ERR_NULL_POINTER;
+        if (p->seqlen_k > 0 && (!p->k || !p->v)) return FA_ERR_NULL_POINTER;
+    }
+    const int64_t strides[] = {p->q_row_stride, p->q_head_stride, p->o_row_stride, p->o_head_stride,
+                               ragged ? 0 : p->q_batch_stride, ragged ? 0 : p->o_batch_stride,
+                               p->k_row_stride, p->k_head_stride, p->k_batch_stride, p->v_row_stride, p->v_head_stride, p->v_batch_stride};
+    for (int64_t s : strides)
+        if (s % 8 != 0) return FA_ERR_BAD_STRIDE;
+    // 64-bit base per tile + 32-bit (row * stride) lane offset, row < 64
+    if (p->k_row_stride < 0 || p->v_row_stride < 0 || p->k_row_stride >= (1 << 24) || p->v_row_stride >= (1 << 24))
+        return FA_ERR_BAD_STRIDE;
+    const void *ptrs[] = {p->q, p->k, p->v, p->o};
+    for (const void *ptr : ptrs)
+        if (reinterpret_cast<uintptr_t>(ptr) % 16 != 0) return FA_ERR_BAD_STRIDE;
+    if (p->num_splits < 0) return FA_ERR_BAD_SHAPE;
+    if (p->softcap < 0.f || std::isnan(p->softcap) || std::isnan(p->softmax_scale)) return FA_ERR_BAD_SHAPE;
+    if (p->leftpad_k && p->block_table) return FA_ERR_UNSUPPORTED;  // as fa_fwd
+    if (p->block_table) {
+        if (p->kv_batch_idx) return FA_ERR_UNSUPPORTED;  // as fa_fwd
+        if (p->page_block_size <= 0) return FA_ERR_BAD_SHAPE;  // any size
+        if (p->block_table_batch_stride < 0 || p->block_table_batch_stride > 0x7fffffff) return FA_ERR_BAD_STRIDE;
+    }
+    return FA_OK;
+}
+
 // the kernel params of a launch that validate and the plan have accepted (the route adds what its kernel has beside KParams)
 inline void fill_fp8_cache(const fa_fwd_params *p, const Fp8CachePlan &pl, int32_t dv, KParams &kp) {
     fwd_fill_params(p, dv, kp);

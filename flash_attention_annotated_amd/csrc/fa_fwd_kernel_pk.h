@@ -24,6 +24,10 @@
 // What WALKS the key tiles is the policy WALK: RangeWalk (pk_fwd_kernel, kv8_fwd_kernel: every 64-key tile of the block's key
 // range, in order) or ListWalk (sp_fwd_kernel, fa_fwd_kernel_sp.h: the tiles of the key blocks a per-kv-head list names, in list
 // order).  Both run the same load_tile / tile step / store_tile; every use of WALK::SPARSE says what differs.
+// What a query row SEES of the walked tiles is the policy MASK: RangeMask (all three kernels above: the lane's key range
+// [lim_lo, lim_hi) from is_causal / the window, bottom-right aligned) or TreeMask (tr_fwd_kernel, fa_fwd_kernel_tr.h: the whole
+// committed prefix and, of the sq draft keys at the end of the cache, the ones a 64-bit word per query row names).  Every use
+// of MASK::TREE says what differs; with RangeMask nothing of it is compiled in.
 // Not here (the plan keeps such calls on the other kernels): all-fp8, ALiBi, dropout, attention_chunk, a V head dim of its
 // own, qv, head dims above 128.
 #pragma once
@@ -78,8 +82,24 @@ struct ListWalk {
     int32_t max_blocks, block_size;
 };
 
-template <typename T, int D, bool SOFTCAP, typename KV, typename WALK = RangeWalk>
-__device__ __forceinline__ void packed_rows_fwd(const PkParams &pa, const WALK &walk = WALK()) {
+
+// ---- what a query row sees of the keys ---------------------------------------------------------------------------------------
+// the lane's own key range [lim_lo, lim_hi): is_causal / window, bottom-right aligned on sk
+struct RangeMask {
+    static constexpr bool TREE = false;
+};
+// Token tree of a speculative-decoding verify step: the sq query rows of a batch entry are the tree's nodes, their keys the last
+// sq rows of the cache.  With shift = sk - sq and t = key - shift: t < 0 (the committed prefix) is seen by every row, a tree key
+// by the rows whose word has bit t set; bits at or above sq and tree keys with t >= 64 count as not set.  Words are int64 behind
+// element strides, addressed like q: (batch, row) for dense queries, row of the whole batch (batch stride unused) for ragged ones.
+struct TreeMask {
+    static constexpr bool TREE = true;
+    const int64_t *words;
+    int64_t batch_stride, row_stride;
+};
+
+template <typename T, int D, bool SOFTCAP, typename KV, typename WALK = RangeWalk, typename MASK = RangeMask>
+__device__ __forceinline__ void packed_rows_fwd(const PkParams &pa, const WALK &walk = WALK(), const MASK &mask = MASK()) {
     typedef typename KV::E E;
     const KParams &p = pa.p;
     constexpr int NT = PK_NWAVES * 64;
@@ -121,7 +141,7 @@ __device__ __forceinline__ void packed_rows_fwd(const PkParams &pa, const WALK &
         sq = p.seqused_q ? p.seqused_q[batch] : p.seqlen_q;
     }
     bool ragged_k = false;
-    if constexpr (!KV::FP8_CACHE && !WALK::SPARSE) ragged_k = p.cu_seqlens_k != nullptr;  // (fa_fwd_kv8_validate / fa_fwd_sparse_kv_validate refuse cu_seqlens_k)
+    if constexpr (!KV::FP8_CACHE && !WALK::SPARSE && !MASK::TREE) ragged_k = p.cu_seqlens_k != nullptr;  // (fa_fwd_kv8_validate / fa_fwd_sparse_kv_validate / fa_fwd_tree_validate refuse cu_seqlens_k)
     if (ragged_k) {
         const int k0 = p.cu_seqlens_k[batch];
         sk = p.seqused_k ? p.seqused_k[batch] : p.cu_seqlens_k[batch + 1] - k0;
@@ -129,7 +149,7 @@ __device__ __forceinline__ void packed_rows_fwd(const PkParams &pa, const WALK &
         v_base = (int64_t)k0 * p.v_row_stride;
     } else {
         sk = p.seqused_k ? p.seqused_k[batch] : p.seqlen_k;
-        if constexpr (KV::FP8_CACHE || WALK::SPARSE) sk = min(sk, p.seqlen_k);  // a cache: never past the capacity
+        if constexpr (KV::FP8_CACHE || WALK::SPARSE || MASK::TREE) sk = min(sk, p.seqlen_k);  // a cache: never past the capacity
         const int kv_batch = p.kv_batch_idx ? p.kv_batch_idx[batch] : batch;
         k_base = (int64_t)kv_batch * p.k_batch_stride;
         v_base = (int64_t)kv_batch * p.v_batch_stride;
@@ -190,6 +210,17 @@ __device__ __forceinline__ void packed_rows_fwd(const PkParams &pa, const WALK &
     int lim_hi = sk, lim_lo = 0;
     if (p.window_right >= 0) lim_hi = min(sk, my_row + shift + p.window_right + 1);
     if (p.window_left >= 0) lim_lo = max(0, my_row + shift - p.window_left);
+    // TreeMask (fa_fwd_tree_validate refuses is_causal and the windows: the block's key range is all of [0, sk) and the lane's
+    // range is not used): the word of the lane's own QUERY row, loaded once and cut to the bits that name a key of this entry,
+    // t in [max(0, -shift), min(sq, 64)) -- so a set bit is a key below sk, and `sees` says whether the row has a key at all
+    uint64_t word = 0;
+    bool sees = false;
+    if constexpr (MASK::TREE) {
+        word = (uint64_t)mask.words[bq * mask.batch_stride + row_g * mask.row_stride];
+        if (sq < 64) word &= (uint64_t(1) << max(sq, 0)) - 1;
+        if (shift < 0) word = shift > -64 ? word >> -shift << -shift : 0;
+        sees = shift > 0 || word != 0;
+    }
 
     // ---- Q fragments: B operand of S^T = K.Q^T; k-step ks of lane (r, hh) holds Q[row r][KV::q_col(ks, hh) .. + 8]
     // (branch-free, zeroed by selects)
@@ -340,6 +371,7 @@ __device__ __forceinline__ void packed_rows_fwd(const PkParams &pa, const WALK &
             skip = skip || (k0 + BLOCK_N - 1 < wq_lo + shift - p.window_left);
             need_mask = need_mask || (k0 < wq_hi + shift - p.window_left);
         }
+        if constexpr (MASK::TREE) need_mask = k0 + BLOCK_N > shift;  // reaches sk or a draft key: at most two tiles (sq <= 64)
 
         if (!skip) {  // (wave-uniform: EXEC is full at the transposed reads)
             const char *kbuf = smem + cur * TILE_BYTES;
@@ -349,7 +381,11 @@ __device__ __forceinline__ void packed_rows_fwd(const PkParams &pa, const WALK &
             zero_scores(s);
             KV::scores(kbuf, kbase, qf, s);
             if constexpr (SOFTCAP) softcap_scores(s, sc);
-            if (need_mask) mask_scores(s, k0, hh, lim_lo, lim_hi);  // boundary tiles only
+            if constexpr (MASK::TREE) {
+                if (need_mask) mask_scores(s, k0, hh, shift, word);  // the tiles of the draft keys only
+            } else {
+                if (need_mask) mask_scores(s, k0, hh, lim_lo, lim_hi);  // boundary tiles only
+            }
             u32x4 pf[4];
             softmax_step<T, DBLOCKS>(s, m_run, l_run, o_acc, sc, pf);
 #pragma unroll
@@ -371,7 +407,11 @@ __device__ __forceinline__ void packed_rows_fwd(const PkParams &pa, const WALK &
     } else {
         inv = empty ? 1.f : 1.f / l_tot;
     }
-    if constexpr (WALK::SPARSE) {
+    if constexpr (MASK::TREE) {
+        // kv8's split convention below, for both cache types (the merge is fa_fwd_combine): a part without a key of the row
+        // writes -inf when the row sees a key anywhere, +inf when its word and an empty prefix leave it none.  No sink
+        if (p.num_splits > 1 && empty && sees) lse_row = -INFINITY;
+    } else if constexpr (WALK::SPARSE) {
         // kv8's split convention below, for both cache types (the merge is fa_fwd_combine); "the row sees a key" means a
         // LISTED key here: an empty part looks through the whole list (uniform addresses, entries in front of the count
         // only) for a block in range that meets the row's key range.  Rare: only the rows of a part that found nothing

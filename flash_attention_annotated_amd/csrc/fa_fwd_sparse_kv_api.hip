@@ -52,37 +52,6 @@ const char *plan_text(const Fp8CachePlan &pl, const fa_sparse_kv_params *s, char
     return name;
 }
 
-// The 16-bit half of the validation: validate_fp8_cache's rules with k / v strides in 16-bit elements and no descales
-int validate_16bit_cache(const fa_fwd_params *p) {
-    const bool ragged = p->cu_seqlens_q != nullptr;
-    if (ragged && (!p->seqused_k || p->total_q < 0)) return FA_ERR_BAD_SHAPE;
-    const bool empty = p->seqlen_q == 0 || (ragged && p->total_q == 0);
-    if (!empty) {
-        if (!p->q || !p->o || !p->softmax_lse) return FA_ERR_NULL_POINTER;
-        if (p->seqlen_k > 0 && (!p->k || !p->v)) return FA_ERR_NULL_POINTER;
-    }
-    const int64_t strides[] = {p->q_row_stride, p->q_head_stride, p->o_row_stride, p->o_head_stride,
-                               ragged ? 0 : p->q_batch_stride, ragged ? 0 : p->o_batch_stride,
-                               p->k_row_stride, p->k_head_stride, p->k_batch_stride, p->v_row_stride, p->v_head_stride, p->v_batch_stride};
-    for (int64_t s : strides)
-        if (s % 8 != 0) return FA_ERR_BAD_STRIDE;
-    // 64-bit base per tile + 32-bit (row * stride) lane offset, row < 64
-    if (p->k_row_stride < 0 || p->v_row_stride < 0 || p->k_row_stride >= (1 << 24) || p->v_row_stride >= (1 << 24))
-        return FA_ERR_BAD_STRIDE;
-    const void *ptrs[] = {p->q, p->k, p->v, p->o};
-    for (const void *ptr : ptrs)
-        if (reinterpret_cast<uintptr_t>(ptr) % 16 != 0) return FA_ERR_BAD_STRIDE;
-    if (p->num_splits < 0) return FA_ERR_BAD_SHAPE;
-    if (p->softcap < 0.f || std::isnan(p->softcap) || std::isnan(p->softmax_scale)) return FA_ERR_BAD_SHAPE;
-    if (p->leftpad_k && p->block_table) return FA_ERR_UNSUPPORTED;  // as fa_fwd
-    if (p->block_table) {
-        if (p->kv_batch_idx) return FA_ERR_UNSUPPORTED;  // as fa_fwd
-        if (p->page_block_size <= 0) return FA_ERR_BAD_SHAPE;  // any size
-        if (p->block_table_batch_stride < 0 || p->block_table_batch_stride > 0x7fffffff) return FA_ERR_BAD_STRIDE;
-    }
-    return FA_OK;
-}
-
 template <typename T, int D, typename KV>
 int launch_form(const Fp8CachePlan &pl, const fa::SpParams &sa, hipStream_t stream) {
     constexpr int smem = KV::FP8_CACHE ? fa::smem_bytes_kv8<D>() : fa::smem_bytes<D, fa::PK_NWAVES>(), NT = fa::PK_NWAVES * 64;
@@ -125,7 +94,7 @@ int fa_fwd_sparse_kv_validate(const fa_fwd_params *p, const fa_sparse_kv_params 
     if (p->h % p->h_k != 0) return FA_ERR_BAD_HEADS;
     if ((int64_t)p->seqlen_q * (p->h / p->h_k) > 0x7fffffff) return FA_ERR_BAD_SHAPE;  // (the kernel counts packed rows in 32 bits)
     if (s->fp8_cache && (!p->k_descale || !p->v_descale)) return FA_ERR_NULL_POINTER;  // (both descales are required)
-    const int st = s->fp8_cache ? fa::validate_fp8_cache(p, plan_unsplit) : validate_16bit_cache(p);
+    const int st = s->fp8_cache ? fa::validate_fp8_cache(p, plan_unsplit) : fa::validate_16bit_cache(p);
     if (st != FA_OK) return st;
     const fa::SplitPlan sp = plan_sparse(p, s).split;
     return sp.splits > 1 && fa::workspace_short(p, sp.total) ? FA_ERR_WORKSPACE : FA_OK;

@@ -40,6 +40,20 @@ __device__ __forceinline__ void mask_scores(f32x16 (&s)[2], int k0, int hh, int 
         }
 }
 
+// element mask of a tile that holds draft keys of a token tree (TreeMask, fa_fwd_kernel_pk.h): key p of the tile at k0 stays iff
+// p < shift (the committed prefix) or bit p - shift < 64 of the lane's word is set; the caller has cut the word to the bits
+// that name a key below sk
+__device__ __forceinline__ void mask_scores(f32x16 (&s)[2], int k0, int hh, int shift, uint64_t word) {
+#pragma unroll
+    for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            const int t = k0 + kb * 32 + (i & 3) + 8 * (i >> 2) + 4 * hh - shift;
+            const bool seen = t < 0 || (t < 64 && ((word >> (t & 63)) & 1) != 0);
+            if (!seen) s[kb][i] = -INFINITY;
+        }
+}
+
 // Online softmax of one tile (per lane = per row): new running maximum, rescale of l_run and of the NDB accumulator blocks
 // (skipped, wave-uniformly, when no row's maximum moved), s -> exp2 weights, row sum, and the weights packed to T: the
 // accumulator registers ARE the B operand of O^T += V^T.P^T (pf[st] = keys 16 st .. 16 st + 15 of the tile).

@@ -1213,6 +1213,12 @@ struct SparseLists {
     bool fp8_cache;      // e4m3 caches (else 16-bit caches of q's dtype)
 };
 
+// The words of fwd_kvcache_tree (include/fa_fwd.h, fa_tree_params), checked there
+struct TreeWords {
+    Tensor mask;     // int64 (b, seqlen_q), or (total_q,) beside cu_seqlens_q
+    bool fp8_cache;  // e4m3 caches (else 16-bit caches of q's dtype)
+};
+
 // 16-bit queries over an fp8 (e4m3) KV cache -- kv_cache_dtype = fp8 of a serving stack (include/fa_fwd.h, fa_fwd_kv8): q and
 // out fp16 / bf16, k / v the cache as Float8_e4m3fn, (b_cache, seqlen_k, h_k, d) or pages behind page_table, k_descale /
 // v_descale fp32 (b, h_k).  Dense q (b, seqlen_q, h, d) or ragged q (total_q, h, d) with cu_seqlens_q; cache_seqlens in
@@ -1223,18 +1229,19 @@ struct SparseLists {
 // other argument is handled alike, so fwd_qv8 below is this function with mla set.
 // sparse: the block-sparse read (fa_fwd_sparse_kv) of fwd_kvcache_sparse below, over an e4m3 cache or -- the one case where k / v
 // are 16-bit here -- a cache of q's dtype; the lists ride beside the same params, everything else is handled alike.
+// tree: tree attention (fa_fwd_tree) of fwd_kvcache_tree below, over either cache type as well; the words ride beside the params.
 std::tuple<Tensor, Tensor> fwd_kv8(const Tensor &q, const Tensor &k, const Tensor &v, const OptTensor &out_,
                                    const OptTensor &cu_seqlens_q, const OptTensor &seqused_q, const OptTensor &seqused_k,
                                    c10::optional<int64_t> max_seqlen_q_, const OptTensor &page_table, const OptTensor &kv_batch_idx,
                                    const OptTensor &leftpad_k, const OptTensor &k_descale, const OptTensor &v_descale,
                                    double softmax_scale, bool is_causal, int64_t window_size_left, int64_t window_size_right,
                                    double softcap, int64_t num_splits, const OptTensor &qv = c10::nullopt, bool mla = false,
-                                   const SparseLists *sparse = nullptr) {
-    const bool wide_cache = sparse && !sparse->fp8_cache;  // 16-bit k / v: strides in 2-byte elements
+                                   const SparseLists *sparse = nullptr, const TreeWords *tree = nullptr) {
+    const bool wide_cache = (sparse && !sparse->fp8_cache) || (tree && !tree->fp8_cache);  // 16-bit k / v: strides in 2-byte elements
     CHECK_DEVICE(k, "k"); CHECK_LAST_CONTIGUOUS(k, "Input tensor must have contiguous last dimension");
     CHECK_DEVICE(v, "v"); CHECK_LAST_CONTIGUOUS(v, "Input tensor must have contiguous last dimension");
     const bool ragged = cu_seqlens_q.has_value();
-    TORCH_CHECK(k.dim() == 4 && v.dim() == 4, sparse ? "k / v" : "an fp8 k / v",
+    TORCH_CHECK(k.dim() == 4 && v.dim() == 4, sparse || tree ? "k / v" : "an fp8 k / v",
                 " must be a KV cache of shape (batch or num_pages, seqlen or page_size, num_heads_k, head_size)");
     const int64_t head_size = q.size(-1), num_heads = q.size(-2), num_heads_k = k.size(2);
     const int64_t head_size_v = mla ? v.size(3) : head_size;
@@ -1292,6 +1299,9 @@ std::tuple<Tensor, Tensor> fwd_kv8(const Tensor &q, const Tensor &k, const Tenso
         TORCH_CHECK(sparse->idx.size(0) == 1 || sparse->idx.size(0) == batch_size, "kv_block_idx must have shape (batch_size | 1, num_heads_k | 1, max_blocks)");
         TORCH_CHECK(sparse->idx.size(1) == 1 || sparse->idx.size(1) == num_heads_k, "kv_block_idx must have shape (batch_size | 1, num_heads_k | 1, max_blocks)");
     }
+    if (tree)
+        TORCH_CHECK(tree->mask.sizes() == (ragged ? c10::IntArrayRef({total_q}) : c10::IntArrayRef({batch_size, seqlen_q})),
+                    "tree_mask must have shape (batch_size, seqlen_q), or (total_q,) with cu_seqlens_q");
     if (seqlen_k == 0 || seqlen_q == 0) {
         fill_empty(out, softmax_lse);
         return {out, softmax_lse};
@@ -1321,11 +1331,26 @@ std::tuple<Tensor, Tensor> fwd_kv8(const Tensor &q, const Tensor &k, const Tenso
         sp.block_size = (int32_t)sparse->block_size;
         sp.fp8_cache = sparse->fp8_cache ? 1 : 0;
     }
-    const char *entry = sparse ? "fa_fwd_sparse_kv" : mla ? "fa_fwd_qv8" : "fa_fwd_kv8";
-    const int64_t need = sparse ? fa_fwd_sparse_kv_workspace_size(&p, &sp) : mla ? fa_fwd_qv8_workspace_size(&p) : fa_fwd_kv8_workspace_size(&p);
+    fa_tree_params tp{};
+    if (tree) {
+        tp.abi_version = FA_ABI_VERSION;
+        tp.struct_size = sizeof(fa_tree_params);
+        tp.tree_mask = static_cast<const int64_t *>(tree->mask.data_ptr());
+        tp.batch_stride = ragged ? 0 : tree->mask.stride(0);
+        tp.row_stride = tree->mask.stride(-1);
+        tp.fp8_cache = tree->fp8_cache ? 1 : 0;
+    }
+    const char *entry = tree ? "fa_fwd_tree" : sparse ? "fa_fwd_sparse_kv" : mla ? "fa_fwd_qv8" : "fa_fwd_kv8";
+    const int64_t need = tree     ? fa_fwd_tree_workspace_size(&p, &tp)
+                         : sparse ? fa_fwd_sparse_kv_workspace_size(&p, &sp)
+                         : mla    ? fa_fwd_qv8_workspace_size(&p)
+                                  : fa_fwd_kv8_workspace_size(&p);
     TORCH_CHECK(need >= 0, entry, "_workspace_size failed (", need, "): ", fa_strerror((int)need));
     const Tensor workspace = set_workspace(p, need, q);  // split-KV partials
-    const int st = sparse ? fa_fwd_sparse_kv(&p, &sp, current_stream(q)) : mla ? fa_fwd_qv8(&p, current_stream(q)) : fa_fwd_kv8(&p, current_stream(q));
+    const int st = tree     ? fa_fwd_tree(&p, &tp, current_stream(q))
+                   : sparse ? fa_fwd_sparse_kv(&p, &sp, current_stream(q))
+                   : mla    ? fa_fwd_qv8(&p, current_stream(q))
+                            : fa_fwd_kv8(&p, current_stream(q));
     TORCH_CHECK(st == 0, entry, " failed (", st, "): ", fa_strerror(st));
     o.finish();
     return {out, softmax_lse};
@@ -1375,6 +1400,45 @@ std::tuple<Tensor, Tensor> fwd_kvcache_sparse(const Tensor &q, const Tensor &k, 
     return fwd_kv8(q, k, v, c10::nullopt, cu_seqlens_q, c10::nullopt, seqused_k, max_seqlen_q_, page_table, kv_batch_idx, leftpad_k,
                    k_descale, v_descale, softmax_scale, is_causal, window_size_left, window_size_right, softcap, num_splits, c10::nullopt,
                    false, &lists);
+}
+
+// hopper_interface.flash_attn_with_kvcache_tree / torch.ops.flash_attn_3.fwd_kvcache_tree: the verify step of speculative decoding
+// over a token tree (include/fa_fwd.h, fa_fwd_tree): every query row sees the committed prefix of the cache and the draft keys
+// its int64 word names.  16-bit caches of q's dtype or e4m3 caches with both descales; read-only, no causal / window / rotary
+// argument (the words are the mask; positions in a tree are depths, so the caller rotates before the append).  The refusals by
+// argument stand here; the cache side, out, the workspace and the launch are fwd_kv8's.  Nothing of the words is read on the host.
+std::tuple<Tensor, Tensor> fwd_kvcache_tree(const Tensor &q, const Tensor &k, const Tensor &v, const Tensor &tree_mask,
+                                            const OptTensor &seqused_k, const OptTensor &kv_batch_idx, const OptTensor &leftpad_k,
+                                            const OptTensor &page_table, const OptTensor &cu_seqlens_q,
+                                            c10::optional<int64_t> max_seqlen_q_, const OptTensor &k_descale, const OptTensor &v_descale,
+                                            c10::optional<double> softmax_scale_, double softcap, int64_t num_splits) {
+    const auto q_dtype = q.scalar_type();
+    TORCH_CHECK(q_dtype == at::kHalf || q_dtype == at::kBFloat16,
+                "This flash attention build supports tree attention over a KV cache for fp16 / bf16 queries only");
+    TORCH_CHECK(k.scalar_type() == v.scalar_type(), "k_cache and v_cache must have the same dtype");
+    const bool fp8_cache = k.scalar_type() == at::kFloat8_e4m3fn;
+    TORCH_CHECK(fp8_cache || k.scalar_type() == q_dtype,
+                "k_cache / v_cache must have the dtype of the query or be torch.float8_e4m3fn under an fp16 / bf16 query");
+    if (fp8_cache) {
+        TORCH_CHECK(k_descale.has_value() && v_descale.has_value(), "k_descale and v_descale must be provided with an fp8 KV cache");
+    } else {
+        TORCH_CHECK(!k_descale.has_value() && !v_descale.has_value(), "k_descale / v_descale belong to an fp8 KV cache");
+    }
+    TORCH_CHECK(tree_mask.scalar_type() == at::kLong, "tree_mask must have dtype int64");
+    TORCH_CHECK(tree_mask.is_cuda() && tree_mask.device() == q.device(), "tree_mask must be on the same CUDA device as query");
+    TORCH_CHECK(k.dim() == 4 && v.dim() == 4 && v.size(-1) == q.size(-1) && k.size(-1) == q.size(-1),
+                "This flash attention build does not support a V headdim of its own with tree attention over a KV cache.");
+    TORCH_CHECK(q.size(-1) <= 128 && q.size(-1) % 16 == 0,
+                "This flash attention build supports tree attention over a KV cache for head_size <= 128 that is a multiple of 16, "
+                "got ", q.size(-1));
+    check_ragged_q(q, cu_seqlens_q, max_seqlen_q_);
+    const int64_t nodes = cu_seqlens_q.has_value() ? *max_seqlen_q_ : q.size(1);
+    TORCH_CHECK(nodes <= 64, "This flash attention build supports token trees of at most 64 nodes (one int64 word per query row), got ",
+                nodes);
+    const double softmax_scale = softmax_scale_.has_value() ? *softmax_scale_ : 1.0 / std::sqrt((double)q.size(-1));
+    const TreeWords words{tree_mask, fp8_cache};
+    return fwd_kv8(q, k, v, c10::nullopt, cu_seqlens_q, c10::nullopt, seqused_k, max_seqlen_q_, page_table, kv_batch_idx, leftpad_k,
+                   k_descale, v_descale, softmax_scale, false, -1, -1, softcap, num_splits, c10::nullopt, false, nullptr, &words);
 }
 
 // The MLA decode shape over an fp8 KV cache (include/fa_fwd.h, fa_fwd_qv8): q (.., h, d <= 64) and the optional qv (.., h, d_v)
@@ -3251,6 +3315,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("k_descale") = py::none(), py::arg("v_descale") = py::none(), py::arg("softmax_scale") = py::none(),
           py::arg("is_causal") = false, py::arg("window_size_left") = -1, py::arg("window_size_right") = -1, py::arg("softcap") = 0.0,
           py::arg("num_splits") = 0);
+    m.def("fwd_kvcache_tree", &fwd_kvcache_tree,
+          "tree attention over a KV cache: every query row sees the committed prefix and the draft keys its word names; returns (out, softmax_lse)",
+          py::arg("q"), py::arg("k_cache"), py::arg("v_cache"), py::arg("tree_mask"), py::arg("cache_seqlens") = py::none(),
+          py::arg("cache_batch_idx") = py::none(), py::arg("cache_leftpad") = py::none(), py::arg("page_table") = py::none(),
+          py::arg("cu_seqlens_q") = py::none(), py::arg("max_seqlen_q") = py::none(), py::arg("k_descale") = py::none(),
+          py::arg("v_descale") = py::none(), py::arg("softmax_scale") = py::none(), py::arg("softcap") = 0.0, py::arg("num_splits") = 0);
     for (const bool plan : {false, true}) {
         m.def(plan ? "kvcache_block_summary_update_plan" : "kvcache_block_summary_update",
               [plan](const Tensor &k_summary, const Tensor &k_cache, const OptTensor &seqlens_old, const Tensor &seqlens_new,

@@ -48,7 +48,13 @@ KVCACHE_SPARSE_SCHEMA = (
     "Tensor? cu_seqlens_q = None, int? max_seqlen_q = None, Tensor? k_descale = None, Tensor? v_descale = None, "
     "float? softmax_scale = None, bool is_causal = False, int window_size_left = -1, int window_size_right = -1, "
     "float softcap = 0.0, int num_splits = 0) -> (Tensor, Tensor)")
-# ... nor what produces its lists (include/fa_block_select.h): the block summaries of the keys, updated in place on append, and
+# nor this: tree attention over a KV cache (the verify step of speculative decoding over a token tree), read-only
+KVCACHE_TREE_SCHEMA = (
+    "fwd_kvcache_tree(Tensor q, Tensor k_cache, Tensor v_cache, Tensor tree_mask, Tensor? cache_seqlens = None, "
+    "Tensor? cache_batch_idx = None, Tensor? cache_leftpad = None, Tensor? page_table = None, Tensor? cu_seqlens_q = None, "
+    "int? max_seqlen_q = None, Tensor? k_descale = None, Tensor? v_descale = None, float? softmax_scale = None, "
+    "float softcap = 0.0, int num_splits = 0) -> (Tensor, Tensor)")
+# ... nor what produces the sparse route's lists (include/fa_block_select.h): the block summaries of the keys, updated in place on append, and
 # the Quest selection.  Every tensor the launches write is a mutated argument and nothing is returned, so that a traced graph
 # holds no alias of an input; hopper_interface allocates what the caller does not give
 BLOCK_SUMMARY_SCHEMA = (
@@ -60,8 +66,8 @@ SELECT_BLOCKS_SCHEMA = (
     "Tensor(c!) scores) -> ()")
 
 _ops = torch.library.Library("flash_attn_3", "DEF")
-for _schema in (FWD_SCHEMA, BWD_SCHEMA, COMBINE_SCHEMA, METADATA_SCHEMA, APPEND_FP8_SCHEMA, KVCACHE_SPARSE_SCHEMA, BLOCK_SUMMARY_SCHEMA,
-                SELECT_BLOCKS_SCHEMA):
+for _schema in (FWD_SCHEMA, BWD_SCHEMA, COMBINE_SCHEMA, METADATA_SCHEMA, APPEND_FP8_SCHEMA, KVCACHE_SPARSE_SCHEMA, KVCACHE_TREE_SCHEMA,
+                BLOCK_SUMMARY_SCHEMA, SELECT_BLOCKS_SCHEMA):
     _ops.define(_schema)
 
 
@@ -129,6 +135,23 @@ def _fwd_kvcache_sparse_meta(q, k_cache, v_cache, kv_block_cnt, kv_block_idx, kv
     return torch.empty_like(q), q.new_empty(lse_shape, dtype=torch.float32)
 
 
+def _fwd_kvcache_tree(q, k_cache, v_cache, tree_mask, cache_seqlens=None, cache_batch_idx=None, cache_leftpad=None, page_table=None,
+                      cu_seqlens_q=None, max_seqlen_q=None, k_descale=None, v_descale=None, softmax_scale=None, softcap=0.0,
+                      num_splits=0):
+    """The binding's fwd_kvcache_tree (fa_fwd_tree): one launch (+ the merge of a split call), no host sync."""
+    out, lse = _lib.binding().fwd_kvcache_tree(q, k_cache, v_cache, tree_mask, cache_seqlens, cache_batch_idx, cache_leftpad,
+                                               page_table, cu_seqlens_q, max_seqlen_q, k_descale, v_descale, softmax_scale, softcap,
+                                               num_splits)
+    return out, lse
+
+
+def _fwd_kvcache_tree_meta(q, k_cache, v_cache, tree_mask, cache_seqlens=None, cache_batch_idx=None, cache_leftpad=None,
+                           page_table=None, cu_seqlens_q=None, max_seqlen_q=None, k_descale=None, v_descale=None, softmax_scale=None,
+                           softcap=0.0, num_splits=0):
+    lse_shape = (q.shape[1], q.shape[0]) if q.dim() == 3 else (q.shape[0], q.shape[2], q.shape[1])
+    return torch.empty_like(q), q.new_empty(lse_shape, dtype=torch.float32)
+
+
 def _kvcache_block_summary_update(k_summary, k_cache, seqlens_old, seqlens_new, kv_block_size=128, max_seqlen_new=None,
                                   cache_batch_idx=None, page_table=None):
     """The binding's kvcache_block_summary_update (fa_block_summary_update): one launch, in place."""
@@ -182,6 +205,8 @@ _ops.impl("kvcache_append_fp8", _kvcache_append_fp8, "CUDA")
 _ops.impl("kvcache_append_fp8", _kvcache_append_fp8_meta, "Meta")
 _ops.impl("fwd_kvcache_sparse", _fwd_kvcache_sparse, "CUDA")
 _ops.impl("fwd_kvcache_sparse", _fwd_kvcache_sparse_meta, "Meta")
+_ops.impl("fwd_kvcache_tree", _fwd_kvcache_tree, "CUDA")
+_ops.impl("fwd_kvcache_tree", _fwd_kvcache_tree_meta, "Meta")
 _ops.impl("kvcache_block_summary_update", _kvcache_block_summary_update, "CUDA")
 _ops.impl("kvcache_block_summary_update", _nothing, "Meta")
 _ops.impl("kvcache_select_blocks", _kvcache_select_blocks, "CUDA")

@@ -270,6 +270,162 @@ def flash_attn_with_kvcache_sparse(q, k_cache, v_cache, kv_block_cnt, kv_block_i
     return (out, softmax_lse) if return_softmax_lse else out
 
 
+def flash_attn_with_kvcache_tree(q, k_cache, v_cache, tree_mask, *, cache_seqlens=None, cache_batch_idx=None, cache_leftpad=None,
+                                 page_table=None, cu_seqlens_q=None, max_seqlen_q=None, k_descale=None, v_descale=None,
+                                 softmax_scale=None, softcap=0.0, num_splits=0, return_softmax_lse=False):
+    """Tree attention over a KV cache: the verify step of speculative decoding whose draft is a token TREE (Medusa, EAGLE-2,
+    SpecInfer, sequoia) of up to 64 nodes, verified in one pass.  Not in the reference.
+    q: (batch, T, nheads, headdim), or (total_q, nheads, headdim) with cu_seqlens_q + max_seqlen_q; fp16 / bf16, headdim <= 128
+    and a multiple of 16; T / max_seqlen_q <= 64.  The rows of batch entry b are the sq(b) nodes of its tree (T, or from
+    cu_seqlens_q).  k_cache / v_cache: as in flash_attn_with_kvcache (batched with cache_batch_idx / cache_leftpad, or pages of
+    any size behind page_table), of q's dtype or torch.float8_e4m3fn; the fp8 case takes both k_descale / v_descale, fp32
+    (batch, nheads_k).  sk(b) is the fill level of the cache INCLUDING the sq(b) draft tokens, which the caller appended at
+    positions [sk(b) - sq(b), sk(b)): cache_seqlens, clamped to the capacity, minus cache_leftpad.
+    tree_mask: int64 (batch, T), or (total_q,) for ragged queries, on the device (any strides).  With shift = sk(b) - sq(b) and
+    t = j - shift, key j of batch b is visible to query row i of any head iff
+      * j < sk(b), and
+      * t < 0, or (t < 64 and bit t of tree_mask[b, i] is set): the committed prefix (t < 0) is seen by every node, a draft key
+        by the nodes whose word names it -- their ancestors and themselves (tree_mask_from_parents builds such words).
+    softcap applies as elsewhere.  Bits at or above sq(b) are ignored.  A draft key with t >= 64 is invisible: T / max_seqlen_q
+    above 64 is refused, and a ragged entry that is longer at run time falls under this rule, without a fault.  No structure is
+    assumed of the words: they need not be lower-triangular, and the diagonal bit is the caller's duty.  A chain (row i = bits
+    0 .. i) is causal=True of flash_attn_with_kvcache.  A row with no visible key gives out = 0, lse = +inf.
+    Positions in a tree are depths, not indices, so there is no rotary here: rotate q and k by the depth of each node yourself
+    before the append.  Read-only: append the draft with flash_attn_with_kvcache(k=, v=) or kvcache_append_fp8 first, then call
+    this on the new fill levels; kvcache_keep_tree_path_ compacts the cache to the accepted path afterwards.
+    The kernel is the PackGQA body (the nheads / nheads_k heads of a group share one pass over the cache, T * g rows fill the
+    tiles); only the at most two 64-key tiles that hold draft keys take the mask.  num_splits: 1 = off, N = N parts of the key
+    range, 0 = the count the PackGQA shape gets -- from shapes only.  Nothing of tree_mask or cache_seqlens is read on the host
+    and nothing synchronises: the call can be captured into a HIP graph, and a replay after both were overwritten in place
+    computes the new tree.
+    No causal / window_size (the words are the mask), qv, learnable sink, ALiBi, dropout, attention_chunk, rotary or V headdim of
+    its own, and no backward.
+    Cost, measured on MI355X (tools/tree_verify_bench.py, profiles/tree_verify.jsonl; hq32 / hkv8 d128, page 64, cache 8192 /
+    32768, batch 1 / 8 / 64, T = 16 / 64): 0.94 - 1.03 x flash_attn_with_kvcache(causal=True, pack_gqa=True) on a chain over the
+    same bf16 cache, 0.97 - 1.00 x over an e4m3 cache, the same for a random forest; a chain's output is bit-equal to that
+    call's.  DESIGN.md section 4.31.
+    Returns out, or (out, softmax_lse) when return_softmax_lse: (batch, nheads, T), ragged (nheads, total_q)."""
+    assert k_cache.stride(-1) == 1, "k_cache must have contiguous last dimension"
+    assert v_cache.stride(-1) == 1, "v_cache must have contiguous last dimension"
+    if cache_seqlens is not None and isinstance(cache_seqlens, int):
+        cache_seqlens = torch.full((q.shape[0],), cache_seqlens, dtype=torch.int32, device=k_cache.device)
+    out, softmax_lse = torch.ops.flash_attn_3.fwd_kvcache_tree(
+        q, k_cache, v_cache, tree_mask, cache_seqlens, cache_batch_idx, cache_leftpad, page_table, cu_seqlens_q, max_seqlen_q,
+        k_descale, v_descale, softmax_scale, softcap, num_splits)
+    return (out, softmax_lse) if return_softmax_lse else out
+
+
+def _bit(i):
+    """Bit i of a word as an int64 value (bit 63 is the sign)."""
+    return (1 << i) - (1 << 64 if i == 63 else 0)
+
+
+def tree_mask_from_parents(parents):
+    """The words flash_attn_with_kvcache_tree takes, from the parent of every node.  parents: int (batch, T), T <= 64, on any
+    device; parents[b, i] < i is the parent of node i, -1 marks a root (a forest is fine).  Returns int64 (batch, T): bit j of
+    word i is set iff j is i or an ancestor of i.  A parent precedes its child, so one pass in node order closes the relation:
+    T steps of fixed shape, no host sync."""
+    assert parents.dim() == 2 and parents.shape[1] <= 64, "parents must be (batch, T) with T <= 64"
+    b, T = parents.shape
+    parents = parents.long()
+    words = torch.zeros((b, T), dtype=torch.int64, device=parents.device)
+    for i in range(T):
+        par = parents[:, i]
+        up = words.gather(1, par.clamp(0, max(i - 1, 0))[:, None])[:, 0]  # (the word of the parent is complete: it precedes i)
+        words[:, i] = torch.where((par >= 0) & (par < i), up, torch.zeros_like(up)) | _bit(i)
+    return words
+
+
+def tree_visibility(words, sk, num_keys):
+    """The definition of flash_attn_with_kvcache_tree for one batch entry, explicitly: words int64 (sq,), sk the fill level
+    including the sq draft keys -> bool (sq, num_keys), [i, j] = key j is visible to row i."""
+    sq = words.shape[0]
+    t = torch.arange(num_keys, device=words.device) - (sk - sq)
+    bits = (words[:, None] >> t.clamp(0, 63)[None, :]) & 1
+    tree = (t >= 0) & (t < min(sq, 64))
+    return (t + (sk - sq) < sk)[None, :] & ((t < 0)[None, :] | (tree[None, :] & (bits != 0)))
+
+
+def tree_attention_ref(q, k_cache, v_cache, tree_mask, *, cache_seqlens=None, cache_batch_idx=None, cache_leftpad=None,
+                       page_table=None, cu_seqlens_q=None, max_seqlen_q=None, k_descale=None, v_descale=None, softmax_scale=None,
+                       softcap=0.0, num_splits=0, return_softmax_lse=False):
+    """The oracle of flash_attn_with_kvcache_tree in plain torch, on any device, under the same arguments: a host loop over the
+    batch entries that gathers the logical cache (pages, cache_batch_idx, cache_leftpad; an fp8 cache dequantised exactly, value
+    times descale), builds the explicit visibility (tree_visibility) and takes the softmax in fp64.  num_splits changes nothing.
+    Returns out in fp64 with q's shape, or (out, lse) when return_softmax_lse: lse fp64 (batch, nheads, T), ragged
+    (nheads, total_q); a row with no visible key gives out = 0, lse = +inf."""
+    ragged = cu_seqlens_q is not None
+    batch = cu_seqlens_q.numel() - 1 if ragged else q.shape[0]
+    h, d, h_k = q.shape[-2], q.shape[-1], k_cache.shape[2]
+    g = h // h_k
+    scale = d ** -0.5 if softmax_scale is None else softmax_scale
+    out = torch.zeros(q.shape, dtype=torch.float64, device=q.device)
+    lse = torch.full((h, q.shape[0]) if ragged else (batch, h, q.shape[1]), float("inf"), dtype=torch.float64, device=q.device)
+    for b in range(batch):
+        rows = slice(int(cu_seqlens_q[b]), int(cu_seqlens_q[b + 1])) if ragged else slice(None)
+        qb = (q[rows] if ragged else q[b]).double()                     # (sq, h, d)
+        words = tree_mask[rows] if ragged else tree_mask[b]
+        fp8 = k_cache.dtype == torch.float8_e4m3fn
+        kc, vc = (c.view(torch.uint8) if fp8 else c for c in (k_cache, v_cache))  # (indexing needs no fp8 kernel)
+        if page_table is not None:
+            kb, vb = (c[page_table[b].long()].flatten(0, 1) for c in (kc, vc))
+        else:
+            slot = b if cache_batch_idx is None else int(cache_batch_idx[b])
+            kb, vb = kc[slot], vc[slot]
+        if fp8:
+            kb, vb = kb.view(k_cache.dtype).float(), vb.view(k_cache.dtype).float()
+        cap = kb.shape[0]
+        sk = cap if cache_seqlens is None else min(int(cache_seqlens[b]), cap)
+        lp = 0 if cache_leftpad is None else int(cache_leftpad[b])
+        sk = max(sk - lp, 0)
+        kb, vb = kb[lp:].double(), vb[lp:].double()                     # (keys, h_k, d): every e4m3 / 16-bit value is an fp64 value
+        if k_descale is not None:
+            kb, vb = kb * k_descale[b].double()[None, :, None], vb * v_descale[b].double()[None, :, None]
+        vis = tree_visibility(words, sk, kb.shape[0])                   # (sq, keys)
+        s = torch.einsum("qhd,khd->hqk", qb, kb.repeat_interleave(g, dim=1)) * scale
+        if softcap > 0:
+            s = softcap * torch.tanh(s / softcap)
+        s = s.masked_fill(~vis[None], float("-inf"))
+        l = torch.logsumexp(s, dim=-1)                                  # (h, sq); -inf where nothing is visible
+        p = torch.exp(s - l.masked_fill(torch.isinf(l), 0.0)[..., None])
+        o = torch.einsum("hqk,khd->qhd", p, vb.repeat_interleave(g, dim=1))
+        l = l.masked_fill(torch.isinf(l), float("inf"))
+        if ragged:
+            out[rows], lse[:, rows] = o, l
+        else:
+            out[b], lse[b] = o, l
+    return (out, lse) if return_softmax_lse else out
+
+
+def kvcache_keep_tree_path_(k_cache, v_cache, cache_seqlens, path, path_len, *, page_table=None, cache_batch_idx=None):
+    """After a tree was verified: keeps the accepted root-to-leaf path of the draft and drops the rest, in place.
+    cache_seqlens: int32 (batch,), the fill levels of the committed prefix -- the `shift` of flash_attn_with_kvcache_tree, i.e. the
+    levels BEFORE the draft was appended (the tree call's cache_seqlens minus its node count); the draft occupies the rows from
+    there on.  path: int32 (batch, P), node indices in ascending order, the first path_len[b] (int32 (batch,)) of them valid.
+    Moves the K / V rows of the accepted nodes from shift + path[b, j] to shift + j and returns the new fill levels
+    shift + path_len (int32 (batch,)); what lies behind them is stale.  Positions count from the start of a cache entry (no
+    cache_leftpad).  Torch indexing on any device, the right-hand side gathered before anything is written, so overlapping moves
+    are safe; works on 16-bit caches and on the bytes of an fp8 cache alike; no host sync."""
+    shift, n = cache_seqlens.long()[:, None], path_len.long()[:, None]
+    P = path.shape[1]
+    j = torch.arange(P, device=path.device)[None, :]
+    paged = page_table is not None
+    cap = page_table.shape[1] * k_cache.shape[1] if paged else k_cache.shape[1]
+    dst = (shift + j).clamp(0, cap - 1)
+    src = torch.where(j < n, (shift + path.long()).clamp(0, cap - 1), dst)  # (behind the path: a row onto itself)
+    if paged:
+        page = k_cache.shape[1]
+        at = lambda pos: (page_table.long().gather(1, pos // page), pos % page)
+    else:
+        slot = torch.arange(path.shape[0], device=path.device) if cache_batch_idx is None else cache_batch_idx.long()
+        at = lambda pos: (slot[:, None].expand_as(pos), pos)
+    for cache in (k_cache, v_cache):
+        raw = cache.view(torch.uint8) if cache.dtype == torch.float8_e4m3fn else cache  # (indexing needs no fp8 kernel)
+        kept = raw[at(src)]
+        raw[at(dst)] = kept
+    return (cache_seqlens + path_len).to(torch.int32)
+
+
 def kvcache_append_fp8(k_cache, v_cache, k, v, cache_seqlens, k_descale, v_descale, *, cu_seqlens_k_new=None,
                        max_seqlen_k_new=None, cache_batch_idx=None, page_table=None, rotary_cos=None, rotary_sin=None,
                        rotary_seqlens=None, rotary_interleaved=True):

@@ -251,7 +251,7 @@ int fa_fwd_validate(const fa_fwd_params *params);
  * device access; the text lives in thread-local storage until the next call on the same thread. */
 const char *fa_fwd_plan_name(const fa_fwd_params *params, int32_t num_cus);
 
-/* Test hook: the name of the plan the calling thread's most recent fa_fwd() (or fa_fwd_sink, fa_fwd_block_sparse, fa_fwd_kv8, fa_fwd_qv8, fa_fwd_sparse_kv) launched (same text as fa_fwd_plan_name on that
+/* Test hook: the name of the plan the calling thread's most recent fa_fwd() (or fa_fwd_sink, fa_fwd_block_sparse, fa_fwd_kv8, fa_fwd_qv8, fa_fwd_sparse_kv, fa_fwd_tree) launched (same text as fa_fwd_plan_name on that
  * call's params and the device's CU count; for a wide V run as several 256-column calls, the outer "... cols=N" plan).  NULL
  * before the first call or when that call failed validation; unspecified after a call that returned any other error (a failed
  * 256-column part leaves that part's plan).  fa_fwd keeps a struct copy; the text is made here, in
@@ -464,6 +464,59 @@ int fa_fwd_sparse_kv_validate(const fa_fwd_params *params, const fa_sparse_kv_pa
 int64_t fa_fwd_sparse_kv_workspace_size(const fa_fwd_params *params, const fa_sparse_kv_params *sparse);
 const char *fa_fwd_sparse_kv_plan_name(const fa_fwd_params *params, const fa_sparse_kv_params *sparse, int32_t num_cus);
 uint32_t fa_sparse_kv_params_size(void);
+
+/*
+ * Tree attention over a KV cache: the verify step of speculative decoding whose draft is a token TREE (Medusa, EAGLE-2,
+ * SpecInfer, sequoia) of up to 64 nodes.  The query rows of batch entry b are the sq(b) nodes of its tree (seqlen_q, or
+ * cu_seqlens_q[b + 1] - cu_seqlens_q[b] for ragged queries); the caller has appended their keys / values at positions
+ * [sk(b) - sq(b), sk(b)) of the cache, sk(b) = the fill level as the other cache routes compute it (seqused_k, clamped to the
+ * capacity, minus leftpad_k) INCLUDING the draft.
+ *   tree_mask  int64 on the device, logical shape (b, seqlen_q) behind the two element strides below; ragged queries: (total_q,),
+ *              row_stride alone (batch_stride is not read)
+ * With shift = sk(b) - sq(b) and t = j - shift, key j of batch b is visible to query row i of any head iff
+ *   j < sk(b)  AND  ( t < 0  OR  ( t < 64  AND  bit t of tree_mask[b, i] is set ) ),
+ * so the committed prefix is seen by every node; softcap applies as elsewhere.  Bits at or above sq(b) are ignored.  A tree key
+ * with t >= 64 is invisible: seqlen_q (the bound of every sq(b)) above 64 is refused, and a ragged entry that is longer at run
+ * time falls under this rule, without a fault.  No structure is assumed of the words: they need not be lower-triangular, and the
+ * diagonal bit is the caller's duty.  A chain is row i = bits 0 .. i, which is is_causal of the other routes.  A row with no
+ * visible key gives O = 0, LSE = +inf, split or not.  Positions in a tree are depths, not indices: there is no rotary here, the
+ * caller rotates q / k before the append.  Read-only.
+ * The host never reads the words or the fill levels: the call can be captured into a HIP graph, and a replay after both were
+ * overwritten in place computes the new tree.  The callee never allocates and never synchronises.
+ * params->dtype names q / o (fp16 / bf16).  fp8_cache = 0: k / v are 16-bit elements of that type, strides in elements, descales
+ * ignored.  fp8_cache != 0: k / v point at e4m3 BYTES with byte strides, and k_descale / v_descale (fa_fwd_kv8's meaning) are
+ * both required.
+ * One kernel, tr_fwd_kernel (csrc/fa_fwd_kernel_tr.h): the packed-row body of pk_fwd_kernel / kv8_fwd_kernel with the per-row
+ * word in place of the lane's key range; only the (at most two) 64-key tiles that reach past shift take the element mask.
+ * Served: a dense cache with seqused_k, kv_batch_idx and leftpad_k; a paged cache with any page_block_size >= 1; dense and ragged
+ * queries (cu_seqlens_q without cu_seqlens_k, seqused_k required); softcap; head dims <= 128 that are multiples of 16; split-KV
+ * over the key range.  num_splits: 1 = off, N > 1 = N parts (clamped to the key tiles), 0 = what fa_fwd's heuristic gives the pk
+ * shape (shapes only); partials, workspace layout and the merge (one fa_fwd_combine launch) are fa_fwd_kv8's, for both cache types.
+ * FA_ERR_UNSUPPORTED, checked before anything the params may lack: dtype fp8 (the all-fp8 call), d > 128 or d % 16 != 0, d_v
+ * set and != d, seqlen_q > 64, is_causal, a window side >= 0, attention_chunk, qv, ALiBi, dropout, s_dmask, cu_seqlens_k (and
+ * block_table beside kv_batch_idx or leftpad_k).  There is no sink argument and no rotary argument.  FA_ERR_NULL_POINTER: a NULL
+ * tree_mask, a missing descale with fp8_cache.  FA_ERR_BAD_STRIDE: tree_mask not 8-byte aligned, a negative stride.
+ * FA_ERR_WORKSPACE when a split call lacks its workspace (fa_fwd_tree_workspace_size() bytes, 256-byte aligned; 0 unsplit).
+ * fa_fwd_last_plan_name() names such a call
+ *   "tr_fwd_kernel D=<64|128> waves=4[ SOFTCAP] KV=<16|e4m3> block_m=128 splits=<N>";
+ * fa_fwd_tree_plan_name gives the same text from the two structs alone (num_cus decides nothing), NULL when fa_fwd_tree would
+ * reject them.
+ */
+typedef struct fa_tree_params {
+    uint32_t abi_version; /* FA_ABI_VERSION */
+    uint32_t struct_size; /* sizeof(fa_tree_params) */
+    const int64_t *tree_mask; /* device pointer, required */
+    int64_t batch_stride, row_stride; /* element strides, >= 0 */
+    int32_t fp8_cache; /* 0: 16-bit k / v; != 0: e4m3 bytes + descales */
+    int32_t reserved;
+} fa_tree_params;
+
+int fa_fwd_tree(const fa_fwd_params *params, const fa_tree_params *tree, void *stream);
+/* Validation only; no device access. */
+int fa_fwd_tree_validate(const fa_fwd_params *params, const fa_tree_params *tree);
+int64_t fa_fwd_tree_workspace_size(const fa_fwd_params *params, const fa_tree_params *tree);
+const char *fa_fwd_tree_plan_name(const fa_fwd_params *params, const fa_tree_params *tree, int32_t num_cus);
+uint32_t fa_tree_params_size(void);
 
 /* Human-readable text for a status code (static storage). */
 const char *fa_strerror(int status);
