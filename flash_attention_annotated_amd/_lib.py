@@ -1,4 +1,4 @@
-"""Build and loading of the native code: libfa_fwd_gfx950.so (the C-ABI of include/fa_fwd.h, fa_bwd.h, fa_rotary.h, fa_norm.h, fa_xent.h, fa_act.h, fa_gemm_act.h, fa_dropout_norm.h, fa_sample.h, fa_spec_sample.h, fa_block_select.h and fa_block_pattern.h) and
+"""Build and loading of the native code: libfa_fwd_gfx950.so (the C-ABI of include/fa_fwd.h, fa_bwd.h, fa_rotary.h, fa_norm.h, fa_xent.h, fa_act.h, fa_gemm_act.h, fa_dropout_norm.h, fa_sample.h, fa_spec_sample.h, fa_tree_sample.h, fa_block_select.h and fa_block_pattern.h) and
 the compiled host module flash_attn_2_cuda_C (csrc/torch_binding.cpp), which is the only host path of both operator
 surfaces.  Python launches nothing through ctypes: the struct mirrors below serve the ABI tests, `bench.py --variant`
 and the developer tools, which call the C-ABI directly.
@@ -121,6 +121,11 @@ SPEC_SAMPLE_SYMBOLS = ("fa_spec_sample", "fa_spec_sample_validate", "fa_spec_sam
                        "fa_spec_sample_plan")
 FA_SPEC_TOKENS_INT32, FA_SPEC_TOKENS_INT64 = 0, 1
 FA_SPEC_RECORD_BYTES = 24
+# every symbol include/fa_tree_sample.h declares (csrc/fa_tree_sample.hip)
+TREE_SAMPLE_SYMBOLS = ("fa_tree_sample", "fa_tree_sample_validate", "fa_tree_sample_params_size", "fa_tree_sample_workspace_size",
+                       "fa_tree_sample_plan")
+FA_TREE_TOKENS_INT32, FA_TREE_TOKENS_INT64 = 0, 1
+FA_TREE_RECORD_BYTES, FA_TREE_SAMPLE_MAX_NODES = 24, 64
 # every symbol include/fa_block_select.h declares (csrc/fa_block_select.hip)
 BLOCK_SELECT_SYMBOLS = tuple(f"fa_block_{unit}{suffix}" for unit in ("summary_update", "select")
                              for suffix in ("", "_validate", "_workspace_size", "_plan_name")) + (
@@ -456,6 +461,27 @@ class FaSpecSampleForm(ctypes.Structure):
                                               "index_passes", "frac_bits", "grid_a", "grid_b")]
 
 
+class FaTreeSampleParams(ctypes.Structure):
+    """Field-for-field mirror of `struct fa_tree_sample_params` (include/fa_tree_sample.h)."""
+
+    _fields_ = (
+        [("abi_version", ctypes.c_uint32), ("struct_size", ctypes.c_uint32)]
+        + [(n, ctypes.c_void_p) for n in ("logits", "logits_draft", "tokens_draft", "parents", "u_acc", "u_res", "rng_state", "workspace",
+                                          "path", "path_len", "tokens", "num_generated", "p_tok", "q_tok", "visited", "accepted")]
+        + [(n, ctypes.c_int64) for n in ("logits_batch_stride", "logits_node_stride", "draft_batch_stride", "draft_node_stride",
+                                         "tokens_draft_batch_stride", "parents_batch_stride", "workspace_bytes", "B")]
+        + [(n, ctypes.c_int32) for n in ("T", "V", "logits_dtype", "tokens_dtype", "top_k")]
+        + [("top_p", ctypes.c_float), ("temperature", ctypes.c_float), ("reserved", ctypes.c_int32)]
+    )
+
+
+class FaTreeSampleForm(ctypes.Structure):
+    """Field-for-field mirror of `struct fa_tree_sample_form` (include/fa_tree_sample.h): the form a tree verification call takes."""
+
+    _fields_ = [(n, ctypes.c_int32) for n in ("cw", "threads", "drafts", "topk", "topp", "k", "key_bits", "key_passes", "index_bits",
+                                              "index_passes", "frac_bits", "grid_a", "grid_b")]
+
+
 class FaBlockSummaryParams(ctypes.Structure):
     """Field-for-field mirror of `struct fa_block_summary_params` (include/fa_block_select.h)."""
 
@@ -671,7 +697,7 @@ def build(force=False, verbose=False):
     """Compile csrc/ for gfx950 into the in-tree shared library (hipcc cross-compiles without a GPU)."""
     srcs = [os.path.join(CSRC, f) for f in ("fa_fwd_api.hip", "fa_fwd_kv8_api.hip", "fa_fwd_qv8_api.hip", "fa_fwd_sparse_kv_api.hip", "fa_fwd_tree_api.hip", "fa_kvcache_append_kv8.hip",
                                               "fa_kvcache_append_qv8.hip", "fa_bwd_api.hip", "fa_bwd_bs_api.hip", "fa_rotary_emb.hip", "fa_norm.hip", "fa_xent.hip", "fa_act.hip", "fa_gemm_act.hip",
-                                              "fa_dropout_norm.hip", "fa_sample.hip", "fa_spec_sample.hip", "fa_block_select.hip",
+                                              "fa_dropout_norm.hip", "fa_sample.hip", "fa_spec_sample.hip", "fa_tree_sample.hip", "fa_block_select.hip",
                                               "fa_block_pattern.hip")]
     if not force and not is_stale():
         return LIB_PATH
@@ -801,6 +827,8 @@ _PROTOTYPES = {
     "fa_sample.h": tuple(_unit("fa", (("sample", FaSampleParams),), FaSampleForm)),
     "fa_spec_sample.h": tuple(_unit("fa_spec", (("sample", FaSpecSampleParams),), FaSpecSampleForm))
     + (("fa_spec_sample_workspace_size", [_I64, _I32], _I64),),
+    "fa_tree_sample.h": tuple(_unit("fa_tree", (("sample", FaTreeSampleParams),), FaTreeSampleForm))
+    + (("fa_tree_sample_workspace_size", [_I64, _I32], _I64),),
     "fa_block_select.h": tuple(
         row for unit, struct, size in (("fa_block_summary_update", FaBlockSummaryParams, "fa_block_summary_params_size"),
                                        ("fa_block_select", FaBlockSelectParams, "fa_block_select_params_size"))
@@ -949,6 +977,10 @@ def new_sample_params():
 
 def new_spec_sample_params():
     return _new(FaSpecSampleParams, ("logits",), tokens_dtype=FA_SPEC_TOKENS_INT64, temperature=1.0)
+
+
+def new_tree_sample_params():
+    return _new(FaTreeSampleParams, ("logits",), tokens_dtype=FA_TREE_TOKENS_INT64, temperature=1.0)
 
 
 def new_block_summary_params():

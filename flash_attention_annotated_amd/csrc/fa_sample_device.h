@@ -1,5 +1,5 @@
-// fa_sample_device.h — what the two sampling units (fa_sample.hip: the draw and the filter; fa_spec_sample.hip: the verification of
-// draft tokens) share: the row walks, the order-preserving key, the candidate set as a pair (K, J), the radix descent over
+// fa_sample_device.h — what the sampling units (fa_sample.hip: the draw and the filter; fa_spec_sample.hip: the verification of
+// a chain of draft tokens; fa_tree_sample.hip: of a tree of them) share: the row walks, the order-preserving key, the candidate set as a pair (K, J), the radix descent over
 // histograms in LDS, and the selection of a row's candidate set by top-k and top-p.  Everything here is an inline function:
 // including it adds no kernel to a unit and renames none.  The rule these functions implement is written out in
 // include/fa_sample.h; how a descent works, at the head of fa_sample.hip.
@@ -282,6 +282,33 @@ __device__ __forceinline__ Kept select_set(Shared &sh, const Row &row, const Sel
         }
     }
     return {set, Z, Zk};
+}
+
+// What a selection leaves behind of a row for a later launch (the verification units: a chain, fa_spec_sample.hip, and a tree,
+// fa_tree_sample.hip): 24 bytes in the workspace
+struct Record {
+    float m;  // the maximum of s; -inf: the row keeps nothing
+    uint32_t K;
+    int32_t J;
+    int32_t flags;  // the unit's own
+    uint64_t Zk;    // the sum of the weights of the kept set
+};
+
+// the record of a row, and its maximum into row.m
+template <int CW>
+__device__ __forceinline__ Record select_row(Shared &sh, Row &row, const Selection &how) {
+    row.m = row_max<CW>(sh, row);
+    if (row.m == -INFINITY) return {row.m, 0xffffffffu, 0, 0, 0u};  // (no key is above K and no index below J)
+    const Kept sel = select_set<CW, false>(sh, row, how);
+    return {row.m, sel.set.K, sel.set.J, 0, sel.Zk};
+}
+
+// P of the entry x at column i of a row with the record `rec` (row.m == rec.m)
+__device__ __forceinline__ float prob_of(const Row &row, const Record &rec, float x, int i) {
+    const float sv = row.s(x);
+    const Set kept = {rec.K, rec.J};
+    if (rec.Zk == 0 || !kept.has(full_key(sv) >> row.key_shift, i)) return 0.0f;
+    return (float)((double)row.scaled_e(sv) / (double)rec.Zk);  // (e, not its truncated weight: the smallest P keeps its digits)
 }
 
 // the uniform of row r under the seed mix `mix` (include/fa_sample.h)

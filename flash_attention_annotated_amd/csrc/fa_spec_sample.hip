@@ -1,6 +1,7 @@
 // fa_spec_sample.hip — fa_spec_sample (include/fa_spec_sample.h): the verification step of speculative sampling in two launches.
 // A translation unit of its own; the walks, the keys, the candidate set (K, J), the radix descent and the selection by top-k
-// and top-p are the inline functions of fa_sample_device.h, shared with fa_sample.hip, whose head says how a descent works.
+// and top-p, the Record of a row and the probability of an entry are the inline functions of fa_sample_device.h, shared with
+// fa_sample.hip, whose head says how a descent works, and with fa_tree_sample.hip.
 //
 // Phase A, spec_select_kernel<CW>: one workgroup per position (b, t), t <= S.  It selects the kept set of the target row and,
 // where t < S, of the draft row, exactly as the filter of fa_sample.hip does (all ties of the k-th value stay), writes a Record
@@ -15,13 +16,6 @@ namespace {
 
 using namespace fa_sample_dev;
 
-struct Record {
-    float m;  // the maximum of s; -inf: the row keeps nothing
-    uint32_t K;
-    int32_t J;
-    int32_t accept;  // of a target record of (b, t), t < S
-    uint64_t Zk;     // the sum of the weights of the kept set
-};
 static_assert(sizeof(Record) == FA_SPEC_RECORD_BYTES, "the record layout of include/fa_spec_sample.h");
 
 __device__ __forceinline__ Row target_row(const fa_spec_sample_params &p, const fa_spec_sample_form &f, int64_t b, int t) {
@@ -31,23 +25,6 @@ __device__ __forceinline__ Row target_row(const fa_spec_sample_params &p, const 
 __device__ __forceinline__ Row draft_row(const fa_spec_sample_params &p, const fa_spec_sample_form &f, int64_t b, int t) {
     const int64_t at = b * p.draft_batch_stride + (int64_t)t * p.draft_pos_stride;
     return make_row(const_cast<char *>(row_of(p.logits_draft, p.logits_dtype, at, 1)), p.logits_dtype, p.V, p.temperature, f.key_bits, f.frac_bits);
-}
-
-// the record of a row, and its maximum into row.m
-template <int CW>
-__device__ __forceinline__ Record select_row(Shared &sh, Row &row, const Selection &how) {
-    row.m = row_max<CW>(sh, row);
-    if (row.m == -INFINITY) return {row.m, 0xffffffffu, 0, 0, 0u};  // (no key is above K and no index below J)
-    const Kept sel = select_set<CW, false>(sh, row, how);
-    return {row.m, sel.set.K, sel.set.J, 0, sel.Zk};
-}
-
-// P of the entry x at column i of a row with the record `rec` (row.m == rec.m)
-__device__ __forceinline__ float prob_of(const Row &row, const Record &rec, float x, int i) {
-    const float sv = row.s(x);
-    const Set kept = {rec.K, rec.J};
-    if (rec.Zk == 0 || !kept.has(full_key(sv) >> row.key_shift, i)) return 0.0f;
-    return (float)((double)row.scaled_e(sv) / (double)rec.Zk);  // (e, not its truncated weight: the smallest P keeps its digits)
 }
 
 __device__ __forceinline__ int64_t draft_token(const fa_spec_sample_params &p, int64_t b, int t) {
@@ -80,12 +57,12 @@ __global__ __launch_bounds__(MAX_THREADS) void spec_select_kernel(const fa_spec_
                     P = prob_of(rp, a, load_one(rp.base, rp.dt, x), (int)x);
                     Q = prob_of(rq, d, load_one(rq.base, rq.dt, x), (int)x);
                     const float u = p.u_acc ? p.u_acc[at] : uniform_of(mix, at);
-                    a.accept = (double)u * (double)Q <= (double)P ? 1 : 0;
+                    a.flags = (double)u * (double)Q <= (double)P ? 1 : 0;
                 }
                 rec_q[at] = d;
                 if (p.p_tok) p.p_tok[at] = P;
                 if (p.q_tok) p.q_tok[at] = Q;
-                if (p.accepted) p.accepted[at] = a.accept;
+                if (p.accepted) p.accepted[at] = a.flags;
             }
         }
         if (threadIdx.x == 0) rec_p[r] = a;
@@ -101,7 +78,7 @@ __global__ __launch_bounds__(MAX_THREADS) void spec_resample_kernel(const fa_spe
     const uint32_t mix = p.rng_state ? seed_mix(p.rng_state) : 0u;
     for (int64_t b = blockIdx.x; b < p.B; b += gridDim.x) {
         int n = S;  // (the same loads in every thread)
-        for (int t = S - 1; t >= 0; --t) n = rec_p[b * (S + 1) + t].accept ? n : t;
+        for (int t = S - 1; t >= 0; --t) n = rec_p[b * (S + 1) + t].flags ? n : t;
         const Record a = rec_p[b * (S + 1) + n];
         Row rp = target_row(p, f, b, n);
         rp.m = a.m;

@@ -28,6 +28,7 @@
 #include "fa_xent.h"
 #include "fa_sample.h"
 #include "fa_spec_sample.h"
+#include "fa_tree_sample.h"
 #include "fa_block_select.h"
 #include "fa_block_pattern.h"
 #include "fa_act.h"
@@ -2886,6 +2887,100 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> sample_speculative_impl(const
     return {tokens, num, p_tok, q_tok, accepted};
 }
 
+// ---- fused acceptance walk over a tree of draft tokens (utils.generation.sample_speculative_tree; include/fa_tree_sample.h).
+// Launches on the current stream, no synchronisation; the outputs and the records' workspace come from the caching allocator:
+// capturable in a HIP graph.
+py::dict tree_sample_plan_dict(const fa_tree_sample_form &l) {
+    return plan_dict(l, {"cw", "threads", "drafts", "topk", "topp", "k", "key_bits", "key_passes", "index_bits", "index_passes",
+                         "frac_bits", "grid_a", "grid_b"});
+}
+
+// (tokens (B, T) of the dtype of tokens_draft, num_generated (B) int64, path (B, T) int32, path_len (B) int32, p_tok, q_tok (B, T)
+// fp32, visited, accepted (B, T) int32); the last four are empty without `stats`.  logits_draft absent: the one-hot rule.  The
+// uniforms are (u_acc, u_res), or `rng_state` = (seed, offset) on the device, or with neither that pair drawn on the device from
+// the default generator
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> sample_speculative_tree_impl(
+    const Tensor &logits, const OptTensor &logits_draft, const Tensor &tokens_draft, const Tensor &parents, int64_t top_k, double top_p,
+    double temperature, const OptTensor &u_acc, const OptTensor &u_res, const OptTensor &rng_state, bool stats, fa_tree_sample_form *plan) {
+    const char *op = "sample_speculative_tree: ";
+    TORCH_CHECK(logits.is_cuda() && tokens_draft.is_cuda() && parents.is_cuda(), op, "logits, tokens_draft and parents must be on CUDA");
+    TORCH_CHECK(logits.dim() == 3 && logits.size(1) >= 1 && logits.size(1) <= FA_TREE_SAMPLE_MAX_NODES, op,
+                "logits must have shape (batch_size, nodes, vocab_size) with 1 <= nodes <= 64");
+    const int64_t B = logits.size(0), T = logits.size(1), V = logits.size(2);
+    TORCH_CHECK(V >= 1 && V <= std::numeric_limits<int32_t>::max(), op, "logits must have 1 <= vocab_size < 2^31 columns");
+    TORCH_CHECK(B * 2 * T <= std::numeric_limits<int32_t>::max(), op, "batch_size * 2 nodes must be below 2^31");
+    TORCH_CHECK(tokens_draft.dim() == 2 && tokens_draft.size(0) == B && tokens_draft.size(1) == T, op,
+                "tokens_draft must have shape (batch_size, nodes)");
+    TORCH_CHECK(parents.dim() == 2 && parents.size(0) == B && parents.size(1) == T && parents.scalar_type() == at::kInt, op,
+                "parents must be int32 of shape (batch_size, nodes)");
+    TORCH_CHECK(logits.stride(-1) == 1 || V == 1, op, "logits must have contiguous last dimension");
+    TORCH_CHECK((tokens_draft.stride(-1) == 1 && parents.stride(-1) == 1) || T == 1, op,
+                "tokens_draft and parents must have contiguous last dimension");
+    TORCH_CHECK(tokens_draft.scalar_type() == at::kLong || tokens_draft.scalar_type() == at::kInt, op, "tokens_draft must be int32 or int64");
+    if (logits_draft.has_value()) {
+        TORCH_CHECK(logits_draft->is_cuda() && logits_draft->dim() == 3 && logits_draft->size(0) == B && logits_draft->size(1) == T &&
+                        logits_draft->size(2) == V, op, "logits_draft must be on CUDA with shape (batch_size, nodes, vocab_size)");
+        TORCH_CHECK(logits_draft->stride(-1) == 1 || V == 1, op, "logits_draft must have contiguous last dimension");
+        TORCH_CHECK(logits_draft->scalar_type() == logits.scalar_type(), op, "logits_draft must have the dtype of logits");
+    }
+    TORCH_CHECK(top_k >= 0 && top_k <= std::numeric_limits<int32_t>::max(), op, "top_k must be in [0, 2^31)");
+    TORCH_CHECK(u_acc.has_value() == u_res.has_value(), op, "u_acc and u_res come together");
+    TORCH_CHECK(!(u_res.has_value() && rng_state.has_value()), op, "u and rng_state exclude each other");
+    if (u_res.has_value()) {
+        check_vector(op, *u_res, "u_res", B, "(batch_size)", true);
+        TORCH_CHECK(u_acc->is_cuda() && u_acc->dim() == 2 && u_acc->size(0) == B && u_acc->size(1) == T && u_acc->is_contiguous(), op,
+                    "u_acc must have shape (batch_size, nodes) and be contiguous");
+        TORCH_CHECK(u_res->scalar_type() == at::kFloat && u_acc->scalar_type() == at::kFloat, op, "u_acc and u_res must be fp32");
+    }
+    if (rng_state.has_value())
+        TORCH_CHECK(rng_state->is_cuda() && rng_state->scalar_type() == at::kLong && rng_state->numel() == 2 && rng_state->is_contiguous(),
+                    op, "rng_state must be two int64 on the device");
+    auto p = new_params<fa_tree_sample_params>();
+    p.logits_dtype = row_dtype_code(op, logits.scalar_type(), "logits");
+    p.tokens_dtype = tokens_draft.scalar_type() == at::kLong ? FA_TREE_TOKENS_INT64 : FA_TREE_TOKENS_INT32;
+    c10::hip::HIPGuardMasqueradingAsCUDA device_guard(logits.device());
+    const auto f32 = logits.options().dtype(at::kFloat), i32 = logits.options().dtype(at::kInt);
+    Tensor tokens = at::empty({B, T}, tokens_draft.options()), num = at::empty({B}, logits.options().dtype(at::kLong));
+    Tensor path = at::empty({B, T}, i32), path_len = at::empty({B}, i32);
+    Tensor p_tok = stats ? at::empty({B, T}, f32) : none(f32), q_tok = stats ? at::empty({B, T}, f32) : none(f32);
+    Tensor visited = stats ? at::empty({B, T}, i32) : none(i32), accepted = stats ? at::empty({B, T}, i32) : none(i32);
+    TORCH_CHECK(B > 0 || !plan, op, "a plan needs at least one sequence");
+    if (B == 0) return {tokens, num, path, path_len, p_tok, q_tok, visited, accepted};
+    Tensor state;  // (kept alive to the launch)
+    if (u_res.has_value()) {
+        p.u_res = static_cast<const float *>(u_res->data_ptr());
+        p.u_acc = static_cast<const float *>(u_acc->data_ptr());
+    } else if (rng_state.has_value()) {
+        p.rng_state = static_cast<const uint64_t *>(rng_state->data_ptr());
+    } else if (plan) {
+        p.rng_state = reinterpret_cast<const uint64_t *>(uintptr_t(16));  // (a plan reads no memory)
+    } else {
+        state = dropout_state(1.0, c10::nullopt, logits);
+        p.rng_state = static_cast<const uint64_t *>(state.data_ptr());
+    }
+    p.workspace_bytes = fa_tree_sample_workspace_size(B, (int32_t)T);
+    Tensor workspace = at::empty({p.workspace_bytes}, logits.options().dtype(at::kByte));
+    p.workspace = workspace.data_ptr();
+    p.logits = logits.data_ptr();
+    p.logits_draft = logits_draft.has_value() ? logits_draft->data_ptr() : nullptr;
+    p.tokens_draft = tokens_draft.data_ptr();
+    p.parents = static_cast<const int32_t *>(parents.data_ptr());
+    p.path = static_cast<int32_t *>(path.data_ptr()); p.path_len = static_cast<int32_t *>(path_len.data_ptr());
+    p.tokens = tokens.data_ptr();
+    p.num_generated = static_cast<int64_t *>(num.data_ptr());
+    if (stats) {
+        p.p_tok = static_cast<float *>(p_tok.data_ptr()); p.q_tok = static_cast<float *>(q_tok.data_ptr());
+        p.visited = static_cast<int32_t *>(visited.data_ptr()); p.accepted = static_cast<int32_t *>(accepted.data_ptr());
+    }
+    p.logits_batch_stride = logits.stride(0); p.logits_node_stride = logits.stride(1);
+    if (logits_draft.has_value()) { p.draft_batch_stride = logits_draft->stride(0); p.draft_node_stride = logits_draft->stride(1); }
+    p.tokens_draft_batch_stride = tokens_draft.stride(0); p.parents_batch_stride = parents.stride(0);
+    p.B = B; p.T = (int32_t)T; p.V = (int32_t)V;
+    p.top_k = (int32_t)top_k; p.top_p = (float)top_p; p.temperature = (float)temperature;
+    launch_or_plan("fa_tree_sample", fa_tree_sample, fa_tree_sample_plan, p, plan, logits);
+    return {tokens, num, path, path_len, p_tok, q_tok, visited, accepted};
+}
+
 // ---- block summaries of the keys and the Quest block selection (hopper_interface.kvcache_block_summary_update /
 // kvcache_select_blocks; include/fa_block_select.h): what produces the lists fwd_kvcache_sparse reads.  Launches on the current
 // stream, nothing is read on the host; every tensor the launches write is an argument: capturable in a HIP graph.  plan: the
@@ -3430,6 +3525,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     def_row_op(m, "sample_speculative", sample_speculative_impl, spec_sample_plan_dict,
                "fused verification of draft tokens (speculative sampling): (tokens, num_generated, p_tok, q_tok, accepted)",
                py::arg("logits"), py::arg("logits_draft"), py::arg("tokens_draft"), py::arg("top_k"), py::arg("top_p"),
+               py::arg("temperature"), py::arg("u_acc"), py::arg("u_res"), py::arg("rng_state"), py::arg("stats"));
+    def_row_op(m, "sample_speculative_tree", sample_speculative_tree_impl, tree_sample_plan_dict,
+               "fused acceptance walk over a tree of draft tokens: (tokens, num_generated, path, path_len, p_tok, q_tok, visited, accepted)",
+               py::arg("logits"), py::arg("logits_draft"), py::arg("tokens_draft"), py::arg("parents"), py::arg("top_k"), py::arg("top_p"),
                py::arg("temperature"), py::arg("u_acc"), py::arg("u_res"), py::arg("rng_state"), py::arg("stats"));
     m.def("sample", &sample, "fused top-k / top-p sampling of a token per row: (token, kept, mass)", py::arg("logits"), py::arg("top_k"),
           py::arg("top_p"), py::arg("temperature"), py::arg("u"), py::arg("rng_state"), py::arg("stats"));

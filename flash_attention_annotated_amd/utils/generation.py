@@ -7,6 +7,8 @@
     sample_speculative                                     :209-265
     sample_ref, filter_ref, uniform_ref          pure torch: the contract of include/fa_sample.h, the CPU oracle
     sample_speculative_ref                       pure torch: the contract of include/fa_spec_sample.h, the CPU oracle
+    sample_speculative_tree                      not in the reference: the acceptance walk over a TREE of draft tokens
+    sample_speculative_tree_ref                  pure torch: the contract of include/fa_tree_sample.h, the CPU oracle
 
 Same signatures and defaults; `sample` and `sample_speculative` have two keyword-only additions, `generator` and `u`.  Where the reference chains topk,
 a full sort, softmax, cumsum, scatter, masked_fill and multinomial, CUDA tensors here take one launch of the HIP kernels of
@@ -21,6 +23,11 @@ include/fa_spec_sample.h.  One thing differs from the reference on purpose: the 
 `tokens[:, first_rejected_idx] = resample`, which for a batch of more than one sequence sets whole columns (every sequence gets
 the other sequences' resampled tokens at their rejection columns).  Here the write is per row, `tokens[b, first_rejected_idx[b]]
 = resample[b]`, which is what the algorithm means; the tokens up to `num_generated` are the valid ones either way.
+
+`sample_speculative_tree` does the same for a draft that is a token tree (SpecInfer's multi-round rejection, arXiv 2305.09781; a
+one-hot rule for deterministic drafters such as Medusa and EAGLE): it follows `flash_attn_with_kvcache_tree`, walks down from the
+root accepting at most one child per level, draws one more token, and returns the `path` / `path_len` that
+`kvcache_keep_tree_path_` takes.  Two launches of csrc/fa_tree_sample.hip; the rule is written out in include/fa_tree_sample.h.
 
 The rule is written out in include/fa_sample.h.  Unlike the reference's, it leaves no tie open: the token is a function of
 (logits, top_k, top_p, temperature, u).  Without `u` the uniforms come from a counter hash of (row, seed, offset), and (seed,
@@ -39,7 +46,8 @@ from torch import Tensor
 from .._lib import binding as _binding
 
 __all__ = ["InferenceParams", "modify_logits_for_top_k_filtering", "modify_logits_for_top_p_filtering", "sample", "sample_ref",
-           "filter_ref", "uniform_ref", "sample_speculative", "sample_speculative_ref"]
+           "filter_ref", "uniform_ref", "sample_speculative", "sample_speculative_ref", "sample_speculative_tree",
+           "sample_speculative_tree_ref"]
 
 _custom_op = torch.library.custom_op
 _register_fake = torch.library.register_fake
@@ -109,6 +117,36 @@ def _sample_speculative_fake(logits, logits_draft, tokens_draft, top_k, top_p, t
     shape = (b, s) if stats else (0,)
     return (tokens_draft.new_empty((b, s + 1)), logits.new_empty((b,), dtype=torch.int64), logits.new_empty(shape, dtype=torch.float32),
             logits.new_empty(shape, dtype=torch.float32), logits.new_empty(shape, dtype=torch.int32))
+
+
+@_custom_op("flash_attn_amd::_sample_speculative_tree", mutates_args=(), device_types="cuda")
+def _sample_speculative_tree(logits: Tensor, logits_draft: Optional[Tensor], tokens_draft: Tensor, parents: Tensor, top_k: int,
+                             top_p: float, temperature: float, u_acc: Optional[Tensor], u_res: Optional[Tensor],
+                             rng_state: Optional[Tensor],
+                             stats: bool) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """(tokens (batch, nodes) of the dtype of tokens_draft, num_generated (batch,) int64, path (batch, nodes) int32, path_len
+    (batch,) int32, p_tok, q_tok (batch, nodes) fp32, visited, accepted (batch, nodes) int32); the last four are empty without
+    `stats`.  The uniforms are (`u_acc`, `u_res`), else `rng_state` = (seed, offset) on the device; `sample_speculative_tree`
+    always passes one of them: the op has no hidden state."""
+    return _binding().sample_speculative_tree(logits, logits_draft, tokens_draft, parents, top_k, top_p, temperature, u_acc, u_res,
+                                              rng_state, stats)
+
+
+@_register_fake("flash_attn_amd::_sample_speculative_tree")
+def _sample_speculative_tree_fake(logits, logits_draft, tokens_draft, parents, top_k, top_p, temperature, u_acc, u_res, rng_state, stats):
+    b, t = tokens_draft.shape
+    shape = (b, t) if stats else (0,)
+    return (tokens_draft.new_empty((b, t)), logits.new_empty((b,), dtype=torch.int64), logits.new_empty((b, t), dtype=torch.int32),
+            logits.new_empty((b,), dtype=torch.int32), logits.new_empty(shape, dtype=torch.float32),
+            logits.new_empty(shape, dtype=torch.float32), logits.new_empty(shape, dtype=torch.int32),
+            logits.new_empty(shape, dtype=torch.int32))
+
+
+def _plan_sample_speculative_tree(logits, logits_draft, tokens_draft, parents, top_k=1, top_p=0.0, temperature=1.0):
+    """The form `sample_speculative_tree` takes with these tensors, launching nothing: fa_tree_sample_form
+    (include/fa_tree_sample.h) as a dict."""
+    return _binding().sample_speculative_tree_plan(logits, logits_draft, tokens_draft, parents, top_k, top_p, temperature, None, None,
+                                                   None, False)
 
 
 def _plan_sample_speculative(logits, logits_draft, tokens_draft, top_k=1, top_p=0.0, temperature=1.0):
@@ -304,6 +342,133 @@ def sample_speculative_ref(logits, logits_draft, tokens_draft, top_k, top_p, tem
     return tokens, n + 1, p_tok, q_tok, accepted.int(), margin, torch.minimum(mp[:, :s], mq), m_acc
 
 
+def sample_speculative_tree_ref(logits, logits_draft, tokens_draft, parents, top_k, top_p, temperature, u, stats=False):
+    """The contract of include/fa_tree_sample.h in torch, literally and with stable sorts: (tokens (B, T) of the dtype of
+    tokens_draft, num_generated (B,) int64, path (B, T) int32, path_len (B,) int32) from logits (B, T, V), logits_draft (B, T, V)
+    or None (the one-hot rule), tokens_draft (B, T), parents (B, T) and the uniforms u = (u_acc (B, T), u_res (B,)); in fp64 where
+    logits are fp64 and in fp32 otherwise.  The nodes are taken in index order, which is the order of the walk: a child follows
+    its parent and its earlier siblings.  Probabilities are floating point (P - c Q in two roundings, not the header's fmaf and
+    fixed point): what separates the two is what `margin` measures.
+    With `stats`: (tokens, num_generated, path, path_len, p_tok, q_tok, visited, accepted, margin).  margin (B,) is the least
+    distance of a comparison made along the walk of the sequence from the value it compares with: the top-p cumulative sums of
+    the rows of every node on the path (the draft row where a child was tried), the acceptance tests (round 0: |u q - p| relative
+    to max(p, q); later rounds |u q - r_x / R| relative to max(q, r_x / R); one-hot: |u Z_r - w_x| relative to max(w_x, Z_r)), the
+    sums R(c) and Z_r (compared with 0) and the cumulative sums of the draw's weights (compared with u_res times their total).
+    Sequences where it is small are those whose result rounding may change.  With stats == "positions" one more follows, (B, T):
+    the lesser top-p margin of the rows of a node's parent, on which its p_tok and q_tok rest."""
+    b, t, v = logits.shape
+    dev = logits.device
+    u_acc, u_res = u
+    drafts = logits_draft is not None
+    P, mp = _kept_probs(logits.reshape(b * t, v), top_k, top_p, temperature)
+    P, mp = P.view(b, t, v), mp.view(b, t)
+    dt = P.dtype
+    if drafts:
+        Q, mq = _kept_probs(logits_draft.reshape(b * t, v), top_k, top_p, temperature)
+        Q, mq = Q.view(b, t, v), mq.view(b, t)
+    inf = torch.tensor(float("inf"), dtype=dt, device=dev)
+    zero, one = torch.zeros((), dtype=dt, device=dev), torch.ones((), dtype=dt, device=dev)
+    rows = torch.arange(b, device=dev)
+    par_all = parents.long()
+    n = torch.zeros(b, dtype=torch.int64, device=dev)    # the node the walk is at
+    m = torch.zeros(b, dtype=torch.int64, device=dev)    # the rejections at n
+    c = torch.zeros(b, dtype=dt, device=dev)
+    R = torch.zeros(b, dtype=dt, device=dev)             # R(c) of the last rejection at n; one-hot: Z_r
+    done = torch.zeros(b, dtype=torch.bool, device=dev)  # nothing is left at n: its siblings are not tried
+    gone = torch.zeros(b, v, dtype=torch.bool, device=dev)  # one-hot: the tokens rejected at n
+    margin = mp[:, 0].clone()
+    p_tok, q_tok = torch.zeros(b, t, dtype=dt, device=dev), torch.zeros(b, t, dtype=dt, device=dev)
+    m_rows = torch.full((b, t), float("inf"), dtype=dt, device=dev)
+    visited, accepted = torch.zeros(b, t, dtype=torch.int32, device=dev), torch.zeros(b, t, dtype=torch.int32, device=dev)
+    path = torch.zeros(b, t, dtype=torch.int32, device=dev)
+    length = torch.ones(b, dtype=torch.int64, device=dev)
+    if not drafts:
+        R = P[:, 0].sum(dim=1)
+    for i in range(1, t):
+        par = par_all[:, i]
+        present = (par >= 0) & (par < i)
+        pc = par.clamp(0, i - 1)
+        x = tokens_draft[:, i].long()
+        inside = (x >= 0) & (x < v)  # a token outside [0, V) is rejected, and nothing is read for it
+        xc = x.clamp(0, v - 1)
+        p0 = torch.where(present & inside, P[rows, pc, xc], zero)
+        q0 = torch.where(present & inside, Q[rows, pc, xc] if drafts else one, zero)
+        p_tok[:, i], q_tok[:, i] = p0, q0
+        m_rows[:, i] = torch.where(present, torch.minimum(mp[rows, pc], mq[rows, pc]) if drafts else mp[rows, pc], inf)
+        run = present & (par == n) & ~done
+        if not bool(run.any()):
+            continue
+        ui = u_acc[:, i].to(dt)
+        Pn = P[rows, n]
+        if drafts:
+            Qn = Q[rows, n]
+            margin = torch.where(run, torch.minimum(margin, mq[rows, n]), margin)
+            first = m == 0
+            rx = (p0 - c * q0).clamp_min(0.0)
+            lhs = torch.where(first, ui * q0, ui * q0 * R)
+            rhs = torch.where(first, p0, rx)
+            ok = (lhs <= rhs) & inside
+            share = torch.where(first, p0, rx / torch.where(R > 0, R, torch.ones_like(R)))  # (R > 0 where a later round runs)
+            larger = torch.maximum(share, q0)
+            m_acc = torch.where(inside & (larger > 0), (ui * q0 - share).abs() / torch.where(larger > 0, larger, torch.ones_like(larger)), inf)
+        else:
+            w = torch.where(inside & ~gone[rows, xc], p0, zero)
+            ok = (w > 0) & (ui * R <= w)
+            larger = torch.maximum(w, R)
+            m_acc = torch.where(w > 0, (ui * R - w).abs() / torch.where(larger > 0, larger, torch.ones_like(larger)), inf)
+        margin = torch.where(run, torch.minimum(margin, m_acc), margin)
+        visited[:, i] = run.int()
+        yes, no = run & ok, run & ~ok
+        accepted[:, i] = yes.int()
+        # rejected: the next round's c and R
+        if drafts:
+            c_next = torch.where(first, torch.ones_like(c), c + R)
+            R_next = (Pn - c_next[:, None] * Qn).clamp_min(0.0).sum(dim=1)
+            c, R = torch.where(no, c_next, c), torch.where(no, R_next, R)
+        else:
+            gone[rows[no & (w > 0)], xc[no & (w > 0)]] = True
+            R = torch.where(no, R - w, R)
+        m = torch.where(no, m + 1, m)
+        done = done | (no & (R <= 0))
+        margin = torch.where(no & (R > 0), torch.minimum(margin, R), margin)  # (a sum of exactly 0: of rows equal entry by entry)
+        # accepted: down to i
+        path[rows[yes], length[yes]] = i
+        length = torch.where(yes, length + 1, length)
+        n = torch.where(yes, torch.full_like(n, i), n)
+        m, c = torch.where(yes, torch.zeros_like(m), m), torch.where(yes, torch.zeros_like(c), c)
+        margin = torch.where(yes, torch.minimum(margin, mp[:, i]), margin)
+        if drafts:
+            R = torch.where(yes, torch.zeros_like(R), R)
+        else:
+            R = torch.where(yes, P[:, i].sum(dim=1), R)
+            gone[yes] = False
+    Pn = P[rows, n]
+    if drafts:
+        residual = (Pn - c[:, None] * Q[rows, n]).clamp_min(0.0)
+        from_p = (m == 0) | (residual.sum(dim=1) <= 0)  # no child, or no residual weight: p_n itself
+        w = torch.where(from_p[:, None], Pn, residual)
+    else:
+        w = Pn.masked_fill(gone, 0.0)
+    total = w.sum(dim=1)
+    cum, at = w.cumsum(dim=1), (u_res.to(dt) * total)[:, None]  # (the share exceeds u where the sum exceeds u * total)
+    positive = w > 0
+    hit = (cum > at) & positive
+    last = v - 1 - positive.flip(1).int().argmax(dim=1)
+    token = torch.where(hit.any(dim=1), hit.int().argmax(dim=1), last)
+    token = torch.where(total > 0, token, torch.zeros_like(token))  # (a target row that keeps nothing, or nothing left of it)
+    # the tokens of the path without the root's, then the drawn one
+    cols = torch.arange(t, device=dev)[None, :]
+    nxt = torch.cat([path[:, 1:], path.new_zeros(b, 1)], dim=1).long()
+    tokens = torch.where(cols < length[:, None] - 1, tokens_draft.gather(1, nxt), torch.zeros_like(tokens_draft))
+    tokens[rows, length - 1] = token.to(tokens.dtype)
+    out = (tokens, length.clone(), path, length.int())
+    if not stats:
+        return out
+    margin = torch.minimum(margin, (cum - at).abs().masked_fill(~positive, float("inf")).min(dim=1).values)
+    out = out + (p_tok, q_tok, visited, accepted, margin)
+    return out + (m_rows,) if stats == "positions" else out
+
+
 def _lowbias32(x):
     x = x ^ (x >> 16)
     x = (x * 0x7FEB352D) & 0xFFFFFFFF
@@ -416,3 +581,64 @@ def sample_speculative(logits, logits_draft, tokens_draft, top_k=1, top_p=0.0, t
         rng_state = torch.randint(-(1 << 62), 1 << 62, (2,), generator=generator, device=logits.device, dtype=torch.int64)
     u_acc, u_res = u if u is not None else (None, None)
     return _sample_speculative(logits, logits_draft, tokens_draft, top_k, top_p, temperature, u_acc, u_res, rng_state, False)[:2]
+
+
+def sample_speculative_tree(logits, logits_draft, tokens_draft, parents, top_k=1, top_p=0.0, temperature=1.0, *, generator=None,
+                            u=None, stats=False):
+    """Verify a TREE of draft tokens per sequence against the target model: walk down from the root, accepting at most one child
+    per level by multi-round rejection (SpecInfer, arXiv 2305.09781), and emit the accepted path plus one more token.  What
+    follows `flash_attn_with_kvcache_tree` in a tree-shaped verify step; `path` and `path_len` are what
+    `kvcache_keep_tree_path_` takes.  Not in the reference.  The rule is in include/fa_tree_sample.h.
+
+    logits        (batch, nodes, vocab) target logits, fp16 / bf16 / fp32, any batch and node stride; row n is the distribution
+                  of the token that follows node n.  1 <= nodes <= 64
+    logits_draft  (batch, nodes, vocab) of the same dtype: row n is the distribution the children of node n were drawn from,
+                  independently (duplicates allowed); or None for a deterministic drafter (Medusa / EAGLE with top-m children):
+                  a child is accepted with the target's probability of its token among the tokens not yet rejected at its parent
+    tokens_draft  (batch, nodes) int32 or int64: the token of every node; entry 0, the root's (the last committed token), is not
+                  read
+    parents       (batch, nodes) int32: parents[b, i] in [0, i) is the parent of node i > 0; any other value (-1) marks an absent
+                  node, the padding of ragged trees, as in `tree_mask_from_parents`.  The children of a node are tried in
+                  ascending index order
+    top_k, top_p, temperature: as in `sample_speculative`, applied to both models' rows
+    generator     the torch.Generator (of the logits' device) that (seed, offset) are drawn from; default: the device's own
+    u             (u_acc (batch, nodes), u_res (batch,)) fp32 uniforms in [0, 1): u_acc[b, i] tests node i (entry 0 unused), u_res
+                  draws the last token; instead of a generator
+
+    -> (tokens (batch, nodes) of the dtype of tokens_draft, num_generated (batch,) int64, path (batch, nodes) int32, path_len
+    (batch,) int32).  path[b, :path_len[b]] are the accepted nodes in ascending order, the root first; tokens[b, :num_generated[b]]
+    are their tokens without the root's and then the token drawn behind the last of them; num_generated = path_len.  Behind
+    them both hold 0.  With `stats` four more follow, (batch, nodes) each: p_tok, q_tok fp32 (the target's and the draft's
+    probability of a node's token under its parent, before any rejection), visited and accepted int32.  Nothing is modified.
+    A chain (parents = -1, 0, 1, ...) is `sample_speculative`, bit for bit.
+    """
+    if logits.dim() != 3 or not 1 <= logits.shape[1] <= 64:
+        raise ValueError("logits must have shape (batch, nodes, vocab) with 1 <= nodes <= 64")
+    b, t, v = logits.shape
+    if logits_draft is not None and tuple(logits_draft.shape) != (b, t, v):
+        raise ValueError(f"logits_draft must have shape {(b, t, v)}: got {tuple(logits_draft.shape)}")
+    if tuple(tokens_draft.shape) != (b, t) or tuple(parents.shape) != (b, t):
+        raise ValueError(f"tokens_draft and parents must have shape {(b, t)}: got {tuple(tokens_draft.shape)} and {tuple(parents.shape)}")
+    if tokens_draft.dtype not in (torch.int32, torch.int64):
+        raise TypeError("tokens_draft must be int32 or int64")
+    if top_p > 1.0:
+        raise ValueError("top_p must be at most 1")
+    top_p = max(float(top_p), 0.0)
+    if not logits.is_cuda:
+        if u is None:
+            u = (torch.rand(b, t, generator=generator, device=logits.device), torch.rand(b, generator=generator, device=logits.device))
+        out = sample_speculative_tree_ref(logits, logits_draft, tokens_draft, parents, top_k, top_p, temperature, u, stats=bool(stats))
+        return out[:8] if stats else out
+    if v > 1 and (logits.stride(-1) != 1 or (logits_draft is not None and logits_draft.stride(-1) != 1)):
+        raise ValueError("logits and logits_draft must have a contiguous last dimension")
+    if t > 1 and tokens_draft.stride(-1) != 1:
+        tokens_draft = tokens_draft.contiguous()
+    if parents.dtype != torch.int32 or (t > 1 and parents.stride(-1) != 1):
+        parents = parents.to(torch.int32).contiguous()
+    rng_state = None
+    if u is None:  # drawn here, not inside the op: the op is a function of its arguments
+        rng_state = torch.randint(-(1 << 62), 1 << 62, (2,), generator=generator, device=logits.device, dtype=torch.int64)
+    u_acc, u_res = u if u is not None else (None, None)
+    out = _sample_speculative_tree(logits, logits_draft, tokens_draft, parents, top_k, top_p, temperature, u_acc, u_res, rng_state,
+                                   bool(stats))
+    return out if stats else out[:4]
