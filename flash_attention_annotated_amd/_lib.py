@@ -75,6 +75,11 @@ EXPORTED_SYMBOLS = (
     "fa_fwd_tree_workspace_size",
     "fa_fwd_tree_plan_name",
     "fa_tree_params_size",
+    "fa_fwd_topk_kv",
+    "fa_fwd_topk_kv_validate",
+    "fa_fwd_topk_kv_workspace_size",
+    "fa_fwd_topk_kv_plan_name",
+    "fa_topk_kv_params_size",
     # include/fa_bwd.h
     "fa_bwd",
     "fa_bwd_validate",
@@ -645,6 +650,14 @@ class FaTreeParams(ctypes.Structure):
                 ("batch_stride", ctypes.c_int64), ("row_stride", ctypes.c_int64), ("fp8_cache", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
+class FaTopkKvParams(ctypes.Structure):
+    """Field-for-field mirror of `struct fa_topk_kv_params` (include/fa_fwd.h)."""
+
+    _fields_ = [("abi_version", ctypes.c_uint32), ("struct_size", ctypes.c_uint32), ("indices", ctypes.c_void_p),
+                ("batch_stride", ctypes.c_int64), ("row_stride", ctypes.c_int64), ("head_stride", ctypes.c_int64),
+                ("topk", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
 class FaBlockSparseBwdParams(ctypes.Structure):
     """Field-for-field mirror of `struct fa_block_sparse_bwd_params` (include/fa_bwd.h)."""
 
@@ -668,6 +681,7 @@ class FaSinkGradParams(ctypes.Structure):
 
 
 HASH_PATH = os.path.join(_HERE, "libfa_fwd_gfx950.srchash")
+NO_PACKED_FP32_UNITS = ("fa_fwd_topk_kv_api.hip",)
 
 
 def _deps():
@@ -704,11 +718,22 @@ def build(force=False, verbose=False):
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     if not os.path.exists(hipcc):
         hipcc = "hipcc"
-    cmd = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
-           "-I", INCLUDE, "-I", CSRC, *srcs, "-o", LIB_PATH]
-    if verbose:
-        print(" ".join(cmd), file=sys.stderr)
-    subprocess.run(cmd, check=True)
+    common = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-I", INCLUDE, "-I", CSRC]
+    import tempfile
+    with tempfile.TemporaryDirectory(prefix="fa_obj_") as tmp:
+        # units compiled without the packed fp32 instructions (v_pk_mul_f32 / v_pk_add_f32 / v_pk_fma_f32): an object each,
+        # linked beside the other units, whose device code stays what their tests pin
+        objs = []
+        for unit in NO_PACKED_FP32_UNITS:
+            objs.append(os.path.join(tmp, os.path.splitext(unit)[0] + ".o"))
+            cmd = [*common, "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops", "-c", os.path.join(CSRC, unit), "-o", objs[-1]]
+            if verbose:
+                print(" ".join(cmd), file=sys.stderr)
+            subprocess.run(cmd, check=True)
+        cmd = [*common, "-shared", *objs, *srcs, "-o", LIB_PATH]  # (objects first: hipcc puts `-x hip` in front of every source)
+        if verbose:
+            print(" ".join(cmd), file=sys.stderr)
+        subprocess.run(cmd, check=True)
     build_binding(verbose)
     with open(HASH_PATH, "w") as f:
         f.write(source_hash() + "\n")
@@ -757,7 +782,7 @@ def _unit(prefix, structs, plan_struct, workspace_struct=None):
 
 _FWD, _BWD, _KV8 = _P(FaFwdParams), _P(FaBwdParams), _P(FaKvcacheAppendKv8Params)
 _SINK, _BS, _BS_BWD, _SPARSE_KV = _P(FaSinkParams), _P(FaBlockSparseParams), _P(FaBlockSparseBwdParams), _P(FaSparseKvParams)
-_TREE = _P(FaTreeParams)
+_TREE, _TOPK_KV = _P(FaTreeParams), _P(FaTopkKvParams)
 # every C entry point, by header: (symbol, argtypes, restype); a row whose params struct has a `*_params_size` also names that
 # symbol and the mirror it is checked against (the `*_params_size` symbols themselves are all `uint32_t (void)`)
 _PROTOTYPES = {
@@ -802,6 +827,10 @@ _PROTOTYPES = {
         ("fa_fwd_tree_validate", [_FWD, _TREE], _INT),
         ("fa_fwd_tree_workspace_size", [_FWD, _TREE], _I64),
         ("fa_fwd_tree_plan_name", [_FWD, _TREE, _I32], _STR),
+        ("fa_fwd_topk_kv", [_FWD, _TOPK_KV, _VOID], _INT, "fa_topk_kv_params_size", FaTopkKvParams),
+        ("fa_fwd_topk_kv_validate", [_FWD, _TOPK_KV], _INT),
+        ("fa_fwd_topk_kv_workspace_size", [_FWD, _TOPK_KV], _I64),
+        ("fa_fwd_topk_kv_plan_name", [_FWD, _TOPK_KV, _I32], _STR),
     ),
     "fa_bwd.h": (
         ("fa_bwd", [_BWD, _VOID], _INT, "fa_bwd_params_size", FaBwdParams),
@@ -933,6 +962,10 @@ def new_sparse_kv_params():
 
 def new_tree_params():
     return _new(FaTreeParams, row_stride=1)
+
+
+def new_topk_kv_params():
+    return _new(FaTopkKvParams, topk=1)
 
 
 def new_sink_grad_params():

@@ -1220,6 +1220,11 @@ struct TreeWords {
     bool fp8_cache;  // e4m3 caches (else 16-bit caches of q's dtype)
 };
 
+// The list of fwd_kvcache_topk (include/fa_fwd.h, fa_topk_kv_params), checked there
+struct TopkList {
+    Tensor indices;  // int32 (b, seqlen_q, h_k | 1, topk)
+};
+
 // 16-bit queries over an fp8 (e4m3) KV cache -- kv_cache_dtype = fp8 of a serving stack (include/fa_fwd.h, fa_fwd_kv8): q and
 // out fp16 / bf16, k / v the cache as Float8_e4m3fn, (b_cache, seqlen_k, h_k, d) or pages behind page_table, k_descale /
 // v_descale fp32 (b, h_k).  Dense q (b, seqlen_q, h, d) or ragged q (total_q, h, d) with cu_seqlens_q; cache_seqlens in
@@ -1231,18 +1236,19 @@ struct TreeWords {
 // sparse: the block-sparse read (fa_fwd_sparse_kv) of fwd_kvcache_sparse below, over an e4m3 cache or -- the one case where k / v
 // are 16-bit here -- a cache of q's dtype; the lists ride beside the same params, everything else is handled alike.
 // tree: tree attention (fa_fwd_tree) of fwd_kvcache_tree below, over either cache type as well; the words ride beside the params.
+// topk: the top-k token-sparse MLA decode (fa_fwd_topk_kv) of fwd_kvcache_topk below, with mla set, over a 16-bit cache of q's dtype.
 std::tuple<Tensor, Tensor> fwd_kv8(const Tensor &q, const Tensor &k, const Tensor &v, const OptTensor &out_,
                                    const OptTensor &cu_seqlens_q, const OptTensor &seqused_q, const OptTensor &seqused_k,
                                    c10::optional<int64_t> max_seqlen_q_, const OptTensor &page_table, const OptTensor &kv_batch_idx,
                                    const OptTensor &leftpad_k, const OptTensor &k_descale, const OptTensor &v_descale,
                                    double softmax_scale, bool is_causal, int64_t window_size_left, int64_t window_size_right,
                                    double softcap, int64_t num_splits, const OptTensor &qv = c10::nullopt, bool mla = false,
-                                   const SparseLists *sparse = nullptr, const TreeWords *tree = nullptr) {
-    const bool wide_cache = (sparse && !sparse->fp8_cache) || (tree && !tree->fp8_cache);  // 16-bit k / v: strides in 2-byte elements
+                                   const SparseLists *sparse = nullptr, const TreeWords *tree = nullptr, const TopkList *topk = nullptr) {
+    const bool wide_cache = (sparse && !sparse->fp8_cache) || (tree && !tree->fp8_cache) || topk;  // 16-bit k / v: strides in 2-byte elements
     CHECK_DEVICE(k, "k"); CHECK_LAST_CONTIGUOUS(k, "Input tensor must have contiguous last dimension");
     CHECK_DEVICE(v, "v"); CHECK_LAST_CONTIGUOUS(v, "Input tensor must have contiguous last dimension");
     const bool ragged = cu_seqlens_q.has_value();
-    TORCH_CHECK(k.dim() == 4 && v.dim() == 4, sparse || tree ? "k / v" : "an fp8 k / v",
+    TORCH_CHECK(k.dim() == 4 && v.dim() == 4, sparse || tree || topk ? "k / v" : "an fp8 k / v",
                 " must be a KV cache of shape (batch or num_pages, seqlen or page_size, num_heads_k, head_size)");
     const int64_t head_size = q.size(-1), num_heads = q.size(-2), num_heads_k = k.size(2);
     const int64_t head_size_v = mla ? v.size(3) : head_size;
@@ -1303,6 +1309,10 @@ std::tuple<Tensor, Tensor> fwd_kv8(const Tensor &q, const Tensor &k, const Tenso
     if (tree)
         TORCH_CHECK(tree->mask.sizes() == (ragged ? c10::IntArrayRef({total_q}) : c10::IntArrayRef({batch_size, seqlen_q})),
                     "tree_mask must have shape (batch_size, seqlen_q), or (total_q,) with cu_seqlens_q");
+    if (topk)
+        TORCH_CHECK(topk->indices.size(0) == batch_size && topk->indices.size(1) == seqlen_q &&
+                        (topk->indices.size(2) == 1 || topk->indices.size(2) == num_heads_k),
+                    "indices must have shape (batch_size, seqlen_q, num_heads_k | 1, topk)");
     if (seqlen_k == 0 || seqlen_q == 0) {
         fill_empty(out, softmax_lse);
         return {out, softmax_lse};
@@ -1341,14 +1351,26 @@ std::tuple<Tensor, Tensor> fwd_kv8(const Tensor &q, const Tensor &k, const Tenso
         tp.row_stride = tree->mask.stride(-1);
         tp.fp8_cache = tree->fp8_cache ? 1 : 0;
     }
-    const char *entry = tree ? "fa_fwd_tree" : sparse ? "fa_fwd_sparse_kv" : mla ? "fa_fwd_qv8" : "fa_fwd_kv8";
-    const int64_t need = tree     ? fa_fwd_tree_workspace_size(&p, &tp)
+    fa_topk_kv_params kp{};
+    if (topk) {
+        kp.abi_version = FA_ABI_VERSION;
+        kp.struct_size = sizeof(fa_topk_kv_params);
+        kp.indices = static_cast<const int32_t *>(topk->indices.data_ptr());
+        kp.batch_stride = topk->indices.stride(0);
+        kp.row_stride = topk->indices.stride(1);
+        kp.head_stride = topk->indices.size(2) == 1 ? 0 : topk->indices.stride(2);
+        kp.topk = (int32_t)topk->indices.size(3);
+    }
+    const char *entry = topk ? "fa_fwd_topk_kv" : tree ? "fa_fwd_tree" : sparse ? "fa_fwd_sparse_kv" : mla ? "fa_fwd_qv8" : "fa_fwd_kv8";
+    const int64_t need = topk     ? fa_fwd_topk_kv_workspace_size(&p, &kp)
+                         : tree   ? fa_fwd_tree_workspace_size(&p, &tp)
                          : sparse ? fa_fwd_sparse_kv_workspace_size(&p, &sp)
                          : mla    ? fa_fwd_qv8_workspace_size(&p)
                                   : fa_fwd_kv8_workspace_size(&p);
     TORCH_CHECK(need >= 0, entry, "_workspace_size failed (", need, "): ", fa_strerror((int)need));
     const Tensor workspace = set_workspace(p, need, q);  // split-KV partials
-    const int st = tree     ? fa_fwd_tree(&p, &tp, current_stream(q))
+    const int st = topk     ? fa_fwd_topk_kv(&p, &kp, current_stream(q))
+                   : tree   ? fa_fwd_tree(&p, &tp, current_stream(q))
                    : sparse ? fa_fwd_sparse_kv(&p, &sp, current_stream(q))
                    : mla    ? fa_fwd_qv8(&p, current_stream(q))
                             : fa_fwd_kv8(&p, current_stream(q));
@@ -1440,6 +1462,36 @@ std::tuple<Tensor, Tensor> fwd_kvcache_tree(const Tensor &q, const Tensor &k, co
     const TreeWords words{tree_mask, fp8_cache};
     return fwd_kv8(q, k, v, c10::nullopt, cu_seqlens_q, c10::nullopt, seqused_k, max_seqlen_q_, page_table, kv_batch_idx, leftpad_k,
                    k_descale, v_descale, softmax_scale, false, -1, -1, softcap, num_splits, c10::nullopt, false, nullptr, &words);
+}
+
+// hopper_interface.flash_attn_with_kvcache_topk / torch.ops.flash_attn_3.fwd_kvcache_topk: MLA decode over the key positions an
+// int32 list names per query token (include/fa_fwd.h, fa_fwd_topk_kv).  q (b, seqlen_q, h, d <= 64) and the optional qv
+// (b, seqlen_q, h, d_v) fp16 / bf16, k (.., h_k, d) and v (.., h_k, d_v in [256, 512]) of q's dtype, batched (kv_batch_idx) or
+// paged; read-only.  The refusals by argument stand here; the cache side, out, the workspace and the launch are fwd_kv8's.
+// Nothing of the list is read on the host.
+std::tuple<Tensor, Tensor> fwd_kvcache_topk(const Tensor &q, const Tensor &k, const Tensor &v, const Tensor &indices, const OptTensor &qv,
+                                            const OptTensor &seqused_k, const OptTensor &kv_batch_idx, const OptTensor &page_table,
+                                            c10::optional<double> softmax_scale_, int64_t num_splits) {
+    const auto q_dtype = q.scalar_type();
+    TORCH_CHECK(q_dtype == at::kHalf || q_dtype == at::kBFloat16,
+                "This flash attention build supports top-k attention over a KV cache for fp16 / bf16 queries only");
+    TORCH_CHECK(k.scalar_type() == q_dtype && v.scalar_type() == q_dtype,
+                "This flash attention build supports top-k attention over a KV cache of the query's dtype only (no fp8 cache)");
+    TORCH_CHECK(indices.scalar_type() == at::kInt, "indices must have dtype int32");
+    TORCH_CHECK(indices.is_cuda() && indices.device() == q.device(), "indices must be on the same CUDA device as query");
+    TORCH_CHECK(indices.dim() == 4 && indices.size(3) >= 1, "indices must have shape (batch_size, seqlen_q, num_heads_k | 1, topk), topk >= 1");
+    TORCH_CHECK(indices.size(3) == 1 || indices.stride(3) == 1, "indices must have contiguous last dimension");
+    CHECK_DEVICE(q, "q"); CHECK_LAST_CONTIGUOUS(q, "Input tensor must have contiguous last dimension");
+    TORCH_CHECK(q.dim() == 4, "q must have shape (batch_size, seqlen_q, num_heads, head_size)");
+    TORCH_CHECK(k.dim() == 4 && v.dim() == 4 && k.size(-1) == q.size(-1) && q.size(-1) <= 64 && q.size(-1) % 8 == 0 && v.size(-1) >= 256 &&
+                    v.size(-1) <= 512 && v.size(-1) % 8 == 0,
+                "This flash attention build supports top-k attention over the MLA cache shape only: head_size <= 64 beside "
+                "head_size_v in [256, 512], both multiples of 8");
+    const double softmax_scale = softmax_scale_.has_value() ? *softmax_scale_
+                                                            : 1.0 / std::sqrt((double)(q.size(-1) + (qv.has_value() ? v.size(-1) : 0)));
+    const TopkList list{indices};
+    return fwd_kv8(q, k, v, c10::nullopt, c10::nullopt, c10::nullopt, seqused_k, c10::nullopt, page_table, kv_batch_idx, c10::nullopt,
+                   c10::nullopt, c10::nullopt, softmax_scale, false, -1, -1, 0.0, num_splits, qv, true, nullptr, nullptr, &list);
 }
 
 // The MLA decode shape over an fp8 KV cache (include/fa_fwd.h, fa_fwd_qv8): q (.., h, d <= 64) and the optional qv (.., h, d_v)
@@ -3416,6 +3468,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("cache_batch_idx") = py::none(), py::arg("cache_leftpad") = py::none(), py::arg("page_table") = py::none(),
           py::arg("cu_seqlens_q") = py::none(), py::arg("max_seqlen_q") = py::none(), py::arg("k_descale") = py::none(),
           py::arg("v_descale") = py::none(), py::arg("softmax_scale") = py::none(), py::arg("softcap") = 0.0, py::arg("num_splits") = 0);
+    m.def("fwd_kvcache_topk", &fwd_kvcache_topk,
+          "MLA decode over the key positions an int32 list names per query token; returns (out, softmax_lse)",
+          py::arg("q"), py::arg("k_cache"), py::arg("v_cache"), py::arg("indices"), py::arg("qv") = py::none(),
+          py::arg("cache_seqlens") = py::none(), py::arg("cache_batch_idx") = py::none(), py::arg("page_table") = py::none(),
+          py::arg("softmax_scale") = py::none(), py::arg("num_splits") = 0);
     for (const bool plan : {false, true}) {
         m.def(plan ? "kvcache_block_summary_update_plan" : "kvcache_block_summary_update",
               [plan](const Tensor &k_summary, const Tensor &k_cache, const OptTensor &seqlens_old, const Tensor &seqlens_new,

@@ -54,6 +54,10 @@ KVCACHE_TREE_SCHEMA = (
     "Tensor? cache_batch_idx = None, Tensor? cache_leftpad = None, Tensor? page_table = None, Tensor? cu_seqlens_q = None, "
     "int? max_seqlen_q = None, Tensor? k_descale = None, Tensor? v_descale = None, float? softmax_scale = None, "
     "float softcap = 0.0, int num_splits = 0) -> (Tensor, Tensor)")
+# nor this: MLA decode over the key positions a top-k list names per query token (DeepSeek-V3.2-style sparse attention), read-only
+KVCACHE_TOPK_SCHEMA = (
+    "fwd_kvcache_topk(Tensor q, Tensor k_cache, Tensor v_cache, Tensor indices, Tensor? qv = None, Tensor? cache_seqlens = None, "
+    "Tensor? cache_batch_idx = None, Tensor? page_table = None, float? softmax_scale = None, int num_splits = 0) -> (Tensor, Tensor)")
 # ... nor what produces the sparse route's lists (include/fa_block_select.h): the block summaries of the keys, updated in place on append, and
 # the Quest selection.  Every tensor the launches write is a mutated argument and nothing is returned, so that a traced graph
 # holds no alias of an input; hopper_interface allocates what the caller does not give
@@ -67,7 +71,7 @@ SELECT_BLOCKS_SCHEMA = (
 
 _ops = torch.library.Library("flash_attn_3", "DEF")
 for _schema in (FWD_SCHEMA, BWD_SCHEMA, COMBINE_SCHEMA, METADATA_SCHEMA, APPEND_FP8_SCHEMA, KVCACHE_SPARSE_SCHEMA, KVCACHE_TREE_SCHEMA,
-                BLOCK_SUMMARY_SCHEMA, SELECT_BLOCKS_SCHEMA):
+                KVCACHE_TOPK_SCHEMA, BLOCK_SUMMARY_SCHEMA, SELECT_BLOCKS_SCHEMA):
     _ops.define(_schema)
 
 
@@ -152,6 +156,20 @@ def _fwd_kvcache_tree_meta(q, k_cache, v_cache, tree_mask, cache_seqlens=None, c
     return torch.empty_like(q), q.new_empty(lse_shape, dtype=torch.float32)
 
 
+def _fwd_kvcache_topk(q, k_cache, v_cache, indices, qv=None, cache_seqlens=None, cache_batch_idx=None, page_table=None,
+                      softmax_scale=None, num_splits=0):
+    """The binding's fwd_kvcache_topk (fa_fwd_topk_kv): one launch (+ the merge of a split call), no host sync."""
+    out, lse = _lib.binding().fwd_kvcache_topk(q, k_cache, v_cache, indices, qv, cache_seqlens, cache_batch_idx, page_table,
+                                               softmax_scale, num_splits)
+    return out, lse
+
+
+def _fwd_kvcache_topk_meta(q, k_cache, v_cache, indices, qv=None, cache_seqlens=None, cache_batch_idx=None, page_table=None,
+                           softmax_scale=None, num_splits=0):
+    return (q.new_empty((*q.shape[:-1], v_cache.shape[-1])),
+            q.new_empty((q.shape[0], q.shape[2], q.shape[1]), dtype=torch.float32))
+
+
 def _kvcache_block_summary_update(k_summary, k_cache, seqlens_old, seqlens_new, kv_block_size=128, max_seqlen_new=None,
                                   cache_batch_idx=None, page_table=None):
     """The binding's kvcache_block_summary_update (fa_block_summary_update): one launch, in place."""
@@ -207,6 +225,8 @@ _ops.impl("fwd_kvcache_sparse", _fwd_kvcache_sparse, "CUDA")
 _ops.impl("fwd_kvcache_sparse", _fwd_kvcache_sparse_meta, "Meta")
 _ops.impl("fwd_kvcache_tree", _fwd_kvcache_tree, "CUDA")
 _ops.impl("fwd_kvcache_tree", _fwd_kvcache_tree_meta, "Meta")
+_ops.impl("fwd_kvcache_topk", _fwd_kvcache_topk, "CUDA")
+_ops.impl("fwd_kvcache_topk", _fwd_kvcache_topk_meta, "Meta")
 _ops.impl("kvcache_block_summary_update", _kvcache_block_summary_update, "CUDA")
 _ops.impl("kvcache_block_summary_update", _nothing, "Meta")
 _ops.impl("kvcache_select_blocks", _kvcache_select_blocks, "CUDA")

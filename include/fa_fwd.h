@@ -251,7 +251,7 @@ int fa_fwd_validate(const fa_fwd_params *params);
  * device access; the text lives in thread-local storage until the next call on the same thread. */
 const char *fa_fwd_plan_name(const fa_fwd_params *params, int32_t num_cus);
 
-/* Test hook: the name of the plan the calling thread's most recent fa_fwd() (or fa_fwd_sink, fa_fwd_block_sparse, fa_fwd_kv8, fa_fwd_qv8, fa_fwd_sparse_kv, fa_fwd_tree) launched (same text as fa_fwd_plan_name on that
+/* Test hook: the name of the plan the calling thread's most recent fa_fwd() (or fa_fwd_sink, fa_fwd_block_sparse, fa_fwd_kv8, fa_fwd_qv8, fa_fwd_sparse_kv, fa_fwd_tree, fa_fwd_topk_kv) launched (same text as fa_fwd_plan_name on that
  * call's params and the device's CU count; for a wide V run as several 256-column calls, the outer "... cols=N" plan).  NULL
  * before the first call or when that call failed validation; unspecified after a call that returned any other error (a failed
  * 256-column part leaves that part's plan).  fa_fwd keeps a struct copy; the text is made here, in
@@ -517,6 +517,54 @@ int fa_fwd_tree_validate(const fa_fwd_params *params, const fa_tree_params *tree
 int64_t fa_fwd_tree_workspace_size(const fa_fwd_params *params, const fa_tree_params *tree);
 const char *fa_fwd_tree_plan_name(const fa_fwd_params *params, const fa_tree_params *tree, int32_t num_cus);
 uint32_t fa_tree_params_size(void);
+
+/*
+ * Top-k token-sparse MLA decode over the latent KV cache: the attention half of DeepSeek-V3.2-style sparse attention.  Every
+ * query token attends to the key POSITIONS an int32 list names for it, and to those alone.  The cache is the MLA shape of the qv
+ * kernel: k (.., h_k, d <= 64), v (.., h_k, d_v in [256, 512]), 16-bit elements of params->dtype; params->qv is optional
+ * (S = (q.K^T + qv.V^T) * softmax_scale).  Dense queries only.  sk(b) is the fill level as the other cache routes compute it:
+ * seqused_k, clamped to the capacity seqlen_k.
+ *   indices  int32 on the device, logical shape (b, seqlen_q, h_k | 1, topk) behind the three element strides below (a shared
+ *            head dimension has stride 0); the last stride is 1.  topk >= 1, any value.
+ * An entry is a LOGICAL position of the sequence (the kernel does the page lookup).  With g = h / h_k, key j of batch b is visible
+ * to query token i, head hd iff j is among indices[b, i, hd / g, :] and 0 <= j < sk(b).  The list is the mask: there is no
+ * causal, window, chunk, softcap, ALiBi, dropout or leftpad argument here.  Any order of entries (rounding only); a duplicate
+ * counts twice -- distinct entries are the caller's duty.  An entry outside [0, sk(b)) -- -1, the usual filler, or any other
+ * value -- contributes nothing and is never used to form an address: the comparison is unsigned against sk(b) and comes before
+ * any page number or row offset.  A 64-entry tile without a valid entry loads no K/V row.  A row with no visible key gives
+ * O = 0, LSE = +inf, split or not.  Read-only.
+ * The host reads nothing of the list or the fill levels: the call can be captured into a HIP graph, and a replay after the list
+ * was overwritten in place computes the new selection.  The callee never allocates and never synchronises.
+ * One kernel, tk_fwd_kernel (csrc/fa_fwd_kernel_tk.h): a workgroup's 32 rows are 32 heads of ONE token; it walks the list in
+ * tiles of 64 entries and gathers single cache rows.  Served: a dense cache with seqused_k and kv_batch_idx; a paged cache with
+ * any page_block_size >= 1; split-KV over the tiles of the LIST.  num_splits: 1 = off, N > 1 = N parts (at most 128; parts behind the last tile are empty),
+ * 0 = what the qv kernel's heuristic gives b * seqlen_q single-token queries over a key length of topk (shapes only); partials,
+ * workspace layout and the merge (one fa_fwd_combine launch, d = d_v) are fa_fwd's.
+ * FA_ERR_UNSUPPORTED, checked before anything the params may lack: dtype fp8, d > 64 or d % 8 != 0, d_v outside [256, 512] or
+ * d_v % 8 != 0, is_causal, a window side >= 0, attention_chunk, softcap, ALiBi, dropout, s_dmask, leftpad_k, cu_seqlens_q,
+ * cu_seqlens_k, block_table beside kv_batch_idx.  FA_ERR_NULL_POINTER: NULL indices.  FA_ERR_BAD_SHAPE: topk < 1.
+ * FA_ERR_BAD_STRIDE: a negative stride, indices not 4-byte aligned.  FA_ERR_WORKSPACE when a split call lacks its workspace
+ * (fa_fwd_topk_kv_workspace_size() bytes, 256-byte aligned; 0 unsplit).
+ * fa_fwd_last_plan_name() names such a call
+ *   "tk_fwd_kernel DVT=<256|512> waves=4 topk=<topk> splits=<N>";
+ * fa_fwd_topk_kv_plan_name gives the same text from the two structs alone (num_cus decides nothing), NULL when fa_fwd_topk_kv
+ * would reject them.
+ */
+typedef struct fa_topk_kv_params {
+    uint32_t abi_version; /* FA_ABI_VERSION */
+    uint32_t struct_size; /* sizeof(fa_topk_kv_params) */
+    const int32_t *indices; /* device pointer, required */
+    int64_t batch_stride, row_stride, head_stride; /* element strides, >= 0, 0 = broadcast */
+    int32_t topk; /* entries per list, >= 1 */
+    int32_t reserved;
+} fa_topk_kv_params;
+
+int fa_fwd_topk_kv(const fa_fwd_params *params, const fa_topk_kv_params *topk, void *stream);
+/* Validation only; no device access. */
+int fa_fwd_topk_kv_validate(const fa_fwd_params *params, const fa_topk_kv_params *topk);
+int64_t fa_fwd_topk_kv_workspace_size(const fa_fwd_params *params, const fa_topk_kv_params *topk);
+const char *fa_fwd_topk_kv_plan_name(const fa_fwd_params *params, const fa_topk_kv_params *topk, int32_t num_cus);
+uint32_t fa_topk_kv_params_size(void);
 
 /* Human-readable text for a status code (static storage). */
 const char *fa_strerror(int status);
