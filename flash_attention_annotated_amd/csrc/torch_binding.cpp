@@ -31,6 +31,7 @@
 #include "fa_tree_sample.h"
 #include "fa_block_select.h"
 #include "fa_block_pattern.h"
+#include "fa_index_topk.h"
 #include "fa_act.h"
 #include "fa_gemm_act.h"
 #include "fa_dropout_norm.h"
@@ -3168,6 +3169,85 @@ std::string block_select_impl(const Tensor &q, const Tensor &k_summary, const Te
     return {};
 }
 
+// ---- the lightning indexer (hopper_interface.kvcache_index_topk; include/fa_index_topk.h): what produces the lists
+// fwd_kvcache_topk reads.  Launches on the current stream, nothing is read on the host; both tensors the launches write are
+// arguments: capturable in a HIP graph.  plan: the form the call takes as text, and nothing is launched.
+std::string index_topk_impl(const Tensor &q_index, const Tensor &k_index_cache, const Tensor &weights, const Tensor &cache_seqlens,
+                            int64_t topk, const OptTensor &cache_batch_idx, const OptTensor &page_table, bool causal,
+                            const Tensor &indices, const Tensor &logits, bool plan) {
+    TORCH_CHECK(q_index.is_cuda() && (q_index.scalar_type() == at::kHalf || q_index.scalar_type() == at::kBFloat16),
+                "q_index must be an fp16 or bf16 CUDA tensor");
+    TORCH_CHECK(q_index.dim() == 4, "q_index must have shape (batch_size, seqlen_q, index_heads, index_dim); ragged queries are not supported");
+    CHECK_LAST_CONTIGUOUS(q_index, "q_index must have contiguous last dimension");
+    const int64_t batch_size = q_index.size(0), seqlen_q = q_index.size(1), heads = q_index.size(2), dim = q_index.size(3);
+    TORCH_CHECK(dim == 64 || dim == 128, "q_index: index_dim must be 64 or 128, got ", dim);
+    TORCH_CHECK(heads >= 16 && heads <= FA_INDEX_MAX_HEADS && heads % 16 == 0, "q_index: index_heads must be a multiple of 16, at most ",
+                FA_INDEX_MAX_HEADS, ", got ", heads);
+    TORCH_CHECK(seqlen_q >= 1 && seqlen_q <= FA_INDEX_MAX_ROWS, "q_index: seqlen_q must be in [1, ", FA_INDEX_MAX_ROWS, "], got ", seqlen_q);
+    TORCH_CHECK(k_index_cache.scalar_type() != at::kFloat8_e4m3fn, "an e4m3 k_index_cache is not supported");
+    TORCH_CHECK(k_index_cache.is_cuda() && k_index_cache.device() == q_index.device() && k_index_cache.scalar_type() == q_index.scalar_type(),
+                "k_index_cache must be on the device of q_index and have its dtype");
+    TORCH_CHECK(k_index_cache.dim() == 3 && k_index_cache.size(2) == dim,
+                "k_index_cache must have shape (batch or num_pages, seqlen or page_size, index_dim)");
+    CHECK_LAST_CONTIGUOUS(k_index_cache, "k_index_cache must have contiguous last dimension");
+    TORCH_CHECK(weights.scalar_type() == at::kFloat && weights.is_cuda() && weights.device() == q_index.device() &&
+                    weights.sizes() == c10::IntArrayRef({batch_size, seqlen_q, heads}) && weights.stride(2) == 1,
+                "weights must be fp32 (batch_size, seqlen_q, index_heads) with contiguous last dimension");
+    check_fill(cache_seqlens, "cache_seqlens", batch_size, q_index);
+    int64_t capacity;
+    if (page_table.has_value()) {
+        TORCH_CHECK(!cache_batch_idx.has_value(), "Paged KVcache does not support cache_batch_idx");
+        TORCH_CHECK(page_table->scalar_type() == at::kInt && page_table->is_cuda() && page_table->dim() == 2 &&
+                        page_table->size(0) == batch_size && page_table->stride(1) == 1,
+                    "page_table must be an int32 CUDA tensor of shape (batch_size, max_num_pages_per_seq) with contiguous last dimension");
+        capacity = page_table->size(1) * k_index_cache.size(1);
+    } else {
+        capacity = k_index_cache.size(1);
+        if (cache_batch_idx.has_value()) check_fill(*cache_batch_idx, "cache_batch_idx", batch_size, q_index);
+        else TORCH_CHECK(batch_size <= k_index_cache.size(0), "the batch must fit the cache without cache_batch_idx");
+    }
+    TORCH_CHECK(capacity >= 1 && capacity <= FA_INDEX_MAX_KEYS, "the capacity must be in [1, ", FA_INDEX_MAX_KEYS, "], got ", capacity);
+    TORCH_CHECK(topk >= 1, "topk must be at least 1, got ", topk);
+    TORCH_CHECK(indices.scalar_type() == at::kInt && indices.is_cuda() && indices.device() == q_index.device() && indices.dim() == 4 &&
+                    indices.size(0) == batch_size && indices.size(1) == seqlen_q && indices.size(2) == 1 && indices.size(3) >= topk &&
+                    indices.stride(3) == 1,
+                "indices must be int32 (batch_size, seqlen_q, 1, width >= topk) with contiguous last dimension");
+    TORCH_CHECK(logits.scalar_type() == at::kFloat && logits.is_cuda() && logits.device() == q_index.device() && logits.dim() == 3 &&
+                    logits.size(0) == batch_size && logits.size(1) == seqlen_q && logits.size(2) >= capacity && logits.stride(2) == 1,
+                "logits must be fp32 (batch_size, seqlen_q, width >= capacity) with contiguous last dimension");
+    const Tensor qc = aligned_or_copy(q_index);
+    TORCH_CHECK(aligned(k_index_cache), "k_index_cache must be 16-byte aligned with strides that are multiples of 8 elements");
+    auto p = new_params<fa_index_topk_params>();
+    p.q_index = qc.data_ptr(); p.k_index_cache = k_index_cache.data_ptr();
+    p.weights = static_cast<const float *>(weights.data_ptr());
+    p.cache_seqlens = static_cast<const int32_t *>(cache_seqlens.data_ptr());
+    p.cache_batch_idx = static_cast<const int32_t *>(ptr(cache_batch_idx));
+    p.page_table = static_cast<const int32_t *>(ptr(page_table));
+    p.logits = static_cast<float *>(logits.data_ptr()); p.indices = static_cast<int32_t *>(indices.data_ptr());
+    p.q_batch_stride = qc.stride(0); p.q_row_stride = qc.stride(1); p.q_head_stride = qc.stride(2);
+    p.cache_batch_stride = k_index_cache.stride(0); p.cache_row_stride = k_index_cache.stride(1);
+    p.w_batch_stride = weights.stride(0); p.w_row_stride = weights.stride(1);
+    if (page_table.has_value()) { p.page_table_batch_stride = page_table->stride(0); p.page_size = (int32_t)k_index_cache.size(1); }
+    p.logits_batch_stride = logits.stride(0); p.logits_row_stride = logits.stride(1);
+    p.idx_batch_stride = indices.stride(0); p.idx_row_stride = indices.stride(1);
+    p.b = (int32_t)batch_size; p.s_q = (int32_t)seqlen_q; p.h_i = (int32_t)heads; p.d_i = (int32_t)dim;
+    p.capacity = (int32_t)capacity;
+    p.topk = (int32_t)std::min<int64_t>(topk, 0x7fffffff);
+    p.list_width = (int32_t)std::min<int64_t>(indices.size(3), 0x7fffffff);
+    p.logits_width = (int32_t)std::min<int64_t>(logits.size(2), 0x7fffffff);
+    p.is_causal = causal ? 1 : 0;
+    p.dtype = p.cache_dtype = dtype_code(q_index);
+    if (plan) {
+        const char *name = fa_index_topk_plan_name(&p);
+        TORCH_CHECK(name, "fa_index_topk refused (", fa_index_topk_validate(&p), "): ", fa_strerror(fa_index_topk_validate(&p)));
+        return name;
+    }
+    c10::hip::HIPGuardMasqueradingAsCUDA device_guard(q_index.device());
+    const int st = fa_index_topk(&p, current_stream(q_index));
+    TORCH_CHECK(st == 0, "fa_index_topk failed (", st, "): ", fa_strerror(st));
+    return {};
+}
+
 // ---- block-sparse prefill patterns (cute_interface.block_sparse_select; include/fa_block_pattern.h): what produces the lists
 // cute_fwd_block_sparse / cute_bwd_block_sparse read.  Launches on the current stream, nothing is read on the host; every tensor
 // the launches write, the workspace included, is an argument: capturable in a HIP graph.  The params of a call, checked; the
@@ -3497,6 +3577,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
               py::arg("q"), py::arg("k_summary"), py::arg("cache_seqlens"), py::arg("num_blocks"), py::arg("kv_block_size"),
               py::arg("sink_blocks"), py::arg("local_blocks"), py::arg("group_reduce"), py::arg("cache_batch_idx"),
               py::arg("kv_block_cnt"), py::arg("kv_block_idx"), py::arg("scores"));
+        m.def(plan ? "kvcache_index_topk_plan" : "kvcache_index_topk",
+              [plan](const Tensor &q_index, const Tensor &k_index_cache, const Tensor &weights, const Tensor &cache_seqlens, int64_t topk,
+                     const OptTensor &cache_batch_idx, const OptTensor &page_table, bool causal, const Tensor &indices, const Tensor &logits) {
+                  return index_topk_impl(q_index, k_index_cache, weights, cache_seqlens, topk, cache_batch_idx, page_table, causal, indices,
+                                         logits, plan);
+              },
+              plan ? "the form kvcache_index_topk takes with these arguments, as text; nothing is launched"
+                   : "lightning indexer: index logits against the index-key cache and the top-k positions per query token; writes indices and logits",
+              py::arg("q_index"), py::arg("k_index_cache"), py::arg("weights"), py::arg("cache_seqlens"), py::arg("topk"),
+              py::arg("cache_batch_idx"), py::arg("page_table"), py::arg("causal"), py::arg("indices"), py::arg("logits"));
     }
     for (const int mode : {0, 1, 2}) {  // the launch, the form, the workspace's bytes
         m.def(mode == 0 ? "block_pattern" : mode == 1 ? "block_pattern_plan" : "block_pattern_workspace_size",

@@ -68,10 +68,15 @@ SELECT_BLOCKS_SCHEMA = (
     "kvcache_select_blocks(Tensor q, Tensor k_summary, Tensor cache_seqlens, int num_blocks, int kv_block_size, int sink_blocks, "
     "int local_blocks, str group_reduce, Tensor? cache_batch_idx, Tensor(a!) kv_block_cnt, Tensor(b!) kv_block_idx, "
     "Tensor(c!) scores) -> ()")
+# ... nor what produces the top-k route's lists (include/fa_index_topk.h): the lightning indexer.  Both tensors the launches write are
+# mutated arguments and nothing is returned
+INDEX_TOPK_SCHEMA = (
+    "kvcache_index_topk(Tensor q_index, Tensor k_index_cache, Tensor weights, Tensor cache_seqlens, int topk, Tensor? cache_batch_idx, "
+    "Tensor? page_table, bool causal, Tensor(a!) indices, Tensor(b!) logits) -> ()")
 
 _ops = torch.library.Library("flash_attn_3", "DEF")
 for _schema in (FWD_SCHEMA, BWD_SCHEMA, COMBINE_SCHEMA, METADATA_SCHEMA, APPEND_FP8_SCHEMA, KVCACHE_SPARSE_SCHEMA, KVCACHE_TREE_SCHEMA,
-                KVCACHE_TOPK_SCHEMA, BLOCK_SUMMARY_SCHEMA, SELECT_BLOCKS_SCHEMA):
+                KVCACHE_TOPK_SCHEMA, BLOCK_SUMMARY_SCHEMA, SELECT_BLOCKS_SCHEMA, INDEX_TOPK_SCHEMA):
     _ops.define(_schema)
 
 
@@ -184,6 +189,12 @@ def _kvcache_select_blocks(q, k_summary, cache_seqlens, num_blocks, kv_block_siz
                                          group_reduce, cache_batch_idx, kv_block_cnt, kv_block_idx, scores)
 
 
+def _kvcache_index_topk(q_index, k_index_cache, weights, cache_seqlens, topk, cache_batch_idx, page_table, causal, indices, logits):
+    """The binding's kvcache_index_topk (fa_index_topk): the logits launch and the selection launch, no host sync."""
+    _lib.binding().kvcache_index_topk(q_index, k_index_cache, weights, cache_seqlens, topk, cache_batch_idx, page_table, causal,
+                                      indices, logits)
+
+
 def _nothing(*args, **kwargs):
     """The fake of an op that only mutates its arguments."""
 
@@ -231,3 +242,5 @@ _ops.impl("kvcache_block_summary_update", _kvcache_block_summary_update, "CUDA")
 _ops.impl("kvcache_block_summary_update", _nothing, "Meta")
 _ops.impl("kvcache_select_blocks", _kvcache_select_blocks, "CUDA")
 _ops.impl("kvcache_select_blocks", _nothing, "Meta")
+_ops.impl("kvcache_index_topk", _kvcache_index_topk, "CUDA")
+_ops.impl("kvcache_index_topk", _nothing, "Meta")

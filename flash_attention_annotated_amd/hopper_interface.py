@@ -625,6 +625,84 @@ def select_blocks_ref(q, k_summary, cache_seqlens, num_blocks, *, kv_block_size=
     return SelectedBlocks(cnt, idx, scores, U, A)
 
 
+def kvcache_index_topk(q_index, k_index_cache, weights, cache_seqlens, topk, *, cache_batch_idx=None, page_table=None, causal=True,
+                       indices=None, logits=None, return_logits=False):
+    """The lightning indexer of DeepSeek-V3.2-style sparse attention (DSA): which key positions every query token of a decode,
+    MTP or verify step attends to -- the list flash_attn_with_kvcache_topk takes.  Not in the reference.  Two launches (the logits
+    split over chunks of keys, so that batch 1 fills the chip; then one workgroup per (batch, token) selects), no host sync, no
+    sort, no atomics on results; HIP-graph capturable with indices and logits given.  include/fa_index_topk.h pins the rule.
+    q_index: (batch, seqlen_q <= 16, index_heads, index_dim) fp16 / bf16; index_dim 64 or 128; index_heads a multiple of 16, at
+    most 64.  weights: fp32 (batch, seqlen_q, index_heads); fold the softmax scale and any index_heads ** -0.5 into it.
+    k_index_cache: the indexer's own single-head key cache of q_index's dtype -- (slots, capacity, index_dim) with cache_batch_idx,
+    or pages (num_pages, page_size, index_dim) of any size behind page_table (batch, capacity / page_size); capacity <= 131072.
+    sk(b) = cache_seqlens[b] clamped to [0, capacity]; rows at or behind it are never read.
+    L[b, i, s] = sum_j weights[b, i, j] * relu(q_index[b, i, j] . k_index[b, s]), fp32 throughout.  Key s is a candidate of token
+    i iff s < n(b, i): n = sk(b), or with causal (the default) clamp(sk(b) - (seqlen_q - 1 - i), 0, sk(b)), bottom-right aligned.
+    K = min(topk, n) candidates of the highest L are chosen, equal logits by the lower position (-0 equals +0).
+    Returns indices: int32 (batch, seqlen_q, 1, width >= topk), [b, i, 0, :K] the chosen logical positions ASCENDING, [K:topk) = -1;
+    a fresh tensor (width = topk) or the buffer given.  return_logits: also logits, fp32 (batch, seqlen_q, width >= capacity): L, and
+    -inf at and behind n(b, i); the buffer given or a fresh one.  With NaN inputs the choice is unspecified but every index is in
+    [0, n) or -1.  CPU tensors take index_topk_ref.  No e4m3 index cache, prefill-sized or ragged queries, per-kv-head lists, forced
+    positions, physical-slot output or backward.  One decode step of sparse attention is three calls:
+        flash_attn_with_kvcache(q, kv_cache, v_cache, k=k_new, v=v_new, cache_seqlens=lens, ...)   # the append (and k_index_cache[...] = its new rows)
+        idx = kvcache_index_topk(q_index, k_index_cache, weights, lens + 1, 2048, page_table=table)
+        out = flash_attn_with_kvcache_topk(q, kv_cache, v_cache, idx, qv=qv, cache_seqlens=lens + 1, page_table=table)
+    Cost, measured on MI355X: tools/index_topk_bench.py, profiles/index_topk.jsonl, DESIGN.md section 4.34."""
+    b, s_q = q_index.shape[0], q_index.shape[1]
+    capacity = page_table.shape[1] * k_index_cache.shape[1] if page_table is not None else k_index_cache.shape[1]
+    if indices is None:
+        indices = torch.empty((b, s_q, 1, topk), dtype=torch.int32, device=q_index.device)
+    if logits is None:
+        logits = torch.empty((b, s_q, capacity), dtype=torch.float32, device=q_index.device)
+    if not q_index.is_cuda:
+        ref = index_topk_ref(q_index, k_index_cache, weights, cache_seqlens, topk, cache_batch_idx=cache_batch_idx, page_table=page_table,
+                             causal=causal)
+        indices[..., :topk].copy_(ref.indices), logits[..., :capacity].copy_(ref.logits.float())
+    else:
+        torch.ops.flash_attn_3.kvcache_index_topk(q_index, k_index_cache, weights, cache_seqlens, topk, cache_batch_idx, page_table,
+                                                  causal, indices, logits)
+    return (indices, logits) if return_logits else indices
+
+
+class IndexTopk(NamedTuple):
+    """index_topk_ref's result.  logits: fp64 (batch, seqlen_q, capacity), L, and -inf at and behind n(b, i).  indices: int32
+    (batch, seqlen_q, 1, topk).  A: fp64 like logits, sum_j |w_j| sum_c |q_c k_c|, what an fp32 evaluation of L errs in proportion
+    to; 0 at and behind n(b, i)."""
+    logits: torch.Tensor
+    indices: torch.Tensor
+    A: torch.Tensor
+
+
+def index_topk_ref(q_index, k_index_cache, weights, cache_seqlens, topk, *, cache_batch_idx=None, page_table=None, causal=True):
+    """The oracle of kvcache_index_topk in plain torch, on any device: L in fp64, the choice by a stable sort."""
+    b, s_q, h_i, d_i = q_index.shape
+    assert 1 <= s_q <= 16 and d_i in (64, 128) and h_i % 16 == 0 and 16 <= h_i <= 64 and topk >= 1
+    paged, dev = page_table is not None, q_index.device
+    capacity = page_table.shape[1] * k_index_cache.shape[1] if paged else k_index_cache.shape[1]
+    logits = torch.full((b, s_q, capacity), float("-inf"), dtype=torch.float64, device=dev)
+    A = torch.zeros((b, s_q, capacity), dtype=torch.float64, device=dev)
+    indices = torch.full((b, s_q, 1, topk), -1, dtype=torch.int32, device=dev)
+    for e in range(b):
+        sk = min(max(int(cache_seqlens[e]), 0), capacity)
+        if sk == 0:
+            continue
+        if paged:
+            t = torch.arange(sk, device=dev)
+            rows = k_index_cache[page_table[e].long()[t // k_index_cache.shape[1]], t % k_index_cache.shape[1]]
+        else:
+            rows = k_index_cache[e if cache_batch_idx is None else int(cache_batch_idx[e]), :sk]
+        rows, q, w = rows.double(), q_index[e].double(), weights[e].double()  # (sk, d), (s_q, h, d), (s_q, h)
+        L = (torch.einsum("ihc,sc->ihs", q, rows).clamp_min(0) * w[:, :, None]).sum(1)  # (s_q, sk)
+        mag = (torch.einsum("ihc,sc->ihs", q.abs(), rows.abs()) * w.abs()[:, :, None]).sum(1)
+        for i in range(s_q):
+            n = min(max(sk - (s_q - 1 - i), 0), sk) if causal else sk
+            logits[e, i, :n], A[e, i, :n] = L[i, :n], mag[i, :n]
+            K = min(topk, n)
+            order = torch.sort(-(L[i, :n] + 0.0), stable=True).indices[:K]  # equal logits: the lower position first
+            indices[e, i, 0, :K] = order.sort().values.int()
+    return IndexTopk(logits, indices, A)
+
+
 def get_scheduler_metadata(batch_size, max_seqlen_q, max_seqlen_k, num_heads_q, num_heads_kv, headdim, cache_seqlens,
                            qkv_dtype=torch.bfloat16, headdim_v=None, cu_seqlens_q=None, cu_seqlens_k_new=None,
                            cache_leftpad=None, page_size=None, max_seqlen_k_new=0, causal=False, window_size=(-1, -1),
