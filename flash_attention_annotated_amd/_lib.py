@@ -1,4 +1,4 @@
-"""Build and loading of the native code: libfa_fwd_gfx950.so (the C-ABI of include/fa_fwd.h, fa_bwd.h, fa_rotary.h, fa_norm.h, fa_xent.h, fa_act.h, fa_gemm_act.h, fa_dropout_norm.h, fa_sample.h, fa_spec_sample.h, fa_tree_sample.h, fa_block_select.h, fa_block_pattern.h and fa_index_topk.h) and
+"""Build and loading of the native code: libfa_fwd_gfx950.so (the C-ABI of include/fa_fwd.h, fa_bwd.h, fa_rotary.h, fa_norm.h, fa_xent.h, fa_act.h, fa_gemm_act.h, fa_dropout_norm.h, fa_sample.h, fa_spec_sample.h, fa_tree_sample.h, fa_block_select.h, fa_block_pattern.h, fa_index_topk.h and fa_index_prefill.h) and
 the compiled host module flash_attn_2_cuda_C (csrc/torch_binding.cpp), which is the only host path of both operator
 surfaces.  Python launches nothing through ctypes: the struct mirrors below serve the ABI tests, `bench.py --variant`
 and the developer tools, which call the C-ABI directly.
@@ -145,6 +145,10 @@ FA_BLOCK_PATTERN_BLOCK, FA_BLOCK_PATTERN_MAX_BLOCKS = 128, 8192
 INDEX_TOPK_SYMBOLS = ("fa_index_topk", "fa_index_topk_validate", "fa_index_topk_workspace_size", "fa_index_topk_plan_name",
                       "fa_index_topk_params_size")
 FA_INDEX_MAX_KEYS, FA_INDEX_MAX_HEADS, FA_INDEX_MAX_ROWS = 131072, 64, 16
+# every symbol include/fa_index_prefill.h declares (csrc/fa_index_prefill.hip)
+INDEX_PREFILL_SYMBOLS = ("fa_index_prefill", "fa_index_prefill_validate", "fa_index_prefill_workspace_size", "fa_index_prefill_plan_name",
+                         "fa_index_prefill_params_size")
+FA_INDEX_PREFILL_BLOCK = 8
 
 
 class FaFwdParams(ctypes.Structure):
@@ -552,6 +556,23 @@ class FaIndexTopkParams(ctypes.Structure):
     )
 
 
+class FaIndexPrefillParams(ctypes.Structure):
+    """Field-for-field mirror of `struct fa_index_prefill_params` (include/fa_index_prefill.h)."""
+
+    _fields_ = (
+        [("abi_version", ctypes.c_uint32), ("struct_size", ctypes.c_uint32)]
+        + [(n, ctypes.c_void_p) for n in ("q_index", "k_index_cache", "weights", "cache_seqlens", "cache_batch_idx", "page_table",
+                                          "cu_seqlens_q", "cache_leftpad", "workspace", "indices")]
+        + [(f"q_{s}_stride", ctypes.c_int64) for s in ("batch", "row", "head")]
+        + [(f"cache_{s}_stride", ctypes.c_int64) for s in ("batch", "row")]
+        + [(f"w_{s}_stride", ctypes.c_int64) for s in ("batch", "row")]
+        + [(n, ctypes.c_int64) for n in ("page_table_batch_stride", "workspace_row_stride", "idx_batch_stride", "idx_row_stride",
+                                         "workspace_rows")]
+        + [(n, ctypes.c_int32) for n in ("b", "s_q", "h_i", "d_i", "capacity", "page_size", "topk", "list_width", "workspace_width",
+                                         "is_causal", "dtype", "cache_dtype")]
+    )
+
+
 class FaActPlan(ctypes.Structure):
     """Field-for-field mirror of `struct fa_act_plan` (include/fa_act.h): the form an activation call takes."""
 
@@ -702,7 +723,7 @@ class FaSinkGradParams(ctypes.Structure):
 
 
 HASH_PATH = os.path.join(_HERE, "libfa_fwd_gfx950.srchash")
-NO_PACKED_FP32_UNITS = ("fa_fwd_topk_kv_api.hip", "fa_index_topk.hip")
+NO_PACKED_FP32_UNITS = ("fa_fwd_topk_kv_api.hip", "fa_index_topk.hip", "fa_index_prefill.hip")
 
 
 def _deps():
@@ -896,6 +917,12 @@ _PROTOTYPES = {
         ("fa_index_topk_workspace_size", [_P(FaIndexTopkParams)], _I64),
         ("fa_index_topk_plan_name", [_P(FaIndexTopkParams)], _STR),
     ),
+    "fa_index_prefill.h": (
+        ("fa_index_prefill", [_P(FaIndexPrefillParams), _VOID], _INT, "fa_index_prefill_params_size", FaIndexPrefillParams),
+        ("fa_index_prefill_validate", [_P(FaIndexPrefillParams)], _INT),
+        ("fa_index_prefill_workspace_size", [_P(FaIndexPrefillParams), _I32], _I64),
+        ("fa_index_prefill_plan_name", [_P(FaIndexPrefillParams)], _STR),
+    ),
 }
 
 _lib = None
@@ -1057,6 +1084,10 @@ def new_block_pattern_params():
 
 def new_index_topk_params():
     return _new(FaIndexTopkParams, ("cache",), dtype=FA_DTYPE_BF16, topk=1, is_causal=1)
+
+
+def new_index_prefill_params():
+    return _new(FaIndexPrefillParams, ("cache",), dtype=FA_DTYPE_BF16, topk=1, is_causal=1)
 
 
 def new_act_fwd_params():

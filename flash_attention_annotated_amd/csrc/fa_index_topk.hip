@@ -2,7 +2,8 @@
 // of a decode-sized step against the indexer's single-head key cache, and the top-k positions of every query token as the list
 // the token-sparse MLA decode reads.  A translation unit of its own.  The workgroup scan and the host predicates are
 // fa_rowwise.h's, the order-preserving key of a logit is the one of fa_sample_device.h; the descent is the method of
-// fa_block_select.hip's block_select_kernel over a row that lives in global memory (a copy: that unit stays what its tests pin).
+// fa_block_select.hip's block_select_kernel over a row that lives in global memory (a copy: that unit stays what its tests pin),
+// and its text is fa_index_select.h's, shared with the prefill-sized unit fa_index_prefill.hip.
 //
 // index_logits_kernel<DT, D, MB>: one workgroup of 4 waves per (chunk of keys, batch entry).  The query fragments of a group of
 //   TG tokens lie in LDS in MFMA operand order (slot (token, m block, k step), then lane: every fragment read is 64 consecutive
@@ -11,19 +12,17 @@
 //   no LDS for K), the page of a row is resolved once per row.  S (heads x keys) = Q . K^T on v_mfma_f32_32x32x16: the
 //   accumulator holds 16 heads of ONE key per lane, so ReLU, the weights and the head sum are in-lane but for one swap with
 //   lane ^ 32.  The tokens of the group loop over the resident tile; a logit per key leaves as one 256-byte store per wave.
-// index_select_kernel: one workgroup per (token, batch entry).  The cut by four 8-bit passes over the keys of the row (read from
-//   L2 each pass; equal digits of a wave are counted by ballot, so a row of equal logits does not serialise on one LDS word),
-//   then wave w compacts its contiguous segment by ballots behind the counts of the waves before it.  Integer logic only: a
-//   NaN logit is a key like any other.
+// index_select_kernel: one workgroup per (token, batch entry) runs fa_index_select.h's index_select_row over the token's row of
+//   logits.
 #include "../../include/fa_index_topk.h"
-#include "fa_sample_device.h"
+#include "fa_index_select.h"
 
 #include <cstdio>
 
 namespace {
 
 using namespace fa_row;
-using fa_sample_dev::full_key;
+using namespace fa_index_sel;
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
@@ -33,8 +32,6 @@ constexpr int THREADS = 256, WAVES = THREADS / WAVE;  // of the logits
 constexpr int TILE = 64;                              // key rows of a wave's tile
 constexpr int CHUNK_MIN = WAVES * TILE, CHUNK_MAX = 1024, GRID_AIM = 1024;
 constexpr int Q_LDS_BYTES = 48 * 1024;                // of the query fragments of a token group
-constexpr int SELECT_SMALL = 256, SELECT_LARGE = 1024, SELECT_SMALL_KEYS = 4096;  // the selection's workgroup by capacity
-constexpr int RADIX_BITS = 8, BINS = 1 << RADIX_BITS, PASSES = 32 / RADIX_BITS;
 
 __host__ __device__ constexpr int tokens_per_group(int D, int MB) {
     return Q_LDS_BYTES / (MB * 32 * D * 2) < FA_INDEX_MAX_ROWS ? Q_LDS_BYTES / (MB * 32 * D * 2) : FA_INDEX_MAX_ROWS;
@@ -164,84 +161,9 @@ __global__ __launch_bounds__(THREADS) void index_logits_kernel(const fa_index_to
 
 // ---- selection --------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(SELECT_LARGE) void index_select_kernel(const fa_index_topk_params p) {
-    __shared__ uint32_t hist[BINS];
-    __shared__ uint64_t part[MAX_WAVES];
-    __shared__ uint32_t cut_digit, cut_above;
-    __shared__ uint32_t wave_gt[MAX_WAVES], wave_eq[MAX_WAVES];
-    const int i = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, T = blockDim.x, lane = tid & 63, wave = tid >> 6, nw = T >> 6;
-    const int n = visible_of(p, fill_of(p, b), i);
-    const int K = p.topk < n ? p.topk : n;
-    const float *u = p.logits + b * p.logits_batch_stride + i * p.logits_row_stride;
-    int32_t *idx = p.indices + b * p.idx_batch_stride + i * p.idx_row_stride;
-    for (int x = K + tid; x < p.topk; x += T) idx[x] = -1;
-    if (K == n) {  // every candidate is chosen (uniform; n = 0 as well)
-        for (int j = tid; j < n; j += T) idx[j] = j;
-        return;
-    }
-
-    // the cut: the key `cut` of which `ties_in` >= 1 entries are chosen beside every entry above it (1 <= K < n)
-    uint32_t prefix = 0, want = (uint32_t)K;
-    for (int shift = 32 - RADIX_BITS; shift >= 0; shift -= RADIX_BITS) {
-        for (int x = tid; x < BINS; x += T) hist[x] = 0;
-        __syncthreads();
-        for (int j0 = 0; j0 < n; j0 += T) {  // (uniform bounds: every lane takes part in the ballots)
-            const int j = j0 + tid;
-            const uint32_t key = j < n ? full_key(u[j] + 0.0f) : 0u;
-            const bool in = j < n && (shift + RADIX_BITS == 32 || key >> (shift + RADIX_BITS) == prefix);
-            const uint32_t digit = (key >> shift) & (BINS - 1);
-            uint64_t todo = __ballot(in);
-            for (int round = 0; round < 4 && todo; ++round) {  // the four most frequent-first digits of the wave: one add each
-                const int leader = __ffsll((unsigned long long)todo) - 1;
-                const uint32_t dl = __shfl(digit, leader, WAVE);
-                const uint64_t same = __ballot(in && digit == dl);
-                if (lane == leader) atomicAdd(&hist[dl], (uint32_t)__popcll(same));  // (counts: any order gives the same histogram)
-                todo &= ~same;
-            }
-            if (todo >> lane & 1) atomicAdd(&hist[digit], 1u);
-        }
-        __syncthreads();
-        const uint64_t mine = tid < BINS ? hist[BINS - 1 - tid] : 0u;  // thread t: digit 255 - t; `above`: the higher digits
-        uint64_t total;
-        const uint64_t above = wg_exclusive_scan(mine, part, total);
-        if (tid < BINS && above < want && want <= above + mine) { cut_digit = BINS - 1 - tid; cut_above = (uint32_t)above; }
-        __syncthreads();  // (one thread wrote: at least `want` entries carry the prefix)
-        prefix = prefix << RADIX_BITS | cut_digit;
-        want -= cut_above;
-    }
-    const uint32_t cut = prefix, ties_in = want;
-
-    // ascending compaction: wave w owns the positions [w * seg, (w + 1) * seg), walked 64 at a time
-    const int seg = ((n + nw - 1) / nw + WAVE - 1) / WAVE * WAVE;
-    const int lo = wave * seg < n ? wave * seg : n, hi = lo + seg < n ? lo + seg : n;
-    uint32_t gt = 0, eq = 0;
-    for (int j0 = lo; j0 < hi; j0 += WAVE) {
-        const int j = j0 + lane;
-        const uint32_t key = j < hi ? full_key(u[j] + 0.0f) : 0u;
-        gt += (uint32_t)__popcll(__ballot(j < hi && key > cut));
-        eq += (uint32_t)__popcll(__ballot(j < hi && key == cut));
-    }
-    if (lane == 0) { wave_gt[wave] = gt; wave_eq[wave] = eq; }
-    __syncthreads();
-    uint32_t tie_run = 0, at = 0;  // the ties and the chosen positions before this wave's segment
-    for (int v = 0; v < wave; ++v) {
-        const uint32_t e = wave_eq[v], left = ties_in > tie_run ? ties_in - tie_run : 0u;
-        at += wave_gt[v] + (e < left ? e : left);
-        tie_run += e;
-    }
-    const uint64_t before = (1ull << lane) - 1ull;
-    for (int j0 = lo; j0 < hi; j0 += WAVE) {
-        const int j = j0 + lane;
-        const uint32_t key = j < hi ? full_key(u[j] + 0.0f) : 0u;
-        const bool is_eq = j < hi && key == cut;
-        const uint64_t beq = __ballot(is_eq);
-        const uint32_t rank = tie_run + (uint32_t)__popcll(beq & before);
-        const bool chosen = j < hi && (key > cut || (is_eq && rank < ties_in));
-        const uint64_t bc = __ballot(chosen);
-        const uint32_t pos = at + (uint32_t)__popcll(bc & before);
-        if (chosen && pos < (uint32_t)K) idx[pos] = j;  // (pos < K always with finite logits; the guard costs nothing)
-        at += (uint32_t)__popcll(bc);
-        tie_run += (uint32_t)__popcll(beq);
-    }
+    const int i = blockIdx.x, b = blockIdx.y;
+    index_select_row(p.logits + b * p.logits_batch_stride + i * p.logits_row_stride, p.indices + b * p.idx_batch_stride + i * p.idx_row_stride,
+                     visible_of(p, fill_of(p, b), i), p.topk);
 }
 
 // ---- host -------------------------------------------------------------------------------------------------------------------
@@ -252,7 +174,7 @@ struct Form {
 };
 Form form_of(const fa_index_topk_params *p) {
     const int chunk = chunk_of(p->b, p->capacity);
-    return {chunk, (p->capacity + chunk - 1) / chunk, p->capacity <= SELECT_SMALL_KEYS ? SELECT_SMALL : SELECT_LARGE};
+    return {chunk, (p->capacity + chunk - 1) / chunk, select_threads(p->capacity)};
 }
 
 template <int DT, int D>

@@ -32,6 +32,7 @@
 #include "fa_block_select.h"
 #include "fa_block_pattern.h"
 #include "fa_index_topk.h"
+#include "fa_index_prefill.h"
 #include "fa_act.h"
 #include "fa_gemm_act.h"
 #include "fa_dropout_norm.h"
@@ -3172,9 +3173,11 @@ std::string block_select_impl(const Tensor &q, const Tensor &k_summary, const Te
 // ---- the lightning indexer (hopper_interface.kvcache_index_topk; include/fa_index_topk.h): what produces the lists
 // fwd_kvcache_topk reads.  Launches on the current stream, nothing is read on the host; both tensors the launches write are
 // arguments: capturable in a HIP graph.  plan: the form the call takes as text, and nothing is launched.
-std::string index_topk_impl(const Tensor &q_index, const Tensor &k_index_cache, const Tensor &weights, const Tensor &cache_seqlens,
-                            int64_t topk, const OptTensor &cache_batch_idx, const OptTensor &page_table, bool causal,
-                            const Tensor &indices, const Tensor &logits, bool plan) {
+// The checks both indexer entries share: everything but the tensor of logits.  max_rows: the entry's limit on seqlen_q (0: none).
+// Returns the capacity.
+int64_t index_check_inputs(const Tensor &q_index, const Tensor &k_index_cache, const Tensor &weights, const Tensor &cache_seqlens,
+                           int64_t topk, const OptTensor &cache_batch_idx, const OptTensor &page_table, const Tensor &indices,
+                           int64_t max_rows) {
     TORCH_CHECK(q_index.is_cuda() && (q_index.scalar_type() == at::kHalf || q_index.scalar_type() == at::kBFloat16),
                 "q_index must be an fp16 or bf16 CUDA tensor");
     TORCH_CHECK(q_index.dim() == 4, "q_index must have shape (batch_size, seqlen_q, index_heads, index_dim); ragged queries are not supported");
@@ -3183,7 +3186,8 @@ std::string index_topk_impl(const Tensor &q_index, const Tensor &k_index_cache, 
     TORCH_CHECK(dim == 64 || dim == 128, "q_index: index_dim must be 64 or 128, got ", dim);
     TORCH_CHECK(heads >= 16 && heads <= FA_INDEX_MAX_HEADS && heads % 16 == 0, "q_index: index_heads must be a multiple of 16, at most ",
                 FA_INDEX_MAX_HEADS, ", got ", heads);
-    TORCH_CHECK(seqlen_q >= 1 && seqlen_q <= FA_INDEX_MAX_ROWS, "q_index: seqlen_q must be in [1, ", FA_INDEX_MAX_ROWS, "], got ", seqlen_q);
+    TORCH_CHECK(seqlen_q >= 1 && (!max_rows || seqlen_q <= max_rows), "q_index: seqlen_q must be in [1, ", max_rows, "], got ", seqlen_q);
+    TORCH_CHECK(batch_size * seqlen_q <= 0x7fffffff, "q_index: batch_size * seqlen_q must stay below 2^31");
     TORCH_CHECK(k_index_cache.scalar_type() != at::kFloat8_e4m3fn, "an e4m3 k_index_cache is not supported");
     TORCH_CHECK(k_index_cache.is_cuda() && k_index_cache.device() == q_index.device() && k_index_cache.scalar_type() == q_index.scalar_type(),
                 "k_index_cache must be on the device of q_index and have its dtype");
@@ -3212,31 +3216,49 @@ std::string index_topk_impl(const Tensor &q_index, const Tensor &k_index_cache, 
                     indices.size(0) == batch_size && indices.size(1) == seqlen_q && indices.size(2) == 1 && indices.size(3) >= topk &&
                     indices.stride(3) == 1,
                 "indices must be int32 (batch_size, seqlen_q, 1, width >= topk) with contiguous last dimension");
-    TORCH_CHECK(logits.scalar_type() == at::kFloat && logits.is_cuda() && logits.device() == q_index.device() && logits.dim() == 3 &&
-                    logits.size(0) == batch_size && logits.size(1) == seqlen_q && logits.size(2) >= capacity && logits.stride(2) == 1,
-                "logits must be fp32 (batch_size, seqlen_q, width >= capacity) with contiguous last dimension");
-    const Tensor qc = aligned_or_copy(q_index);
     TORCH_CHECK(aligned(k_index_cache), "k_index_cache must be 16-byte aligned with strides that are multiples of 8 elements");
-    auto p = new_params<fa_index_topk_params>();
+    return capacity;
+}
+
+// the fields both params structs name alike
+template <class Params>
+void index_fill_params(Params &p, const Tensor &qc, const Tensor &k_index_cache, const Tensor &weights, const Tensor &cache_seqlens,
+                       int64_t topk, const OptTensor &cache_batch_idx, const OptTensor &page_table, bool causal, const Tensor &indices,
+                       int64_t capacity) {
     p.q_index = qc.data_ptr(); p.k_index_cache = k_index_cache.data_ptr();
     p.weights = static_cast<const float *>(weights.data_ptr());
     p.cache_seqlens = static_cast<const int32_t *>(cache_seqlens.data_ptr());
     p.cache_batch_idx = static_cast<const int32_t *>(ptr(cache_batch_idx));
     p.page_table = static_cast<const int32_t *>(ptr(page_table));
-    p.logits = static_cast<float *>(logits.data_ptr()); p.indices = static_cast<int32_t *>(indices.data_ptr());
+    p.indices = static_cast<int32_t *>(indices.data_ptr());
     p.q_batch_stride = qc.stride(0); p.q_row_stride = qc.stride(1); p.q_head_stride = qc.stride(2);
     p.cache_batch_stride = k_index_cache.stride(0); p.cache_row_stride = k_index_cache.stride(1);
     p.w_batch_stride = weights.stride(0); p.w_row_stride = weights.stride(1);
     if (page_table.has_value()) { p.page_table_batch_stride = page_table->stride(0); p.page_size = (int32_t)k_index_cache.size(1); }
-    p.logits_batch_stride = logits.stride(0); p.logits_row_stride = logits.stride(1);
     p.idx_batch_stride = indices.stride(0); p.idx_row_stride = indices.stride(1);
-    p.b = (int32_t)batch_size; p.s_q = (int32_t)seqlen_q; p.h_i = (int32_t)heads; p.d_i = (int32_t)dim;
+    p.b = (int32_t)qc.size(0); p.s_q = (int32_t)qc.size(1); p.h_i = (int32_t)qc.size(2); p.d_i = (int32_t)qc.size(3);
     p.capacity = (int32_t)capacity;
     p.topk = (int32_t)std::min<int64_t>(topk, 0x7fffffff);
     p.list_width = (int32_t)std::min<int64_t>(indices.size(3), 0x7fffffff);
-    p.logits_width = (int32_t)std::min<int64_t>(logits.size(2), 0x7fffffff);
     p.is_causal = causal ? 1 : 0;
-    p.dtype = p.cache_dtype = dtype_code(q_index);
+    p.dtype = p.cache_dtype = dtype_code(qc);
+}
+
+std::string index_topk_impl(const Tensor &q_index, const Tensor &k_index_cache, const Tensor &weights, const Tensor &cache_seqlens,
+                            int64_t topk, const OptTensor &cache_batch_idx, const OptTensor &page_table, bool causal,
+                            const Tensor &indices, const Tensor &logits, bool plan) {
+    const int64_t capacity = index_check_inputs(q_index, k_index_cache, weights, cache_seqlens, topk, cache_batch_idx, page_table, indices,
+                                                FA_INDEX_MAX_ROWS);
+    const int64_t batch_size = q_index.size(0), seqlen_q = q_index.size(1);
+    TORCH_CHECK(logits.scalar_type() == at::kFloat && logits.is_cuda() && logits.device() == q_index.device() && logits.dim() == 3 &&
+                    logits.size(0) == batch_size && logits.size(1) == seqlen_q && logits.size(2) >= capacity && logits.stride(2) == 1,
+                "logits must be fp32 (batch_size, seqlen_q, width >= capacity) with contiguous last dimension");
+    const Tensor qc = aligned_or_copy(q_index);
+    auto p = new_params<fa_index_topk_params>();
+    index_fill_params(p, qc, k_index_cache, weights, cache_seqlens, topk, cache_batch_idx, page_table, causal, indices, capacity);
+    p.logits = static_cast<float *>(logits.data_ptr());
+    p.logits_batch_stride = logits.stride(0); p.logits_row_stride = logits.stride(1);
+    p.logits_width = (int32_t)std::min<int64_t>(logits.size(2), 0x7fffffff);
     if (plan) {
         const char *name = fa_index_topk_plan_name(&p);
         TORCH_CHECK(name, "fa_index_topk refused (", fa_index_topk_validate(&p), "): ", fa_strerror(fa_index_topk_validate(&p)));
@@ -3245,6 +3267,33 @@ std::string index_topk_impl(const Tensor &q_index, const Tensor &k_index_cache, 
     c10::hip::HIPGuardMasqueradingAsCUDA device_guard(q_index.device());
     const int st = fa_index_topk(&p, current_stream(q_index));
     TORCH_CHECK(st == 0, "fa_index_topk failed (", st, "): ", fa_strerror(st));
+    return {};
+}
+
+// ---- its prefill-sized form (hopper_interface.kvcache_index_topk_prefill; include/fa_index_prefill.h): any seqlen_q; the logits
+// are a workspace (rows, width >= capacity) the call walks in rounds of whole token blocks.  Capturable like the entry above.
+std::string index_prefill_impl(const Tensor &q_index, const Tensor &k_index_cache, const Tensor &weights, const Tensor &cache_seqlens,
+                               int64_t topk, const OptTensor &cache_batch_idx, const OptTensor &page_table, bool causal,
+                               const Tensor &indices, const Tensor &workspace, bool plan) {
+    const int64_t capacity = index_check_inputs(q_index, k_index_cache, weights, cache_seqlens, topk, cache_batch_idx, page_table, indices, 0);
+    TORCH_CHECK(workspace.scalar_type() == at::kFloat && workspace.is_cuda() && workspace.device() == q_index.device() && workspace.dim() == 2 &&
+                    workspace.size(0) >= FA_INDEX_PREFILL_BLOCK && workspace.size(1) >= capacity && workspace.stride(1) == 1 &&
+                    workspace.stride(0) >= workspace.size(1),
+                "workspace must be fp32 (rows >= ", FA_INDEX_PREFILL_BLOCK, ", width >= capacity) with contiguous last dimension");
+    const Tensor qc = aligned_or_copy(q_index);
+    auto p = new_params<fa_index_prefill_params>();
+    index_fill_params(p, qc, k_index_cache, weights, cache_seqlens, topk, cache_batch_idx, page_table, causal, indices, capacity);
+    p.workspace = static_cast<float *>(workspace.data_ptr());
+    p.workspace_row_stride = workspace.stride(0); p.workspace_rows = workspace.size(0);
+    p.workspace_width = (int32_t)std::min<int64_t>(workspace.size(1), 0x7fffffff);
+    if (plan) {
+        const char *name = fa_index_prefill_plan_name(&p);
+        TORCH_CHECK(name, "fa_index_prefill refused (", fa_index_prefill_validate(&p), "): ", fa_strerror(fa_index_prefill_validate(&p)));
+        return name;
+    }
+    c10::hip::HIPGuardMasqueradingAsCUDA device_guard(q_index.device());
+    const int st = fa_index_prefill(&p, current_stream(q_index));
+    TORCH_CHECK(st == 0, "fa_index_prefill failed (", st, "): ", fa_strerror(st));
     return {};
 }
 
@@ -3587,6 +3636,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
                    : "lightning indexer: index logits against the index-key cache and the top-k positions per query token; writes indices and logits",
               py::arg("q_index"), py::arg("k_index_cache"), py::arg("weights"), py::arg("cache_seqlens"), py::arg("topk"),
               py::arg("cache_batch_idx"), py::arg("page_table"), py::arg("causal"), py::arg("indices"), py::arg("logits"));
+        m.def(plan ? "kvcache_index_topk_prefill_plan" : "kvcache_index_topk_prefill",
+              [plan](const Tensor &q_index, const Tensor &k_index_cache, const Tensor &weights, const Tensor &cache_seqlens, int64_t topk,
+                     const OptTensor &cache_batch_idx, const OptTensor &page_table, bool causal, const Tensor &indices, const Tensor &workspace) {
+                  return index_prefill_impl(q_index, k_index_cache, weights, cache_seqlens, topk, cache_batch_idx, page_table, causal, indices,
+                                            workspace, plan);
+              },
+              plan ? "the form kvcache_index_topk_prefill takes with these arguments, as text; nothing is launched"
+                   : "lightning indexer of a prompt: index logits in rounds over a workspace and the top-k positions per query token; writes indices",
+              py::arg("q_index"), py::arg("k_index_cache"), py::arg("weights"), py::arg("cache_seqlens"), py::arg("topk"),
+              py::arg("cache_batch_idx"), py::arg("page_table"), py::arg("causal"), py::arg("indices"), py::arg("workspace"));
     }
     for (const int mode : {0, 1, 2}) {  // the launch, the form, the workspace's bytes
         m.def(mode == 0 ? "block_pattern" : mode == 1 ? "block_pattern_plan" : "block_pattern_workspace_size",

@@ -73,10 +73,14 @@ SELECT_BLOCKS_SCHEMA = (
 INDEX_TOPK_SCHEMA = (
     "kvcache_index_topk(Tensor q_index, Tensor k_index_cache, Tensor weights, Tensor cache_seqlens, int topk, Tensor? cache_batch_idx, "
     "Tensor? page_table, bool causal, Tensor(a!) indices, Tensor(b!) logits) -> ()")
+# ... and the prefill-sized form of it (include/fa_index_prefill.h): the logits are a workspace of rows the call walks in rounds
+INDEX_PREFILL_SCHEMA = (
+    "kvcache_index_topk_prefill(Tensor q_index, Tensor k_index_cache, Tensor weights, Tensor cache_seqlens, int topk, "
+    "Tensor? cache_batch_idx, Tensor? page_table, bool causal, Tensor(a!) indices, Tensor(b!) workspace) -> ()")
 
 _ops = torch.library.Library("flash_attn_3", "DEF")
 for _schema in (FWD_SCHEMA, BWD_SCHEMA, COMBINE_SCHEMA, METADATA_SCHEMA, APPEND_FP8_SCHEMA, KVCACHE_SPARSE_SCHEMA, KVCACHE_TREE_SCHEMA,
-                KVCACHE_TOPK_SCHEMA, BLOCK_SUMMARY_SCHEMA, SELECT_BLOCKS_SCHEMA, INDEX_TOPK_SCHEMA):
+                KVCACHE_TOPK_SCHEMA, BLOCK_SUMMARY_SCHEMA, SELECT_BLOCKS_SCHEMA, INDEX_TOPK_SCHEMA, INDEX_PREFILL_SCHEMA):
     _ops.define(_schema)
 
 
@@ -195,6 +199,13 @@ def _kvcache_index_topk(q_index, k_index_cache, weights, cache_seqlens, topk, ca
                                       indices, logits)
 
 
+def _kvcache_index_topk_prefill(q_index, k_index_cache, weights, cache_seqlens, topk, cache_batch_idx, page_table, causal, indices,
+                                workspace):
+    """The binding's kvcache_index_topk_prefill (fa_index_prefill): a logits and a selection launch per round, no host sync."""
+    _lib.binding().kvcache_index_topk_prefill(q_index, k_index_cache, weights, cache_seqlens, topk, cache_batch_idx, page_table, causal,
+                                              indices, workspace)
+
+
 def _nothing(*args, **kwargs):
     """The fake of an op that only mutates its arguments."""
 
@@ -244,3 +255,5 @@ _ops.impl("kvcache_select_blocks", _kvcache_select_blocks, "CUDA")
 _ops.impl("kvcache_select_blocks", _nothing, "Meta")
 _ops.impl("kvcache_index_topk", _kvcache_index_topk, "CUDA")
 _ops.impl("kvcache_index_topk", _nothing, "Meta")
+_ops.impl("kvcache_index_topk_prefill", _kvcache_index_topk_prefill, "CUDA")
+_ops.impl("kvcache_index_topk_prefill", _nothing, "Meta")

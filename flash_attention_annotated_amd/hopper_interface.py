@@ -642,7 +642,8 @@ def kvcache_index_topk(q_index, k_index_cache, weights, cache_seqlens, topk, *, 
     Returns indices: int32 (batch, seqlen_q, 1, width >= topk), [b, i, 0, :K] the chosen logical positions ASCENDING, [K:topk) = -1;
     a fresh tensor (width = topk) or the buffer given.  return_logits: also logits, fp32 (batch, seqlen_q, width >= capacity): L, and
     -inf at and behind n(b, i); the buffer given or a fresh one.  With NaN inputs the choice is unspecified but every index is in
-    [0, n) or -1.  CPU tensors take index_topk_ref.  No e4m3 index cache, prefill-sized or ragged queries, per-kv-head lists, forced
+    [0, n) or -1.  CPU tensors take index_topk_ref.  More than 16 query tokens (a prompt, a chunk of a chunked prefill) take
+    kvcache_index_topk_prefill, which gives a token the same list.  No e4m3 index cache, ragged queries, per-kv-head lists, forced
     positions, physical-slot output or backward.  One decode step of sparse attention is three calls:
         flash_attn_with_kvcache(q, kv_cache, v_cache, k=k_new, v=v_new, cache_seqlens=lens, ...)   # the append (and k_index_cache[...] = its new rows)
         idx = kvcache_index_topk(q_index, k_index_cache, weights, lens + 1, 2048, page_table=table)
@@ -664,6 +665,50 @@ def kvcache_index_topk(q_index, k_index_cache, weights, cache_seqlens, topk, *, 
     return (indices, logits) if return_logits else indices
 
 
+INDEX_PREFILL_BLOCK = 8  # FA_INDEX_PREFILL_BLOCK: the tokens of one workgroup's block
+INDEX_PREFILL_WORKSPACE_CAP = 256 << 20  # bytes of the workspace kvcache_index_topk_prefill allocates when none is given
+
+
+def kvcache_index_topk_prefill(q_index, k_index_cache, weights, cache_seqlens, topk, *, cache_batch_idx=None, page_table=None,
+                               causal=True, indices=None, workspace=None, return_logits=False):
+    """The lightning indexer for a prompt or a chunk of a chunked prefill: kvcache_index_topk's rule, word for word, for ANY
+    seqlen_q >= 1 (batch * seqlen_q < 2^31) -- a token's logits are bit-equal to what kvcache_index_topk computes for it, so a
+    position's list does not depend on which call produced it; seqlen_q <= 16 is accepted and gives that call's result.  Not in the
+    reference.  include/fa_index_prefill.h pins the rule and the layout.  Arguments as kvcache_index_topk's, but for the logits:
+    (batch, seqlen_q, capacity) fp32 is 2 GiB at 4096 x 131072, so they are a WORKSPACE here, fp32 (rows >= 8, width >= capacity)
+    with contiguous last dimension.  The call runs in rounds of rows // 8 token blocks (8 tokens of one batch entry each): the
+    logits launch of the round (index_logits_prefill_kernel: the block's queries in registers, the key tiles through LDS, one
+    workgroup per (token block, chunk of keys), tiles behind the block's causal edge skipped), its selection launch, then the next
+    round on the same rows, ordered by the stream.  The result does not depend on rows.  workspace=None allocates one round,
+    batch * ceil(seqlen_q / 8) * 8 rows, but at most INDEX_PREFILL_WORKSPACE_CAP = 256 MiB (and at least 8 rows).  No host sync,
+    no sort, no atomics on results; HIP-graph capturable with indices and workspace given.
+    Returns indices: int32 (batch, seqlen_q, 1, width >= topk), [b, i, 0, :K] the chosen logical positions ASCENDING, [K:topk) = -1;
+    a fresh tensor or the buffer given.  return_logits (only where one round holds every row, else ValueError): also a view
+    (batch, seqlen_q, width) of the workspace, of which [b, i, :n(b, i)] holds L and the rest is NOT written.  CPU tensors take
+    index_topk_prefill_ref.  No e4m3 index cache, ragged queries, per-kv-head lists, forced positions or backward.
+    Cost, measured on MI355X: tools/index_prefill_bench.py, profiles/index_prefill.jsonl, DESIGN.md section 4.35."""
+    b, s_q = q_index.shape[0], q_index.shape[1]
+    capacity = page_table.shape[1] * k_index_cache.shape[1] if page_table is not None else k_index_cache.shape[1]
+    if indices is None:
+        indices = torch.empty((b, s_q, 1, topk), dtype=torch.int32, device=q_index.device)
+    padded = -(-s_q // INDEX_PREFILL_BLOCK) * INDEX_PREFILL_BLOCK  # the rows of a batch entry in a one-round workspace
+    if not q_index.is_cuda:
+        ref = index_topk_prefill_ref(q_index, k_index_cache, weights, cache_seqlens, topk, cache_batch_idx=cache_batch_idx,
+                                     page_table=page_table, causal=causal)
+        indices[..., :topk].copy_(ref.indices)
+        return (indices, ref.logits.float()) if return_logits else indices
+    if workspace is None:
+        fit = INDEX_PREFILL_WORKSPACE_CAP // (4 * capacity) // INDEX_PREFILL_BLOCK * INDEX_PREFILL_BLOCK
+        workspace = torch.empty((max(min(b * padded, fit), INDEX_PREFILL_BLOCK), capacity), dtype=torch.float32, device=q_index.device)
+    if return_logits and workspace.shape[0] < b * padded:
+        raise ValueError(f"return_logits needs a workspace that holds every row in one round: {b * padded} rows, got {workspace.shape[0]}")
+    torch.ops.flash_attn_3.kvcache_index_topk_prefill(q_index, k_index_cache, weights, cache_seqlens, topk, cache_batch_idx, page_table,
+                                                      causal, indices, workspace)
+    if not return_logits:
+        return indices
+    return indices, workspace.as_strided((b, s_q, workspace.shape[1]), (padded * workspace.stride(0), workspace.stride(0), 1))
+
+
 class IndexTopk(NamedTuple):
     """index_topk_ref's result.  logits: fp64 (batch, seqlen_q, capacity), L, and -inf at and behind n(b, i).  indices: int32
     (batch, seqlen_q, 1, topk).  A: fp64 like logits, sum_j |w_j| sum_c |q_c k_c|, what an fp32 evaluation of L errs in proportion
@@ -675,8 +720,18 @@ class IndexTopk(NamedTuple):
 
 def index_topk_ref(q_index, k_index_cache, weights, cache_seqlens, topk, *, cache_batch_idx=None, page_table=None, causal=True):
     """The oracle of kvcache_index_topk in plain torch, on any device: L in fp64, the choice by a stable sort."""
+    assert q_index.shape[1] <= 16
+    return _index_topk_rule(q_index, k_index_cache, weights, cache_seqlens, topk, cache_batch_idx, page_table, causal)
+
+
+def index_topk_prefill_ref(q_index, k_index_cache, weights, cache_seqlens, topk, *, cache_batch_idx=None, page_table=None, causal=True):
+    """The oracle of kvcache_index_topk_prefill: index_topk_ref's rule without the limit on seqlen_q."""
+    return _index_topk_rule(q_index, k_index_cache, weights, cache_seqlens, topk, cache_batch_idx, page_table, causal)
+
+
+def _index_topk_rule(q_index, k_index_cache, weights, cache_seqlens, topk, cache_batch_idx, page_table, causal):
     b, s_q, h_i, d_i = q_index.shape
-    assert 1 <= s_q <= 16 and d_i in (64, 128) and h_i % 16 == 0 and 16 <= h_i <= 64 and topk >= 1
+    assert s_q >= 1 and d_i in (64, 128) and h_i % 16 == 0 and 16 <= h_i <= 64 and topk >= 1
     paged, dev = page_table is not None, q_index.device
     capacity = page_table.shape[1] * k_index_cache.shape[1] if paged else k_index_cache.shape[1]
     logits = torch.full((b, s_q, capacity), float("-inf"), dtype=torch.float64, device=dev)
