@@ -80,6 +80,10 @@ EXPORTED_SYMBOLS = (
     "fa_fwd_topk_kv_workspace_size",
     "fa_fwd_topk_kv_plan_name",
     "fa_topk_kv_params_size",
+    "fa_fwd_topk_kv8",
+    "fa_fwd_topk_kv8_validate",
+    "fa_fwd_topk_kv8_workspace_size",
+    "fa_fwd_topk_kv8_plan_name",
     # include/fa_bwd.h
     "fa_bwd",
     "fa_bwd_validate",
@@ -724,6 +728,9 @@ class FaSinkGradParams(ctypes.Structure):
 
 HASH_PATH = os.path.join(_HERE, "libfa_fwd_gfx950.srchash")
 NO_PACKED_FP32_UNITS = ("fa_fwd_topk_kv_api.hip", "fa_index_topk.hip", "fa_index_prefill.hip")
+# units built as objects of their own with the library's plain flags (fa_fwd_topk_kv8_api.hip: qv8_fwd_kernel's options, whose
+# bits its result must equal)
+OWN_OBJECT_UNITS = ("fa_fwd_topk_kv8_api.hip",)
 
 
 def _deps():
@@ -766,9 +773,10 @@ def build(force=False, verbose=False):
         # units compiled without the packed fp32 instructions (v_pk_mul_f32 / v_pk_add_f32 / v_pk_fma_f32): an object each,
         # linked beside the other units, whose device code stays what their tests pin
         objs = []
-        for unit in NO_PACKED_FP32_UNITS:
+        for unit in NO_PACKED_FP32_UNITS + OWN_OBJECT_UNITS:
             objs.append(os.path.join(tmp, os.path.splitext(unit)[0] + ".o"))
-            cmd = [*common, "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops", "-c", os.path.join(CSRC, unit), "-o", objs[-1]]
+            no_packed = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"] if unit in NO_PACKED_FP32_UNITS else []
+            cmd = [*common, *no_packed, "-c", os.path.join(CSRC, unit), "-o", objs[-1]]
             if verbose:
                 print(" ".join(cmd), file=sys.stderr)
             subprocess.run(cmd, check=True)
@@ -873,6 +881,10 @@ _PROTOTYPES = {
         ("fa_fwd_topk_kv_validate", [_FWD, _TOPK_KV], _INT),
         ("fa_fwd_topk_kv_workspace_size", [_FWD, _TOPK_KV], _I64),
         ("fa_fwd_topk_kv_plan_name", [_FWD, _TOPK_KV, _I32], _STR),
+        ("fa_fwd_topk_kv8", [_FWD, _TOPK_KV, _VOID], _INT),
+        ("fa_fwd_topk_kv8_validate", [_FWD, _TOPK_KV], _INT),
+        ("fa_fwd_topk_kv8_workspace_size", [_FWD, _TOPK_KV], _I64),
+        ("fa_fwd_topk_kv8_plan_name", [_FWD, _TOPK_KV, _I32], _STR),
     ),
     "fa_bwd.h": (
         ("fa_bwd", [_BWD, _VOID], _INT, "fa_bwd_params_size", FaBwdParams),

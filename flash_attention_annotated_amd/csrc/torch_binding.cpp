@@ -1225,6 +1225,7 @@ struct TreeWords {
 // The list of fwd_kvcache_topk (include/fa_fwd.h, fa_topk_kv_params), checked there
 struct TopkList {
     Tensor indices;  // int32 (b, seqlen_q, h_k | 1, topk)
+    bool fp8_cache;  // e4m3 caches (else 16-bit caches of q's dtype)
 };
 
 // 16-bit queries over an fp8 (e4m3) KV cache -- kv_cache_dtype = fp8 of a serving stack (include/fa_fwd.h, fa_fwd_kv8): q and
@@ -1238,7 +1239,8 @@ struct TopkList {
 // sparse: the block-sparse read (fa_fwd_sparse_kv) of fwd_kvcache_sparse below, over an e4m3 cache or -- the one case where k / v
 // are 16-bit here -- a cache of q's dtype; the lists ride beside the same params, everything else is handled alike.
 // tree: tree attention (fa_fwd_tree) of fwd_kvcache_tree below, over either cache type as well; the words ride beside the params.
-// topk: the top-k token-sparse MLA decode (fa_fwd_topk_kv) of fwd_kvcache_topk below, with mla set, over a 16-bit cache of q's dtype.
+// topk: the top-k token-sparse MLA decode of fwd_kvcache_topk below, with mla set: fa_fwd_topk_kv over a 16-bit cache of q's
+// dtype, fa_fwd_topk_kv8 over an e4m3 cache.
 std::tuple<Tensor, Tensor> fwd_kv8(const Tensor &q, const Tensor &k, const Tensor &v, const OptTensor &out_,
                                    const OptTensor &cu_seqlens_q, const OptTensor &seqused_q, const OptTensor &seqused_k,
                                    c10::optional<int64_t> max_seqlen_q_, const OptTensor &page_table, const OptTensor &kv_batch_idx,
@@ -1246,7 +1248,7 @@ std::tuple<Tensor, Tensor> fwd_kv8(const Tensor &q, const Tensor &k, const Tenso
                                    double softmax_scale, bool is_causal, int64_t window_size_left, int64_t window_size_right,
                                    double softcap, int64_t num_splits, const OptTensor &qv = c10::nullopt, bool mla = false,
                                    const SparseLists *sparse = nullptr, const TreeWords *tree = nullptr, const TopkList *topk = nullptr) {
-    const bool wide_cache = (sparse && !sparse->fp8_cache) || (tree && !tree->fp8_cache) || topk;  // 16-bit k / v: strides in 2-byte elements
+    const bool wide_cache = (sparse && !sparse->fp8_cache) || (tree && !tree->fp8_cache) || (topk && !topk->fp8_cache);  // 16-bit k / v: strides in 2-byte elements
     CHECK_DEVICE(k, "k"); CHECK_LAST_CONTIGUOUS(k, "Input tensor must have contiguous last dimension");
     CHECK_DEVICE(v, "v"); CHECK_LAST_CONTIGUOUS(v, "Input tensor must have contiguous last dimension");
     const bool ragged = cu_seqlens_q.has_value();
@@ -1363,15 +1365,18 @@ std::tuple<Tensor, Tensor> fwd_kv8(const Tensor &q, const Tensor &k, const Tenso
         kp.head_stride = topk->indices.size(2) == 1 ? 0 : topk->indices.stride(2);
         kp.topk = (int32_t)topk->indices.size(3);
     }
-    const char *entry = topk ? "fa_fwd_topk_kv" : tree ? "fa_fwd_tree" : sparse ? "fa_fwd_sparse_kv" : mla ? "fa_fwd_qv8" : "fa_fwd_kv8";
-    const int64_t need = topk     ? fa_fwd_topk_kv_workspace_size(&p, &kp)
+    const bool topk8 = topk && topk->fp8_cache;
+    const char *entry = topk8 ? "fa_fwd_topk_kv8" : topk ? "fa_fwd_topk_kv" : tree ? "fa_fwd_tree" : sparse ? "fa_fwd_sparse_kv" : mla ? "fa_fwd_qv8" : "fa_fwd_kv8";
+    const int64_t need = topk8    ? fa_fwd_topk_kv8_workspace_size(&p, &kp)
+                         : topk   ? fa_fwd_topk_kv_workspace_size(&p, &kp)
                          : tree   ? fa_fwd_tree_workspace_size(&p, &tp)
                          : sparse ? fa_fwd_sparse_kv_workspace_size(&p, &sp)
                          : mla    ? fa_fwd_qv8_workspace_size(&p)
                                   : fa_fwd_kv8_workspace_size(&p);
     TORCH_CHECK(need >= 0, entry, "_workspace_size failed (", need, "): ", fa_strerror((int)need));
     const Tensor workspace = set_workspace(p, need, q);  // split-KV partials
-    const int st = topk     ? fa_fwd_topk_kv(&p, &kp, current_stream(q))
+    const int st = topk8    ? fa_fwd_topk_kv8(&p, &kp, current_stream(q))
+                   : topk   ? fa_fwd_topk_kv(&p, &kp, current_stream(q))
                    : tree   ? fa_fwd_tree(&p, &tp, current_stream(q))
                    : sparse ? fa_fwd_sparse_kv(&p, &sp, current_stream(q))
                    : mla    ? fa_fwd_qv8(&p, current_stream(q))
@@ -1468,32 +1473,41 @@ std::tuple<Tensor, Tensor> fwd_kvcache_tree(const Tensor &q, const Tensor &k, co
 
 // hopper_interface.flash_attn_with_kvcache_topk / torch.ops.flash_attn_3.fwd_kvcache_topk: MLA decode over the key positions an
 // int32 list names per query token (include/fa_fwd.h, fa_fwd_topk_kv).  q (b, seqlen_q, h, d <= 64) and the optional qv
-// (b, seqlen_q, h, d_v) fp16 / bf16, k (.., h_k, d) and v (.., h_k, d_v in [256, 512]) of q's dtype, batched (kv_batch_idx) or
-// paged; read-only.  The refusals by argument stand here; the cache side, out, the workspace and the launch are fwd_kv8's.
+// (b, seqlen_q, h, d_v) fp16 / bf16, k (.., h_k, d) and v (.., h_k, d_v in [256, 512]) of q's dtype, or Float8_e4m3fn with both
+// descales (fa_fwd_topk_kv8; head dims in multiples of 16), batched (kv_batch_idx) or paged; read-only.  The refusals by argument stand here; the cache side, out, the workspace and the launch are fwd_kv8's.
 // Nothing of the list is read on the host.
 std::tuple<Tensor, Tensor> fwd_kvcache_topk(const Tensor &q, const Tensor &k, const Tensor &v, const Tensor &indices, const OptTensor &qv,
                                             const OptTensor &seqused_k, const OptTensor &kv_batch_idx, const OptTensor &page_table,
-                                            c10::optional<double> softmax_scale_, int64_t num_splits) {
+                                            c10::optional<double> softmax_scale_, int64_t num_splits, const OptTensor &k_descale,
+                                            const OptTensor &v_descale) {
     const auto q_dtype = q.scalar_type();
     TORCH_CHECK(q_dtype == at::kHalf || q_dtype == at::kBFloat16,
                 "This flash attention build supports top-k attention over a KV cache for fp16 / bf16 queries only");
-    TORCH_CHECK(k.scalar_type() == q_dtype && v.scalar_type() == q_dtype,
-                "This flash attention build supports top-k attention over a KV cache of the query's dtype only (no fp8 cache)");
+    TORCH_CHECK(k.scalar_type() == v.scalar_type(), "k_cache and v_cache must have the same dtype");
+    const bool fp8_cache = k.scalar_type() == at::kFloat8_e4m3fn;
+    TORCH_CHECK(fp8_cache || k.scalar_type() == q_dtype,
+                "k_cache / v_cache must have the dtype of the query or be torch.float8_e4m3fn under an fp16 / bf16 query");
+    if (fp8_cache) {
+        TORCH_CHECK(k_descale.has_value() && v_descale.has_value(), "k_descale and v_descale must be provided with an fp8 KV cache");
+    } else {
+        TORCH_CHECK(!k_descale.has_value() && !v_descale.has_value(), "k_descale / v_descale belong to an fp8 KV cache");
+    }
+    const int64_t grain = fp8_cache ? 16 : 8;
     TORCH_CHECK(indices.scalar_type() == at::kInt, "indices must have dtype int32");
     TORCH_CHECK(indices.is_cuda() && indices.device() == q.device(), "indices must be on the same CUDA device as query");
     TORCH_CHECK(indices.dim() == 4 && indices.size(3) >= 1, "indices must have shape (batch_size, seqlen_q, num_heads_k | 1, topk), topk >= 1");
     TORCH_CHECK(indices.size(3) == 1 || indices.stride(3) == 1, "indices must have contiguous last dimension");
     CHECK_DEVICE(q, "q"); CHECK_LAST_CONTIGUOUS(q, "Input tensor must have contiguous last dimension");
     TORCH_CHECK(q.dim() == 4, "q must have shape (batch_size, seqlen_q, num_heads, head_size)");
-    TORCH_CHECK(k.dim() == 4 && v.dim() == 4 && k.size(-1) == q.size(-1) && q.size(-1) <= 64 && q.size(-1) % 8 == 0 && v.size(-1) >= 256 &&
-                    v.size(-1) <= 512 && v.size(-1) % 8 == 0,
+    TORCH_CHECK(k.dim() == 4 && v.dim() == 4 && k.size(-1) == q.size(-1) && q.size(-1) <= 64 && q.size(-1) % grain == 0 && v.size(-1) >= 256 &&
+                    v.size(-1) <= 512 && v.size(-1) % grain == 0,
                 "This flash attention build supports top-k attention over the MLA cache shape only: head_size <= 64 beside "
-                "head_size_v in [256, 512], both multiples of 8");
+                "head_size_v in [256, 512], both multiples of 8 (of 16 over an fp8 KV cache)");
     const double softmax_scale = softmax_scale_.has_value() ? *softmax_scale_
                                                             : 1.0 / std::sqrt((double)(q.size(-1) + (qv.has_value() ? v.size(-1) : 0)));
-    const TopkList list{indices};
+    const TopkList list{indices, fp8_cache};
     return fwd_kv8(q, k, v, c10::nullopt, c10::nullopt, c10::nullopt, seqused_k, c10::nullopt, page_table, kv_batch_idx, c10::nullopt,
-                   c10::nullopt, c10::nullopt, softmax_scale, false, -1, -1, 0.0, num_splits, qv, true, nullptr, nullptr, &list);
+                   k_descale, v_descale, softmax_scale, false, -1, -1, 0.0, num_splits, qv, true, nullptr, nullptr, &list);
 }
 
 // The MLA decode shape over an fp8 KV cache (include/fa_fwd.h, fa_fwd_qv8): q (.., h, d <= 64) and the optional qv (.., h, d_v)
@@ -3601,7 +3615,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "MLA decode over the key positions an int32 list names per query token; returns (out, softmax_lse)",
           py::arg("q"), py::arg("k_cache"), py::arg("v_cache"), py::arg("indices"), py::arg("qv") = py::none(),
           py::arg("cache_seqlens") = py::none(), py::arg("cache_batch_idx") = py::none(), py::arg("page_table") = py::none(),
-          py::arg("softmax_scale") = py::none(), py::arg("num_splits") = 0);
+          py::arg("softmax_scale") = py::none(), py::arg("num_splits") = 0, py::arg("k_descale") = py::none(),
+          py::arg("v_descale") = py::none());
     for (const bool plan : {false, true}) {
         m.def(plan ? "kvcache_block_summary_update_plan" : "kvcache_block_summary_update",
               [plan](const Tensor &k_summary, const Tensor &k_cache, const OptTensor &seqlens_old, const Tensor &seqlens_new,

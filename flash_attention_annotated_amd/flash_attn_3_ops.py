@@ -57,7 +57,8 @@ KVCACHE_TREE_SCHEMA = (
 # nor this: MLA decode over the key positions a top-k list names per query token (DeepSeek-V3.2-style sparse attention), read-only
 KVCACHE_TOPK_SCHEMA = (
     "fwd_kvcache_topk(Tensor q, Tensor k_cache, Tensor v_cache, Tensor indices, Tensor? qv = None, Tensor? cache_seqlens = None, "
-    "Tensor? cache_batch_idx = None, Tensor? page_table = None, float? softmax_scale = None, int num_splits = 0) -> (Tensor, Tensor)")
+    "Tensor? cache_batch_idx = None, Tensor? page_table = None, float? softmax_scale = None, int num_splits = 0, "
+    "Tensor? k_descale = None, Tensor? v_descale = None) -> (Tensor, Tensor)")
 # ... nor what produces the sparse route's lists (include/fa_block_select.h): the block summaries of the keys, updated in place on append, and
 # the Quest selection.  Every tensor the launches write is a mutated argument and nothing is returned, so that a traced graph
 # holds no alias of an input; hopper_interface allocates what the caller does not give
@@ -166,15 +167,16 @@ def _fwd_kvcache_tree_meta(q, k_cache, v_cache, tree_mask, cache_seqlens=None, c
 
 
 def _fwd_kvcache_topk(q, k_cache, v_cache, indices, qv=None, cache_seqlens=None, cache_batch_idx=None, page_table=None,
-                      softmax_scale=None, num_splits=0):
-    """The binding's fwd_kvcache_topk (fa_fwd_topk_kv): one launch (+ the merge of a split call), no host sync."""
+                      softmax_scale=None, num_splits=0, k_descale=None, v_descale=None):
+    """The binding's fwd_kvcache_topk (fa_fwd_topk_kv; an e4m3 cache: fa_fwd_topk_kv8): one launch (+ the merge of a split call),
+    no host sync."""
     out, lse = _lib.binding().fwd_kvcache_topk(q, k_cache, v_cache, indices, qv, cache_seqlens, cache_batch_idx, page_table,
-                                               softmax_scale, num_splits)
+                                               softmax_scale, num_splits, k_descale, v_descale)
     return out, lse
 
 
 def _fwd_kvcache_topk_meta(q, k_cache, v_cache, indices, qv=None, cache_seqlens=None, cache_batch_idx=None, page_table=None,
-                           softmax_scale=None, num_splits=0):
+                           softmax_scale=None, num_splits=0, k_descale=None, v_descale=None):
     return (q.new_empty((*q.shape[:-1], v_cache.shape[-1])),
             q.new_empty((q.shape[0], q.shape[2], q.shape[1]), dtype=torch.float32))
 

@@ -316,13 +316,15 @@ def flash_attn_with_kvcache_tree(q, k_cache, v_cache, tree_mask, *, cache_seqlen
 
 
 def flash_attn_with_kvcache_topk(q, k_cache, v_cache, indices, qv=None, cache_seqlens=None, cache_batch_idx=None, page_table=None,
-                                 softmax_scale=None, num_splits=0, return_softmax_lse=False):
+                                 softmax_scale=None, num_splits=0, return_softmax_lse=False, k_descale=None, v_descale=None):
     """Top-k token-sparse MLA decode over the latent KV cache: the attention half of DeepSeek-V3.2-style sparse attention (DSA).
     Every query token attends to the key positions its list names, and to those alone.  Not in the reference.
     q: (batch, seqlen_q, nheads, headdim <= 64); qv: optional (batch, seqlen_q, nheads, headdim_v); fp16 / bf16.  k_cache
-    (.., nheads_k, headdim) / v_cache (.., nheads_k, headdim_v in [256, 512]): the MLA cache of q's dtype as in
-    flash_attn_with_kvcache -- batched with cache_batch_idx, or pages of any size behind page_table.  sk(b) is the fill level:
-    cache_seqlens, clamped to the capacity.
+    (.., nheads_k, headdim) / v_cache (.., nheads_k, headdim_v in [256, 512]): the MLA cache as in flash_attn_with_kvcache --
+    batched with cache_batch_idx, or pages of any size behind page_table -- of q's dtype (head dims in multiples of 8), or
+    torch.float8_e4m3fn (head dims in multiples of 16) with both k_descale / v_descale, fp32 (batch, nheads_k): the cache
+    kvcache_append_fp8 writes, S = (kd q K8^T + vd qv V8^T) * softmax_scale and O = vd P V8 / l in fp32.  sk(b) is the fill
+    level: cache_seqlens, clamped to the capacity.
     indices: int32 (batch, seqlen_q, nheads_k | 1, topk) on the device, last dimension contiguous, any other strides; a head
     dimension of size 1 is shared by all kv heads.  topk >= 1, any value.  An entry is a LOGICAL position of the sequence (the
     kernel does the page lookup).  With g = nheads / nheads_k, key j of batch b is visible to query token i, head h iff j is
@@ -335,16 +337,18 @@ def flash_attn_with_kvcache_topk(q, k_cache, v_cache, indices, qv=None, cache_se
     num_splits: 1 = off, N = N parts of the list's TILES, 0 = the count the MLA decode shape gets for a key length of topk --
     from shapes only.  Nothing of indices or cache_seqlens is read on the host and nothing synchronises: the call can be
     captured into a HIP graph, and a replay after indices was overwritten in place computes the new selection.
-    Read-only: append with flash_attn_with_kvcache(k=, v=) first, then call this on the new fill levels.  No fp8 cache, ragged
+    Read-only: append with flash_attn_with_kvcache(k=, v=) or kvcache_append_fp8 first, then call this on the new fill levels.  No ragged
     queries, per-entry counts, physical-slot lists or backward; the selection step that produces the lists is not part of it.
-    At nheads / nheads_k > 32 the row blocks of a token gather the same rows again, from L2.  DESIGN.md section 4.33.
+    At nheads / nheads_k > 32 the row blocks of a token gather the same rows again, from L2.  DESIGN.md sections 4.33 (16-bit cache, tk_fwd_kernel) and 4.36
+    (fp8 cache, tk8_fwd_kernel: with every position listed in order, bit-equal to flash_attn_with_kvcache(qv=, k_descale=,
+    v_descale=)).
     Returns out (batch, seqlen_q, nheads, headdim_v), or (out, softmax_lse) when return_softmax_lse: (batch, nheads, seqlen_q)."""
     assert k_cache.stride(-1) == 1, "k_cache must have contiguous last dimension"
     assert v_cache.stride(-1) == 1, "v_cache must have contiguous last dimension"
     if cache_seqlens is not None and isinstance(cache_seqlens, int):
         cache_seqlens = torch.full((q.shape[0],), cache_seqlens, dtype=torch.int32, device=k_cache.device)
     out, softmax_lse = torch.ops.flash_attn_3.fwd_kvcache_topk(q, k_cache, v_cache, indices, qv, cache_seqlens, cache_batch_idx,
-                                                                page_table, softmax_scale, num_splits)
+                                                                page_table, softmax_scale, num_splits, k_descale, v_descale)
     return (out, softmax_lse) if return_softmax_lse else out
 
 

@@ -251,7 +251,7 @@ int fa_fwd_validate(const fa_fwd_params *params);
  * device access; the text lives in thread-local storage until the next call on the same thread. */
 const char *fa_fwd_plan_name(const fa_fwd_params *params, int32_t num_cus);
 
-/* Test hook: the name of the plan the calling thread's most recent fa_fwd() (or fa_fwd_sink, fa_fwd_block_sparse, fa_fwd_kv8, fa_fwd_qv8, fa_fwd_sparse_kv, fa_fwd_tree, fa_fwd_topk_kv) launched (same text as fa_fwd_plan_name on that
+/* Test hook: the name of the plan the calling thread's most recent fa_fwd() (or fa_fwd_sink, fa_fwd_block_sparse, fa_fwd_kv8, fa_fwd_qv8, fa_fwd_sparse_kv, fa_fwd_tree, fa_fwd_topk_kv, fa_fwd_topk_kv8) launched (same text as fa_fwd_plan_name on that
  * call's params and the device's CU count; for a wide V run as several 256-column calls, the outer "... cols=N" plan).  NULL
  * before the first call or when that call failed validation; unspecified after a call that returned any other error (a failed
  * 256-column part leaves that part's plan).  fa_fwd keeps a struct copy; the text is made here, in
@@ -565,6 +565,24 @@ int fa_fwd_topk_kv_validate(const fa_fwd_params *params, const fa_topk_kv_params
 int64_t fa_fwd_topk_kv_workspace_size(const fa_fwd_params *params, const fa_topk_kv_params *topk);
 const char *fa_fwd_topk_kv_plan_name(const fa_fwd_params *params, const fa_topk_kv_params *topk, int32_t num_cus);
 uint32_t fa_topk_kv_params_size(void);
+
+/*
+ * The same call over the fp8 (OCP e4m3fn) latent KV cache: fa_fwd_topk_kv's definition word for word (the list, its strides,
+ * validity by unsigned compare, duplicates, empty rows, split-KV over the tiles of the list, num_splits, the workspace, no host
+ * read), with the cache and the arithmetic of fa_fwd_qv8: k (.., h_k, d <= 64) and v (.., h_k, d_v in [256, 512]) are e4m3
+ * bytes under 16-bit q / qv / o of params->dtype, both head dims multiples of 16, k / v strides in bytes and multiples of 16,
+ * the row strides below 2^24, base pointers 16-byte aligned; k_descale / v_descale fp32 behind their (batch, head) strides,
+ * NULL = 1.  S = (kd . q.K8^T + vd . qv.V8^T) . softmax_scale, O = vd . P.V8 / l in fp32; kd never enters a second time.
+ * One kernel, tk8_fwd_kernel (csrc/fa_fwd_kernel_tk8.h).  With every position listed in order the unsplit result is bit-equal to
+ * fa_fwd_qv8's on the same cache.  The same struct; the refusals are fa_fwd_topk_kv's with d % 16 / d_v % 16 and fa_fwd_qv8's
+ * FA_ERR_BAD_STRIDE rules for the cache.  fa_fwd_last_plan_name() names such a call
+ *   "tk8_fwd_kernel DVT=<256|512> waves=4 topk=<topk> splits=<N>".
+ */
+int fa_fwd_topk_kv8(const fa_fwd_params *params, const fa_topk_kv_params *topk, void *stream);
+/* Validation only; no device access. */
+int fa_fwd_topk_kv8_validate(const fa_fwd_params *params, const fa_topk_kv_params *topk);
+int64_t fa_fwd_topk_kv8_workspace_size(const fa_fwd_params *params, const fa_topk_kv_params *topk);
+const char *fa_fwd_topk_kv8_plan_name(const fa_fwd_params *params, const fa_topk_kv_params *topk, int32_t num_cus);
 
 /* Human-readable text for a status code (static storage). */
 const char *fa_strerror(int status);
