@@ -33,6 +33,7 @@
 #include "fa_block_pattern.h"
 #include "fa_index_topk.h"
 #include "fa_index_prefill.h"
+#include "fa_index_topk8.h"
 #include "fa_act.h"
 #include "fa_gemm_act.h"
 #include "fa_dropout_norm.h"
@@ -3191,7 +3192,7 @@ std::string block_select_impl(const Tensor &q, const Tensor &k_summary, const Te
 // Returns the capacity.
 int64_t index_check_inputs(const Tensor &q_index, const Tensor &k_index_cache, const Tensor &weights, const Tensor &cache_seqlens,
                            int64_t topk, const OptTensor &cache_batch_idx, const OptTensor &page_table, const Tensor &indices,
-                           int64_t max_rows) {
+                           int64_t max_rows, bool fp8_cache = false) {
     TORCH_CHECK(q_index.is_cuda() && (q_index.scalar_type() == at::kHalf || q_index.scalar_type() == at::kBFloat16),
                 "q_index must be an fp16 or bf16 CUDA tensor");
     TORCH_CHECK(q_index.dim() == 4, "q_index must have shape (batch_size, seqlen_q, index_heads, index_dim); ragged queries are not supported");
@@ -3202,9 +3203,14 @@ int64_t index_check_inputs(const Tensor &q_index, const Tensor &k_index_cache, c
                 FA_INDEX_MAX_HEADS, ", got ", heads);
     TORCH_CHECK(seqlen_q >= 1 && (!max_rows || seqlen_q <= max_rows), "q_index: seqlen_q must be in [1, ", max_rows, "], got ", seqlen_q);
     TORCH_CHECK(batch_size * seqlen_q <= 0x7fffffff, "q_index: batch_size * seqlen_q must stay below 2^31");
-    TORCH_CHECK(k_index_cache.scalar_type() != at::kFloat8_e4m3fn, "an e4m3 k_index_cache is not supported");
-    TORCH_CHECK(k_index_cache.is_cuda() && k_index_cache.device() == q_index.device() && k_index_cache.scalar_type() == q_index.scalar_type(),
-                "k_index_cache must be on the device of q_index and have its dtype");
+    if (fp8_cache) {
+        TORCH_CHECK(k_index_cache.is_cuda() && k_index_cache.device() == q_index.device() && k_index_cache.scalar_type() == at::kFloat8_e4m3fn,
+                    "k_index_cache must be a float8_e4m3fn tensor on the device of q_index");
+    } else {
+        TORCH_CHECK(k_index_cache.scalar_type() != at::kFloat8_e4m3fn, "an e4m3 k_index_cache is not supported");
+        TORCH_CHECK(k_index_cache.is_cuda() && k_index_cache.device() == q_index.device() && k_index_cache.scalar_type() == q_index.scalar_type(),
+                    "k_index_cache must be on the device of q_index and have its dtype");
+    }
     TORCH_CHECK(k_index_cache.dim() == 3 && k_index_cache.size(2) == dim,
                 "k_index_cache must have shape (batch or num_pages, seqlen or page_size, index_dim)");
     CHECK_LAST_CONTIGUOUS(k_index_cache, "k_index_cache must have contiguous last dimension");
@@ -3230,7 +3236,13 @@ int64_t index_check_inputs(const Tensor &q_index, const Tensor &k_index_cache, c
                     indices.size(0) == batch_size && indices.size(1) == seqlen_q && indices.size(2) == 1 && indices.size(3) >= topk &&
                     indices.stride(3) == 1,
                 "indices must be int32 (batch_size, seqlen_q, 1, width >= topk) with contiguous last dimension");
-    TORCH_CHECK(aligned(k_index_cache), "k_index_cache must be 16-byte aligned with strides that are multiples of 8 elements");
+    if (fp8_cache) {
+        TORCH_CHECK(reinterpret_cast<uintptr_t>(k_index_cache.data_ptr()) % 16 == 0 && k_index_cache.stride(0) % 16 == 0 &&
+                        k_index_cache.stride(1) % 16 == 0,
+                    "an e4m3 k_index_cache must be 16-byte aligned with strides that are multiples of 16 bytes");
+    } else {
+        TORCH_CHECK(aligned(k_index_cache), "k_index_cache must be 16-byte aligned with strides that are multiples of 8 elements");
+    }
     return capacity;
 }
 
@@ -3309,6 +3321,113 @@ std::string index_prefill_impl(const Tensor &q_index, const Tensor &k_index_cach
     const int st = fa_index_prefill(&p, current_stream(q_index));
     TORCH_CHECK(st == 0, "fa_index_prefill failed (", st, "): ", fa_strerror(st));
     return {};
+}
+
+// ---- the indexer over an e4m3 index-key cache with one scale per token (hopper_interface.kvcache_index_topk(k_index_scale=) and
+// kvcache_index_append_fp8; include/fa_index_topk8.h).  Capturable like the entries above.
+// k_index_scale: fp32, the leading two dimensions of the cache
+void index_check_scale(const Tensor &k_index_scale, const Tensor &k_index_cache) {
+    TORCH_CHECK(k_index_scale.scalar_type() == at::kFloat && k_index_scale.is_cuda() && k_index_scale.device() == k_index_cache.device() &&
+                    k_index_scale.dim() == 2 && k_index_scale.size(0) == k_index_cache.size(0) &&
+                    k_index_scale.size(1) == k_index_cache.size(1) && k_index_scale.stride(1) == 1 && k_index_scale.stride(0) >= 0,
+                "k_index_scale must be fp32 (batch or num_pages, seqlen or page_size) on the device of k_index_cache with contiguous last "
+                "dimension");
+}
+
+std::string index_topk8_impl(const Tensor &q_index, const Tensor &k_index_cache, const Tensor &k_index_scale, const Tensor &weights,
+                             const Tensor &cache_seqlens, int64_t topk, const OptTensor &cache_batch_idx, const OptTensor &page_table,
+                             bool causal, const Tensor &indices, const Tensor &logits, bool plan) {
+    const int64_t capacity = index_check_inputs(q_index, k_index_cache, weights, cache_seqlens, topk, cache_batch_idx, page_table, indices,
+                                                FA_INDEX_MAX_ROWS, true);
+    index_check_scale(k_index_scale, k_index_cache);
+    const int64_t batch_size = q_index.size(0), seqlen_q = q_index.size(1);
+    TORCH_CHECK(logits.scalar_type() == at::kFloat && logits.is_cuda() && logits.device() == q_index.device() && logits.dim() == 3 &&
+                    logits.size(0) == batch_size && logits.size(1) == seqlen_q && logits.size(2) >= capacity && logits.stride(2) == 1,
+                "logits must be fp32 (batch_size, seqlen_q, width >= capacity) with contiguous last dimension");
+    const Tensor qc = aligned_or_copy(q_index);
+    auto p = new_params<fa_index_topk8_params>();
+    index_fill_params(p, qc, k_index_cache, weights, cache_seqlens, topk, cache_batch_idx, page_table, causal, indices, capacity);
+    p.cache_dtype = FA_DTYPE_FP8_E4M3;
+    p.k_index_scale = static_cast<const float *>(k_index_scale.data_ptr());
+    p.scale_batch_stride = k_index_scale.stride(0);
+    p.logits = static_cast<float *>(logits.data_ptr());
+    p.logits_batch_stride = logits.stride(0); p.logits_row_stride = logits.stride(1);
+    p.logits_width = (int32_t)std::min<int64_t>(logits.size(2), 0x7fffffff);
+    if (plan) {
+        const char *name = fa_index_topk8_plan_name(&p);
+        TORCH_CHECK(name, "fa_index_topk8 refused (", fa_index_topk8_validate(&p), "): ", fa_strerror(fa_index_topk8_validate(&p)));
+        return name;
+    }
+    c10::hip::HIPGuardMasqueradingAsCUDA device_guard(q_index.device());
+    const int st = fa_index_topk8(&p, current_stream(q_index));
+    TORCH_CHECK(st == 0, "fa_index_topk8 failed (", st, "): ", fa_strerror(st));
+    return {};
+}
+
+// the quantising append to that cache: one launch; returns the new fill levels
+Tensor kvcache_index_append_fp8(const Tensor &k_index_cache, const Tensor &k_index_scale, const Tensor &k_index_new,
+                                const Tensor &cache_seqlens, const OptTensor &cu_seqlens_k_new, const OptTensor &cache_batch_idx,
+                                const OptTensor &page_table) {
+    TORCH_CHECK(k_index_cache.is_cuda() && k_index_cache.scalar_type() == at::kFloat8_e4m3fn && k_index_cache.dim() == 3 &&
+                    (k_index_cache.size(2) == 64 || k_index_cache.size(2) == 128),
+                "k_index_cache must be a float8_e4m3fn CUDA tensor of shape (batch or num_pages, seqlen or page_size, index_dim 64 or 128)");
+    CHECK_LAST_CONTIGUOUS(k_index_cache, "k_index_cache must have contiguous last dimension");
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(k_index_cache.data_ptr()) % 8 == 0 && k_index_cache.stride(0) % 8 == 0 && k_index_cache.stride(1) % 8 == 0,
+                "k_index_cache must be 8-byte aligned with strides that are multiples of 8 bytes to be appended to");
+    index_check_scale(k_index_scale, k_index_cache);
+    const int64_t dim = k_index_cache.size(2), batch_size = cache_seqlens.numel();
+    TORCH_CHECK(batch_size >= 1, "cache_seqlens must hold a fill level per batch entry");
+    check_fill(cache_seqlens, "cache_seqlens", batch_size, k_index_cache);
+    const bool ragged = cu_seqlens_k_new.has_value();
+    TORCH_CHECK(k_index_new.is_cuda() && k_index_new.device() == k_index_cache.device() &&
+                    (k_index_new.scalar_type() == at::kHalf || k_index_new.scalar_type() == at::kBFloat16),
+                "k_index_new must be an fp16 or bf16 tensor on the device of k_index_cache");
+    if (ragged) {
+        TORCH_CHECK(cu_seqlens_k_new->scalar_type() == at::kInt && cu_seqlens_k_new->is_cuda() &&
+                        cu_seqlens_k_new->device() == k_index_cache.device() && cu_seqlens_k_new->dim() == 1 &&
+                        cu_seqlens_k_new->size(0) == batch_size + 1 && cu_seqlens_k_new->is_contiguous(),
+                    "cu_seqlens_k_new must be a contiguous int32 CUDA tensor of shape (batch_size + 1,)");
+        TORCH_CHECK(k_index_new.dim() == 2 && k_index_new.size(1) == dim, "k_index_new must have shape (total_new, index_dim) with cu_seqlens_k_new");
+    } else {
+        TORCH_CHECK(k_index_new.dim() == 3 && k_index_new.size(0) == batch_size && k_index_new.size(2) == dim,
+                    "k_index_new must have shape (batch_size, seqlen_new, index_dim)");
+    }
+    CHECK_LAST_CONTIGUOUS(k_index_new, "k_index_new must have contiguous last dimension");
+    TORCH_CHECK(k_index_new.size(0) <= 0x7fffffff && k_index_new.numel() / dim <= 0x7fffffff, "k_index_new: the rows must stay below 2^31");
+    int64_t capacity;
+    if (page_table.has_value()) {
+        TORCH_CHECK(!cache_batch_idx.has_value(), "Paged KVcache does not support cache_batch_idx");
+        TORCH_CHECK(page_table->scalar_type() == at::kInt && page_table->is_cuda() && page_table->dim() == 2 &&
+                        page_table->size(0) == batch_size && page_table->stride(1) == 1,
+                    "page_table must be an int32 CUDA tensor of shape (batch_size, max_num_pages_per_seq) with contiguous last dimension");
+        capacity = page_table->size(1) * k_index_cache.size(1);
+    } else {
+        capacity = k_index_cache.size(1);
+        if (cache_batch_idx.has_value()) check_fill(*cache_batch_idx, "cache_batch_idx", batch_size, k_index_cache);
+        else TORCH_CHECK(batch_size <= k_index_cache.size(0), "the batch must fit the cache without cache_batch_idx");
+    }
+    TORCH_CHECK(capacity >= 1 && capacity <= FA_INDEX_MAX_KEYS, "the capacity must be in [1, ", FA_INDEX_MAX_KEYS, "], got ", capacity);
+    c10::hip::HIPGuardMasqueradingAsCUDA device_guard(k_index_cache.device());
+    const Tensor kn = aligned_or_copy(k_index_new);
+    Tensor seqused_out = at::empty({batch_size}, cache_seqlens.options());
+    auto p = new_params<fa_index_append8_params>();
+    p.k_index_new = kn.data_ptr(); p.k_index_cache = k_index_cache.data_ptr();
+    p.k_index_scale = static_cast<float *>(k_index_scale.data_ptr());
+    p.cache_seqlens = static_cast<const int32_t *>(cache_seqlens.data_ptr());
+    p.cache_batch_idx = static_cast<const int32_t *>(ptr(cache_batch_idx));
+    p.page_table = static_cast<const int32_t *>(ptr(page_table));
+    p.cu_seqlens_k_new = static_cast<const int32_t *>(ptr(cu_seqlens_k_new));
+    p.seqused_out = static_cast<int32_t *>(seqused_out.data_ptr());
+    if (ragged) { p.new_row_stride = kn.stride(0); p.total_new = (int32_t)kn.size(0); }
+    else { p.new_batch_stride = kn.stride(0); p.new_row_stride = kn.stride(1); p.s_new = (int32_t)kn.size(1); }
+    p.cache_batch_stride = k_index_cache.stride(0); p.cache_row_stride = k_index_cache.stride(1);
+    p.scale_batch_stride = k_index_scale.stride(0);
+    if (page_table.has_value()) { p.page_table_batch_stride = page_table->stride(0); p.page_size = (int32_t)k_index_cache.size(1); }
+    p.b = (int32_t)batch_size; p.d_i = (int32_t)dim; p.capacity = (int32_t)capacity;
+    p.dtype = dtype_code(kn);
+    const int st = fa_index_append8(&p, current_stream(k_index_cache));
+    TORCH_CHECK(st == 0, "fa_index_append8 failed (", st, "): ", fa_strerror(st));
+    return seqused_out;
 }
 
 // ---- block-sparse prefill patterns (cute_interface.block_sparse_select; include/fa_block_pattern.h): what produces the lists
@@ -3661,7 +3780,22 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
                    : "lightning indexer of a prompt: index logits in rounds over a workspace and the top-k positions per query token; writes indices",
               py::arg("q_index"), py::arg("k_index_cache"), py::arg("weights"), py::arg("cache_seqlens"), py::arg("topk"),
               py::arg("cache_batch_idx"), py::arg("page_table"), py::arg("causal"), py::arg("indices"), py::arg("workspace"));
+        m.def(plan ? "kvcache_index_topk_fp8_plan" : "kvcache_index_topk_fp8",
+              [plan](const Tensor &q_index, const Tensor &k_index_cache, const Tensor &k_index_scale, const Tensor &weights,
+                     const Tensor &cache_seqlens, int64_t topk, const OptTensor &cache_batch_idx, const OptTensor &page_table, bool causal,
+                     const Tensor &indices, const Tensor &logits) {
+                  return index_topk8_impl(q_index, k_index_cache, k_index_scale, weights, cache_seqlens, topk, cache_batch_idx, page_table,
+                                          causal, indices, logits, plan);
+              },
+              plan ? "the form kvcache_index_topk_fp8 takes with these arguments, as text; nothing is launched"
+                   : "lightning indexer over an e4m3 index-key cache with one scale per token; writes indices and logits",
+              py::arg("q_index"), py::arg("k_index_cache"), py::arg("k_index_scale"), py::arg("weights"), py::arg("cache_seqlens"),
+              py::arg("topk"), py::arg("cache_batch_idx"), py::arg("page_table"), py::arg("causal"), py::arg("indices"), py::arg("logits"));
     }
+    m.def("kvcache_index_append_fp8", &kvcache_index_append_fp8,
+          "quantising in-place append of 16-bit rows to an e4m3 index-key cache and its per-token scales; returns the new fill levels",
+          py::arg("k_index_cache"), py::arg("k_index_scale"), py::arg("k_index_new"), py::arg("cache_seqlens"),
+          py::arg("cu_seqlens_k_new") = py::none(), py::arg("cache_batch_idx") = py::none(), py::arg("page_table") = py::none());
     for (const int mode : {0, 1, 2}) {  // the launch, the form, the workspace's bytes
         m.def(mode == 0 ? "block_pattern" : mode == 1 ? "block_pattern_plan" : "block_pattern_workspace_size",
               [mode](const Tensor &q, const Tensor &k, const Tensor &full_block_cnt, const Tensor &full_block_idx, const Tensor &mask_block_cnt,

@@ -78,10 +78,19 @@ INDEX_TOPK_SCHEMA = (
 INDEX_PREFILL_SCHEMA = (
     "kvcache_index_topk_prefill(Tensor q_index, Tensor k_index_cache, Tensor weights, Tensor cache_seqlens, int topk, "
     "Tensor? cache_batch_idx, Tensor? page_table, bool causal, Tensor(a!) indices, Tensor(b!) workspace) -> ()")
+# ... and the indexer over an e4m3 index-key cache with one fp32 scale per token (include/fa_index_topk8.h), with the quantising
+# append that fills that cache and its scales in place and returns the new fill levels
+INDEX_TOPK_FP8_SCHEMA = (
+    "kvcache_index_topk_fp8(Tensor q_index, Tensor k_index_cache, Tensor k_index_scale, Tensor weights, Tensor cache_seqlens, int topk, "
+    "Tensor? cache_batch_idx, Tensor? page_table, bool causal, Tensor(a!) indices, Tensor(b!) logits) -> ()")
+INDEX_APPEND_FP8_SCHEMA = (
+    "kvcache_index_append_fp8(Tensor(a!) k_index_cache, Tensor(b!) k_index_scale, Tensor k_index_new, Tensor cache_seqlens, "
+    "Tensor? cu_seqlens_k_new = None, Tensor? cache_batch_idx = None, Tensor? page_table = None) -> Tensor")
 
 _ops = torch.library.Library("flash_attn_3", "DEF")
 for _schema in (FWD_SCHEMA, BWD_SCHEMA, COMBINE_SCHEMA, METADATA_SCHEMA, APPEND_FP8_SCHEMA, KVCACHE_SPARSE_SCHEMA, KVCACHE_TREE_SCHEMA,
-                KVCACHE_TOPK_SCHEMA, BLOCK_SUMMARY_SCHEMA, SELECT_BLOCKS_SCHEMA, INDEX_TOPK_SCHEMA, INDEX_PREFILL_SCHEMA):
+                KVCACHE_TOPK_SCHEMA, BLOCK_SUMMARY_SCHEMA, SELECT_BLOCKS_SCHEMA, INDEX_TOPK_SCHEMA, INDEX_PREFILL_SCHEMA,
+                INDEX_TOPK_FP8_SCHEMA, INDEX_APPEND_FP8_SCHEMA):
     _ops.define(_schema)
 
 
@@ -208,6 +217,25 @@ def _kvcache_index_topk_prefill(q_index, k_index_cache, weights, cache_seqlens, 
                                               indices, workspace)
 
 
+def _kvcache_index_topk_fp8(q_index, k_index_cache, k_index_scale, weights, cache_seqlens, topk, cache_batch_idx, page_table, causal,
+                            indices, logits):
+    """The binding's kvcache_index_topk_fp8 (fa_index_topk8): the logits launch over the byte tile and the selection launch."""
+    _lib.binding().kvcache_index_topk_fp8(q_index, k_index_cache, k_index_scale, weights, cache_seqlens, topk, cache_batch_idx,
+                                          page_table, causal, indices, logits)
+
+
+def _kvcache_index_append_fp8(k_index_cache, k_index_scale, k_index_new, cache_seqlens, cu_seqlens_k_new=None, cache_batch_idx=None,
+                              page_table=None):
+    """The binding's kvcache_index_append_fp8 (fa_index_append8): one launch, returns the new fill levels."""
+    return _lib.binding().kvcache_index_append_fp8(k_index_cache, k_index_scale, k_index_new, cache_seqlens, cu_seqlens_k_new,
+                                                   cache_batch_idx, page_table)
+
+
+def _kvcache_index_append_fp8_meta(k_index_cache, k_index_scale, k_index_new, cache_seqlens, cu_seqlens_k_new=None,
+                                   cache_batch_idx=None, page_table=None):
+    return torch.empty_like(cache_seqlens)
+
+
 def _nothing(*args, **kwargs):
     """The fake of an op that only mutates its arguments."""
 
@@ -259,3 +287,7 @@ _ops.impl("kvcache_index_topk", _kvcache_index_topk, "CUDA")
 _ops.impl("kvcache_index_topk", _nothing, "Meta")
 _ops.impl("kvcache_index_topk_prefill", _kvcache_index_topk_prefill, "CUDA")
 _ops.impl("kvcache_index_topk_prefill", _nothing, "Meta")
+_ops.impl("kvcache_index_topk_fp8", _kvcache_index_topk_fp8, "CUDA")
+_ops.impl("kvcache_index_topk_fp8", _nothing, "Meta")
+_ops.impl("kvcache_index_append_fp8", _kvcache_index_append_fp8, "CUDA")
+_ops.impl("kvcache_index_append_fp8", _kvcache_index_append_fp8_meta, "Meta")

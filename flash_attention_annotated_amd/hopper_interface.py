@@ -630,7 +630,7 @@ def select_blocks_ref(q, k_summary, cache_seqlens, num_blocks, *, kv_block_size=
 
 
 def kvcache_index_topk(q_index, k_index_cache, weights, cache_seqlens, topk, *, cache_batch_idx=None, page_table=None, causal=True,
-                       indices=None, logits=None, return_logits=False):
+                       indices=None, logits=None, return_logits=False, k_index_scale=None):
     """The lightning indexer of DeepSeek-V3.2-style sparse attention (DSA): which key positions every query token of a decode,
     MTP or verify step attends to -- the list flash_attn_with_kvcache_topk takes.  Not in the reference.  Two launches (the logits
     split over chunks of keys, so that batch 1 fills the chip; then one workgroup per (batch, token) selects), no host sync, no
@@ -647,8 +647,15 @@ def kvcache_index_topk(q_index, k_index_cache, weights, cache_seqlens, topk, *, 
     a fresh tensor (width = topk) or the buffer given.  return_logits: also logits, fp32 (batch, seqlen_q, width >= capacity): L, and
     -inf at and behind n(b, i); the buffer given or a fresh one.  With NaN inputs the choice is unspecified but every index is in
     [0, n) or -1.  CPU tensors take index_topk_ref.  More than 16 query tokens (a prompt, a chunk of a chunked prefill) take
-    kvcache_index_topk_prefill, which gives a token the same list.  No e4m3 index cache, ragged queries, per-kv-head lists, forced
-    positions, physical-slot output or backward.  One decode step of sparse attention is three calls:
+    kvcache_index_topk_prefill, which gives a token the same list.  No ragged queries, per-kv-head lists, forced positions,
+    physical-slot output or backward.
+    An e4m3 index cache: k_index_cache torch.float8_e4m3fn of the same shapes (16-byte aligned, row stride a multiple of 16 bytes)
+    with k_index_scale, fp32 (slots, capacity) or (num_pages, page_size), one positive finite scale per token: the key at a
+    position is k_index_scale[..] * float(k_index_cache[..]), q_index stays 16-bit, and L = scale * sum_j weights * relu(q . k8)
+    (index_logits8_kernel, include/fa_index_topk8.h; the bytes are expanded exactly, the one new rounding is the multiply by the
+    scale).  kvcache_index_append_fp8 fills that cache.  A 16-bit cache with a scale, or an e4m3 cache without one, is refused.
+    Cost of that route: tools/index_topk8_bench.py, profiles/index_topk8.jsonl, DESIGN.md section 4.37.
+    One decode step of sparse attention is three calls:
         flash_attn_with_kvcache(q, kv_cache, v_cache, k=k_new, v=v_new, cache_seqlens=lens, ...)   # the append (and k_index_cache[...] = its new rows)
         idx = kvcache_index_topk(q_index, k_index_cache, weights, lens + 1, 2048, page_table=table)
         out = flash_attn_with_kvcache_topk(q, kv_cache, v_cache, idx, qv=qv, cache_seqlens=lens + 1, page_table=table)
@@ -659,14 +666,40 @@ def kvcache_index_topk(q_index, k_index_cache, weights, cache_seqlens, topk, *, 
         indices = torch.empty((b, s_q, 1, topk), dtype=torch.int32, device=q_index.device)
     if logits is None:
         logits = torch.empty((b, s_q, capacity), dtype=torch.float32, device=q_index.device)
+    fp8 = k_index_cache.dtype == torch.float8_e4m3fn
+    if fp8 and k_index_scale is None:
+        raise ValueError("an e4m3 k_index_cache needs k_index_scale, its fp32 scale per token")
+    if not fp8 and k_index_scale is not None:
+        raise ValueError("k_index_scale goes with an e4m3 k_index_cache; a 16-bit k_index_cache has no scale")
     if not q_index.is_cuda:
-        ref = index_topk_ref(q_index, k_index_cache, weights, cache_seqlens, topk, cache_batch_idx=cache_batch_idx, page_table=page_table,
+        keys = k_index_cache.float() * k_index_scale[..., None] if fp8 else k_index_cache  # (the rule only upcasts)
+        ref = index_topk_ref(q_index, keys, weights, cache_seqlens, topk, cache_batch_idx=cache_batch_idx, page_table=page_table,
                              causal=causal)
         indices[..., :topk].copy_(ref.indices), logits[..., :capacity].copy_(ref.logits.float())
+    elif fp8:
+        torch.ops.flash_attn_3.kvcache_index_topk_fp8(q_index, k_index_cache, k_index_scale, weights, cache_seqlens, topk, cache_batch_idx,
+                                                      page_table, causal, indices, logits)
     else:
         torch.ops.flash_attn_3.kvcache_index_topk(q_index, k_index_cache, weights, cache_seqlens, topk, cache_batch_idx, page_table,
                                                   causal, indices, logits)
     return (indices, logits) if return_logits else indices
+
+
+def kvcache_index_append_fp8(k_index_cache, k_index_scale, k_index_new, cache_seqlens, *, cu_seqlens_k_new=None, max_seqlen_k_new=None,
+                             cache_batch_idx=None, page_table=None):
+    """The write half of the e4m3 index-key cache kvcache_index_topk(k_index_scale=) reads: the fp16 / bf16 rows k_index_new --
+    (batch, seqlen_new, index_dim), or (total_new, index_dim) with cu_seqlens_k_new -- are quantised in place at
+    cache_seqlens[b] + i, through cache_batch_idx or page_table (any page size); rows past the capacity are dropped.  Not in the
+    reference.  include/fa_index_topk8.h pins the format and the rule.  k_index_cache: torch.float8_e4m3fn (slots, capacity,
+    index_dim 64 or 128) or pages (num_pages, page_size, index_dim); k_index_scale: fp32, its leading two dimensions.  Per row:
+    scale = 2^e, e the smallest integer with max|x| * 2^-e <= 448 (clamped to [-126, 127]; an all-zero row: scale 1), the bytes
+    x / scale rounded to nearest even -- exact scaling, always in range.  A row with a non-finite value leaves its own bytes and
+    scale unspecified.  Any rotary embedding is the caller's (layers.rotary) before this call.  One launch
+    (index_append8_kernel), no host sync, HIP-graph capturable.  Returns the new fill levels min(cache_seqlens + new rows,
+    capacity), int32 (batch,) on the device; cache_seqlens itself is not modified.  max_seqlen_k_new is accepted for the signature
+    of kvcache_append_fp8 and not needed: the launch does not depend on it."""
+    return torch.ops.flash_attn_3.kvcache_index_append_fp8(k_index_cache, k_index_scale, k_index_new, cache_seqlens, cu_seqlens_k_new,
+                                                           cache_batch_idx, page_table)
 
 
 INDEX_PREFILL_BLOCK = 8  # FA_INDEX_PREFILL_BLOCK: the tokens of one workgroup's block
@@ -689,7 +722,8 @@ def kvcache_index_topk_prefill(q_index, k_index_cache, weights, cache_seqlens, t
     Returns indices: int32 (batch, seqlen_q, 1, width >= topk), [b, i, 0, :K] the chosen logical positions ASCENDING, [K:topk) = -1;
     a fresh tensor or the buffer given.  return_logits (only where one round holds every row, else ValueError): also a view
     (batch, seqlen_q, width) of the workspace, of which [b, i, :n(b, i)] holds L and the rest is NOT written.  CPU tensors take
-    index_topk_prefill_ref.  No e4m3 index cache, ragged queries, per-kv-head lists, forced positions or backward.
+    index_topk_prefill_ref.  No e4m3 index cache here (refused by message: kvcache_index_topk(k_index_scale=) reads one, 16 tokens
+    a call), ragged queries, per-kv-head lists, forced positions or backward.
     Cost, measured on MI355X: tools/index_prefill_bench.py, profiles/index_prefill.jsonl, DESIGN.md section 4.35."""
     b, s_q = q_index.shape[0], q_index.shape[1]
     capacity = page_table.shape[1] * k_index_cache.shape[1] if page_table is not None else k_index_cache.shape[1]
