@@ -1,4 +1,4 @@
-"""Build and loading of the native code: libfa_fwd_gfx950.so (the C-ABI of include/fa_fwd.h, fa_bwd.h, fa_rotary.h, fa_norm.h, fa_xent.h, fa_act.h, fa_gemm_act.h, fa_dropout_norm.h, fa_sample.h, fa_spec_sample.h, fa_tree_sample.h, fa_block_select.h, fa_block_pattern.h, fa_index_topk.h, fa_index_prefill.h and fa_index_topk8.h) and
+"""Build and loading of the native code: libfa_fwd_gfx950.so (the C-ABI of include/fa_fwd.h, fa_bwd.h, fa_rotary.h, fa_norm.h, fa_xent.h, fa_act.h, fa_gemm_act.h, fa_dropout_norm.h, fa_sample.h, fa_spec_sample.h, fa_tree_sample.h, fa_block_select.h, fa_block_pattern.h, fa_index_topk.h, fa_index_prefill.h, fa_index_topk8.h and fa_index_prefill8.h) and
 the compiled host module flash_attn_2_cuda_C (csrc/torch_binding.cpp), which is the only host path of both operator
 surfaces.  Python launches nothing through ctypes: the struct mirrors below serve the ABI tests, `bench.py --variant`
 and the developer tools, which call the C-ABI directly.
@@ -157,6 +157,10 @@ FA_INDEX_PREFILL_BLOCK = 8
 INDEX_TOPK8_SYMBOLS = ("fa_index_topk8", "fa_index_topk8_validate", "fa_index_topk8_workspace_size", "fa_index_topk8_plan_name",
                        "fa_index_topk8_params_size", "fa_index_append8", "fa_index_append8_validate", "fa_index_append8_plan_name",
                        "fa_index_append8_params_size")
+# every symbol include/fa_index_prefill8.h declares (csrc/fa_index_prefill8.hip)
+INDEX_PREFILL8_SYMBOLS = ("fa_index_prefill8", "fa_index_prefill8_validate", "fa_index_prefill8_workspace_size",
+                          "fa_index_prefill8_plan_name", "fa_index_prefill8_params_size")
+FA_INDEX_PREFILL8_TILE = 128
 
 
 class FaFwdParams(ctypes.Structure):
@@ -599,6 +603,23 @@ class FaIndexTopk8Params(ctypes.Structure):
     )
 
 
+class FaIndexPrefill8Params(ctypes.Structure):
+    """Field-for-field mirror of `struct fa_index_prefill8_params` (include/fa_index_prefill8.h)."""
+
+    _fields_ = (
+        [("abi_version", ctypes.c_uint32), ("struct_size", ctypes.c_uint32)]
+        + [(n, ctypes.c_void_p) for n in ("q_index", "k_index_cache", "weights", "cache_seqlens", "cache_batch_idx", "page_table",
+                                          "cu_seqlens_q", "cache_leftpad", "workspace", "indices", "k_index_scale")]
+        + [(f"q_{s}_stride", ctypes.c_int64) for s in ("batch", "row", "head")]
+        + [(f"cache_{s}_stride", ctypes.c_int64) for s in ("batch", "row")]
+        + [(f"w_{s}_stride", ctypes.c_int64) for s in ("batch", "row")]
+        + [(n, ctypes.c_int64) for n in ("page_table_batch_stride", "workspace_row_stride", "idx_batch_stride", "idx_row_stride",
+                                         "workspace_rows", "scale_batch_stride")]
+        + [(n, ctypes.c_int32) for n in ("b", "s_q", "h_i", "d_i", "capacity", "page_size", "topk", "list_width", "workspace_width",
+                                         "is_causal", "dtype", "cache_dtype")]
+    )
+
+
 class FaIndexAppend8Params(ctypes.Structure):
     """Field-for-field mirror of `struct fa_index_append8_params` (include/fa_index_topk8.h)."""
 
@@ -762,7 +783,8 @@ class FaSinkGradParams(ctypes.Structure):
 
 
 HASH_PATH = os.path.join(_HERE, "libfa_fwd_gfx950.srchash")
-NO_PACKED_FP32_UNITS = ("fa_fwd_topk_kv_api.hip", "fa_index_topk.hip", "fa_index_prefill.hip", "fa_index_topk8.hip")
+NO_PACKED_FP32_UNITS = ("fa_fwd_topk_kv_api.hip", "fa_index_topk.hip", "fa_index_prefill.hip", "fa_index_topk8.hip",
+                        "fa_index_prefill8.hip")
 # units built as objects of their own with the library's plain flags (fa_fwd_topk_kv8_api.hip: qv8_fwd_kernel's options, whose
 # bits its result must equal)
 OWN_OBJECT_UNITS = ("fa_fwd_topk_kv8_api.hip",)
@@ -979,6 +1001,12 @@ _PROTOTYPES = {
         ("fa_index_append8_validate", [_P(FaIndexAppend8Params)], _INT),
         ("fa_index_append8_plan_name", [_P(FaIndexAppend8Params)], _STR),
     ),
+    "fa_index_prefill8.h": (
+        ("fa_index_prefill8", [_P(FaIndexPrefill8Params), _VOID], _INT, "fa_index_prefill8_params_size", FaIndexPrefill8Params),
+        ("fa_index_prefill8_validate", [_P(FaIndexPrefill8Params)], _INT),
+        ("fa_index_prefill8_workspace_size", [_P(FaIndexPrefill8Params), _I32], _I64),
+        ("fa_index_prefill8_plan_name", [_P(FaIndexPrefill8Params)], _STR),
+    ),
 }
 
 _lib = None
@@ -1148,6 +1176,10 @@ def new_index_prefill_params():
 
 def new_index_topk8_params():
     return _new(FaIndexTopk8Params, dtype=FA_DTYPE_BF16, cache_dtype=FA_DTYPE_FP8_E4M3, topk=1, is_causal=1)
+
+
+def new_index_prefill8_params():
+    return _new(FaIndexPrefill8Params, dtype=FA_DTYPE_BF16, cache_dtype=FA_DTYPE_FP8_E4M3, topk=1, is_causal=1)
 
 
 def new_index_append8_params():

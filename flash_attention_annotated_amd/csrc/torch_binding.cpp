@@ -33,6 +33,7 @@
 #include "fa_block_pattern.h"
 #include "fa_index_topk.h"
 #include "fa_index_prefill.h"
+#include "fa_index_prefill8.h"
 #include "fa_index_topk8.h"
 #include "fa_act.h"
 #include "fa_gemm_act.h"
@@ -3298,20 +3299,28 @@ std::string index_topk_impl(const Tensor &q_index, const Tensor &k_index_cache, 
 
 // ---- its prefill-sized form (hopper_interface.kvcache_index_topk_prefill; include/fa_index_prefill.h): any seqlen_q; the logits
 // are a workspace (rows, width >= capacity) the call walks in rounds of whole token blocks.  Capturable like the entry above.
-std::string index_prefill_impl(const Tensor &q_index, const Tensor &k_index_cache, const Tensor &weights, const Tensor &cache_seqlens,
-                               int64_t topk, const OptTensor &cache_batch_idx, const OptTensor &page_table, bool causal,
-                               const Tensor &indices, const Tensor &workspace, bool plan) {
-    const int64_t capacity = index_check_inputs(q_index, k_index_cache, weights, cache_seqlens, topk, cache_batch_idx, page_table, indices, 0);
-    TORCH_CHECK(workspace.scalar_type() == at::kFloat && workspace.is_cuda() && workspace.device() == q_index.device() && workspace.dim() == 2 &&
+// the workspace check and the fields fa_index_prefill_params and fa_index_prefill8_params name alike
+template <class Params>
+void index_prefill_fill(Params &p, const Tensor &qc, const Tensor &k_index_cache, const Tensor &weights, const Tensor &cache_seqlens,
+                        int64_t topk, const OptTensor &cache_batch_idx, const OptTensor &page_table, bool causal, const Tensor &indices,
+                        const Tensor &workspace, int64_t capacity) {
+    TORCH_CHECK(workspace.scalar_type() == at::kFloat && workspace.is_cuda() && workspace.device() == qc.device() && workspace.dim() == 2 &&
                     workspace.size(0) >= FA_INDEX_PREFILL_BLOCK && workspace.size(1) >= capacity && workspace.stride(1) == 1 &&
                     workspace.stride(0) >= workspace.size(1),
                 "workspace must be fp32 (rows >= ", FA_INDEX_PREFILL_BLOCK, ", width >= capacity) with contiguous last dimension");
-    const Tensor qc = aligned_or_copy(q_index);
-    auto p = new_params<fa_index_prefill_params>();
     index_fill_params(p, qc, k_index_cache, weights, cache_seqlens, topk, cache_batch_idx, page_table, causal, indices, capacity);
     p.workspace = static_cast<float *>(workspace.data_ptr());
     p.workspace_row_stride = workspace.stride(0); p.workspace_rows = workspace.size(0);
     p.workspace_width = (int32_t)std::min<int64_t>(workspace.size(1), 0x7fffffff);
+}
+
+std::string index_prefill_impl(const Tensor &q_index, const Tensor &k_index_cache, const Tensor &weights, const Tensor &cache_seqlens,
+                               int64_t topk, const OptTensor &cache_batch_idx, const OptTensor &page_table, bool causal,
+                               const Tensor &indices, const Tensor &workspace, bool plan) {
+    const int64_t capacity = index_check_inputs(q_index, k_index_cache, weights, cache_seqlens, topk, cache_batch_idx, page_table, indices, 0);
+    const Tensor qc = aligned_or_copy(q_index);
+    auto p = new_params<fa_index_prefill_params>();
+    index_prefill_fill(p, qc, k_index_cache, weights, cache_seqlens, topk, cache_batch_idx, page_table, causal, indices, workspace, capacity);
     if (plan) {
         const char *name = fa_index_prefill_plan_name(&p);
         TORCH_CHECK(name, "fa_index_prefill refused (", fa_index_prefill_validate(&p), "): ", fa_strerror(fa_index_prefill_validate(&p)));
@@ -3361,6 +3370,30 @@ std::string index_topk8_impl(const Tensor &q_index, const Tensor &k_index_cache,
     c10::hip::HIPGuardMasqueradingAsCUDA device_guard(q_index.device());
     const int st = fa_index_topk8(&p, current_stream(q_index));
     TORCH_CHECK(st == 0, "fa_index_topk8 failed (", st, "): ", fa_strerror(st));
+    return {};
+}
+
+// its prefill-sized form (hopper_interface.kvcache_index_topk_prefill(k_index_scale=); include/fa_index_prefill8.h)
+std::string index_prefill8_impl(const Tensor &q_index, const Tensor &k_index_cache, const Tensor &k_index_scale, const Tensor &weights,
+                                const Tensor &cache_seqlens, int64_t topk, const OptTensor &cache_batch_idx, const OptTensor &page_table,
+                                bool causal, const Tensor &indices, const Tensor &workspace, bool plan) {
+    const int64_t capacity = index_check_inputs(q_index, k_index_cache, weights, cache_seqlens, topk, cache_batch_idx, page_table, indices, 0,
+                                                true);
+    index_check_scale(k_index_scale, k_index_cache);
+    const Tensor qc = aligned_or_copy(q_index);
+    auto p = new_params<fa_index_prefill8_params>();
+    index_prefill_fill(p, qc, k_index_cache, weights, cache_seqlens, topk, cache_batch_idx, page_table, causal, indices, workspace, capacity);
+    p.cache_dtype = FA_DTYPE_FP8_E4M3;
+    p.k_index_scale = static_cast<const float *>(k_index_scale.data_ptr());
+    p.scale_batch_stride = k_index_scale.stride(0);
+    if (plan) {
+        const char *name = fa_index_prefill8_plan_name(&p);
+        TORCH_CHECK(name, "fa_index_prefill8 refused (", fa_index_prefill8_validate(&p), "): ", fa_strerror(fa_index_prefill8_validate(&p)));
+        return name;
+    }
+    c10::hip::HIPGuardMasqueradingAsCUDA device_guard(q_index.device());
+    const int st = fa_index_prefill8(&p, current_stream(q_index));
+    TORCH_CHECK(st == 0, "fa_index_prefill8 failed (", st, "): ", fa_strerror(st));
     return {};
 }
 
@@ -3791,6 +3824,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
                    : "lightning indexer over an e4m3 index-key cache with one scale per token; writes indices and logits",
               py::arg("q_index"), py::arg("k_index_cache"), py::arg("k_index_scale"), py::arg("weights"), py::arg("cache_seqlens"),
               py::arg("topk"), py::arg("cache_batch_idx"), py::arg("page_table"), py::arg("causal"), py::arg("indices"), py::arg("logits"));
+        m.def(plan ? "kvcache_index_topk_prefill_fp8_plan" : "kvcache_index_topk_prefill_fp8",
+              [plan](const Tensor &q_index, const Tensor &k_index_cache, const Tensor &k_index_scale, const Tensor &weights,
+                     const Tensor &cache_seqlens, int64_t topk, const OptTensor &cache_batch_idx, const OptTensor &page_table, bool causal,
+                     const Tensor &indices, const Tensor &workspace) {
+                  return index_prefill8_impl(q_index, k_index_cache, k_index_scale, weights, cache_seqlens, topk, cache_batch_idx, page_table,
+                                             causal, indices, workspace, plan);
+              },
+              plan ? "the form kvcache_index_topk_prefill_fp8 takes with these arguments, as text; nothing is launched"
+                   : "lightning indexer of a prompt over an e4m3 index-key cache with one scale per token; writes indices",
+              py::arg("q_index"), py::arg("k_index_cache"), py::arg("k_index_scale"), py::arg("weights"), py::arg("cache_seqlens"),
+              py::arg("topk"), py::arg("cache_batch_idx"), py::arg("page_table"), py::arg("causal"), py::arg("indices"), py::arg("workspace"));
     }
     m.def("kvcache_index_append_fp8", &kvcache_index_append_fp8,
           "quantising in-place append of 16-bit rows to an e4m3 index-key cache and its per-token scales; returns the new fill levels",

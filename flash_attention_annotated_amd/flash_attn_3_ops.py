@@ -86,11 +86,15 @@ INDEX_TOPK_FP8_SCHEMA = (
 INDEX_APPEND_FP8_SCHEMA = (
     "kvcache_index_append_fp8(Tensor(a!) k_index_cache, Tensor(b!) k_index_scale, Tensor k_index_new, Tensor cache_seqlens, "
     "Tensor? cu_seqlens_k_new = None, Tensor? cache_batch_idx = None, Tensor? page_table = None) -> Tensor")
+# ... and the prefill-sized form over that cache (include/fa_index_prefill8.h)
+INDEX_PREFILL_FP8_SCHEMA = (
+    "kvcache_index_topk_prefill_fp8(Tensor q_index, Tensor k_index_cache, Tensor k_index_scale, Tensor weights, Tensor cache_seqlens, "
+    "int topk, Tensor? cache_batch_idx, Tensor? page_table, bool causal, Tensor(a!) indices, Tensor(b!) workspace) -> ()")
 
 _ops = torch.library.Library("flash_attn_3", "DEF")
 for _schema in (FWD_SCHEMA, BWD_SCHEMA, COMBINE_SCHEMA, METADATA_SCHEMA, APPEND_FP8_SCHEMA, KVCACHE_SPARSE_SCHEMA, KVCACHE_TREE_SCHEMA,
                 KVCACHE_TOPK_SCHEMA, BLOCK_SUMMARY_SCHEMA, SELECT_BLOCKS_SCHEMA, INDEX_TOPK_SCHEMA, INDEX_PREFILL_SCHEMA,
-                INDEX_TOPK_FP8_SCHEMA, INDEX_APPEND_FP8_SCHEMA):
+                INDEX_TOPK_FP8_SCHEMA, INDEX_APPEND_FP8_SCHEMA, INDEX_PREFILL_FP8_SCHEMA):
     _ops.define(_schema)
 
 
@@ -224,6 +228,14 @@ def _kvcache_index_topk_fp8(q_index, k_index_cache, k_index_scale, weights, cach
                                           page_table, causal, indices, logits)
 
 
+def _kvcache_index_topk_prefill_fp8(q_index, k_index_cache, k_index_scale, weights, cache_seqlens, topk, cache_batch_idx, page_table,
+                                    causal, indices, workspace):
+    """The binding's kvcache_index_topk_prefill_fp8 (fa_index_prefill8): a logits launch over byte tiles and a selection launch per
+    round, no host sync."""
+    _lib.binding().kvcache_index_topk_prefill_fp8(q_index, k_index_cache, k_index_scale, weights, cache_seqlens, topk, cache_batch_idx,
+                                                  page_table, causal, indices, workspace)
+
+
 def _kvcache_index_append_fp8(k_index_cache, k_index_scale, k_index_new, cache_seqlens, cu_seqlens_k_new=None, cache_batch_idx=None,
                               page_table=None):
     """The binding's kvcache_index_append_fp8 (fa_index_append8): one launch, returns the new fill levels."""
@@ -289,5 +301,7 @@ _ops.impl("kvcache_index_topk_prefill", _kvcache_index_topk_prefill, "CUDA")
 _ops.impl("kvcache_index_topk_prefill", _nothing, "Meta")
 _ops.impl("kvcache_index_topk_fp8", _kvcache_index_topk_fp8, "CUDA")
 _ops.impl("kvcache_index_topk_fp8", _nothing, "Meta")
+_ops.impl("kvcache_index_topk_prefill_fp8", _kvcache_index_topk_prefill_fp8, "CUDA")
+_ops.impl("kvcache_index_topk_prefill_fp8", _nothing, "Meta")
 _ops.impl("kvcache_index_append_fp8", _kvcache_index_append_fp8, "CUDA")
 _ops.impl("kvcache_index_append_fp8", _kvcache_index_append_fp8_meta, "Meta")

@@ -707,7 +707,7 @@ INDEX_PREFILL_WORKSPACE_CAP = 256 << 20  # bytes of the workspace kvcache_index_
 
 
 def kvcache_index_topk_prefill(q_index, k_index_cache, weights, cache_seqlens, topk, *, cache_batch_idx=None, page_table=None,
-                               causal=True, indices=None, workspace=None, return_logits=False):
+                               causal=True, indices=None, workspace=None, return_logits=False, k_index_scale=None):
     """The lightning indexer for a prompt or a chunk of a chunked prefill: kvcache_index_topk's rule, word for word, for ANY
     seqlen_q >= 1 (batch * seqlen_q < 2^31) -- a token's logits are bit-equal to what kvcache_index_topk computes for it, so a
     position's list does not depend on which call produced it; seqlen_q <= 16 is accepted and gives that call's result.  Not in the
@@ -722,16 +722,27 @@ def kvcache_index_topk_prefill(q_index, k_index_cache, weights, cache_seqlens, t
     Returns indices: int32 (batch, seqlen_q, 1, width >= topk), [b, i, 0, :K] the chosen logical positions ASCENDING, [K:topk) = -1;
     a fresh tensor or the buffer given.  return_logits (only where one round holds every row, else ValueError): also a view
     (batch, seqlen_q, width) of the workspace, of which [b, i, :n(b, i)] holds L and the rest is NOT written.  CPU tensors take
-    index_topk_prefill_ref.  No e4m3 index cache here (refused by message: kvcache_index_topk(k_index_scale=) reads one, 16 tokens
-    a call), ragged queries, per-kv-head lists, forced positions or backward.
-    Cost, measured on MI355X: tools/index_prefill_bench.py, profiles/index_prefill.jsonl, DESIGN.md section 4.35."""
+    index_topk_prefill_ref.  No ragged queries, per-kv-head lists, forced positions or backward.
+    An e4m3 index cache: k_index_cache torch.float8_e4m3fn with k_index_scale, the format include/fa_index_topk8.h defines and
+    kvcache_index_append_fp8 fills, routed as kvcache_index_topk routes it (a 16-bit cache with a scale, or an e4m3 cache without
+    one, is refused).  Everything above holds as stated, and a token's logits are bit-equal to what
+    kvcache_index_topk(k_index_scale=) computes for it (index_logits_prefill8_kernel, include/fa_index_prefill8.h: byte tiles of
+    128 key rows through LDS with their scales, expanded exactly at the matrix operand).
+    Cost, measured on MI355X: tools/index_prefill_bench.py, profiles/index_prefill.jsonl; of the e4m3
+    route tools/index_prefill8_bench.py, profiles/index_prefill8.jsonl, DESIGN.md section 4.38."""
     b, s_q = q_index.shape[0], q_index.shape[1]
     capacity = page_table.shape[1] * k_index_cache.shape[1] if page_table is not None else k_index_cache.shape[1]
     if indices is None:
         indices = torch.empty((b, s_q, 1, topk), dtype=torch.int32, device=q_index.device)
     padded = -(-s_q // INDEX_PREFILL_BLOCK) * INDEX_PREFILL_BLOCK  # the rows of a batch entry in a one-round workspace
+    fp8 = k_index_cache.dtype == torch.float8_e4m3fn
+    if fp8 and k_index_scale is None:
+        raise ValueError("an e4m3 k_index_cache needs k_index_scale, its fp32 scale per token")
+    if not fp8 and k_index_scale is not None:
+        raise ValueError("k_index_scale goes with an e4m3 k_index_cache; a 16-bit k_index_cache has no scale")
     if not q_index.is_cuda:
-        ref = index_topk_prefill_ref(q_index, k_index_cache, weights, cache_seqlens, topk, cache_batch_idx=cache_batch_idx,
+        keys = k_index_cache.float() * k_index_scale[..., None] if fp8 else k_index_cache  # (the rule only upcasts)
+        ref = index_topk_prefill_ref(q_index, keys, weights, cache_seqlens, topk, cache_batch_idx=cache_batch_idx,
                                      page_table=page_table, causal=causal)
         indices[..., :topk].copy_(ref.indices)
         return (indices, ref.logits.float()) if return_logits else indices
@@ -740,8 +751,12 @@ def kvcache_index_topk_prefill(q_index, k_index_cache, weights, cache_seqlens, t
         workspace = torch.empty((max(min(b * padded, fit), INDEX_PREFILL_BLOCK), capacity), dtype=torch.float32, device=q_index.device)
     if return_logits and workspace.shape[0] < b * padded:
         raise ValueError(f"return_logits needs a workspace that holds every row in one round: {b * padded} rows, got {workspace.shape[0]}")
-    torch.ops.flash_attn_3.kvcache_index_topk_prefill(q_index, k_index_cache, weights, cache_seqlens, topk, cache_batch_idx, page_table,
-                                                      causal, indices, workspace)
+    if fp8:
+        torch.ops.flash_attn_3.kvcache_index_topk_prefill_fp8(q_index, k_index_cache, k_index_scale, weights, cache_seqlens, topk,
+                                                              cache_batch_idx, page_table, causal, indices, workspace)
+    else:
+        torch.ops.flash_attn_3.kvcache_index_topk_prefill(q_index, k_index_cache, weights, cache_seqlens, topk, cache_batch_idx,
+                                                          page_table, causal, indices, workspace)
     if not return_logits:
         return indices
     return indices, workspace.as_strided((b, s_q, workspace.shape[1]), (padded * workspace.stride(0), workspace.stride(0), 1))
